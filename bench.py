@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: batched MCTS self-play on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload at N=1: 4096 concurrent games, 400 sims/move, 12x128 net (random-init seed 1, .npy layout), bf16 — the
 per-GPU shard of BASELINE.json configs[2] (32768 games over 8 GPUs), i.e. configs[1]'s game count at the sims/move
@@ -16,8 +16,15 @@ finished games drained in the timed region / its wall time.  The games are first
 (a fresh start has every game at ply 0), so both figures are steady-state figures.
 
 Prints ONE JSON line on rank 0, with the dominant kernel's roofline (MFMA; HIP events on the engine's stream,
-sampled over the timed region) and a CPU baseline: the reference's architecture (one host thread per game,
-double-buffered batches) on this box's cores with the GPU tower as its evaluator.
+sampled over the timed region).  A plain run does only that: set-up, warm-up, the timed steps, the line.  `--full`
+adds what takes runs of its own: the legs beside the headline (one batch, 16384 games, the evaluation cache, f16, the
+other BASELINE configs), the vendor GEMM ceiling, and a CPU baseline: the reference's architecture (one host thread per
+game, double-buffered batches) on this box's cores with the GPU tower as its evaluator.
+
+`--dump-outputs DIR` writes what the timed path computed, as of the end of its last step, to DIR/<name>.npy (float32 /
+float64; rank 0's shard): the region's counters, every slot's game state and root position, and every root's edges
+(move, prior, visits, total score).  The inputs are seeded, so two builds run with the same arguments can be compared
+array for array.
 
 `--gpus N` without a launcher (no WORLD_SIZE in the environment) starts the N ranks itself, one child process per
 GPU, before anything touches the GPU in this process; under torchrun it is one of the ranks.
@@ -169,6 +176,56 @@ def measure(sp, args, steps, warmup, group=None):
         group.barrier()
     st1 = sp.stats()
     return {k: st1[k] - st0[k] for k in st1}, finished, t1 - t0, sp.timing(), per_step[warmup:]
+
+
+DUMP_MAX_BYTES = 60 << 20   # --dump-outputs: all arrays together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(sp, counters, out_dir):
+    """--dump-outputs: what the timed path computed, as of the end of its last step (the engines synced), as float32 /
+    float64 arrays in out_dir/<name>.npy.  Slots are in SelfPlay order (engine after engine).  Every array has a row per
+    slot or per root edge, so none is empty (the game lines a step drains are not dumped: in the steady state most
+    finished games started from a loaded position and are not written, and a step may drain none).  An array larger
+    than its share of DUMP_MAX_BYTES keeps a fixed, seeded sample of its rows (root_edges at 16384 games and more)."""
+    import numpy as np
+    from ataxxzero_amd import link
+    states, words, edges = [], [], []
+    slot = 0
+    for e in sp.engines:
+        for g in range(e.G):
+            s = e.game_state(g)
+            states.append(s.as_tuple())
+            if s.n_nodes == 0:
+                words.append((0, 0))
+            else:
+                boards, info, ed, moves = e.tree(g)
+                words.append((int(boards[0, 0]), int(boards[0, 1])))
+                first, n = int(info[0, 0]), int(info[0, 1]) & 0xFFFF   # the root's edge range
+                r = np.ascontiguousarray(ed[first:first + n])
+                edges.append(np.stack([np.full(n, slot, np.float64), moves[first:first + n].astype(np.float64),
+                                       r[:, 0].copy().view(np.float32).astype(np.float64), r[:, 1].astype(np.float64),
+                                       r[:, 2].copy().view(np.float32).astype(np.float64)], axis=1))
+            slot += 1
+    words = np.asarray(words, dtype=np.uint64)
+    sq = np.arange(49, dtype=np.uint64)
+    cells = ((words[:, :1] >> sq) & np.uint64(1)) + 2 * ((words[:, 1:] >> sq) & np.uint64(1))   # 0 empty, 1 x, 2 o
+    out = {
+        # the timed region's counters (link.STAT_NAMES order)
+        "counters": np.array([counters.get(k, 0) for k in link.STAT_NAMES], dtype=np.float64),
+        # per slot: link.GameState's fields
+        "game_state": np.array(states, dtype=np.float64).reshape(-1, len(link.GameState._fields_)),
+        # per slot: the root position, 49 cells (square = bit index) then the side to move
+        "root_position": np.concatenate([cells, (words[:, :1] >> np.uint64(63))], axis=1).astype(np.float32),
+        # per root edge: slot, move (from | to << 8), prior, visits, total score
+        "root_edges": np.concatenate(edges),
+    }
+    share = DUMP_MAX_BYTES // len(out)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        if a.nbytes > share:
+            keep = share // (a.nbytes // len(a))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 SNAPSHOT = os.path.join("profiles", "round2_steady_state_positions.npz")
@@ -428,12 +485,17 @@ def main():
                     help="AZH_FLAG_EVAL_CACHE: positions a game's search has already evaluated are not sent to the net "
                          "again (engine.py's NNEvaluator.cache).  Off in the headline: the C++ generator evaluates every "
                          "new node")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the legs beside the headline (--legs), the vendor GEMM "
+                         "ceiling and the CPU baseline (a plain run: set-up, warm-up, the timed steps, the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed (as of its last step) to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gemm-ceiling", action="store_true",
                     help="skip the vendor-library bf16 GEMM measured beside the roofline (context for roofline.frac)")
     ap.add_argument("--no-target-leg", action="store_true", help="skip the 16384-game leg reported beside the headline")
     ap.add_argument("--legs", default="all",
-                    help="comma-separated legs to measure beside the headline (default all): one_batch, target_10k_games, "
+                    help="with --full, comma-separated legs to measure beside the headline (default all): one_batch, target_10k_games, "
                          "target_10k_games_two_half_batches, "
                          "with_eval_cache, target_10k_games_with_eval_cache, with_f16, config1_random_play, config2, config4, "
                          "config5_arena, config5_arena_balanced")
@@ -488,6 +550,8 @@ def main():
                            select_budget=args.select_budget, flags=link.FLAG_EVAL_CACHE if args.eval_cache else 0)
     ages = spread(sp, args, distrib.shard_seed(selfplay.DEFAULT_SEED, group.rank))
     d, finished, dt, tm, finished_per_step = measure(sp, args, args.steps, args.warmup, group)
+    if args.dump_outputs and group.rank == 0:
+        dump_outputs(sp, d, args.dump_outputs)
     steps_total, t_max, rate = distrib.aggregate(group, d["steps"], dt)
     evals_total = group.reduce(d["nn_evals"], "sum")
     plies_total = group.reduce(d["plies"], "sum")
@@ -577,7 +641,7 @@ def main():
         }
         sp.close()
         def want(leg):
-            return group.world == 1 and not args.no_target_leg and (args.legs == "all" or leg in args.legs.split(","))
+            return group.world == 1 and args.full and not args.no_target_leg and (args.legs == "all" or leg in args.legs.split(","))
 
         if want("one_batch") and args.streams != 1:
             # the headline workload as ONE batch: the tower launch and the tree launch alone on the chip, i.e. the
@@ -641,9 +705,9 @@ def main():
                     out["config5_arena_two_launches"] = config5_leg(games=og or 1000)
                 finally:
                     del os.environ["AZH_ARENA_PAIR"]
-        if group.world == 1 and not args.no_gemm_ceiling:
+        if group.world == 1 and args.full and not args.no_gemm_ceiling:
             out["roofline"]["vendor_gemm_on_this_box"] = vendor_gemm_ceiling()
-        if group.world == 1 and not args.no_cpu_baseline:
+        if group.world == 1 and args.full and not args.no_cpu_baseline:
             net = link.Net(conv, bn)
             out["cpu_baseline"] = cpu_baseline(net, args.visits, args.dtype, args.cpu_seconds)
             net.close()

@@ -361,10 +361,10 @@ def test_generator_with_a_game_count_writes_exactly_those_games_and_exits(tmp_pa
 
 
 def test_bench_contract_line():
-    """bench.py prints ONE JSON line with the driver's keys, the roofline and the cpu_baseline objects."""
+    """bench.py --full prints ONE JSON line with the driver's keys, the roofline and the cpu_baseline objects."""
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--games", "96", "--visits", "8", "--blocks", "1",
                           "--steps", "30", "--warmup", "10", "--iters-per-step", "10", "--phase-fill", "30",
-                          "--cpu-seconds", "1.5", "--no-target-leg"], cwd=ROOT, capture_output=True, timeout=400)
+                          "--cpu-seconds", "1.5", "--no-target-leg", "--full"], cwd=ROOT, capture_output=True, timeout=400)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     lines = [l for l in res.stdout.decode().splitlines() if l.strip()]
     assert len(lines) == 1
@@ -399,7 +399,7 @@ def test_bench_line_carries_every_baseline_config_with_one_definition_of_the_tow
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--games", "96", "--visits", "8", "--blocks", "1",
                           "--steps", "4", "--warmup", "1", "--iters-per-step", "10", "--phase-fill", "20", "--no-cpu-baseline",
                           "--no-gemm-ceiling", "--legs", "one_batch,with_f16,config2,config4,config5_arena,config5_arena_balanced",
-                          "--other-configs-games", "64", "--arena-ab"], cwd=ROOT, capture_output=True, timeout=900)
+                          "--other-configs-games", "64", "--arena-ab", "--full"], cwd=ROOT, capture_output=True, timeout=900)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     d = json.loads([l for l in res.stdout.decode().splitlines() if l.strip()][-1])
     assert d["games_per_s_from_plies"] is None   # (only quoted for the 400-sim workload the snapshot was drawn from)
@@ -429,6 +429,44 @@ def test_bench_line_carries_every_baseline_config_with_one_definition_of_the_tow
         assert c["per_launch_frac"] > 0 and abs(c["per_launch_frac"] - c["per_launch_tflops"] / 2500.0) < 1e-12
         assert c["tower_ms_per_launch"] < c["ms_per_iteration"] * 1.05
         assert "steps_per_s_while_ge512_live" not in c      # (64 games here: the phase does not exist)
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full): the headline line without the legs, the CPU baseline or the GEMM ceiling; --steps sets the
+    timed steps; --dump-outputs writes the timed path's outputs, and a second run with the same arguments writes the same
+    arrays bit for bit, none of them empty.  The bench's own set-up (slots loaded with steady-state positions) and short
+    steps: games finish in the region, but none of them is written, so a step drains no game line."""
+    lines = []
+    for run in ("a", "b"):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--games", "96", "--visits", "8", "--blocks", "1",
+                              "--steps", "3", "--warmup", "1", "--iters-per-step", "50", "--phase-fill", "30",
+                              "--dump-outputs", str(tmp_path / run)], cwd=ROOT, capture_output=True, timeout=300)
+        assert res.returncode == 0, res.stderr.decode()[-2000:]
+        out = [l for l in res.stdout.decode().splitlines() if l.strip()]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    d = lines[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert abs(d["ms_per_step"] - 50 * d["ms_per_iteration"]) < 1e-6 * d["ms_per_step"]
+    for k in ("cpu_baseline", "one_batch", "target_10k_games", "with_f16", "config2", "config5_arena"):
+        assert k not in d, k
+    assert "vendor_gemm_on_this_box" not in d["roofline"]
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(os.listdir(str(tmp_path / "b"))) == ["counters.npy", "game_state.npy", "root_edges.npy",
+                                                                 "root_position.npy"]
+    total = 0
+    for name in names:
+        a, b = np.load(str(tmp_path / "a" / name)), np.load(str(tmp_path / "b" / name))
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and a.shape == b.shape, name
+        assert (a.view(np.uint8) == b.view(np.uint8)).all(), name
+        total += a.nbytes
+    assert total <= 64e6
+    counters = np.load(str(tmp_path / "a" / "counters.npy"))
+    assert counters[link.STAT_NAMES.index("steps")] == d["counters"]["steps"] > 0
+    state = np.load(str(tmp_path / "a" / "game_state.npy"))
+    edges = np.load(str(tmp_path / "a" / "root_edges.npy"))
+    assert state.shape == (96, 10) and np.load(str(tmp_path / "a" / "root_position.npy")).shape == (96, 50)
+    assert edges.shape[1] == 5 and edges[:, 3].sum() > 0 and set(edges[:, 0].astype(int)) <= set(range(96))
 
 
 def test_bench_py_two_ranks_on_one_gpu():

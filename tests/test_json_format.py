@@ -6,14 +6,18 @@ nlohmann's format_buffer (plain decimals between 1e-4 and 1e15, d.ddde-XX outsid
 
 * the library itself — nlohmann::json 3.1.1 is installed in this image (/opt/conda/include/json.hpp; third party, not part
   of the reference) and oracle/json_entry_dump.cpp builds and streams the entry with it exactly as the reference's code
-  does: whole lines must be equal byte for byte;
+  does: whole lines must be equal byte for byte (where the header is not installed: equal to the sha256 of the lines it
+  wrote, stored in tests/golden/nlohmann_line_digests.json);
 * Python's `json.dumps(entry, sort_keys=True, separators=(",", ":"))`: the same bytes except for the one double in a
   thousand that Grisu2 writes with 17 digits where 16 suffice (repr always finds the shortest) — compared with those
   doubles normalised, and value for value.
 """
 import ctypes
+import hashlib
 import json
+import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -138,31 +142,16 @@ def test_malformed_records_are_refused():
 # ------------------------------------------------------------------ against the library the reference itself uses
 
 NLOHMANN = "/opt/conda/include/json.hpp"     # nlohmann::json 3.1.1 ships with this image (third party, not the reference)
+# sha256 of every line the library wrote for the record sets below: where the header is not installed the lines are checked
+# against these; where it is, the library's own lines must still give them (rewrite: python -m tests.test_json_format)
+DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nlohmann_line_digests.json")
 
 
-@pytest.fixture(scope="module")
-def entry_dump(tmp_path_factory):
-    """oracle/json_entry_dump.cpp: builds the entry with nlohmann::json exactly as cpp/self_play_client.cpp:512-578 does and
-    streams it as :639-641 does"""
-    import os
-    import subprocess
-    if not os.path.exists(NLOHMANN):
-        pytest.skip("nlohmann json.hpp is not installed here")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path_factory.mktemp("nlohmann") / "json_entry_dump")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + os.path.dirname(NLOHMANN), "-o", exe,
-                           os.path.join(root, "oracle", "json_entry_dump.cpp")])
-
-    def run(records):
-        out = subprocess.run([exe], input=b"".join(np.ascontiguousarray(r, dtype=np.uint32).tobytes() for r in records),
-                             capture_output=True, check=True)
-        return out.stdout.split(b"\n")[:-1]
-    return run
+def digest(line):
+    return hashlib.sha256(line).hexdigest()
 
 
-def test_lines_equal_what_nlohmann_json_itself_writes(entry_dump):
-    """Byte for byte, including the doubles for which Grisu2 — the library's algorithm — does NOT find the shortest
-    digits (json.dumps then differs from the reference, and so did this formatter while it asked std::to_chars)."""
+def random_records():
     rng = np.random.default_rng(2026)
     records, entries = [], []
     for case in range(120):
@@ -171,17 +160,10 @@ def test_lines_equal_what_nlohmann_json_itself_writes(entry_dump):
                                    zero_total_at=0 if case % 11 == 10 else None)
         records.append(rec)
         entries.append(entry)
-    theirs = entry_dump(records)
-    assert len(theirs) == len(records)
-    not_shortest = 0
-    for rec, entry, line in zip(records, entries, theirs):
-        assert link.format_record_json(rec) == line
-        assert json.loads(line) == entry                 # same values either way
-        not_shortest += line != dumped(entry)
-    assert not_shortest > 0, "the sample should hold doubles that Grisu2 writes with 17 digits where 16 suffice"
+    return records, entries
 
 
-def test_every_visit_ratio_up_to_800_visits_is_written_as_the_library_writes_it(entry_dump):
+def visit_ratio_records():
     """n / N for every N <= 800 and every n <= N (the configs' visit counts: 100, 200, 400, 800), two per ply entry, and a
     sample of ratios up to the engine's limit of 60000 visits"""
     head = [MAGIC, 0, 0, 0, 1, 0, 0, 0]
@@ -206,9 +188,63 @@ def test_every_visit_ratio_up_to_800_visits_is_written_as_the_library_writes_it(
         if plies == 2000:
             flush()
     flush()
-    theirs = entry_dump(records)
-    for rec, line in zip(records, theirs):
-        assert link.format_record_json(rec) == line
+    return records
+
+
+def build_entry_dump(out_dir):
+    """oracle/json_entry_dump.cpp: builds the entry with nlohmann::json exactly as cpp/self_play_client.cpp:512-578 does and
+    streams it as :639-641 does -> records -> sha256 of each line it wrote"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(out_dir, "json_entry_dump")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + os.path.dirname(NLOHMANN), "-o", exe,
+                           os.path.join(root, "oracle", "json_entry_dump.cpp")])
+
+    def run(records):
+        out = subprocess.run([exe], input=b"".join(np.ascontiguousarray(r, dtype=np.uint32).tobytes() for r in records),
+                             capture_output=True, check=True)
+        return [digest(line) for line in out.stdout.split(b"\n")[:-1]]
+    return run
+
+
+@pytest.fixture(scope="module")
+def entry_dump(tmp_path_factory):
+    """name -> the library's line digests for that record set: from the library where it is installed (and then equal to
+    the stored ones), else the stored ones"""
+    with open(DIGESTS) as f:
+        stored = json.load(f)
+    if not os.path.exists(NLOHMANN):
+        return lambda name, records: stored[name]
+    run = build_entry_dump(str(tmp_path_factory.mktemp("nlohmann")))
+
+    def theirs(name, records):
+        lines = run(records)
+        assert lines == stored[name], "the installed nlohmann::json writes other lines than the stored digests record"
+        return lines
+    return theirs
+
+
+def test_lines_equal_what_nlohmann_json_itself_writes(entry_dump):
+    """Byte for byte, including the doubles for which Grisu2 — the library's algorithm — does NOT find the shortest
+    digits (json.dumps then differs from the reference, and so did this formatter while it asked std::to_chars)."""
+    records, entries = random_records()
+    theirs = entry_dump("random_records", records)
+    assert len(theirs) == len(records)
+    not_shortest = 0
+    for rec, entry, their_digest in zip(records, entries, theirs):
+        line = link.format_record_json(rec)
+        assert digest(line) == their_digest
+        assert json.loads(line) == entry                 # same values either way
+        not_shortest += line != dumped(entry)
+    assert not_shortest > 0, "the sample should hold doubles that Grisu2 writes with 17 digits where 16 suffice"
+
+
+def test_every_visit_ratio_up_to_800_visits_is_written_as_the_library_writes_it(entry_dump):
+    """n / N for every N <= 800 and every n <= N, and a sample of ratios up to 60000 visits (visit_ratio_records)"""
+    records = visit_ratio_records()
+    theirs = entry_dump("visit_ratio_records", records)
+    assert len(theirs) == len(records)
+    for rec, their_digest in zip(records, theirs):
+        assert digest(link.format_record_json(rec)) == their_digest
 
 
 def test_formatter_is_clean_under_address_and_undefined_behaviour_sanitizers(tmp_path):
@@ -229,3 +265,13 @@ def test_formatter_is_clean_under_address_and_undefined_behaviour_sanitizers(tmp
     assert res.returncode == 0, res.stderr.decode()[-3000:]
     formatted, refused, small = (int(x) for x in re.findall(rb"\d+", res.stdout))
     assert formatted > 3000 and refused > 3000 and small > 100
+
+
+if __name__ == "__main__":
+    # rewrite tests/golden/nlohmann_line_digests.json from the installed library
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        run = build_entry_dump(tmp)
+        with open(DIGESTS, "w") as f:
+            json.dump({"random_records": run(random_records()[0]), "visit_ratio_records": run(visit_ratio_records())}, f, indent=0)
+            f.write("\n")

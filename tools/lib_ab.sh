@@ -8,7 +8,7 @@ name=$1; V=$(realpath $2); rounds=${3:-2}; legs=${4:-one_batch,config2,config4}
 for round in $(seq 1 $rounds); do
   for lib in product $name; do
     if [ $lib = product ]; then unset AZH_LIB; else export AZH_LIB=$V; fi
-    timeout -k 10 400 python3 bench.py --steps 16 --warmup 3 --no-cpu-baseline --no-gemm-ceiling --legs $legs | python3 -c "
+    timeout -k 10 400 python3 bench.py --full --steps 16 --warmup 3 --no-cpu-baseline --no-gemm-ceiling --legs $legs | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s='round $round %-10s headline %.3f M node-evals/s (tower %.4f over the chip, tree phase per half %.4f ms)' % ('$lib', d['value']/1e6, d['roofline']['frac'], d['tree_roofline']['tree_phase_ms_per_iteration'])

@@ -1,12 +1,12 @@
 #!/bin/bash
-# rocprofv3 kernel trace of the config-5 arena leg (bench.py --legs config5_arena): how long the tower, the tree launch and the
+# rocprofv3 kernel trace of the config-5 arena leg (bench.py --full --legs config5_arena): how long the tower, the tree launch and the
 # re-roots take as the match thins out, and what an iteration's kernel boundaries cost.  GPU box, repo root.
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=${OUT:-$R/gpurun_out/prof_arena}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-gemm-ceiling --legs config5_arena > $OUT/trace.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-gemm-ceiling --legs config5_arena > $OUT/trace.log 2>&1 || exit 1
 python3 - "$OUT" <<'PY'
 import csv, glob, os, sys
 f = max(glob.glob(os.path.join(sys.argv[1], "trace", "*", "*_kernel_trace.csv")), key=os.path.getmtime)

@@ -27,7 +27,7 @@ done
 for round in 1 2; do
   for lib in product $name; do
     if [ $lib = product ]; then unset AZH_LIB; else export AZH_LIB=$V; fi
-    timeout -k 10 300 python3 bench.py --steps 8 --warmup 2 --streams 1 --no-cpu-baseline --no-gemm-ceiling --legs target_10k_games |
+    timeout -k 10 300 python3 bench.py --full --steps 8 --warmup 2 --streams 1 --no-cpu-baseline --no-gemm-ceiling --legs target_10k_games |
       python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); t=d['target_10k_games']
