@@ -99,3 +99,165 @@ def forward_sym(conv_weights, bn_params, features, dtype=np.float64):
     """sym_average around the restated net.  -> (policy (n,7,7,17), value (n,1))."""
     features = np.asarray(features, dtype=dtype)
     return sym_average(lambda images: forward(conv_weights, bn_params, images, dtype=dtype), features)
+
+
+# ---------------------------------------------------------------- the 16-bit towers' arithmetic, rounding for rounding
+#
+# forward_lowp restates what the HIP towers (ataxxzero_amd/csrc/net_kernels.hip) compute, in float64 with a rounding at
+# exactly the places where the kernels round (line numbers of net_kernels.hip):
+#   batch norm   azh_net_create :1643-1646: inv = 1/sqrt(double(var) + double(eps)), eps arriving as a float (link.Net
+#                passes a c_float); scale = float(inv), shift = float(-double(mean) * inv)
+#   conv weights pack_conv :1423-1440, pack_conv16 :1443-1458, the im2col first layer :1528-1537: the float product
+#                w * scale, rounded once to bf16 / f16 (f32_to_bf16 :1398, f32_to_f16 :1408: round to nearest even)
+#   head weights net_pack :1490-1495: the policy and value 1x1 convolutions rounded to 16 bits without a scale
+#   input planes exact 0 / 1
+#   each layer   the f32 accumulator starts at the shift (:246, :832-842) plus, for a block's second convolution, the
+#                stored 16-bit residual input (:272, :868), and sums the products; the epilogue converts the sum to 16
+#                bits with round to nearest even (__builtin_convertvector, :439, :766) and applies ReLU, which commutes
+#                with the conversion (:746-750)
+#   outputs      logits = the f32 head accumulators (:591, :1313-1315); the value conv channel stays f32 (:593, :1316);
+#                value = tanhf(s + fc_b), s the fmaf chain over c = 7 x + y of vcell[c] * fc_w[c] (:603-604, :1326-1327)
+# The sums themselves are taken in float64 and rounded to float once: on nets whose products and partial sums are all
+# exact in f32 (tests/net_exact.py) that IS the kernels' accumulator in every summation order; elsewhere the two differ
+# by accumulation-order noise.  fmt "f32" is the f32 tower (the same folding, no 16-bit rounding anywhere).
+
+LOWP_FORMATS = ("f32", "bf16", "f16")
+
+
+def round_bf16(x):
+    """float32 array -> the nearest bf16 values (round to nearest even), as float32.  Bit for bit the host's f32_to_bf16:
+    NaN stays a (quiet) NaN, overflow goes to infinity."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    r = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)
+    r = np.where(nan, u | np.uint32(0x00400000), r) & np.uint32(0xFFFF0000)
+    return r.view(np.float32)
+
+
+def round_f16(x):
+    """float32 array -> the nearest IEEE half values (round to nearest even, subnormals kept, overflow to infinity), as
+    float32; integer operations on the float32 encoding."""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.int64)
+    sign = (u >> 16) & 0x8000
+    a = u & 0x7FFFFFFF
+    # normal halves (|x| >= 2^-14): keep 10 of the 23 fraction bits, ties to the even neighbour, rebias 127 -> 15
+    h_norm = ((a + 0xFFF + ((a >> 13) & 1)) >> 13) - (112 << 10)
+    # subnormal halves: |x| / 2^-24 rounded to an integer, ties to even
+    e = a >> 23
+    m = (a & 0x7FFFFF) | 0x800000
+    s = np.clip(126 - e, 1, 31)
+    q = m >> s
+    rem = m & ((1 << s) - 1)
+    half = 1 << (s - 1)
+    h_sub = q + ((rem > half) | ((rem == half) & (q & 1 == 1)))
+    h = np.where(a >= 0x38800000, h_norm, np.where(e >= 102, h_sub, 0))
+    h = np.where(a >= 0x477FF000, 0x7C00, h)            # >= 65520: infinity
+    h = np.where(a > 0x7F800000, 0x7E00, h)             # NaN
+    return ((sign | h).astype(np.uint16)).view(np.float16).astype(np.float32)
+
+
+def _rounder(fmt):
+    if fmt not in LOWP_FORMATS:
+        raise ValueError("fmt must be one of %s, got %r" % (LOWP_FORMATS, fmt))
+    return {"f32": lambda x: np.asarray(x, dtype=np.float32), "bf16": round_bf16, "f16": round_f16}[fmt]
+
+
+def bn_constants(mean, var, eps=BN_EPS):
+    """(scale, shift) as float32, as azh_net_create derives them (net_kernels.hip:1634-1650)."""
+    inv = 1.0 / np.sqrt(np.asarray(var, np.float32).astype(np.float64) + np.float64(np.float32(eps)))
+    return inv.astype(np.float32), (-np.asarray(mean, np.float32).astype(np.float64) * inv).astype(np.float32)
+
+
+def lowp_parameters(conv_weights, bn_params, fmt, eps=BN_EPS):
+    """The net as the towers hold it: [(16-bit folded weights (3,3,c,o), f32 shift (o,))] per tower layer, the 16-bit
+    policy (c,17) and value (c,) head weights, fc_w (49,) and fc_b as float32 — every entry a float32 value."""
+    rnd = _rounder(fmt)
+    cw = [np.asarray(a, dtype=np.float32) for a in conv_weights]
+    blocks = (len(cw) - 5) // 2
+    layers = []
+    for i in range(2 * blocks + 1):
+        scale, shift = bn_constants(bn_params[2 * i], bn_params[2 * i + 1], eps)
+        layers.append((rnd(cw[i] * scale), shift))                       # f32 product, one rounding (pack_conv)
+    head_p = rnd(cw[2 * blocks + 1][0, 0])                                # net_pack: heads unscaled
+    head_v = rnd(cw[2 * blocks + 2][0, 0, :, 0])
+    return layers, head_p, head_v, cw[2 * blocks + 3].reshape(49), np.float32(cw[2 * blocks + 4].reshape(-1)[0])
+
+
+def _truncate_bf16(x):
+    return (np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
+
+
+def _truncate_f16(x):
+    x = np.asarray(x, dtype=np.float32)
+    t = round_f16(x).astype(np.float16)
+    return np.where(np.abs(t.astype(np.float32)) > np.abs(x), np.nextafter(t, np.float16(0)), t).astype(np.float32)
+
+
+def _only_tap(w, i, j):
+    out = np.zeros_like(w)
+    out[i, j] = w[i, j]
+    return out
+
+
+def _forward_lowp(conv_weights, bn_params, features, fmt, eps=BN_EPS, defect=None):
+    """forward_lowp with an optional deliberate `defect` (tests/test_net_emulation.py's mutants: what a subtly wrong
+    kernel would compute).  -> (policy (n,7,7,17), value (n,1), activations per tower layer)."""
+    rnd = _rounder(fmt)
+    f32 = np.float32
+    layers, head_p, head_v, fc_w, fc_b = lowp_parameters(conv_weights, bn_params, fmt, eps)
+    if defect == "scale_after_rounding":
+        cw = [np.asarray(a, dtype=np.float32) for a in conv_weights]
+        layers = [(rnd(rnd(cw[i]) * bn_constants(bn_params[2 * i], bn_params[2 * i + 1], eps)[0]), sh)
+                  for i, (_, sh) in enumerate(layers)]
+    if defect == "truncate" and fmt != "f32":
+        rnd = _truncate_bf16 if fmt == "bf16" else _truncate_f16
+    h = np.asarray(features, dtype=np.float64)
+    acts = []
+
+    def layer(x, w, shift, residual=None, index=0):
+        z = conv2d_same(x, w.astype(np.float64))
+        if defect == "edge_tap" and index > 0:
+            # one on-board tap (dx = +1, dy = 0) missing for the cells of the y = 0 edge
+            zt = conv2d_same(x, _only_tap(w.astype(np.float64), 2, 1))
+            z[:, :, 0, :] -= zt[:, :, 0, :]
+        z = z + shift.astype(np.float64)
+        if residual is not None and defect != "residual_after_rounding":
+            z = z + residual
+        out = rnd(z.astype(np.float32)).astype(np.float64)
+        if residual is not None and defect == "residual_after_rounding":
+            out = rnd((out + residual).astype(np.float32)).astype(np.float64)
+        return np.maximum(out, 0)
+
+    blocks = (len(layers) - 1) // 2
+    h = layer(h, *layers[0])
+    acts.append(h)
+    for b in range(blocks):
+        t = layer(h, *layers[1 + 2 * b], index=1 + 2 * b)
+        acts.append(t)
+        h = layer(t, *layers[2 + 2 * b], residual=h, index=2 + 2 * b)
+        acts.append(h)
+    policy = (h @ head_p.astype(np.float64)).astype(np.float32)
+    vcell = (h @ head_v.astype(np.float64)).astype(np.float32)             # (n,7,7), f32
+    if defect == "policy16_from_value_row":
+        policy[..., 16] = vcell
+    v = (np.swapaxes(vcell, 1, 2) if defect == "value_xy_swapped" else vcell).reshape(len(h), 49)
+    s = np.zeros(len(h), dtype=np.float32)
+    for c in range(49):                                                   # fmaf chain, c = 7 x + y (model.py:75)
+        s = (v[:, c].astype(np.float64) * np.float64(fc_w[c]) + s.astype(np.float64)).astype(f32)
+    value = np.tanh((s + fc_b).astype(f32).astype(np.float64)).reshape(-1, 1)
+    return policy.astype(np.float64) + 0.0, value, acts      # (+ 0.0: a zero logit is +0, as the kernels write it)
+
+
+def forward_lowp(conv_weights, bn_params, features, fmt, eps=BN_EPS):
+    """The tower of dtype `fmt` ("f32", "bf16", "f16") restated rounding for rounding (see above).
+    -> (policy logits (n,7,7,17), value (n,1)) in float64; the logits are float32 values, the value is the float64
+    tanh of the kernels' float32 argument (their tanhf is within a few ulp of it)."""
+    policy, value, _ = _forward_lowp(conv_weights, bn_params, features, fmt, eps)
+    return policy, value
+
+
+def forward_lowp_sym(conv_weights, bn_params, features, fmt, eps=BN_EPS):
+    """sym_average around forward_lowp: the symmetry-averaged towers (azh_net_launch_sym + k_sym_reduce, whose f32 sum
+    of eight logits times 0.125 is exact wherever the eight logits are exact integers of magnitude < 2^21)."""
+    features = np.asarray(features, dtype=np.float64)
+    return sym_average(lambda images: forward_lowp(conv_weights, bn_params, images, fmt, eps), features)
