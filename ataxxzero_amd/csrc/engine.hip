@@ -627,24 +627,18 @@ __global__ __launch_bounds__(1024) void k_compact(const int *need, int G, int *l
 
 // ------------------------------------------------------------------ priors + backup
 
-// `s`: the game's state in the caller's registers (uniform over the lanes); updated, not stored.
-__device__ inline void backup_game(const EngineParams &P, int g, azh_game_state &s)
+// Evaluations::populate (:204-271): the priors of `node` from one row of logits — a softmax over the legal moves' logits,
+// identical to the reference's 833-way softmax renormalised over the legal moves — then, at the root (`root`), the
+// Dirichlet mix keyed by (uid, ply).  Wave-cooperative.
+__device__ inline void apply_priors(const EngineParams &P, const Arena &A, int node, const float *row, bool root, u32 uid,
+                                    u32 ply)
 {
     const int lane = lane_id();
-    const int kind = s.leaf_kind;
-    if (kind == AZH_LEAF_NONE || kind == AZH_LEAF_DESCENT)
-        return;  // nothing evaluated; a parked descent keeps its state
-    Arena A = arena_of(P, s.arena, g);
-
-    if (kind == AZH_LEAF_EVAL || kind == AZH_LEAF_ROOT) {
-        // Evaluations::populate (:204-271): softmax over the legal moves' logits —
-        // identical to the reference's 833-way softmax renormalised over the legal
-        // moves — then the Dirichlet mix at the root.
-        const uint4 info = A.ni[s.leaf_node];
+    {
+        const uint4 info = A.ni[node];
         const u32 first = info.x;
         const int M = (int)(info.y & 0xFFFFu);
         const int rounds = (M + 63) >> 6;
-        const float *row = P.logits + (size_t)g * AZH_POLICY_SIZE;
         float l[4], ex[4];
         float pr[4];
         if (P.flags & AZH_FLAG_PY_POSTERIOR) {
@@ -708,7 +702,7 @@ __device__ inline void backup_game(const EngineParams &P, int g, azh_game_state 
             for (int k = 0; k < 4; k++)
                 pr[k] = S > 0.0f ? ex[k] / S : ex[k];
         }
-        if (kind == AZH_LEAF_ROOT && P.noise_w > 0.0f) {
+        if (root && P.noise_w > 0.0f) {
             float gm[4];
             float gpart = 0.0f;
 #pragma unroll
@@ -716,7 +710,7 @@ __device__ inline void backup_game(const EngineParams &P, int g, azh_game_state 
                 const int j = lane + 64 * k;
                 gm[k] = 0.0f;
                 if (k < rounds && j < M) {
-                    gm[k] = det_gamma(P.alpha, P.k0, P.k1, s.uid, (u32)s.ply, (u32)j);
+                    gm[k] = det_gamma(P.alpha, P.k0, P.k1, uid, ply, (u32)j);
                     gpart = gpart + gm[k];
                 }
             }
@@ -740,6 +734,19 @@ __device__ inline void backup_game(const EngineParams &P, int g, azh_game_state 
                 reinterpret_cast<u32 *>(&A.ed[first + j])[0] = f2u(pr[k]) & PRIOR_MASK;
         }
     }
+}
+
+// `s`: the game's state in the caller's registers (uniform over the lanes); updated, not stored.
+__device__ inline void backup_game(const EngineParams &P, int g, azh_game_state &s)
+{
+    const int lane = lane_id();
+    const int kind = s.leaf_kind;
+    if (kind == AZH_LEAF_NONE || kind == AZH_LEAF_DESCENT)
+        return;  // nothing evaluated; a parked descent keeps its state
+    Arena A = arena_of(P, s.arena, g);
+
+    if (kind == AZH_LEAF_EVAL || kind == AZH_LEAF_ROOT)
+        apply_priors(P, A, s.leaf_node, P.logits + (size_t)g * AZH_POLICY_SIZE, kind == AZH_LEAF_ROOT, s.uid, (u32)s.ply);
 
     if ((P.flags & AZH_FLAG_EVAL_CACHE) && kind == AZH_LEAF_EVAL) {
         // the leaf now carries an evaluation: remember its value and enter it in the table
@@ -1010,6 +1017,8 @@ __global__ void k_reduce_stats(const u64 *stats, int G, u64 *out)
 
 }  // namespace azh
 
+#include "vl_search.h"
+
 using namespace azh;
 
 // ------------------------------------------------------------------ host
@@ -1067,12 +1076,29 @@ struct azh_engine {
     bool stamp_next = false;   // azh_engine_tree_stamps: the next fused tree launch of the loop is the stamped instantiation
     int thin_mode = -1;        // azh_engine_set_thin_batches: 0 the 3-board tower, 1 one board per workgroup, -1 by the engine's size
     int adv_workers = 8;       // workgroups at the head of every tower launch of the device loop that play the queued moves
+    // leaf-parallel search (azh_engine_set_leaf_batch): K leaves per game and iteration in slots g K + p.  With K > 1 the
+    // leaf buffers of P (boards, need flags, list, need mask, logits, values) point at G K-slot buffers; with K = 1 at the
+    // engine's own G-slot ones, and every launch is the one-leaf search's.
+    VlParams V{};
+    int vl_slots_cap = 0;  // slots the G K buffers were allocated for
+    ulonglong2 *g_leaf_board = nullptr;
+    int *g_need_eval = nullptr, *g_leaf_list = nullptr;
+    u32 *g_need_mask = nullptr;
+    int g_mask_words = 0;
+    float *g_logits = nullptr, *g_values = nullptr;
+    ulonglong2 *vl_leaf_board = nullptr;  // the G K-slot buffers while K = 1 is in force
+    int *vl_need_eval = nullptr, *vl_leaf_list = nullptr;
+    u32 *vl_need_mask = nullptr;
+    int vl_mask_words = 0;
+    float *vl_logits = nullptr, *vl_values = nullptr;
 };
+
+static int leaf_k(const azh_engine *e) { return e->V.K > 1 ? e->V.K : 1; }
 
 // the tower for this engine's leaf batches: one board per workgroup for engines (or batches the host says are) small
 static int thin_batches(const azh_engine *e)
 {
-    return e->thin_mode >= 0 ? e->thin_mode : (e->P.G <= AZH_THIN_MAX_GAMES ? 1 : 0);
+    return e->thin_mode >= 0 ? e->thin_mode : (e->P.G * leaf_k(e) <= AZH_THIN_MAX_GAMES ? 1 : 0);  // (by slots: G K)
 }
 
 static const size_t MAX_TIMED_SAMPLES = 8192;
@@ -1179,6 +1205,16 @@ extern "C" int azh_engine_create(const azh_config *cfg, azh_engine **out)
     // one move-playing workgroup per 128 game slots (an iteration queues about one game in 400 at 400 sims/move, one in 200
     // at 200), at least 8, at most 64, a multiple of 8 (the tiles behind them keep their XCD)
     e->adv_workers = std::min(64, std::max(8, (P.G / 128 + 7) / 8 * 8));
+    e->V.K = 1;
+    e->V.vl = 1;
+    e->V.path_cap = P.path_cap;
+    e->g_leaf_board = P.leaf_board;
+    e->g_need_eval = P.need_eval;
+    e->g_leaf_list = P.leaf_list;
+    e->g_need_mask = P.need_mask;
+    e->g_mask_words = P.mask_words;
+    e->g_logits = P.logits;
+    e->g_values = P.values;
     hipLaunchKernelGGL(k_init, dim3(P.G), dim3(WAVE), 0, e->stream, P);
     if (hipStreamSynchronize(e->stream) != hipSuccess) {
         azh_engine_destroy(e);
@@ -1244,6 +1280,11 @@ static int enqueue_advance(azh_engine *e, hipStream_t stream, hipEvent_t done = 
 
 static int enqueue_select(azh_engine *e)
 {
+    if (leaf_k(e) > 1) {
+        hipLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, e->P, e->V, 2);
+        AZH_HIP(hipGetLastError());
+        return enqueue_advance(e, e->stream);
+    }
     hipLaunchKernelGGL(k_select, dim3(e->P.G), dim3(WAVE), 0, e->stream, e->P);
     if (enqueue_compact(e))
         return -1;
@@ -1252,6 +1293,11 @@ static int enqueue_select(azh_engine *e)
 
 static int enqueue_backup(azh_engine *e)
 {
+    if (leaf_k(e) > 1) {
+        hipLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, e->P, e->V, 1);
+        AZH_HIP(hipGetLastError());
+        return 0;
+    }
     hipLaunchKernelGGL(k_backup, dim3(e->P.G), dim3(WAVE), 0, e->stream, e->P);
     hipLaunchKernelGGL(k_mark, dim3(e->P.G), dim3(WAVE), 0, e->stream, e->P);
     AZH_HIP(hipGetLastError());
@@ -1276,6 +1322,8 @@ extern "C" int azh_engine_leaves(azh_engine *e, int32_t *need_eval, uint64_t *le
 {
     if (!e)
         return azh_fail(-1, "azh_engine_leaves: null engine");
+    if (leaf_k(e) > 1)
+        return azh_fail(-2, "azh_engine_leaves: %d leaves per game: use azh_engine_batch_leaves", leaf_k(e));
     AZH_HIP(hipStreamSynchronize(e->stream));
     if (need_eval)
         AZH_HIP(hipMemcpy(need_eval, e->P.need_eval, (size_t)e->P.G * 4, hipMemcpyDeviceToHost));
@@ -1289,6 +1337,8 @@ extern "C" int azh_engine_leaf_features(azh_engine *e, float *out, int32_t *game
 {
     if (!e || !out)
         return azh_fail(-1, "azh_engine_leaf_features: null argument");
+    if (leaf_k(e) > 1)
+        return azh_fail(-2, "azh_engine_leaf_features: not available with %d leaves per game", leaf_k(e));
     AZH_HIP(hipStreamSynchronize(e->stream));
     int n = 0;
     AZH_HIP(hipMemcpy(&n, e->P.leaf_count, 4, hipMemcpyDeviceToHost));
@@ -1310,7 +1360,7 @@ extern "C" int azh_engine_leaf_features(azh_engine *e, float *out, int32_t *game
 static int launch_eval(azh_engine *e, azh_net *net, int dtype, const int *list, const int *count, const AdvanceHook *hook = nullptr)
 {
     if (!(e->P.flags & AZH_FLAG_SYMMETRY_AVG))
-        return azh_net_launch(net, dtype, (const unsigned long long *)e->P.leaf_board, list, count, e->P.G,
+        return azh_net_launch(net, dtype, (const unsigned long long *)e->P.leaf_board, list, count, e->P.G * leaf_k(e),
                               e->P.blockers, e->P.logits, e->P.values, e->stream, nullptr, thin_batches(e), hook);
     if (!e->d_sym_logits) {
         AZH_HIP(hipMalloc((void **)&e->d_sym_logits, (size_t)e->P.G * 8 * AZH_POLICY_SIZE * 4));
@@ -1333,6 +1383,8 @@ extern "C" int azh_engine_set_evals(azh_engine *e, const float *logits, const fl
 {
     if (!e || !logits || !values)
         return azh_fail(-1, "azh_engine_set_evals: null argument");
+    if (leaf_k(e) > 1)
+        return azh_fail(-2, "azh_engine_set_evals: %d leaves per game: use azh_engine_set_batch_evals", leaf_k(e));
     AZH_HIP(hipMemcpyAsync(e->P.logits, logits, (size_t)e->P.G * AZH_POLICY_SIZE * 4, hipMemcpyHostToDevice, e->stream));
     AZH_HIP(hipMemcpyAsync(e->P.values, values, (size_t)e->P.G * 4, hipMemcpyHostToDevice, e->stream));
     AZH_HIP(hipStreamSynchronize(e->stream));
@@ -1389,6 +1441,10 @@ struct RunLoop {
     // one fused tree launch; ev (or nullptr) is signalled by the kernel's own completion
     void launch_tree(bool stamped, int mode, hipEvent_t ev)
     {
+        if (leaf_k(e) > 1) {  // leaf-parallel search: one workgroup per game (not stamped: azh_engine_tree_stamps refuses)
+            hipExtLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, nullptr, ev, 0, e->P, e->V, mode);
+            return;
+        }
         const bool small = e->P.G <= TREE_ONE_ROUND_GAMES;
         const int waves = small ? TREE_WAVES_SMALL : TREE_WAVES_LARGE;
         const dim3 grid((e->P.G + waves - 1) / waves), block(waves * WAVE);
@@ -1543,6 +1599,8 @@ extern "C" int azh_engine_tree_stamps(azh_engine *e, azh_net *net, int dtype, ui
 {
     if (!e || !net || !out)
         return azh_fail(-1, "azh_engine_tree_stamps: null argument");
+    if (leaf_k(e) > 1)
+        return azh_fail(-2, "azh_engine_tree_stamps: not available with %d leaves per game", leaf_k(e));
     if (!e->P.stamps) {
         void *q = nullptr;
         AZH_HIP(hipMalloc(&q, (size_t)e->P.G * TREE_STAMPS * 8));
@@ -1557,6 +1615,105 @@ extern "C" int azh_engine_tree_stamps(azh_engine *e, azh_net *net, int dtype, ui
         return rc;
     AZH_HIP(hipStreamSynchronize(e->stream));
     AZH_HIP(hipMemcpy(out, e->P.stamps, (size_t)e->P.G * TREE_STAMPS * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Leaf-parallel search: K leaves per game and iteration, spread by a virtual loss of `virtual_loss` visits
+// (vl_search.h).  Between iterations only; K = 1 restores the one-leaf search and its kernels.
+extern "C" int azh_engine_set_leaf_batch(azh_engine *e, int leaves_per_game, int virtual_loss)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_set_leaf_batch: null engine");
+    if (leaves_per_game < 1 || leaves_per_game > VL_MAX_LEAVES || virtual_loss < 1 || virtual_loss > VL_MAX_LOSS)
+        return azh_fail(-2, "azh_engine_set_leaf_batch: need 1 <= leaves_per_game <= %d and 1 <= virtual_loss <= %d",
+                        VL_MAX_LEAVES, VL_MAX_LOSS);
+    if (e->selected)
+        return azh_fail(-3, "azh_engine_set_leaf_batch: a selected batch awaits its backup");
+    if (leaves_per_game > 1) {
+        const uint32_t bad = e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_EVAL_CACHE | AZH_FLAG_SYMMETRY_AVG);
+        if (bad || e->P.select_budget > 0)
+            return azh_fail(-4, "azh_engine_set_leaf_batch: more than one leaf per game is not supported with %s",
+                            e->P.select_budget > 0 ? "select_budget > 0"
+                            : (bad & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS"
+                            : (bad & AZH_FLAG_EVAL_CACHE) ? "AZH_FLAG_EVAL_CACHE" : "AZH_FLAG_SYMMETRY_AVG");
+    }
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_HIP(hipStreamSynchronize(e->stream2));
+    EngineParams &P = e->P;
+    const size_t G = (size_t)P.G, K = (size_t)leaves_per_game;
+    if (K > 1 && e->V.K <= 1 && e->vl_slots_cap > 0) {
+        // back to K-slot buffers allocated by an earlier call
+        P.leaf_board = e->vl_leaf_board; P.need_eval = e->vl_need_eval; P.leaf_list = e->vl_leaf_list;
+        P.need_mask = e->vl_need_mask; P.mask_words = e->vl_mask_words; P.logits = e->vl_logits; P.values = e->vl_values;
+    }
+    if (K > 1 && (int)(G * K) > e->vl_slots_cap) {
+        // slot buffers for G K leaves (kept for the engine's life; a larger K later allocates again)
+        const size_t n = G * K;
+        const int mw = (int)((n + 31) / 32);
+        int rc = 0;
+        rc |= dev_alloc(e, &e->V.kind, n);
+        rc |= dev_alloc(e, &e->V.leaf_edge, n);
+        rc |= dev_alloc(e, &e->V.leaf_node, n);
+        rc |= dev_alloc(e, &e->V.path_len, n);
+        rc |= dev_alloc(e, &e->V.path, n * (size_t)P.path_cap);
+        rc |= dev_alloc(e, &P.leaf_board, n);
+        rc |= dev_alloc(e, &P.need_eval, n);
+        rc |= dev_alloc(e, &P.leaf_list, n);
+        rc |= dev_alloc(e, &P.need_mask, 2 * (size_t)mw);
+        rc |= dev_alloc(e, &P.logits, n * AZH_POLICY_SIZE);
+        rc |= dev_alloc(e, &P.values, n);
+        P.mask_words = mw;
+        if (rc) {
+            P.leaf_board = e->g_leaf_board; P.need_eval = e->g_need_eval; P.leaf_list = e->g_leaf_list;
+            P.need_mask = e->g_need_mask; P.mask_words = e->g_mask_words; P.logits = e->g_logits; P.values = e->g_values;
+            e->V.K = 1;
+            e->vl_slots_cap = 0;
+            return rc;
+        }
+        e->vl_slots_cap = (int)n;
+    }
+    if (K > 1) {
+        e->vl_leaf_board = P.leaf_board; e->vl_need_eval = P.need_eval; e->vl_leaf_list = P.leaf_list;
+        e->vl_need_mask = P.need_mask; e->vl_mask_words = P.mask_words; e->vl_logits = P.logits; e->vl_values = P.values;
+    } else {
+        P.leaf_board = e->g_leaf_board; P.need_eval = e->g_need_eval; P.leaf_list = e->g_leaf_list;
+        P.need_mask = e->g_need_mask; P.mask_words = e->g_mask_words; P.logits = e->g_logits; P.values = e->g_values;
+    }
+    e->V.K = (int)K;
+    e->V.vl = virtual_loss;
+    return 0;
+}
+
+// The current batch: per slot g K + p its kind (AZH_LEAF_*), leaf board (mover, opponent; zero unless the slot needs the
+// net) and the last edge of its path (0xFFFFFFFF: none).  Any pointer may be NULL.
+extern "C" int azh_engine_batch_leaves(azh_engine *e, int32_t *kind, uint64_t *leaf_boards, uint32_t *leaf_edge)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_batch_leaves: null engine");
+    if (leaf_k(e) < 2)
+        return azh_fail(-2, "azh_engine_batch_leaves: one leaf per game: use azh_engine_leaves");
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    const size_t n = (size_t)e->P.G * leaf_k(e);
+    if (kind)
+        AZH_HIP(hipMemcpy(kind, e->V.kind, n * 4, hipMemcpyDeviceToHost));
+    if (leaf_boards)
+        AZH_HIP(hipMemcpy(leaf_boards, e->P.leaf_board, n * 16, hipMemcpyDeviceToHost));
+    if (leaf_edge)
+        AZH_HIP(hipMemcpy(leaf_edge, e->V.leaf_edge, n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Evaluations of the current batch from outside: logits [G K][833], values [G K], by slot.
+extern "C" int azh_engine_set_batch_evals(azh_engine *e, const float *logits, const float *values)
+{
+    if (!e || !logits || !values)
+        return azh_fail(-1, "azh_engine_set_batch_evals: null argument");
+    if (leaf_k(e) < 2)
+        return azh_fail(-2, "azh_engine_set_batch_evals: one leaf per game: use azh_engine_set_evals");
+    const size_t n = (size_t)e->P.G * leaf_k(e);
+    AZH_HIP(hipMemcpyAsync(e->P.logits, logits, n * AZH_POLICY_SIZE * 4, hipMemcpyHostToDevice, e->stream));
+    AZH_HIP(hipMemcpyAsync(e->P.values, values, n * 4, hipMemcpyHostToDevice, e->stream));
+    AZH_HIP(hipStreamSynchronize(e->stream));
     return 0;
 }
 

@@ -24,6 +24,9 @@ DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "float32": DTYPE_F32, "bf16": DTYPE_BF16,
           "f16": DTYPE_F16, "fp16": DTYPE_F16}
 LEAF_NONE, LEAF_EVAL, LEAF_TERMINAL, LEAF_ROOT = 0, 1, 2, 3
+LEAF_COLLISION = 5          # leaf-parallel search: the path met a node an earlier path of its batch created
+MAX_LEAVES_PER_GAME, MAX_VIRTUAL_LOSS = 64, 16
+STAT_COLLISIONS = 15        # AZH_STAT_COLLISIONS (not in STAT_NAMES, whose order the bench's dumps follow): Engine.collisions()
 FLAG_NO_REUSE, FLAG_TIE_FIRST, FLAG_PY_POSTERIOR, FLAG_SAMPLE_POW5, FLAG_KEEP_UNFINISHED, FLAG_TWO_NETS = 1, 2, 4, 8, 16, 32
 FLAG_ARENA = 63
 FLAG_SYMMETRY_AVG = 128    # nn_evals.py:48-62 on every evaluation
@@ -99,6 +102,9 @@ SIGNATURES = {
     "azh_engine_sync": (ctypes.c_int, [_vp]),
     "azh_engine_set_visits": (ctypes.c_int, [_vp, ctypes.c_int]),
     "azh_engine_set_thin_batches": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "azh_engine_set_leaf_batch": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "azh_engine_batch_leaves": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
+    "azh_engine_set_batch_evals": (ctypes.c_int, [_vp, _vp, _vp]),
     "azh_engine_game_state": (ctypes.c_int, [_vp, ctypes.c_int, _P(GameState)]),
     "azh_engine_tree": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "azh_engine_tree_raw": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
@@ -339,6 +345,7 @@ class Engine:
         self.node_cap = load().azh_engine_node_cap(h)
         self.edge_cap = load().azh_engine_edge_cap(h)
         self._json = np.zeros(1 << 22, dtype=np.uint8)
+        self.K = 1
 
     def close(self):
         if getattr(self, "h", None):
@@ -394,6 +401,32 @@ class Engine:
     def set_thin_batches(self, mode):
         """0: the 3-board tower; 1: one board per workgroup (a handful of leaves per iteration); -1: by the engine's size."""
         check(load().azh_engine_set_thin_batches(self.h, int(mode)))
+
+    def set_leaf_batch(self, leaves_per_game, virtual_loss=1):
+        """Leaf-parallel search: up to K leaves per game and iteration, spread by a virtual loss ("Leaf-parallel
+        search").  Between iterations only; K = 1 is the one-leaf search."""
+        check(load().azh_engine_set_leaf_batch(self.h, int(leaves_per_game), int(virtual_loss)))
+        self.K = int(leaves_per_game)
+
+    def batch_leaves(self):
+        """-> kind (G, K) int32, leaf boards (G, K, 2) u64 (mover, opponent), leaf edge (G, K) u32 of the current batch."""
+        kind = np.zeros((self.G, self.K), dtype=np.int32)
+        boards = np.zeros((self.G, self.K, 2), dtype=np.uint64)
+        edge = np.zeros((self.G, self.K), dtype=np.uint32)
+        check(load().azh_engine_batch_leaves(self.h, _ptr(kind), _ptr(boards), _ptr(edge)))
+        return kind, boards, edge
+
+    def set_batch_evals(self, logits, values):
+        """Evaluations of the batch by slot: logits (G K, 833), values (G K,)."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32).reshape(self.G * self.K, POLICY_SIZE)
+        values = np.ascontiguousarray(values, dtype=np.float32).reshape(self.G * self.K)
+        check(load().azh_engine_set_batch_evals(self.h, _ptr(logits), _ptr(values)))
+
+    def collisions(self):
+        """Paths of the leaf-parallel search that ended at a node created earlier in their batch (AZH_STAT_COLLISIONS)."""
+        out = np.zeros(STAT_COUNT, dtype=np.uint64)
+        check(load().azh_engine_stats(self.h, _ptr(out)))
+        return int(out[STAT_COLLISIONS])
 
     def set_positions(self, boards, plies):
         """Every slot restarts at boards[g] (packed x | turn << 63, o) / plies[g] with a fresh tree (counted, not written)."""

@@ -94,9 +94,19 @@ class Position:
 
 
 class Searcher:
-    TIME_CAP_VISITS = 20000  # arena size of a time-controlled search
+    TIME_CAP_VISITS = 20000  # arena size of a time-controlled search (per leaf of a leaf-parallel iteration, below)
+    MAX_VISITS = 60000       # the engine's limit (16-bit visit counts); a search of this many visits holds about 3.5 KB of
+                             # tree per visit (96 edge slots of 18 bytes per node, two arenas): at most about 210 MB
 
-    def __init__(self, network_path, dtype="f16", symmetry_average=False):
+    def __init__(self, network_path, dtype="f16", symmetry_average=False, parallel_leaves=1, virtual_loss=1):
+        # parallel_leaves = K > 1: leaf-parallel search with virtual loss ("Leaf-parallel search"): up to K
+        # leaves per iteration in one tower launch.  An extension; 1 is the reference's one-leaf search.
+        if not 1 <= parallel_leaves <= link.MAX_LEAVES_PER_GAME or not 1 <= virtual_loss <= link.MAX_VIRTUAL_LOSS:
+            raise ValueError("need 1 <= parallel_leaves <= %d and 1 <= virtual_loss <= %d"
+                             % (link.MAX_LEAVES_PER_GAME, link.MAX_VIRTUAL_LOSS))
+        if parallel_leaves > 1 and symmetry_average:
+            raise ValueError("symmetry averaging is not available with parallel_leaves > 1")
+        self.parallel_leaves, self.virtual_loss = parallel_leaves, virtual_loss
         # symmetry_average: every evaluation is nn_evals.evaluate (nn_evals.py:48-62); with one game the
         # eight images ride in the same tower launch, so it costs no time
         self.extra_flags = link.FLAG_SYMMETRY_AVG if symmetry_average else 0
@@ -106,8 +116,14 @@ class Searcher:
         self.last_steps = 0
         self.last_seconds = 0.0
 
+    def time_cap(self):
+        """Visit cap of a time-controlled search: grows with the leaves per iteration, up to the engine's limit."""
+        return min(self.TIME_CAP_VISITS * self.parallel_leaves, self.MAX_VISITS)
+
     def root_visits(self, pos, visits=None, seconds=None):
         """-> [(move u16, visits)] over the expanded root edges after the search."""
+        if self.parallel_leaves > 1:
+            return self._root_visits_parallel(pos, visits, seconds)
         cap = visits if visits is not None else self.TIME_CAP_VISITS
         cfg = link.Config(games=1, visits=cap + 1, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
                           dirichlet_weight=0.0, start_turn=pos.turn, seed=random.getrandbits(63), start_x=pos.x,
@@ -131,6 +147,38 @@ class Searcher:
         finally:
             eng.close()
         self.last_steps, self.last_seconds = steps, max(time.time() - start, 1e-9)
+        first, n = int(info[0, 0]), int(info[0, 1] & 0xFFFF)
+        return [(int(moves[first + j]), int(edges[first + j, 1])) for j in range(n) if int(edges[first + j, 3]) != 0xFFFFFFFF]
+
+    def _root_visits_parallel(self, pos, visits, seconds):
+        """The leaf-parallel search: iterations of up to K leaves until the root has `visits` visits (exactly: the last
+        batch is truncated) or the time is used; last_steps counts root visits, not iterations."""
+        K = self.parallel_leaves
+        target = visits if visits is not None else self.time_cap()
+        cfg = link.Config(games=1, visits=target, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
+                          dirichlet_weight=0.0, start_turn=pos.turn, seed=random.getrandbits(63), start_x=pos.x,
+                          start_o=pos.o, blockers=0, flags=link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR | self.extra_flags)
+        eng = link.Engine(cfg)
+        start = time.time()
+        try:
+            eng.set_leaf_batch(K, self.virtual_loss)
+            eng.run(self.net, 1, self.dtype)  # the root evaluation
+            rv = 0
+            while rv < target and (seconds is None or time.time() - start < seconds):
+                # no run may go past the iteration that reaches the target: the move would be played in the next one
+                chunk = -(-(target - rv) // K)
+                if seconds is not None:
+                    chunk = min(chunk, 16)
+                eng.run(self.net, chunk, self.dtype)
+                now = eng.game_state(0).root_visits  # (waits for the run)
+                if now == rv:
+                    break  # a finished root: nothing to search
+                rv = now
+            eng.sync()
+            boards, info, edges, moves = eng.tree(0)
+        finally:
+            eng.close()
+        self.last_steps, self.last_seconds = rv, max(time.time() - start, 1e-9)
         first, n = int(info[0, 0]), int(info[0, 1] & 0xFFFF)
         return [(int(moves[first + j]), int(edges[first + j, 1])) for j in range(n) if int(edges[first + j, 3]) != 0xFFFFFFFF]
 

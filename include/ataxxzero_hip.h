@@ -35,7 +35,8 @@ extern "C" {
 #define AZH_STAT_COUNT 16
 
 enum { AZH_DTYPE_F32 = 0, AZH_DTYPE_BF16 = 1, AZH_DTYPE_F16 = 2 };
-enum { AZH_LEAF_NONE = 0, AZH_LEAF_EVAL = 1, AZH_LEAF_TERMINAL = 2, AZH_LEAF_ROOT = 3, AZH_LEAF_DESCENT = 4 };
+enum { AZH_LEAF_NONE = 0, AZH_LEAF_EVAL = 1, AZH_LEAF_TERMINAL = 2, AZH_LEAF_ROOT = 3, AZH_LEAF_DESCENT = 4,
+       AZH_LEAF_COLLISION = 5 /* leaf-parallel search: the path met a node an earlier path of its batch created */ };
 
 /* ------------------------------------------------------------------ errors */
 const char *azh_last_error(void);
@@ -188,7 +189,8 @@ enum {
     AZH_STAT_PLIES, AZH_STAT_GAMES, AZH_STAT_DROPPED, AZH_STAT_EDGE_OVERFLOW, AZH_STAT_REROOT_NODES,
     AZH_STAT_REROOT_EDGES, AZH_STAT_RING_OVERFLOW, AZH_STAT_CACHE_HITS,
     AZH_STAT_PARKED,        /* (game, iteration) pairs in which a descent was parked by select_budget */
-    AZH_STAT_REROOT_SPILLS  /* re-roots whose breadth-first frontier outgrew its LDS queue (the rest went through HBM) */
+    AZH_STAT_REROOT_SPILLS, /* re-roots whose breadth-first frontier outgrew its LDS queue (the rest went through HBM) */
+    AZH_STAT_COLLISIONS     /* leaf-parallel search: paths that ended at a node created earlier in their batch */
 };
 
 typedef struct {
@@ -239,6 +241,23 @@ int azh_engine_sync(azh_engine *e);
 /* change the root-visit threshold (global_visits) for the coming moves; 1 <= visits <= the
  * value the engine was created with */
 int azh_engine_set_visits(azh_engine *e, int visits);
+/* Leaf-parallel search (an extension; the reference searches one leaf per tree at a time): every game selects up to
+ * `leaves_per_game` = K leaves per iteration (1 <= K <= 64), spread over different lines by a virtual loss of
+ * `virtual_loss` visits (1 .. 16) on every edge an earlier path of the batch took; the leaves of all games are evaluated
+ * in one tower launch (slots g K + p; the thin tower while G K <= AZH_THIN_MAX_GAMES) and every path is backed up before
+ * the next select.  Definition: DESIGN.md, "Leaf-parallel search".  Call before the first select or between iterations;
+ * K = 1 restores the one-leaf search exactly.  K > 1 is refused with AZH_FLAG_TWO_NETS, AZH_FLAG_EVAL_CACHE,
+ * AZH_FLAG_SYMMETRY_AVG and select_budget > 0.  With K > 1, azh_engine_select / _eval / _backup / _run work on the
+ * batch, azh_engine_leaves / _set_evals / _leaf_features / _tree_stamps return an error (their buffers are G-sized): use
+ * the two calls below. */
+int azh_engine_set_leaf_batch(azh_engine *e, int leaves_per_game, int virtual_loss);
+/* kind [G K] (AZH_LEAF_NONE for an empty slot, _EVAL, _TERMINAL, _ROOT, _COLLISION), leaf_boards [G K][2] (mover,
+ * opponent; zero unless the slot needs the net), leaf_edge [G K] (the last edge of the slot's path, 0xFFFFFFFF: none);
+ * any pointer may be NULL */
+int azh_engine_batch_leaves(azh_engine *e, int32_t *kind, uint64_t *leaf_boards, uint32_t *leaf_edge);
+/* evaluations of the batch from outside, by slot: logits [G K][833], values [G K] */
+int azh_engine_set_batch_evals(azh_engine *e, const float *logits, const float *values);
+
 /* Which tower the device-resident loop evaluates its leaves with: 0 the 3-board workgroups (throughput), 1 one board per
  * workgroup (latency: azh_net_forward_thin's kernel), -1 (default) by the engine's size — thin for engines of at most
  * AZH_THIN_MAX_GAMES game slots.  A host that knows its batch has thinned out (a match under a game limit whose last games

@@ -1,0 +1,198 @@
+"""Leaf-parallel search with virtual loss on the MI355X (azh_engine_set_leaf_batch): every iteration of the HIP engine
+equals the numpy restatement (tests/vl_reference.py), the device loop equals host stepping, K = 1 is today's search, and
+the UAI front-end searches exactly the visits it is asked for."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from ataxxzero_amd import link, model
+from oracle import oracle_lib as orc
+from tests import helpers
+from tests import vl_reference as vlr
+
+pytestmark = pytest.mark.gpu
+
+ROOT = helpers.ROOT
+UAI = link.FLAG_NO_REUSE | link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR
+
+
+def _positions(G, blockers):
+    """G distinct unfinished fixture positions of the given blocker set, the last one near the end of its game."""
+    name = "rules_block4.json.gz" if blockers else "rules_noblock.json.gz"
+    out = []
+    for rec in helpers.load_gz(name):
+        p = orc.pos_from_fen(rec["fen"])
+        if orc.result(p) != 0 or len(orc.movegen(p)) == 0:
+            continue
+        empty = 49 - bin(int(p.pieces[0]) | int(p.pieces[1]) | int(p.blockers)).count("1")
+        out.append((empty, [int(p.pieces[0]) | (p.turn << 63), int(p.pieces[1])]))
+    out.sort(key=lambda t: -t[0])
+    picks = [out[i * (len(out) // (2 * G + 1))][1] for i in range(G - 1)] + [min(out, key=lambda t: t[0])[1]]
+    return np.array(picks, dtype=np.uint64)
+
+
+def _engine(G, K, VL, flags, blockers=0, visits=300, seed=11):
+    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
+    cfg = link.Config(games=G, visits=visits, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
+                      dirichlet_weight=0.0 if flags else 0.25, start_turn=0, seed=seed, start_x=int(p.pieces[0]),
+                      start_o=int(p.pieces[1]), blockers=blockers, flags=flags)
+    e = link.Engine(cfg)
+    e.set_positions(_positions(G, blockers), np.full(G, 10, np.int32))
+    e.set_leaf_batch(K, VL)
+    return e, cfg
+
+
+CASES = [  # (G, K, VL, flags, blockers)
+    (1, 2, 1, UAI, 0), (1, 64, 3, UAI, 0), (1, 16, 3, 0, 0), (5, 7, 3, 0, 0), (5, 16, 1, UAI, 0), (5, 64, 1, 0, 0),
+    (5, 2, 3, UAI, 0), (5, 16, 3, 0, helpers.BLOCK4_MASK),
+]
+SEEN = {"collision": 0, "terminal": 0, "truncated": 0}
+
+
+@pytest.mark.parametrize("G,K,VL,flags,blockers", CASES)
+def test_every_iteration_equals_the_restatement(G, K, VL, flags, blockers):
+    e, cfg = _engine(G, K, VL, flags, blockers)
+    done = np.zeros(G, bool)
+    for _ in range(400):
+        pre = [e.tree(g) for g in range(G)]
+        st = [e.game_state(g) for g in range(G)]
+        e.select()
+        kind, lb, le = e.batch_leaves()
+        batches = {}
+        for g in range(G):
+            if st[g].phase == 1 and not done[g]:
+                b = vlr.select(pre[g], st[g].root_visits, cfg.visits, K, VL, cfg.c_puct, bool(flags & 2), blockers)
+                k = len(b.kind)
+                assert list(kind[g, :k]) == b.kind and (kind[g, k:] == 0).all()
+                assert list(le[g, :k]) == b.leaf_edge
+                assert [tuple(int(v) for v in x) for x in lb[g, :k]] == b.leaf_board
+                batches[g] = b
+                SEEN["collision"] += b.kind.count(vlr.LEAF_COLLISION)
+                SEEN["terminal"] += b.kind.count(vlr.LEAF_TERMINAL)
+                SEEN["truncated"] += int(k < K and st[g].root_visits + k == cfg.visits)
+            elif st[g].phase == 0:
+                assert kind[g, 0] == vlr.LEAF_ROOT and (kind[g, 1:] == 0).all()
+        logits, values = helpers.synthetic_evals_distinct(lb.reshape(-1, 2))
+        e.set_batch_evals(logits, values)
+        e.backup()
+        for g, b in batches.items():
+            post = e.tree(g)
+            exp, added = vlr.expected_tree(b, values[g * K:(g + 1) * K], post)
+            for a, x in zip(exp, post):
+                assert a.shape == x.shape and (a == x).all()
+            assert e.game_state(g).root_visits == st[g].root_visits + added
+            if st[g].root_visits + added >= cfg.visits:
+                done[g] = True  # the move is due: the next select plays it
+        if done.all():
+            break
+    assert done.all()
+    e.close()
+
+
+def test_the_matrix_met_collisions_terminal_paths_and_truncation():
+    assert SEEN["collision"] > 0 and SEEN["terminal"] > 0 and SEEN["truncated"] > 0, SEEN
+
+
+def _net(blocks=2, seed=3):
+    conv, bn = model.random_init(blocks, 128, seed=seed, perturb_bn=True)
+    return link.Net(conv, bn)
+
+
+def _dump(e):
+    return [e.game_state(g).as_tuple() for g in range(e.G)], [e.tree(g) for g in range(e.G)]
+
+
+@pytest.mark.parametrize("G,K,dtype", [(3, 16, link.DTYPE_F32), (3, 16, link.DTYPE_F16), (9, 64, link.DTYPE_BF16)])
+def test_device_loop_equals_host_stepping(G, K, dtype):
+    net = _net()
+    n = 40
+    a, _ = _engine(G, K, 2, 0, visits=200)
+    b, _ = _engine(G, K, 2, 0, visits=200)
+    a.run(net, n, dtype)
+    a.sync()
+    for _ in range(n):
+        b.select()
+        b.eval(net, dtype)
+        b.backup()
+    sa, ta = _dump(a)
+    sb, tb = _dump(b)
+    assert sa == sb
+    for x, y in zip(ta, tb):
+        for u, v in zip(x, y):
+            assert (u == v).all()
+    assert a.stats() == b.stats() and a.collisions() == b.collisions()
+    assert a.stats()["plies"] > 0  # moves were played inside the loop (re-roots under K leaves per game)
+    a.close(), b.close()
+
+
+def test_k1_through_the_new_call_is_the_one_leaf_search_and_bad_combinations_fail():
+    net = _net()
+    a, _ = _engine(4, 1, 1, 0)
+    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
+    cfg = link.Config(games=4, visits=300, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
+                      dirichlet_weight=0.25, start_turn=0, seed=11, start_x=int(p.pieces[0]), start_o=int(p.pieces[1]),
+                      blockers=0, flags=0)
+    b = link.Engine(cfg)
+    b.set_positions(_positions(4, 0), np.full(4, 10, np.int32))
+    a.set_leaf_batch(8, 2)   # there and back again, between iterations
+    a.set_leaf_batch(1, 1)
+    a.run(net, 30, link.DTYPE_BF16)
+    b.run(net, 30, link.DTYPE_BF16)
+    sa, ta = _dump(a)
+    sb, tb = _dump(b)
+    assert sa == sb and all((u == v).all() for x, y in zip(ta, tb) for u, v in zip(x, y))
+    # errors: the G-sized calls under K > 1, unsupported flags and budgets, bounds
+    a.set_leaf_batch(4, 1)
+    with pytest.raises(link.AzhError):
+        a.leaves()
+    with pytest.raises(link.AzhError):
+        a.set_evals(np.zeros((4, 833), np.float32), np.zeros(4, np.float32))
+    for bad in [(0, 1), (65, 1), (4, 0), (4, 17)]:
+        with pytest.raises(link.AzhError):
+            a.set_leaf_batch(*bad)
+    for flags, budget in [(link.FLAG_TWO_NETS, 0), (link.FLAG_EVAL_CACHE, 0), (0, 4)]:
+        cfg.flags, cfg.select_budget = flags, budget
+        c = link.Engine(cfg)
+        with pytest.raises(link.AzhError):
+            c.set_leaf_batch(8, 1)
+        c.set_leaf_batch(1, 1)
+        c.close()
+    a.close(), b.close()
+
+
+def _npy(tmp_path):
+    conv, bn = model.random_init(2, 128, seed=5, perturb_bn=True)
+    path = str(tmp_path / "net.npy")
+    model.save_model(path, conv, bn)
+    return path
+
+
+def test_searcher_visits_sum_exactly(tmp_path):
+    from ataxxzero_amd import uai
+    s = uai.Searcher(_npy(tmp_path), dtype="f16", parallel_leaves=16)
+    edges = s.root_visits(uai.Position.initial(), visits=200)
+    assert sum(n for _, n in edges) == 200 and s.last_steps == 200
+    edges = s.root_visits(uai.Position.initial(), seconds=0.05)
+    assert sum(n for _, n in edges) == s.last_steps > 16
+
+
+def test_cli_parallel_leaves_plays_legal_moves(tmp_path):
+    net = _npy(tmp_path)
+    script = "uai\nisready\nposition fen x5o/7/7/7/7/7/o5x x\ngo movetime 200\nmoves g2\ngo movetime 200\nquit\n"
+    env = dict(os.environ)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "uai_interface.py"), "--network-path", net,
+                          "--parallel-leaves", "16", "--virtual-loss", "2", "--visits", "64"],
+                         input=script, capture_output=True, text=True, timeout=120, cwd=ROOT, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    best = [l.split()[1] for l in out.stdout.splitlines() if l.startswith("bestmove")]
+    assert len(best) == 2
+    from ataxxzero_amd import uai
+    pos = uai.Position.initial()
+    legal, _ = pos.legal_moves()
+    assert uai.decode_move(best[0]) in legal
+    pos.move(uai.decode_move("g2"))
+    legal, _ = pos.legal_moves()
+    assert uai.decode_move(best[1]) in legal

@@ -20,7 +20,8 @@ __all__ = ["uai_encode_square", "uai_encode_move", "uai_decode_square", "uai_dec
 def main(options):
     from ataxxzero_amd import selfplay, uai
     selfplay.select_device(0)
-    searcher = uai.Searcher(options.network_path, dtype=options.dtype, symmetry_average=options.symmetry_average)
+    searcher = uai.Searcher(options.network_path, dtype=options.dtype, symmetry_average=options.symmetry_average,
+                            parallel_leaves=options.parallel_leaves, virtual_loss=options.virtual_loss)
     session = uai.Session(searcher, visits=options.visits, safety_ms=options.safety_ms, show_game=options.show_game,
                           log=sys.stderr)
     session.serve(sys.stdin, sys.stdout)
@@ -33,6 +34,11 @@ if __name__ == "__main__":
     cli.add_argument("--safety-ms", type=int, default=0, metavar="MS", help="margin subtracted from every movetime")
     cli.add_argument("--show-game", action="store_true", help="echo positions set by `position fen` to stderr")
     cli.add_argument("--symmetry-average", action="store_true", help="evaluate every position as the mean over its 8 dihedral images (nn_evals.py:48-62; extension)")
+    cli.add_argument("--parallel-leaves", type=int, default=1, metavar="K",
+                     help="leaves per search iteration, 1..64, spread by a virtual loss and evaluated in one tower launch "
+                          "(extension; 1 = the reference's one-leaf search)")
+    cli.add_argument("--virtual-loss", type=int, default=1, metavar="V",
+                     help="visits of virtual loss per path on every edge it takes, 1..16 (with --parallel-leaves > 1)")
     cli.add_argument("--dtype", default="f16", choices=["bf16", "f16", "f32"],
                      help="tower arithmetic (extension).  Match play defaults to f16: with a trained net the f16 search picks "
                           "the f32 search's move in 100 %% of test positions, bf16 in 96 %% (DESIGN.md section 5); bf16 is 3-6 %% faster")
