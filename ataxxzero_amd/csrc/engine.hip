@@ -10,6 +10,8 @@
 //   mark_game     "is the move due?"            generate_game :522-525
 //   advance_game  sample, record, re-root       sample_proportionally_to_visits :495-506,
 //                                               generate_game :526-578, MCTS::play :475-492
+//   k_play_moves  a move the host names          MCTS.play, engine.py:411-424 (the same re-root: reroot_game)
+//   k_root_report root edges, principal line     MCTSEngine.genmove's report, engine.py:474-530
 // Each game contributes exactly one leaf per search iteration, so the per-iteration evaluation
 // batch is the number of concurrent games.  The device-resident loop (run_loop) runs an
 // iteration as TWO launches on one stream — the fused tower, then k_tree = backup + mark + the
@@ -838,6 +840,179 @@ __global__ __launch_bounds__(WAVE) void k_advance_list(EngineParams P)
     }
 }
 
+// azh_engine_play_moves: the host names the move of every game (0xFFFF: none), one wave per game.  The move is looked up
+// among the root's edges and played through reroot_game — the re-root of advance_game without its sampling, its ply record
+// and its game bookkeeping: no random number, no record, AZH_STAT_PLIES untouched, and the game never becomes a line
+// (no_emit, as a loaded position).  A game whose own move was due (phase 2) stays in the move queue until
+// k_unqueue_played, launched behind this kernel, takes it out.
+__global__ __launch_bounds__(WAVE) void k_play_moves(EngineParams P, const u16 *moves, int *status)
+{
+    __shared__ TreeLds L;
+    const int g = blockIdx.x, lane = lane_id();
+    const u32 want = moves[g];
+    if (want == 0xFFFFu) {
+        if (lane == 0)
+            status[g] = AZH_PLAY_NONE;
+        return;
+    }
+    azh_game_state s = P.gs[g];
+    if (s.phase == 3) {
+        if (lane == 0)
+            status[g] = AZH_PLAY_BUSY;
+        return;
+    }
+    Arena A = arena_of(P, s.arena, g);
+    Arena B = arena_of(P, 1 - s.arena, g);
+    const uint4 rinfo = A.ni[0];
+    const u32 first = rinfo.x;
+    const int M = (int)(rinfo.y & 0xFFFFu);  // (0 at a finished root: every move is refused)
+    int chosen = -1;
+    u32 child = ENONE;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int j = lane + 64 * k;
+        u32 ch = ENONE;
+        bool hit = false;
+        if (j < M) {
+            hit = (u32)A.em[first + j] == want;
+            ch = edge_child(A.ed[first + j]);
+        }
+        const u64 mask = __ballot(hit);
+        if (chosen < 0 && mask) {
+            const int l = __ffsll((long long)mask) - 1;
+            chosen = 64 * k + l;
+            child = (u32)read_lane((int)ch, l);
+        }
+    }
+    if (chosen < 0) {
+        if (lane == 0)
+            status[g] = AZH_PLAY_ILLEGAL;
+        return;
+    }
+    const u32 c = (P.flags & AZH_FLAG_NO_REUSE) ? ENONE : child;
+    RerootStats rs;
+    const int result = reroot_game(P, g, L, s, A, B, A.nb[0], want, c, rs);
+    s.ply = min(s.ply, P.max_plies - 1);
+    s.phase = result != 0 ? 3 : 0;
+    s.leaf_kind = AZH_LEAF_NONE;  // (a descent parked by select_budget is given up with the tree it was in)
+    s.leaf_node = 0;
+    s.path_len = 0;
+    if (lane == 0) {
+        P.force[g] = 0;
+        P.no_emit[g] = s.ply + 1;
+        P.gs[g] = s;
+        status[g] = result != 0 ? AZH_PLAY_FINISHED : (c == ENONE ? AZH_PLAY_FRESH : AZH_PLAY_KEPT);
+    }
+    const u64 inc = lane == AZH_STAT_REROOT_NODES ? rs.nodes
+                  : lane == AZH_STAT_REROOT_EDGES ? rs.edges
+                  : lane == AZH_STAT_REROOT_SPILLS ? rs.spill : 0ull;
+    if (lane < NSTAT)
+        add_stat(P, g, lane, inc);
+}
+
+// Behind k_play_moves: the move queue keeps, in their order, the games whose own move is still due (one wave).
+__global__ __launch_bounds__(WAVE) void k_unqueue_played(EngineParams P)
+{
+    const int lane = lane_id();
+    const int n = *P.adv_count;
+    const u64 lt = (1ULL << lane) - 1ULL;
+    int kept = 0;
+    for (int base = 0; base < n; base += WAVE) {
+        const int i = base + lane;
+        int g = 0;
+        bool keep = false;
+        if (i < n) {
+            g = P.adv_list[i];
+            keep = P.gs[g].phase == 2;
+        }
+        const u64 mask = __ballot(keep);  // (every lane's load has returned: the stores below land at or before `base`)
+        if (keep)
+            P.adv_list[kept + __popcll(mask & lt)] = g;
+        kept += __popcll(mask);
+    }
+    if (lane == 0)
+        *P.adv_count = kept;
+}
+
+// azh_engine_root_report: one wave per game writes the fixed-size record the header documents — the root's edges and
+// the principal variation.  The walk is a dependent chain of at most AZH_PV_MAX levels: once per `go`, not per iteration.
+__global__ __launch_bounds__(WAVE) void k_root_report(EngineParams P, int first_game, u32 *out)
+{
+    const int g = first_game + (int)blockIdx.x, lane = lane_id();
+    u32 *rec = out + (size_t)blockIdx.x * AZH_ROOT_REPORT_WORDS;
+    const azh_game_state s = P.gs[g];
+    Arena A = arena_of(P, s.arena, g);
+    const uint4 rinfo = A.ni[0];
+    const int M = min((int)(rinfo.y & 0xFFFFu), AZH_MAX_MOVES);
+    int expanded = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int j = lane + 64 * k;
+        uint4 row = make_uint4(0u, 0u, 0u, 0u);
+        bool has = false;
+        if (j < M) {
+            const uint4 ev = A.ed[rinfo.x + j];
+            row = make_uint4((u32)A.em[rinfo.x + j], edge_visits(ev), ev.y, ev.x & PRIOR_MASK);
+            has = edge_child(ev) != ENONE;
+        }
+        u32 *r = rec + 4 + 4 * j;  // (records are AZH_ROOT_REPORT_WORDS apart: word stores, no 16-byte alignment)
+        r[0] = row.x; r[1] = row.y; r[2] = row.z; r[3] = row.w;
+        expanded += __popcll(__ballot(has));
+    }
+    if (lane == 0) {
+        rec[0] = (u32)s.root_visits;
+        rec[1] = (u32)M;
+        rec[2] = (u32)expanded;
+        rec[3] = rinfo.y >> 16;
+    }
+    // principal variation: lane d keeps the pair of depth d
+    u32 pv_move = 0, pv_n = 0;
+    int len = 0;
+    u32 kid = pack_kid(rinfo.x, (u32)M, (rinfo.y >> 16) != 0u);
+    while (len < AZH_PV_MAX && !kid_finished(kid) && kid_count(kid) > 0) {
+        const u32 first = kid_first(kid);
+        const int Mk = kid_count(kid);
+        u64 key = 0;
+        u32 mine_z = ENONE << 16, mine_w = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int j = lane + 64 * k;
+            if (j < Mk) {
+                const uint4 ev = A.ed[first + j];
+                const u64 kj = ((u64)edge_visits(ev) << 32) | (u64)(0xFFFFFFFFu - (u32)j);  // most visits, first on a tie
+                if (kj > key) {
+                    key = kj;
+                    mine_z = ev.z;
+                    mine_w = ev.w;
+                }
+            }
+        }
+        key = wave_max_u64(key);
+        const u32 n = (u32)(key >> 32);
+        if (n == 0u)
+            break;
+        const int bj = (int)(0xFFFFFFFFu - (u32)key);
+        const u32 z = (u32)read_lane((int)mine_z, bj & 63);
+        const u32 w = (u32)read_lane((int)mine_w, bj & 63);
+        const u32 mv = A.em[first + (u32)bj];
+        if (lane == len) {
+            pv_move = mv;
+            pv_n = n;
+        }
+        len++;
+        if ((z >> 16) == ENONE)
+            break;
+        kid = w;
+    }
+    u32 *pv = rec + AZH_ROOT_REPORT_PV;
+    if (lane == 0)
+        pv[0] = (u32)len;
+    if (lane < AZH_PV_MAX) {
+        pv[1 + 2 * lane] = pv_move;
+        pv[2 + 2 * lane] = pv_n;
+    }
+}
+
 // The dense, game-ordered leaf list(s) of k_compact, written inside the tree launch by the workgroup that finishes
 // last.  Every workgroup ORs its games' need bits into a bit mask (one returning agent-scope atomic per workgroup,
 // performed before it draws its ticket from an agent-scope counter); the workgroup whose ticket is the last reads the
@@ -1035,6 +1210,9 @@ struct azh_engine {
     std::vector<void *> allocs;
     float *d_feat = nullptr;
     float *d_sym_logits = nullptr, *d_sym_values = nullptr;  // AZH_FLAG_SYMMETRY_AVG scratch
+    u16 *d_play_moves = nullptr;   // azh_engine_play_moves: moves [G] and status [G], allocated by the first call
+    int *d_play_status = nullptr;
+    u32 *d_report = nullptr;       // azh_engine_root_report: [G][AZH_ROOT_REPORT_WORDS], allocated by the first call
     u64 *d_stat_out = nullptr;
     // finished games formatted but not yet handed out
     std::vector<std::string> pending;
@@ -1810,6 +1988,42 @@ extern "C" int azh_engine_set_positions(azh_engine *e, const uint64_t *boards, c
     (void)hipFree(d_b);
     (void)hipFree(d_p);
     AZH_HIP(rc);
+    return 0;
+}
+
+// The host names the move of every slot (moves [G], 0xFFFF: none); status_out [G] = AZH_PLAY_*.  Definition: the header.
+extern "C" int azh_engine_play_moves(azh_engine *e, const uint16_t *moves, int32_t *status_out)
+{
+    if (!e || !moves || !status_out)
+        return azh_fail(-1, "azh_engine_play_moves: null argument");
+    if (e->selected)
+        return azh_fail(-3, "azh_engine_play_moves: a selected batch awaits its backup");
+    if (e->P.flags & AZH_FLAG_TWO_NETS)
+        return azh_fail(-4, "azh_engine_play_moves: not available on AZH_FLAG_TWO_NETS engines");
+    const size_t G = (size_t)e->P.G;
+    if (!e->d_play_moves && (dev_alloc(e, &e->d_play_moves, G) || dev_alloc(e, &e->d_play_status, G)))
+        return -1;
+    AZH_HIP(hipStreamSynchronize(e->stream2));  // (side-stream re-roots of an earlier run)
+    AZH_HIP(hipMemcpyAsync(e->d_play_moves, moves, G * sizeof(u16), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_play_moves, dim3(e->P.G), dim3(WAVE), 0, e->stream, e->P, (const u16 *)e->d_play_moves, e->d_play_status);
+    hipLaunchKernelGGL(k_unqueue_played, dim3(1), dim3(WAVE), 0, e->stream, e->P);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipMemcpyAsync(status_out, e->d_play_status, G * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// Root edges and principal variation of n_games slots: n_games records of AZH_ROOT_REPORT_WORDS u32 (layout: the header).
+extern "C" int azh_engine_root_report(azh_engine *e, int first_game, int n_games, uint32_t *out)
+{
+    if (!e || !out || first_game < 0 || n_games < 1 || first_game > e->P.G - n_games)
+        return azh_fail(-1, "azh_engine_root_report: bad argument");
+    if (!e->d_report && dev_alloc(e, &e->d_report, (size_t)e->P.G * AZH_ROOT_REPORT_WORDS))
+        return -1;
+    hipLaunchKernelGGL(k_root_report, dim3(n_games), dim3(WAVE), 0, e->stream, e->P, first_game, e->d_report);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipMemcpyAsync(out, e->d_report, (size_t)n_games * AZH_ROOT_REPORT_WORDS * 4, hipMemcpyDeviceToHost, e->stream));
+    AZH_HIP(hipStreamSynchronize(e->stream));
     return 0;
 }
 

@@ -1,6 +1,6 @@
 // Device code of the search engine that more than one translation unit compiles: the engine's parameter block, the HBM
-// layout helpers of the tree arenas, game start, and the ply advance (sample the move, record the ply, re-root, finish or
-// restart the game).  engine.hip owns the tree kernels; net_kernels.hip compiles advance_game too, because the device-resident
+// layout helpers of the tree arenas, game start, the re-root (reroot_game: also behind the moves a host names, k_play_moves in
+// engine.hip) and the ply advance (sample the move, record the ply, re-root, finish or restart the game).  engine.hip owns the tree kernels; net_kernels.hip compiles advance_game too, because the device-resident
 // loop plays the queued moves INSIDE the tower launch (advance_worker below, round 6): the tower leaves no wave slot and no
 // LDS beside itself, so a re-root launch on a side stream waited most of its life for the tower's first workgroups to retire,
 // and its cross-stream events cost every iteration 7-10 us whether or not a move was due (profiles/round6_reroots_in_the_tower_launch.txt).
@@ -240,24 +240,168 @@ __device__ inline void init_game(const EngineParams &P, int g, u32 uid, azh_game
 
 constexpr u32 PRIOR_MASK = 0x7FFFFFFFu;  // the prior proper (AZH_HINT_SIGN: bit 31 marks the remembered child)
 
+// ------------------------------------------------------------------ re-root
+
+struct RerootStats {
+    u64 nodes = 0, edges = 0, spill = 0;  // AZH_STAT_REROOT_NODES / _EDGES / _SPILLS of this re-root
+};
+
+// The root edge with move `mv` has been played: the tree of the position after it is built in the other arena B — the
+// subtree of the edge's child `c` with its counts and priors, or (c == ENONE: no child, or a tree that is not kept) a
+// fresh one-node tree — the evaluation cache's table of that arena is rebuilt, the arenas flip and the ply goes up.
+// `rootw`: the root's packed board.  Returns the adjudication of the new root (0: not finished).  Used by advance_game
+// (the move the device sampled) and by k_play_moves (a move the host names, engine.hip).
+__device__ inline int reroot_game(const EngineParams &P, int g, TreeLds &L, azh_game_state &s, const Arena &A, const Arena &B,
+                                  const ulonglong2 rootw, u32 mv, u32 c, RerootStats &st)
+{
+    u16 *s_moves = L.moves;
+    u32 *s_old = L.old, *s_pref = L.pref;
+    u32 *spill = P.bfs_spill + (size_t)g * 3 * P.node_cap;
+    const int node_cap = P.node_cap;
+    // frontier queue accessors: LDS for the first BFS_QL nodes, HBM beyond
+    auto q_put = [&](u32 i, u32 a, u32 b, u32 d) {
+        if (i < (u32)BFS_QL) {
+            L.q[0][i] = a; L.q[1][i] = b; L.q[2][i] = d;
+        } else {
+            spill[i] = a; spill[node_cap + i] = b; spill[2 * node_cap + i] = d;
+        }
+    };
+    auto q_get = [&](u32 i, int f) -> u32 { return i < (u32)BFS_QL ? L.q[f][i] : spill[(size_t)f * node_cap + i]; };
+    const int lane = lane_id();
+    const u64 lt = (1ULL << lane) - 1ULL;
+    // MCTS::play (:475-492): keep the chosen child's subtree, compacted breadth-first
+    // into the other arena (children keep their edge order).
+    int result;
+    if (c == ENONE) {
+        // miss: fresh tree from the position after the move (:479-483)
+        const Board nbrd = make_move(unpack_board(rootw.x, rootw.y), (int)(mv & 0xFF), (int)(mv >> 8));
+        const int Mn = wave_movegen(nbrd, P.blockers, s_moves, &result);
+        wave_sync();
+        const int Mw = result != 0 ? 0 : Mn;
+        for (int j = lane; j < Mw; j += WAVE) {
+            B.ed[j] = fresh_edge(0u);
+            B.em[j] = s_moves[j];
+        }
+        if (lane == 0) {
+            float tv = result == 1 ? 1.0f : -1.0f;
+            if (nbrd.turn == 1)
+                tv = -tv;
+            B.nb[0] = make_ulonglong2(pack_word0(nbrd), nbrd.o);
+            B.ni[0] = result != 0 ? make_uint4(0u, (u32)result << 16, 0u, f2u(tv)) : make_uint4(0u, (u32)Mw, 0u, 0u);
+        }
+        s.n_nodes = 1;
+        s.n_edges = Mw;
+        s.root_visits = 0;
+    } else {
+        const uint4 cinfo = A.ni[c];
+        result = (int)(cinfo.y >> 16);
+        // Breadth-first copy, up to 64 frontier nodes per pass.  Nodes are numbered in
+        // (parent order, edge order) and a node's edges land at the running edge count,
+        // exactly as the node-at-a-time loop of the oracle does, so the compacted arena is
+        // bit-identical.  The frontier (old node id, old edge range, parent edge) is queued in
+        // LDS when a child is discovered — its edge range is part of the edge that leads to it —
+        // so one pass costs ONE dependent memory round trip.
+        u32 t = 1, eb = 0, rv = 0, qs = 0;
+        if (lane == 0)
+            q_put(0u, c, pack_kid(cinfo.x, cinfo.y & 0xFFFFu, (cinfo.y >> 16) != 0u), 0u);
+        wave_sync();
+        while (qs < t) {
+            const u32 nchunk = min(t - qs, (u32)WAVE);
+            u32 of = 0, Mq = 0, kw = 0, old = 0, pe = 0;
+            if ((u32)lane < nchunk) {
+                old = q_get(qs + lane, 0);
+                kw = q_get(qs + lane, 1);
+                pe = q_get(qs + lane, 2);
+                of = kid_first(kw);
+                Mq = (u32)kid_count(kw);
+            }
+            const u32 incl = (u32)wave_incl_scan((int)Mq);
+            const u32 Ef = (u32)bcast_last((int)incl);
+            if ((u32)lane < nchunk) {
+                const u32 nf = Mq ? eb + incl - Mq : 0u;
+                s_old[lane] = of;
+                s_pref[lane] = incl - Mq;
+                // node copy: not on the dependent chain (nothing below waits for these loads)
+                B.nb[qs + lane] = A.nb[old];
+                const uint4 oinfo = A.ni[old];
+                B.ni[qs + lane] = make_uint4(nf, oinfo.y, 0u, oinfo.w);
+                if (qs + lane > 0)  // the edge that leads here was copied in an earlier pass: now it learns the new range
+                    reinterpret_cast<u32 *>(&B.ed[pe])[3] = pack_kid(nf, Mq, kid_finished(kw));
+            }
+            if (lane == 0)
+                s_pref[nchunk] = Ef;
+            wave_sync();
+            for (u32 e0 = 0; e0 < Ef; e0 += WAVE) {
+                const u32 e = e0 + (u32)lane;
+                const bool valid = e < Ef;
+                uint4 ed = fresh_edge(0u);
+                u16 m = 0;
+                if (valid) {
+                    u32 lo = 0, hi = nchunk;  // largest i with s_pref[i] <= e
+                    while (hi - lo > 1) {
+                        const u32 mid = (lo + hi) >> 1;
+                        if (s_pref[mid] <= e) lo = mid;
+                        else hi = mid;
+                    }
+                    const u32 src = s_old[lo] + (e - s_pref[lo]);
+                    ed = A.ed[src];
+                    m = A.em[src];
+                    if (qs == 0 && lo == 0)
+                        rv += edge_visits(ed);
+                }
+                const bool has = valid && edge_child(ed) != ENONE;
+                const u64 mask = __ballot(has);
+                const u32 dst = eb + e;
+                if (has) {
+                    const u32 nc = t + (u32)__popcll(mask & lt);
+                    q_put(nc, edge_child(ed), ed.w, dst);
+                    ed.z = (ed.z & 0xFFFFu) | (nc << 16);  // (ed.w still names the OLD range: rewritten when the child is copied)
+                }
+                if (valid) {
+                    B.ed[dst] = ed;
+                    B.em[dst] = m;
+                }
+                t += (u32)__popcll(mask);
+            }
+            eb += Ef;
+            qs += nchunk;
+            wave_sync();
+        }
+        s.n_nodes = (int)t;
+        s.n_edges = (int)eb;
+        s.root_visits = (int)wave_sum_u32(rv);
+        st.nodes = t;
+        st.edges = eb;
+        st.spill = t > (u32)BFS_QL ? 1 : 0;
+    }
+    if (P.flags & AZH_FLAG_EVAL_CACHE) {
+        // the kept subtree's evaluations stay usable: rebuild the table of the new arena from its nodes (all but the
+        // root, whose priors are about to get this ply's noise; finished positions carry no priors)
+        u32 *tt = tt_of(P, 1 - s.arena, g);
+        tt_clear(tt, P.tt_size);
+        __threadfence();
+        wave_sync();
+        for (u32 n = 1u + (u32)lane; n < (u32)s.n_nodes; n += WAVE) {
+            const uint4 info = B.ni[n];
+            if ((info.y >> 16) == 0u && (info.y & 0xFFFFu) != 0u) {
+                const ulonglong2 b = B.nb[n];
+                tt_insert(tt, (u32)P.tt_size - 1u, b.x, b.y, n);
+            }
+        }
+    }
+    s.arena = 1 - s.arena;
+    s.ply += 1;
+    wave_sync();
+    return result;
+}
+
 // ------------------------------------------------------------------ ply advance
 
 __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
 {
     u16 *s_moves = L.moves;
-    u32 *s_old = L.old, *s_pref = L.pref;
+    u32 *s_pref = L.pref;
     u64 *s_w = L.w;
-    u32 *spill = P.bfs_spill + (size_t)g * 3 * P.node_cap;
-    const int node_cap = P.node_cap;
-    // frontier queue accessors: LDS for the first BFS_QL nodes, HBM beyond
-    auto q_put = [&](u32 i, u32 a, u32 b, u32 c) {
-        if (i < (u32)BFS_QL) {
-            L.q[0][i] = a; L.q[1][i] = b; L.q[2][i] = c;
-        } else {
-            spill[i] = a; spill[node_cap + i] = b; spill[2 * node_cap + i] = c;
-        }
-    };
-    auto q_get = [&](u32 i, int f) -> u32 { return i < (u32)BFS_QL ? L.q[f][i] : spill[(size_t)f * node_cap + i]; };
     const int lane = lane_id();
     azh_game_state s = P.gs[g];
     // while (root.all_edge_visits < global_visits) step();  (:522-525)
@@ -389,130 +533,10 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
         rec[7] = 0;
     }
 
-    // MCTS::play (:475-492): keep the chosen child's subtree, compacted breadth-first
-    // into the other arena (children keep their edge order).
-    int result;
-    u64 st_nodes = 0, st_edges = 0, st_spill = 0;
-    if (c == ENONE) {
-        // miss: fresh tree from the position after the move (:479-483)
-        const Board nbrd = make_move(unpack_board(rootw.x, rootw.y), (int)(mv & 0xFF), (int)(mv >> 8));
-        const int Mn = wave_movegen(nbrd, P.blockers, s_moves, &result);
-        wave_sync();
-        const int Mw = result != 0 ? 0 : Mn;
-        for (int j = lane; j < Mw; j += WAVE) {
-            B.ed[j] = fresh_edge(0u);
-            B.em[j] = s_moves[j];
-        }
-        if (lane == 0) {
-            float tv = result == 1 ? 1.0f : -1.0f;
-            if (nbrd.turn == 1)
-                tv = -tv;
-            B.nb[0] = make_ulonglong2(pack_word0(nbrd), nbrd.o);
-            B.ni[0] = result != 0 ? make_uint4(0u, (u32)result << 16, 0u, f2u(tv)) : make_uint4(0u, (u32)Mw, 0u, 0u);
-        }
-        s.n_nodes = 1;
-        s.n_edges = Mw;
-        s.root_visits = 0;
-    } else {
-        const uint4 cinfo = A.ni[c];
-        result = (int)(cinfo.y >> 16);
-        // Breadth-first copy, up to 64 frontier nodes per pass.  Nodes are numbered in
-        // (parent order, edge order) and a node's edges land at the running edge count,
-        // exactly as the node-at-a-time loop of the oracle does, so the compacted arena is
-        // bit-identical.  The frontier (old node id, old edge range, parent edge) is queued in
-        // LDS when a child is discovered — its edge range is part of the edge that leads to it —
-        // so one pass costs ONE dependent memory round trip.
-        u32 t = 1, eb = 0, rv = 0, qs = 0;
-        if (lane == 0)
-            q_put(0u, c, pack_kid(cinfo.x, cinfo.y & 0xFFFFu, (cinfo.y >> 16) != 0u), 0u);
-        wave_sync();
-        while (qs < t) {
-            const u32 nchunk = min(t - qs, (u32)WAVE);
-            u32 of = 0, Mq = 0, kw = 0, old = 0, pe = 0;
-            if ((u32)lane < nchunk) {
-                old = q_get(qs + lane, 0);
-                kw = q_get(qs + lane, 1);
-                pe = q_get(qs + lane, 2);
-                of = kid_first(kw);
-                Mq = (u32)kid_count(kw);
-            }
-            const u32 incl = (u32)wave_incl_scan((int)Mq);
-            const u32 Ef = (u32)bcast_last((int)incl);
-            if ((u32)lane < nchunk) {
-                const u32 nf = Mq ? eb + incl - Mq : 0u;
-                s_old[lane] = of;
-                s_pref[lane] = incl - Mq;
-                // node copy: not on the dependent chain (nothing below waits for these loads)
-                B.nb[qs + lane] = A.nb[old];
-                const uint4 oinfo = A.ni[old];
-                B.ni[qs + lane] = make_uint4(nf, oinfo.y, 0u, oinfo.w);
-                if (qs + lane > 0)  // the edge that leads here was copied in an earlier pass: now it learns the new range
-                    reinterpret_cast<u32 *>(&B.ed[pe])[3] = pack_kid(nf, Mq, kid_finished(kw));
-            }
-            if (lane == 0)
-                s_pref[nchunk] = Ef;
-            wave_sync();
-            for (u32 e0 = 0; e0 < Ef; e0 += WAVE) {
-                const u32 e = e0 + (u32)lane;
-                const bool valid = e < Ef;
-                uint4 ed = fresh_edge(0u);
-                u16 m = 0;
-                if (valid) {
-                    u32 lo = 0, hi = nchunk;  // largest i with s_pref[i] <= e
-                    while (hi - lo > 1) {
-                        const u32 mid = (lo + hi) >> 1;
-                        if (s_pref[mid] <= e) lo = mid;
-                        else hi = mid;
-                    }
-                    const u32 src = s_old[lo] + (e - s_pref[lo]);
-                    ed = A.ed[src];
-                    m = A.em[src];
-                    if (qs == 0 && lo == 0)
-                        rv += edge_visits(ed);
-                }
-                const bool has = valid && edge_child(ed) != ENONE;
-                const u64 mask = __ballot(has);
-                const u32 dst = eb + e;
-                if (has) {
-                    const u32 nc = t + (u32)__popcll(mask & lt);
-                    q_put(nc, edge_child(ed), ed.w, dst);
-                    ed.z = (ed.z & 0xFFFFu) | (nc << 16);  // (ed.w still names the OLD range: rewritten when the child is copied)
-                }
-                if (valid) {
-                    B.ed[dst] = ed;
-                    B.em[dst] = m;
-                }
-                t += (u32)__popcll(mask);
-            }
-            eb += Ef;
-            qs += nchunk;
-            wave_sync();
-        }
-        s.n_nodes = (int)t;
-        s.n_edges = (int)eb;
-        s.root_visits = (int)wave_sum_u32(rv);
-        st_nodes = t;
-        st_edges = eb;
-        st_spill = t > (u32)BFS_QL ? 1 : 0;
-    }
-    if (P.flags & AZH_FLAG_EVAL_CACHE) {
-        // the kept subtree's evaluations stay usable: rebuild the table of the new arena from its nodes (all but the
-        // root, whose priors are about to get this ply's noise; finished positions carry no priors)
-        u32 *tt = tt_of(P, 1 - s.arena, g);
-        tt_clear(tt, P.tt_size);
-        __threadfence();
-        wave_sync();
-        for (u32 n = 1u + (u32)lane; n < (u32)s.n_nodes; n += WAVE) {
-            const uint4 info = B.ni[n];
-            if ((info.y >> 16) == 0u && (info.y & 0xFFFFu) != 0u) {
-                const ulonglong2 b = B.nb[n];
-                tt_insert(tt, (u32)P.tt_size - 1u, b.x, b.y, n);
-            }
-        }
-    }
-    s.arena = 1 - s.arena;
-    s.ply += 1;
-    wave_sync();
+    // MCTS::play (:475-492), the evaluation-cache rebuild, the arena flip
+    RerootStats rs;
+    const int result = reroot_game(P, g, L, s, A, B, rootw, mv, c, rs);
+    const u64 st_nodes = rs.nodes, st_edges = rs.edges, st_spill = rs.spill;
 
     u64 st_games = 0, st_dropped = 0, st_ring = 0;
     const bool cut = result == 0 && s.ply >= P.max_plies;

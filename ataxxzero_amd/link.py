@@ -32,6 +32,12 @@ FLAG_ARENA = 63
 FLAG_SYMMETRY_AVG = 128    # nn_evals.py:48-62 on every evaluation
 FLAG_ONE_RANDOM_MOVE = 64  # cpp/self_play_client.cpp:515-552 (compile-time variant of the reference client)
 FLAG_EVAL_CACHE = 256      # engine.py:127-234: positions a game's search has already evaluated are not evaluated again
+# azh_engine_play_moves / azh_engine_root_report (include/ataxxzero_hip.h)
+PLAY_NONE, PLAY_KEPT, PLAY_FRESH, PLAY_FINISHED, PLAY_ILLEGAL, PLAY_BUSY = 0, 1, 2, 3, -1, -2
+NO_MOVE = 0xFFFF            # a slot azh_engine_play_moves leaves alone
+PV_MAX = 32
+ROOT_REPORT_PV = 4 + 4 * MAX_MOVES
+ROOT_REPORT_WORDS = ROOT_REPORT_PV + 1 + 2 * PV_MAX
 STAT_NAMES = ["steps", "nn_evals", "levels", "children", "new_moves", "plies", "games", "dropped",
               "edge_overflow", "reroot_nodes", "reroot_edges", "ring_overflow", "cache_hits", "parked", "reroot_spills"]
 
@@ -55,6 +61,25 @@ class GameState(ctypes.Structure):
 
     def as_tuple(self):
         return tuple(getattr(self, n) for n, _ in self._fields_)
+
+
+class RootReport:
+    """One slot's record of azh_engine_root_report: root_visits, result (0: not finished), expanded (root edges with a
+    child), the root's edges in move generation order — moves (M,) u16, visits (M,) u32, scores (M,) f32 (total score W,
+    seen from the side to move), priors (M,) f32 — and the principal variation: pv (L,) u16 moves, pv_visits (L,) u32."""
+    __slots__ = ("root_visits", "result", "expanded", "moves", "visits", "scores", "priors", "pv", "pv_visits")
+
+    def __init__(self, words):
+        self.root_visits, m, self.expanded, self.result = (int(v) for v in words[:4])
+        rows = words[4:4 + 4 * m].reshape(m, 4)
+        self.moves = rows[:, 0].astype(np.uint16)
+        self.visits = rows[:, 1].copy()
+        self.scores = rows[:, 2].copy().view(np.float32)
+        self.priors = rows[:, 3].copy().view(np.float32)
+        n = int(words[ROOT_REPORT_PV])
+        line = words[ROOT_REPORT_PV + 1:ROOT_REPORT_PV + 1 + 2 * n].reshape(n, 2)
+        self.pv = line[:, 0].astype(np.uint16)
+        self.pv_visits = line[:, 1].copy()
 
 
 class Timing(ctypes.Structure):
@@ -105,6 +130,8 @@ SIGNATURES = {
     "azh_engine_set_leaf_batch": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
     "azh_engine_batch_leaves": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "azh_engine_set_batch_evals": (ctypes.c_int, [_vp, _vp, _vp]),
+    "azh_engine_play_moves": (ctypes.c_int, [_vp, _vp, _vp]),
+    "azh_engine_root_report": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
     "azh_engine_game_state": (ctypes.c_int, [_vp, ctypes.c_int, _P(GameState)]),
     "azh_engine_tree": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "azh_engine_tree_raw": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
@@ -441,6 +468,23 @@ class Engine:
     def set_game_limit(self, games):
         """Play uids 0 .. games - 1 only; slots past the limit go idle (call before the first iteration)."""
         check(load().azh_engine_set_game_limit(self.h, int(games)))
+
+    def play_moves(self, moves):
+        """The host names the move of every slot (u16 from | to << 8; NO_MOVE leaves the slot alone): the root edge's child
+        becomes the root with its subtree (PLAY_KEPT), or a fresh one-node tree is started (PLAY_FRESH).  -> status (G,)
+        int32 of PLAY_* (azh_engine_play_moves)."""
+        moves = np.ascontiguousarray(moves, dtype=np.uint16).reshape(self.G)
+        status = np.zeros(self.G, dtype=np.int32)
+        check(load().azh_engine_play_moves(self.h, _ptr(moves), _ptr(status)))
+        return status
+
+    def root_report(self, first=0, n=None):
+        """-> [RootReport] for the slots first .. first + n - 1 (all from `first` on by default): root edges and principal
+        variation, a few KB per slot instead of the whole tree (azh_engine_root_report)."""
+        n = self.G - first if n is None else n
+        out = np.zeros((max(n, 1), ROOT_REPORT_WORDS), dtype=np.uint32)
+        check(load().azh_engine_root_report(self.h, int(first), int(n), _ptr(out)))
+        return [RootReport(out[i]) for i in range(n)]
 
     def game_state(self, g):
         s = GameState()

@@ -7,6 +7,12 @@ the reference engine ends up with when a UAI master sends one `moves` message pe
 (engine.set_state, engine.py:452-472).  With `visits` the search is exactly `visits` MCTS steps
 (uai_interface.py:44-46); with a time budget it runs until the time is used.  The move is then
 sampled on the host exactly like sample_with_exponential_weight (engine.py:532-548).
+
+With `reuse_tree` (an option, off by default) one engine lives for the whole dialogue and its tree follows the game:
+at every `go` the searcher walks from the position its tree is rooted at to the session's position — the same position,
+or one or two moves away (engine.set_state's grandchild rule, engine.py:452-472, and the one-move case), played on the
+device with azh_engine_play_moves so that the subtree, its counts and priors are kept — and starts a fresh tree only when
+the new position is not there.  The root's edges and the principal variation come from azh_engine_root_report.
 """
 import random
 import time
@@ -93,12 +99,57 @@ class Position:
         return "\n".join(rows)
 
 
+def find_path(root, target, successors, max_plies=2):
+    """The moves that lead from position `root` to position `target` in at most `max_plies` plies, or None.
+    `successors(position)` yields (move, position after it) in move generation order; positions are compared with ==.
+    [] when the positions are equal; a shorter path wins, and of two paths of the same length the first one in move
+    order (first move, then second), which is the order of engine.set_state's two loops (engine.py:458-460)."""
+    if root == target:
+        return []
+    frontier = [(root, [])]
+    for _ in range(max_plies):
+        deeper = []
+        for position, path in frontier:
+            for move, child in successors(position):
+                if child == target:
+                    return path + [move]
+                deeper.append((child, path + [move]))
+        frontier = deeper
+    return None
+
+
+class GpuSuccessors:
+    """Move generator for find_path on the GPU rules, positions as (x, o, turn).  prefetch() generates the moves of many
+    positions with one rules call and one make-move call."""
+
+    def __init__(self):
+        self.known = {}
+
+    def prefetch(self, positions):
+        todo = [p for p in dict.fromkeys(positions) if p not in self.known]
+        if not todo:
+            return
+        boards = np.array([link.pack_board(*p) for p in todo], dtype=np.uint64)
+        moves, counts, results = link.rules_batch(boards, 0)
+        rows = [(i, int(m)) for i in range(len(todo)) if results[i] == 0 for m in moves[i, :counts[i]]]
+        after = link.makemove_batch(boards[[i for i, _ in rows]], np.array([m for _, m in rows], dtype=np.uint16)) if rows else []
+        for p in todo:
+            self.known[p] = []
+        for (i, m), b in zip(rows, after):
+            self.known[todo[i]].append((m, (int(b[0]) & ~(1 << 63), int(b[1]), int(b[0]) >> 63)))
+
+    def __call__(self, position):
+        self.prefetch([position])
+        return self.known[position]
+
+
 class Searcher:
     TIME_CAP_VISITS = 20000  # arena size of a time-controlled search (per leaf of a leaf-parallel iteration, below)
     MAX_VISITS = 60000       # the engine's limit (16-bit visit counts); a search of this many visits holds about 3.5 KB of
                              # tree per visit (96 edge slots of 18 bytes per node, two arenas): at most about 210 MB
 
-    def __init__(self, network_path, dtype="f16", symmetry_average=False, parallel_leaves=1, virtual_loss=1):
+    def __init__(self, network_path, dtype="f16", symmetry_average=False, parallel_leaves=1, virtual_loss=1,
+                 reuse_tree=False, show_pv=False):
         # parallel_leaves = K > 1: leaf-parallel search with virtual loss (DESIGN.md, "Leaf-parallel search"): up to K
         # leaves per iteration in one tower launch.  An extension; 1 is the reference's one-leaf search.
         if not 1 <= parallel_leaves <= link.MAX_LEAVES_PER_GAME or not 1 <= virtual_loss <= link.MAX_VIRTUAL_LOSS:
@@ -115,13 +166,106 @@ class Searcher:
         self.dtype = link.DTYPES[dtype]
         self.last_steps = 0
         self.last_seconds = 0.0
+        # reuse_tree: one engine for the session, its tree re-rooted along the moves played (module docstring).
+        # show_pv: the root report of the last search is kept for Session's `info nodes ... pv ...` line.
+        self.reuse_tree, self.show_pv = reuse_tree, show_pv
+        self.last_inherited = 0   # root visits the last search started with (0 without reuse_tree)
+        self.last_report = None   # link.RootReport of the last search (reuse_tree or show_pv)
+        self.last_note = None     # why the last search was shorter than asked, or None
+        self.engine = None        # the session's engine (reuse_tree)
+        self.root = None          # (x, o, turn) the session engine's tree is rooted at; None: no tree to keep
 
     def time_cap(self):
         """Visit cap of a time-controlled search: grows with the leaves per iteration, up to the engine's limit."""
         return min(self.TIME_CAP_VISITS * self.parallel_leaves, self.MAX_VISITS)
 
+    # ------------------------------------------------------------ the session engine (reuse_tree)
+
+    def new_game(self):
+        """`uainewgame`: the next search starts from a fresh tree whatever the position."""
+        self.root = None
+
+    def close(self):
+        if self.engine is not None:
+            self.engine.close()
+            self.engine = None
+        self.root = None
+
+    def _session_engine(self, pos):
+        if self.engine is None:
+            # visits = the engine's limit: no move ever comes due on the device
+            cfg = link.Config(games=1, visits=self.MAX_VISITS, max_plies=400, edges_per_node=96, c_puct=1.0,
+                              dirichlet_alpha=0.15, dirichlet_weight=0.0, start_turn=pos.turn, seed=random.getrandbits(63),
+                              start_x=pos.x, start_o=pos.o, blockers=0,
+                              flags=link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR | self.extra_flags)
+            self.engine = link.Engine(cfg)
+            if self.parallel_leaves > 1:
+                self.engine.set_leaf_batch(self.parallel_leaves, self.virtual_loss)
+        return self.engine
+
+    def _bring_tree_to(self, pos):
+        """The session engine's tree rooted at `pos`: kept where `pos` is the tree's root or at most two moves below it."""
+        eng = self._session_engine(pos)
+        target = (pos.x, pos.o, pos.turn)
+        path = None
+        if self.root is not None:
+            successors = GpuSuccessors()
+            successors.prefetch([child for _, child in successors(self.root)])
+            path = find_path(self.root, target, successors)
+        for move in path or []:
+            if eng.play_moves([move])[0] <= 0:   # (not a root edge, or an idle slot: a finished root)
+                path = None
+                break
+        if path is None:
+            eng.set_positions(pos.packed().reshape(1, 2), [0])
+        self.root = target
+        return eng
+
+    def _root_visits_reusing(self, pos, visits, seconds):
+        """The search on the session's tree: `visits` MORE steps (K > 1: more root visits) on top of the inherited ones,
+        or until the time is used; never past the engine's limit of MAX_VISITS root visits."""
+        K = self.parallel_leaves
+        start = time.time()
+        eng = self._bring_tree_to(pos)
+        state = eng.game_state(0)
+        inherited = rv = state.root_visits
+        limit = self.MAX_VISITS
+        target = limit if visits is None else min(inherited + visits, limit)
+        self.last_note = None
+        if visits is not None and inherited + visits > limit:
+            self.last_note = "search shortened to %d of %d visits: %d inherited, the tree holds %d" % (
+                target - inherited, visits, inherited, limit)
+        if state.phase == 0 and rv < target:
+            eng.run(self.net, 1, self.dtype)   # the root's evaluation
+            state = eng.game_state(0)
+        while rv < target and (seconds is None or time.time() - start < seconds):
+            if state.phase != 1:
+                if state.phase == 2:   # the arena is full: the device's own move is due, and a run would play it
+                    self.last_note = self.last_note or "search stopped at %d visits: the tree's arena is full" % rv
+                break
+            todo = target - rv
+            if todo >= K:
+                chunk = todo // K if seconds is None else min(todo // K, 64 if K == 1 else 16)
+                eng.run(self.net, chunk, self.dtype)
+            else:   # K > 1: the last batch is cut to the visits that are missing
+                eng.set_leaf_batch(todo, self.virtual_loss)
+                eng.run(self.net, 1, self.dtype)
+                eng.sync()
+                eng.set_leaf_batch(K, self.virtual_loss)
+            state = eng.game_state(0)   # (waits for the run)
+            if state.root_visits == rv:
+                break   # a finished root: nothing to search
+            rv = state.root_visits
+        self.last_report = eng.root_report(0, 1)[0]
+        self.last_inherited = inherited
+        self.last_steps, self.last_seconds = rv - inherited, max(time.time() - start, 1e-9)
+        return [(int(m), int(n)) for m, n in zip(self.last_report.moves, self.last_report.visits) if n > 0]
+
     def root_visits(self, pos, visits=None, seconds=None):
         """-> [(move u16, visits)] over the expanded root edges after the search."""
+        self.last_inherited, self.last_report, self.last_note = 0, None, None
+        if self.reuse_tree:
+            return self._root_visits_reusing(pos, visits, seconds)
         if self.parallel_leaves > 1:
             return self._root_visits_parallel(pos, visits, seconds)
         cap = visits if visits is not None else self.TIME_CAP_VISITS
@@ -144,6 +288,8 @@ class Searcher:
                     steps += 64
             eng.sync()
             boards, info, edges, moves = eng.tree(0)
+            if self.show_pv:
+                self.last_report = eng.root_report(0, 1)[0]
         finally:
             eng.close()
         self.last_steps, self.last_seconds = steps, max(time.time() - start, 1e-9)
@@ -176,15 +322,31 @@ class Searcher:
                 rv = now
             eng.sync()
             boards, info, edges, moves = eng.tree(0)
+            if self.show_pv:
+                self.last_report = eng.root_report(0, 1)[0]
         finally:
             eng.close()
         self.last_steps, self.last_seconds = rv, max(time.time() - start, 1e-9)
         first, n = int(info[0, 0]), int(info[0, 1] & 0xFFFF)
         return [(int(moves[first + j]), int(edges[first + j, 1])) for j in range(n) if int(edges[first + j, 3]) != 0xFFFFFFFF]
 
+    def pv_line(self):
+        """`info nodes <root visits> inherited <n> score <q> pv <moves>` for the last search (show_pv), or None: q is
+        W / n of the line's first edge for the side to move, mapped to [-1, 1]."""
+        r = self.last_report
+        if r is None:
+            return None
+        text = "info nodes %d inherited %d" % (r.root_visits, self.last_inherited)
+        if len(r.pv):
+            j = r.moves.tolist().index(int(r.pv[0]))
+            text += " score %.4f pv %s" % (2.0 * float(r.scores[j]) / float(r.visits[j]) - 1.0,
+                                          " ".join(encode_move(int(m)) for m in r.pv))
+        return text
+
     def genmove(self, pos, visits=None, seconds=None, exponent=5.0):
         legal, result = pos.legal_moves()
         if not legal:
+            self.last_inherited, self.last_report, self.last_note = 0, None, None
             return 0xFFFF  # the reference answers "pass" when no edge was visited (engine.py:495-496)
         edges = self.root_visits(pos, visits=visits, seconds=seconds)
         if not edges:
@@ -251,6 +413,8 @@ class Session:
 
     def on_newgame(self, rest):
         self.position = Position.initial()
+        if getattr(self.searcher, "reuse_tree", False):
+            self.searcher.new_game()
         return []
 
     def on_moves(self, rest):
@@ -271,7 +435,12 @@ class Session:
             budget_ms = max(int(rest) - self.safety_ms, 1)
             move = self.searcher.genmove(self.position, seconds=budget_ms * 1e-3)
         speed = self.searcher.last_steps / self.searcher.last_seconds
-        return ["info speed %f nps" % (speed,), "bestmove %s" % (encode_move(move),)]
+        lines = ["info speed %f nps" % (speed,)]
+        if getattr(self.searcher, "last_note", None):
+            lines.append("info string %s" % (self.searcher.last_note,))
+        if getattr(self.searcher, "show_pv", False) and self.searcher.pv_line():
+            lines.append(self.searcher.pv_line())
+        return lines + ["bestmove %s" % (encode_move(move),)]
 
     def handle(self, line):
         """-> (lines to print, keep going)."""

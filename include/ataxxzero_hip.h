@@ -273,6 +273,50 @@ int azh_engine_set_thin_batches(azh_engine *e, int mode);
  * be found at instead of waiting a game generation (about 70 s at 400 sims/move) for the steady state to form. */
 int azh_engine_set_positions(azh_engine *e, const uint64_t *boards, const int32_t *plies);
 
+/* ------------------------------------------------------------------ moves named by the host (an extension)
+ * A front-end that keeps its search tree across moves (uai_interface.py --reuse-tree; the reference's
+ * MCTSEngine.set_state, engine.py:452-472, walks to the new root with MCTS.play, engine.py:411-424) tells the engine
+ * which move was played instead of letting it sample one.
+ *
+ * azh_engine_play_moves: moves [games], one per slot, u16 = from | to << 8; 0xFFFF leaves the slot alone.  Per slot with
+ * a move, status_out [games] is
+ *   AZH_PLAY_KEPT      the root edge had a child: that child is the root now, with its subtree, visit counts, total scores
+ *                      and priors (the re-root of the device's own moves: breadth-first compaction into the other arena)
+ *   AZH_PLAY_FRESH     the edge had no child, or the engine was created with AZH_FLAG_NO_REUSE: a one-node tree at the
+ *                      position after the move
+ *   AZH_PLAY_FINISHED  the move was played (subtree kept or not) and the new root is a finished position: the slot goes idle
+ *                      at that root (phase 3; azh_engine_set_positions starts it again)
+ *   AZH_PLAY_ILLEGAL   the move is not among the root's edges: every byte of the slot's arenas and state is as before
+ *   AZH_PLAY_BUSY      the slot is idle (phase 3): untouched
+ *   AZH_PLAY_NONE      no move was given
+ * After a move that was played the slot's ply is one higher (it stops at max_plies - 1: the ply cut belongs to the games
+ * the device plays itself), its root is evaluated again by the next select (phase 0, as after a sampled move), no random
+ * number has been drawn, no ply record written, AZH_STAT_PLIES has not moved (AZH_STAT_REROOT_* count the copy), and the
+ * slot's game never becomes a game line (as after azh_engine_set_positions).  With AZH_FLAG_EVAL_CACHE the new arena's table
+ * is rebuilt as after a sampled move.
+ * A slot whose OWN move is due (phase 2: its root has reached `visits`; a leaf-parallel search that ran exactly to its
+ * target ends there) is taken out of the move queue and the host's move is played IN PLACE of the sampled one: the device
+ * never samples for a slot the host has moved in before the next select.
+ * Refused with an error, nothing changed: while a batch selected with azh_engine_select awaits its azh_engine_backup, and
+ * on AZH_FLAG_TWO_NETS engines.  Enqueued on the engine's stream; returns when status_out has been written. */
+enum { AZH_PLAY_NONE = 0, AZH_PLAY_KEPT = 1, AZH_PLAY_FRESH = 2, AZH_PLAY_FINISHED = 3, AZH_PLAY_ILLEGAL = -1,
+       AZH_PLAY_BUSY = -2 };
+int azh_engine_play_moves(azh_engine *e, const uint16_t *moves /* [games] */, int32_t *status_out /* [games] */);
+
+/* azh_engine_root_report: what a front-end prints about a search, without copying the tree (azh_engine_tree moves 16 B per
+ * node twice and 18 B per edge: tens of MB at 60000 visits).  For the slots first_game .. first_game + n_games - 1, one
+ * record of AZH_ROOT_REPORT_WORDS u32 each:
+ *   [0] root visits   [1] root edges M (<= AZH_MAX_MOVES)   [2] root edges with a child   [3] the root's result (0: not
+ *   finished, 1 / 2: as azh_rules_batch)
+ *   [4 + 4 j .. 7 + 4 j], j < M, in edge (= move generation) order: move, visits, total score W (f32 bits, seen from the
+ *   side to move at the root), prior (f32 bits); zero for j >= M
+ *   [AZH_ROOT_REPORT_PV]  number of moves L of the principal variation, then L pairs (move, visits of its edge): from the
+ *   root the edge with the most visits, the first one in edge order on a tie; the line ends before an edge with 0 visits,
+ *   after an edge without a child or into a finished position, and after AZH_PV_MAX moves; zero beyond L pairs. */
+#define AZH_PV_MAX 32
+enum { AZH_ROOT_REPORT_PV = 4 + 4 * AZH_MAX_MOVES, AZH_ROOT_REPORT_WORDS = AZH_ROOT_REPORT_PV + 1 + 2 * AZH_PV_MAX };
+int azh_engine_root_report(azh_engine *e, int first_game, int n_games, uint32_t *out /* [n_games][AZH_ROOT_REPORT_WORDS] */);
+
 int azh_engine_game_state(azh_engine *e, int game, azh_game_state *out);
 /* arena dump: boards [n_nodes][2] u64, info [n_nodes][4] u32
  * (first_edge, n_edges | result << 16, 0, terminal value bits), edges

@@ -6,6 +6,14 @@ root visits per second, iterations, the HIP-event time per iteration of the tree
 iteration sampled), and collisions per path.  K = 1 is the one-leaf search exactly as uai.Searcher runs it.
 
     python tools/uai_nps.py [--movetime-ms 1000] [--ks 1,8,16,32,48,64] [--out profiles/FILE.txt]
+
+--reuse-tree measures what keeping the tree across moves is worth instead: a fixed line of 16 plies (the engine's own
+moves of one session at a fixed seed) is played through uai.Session at `go movetime 200` — `moves a b` + `go`, the
+tree's owner moving every second ply — with and without --reuse-tree, K = 1 and K = 32.  Per `go`: inherited root
+visits, new visits, wall time of the whole `go`; then the per-`go` overhead outside the search: a fresh engine + the
+whole-tree copy (what every `go` costs without reuse) against the re-root + root report of the session engine.
+
+    python tools/uai_nps.py --reuse-tree [--out profiles/uai_tree_reuse.txt]
 """
 import argparse
 import os
@@ -59,8 +67,131 @@ def search(net, pos, K, VL, seconds, dtype):
                 tower_ms=tm["net_ms"] / max(tm["iterations"], 1), collisions=coll, paths=steps, capped=rv >= target)
 
 
+def _searcher(net_path, K, reuse):
+    return uai.Searcher(net_path, dtype="f16", parallel_leaves=K, virtual_loss=1, reuse_tree=reuse)
+
+
+def reuse_line(net_path, plies, seconds):
+    """The fixed line: the moves a K = 1 reuse session plays against itself from the start position at seed 1."""
+    random.seed(1)
+    session = uai.Session(_searcher(net_path, 1, True))
+    session.handle("uainewgame")
+    line = []
+    for _ in range(plies):
+        out, _ = session.handle("go movetime %d" % int(seconds * 1000))
+        move = out[-1].split()[1]
+        if move == "0000":
+            break
+        line.append(move)
+        session.handle("moves " + move)
+    session.searcher.close()
+    return line
+
+
+def reference_openings(games, plies):
+    """The first `plies` moves of the first `games` random-play games the reference wrote (tests/golden), as UAI text."""
+    import gzip
+    import json
+    square = lambda xy: "abcdefg"[xy[0]] + str(7 - xy[1])
+    out = []
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "random_play_games.jsonl.gz")) as f:
+        for text in f.read().decode().split("\n")[:games]:
+            moves = json.loads(text)["moves"][:plies]
+            out.append([square(m[1]) if m[0] == "c" else square(m[0]) + square(m[1]) for m in moves])
+    return out
+
+
+def reuse_report(net, conv, bn, movetime_ms, out_path):
+    import tempfile
+    seconds = movetime_ms * 1e-3
+    net_path = os.path.join(tempfile.mkdtemp(), "net.npy")
+    model.save_model(net_path, conv, bn)
+    fixed = [("own", reuse_line(net_path, 16, seconds))] + [("ref-%d" % i, line) for i, line in enumerate(reference_openings(2, 16))]
+    lines = ["# tools/uai_nps.py --reuse-tree: go movetime %d ms, 12x128 net with RANDOM weights (a flat policy: the search's visits"
+             % movetime_ms,
+             "# spread over all replies, the least a kept tree can be worth), f16, virtual loss 1; one session per (line, K, reuse);",
+             "# the engine is asked to move at every second ply of a fixed line, after `moves a b`.  Lines:"]
+    lines += ["#   %-5s %s" % (name, " ".join(line)) for name, line in fixed]
+    lines += ["# own: the moves a K = 1 reuse session played against itself at seed 1 (it ends when a side has no move);",
+              "# ref-i: the first 16 plies of the i-th random-play game under tests/golden",
+              "# columns: line  K  reuse  ply  inherited  new visits  root visits  go wall ms"]
+    summary = []
+    for K in (1, 32):
+        for reuse in (False, True):
+            inh = new = gos = 0
+            wall = 0.0
+            for name, line in fixed:
+                random.seed(2)
+                searcher = _searcher(net_path, K, reuse)
+                session = uai.Session(searcher)
+                session.handle("uainewgame")
+                session.handle("go movetime 50")   # warm-up (allocations, code objects); the tree is dropped again
+                session.handle("uainewgame")
+                for ply in range(0, len(line), 2):
+                    if ply:
+                        session.handle("moves %s %s" % (line[ply - 2], line[ply - 1]))
+                    t0 = time.time()
+                    session.handle("go movetime %d" % movetime_ms)
+                    dt = time.time() - t0
+                    text = "%-5s K=%-3d reuse=%d ply %2d  inherited %6d  new %6d  root %6d  go %7.1f ms" % (
+                        name, K, int(reuse), ply, searcher.last_inherited, searcher.last_steps,
+                        searcher.last_inherited + searcher.last_steps, dt * 1e3)
+                    print(text, flush=True)
+                    lines.append(text)
+                    inh += searcher.last_inherited
+                    new += searcher.last_steps
+                    wall += dt
+                    gos += 1
+                searcher.close()
+            summary.append("summary K=%-3d reuse=%d  %d go  inherited %d  new %d  inherited share of root visits %.1f %%  "
+                           "go wall %.1f ms mean (budget %d ms)" % (K, int(reuse), gos, inh, new, 100.0 * inh / max(inh + new, 1),
+                                                                     wall / gos * 1e3, movetime_ms))
+    # the per-go overhead outside the search, on trees of the size a 200 ms search leaves
+    pos = uai.Position.initial()
+    for K in (1, 32):
+        fresh, copy, reroot, report = [], [], [], []
+        for rep in range(5):
+            t0 = time.time()
+            target = min(uai.Searcher.TIME_CAP_VISITS * K, uai.Searcher.MAX_VISITS)
+            eng = link.Engine(link.Config(games=1, visits=target + (1 if K == 1 else 0), max_plies=400, edges_per_node=96,
+                                          c_puct=1.0, dirichlet_alpha=0.15, dirichlet_weight=0.0, start_turn=pos.turn, seed=1,
+                                          start_x=pos.x, start_o=pos.o, blockers=0,
+                                          flags=link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR))
+            if K > 1:
+                eng.set_leaf_batch(K, 1)
+            eng.sync()
+            t1 = time.time()
+            eng.run(net, 1 + (1500 if K == 1 else 400), link.DTYPE_F16)
+            eng.sync()
+            t2 = time.time()
+            eng.tree(0)
+            t3 = time.time()
+            rep_ = eng.root_report(0, 1)[0]
+            t4 = time.time()
+            eng.play_moves([int(rep_.pv[0])])
+            t5 = time.time()
+            nodes = eng.game_state(0).n_nodes
+            eng.close()
+            t6 = time.time()
+            fresh.append((t1 - t0) + (t6 - t5))
+            copy.append(t3 - t2)
+            report.append(t4 - t3)
+            reroot.append(t5 - t4)
+        med = lambda v: sorted(v)[len(v) // 2] * 1e3
+        summary.append("overhead K=%-3d per go, median of 5: engine create + destroy %.2f ms, whole-tree copy %.2f ms (root %d visits) | "
+                       "re-root (play_moves, %d nodes kept) %.2f ms, root report %.2f ms"
+                       % (K, med(fresh), med(copy), rep_.root_visits, nodes, med(reroot), med(report)))
+    for text in summary:
+        print(text, flush=True)
+    lines += summary
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--reuse-tree", action="store_true", help="measure tree reuse across the moves of a fixed line instead")
     ap.add_argument("--movetime-ms", type=int, default=1000)
     ap.add_argument("--ks", default="1,8,16,32,48,64")
     ap.add_argument("--virtual-loss", type=int, default=1)
@@ -70,6 +201,9 @@ def main():
     conv, bn = model.random_init(12, 128, seed=1, perturb_bn=True)
     net = link.Net(conv, bn)
     dtype = link.DTYPE_F16
+    if a.reuse_tree:
+        reuse_report(net, conv, bn, 200, a.out)
+        return
     ks = [int(k) for k in a.ks.split(",")]
     lines = ["# tools/uai_nps.py: go movetime %d ms, 12x128 net, f16, virtual loss %d, one engine per search"
              % (a.movetime_ms, a.virtual_loss),
