@@ -934,6 +934,32 @@ __global__ __launch_bounds__(WAVE) void k_unqueue_played(EngineParams P)
         *P.adv_count = kept;
 }
 
+// azh_engine_root_proofs: one wave per game — the decided value (0: none, +1 / -1: the side to move there wins / loses) of
+// the root and of the child of every root edge, from the marks the solver and the expansion of finished positions leave
+// (node_info.w; the finished bit of the edge's range word).
+__global__ __launch_bounds__(WAVE) void k_root_proofs(EngineParams P, int first_game, int *out)
+{
+    const int g = first_game + (int)blockIdx.x, lane = lane_id();
+    int *rec = out + (size_t)blockIdx.x * AZH_ROOT_PROOF_WORDS;
+    const azh_game_state s = P.gs[g];
+    Arena A = arena_of(P, s.arena, g);
+    const uint4 rinfo = A.ni[0];
+    const int M = min((int)(rinfo.y & 0xFFFFu), AZH_MAX_MOVES);
+    // (AZH_FLAG_EVAL_CACHE keeps a node's evaluation in the same word: only an exact +-1 of a finished or proven node counts)
+    const bool rdec = (rinfo.y >> 16) != 0u || (!(P.flags & AZH_FLAG_EVAL_CACHE) && (rinfo.w & 0x7FFFFFFFu) == 0x3F800000u);
+    if (lane == 0)
+        rec[0] = rdec ? ((rinfo.w >> 31) ? -1 : 1) : 0;
+    for (int j = lane; j < AZH_MAX_MOVES; j += WAVE) {
+        int v = 0;
+        if (j < M) {
+            const uint4 ev = A.ed[rinfo.x + j];
+            if (edge_child(ev) != ENONE && kid_finished(ev.w))
+                v = (A.ni[edge_child(ev)].w >> 31) ? -1 : 1;
+        }
+        rec[1 + j] = v;
+    }
+}
+
 // azh_engine_root_report: one wave per game writes the fixed-size record the header documents — the root's edges and
 // the principal variation.  The walk is a dependent chain of at most AZH_PV_MAX levels: once per `go`, not per iteration.
 __global__ __launch_bounds__(WAVE) void k_root_report(EngineParams P, int first_game, u32 *out)
@@ -1269,6 +1295,10 @@ struct azh_engine {
     u32 *vl_need_mask = nullptr;
     int vl_mask_words = 0;
     float *vl_logits = nullptr, *vl_values = nullptr;
+    // proven wins and losses (azh_engine_set_solver): while it is on, every K — 1 included — runs through k_vl_tree and the
+    // G K-slot buffers (vl_active: P's leaf buffers point at them), and its backup is followed by the proof pass
+    bool vl_active = false;   // (the solver's own switch is V.solver)
+    int32_t *d_proofs = nullptr;  // azh_engine_root_proofs: [G][AZH_ROOT_PROOF_WORDS], allocated by the first call
 };
 
 static int leaf_k(const azh_engine *e) { return e->V.K > 1 ? e->V.K : 1; }
@@ -1363,6 +1393,7 @@ extern "C" int azh_engine_create(const azh_config *cfg, azh_engine **out)
     rc |= dev_alloc(e, &P.stats, G * NSTAT);
     rc |= dev_alloc(e, &P.bfs_spill, G * 3 * P.node_cap);
     rc |= dev_alloc(e, &e->d_stat_out, NSTAT);
+    rc |= dev_alloc(e, &e->V.proofs, G * AZH_PROOF_STAT_COUNT);
     if (rc) {
         azh_engine_destroy(e);
         return rc;
@@ -1458,7 +1489,7 @@ static int enqueue_advance(azh_engine *e, hipStream_t stream, hipEvent_t done = 
 
 static int enqueue_select(azh_engine *e)
 {
-    if (leaf_k(e) > 1) {
+    if (e->vl_active) {
         hipLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, e->P, e->V, 2);
         AZH_HIP(hipGetLastError());
         return enqueue_advance(e, e->stream);
@@ -1471,7 +1502,7 @@ static int enqueue_select(azh_engine *e)
 
 static int enqueue_backup(azh_engine *e)
 {
-    if (leaf_k(e) > 1) {
+    if (e->vl_active) {
         hipLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, e->P, e->V, 1);
         AZH_HIP(hipGetLastError());
         return 0;
@@ -1500,8 +1531,9 @@ extern "C" int azh_engine_leaves(azh_engine *e, int32_t *need_eval, uint64_t *le
 {
     if (!e)
         return azh_fail(-1, "azh_engine_leaves: null engine");
-    if (leaf_k(e) > 1)
-        return azh_fail(-2, "azh_engine_leaves: %d leaves per game: use azh_engine_batch_leaves", leaf_k(e));
+    if (e->vl_active)
+        return azh_fail(-2, "azh_engine_leaves: %d leaves per game%s: use azh_engine_batch_leaves", leaf_k(e),
+                        e->V.solver ? " with the solver" : "");
     AZH_HIP(hipStreamSynchronize(e->stream));
     if (need_eval)
         AZH_HIP(hipMemcpy(need_eval, e->P.need_eval, (size_t)e->P.G * 4, hipMemcpyDeviceToHost));
@@ -1515,8 +1547,9 @@ extern "C" int azh_engine_leaf_features(azh_engine *e, float *out, int32_t *game
 {
     if (!e || !out)
         return azh_fail(-1, "azh_engine_leaf_features: null argument");
-    if (leaf_k(e) > 1)
-        return azh_fail(-2, "azh_engine_leaf_features: not available with %d leaves per game", leaf_k(e));
+    if (e->vl_active)
+        return azh_fail(-2, "azh_engine_leaf_features: not available with %d leaves per game%s", leaf_k(e),
+                        e->V.solver ? " and the solver" : "");
     AZH_HIP(hipStreamSynchronize(e->stream));
     int n = 0;
     AZH_HIP(hipMemcpy(&n, e->P.leaf_count, 4, hipMemcpyDeviceToHost));
@@ -1561,8 +1594,9 @@ extern "C" int azh_engine_set_evals(azh_engine *e, const float *logits, const fl
 {
     if (!e || !logits || !values)
         return azh_fail(-1, "azh_engine_set_evals: null argument");
-    if (leaf_k(e) > 1)
-        return azh_fail(-2, "azh_engine_set_evals: %d leaves per game: use azh_engine_set_batch_evals", leaf_k(e));
+    if (e->vl_active)
+        return azh_fail(-2, "azh_engine_set_evals: %d leaves per game%s: use azh_engine_set_batch_evals", leaf_k(e),
+                        e->V.solver ? " with the solver" : "");
     AZH_HIP(hipMemcpyAsync(e->P.logits, logits, (size_t)e->P.G * AZH_POLICY_SIZE * 4, hipMemcpyHostToDevice, e->stream));
     AZH_HIP(hipMemcpyAsync(e->P.values, values, (size_t)e->P.G * 4, hipMemcpyHostToDevice, e->stream));
     AZH_HIP(hipStreamSynchronize(e->stream));
@@ -1619,7 +1653,7 @@ struct RunLoop {
     // one fused tree launch; ev (or nullptr) is signalled by the kernel's own completion
     void launch_tree(bool stamped, int mode, hipEvent_t ev)
     {
-        if (leaf_k(e) > 1) {  // leaf-parallel search: one workgroup per game (not stamped: azh_engine_tree_stamps refuses)
+        if (e->vl_active) {  // leaf-parallel search: one workgroup per game (not stamped: azh_engine_tree_stamps refuses)
             hipExtLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, nullptr, ev, 0, e->P, e->V, mode);
             return;
         }
@@ -1777,8 +1811,9 @@ extern "C" int azh_engine_tree_stamps(azh_engine *e, azh_net *net, int dtype, ui
 {
     if (!e || !net || !out)
         return azh_fail(-1, "azh_engine_tree_stamps: null argument");
-    if (leaf_k(e) > 1)
-        return azh_fail(-2, "azh_engine_tree_stamps: not available with %d leaves per game", leaf_k(e));
+    if (e->vl_active)
+        return azh_fail(-2, "azh_engine_tree_stamps: not available with %d leaves per game%s", leaf_k(e),
+                        e->V.solver ? " and the solver" : "");
     if (!e->P.stamps) {
         void *q = nullptr;
         AZH_HIP(hipMalloc(&q, (size_t)e->P.G * TREE_STAMPS * 8));
@@ -1797,20 +1832,18 @@ extern "C" int azh_engine_tree_stamps(azh_engine *e, azh_net *net, int dtype, ui
 }
 
 // Leaf-parallel search: K leaves per game and iteration, spread by a virtual loss of `virtual_loss` visits
-// (vl_search.h).  Between iterations only; K = 1 restores the one-leaf search and its kernels.
-extern "C" int azh_engine_set_leaf_batch(azh_engine *e, int leaves_per_game, int virtual_loss)
+// (vl_search.h), and the solver on top of it.  k_vl_tree and the G K-slot buffers are in force while K > 1 or the solver is
+// on; K = 1 without the solver is the one-leaf search and its kernels.  `who`: the calling entry point, for its errors.
+static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, bool solver, const char *who)
 {
-    if (!e)
-        return azh_fail(-1, "azh_engine_set_leaf_batch: null engine");
-    if (leaves_per_game < 1 || leaves_per_game > VL_MAX_LEAVES || virtual_loss < 1 || virtual_loss > VL_MAX_LOSS)
-        return azh_fail(-2, "azh_engine_set_leaf_batch: need 1 <= leaves_per_game <= %d and 1 <= virtual_loss <= %d",
-                        VL_MAX_LEAVES, VL_MAX_LOSS);
     if (e->selected)
-        return azh_fail(-3, "azh_engine_set_leaf_batch: a selected batch awaits its backup");
-    if (leaves_per_game > 1) {
+        return azh_fail(-3, "%s: a selected batch awaits its backup", who);
+    const bool want = leaves_per_game > 1 || solver;
+    if (want) {
         const uint32_t bad = e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_EVAL_CACHE | AZH_FLAG_SYMMETRY_AVG);
         if (bad || e->P.select_budget > 0)
-            return azh_fail(-4, "azh_engine_set_leaf_batch: more than one leaf per game is not supported with %s",
+            return azh_fail(-4, "%s: %s is not supported with %s", who,
+                            leaves_per_game > 1 ? "more than one leaf per game" : "the solver",
                             e->P.select_budget > 0 ? "select_budget > 0"
                             : (bad & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS"
                             : (bad & AZH_FLAG_EVAL_CACHE) ? "AZH_FLAG_EVAL_CACHE" : "AZH_FLAG_SYMMETRY_AVG");
@@ -1819,12 +1852,12 @@ extern "C" int azh_engine_set_leaf_batch(azh_engine *e, int leaves_per_game, int
     AZH_HIP(hipStreamSynchronize(e->stream2));
     EngineParams &P = e->P;
     const size_t G = (size_t)P.G, K = (size_t)leaves_per_game;
-    if (K > 1 && e->V.K <= 1 && e->vl_slots_cap > 0) {
+    if (want && !e->vl_active && e->vl_slots_cap > 0) {
         // back to K-slot buffers allocated by an earlier call
         P.leaf_board = e->vl_leaf_board; P.need_eval = e->vl_need_eval; P.leaf_list = e->vl_leaf_list;
         P.need_mask = e->vl_need_mask; P.mask_words = e->vl_mask_words; P.logits = e->vl_logits; P.values = e->vl_values;
     }
-    if (K > 1 && (int)(G * K) > e->vl_slots_cap) {
+    if (want && (int)(G * K) > e->vl_slots_cap) {
         // slot buffers for G K leaves (kept for the engine's life; a larger K later allocates again)
         const size_t n = G * K;
         const int mw = (int)((n + 31) / 32);
@@ -1845,12 +1878,14 @@ extern "C" int azh_engine_set_leaf_batch(azh_engine *e, int leaves_per_game, int
             P.leaf_board = e->g_leaf_board; P.need_eval = e->g_need_eval; P.leaf_list = e->g_leaf_list;
             P.need_mask = e->g_need_mask; P.mask_words = e->g_mask_words; P.logits = e->g_logits; P.values = e->g_values;
             e->V.K = 1;
+            e->V.solver = 0;
+            e->vl_active = false;
             e->vl_slots_cap = 0;
             return rc;
         }
         e->vl_slots_cap = (int)n;
     }
-    if (K > 1) {
+    if (want) {
         e->vl_leaf_board = P.leaf_board; e->vl_need_eval = P.need_eval; e->vl_leaf_list = P.leaf_list;
         e->vl_need_mask = P.need_mask; e->vl_mask_words = P.mask_words; e->vl_logits = P.logits; e->vl_values = P.values;
     } else {
@@ -1859,6 +1894,43 @@ extern "C" int azh_engine_set_leaf_batch(azh_engine *e, int leaves_per_game, int
     }
     e->V.K = (int)K;
     e->V.vl = virtual_loss;
+    e->V.solver = solver ? 1 : 0;
+    e->vl_active = want;
+    return 0;
+}
+
+// Between iterations only; K = 1 restores the one-leaf search and its kernels (unless the solver is on).
+extern "C" int azh_engine_set_leaf_batch(azh_engine *e, int leaves_per_game, int virtual_loss)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_set_leaf_batch: null engine");
+    if (leaves_per_game < 1 || leaves_per_game > VL_MAX_LEAVES || virtual_loss < 1 || virtual_loss > VL_MAX_LOSS)
+        return azh_fail(-2, "azh_engine_set_leaf_batch: need 1 <= leaves_per_game <= %d and 1 <= virtual_loss <= %d",
+                        VL_MAX_LEAVES, VL_MAX_LOSS);
+    return set_leaf_mode(e, leaves_per_game, virtual_loss, e->V.solver != 0, "azh_engine_set_leaf_batch");
+}
+
+// Proven wins and losses on (every K through k_vl_tree, its backup followed by the proof pass) or off (today's dispatch;
+// marks already in the tree stay).  Between iterations only.
+extern "C" int azh_engine_set_solver(azh_engine *e, int on)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_set_solver: null engine");
+    return set_leaf_mode(e, leaf_k(e), e->V.vl, on != 0, "azh_engine_set_solver");
+}
+
+// Sums over the games of the proof pass's counters: out [AZH_PROOF_STAT_COUNT].
+extern "C" int azh_engine_proof_stats(azh_engine *e, uint64_t *out)
+{
+    if (!e || !out)
+        return azh_fail(-1, "azh_engine_proof_stats: bad argument");
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    std::vector<uint64_t> h((size_t)e->P.G * AZH_PROOF_STAT_COUNT);
+    AZH_HIP(hipMemcpy(h.data(), e->V.proofs, h.size() * 8, hipMemcpyDeviceToHost));
+    for (int k = 0; k < AZH_PROOF_STAT_COUNT; k++)
+        out[k] = 0;
+    for (size_t i = 0; i < h.size(); i++)
+        out[i % AZH_PROOF_STAT_COUNT] += h[i];
     return 0;
 }
 
@@ -1868,7 +1940,7 @@ extern "C" int azh_engine_batch_leaves(azh_engine *e, int32_t *kind, uint64_t *l
 {
     if (!e)
         return azh_fail(-1, "azh_engine_batch_leaves: null engine");
-    if (leaf_k(e) < 2)
+    if (!e->vl_active)
         return azh_fail(-2, "azh_engine_batch_leaves: one leaf per game: use azh_engine_leaves");
     AZH_HIP(hipStreamSynchronize(e->stream));
     const size_t n = (size_t)e->P.G * leaf_k(e);
@@ -1886,7 +1958,7 @@ extern "C" int azh_engine_set_batch_evals(azh_engine *e, const float *logits, co
 {
     if (!e || !logits || !values)
         return azh_fail(-1, "azh_engine_set_batch_evals: null argument");
-    if (leaf_k(e) < 2)
+    if (!e->vl_active)
         return azh_fail(-2, "azh_engine_set_batch_evals: one leaf per game: use azh_engine_set_evals");
     const size_t n = (size_t)e->P.G * leaf_k(e);
     AZH_HIP(hipMemcpyAsync(e->P.logits, logits, n * AZH_POLICY_SIZE * 4, hipMemcpyHostToDevice, e->stream));
@@ -2023,6 +2095,20 @@ extern "C" int azh_engine_root_report(azh_engine *e, int first_game, int n_games
     hipLaunchKernelGGL(k_root_report, dim3(n_games), dim3(WAVE), 0, e->stream, e->P, first_game, e->d_report);
     AZH_HIP(hipGetLastError());
     AZH_HIP(hipMemcpyAsync(out, e->d_report, (size_t)n_games * AZH_ROOT_REPORT_WORDS * 4, hipMemcpyDeviceToHost, e->stream));
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// Decided values of the root and of its edges' children: n_games records of AZH_ROOT_PROOF_WORDS i32 (layout: the header).
+extern "C" int azh_engine_root_proofs(azh_engine *e, int first_game, int n_games, int32_t *out)
+{
+    if (!e || !out || first_game < 0 || n_games < 1 || first_game > e->P.G - n_games)
+        return azh_fail(-1, "azh_engine_root_proofs: bad argument");
+    if (!e->d_proofs && dev_alloc(e, &e->d_proofs, (size_t)e->P.G * AZH_ROOT_PROOF_WORDS))
+        return -1;
+    hipLaunchKernelGGL(k_root_proofs, dim3(n_games), dim3(WAVE), 0, e->stream, e->P, first_game, e->d_proofs);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipMemcpyAsync(out, e->d_proofs, (size_t)n_games * AZH_ROOT_PROOF_WORDS * 4, hipMemcpyDeviceToHost, e->stream));
     AZH_HIP(hipStreamSynchronize(e->stream));
     return 0;
 }

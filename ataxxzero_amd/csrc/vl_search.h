@@ -31,6 +31,8 @@ struct VlParams {
     int *leaf_node;   // [G * K] the node the path ended at
     int *path_len;    // [G * K] edges on the path
     int *path;        // [G * K][path_cap] the paths' edges, root first
+    int solver;       // azh_engine_set_solver: the backup is followed by the proof pass (vl_prove)
+    u64 *proofs;      // [G][2] counters of the proof pass: AZH_PROOF_STAT_NODES, _HITS (azh_engine_proof_stats)
 };
 
 // Selects the game's batch: k paths in path order (phase 1), the root evaluation (phase 0, slot 0), or nothing.  `s` is
@@ -249,6 +251,91 @@ __device__ inline void vl_backup_priors(const EngineParams &P, const VlParams &V
             apply_priors(P, A, V.leaf_node[base + p], P.logits + (base + p) * AZH_POLICY_SIZE, false, 0u, 0u);
 }
 
+// The proof pass (azh_engine_set_solver; DESIGN.md "Proven wins and losses"; tests/solver_reference.py restates it), run by
+// the backup's wave after vl_backup_edges.  A node is DECIDED if it is a finished position or PROVEN; both are stored the
+// same way — the node's value (the bits of +1.0f: its side to move wins, -1.0f: it loses) in node_info.w, and the
+// "finished" bit of the range word of the edge that leads to it — so select ends a path there and the backup reads its
+// value exactly as it does for a finished position; a proven node keeps its edge count in that word and its result bits 0
+// (the game is not over: reroot_game copies both words as they are, and the root is descended from whatever its own mark).
+// For every TERMINAL path whose last node became decided in this batch (`fresh`: a finished position the batch created; a
+// hit of a position settled earlier proves nothing new, its parent was tested then) in path order, from the parent X of
+// the path's last node upwards: X is a proven win if a child
+// of X is decided with -1, a proven loss if every edge of X has a child decided with +1 (one 16-byte load per child,
+// lane-striped like select's level, the decided children's values gathered behind it, one ballot each); when X becomes
+// proven the walk goes on with X's parent, else — or when X was decided already — it stops.  A mark is made visible to the
+// loads of the next step and of the next path by a workgroup-scope fence (same wave, same CU), like a path's virtual loss.
+// `kind`, `len`, `leaf`, `fresh`: lane p's path.  W and n are never touched.
+__device__ inline void vl_prove(const EngineParams &P, const VlParams &V, int g, const Arena &A, int k, int kind, int len, int leaf,
+                                bool fresh)
+{
+    const int lane = lane_id();
+    const size_t base = (size_t)g * V.K;
+    const bool term = lane < k && kind == AZH_LEAF_TERMINAL && len > 0;
+    const bool walk = term && fresh;
+    bool hit = false;  // a path that ended at a proven node (not a finished position)
+    if (term && !fresh)
+        hit = (A.ni[leaf].y >> 16) == 0u;
+    const u64 st_hits = (u64)__popcll(__ballot(hit));
+    u64 st_nodes = 0;
+    const uint4 rinfo = A.ni[0];
+    const u32 root_kid = pack_kid(rinfo.x, rinfo.y & 0xFFFFu, 0u);
+    bool root_decided = (rinfo.y >> 16) != 0u || (rinfo.w & 0x7FFFFFFFu) == 0x3F800000u;
+    __threadfence_block();
+    wave_sync();
+    for (u64 todo = __ballot(walk); todo; todo &= todo - 1ull) {
+        const int p = __ffsll((long long)todo) - 1;
+        const int *path = V.path + (base + (size_t)p) * V.path_cap;
+        for (int d = read_lane(len, p) - 1; d >= 0; d--) {
+            // X: the node at depth d of the path — the root, or the child of the path's edge d - 1
+            u32 x = 0, xkid = root_kid, pe = 0;
+            if (d > 0) {
+                pe = (u32)__builtin_amdgcn_readfirstlane(path[d - 1]);
+                const uint2 pr = reinterpret_cast<const uint2 *>(&A.ed[pe])[1];
+                x = (u32)__builtin_amdgcn_readfirstlane((int)(pr.x >> 16));
+                xkid = (u32)__builtin_amdgcn_readfirstlane((int)pr.y);
+                if (kid_finished(xkid))
+                    break;  // proven by an earlier path of this batch
+            } else if (root_decided) {
+                break;
+            }
+            const int M = kid_count(xkid);
+            const u32 first = kid_first(xkid);
+            bool loses = false, open = false;  // among this lane's children: one decided with -1; one not decided with +1
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int j = lane + 64 * r;
+                if (j < M) {
+                    const uint4 ev = A.ed[first + j];
+                    const u32 c = edge_child(ev);
+                    if (c != ENONE && kid_finished(ev.w)) {
+                        if (A.ni[c].w >> 31)
+                            loses = true;
+                    } else {
+                        open = true;
+                    }
+                }
+            }
+            const bool win = __ballot(loses) != 0ull;
+            if (!win && (M == 0 || __ballot(open) != 0ull))
+                break;
+            if (lane == 0) {
+                reinterpret_cast<u32 *>(&A.ni[x])[3] = f2u(win ? 1.0f : -1.0f);
+                if (d > 0)
+                    reinterpret_cast<u32 *>(&A.ed[pe])[3] = xkid | 0x80000000u;
+            }
+            if (d == 0)
+                root_decided = true;
+            st_nodes += 1;
+            __threadfence_block();
+            wave_sync();
+        }
+    }
+    if (lane == 0 && (st_nodes | st_hits)) {
+        V.proofs[(size_t)g * 2 + AZH_PROOF_STAT_NODES] += st_nodes;
+        V.proofs[(size_t)g * 2 + AZH_PROOF_STAT_HITS] += st_hits;
+    }
+}
+
 // The batch's edge backup (one wave; lane p = path p).  Level by level — the paths that share an edge share it at the
 // same depth — every edge gets ONE read-modify-write: W plus the scores of the EVAL and TERMINAL paths through it in path
 // order (f32, the oracle's per-level inversion), visits plus those paths minus every path's virtual loss.
@@ -265,15 +352,16 @@ __device__ inline void vl_backup_edges(const EngineParams &P, const VlParams &V,
     const int k = s.path_len;
     const size_t base = (size_t)g * V.K;
     Arena A = arena_of(P, s.arena, g);
-    int kind = AZH_LEAF_NONE, len = 0;
+    int kind = AZH_LEAF_NONE, len = 0, leaf = 0;
     float v = 0.0f;
     if (lane < k) {
         kind = V.kind[base + lane];
         len = V.path_len[base + lane];
+        leaf = V.leaf_node[base + lane];
         if (kind == AZH_LEAF_EVAL)
             v = P.values[base + lane];
         else if (kind == AZH_LEAF_TERMINAL)
-            v = u2f(A.ni[V.leaf_node[base + lane]].w);
+            v = u2f(A.ni[leaf].w);
     }
     const bool counted = kind == AZH_LEAF_EVAL || kind == AZH_LEAF_TERMINAL;
     // step() part 4 (:449-459), as backup_game: the score seen from the edge `flips` levels above the leaf
@@ -281,6 +369,7 @@ __device__ inline void vl_backup_edges(const EngineParams &P, const VlParams &V,
     const float fa = 1.0f - sc0, fb = 1.0f - fa, fc = 1.0f - fb;
     const int *path = V.path + (base + (size_t)(lane < k ? lane : 0)) * V.path_cap;
     const int maxlen = (int)wave_max_u32((u32)len);
+    bool fresh = false;  // the path's last edge had no visit before this batch: its child was created by the batch
     for (int d = 0; d < maxlen; d++) {
         const bool on = d < len;
         const u32 e = on ? (u32)path[d] : NONE;
@@ -308,12 +397,16 @@ __device__ inline void vl_backup_edges(const EngineParams &P, const VlParams &V,
                 }
             }
         }
+        if (on && d == len - 1)
+            fresh = (z & 0xFFFFu) == (u32)V.vl * paths;
         if (leader) {
             rec[1] = f2u(W);
             rec[2] = z + adds - (u32)V.vl * paths;  // (visits: the low half; never borrows from the child id)
         }
     }
     s.root_visits += (int)wave_sum_u32((counted && len > 0) ? 1u : 0u);
+    if (V.solver)
+        vl_prove(P, V, g, A, k, kind, len, leaf, fresh);
     s.leaf_kind = AZH_LEAF_NONE;
     s.path_len = 0;
 }

@@ -38,6 +38,7 @@ NO_MOVE = 0xFFFF            # a slot azh_engine_play_moves leaves alone
 PV_MAX = 32
 ROOT_REPORT_PV = 4 + 4 * MAX_MOVES
 ROOT_REPORT_WORDS = ROOT_REPORT_PV + 1 + 2 * PV_MAX
+ROOT_PROOF_WORDS = 1 + MAX_MOVES   # azh_engine_root_proofs
 STAT_NAMES = ["steps", "nn_evals", "levels", "children", "new_moves", "plies", "games", "dropped",
               "edge_overflow", "reroot_nodes", "reroot_edges", "ring_overflow", "cache_hits", "parked", "reroot_spills"]
 
@@ -130,6 +131,9 @@ SIGNATURES = {
     "azh_engine_set_leaf_batch": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
     "azh_engine_batch_leaves": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "azh_engine_set_batch_evals": (ctypes.c_int, [_vp, _vp, _vp]),
+    "azh_engine_set_solver": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "azh_engine_proof_stats": (ctypes.c_int, [_vp, _vp]),
+    "azh_engine_root_proofs": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
     "azh_engine_play_moves": (ctypes.c_int, [_vp, _vp, _vp]),
     "azh_engine_root_report": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
     "azh_engine_game_state": (ctypes.c_int, [_vp, ctypes.c_int, _P(GameState)]),
@@ -434,6 +438,25 @@ class Engine:
         search").  Between iterations only; K = 1 is the one-leaf search."""
         check(load().azh_engine_set_leaf_batch(self.h, int(leaves_per_game), int(virtual_loss)))
         self.K = int(leaves_per_game)
+
+    def set_solver(self, on=True):
+        """Proven wins and losses in the tree ("Proven wins and losses").  While it is on every K, 1 included,
+        runs through the leaf-parallel kernel (batch_leaves / set_batch_evals).  Between iterations only."""
+        check(load().azh_engine_set_solver(self.h, 1 if on else 0))
+
+    def proof_stats(self):
+        """-> {"proven_nodes", "proven_hits"}: nodes the proof pass proved; paths that ended at a proven node."""
+        out = np.zeros(2, dtype=np.uint64)
+        check(load().azh_engine_proof_stats(self.h, _ptr(out)))
+        return {"proven_nodes": int(out[0]), "proven_hits": int(out[1])}
+
+    def root_proofs(self, first=0, n=None):
+        """-> [(root value, child values (M,) int32 in root edge order)] for the slots first .. first + n - 1: 0 not decided,
+        +1 / -1 the side to move at that node wins / loses (azh_engine_root_proofs)."""
+        n = self.G - first if n is None else n
+        out = np.zeros((max(n, 1), ROOT_PROOF_WORDS), dtype=np.int32)
+        check(load().azh_engine_root_proofs(self.h, int(first), int(n), _ptr(out)))
+        return [(int(out[i, 0]), out[i, 1:].copy()) for i in range(n)]
 
     def batch_leaves(self):
         """-> kind (G, K) int32, leaf boards (G, K, 2) u64 (mover, opponent), leaf edge (G, K) u32 of the current batch."""

@@ -13,6 +13,10 @@ at every `go` the searcher walks from the position its tree is rooted at to the 
 or one or two moves away (engine.set_state's grandchild rule, engine.py:452-472, and the one-move case), played on the
 device with azh_engine_play_moves so that the subtree, its counts and priors are kept — and starts a fresh tree only when
 the new position is not there.  The root's edges and the principal variation come from azh_engine_root_report.
+
+With `solver` (an option, off by default) the search proves wins and losses in its tree ("Proven wins and
+losses"; every K then runs through the leaf-parallel kernel): a move that is proven to win is played without sampling, a
+root that is proven lost plays its most visited move, and a timed search stops as soon as the root is proven.
 """
 import random
 import time
@@ -149,7 +153,7 @@ class Searcher:
                              # tree per visit (96 edge slots of 18 bytes per node, two arenas): at most about 210 MB
 
     def __init__(self, network_path, dtype="f16", symmetry_average=False, parallel_leaves=1, virtual_loss=1,
-                 reuse_tree=False, show_pv=False):
+                 reuse_tree=False, show_pv=False, solver=False):
         # parallel_leaves = K > 1: leaf-parallel search with virtual loss ("Leaf-parallel search"): up to K
         # leaves per iteration in one tower launch.  An extension; 1 is the reference's one-leaf search.
         if not 1 <= parallel_leaves <= link.MAX_LEAVES_PER_GAME or not 1 <= virtual_loss <= link.MAX_VIRTUAL_LOSS:
@@ -157,7 +161,13 @@ class Searcher:
                              % (link.MAX_LEAVES_PER_GAME, link.MAX_VIRTUAL_LOSS))
         if parallel_leaves > 1 and symmetry_average:
             raise ValueError("symmetry averaging is not available with parallel_leaves > 1")
+        if solver and symmetry_average:
+            raise ValueError("symmetry averaging is not available with the solver")
         self.parallel_leaves, self.virtual_loss = parallel_leaves, virtual_loss
+        # solver: proven wins and losses (azh_engine_set_solver).  last_proofs: (root value, [(move, value of the move's
+        # child for the side to move there)] in edge order) after the last search, None without the solver;
+        # last_proven: "win" / "loss" when genmove's move came from a proof, else None
+        self.solver, self.last_proofs, self.last_proven = solver, None, None
         # symmetry_average: every evaluation is nn_evals.evaluate (nn_evals.py:48-62); with one game the
         # eight images ride in the same tower launch, so it costs no time
         self.extra_flags = link.FLAG_SYMMETRY_AVG if symmetry_average else 0
@@ -201,6 +211,8 @@ class Searcher:
             self.engine = link.Engine(cfg)
             if self.parallel_leaves > 1:
                 self.engine.set_leaf_batch(self.parallel_leaves, self.virtual_loss)
+            if self.solver:
+                self.engine.set_solver(True)
         return self.engine
 
     def _bring_tree_to(self, pos):
@@ -256,17 +268,30 @@ class Searcher:
             if state.root_visits == rv:
                 break   # a finished root: nothing to search
             rv = state.root_visits
+            if seconds is not None and self._root_proven(eng):
+                break
         self.last_report = eng.root_report(0, 1)[0]
+        self._keep_proofs(eng, self.last_report.moves)
         self.last_inherited = inherited
         self.last_steps, self.last_seconds = rv - inherited, max(time.time() - start, 1e-9)
         return [(int(m), int(n)) for m, n in zip(self.last_report.moves, self.last_report.visits) if n > 0]
 
+    def _root_proven(self, eng):
+        return self.solver and eng.root_proofs(0, 1)[0][0] != 0
+
+    def _keep_proofs(self, eng, moves):
+        """last_proofs from the engine; `moves`: the root's moves in edge order."""
+        self.last_proofs = None
+        if self.solver:
+            root, kids = eng.root_proofs(0, 1)[0]
+            self.last_proofs = (root, [(int(m), int(kids[j])) for j, m in enumerate(moves)])
+
     def root_visits(self, pos, visits=None, seconds=None):
         """-> [(move u16, visits)] over the expanded root edges after the search."""
-        self.last_inherited, self.last_report, self.last_note = 0, None, None
+        self.last_inherited, self.last_report, self.last_note, self.last_proofs = 0, None, None, None
         if self.reuse_tree:
             return self._root_visits_reusing(pos, visits, seconds)
-        if self.parallel_leaves > 1:
+        if self.parallel_leaves > 1 or self.solver:   # (the solver runs every K through the leaf-parallel kernel)
             return self._root_visits_parallel(pos, visits, seconds)
         cap = visits if visits is not None else self.TIME_CAP_VISITS
         cfg = link.Config(games=1, visits=cap + 1, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
@@ -308,6 +333,8 @@ class Searcher:
         start = time.time()
         try:
             eng.set_leaf_batch(K, self.virtual_loss)
+            if self.solver:
+                eng.set_solver(True)
             eng.run(self.net, 1, self.dtype)  # the root evaluation
             rv = 0
             while rv < target and (seconds is None or time.time() - start < seconds):
@@ -320,10 +347,13 @@ class Searcher:
                 if now == rv:
                     break  # a finished root: nothing to search
                 rv = now
+                if seconds is not None and self._root_proven(eng):
+                    break
             eng.sync()
             boards, info, edges, moves = eng.tree(0)
             if self.show_pv:
                 self.last_report = eng.root_report(0, 1)[0]
+            self._keep_proofs(eng, moves[int(info[0, 0]):int(info[0, 0]) + int(info[0, 1] & 0xFFFF)])
         finally:
             eng.close()
         self.last_steps, self.last_seconds = rv, max(time.time() - start, 1e-9)
@@ -339,18 +369,30 @@ class Searcher:
         text = "info nodes %d inherited %d" % (r.root_visits, self.last_inherited)
         if len(r.pv):
             j = r.moves.tolist().index(int(r.pv[0]))
-            text += " score %.4f pv %s" % (2.0 * float(r.scores[j]) / float(r.visits[j]) - 1.0,
-                                          " ".join(encode_move(int(m)) for m in r.pv))
+            score = 2.0 * float(r.scores[j]) / float(r.visits[j]) - 1.0
+            if self.last_proofs is not None and self.last_proofs[1][j][1] != 0:
+                score = -float(self.last_proofs[1][j][1])   # a proven first edge: the child's mover loses = this side wins
+            text += " score %.4f pv %s" % (score, " ".join(encode_move(int(m)) for m in r.pv))
         return text
 
     def genmove(self, pos, visits=None, seconds=None, exponent=5.0):
         legal, result = pos.legal_moves()
+        self.last_proven = None
         if not legal:
-            self.last_inherited, self.last_report, self.last_note = 0, None, None
+            self.last_inherited, self.last_report, self.last_note, self.last_proofs = 0, None, None, None
             return 0xFFFF  # the reference answers "pass" when no edge was visited (engine.py:495-496)
         edges = self.root_visits(pos, visits=visits, seconds=seconds)
         if not edges:
             return legal[0]
+        if self.last_proofs is not None:
+            root, kids = self.last_proofs
+            winning = [mv for mv, v in kids if v == -1]
+            if winning:   # the first proven winning move in edge order, without sampling
+                self.last_proven = "win"
+                return winning[0]
+            if root == -1:   # every move loses: the most visited one, the first on a tie
+                self.last_proven = "loss"
+                return max(edges, key=lambda t: t[1])[0]
         # sample_with_exponential_weight (engine.py:532-548)
         total = float(sum(n for _, n in edges))
         max_visits = max(n for _, n in edges)
@@ -438,6 +480,8 @@ class Session:
         lines = ["info speed %f nps" % (speed,)]
         if getattr(self.searcher, "last_note", None):
             lines.append("info string %s" % (self.searcher.last_note,))
+        if getattr(self.searcher, "last_proven", None):
+            lines.append("info string proven %s" % (self.searcher.last_proven,))
         if getattr(self.searcher, "show_pv", False) and self.searcher.pv_line():
             lines.append(self.searcher.pv_line())
         return lines + ["bestmove %s" % (encode_move(move),)]

@@ -258,6 +258,32 @@ int azh_engine_batch_leaves(azh_engine *e, int32_t *kind, uint64_t *leaf_boards,
 /* evaluations of the batch from outside, by slot: logits [G K][833], values [G K] */
 int azh_engine_set_batch_evals(azh_engine *e, const float *logits, const float *values);
 
+/* Proven wins and losses in the tree (MCTS-solver; an extension, off by default; DESIGN.md, "Proven wins and losses").
+ * A node is DECIDED if it is a finished position or was PROVEN: after every batch's backup, for each path that ended at a
+ * decided node, the node's parent is a proven win (+1 for its side to move) if one of its children is decided with -1, and
+ * a proven loss (-1) if every one of its edges has a child decided with +1; a new proof is carried on towards the root.  A
+ * path that reaches a decided node other than the root ends there (AZH_LEAF_TERMINAL) and backs up the node's value; the
+ * root is always descended from.  Nothing else in the search changes: no move is pruned, W and n are the leaf-parallel
+ * search's.  A proven node keeps its edges and result 0; its value is word 3 of its azh_engine_tree info row (the bits of
+ * +-1.0f, as a finished position's terminal value) and the "finished" bit of the range word of the edge that leads to it
+ * (azh_engine_tree_raw) is set; both are carried through re-roots (the device's own moves and azh_engine_play_moves).
+ * While the solver is on, EVERY leaves_per_game — 1 included — runs through the leaf-parallel kernel: the step-wise calls
+ * are azh_engine_batch_leaves / _set_batch_evals with K = leaves_per_game slots per game.  Call between iterations only.
+ * Refused with AZH_FLAG_TWO_NETS, AZH_FLAG_EVAL_CACHE, AZH_FLAG_SYMMETRY_AVG and select_budget > 0.  Turning it off
+ * returns to the dispatch azh_engine_set_leaf_batch describes; marks already in the tree stay where they are (every tree
+ * kernel ends a path at them as at a finished position). */
+int azh_engine_set_solver(azh_engine *e, int on);
+/* Counters of the proof pass, summed over the game slots since the engine was created: nodes proven, and paths that ended
+ * at a proven node (a settled line hit again). */
+enum { AZH_PROOF_STAT_NODES = 0, AZH_PROOF_STAT_HITS = 1, AZH_PROOF_STAT_COUNT = 2 };
+int azh_engine_proof_stats(azh_engine *e, uint64_t *out /* [AZH_PROOF_STAT_COUNT] */);
+/* For the slots first_game .. first_game + n_games - 1, one record of AZH_ROOT_PROOF_WORDS i32 each: [0] the decided value
+ * of the root (0: not decided; +1 / -1: its side to move wins / loses — a finished root included), [1 + j], j < root edges,
+ * in edge order as azh_engine_root_report: the decided value of edge j's child, seen from the side to move THERE (-1: the
+ * move wins for the root's mover); 0 for an edge without a child, an undecided child and j >= root edges. */
+enum { AZH_ROOT_PROOF_WORDS = 1 + AZH_MAX_MOVES };
+int azh_engine_root_proofs(azh_engine *e, int first_game, int n_games, int32_t *out /* [n_games][AZH_ROOT_PROOF_WORDS] */);
+
 /* Which tower the device-resident loop evaluates its leaves with: 0 the 3-board workgroups (throughput), 1 one board per
  * workgroup (latency: azh_net_forward_thin's kernel), -1 (default) by the engine's size — thin for engines of at most
  * AZH_THIN_MAX_GAMES game slots.  A host that knows its batch has thinned out (a match under a game limit whose last games

@@ -1,0 +1,104 @@
+"""Plain numpy restatement of the proof layer of the leaf-parallel search ("Proven wins and losses"), on top of
+tests/vl_reference.py, whose arrays-in / arrays-out style it keeps.
+
+A node is DECIDED if it is a finished position (result bits in info word 1, as ever) or if it was PROVEN: a proven node
+keeps its edges and its result bits 0, and carries its value — the bits of +1.0f (the side to move there wins) or -1.0f
+(it loses) — in info word 3, where a finished position carries its terminal value and every other node a 0.
+
+select() is vl_reference.select with one more way for a path to end: at a decided node that is not the root (TERMINAL;
+the backup then uses the node's value like a finished position's).  backup() is vl_reference.backup followed by the proof
+rule, applied in path order to the TERMINAL paths whose last node became decided in this batch (a finished position the
+batch created: node id >= b.nodes0; hitting a position settled earlier proves nothing new): from the parent X of the path's last node upwards, X is a proven win
+if some child of X is decided with value -1, a proven loss if every edge of X has a child and every child is decided with
+value +1; when X becomes proven the walk goes on with X's parent, otherwise (or when X was decided already) it stops.
+(An EVAL path ends at a node that has just been created, which is never decided: it proves nothing.)  Proofs only set
+marks: W and n are vl_reference's.
+"""
+import numpy as np
+
+from tests import vl_reference as vlr
+
+NONE = vlr.NONE
+LEAF_NONE, LEAF_EVAL, LEAF_TERMINAL, LEAF_ROOT, LEAF_COLLISION = (vlr.LEAF_NONE, vlr.LEAF_EVAL, vlr.LEAF_TERMINAL,
+                                                                  vlr.LEAF_ROOT, vlr.LEAF_COLLISION)
+WIN_BITS, LOSS_BITS = 0x3F800000, 0xBF800000   # +1.0f, -1.0f
+_PROVEN_FLAG = 0x80000000                      # select()'s private mark in a copy of info word 1: never handed out
+
+
+def decided_value(info_row):
+    """+1 / -1 for a decided node (finished or proven), seen from its side to move; 0 for an undecided one."""
+    w = int(info_row[3])
+    if (int(info_row[1]) >> 16) == 0 and w not in (WIN_BITS, LOSS_BITS):
+        return 0
+    return 1 if w == WIN_BITS else -1
+
+
+def is_proven(info_row):
+    """Decided without being a finished position."""
+    return (int(info_row[1]) >> 16) == 0 and int(info_row[3]) in (WIN_BITS, LOSS_BITS)
+
+
+def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers):
+    """vl_reference.select on a tree in which every proven node but the root ends a path like a finished position."""
+    boards, info, edges, moves = tree
+    info = np.array(info, dtype=np.uint32).reshape(-1, 4).copy()
+    marked = [n for n in range(1, len(info)) if is_proven(info[n])]
+    for n in marked:
+        info[n, 1] |= _PROVEN_FLAG   # vl_reference: "result != 0" ends the path, its value is info word 3
+    b = vlr.select((boards, info, edges, moves), root_visits, visits, K, VL, c_puct, tie_first, blockers)
+    b.nodes0 = len(info)   # nodes from this id on were created by this batch
+    for n in marked:
+        b.info[n][1] &= ~_PROVEN_FLAG
+    b.proven_hits = sum(1 for p, k in enumerate(b.kind) if k == LEAF_TERMINAL and b.leaf_node[p] in set(marked))
+    return b
+
+
+def prove(b):
+    """The proof rule after a batch's backup.  Sets info word 3 of the nodes it proves in b.info and returns them in the
+    order they were proven: [(node, value, path, levels above the path's last node)]."""
+    out = []
+    for p, path in enumerate(b.paths):
+        if b.kind[p] != LEAF_TERMINAL or not path or b.leaf_node[p] < b.nodes0:
+            continue
+        nodes = [0] + [b.child[e] for e in path]
+        for d in range(len(path) - 1, -1, -1):
+            x = nodes[d]
+            if decided_value(b.info[x]) != 0:
+                break
+            first, m = b.info[x][0], b.info[x][1] & 0xFFFF
+            vals = [decided_value(b.info[b.child[e]]) if b.child[e] != NONE else None for e in range(first, first + m)]
+            if any(v == -1 for v in vals):
+                value = 1
+            elif m > 0 and all(v == 1 for v in vals):
+                value = -1
+            else:
+                break
+            b.info[x][3] = WIN_BITS if value == 1 else LOSS_BITS
+            out.append((x, value, p, len(path) - d))
+    return out
+
+
+def backup(b, values):
+    """-> (edges (m, 4) u32, root visits added, proven [(node, value, path, levels)]); b.info carries the new marks."""
+    edges, added = vlr.backup(b, values)
+    return edges, added, prove(b)
+
+
+def expected_tree(b, values, post_tree):
+    """The whole dump after the backup and its proofs (the priors of the batch's new edges from `post_tree`, as
+    vl_reference.expected_tree) -> ((boards, info, edges, moves), root visits added, proven)."""
+    proven = prove(b)
+    tree, added = vlr.expected_tree(b, values, post_tree)
+    return tree, added, proven
+
+
+def finished_bits(tree):
+    """Per edge: 1 where the device's edge record must carry the "finished" bit of its child's range (bit 31 of word 3 of
+    azh_engine_tree_raw) — the child is decided — else 0."""
+    boards, info, edges, moves = tree
+    out = np.zeros(len(edges), dtype=np.uint32)
+    for e in range(len(edges)):
+        c = int(edges[e, 3])
+        if c != NONE and decided_value(info[c]) != 0:
+            out[e] = 1
+    return out

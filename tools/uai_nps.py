@@ -14,6 +14,12 @@ visits, new visits, wall time of the whole `go`; then the per-`go` overhead outs
 whole-tree copy (what every `go` costs without reuse) against the re-root + root report of the session engine.
 
     python tools/uai_nps.py --reuse-tree [--out profiles/uai_tree_reuse.txt]
+
+--solver measures what the proof layer costs ("Proven wins and losses"): every (position, K) of --ks is searched
+with the solver off and on, one after the other in the same process; the lines carry the proof counters.  With the solver
+on K = 1 runs through the leaf-parallel kernel, so its off/on pair is also the one-leaf kernels against k_vl_tree.
+
+    python tools/uai_nps.py --solver --ks 1,32 [--out profiles/uai_solver.txt]
 """
 import argparse
 import os
@@ -34,7 +40,7 @@ POSITIONS = [
 ]
 
 
-def search(net, pos, K, VL, seconds, dtype):
+def search(net, pos, K, VL, seconds, dtype, solver=False):
     """One timed search as uai.Searcher runs it, with every iteration's tree and tower launches timed."""
     target = min(uai.Searcher.TIME_CAP_VISITS * K, uai.Searcher.MAX_VISITS)
     cfg = link.Config(games=1, visits=target + (1 if K == 1 else 0), max_plies=400, edges_per_node=96, c_puct=1.0,
@@ -43,6 +49,8 @@ def search(net, pos, K, VL, seconds, dtype):
     eng = link.Engine(cfg)
     if K > 1:
         eng.set_leaf_batch(K, VL)
+    if solver:
+        eng.set_solver(True)
     eng.timing_reset(1)
     start = time.time()
     eng.run(net, 1, dtype)
@@ -57,13 +65,16 @@ def search(net, pos, K, VL, seconds, dtype):
         if now == rv:
             break
         rv = now
+        if solver and eng.root_proofs(0, 1)[0][0] != 0:   # as uai.Searcher: a timed search ends once the root is proven
+            break
     eng.sync()
     elapsed = time.time() - start
     tm = eng.timing()
     coll = eng.collisions()
     steps = eng.stats()["steps"]
+    proofs = eng.proof_stats()
     eng.close()
-    return dict(visits=rv, seconds=elapsed, iterations=iters, tree_ms=tm["select_ms"] / max(tm["iterations"], 1),
+    return dict(proofs=proofs, visits=rv, seconds=elapsed, iterations=iters, tree_ms=tm["select_ms"] / max(tm["iterations"], 1),
                 tower_ms=tm["net_ms"] / max(tm["iterations"], 1), collisions=coll, paths=steps, capped=rv >= target)
 
 
@@ -192,6 +203,7 @@ def reuse_report(net, conv, bn, movetime_ms, out_path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reuse-tree", action="store_true", help="measure tree reuse across the moves of a fixed line instead")
+    ap.add_argument("--solver", action="store_true", help="every (position, K) with the proof layer off and on")
     ap.add_argument("--movetime-ms", type=int, default=1000)
     ap.add_argument("--ks", default="1,8,16,32,48,64")
     ap.add_argument("--virtual-loss", type=int, default=1)
@@ -209,6 +221,26 @@ def main():
              % (a.movetime_ms, a.virtual_loss),
              "# columns: position K visits/s  iterations  tree ms/it  tower ms/it  collisions/path  capped  ratio-to-K1"]
     search(net, uai.Position.from_fen(POSITIONS[0][1]), 1, 1, 0.2, dtype)  # warm-up (code objects, allocations)
+    if a.solver:
+        lines[1] = "# columns: position K solver visits/s  iterations  tree ms/it  tower ms/it  proven nodes  proven hits  on/off"
+        search(net, uai.Position.from_fen(POSITIONS[0][1]), 1, 1, 0.2, dtype, solver=True)
+        for name, fen in POSITIONS:
+            pos = uai.Position.from_fen(fen)
+            for K in ks:
+                off = None
+                for on in (False, True):
+                    r = search(net, pos, K, a.virtual_loss, a.movetime_ms * 1e-3, dtype, solver=on)
+                    nps = r["visits"] / r["seconds"]
+                    off = nps if not on else off
+                    line = "%-6s K=%-3d solver=%d %9.0f visits/s  %6d it  tree %.4f  tower %.4f  proven %d  hits %d  x%.3f" % (
+                        name, K, int(on), nps, r["iterations"], r["tree_ms"], r["tower_ms"], r["proofs"]["proven_nodes"],
+                        r["proofs"]["proven_hits"], nps / off)
+                    print(line, flush=True)
+                    lines.append(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     for name, fen in POSITIONS:
         pos = uai.Position.from_fen(fen)
         base = None

@@ -22,7 +22,7 @@ def main(options):
     selfplay.select_device(0)
     searcher = uai.Searcher(options.network_path, dtype=options.dtype, symmetry_average=options.symmetry_average,
                             parallel_leaves=options.parallel_leaves, virtual_loss=options.virtual_loss,
-                            reuse_tree=options.reuse_tree, show_pv=options.show_pv)
+                            reuse_tree=options.reuse_tree, show_pv=options.show_pv, solver=options.solver)
     session = uai.Session(searcher, visits=options.visits, safety_ms=options.safety_ms, show_game=options.show_game,
                           log=sys.stderr)
     session.serve(sys.stdin, sys.stdout)
@@ -45,6 +45,9 @@ if __name__ == "__main__":
                           "is the old root or one or two moves below it (engine.py:452-472); --visits N then means N MORE steps")
     cli.add_argument("--show-pv", action="store_true",
                      help="before bestmove, print `info nodes <root visits> inherited <n> score <q> pv <moves>`")
+    cli.add_argument("--solver", action="store_true",
+                     help="prove wins and losses in the search tree (MCTS-solver; extension): a proven winning move is played "
+                          "without sampling (`info string proven win`), a timed search stops once the root is proven")
     cli.add_argument("--dtype", default="f16", choices=["bf16", "f16", "f32"],
                      help="tower arithmetic (extension).  Match play defaults to f16: with a trained net the f16 search picks "
                           "the f32 search's move in 100 %% of test positions, bf16 in 96 %% (DESIGN.md section 5); bf16 is 3-6 %% faster")
