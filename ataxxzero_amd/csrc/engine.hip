@@ -17,9 +17,9 @@
 // iteration as TWO launches on one stream — the fused tower, then k_tree = backup + mark + the
 // next select + the leaf-list compaction, one wave per game, four games per workgroup — with the
 // queued moves (advance_game, engine_device.h) played by the first workgroups of the tower launch.  The step-wise API
-// (azh_engine_select / _backup, used by the lock-step parity tests and the reference ABI) runs
-// the same device functions as separate kernels: k_select -> k_compact -> k_advance_list ->
-// (evaluator) -> k_backup -> k_mark.
+// (azh_engine_select / _backup, used by the lock-step parity tests and the reference ABI) launches
+// the same k_tree one half at a time (enqueue_tree): mode 2 (select + compaction) -> k_advance_list ->
+// (evaluator) -> mode 1 (backup + mark).
 //
 // HBM layout (per game, two ping-pong arenas so re-rooting compacts by copying):
 //   node_board [2][G][node_cap]  16 B  x stones | turn<<63, o stones
@@ -601,32 +601,6 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
     return need;
 }
 
-// Dense, game-ordered list of the games whose leaf needs the evaluator.
-__global__ __launch_bounds__(1024) void k_compact(const int *need, int G, int *list, int *count, int cls, int any)
-{
-    __shared__ int s_sum[1024];
-    const int t = threadIdx.x;
-    const int c = (G + 1023) / 1024;
-    const int lo = t * c, hi = min(G, lo + c);
-    int cnt = 0;
-    for (int i = lo; i < hi; i++)
-        cnt += any ? need[i] != 0 : need[i] == cls;
-    s_sum[t] = cnt;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = t >= off ? s_sum[t - off] : 0;
-        __syncthreads();
-        s_sum[t] += v;
-        __syncthreads();
-    }
-    int base = s_sum[t] - cnt;
-    for (int i = lo; i < hi; i++)
-        if (any ? need[i] != 0 : need[i] == cls)
-            list[base++] = i;
-    if (t == 1023)
-        *count = s_sum[1023];
-}
-
 // ------------------------------------------------------------------ priors + backup
 
 // Evaluations::populate (:204-271): the priors of `node` from one row of logits — a softmax over the legal moves' logits,
@@ -779,24 +753,8 @@ __device__ inline void backup_game(const EngineParams &P, int g, azh_game_state 
     s.leaf_kind = AZH_LEAF_NONE;
 }
 
-// The tree phases as kernels (step-wise API) and fused (device-resident loop): one wave owns a game through
-// backup -> mark -> select, so a step costs one launch instead of three.
-__global__ __launch_bounds__(WAVE) void k_select(EngineParams P)
-{
-    __shared__ u16 s_moves[MAX_MOVES];  // the move list of the node being expanded: all the scratch a descent needs
-    azh_game_state s = P.gs[blockIdx.x];
-    select_game(P, blockIdx.x, s, s_moves);
-}
-
-__global__ __launch_bounds__(WAVE) void k_backup(EngineParams P)
-{
-    const int g = blockIdx.x;
-    azh_game_state s = P.gs[g];
-    const int kind = s.leaf_kind;
-    backup_game(P, g, s);
-    if (kind != AZH_LEAF_NONE && kind != AZH_LEAF_DESCENT && threadIdx.x == 0)
-        P.gs[g] = s;
-}
+// The tree phases (backup_game, mark_game, select_game) run in one kernel, k_tree below, for the device-resident loop
+// and the step-wise API alike; only the queued re-roots have a kernel of their own (k_advance_list).
 
 // while (root.all_edge_visits < global_visits) step();  (:522-525): once the threshold is reached the move is due.
 // The game is only MARKED here (phase 2) and queued; the next select gives it no leaf, and the re-root
@@ -810,16 +768,6 @@ __device__ inline void mark_game(const EngineParams &P, int g, azh_game_state &s
         if (lane_id() == 0)
             P.adv_list[atomicAdd(P.adv_count, 1)] = g;
     }
-}
-
-__global__ __launch_bounds__(WAVE) void k_mark(EngineParams P)
-{
-    const int g = blockIdx.x;
-    azh_game_state s = P.gs[g];
-    const int phase = s.phase;
-    mark_game(P, g, s, P.force[g]);
-    if (s.phase != phase && threadIdx.x == 0)
-        P.gs[g] = s;
 }
 
 __global__ __launch_bounds__(WAVE) void k_advance_list(EngineParams P)
@@ -1039,8 +987,8 @@ __global__ __launch_bounds__(WAVE) void k_root_report(EngineParams P, int first_
     }
 }
 
-// The dense, game-ordered leaf list(s) of k_compact, written inside the tree launch by the workgroup that finishes
-// last.  Every workgroup ORs its games' need bits into a bit mask (one returning agent-scope atomic per workgroup,
+// The dense, game-ordered list(s) of the games whose leaf needs the evaluator (need_eval != 0; with two nets one list
+// per class), written inside the tree launch by the workgroup that finishes last.  Every workgroup ORs its games' need bits into a bit mask (one returning agent-scope atomic per workgroup,
 // performed before it draws its ticket from an agent-scope counter); the workgroup whose ticket is the last reads the
 // mask — 16 bytes per 128 games — expands it in game order and clears it for the next launch.  Atomics and L1-bypassing
 // loads on both sides, so no fence is needed (MI355X_MICROARCH.md, hand-off forms).  One kernel and one kernel boundary
@@ -1094,6 +1042,25 @@ __device__ inline void compact_leaves(const EngineParams &P, int two, int *s_cnt
             *P.leaf_count2 = t2;
         __hip_atomic_store(&P.tree_done[TICKET_SHARDS * TICKET_STRIDE], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+// A tree workgroup's ticket, drawn by its thread 0 behind its ORs into need_mask (`seen`: what those fetch_ors returned):
+// whether this workgroup is the last of the launch, the one that calls compact_leaves.
+__device__ inline int last_tree_workgroup(const EngineParams &P, u32 seen)
+{
+    // the ORs have returned, i.e. have been performed, before the ticket is drawn
+    asm volatile("s_waitcnt vmcnt(0)" : : "v"(seen) : "memory");
+    // two-level ticket: the workgroup that completes its shard draws a ticket of the top counter
+    const int shard = (int)(blockIdx.x % TICKET_SHARDS);
+    const int in_shard = ((int)gridDim.x - 1 - shard) / TICKET_SHARDS + 1;
+    int last = 0;
+    if (__hip_atomic_fetch_add(&P.tree_done[shard * TICKET_STRIDE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == in_shard - 1) {
+        __hip_atomic_store(&P.tree_done[shard * TICKET_STRIDE], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int shards = min((int)gridDim.x, TICKET_SHARDS);
+        last = __hip_atomic_fetch_add(&P.tree_done[TICKET_SHARDS * TICKET_STRIDE], 1, __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT) == shards - 1;
+    }
+    return last;
 }
 
 // The tree phase of a search iteration as ONE launch: a wave owns a game through backup -> "is the move due?" ->
@@ -1162,19 +1129,7 @@ __global__ __launch_bounds__(TREE_WAVES * WAVE) __attribute__((amdgpu_waves_per_
         if (m2)
             seen |= __hip_atomic_fetch_or(&P.need_mask[P.mask_words + (g0 >> 5)], m2 << (g0 & 31), __ATOMIC_RELAXED,
                                           __HIP_MEMORY_SCOPE_AGENT);
-        // the ORs have returned, i.e. have been performed, before the ticket is drawn
-        asm volatile("s_waitcnt vmcnt(0)" : : "v"(seen) : "memory");
-        // two-level ticket: the workgroup that completes its shard draws a ticket of the top counter
-        const int shard = (int)(blockIdx.x % TICKET_SHARDS);
-        const int in_shard = ((int)gridDim.x - 1 - shard) / TICKET_SHARDS + 1;
-        int last = 0;
-        if (__hip_atomic_fetch_add(&P.tree_done[shard * TICKET_STRIDE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == in_shard - 1) {
-            __hip_atomic_store(&P.tree_done[shard * TICKET_STRIDE], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int shards = min((int)gridDim.x, TICKET_SHARDS);
-            last = __hip_atomic_fetch_add(&P.tree_done[TICKET_SHARDS * TICKET_STRIDE], 1, __ATOMIC_RELAXED,
-                                          __HIP_MEMORY_SCOPE_AGENT) == shards - 1;
-        }
-        s_last = last;
+        s_last = last_tree_workgroup(P, seen);
     }
     __syncthreads();
     if (s_last)
@@ -1473,8 +1428,6 @@ extern "C" void azh_engine_destroy(azh_engine *e)
 extern "C" int azh_engine_node_cap(const azh_engine *e) { return e ? e->P.node_cap : -1; }
 extern "C" int azh_engine_edge_cap(const azh_engine *e) { return e ? e->P.edge_cap : -1; }
 
-static int enqueue_compact(azh_engine *e);
-
 constexpr int ADV_GRID = 64;  // one wave each; a search iteration queues G * (1 / visits + ...) re-roots: about 11 at 4096 games
 
 // the queued re-roots, on `stream` (always after a select has passed over the queued games); `done`, if given, is
@@ -1487,31 +1440,34 @@ static int enqueue_advance(azh_engine *e, hipStream_t stream, hipEvent_t done = 
     return 0;
 }
 
-static int enqueue_select(azh_engine *e)
-{
-    if (e->vl_active) {
-        hipLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, e->P, e->V, 2);
-        AZH_HIP(hipGetLastError());
-        return enqueue_advance(e, e->stream);
-    }
-    hipLaunchKernelGGL(k_select, dim3(e->P.G), dim3(WAVE), 0, e->stream, e->P);
-    if (enqueue_compact(e))
-        return -1;
-    return enqueue_advance(e, e->stream);
-}
+// one leaf list per net (arena)
+static int two_lists(const azh_engine *e) { return (e->P.flags & AZH_FLAG_TWO_NETS) && e->arena_lists; }
 
-static int enqueue_backup(azh_engine *e)
+// One tree launch on the engine's stream, for the device-resident loop and the step-wise API alike.  mode bit 0: backup +
+// mark, bit 1: select + leaf list; ev (or nullptr) is signalled by the kernel's own completion.
+static int enqueue_tree(azh_engine *e, int mode, bool stamped = false, hipEvent_t ev = nullptr)
 {
-    if (e->vl_active) {
-        hipLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, e->P, e->V, 1);
-        AZH_HIP(hipGetLastError());
-        return 0;
-    }
-    hipLaunchKernelGGL(k_backup, dim3(e->P.G), dim3(WAVE), 0, e->stream, e->P);
-    hipLaunchKernelGGL(k_mark, dim3(e->P.G), dim3(WAVE), 0, e->stream, e->P);
+    const int two = two_lists(e);
+    const bool small = e->P.G <= TREE_ONE_ROUND_GAMES;
+    const int waves = small ? TREE_WAVES_SMALL : TREE_WAVES_LARGE;
+    const dim3 grid((e->P.G + waves - 1) / waves), block(waves * WAVE);
+    if (e->vl_active)  // leaf-parallel search: one workgroup per game (not stamped: azh_engine_tree_stamps refuses)
+        hipExtLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, nullptr, ev, 0, e->P, e->V, mode);
+    else if (stamped && small)
+        hipExtLaunchKernelGGL((k_tree<true, TREE_WAVES_SMALL>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
+    else if (stamped)
+        hipExtLaunchKernelGGL((k_tree<true, TREE_WAVES_LARGE>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
+    else if (small)
+        hipExtLaunchKernelGGL((k_tree<false, TREE_WAVES_SMALL>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
+    else
+        hipExtLaunchKernelGGL((k_tree<false, TREE_WAVES_LARGE>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
     AZH_HIP(hipGetLastError());
     return 0;
 }
+
+static int enqueue_select(azh_engine *e) { return enqueue_tree(e, 2) || enqueue_advance(e, e->stream); }
+
+static int enqueue_backup(azh_engine *e) { return enqueue_tree(e, 1); }
 
 extern "C" int azh_engine_select(azh_engine *e, int32_t *n_leaves_out)
 {
@@ -1614,18 +1570,6 @@ extern "C" int azh_engine_backup(azh_engine *e)
     return 0;
 }
 
-static int enqueue_compact(azh_engine *e)
-{
-    const int two = (e->P.flags & AZH_FLAG_TWO_NETS) && e->arena_lists;
-    hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, e->stream, (const int *)e->P.need_eval, e->P.G, e->P.leaf_list,
-                       e->P.leaf_count, 1, two ? 0 : 1);
-    if (two)
-        hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, e->stream, (const int *)e->P.need_eval, e->P.G,
-                           e->P.leaf_list2, e->P.leaf_count2, 2, 0);
-    AZH_HIP(hipGetLastError());
-    return 0;
-}
-
 // Device-resident loop.  Iteration = select -> tower -> backup -> "is the move due?"; consecutive iterations run
 // backup + mark + the next select of one game in a single fused launch (k_tree), and the queued re-roots
 // inside the tower launch that follows (its first workgroups).
@@ -1646,29 +1590,9 @@ struct RunLoop {
     azh_engine *e;
     azh_net *net_a, *net_b;
     int dtype, iterations;
-    int two = 0;
     bool pair = false, side = false;
     AdvanceHook hook;
 
-    // one fused tree launch; ev (or nullptr) is signalled by the kernel's own completion
-    void launch_tree(bool stamped, int mode, hipEvent_t ev)
-    {
-        if (e->vl_active) {  // leaf-parallel search: one workgroup per game (not stamped: azh_engine_tree_stamps refuses)
-            hipExtLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, nullptr, ev, 0, e->P, e->V, mode);
-            return;
-        }
-        const bool small = e->P.G <= TREE_ONE_ROUND_GAMES;
-        const int waves = small ? TREE_WAVES_SMALL : TREE_WAVES_LARGE;
-        const dim3 grid((e->P.G + waves - 1) / waves), block(waves * WAVE);
-        if (stamped && small)
-            hipExtLaunchKernelGGL((k_tree<true, TREE_WAVES_SMALL>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
-        else if (stamped)
-            hipExtLaunchKernelGGL((k_tree<true, TREE_WAVES_LARGE>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
-        else if (small)
-            hipExtLaunchKernelGGL((k_tree<false, TREE_WAVES_SMALL>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
-        else
-            hipExtLaunchKernelGGL((k_tree<false, TREE_WAVES_LARGE>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
-    }
     // side-stream mode: ev_sel is signalled by the tree launch itself, ev_adv by the re-root launch (hipExtLaunchKernelGGL's
     // stop event: no event-record packets at the kernel boundaries of the main stream)
     int side_advance()
@@ -1681,18 +1605,18 @@ struct RunLoop {
 
     int begin()
     {
-        two = (e->P.flags & AZH_FLAG_TWO_NETS) && e->arena_lists;  // one leaf list per net
         // arena: the two nets' towers as one launch (AZH_ARENA_PAIR=0: two launches back to back, for A/B runs)
         const char *pair_s = getenv("AZH_ARENA_PAIR");  // (read per call: a test switches it inside one process)
         const bool pair_env = !(pair_s && atoi(pair_s) == 0);
-        pair = pair_env && two && !(e->P.flags & AZH_FLAG_SYMMETRY_AVG);
+        pair = pair_env && two_lists(e) && !(e->P.flags & AZH_FLAG_SYMMETRY_AVG);
         const char *side_s = getenv("AZH_REROOT_SIDE_STREAM");
         side = side_s && atoi(side_s) != 0;
         hook.workers = e->adv_workers;
         hook.at_head = 1;   // (decided per launch by the tower's launch functions: in front only where workgroups queue for slots)
         hook.P = e->P;
         e->unfetched_work = true;  // (every path that can finish a game goes through a re-root)
-        launch_tree(false, 2, side ? e->ev_sel : nullptr);  // select + leaf list
+        if (enqueue_tree(e, 2, false, side ? e->ev_sel : nullptr))  // select + leaf list
+            return -1;
         return side_advance();
     }
 
@@ -1727,13 +1651,11 @@ struct RunLoop {
         const int last = it + 1 == iterations;
         if (side)
             AZH_HIP(hipStreamWaitEvent(e->stream, e->ev_adv, 0));
-        if (e->stamp_next && !last) {
-            launch_tree(true, 3, side ? e->ev_sel : nullptr);
+        const bool stamped = e->stamp_next && !last;
+        if (enqueue_tree(e, last ? 1 : 3, stamped, last || !side ? nullptr : e->ev_sel))
+            return -1;
+        if (stamped)
             e->stamp_next = false;
-        } else {
-            launch_tree(false, last ? 1 : 3, last || !side ? nullptr : e->ev_sel);
-        }
-        AZH_HIP(hipGetLastError());
         if (!last && side_advance()) return -1;
         if (rec) {
             e->samples++;

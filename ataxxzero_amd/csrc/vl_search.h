@@ -454,17 +454,7 @@ __global__ __launch_bounds__(VL_WAVES * WAVE) void k_vl_tree(EngineParams P, VlP
                 seen |= __hip_atomic_fetch_or(&P.need_mask[bit >> 5], bits << off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             done += take;
         }
-        asm volatile("s_waitcnt vmcnt(0)" : : "v"(seen) : "memory");
-        const int shard = (int)(blockIdx.x % TICKET_SHARDS);
-        const int in_shard = ((int)gridDim.x - 1 - shard) / TICKET_SHARDS + 1;
-        int last = 0;
-        if (__hip_atomic_fetch_add(&P.tree_done[shard * TICKET_STRIDE], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == in_shard - 1) {
-            __hip_atomic_store(&P.tree_done[shard * TICKET_STRIDE], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int shards = min((int)gridDim.x, TICKET_SHARDS);
-            last = __hip_atomic_fetch_add(&P.tree_done[TICKET_SHARDS * TICKET_STRIDE], 1, __ATOMIC_RELAXED,
-                                          __HIP_MEMORY_SCOPE_AGENT) == shards - 1;
-        }
-        s_last = last;
+        s_last = last_tree_workgroup(P, seen);
     }
     __syncthreads();
     if (s_last)

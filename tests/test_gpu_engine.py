@@ -216,6 +216,30 @@ def test_leaf_features_are_reference_rows():
         ge.backup()
 
 
+@pytest.mark.parametrize("games", [1, 3, 33, 130])
+def test_stepwise_leaf_list_at_the_edges_of_the_mask_geometry(games):
+    """The step-wise select's dense leaf list (need bits -> mask -> the last workgroup's expansion) where the geometry can
+    go wrong: fewer games than a workgroup's four waves, a partly filled last workgroup, a 32-game mask word crossed with a
+    partial workgroup, more than four mask words.  With 4 visits per move, moves come due every few iterations, at
+    different iterations in different games, so most selects leave some games without a leaf: the list is sparse, and the
+    oracle alone says which games are in it."""
+    oe, ge = make_pair(games=games, visits=4)
+    counts = []
+    for _ in range(40):
+        n_o, need_o = oe.select()
+        n = ge.select()
+        assert n == n_o
+        assert list(ge.leaf_features(n)[1]) == [g for g in range(games) if need_o[g]]
+        counts.append(n)
+        logits, values = synthetic_evals(oe.leaf_boards())
+        oe.backup(logits, values)
+        ge.set_evals(logits, values)
+        ge.backup()
+    assert min(counts) < games                                     # a select that left a game without a leaf ...
+    assert games == 1 or any(0 < n < games for n in counts)        # ... and one that left some with and some without
+    compare_all(oe, ge, range(games))
+
+
 @pytest.mark.parametrize("dtype,visits", [("bf16", 24), ("f16", 100)])
 def test_device_resident_selfplay_with_builtin_net(dtype, visits):
     conv, bn = model.random_init(2, 128, seed=2)

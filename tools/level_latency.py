@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Per-level cost of the PUCT descent: host-timed k_select launches against the deepest path of the launch."""
+"""Per-level cost of the PUCT descent: host-timed step-wise selects against the deepest path of the launch.  A select is
+k_tree in mode 2 — the descent of every game plus the leaf-list tail (need mask, tickets, the last workgroup's compaction) —
+followed by k_advance_list, so the fit's constant term includes that tail; the slope per level is the descent's."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

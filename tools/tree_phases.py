@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Warm self-play batch driven through the step-wise API (k_select / tower / k_backup / k_advance as separate
-launches), for a per-phase kernel trace: rocprofv3 --kernel-trace --stats -- python3 tools/tree_phases.py"""
+"""Warm self-play batch driven through the step-wise API (k_tree mode 2 = select + leaf list / k_advance_list / tower / k_tree mode 1 = backup + mark
+as separate launches), for a per-phase kernel trace: rocprofv3 --kernel-trace --stats -- python3 tools/tree_phases.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ataxxzero_amd import link, model, selfplay
