@@ -407,6 +407,14 @@ __host__ __device__ inline Philox4 philox(u32 k0, u32 k1, u32 c0, u32 c1, u32 c2
 constexpr u32 STREAM_SAMPLE = 1u;
 constexpr u32 STREAM_RANDOM_PLAY = 2u;
 constexpr u32 STREAM_RANDOM_PLY = 3u;
+constexpr u32 STREAM_PLAYOUT_CAP = 4u;
+
+// Playout cap randomization (azh_engine_set_playout_cap): is ply `ply` of game `uid` searched in FULL?  A pure function of
+// the engine's Philox key, so a trainer or a test restates it without a device (azh_playout_cap_kind).
+__host__ __device__ inline bool playout_cap_full(u32 k0, u32 k1, u32 uid, u32 ply, u32 full_per_65536)
+{
+    return (philox(k0, k1, uid, ply, STREAM_PLAYOUT_CAP, 0u).v[0] >> 16) < full_per_65536;
+}
 constexpr u32 STREAM_GAMMA = 0x10000u;
 
 // Gamma(alpha, 1), alpha < 1: Marsaglia-Tsang on alpha + 1 with a polar normal,

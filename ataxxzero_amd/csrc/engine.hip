@@ -114,6 +114,15 @@ __global__ __launch_bounds__(WAVE) void k_init(EngineParams P)
         P.stats[(size_t)g * NSTAT + k] = 0;
 }
 
+// azh_engine_set_playout_cap: the kind of the ply every slot is at (one thread per slot)
+__global__ void k_ply_kinds(EngineParams P)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < P.G)
+        P.ply_kind[g] = playout_cap_full(P.k0, P.k1, P.gs[g].uid, (u32)P.gs[g].ply, P.full_per_65536) ? PLY_FULL
+                                                                                                     : (u32)P.fast_visits;
+}
+
 // ------------------------------------------------------------------ select + expand
 
 // Q + U of one edge (total_action_score :310-324) — IEEE division and square root in the fixed order the oracle restates.
@@ -604,8 +613,9 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
 // ------------------------------------------------------------------ priors + backup
 
 // Evaluations::populate (:204-271): the priors of `node` from one row of logits — a softmax over the legal moves' logits,
-// identical to the reference's 833-way softmax renormalised over the legal moves — then, at the root (`root`), the
-// Dirichlet mix keyed by (uid, ply).  Wave-cooperative.
+// identical to the reference's 833-way softmax renormalised over the legal moves — then, at the root (`root`: the root of a
+// ply that gets noise — every ply, or with the playout cap on the FULL ones), the Dirichlet mix keyed by (uid, ply).
+// Wave-cooperative.
 __device__ inline void apply_priors(const EngineParams &P, const Arena &A, int node, const float *row, bool root, u32 uid,
                                     u32 ply)
 {
@@ -712,8 +722,8 @@ __device__ inline void apply_priors(const EngineParams &P, const Arena &A, int n
     }
 }
 
-// `s`: the game's state in the caller's registers (uniform over the lanes); updated, not stored.
-__device__ inline void backup_game(const EngineParams &P, int g, azh_game_state &s)
+// `s`: the game's state in the caller's registers (uniform over the lanes); updated, not stored.  `pk`: the ply's kind word.
+__device__ inline void backup_game(const EngineParams &P, int g, azh_game_state &s, u32 pk)
 {
     const int lane = lane_id();
     const int kind = s.leaf_kind;
@@ -722,7 +732,8 @@ __device__ inline void backup_game(const EngineParams &P, int g, azh_game_state 
     Arena A = arena_of(P, s.arena, g);
 
     if (kind == AZH_LEAF_EVAL || kind == AZH_LEAF_ROOT)
-        apply_priors(P, A, s.leaf_node, P.logits + (size_t)g * AZH_POLICY_SIZE, kind == AZH_LEAF_ROOT, s.uid, (u32)s.ply);
+        apply_priors(P, A, s.leaf_node, P.logits + (size_t)g * AZH_POLICY_SIZE, kind == AZH_LEAF_ROOT && (pk & PLY_FULL) != 0u,
+                     s.uid, (u32)s.ply);
 
     if ((P.flags & AZH_FLAG_EVAL_CACHE) && kind == AZH_LEAF_EVAL) {
         // the leaf now carries an evaluation: remember its value and enter it in the table
@@ -760,10 +771,11 @@ __device__ inline void backup_game(const EngineParams &P, int g, azh_game_state 
 // The game is only MARKED here (phase 2) and queued; the next select gives it no leaf, and the re-root
 // (advance_game) then runs from the queue in its own launch, beside the tower of the other games — a deep
 // subtree copy (one dependent round trip per tree level) no longer sits on every iteration's critical path.
-// `forced`: force[g], loaded by the caller beside the state.
-__device__ inline void mark_game(const EngineParams &P, int g, azh_game_state &s, int forced)
+// `forced`: force[g], loaded by the caller beside the state; `pk`: the ply's kind word (playout cap: a FAST ply's move is
+// due at fast_visits).
+__device__ inline void mark_game(const EngineParams &P, int g, azh_game_state &s, int forced, u32 pk)
 {
-    if (s.phase == 1 && s.leaf_kind != AZH_LEAF_DESCENT && (s.root_visits >= P.visits || forced != 0)) {
+    if (s.phase == 1 && s.leaf_kind != AZH_LEAF_DESCENT && (s.root_visits >= ply_threshold(P, pk) || forced != 0)) {
         s.phase = 2;
         if (lane_id() == 0)
             P.adv_list[atomicAdd(P.adv_count, 1)] = g;
@@ -841,6 +853,7 @@ __global__ __launch_bounds__(WAVE) void k_play_moves(EngineParams P, const u16 *
     RerootStats rs;
     const int result = reroot_game(P, g, L, s, A, B, A.nb[0], want, c, rs);
     s.ply = min(s.ply, P.max_plies - 1);
+    begin_ply(P, g, s.uid, s.ply);
     s.phase = result != 0 ? 3 : 0;
     s.leaf_kind = AZH_LEAF_NONE;  // (a descent parked by select_budget is given up with the tree it was in)
     s.leaf_node = 0;
@@ -1083,11 +1096,12 @@ __global__ __launch_bounds__(TREE_WAVES * WAVE) __attribute__((amdgpu_waves_per_
     if (g < P.G) {
         azh_game_state s = P.gs[g];
         const int forced = P.force[g];  // (same round trip as the state)
+        const u32 pk = ply_kind_of(P, g);
         if constexpr (STAMP) st[1] = tree_stamp();
         if (mode & 1) {
-            backup_game(P, g, s);
+            backup_game(P, g, s, pk);
             if constexpr (STAMP) st[2] = tree_stamp();
-            mark_game(P, g, s, forced);
+            mark_game(P, g, s, forced, pk);
         }
         if constexpr (STAMP) {
             st[3] = tree_stamp();
@@ -1903,9 +1917,48 @@ extern "C" int azh_engine_set_visits(azh_engine *e, int visits)
 {
     if (!e || visits < 1 || visits > e->cfg.visits)
         return azh_fail(-1, "azh_engine_set_visits: need 1 <= visits <= %d", e ? e->cfg.visits : 0);
+    if (visits < e->P.fast_visits)
+        return azh_fail(-2, "azh_engine_set_visits: %d is below the playout cap's fast_visits %d", visits, e->P.fast_visits);
     AZH_HIP(hipStreamSynchronize(e->stream));
     e->P.visits = visits;
     return 0;
+}
+
+// Playout cap randomization: FAST plies (threshold fast_visits, no root noise) and FULL plies (threshold `visits`, noise),
+// the kind a pure function of (seed, uid, ply).  Definition: the header and DESIGN.md.  Between iterations only.
+extern "C" int azh_engine_set_playout_cap(azh_engine *e, int fast_visits, int full_per_65536)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_set_playout_cap: null engine");
+    if (fast_visits < 0 || fast_visits > e->P.visits || full_per_65536 < 0 || full_per_65536 > 65536)
+        return azh_fail(-2, "azh_engine_set_playout_cap: need 0 <= fast_visits <= visits (%d) and 0 <= full_per_65536 <= 65536",
+                        e->P.visits);
+    if (e->selected)
+        return azh_fail(-3, "azh_engine_set_playout_cap: a selected batch awaits its backup");
+    if (fast_visits != 0 && (e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_ONE_RANDOM_MOVE)))
+        return azh_fail(-4, "azh_engine_set_playout_cap: not supported with %s",
+                        (e->P.flags & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS" : "AZH_FLAG_ONE_RANDOM_MOVE");
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_HIP(hipStreamSynchronize(e->stream2));
+    if (fast_visits == 0) {
+        e->P.fast_visits = 0;
+        e->P.full_per_65536 = 0;
+        return 0;
+    }
+    if (!e->P.ply_kind && dev_alloc(e, &e->P.ply_kind, (size_t)e->P.G))
+        return -1;
+    e->P.fast_visits = fast_visits;
+    e->P.full_per_65536 = (u32)full_per_65536;
+    hipLaunchKernelGGL(k_ply_kinds, dim3((e->P.G + 255) / 256), dim3(256), 0, e->stream, e->P);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// The kind of ply `ply` of game `uid` under `seed`: 1 FULL, 0 FAST.  Host arithmetic only.
+extern "C" int azh_playout_cap_kind(uint64_t seed, uint32_t uid, uint32_t ply, uint32_t full_per_65536)
+{
+    return playout_cap_full((u32)seed, (u32)(seed >> 32), uid, ply, full_per_65536) ? 1 : 0;
 }
 
 // At most `games` games are played: uids 0 .. games - 1 (slot g plays uids g, g + G, ...).  A slot whose next game
@@ -2216,6 +2269,21 @@ extern "C" int azh_engine_fetch(azh_engine *e)
 
 extern "C" long long azh_engine_implicit_fetches(const azh_engine *e) { return e ? e->implicit_fetches : -1; }
 
+// Diagnostic: the records an azh_engine_fetch has taken off the device and no drain has formatted yet, as they lie in the
+// ring (layout: azh_format_record_json); nothing is consumed.  For tests that read what a game line does not carry: uids,
+// visit counts, the plies' "full" words.
+extern "C" int azh_engine_staged_records(azh_engine *e, uint32_t *buf, int64_t cap, int64_t *words)
+{
+    if (!e || !words || (!buf && cap > 0))
+        return azh_fail(-1, "azh_engine_staged_records: null argument");
+    *words = (int64_t)e->staged.size();
+    if (*words > cap)
+        return azh_fail(-6, "azh_engine_staged_records: %lld words staged, the buffer has %lld", (long long)*words, (long long)cap);
+    if (*words)
+        memcpy(buf, e->staged.data(), (size_t)*words * 4);
+    return 0;
+}
+
 // the fetched records -> lines (in uid order where that is asked for); host work only
 static void format_staged(azh_engine *e)
 {
@@ -2244,9 +2312,9 @@ static void format_staged(azh_engine *e)
     const bool ids = (e->P.flags & AZH_FLAG_TWO_NETS) != 0;
     for (auto &o : order) {
         const uint32_t *rec = host.data() + o.second;
-        const bool dropped = rec[7] == 1;
+        const bool dropped = (rec[7] & 3u) == 1;
         std::string line = dropped ? std::string() : azh_format_game_json(rec, rec[5], ids);
-        if (rec[7] == 2 && !ids)
+        if ((rec[7] & 3u) == 2 && !ids)
             line.clear();  // a game that began at a loaded position: record drained and formatted like any other
                            // (the measured path does the same work per finished ply), but it is not a whole game.
                            // (The arena hands such games out: a match from given openings — uai_ringmaster.py:185-196 —

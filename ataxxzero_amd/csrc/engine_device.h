@@ -16,6 +16,8 @@ constexpr int REC_HDR_WORDS = 8;
 constexpr int REC_MAXD = 256;
 constexpr int REC_STRIDE_WORDS = REC_HDR_WORDS + REC_MAXD;
 constexpr u32 RING_MAGIC = 0x415A4847u;  // "AZHG"
+constexpr u32 REC_KIND_PLAYOUT_CAP = 4u;  // header word 7, beside its kind in bits 0-1: the game was played with the playout cap on
+                                          // (word 5 of every ply: 1 = FULL), and its line carries "full"
 constexpr int NSTAT = AZH_STAT_COUNT;
 constexpr int BFS_QL = 384;  // re-root frontier entries kept in LDS; later ones spill to bfs_spill in HBM
 
@@ -64,7 +66,28 @@ struct EngineParams {
     u64 *ring_head;
     u64 *stats;
     u32 *bfs_spill;  // [G][3][node_cap] frontier entries beyond BFS_QL
+    // playout cap randomization (azh_engine_set_playout_cap; DESIGN.md "Playout cap randomization"), off while fast_visits == 0
+    int fast_visits;       // root-visit threshold of a FAST ply (a FULL ply's is `visits`)
+    u32 full_per_65536;    // a ply is FULL iff (philox(uid, ply, STREAM_PLAYOUT_CAP).v[0] >> 16) < this
+    u32 *ply_kind;         // [G] the kind of the ply each slot is searching, derived where the ply begins (begin_ply): PLY_FULL,
+                           // or the FAST ply's threshold — the tree kernels read one word instead of running Philox per mark
 };
+
+constexpr u32 PLY_FULL = 0x80000000u;
+
+// A ply of slot g begins (game start and restart, after a re-root, a loaded position, the setter itself): its kind.
+__device__ inline void begin_ply(const EngineParams &P, int g, u32 uid, int ply)
+{
+    if (P.fast_visits != 0 && lane_id() == 0) {
+        asm volatile("" : "+v"(uid));  // the Philox block in vector registers: its callers have no scalar registers to spare
+        P.ply_kind[g] = playout_cap_full(P.k0, P.k1, uid, (u32)ply, P.full_per_65536) ? PLY_FULL : (u32)P.fast_visits;
+    }
+}
+
+// The kind word of slot g's ply as the tree kernels use it (g wave-uniform: a scalar load); PLY_FULL while the mode is off.
+__device__ inline u32 ply_kind_of(const EngineParams &P, int g) { return P.fast_visits != 0 ? P.ply_kind[g] : PLY_FULL; }
+// root visits at which the ply's move is due
+__device__ inline int ply_threshold(const EngineParams &P, u32 kind) { return (kind & PLY_FULL) ? P.visits : (int)kind; }
 
 // Per-block (= per-game wave) LDS scratch shared by the tree phases.
 struct TreeLds {
@@ -205,6 +228,7 @@ __device__ inline void init_game_at(const EngineParams &P, int g, u32 uid, azh_g
     }
     if (P.flags & AZH_FLAG_EVAL_CACHE)
         tt_clear(tt_of(P, 0, g), P.tt_size);
+    begin_ply(P, g, uid, ply);
     wave_sync();
     s.phase = 0;
     s.arena = 0;
@@ -528,7 +552,7 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
         rec[2] = (u32)rootw.y;
         rec[3] = (u32)(rootw.y >> 32);
         rec[4] = (mv & 0xFFFFu) | ((u32)nd << 16);
-        rec[5] = 0;
+        rec[5] = (P.fast_visits != 0 && (P.ply_kind[g] & PLY_FULL)) ? 1u : 0u;  // playout cap: 1 = searched in full
         rec[6] = 0;
         rec[7] = 0;
     }
@@ -584,7 +608,8 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
                 out[4] = (u32)result;
                 out[5] = (u32)words;
                 out[6] = (P.flags & AZH_FLAG_ONE_RANDOM_MOVE) ? (u32)random_ply_of(P, s.uid) + 1u : 0u;
-                out[7] = loaded ? 2u : 0u;    // 2: partial game (begins at a loaded position): formatted by the host, not written
+                out[7] = (loaded ? 2u : 0u)   // 2: partial game (begins at a loaded position): formatted by the host, not written
+                         | (P.fast_visits != 0 ? REC_KIND_PLAYOUT_CAP : 0u);
             }
             u32 pos = 8;
             for (int p = p0; p < s.ply; p++) {
@@ -608,6 +633,7 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
         init_game(P, g, s.uid + (u32)P.G, s, s_moves);
     } else {
         s.phase = 0;
+        begin_ply(P, g, s.uid, s.ply);
     }
     if (lane == 0) {
         P.force[g] = 0;

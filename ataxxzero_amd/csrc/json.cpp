@@ -205,13 +205,14 @@ static void append_double(double v, std::string &out)
 }
 
 // rec: ring record (engine.hip k_advance): 8-word header {magic, slot, uid, plies,
-// result, words, random_ply + 1 (0 = none), 0} then per ply {x lo, x hi, o lo, o hi, move | nd << 16, 0,
-// nd x (move | visits << 16)}.
+// result, words, random_ply + 1 (0 = none), kind (1 dropped, 2 partial; | 4: playout cap on)} then per ply {x lo, x hi,
+// o lo, o hi, move | nd << 16, full (playout cap: 1 = searched in full), nd x (move | visits << 16)}.
 // with_ids (arena): two extra keys, "slot" and "uid", so the caller can tell which net had x.
 std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_ids)
 {
     const uint32_t plies = rec[3], result = rec[4];
-    std::string boards = "[", dists = "[", moves = "[";
+    std::string boards = "[", dists = "[", moves = "[", full = "[";
+    const bool capped = (rec[7] & 4u) != 0;  // playout cap (engine_device.h REC_KIND_PLAYOUT_CAP): word 5 of a ply = searched in full
     size_t pos = 8;
     for (uint32_t p = 0; p < plies && pos + 6 <= words; p++) {
         const uint64_t x = (uint64_t)rec[pos] | ((uint64_t)rec[pos + 1] << 32);
@@ -221,7 +222,9 @@ std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_id
             boards += ',';
             dists += ',';
             moves += ',';
+            full += ',';
         }
+        full += rec[pos + 5] ? '1' : '0';
         boards += '[';
         for (int y = 0; y < 7; y++)
             for (int xx = 0; xx < 7; xx++) {
@@ -256,7 +259,8 @@ std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_id
         dists += '}';
         pos += 6 + nd;
     }
-    std::string out = "{\"boards\":" + boards + "],\"dists\":" + dists + "],\"moves\":" + moves + "],\"result\":";
+    std::string out = "{\"boards\":" + boards + "],\"dists\":" + dists + (capped ? "],\"full\":" + full : std::string()) +
+                      "],\"moves\":" + moves + "],\"result\":";
     if (rec[6])  // ONE_RANDOM_MOVE games (cpp/self_play_client.cpp:517); keys stay sorted as nlohmann emits them
         out = out.substr(0, out.size() - 9) + "\"random_ply\":" + std::to_string(rec[6] - 1) + ",\"result\":";
     out += std::to_string(result);
@@ -281,7 +285,7 @@ bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plie
     if (rec[7] == 1)  // the marker a dropped game leaves: a header and nothing else
         return rec[5] == 8;
     *why = "header fields out of range";
-    if (rec[7] > 2 || rec[4] > 2 || (max_plies && rec[3] > max_plies))
+    if ((rec[7] & ~4u) > 2 || (rec[7] & 3u) == 1 || rec[4] > 2 || (max_plies && rec[3] > max_plies))
         return false;
     *why = "a ply runs past the record's words";
     size_t pos = 8;

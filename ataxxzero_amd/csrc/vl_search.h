@@ -4,7 +4,7 @@
 // (puct_score, apply_priors, mark_game, compact_leaves); none of those changes with it.
 //
 // The definition (DESIGN.md "Leaf-parallel search"; tests/vl_reference.py restates it in numpy):
-//   k = min(K, visits - root_visits) paths per iteration (at least 1), selected as if one after the other, each on the
+//   k = min(K, T - root_visits) paths per iteration (at least 1; T = visits, or the ply's own threshold under the playout cap), selected as if one after the other, each on the
 //   tree the earlier paths of the batch left: an edge taken by c earlier paths scores with n + VL c visits and an
 //   unchanged W (a virtual loss is a visit that scored 0 for the mover), N is the sum of the children's effective
 //   counts.  A path ends at an edge without a child (EVAL: expanded exactly as select_game does, its node and edges
@@ -37,7 +37,8 @@ struct VlParams {
 
 // Selects the game's batch: k paths in path order (phase 1), the root evaluation (phase 0, slot 0), or nothing.  `s` is
 // the game's state in registers (uniform over the lanes); stored here.  Returns the slots that need the net (bit p: slot p).
-__device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, int g, azh_game_state &s, u16 *s_moves)
+// `pk`: the ply's kind word (its threshold is the T of k below).
+__device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, int g, azh_game_state &s, u16 *s_moves, u32 pk)
 {
     const int lane = lane_id();
     const int K = V.K;
@@ -66,7 +67,7 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
         s.leaf_kind = AZH_LEAF_ROOT;
     } else {
         const int nodes0 = s.n_nodes;  // nodes from this id on were created by this batch (unevaluated until its backup)
-        const int k = max(1, min(K, P.visits - s.root_visits));
+        const int k = max(1, min(K, ply_threshold(P, pk) - s.root_visits));
         const uint4 rinfo = A.ni[0];
         const u32 root_kid = pack_kid(rinfo.x, rinfo.y & 0xFFFFu, (rinfo.y >> 16) != 0u);
         for (int p = 0; p < k; p++) {
@@ -235,13 +236,13 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
 
 // The priors of the batch's new nodes (wave w of the game's workgroup: paths w, w + VL_WAVES, ...) and of the root after
 // its evaluation (wave 0).  Reads the state; changes nothing the other waves read.
-__device__ inline void vl_backup_priors(const EngineParams &P, const VlParams &V, int g, const azh_game_state &s, int w)
+__device__ inline void vl_backup_priors(const EngineParams &P, const VlParams &V, int g, const azh_game_state &s, int w, u32 pk)
 {
     const size_t base = (size_t)g * V.K;
     Arena A = arena_of(P, s.arena, g);
     if (s.leaf_kind == AZH_LEAF_ROOT) {
         if (w == 0)
-            apply_priors(P, A, 0, P.logits + base * AZH_POLICY_SIZE, true, s.uid, (u32)s.ply);
+            apply_priors(P, A, 0, P.logits + base * AZH_POLICY_SIZE, (pk & PLY_FULL) != 0u, s.uid, (u32)s.ply);
         return;
     }
     if (s.leaf_kind != AZH_LEAF_EVAL)
@@ -423,8 +424,9 @@ __global__ __launch_bounds__(VL_WAVES * WAVE) void k_vl_tree(EngineParams P, VlP
     const int g = blockIdx.x;
     azh_game_state s = P.gs[g];
     const int forced = P.force[g];
+    const u32 pk = ply_kind_of(P, g);
     if (mode & 1) {
-        vl_backup_priors(P, V, g, s, w);
+        vl_backup_priors(P, V, g, s, w, pk);
         if (w == 0)
             vl_backup_edges(P, V, g, s);
         __threadfence_block();
@@ -433,9 +435,9 @@ __global__ __launch_bounds__(VL_WAVES * WAVE) void k_vl_tree(EngineParams P, VlP
     u64 need = 0;
     if (w == 0) {
         if (mode & 1)
-            mark_game(P, g, s, forced);
+            mark_game(P, g, s, forced, pk);
         if (mode & 2)
-            need = vl_select_game(P, V, g, s, s_moves);  // stores the state
+            need = vl_select_game(P, V, g, s, s_moves, pk);  // stores the state
         else if (lane_id() == 0)
             P.gs[g] = s;
     }

@@ -131,6 +131,8 @@ SIGNATURES = {
     "azh_engine_set_leaf_batch": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
     "azh_engine_batch_leaves": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "azh_engine_set_batch_evals": (ctypes.c_int, [_vp, _vp, _vp]),
+    "azh_engine_set_playout_cap": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
+    "azh_playout_cap_kind": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     "azh_engine_set_solver": (ctypes.c_int, [_vp, ctypes.c_int]),
     "azh_engine_proof_stats": (ctypes.c_int, [_vp, _vp]),
     "azh_engine_root_proofs": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
@@ -146,6 +148,7 @@ SIGNATURES = {
     "azh_engine_fetch": (ctypes.c_int, [_vp]),
     "azh_engine_query": (ctypes.c_int, [_vp]),
     "azh_engine_implicit_fetches": (ctypes.c_longlong, [_vp]),
+    "azh_engine_staged_records": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _P(ctypes.c_int64)]),
     "azh_engine_drain_json": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _P(ctypes.c_int64), _P(_i32)]),
     "azh_format_record_json": (ctypes.c_int, [_vp, ctypes.c_int64, _i32, _vp, ctypes.c_int64, _P(ctypes.c_int64)]),
     "azh_engine_set_emit_order": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -239,6 +242,19 @@ def format_record_json(rec, with_ids=False):
                                            ctypes.byref(used))
     check(rc)
     return bytes(buf[:used.value])
+
+
+def playout_cap_kind(seed, uid, ply, full_per_65536):
+    """Playout cap randomization: 1 if ply `ply` of game `uid` of an engine with `seed` is a FULL ply, else 0
+    (azh_playout_cap_kind; host arithmetic, no GPU needed)."""
+    return int(load().azh_playout_cap_kind(int(seed), int(uid), int(ply), int(full_per_65536)))
+
+
+def full_per_65536(full_fraction):
+    """The setter's integer for a share of FULL plies in [0, 1]."""
+    if not 0.0 <= full_fraction <= 1.0:
+        raise ValueError("full_fraction must lie in [0, 1]")
+    return int(round(full_fraction * 65536))
 
 
 # ------------------------------------------------------------------ rules
@@ -429,6 +445,12 @@ class Engine:
     def set_visits(self, visits):
         check(load().azh_engine_set_visits(self.h, visits))
 
+    def set_playout_cap(self, fast_visits, full_per_65536):
+        """Playout cap randomization: FAST plies are played at `fast_visits` root visits without root noise, FULL
+        plies — a share full_per_65536 / 65536, drawn per (uid, ply) — as today; game lines gain "full".  fast_visits = 0:
+        off.  Between iterations only."""
+        check(load().azh_engine_set_playout_cap(self.h, int(fast_visits), int(full_per_65536)))
+
     def set_thin_batches(self, mode):
         """0: the 3-board tower; 1: one board per workgroup (a handful of leaves per iteration); -1: by the engine's size."""
         check(load().azh_engine_set_thin_batches(self.h, int(mode)))
@@ -566,6 +588,17 @@ class Engine:
     def implicit_fetches(self):
         """Times a drain had to fetch by itself (= waited for the device); 0 in a loop that fetches before it drains."""
         return int(load().azh_engine_implicit_fetches(self.h))
+
+    def staged_records(self):
+        """Diagnostic: the record words fetch() took off the device and drain_json() has not yet formatted (uint32, the
+        ring's layout: include/ataxxzero_hip.h, azh_format_record_json); nothing is consumed."""
+        n = ctypes.c_int64(0)
+        rc = load().azh_engine_staged_records(self.h, None, 0, ctypes.byref(n))
+        if rc not in (0, -6):
+            check(rc)
+        out = np.zeros(max(int(n.value), 1), dtype=np.uint32)
+        check(load().azh_engine_staged_records(self.h, _ptr(out), out.size, ctypes.byref(n)))
+        return out[:int(n.value)]
 
     def drain_json(self):
         """Finished games since the last call, as a list of JSON lines (bytes, no newline)."""

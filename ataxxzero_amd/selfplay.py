@@ -77,10 +77,13 @@ class SelfPlay:
     half runs its tree kernels or the ramp or tail of its tower launch, the other half's tower fills
     the idle CUs (+10 % at 4096 games, +24 % at 2048, nothing from 16384 on:
     profiles/round4_half_batches_and_reserved_cus.txt; bench.py's and the generator's default).
-    The halves are independent game shards (distinct Philox streams, their own uids)."""
+    The halves are independent game shards (distinct Philox streams, their own uids).
+
+    `fast_visits` > 0 turns playout cap randomization on in every half-batch engine (link.Engine.set_playout_cap): a share
+    `full_fraction` of the plies is searched with `visits` and root noise, the others with `fast_visits` and none."""
 
     def __init__(self, conv_weights, bn_params, games, visits, dtype="bf16", seed=DEFAULT_SEED,
-                 fen=START_FEN_SELFPLAY, streams=1, **cfg):
+                 fen=START_FEN_SELFPLAY, streams=1, fast_visits=0, full_fraction=0.25, **cfg):
         self.dtype = link.DTYPES[dtype]
         self.net = link.Net(conv_weights, bn_params, model.BN_EPSILON)
         if streams < 1 or games < streams:
@@ -91,6 +94,8 @@ class SelfPlay:
                         for i in range(streams)]
         self.engine = self.engines[0]
         self.games = games
+        if fast_visits:
+            self.set_playout_cap(fast_visits, full_fraction)
 
     def run(self, iterations):
         # every engine's whole run is enqueued on its own stream (the calls are asynchronous): the half-batches then
@@ -110,6 +115,11 @@ class SelfPlay:
     def set_visits(self, visits):
         for e in self.engines:
             e.set_visits(visits)
+
+    def set_playout_cap(self, fast_visits, full_fraction=0.25):
+        """Playout cap randomization in every half-batch engine; fast_visits = 0 turns it off."""
+        for e in self.engines:
+            e.set_playout_cap(fast_visits, link.full_per_65536(full_fraction))
 
     def set_thin_batches(self, mode):
         """1: the towers run one board per workgroup (a handful of leaves per iteration: the tail of a run under a game

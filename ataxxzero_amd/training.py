@@ -107,12 +107,25 @@ def _policy_target(entry, ply, symmetry_index):
     return target
 
 
+def _draw_ply(entry):
+    """The ply a sample of `entry` is taken from, or None if the entry has none to give.  An entry of a generator run with
+    the playout cap carries "full" (one 0 / 1 per ply): only its FULL plies — searched with the whole budget and root
+    noise — are policy targets, so the ply is drawn among those, and an entry without one is skipped.  Every other entry
+    draws exactly as the reference does (train.py:46)."""
+    if "full" not in entry:
+        return random.randrange(len(entry["boards"]))
+    full = [p for p, f in enumerate(entry["full"]) if f]
+    return full[random.randrange(len(full))] if full else None
+
+
 def get_sample_from_entries(entries):
     """One training sample (train.py:43-77).  The draws from `random` come in the reference's order — game, ply,
     symmetry — so a games file yields the same minibatches as there."""
     while True:
         entry = random.choice(entries)
-        ply = random.randrange(len(entry["boards"]))
+        ply = _draw_ply(entry)
+        if ply is None:
+            continue
         if "random_ply" in entry:                   # ONE_RANDOM_MOVE games: the position right after the random move
             ply = entry["random_ply"] + 1
         if entry["moves"][ply] == "pass":
@@ -231,7 +244,9 @@ def make_minibatch(entries, size):
     cells, movers, syms, results, rows, pidx, pw = [], [], [], [], [], [], []
     while len(cells) < size:
         entry = random.choice(entries)                      # the reference's draws, in its order (train.py:45-60)
-        ply = random.randrange(len(entry["boards"]))
+        ply = _draw_ply(entry)
+        if ply is None:
+            continue
         if "random_ply" in entry:
             ply = entry["random_ply"] + 1
         if entry["moves"][ply] == "pass":
@@ -336,6 +351,9 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
     entries = load_entries(games_paths)
     ply_count = sum(len(e["moves"]) for e in entries)
     log("Found %i games with %i plies." % (len(entries), ply_count))
+    if any("full" in e for e in entries):                                 # playout cap: only FULL plies are policy targets
+        ply_count = sum(sum(1 for f in e["full"] if f) if "full" in e else len(e["moves"]) for e in entries)
+        log("Playout cap: %i of them are training targets (fully searched)." % ply_count)
     test_entries, train_entries = entries[:10], entries[10:]
     device = device or torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if old_path is not None:

@@ -258,6 +258,27 @@ int azh_engine_batch_leaves(azh_engine *e, int32_t *kind, uint64_t *leaf_boards,
 /* evaluations of the batch from outside, by slot: logits [G K][833], values [G K] */
 int azh_engine_set_batch_evals(azh_engine *e, const float *logits, const float *values);
 
+/* Playout cap randomization (an extension, off by default; the reference searches every ply with `visits`): most plies of
+ * a game get a cheap search, a random share the full one, and only those are training targets (KataGo).  While it is on,
+ * every ply of every game is FAST or FULL — FULL iff (philox(seed; uid, ply, 4, 0).v[0] >> 16) < full_per_65536, a pure
+ * function of the engine's seed, the game's uid and the ply (azh_playout_cap_kind restates it on the host; stream 4 is
+ * drawn from by nothing else, so no other random number moves).  A FULL ply's move is due at `visits` root visits and its
+ * root priors get the Dirichlet mix, bit for bit those of the uncapped engine at the same uid, ply and position; a FAST
+ * ply's move is due at `fast_visits` and its root priors are the plain posterior.  The leaf-parallel search's
+ * k = max(1, min(K, T - root_visits)) uses the ply's own threshold T.  Every ply still begins with the root's evaluation: a
+ * root that inherits `fast_visits` visits or more plays its FAST move right after it.  Sampling, re-root, evaluation cache,
+ * select budget and the K-leaf search are unchanged.  The record of a game finished while the mode is on says so (bit 2 of
+ * header word 7) and word 5 of each ply is 1 for a FULL ply: the game's line gains "full": [0,1,...], one entry per ply,
+ * between "dists" and "moves".  Lines of an engine with the mode off are byte for byte what they were.
+ * fast_visits = 0 switches the mode off; else 1 <= fast_visits <= visits and 0 <= full_per_65536 <= 65536 (65536: every
+ * ply FULL, 0: none).  Call before the first select or between iterations.  Refused with AZH_FLAG_TWO_NETS (match play
+ * searches every move alike) and AZH_FLAG_ONE_RANDOM_MOVE; while it is on azh_engine_set_visits refuses values below
+ * fast_visits.  Definition and measurements: DESIGN.md, "Playout cap randomization". */
+int azh_engine_set_playout_cap(azh_engine *e, int fast_visits, int full_per_65536);
+/* The kind of ply `ply` of game `uid` of an engine created with `seed`: 1 FULL, 0 FAST.  Host arithmetic only, usable
+ * without a device (trainers, tests). */
+int azh_playout_cap_kind(uint64_t seed, uint32_t uid, uint32_t ply, uint32_t full_per_65536);
+
 /* Proven wins and losses in the tree (MCTS-solver; an extension, off by default; DESIGN.md, "Proven wins and losses").
  * A node is DECIDED if it is a finished position or was PROVEN: after every batch's backup, for each path that ended at a
  * decided node, the node's parent is a proven win (+1 for its side to move) if one of its children is decided with -1, and
@@ -386,9 +407,15 @@ int azh_engine_query(azh_engine *e);
 /* How many times azh_engine_drain_json had to fetch by itself (and so waited for the device) since the engine was created:
  * 0 for a host loop that fetches explicitly before every drain sequence. */
 long long azh_engine_implicit_fetches(const azh_engine *e);
+/* Diagnostic: the records the last azh_engine_fetch took off the device and no drain has formatted yet, copied as they lie
+ * in the ring (one after the other, each as azh_format_record_json describes; dropped games' 8-word markers included).
+ * Nothing is consumed: the next azh_engine_drain_json formats them as usual.  *words = words staged; -6 if `cap` (in
+ * words) is smaller (nothing written).  What a game line does not carry — uid, visit counts, the "full" words of the
+ * plies — can be read here. */
+int azh_engine_staged_records(azh_engine *e, uint32_t *buf, int64_t cap, int64_t *words);
 /* The line of ONE finished-game record (the words between two ring headers, as the device loop leaves them: 8-word header
- * {magic, slot, uid, plies, result, words, random_ply + 1, kind}, then per ply {x lo, x hi, o lo, o hi, move | nd << 16, 0,
- * nd x (move | visits << 16)}) exactly as azh_engine_drain_json writes it, without the newline: what the reference's
+ * {magic, slot, uid, plies, result, words, random_ply + 1, kind}, then per ply {x lo, x hi, o lo, o hi, move | nd << 16, full,
+ * nd x (move | visits << 16)}; kind | 4 and full: azh_engine_set_playout_cap) exactly as azh_engine_drain_json writes it, without the newline: what the reference's
  * `entry.dump()` gives (cpp/self_play_client.cpp:565-578,639-641: nlohmann::json — sorted keys, no whitespace, floats as
  * the digits its Grisu2 finds, plain decimals from 1e-4 up, d.ddde-XX below).  Host code only, usable without a device.
  * *used = bytes the line has; -6 if `cap` is smaller (nothing written), -2 if the words are not a well-formed record.

@@ -1,0 +1,312 @@
+"""Playout cap randomization on the MI355X (azh_engine_set_playout_cap): per-ply thresholds in lock step with a host-driven
+uncapped engine, records that say which plies were searched in full, root noise on FULL plies only, the leaf-parallel
+batch size, the device loop against host stepping, the degenerate settings and the refusals."""
+import json
+import re
+
+import numpy as np
+import pytest
+
+from ataxxzero_amd import link, model
+from oracle import oracle_lib as orc
+from tests import helpers
+
+pytestmark = pytest.mark.gpu
+
+MAGIC = 0x415A4847
+SEED = 424242
+
+
+def _late_start():
+    """An unfinished fixture position with 10-14 empty squares and both sides well alive: games from it last a few dozen
+    plies, so thresholds, tree reuse, game ends and restarts all occur within a few hundred iterations."""
+    for rec in helpers.load_gz("rules_noblock.json.gz"):
+        p = orc.pos_from_fen(rec["fen"])
+        x, o = int(p.pieces[0]), int(p.pieces[1])
+        if orc.result(p) != 0 or len(orc.movegen(p)) == 0:
+            continue
+        if 10 <= 49 - bin(x | o).count("1") <= 14 and min(bin(x).count("1"), bin(o).count("1")) >= 10:
+            return x, o, int(p.turn)
+    raise AssertionError("no such fixture position")
+
+
+START = _late_start()
+
+
+def _engine(games, visits, weight=0.0, seed=SEED, flags=0, cap=None, K=1):
+    x, o, turn = START
+    cfg = link.Config(games=games, visits=visits, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
+                      dirichlet_weight=weight, start_turn=turn, seed=seed, start_x=x, start_o=o, blockers=0, flags=flags)
+    e = link.Engine(cfg)
+    if K > 1:
+        e.set_leaf_batch(K, 1)
+    if cap is not None:
+        e.set_playout_cap(*cap)
+    return e
+
+
+def _net(seed=3):
+    conv, bn = model.random_init(1, 128, seed=seed, perturb_bn=True)
+    return link.Net(conv, bn)
+
+
+def _step(e):
+    """one iteration of the step-wise API with the synthetic evaluator -> (need, leaf boards)"""
+    e.select()
+    need, lb = e.leaves()
+    logits, values = helpers.synthetic_evals_distinct(lb)
+    e.set_evals(logits, values)
+    e.backup()
+    return need, lb
+
+
+def _dump(e):
+    return [e.game_state(g).as_tuple() for g in range(e.G)], [e.tree(g) for g in range(e.G)]
+
+
+def _same(da, db):
+    (sa, ta), (sb, tb) = da, db
+    assert sa == sb
+    for x, y in zip(ta, tb):
+        for u, v in zip(x, y):
+            assert u.shape == v.shape and (u == v).all()
+
+
+def _strip_full(line):
+    return re.sub(rb',"full":\[[01,]*\]', b"", line)
+
+
+def _records(words):
+    """[(slot, uid, result, kind word, [(move, full, {move: visits})])] of the staged record words (dropped markers skipped)"""
+    out, pos = [], 0
+    while pos < len(words):
+        assert words[pos] == MAGIC
+        slot, uid, plies, result, n, kind = (int(words[pos + i]) for i in (1, 2, 3, 4, 5, 7))
+        if kind & 3 != 1:
+            q, rows = pos + 8, []
+            for _ in range(plies):
+                nd = int(words[q + 4]) >> 16
+                rows.append((int(words[q + 4]) & 0xFFFF, int(words[q + 5]),
+                             {int(w) & 0xFFFF: int(w) >> 16 for w in words[q + 6:q + 6 + nd]}))
+                q += 6 + nd
+            assert q == pos + n
+            out.append((slot, uid, result, kind, rows))
+        pos += n
+    return out
+
+
+def test_lock_step_with_a_host_driven_uncapped_engine():
+    """A (cap on) against B (cap off), whose threshold the host sets before every iteration from the kind of the ply B is
+    at: every state word and tree row equal after every iteration over three complete games, the lines equal but for
+    A's "full" key."""
+    visits, fast, frac = 24, 6, 32768
+    a = _engine(1, visits, cap=(fast, frac))
+    b = _engine(1, visits)
+    lines_a, lines_b, kinds_seen, inherited_fast = [], [], set(), 0
+    for it in range(6000):
+        sb = b.game_state(0)
+        kind = link.playout_cap_kind(SEED, sb.uid, sb.ply, frac)
+        kinds_seen.add(kind)
+        inherited_fast += int(sb.phase == 0 and not kind and sb.root_visits >= fast)
+        b.set_visits(visits if kind else fast)
+        _step(a)
+        _step(b)
+        _same(_dump(a), _dump(b))
+        lines_a += a.drain_json()
+        lines_b += b.drain_json()
+        if len(lines_b) >= 3:
+            break
+    assert len(lines_a) == len(lines_b) >= 3
+    assert kinds_seen == {0, 1} and inherited_fast > 0   # (a re-rooted root that already met its fast threshold)
+    for uid, (la, lb) in enumerate(zip(lines_a, lines_b)):
+        assert b"full" not in lb and _strip_full(la) == lb
+        ea = json.loads(la)
+        assert list(ea.keys()) == ["boards", "dists", "full", "moves", "result"]
+        assert ea["full"] == [link.playout_cap_kind(SEED, uid, p, frac) for p in range(len(ea["moves"]))]
+    a.close(), b.close()
+
+
+@pytest.mark.parametrize("games", [5, 33, 130])
+def test_records_say_what_was_searched(games):
+    visits, fast, frac = 16, 4, 16384
+    net = _net()
+    e = _engine(games, visits, weight=0.25, cap=(fast, frac))
+    recs, lines = [], []
+    for _ in range(40):
+        e.run(net, 100, link.DTYPE_BF16)
+        e.fetch()
+        recs += _records(e.staged_records())
+        lines += e.drain_json()
+        if {r[0] for r in recs} == set(range(games)):
+            break
+    assert {r[0] for r in recs} == set(range(games))       # every slot has finished a game
+    assert len(lines) == len(recs)
+    fulls = fasts = exact = 0
+    for slot, uid, result, kind, rows in recs:
+        assert kind == 4 and uid % games == slot and result in (1, 2)
+        inherited = 0
+        for ply, (move, full, counts) in enumerate(rows):
+            assert full == link.playout_cap_kind(SEED, uid, ply, frac), (uid, ply)
+            T = visits if full else fast
+            total = sum(counts.values())
+            assert total >= T, (uid, ply, total, T)
+            if inherited < T:
+                assert total < T + 1, (uid, ply, total, T, inherited)      # K = 1: the move is due at exactly T
+                exact += 1
+            else:
+                assert total == inherited, (uid, ply, total, inherited)  # played after the root's evaluation alone
+            # what the next root inherits: every visit of the played edge but the one that created its child
+            inherited = max(counts.get(move, 0) - 1, 0)
+            fulls += full
+            fasts += 1 - full
+    assert fulls > 0 and fasts > fulls and exact > 0
+    by_key = sorted(json.loads(l)["full"] for l in lines)
+    assert by_key == sorted([full for _, full, _ in rows] for _, _, _, _, rows in recs)
+    e.close()
+
+
+def _root_priors(e, g):
+    return e.root_report(g, 1)[0].priors.view(np.uint32).copy()
+
+
+def test_root_noise_on_full_plies_only():
+    """The root priors after the root's evaluation at every ply of each slot's first game (uid = slot): on FAST plies
+    those of an engine without noise, on FULL plies those of the uncapped engine with noise, at the same uid, ply and
+    position (loaded with set_positions: uids restart at the slot numbers), bit for bit."""
+    G, visits, fast, frac = 8, 12, 3, 32768
+    a = _engine(G, visits, weight=0.25, cap=(fast, frac))
+    plain = _engine(G, visits, weight=0.0)
+    noisy = _engine(G, visits, weight=0.25)
+    checked = {0: 0, 1: 0}
+    differ = 0
+    for it in range(1500):
+        before = [a.game_state(g) for g in range(G)]
+        if all(s.uid != g for g, s in enumerate(before)):
+            break
+        roots = np.array([a.tree(g)[0][0] for g in range(G)], dtype=np.uint64)
+        _step(a)
+        due = [g for g, s in enumerate(before) if s.uid == g and s.phase == 0 and a.game_state(g).phase == 1]
+        if not due:
+            continue
+        plies = np.array([s.ply for s in before], dtype=np.int32)
+        for ref in (plain, noisy):
+            ref.set_positions(roots, plies)
+            _step(ref)
+        for g in due:
+            kind = link.playout_cap_kind(SEED, g, before[g].ply, frac)
+            got, p0, p1 = _root_priors(a, g), _root_priors(plain, g), _root_priors(noisy, g)
+            assert len(got) == len(p0) == len(p1) > 0
+            assert (got == (p1 if kind else p0)).all(), (g, before[g].ply, kind)
+            differ += int((p0 != p1).any())
+            checked[kind] += 1
+    assert checked[0] > 20 and checked[1] > 20 and differ > 40, (checked, differ)
+    a.close(), plain.close(), noisy.close()
+
+
+@pytest.mark.parametrize("K", [4, 8])
+def test_leaf_parallel_batches_stop_at_the_plys_own_threshold(K):
+    G, visits, fast, frac = 3, 24, 6, 32768
+    e = _engine(G, visits, cap=(fast, frac), K=K)
+    seen = {0: 0, 1: 0}
+    truncated = 0
+    for it in range(400):
+        st = [e.game_state(g) for g in range(G)]
+        e.select()
+        kind, lb, _ = e.batch_leaves()
+        for g, s in enumerate(st):
+            filled = int((kind[g] != link.LEAF_NONE).sum())
+            if s.phase == 1:
+                full = link.playout_cap_kind(SEED, s.uid, s.ply, frac)
+                T = visits if full else fast
+                want = max(1, min(K, T - s.root_visits))
+                assert filled == want and (kind[g, :want] != link.LEAF_NONE).all(), (it, g, filled, want)
+                seen[full] += 1
+                truncated += int(want < K and not full)
+            elif s.phase == 0:
+                assert filled == 1 and kind[g, 0] == link.LEAF_ROOT
+            else:
+                assert filled == 0
+        logits, values = helpers.synthetic_evals_distinct(lb.reshape(-1, 2))
+        e.set_batch_evals(logits, values)
+        e.backup()
+    assert seen[0] > 10 and seen[1] > 10 and truncated > 0 and e.stats()["plies"] > 10
+    e.close()
+
+
+def test_device_loop_equals_host_stepping_with_the_cap_on():
+    net = _net()
+    n, G = 200, 33
+    a = _engine(G, 16, weight=0.25, cap=(4, 16384))
+    b = _engine(G, 16, weight=0.25, cap=(4, 16384))
+    a.run(net, n, link.DTYPE_BF16)
+    a.sync()
+    for _ in range(n):
+        b.select()
+        b.eval(net, link.DTYPE_BF16)
+        b.backup()
+    _same(_dump(a), _dump(b))
+    assert a.stats() == b.stats() and a.stats()["plies"] > 10 * G
+    la, lb = a.drain_json(), b.drain_json()
+    assert sorted(la) == sorted(lb) and all(b'"full":[' in l for l in la)
+    a.close(), b.close()
+
+
+def test_every_ply_full_and_switched_off_are_the_uncapped_engine():
+    net = _net(seed=5)
+    n, G = 400, 5
+    ref = _engine(G, 12, weight=0.25)
+    every = _engine(G, 12, weight=0.25, cap=(3, 65536))
+    off = _engine(G, 12, weight=0.25, cap=(3, 16384))
+    off.set_playout_cap(0, 0)
+    for e in (ref, every, off):
+        e.run(net, n, link.DTYPE_F32)
+        e.sync()
+    _same(_dump(ref), _dump(every))
+    _same(_dump(ref), _dump(off))
+    want = ref.drain_json()
+    assert len(want) >= G and not any(b"full" in l for l in want)
+    assert off.drain_json() == want                      # byte for byte, no "full" key
+    got = every.drain_json()
+    assert [_strip_full(l) for l in got] == want
+    assert all(set(json.loads(l)["full"]) == {1} for l in got)
+    assert ref.stats() == every.stats() == off.stats()
+    for e in (ref, every, off):
+        e.close()
+
+
+def test_refusals_leave_the_engine_usable():
+    e = _engine(4, 24)
+    for bad in [(25, 100), (-1, 100), (6, -1), (6, 65537)]:
+        with pytest.raises(link.AzhError):
+            e.set_playout_cap(*bad)
+    _step(e)
+    e.set_playout_cap(6, 16384)
+    with pytest.raises(link.AzhError):
+        e.set_visits(5)                       # below fast_visits while the mode is on
+    e.set_visits(6)
+    e.set_visits(24)
+    e.select()
+    with pytest.raises(link.AzhError):
+        e.set_playout_cap(8, 16384)           # a selected batch awaits its backup
+    need, lb = e.leaves()
+    e.set_evals(*helpers.synthetic_evals_distinct(lb))
+    e.backup()
+    e.set_playout_cap(0, 0)
+    e.set_visits(5)                           # the mode is off: any value up to the engine's own
+    for _ in range(30):
+        _step(e)
+    assert e.stats()["plies"] > 0
+    e.close()
+    for flags in (link.FLAG_TWO_NETS, link.FLAG_ONE_RANDOM_MOVE):
+        r = _engine(4, 24, flags=flags)
+        with pytest.raises(link.AzhError):
+            r.set_playout_cap(6, 16384)
+        r.set_playout_cap(0, 0)               # switching off is no request for the mode
+        net = _net()
+        if flags == link.FLAG_TWO_NETS:
+            r.run_arena(net, net, 20, link.DTYPE_F32)
+        else:
+            r.run(net, 20, link.DTYPE_F32)
+        r.sync()
+        assert r.stats()["steps"] > 0
+        r.close()

@@ -1,0 +1,132 @@
+#!/usr/bin/python
+"""What playout cap randomization buys the generator: its own loop (two half-batches, evaluation cache, select budget 48,
+bf16 12x128 tower, steady-state positions loaded as bench.py does) with the cap off against the cap on, legs alternating
+in one process.  Per leg: plies/s, finished games/s, FULL plies/s (plies/s x the share of FULL plies among the plies the
+leg's finished records carry) and how much longer the tower launch — which carries the move-playing workgroups — lasts
+than the bare tower at the leg's mean batch: with the moves inside the tower launch there is no per-iteration
+observable of "the workers outlasted the tiles", so the mean excess per launch stands in for that share.
+
+    python tools/playout_cap_rate.py [--pairs 3] [--steps 8] [--out profiles/playout_cap.txt]
+
+Appends its report to --out.  GPU box, repo root."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from ataxxzero_amd import link, model, selfplay  # noqa: E402
+
+SNAPSHOT = os.path.join(ROOT, "profiles", "round2_steady_state_positions.npz")
+MAGIC = 0x415A4847
+
+
+def full_share(words):
+    """(FULL plies, plies) over the staged record words"""
+    full = plies = pos = 0
+    while pos + 8 <= len(words):
+        if words[pos] != MAGIC:
+            pos += 1
+            continue
+        n, q = int(words[pos + 5]), pos + 8
+        if int(words[pos + 7]) & 3 != 1:
+            for _ in range(int(words[pos + 3])):
+                full += int(words[q + 5])
+                plies += 1
+                q += 6 + (int(words[q + 4]) >> 16)
+        pos += max(n, 8)
+    return full, plies
+
+
+def leg(conv, bn, args, cap, seed):
+    sp = selfplay.SelfPlay(conv, bn, games=args.games, visits=args.visits, dtype=args.dtype, seed=seed, streams=2,
+                           flags=link.FLAG_EVAL_CACHE, select_budget=48,
+                           fast_visits=args.fast_visits if cap else 0, full_fraction=args.full_search_fraction)
+    snap = np.load(SNAPSHOT)
+    rng = np.random.default_rng(seed)
+    pick = rng.permutation(len(snap["plies"])) if args.games == len(snap["plies"]) else rng.integers(0, len(snap["plies"]), size=args.games)
+    sp.set_positions(snap["boards"][pick], snap["plies"][pick])
+    for _ in range(args.fill // 250):
+        sp.run(250)
+        sp.drain()
+    sp.sync()
+    st0 = sp.stats()
+    sp.timing_reset(16)
+    full = plies = 0
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        sp.run(250)
+        sp.fetch()
+        for e in sp.engines:
+            f, p = full_share(e.staged_records())
+            full, plies = full + f, plies + p
+        sp.drain()
+    sp.sync()
+    dt = time.perf_counter() - t0
+    st = {k: v - st0[k] for k, v in sp.stats().items()}
+    tm = sp.timing()
+    iters = 250 * args.steps
+    batch = st["nn_evals"] / (2.0 * iters)                      # mean leaves per tower launch (two half-batches)
+    tower_ms = tm["net_ms"] / max(1, tm["iterations"])
+    bare_ms = sp.net.bench(max(1, int(round(batch))), 20, link.DTYPES[args.dtype])
+    sp.close()
+    share = 1.0 if not cap else (full / plies if plies else float("nan"))   # (cap off: every ply is searched in full)
+    return {"cap": cap, "plies_s": st["plies"] / dt, "games_s": st["games"] / dt,
+            "full_share": share, "full_plies_s": st["plies"] / dt * share, "evals_s": st["nn_evals"] / dt,
+            "plies_per_iter": st["plies"] / (2.0 * iters), "batch": batch, "tower_us": 1e3 * tower_ms,
+            "bare_us": 1e3 * bare_ms, "iter_s": iters / dt}
+
+
+def row(r):
+    return ("%-4s plies/s %8.1f  games/s %6.2f  full plies/s %8.1f (share %.3f)  evals/s %9.0f  iterations/s %7.1f  "
+            "moves due per launch %5.1f  leaves per launch %6.0f  tower launch %6.1f us, bare tower at that batch %6.1f us (excess %5.1f us)" % (
+                "on" if r["cap"] else "off", r["plies_s"], r["games_s"], r["full_plies_s"], r["full_share"],
+                r["evals_s"], r["iter_s"], r["plies_per_iter"], r["batch"], r["tower_us"], r["bare_us"], r["tower_us"] - r["bare_us"]))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--games", type=int, default=4096)
+    ap.add_argument("--visits", type=int, default=400)
+    ap.add_argument("--fast-visits", type=int, default=100)
+    ap.add_argument("--full-search-fraction", type=float, default=0.25)
+    ap.add_argument("--blocks", type=int, default=12)
+    ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=8, help="timed steps of 250 iterations per leg")
+    ap.add_argument("--fill", type=int, default=1000, help="untimed iterations after the positions are loaded")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "playout_cap.txt"))
+    args = ap.parse_args()
+    selfplay.select_device(0)
+    conv, bn = model.random_init(args.blocks, 128, seed=1, perturb_bn=True)
+    lines = ["== tools/playout_cap_rate.py: MEASURED ON THE DEVICE (%s) — %d games in two half-batches, %dx128 %s, visits %d; "
+             "cap on = --fast-visits %d --full-search-fraction %.2f; %d timed steps of 250 iterations per leg after %d untimed"
+             % (link.pci_bus_id(0), args.games, args.blocks, args.dtype, args.visits, args.fast_visits,
+                args.full_search_fraction, args.steps, args.fill)]
+    rows = []
+    for pair in range(args.pairs):
+        for cap in (False, True):
+            r = leg(conv, bn, args, cap, seed=1000 + pair)
+            rows.append(r)
+            lines.append(row(r))
+            print(lines[-1], flush=True)
+    for key, name in (("plies_s", "plies/s"), ("games_s", "finished games/s"), ("full_plies_s", "full plies/s")):
+        off = [r[key] for r in rows if not r["cap"]]
+        on = [r[key] for r in rows if r["cap"]]
+        m_off, m_on = statistics.mean(off), statistics.mean(on)
+        lines.append("mean %-17s off %9.2f  on %9.2f  ratio %s" % (name, m_off, m_on, "%.3f" % (m_on / m_off) if m_off else "-"))
+        print(lines[-1])
+    bound = args.visits / (args.full_search_fraction * args.visits + (1 - args.full_search_fraction) * args.fast_visits)
+    lines.append("(visits / mean threshold = %.2fx: arithmetic, not a measurement, and no bound — a re-rooted root inherits visits, "
+                 "and one that already meets the fast threshold plays after its root evaluation alone)" % bound)
+    with open(args.out, "a") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

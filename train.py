@@ -3,7 +3,9 @@
 
 Stands in for the reference's train.py: looper.py:140-148 runs
 `python train.py --steps S --games G... --old-path A.npy --new-path B.npy`; the sample pipeline and optimiser
-settings follow train.py:43-157 and live in ataxxzero_amd/training.py.
+settings follow train.py:43-157 and live in ataxxzero_amd/training.py.  Entries written with the generator's playout cap on
+carry "full" (one 0 / 1 per ply): samples are then drawn from the fully searched plies only (an extension; entries
+without the key are sampled exactly as the reference does).
 """
 from ataxxzero_amd import training
 from ataxxzero_amd.cli import flag, parse, switch
