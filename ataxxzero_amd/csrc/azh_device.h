@@ -415,6 +415,60 @@ __host__ __device__ inline bool playout_cap_full(u32 k0, u32 k1, u32 uid, u32 pl
 {
     return (philox(k0, k1, uid, ply, STREAM_PLAYOUT_CAP, 0u).v[0] >> 16) < full_per_65536;
 }
+// Forced playouts and policy target pruning (azh_engine_set_forced_playouts; DESIGN.md, "Forced playouts and policy target
+// pruning").  Every f32 operation is a single IEEE one in the order written, in whichever translation unit this is compiled
+// (the tower's unit contracts by default: the pragmas keep a multiply and an add apart here).
+// The visits a root edge of prior `prior` is owed at N root visits, as a real number: sqrt(k P N).
+__host__ __device__ inline float forced_bound(float k, float prior, u32 N)
+{
+#pragma clang fp contract(off)
+    return sqrtf((k * prior) * (float)N);
+}
+// Q + U of an edge with n visits and mean score q (puct_score's operation order; sq = sqrt(1 + N)).
+__host__ __device__ inline float forced_score(float prior, float q, u32 n, float sq, float c_puct)
+{
+#pragma clang fp contract(off)
+    const float u = (sq / (1.0f + (float)n)) * (c_puct * prior);
+    return u + q;
+}
+// The per-edge rule of the pruning: the visits written into the ply's record for a root edge other than the most visited one
+// (n >= 1 visits, total score W, prior `prior` without its mark) when that one's score is S: up to floor(sqrt(k P N)) visits
+// are taken back, one at a time, while the edge with one visit fewer would still score below S; an edge that lost a visit
+// and is left with one is left out (0).
+__host__ __device__ inline u32 forced_prune_edge(float prior, float W, u32 n, u32 N, float k, float c_puct, float sq, float S)
+{
+    const float fb = floorf(forced_bound(k, prior, N));
+    const u32 f = fb >= (float)n ? n : (u32)fb;  // (no more than n visits can go: the cast stays in range for any k)
+    const float q = W / (float)n;
+    u32 m = n;
+    for (u32 i = 0; i < f; i++) {
+        if (m >= 1u && forced_score(prior, q, m - 1u, sq, c_puct) < S)
+            m -= 1u;
+        else
+            break;
+    }
+    return (m < n && m <= 1u) ? 0u : m;
+}
+// The written visit counts of a whole root (out[j]; 0: edge j is left out of the record): the most visited edge, ties to
+// the lowest index, keeps its visits and sets S; N is the sum of the visits.  Host and device restate the same rule: this
+// is the host's (azh_forced_prune), advance_game holds the wave's.
+__host__ __device__ inline void forced_prune_root(const float *prior, const float *W, const u32 *n, int M, float k, float c_puct,
+                                                  u32 *out)
+{
+    u32 N = 0;
+    int b = 0;
+    for (int j = 0; j < M; j++) {
+        N += n[j];
+        if (n[j] > n[b])
+            b = j;
+    }
+    if (M <= 0)
+        return;
+    const float sq = sqrtf((float)(1u + N));
+    const float S = forced_score(fabsf(prior[b]), n[b] ? W[b] / (float)n[b] : 0.0f, n[b], sq, c_puct);
+    for (int j = 0; j < M; j++)
+        out[j] = (j == b || n[j] == 0u) ? n[j] : forced_prune_edge(fabsf(prior[j]), W[j], n[j], N, k, c_puct, sq, S);
+}
 constexpr u32 STREAM_GAMMA = 0x10000u;
 
 // Gamma(alpha, 1), alpha < 1: Marsaglia-Tsang on alpha + 1 with a polar normal,

@@ -165,9 +165,10 @@ __device__ inline float puct_score(float prior, float W, u32 n, float sq, float 
 }
 
 // `s` is the game's state, held in registers by the caller (the same values in all 64 lanes); written back here.
-// Returns what the leaf needs: 0 nothing, 1 an evaluation (by net A), 2 an evaluation by net B (arena).
+// Returns what the leaf needs: 0 nothing, 1 an evaluation (by net A), 2 an evaluation by net B (arena).  `pk`: the ply's kind
+// word (forced playouts act on the plies whose root got the noise).
 template <bool STAMP = false>
-__device__ inline int select_game(const EngineParams &P, int g, azh_game_state &s, u16 *s_moves, u64 *st = nullptr)
+__device__ inline int select_game(const EngineParams &P, int g, azh_game_state &s, u16 *s_moves, u32 pk, u64 *st = nullptr)
 {
     const int lane = lane_id();
     Arena A = arena_of(P, s.arena, g);
@@ -425,6 +426,72 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
             st_children += (u64)M;
             return false;
         };
+        // Forced playouts (azh_engine_set_forced_playouts; DESIGN.md, "Forced playouts and policy target pruning"): at the
+        // root of a fresh descent on a ply whose root got the noise, an edge with n >= 1 visits and n < sqrt(k P N) is OWED a
+        // visit and the descent takes it — among several the last in edge order, or the first (AZH_FLAG_TIE_FIRST) — instead
+        // of the PUCT arg-max.  One wave-uniform branch in front of the loop: all four records per lane (a root has up to 256
+        // edges) in the loop's record registers, which hold nothing yet; if an edge is owed, the root's level is done here
+        // (path entry, counters, the mark exactly as fast_level moves it) and the loop starts at the child, else the loop
+        // runs as it always has.  Nothing of it lives across the loop's back edge.
+        if (P.forced_k != 0.0f && !resume && (pk & PLY_FULL) != 0u) {
+            const int M0 = kid_count(kid);
+            const u32 f0 = kid_first(kid);
+            uint4 *const rp[4] = {&ea0, &ea1, &eb0, &eb1};
+            u64 ow[4], mk[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int j = lane + 64 * k;
+                bool owed = false, marked = false;
+                if (j < M0) {
+                    const uint4 r = A.ed[f0 + j];
+                    *rp[k] = r;
+                    const u32 n = edge_visits(r);
+                    owed = n >= 1u && edge_child(r) != ENONE && (float)n < forced_bound(P.forced_k, __builtin_fabsf(u2f(r.x)), n_node);
+                    marked = (int)r.x < 0;
+                }
+                ow[k] = __ballot(owed);
+                mk[k] = __ballot(marked);
+            }
+            int bj = -1, pv = -1;
+            if (P.flags & AZH_FLAG_TIE_FIRST) {
+#pragma unroll
+                for (int k = 3; k >= 0; k--)
+                    if (ow[k])
+                        bj = 64 * k + __ffsll((long long)ow[k]) - 1;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    if (ow[k])
+                        bj = 64 * k + 63 - __clzll((long long)ow[k]);
+            }
+            if (bj >= 0) {
+#pragma unroll
+                for (int k = 3; k >= 0; k--)
+                    if (mk[k])
+                        pv = 64 * k + __ffsll((long long)mk[k]) - 1;
+                const int bk = bj >> 6;
+                const u32 mz = bk == 0 ? ea0.z : (bk == 1 ? ea1.z : (bk == 2 ? eb0.z : eb1.z));
+                const u32 mw = bk == 0 ? ea0.w : (bk == 1 ? ea1.w : (bk == 2 ? eb0.w : eb1.w));
+                const u32 zsel = (u32)read_lane((int)mz, bj & 63), wsel = (u32)read_lane((int)mw, bj & 63);
+                levels_done = 1;
+                st_levels += 1;
+                st_children += (u64)M0;
+                push_path(f0 + (u32)bj);
+#if AZH_HINT_SIGN
+                if (M0 <= 2 * WAVE && bj != pv) {  // (wider nodes carry no mark: the general level never sets one)
+                    const bool markable = !kid_finished(wsel) && kid_count(wsel) > 0 && kid_count(wsel) <= 2 * WAVE;
+                    if (pv >= 0 && lane == (pv & 63))
+                        reinterpret_cast<u32 *>(&A.ed[f0 + (u32)pv])[0] = (pv >= WAVE ? ea1.x : ea0.x) & PRIOR_MASK;
+                    if (markable && lane == (bj & 63))
+                        reinterpret_cast<u32 *>(&A.ed[f0 + (u32)bj])[0] = (bj >= WAVE ? ea1.x : ea0.x) | ~PRIOR_MASK;
+                }
+#endif
+                node = zsel >> 16;
+                kid = wsel;
+                n_node = (zsel & 0xFFFFu) - 1u;
+                sq_node = sqrt_1p(n_node);
+            }
+        }
         bool expand = false;
         for (;;) {
             if (level_begin())
@@ -787,7 +854,7 @@ __global__ __launch_bounds__(WAVE) void k_advance_list(EngineParams P)
     __shared__ TreeLds L;
     const int n = *P.adv_count;
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        advance_game(P, P.adv_list[i], L);
+        advance_game<true>(P, P.adv_list[i], L);
         wave_sync();
     }
     // the workgroup that finishes last empties the queue (every workgroup has read the count by then): no memset
@@ -1108,7 +1175,7 @@ __global__ __launch_bounds__(TREE_WAVES * WAVE) __attribute__((amdgpu_waves_per_
             if (!(mode & 1)) st[2] = st[3];
         }
         if (mode & 2)
-            need = select_game<STAMP>(P, g, s, s_moves[w], st);  // stores the state
+            need = select_game<STAMP>(P, g, s, s_moves[w], pk, st);  // stores the state
         else if (lane_id() == 0)
             P.gs[g] = s;
     }
@@ -1605,6 +1672,8 @@ struct RunLoop {
     azh_net *net_a, *net_b;
     int dtype, iterations;
     bool pair = false, side = false;
+    bool own = false;  // forced playouts: the queued moves in a k_advance_list launch of their own, on the engine's stream, in
+                       // front of the tower (the tower kernels' advance_game records no pruned counts: engine_device.h)
     AdvanceHook hook;
 
     // side-stream mode: ev_sel is signalled by the tree launch itself, ev_adv by the re-root launch (hipExtLaunchKernelGGL's
@@ -1625,18 +1694,21 @@ struct RunLoop {
         pair = pair_env && two_lists(e) && !(e->P.flags & AZH_FLAG_SYMMETRY_AVG);
         const char *side_s = getenv("AZH_REROOT_SIDE_STREAM");
         side = side_s && atoi(side_s) != 0;
+        own = !side && e->P.forced_k != 0.0f;
         hook.workers = e->adv_workers;
         hook.at_head = 1;   // (decided per launch by the tower's launch functions: in front only where workgroups queue for slots)
         hook.P = e->P;
         e->unfetched_work = true;  // (every path that can finish a game goes through a re-root)
         if (enqueue_tree(e, 2, false, side ? e->ev_sel : nullptr))  // select + leaf list
             return -1;
+        if (own && enqueue_advance(e, e->stream))
+            return -1;
         return side_advance();
     }
 
     int iteration(int it)
     {
-        const AdvanceHook *moves = side ? nullptr : &hook;
+        const AdvanceHook *moves = side || own ? nullptr : &hook;
         const bool rec = e->timing_stride > 0 && e->loop_iter % e->timing_stride == 0 && e->samples < MAX_TIMED_SAMPLES;
         hipEvent_t *ev = rec ? &e->events[3 * e->samples] : nullptr;
         if (e->close_pending) {
@@ -1670,6 +1742,7 @@ struct RunLoop {
             return -1;
         if (stamped)
             e->stamp_next = false;
+        if (!last && own && enqueue_advance(e, e->stream)) return -1;
         if (!last && side_advance()) return -1;
         if (rec) {
             e->samples++;
@@ -1783,6 +1856,9 @@ static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, b
                             e->P.select_budget > 0 ? "select_budget > 0"
                             : (bad & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS"
                             : (bad & AZH_FLAG_EVAL_CACHE) ? "AZH_FLAG_EVAL_CACHE" : "AZH_FLAG_SYMMETRY_AVG");
+        if (e->P.forced_k != 0.0f)  // (the K-leaf kernel has no forced-playout level)
+            return azh_fail(-4, "%s: %s is not supported with forced playouts (azh_engine_set_forced_playouts)", who,
+                            leaves_per_game > 1 ? "more than one leaf per game" : "the solver");
     }
     AZH_HIP(hipStreamSynchronize(e->stream));
     AZH_HIP(hipStreamSynchronize(e->stream2));
@@ -1959,6 +2035,40 @@ extern "C" int azh_engine_set_playout_cap(azh_engine *e, int fast_visits, int fu
 extern "C" int azh_playout_cap_kind(uint64_t seed, uint32_t uid, uint32_t ply, uint32_t full_per_65536)
 {
     return playout_cap_full((u32)seed, (u32)(seed >> 32), uid, ply, full_per_65536) ? 1 : 0;
+}
+
+// Forced playouts at the root and policy target pruning in the record (KataGo), on the plies whose root priors get the
+// Dirichlet mix.  Definition: the header and DESIGN.md.  Between iterations only.
+extern "C" int azh_engine_set_forced_playouts(azh_engine *e, float k)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_set_forced_playouts: null engine");
+    if (!(k >= 0.0f) || k > 3.0e38f)
+        return azh_fail(-2, "azh_engine_set_forced_playouts: need a finite k >= 0 (0: off)");
+    if (e->selected)
+        return azh_fail(-3, "azh_engine_set_forced_playouts: a selected batch awaits its backup");
+    if (k != 0.0f && (e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_ONE_RANDOM_MOVE)))
+        return azh_fail(-4, "azh_engine_set_forced_playouts: not supported with %s",
+                        (e->P.flags & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS" : "AZH_FLAG_ONE_RANDOM_MOVE");
+    if (k != 0.0f && e->vl_active)
+        return azh_fail(-4, "azh_engine_set_forced_playouts: not supported with %s",
+                        leaf_k(e) > 1 ? "more than one leaf per game (azh_engine_set_leaf_batch)" : "the solver");
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_HIP(hipStreamSynchronize(e->stream2));
+    e->P.forced_k = k;
+    return 0;
+}
+
+// The visit counts policy target pruning writes for a root (out [M]; 0: the edge is left out of the record).  Host arithmetic
+// only: the rule advance_game applies, forced_prune_edge.
+extern "C" int azh_forced_prune(const float *prior, const float *W, const uint32_t *n, int M, float k, float c_puct, uint32_t *out)
+{
+    if (!prior || !W || !n || !out || M < 0)
+        return azh_fail(-1, "azh_forced_prune: bad argument");
+    if (!(k >= 0.0f) || k > 3.0e38f)
+        return azh_fail(-2, "azh_forced_prune: need a finite k >= 0");
+    forced_prune_root(prior, W, n, M, k, c_puct, out);
+    return 0;
 }
 
 // At most `games` games are played: uids 0 .. games - 1 (slot g plays uids g, g + G, ...).  A slot whose next game

@@ -4,7 +4,8 @@
 // loop plays the queued moves INSIDE the tower launch (advance_worker below, round 6): the tower leaves no wave slot and no
 // LDS beside itself, so a re-root launch on a side stream waited most of its life for the tower's first workgroups to retire,
 // and its cross-stream events cost every iteration 7-10 us whether or not a move was due (profiles/round6_reroots_in_the_tower_launch.txt).
-// Nothing here does floating-point arithmetic whose result could depend on the translation unit's contraction mode.
+// Nothing here does floating-point arithmetic whose result could depend on the translation unit's contraction mode (the
+// pruning's arithmetic, azh_device.h's forced_* functions, switches contraction off itself).
 #pragma once
 
 #include "azh_device.h"
@@ -18,6 +19,8 @@ constexpr int REC_STRIDE_WORDS = REC_HDR_WORDS + REC_MAXD;
 constexpr u32 RING_MAGIC = 0x415A4847u;  // "AZHG"
 constexpr u32 REC_KIND_PLAYOUT_CAP = 4u;  // header word 7, beside its kind in bits 0-1: the game was played with the playout cap on
                                           // (word 5 of every ply: 1 = FULL), and its line carries "full"
+constexpr u32 REC_KIND_FORCED = 8u;       // beside it: the game was played with forced playouts on — the visit counts of the plies
+                                          // the mode acts on are the pruned ones (json.cpp ignores the bit)
 constexpr int NSTAT = AZH_STAT_COUNT;
 constexpr int BFS_QL = 384;  // re-root frontier entries kept in LDS; later ones spill to bfs_spill in HBM
 
@@ -71,6 +74,8 @@ struct EngineParams {
     u32 full_per_65536;    // a ply is FULL iff (philox(uid, ply, STREAM_PLAYOUT_CAP).v[0] >> 16) < this
     u32 *ply_kind;         // [G] the kind of the ply each slot is searching, derived where the ply begins (begin_ply): PLY_FULL,
                            // or the FAST ply's threshold — the tree kernels read one word instead of running Philox per mark
+    // forced playouts and policy target pruning (azh_engine_set_forced_playouts), off while forced_k == 0
+    float forced_k;        // a root edge with n >= 1 visits is owed sqrt(forced_k * P * N) of them, on the plies that get root noise
 };
 
 constexpr u32 PLY_FULL = 0x80000000u;
@@ -421,6 +426,53 @@ __device__ inline int reroot_game(const EngineParams &P, int g, TreeLds &L, azh_
 
 // ------------------------------------------------------------------ ply advance
 
+// Policy target pruning (azh_engine_set_forced_playouts; DESIGN.md, "Forced playouts and policy target pruning"): the visit
+// distribution of the ply's record, rec, from the root's M edges (N = root visits) with the forced visits that PUCT would
+// not have spent taken back (forced_prune_edge); an edge pruned to 0 is left out.  Returns the number of entries written.
+// Reads the edges again in two rolled loops of its own instead of sharing advance_game's registers: advance_game is part of
+// the tower kernels, which have no register to spare.
+__device__ inline int record_pruned_counts(const EngineParams &P, const Arena &A, u32 first, int M, u32 N, u32 *rec)
+{
+    const int lane = lane_id();
+    u64 key = 0;  // the most visited edge, ties to the lowest index: it keeps its visits and sets the bar S
+#pragma unroll 1
+    for (int j = lane; j < M; j += WAVE) {
+        const u64 kk = ((u64)(reinterpret_cast<const u32 *>(&A.ed[first + j])[2] & 0xFFFFu) << 32) | (u64)(0xFFFFFFFFu - (u32)j);
+        key = kk > key ? kk : key;
+    }
+    key = wave_max_u64(key);
+    const int best = M > 0 ? (int)(0xFFFFFFFFu - (u32)key) : 0;
+    const u32 n_b = (u32)(key >> 32);
+    const uint2 bw = *reinterpret_cast<const uint2 *>(&A.ed[first + (u32)best]);
+    const float sq = sqrtf((float)(1u + N));
+    const float S = forced_score(u2f(bw.x & PRIOR_MASK), n_b ? u2f(bw.y) / (float)n_b : 0.0f, n_b, sq, P.c_puct);
+    const u64 lt = (1ULL << lane) - 1ULL;
+    int nd = 0;
+#pragma unroll 1
+    for (int j0 = 0; j0 < M; j0 += WAVE) {
+        const int j = j0 + lane;
+        bool has = false;
+        u32 word = 0;
+        if (j < M) {
+            const uint4 ev = A.ed[first + j];
+            u32 wr = edge_visits(ev);
+            if (j != best && wr >= 1u)
+                wr = forced_prune_edge(u2f(ev.x & PRIOR_MASK), u2f(ev.y), wr, N, P.forced_k, P.c_puct, sq, S);
+            has = edge_child(ev) != ENONE && wr != 0u;
+            word = (u32)A.em[first + j] | (wr << 16);
+        }
+        const u64 mask = __ballot(has);
+        if (has)
+            rec[REC_HDR_WORDS + nd + __popcll(mask & lt)] = word;
+        nd += __popcll(mask);
+    }
+    return nd;
+}
+
+// PRUNE: the instantiation that can record pruned counts (forced playouts) — k_advance_list's.  The tower kernels carry the
+// other one: they have no register to spare for the pruning (a 16-bit tower went to scratch memory with it), so while forced
+// playouts are on the device loop plays the queued moves in a k_advance_list launch of its own in front of the tower.
+template <bool PRUNE>
 __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
 {
     u16 *s_moves = L.moves;
@@ -526,18 +578,26 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
         }
     }
 
-    // record the ply (:565-572): board, move, visit distribution over expanded edges
+    // record the ply (:565-572): board, move, visit distribution over expanded edges — on a ply forced playouts act on
+    // (the plies whose root got the noise) the pruned counts instead; the move above and the re-root below see the raw ones
     u32 *rec = P.rec + ((size_t)g * P.max_plies + s.ply) * REC_STRIDE_WORDS;
     const u64 lt = (1ULL << lane) - 1ULL;
     int nd = 0;
+    bool pruned = false;
+    if constexpr (PRUNE)
+        pruned = P.forced_k != 0.0f && (ply_kind_of(P, g) & PLY_FULL) != 0u;
+    if (pruned) {
+        nd = record_pruned_counts(P, A, first, M, N, rec);
+    } else {
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int j = lane + 64 * k;
-        const bool has = j < M && ch[k] != ENONE;
-        const u64 mask = __ballot(has);
-        if (has)
-            rec[REC_HDR_WORDS + nd + __popcll(mask & lt)] = mvs[k] | (nv[k] << 16);
-        nd += __popcll(mask);
+        for (int k = 0; k < 4; k++) {
+            const int j = lane + 64 * k;
+            const bool has = j < M && ch[k] != ENONE;
+            const u64 mask = __ballot(has);
+            if (has)
+                rec[REC_HDR_WORDS + nd + __popcll(mask & lt)] = mvs[k] | (nv[k] << 16);
+            nd += __popcll(mask);
+        }
     }
     const int ck = chosen >> 6, cl = chosen & 63;
     const u32 my_mv = ck == 0 ? mvs[0] : (ck == 1 ? mvs[1] : (ck == 2 ? mvs[2] : mvs[3]));
@@ -609,7 +669,7 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
                 out[5] = (u32)words;
                 out[6] = (P.flags & AZH_FLAG_ONE_RANDOM_MOVE) ? (u32)random_ply_of(P, s.uid) + 1u : 0u;
                 out[7] = (loaded ? 2u : 0u)   // 2: partial game (begins at a loaded position): formatted by the host, not written
-                         | (P.fast_visits != 0 ? REC_KIND_PLAYOUT_CAP : 0u);
+                         | (P.fast_visits != 0 ? REC_KIND_PLAYOUT_CAP : 0u) | (P.forced_k != 0.0f ? REC_KIND_FORCED : 0u);
             }
             u32 pos = 8;
             for (int p = p0; p < s.ply; p++) {
@@ -671,7 +731,7 @@ __device__ inline void advance_worker(const EngineParams &P, unsigned char *smem
     TreeLds &L = *reinterpret_cast<TreeLds *>(smem);
     const int n = *P.adv_count;
     for (int i = worker; i < n; i += workers) {
-        advance_game(P, P.adv_list[i], L);
+        advance_game<false>(P, P.adv_list[i], L);
         wave_sync();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -205,7 +205,8 @@ static void append_double(double v, std::string &out)
 }
 
 // rec: ring record (engine.hip k_advance): 8-word header {magic, slot, uid, plies,
-// result, words, random_ply + 1 (0 = none), kind (1 dropped, 2 partial; | 4: playout cap on)} then per ply {x lo, x hi,
+// result, words, random_ply + 1 (0 = none), kind (1 dropped, 2 partial; | 4: playout cap on; | 8: forced playouts on, the
+// counts of the plies it acts on are the pruned ones — nothing here depends on it)} then per ply {x lo, x hi,
 // o lo, o hi, move | nd << 16, full (playout cap: 1 = searched in full), nd x (move | visits << 16)}.
 // with_ids (arena): two extra keys, "slot" and "uid", so the caller can tell which net had x.
 std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_ids)
@@ -285,7 +286,7 @@ bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plie
     if (rec[7] == 1)  // the marker a dropped game leaves: a header and nothing else
         return rec[5] == 8;
     *why = "header fields out of range";
-    if ((rec[7] & ~4u) > 2 || (rec[7] & 3u) == 1 || rec[4] > 2 || (max_plies && rec[3] > max_plies))
+    if ((rec[7] & ~12u) > 2 || (rec[7] & 3u) == 1 || rec[4] > 2 || (max_plies && rec[3] > max_plies))
         return false;
     *why = "a ply runs past the record's words";
     size_t pos = 8;

@@ -133,6 +133,8 @@ SIGNATURES = {
     "azh_engine_set_batch_evals": (ctypes.c_int, [_vp, _vp, _vp]),
     "azh_engine_set_playout_cap": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int]),
     "azh_playout_cap_kind": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
+    "azh_engine_set_forced_playouts": (ctypes.c_int, [_vp, _f32]),
+    "azh_forced_prune": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _f32, _f32, _vp]),
     "azh_engine_set_solver": (ctypes.c_int, [_vp, ctypes.c_int]),
     "azh_engine_proof_stats": (ctypes.c_int, [_vp, _vp]),
     "azh_engine_root_proofs": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
@@ -248,6 +250,20 @@ def playout_cap_kind(seed, uid, ply, full_per_65536):
     """Playout cap randomization: 1 if ply `ply` of game `uid` of an engine with `seed` is a FULL ply, else 0
     (azh_playout_cap_kind; host arithmetic, no GPU needed)."""
     return int(load().azh_playout_cap_kind(int(seed), int(uid), int(ply), int(full_per_65536)))
+
+
+def forced_prune(prior, W, n, k, c_puct):
+    """Policy target pruning (Engine.set_forced_playouts): the visit counts written into a ply's record for a root with
+    priors `prior` (after the noise mix), total scores `W` and visits `n` — (M,) u32, 0 where the edge is left out
+    (azh_forced_prune; host arithmetic, no GPU needed)."""
+    prior = np.ascontiguousarray(prior, dtype=np.float32)
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    n = np.ascontiguousarray(n, dtype=np.uint32)
+    if not len(prior) == len(W) == len(n):
+        raise ValueError("prior, W and n must have one entry per root edge")
+    out = np.zeros(len(n), dtype=np.uint32)
+    check(load().azh_forced_prune(_ptr(prior), _ptr(W), _ptr(n), len(n), float(k), float(c_puct), _ptr(out)))
+    return out
 
 
 def full_per_65536(full_fraction):
@@ -450,6 +466,12 @@ class Engine:
         plies — a share full_per_65536 / 65536, drawn per (uid, ply) — as today; game lines gain "full".  fast_visits = 0:
         off.  Between iterations only."""
         check(load().azh_engine_set_playout_cap(self.h, int(fast_visits), int(full_per_65536)))
+
+    def set_forced_playouts(self, k):
+        """Forced playouts at the root and policy target pruning in the records, on the plies whose root gets
+        the Dirichlet mix: a root edge with n >= 1 visits is owed sqrt(k P N) of them, and the counts that go into the game's
+        `dists` leave out the forced visits PUCT would not have spent.  k = 0: off (the default); KataGo uses 2."""
+        check(load().azh_engine_set_forced_playouts(self.h, float(k)))
 
     def set_thin_batches(self, mode):
         """0: the 3-board tower; 1: one board per workgroup (a handful of leaves per iteration); -1: by the engine's size."""

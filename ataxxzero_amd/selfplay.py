@@ -80,10 +80,13 @@ class SelfPlay:
     The halves are independent game shards (distinct Philox streams, their own uids).
 
     `fast_visits` > 0 turns playout cap randomization on in every half-batch engine (link.Engine.set_playout_cap): a share
-    `full_fraction` of the plies is searched with `visits` and root noise, the others with `fast_visits` and none."""
+    `full_fraction` of the plies is searched with `visits` and root noise, the others with `fast_visits` and none.
+
+    `forced_playouts` = k > 0 turns forced playouts and policy target pruning on in every half-batch engine
+    (link.Engine.set_forced_playouts), on the plies that get root noise."""
 
     def __init__(self, conv_weights, bn_params, games, visits, dtype="bf16", seed=DEFAULT_SEED,
-                 fen=START_FEN_SELFPLAY, streams=1, fast_visits=0, full_fraction=0.25, **cfg):
+                 fen=START_FEN_SELFPLAY, streams=1, fast_visits=0, full_fraction=0.25, forced_playouts=0.0, **cfg):
         self.dtype = link.DTYPES[dtype]
         self.net = link.Net(conv_weights, bn_params, model.BN_EPSILON)
         if streams < 1 or games < streams:
@@ -96,6 +99,8 @@ class SelfPlay:
         self.games = games
         if fast_visits:
             self.set_playout_cap(fast_visits, full_fraction)
+        if forced_playouts:
+            self.set_forced_playouts(forced_playouts)
 
     def run(self, iterations):
         # every engine's whole run is enqueued on its own stream (the calls are asynchronous): the half-batches then
@@ -120,6 +125,11 @@ class SelfPlay:
         """Playout cap randomization in every half-batch engine; fast_visits = 0 turns it off."""
         for e in self.engines:
             e.set_playout_cap(fast_visits, link.full_per_65536(full_fraction))
+
+    def set_forced_playouts(self, k):
+        """Forced playouts and policy target pruning in every half-batch engine; k = 0 turns them off."""
+        for e in self.engines:
+            e.set_forced_playouts(k)
 
     def set_thin_batches(self, mode):
         """1: the towers run one board per workgroup (a handful of leaves per iteration: the tail of a run under a game

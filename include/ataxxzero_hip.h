@@ -279,6 +279,34 @@ int azh_engine_set_playout_cap(azh_engine *e, int fast_visits, int full_per_6553
  * without a device (trainers, tests). */
 int azh_playout_cap_kind(uint64_t seed, uint32_t uid, uint32_t ply, uint32_t full_per_65536);
 
+/* Forced playouts and policy target pruning (an extension, off by default; KataGo, "Accelerating Self-Play Learning in Go",
+ * section 3.2).  k = 0 switches the mode off (the state after create), k > 0 on (KataGo: 2); k < 0 or NaN is refused.  The
+ * mode acts on the plies whose root priors get the Dirichlet mix: every ply while the playout cap is off, the FULL plies
+ * while it is on; FAST plies are searched and recorded as ever.  All f32 operations below are single IEEE operations in the
+ * order written, sqrtf the correctly rounded one.
+ * FORCED PLAYOUTS, at the root level of a fresh descent (not of one the level budget parked and that resumes): with
+ * N = root_visits, P_j the prior of root edge j after the noise mix and n_j its visits, edge j is OWED iff n_j >= 1 and
+ * (float)n_j < sqrtf((k * P_j) * (float)N).  If an edge is owed the descent takes an owed edge — the last in edge order, the
+ * first under AZH_FLAG_TIE_FIRST — else the level is the PUCT level.  Below the root nothing changes; the root level counts
+ * in the level budget and the counters as any level.
+ * POLICY TARGET PRUNING, when the ply is recorded: the move is sampled from the raw visits and the tree is re-rooted exactly
+ * as with the mode off (the game's trajectory does not depend on pruning; the played move may be absent from the ply's
+ * dists); only the visit counts written into the record, and so the line's dists, change.  With sq = sqrtf((float)(1 + N)),
+ * b the root edge with the most visits (ties: the lowest index) and S = ((sq / (1 + n_b)) * (c_puct * P_b)) + W_b / n_b, edge
+ * b keeps n_b, and for every other edge j with n_j >= 1: f_j = (u32)floorf(sqrtf((k * P_j) * (float)N)), q_j = W_j /
+ * (float)n_j, m = n_j; up to f_j times: if m >= 1 and ((sq / (1.0f + (float)(m - 1))) * (c_puct * P_j)) + q_j < S then m -= 1,
+ * else stop; if m < n_j and m <= 1 then m = 0.  Edges with m = 0 are left out of the record; nd counts the written ones.
+ * The record of a game finished while the mode is on carries bit 3 (value 8) in header word 7; its line has the usual keys.
+ * Refused (the engine stays as it was) with AZH_FLAG_TWO_NETS and AZH_FLAG_ONE_RANDOM_MOVE, with more than one leaf per
+ * game and with the solver; while the mode is on azh_engine_set_leaf_batch (K > 1) and azh_engine_set_solver (on) refuse in
+ * turn.  Call before the first select or between iterations.  Definition and measurements: DESIGN.md, "Forced playouts and
+ * policy target pruning". */
+int azh_engine_set_forced_playouts(azh_engine *e, float k);
+/* The visit counts the pruning above writes for a root of M edges — prior [M] (after the noise mix), W [M] total scores,
+ * n [M] visits, N their sum — into out [M] (0: the edge is left out of the record).  Host arithmetic only, usable without a
+ * device: the same per-edge function the device's ply record uses. */
+int azh_forced_prune(const float *prior, const float *W, const uint32_t *n, int M, float k, float c_puct, uint32_t *out);
+
 /* Proven wins and losses in the tree (MCTS-solver; an extension, off by default; DESIGN.md, "Proven wins and losses").
  * A node is DECIDED if it is a finished position or was PROVEN: after every batch's backup, for each path that ended at a
  * decided node, the node's parent is a proven win (+1 for its side to move) if one of its children is decided with -1, and

@@ -1,0 +1,343 @@
+"""Forced playouts and policy target pruning on the MI355X (azh_engine_set_forced_playouts): the search in lock step with
+the numpy restatement (tests/forced_reference.py) iteration by iteration, the pruned counts of the staged records, the
+playout cap's FAST plies left alone, the tie rule, wide roots, the device loop against host stepping, off is off, and the
+refusals."""
+import numpy as np
+import pytest
+
+from ataxxzero_amd import link, model
+from oracle import oracle_lib as orc
+from tests import forced_reference as fr
+from tests import helpers
+from tests import vl_reference as vlr
+
+pytestmark = pytest.mark.gpu
+
+MAGIC = 0x415A4847
+SEED = 424242
+C_PUCT = 1.0
+REC_KIND_FORCED = 8
+
+# Positions with many legal moves, found on the CPU with the oracle's uniformly random play from the plain start position
+# (x5o/7/7/7/7/7/o5x x, no blockers): the widest with at most 128 moves (128) and the widest of all (157) in 20,000 games.
+WIDE_FEN_MID = "1xxoo2/x3o2/oooooo1/1ooooo1/1o2o1o/1oo1xx1/1oo1x1x o"
+WIDE_FEN_BIG = "2oo1xx/o2o3/o2oooo/2oo2o/2oo3/o1oooo1/1o2o2 o"
+
+
+def _late_start():
+    """An unfinished fixture position with 10-14 empty squares and both sides well alive: games from it last a few dozen
+    plies, so thresholds, tree reuse, game ends and restarts all occur within a few hundred iterations."""
+    for rec in helpers.load_gz("rules_noblock.json.gz"):
+        p = orc.pos_from_fen(rec["fen"])
+        x, o = int(p.pieces[0]), int(p.pieces[1])
+        if orc.result(p) != 0 or len(orc.movegen(p)) == 0:
+            continue
+        if 10 <= 49 - bin(x | o).count("1") <= 14 and min(bin(x).count("1"), bin(o).count("1")) >= 10:
+            return x, o, int(p.turn)
+    raise AssertionError("no such fixture position")
+
+
+START = _late_start()
+
+
+def _engine(games, visits, weight=0.25, seed=SEED, flags=0, cap=None, k=None, start=START, edges_per_node=96):
+    x, o, turn = start
+    cfg = link.Config(games=games, visits=visits, max_plies=400, edges_per_node=edges_per_node, c_puct=C_PUCT,
+                      dirichlet_alpha=0.15, dirichlet_weight=weight, start_turn=turn, seed=seed, start_x=x, start_o=o,
+                      blockers=0, flags=flags)
+    e = link.Engine(cfg)
+    if cap is not None:
+        e.set_playout_cap(*cap)
+    if k is not None:
+        e.set_forced_playouts(k)
+    return e
+
+
+def _net(seed=3):
+    conv, bn = model.random_init(1, 128, seed=seed, perturb_bn=True)
+    return link.Net(conv, bn)
+
+
+def _step(e):
+    e.select()
+    need, lb = e.leaves()
+    logits, values = helpers.synthetic_evals_distinct(lb)
+    e.set_evals(logits, values)
+    e.backup()
+    return values
+
+
+def _dump(e):
+    return [e.game_state(g).as_tuple() for g in range(e.G)], [e.tree(g) for g in range(e.G)]
+
+
+def _same(da, db):
+    (sa, ta), (sb, tb) = da, db
+    assert sa == sb
+    for x, y in zip(ta, tb):
+        for u, v in zip(x, y):
+            assert u.shape == v.shape and (u == v).all()
+
+
+def _records(words):
+    """[(slot, uid, result, kind word, [(move, full, {move: visits})])] of the staged record words (dropped markers skipped)"""
+    out, pos = [], 0
+    while pos < len(words):
+        assert words[pos] == MAGIC
+        slot, uid, plies, result, n, kind = (int(words[pos + i]) for i in (1, 2, 3, 4, 5, 7))
+        if kind & 3 != 1:
+            q, rows = pos + 8, []
+            for _ in range(plies):
+                nd = int(words[q + 4]) >> 16
+                rows.append((int(words[q + 4]) & 0xFFFF, int(words[q + 5]),
+                             {int(w) & 0xFFFF: int(w) >> 16 for w in words[q + 6:q + 6 + nd]}))
+                q += 6 + nd
+            assert q == pos + n
+            out.append((slot, uid, result, kind, rows))
+        pos += n
+    return out
+
+
+def _check_root_marks(e, g=0):
+    """the raw-mark invariant of tests/test_gpu_engine.py at the root: at most one mark, and only on an edge whose child
+    exists, is unfinished and has 1 .. 128 moves"""
+    _, info, _, _ = e.tree(g)
+    raw = e.tree_raw(g)
+    first, m = int(info[0, 0]), int(info[0, 1] & 0xFFFF)
+    idx = np.nonzero((raw[first:first + m, 0] >> 31) != 0)[0]
+    assert len(idx) <= 1, idx.tolist()
+    if len(idx):
+        z, w = int(raw[first + idx[0], 2]), int(raw[first + idx[0], 3])
+        assert m <= 128 and (z >> 16) != 0xFFFF and (w >> 31) == 0 and 1 <= ((w >> 23) & 0xFF) <= 128, (m, hex(z), hex(w))
+    return len(idx)
+
+
+def _expected_counts(tree, k):
+    """{move: written visits} of the ply played from `tree`, by the restatement"""
+    prior, W, n, moves, child = fr.root_arrays(tree)
+    m = fr.prune(prior, W, n, k, C_PUCT)
+    return {int(mv): int(c) for mv, c, ch in zip(moves, m, child) if ch != vlr.NONE and c != 0}
+
+
+def _raw_counts(tree):
+    prior, W, n, moves, child = fr.root_arrays(tree)
+    return {int(mv): int(c) for mv, c, ch in zip(moves, n, child) if ch != vlr.NONE}
+
+
+def _lock_step(e, k, games, cap=None, tie_first=False, max_iterations=9000):
+    """One game slot against the restatement, iteration by iteration, over `games` complete games -> counters.  An
+    iteration of the step-wise API is select (a game whose move is due gets no leaf), the due moves, backup and mark: a
+    game in phase 1 takes one path, and when the iteration leaves it in phase 2 its move is played by the next one, from the
+    tree as it then stands."""
+    seen = {"owed": 0, "differs": 0, "marks": 0, "pruned_plies": 0, "fast": 0, "full": 0, "fast_owed_ignored": 0}
+    expected = {}    # (uid, ply) -> ({move: written visits}, full)
+    done = 0
+    for it in range(max_iterations):
+        st = e.game_state(0)
+        full = 1 if cap is None else link.playout_cap_kind(SEED, st.uid, st.ply, cap[1])
+        b = None
+        if st.phase == 1:
+            pre = e.tree(0)
+            b = fr.select(pre, st.root_visits, k, bool(full), C_PUCT, tie_first, 0)
+            if not full:
+                prior, W, n, _, _ = fr.root_arrays(pre)
+                seen["fast_owed_ignored"] += int(fr.owed(prior, n, st.root_visits, k).any())
+        values = _step(e)
+        s2 = e.game_state(0)
+        if b is not None:
+            assert (s2.uid, s2.ply) == (st.uid, st.ply)
+            post = e.tree(0)
+            (eb, ei, ee, em), added = vlr.expected_tree(b, values, post)
+            assert (eb == post[0]).all() and (ei == post[1]).all() and (ee == post[2]).all() and (em == post[3]).all(), it
+            assert s2.root_visits == st.root_visits + added
+            seen["owed"] += int(b.forced is not None)
+            seen["differs"] += int(b.forced is not None and b.forced != b.puct)
+            seen["marks"] += _check_root_marks(e)
+        if s2.phase == 2 and st.phase != 2:
+            # the move of this ply is due: the next iteration plays it from this tree
+            post = e.tree(0)
+            want = _expected_counts(post, k) if full else _raw_counts(post)
+            seen["pruned_plies"] += int(bool(full) and want != _raw_counts(post))
+            expected[(s2.uid, s2.ply)] = (want, full)
+        if s2.uid != st.uid:
+            e.fetch()
+            for slot, uid, result, kind, rows in _records(e.staged_records()):
+                assert kind & REC_KIND_FORCED and bool(kind & 4) == (cap is not None)
+                for ply, (move, fullw, counts) in enumerate(rows):
+                    want, f = expected[(uid, ply)]
+                    assert counts == want, (uid, ply, f, counts, want)
+                    assert cap is None or fullw == f
+                    seen["full" if f else "fast"] += 1
+                done += 1
+            e.drain_json()
+            if done >= games:
+                break
+    assert done >= games
+    return seen
+
+
+def test_lock_step_with_the_restatement():
+    e = _engine(1, 48, k=2.0)
+    seen = _lock_step(e, 2.0, 3)
+    assert seen["owed"] > 0 and seen["differs"] > 0 and seen["pruned_plies"] > 0 and seen["marks"] > 0, seen
+    e.close()
+
+
+def test_lock_step_with_the_playout_cap_on():
+    cap = (6, 32768)
+    e = _engine(1, 48, k=2.0, cap=cap)
+    seen = _lock_step(e, 2.0, 3, cap=cap)
+    assert seen["owed"] > 0 and seen["differs"] > 0 and seen["pruned_plies"] > 0, seen
+    assert seen["fast"] > 0 and seen["full"] > 0 and seen["fast_owed_ignored"] > 0, seen
+    e.close()
+
+
+def test_lock_step_with_ties_to_the_first_edge():
+    e = _engine(1, 48, k=2.0, flags=link.FLAG_TIE_FIRST)
+    seen = _lock_step(e, 2.0, 1, tie_first=True)
+    assert seen["owed"] > 0 and seen["differs"] > 0, seen
+    e.close()
+
+
+@pytest.mark.parametrize("fen,lo,hi", [(WIDE_FEN_MID, 65, 128), (WIDE_FEN_BIG, 129, 256)])
+def test_wide_roots(fen, lo, hi):
+    """One ply from a position with more than 64 (two records per lane) and more than 128 (the general level's four) legal
+    moves, visits enough that owed edges lie beyond the first record of a lane, in lock step with the restatement."""
+    p = orc.pos_from_fen(fen)
+    M = len(orc.movegen(p))
+    assert lo <= M <= hi
+    visits, k = 3 * M, 8.0
+    e = _engine(1, visits, k=k, edges_per_node=200)
+    e.set_positions(np.array([[int(p.pieces[0]) | (int(p.turn) << 63), int(p.pieces[1])]], dtype=np.uint64),
+                    np.zeros(1, dtype=np.int32))
+    owed_high = differs = 0
+    for it in range(visits + 5):
+        st = e.game_state(0)
+        if st.phase == 2:
+            break
+        if st.phase != 1:
+            _step(e)
+            continue
+        pre = e.tree(0)
+        assert int(pre[1][0, 1]) & 0xFFFF == M
+        b = fr.select(pre, st.root_visits, k, True, C_PUCT, False, 0)
+        values = _step(e)
+        post = e.tree(0)
+        (eb, ei, ee, em), added = vlr.expected_tree(b, values, post)
+        assert (eb == post[0]).all() and (ei == post[1]).all() and (ee == post[2]).all() and (em == post[3]).all(), it
+        owed_high += int(b.forced is not None and b.forced >= 64)
+        differs += int(b.forced is not None and b.forced != b.puct)
+        _check_root_marks(e)
+    st = e.game_state(0)
+    assert st.phase == 2 and st.root_visits >= visits and owed_high > 0 and differs > 0, (st.as_tuple(), owed_high, differs)
+    e.close()
+
+
+@pytest.mark.parametrize("games", [5, 33, 130])
+def test_device_loop_equals_host_stepping(games):
+    net = _net()
+    visits, k, n = 16, 2.0, 600
+    a = _engine(games, visits, k=k)
+    b = _engine(games, visits, k=k)
+    a.run(net, n, link.DTYPE_BF16)
+    a.sync()
+    for _ in range(n):
+        b.select()
+        b.eval(net, link.DTYPE_BF16)
+        b.backup()
+    _same(_dump(a), _dump(b))
+    assert a.stats() == b.stats() and a.stats()["plies"] > 4 * games
+    a.fetch(), b.fetch()
+    ra, rb = _records(a.staged_records()), _records(b.staged_records())
+    assert sorted(a.drain_json()) == sorted(b.drain_json()) and len(ra) == len(rb) > 0
+    short = 0
+    for slot, uid, result, kind, rows in ra:
+        assert kind & REC_KIND_FORCED
+        for move, full, counts in rows:
+            assert counts and all(c >= 1 for c in counts.values())
+            assert sum(counts.values()) <= visits      # (every ply is played at `visits` raw visits: an inherited root has fewer)
+            short += int(sum(counts.values()) < visits)
+    assert short > 0     # some ply wrote fewer visits than its threshold: something was pruned
+    a.close(), b.close()
+
+
+def test_off_is_off():
+    ref = _engine(3, 24)
+    never = _engine(3, 24)
+    off = _engine(3, 24, k=2.0)
+    off.set_forced_playouts(0.0)
+    lines = {id(x): [] for x in (ref, never, off)}
+    for it in range(1500):
+        for x in (ref, never, off):
+            _step(x)
+        if it % 10 == 0 or len(lines[id(ref)]) >= 3:
+            _same(_dump(ref), _dump(never))
+            _same(_dump(ref), _dump(off))
+        for x in (ref, never, off):
+            x.fetch()
+            for r in _records(x.staged_records()):
+                assert not r[3] & REC_KIND_FORCED
+            lines[id(x)] += x.drain_json()
+        if len(lines[id(ref)]) >= 3:
+            break
+    assert len(lines[id(ref)]) >= 3 and lines[id(ref)] == lines[id(never)] == lines[id(off)]
+    assert ref.stats() == never.stats() == off.stats()
+    # ... and the mode, switched on, does change the search (the comparison above is not vacuous)
+    on = _engine(3, 24, k=2.0)
+    ref2 = _engine(3, 24)
+    differ = False
+    for it in range(200):
+        _step(on), _step(ref2)
+        differ = differ or any((x.shape != y.shape or (x != y).any()) for g in range(3) for x, y in zip(on.tree(g), ref2.tree(g)))
+    assert differ
+    for x in (ref, never, off, on, ref2):
+        x.close()
+
+
+def test_refusals_leave_the_engine_usable():
+    e = _engine(4, 24)
+    for bad in (-1.0, float("nan")):
+        with pytest.raises(link.AzhError):
+            e.set_forced_playouts(bad)
+    _step(e)
+    e.select()
+    with pytest.raises(link.AzhError):
+        e.set_forced_playouts(2.0)            # a selected batch awaits its backup
+    need, lb = e.leaves()
+    e.set_evals(*helpers.synthetic_evals_distinct(lb))
+    e.backup()
+    e.set_forced_playouts(2.0)
+    with pytest.raises(link.AzhError):
+        e.set_leaf_batch(4, 1)                # K > 1 while the mode is on
+    with pytest.raises(link.AzhError):
+        e.set_solver(True)
+    e.set_leaf_batch(1, 1)                    # K = 1 without the solver is the one-leaf search: no request
+    for _ in range(40):
+        _step(e)
+    assert e.stats()["plies"] > 0
+    e.set_forced_playouts(0.0)
+    e.set_leaf_batch(4, 1)
+    with pytest.raises(link.AzhError):
+        e.set_forced_playouts(2.0)            # ... and the other way round
+    e.set_leaf_batch(1, 1)
+    e.set_solver(True)
+    with pytest.raises(link.AzhError):
+        e.set_forced_playouts(2.0)
+    e.set_solver(False)
+    e.set_forced_playouts(2.0)
+    for _ in range(30):
+        _step(e)
+    e.close()
+    for flags in (link.FLAG_TWO_NETS, link.FLAG_ONE_RANDOM_MOVE):
+        r = _engine(4, 24, weight=0.0, flags=flags)
+        with pytest.raises(link.AzhError):
+            r.set_forced_playouts(2.0)
+        r.set_forced_playouts(0.0)            # switching off is no request for the mode
+        net = _net()
+        if flags == link.FLAG_TWO_NETS:
+            r.run_arena(net, net, 20, link.DTYPE_F32)
+        else:
+            r.run(net, 20, link.DTYPE_F32)
+        r.sync()
+        assert r.stats()["steps"] > 0
+        r.close()

@@ -8,6 +8,12 @@ observable of "the workers outlasted the tiles", so the mean excess per launch s
 
     python tools/playout_cap_rate.py [--pairs 3] [--steps 8] [--out profiles/playout_cap.txt]
 
+With --forced-playouts K the two legs are forced playouts and policy target pruning off against on (k = K) instead — the cap
+off in both, or on in both with --cap — and the report adds the mean share of a ply's visits the pruning took out of its
+record, over the plies the mode acts on:
+
+    python tools/playout_cap_rate.py --forced-playouts 2 [--cap] --out profiles/forced_playouts.txt
+
 Appends its report to --out.  GPU box, repo root."""
 import argparse
 import os
@@ -24,6 +30,26 @@ from ataxxzero_amd import link, model, selfplay  # noqa: E402
 
 SNAPSHOT = os.path.join(ROOT, "profiles", "round2_steady_state_positions.npz")
 MAGIC = 0x415A4847
+
+
+def pruned_share(words, visits):
+    """(sum over the acting plies of 1 - written visits / `visits`, acting plies) over the staged record words of an engine
+    with forced playouts on: the plies of games that carry the mode's bit (8 in header word 7), FULL ones if the cap is on"""
+    share, acting, pos = 0.0, 0, 0
+    while pos + 8 <= len(words):
+        if words[pos] != MAGIC:
+            pos += 1
+            continue
+        n, q, kind = int(words[pos + 5]), pos + 8, int(words[pos + 7])
+        if kind & 3 != 1:
+            for _ in range(int(words[pos + 3])):
+                nd = int(words[q + 4]) >> 16
+                if kind & 8 and (int(words[q + 5]) or not kind & 4):
+                    share += 1.0 - min(1.0, float((words[q + 6:q + 6 + nd] >> 16).sum()) / visits)
+                    acting += 1
+                q += 6 + nd
+        pos += max(n, 8)
+    return share, acting
 
 
 def full_share(words):
@@ -43,10 +69,11 @@ def full_share(words):
     return full, plies
 
 
-def leg(conv, bn, args, cap, seed):
+def leg(conv, bn, args, cap, seed, forced=0.0):
     sp = selfplay.SelfPlay(conv, bn, games=args.games, visits=args.visits, dtype=args.dtype, seed=seed, streams=2,
                            flags=link.FLAG_EVAL_CACHE, select_budget=48,
-                           fast_visits=args.fast_visits if cap else 0, full_fraction=args.full_search_fraction)
+                           fast_visits=args.fast_visits if cap else 0, full_fraction=args.full_search_fraction,
+                           forced_playouts=forced)
     snap = np.load(SNAPSHOT)
     rng = np.random.default_rng(seed)
     pick = rng.permutation(len(snap["plies"])) if args.games == len(snap["plies"]) else rng.integers(0, len(snap["plies"]), size=args.games)
@@ -57,7 +84,8 @@ def leg(conv, bn, args, cap, seed):
     sp.sync()
     st0 = sp.stats()
     sp.timing_reset(16)
-    full = plies = 0
+    full = plies = acting = 0
+    pruned = 0.0
     t0 = time.perf_counter()
     for _ in range(args.steps):
         sp.run(250)
@@ -65,6 +93,9 @@ def leg(conv, bn, args, cap, seed):
         for e in sp.engines:
             f, p = full_share(e.staged_records())
             full, plies = full + f, plies + p
+            if forced:
+                s, a = pruned_share(e.staged_records(), args.visits)
+                pruned, acting = pruned + s, acting + a
         sp.drain()
     sp.sync()
     dt = time.perf_counter() - t0
@@ -76,7 +107,7 @@ def leg(conv, bn, args, cap, seed):
     bare_ms = sp.net.bench(max(1, int(round(batch))), 20, link.DTYPES[args.dtype])
     sp.close()
     share = 1.0 if not cap else (full / plies if plies else float("nan"))   # (cap off: every ply is searched in full)
-    return {"cap": cap, "plies_s": st["plies"] / dt, "games_s": st["games"] / dt,
+    return {"forced": forced, "pruned_share": pruned / acting if acting else float("nan"), "cap": cap, "plies_s": st["plies"] / dt, "games_s": st["games"] / dt,
             "full_share": share, "full_plies_s": st["plies"] / dt * share, "evals_s": st["nn_evals"] / dt,
             "plies_per_iter": st["plies"] / (2.0 * iters), "batch": batch, "tower_us": 1e3 * tower_ms,
             "bare_us": 1e3 * bare_ms, "iter_s": iters / dt}
@@ -85,7 +116,7 @@ def leg(conv, bn, args, cap, seed):
 def row(r):
     return ("%-4s plies/s %8.1f  games/s %6.2f  full plies/s %8.1f (share %.3f)  evals/s %9.0f  iterations/s %7.1f  "
             "moves due per launch %5.1f  leaves per launch %6.0f  tower launch %6.1f us, bare tower at that batch %6.1f us (excess %5.1f us)" % (
-                "on" if r["cap"] else "off", r["plies_s"], r["games_s"], r["full_plies_s"], r["full_share"],
+                ("k=%g" % r["forced"] if r["forced"] else "k=0") if r["by_forced"] else "on" if r["cap"] else "off", r["plies_s"], r["games_s"], r["full_plies_s"], r["full_share"],
                 r["evals_s"], r["iter_s"], r["plies_per_iter"], r["batch"], r["tower_us"], r["bare_us"], r["tower_us"] - r["bare_us"]))
 
 
@@ -100,6 +131,9 @@ def main():
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--steps", type=int, default=8, help="timed steps of 250 iterations per leg")
     ap.add_argument("--fill", type=int, default=1000, help="untimed iterations after the positions are loaded")
+    ap.add_argument("--forced-playouts", type=float, default=0.0, metavar="K",
+                    help="the legs are forced playouts off against on (k = K) instead of the cap off against on")
+    ap.add_argument("--cap", action="store_true", help="with --forced-playouts: the playout cap on in both legs")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "playout_cap.txt"))
     args = ap.parse_args()
     selfplay.select_device(0)
@@ -109,21 +143,32 @@ def main():
              % (link.pci_bus_id(0), args.games, args.blocks, args.dtype, args.visits, args.fast_visits,
                 args.full_search_fraction, args.steps, args.fill)]
     rows = []
+    by_forced = args.forced_playouts > 0
+    if by_forced:
+        lines[0] += "; legs: forced playouts off against k = %g, the cap %s in both" % (args.forced_playouts, "on" if args.cap else "off")
     for pair in range(args.pairs):
-        for cap in (False, True):
-            r = leg(conv, bn, args, cap, seed=1000 + pair)
+        for second in (False, True):
+            if by_forced:
+                r = leg(conv, bn, args, args.cap, seed=1000 + pair, forced=args.forced_playouts if second else 0.0)
+            else:
+                r = leg(conv, bn, args, second, seed=1000 + pair)
+            r["by_forced"], r["second"] = by_forced, second
             rows.append(r)
-            lines.append(row(r))
+            lines.append(row(r) + ("  visits pruned per acting ply %.4f" % r["pruned_share"] if r["forced"] else ""))
             print(lines[-1], flush=True)
     for key, name in (("plies_s", "plies/s"), ("games_s", "finished games/s"), ("full_plies_s", "full plies/s")):
-        off = [r[key] for r in rows if not r["cap"]]
-        on = [r[key] for r in rows if r["cap"]]
+        off = [r[key] for r in rows if not r["second"]]
+        on = [r[key] for r in rows if r["second"]]
         m_off, m_on = statistics.mean(off), statistics.mean(on)
         lines.append("mean %-17s off %9.2f  on %9.2f  ratio %s" % (name, m_off, m_on, "%.3f" % (m_on / m_off) if m_off else "-"))
         print(lines[-1])
+    if by_forced:
+        lines.append("mean share of a ply's visits pruned from its record, over the plies the mode acts on: %.4f"
+                     % statistics.mean(r["pruned_share"] for r in rows if r["second"]))
     bound = args.visits / (args.full_search_fraction * args.visits + (1 - args.full_search_fraction) * args.fast_visits)
-    lines.append("(visits / mean threshold = %.2fx: arithmetic, not a measurement, and no bound — a re-rooted root inherits visits, "
-                 "and one that already meets the fast threshold plays after its root evaluation alone)" % bound)
+    if not by_forced:
+        lines.append("(visits / mean threshold = %.2fx: arithmetic, not a measurement, and no bound — a re-rooted root inherits visits, "
+                     "and one that already meets the fast threshold plays after its root evaluation alone)" % bound)
     with open(args.out, "a") as f:
         f.write("\n".join(lines) + "\n")
 
