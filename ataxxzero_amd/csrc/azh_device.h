@@ -408,6 +408,7 @@ constexpr u32 STREAM_SAMPLE = 1u;
 constexpr u32 STREAM_RANDOM_PLAY = 2u;
 constexpr u32 STREAM_RANDOM_PLY = 3u;
 constexpr u32 STREAM_PLAYOUT_CAP = 4u;
+constexpr u32 STREAM_EVAL_SYMMETRY = 5u;
 
 // Playout cap randomization (azh_engine_set_playout_cap): is ply `ply` of game `uid` searched in FULL?  A pure function of
 // the engine's Philox key, so a trainer or a test restates it without a device (azh_playout_cap_kind).
@@ -469,6 +470,107 @@ __host__ __device__ inline void forced_prune_root(const float *prior, const floa
     for (int j = 0; j < M; j++)
         out[j] = (j == b || n[j] == 0u) ? n[j] : forced_prune_edge(fabsf(prior[j]), W[j], n[j], N, k, c_puct, sq, S);
 }
+
+// ---------------------------------------------------------------- random symmetry per evaluation
+// azh_engine_set_random_symmetry ("Random symmetry per evaluation"): every position goes to the evaluator as its
+// image under one of the 8 dihedral symmetries of the board, and the logits come back through the same symmetry's move map.
+// Symmetry s, as training._symmetry_bits (train.py:11-23): bit 0 mirrors x, bit 1 mirrors y, bit 2 then transposes, on the
+// cells (x, y) = (sq % 7, 6 - sq / 7) of policy_index.  Host and device share every function but the wave's ballot form.
+
+// image_s: where a stone on `sq` lies in the image
+__host__ __device__ inline int symmetry_cell(int s, int sq)
+{
+    int x = sq % 7, y = 6 - sq / 7;
+    if (s & 1) x = 6 - x;
+    if (s & 2) y = 6 - y;
+    if (s & 4) { const int t = x; x = y; y = t; }
+    return x + 7 * (6 - y);
+}
+// the cell whose image is `sq` (the inverse: the transposition is undone first)
+__host__ __device__ inline int symmetry_source_cell(int s, int sq)
+{
+    int x = sq % 7, y = 6 - sq / 7;
+    if (s & 4) { const int t = x; x = y; y = t; }
+    if (s & 1) x = 6 - x;
+    if (s & 2) y = 6 - y;
+    return x + 7 * (6 - y);
+}
+// T_s on a bitboard, one lane (or the host) on its own: a loop over the stones, registers only.
+__host__ __device__ inline u64 symmetry_board(int s, u64 bb)
+{
+    u64 out = 0;
+    for (u64 r = bb & BOARD_MASK; r; r &= r - 1ULL)
+        out |= 1ULL << symmetry_cell(s, __builtin_ctzll(r));
+    return out;
+}
+// T_s on a move: both squares by image_s — a clone stays a clone and policy_index finds the jump's layer from the squares.
+// A value that is no board move (a pass) is returned as it is.
+__host__ __device__ inline u32 symmetry_move(int s, u32 move)
+{
+    const u32 from = move & 0xFFu, to = (move >> 8) & 0xFFu;
+    if (from >= 49u || to >= 49u)
+        return move;
+    return (u32)symmetry_cell(s, (int)from) | ((u32)symmetry_cell(s, (int)to) << 8);
+}
+// T_s on a flat policy index 119 x + 17 y + layer, real move or not: the destination cell by image_s, a jump layer by the image
+// of its (dx, dy) = to - from, the clone layer as it is.  For a move m, symmetry_policy_index(s, policy_index(m)) =
+// policy_index(symmetry_move(s, m)); over all 833 indices it is the permutation that brings the logits of the image back:
+// logits_of_the_position[i] = logits_of_the_image[symmetry_policy_index(s, i)].
+__host__ __device__ inline int symmetry_policy_index(int s, int index)
+{
+    // (the three bits enter as 0 / 1 factors, not as conditions: nothing of s has to be kept as a lane mask around the caller's loop)
+    const int fx = s & 1, fy = (s >> 1) & 1, tr = (s >> 2) & 1;
+    const int x0 = index / 119, rest = index - 119 * x0, y0 = rest / 17;
+    int layer = rest - 17 * y0;
+    if (layer != 16) {
+        int dx, dy;
+        if (layer < 5) { dx = -2; dy = layer - 2; }
+        else if (layer >= 11) { dx = 2; dy = layer - 13; }
+        else { dx = (layer - 5) / 2 - 1; dy = ((layer - 5) & 1) ? 2 : -2; }
+        dx *= 1 - 2 * fx;
+        dy *= 1 - 2 * fy;
+        const int ex = dx + tr * (dy - dx), ey = dy + tr * (dx - dy);
+        if (ex == -2) layer = ey + 2;
+        else if (ex == 2) layer = 13 + ey;
+        else layer = 5 + 2 * (ex + 1) + (ey > 0 ? 1 : 0);
+    }
+    const int x1 = x0 + fx * (6 - 2 * x0), y1 = y0 + fy * (6 - 2 * y0);
+    const int x = x1 + tr * (y1 - x1), y = y1 + tr * (x1 - y1);
+    return 119 * x + 17 * y + layer;
+}
+// The game's key word (one per game: written where the game begins) and the symmetry of a position of that game: a hash of the
+// key and the UNTRANSFORMED leaf board (mover, opponent), u32 arithmetic — a pure function a host restates (azh_eval_symmetry).
+__host__ __device__ inline u32 eval_symmetry_key(u32 k0, u32 k1, u32 uid)
+{
+    return philox(k0, k1, uid, 0u, STREAM_EVAL_SYMMETRY, 0u).v[0];
+}
+__host__ __device__ inline u32 eval_symmetry_mix(u32 a, u32 w)
+{
+    a = (a ^ w) * 0x9E3779B1u;
+    return a ^ (a >> 15);
+}
+__host__ __device__ inline int eval_symmetry_of(u32 key, u64 mover, u64 opponent)
+{
+    u32 a = eval_symmetry_mix(key, (u32)mover);
+    a = eval_symmetry_mix(a, (u32)(mover >> 32));
+    a = eval_symmetry_mix(a, (u32)opponent);
+    a = eval_symmetry_mix(a, (u32)(opponent >> 32));
+    a = a * 0x85EBCA77u;
+    a ^= a >> 13;
+    return (int)(a >> 29);
+}
+// T_s on the two bitboards of a position the whole wave holds (s, mover, opponent wave-uniform): lane i < 49 tests the source
+// cell of image cell i and a ballot assembles each word.  No LDS, no memory.
+__device__ inline void wave_symmetry_boards(int s, u64 &mover, u64 &opponent)
+{
+    const int lane = lane_id();
+    const int src = symmetry_source_cell(s, lane < 49 ? lane : 0);
+    const u64 m = __ballot(lane < 49 && ((mover >> src) & 1ULL) != 0ULL);
+    const u64 o = __ballot(lane < 49 && ((opponent >> src) & 1ULL) != 0ULL);
+    mover = m;
+    opponent = o;
+}
+
 constexpr u32 STREAM_GAMMA = 0x10000u;
 
 // Gamma(alpha, 1), alpha < 1: Marsaglia-Tsang on alpha + 1 with a polar normal,

@@ -123,6 +123,26 @@ __global__ void k_ply_kinds(EngineParams P)
                                                                                                      : (u32)P.fast_visits;
 }
 
+// azh_engine_set_random_symmetry: the key word of the game every slot is at (one thread per slot)
+__global__ void k_eval_keys(EngineParams P)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < P.G)
+        P.eval_key[g] = eval_symmetry_key(P.k0, P.k1, P.gs[g].uid);
+}
+
+// The symmetry under which `node` of slot g's tree goes to the evaluator (0, the identity, while the mode is off): a function
+// of the game's key word and the node's own board, so the select that sends the position, the backup that gathers its logits,
+// the root's re-evaluation at a later ply and a transposition's source node all agree on it.  g, node: wave-uniform.
+__device__ inline int eval_symmetry_at(const EngineParams &P, const Arena &A, int g, int node)
+{
+    if (P.random_symmetry == 0u)
+        return 0;
+    const ulonglong2 w = A.nb[node];
+    const Board b = unpack_board(w.x, w.y);
+    return __builtin_amdgcn_readfirstlane(eval_symmetry_of(P.eval_key[g], b.turn ? b.o : b.x, b.turn ? b.x : b.o));
+}
+
 // ------------------------------------------------------------------ select + expand
 
 // Q + U of one edge (total_action_score :310-324) — IEEE division and square root in the fixed order the oracle restates.
@@ -655,6 +675,8 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
     int need = (kind == AZH_LEAF_EVAL || kind == AZH_LEAF_ROOT) ? 1 : 0;
     if (need && (P.flags & AZH_FLAG_TWO_NETS))
         need = 1 + ((s.ply + g) & 1);  // net A (1) / net B (2) is to move; even slots give x to A
+    if (P.random_symmetry != 0u && need)  // the evaluator sees the position's image (the node keeps the position itself)
+        wave_symmetry_boards(eval_symmetry_of(P.eval_key[g], leaf_mover, leaf_opp), leaf_mover, leaf_opp);
     if (lane == 0) {
         P.gs[g] = s;
         P.need_eval[g] = need;
@@ -682,11 +704,13 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
 // Evaluations::populate (:204-271): the priors of `node` from one row of logits — a softmax over the legal moves' logits,
 // identical to the reference's 833-way softmax renormalised over the legal moves — then, at the root (`root`: the root of a
 // ply that gets noise — every ply, or with the playout cap on the FULL ones), the Dirichlet mix keyed by (uid, ply).
-// Wave-cooperative.
+// `sym` (wave-uniform; eval_symmetry_at): the row holds the logits of the position's image under that symmetry, so a move's
+// logit is the one of its image; 0: the row is the position's own.  Wave-cooperative.
 __device__ inline void apply_priors(const EngineParams &P, const Arena &A, int node, const float *row, bool root, u32 uid,
-                                    u32 ply)
+                                    u32 ply, int sym)
 {
     const int lane = lane_id();
+    const auto logit_index = [sym](u32 mv) { return policy_index(sym != 0 ? symmetry_move(sym, mv) : mv); };
     {
         const uint4 info = A.ni[node];
         const u32 first = info.x;
@@ -697,29 +721,48 @@ __device__ inline void apply_priors(const EngineParams &P, const Arena &A, int n
         if (P.flags & AZH_FLAG_PY_POSTERIOR) {
             // engine.py:197-203: softmax over all 833 logits, gather the legal moves, divide by
             // (their sum + 1e-6)
-            float la[14];
-            float mx = -INFINITY;
+            float mx = -INFINITY, S;
+            if (sym != 0) {
+                // The row holds the image's logits: they are summed in the POSITION's index order (row[T_s(i)] for i ascending),
+                // the same terms in the same order as over a row brought back through the permutation — the f32 sum is
+                // invariant under a permutation only in exact arithmetic, and the priors are part of the bit-exact contract.
+                // Two rolled passes (the maximum does not depend on the order): the index map is not worth 14 copies.
+#pragma unroll 1
+                for (int i = lane; i < AZH_POLICY_SIZE; i += WAVE) {
+                    const float v = row[i];
+                    if (v > mx)
+                        mx = v;
+                }
+                mx = wave_max_f32(mx);
+                float part = 0.0f;
+#pragma unroll 1
+                for (int i = lane; i < AZH_POLICY_SIZE; i += WAVE)
+                    part = part + det_expf(row[symmetry_policy_index(sym, i)] - mx);
+                S = wave_sum_f32(part);
+            } else {
+                float la[14];
 #pragma unroll
-            for (int t = 0; t < 14; t++) {
-                const int i = lane + 64 * t;
-                la[t] = i < AZH_POLICY_SIZE ? row[i] : -INFINITY;
-                if (la[t] > mx)
-                    mx = la[t];
+                for (int t = 0; t < 14; t++) {
+                    const int i = lane + 64 * t;
+                    la[t] = i < AZH_POLICY_SIZE ? row[i] : -INFINITY;
+                    if (la[t] > mx)
+                        mx = la[t];
+                }
+                mx = wave_max_f32(mx);
+                float part = 0.0f;
+#pragma unroll
+                for (int t = 0; t < 14; t++)
+                    if (lane + 64 * t < AZH_POLICY_SIZE)
+                        part = part + det_expf(la[t] - mx);
+                S = wave_sum_f32(part);
             }
-            mx = wave_max_f32(mx);
-            float part = 0.0f;
-#pragma unroll
-            for (int t = 0; t < 14; t++)
-                if (lane + 64 * t < AZH_POLICY_SIZE)
-                    part = part + det_expf(la[t] - mx);
-            const float S = wave_sum_f32(part);
             float lpart = 0.0f;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int j = lane + 64 * k;
                 ex[k] = 0.0f;
                 if (k < rounds && j < M) {
-                    ex[k] = det_expf(row[policy_index(A.em[first + j])] - mx) / S;
+                    ex[k] = det_expf(row[logit_index(A.em[first + j])] - mx) / S;
                     lpart = lpart + ex[k];
                 }
             }
@@ -734,7 +777,7 @@ __device__ inline void apply_priors(const EngineParams &P, const Arena &A, int n
                 const int j = lane + 64 * k;
                 l[k] = -INFINITY;
                 if (k < rounds && j < M) {
-                    l[k] = row[policy_index(A.em[first + j])];
+                    l[k] = row[logit_index(A.em[first + j])];
                     if (l[k] > mx)
                         mx = l[k];
                 }
@@ -800,7 +843,7 @@ __device__ inline void backup_game(const EngineParams &P, int g, azh_game_state 
 
     if (kind == AZH_LEAF_EVAL || kind == AZH_LEAF_ROOT)
         apply_priors(P, A, s.leaf_node, P.logits + (size_t)g * AZH_POLICY_SIZE, kind == AZH_LEAF_ROOT && (pk & PLY_FULL) != 0u,
-                     s.uid, (u32)s.ply);
+                     s.uid, (u32)s.ply, eval_symmetry_at(P, A, g, s.leaf_node));
 
     if ((P.flags & AZH_FLAG_EVAL_CACHE) && kind == AZH_LEAF_EVAL) {
         // the leaf now carries an evaluation: remember its value and enter it in the table
@@ -1672,8 +1715,9 @@ struct RunLoop {
     azh_net *net_a, *net_b;
     int dtype, iterations;
     bool pair = false, side = false;
-    bool own = false;  // forced playouts: the queued moves in a k_advance_list launch of their own, on the engine's stream, in
-                       // front of the tower (the tower kernels' advance_game records no pruned counts: engine_device.h)
+    bool own = false;  // forced playouts, random symmetry: the queued moves in a k_advance_list launch of their own, on the engine's
+                       // stream, in front of the tower (the tower kernels' advance_game records no pruned counts and writes no
+                       // key word: engine_device.h)
     AdvanceHook hook;
 
     // side-stream mode: ev_sel is signalled by the tree launch itself, ev_adv by the re-root launch (hipExtLaunchKernelGGL's
@@ -1694,7 +1738,7 @@ struct RunLoop {
         pair = pair_env && two_lists(e) && !(e->P.flags & AZH_FLAG_SYMMETRY_AVG);
         const char *side_s = getenv("AZH_REROOT_SIDE_STREAM");
         side = side_s && atoi(side_s) != 0;
-        own = !side && e->P.forced_k != 0.0f;
+        own = !side && (e->P.forced_k != 0.0f || e->P.random_symmetry != 0u);
         hook.workers = e->adv_workers;
         hook.at_head = 1;   // (decided per launch by the tower's launch functions: in front only where workgroups queue for slots)
         hook.P = e->P;
@@ -2069,6 +2113,69 @@ extern "C" int azh_forced_prune(const float *prior, const float *W, const uint32
         return azh_fail(-2, "azh_forced_prune: need a finite k >= 0");
     forced_prune_root(prior, W, n, M, k, c_puct, out);
     return 0;
+}
+
+// Is `bb` its own image under all 8 symmetries?  (the two mirrors and the transposition generate them)
+static bool symmetry_invariant(u64 bb)
+{
+    return symmetry_board(1, bb) == bb && symmetry_board(2, bb) == bb && symmetry_board(4, bb) == bb;
+}
+
+// Random symmetry per evaluation: every position goes to the evaluator as its image under a symmetry that is a pure function
+// of (seed, uid, position), and its logits are gathered through the same symmetry's move map.  Definition: the header and
+// DESIGN.md.  Between iterations only.
+extern "C" int azh_engine_set_random_symmetry(azh_engine *e, int on)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_set_random_symmetry: null engine");
+    if (e->selected)
+        return azh_fail(-3, "azh_engine_set_random_symmetry: a selected batch awaits its backup");
+    if (on && (e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_SYMMETRY_AVG)))
+        return azh_fail(-4, "azh_engine_set_random_symmetry: not supported with %s",
+                        (e->P.flags & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS" : "AZH_FLAG_SYMMETRY_AVG");
+    if (on && !symmetry_invariant(e->P.blockers & BOARD_MASK))
+        return azh_fail(-4, "azh_engine_set_random_symmetry: not supported with a blockers mask (0x%llx) that is not its own "
+                            "image under all 8 symmetries (the tower takes one blocker plane per launch)",
+                        (unsigned long long)e->P.blockers);
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_HIP(hipStreamSynchronize(e->stream2));
+    if (!on) {
+        e->P.random_symmetry = 0u;
+        return 0;
+    }
+    if (!e->P.eval_key && dev_alloc(e, &e->P.eval_key, (size_t)e->P.G))
+        return -1;
+    e->P.random_symmetry = 1u;
+    hipLaunchKernelGGL(k_eval_keys, dim3((e->P.G + 255) / 256), dim3(256), 0, e->stream, e->P);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// The symmetry (0..7) under which the position (mover, opponent) of game `uid` is evaluated by an engine created with `seed`.
+// Host arithmetic only: the functions the kernels call.
+extern "C" int azh_eval_symmetry(uint64_t seed, uint32_t uid, uint64_t mover, uint64_t opponent)
+{
+    return eval_symmetry_of(eval_symmetry_key((u32)seed, (u32)(seed >> 32), uid), mover, opponent);
+}
+
+// T_s on a bitboard (bits beyond the 49 cells are dropped; s is taken modulo 8).  Host arithmetic only.
+extern "C" uint64_t azh_symmetry_board(int s, uint64_t bitboard) { return symmetry_board(s & 7, bitboard); }
+
+// T_s on a flat policy index (all 833: the permutation that brings an image's logits back).  Host arithmetic only.
+extern "C" int azh_symmetry_policy_index(int s, int index)
+{
+    if (s < 0 || s > 7 || index < 0 || index >= AZH_POLICY_SIZE)
+        return azh_fail(-1, "azh_symmetry_policy_index: need 0 <= s <= 7 and 0 <= index < %d", AZH_POLICY_SIZE);
+    return symmetry_policy_index(s, index);
+}
+
+// T_s on a move (u16 from | to << 8; a value that is no board move, a pass, comes back as it is).  Host arithmetic only.
+extern "C" int azh_symmetry_move(int s, uint16_t move)
+{
+    if (s < 0 || s > 7)
+        return azh_fail(-1, "azh_symmetry_move: need 0 <= s <= 7");
+    return (int)symmetry_move(s, (u32)move);
 }
 
 // At most `games` games are played: uids 0 .. games - 1 (slot g plays uids g, g + G, ...).  A slot whose next game

@@ -76,6 +76,10 @@ struct EngineParams {
                            // or the FAST ply's threshold — the tree kernels read one word instead of running Philox per mark
     // forced playouts and policy target pruning (azh_engine_set_forced_playouts), off while forced_k == 0
     float forced_k;        // a root edge with n >= 1 visits is owed sqrt(forced_k * P * N) of them, on the plies that get root noise
+    // random symmetry per evaluation (azh_engine_set_random_symmetry; DESIGN.md "Random symmetry per evaluation"), off while 0
+    u32 random_symmetry;   // the evaluator sees T_s of every leaf board and apply_priors gathers through T_s of every move
+    u32 *eval_key;         // [G] the key word of each slot's game (eval_symmetry_key), written where a game begins (begin_game_key):
+                           // s = eval_symmetry_of(key, the position) — no Philox block on the tree kernels' per-iteration path
 };
 
 constexpr u32 PLY_FULL = 0x80000000u;
@@ -86,6 +90,15 @@ __device__ inline void begin_ply(const EngineParams &P, int g, u32 uid, int ply)
     if (P.fast_visits != 0 && lane_id() == 0) {
         asm volatile("" : "+v"(uid));  // the Philox block in vector registers: its callers have no scalar registers to spare
         P.ply_kind[g] = playout_cap_full(P.k0, P.k1, uid, (u32)ply, P.full_per_65536) ? PLY_FULL : (u32)P.fast_visits;
+    }
+}
+
+// A game of slot g begins (start, restart, a loaded position, the game limit's late starts: init_game_at): its key word.
+__device__ inline void begin_game_key(const EngineParams &P, int g, u32 uid)
+{
+    if (P.random_symmetry != 0u && lane_id() == 0) {
+        asm volatile("" : "+v"(uid));  // (as begin_ply: the block in vector registers)
+        P.eval_key[g] = eval_symmetry_key(P.k0, P.k1, uid);
     }
 }
 
@@ -212,7 +225,9 @@ __device__ inline void tt_clear(u32 *tt, int size)
 }
 
 // Fresh tree at the start position in arena 0 (generate_game :510-512,
-// MCTS::init_from_scratch :380-383).  Wave-cooperative; s_moves is LDS scratch.
+// MCTS::init_from_scratch :380-383).  Wave-cooperative; s_moves is LDS scratch.  KEY: the instantiation that writes the game's
+// key word of the random symmetry (begin_game_key) — every caller's but the tower kernels' advance_game, see there.
+template <bool KEY = true>
 __device__ inline void init_game_at(const EngineParams &P, int g, u32 uid, azh_game_state &s, u16 *s_moves, Board b, int ply,
                                     int loaded)
 {
@@ -234,6 +249,8 @@ __device__ inline void init_game_at(const EngineParams &P, int g, u32 uid, azh_g
     if (P.flags & AZH_FLAG_EVAL_CACHE)
         tt_clear(tt_of(P, 0, g), P.tt_size);
     begin_ply(P, g, uid, ply);
+    if constexpr (KEY)
+        begin_game_key(P, g, uid);
     wave_sync();
     s.phase = 0;
     s.arena = 0;
@@ -248,6 +265,7 @@ __device__ inline void init_game_at(const EngineParams &P, int g, u32 uid, azh_g
 }
 
 // Fresh game at the configured start position — or, past the game limit, no game: the slot goes idle.
+template <bool KEY = true>
 __device__ inline void init_game(const EngineParams &P, int g, u32 uid, azh_game_state &s, u16 *s_moves)
 {
     if (P.uid_limit != 0u && uid >= P.uid_limit) {
@@ -264,7 +282,7 @@ __device__ inline void init_game(const EngineParams &P, int g, u32 uid, azh_game
     b.x = P.start_x;
     b.o = P.start_o;
     b.turn = P.start_turn;
-    init_game_at(P, g, uid, s, s_moves, b, 0, 0);
+    init_game_at<KEY>(P, g, uid, s, s_moves, b, 0, 0);
 }
 
 constexpr u32 PRIOR_MASK = 0x7FFFFFFFu;  // the prior proper (AZH_HINT_SIGN: bit 31 marks the remembered child)
@@ -472,6 +490,10 @@ __device__ inline int record_pruned_counts(const EngineParams &P, const Arena &A
 // PRUNE: the instantiation that can record pruned counts (forced playouts) — k_advance_list's.  The tower kernels carry the
 // other one: they have no register to spare for the pruning (a 16-bit tower went to scratch memory with it), so while forced
 // playouts are on the device loop plays the queued moves in a k_advance_list launch of its own in front of the tower.
+// The same goes for the key word of the random symmetry, one Philox block where a game begins: inlined in the tower kernels
+// it sent k_tower2<1, false> and <2, false> to scratch memory (12 bytes per lane, 2 VGPR spills;
+// profiles/random_symmetry.txt), so their instantiation starts games without it and that mode, too, plays its moves in
+// k_advance_list.
 template <bool PRUNE>
 __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
 {
@@ -646,7 +668,7 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
     if (no_sample) {
         st_dropped = 1;
         drop_marker();
-        init_game(P, g, s.uid + (u32)P.G, s, s_moves);
+        init_game<PRUNE>(P, g, s.uid + (u32)P.G, s, s_moves);
     } else if (result != 0 || (cut && (P.flags & AZH_FLAG_KEEP_UNFINISHED))) {
         // finished: emit the packed record (generate_game :577-578, Worker :637-642)
         const u32 *recg = P.rec + (size_t)g * P.max_plies * REC_STRIDE_WORDS;
@@ -686,11 +708,11 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
             st_ring = 1;
         }
         st_dropped = cut ? 1 : 0;  // arena: "invalid" -> annulled (uai_ringmaster.py:147-150)
-        init_game(P, g, s.uid + (u32)P.G, s, s_moves);
+        init_game<PRUNE>(P, g, s.uid + (u32)P.G, s, s_moves);
     } else if (cut) {
         st_dropped = 1;  // null-result games are skipped (:628-631)
         drop_marker();
-        init_game(P, g, s.uid + (u32)P.G, s, s_moves);
+        init_game<PRUNE>(P, g, s.uid + (u32)P.G, s, s_moves);
     } else {
         s.phase = 0;
         begin_ply(P, g, s.uid, s.ply);

@@ -207,6 +207,13 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
     s.leaf_node = 0;
     s.path_len = paths;
     const bool need = r_kind == AZH_LEAF_EVAL || r_kind == AZH_LEAF_ROOT;
+    if (P.random_symmetry != 0u && lane < K && need) {
+        // the evaluator sees the image of every slot's position; lane p owns slot p, so each lane transforms its own two
+        // words in registers (symmetry_board: a loop over the stones; no LDS — the workgroup's other waves are at work)
+        const int sy = eval_symmetry_of(P.eval_key[g], r_mover, r_opp);
+        r_mover = symmetry_board(sy, r_mover);
+        r_opp = symmetry_board(sy, r_opp);
+    }
     if (lane < K) {
         V.kind[base + lane] = r_kind;
         V.leaf_edge[base + lane] = r_edge;
@@ -242,14 +249,17 @@ __device__ inline void vl_backup_priors(const EngineParams &P, const VlParams &V
     Arena A = arena_of(P, s.arena, g);
     if (s.leaf_kind == AZH_LEAF_ROOT) {
         if (w == 0)
-            apply_priors(P, A, 0, P.logits + base * AZH_POLICY_SIZE, (pk & PLY_FULL) != 0u, s.uid, (u32)s.ply);
+            apply_priors(P, A, 0, P.logits + base * AZH_POLICY_SIZE, (pk & PLY_FULL) != 0u, s.uid, (u32)s.ply,
+                         eval_symmetry_at(P, A, g, 0));
         return;
     }
     if (s.leaf_kind != AZH_LEAF_EVAL)
         return;
     for (int p = w; p < s.path_len; p += VL_WAVES)
-        if (V.kind[base + p] == AZH_LEAF_EVAL)
-            apply_priors(P, A, V.leaf_node[base + p], P.logits + (base + p) * AZH_POLICY_SIZE, false, 0u, 0u);
+        if (V.kind[base + p] == AZH_LEAF_EVAL) {
+            const int node = V.leaf_node[base + p];
+            apply_priors(P, A, node, P.logits + (base + p) * AZH_POLICY_SIZE, false, 0u, 0u, eval_symmetry_at(P, A, g, node));
+        }
 }
 
 // The proof pass (azh_engine_set_solver; DESIGN.md "Proven wins and losses"; tests/solver_reference.py restates it), run by

@@ -135,6 +135,11 @@ SIGNATURES = {
     "azh_playout_cap_kind": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     "azh_engine_set_forced_playouts": (ctypes.c_int, [_vp, _f32]),
     "azh_forced_prune": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _f32, _f32, _vp]),
+    "azh_engine_set_random_symmetry": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "azh_eval_symmetry": (ctypes.c_int, [_u64, ctypes.c_uint32, _u64, _u64]),
+    "azh_symmetry_board": (_u64, [ctypes.c_int, _u64]),
+    "azh_symmetry_move": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint16]),
+    "azh_symmetry_policy_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "azh_engine_set_solver": (ctypes.c_int, [_vp, ctypes.c_int]),
     "azh_engine_proof_stats": (ctypes.c_int, [_vp, _vp]),
     "azh_engine_root_proofs": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
@@ -264,6 +269,34 @@ def forced_prune(prior, W, n, k, c_puct):
     out = np.zeros(len(n), dtype=np.uint32)
     check(load().azh_forced_prune(_ptr(prior), _ptr(W), _ptr(n), len(n), float(k), float(c_puct), _ptr(out)))
     return out
+
+
+def eval_symmetry(seed, uid, mover, opponent):
+    """Random symmetry per evaluation (Engine.set_random_symmetry): the symmetry 0..7 under which the position (mover,
+    opponent) of game `uid` of an engine with `seed` is evaluated (azh_eval_symmetry; host arithmetic, no GPU needed)."""
+    return int(load().azh_eval_symmetry(int(seed), int(uid), int(mover), int(opponent)))
+
+
+def symmetry_board(s, bitboard):
+    """T_s on a bitboard: bit 0 of s mirrors x, bit 1 mirrors y, bit 2 then transposes (azh_symmetry_board; host arithmetic)."""
+    return int(load().azh_symmetry_board(int(s), int(bitboard)))
+
+
+def symmetry_move(s, move):
+    """T_s on a move (u16 from | to << 8): both squares by the symmetry (azh_symmetry_move; host arithmetic)."""
+    rc = int(load().azh_symmetry_move(int(s), int(move)))
+    if rc < 0:
+        check(rc)
+    return rc
+
+
+def symmetry_policy_index(s, index):
+    """T_s on a flat policy index 119 x + 17 y + layer (all 833): logits of the position [i] = logits of the image
+    [symmetry_policy_index(s, i)] (azh_symmetry_policy_index; host arithmetic)."""
+    rc = int(load().azh_symmetry_policy_index(int(s), int(index)))
+    if rc < 0:
+        check(rc)
+    return rc
 
 
 def full_per_65536(full_fraction):
@@ -472,6 +505,12 @@ class Engine:
         the Dirichlet mix: a root edge with n >= 1 visits is owed sqrt(k P N) of them, and the counts that go into the game's
         `dists` leave out the forced visits PUCT would not have spent.  k = 0: off (the default); KataGo uses 2."""
         check(load().azh_engine_set_forced_playouts(self.h, float(k)))
+
+    def set_random_symmetry(self, on=True):
+        """Random symmetry per evaluation: every position goes to the evaluator as its image under a symmetry
+        drawn per (seed, uid, position) — link.eval_symmetry — and its logits come back through that symmetry's move map;
+        leaves() / batch_leaves() / leaf_features() return the image.  No tower work is added.  Between iterations only."""
+        check(load().azh_engine_set_random_symmetry(self.h, 1 if on else 0))
 
     def set_thin_batches(self, mode):
         """0: the 3-board tower; 1: one board per workgroup (a handful of leaves per iteration); -1: by the engine's size."""

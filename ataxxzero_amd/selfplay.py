@@ -83,10 +83,15 @@ class SelfPlay:
     `full_fraction` of the plies is searched with `visits` and root noise, the others with `fast_visits` and none.
 
     `forced_playouts` = k > 0 turns forced playouts and policy target pruning on in every half-batch engine
-    (link.Engine.set_forced_playouts), on the plies that get root noise."""
+    (link.Engine.set_forced_playouts), on the plies that get root noise.
+
+    `random_symmetry` turns the random symmetry per evaluation on in every half-batch engine
+    (link.Engine.set_random_symmetry): every leaf goes to the net as its image under a symmetry drawn per (seed, uid,
+    position); the start position's blockers must be their own image under all 8 symmetries."""
 
     def __init__(self, conv_weights, bn_params, games, visits, dtype="bf16", seed=DEFAULT_SEED,
-                 fen=START_FEN_SELFPLAY, streams=1, fast_visits=0, full_fraction=0.25, forced_playouts=0.0, **cfg):
+                 fen=START_FEN_SELFPLAY, streams=1, fast_visits=0, full_fraction=0.25, forced_playouts=0.0,
+                 random_symmetry=False, **cfg):
         self.dtype = link.DTYPES[dtype]
         self.net = link.Net(conv_weights, bn_params, model.BN_EPSILON)
         if streams < 1 or games < streams:
@@ -101,6 +106,8 @@ class SelfPlay:
             self.set_playout_cap(fast_visits, full_fraction)
         if forced_playouts:
             self.set_forced_playouts(forced_playouts)
+        if random_symmetry:
+            self.set_random_symmetry(True)
 
     def run(self, iterations):
         # every engine's whole run is enqueued on its own stream (the calls are asynchronous): the half-batches then
@@ -130,6 +137,11 @@ class SelfPlay:
         """Forced playouts and policy target pruning in every half-batch engine; k = 0 turns them off."""
         for e in self.engines:
             e.set_forced_playouts(k)
+
+    def set_random_symmetry(self, on=True):
+        """The random symmetry per evaluation in every half-batch engine."""
+        for e in self.engines:
+            e.set_random_symmetry(on)
 
     def set_thin_batches(self, mode):
         """1: the towers run one board per workgroup (a handful of leaves per iteration: the tail of a run under a game

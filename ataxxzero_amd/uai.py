@@ -153,7 +153,7 @@ class Searcher:
                              # tree per visit (96 edge slots of 18 bytes per node, two arenas): at most about 210 MB
 
     def __init__(self, network_path, dtype="f16", symmetry_average=False, parallel_leaves=1, virtual_loss=1,
-                 reuse_tree=False, show_pv=False, solver=False):
+                 reuse_tree=False, show_pv=False, solver=False, random_symmetry=False):
         # parallel_leaves = K > 1: leaf-parallel search with virtual loss ("Leaf-parallel search"): up to K
         # leaves per iteration in one tower launch.  An extension; 1 is the reference's one-leaf search.
         if not 1 <= parallel_leaves <= link.MAX_LEAVES_PER_GAME or not 1 <= virtual_loss <= link.MAX_VIRTUAL_LOSS:
@@ -163,7 +163,12 @@ class Searcher:
             raise ValueError("symmetry averaging is not available with parallel_leaves > 1")
         if solver and symmetry_average:
             raise ValueError("symmetry averaging is not available with the solver")
+        if random_symmetry and symmetry_average:
+            raise ValueError("a random symmetry per evaluation is not available with symmetry averaging")
         self.parallel_leaves, self.virtual_loss = parallel_leaves, virtual_loss
+        # random_symmetry: every position is evaluated under one of the 8 symmetries of the board, drawn per (engine seed,
+        # position) — link.Engine.set_random_symmetry; the net's orientation bias averages out over a search at no tower work
+        self.random_symmetry = random_symmetry
         # solver: proven wins and losses (azh_engine_set_solver).  last_proofs: (root value, [(move, value of the move's
         # child for the side to move there)] in edge order) after the last search, None without the solver;
         # last_proven: "win" / "loss" when genmove's move came from a proof, else None
@@ -209,6 +214,8 @@ class Searcher:
                               start_x=pos.x, start_o=pos.o, blockers=0,
                               flags=link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR | self.extra_flags)
             self.engine = link.Engine(cfg)
+            if self.random_symmetry:
+                self.engine.set_random_symmetry(True)
             if self.parallel_leaves > 1:
                 self.engine.set_leaf_batch(self.parallel_leaves, self.virtual_loss)
             if self.solver:
@@ -301,6 +308,8 @@ class Searcher:
         eng = link.Engine(cfg)
         start = time.time()
         try:
+            if self.random_symmetry:
+                eng.set_random_symmetry(True)
             if visits is not None:
                 eng.run(self.net, 1 + visits, self.dtype)  # root evaluation + `visits` steps
                 steps = visits
@@ -335,6 +344,8 @@ class Searcher:
             eng.set_leaf_batch(K, self.virtual_loss)
             if self.solver:
                 eng.set_solver(True)
+            if self.random_symmetry:
+                eng.set_random_symmetry(True)
             eng.run(self.net, 1, self.dtype)  # the root evaluation
             rv = 0
             while rv < target and (seconds is None or time.time() - start < seconds):

@@ -307,6 +307,49 @@ int azh_engine_set_forced_playouts(azh_engine *e, float k);
  * device: the same per-edge function the device's ply record uses. */
 int azh_forced_prune(const float *prior, const float *W, const uint32_t *n, int M, float k, float c_puct, uint32_t *out);
 
+/* Random symmetry per evaluation (an extension, off by default; AlphaGo Zero / AlphaZero evaluate every leaf under a random
+ * dihedral symmetry, and so does the reference's symmetry variant of its Python engine).  While it is on, every position
+ * that goes to the evaluator — new leaves and the root's evaluation at the start of a ply — goes as its image T_s(mover),
+ * T_s(opponent) under one symmetry s of the board, and the prior of every edge is gathered from the logit of T_s(move); the
+ * value is used as it comes (under AZH_FLAG_PY_POSTERIOR the 833-way softmax sums the image's logits in the position's index
+ * order, azh_symmetry_policy_index: the same f32 sum as over logits brought back).  No tower work is added (AZH_FLAG_SYMMETRY_AVG costs 8x).
+ * Symmetry s in 0..7 as train.py:11-23: bit 0 mirrors x, bit 1 mirrors y, bit 2 then transposes, on the cells (x, y) =
+ * (sq % 7, 6 - sq / 7) of the policy index: image_s(x, y) = x <- 6 - x if bit 0, y <- 6 - y if bit 1, then x <-> y if bit 2.
+ * T_s(bitboard) has a stone at image_s(c) for every stone at c; T_s(move) maps from and to by image_s (a clone stays a clone,
+ * a jump's layer follows from the transformed squares).
+ * WHICH s is a pure function of the engine's seed, the game's uid and the position: key = philox(seed; uid, 0, 5, 0).v[0]
+ * (stream 5 is drawn from by nothing else, so no other random number moves) and, over the UNTRANSFORMED leaf board, u32
+ * arithmetic:  a = key;  for w in (lo32(mover), hi32(mover), lo32(opponent), hi32(opponent)): a = (a ^ w) * 0x9E3779B1,
+ * a ^= a >> 15;  then a = a * 0x85EBCA77, a ^= a >> 13, s = a >> 29.  azh_eval_symmetry restates it on the host.  It does not
+ * depend on iteration order, a parked descent or the evaluation cache: a position of a game is always seen the same way, so
+ * the root's re-evaluation uses the symmetry of the node's first evaluation, and with AZH_FLAG_EVAL_CACHE a transposition
+ * takes priors that were gathered under its own s — cache on still builds the trees of cache off.  (The reference's variant
+ * draws a fresh symmetry per evaluation.)
+ * azh_engine_leaves, _batch_leaves and _leaf_features return the image; azh_engine_set_evals and _set_batch_evals take the
+ * logits of the image: an outside evaluator needs no change.  Node boards, records, game lines, the cache's keys, sampling,
+ * the Dirichlet mix, re-roots and azh_engine_root_report are untouched, and with the mode off every engine behaves byte for
+ * byte as before.  Composes with select_budget, the evaluation cache, the playout cap, forced playouts, ONE_RANDOM_MOVE, the
+ * leaf-parallel search, the solver, thin batches, half-batches, azh_engine_play_moves and azh_engine_set_positions.
+ * Refused (the engine stays as it was) with AZH_FLAG_TWO_NETS, with AZH_FLAG_SYMMETRY_AVG, and when the engine's blockers
+ * mask is not its own image under all 8 symmetries (the tower takes the blocker plane once per launch; no blockers, the four
+ * corners and the self-play start's diamond are).  Call before the first select or between iterations; off (0) is the state
+ * after create.  Definition and measurements: DESIGN.md, "Random symmetry per evaluation". */
+int azh_engine_set_random_symmetry(azh_engine *e, int on);
+/* The symmetry, 0..7, under which an engine created with `seed` and the mode on evaluates the position (mover, opponent) of
+ * game `uid`.  Host arithmetic only, usable without a device: the same function the kernels call. */
+int azh_eval_symmetry(uint64_t seed, uint32_t uid, uint64_t mover, uint64_t opponent);
+/* T_s on a bitboard (s is taken modulo 8, bits beyond the 49 cells are dropped) and on a move (u16 from | to << 8; a value that
+ * is no board move, such as the pass 0xFFFF, comes back as it is; a negative code for s outside 0..7).  Host arithmetic only:
+ * the same functions as the device's. */
+uint64_t azh_symmetry_board(int s, uint64_t bitboard);
+int azh_symmetry_move(int s, uint16_t move);
+/* T_s on a flat policy index 119 x + 17 y + layer, for all 833 of them (the destination cell by image_s, a jump layer by the
+ * image of its (dx, dy), the clone layer as it is): for a move m it is the index of T_s(m), and as a whole it is the
+ * permutation that turns the logits of the image into logits of the position, position[i] = image[azh_symmetry_policy_index(s,
+ * i)] — what a host needs to compare a mode-on engine with a mode-off one.  A negative code for s outside 0..7 or an index
+ * outside 0..832.  Host arithmetic only. */
+int azh_symmetry_policy_index(int s, int index);
+
 /* Proven wins and losses in the tree (MCTS-solver; an extension, off by default; DESIGN.md, "Proven wins and losses").
  * A node is DECIDED if it is a finished position or was PROVEN: after every batch's backup, for each path that ended at a
  * decided node, the node's parent is a proven win (+1 for its side to move) if one of its children is decided with -1, and

@@ -14,6 +14,11 @@ record, over the plies the mode acts on:
 
     python tools/playout_cap_rate.py --forced-playouts 2 [--cap] --out profiles/forced_playouts.txt
 
+With --random-symmetry the two legs are the random symmetry per evaluation off against on (the cap and forced playouts as
+given, the same in both legs):
+
+    python tools/playout_cap_rate.py --random-symmetry --out profiles/random_symmetry.txt
+
 Appends its report to --out.  GPU box, repo root."""
 import argparse
 import os
@@ -69,11 +74,11 @@ def full_share(words):
     return full, plies
 
 
-def leg(conv, bn, args, cap, seed, forced=0.0):
+def leg(conv, bn, args, cap, seed, forced=0.0, symmetry=False):
     sp = selfplay.SelfPlay(conv, bn, games=args.games, visits=args.visits, dtype=args.dtype, seed=seed, streams=2,
                            flags=link.FLAG_EVAL_CACHE, select_budget=48,
                            fast_visits=args.fast_visits if cap else 0, full_fraction=args.full_search_fraction,
-                           forced_playouts=forced)
+                           forced_playouts=forced, random_symmetry=symmetry)
     snap = np.load(SNAPSHOT)
     rng = np.random.default_rng(seed)
     pick = rng.permutation(len(snap["plies"])) if args.games == len(snap["plies"]) else rng.integers(0, len(snap["plies"]), size=args.games)
@@ -107,7 +112,7 @@ def leg(conv, bn, args, cap, seed, forced=0.0):
     bare_ms = sp.net.bench(max(1, int(round(batch))), 20, link.DTYPES[args.dtype])
     sp.close()
     share = 1.0 if not cap else (full / plies if plies else float("nan"))   # (cap off: every ply is searched in full)
-    return {"forced": forced, "pruned_share": pruned / acting if acting else float("nan"), "cap": cap, "plies_s": st["plies"] / dt, "games_s": st["games"] / dt,
+    return {"symmetry": symmetry, "forced": forced, "pruned_share": pruned / acting if acting else float("nan"), "cap": cap, "plies_s": st["plies"] / dt, "games_s": st["games"] / dt,
             "full_share": share, "full_plies_s": st["plies"] / dt * share, "evals_s": st["nn_evals"] / dt,
             "plies_per_iter": st["plies"] / (2.0 * iters), "batch": batch, "tower_us": 1e3 * tower_ms,
             "bare_us": 1e3 * bare_ms, "iter_s": iters / dt}
@@ -116,6 +121,7 @@ def leg(conv, bn, args, cap, seed, forced=0.0):
 def row(r):
     return ("%-4s plies/s %8.1f  games/s %6.2f  full plies/s %8.1f (share %.3f)  evals/s %9.0f  iterations/s %7.1f  "
             "moves due per launch %5.1f  leaves per launch %6.0f  tower launch %6.1f us, bare tower at that batch %6.1f us (excess %5.1f us)" % (
+                ("sym" if r["symmetry"] else "none") if r.get("by_symmetry") else
                 ("k=%g" % r["forced"] if r["forced"] else "k=0") if r["by_forced"] else "on" if r["cap"] else "off", r["plies_s"], r["games_s"], r["full_plies_s"], r["full_share"],
                 r["evals_s"], r["iter_s"], r["plies_per_iter"], r["batch"], r["tower_us"], r["bare_us"], r["tower_us"] - r["bare_us"]))
 
@@ -134,6 +140,9 @@ def main():
     ap.add_argument("--forced-playouts", type=float, default=0.0, metavar="K",
                     help="the legs are forced playouts off against on (k = K) instead of the cap off against on")
     ap.add_argument("--cap", action="store_true", help="with --forced-playouts: the playout cap on in both legs")
+    ap.add_argument("--random-symmetry", action="store_true",
+                    help="the legs are the random symmetry per evaluation off against on (cap with --cap, forced playouts with "
+                         "--forced-playouts K, the same in both legs)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "playout_cap.txt"))
     args = ap.parse_args()
     selfplay.select_device(0)
@@ -143,16 +152,22 @@ def main():
              % (link.pci_bus_id(0), args.games, args.blocks, args.dtype, args.visits, args.fast_visits,
                 args.full_search_fraction, args.steps, args.fill)]
     rows = []
-    by_forced = args.forced_playouts > 0
+    by_symmetry = args.random_symmetry
+    by_forced = args.forced_playouts > 0 and not by_symmetry
+    if by_symmetry:
+        lines[0] += "; legs: random symmetry per evaluation off against on, the cap %s and forced playouts k = %g in both" % (
+            "on" if args.cap else "off", args.forced_playouts)
     if by_forced:
         lines[0] += "; legs: forced playouts off against k = %g, the cap %s in both" % (args.forced_playouts, "on" if args.cap else "off")
     for pair in range(args.pairs):
         for second in (False, True):
-            if by_forced:
+            if by_symmetry:
+                r = leg(conv, bn, args, args.cap, seed=1000 + pair, forced=args.forced_playouts, symmetry=second)
+            elif by_forced:
                 r = leg(conv, bn, args, args.cap, seed=1000 + pair, forced=args.forced_playouts if second else 0.0)
             else:
                 r = leg(conv, bn, args, second, seed=1000 + pair)
-            r["by_forced"], r["second"] = by_forced, second
+            r["by_forced"], r["by_symmetry"], r["second"] = by_forced, by_symmetry, second
             rows.append(r)
             lines.append(row(r) + ("  visits pruned per acting ply %.4f" % r["pruned_share"] if r["forced"] else ""))
             print(lines[-1], flush=True)
@@ -166,7 +181,13 @@ def main():
         lines.append("mean share of a ply's visits pruned from its record, over the plies the mode acts on: %.4f"
                      % statistics.mean(r["pruned_share"] for r in rows if r["second"]))
     bound = args.visits / (args.full_search_fraction * args.visits + (1 - args.full_search_fraction) * args.fast_visits)
-    if not by_forced:
+    for key, name in (("iter_s", "iterations/s"), ("evals_s", "evaluations/s")) if by_symmetry else ():
+        off = [r[key] for r in rows if not r["second"]]
+        on = [r[key] for r in rows if r["second"]]
+        lines.append("mean %-17s off %9.2f  on %9.2f  ratio %.3f  (off legs' own spread: %.2f .. %.2f)" % (
+            name, statistics.mean(off), statistics.mean(on), statistics.mean(on) / statistics.mean(off), min(off), max(off)))
+        print(lines[-1])
+    if not by_forced and not by_symmetry:
         lines.append("(visits / mean threshold = %.2fx: arithmetic, not a measurement, and no bound — a re-rooted root inherits visits, "
                      "and one that already meets the fast threshold plays after its root evaluation alone)" % bound)
     with open(args.out, "a") as f:

@@ -22,7 +22,8 @@ def main(options):
     selfplay.select_device(0)
     searcher = uai.Searcher(options.network_path, dtype=options.dtype, symmetry_average=options.symmetry_average,
                             parallel_leaves=options.parallel_leaves, virtual_loss=options.virtual_loss,
-                            reuse_tree=options.reuse_tree, show_pv=options.show_pv, solver=options.solver)
+                            reuse_tree=options.reuse_tree, show_pv=options.show_pv, solver=options.solver,
+                            random_symmetry=options.random_symmetry)
     session = uai.Session(searcher, visits=options.visits, safety_ms=options.safety_ms, show_game=options.show_game,
                           log=sys.stderr)
     session.serve(sys.stdin, sys.stdout)
@@ -35,6 +36,9 @@ if __name__ == "__main__":
     cli.add_argument("--safety-ms", type=int, default=0, metavar="MS", help="margin subtracted from every movetime")
     cli.add_argument("--show-game", action="store_true", help="echo positions set by `position fen` to stderr")
     cli.add_argument("--symmetry-average", action="store_true", help="evaluate every position as the mean over its 8 dihedral images (nn_evals.py:48-62; extension)")
+    cli.add_argument("--random-symmetry", action="store_true",
+                     help="evaluate every position under one of the 8 symmetries of the board, drawn per position (extension; "
+                          "AlphaZero's leaf evaluation): no extra tower work.  Not with --symmetry-average")
     cli.add_argument("--parallel-leaves", type=int, default=1, metavar="K",
                      help="leaves per search iteration, 1..64, spread by a virtual loss and evaluated in one tower launch "
                           "(extension; 1 = the reference's one-leaf search)")
@@ -52,5 +56,7 @@ if __name__ == "__main__":
                      help="tower arithmetic (extension).  Match play defaults to f16: with a trained net the f16 search picks "
                           "the f32 search's move in 100 %% of test positions, bf16 in 96 %% (DESIGN.md section 5); bf16 is 3-6 %% faster")
     options = cli.parse_args()
+    if options.random_symmetry and options.symmetry_average:
+        cli.error("--random-symmetry and --symmetry-average exclude each other")
     print(options, file=sys.stderr)
     main(options)
