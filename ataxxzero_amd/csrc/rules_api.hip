@@ -322,6 +322,9 @@ extern "C" int azh_rules_batch(int n, const uint64_t *boards, uint64_t blockers,
     if (db.alloc((size_t)n * 16) || dm.alloc((size_t)n * MAX_MOVES * 2) || dc.alloc((size_t)n * 4) || dr.alloc((size_t)n * 4))
         return -4;
     AZH_HIP(hipMemcpy(db.p, boards, (size_t)n * 16, hipMemcpyHostToDevice));
+    // the kernel writes a row's first `count` entries only and whole rows go back to the caller: the rest is zero, not
+    // whatever the allocation held
+    AZH_HIP(hipMemset(dm.p, 0, (size_t)n * MAX_MOVES * 2));
     hipLaunchKernelGGL(k_rules_batch, dim3(n), dim3(WAVE), 0, 0, db.as<ulonglong2>(), n, blockers, dm.as<u16>(),
                        dc.as<int>(), dr.as<int>());
     AZH_HIP(hipGetLastError());

@@ -57,8 +57,8 @@ int azh_device_pci_bus_id(int device, char *buf, int cap);
 int azh_perft(uint64_t x, uint64_t o, uint64_t blockers, int turn, int depth, uint64_t *nodes_out);
 
 /* For n packed boards: legal moves in the reference's movegen order
- * (moves_out [n][AZH_MAX_MOVES]), their count, and the adjudication
- * 0 / 1 / 2.  Any output pointer may be NULL. */
+ * (moves_out [n][AZH_MAX_MOVES], zero past a row's count), their count, and
+ * the adjudication 0 / 1 / 2.  Any output pointer may be NULL. */
 int azh_rules_batch(int n, const uint64_t *boards, uint64_t blockers, uint16_t *moves_out,
                     int32_t *counts_out, int32_t *results_out);
 
