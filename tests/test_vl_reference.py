@@ -97,3 +97,33 @@ def test_last_batch_is_truncated_at_the_visit_budget():
     assert len(b.kind) == 3
     b = vlr.select(tree, 12, 12, 64, 2, 1.0, True, 0)
     assert len(b.kind) == 1  # at least one path, as the one-leaf search
+
+
+def test_a_full_arena_drops_the_path_ends_the_batch_and_forces_the_move():
+    # the start position's first three moves; every child has 16 replies: the edge arena holds the root's 3 and one child's 16
+    tree = _toy_tree([0.5, 0.3, 0.2], [0, 0, 0], [0.0, 0.0, 0.0])
+    free = vlr.select(tree, 0, 100, 4, 2, 1.0, True, 0)
+    assert len(free.kind) == 4 and not free.over and free.kind[:3] == [vlr.LEAF_EVAL] * 3
+    b = vlr.select(tree, 0, 100, 4, 2, 1.0, True, 0, node_cap=10, edge_cap=3 + 16 + 15)
+    assert b.over and b.kind == [vlr.LEAF_EVAL, vlr.LEAF_NONE]          # the batch ends with the dropped path
+    assert b.leaf_edge == [0, 1] and b.paths[1] == [1] and b.leaf_board[1] == (0, 0)
+    assert b.leaf_node[1] == 0 and len(b.boards) == 2 and len(b.n) == 19 and b.child[1] == vlr.NONE   # nothing was added
+    edges, added = vlr.backup(b, [0.25, 0.0])
+    assert added == 1 and list(edges[:3, 1]) == [1, 0, 0] and edges[1, 2] == 0    # no visit, no score, no virtual loss left
+    assert vlr.move_is_due(b, added, 100) and not vlr.move_is_due(free, 3, 100) and vlr.move_is_due(free, 100, 100)
+    # the node arena: no room for any node -> the first path is dropped; a finished child needs a node, too
+    b = vlr.select(tree, 0, 100, 4, 2, 1.0, True, 0, node_cap=1, edge_cap=1000)
+    assert b.over and b.kind == [vlr.LEAF_NONE] and b.leaf_edge == [0]
+    # with room for everything the caps change nothing
+    b = vlr.select(tree, 0, 100, 4, 2, 1.0, True, 0, node_cap=10, edge_cap=1000)
+    assert b.kind == free.kind and b.paths == free.paths and not b.over
+
+
+def test_the_forced_move_is_the_draw_proportional_to_the_root_visits():
+    tree = _toy_tree([0.5, 0.3, 0.2], [0, 0, 0], [0.0, 0.0, 0.0])
+    assert vlr.forced_move(tree, 0, 7, 0, 0) == (0, int(tree[3][0]))     # a root without a visit: its first edge
+    tree = _toy_tree([0.5, 0.3, 0.2], [0, 5, 0], [0.0, 0.0, 0.0])
+    assert all(vlr.forced_move(tree, 5, 7, uid, ply)[0] == 1 for uid in range(4) for ply in range(4))
+    tree = _toy_tree([0.5, 0.3, 0.2], [1, 0, 3], [0.0, 0.0, 0.0])
+    picks = [vlr.forced_move(tree, 4, 7, uid, ply)[0] for uid in range(8) for ply in range(8)]
+    assert set(picks) == {0, 2} and picks.count(2) > picks.count(0)

@@ -4,8 +4,14 @@ It works on the arrays Engine.tree(g) returns — boards (n, 2) u64 packed (x | 
 (first edge, n_edges | result << 16, 0, terminal value bits), edges (m, 4) u32 (prior bits, visits, W bits, child or
 0xFFFFFFFF), moves (m,) u16 — and on the rules of the repository's oracle (oracle/oracle_lib.py) for the nodes a path
 expands.  select() gives each slot's kind, leaf edge and leaf board; backup() the edge words after the backup.  Priors of
-new nodes are not restated: they come from the posterior code, which other tests pin; backup() takes them from the
-engine's dump.
+new nodes are not restated here: backup() takes them from the engine's dump, and tests/priors_reference.py restates them.
+
+The arena-full rule (select with node_cap / edge_cap): a path that would expand a node the arenas cannot hold — the
+game has node_cap nodes already, or the unfinished child's M2 edges do not fit (n_edges + M2 > edge_cap) or are more than
+255 — is DROPPED: kind NONE, its leaf edge the edge it stood on, no node and no edge added, and it keeps its virtual loss
+until the backup like every other path of the batch.  The batch ends with it (no later path is selected), and the game's
+move is FORCED: after this batch's backup the move is due whatever the root's visit count, and the next select plays it
+— forced_move() below, the ordinary draw proportional to the root edges' visits.
 """
 import ctypes
 
@@ -77,9 +83,11 @@ class Batch:
     """One iteration's selected batch and the working tree it left (virtual losses kept apart)."""
 
 
-def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers):
+def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers, node_cap=None, edge_cap=None):
     """The batch of one game in search phase 1: k = max(1, min(K, visits - root_visits)) paths as if one after the other.
-    -> Batch with .kind, .leaf_edge (NONE: none), .leaf_board (mover, opponent; (0, 0) unless EVAL), .paths, .values_of."""
+    node_cap, edge_cap: the arenas' sizes (both None: unbounded) — the arena-full rule of the module's docstring.
+    -> Batch with .kind, .leaf_edge (NONE: none), .leaf_board (mover, opponent; (0, 0) unless EVAL), .paths, .leaf_node,
+    .over (a path was dropped: the batch ended there and the move is forced)."""
     boards, info, edges, moves = tree
     boards = [tuple(int(v) for v in b) for b in boards]
     info = [list(int(v) for v in r) for r in info]
@@ -93,6 +101,8 @@ def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers):
     k = max(1, min(K, visits - root_visits))
     b = Batch()
     b.kind, b.leaf_edge, b.leaf_board, b.paths, b.leaf_node = [], [], [], [], []
+    b.over = False
+    capped = node_cap is not None or edge_cap is not None
     for p in range(k):
         node, path = 0, []
         while True:
@@ -112,6 +122,11 @@ def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers):
                 node = child[e]
                 continue
             cb, res2, mvs, tv = expand_position(boards[node][0], boards[node][1], mv[e], blockers)
+            if capped and ((node_cap is not None and len(boards) >= node_cap) or
+                           (res2 == 0 and ((edge_cap is not None and len(n) + len(mvs) > edge_cap) or len(mvs) > 255))):
+                kind = LEAF_NONE   # dropped: the path stays at `node`, on the edge it stood on
+                b.over = True
+                break
             cid = len(boards)
             boards.append(cb)
             if res2 != 0:
@@ -132,6 +147,8 @@ def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers):
         b.leaf_node.append(node)
         b.leaf_board.append(leaf_board(*boards[node]) if kind == LEAF_EVAL else (0, 0))
         b.paths.append(path)
+        if b.over:
+            break
     b.edges0 = edges0
     b.boards, b.info, b.prior, b.n, b.W, b.child, b.moves = boards, info, prior, n, W, child, mv
     return b
@@ -160,6 +177,30 @@ def backup(b, values):
     out[:, 2] = W
     out[:, 3] = b.child
     return out, added
+
+
+def move_is_due(b, root_visits_after, visits):
+    """After the batch's backup: the game's move is due — the root has its visits, or the batch dropped a path."""
+    return root_visits_after >= visits or b.over
+
+
+def forced_move(tree, root_visits, seed, uid, ply):
+    """The move the select after a due move plays (flags without SAMPLE_POW5 / ONE_RANDOM_MOVE): the draw proportional to
+    the root edges' visits, r = (philox(seed; uid, ply, stream 1, 0)[0] * root_visits) >> 32 against the running sum of the
+    visits in edge order — the first edge whose running sum exceeds r; edge 0 if there is none (a root without a visit).
+    -> (edge index, move)."""
+    boards, info, edges, moves = tree
+    first, M = int(info[0][0]), int(info[0][1]) & 0xFFFF
+    out = (ctypes.c_uint32 * 4)()
+    orc.lib().orc_probe_philox(int(seed), int(uid), int(ply), 1, 0, out)
+    r = (int(out[0]) * int(root_visits)) >> 32
+    cum, chosen = 0, -1
+    for j in range(M):
+        cum += int(edges[first + j][1])
+        if chosen < 0 and cum > r:
+            chosen = j
+    chosen = max(chosen, 0)
+    return chosen, int(moves[first + chosen])
 
 
 def expected_tree(b, values, post_tree):
