@@ -146,41 +146,13 @@ __device__ inline int eval_symmetry_at(const EngineParams &P, const Arena &A, in
 // ------------------------------------------------------------------ select + expand
 
 // Q + U of one edge (total_action_score :310-324) — IEEE division and square root in the fixed order the oracle restates.
-// -DAZH_FAST_SCORE=1 is a MEASUREMENT build only (never shipped, not bit-exact with the oracle): the two divisions and the
-// square root become single approximate instructions (v_rcp_f32 / v_sqrt_f32), i.e. the level's dependent chain without
-// the ~25 instructions that precomputing q = W/n and r = cP/(1+n) at backup time would remove — an upper bound of what
-// that restructuring could buy (profiles/round5_puct_chain_ab.txt).
-#ifndef AZH_FAST_SCORE
-#define AZH_FAST_SCORE 0
-#endif
-#ifndef AZH_SQRT_EARLY
-#define AZH_SQRT_EARLY 1
-#endif
-// Where a node keeps "the child the last descent chose here" (select_game's early request): 1 = the SIGN BIT of that child's
-// prior (priors are >= 0, so the bit is free in every edge: found with one ballot, and present in nodes whose children have
-// all been visited — the tree's upper levels); 0 = the spare word of the node's first unvisited edge (rounds 3-4: two ballots,
-// a find-first-set and a lane read to find, and nothing to find in a fully visited node).
-#ifndef AZH_HINT_SIGN
-#define AZH_HINT_SIGN 1
-#endif
-__device__ inline float puct_sqrt(float x)
-{
-#if AZH_FAST_SCORE
-    return __builtin_amdgcn_sqrtf(x);
-#else
-    return sqrtf(x);
-#endif
-}
+// (Approximate division and square root, an upper bound of what precomputing q = W/n and r = cP/(1+n) at backup time could
+// buy, did not pay for giving up bit-exactness: profiles/round5_puct_chain_ab.txt.)
 __device__ inline float puct_score(float prior, float W, u32 n, float sq, float c_puct)
 {
     prior = __builtin_fabsf(prior);  // (the sign bit may carry the descent's mark: a source modifier, no instruction)
-#if AZH_FAST_SCORE
-    const float q = n ? W * __builtin_amdgcn_rcpf((float)n) : 0.0f;
-    const float u = (sq * __builtin_amdgcn_rcpf(1.0f + (float)n)) * (c_puct * prior);
-#else
     const float q = n ? W / (float)n : 0.0f;
     const float u = (sq / (1.0f + (float)n)) * (c_puct * prior);
-#endif
     return u + q;
 }
 
@@ -236,9 +208,9 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
         // sqrt(1 + N) of the node about to be scanned, computed as soon as N is known — at the END of the level above, while
         // the node's records are still on their way — instead of after their arrival: the IEEE square root (a dozen
         // instructions) leaves the chain between the arrival of a level's records and the request for the next level's.
-        // Same function of the same argument: nothing the oracle could see.  (AZH_SQRT_EARLY=0: where it used to be.)
+        // Same function of the same argument: nothing the oracle could see (profiles/round5_sqrt_early_ab.txt).
         auto sqrt_1p = [](u32 n) {
-            float r = puct_sqrt((float)(1u + n));
+            float r = sqrtf((float)(1u + n));
             asm volatile("" : "+v"(r));  // computed HERE (the optimiser would otherwise sink it to its use behind the wait)
             return r;
         };
@@ -259,7 +231,8 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
         };
         // Early request of the next level (never changes what is selected): a node remembers which child the last descent
         // through it chose — the sign bit of that child's prior (priors are >= 0; one ballot finds it, and every node has
-        // room for it, the fully visited nodes of the upper levels included).  When a node's records arrive, the
+        // room for it, the fully visited nodes of the upper levels included; rounds 3-4 kept an index in the spare word of the
+        // node's first unvisited edge instead: profiles/round5_hint_sign_ab.txt).  When a node's records arrive, the
         // remembered child's own records — its range is in this node's records — are requested at once and the scores are
         // computed while they are in flight; if the scores pick that child, the next level starts with its records
         // already on the way: a level then costs max(memory latency, its instructions) instead of their sum.
@@ -294,26 +267,6 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
             const bool live0 = lane < M, live1 = two && lane + WAVE < M;
             // the remembered child, requested before anything is scored
             int pv = -1, pred = -1;
-#if !AZH_HINT_SIGN
-            int u0 = -1;
-#endif
-#if !AZH_HINT_SIGN
-            auto request_child = [&](int idx) {
-                u32 pz, pk;
-                if (idx < WAVE) {
-                    pz = (u32)read_lane((int)e0.z, idx);
-                    pk = (u32)read_lane((int)e0.w, idx);
-                } else {
-                    pz = (u32)read_lane((int)e1.z, idx - WAVE);
-                    pk = (u32)read_lane((int)e1.w, idx - WAVE);
-                }
-                if ((pz >> 16) != ENONE && !kid_finished(pk) && kid_count(pk) > 0 && kid_count(pk) <= 2 * WAVE) {
-                    load_children(pk, p0, p1);
-                    pred = idx;
-                }
-            };
-#endif
-#if AZH_HINT_SIGN
             {
                 // (a mark is only ever set on an edge whose child exists, is not a finished position and has 1 .. 128 moves
                 // — below — and none of that changes while the edge lives: nothing to check here, one lane read)
@@ -328,31 +281,12 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
                     pred = pv;
                 }
             }
-#else
-            const u64 unv0 = __ballot(live0 && edge_child(e0) == ENONE);
-            const u64 unv1 = two ? __ballot(live1 && edge_child(e1) == ENONE) : 0ull;
-            if (unv0 | unv1) {
-                u32 hw;
-                if (unv0) {
-                    u0 = __ffsll((long long)unv0) - 1;
-                    hw = (u32)read_lane((int)e0.w, u0);
-                } else {
-                    u0 = __ffsll((long long)unv1) - 1;
-                    hw = (u32)read_lane((int)e1.w, u0);
-                    u0 += WAVE;
-                }
-                if ((hw >> 31) && (int)(hw & 0xFFu) < M) {
-                    pv = (int)(hw & 0xFFu);
-                    request_child(pv);
-                }
-            }
-#endif
             const u32 n0 = edge_visits(e0), n1 = edge_visits(e1);
             float sq1;
-            if (AZH_SQRT_EARLY && have_n)
+            if (have_n)
                 sq1 = sq_node;
-            else
-                sq1 = puct_sqrt((float)(1u + (have_n ? n_node : wave_sum_u32((live0 ? n0 : 0u) + (live1 ? n1 : 0u)))));
+            else  // (have_n is false here; the inner test is kept because the instruction schedule changes without it)
+                sq1 = sqrtf((float)(1u + (have_n ? n_node : wave_sum_u32((live0 ? n0 : 0u) + (live1 ? n1 : 0u)))));
             u32 bits0, bits1 = 0u;
             bool valid0, valid1 = false;
             {
@@ -397,7 +331,6 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
                 return false;
             }
             // remember the choice (stored only when it changes)
-#if AZH_HINT_SIGN
             if (bj != pv) {
                 // the mark moves: the lane that holds the edge chosen last time clears its prior's sign bit, the lane that
                 // holds the newly chosen edge sets it.  Two predicated stores: bj and pv may be 64 apart, i.e. the two
@@ -410,16 +343,11 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
                 if (markable && lane == (bj & 63))
                     reinterpret_cast<u32 *>(&A.ed[first + (u32)bj])[0] = (bj >= WAVE ? e1.x : e0.x) | ~PRIOR_MASK;
             }
-#else
-            if (u0 >= 0 && bj != pv && lane == 0)
-                reinterpret_cast<u32 *>(&A.ed[first + (u32)u0])[3] = 0x80000000u | (u32)bj;
-#endif
             node = child;
             kid = wsel;
             n_node = (zsel & 0xFFFFu) - 1u;
             have_n = true;
-            if (AZH_SQRT_EARLY)
-                sq_node = sqrt_1p(n_node);  // (while the requested records are on their way)
+            sq_node = sqrt_1p(n_node);  // (while the requested records are on their way)
             if (pred == bj)
                 cur_loaded = true;  // the records requested before the scores were computed are the next level's
             return true;
@@ -497,7 +425,6 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
                 st_levels += 1;
                 st_children += (u64)M0;
                 push_path(f0 + (u32)bj);
-#if AZH_HINT_SIGN
                 if (M0 <= 2 * WAVE && bj != pv) {  // (wider nodes carry no mark: the general level never sets one)
                     const bool markable = !kid_finished(wsel) && kid_count(wsel) > 0 && kid_count(wsel) <= 2 * WAVE;
                     if (pv >= 0 && lane == (pv & 63))
@@ -505,7 +432,6 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
                     if (markable && lane == (bj & 63))
                         reinterpret_cast<u32 *>(&A.ed[f0 + (u32)bj])[0] = (bj >= WAVE ? ea1.x : ea0.x) | ~PRIOR_MASK;
                 }
-#endif
                 node = zsel >> 16;
                 kid = wsel;
                 n_node = (zsel & 0xFFFFu) - 1u;
@@ -545,7 +471,7 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
                 }
             }
             const u32 ntot = have_n ? n_node : wave_sum_u32(nsum);
-            const float sq = (AZH_SQRT_EARLY && have_n) ? sq_node : puct_sqrt((float)(1u + ntot));
+            const float sq = have_n ? sq_node : sqrtf((float)(1u + ntot));
             // arg-max with ties to the LAST maximal edge (:354) — or the FIRST, python's max()
             // (engine.py:291), in the arena: scores are >= 0, so their bit patterns order like
             // the floats and (bits << 32 | index or ~index) is a total order; NaN scores (never
@@ -581,8 +507,7 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
                 kid = (u32)read_lane((int)mkid, bj & 63);
                 n_node = (zsel & 0xFFFFu) - 1u;
                 have_n = true;
-                if (AZH_SQRT_EARLY)
-                    sq_node = sqrt_1p(n_node);
+                sq_node = sqrt_1p(n_node);
                 cur_loaded = false;
                 continue;
             }
@@ -879,7 +804,8 @@ __device__ inline void backup_game(const EngineParams &P, int g, azh_game_state 
 
 // while (root.all_edge_visits < global_visits) step();  (:522-525): once the threshold is reached the move is due.
 // The game is only MARKED here (phase 2) and queued; the next select gives it no leaf, and the re-root
-// (advance_game) then runs from the queue in its own launch, beside the tower of the other games — a deep
+// (advance_game) then runs from the queue in the first workgroups of the next tower launch (or in a k_advance_list launch
+// of its own in front of it), beside the tower of the other games — a deep
 // subtree copy (one dependent round trip per tree level) no longer sits on every iteration's critical path.
 // `forced`: force[g], loaded by the caller beside the state; `pk`: the ply's kind word (playout cap: a FAST ply's move is
 // due at fast_visits).
@@ -1310,8 +1236,6 @@ struct azh_engine {
     azh_config cfg;
     EngineParams P;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;            // AZH_REROOT_SIDE_STREAM=1 only: queued re-roots (k_advance_list) beside the tower, rounds 3-5's loop
-    hipEvent_t ev_sel = nullptr, ev_adv = nullptr;
     std::vector<void *> allocs;
     float *d_feat = nullptr;
     float *d_sym_logits = nullptr, *d_sym_values = nullptr;  // AZH_FLAG_SYMMETRY_AVG scratch
@@ -1477,14 +1401,7 @@ extern "C" int azh_engine_create(const azh_config *cfg, azh_engine **out)
         azh_engine_destroy(e);
         return rc;
     }
-    // the side stream of the re-roots gets the highest priority the device offers: its few waves must not queue
-    // behind the tower's 1,200 workgroups for the slots those free
-    int prio_low = 0, prio_high = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);
     if (hipStreamCreate(&e->stream) != hipSuccess ||
-        hipStreamCreateWithPriority(&e->stream2, hipStreamDefault, prio_high) != hipSuccess ||
-        hipEventCreateWithFlags(&e->ev_sel, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&e->ev_adv, hipEventDisableTiming) != hipSuccess ||
         hipHostMalloc((void **)&e->h_count, sizeof(int)) != hipSuccess ||
         hipHostMalloc((void **)&e->h_head, sizeof(u64)) != hipSuccess) {
         azh_engine_destroy(e);
@@ -1518,8 +1435,6 @@ extern "C" void azh_engine_destroy(azh_engine *e)
         return;
     if (e->stream)
         (void)hipStreamSynchronize(e->stream);
-    if (e->stream2)
-        (void)hipStreamSynchronize(e->stream2);  // (a re-root launch may still be running under an abandoned run)
     for (auto ev : e->events)
         (void)hipEventDestroy(ev);
     for (void *p : e->allocs)
@@ -1538,12 +1453,6 @@ extern "C" void azh_engine_destroy(azh_engine *e)
         (void)hipHostFree(e->h_stage);
     for (u32 *q : e->h_stage_retired)
         (void)hipHostFree(q);
-    if (e->ev_sel)
-        (void)hipEventDestroy(e->ev_sel);
-    if (e->ev_adv)
-        (void)hipEventDestroy(e->ev_adv);
-    if (e->stream2)
-        (void)hipStreamDestroy(e->stream2);
     if (e->stream)
         (void)hipStreamDestroy(e->stream);
     delete e;
@@ -1554,12 +1463,11 @@ extern "C" int azh_engine_edge_cap(const azh_engine *e) { return e ? e->P.edge_c
 
 constexpr int ADV_GRID = 64;  // one wave each; a search iteration queues G * (1 / visits + ...) re-roots: about 11 at 4096 games
 
-// the queued re-roots, on `stream` (always after a select has passed over the queued games); `done`, if given, is
-// signalled by the kernel's own completion (no separate event packet in the queue)
-static int enqueue_advance(azh_engine *e, hipStream_t stream, hipEvent_t done = nullptr)
+// the queued re-roots in a launch of their own (always after a select has passed over the queued games)
+static int enqueue_advance(azh_engine *e)
 {
     e->unfetched_work = true;  // (every path that can finish a game goes through here)
-    hipExtLaunchKernelGGL(k_advance_list, dim3(ADV_GRID), dim3(WAVE), 0, stream, nullptr, done, 0, e->P);
+    hipExtLaunchKernelGGL(k_advance_list, dim3(ADV_GRID), dim3(WAVE), 0, e->stream, nullptr, nullptr, 0, e->P);
     AZH_HIP(hipGetLastError());
     return 0;
 }
@@ -1568,28 +1476,28 @@ static int enqueue_advance(azh_engine *e, hipStream_t stream, hipEvent_t done = 
 static int two_lists(const azh_engine *e) { return (e->P.flags & AZH_FLAG_TWO_NETS) && e->arena_lists; }
 
 // One tree launch on the engine's stream, for the device-resident loop and the step-wise API alike.  mode bit 0: backup +
-// mark, bit 1: select + leaf list; ev (or nullptr) is signalled by the kernel's own completion.
-static int enqueue_tree(azh_engine *e, int mode, bool stamped = false, hipEvent_t ev = nullptr)
+// mark, bit 1: select + leaf list.
+static int enqueue_tree(azh_engine *e, int mode, bool stamped = false)
 {
     const int two = two_lists(e);
     const bool small = e->P.G <= TREE_ONE_ROUND_GAMES;
     const int waves = small ? TREE_WAVES_SMALL : TREE_WAVES_LARGE;
     const dim3 grid((e->P.G + waves - 1) / waves), block(waves * WAVE);
     if (e->vl_active)  // leaf-parallel search: one workgroup per game (not stamped: azh_engine_tree_stamps refuses)
-        hipExtLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, nullptr, ev, 0, e->P, e->V, mode);
+        hipExtLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, nullptr, nullptr, 0, e->P, e->V, mode);
     else if (stamped && small)
-        hipExtLaunchKernelGGL((k_tree<true, TREE_WAVES_SMALL>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
+        hipExtLaunchKernelGGL((k_tree<true, TREE_WAVES_SMALL>), grid, block, 0, e->stream, nullptr, nullptr, 0, e->P, mode, two);
     else if (stamped)
-        hipExtLaunchKernelGGL((k_tree<true, TREE_WAVES_LARGE>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
+        hipExtLaunchKernelGGL((k_tree<true, TREE_WAVES_LARGE>), grid, block, 0, e->stream, nullptr, nullptr, 0, e->P, mode, two);
     else if (small)
-        hipExtLaunchKernelGGL((k_tree<false, TREE_WAVES_SMALL>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
+        hipExtLaunchKernelGGL((k_tree<false, TREE_WAVES_SMALL>), grid, block, 0, e->stream, nullptr, nullptr, 0, e->P, mode, two);
     else
-        hipExtLaunchKernelGGL((k_tree<false, TREE_WAVES_LARGE>), grid, block, 0, e->stream, nullptr, ev, 0, e->P, mode, two);
+        hipExtLaunchKernelGGL((k_tree<false, TREE_WAVES_LARGE>), grid, block, 0, e->stream, nullptr, nullptr, 0, e->P, mode, two);
     AZH_HIP(hipGetLastError());
     return 0;
 }
 
-static int enqueue_select(azh_engine *e) { return enqueue_tree(e, 2) || enqueue_advance(e, e->stream); }
+static int enqueue_select(azh_engine *e) { return enqueue_tree(e, 2) || enqueue_advance(e); }
 
 static int enqueue_backup(azh_engine *e) { return enqueue_tree(e, 1); }
 
@@ -1701,11 +1609,9 @@ extern "C" int azh_engine_backup(azh_engine *e)
 // The queued moves (sample, record, re-root: advance_game) are played by the first workgroups of the tower launch that
 // follows the tree launch which queued them — dispatched before any tile's workgroup, done after ~0.1 ms, and the next
 // tree launch, behind the tower on the same stream, finds every move played: one stream, two launches per iteration.
-// Rounds 3-5 ran them as k_advance_list on a high-priority side stream beside the tower, with the tree launches' and
-// its own completion signals as cross-stream events: the tower leaves no wave slot and no LDS beside itself, so that
-// launch spent most of its 0.2-0.5 ms waiting for the tower's first workgroups to retire (and outlasted the tower in
-// 5-9 % of the iterations), and the event machinery cost an iteration 7-10 us with nothing queued
-// (profiles/round6_reroots_in_the_tower_launch.txt).  AZH_REROOT_SIDE_STREAM=1 runs that loop (A/B runs; read per call).
+// (Rounds 3-5 ran them as a launch of their own on a high-priority side stream beside the tower; that launch mostly waited
+// for the tower's first workgroups to retire and its events cost every iteration 7-10 us:
+// profiles/round6_reroots_in_the_tower_launch.txt.)
 //
 // A run is enqueued as begin() + `iterations` x iteration(): azh_engine_run does that for one engine, azh_engines_run for
 // several with their iterations interleaved, so that the half-batches of a GPU all start with the first launches enqueued
@@ -1714,21 +1620,11 @@ struct RunLoop {
     azh_engine *e;
     azh_net *net_a, *net_b;
     int dtype, iterations;
-    bool pair = false, side = false;
+    bool pair = false;
     bool own = false;  // forced playouts, random symmetry: the queued moves in a k_advance_list launch of their own, on the engine's
                        // stream, in front of the tower (the tower kernels' advance_game records no pruned counts and writes no
                        // key word: engine_device.h)
     AdvanceHook hook;
-
-    // side-stream mode: ev_sel is signalled by the tree launch itself, ev_adv by the re-root launch (hipExtLaunchKernelGGL's
-    // stop event: no event-record packets at the kernel boundaries of the main stream)
-    int side_advance()
-    {
-        if (!side)
-            return 0;
-        AZH_HIP(hipStreamWaitEvent(e->stream2, e->ev_sel, 0));
-        return enqueue_advance(e, e->stream2, e->ev_adv);
-    }
 
     int begin()
     {
@@ -1736,23 +1632,21 @@ struct RunLoop {
         const char *pair_s = getenv("AZH_ARENA_PAIR");  // (read per call: a test switches it inside one process)
         const bool pair_env = !(pair_s && atoi(pair_s) == 0);
         pair = pair_env && two_lists(e) && !(e->P.flags & AZH_FLAG_SYMMETRY_AVG);
-        const char *side_s = getenv("AZH_REROOT_SIDE_STREAM");
-        side = side_s && atoi(side_s) != 0;
-        own = !side && (e->P.forced_k != 0.0f || e->P.random_symmetry != 0u);
+        own = e->P.forced_k != 0.0f || e->P.random_symmetry != 0u;
         hook.workers = e->adv_workers;
         hook.at_head = 1;   // (decided per launch by the tower's launch functions: in front only where workgroups queue for slots)
         hook.P = e->P;
         e->unfetched_work = true;  // (every path that can finish a game goes through a re-root)
-        if (enqueue_tree(e, 2, false, side ? e->ev_sel : nullptr))  // select + leaf list
+        if (enqueue_tree(e, 2))  // select + leaf list
             return -1;
-        if (own && enqueue_advance(e, e->stream))
+        if (own && enqueue_advance(e))
             return -1;
-        return side_advance();
+        return 0;
     }
 
     int iteration(int it)
     {
-        const AdvanceHook *moves = side || own ? nullptr : &hook;
+        const AdvanceHook *moves = own ? nullptr : &hook;
         const bool rec = e->timing_stride > 0 && e->loop_iter % e->timing_stride == 0 && e->samples < MAX_TIMED_SAMPLES;
         hipEvent_t *ev = rec ? &e->events[3 * e->samples] : nullptr;
         if (e->close_pending) {
@@ -1779,15 +1673,12 @@ struct RunLoop {
         if (rc) return rc;
         if (rec) AZH_HIP(hipEventRecord(ev[1], e->stream));
         const int last = it + 1 == iterations;
-        if (side)
-            AZH_HIP(hipStreamWaitEvent(e->stream, e->ev_adv, 0));
         const bool stamped = e->stamp_next && !last;
-        if (enqueue_tree(e, last ? 1 : 3, stamped, last || !side ? nullptr : e->ev_sel))
+        if (enqueue_tree(e, last ? 1 : 3, stamped))
             return -1;
         if (stamped)
             e->stamp_next = false;
-        if (!last && own && enqueue_advance(e, e->stream)) return -1;
-        if (!last && side_advance()) return -1;
+        if (!last && own && enqueue_advance(e)) return -1;
         if (rec) {
             e->samples++;
             if (last) {
@@ -1905,7 +1796,6 @@ static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, b
                             leaves_per_game > 1 ? "more than one leaf per game" : "the solver");
     }
     AZH_HIP(hipStreamSynchronize(e->stream));
-    AZH_HIP(hipStreamSynchronize(e->stream2));
     EngineParams &P = e->P;
     const size_t G = (size_t)P.G, K = (size_t)leaves_per_game;
     if (want && !e->vl_active && e->vl_slots_cap > 0) {
@@ -2059,7 +1949,6 @@ extern "C" int azh_engine_set_playout_cap(azh_engine *e, int fast_visits, int fu
         return azh_fail(-4, "azh_engine_set_playout_cap: not supported with %s",
                         (e->P.flags & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS" : "AZH_FLAG_ONE_RANDOM_MOVE");
     AZH_HIP(hipStreamSynchronize(e->stream));
-    AZH_HIP(hipStreamSynchronize(e->stream2));
     if (fast_visits == 0) {
         e->P.fast_visits = 0;
         e->P.full_per_65536 = 0;
@@ -2098,7 +1987,6 @@ extern "C" int azh_engine_set_forced_playouts(azh_engine *e, float k)
         return azh_fail(-4, "azh_engine_set_forced_playouts: not supported with %s",
                         leaf_k(e) > 1 ? "more than one leaf per game (azh_engine_set_leaf_batch)" : "the solver");
     AZH_HIP(hipStreamSynchronize(e->stream));
-    AZH_HIP(hipStreamSynchronize(e->stream2));
     e->P.forced_k = k;
     return 0;
 }
@@ -2138,7 +2026,6 @@ extern "C" int azh_engine_set_random_symmetry(azh_engine *e, int on)
                             "image under all 8 symmetries (the tower takes one blocker plane per launch)",
                         (unsigned long long)e->P.blockers);
     AZH_HIP(hipStreamSynchronize(e->stream));
-    AZH_HIP(hipStreamSynchronize(e->stream2));
     if (!on) {
         e->P.random_symmetry = 0u;
         return 0;
@@ -2189,7 +2076,6 @@ extern "C" int azh_engine_set_game_limit(azh_engine *e, int64_t games)
     if (!e || games < 1 || games > 0xFFFFFFFFll)
         return azh_fail(-1, "azh_engine_set_game_limit: bad argument");
     AZH_HIP(hipStreamSynchronize(e->stream));
-    AZH_HIP(hipStreamSynchronize(e->stream2));
     e->P.uid_limit = (u32)games;
     hipLaunchKernelGGL(k_limit_slots, dim3(e->P.G), dim3(WAVE), 0, e->stream, e->P);
     AZH_HIP(hipGetLastError());
@@ -2222,7 +2108,6 @@ extern "C" int azh_engine_set_positions(azh_engine *e, const uint64_t *boards, c
     if (!e || !boards || !plies)
         return azh_fail(-1, "azh_engine_set_positions: null argument");
     AZH_HIP(hipStreamSynchronize(e->stream));
-    AZH_HIP(hipStreamSynchronize(e->stream2));
     const size_t G = (size_t)e->P.G;
     // uids restart at the slot numbers: whatever the previous games left behind (undrained records, games held back
     // for uid order) belongs to uids that are about to be reused, and is discarded with them
@@ -2267,7 +2152,6 @@ extern "C" int azh_engine_play_moves(azh_engine *e, const uint16_t *moves, int32
     const size_t G = (size_t)e->P.G;
     if (!e->d_play_moves && (dev_alloc(e, &e->d_play_moves, G) || dev_alloc(e, &e->d_play_status, G)))
         return -1;
-    AZH_HIP(hipStreamSynchronize(e->stream2));  // (side-stream re-roots of an earlier run)
     AZH_HIP(hipMemcpyAsync(e->d_play_moves, moves, G * sizeof(u16), hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(k_play_moves, dim3(e->P.G), dim3(WAVE), 0, e->stream, e->P, (const u16 *)e->d_play_moves, e->d_play_status);
     hipLaunchKernelGGL(k_unqueue_played, dim3(1), dim3(WAVE), 0, e->stream, e->P);
@@ -2421,10 +2305,9 @@ extern "C" int azh_engine_timing(azh_engine *e, azh_timing *out)
 // the caller has enqueued in between (round 3's loop did exactly that and ran sequentially without saying so).
 static int fetch_records(azh_engine *e)
 {
-    // Everything on the engine's OWN streams: a fetch of one half-batch must not wait for the other half's run (the
+    // Everything on the engine's OWN stream: a fetch of one half-batch must not wait for the other half's run (the
     // legacy null stream would: the engines' streams are blocking streams).
     AZH_HIP(hipStreamSynchronize(e->stream));
-    AZH_HIP(hipStreamSynchronize(e->stream2));  // (idle by now: the last tree launch of a run waits for the last re-roots)
     e->unfetched_work = false;
     AZH_HIP(hipMemcpyAsync(e->h_head, e->P.ring_head, 8, hipMemcpyDeviceToHost, e->stream));
     AZH_HIP(hipStreamSynchronize(e->stream));
@@ -2460,9 +2343,8 @@ static int fetch_records(azh_engine *e)
     return 0;
 }
 
-// 1 while work enqueued on the engine is still in flight, 0 when it is idle: a query, never a wait.  (The main stream is
-// the one asked: everything a run enqueues is on it — in side-stream mode the last tree launch of a run waits for the last
-// re-roots — so an idle main stream means an idle engine.)
+// 1 while work enqueued on the engine is still in flight, 0 when it is idle: a query, never a wait.  (Everything a run
+// enqueues is on the engine's one stream, so an idle stream means an idle engine.)
 extern "C" int azh_engine_query(azh_engine *e)
 {
     if (!e)

@@ -146,7 +146,7 @@ __device__ inline Arena arena_of(const EngineParams &P, int a, int g)
 //      tree, PRIOR_MASK)                     y  total score W (f32 bits)
 //   z  visits (bits 0-15) | child node (bits 16-31, ENONE = not expanded)
 //   w  the child's first edge (bits 0-22) | its edge count (bits 23-30) | finished position (bit 31); 0 in an edge without
-//      a child (rounds 3-4 kept the descent's hint in the first such edge's word: AZH_HINT_SIGN=0)
+//      a child
 // visits <= 60000 and nodes <= visits + 8 (azh_engine_create), edges per game < 2^23, moves per position <= 255.
 constexpr u32 ENONE = 0xFFFFu;
 __device__ inline u32 edge_visits(const uint4 &e) { return e.z & 0xFFFFu; }
@@ -285,7 +285,7 @@ __device__ inline void init_game(const EngineParams &P, int g, u32 uid, azh_game
     init_game_at<KEY>(P, g, uid, s, s_moves, b, 0, 0);
 }
 
-constexpr u32 PRIOR_MASK = 0x7FFFFFFFu;  // the prior proper (AZH_HINT_SIGN: bit 31 marks the remembered child)
+constexpr u32 PRIOR_MASK = 0x7FFFFFFFu;  // the prior proper (bit 31 marks the remembered child)
 
 // ------------------------------------------------------------------ re-root
 

@@ -102,7 +102,7 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
                     }
                 }
                 // N = the sum of the children's effective counts, as the oracle sums them
-                const float sq = puct_sqrt((float)(1u + wave_sum_u32(nsum)));
+                const float sq = sqrtf((float)(1u + wave_sum_u32(nsum)));
                 // arg-max with the engine's tie rule: (score bits << 32 | index or ~index), NaN and empty lanes key 0
                 u64 key = 0;
                 u32 mine = ev[0].z, mkid = ev[0].w;

@@ -124,7 +124,6 @@ def launch(tmp_path, argv, env=None, name="games-0.json"):
     code = STUB % {"root": ROOT, "log": log, "argv": ["--network", "none.npy", "--output-games", out] + argv}
     e = dict(os.environ)
     e.pop("AZH_GAME_COUNT", None)
-    e.pop("AZH_SEQUENTIAL_DRAIN", None)
     e.update(env or {})
     proc = subprocess.Popen([sys.executable, "-c", code], cwd=ROOT, env=e, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     return proc, out, log
@@ -171,21 +170,13 @@ def test_the_stand_in_would_have_caught_round_3s_implicit_fetch(tmp_path):
     assert games == list(range(len(games)))         # (correct games all the same: that is why nobody noticed)
 
 
-def test_sequential_order_on_request_and_with_a_game_target(tmp_path):
-    proc, out, log = launch(tmp_path, ["--max-seconds", "0.2"], env={"AZH_SEQUENTIAL_DRAIN": "1"})
+def test_sequential_order_with_a_game_target(tmp_path):
+    proc, out, log = launch(tmp_path, ["--game-count", "10"])
     text, games, calls = finish(proc, out, log)
     assert proc.returncode == 0, text
     seq = loop_calls(calls)
-    assert "fetch" not in seq and seq[:3] == ["run", "fetch_in_drain", "drain"]   # sequential: the drain itself waits
-    assert games == list(range(3 * seq.count("run")))
-
-    sub = tmp_path / "target"
-    sub.mkdir()
-    proc, out, log = launch(sub, ["--game-count", "10"])
-    text, games, calls = finish(proc, out, log)
-    assert proc.returncode == 0, text
-    seq = loop_calls(calls)
-    assert "fetch" not in seq                       # with a target the rounds stay sequential (counters read every round)
+    # with a target the rounds stay sequential (counters read every round): the drain itself waits
+    assert "fetch" not in seq and seq[:3] == ["run", "fetch_in_drain", "drain"]
     assert ["limit", 10] in calls and ["create", 10, 100] in calls
     assert games == list(range(10))                 # exactly the games below the limit, then the script ends by itself
 

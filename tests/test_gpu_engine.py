@@ -609,19 +609,14 @@ def _oracle_follow(oe, net, blockers, iterations, dtype=link.DTYPE_F32, thin=Fal
     ("C4-full", 4096, 800, 8, 400, 48, 2, 300, "f16"),      # BASELINE configs[3] at its full size: 4096 games, 800 sims/move, 8x128, f16
     ("two-rounds", 8203, 8, 1, 60, 6, 2, 40, "f32"),        # more games than resident waves (8192): one game per workgroup,
                                                             # a need-bit mask with a ragged last word
-    ("turnover-side-stream", 512, 12, 2, 90, 6, 12, 250, "f32"),   # rounds 3-5's loop (AZH_REROOT_SIDE_STREAM=1): the queued moves
-                                                                   # as k_advance_list on a side stream behind events
 ])
-def test_device_resident_loop_matches_oracle_bit_for_bit(name, games, visits, blocks, max_plies, budget, chunks, chunk, dtype, monkeypatch):
+def test_device_resident_loop_matches_oracle_bit_for_bit(name, games, visits, blocks, max_plies, budget, chunks, chunk, dtype):
     """The loop bench.py and the CLI run — azh_engine_run: fused k_tree, the queued moves played by the first workgroups of
     the tower launch, parked descents — against the oracle, iteration for iteration: every game state, every arena word and
     every JSON line.  (The step-wise API the other lock-step tests drive shares the device functions but not the launch
     structure.)  The two BASELINE shapes run in their own dtype with the three-board tower (more than 512 slots): the oracle's
     leaves are evaluated by the same kernel in leaf-list order, which gives every board the slot it has in the loop."""
     dt = link.DTYPES[dtype]
-    if name.endswith("side-stream"):
-        monkeypatch.setenv("AZH_REROOT_SIDE_STREAM", "1")
-        name = name[:-len("-side-stream")]
     conv, bn = model.random_init(blocks, 128, seed=7)
     net = link.Net(conv, bn)
     oe, ge = make_pair(games=games, visits=visits, max_plies=max_plies, seed=99, select_budget=budget)

@@ -2,9 +2,8 @@
 # rocprofv3 passes over bench.py itself (run on the GPU box from the repo root):
 # kernel trace + stats of the default bench command, then PMC passes for the dominant kernel.
 #   ARGS="..."      the bench command's arguments (default: the headline, 6 steps)
-#   KERNELS="a b"   kernels to summarise, substrings of their names (default: k_tower k_tree — since round 6 the queued moves are
-#                   played inside the tower launch; AZH_REROOT_SIDE_STREAM=1 brings k_advance_list back); the first one's
-#                   summary names the sha256 of net_kernels.hip, the others' that of engine.hip
+#   KERNELS="a b"   kernels to summarise, substrings of their names (default: k_tower k_tree — the queued moves are played inside
+#                   the tower launch); the first one's summary names the sha256 of net_kernels.hip, the others' that of engine.hip
 #   NO_TIMED=1      no "last steps x 250 launches" block (for commands whose kernels of interest are a leg's, not the headline's)
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$PWD}
@@ -28,7 +27,7 @@ f = max(glob.glob(os.path.join(sys.argv[1], "trace", "*", "*_kernel_trace.csv"))
 m = re.search(r"--steps (\d+)", sys.argv[2])
 h = re.search(r"--streams (\d+)", sys.argv[2])
 n = (int(m.group(1)) if m else 40) * 250 * (int(h.group(1)) if h else 2)   # bench.py's default: two half-batches in flight
-for name in ("k_tower", "k_tree", "k_advance_list"):   # (k_advance_list: side-stream mode only)
+for name in ("k_tower", "k_tree", "k_advance_list"):   # (k_advance_list: forced playouts / random symmetry only)
     d = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in csv.DictReader(open(f)) if name in r["Kernel_Name"]]
     d = d[-n:]
     if not d:
