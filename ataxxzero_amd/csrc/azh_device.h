@@ -401,12 +401,20 @@ constexpr u32 STREAM_RANDOM_PLAY = 2u;
 constexpr u32 STREAM_RANDOM_PLY = 3u;
 constexpr u32 STREAM_PLAYOUT_CAP = 4u;
 constexpr u32 STREAM_EVAL_SYMMETRY = 5u;
+constexpr u32 STREAM_RESIGN = 6u;
 
 // Playout cap randomization (azh_engine_set_playout_cap): is ply `ply` of game `uid` searched in FULL?  A pure function of
 // the engine's Philox key, so a trainer or a test restates it without a device (azh_playout_cap_kind).
 __host__ __device__ inline bool playout_cap_full(u32 k0, u32 k1, u32 uid, u32 ply, u32 full_per_65536)
 {
     return (philox(k0, k1, uid, ply, STREAM_PLAYOUT_CAP, 0u).v[0] >> 16) < full_per_65536;
+}
+
+// Resignation (azh_engine_set_resign): does game `uid` play through to its real end whatever the rule says?  A pure function
+// of the engine's Philox key (azh_resign_playthrough).
+__host__ __device__ inline bool resign_playthrough(u32 k0, u32 k1, u32 uid, u32 per_65536)
+{
+    return (philox(k0, k1, uid, 0u, STREAM_RESIGN, 0u).v[0] >> 16) < per_65536;
 }
 // Forced playouts and policy target pruning (azh_engine_set_forced_playouts; DESIGN.md, "Forced playouts and policy target
 // pruning").  Every f32 operation is a single IEEE one in the order written, in whichever translation unit this is compiled

@@ -1621,9 +1621,9 @@ struct RunLoop {
     azh_net *net_a, *net_b;
     int dtype, iterations;
     bool pair = false;
-    bool own = false;  // forced playouts, random symmetry: the queued moves in a k_advance_list launch of their own, on the engine's
-                       // stream, in front of the tower (the tower kernels' advance_game records no pruned counts and writes no
-                       // key word: engine_device.h)
+    bool own = false;  // forced playouts, random symmetry, recorded values and resignation: the queued moves in a k_advance_list launch of their own, on the engine's
+                       // stream, in front of the tower (the tower kernels' advance_game records no pruned counts, writes no
+                       // key word and knows no ply value: engine_device.h)
     AdvanceHook hook;
 
     int begin()
@@ -1632,7 +1632,7 @@ struct RunLoop {
         const char *pair_s = getenv("AZH_ARENA_PAIR");  // (read per call: a test switches it inside one process)
         const bool pair_env = !(pair_s && atoi(pair_s) == 0);
         pair = pair_env && two_lists(e) && !(e->P.flags & AZH_FLAG_SYMMETRY_AVG);
-        own = e->P.forced_k != 0.0f || e->P.random_symmetry != 0u;
+        own = e->P.forced_k != 0.0f || e->P.random_symmetry != 0u || e->P.resign_plies != 0u;
         hook.workers = e->adv_workers;
         hook.at_head = 1;   // (decided per launch by the tower's launch functions: in front only where workgroups queue for slots)
         hook.P = e->P;
@@ -2000,6 +2000,59 @@ extern "C" int azh_forced_prune(const float *prior, const float *W, const uint32
     if (!(k >= 0.0f) || k > 3.0e38f)
         return azh_fail(-2, "azh_forced_prune: need a finite k >= 0");
     forced_prune_root(prior, W, n, M, k, c_puct, out);
+    return 0;
+}
+
+// The search's own value in every ply's record, and resignation of decided games.  Definition: the header and DESIGN.md.
+// Between iterations only; every slot's counters are cleared.
+extern "C" int azh_engine_set_resign(azh_engine *e, float q_below, int consecutive, int playthrough_per_65536)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_set_resign: null engine");
+    if (consecutive < 0 || consecutive > 255)
+        return azh_fail(-2, "azh_engine_set_resign: need 0 <= consecutive <= 255 (0: off)");
+    if (consecutive != 0 && (!(q_below >= 0.0f) || !(q_below < 1.0f) || playthrough_per_65536 < 0 || playthrough_per_65536 > 65536))
+        return azh_fail(-2, "azh_engine_set_resign: need 0 <= q_below < 1 and 0 <= playthrough_per_65536 <= 65536");
+    if (e->selected)
+        return azh_fail(-3, "azh_engine_set_resign: a selected batch awaits its backup");
+    if (consecutive != 0 && (e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_ONE_RANDOM_MOVE)))
+        return azh_fail(-4, "azh_engine_set_resign: not supported with %s",
+                        (e->P.flags & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS" : "AZH_FLAG_ONE_RANDOM_MOVE");
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    if (consecutive == 0) {
+        e->P.resign_plies = 0u;
+        e->P.resign_below = 0.0f;
+        e->P.resign_through = 0u;
+        return 0;
+    }
+    if (!e->P.resign_state && dev_alloc(e, &e->P.resign_state, (size_t)e->P.G))
+        return -1;
+    if (!e->P.resign_stats && dev_alloc(e, &e->P.resign_stats, (size_t)AZH_RESIGN_STAT_COUNT))
+        return -1;
+    AZH_HIP(hipMemset(e->P.resign_state, 0, (size_t)e->P.G * sizeof(u32)));
+    e->P.resign_below = q_below;
+    e->P.resign_plies = (u32)consecutive;
+    e->P.resign_through = (u32)playthrough_per_65536;
+    return 0;
+}
+
+// Is game `uid` under `seed` a play-through game?  Host arithmetic only.
+extern "C" int azh_resign_playthrough(uint64_t seed, uint32_t uid, uint32_t playthrough_per_65536)
+{
+    return resign_playthrough((u32)seed, (u32)(seed >> 32), uid, playthrough_per_65536) ? 1 : 0;
+}
+
+// The once-per-game counts of the resign rule since create: out [AZH_RESIGN_STAT_COUNT] (zeros before the mode was ever on).
+extern "C" int azh_engine_resign_stats(azh_engine *e, uint64_t *out)
+{
+    if (!e || !out)
+        return azh_fail(-1, "azh_engine_resign_stats: bad argument");
+    for (int k = 0; k < AZH_RESIGN_STAT_COUNT; k++)
+        out[k] = 0;
+    if (!e->P.resign_stats)
+        return 0;
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_HIP(hipMemcpy(out, e->P.resign_stats, AZH_RESIGN_STAT_COUNT * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

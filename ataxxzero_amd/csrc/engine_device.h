@@ -21,6 +21,9 @@ constexpr u32 REC_KIND_PLAYOUT_CAP = 4u;  // header word 7, beside its kind in b
                                           // (word 5 of every ply: 1 = FULL), and its line carries "full"
 constexpr u32 REC_KIND_FORCED = 8u;       // beside it: the game was played with forced playouts on — the visit counts of the plies
                                           // the mode acts on are the pruned ones (json.cpp ignores the bit)
+constexpr u32 REC_KIND_VALUES = 16u;      // the game was played with the search value recorded (azh_engine_set_resign): word 5 of
+                                          // every ply = the bits of q (sign bit: FULL), and its line carries "values"
+constexpr u32 REC_KIND_RESIGNED = 32u;    // the game ended by resignation: its line carries "resigned"
 constexpr int NSTAT = AZH_STAT_COUNT;
 constexpr int BFS_QL = 384;  // re-root frontier entries kept in LDS; later ones spill to bfs_spill in HBM
 
@@ -80,6 +83,13 @@ struct EngineParams {
     u32 random_symmetry;   // the evaluator sees T_s of every leaf board and apply_priors gathers through T_s of every move
     u32 *eval_key;         // [G] the key word of each slot's game (eval_symmetry_key), written where a game begins (begin_game_key):
                            // s = eval_symmetry_of(key, the position) — no Philox block on the tree kernels' per-iteration path
+    // recorded search value and resignation (azh_engine_set_resign), off while resign_plies == 0
+    float resign_below;       // a counted ply is bad for its mover iff q < this
+    u32 resign_plies;         // the rule fires when the mover's counter of consecutive bad plies reaches this
+    u32 resign_through;       // game uid plays through iff (philox(uid, 0, STREAM_RESIGN).v[0] >> 16) < this
+    u32 *resign_state;        // [G] bits 0-7 / 8-15: the counter of side 1 / 2, bits 16-17: the side the rule first fired for;
+                              // cleared where a game begins (begin_game_key's callers), written by k_advance_list's advance_game
+    u64 *resign_stats;        // [AZH_RESIGN_STAT_COUNT] once-per-game counts (global atomics at a game's end)
 };
 
 constexpr u32 PLY_FULL = 0x80000000u;
@@ -100,6 +110,8 @@ __device__ inline void begin_game_key(const EngineParams &P, int g, u32 uid)
         asm volatile("" : "+v"(uid));  // (as begin_ply: the block in vector registers)
         P.eval_key[g] = eval_symmetry_key(P.k0, P.k1, uid);
     }
+    if (P.resign_plies != 0u && lane_id() == 0)  // the game's resign counters (the same instantiations: every game start but
+        P.resign_state[g] = 0u;                  // the tower kernels', which play no move while the mode is on)
 }
 
 // The kind word of slot g's ply as the tree kernels use it (g wave-uniform: a scalar load); PLY_FULL while the mode is off.
@@ -487,14 +499,17 @@ __device__ inline int record_pruned_counts(const EngineParams &P, const Arena &A
     return nd;
 }
 
-// PRUNE: the instantiation that can record pruned counts (forced playouts) — k_advance_list's.  The tower kernels carry the
+// OWN: the instantiation of the move-playing launch of its own, k_advance_list: the one that can record pruned counts (forced
+// playouts), write a game's key word (random symmetry), and record the ply's value and resign (azh_engine_set_resign).  The
+// tower kernels carry the
 // other one: they have no register to spare for the pruning (a 16-bit tower went to scratch memory with it), so while forced
 // playouts are on the device loop plays the queued moves in a k_advance_list launch of its own in front of the tower.
 // The same goes for the key word of the random symmetry, one Philox block where a game begins: inlined in the tower kernels
 // it sent k_tower2<1, false> and <2, false> to scratch memory (12 bytes per lane, 2 VGPR spills;
 // profiles/random_symmetry.txt), so their instantiation starts games without it and that mode, too, plays its moves in
-// k_advance_list.
-template <bool PRUNE>
+// k_advance_list.  The ply's value, the resign rule and its once-per-game counts live in the OWN instantiation alone for the
+// same reason.
+template <bool OWN>
 __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
 {
     u16 *s_moves = L.moves;
@@ -606,7 +621,7 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
     const u64 lt = (1ULL << lane) - 1ULL;
     int nd = 0;
     bool pruned = false;
-    if constexpr (PRUNE)
+    if constexpr (OWN)
         pruned = P.forced_k != 0.0f && (ply_kind_of(P, g) & PLY_FULL) != 0u;
     if (pruned) {
         nd = record_pruned_counts(P, A, first, M, N, rec);
@@ -627,6 +642,48 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
     const u32 mv = (u32)read_lane((int)my_mv, cl);
     const u32 c = (P.flags & AZH_FLAG_NO_REUSE) ? ENONE : (u32)read_lane((int)my_ch, cl);  // arena engines rebuild the tree every ply
     const ulonglong2 rootw = A.nb[0];
+    u32 w5 = 0;  // word 5 of the ply's record while the mode is on
+    // The ply's value and the resign rule (azh_engine_set_resign): q = W_b / n_b of the most visited root edge b (ties: the
+    // lowest index), one f32 division; a counted ply (not a FAST one) with q < resign_below advances the mover's counter,
+    // any other counted ply resets it; the rule fires when the counter reaches resign_plies.
+    bool resign = false;
+    u32 mover = 0, rs_word = 0;
+    if constexpr (OWN) {
+        w5 = (P.fast_visits != 0 && (P.ply_kind[g] & PLY_FULL)) ? 1u : 0u;
+        if (P.resign_plies != 0u) {
+            u64 key = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int j = lane + 64 * k;
+                if (j < M) {
+                    const u64 kk = ((u64)nv[k] << 32) | (u64)(0xFFFFFFFFu - (u32)j);
+                    key = kk > key ? kk : key;
+                }
+            }
+            key = wave_max_u64(key);
+            const u32 n_b = (u32)(key >> 32);
+            float q = 0.5f;
+            if (n_b != 0u)
+                q = u2f(reinterpret_cast<const u32 *>(&A.ed[first + (0xFFFFFFFFu - (u32)key)])[1]) / (float)n_b;
+            // the rule sees q as the record holds it, without its sign (q >= 0 from any finite evaluator): a pure function of
+            // the record, and neither a NaN nor an infinity of either sign is ever below
+            q = u2f(f2u(q) & 0x7FFFFFFFu);
+            mover = (rootw.x & TURN_BIT) ? 2u : 1u;
+            rs_word = P.resign_state[g];
+            if (n_b != 0u && (P.fast_visits == 0 || w5 != 0u)) {
+                const u32 sh = mover == 1u ? 0u : 8u;
+                u32 cnt = (rs_word >> sh) & 0xFFu;
+                cnt = q < P.resign_below ? min(cnt + 1u, 255u) : 0u;
+                rs_word = (rs_word & ~(0xFFu << sh)) | (cnt << sh);
+                if (cnt >= P.resign_plies) {
+                    if ((rs_word >> 16) == 0u)
+                        rs_word |= mover << 16;
+                    resign = !resign_playthrough(P.k0, P.k1, s.uid, P.resign_through);
+                }
+            }
+            w5 = f2u(q) | (w5 << 31);
+        }
+    }
     if (lane == 0) {
         const u64 bx = rootw.x & ~TURN_BIT;
         rec[0] = (u32)bx;
@@ -634,14 +691,26 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
         rec[2] = (u32)rootw.y;
         rec[3] = (u32)(rootw.y >> 32);
         rec[4] = (mv & 0xFFFFu) | ((u32)nd << 16);
-        rec[5] = (P.fast_visits != 0 && (P.ply_kind[g] & PLY_FULL)) ? 1u : 0u;  // playout cap: 1 = searched in full
+        if constexpr (OWN)
+            rec[5] = w5;
+        else
+            rec[5] = (P.fast_visits != 0 && (P.ply_kind[g] & PLY_FULL)) ? 1u : 0u;  // playout cap: 1 = searched in full
         rec[6] = 0;
         rec[7] = 0;
     }
 
     // MCTS::play (:475-492), the evaluation-cache rebuild, the arena flip
     RerootStats rs;
-    const int result = reroot_game(P, g, L, s, A, B, rootw, mv, c, rs);
+    int result;
+    if (resign) {
+        // the mover resigns: the ply above is the record's last, its move is not played, the game ends here
+        result = 3 - (int)mover;
+        s.ply += 1;
+        __threadfence();
+        wave_sync();
+    } else {
+        result = reroot_game(P, g, L, s, A, B, rootw, mv, c, rs);
+    }
     const u64 st_nodes = rs.nodes, st_edges = rs.edges, st_spill = rs.spill;
 
     u64 st_games = 0, st_dropped = 0, st_ring = 0;
@@ -668,7 +737,7 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
     if (no_sample) {
         st_dropped = 1;
         drop_marker();
-        init_game<PRUNE>(P, g, s.uid + (u32)P.G, s, s_moves);
+        init_game<OWN>(P, g, s.uid + (u32)P.G, s, s_moves);
     } else if (result != 0 || (cut && (P.flags & AZH_FLAG_KEEP_UNFINISHED))) {
         // finished: emit the packed record (generate_game :577-578, Worker :637-642)
         const u32 *recg = P.rec + (size_t)g * P.max_plies * REC_STRIDE_WORDS;
@@ -692,6 +761,23 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
                 out[6] = (P.flags & AZH_FLAG_ONE_RANDOM_MOVE) ? (u32)random_ply_of(P, s.uid) + 1u : 0u;
                 out[7] = (loaded ? 2u : 0u)   // 2: partial game (begins at a loaded position): formatted by the host, not written
                          | (P.fast_visits != 0 ? REC_KIND_PLAYOUT_CAP : 0u) | (P.forced_k != 0.0f ? REC_KIND_FORCED : 0u);
+                if constexpr (OWN) {
+                    if (P.resign_plies != 0u) {
+                        out[7] |= REC_KIND_VALUES | (resign ? REC_KIND_RESIGNED : 0u);
+                        // once-per-game counts: resigned; play-through games that reached their end, those the rule fired
+                        // in, and of those the ones the side it first fired for did not lose
+                        const u32 fired = rs_word >> 16;
+                        if (resign) {
+                            atomicAdd((unsigned long long *)&P.resign_stats[AZH_RESIGN_STAT_RESIGNED], 1ull);
+                        } else if (result != 0 && resign_playthrough(P.k0, P.k1, s.uid, P.resign_through)) {
+                            atomicAdd((unsigned long long *)&P.resign_stats[AZH_RESIGN_STAT_PLAYTHROUGH], 1ull);
+                            if (fired != 0u)
+                                atomicAdd((unsigned long long *)&P.resign_stats[AZH_RESIGN_STAT_FIRED], 1ull);
+                            if (fired != 0u && (u32)result != 3u - fired)
+                                atomicAdd((unsigned long long *)&P.resign_stats[AZH_RESIGN_STAT_FALSE], 1ull);
+                        }
+                    }
+                }
             }
             u32 pos = 8;
             for (int p = p0; p < s.ply; p++) {
@@ -708,14 +794,18 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
             st_ring = 1;
         }
         st_dropped = cut ? 1 : 0;  // arena: "invalid" -> annulled (uai_ringmaster.py:147-150)
-        init_game<PRUNE>(P, g, s.uid + (u32)P.G, s, s_moves);
+        init_game<OWN>(P, g, s.uid + (u32)P.G, s, s_moves);
     } else if (cut) {
         st_dropped = 1;  // null-result games are skipped (:628-631)
         drop_marker();
-        init_game<PRUNE>(P, g, s.uid + (u32)P.G, s, s_moves);
+        init_game<OWN>(P, g, s.uid + (u32)P.G, s, s_moves);
     } else {
         s.phase = 0;
         begin_ply(P, g, s.uid, s.ply);
+        if constexpr (OWN) {
+            if (P.resign_plies != 0u && lane == 0)
+                P.resign_state[g] = rs_word;
+        }
     }
     if (lane == 0) {
         P.force[g] = 0;

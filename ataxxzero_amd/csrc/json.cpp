@@ -208,11 +208,16 @@ static void append_double(double v, std::string &out)
 // result, words, random_ply + 1 (0 = none), kind (1 dropped, 2 partial; | 4: playout cap on; | 8: forced playouts on, the
 // counts of the plies it acts on are the pruned ones — nothing here depends on it)} then per ply {x lo, x hi,
 // o lo, o hi, move | nd << 16, full (playout cap: 1 = searched in full), nd x (move | visits << 16)}.
+// kind | 16: the game was played with the search value recorded (azh_engine_set_resign): word 5 of a ply is the f32 bits of
+// q = W_b / n_b of the most visited root edge (in [0, 1], for the mover) with the sign bit = searched in full, and the line
+// gains "values" (2 q - 1 as a double; a q that is not finite reads 0); | 32: the game ended by resignation, the line gains
+// "resigned" (the side that resigned, 3 - result: the mover of the last ply).
 // with_ids (arena): two extra keys, "slot" and "uid", so the caller can tell which net had x.
 std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_ids)
 {
     const uint32_t plies = rec[3], result = rec[4];
-    std::string boards = "[", dists = "[", moves = "[", full = "[";
+    std::string boards = "[", dists = "[", moves = "[", full = "[", values = "[";
+    const bool valued = (rec[7] & 16u) != 0;  // REC_KIND_VALUES: word 5 of a ply = bits of q | full << 31
     const bool capped = (rec[7] & 4u) != 0;  // playout cap (engine_device.h REC_KIND_PLAYOUT_CAP): word 5 of a ply = searched in full
     size_t pos = 8;
     for (uint32_t p = 0; p < plies && pos + 6 <= words; p++) {
@@ -224,8 +229,15 @@ std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_id
             dists += ',';
             moves += ',';
             full += ',';
+            values += ',';
         }
-        full += rec[pos + 5] ? '1' : '0';
+        full += (valued ? rec[pos + 5] >> 31 : rec[pos + 5]) ? '1' : '0';
+        if (valued) {
+            const uint32_t qb = rec[pos + 5] & 0x7FFFFFFFu;
+            float q;
+            memcpy(&q, &qb, 4);
+            append_double(std::isfinite(q) ? 2.0 * (double)q - 1.0 : 0.0, values);
+        }
         boards += '[';
         for (int y = 0; y < 7; y++)
             for (int xx = 0; xx < 7; xx++) {
@@ -264,9 +276,13 @@ std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_id
                       "],\"moves\":" + moves + "],\"result\":";
     if (rec[6])  // ONE_RANDOM_MOVE games (cpp/self_play_client.cpp:517); keys stay sorted as nlohmann emits them
         out = out.substr(0, out.size() - 9) + "\"random_ply\":" + std::to_string(rec[6] - 1) + ",\"result\":";
+    if (rec[7] & 32u)  // REC_KIND_RESIGNED
+        out = out.substr(0, out.size() - 9) + "\"resigned\":" + std::to_string(3u - result) + ",\"result\":";
     out += std::to_string(result);
     if (with_ids)
         out += ",\"slot\":" + std::to_string(rec[1]) + ",\"uid\":" + std::to_string(rec[2]);
+    if (valued)
+        out += ",\"values\":" + values + "]";
     out += '}';
     return out;
 }
@@ -286,7 +302,7 @@ bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plie
     if (rec[7] == 1)  // the marker a dropped game leaves: a header and nothing else
         return rec[5] == 8;
     *why = "header fields out of range";
-    if ((rec[7] & ~12u) > 2 || (rec[7] & 3u) == 1 || rec[4] > 2 || (max_plies && rec[3] > max_plies))
+    if ((rec[7] & ~60u) > 2 || (rec[7] & 3u) == 1 || rec[4] > 2 || (max_plies && rec[3] > max_plies))
         return false;
     *why = "a ply runs past the record's words";
     size_t pos = 8;

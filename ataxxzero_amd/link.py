@@ -137,6 +137,9 @@ SIGNATURES = {
     "azh_forced_prune": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _f32, _f32, _vp]),
     "azh_engine_set_random_symmetry": (ctypes.c_int, [_vp, ctypes.c_int]),
     "azh_eval_symmetry": (ctypes.c_int, [_u64, ctypes.c_uint32, _u64, _u64]),
+    "azh_engine_set_resign": (ctypes.c_int, [_vp, _f32, ctypes.c_int, ctypes.c_int]),
+    "azh_resign_playthrough": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32]),
+    "azh_engine_resign_stats": (ctypes.c_int, [_vp, _vp]),
     "azh_symmetry_board": (_u64, [ctypes.c_int, _u64]),
     "azh_symmetry_move": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint16]),
     "azh_symmetry_policy_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
@@ -275,6 +278,12 @@ def eval_symmetry(seed, uid, mover, opponent):
     """Random symmetry per evaluation (Engine.set_random_symmetry): the symmetry 0..7 under which the position (mover,
     opponent) of game `uid` of an engine with `seed` is evaluated (azh_eval_symmetry; host arithmetic, no GPU needed)."""
     return int(load().azh_eval_symmetry(int(seed), int(uid), int(mover), int(opponent)))
+
+
+def resign_playthrough(seed, uid, per_65536):
+    """Resignation (Engine.set_resign): 1 if game `uid` of an engine with `seed` is a play-through game — it runs to its real
+    end whatever the rule says — else 0 (azh_resign_playthrough; host arithmetic, no GPU needed)."""
+    return int(load().azh_resign_playthrough(int(seed), int(uid), int(per_65536)))
 
 
 def symmetry_board(s, bitboard):
@@ -511,6 +520,22 @@ class Engine:
         drawn per (seed, uid, position) — link.eval_symmetry — and its logits come back through that symmetry's move map;
         leaves() / batch_leaves() / leaf_features() return the image.  No tower work is added.  Between iterations only."""
         check(load().azh_engine_set_random_symmetry(self.h, 1 if on else 0))
+
+    def set_resign(self, q_below, consecutive, playthrough_per_65536):
+        """The search's value in the game records, and resignation: every ply's record carries q = W_b / n_b of
+        the most visited root edge (game lines gain "values"), and a game whose mover had `consecutive` counted plies in a row
+        with q < q_below ends there, result = 3 - mover (the line gains "resigned") — unless it is a play-through game, a share
+        playthrough_per_65536 / 65536 drawn per uid (link.resign_playthrough).  consecutive = 0: off; q_below = 0 records
+        values and never resigns.  Between iterations only."""
+        check(load().azh_engine_set_resign(self.h, float(q_below), int(consecutive), int(playthrough_per_65536)))
+
+    def resign_stats(self):
+        """-> {"resigned", "playthrough", "playthrough_fired", "playthrough_false"}: games resigned; play-through games
+        finished; those in which the rule fired; of those, the ones the side it fired for did not lose."""
+        out = np.zeros(4, dtype=np.uint64)
+        check(load().azh_engine_resign_stats(self.h, _ptr(out)))
+        return {"resigned": int(out[0]), "playthrough": int(out[1]), "playthrough_fired": int(out[2]),
+                "playthrough_false": int(out[3])}
 
     def set_thin_batches(self, mode):
         """0: the 3-board tower; 1: one board per workgroup (a handful of leaves per iteration); -1: by the engine's size."""

@@ -87,11 +87,14 @@ class SelfPlay:
 
     `random_symmetry` turns the random symmetry per evaluation on in every half-batch engine
     (link.Engine.set_random_symmetry): every leaf goes to the net as its image under a symmetry drawn per (seed, uid,
-    position); the start position's blockers must be their own image under all 8 symmetries."""
+    position); the start position's blockers must be their own image under all 8 symmetries.
+
+    `resign` = (q_below, consecutive, playthrough_fraction) turns the recorded search value and resignation on in every
+    half-batch engine (link.Engine.set_resign); (0, 1, 0) records values and never resigns."""
 
     def __init__(self, conv_weights, bn_params, games, visits, dtype="bf16", seed=DEFAULT_SEED,
                  fen=START_FEN_SELFPLAY, streams=1, fast_visits=0, full_fraction=0.25, forced_playouts=0.0,
-                 random_symmetry=False, **cfg):
+                 random_symmetry=False, resign=None, **cfg):
         self.dtype = link.DTYPES[dtype]
         self.net = link.Net(conv_weights, bn_params, model.BN_EPSILON)
         if streams < 1 or games < streams:
@@ -108,6 +111,8 @@ class SelfPlay:
             self.set_forced_playouts(forced_playouts)
         if random_symmetry:
             self.set_random_symmetry(True)
+        if resign:
+            self.set_resign(*resign)
 
     def run(self, iterations):
         # every engine's whole run is enqueued on its own stream (the calls are asynchronous): the half-batches then
@@ -142,6 +147,18 @@ class SelfPlay:
         """The random symmetry per evaluation in every half-batch engine."""
         for e in self.engines:
             e.set_random_symmetry(on)
+
+    def set_resign(self, q_below, consecutive, playthrough_fraction=0.1):
+        """The recorded search value and resignation in every half-batch engine; consecutive = 0 turns them off."""
+        for e in self.engines:
+            e.set_resign(q_below, consecutive, link.full_per_65536(playthrough_fraction))
+
+    def resign_stats(self):
+        total = {}
+        for e in self.engines:
+            for k, v in e.resign_stats().items():
+                total[k] = total.get(k, 0) + v
+        return total
 
     def set_thin_batches(self, mode):
         """1: the towers run one board per workgroup (a handful of leaves per iteration: the tail of a run under a game

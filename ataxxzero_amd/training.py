@@ -118,7 +118,17 @@ def _draw_ply(entry):
     return full[random.randrange(len(full))] if full else None
 
 
-def get_sample_from_entries(entries):
+def _value_target(entry, ply, mover, value_blend):
+    """The value target of a sample: the game result z seen by the mover, +-1 — or, with value_blend = L != 0 and an entry that
+    carries "values" (the search's own value at every ply, the mover's expectation in [-1, 1]), the blend
+    (1 - L) * z + L * values[ply] in Python floats."""
+    z = 1 if entry["result"] == mover else -1
+    if value_blend and "values" in entry:
+        return (1 - value_blend) * z + value_blend * entry["values"][ply]
+    return z
+
+
+def get_sample_from_entries(entries, value_blend=0.0):
     """One training sample (train.py:43-77).  The draws from `random` come in the reference's order — game, ply,
     symmetry — so a games file yields the same minibatches as there."""
     while True:
@@ -133,7 +143,7 @@ def get_sample_from_entries(entries):
         mover = 1 + ply % 2                         # x (1) moves on even plies
         symmetry_index = random.randrange(8)
         features = apply_symmetry(symmetry_index, board_to_features(entry["boards"][ply], mover))
-        value = [1 if entry["result"] == mover else -1]
+        value = [_value_target(entry, ply, mover, value_blend)]
         return features, _policy_target(entry, ply, symmetry_index), value
 
 
@@ -149,11 +159,11 @@ def load_entries(paths):
     return entries
 
 
-def make_minibatch_reference(entries, size):
+def make_minibatch_reference(entries, size, value_blend=0.0):
     """`size` samples drawn one by one with get_sample_from_entries (train.py:123-130)."""
     feats, pols, vals = [], [], []
     for _ in range(size):
-        f, p, v = get_sample_from_entries(entries)
+        f, p, v = get_sample_from_entries(entries, value_blend)
         feats.append(f)
         pols.append(p)
         vals.append(v)
@@ -233,15 +243,15 @@ def _entry_arrays(entry):
     return cache
 
 
-def make_minibatch(entries, size):
+def make_minibatch(entries, size, value_blend=0.0):
     """The same `size` samples as make_minibatch_reference — same draws from `random` in the same order, bit-identical
     arrays (tests/test_training.py) — assembled with array operations instead of per-sample Python: the sample pipeline,
-    not the GPU step, bounded train.py's rate."""
+    not the GPU step, bounded train.py's rate.  value_blend: _value_target."""
     global _TABLES
     if _TABLES is None:
         _TABLES = _symmetry_tables()
     cell_src, policy_to = _TABLES
-    cells, movers, syms, results, rows, pidx, pw = [], [], [], [], [], [], []
+    cells, movers, syms, targets, rows, pidx, pw = [], [], [], [], [], [], []
     while len(cells) < size:
         entry = random.choice(entries)                      # the reference's draws, in its order (train.py:45-60)
         ply = _draw_ply(entry)
@@ -260,7 +270,7 @@ def make_minibatch(entries, size):
         cells.append(c[ply])
         movers.append(1 + ply % 2)
         syms.append(sym)
-        results.append(entry["result"])
+        targets.append(_value_target(entry, ply, 1 + ply % 2, value_blend))
     cells = np.stack(cells)
     movers = np.asarray(movers, dtype=np.int8)[:, None]
     shown = np.take_along_axis(cells, cell_src[np.asarray(syms)], axis=1)        # [b][x * 7 + y]
@@ -272,7 +282,7 @@ def make_minibatch(entries, size):
     np.add.at(pols, (np.concatenate(rows), np.concatenate(pidx)), np.concatenate(pw))
     if (np.abs(1 - pols.sum(axis=1)) >= 1e-3).any():
         raise AssertionError("policy target does not sum to one")
-    vals = np.where(np.asarray(results)[:, None] == movers, 1, -1).astype(np.float32)
+    vals = np.asarray(targets, dtype=np.float32)[:, None]
     return feats.reshape(size, BOARD, BOARD, 4), pols.reshape(size, BOARD, BOARD, MOVE_TYPES), vals
 
 
@@ -346,7 +356,7 @@ def losses(net, features, policies, values):
 
 
 def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learning_rate=0.001, blocks=12, filters=128,
-          reference_bn_affine=False, device=None, log=print):
+          reference_bn_affine=False, device=None, log=print, value_blend=0.0):
     random.seed(123456789)                                                # train.py:103
     entries = load_entries(games_paths)
     ply_count = sum(len(e["moves"]) for e in entries)
@@ -371,7 +381,7 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
         return tuple(torch.from_numpy(a).to(device) for a in batch)
 
     random.seed(123456789)                                                # train.py:131
-    val_set = to_dev(make_minibatch(test_entries, 2048))
+    val_set = to_dev(make_minibatch(test_entries, 2048, value_blend))
     log("")
     log("Model dimensions: %i filters, %i blocks, %i parameters." % (
         filters, blocks, sum(int(np.prod(a.shape)) for a in cw)))
@@ -384,7 +394,7 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
                 pl, vl, _ = losses(net, *val_set)
             log("Step: %4i -- loss: %.6f  (policy: %.6f  value: %.6f)" % (step_number, float(pl + vl), float(pl), float(vl)))
         net.train()
-        batch = to_dev(make_minibatch(train_entries, minibatch_size))
+        batch = to_dev(make_minibatch(train_entries, minibatch_size, value_blend))
         pl, vl, reg = losses(net, *batch)
         opt.zero_grad(set_to_none=True)
         (pl + vl + reg).backward()

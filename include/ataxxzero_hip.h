@@ -350,6 +350,44 @@ int azh_symmetry_move(int s, uint16_t move);
  * outside 0..832.  Host arithmetic only. */
 int azh_symmetry_policy_index(int s, int index);
 
+/* The search's own value in the game record, and resignation of decided games (an extension, off by default; AlphaGo Zero /
+ * AlphaZero resign decided self-play games and keep a share that never resigns, from which the threshold's false-positive
+ * rate is measured).  consecutive = 0 switches the mode off (the state after create); else 1 <= consecutive <= 255,
+ * 0 <= q_below < 1 and 0 <= playthrough_per_65536 <= 65536.
+ * THE PLY'S VALUE q, when the device plays a move: b = the root edge with the most visits (ties: the lowest index),
+ * q = W_b / (float)n_b, one IEEE f32 division of the edge's total score (azh_engine_root_report's W, in [0, 1] per visit for
+ * the side to move) by its visits; a root without a visited edge has q = 0.5f, and such a ply neither counts nor resets.
+ * q is never negative under a finite evaluator; its sign bit is dropped (the record has no room for it) before the rule
+ * sees it, so the rule is a pure function of the record and no value that is not finite is ever below.
+ * THE RULE: a ply COUNTS unless the playout cap is on and the ply is FAST.  Each side has a counter of its own consecutive
+ * counted plies with q < q_below (the plain IEEE <: a NaN is never below; q_below = 0 records values and never resigns); a
+ * counted ply with q >= q_below (or NaN) resets the mover's counter.  The rule FIRES at a ply after which the mover's
+ * counter is >= consecutive (a counter stops at 255).
+ * Game `uid` is a PLAY-THROUGH game iff (philox(seed; uid, 0, 6, 0).v[0] >> 16) < playthrough_per_65536 (stream 6 is drawn
+ * from by nothing else, so no other random number moves; azh_resign_playthrough restates it): it runs to its real end
+ * whatever the rule says.  In any other game the ply at which the rule fires is recorded as usual — board, visit
+ * distribution, the sampled move, q — and the game ends there with result = 3 - mover (mover 1: x): the sampled move is not
+ * played, no re-root is done, and the slot restarts exactly as after a finished game (ring record, AZH_STAT_GAMES, a fresh
+ * game with uid + games).
+ * THE RECORD of a game finished while the mode is on carries bit 4 (value 16) in header word 7, and word 5 of each ply is
+ * (bits(q) & 0x7FFFFFFF) | (0x80000000 if the playout cap is on and the ply is FULL); a resigned game's carries bit 5
+ * (value 32) too.  The line gains "values": [2 q - 1, ...] (the mover's expectation in [-1, 1], one per ply; a q that is not
+ * finite reads 0) after "result" and, resigned, "resigned": 3 - result, the side that gave up.  Plies played before the
+ * mode was switched on read q = 0.  Sampling, re-root, evaluation cache, select budget, the K-leaf search, the solver,
+ * forced playouts and random symmetry are untouched, and with the mode off every state, tree and record word and every
+ * output byte is what it was.
+ * Refused (the engine stays as it was) with AZH_FLAG_TWO_NETS and AZH_FLAG_ONE_RANDOM_MOVE, and while a selected batch
+ * awaits its backup.  Call before the first select or between iterations; setting it clears every slot's counters.
+ * Definition and measurements: DESIGN.md, "Recorded search value and resignation". */
+int azh_engine_set_resign(azh_engine *e, float q_below, int consecutive, int playthrough_per_65536);
+/* Is game `uid` of an engine created with `seed` a play-through game?  1 / 0.  Host arithmetic only. */
+int azh_resign_playthrough(uint64_t seed, uint32_t uid, uint32_t playthrough_per_65536);
+/* Once-per-game counts since the engine was created: [0] games resigned, [1] play-through games finished, [2] of those, the
+ * games in which the rule fired, [3] of those, the games the side it first fired for did NOT lose (the false positives). */
+enum { AZH_RESIGN_STAT_RESIGNED = 0, AZH_RESIGN_STAT_PLAYTHROUGH = 1, AZH_RESIGN_STAT_FIRED = 2, AZH_RESIGN_STAT_FALSE = 3,
+       AZH_RESIGN_STAT_COUNT = 4 };
+int azh_engine_resign_stats(azh_engine *e, uint64_t *out /* [AZH_RESIGN_STAT_COUNT] */);
+
 /* Proven wins and losses in the tree (MCTS-solver; an extension, off by default; DESIGN.md, "Proven wins and losses").
  * A node is DECIDED if it is a finished position or was PROVEN: after every batch's backup, for each path that ended at a
  * decided node, the node's parent is a proven win (+1 for its side to move) if one of its children is decided with -1, and
