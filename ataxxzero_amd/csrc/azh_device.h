@@ -471,6 +471,48 @@ __host__ __device__ inline void forced_prune_root(const float *prior, const floa
         out[j] = (j == b || n[j] == 0u) ? n[j] : forced_prune_edge(fabsf(prior[j]), W[j], n[j], N, k, c_puct, sq, S);
 }
 
+// Temperature of the move played (azh_engine_set_temperature; DESIGN.md, "Temperature of the move and of the root policy").
+// The fixed-point weight of a root edge with n visits when the most visited edge has exp(log_nmax) of them: (n / n_max)^(1/T)
+// in units of 2^-20, from det_logf / det_expf and one IEEE f32 division, so host and device agree to the bit and the sum of
+// the weights is an integer that no summation order changes.  The best edge weighs exactly 2^20 (det_expf(0) is 1).
+constexpr u32 TEMPERATURE_ONE = 1048576u;
+__host__ __device__ inline u32 temperature_weight(u32 n, float log_nmax, float T)
+{
+#pragma clang fp contract(off)
+    if (n == 0u)
+        return 0u;
+    const float d = fminf(det_logf((float)n) - log_nmax, 0.0f);
+    const float w = det_expf(d / T);
+    const u32 q = (u32)(w * 1048576.0f);
+    return q < TEMPERATURE_ONE ? q : TEMPERATURE_ONE;
+}
+// The choice of a whole root on the host (azh_temperature_pick): advance_game holds the wave's.  v0: word 0 of the ply's
+// sampling block.  q (or null) receives the weights the choice was made on: T == 1 the raw counts (today's proportional draw),
+// T == 0 2^20 at the first maximum and 0 elsewhere, else temperature_weight.  A root without a visit yields edge 0.
+__host__ __device__ inline int temperature_pick_root(const u32 *n, int M, float T, u32 v0, u32 *q)
+{
+    int b = 0;
+    for (int j = 1; j < M; j++)
+        if (n[j] > n[b])
+            b = j;
+    const float lmax = M > 0 ? det_logf((float)n[b]) : 0.0f;
+    u32 S = 0;
+    for (int j = 0; j < M; j++)
+        S += T == 1.0f ? n[j] : (T == 0.0f ? (j == b ? TEMPERATURE_ONE : 0u) : temperature_weight(n[j], lmax, T));
+    const u32 r = (u32)(((u64)v0 * (u64)S) >> 32);
+    int chosen = -1;
+    u32 cum = 0;
+    for (int j = 0; j < M; j++) {
+        const u32 w = T == 1.0f ? n[j] : (T == 0.0f ? (j == b ? TEMPERATURE_ONE : 0u) : temperature_weight(n[j], lmax, T));
+        if (q)
+            q[j] = w;
+        cum += w;
+        if (chosen < 0 && cum > r)
+            chosen = j;
+    }
+    return chosen < 0 ? 0 : chosen;
+}
+
 // ---------------------------------------------------------------- random symmetry per evaluation
 // azh_engine_set_random_symmetry ("Random symmetry per evaluation"): every position goes to the evaluator as its
 // image under one of the 8 dihedral symmetries of the board, and the logits come back through the same symmetry's move map.

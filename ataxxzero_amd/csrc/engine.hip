@@ -696,13 +696,22 @@ __device__ inline void apply_priors(const EngineParams &P, const Arena &A, int n
             for (int k = 0; k < 4; k++)
                 pr[k] = ex[k] / den;
         } else {
+            // the root policy's temperature (azh_engine_set_temperature): at the root of a noise ply whose entry R is not 1
+            // every legal move's logit is multiplied by 1 / R before the maximum is taken; the multiply by 1.0f everywhere
+            // else leaves every logit's bits as they are
+            float inv = 1.0f;
+            if (root && P.root_policy_temperature != nullptr) {
+                const float R = P.root_policy_temperature[ply];
+                if (R != 1.0f)
+                    inv = 1.0f / R;
+            }
             float mx = -INFINITY;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const int j = lane + 64 * k;
                 l[k] = -INFINITY;
                 if (k < rounds && j < M) {
-                    l[k] = row[logit_index(A.em[first + j])];
+                    l[k] = row[logit_index(A.em[first + j])] * inv;
                     if (l[k] > mx)
                         mx = l[k];
                 }
@@ -1243,6 +1252,8 @@ struct azh_engine {
     int *d_play_status = nullptr;
     u32 *d_report = nullptr;       // azh_engine_root_report: [G][AZH_ROOT_REPORT_WORDS], allocated by the first call
     u64 *d_stat_out = nullptr;
+    float *d_move_temperature = nullptr, *d_root_policy_temperature = nullptr;  // azh_engine_set_temperature: [max_plies] each,
+                                                                                // allocated by the first call that brings one
     // finished games formatted but not yet handed out
     std::vector<std::string> pending;
     size_t pending_pos = 0;
@@ -1621,9 +1632,10 @@ struct RunLoop {
     azh_net *net_a, *net_b;
     int dtype, iterations;
     bool pair = false;
-    bool own = false;  // forced playouts, random symmetry, recorded values and resignation: the queued moves in a k_advance_list launch of their own, on the engine's
-                       // stream, in front of the tower (the tower kernels' advance_game records no pruned counts, writes no
-                       // key word and knows no ply value: engine_device.h)
+    bool own = false;  // forced playouts, random symmetry, recorded values and resignation, a move temperature: the queued moves in a
+                       // k_advance_list launch of their own, on the engine's stream, in front of the tower (the tower kernels'
+                       // advance_game records no pruned counts, writes no key word and knows no ply value and no temperature:
+                       // engine_device.h)
     AdvanceHook hook;
 
     int begin()
@@ -1632,7 +1644,7 @@ struct RunLoop {
         const char *pair_s = getenv("AZH_ARENA_PAIR");  // (read per call: a test switches it inside one process)
         const bool pair_env = !(pair_s && atoi(pair_s) == 0);
         pair = pair_env && two_lists(e) && !(e->P.flags & AZH_FLAG_SYMMETRY_AVG);
-        own = e->P.forced_k != 0.0f || e->P.random_symmetry != 0u || e->P.resign_plies != 0u;
+        own = e->P.forced_k != 0.0f || e->P.random_symmetry != 0u || e->P.resign_plies != 0u || e->P.move_temperature != nullptr;
         hook.workers = e->adv_workers;
         hook.at_head = 1;   // (decided per launch by the tower's launch functions: in front only where workgroups queue for slots)
         hook.P = e->P;
@@ -2034,6 +2046,65 @@ extern "C" int azh_engine_set_resign(azh_engine *e, float q_below, int consecuti
     e->P.resign_plies = (u32)consecutive;
     e->P.resign_through = (u32)playthrough_per_65536;
     return 0;
+}
+
+// Per-ply temperature of the move played and of the root policy.  Definition: the header and DESIGN.md.  Between iterations
+// only.  Every check comes before the first change, so a refused call leaves the engine as it was.
+static bool temperature_entry_ok(float t, bool move)
+{
+    if (move)
+        return t == 0.0f || (t >= 1.0f / 64.0f && t <= 64.0f);  // (false for a NaN)
+    return t >= 0.25f && t <= 64.0f;
+}
+
+extern "C" int azh_engine_set_temperature(azh_engine *e, const float *move_temperature, const float *root_policy_temperature)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_set_temperature: null engine");
+    const int n = e->P.max_plies;
+    for (int p = 0; move_temperature && p < n; p++)
+        if (!temperature_entry_ok(move_temperature[p], true))
+            return azh_fail(-2, "azh_engine_set_temperature: move_temperature[%d] = %g: need 0 or 1/64 <= T <= 64", p,
+                            (double)move_temperature[p]);
+    for (int p = 0; root_policy_temperature && p < n; p++)
+        if (!temperature_entry_ok(root_policy_temperature[p], false))
+            return azh_fail(-2, "azh_engine_set_temperature: root_policy_temperature[%d] = %g: need 1/4 <= R <= 64", p,
+                            (double)root_policy_temperature[p]);
+    if (e->selected)
+        return azh_fail(-3, "azh_engine_set_temperature: a selected batch awaits its backup");
+    const u32 bad = AZH_FLAG_ONE_RANDOM_MOVE | AZH_FLAG_SAMPLE_POW5 | AZH_FLAG_PY_POSTERIOR | AZH_FLAG_TWO_NETS;
+    if ((move_temperature || root_policy_temperature) && (e->P.flags & bad))
+        return azh_fail(-4, "azh_engine_set_temperature: not supported with %s",
+                        (e->P.flags & AZH_FLAG_ONE_RANDOM_MOVE) ? "AZH_FLAG_ONE_RANDOM_MOVE"
+                        : (e->P.flags & AZH_FLAG_SAMPLE_POW5)   ? "AZH_FLAG_SAMPLE_POW5"
+                        : (e->P.flags & AZH_FLAG_PY_POSTERIOR)  ? "AZH_FLAG_PY_POSTERIOR"
+                                                                : "AZH_FLAG_TWO_NETS");
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    // the engine's two tables are allocated once and kept; a null argument only takes the pointer out of the parameters
+    if (move_temperature && !e->d_move_temperature && dev_alloc(e, &e->d_move_temperature, (size_t)n))
+        return -1;
+    if (root_policy_temperature && !e->d_root_policy_temperature && dev_alloc(e, &e->d_root_policy_temperature, (size_t)n))
+        return -1;
+    if (move_temperature)
+        AZH_HIP(hipMemcpy(e->d_move_temperature, move_temperature, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    if (root_policy_temperature)
+        AZH_HIP(hipMemcpy(e->d_root_policy_temperature, root_policy_temperature, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    e->P.move_temperature = move_temperature ? e->d_move_temperature : nullptr;
+    e->P.root_policy_temperature = root_policy_temperature ? e->d_root_policy_temperature : nullptr;
+    return 0;
+}
+
+// The move a ply's temperature chooses from a root's visit counts: the device's choice restated on the host
+// (temperature_pick_root).  Returns the edge index; q_out (or null) receives the M weights.  Host arithmetic only.
+extern "C" int azh_temperature_pick(const uint32_t *visits, int M, float temperature, uint64_t seed, uint32_t uid, uint32_t ply,
+                                    uint32_t *q_out)
+{
+    if (!visits || M < 1 || M > MAX_MOVES)
+        return azh_fail(-1, "azh_temperature_pick: bad argument (need visits and 1 <= M <= %d)", MAX_MOVES);
+    if (!temperature_entry_ok(temperature, true))
+        return azh_fail(-2, "azh_temperature_pick: temperature %g: need 0 or 1/64 <= T <= 64", (double)temperature);
+    const Philox4 rr = philox((u32)seed, (u32)(seed >> 32), uid, ply, STREAM_SAMPLE, 0u);
+    return temperature_pick_root(visits, M, temperature, rr.v[0], q_out);
 }
 
 // Is game `uid` under `seed` a play-through game?  Host arithmetic only.

@@ -90,6 +90,10 @@ struct EngineParams {
     u32 *resign_state;        // [G] bits 0-7 / 8-15: the counter of side 1 / 2, bits 16-17: the side the rule first fired for;
                               // cleared where a game begins (begin_game_key's callers), written by k_advance_list's advance_game
     u64 *resign_stats;        // [AZH_RESIGN_STAT_COUNT] once-per-game counts (global atomics at a game's end)
+    // temperature of the move played and of the root policy (azh_engine_set_temperature), each off while null
+    const float *move_temperature;         // [max_plies] 1: the proportional draw, 0: the most visited move, else n^(1/T) in
+                                           // fixed point (temperature_weight); read by k_advance_list's advance_game alone
+    const float *root_policy_temperature;  // [max_plies] apply_priors divides the logits of a noise ply's root by this
 };
 
 constexpr u32 PLY_FULL = 0x80000000u;
@@ -499,6 +503,52 @@ __device__ inline int record_pruned_counts(const EngineParams &P, const Arena &A
     return nd;
 }
 
+// The move of a ply whose temperature T is not 1 (azh_engine_set_temperature; DESIGN.md, "Temperature of the move and of the
+// root policy"): the wave's form of temperature_pick_root.  nv: this lane's visit counts of root edges lane + 64 k (0 beyond
+// M), v0: word 0 of the ply's sampling block.  T == 0: the most visited edge, the first on a tie; else the proportional scan
+// on the fixed-point weights q in place of the counts.
+__device__ inline int tempered_choice(const u32 (&nv)[4], int M, float T, u32 v0)
+{
+    const int lane = lane_id();
+    u64 key = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int j = lane + 64 * k;
+        if (j < M) {
+            const u64 kk = ((u64)nv[k] << 32) | (u64)(0xFFFFFFFFu - (u32)j);
+            key = kk > key ? kk : key;
+        }
+    }
+    key = wave_max_u64(key);
+    if (M <= 0)
+        return 0;
+    if (T == 0.0f)
+        return (int)(0xFFFFFFFFu - (u32)key);
+    const float lmax = det_logf((float)(u32)(key >> 32));
+    u32 q[4];
+    u32 part = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        q[k] = lane + 64 * k < M ? temperature_weight(nv[k], lmax, T) : 0u;
+        part += q[k];
+    }
+    const u32 S = wave_sum_u32(part);  // <= 256 * 2^20
+    const u32 r = (u32)(((u64)v0 * (u64)S) >> 32);
+    int chosen = -1;
+    u32 run = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int j = lane + 64 * k;
+        const int incl = wave_incl_scan((int)q[k]);
+        const u32 cum = run + (u32)incl;
+        const u64 mask = __ballot(j < M && cum > r);
+        if (chosen < 0 && mask)
+            chosen = 64 * k + (__ffsll((long long)mask) - 1);
+        run += (u32)bcast_last(incl);
+    }
+    return chosen < 0 ? 0 : chosen;
+}
+
 // OWN: the instantiation of the move-playing launch of its own, k_advance_list: the one that can record pruned counts (forced
 // playouts), write a game's key word (random symmetry), and record the ply's value and resign (azh_engine_set_resign).  The
 // tower kernels carry the
@@ -508,7 +558,7 @@ __device__ inline int record_pruned_counts(const EngineParams &P, const Arena &A
 // it sent k_tower2<1, false> and <2, false> to scratch memory (12 bytes per lane, 2 VGPR spills;
 // profiles/random_symmetry.txt), so their instantiation starts games without it and that mode, too, plays its moves in
 // k_advance_list.  The ply's value, the resign rule and its once-per-game counts live in the OWN instantiation alone for the
-// same reason.
+// same reason, and so does the ply's move temperature (tempered_choice).
 template <bool OWN>
 __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
 {
@@ -580,16 +630,30 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
         chosen = (int)s_pref[0];
         wave_sync();
     } else {
-        u32 run = 0;
+        // the ply's temperature (azh_engine_set_temperature), in k_advance_list's instantiation alone: an entry of 1 is the
+        // draw below on the raw counts, any other one chooses on fixed-point weights
+        bool tempered = false;
+        if constexpr (OWN) {
+            if (P.move_temperature != nullptr) {
+                const float T = P.move_temperature[s.ply];
+                if (T != 1.0f) {
+                    tempered = true;
+                    chosen = tempered_choice(nv, M, T, rr.v[0]);
+                }
+            }
+        }
+        if (!tempered) {
+            u32 run = 0;
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int j = lane + 64 * k;
-            const int incl = wave_incl_scan((int)nv[k]);
-            const u32 cum = run + (u32)incl;
-            const u64 mask = __ballot(j < M && cum > r);
-            if (chosen < 0 && mask)
-                chosen = 64 * k + (__ffsll((long long)mask) - 1);
-            run += (u32)bcast_last(incl);
+            for (int k = 0; k < 4; k++) {
+                const int j = lane + 64 * k;
+                const int incl = wave_incl_scan((int)nv[k]);
+                const u32 cum = run + (u32)incl;
+                const u64 mask = __ballot(j < M && cum > r);
+                if (chosen < 0 && mask)
+                    chosen = 64 * k + (__ffsll((long long)mask) - 1);
+                run += (u32)bcast_last(incl);
+            }
         }
     }
     if (chosen < 0)

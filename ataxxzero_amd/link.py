@@ -140,6 +140,8 @@ SIGNATURES = {
     "azh_engine_set_resign": (ctypes.c_int, [_vp, _f32, ctypes.c_int, ctypes.c_int]),
     "azh_resign_playthrough": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32]),
     "azh_engine_resign_stats": (ctypes.c_int, [_vp, _vp]),
+    "azh_engine_set_temperature": (ctypes.c_int, [_vp, _vp, _vp]),
+    "azh_temperature_pick": (ctypes.c_int, [_vp, ctypes.c_int, _f32, _u64, ctypes.c_uint32, ctypes.c_uint32, _vp]),
     "azh_symmetry_board": (_u64, [ctypes.c_int, _u64]),
     "azh_symmetry_move": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint16]),
     "azh_symmetry_policy_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
@@ -284,6 +286,18 @@ def resign_playthrough(seed, uid, per_65536):
     """Resignation (Engine.set_resign): 1 if game `uid` of an engine with `seed` is a play-through game — it runs to its real
     end whatever the rule says — else 0 (azh_resign_playthrough; host arithmetic, no GPU needed)."""
     return int(load().azh_resign_playthrough(int(seed), int(uid), int(per_65536)))
+
+
+def temperature_pick(visits, temperature, seed, uid, ply, weights=False):
+    """Temperature of the move played (Engine.set_temperature): the root edge chosen from the visit counts `visits` (in edge
+    order) at `temperature` for ply `ply` of game `uid` of an engine with `seed`; with `weights` -> (edge, the (M,) u32
+    fixed-point weights the choice was made on) (azh_temperature_pick; host arithmetic, no GPU needed)."""
+    visits = np.ascontiguousarray(visits, dtype=np.uint32)
+    q = np.zeros(len(visits), dtype=np.uint32) if weights else None
+    j = load().azh_temperature_pick(_ptr(visits), len(visits), float(temperature), int(seed), int(uid), int(ply), _ptr(q))
+    if j < 0:
+        check(j)
+    return (int(j), q) if weights else int(j)
 
 
 def symmetry_board(s, bitboard):
@@ -528,6 +542,23 @@ class Engine:
         playthrough_per_65536 / 65536 drawn per uid (link.resign_playthrough).  consecutive = 0: off; q_below = 0 records
         values and never resigns.  Between iterations only."""
         check(load().azh_engine_set_resign(self.h, float(q_below), int(consecutive), int(playthrough_per_65536)))
+
+    def set_temperature(self, move_temperature=None, root_policy_temperature=None):
+        """Per-ply temperature of the move played and of the root policy: two tables of max_plies floats, or None
+        (off).  move_temperature[p] = 1 plays ply p in proportion to the visits, 0 the most visited move, T in [1/64, 64] in
+        proportion to visits^(1/T) (link.temperature_pick restates the choice); the recorded `dists` stay the search's.
+        root_policy_temperature[p] = R in [1/4, 64] divides the root's logits by R on the plies that get noise.
+        selfplay.temperature_table makes the tables.  Between iterations only."""
+        def table(t, name):
+            if t is None:
+                return None
+            t = np.ascontiguousarray(t, dtype=np.float32)
+            if t.shape != (self.cfg.max_plies,):
+                raise ValueError("%s must have max_plies = %d entries" % (name, self.cfg.max_plies))
+            return t
+        mt = table(move_temperature, "move_temperature")
+        rt = table(root_policy_temperature, "root_policy_temperature")
+        check(load().azh_engine_set_temperature(self.h, _ptr(mt), _ptr(rt)))
 
     def resign_stats(self):
         """-> {"resigned", "playthrough", "playthrough_fired", "playthrough_false"}: games resigned; play-through games

@@ -68,6 +68,48 @@ def select_device(index):
     return dev
 
 
+def temperature_table(max_plies, start, final=None, halflife=0.0, cutoff=None):
+    """A per-ply temperature schedule for link.Engine.set_temperature, (max_plies,) float32:
+    t(p) = final + (start - final) * 2 ** (-p / halflife) for halflife > 0, else start; t(p) = final for p >= cutoff where a
+    cutoff is given; computed in float64 and rounded to f32; a value below 1/64, the smallest temperature the engine draws
+    at, becomes 0 (the most visited move).  AlphaZero: (1, 0, cutoff=30); KataGo: (0.8, 0.2, halflife=board width)."""
+    final = start if final is None else final
+    p = np.arange(int(max_plies), dtype=np.float64)
+    t = final + (start - final) * 2.0 ** (-p / halflife) if halflife > 0 else np.full(int(max_plies), float(start))
+    if cutoff is not None:
+        t[p >= cutoff] = final
+    t = t.astype(np.float32)
+    t[t < np.float32(1.0 / 64.0)] = 0.0
+    return t
+
+
+def temperature_tables(max_plies, temperature=None, temperature_final=None, halflife=0.0, cutoff=None,
+                       root_policy_temperature=None, root_policy_temperature_final=1.0):
+    """The generator's temperature flags -> (move table or None, root policy table or None), or ValueError: the move's
+    temperature runs from `temperature` to `temperature_final` (default: the same), the root policy's from
+    `root_policy_temperature` to `root_policy_temperature_final` (default 1), both with `halflife` (0: no decay, the final
+    value then holds from `cutoff` on only); end points of 0 or in [1/64, 64] for the move, in [1/4, 64] for the policy."""
+    if not halflife >= 0.0 or (cutoff is not None and cutoff < 0):
+        raise ValueError("--temperature-halflife and --temperature-cutoff must not be negative")
+    if temperature is None and (temperature_final is not None or cutoff is not None):
+        raise ValueError("--temperature-final and --temperature-cutoff need --temperature")
+    if temperature is None and root_policy_temperature is None and halflife:
+        raise ValueError("--temperature-halflife needs --temperature or --root-policy-temperature")
+    move = root = None
+    if temperature is not None:
+        final = temperature if temperature_final is None else temperature_final
+        for t in (temperature, final):
+            if not (t == 0.0 or 1.0 / 64.0 <= t <= 64.0):
+                raise ValueError("--temperature and --temperature-final must be 0 or lie in [1/64, 64]")
+        move = temperature_table(max_plies, temperature, final, halflife, cutoff)
+    if root_policy_temperature is not None:
+        for t in (root_policy_temperature, root_policy_temperature_final):
+            if not 0.25 <= t <= 64.0:
+                raise ValueError("--root-policy-temperature and --root-policy-temperature-final must lie in [1/4, 64]")
+        root = temperature_table(max_plies, root_policy_temperature, root_policy_temperature_final, halflife, None)
+    return move, root
+
+
 class SelfPlay:
     """`games` concurrent MCTS self-play games on one GPU with the built-in net.
 
@@ -90,11 +132,14 @@ class SelfPlay:
     position); the start position's blockers must be their own image under all 8 symmetries.
 
     `resign` = (q_below, consecutive, playthrough_fraction) turns the recorded search value and resignation on in every
-    half-batch engine (link.Engine.set_resign); (0, 1, 0) records values and never resigns."""
+    half-batch engine (link.Engine.set_resign); (0, 1, 0) records values and never resigns.
+
+    `temperature` = (move table or None, root policy table or None), as temperature_tables makes them, sets the per-ply
+    temperature of the move played and of the root policy in every half-batch engine (link.Engine.set_temperature)."""
 
     def __init__(self, conv_weights, bn_params, games, visits, dtype="bf16", seed=DEFAULT_SEED,
                  fen=START_FEN_SELFPLAY, streams=1, fast_visits=0, full_fraction=0.25, forced_playouts=0.0,
-                 random_symmetry=False, resign=None, **cfg):
+                 random_symmetry=False, resign=None, temperature=None, **cfg):
         self.dtype = link.DTYPES[dtype]
         self.net = link.Net(conv_weights, bn_params, model.BN_EPSILON)
         if streams < 1 or games < streams:
@@ -113,6 +158,8 @@ class SelfPlay:
             self.set_random_symmetry(True)
         if resign:
             self.set_resign(*resign)
+        if temperature and (temperature[0] is not None or temperature[1] is not None):
+            self.set_temperature(*temperature)
 
     def run(self, iterations):
         # every engine's whole run is enqueued on its own stream (the calls are asynchronous): the half-batches then
@@ -152,6 +199,11 @@ class SelfPlay:
         """The recorded search value and resignation in every half-batch engine; consecutive = 0 turns them off."""
         for e in self.engines:
             e.set_resign(q_below, consecutive, link.full_per_65536(playthrough_fraction))
+
+    def set_temperature(self, move_temperature=None, root_policy_temperature=None):
+        """The per-ply temperature tables in every half-batch engine; None, None turns both off."""
+        for e in self.engines:
+            e.set_temperature(move_temperature, root_policy_temperature)
 
     def resign_stats(self):
         total = {}

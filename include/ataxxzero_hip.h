@@ -388,6 +388,45 @@ enum { AZH_RESIGN_STAT_RESIGNED = 0, AZH_RESIGN_STAT_PLAYTHROUGH = 1, AZH_RESIGN
        AZH_RESIGN_STAT_COUNT = 4 };
 int azh_engine_resign_stats(azh_engine *e, uint64_t *out /* [AZH_RESIGN_STAT_COUNT] */);
 
+/* Temperature of the move played and of the root policy, per ply (an extension, off by default; AlphaZero plays
+ * proportionally to the visits for 30 plies and then the most visited move, KataGo decays a temperature from 0.8 to 0.2 and
+ * flattens the policy of the roots that get noise, 1.25 -> 1.1).  Each argument is a table of max_plies floats, copied, or
+ * NULL: that part is off.  Both NULL is the state after create, and every byte the engine then produces is what it produced
+ * before the call existed.
+ * THE MOVE, when the device plays the move of ply p (azh_engine_run and the step-wise calls alike; not
+ * azh_engine_play_moves), T = move_temperature[p]:
+ *   T == 1: the proportional draw on the raw visit counts, untouched: a table of ones plays the games of no table.
+ *   T == 0: the most visited root edge, the first one in edge order on a tie.
+ *   else (1/64 <= T <= 64), in fixed point: n_max = the largest visit count of the root's edges; an edge with n_j >= 1 visits
+ *     weighs q_j = min((uint32)(w * 1048576.0f), 1048576) with w = det_expf(d / T) (one IEEE f32 division) and
+ *     d = min(det_logf((float)n_j) - det_logf((float)n_max), 0.0f); an edge without a visit weighs 0; the most visited edges
+ *     weigh exactly 2^20.  S = sum of the q_j (<= 2^28), r = (uint32)(((uint64)v0 * S) >> 32) with v0 word 0 of
+ *     philox(seed; uid, p, 1, 0) — the block of the proportional draw — and the move is the first edge j in edge order with
+ *     q_0 + ... + q_j > r.  Integers throughout: no summation order changes the choice.
+ * Everything after the choice is unchanged: the ply's record holds the search's visit counts (raw, or pruned under forced
+ * playouts) — temperature changes the move, never the policy target — and the value, the resign rule and the re-root follow
+ * as before.  FAST plies of the playout cap take their entry like any other ply.  While a move table is set the device loop
+ * plays its queued moves in the move-playing launch of its own, as under forced playouts.
+ * THE ROOT POLICY: where a root's priors are made on a ply that gets the Dirichlet noise (every ply, or the FULL ones under
+ * the playout cap) and R = root_policy_temperature[ply] != 1, every legal move's logit is multiplied by 1.0f / R (one f32
+ * division per node, one f32 multiply per edge) before the softmax over the legal moves; maximum, det_expf, sum, division
+ * and the Dirichlet mix follow as before.  Other nodes, FAST plies and entries of 1 keep their priors bit for bit.  The
+ * K-leaf search (azh_engine_set_leaf_batch) does the same.
+ * Refused, the engine left as it was: an entry that is NaN or negative, a move temperature that is neither 0 nor in
+ * [1/64, 64] (one in (0, 1/64) is refused, not rounded), a root policy temperature outside [1/4, 64]; tables on an engine
+ * with AZH_FLAG_ONE_RANDOM_MOVE, AZH_FLAG_SAMPLE_POW5, AZH_FLAG_PY_POSTERIOR or AZH_FLAG_TWO_NETS; a call while a selected
+ * batch awaits its backup.  Call before the first select or between iterations.
+ * Definition and measurements: DESIGN.md, "Temperature of the move and of the root policy". */
+int azh_engine_set_temperature(azh_engine *e, const float *move_temperature /* [max_plies] or NULL */,
+                               const float *root_policy_temperature /* [max_plies] or NULL */);
+/* The edge the rule above chooses from the visit counts visits[M] (1 <= M <= 256, in edge order) at `temperature` for ply
+ * `ply` of game `uid` of an engine created with `seed`, restated on the host from the code the device runs; negative on a bad
+ * argument (the temperature's range is azh_engine_set_temperature's).  q_out, unless NULL, receives the M weights the choice
+ * was made on: the q_j above, at temperature 1 the visit counts themselves, at 0 2^20 for the chosen edge and 0 elsewhere.
+ * Visit counts that are all 0 yield edge 0.  Host arithmetic only. */
+int azh_temperature_pick(const uint32_t *visits, int M, float temperature, uint64_t seed, uint32_t uid, uint32_t ply,
+                         uint32_t *q_out);
+
 /* Proven wins and losses in the tree (MCTS-solver; an extension, off by default; DESIGN.md, "Proven wins and losses").
  * A node is DECIDED if it is a finished position or was PROVEN: after every batch's backup, for each path that ended at a
  * decided node, the node's parent is a proven win (+1 for its side to move) if one of its children is decided with -1, and
