@@ -70,7 +70,7 @@ class Match:
         self.openings = None
         self.opening_boards = None   # (pairs, 2) u64: the position after each pairing's opening
         self.limit = None        # set_game_limit: the size of the match
-        self.finished = 0        # games handed out so far
+        self.finished = 0        # games of the match handed out so far (under a limit: those with uid < limit)
         self.thin = False        # the tower runs one board per workgroup (the match's last games)
         if opening_depth > 0:
             # every pairing gets its own random opening, played both ways (uai_ringmaster.py:242-246): slots 2k and 2k + 1
@@ -121,7 +121,9 @@ class Match:
                 e["moves"] = opening + e["moves"]          # (boards[] starts after the opening; only its last entry is used)
             out.append({"moves": e["moves"], "result": e["result"], "white": white, "uid": e["uid"],
                         "final_score": replay_final_score(e), "boards": e["boards"], "opening": opening})
-        self.finished += len(out)
+        # only the cohort's games count (a game past the limit that had begun before the limit was set is still played to its
+        # end and handed out): the switch to thin batches is decided by the match, not by strays
+        self.finished += sum(1 for g in out if self.limit is None or g["uid"] < self.limit)
         self._pick_tower()
         return out
 
@@ -131,7 +133,11 @@ class Match:
         comes, and a loop `while handed_out < cohort` would then enqueue search for an idle engine for ever.  Call right
         after fetch(): the engine's streams are idle there (the call costs one small kernel and waits for nothing), and
         every game the counters know of has been taken off the device — so after the drain that follows, a game the engine
-        has ended and the host has not seen is a lost one."""
+        has ended and the host has not seen is a lost one.
+        The count rule (games + dropped >= limit) presupposes that the limit was set before the first run and has only been
+        raised since: then no game past it ever begins (a slot loaded by opening_depth past the limit stays idle,
+        azh_engine_set_game_limit), idle slots add nothing to any counter, and the two counters hold the cohort's games
+        alone.  A limit set or lowered while games past it are running lets those games count too."""
         st = self.engine.stats()
         if st["ring_overflow"] > 0:
             return "%d finished games did not fit the device's record ring and are lost" % st["ring_overflow"]

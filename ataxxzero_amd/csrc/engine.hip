@@ -72,7 +72,8 @@ __device__ inline u64 tree_stamp()
     return t;
 }
 
-// azh_engine_set_positions: every slot restarts at a given position and ply (fresh tree, uid = slot)
+// azh_engine_set_positions: every slot restarts at a given position and ply (fresh tree, uid = slot).  Under a game limit
+// the slots past it are loaded all the same and left idle, as k_limit_slots would leave them: either call order, one state.
 __global__ __launch_bounds__(WAVE) void k_init_positions(EngineParams P, const ulonglong2 *boards, const int *plies)
 {
     __shared__ u16 s_moves[MAX_MOVES];
@@ -80,23 +81,33 @@ __global__ __launch_bounds__(WAVE) void k_init_positions(EngineParams P, const u
     azh_game_state s;
     const ulonglong2 w = boards[g];
     init_game_at(P, g, (u32)g, s, s_moves, unpack_board(w.x, w.y), plies[g], 1);
+    if (P.uid_limit != 0u && (u32)g >= P.uid_limit)
+        s.phase = 3;
     if (threadIdx.x == 0)
         P.gs[g] = s;
 }
 
-// azh_engine_set_game_limit: a slot whose game is past the limit and has not begun goes idle; an idle slot whose game
-// is below a (raised) limit starts it
+// azh_engine_set_game_limit: a slot whose game is past the limit and has not begun (game_unbegun) goes idle and keeps what it
+// holds; an idle slot whose game is below a (raised) limit starts it — the loaded game it was idled with where it holds one
+// (same root, ply and record start; the words a game's start writes are written again), else a fresh game at the start
+// position.
 __global__ __launch_bounds__(WAVE) void k_limit_slots(EngineParams P)
 {
     __shared__ u16 s_moves[MAX_MOVES];
     const int g = blockIdx.x;
     azh_game_state s = P.gs[g];
+    const int mark = P.no_emit[g];
     if (s.phase == 3 && s.uid < P.uid_limit) {
-        init_game(P, g, s.uid, s, s_moves);
+        if ((mark & NO_EMIT_LOADED) && game_unbegun(s, mark)) {
+            begin_ply(P, g, s.uid, s.ply);
+            begin_game_key(P, g, s.uid);
+            s.phase = 0;
+        } else {
+            init_game(P, g, s.uid, s, s_moves);
+        }
         if (threadIdx.x == 0)
             P.gs[g] = s;
-    } else if (s.phase == 0 && s.leaf_kind == AZH_LEAF_NONE && s.ply == 0 && s.n_nodes == 1 && s.root_visits == 0 &&
-               s.uid >= P.uid_limit) {  // a game that has not begun (and has no root evaluation in flight)
+    } else if (s.phase == 0 && game_unbegun(s, mark) && s.uid >= P.uid_limit) {  // (no root evaluation in flight either)
         if (threadIdx.x == 0)
             P.gs[g].phase = 3;
     }
@@ -2194,7 +2205,9 @@ extern "C" int azh_symmetry_move(int s, uint16_t move)
 // nobody asked for — what a generator given a target count (accelerated_generate_games.py --game-count) wants in
 // uid order, where line N only appears once the slowest of the first N games has ended.  The limit may be RAISED later
 // (games that were dropped leave the caller short of lines): idle slots whose next game is now below it start it.
-// Games that have begun are never stopped.
+// Games that have begun are never stopped.  A slot past the limit that has not begun (game_unbegun: at ply 0, or at the ply
+// azh_engine_set_positions loaded it at) goes idle and keeps what it holds; raised, it resumes that game.  The contract: the
+// header.
 extern "C" int azh_engine_set_game_limit(azh_engine *e, int64_t games)
 {
     if (!e || games < 1 || games > 0xFFFFFFFFll)
@@ -2225,6 +2238,8 @@ extern "C" int azh_engine_set_emit_order(azh_engine *e, int by_uid)
 // Every slot restarts at a given position: boards [G][2] packed (x | turn << 63, o), plies [G] (the ply the position is at;
 // < max_plies).  Fresh trees, uids = slot numbers.  Games started this way are played and counted like any other, but
 // their records would lack the plies before the start, so they are not written (the slot's NEXT game is a normal one).
+// Under a game limit in force the slots past it are loaded and left idle (k_init_positions), as the limit set afterwards
+// leaves them.
 // A measurement set-up hook: bench.py loads the positions a long-running generator was found at
 // (profiles/round2_steady_state_positions.npz) instead of waiting a game generation for the steady state to form.
 extern "C" int azh_engine_set_positions(azh_engine *e, const uint64_t *boards, const int32_t *plies)

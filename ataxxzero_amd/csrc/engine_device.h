@@ -41,7 +41,9 @@ struct EngineParams {
     int tt_size;         // power of two >= 4 * node_cap
     int *no_emit;        // [G] start ply + 1 when the slot's current game was started from a loaded position
                          // (azh_engine_set_positions), else 0: such a game is played, counted and its record assembled and
-                         // handed to the host like any other, but it lacks the plies before the start, so no line is written
+                         // handed to the host like any other, but it lacks the plies before the start, so no line is written.
+                         // NO_EMIT_LOADED beside it: azh_engine_set_positions wrote the word and no host move has since —
+                         // what tells a loaded game that has not begun from the fresh root azh_engine_play_moves leaves
     azh_game_state *gs;
     int *force;
     int *adv_list;   // games whose move is due (phase 2), appended by mark_game, consumed by k_advance_list
@@ -97,6 +99,17 @@ struct EngineParams {
 };
 
 constexpr u32 PLY_FULL = 0x80000000u;
+constexpr int NO_EMIT_LOADED = 1 << 30;        // no_emit: the game stands where azh_engine_set_positions put it (max_plies < 2^30)
+constexpr int NO_EMIT_PLY = NO_EMIT_LOADED - 1;  // no_emit: start ply + 1
+
+// The game limit's "has not begun" (azh_engine_set_game_limit): nothing in flight, a one-node root nobody has
+// evaluated, and no move of this game played — a game the engine started stands at ply 0, a loaded one at its loaded ply with
+// the mark azh_engine_play_moves takes away.  The same test on an idle slot (phase 3) finds the loaded game it was idled with.
+__device__ inline bool game_unbegun(const azh_game_state &s, int no_emit)
+{
+    const bool at_start = (no_emit & NO_EMIT_LOADED) ? s.ply == (no_emit & NO_EMIT_PLY) - 1 : s.ply == 0 && no_emit == 0;
+    return s.leaf_kind == AZH_LEAF_NONE && s.n_nodes == 1 && s.root_visits == 0 && at_start;
+}
 
 // A ply of slot g begins (game start and restart, after a re-root, a loaded position, the setter itself): its kind.
 __device__ inline void begin_ply(const EngineParams &P, int g, u32 uid, int ply)
@@ -260,7 +273,7 @@ __device__ inline void init_game_at(const EngineParams &P, int g, u32 uid, azh_g
         A.nb[0] = make_ulonglong2(pack_word0(b), b.o);
         A.ni[0] = make_uint4(0u, (u32)M | ((u32)res << 16), 0u, 0u);
         P.force[g] = 0;
-        P.no_emit[g] = loaded ? ply + 1 : 0;
+        P.no_emit[g] = loaded ? (ply + 1) | NO_EMIT_LOADED : 0;
     }
     if (P.flags & AZH_FLAG_EVAL_CACHE)
         tt_clear(tt_of(P, 0, g), P.tt_size);
@@ -290,8 +303,10 @@ __device__ inline void init_game(const EngineParams &P, int g, u32 uid, azh_game
         s.leaf_kind = AZH_LEAF_NONE;
         s.path_len = 0;
         s.root_visits = 0;
-        if (lane_id() == 0)
+        if (lane_id() == 0) {
             P.force[g] = 0;
+            P.no_emit[g] = 0;  // (the game that ended here may have been a loaded one: nothing is left to resume)
+        }
         return;
     }
     Board b;
@@ -796,7 +811,7 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
             out[4] = 0; out[5] = 8; out[6] = 0; out[7] = 1;  // word 7: dropped
         }
     };
-    const int loaded = P.no_emit[g];            // start ply + 1 of a game that began at a loaded position, else 0
+    const int loaded = P.no_emit[g] & NO_EMIT_PLY;  // start ply + 1 of a game that began at a loaded position, else 0
     const int p0 = loaded ? loaded - 1 : 0;     // first ply this game recorded
     if (no_sample) {
         st_dropped = 1;

@@ -465,7 +465,9 @@ int azh_engine_set_thin_batches(azh_engine *e, int mode);
  * plies [games] — with a fresh tree.  Such games are played, counted (AZH_STAT_GAMES / _DROPPED), and their records are
  * assembled, drained and formatted like any other (the measured path does the same work per finished game), but no line is
  * handed out: the record lacks the plies before the start.  bench.py loads the positions a long-running generator would
- * be found at instead of waiting a game generation (about 70 s at 400 sims/move) for the steady state to form. */
+ * be found at instead of waiting a game generation (about 70 s at 400 sims/move) for the steady state to form.
+ * Under azh_engine_set_game_limit the slots g >= limit are loaded and left idle (they resume the loaded game when the limit
+ * is raised): see there. */
 int azh_engine_set_positions(azh_engine *e, const uint64_t *boards, const int32_t *plies);
 
 /* ------------------------------------------------------------------ moves named by the host (an extension)
@@ -581,7 +583,19 @@ int azh_engine_set_emit_order(azh_engine *e, int by_uid);
  * order line N appears once the slowest of the first N games has ended, and without a limit every other slot meanwhile
  * plays games nobody will read.  The limit may be raised later (dropped games leave the caller short of lines): idle
  * slots whose next game is now below it start it; games that have begun are never stopped.  (The reference's client has
- * no such notion: it is stopped from outside, looper.py:51-64.) */
+ * no such notion: it is stopped from outside, looper.py:51-64.)
+ * The contract, loaded positions included (tests/test_gpu_game_limit.py):
+ *  - A slot HAS NOT BEGUN when it is in phase 0 with no leaf or root evaluation in flight, has one node and root_visits == 0,
+ *    and no move of its current game has been played since the game was started, neither by the device nor through
+ *    azh_engine_play_moves — started by the engine itself at ply 0, or by azh_engine_set_positions at the loaded ply.
+ *  - The call idles every such slot whose uid is >= games (phase 3).  The slot keeps its uid, its loaded root, its ply and
+ *    where its record starts.  azh_engine_set_positions under a limit already in force leaves the slots g >= games idle in
+ *    the same way: both call orders give the same engine state, word for word.
+ *  - Raised: a slot that was idled while it held a loaded position it had not begun resumes THAT game — same board, same
+ *    ply, same record start; any other idle slot below the new limit starts a fresh game at the start position.
+ *  - Begun games are never stopped: a loaded slot whose root evaluation is in flight or done, and a slot after a host-played
+ *    move, the fresh one-node root of AZH_PLAY_FRESH included.  Idle slots add nothing to any counter.
+ *  - With no limit, or a limit >= the slot count when positions are loaded, nothing differs from an engine without one. */
 int azh_engine_set_game_limit(azh_engine *e, int64_t games);
 
 /* ------------------------------------------------------------------ reference ABI

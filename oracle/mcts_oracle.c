@@ -183,6 +183,7 @@ static void init_game(orc_engine *e, int g, uint32_t uid)
         s->path_len = 0;
         s->root_visits = 0;
         e->force[g] = 0;
+        e->no_emit[g] = 0;   /* (the game that ended here may have been a loaded one: nothing is left to resume) */
         return;
     }
     memset(s, 0, sizeof(*s));
@@ -240,17 +241,30 @@ void orc_engine_destroy(orc_engine *e)
 
 int orc_engine_node_cap(const orc_engine *e) { return e->node_cap; }
 void orc_engine_set_visits(orc_engine *e, int visits) { e->cfg.visits = visits; }
+/* "has not begun" (mcts_oracle.h, the game limit): nothing in flight, a one-node root nobody has evaluated, and the game
+ * stands where it was started — ply 0 for one the engine started, the loaded ply for one orc_engine_set_positions did (the
+ * oracle has no host-played moves, so no_emit != 0 alone says "loaded") */
+static int game_unbegun(const orc_engine *e, int g)
+{
+    const orc_game_state *s = &e->gs[g];
+    const int start = e->no_emit[g] ? e->no_emit[g] - 1 : 0;
+    return s->leaf_kind == ORC_LEAF_NONE && s->n_nodes == 1 && s->root_visits == 0 && s->ply == start;
+}
+
 /* mirror of azh_engine_set_game_limit: uids 0 .. games - 1 are played; a slot whose (next) game is past that goes idle */
 void orc_engine_set_game_limit(orc_engine *e, int64_t games)
 {
     e->uid_limit = (uint32_t)games;
     for (int g = 0; g < e->G; g++) {
         orc_game_state *s = &e->gs[g];
-        if (s->phase == ORC_PHASE_IDLE && s->uid < e->uid_limit)
-            init_game(e, g, s->uid);   /* the limit was raised: the slot plays the game it was waiting with */
-        else if (s->phase == ORC_PHASE_ROOT_EVAL && s->leaf_kind == ORC_LEAF_NONE && s->ply == 0 && s->n_nodes == 1 &&
-                 s->root_visits == 0 && s->uid >= e->uid_limit)
-            s->phase = ORC_PHASE_IDLE; /* a game that has not begun */
+        if (s->phase == ORC_PHASE_IDLE && s->uid < e->uid_limit) {
+            if (e->no_emit[g] != 0 && game_unbegun(e, g))
+                s->phase = ORC_PHASE_ROOT_EVAL;   /* idled with a loaded game it never began: that game, as loaded */
+            else
+                init_game(e, g, s->uid);   /* the limit was raised: the slot plays the game it was waiting with */
+        } else if (s->phase == ORC_PHASE_ROOT_EVAL && game_unbegun(e, g) && s->uid >= e->uid_limit) {
+            s->phase = ORC_PHASE_IDLE; /* a game that has not begun: the slot keeps its uid, root, ply and record start */
+        }
     }
 }
 /* mirror of azh_engine_set_positions: every slot restarts at boards[g] (x | turn << 63, o) / plies[g], fresh tree, uid = g */
@@ -269,6 +283,8 @@ void orc_engine_set_positions(orc_engine *e, const uint64_t *boards, const int32
         make_node(e, g, 0, 0, &p, NULL);
         s->n_nodes = 1;
         tt_clear(e, 0, g);
+        if (e->uid_limit != 0 && (uint32_t)g >= e->uid_limit)
+            s->phase = ORC_PHASE_IDLE;   /* under a limit in force: loaded and left idle, as the limit set afterwards leaves it */
     }
 }
 

@@ -87,10 +87,16 @@ int orc_engine_edge_cap(const orc_engine *e);
 /* root-visit threshold for the coming moves, 1 .. the value the engine was created with (the arenas are sized for
  * that); mirror of azh_engine_set_visits */
 void orc_engine_set_visits(orc_engine *e, int visits);
-/* mirror of azh_engine_set_game_limit (may be raised later: idle slots below the new limit start their game) */
+/* mirror of azh_engine_set_game_limit: uids 0 .. games - 1 are played and nothing else.  A slot with uid >= games that HAS
+ * NOT BEGUN goes idle (ORC_PHASE_IDLE) and keeps its uid, root, ply and record start: phase ROOT_EVAL with nothing in flight,
+ * one node, root_visits == 0, and the ply it was started at — 0 for a game the engine started, the loaded ply for one
+ * orc_engine_set_positions did (the oracle has no host-played moves).  Games that have begun are never stopped; idle slots
+ * add nothing to any counter.  May be raised later: an idle slot below the new limit that was idled with a loaded game it
+ * never began resumes that game (same board, ply and record start); any other starts a fresh game at the start position. */
 void orc_engine_set_game_limit(orc_engine *e, int64_t games);
 /* mirror of azh_engine_set_positions: every slot restarts at boards[g] (x | turn << 63, o) / plies[g] with a fresh tree;
- * such games are counted, not written */
+ * such games are counted, not written.  Under a game limit already in force the slots g >= limit are loaded and left idle:
+ * the state is the one orc_engine_set_game_limit leaves when it is called after the load, word for word */
 void orc_engine_set_positions(orc_engine *e, const uint64_t *boards, const int32_t *plies);
 
 /* phase 1 of an iteration: select/expand in every game; returns #leaves needing

@@ -105,3 +105,44 @@ def linear_evals(features):
     A = (((i * 131 + j * 71 + i * j) % 257) - 128).astype(np.float64) / 128.0
     bvec = (((np.arange(196, dtype=np.int64) * 37) % 101) - 50).astype(np.float64) / 400.0
     return (f @ A).reshape(-1, 7, 7, 17), np.tanh(f @ bvec).reshape(-1, 1)
+
+
+def random_line(fen, seed, blockers_mask=None):
+    """One game of random legal moves from `fen` (numpy's PCG64 under `seed`; nine moves in ten a clone where there is one, so the
+    board fills within some 60 plies): [(packed board (2,) u64 = x | turn << 63, o; ply; empty squares)] for every position of
+    it that is not finished."""
+    rng = np.random.default_rng(seed)
+    p = orc.pos_from_fen(fen)
+    if blockers_mask is not None:
+        p.blockers = blockers_mask
+    out = []
+    while orc.result(p) == 0:
+        x, o = int(p.pieces[0]), int(p.pieces[1])
+        empty = 49 - bin(x).count("1") - bin(o).count("1") - bin(int(p.blockers)).count("1")
+        out.append((np.array([x | (p.turn << 63), o], dtype=np.uint64), len(out), empty))
+        moves = [int(m) for m in orc.movegen(p)]
+        clones = [m for m in moves if (m & 0xFF) == (m >> 8)]
+        if clones and rng.integers(10) != 0:
+            moves = clones
+        m = moves[int(rng.integers(len(moves)))]
+        orc.lib().orc_makemove(p, m & 0xFF, m >> 8)
+    return out
+
+
+def cohort_positions(games, limit, fen=orc.START_FEN_SELFPLAY, seed=1, late_empty=4):
+    """Positions and plies for set_positions under a game limit, one random line per slot, so that the games differ in length:
+    the slots past the limit (g >= limit) stand late in their line, `late_empty` squares or fewer still empty — their games
+    last a few plies; the cohort's slots alternate between an early position (ply 2 + g) and the middle of their line.
+    -> boards (games, 2) u64, plies (games,) int32."""
+    boards = np.zeros((games, 2), dtype=np.uint64)
+    plies = np.zeros(games, dtype=np.int32)
+    for g in range(games):
+        line = random_line(fen, 1000 * seed + g)
+        if g >= limit:
+            pick = next((e for e in line if e[2] <= late_empty), line[-1])
+        elif g % 2 == 0:
+            pick = line[min(2 + g, len(line) - 1)]
+        else:
+            pick = line[len(line) // 2]
+        boards[g], plies[g] = pick[0], pick[1]
+    return boards, plies

@@ -344,3 +344,99 @@ def test_config5_size_match_is_deterministic():
     assert len(a) == 1000 and a == b
     assert sum(1 for v in a.values() if v[2] == "a") == 500   # each net has x in half of the cohort
     assert len({v[0] for v in a.values()}) > 20                # (no root noise in the arena: many pairings repeat a line)
+
+
+# ---------------------------------------------------------------- the match's end: a cohort smaller than the slots loaded
+
+def _legal_from_start(moves):
+    """replays UAI moves from the arena's start position; every one must be legal there -> the result of the last position"""
+    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
+    for mv in moves:
+        assert orc.result(p) == 0 and mv in [orc.move_string(x) for x in orc.movegen(p)], mv
+        c = orc.move_from_string(mv)
+        orc.lib().orc_makemove(p, c & 0xFF, c >> 8)
+    return orc.result(p)
+
+
+@pytest.mark.parametrize("G,N,depth,seed", [(6, 5, 3, 9), (12, 7, 4, 10)])
+def test_match_smaller_than_its_loaded_slots_scores_the_cohort_and_nothing_else(G, N, depth, seed):
+    """arena.Match from openings loads every slot; a limit below the slot count (an odd --game-count, a --concurrent above
+    it) must leave the slots past it idle, whichever of the two was set first.  Driven in uai_ringmaster.py's loop order —
+    fetch, lost_games, run, drain — the match hands out exactly the N games of the cohort, lost_games() has nothing to report
+    in any round in which one of them is still missing, and the counters and Match.finished end at N."""
+    V, round_iters = 8, 50
+    nets = [model.random_init(1, 128, seed=s) for s in (2, 3)]
+    m = arena.Match(nets[0], nets[1], visits=V, games=G, dtype="f32", seed=seed, opening_depth=depth)
+    positions, plies = np.repeat(m.opening_boards, 2, axis=0), np.full(G, depth, dtype=np.int32)
+    # precondition, on the CPU oracle WITHOUT a limit (its leaves evaluated by the match's two nets): a game past the
+    # limit would end in an earlier round than the cohort's last — an engine that plays it counts it while the match runs
+    free = _arena_oracle(m, G, V, seed)
+    free.set_positions(positions, plies)
+    ended = {}
+    for r in range(200):
+        _oracle_follow(free, m.net_a, free.cfg.blockers, round_iters, net_b=m.net_b)
+        ended.update({g: r for g in range(G) if g not in ended and free.game_state(g).uid != g})
+        if len(ended) == G:
+            break
+    assert len(ended) == G and min(ended[g] for g in range(N, G)) < max(ended[g] for g in range(N)), ended
+    m.set_game_limit(N)
+    assert [m.engine.game_state(g).phase for g in range(G)] == [0] * N + [3] * (G - N)    # idle before the first run
+    oe = _arena_oracle(m, G, V, seed)
+    oe.set_game_limit(N)                                  # (the other call order on the oracle: one state)
+    oe.set_positions(positions, plies)
+    compare_all(oe, m.engine, range(G))
+    done = {}
+    m.run(round_iters)
+    for r in range(400):
+        m.fetch()
+        lost = m.lost_games()
+        m.run(round_iters)
+        for g in m.drain():
+            assert g["uid"] not in done
+            done[g["uid"]] = g
+        if len(done) >= N:
+            break
+        # a cohort game is still missing after the drain of what that fetch took off the device: the match must not have
+        # said that it is over (uai_ringmaster.py would give up on it there)
+        assert lost is None, (r, lost, sorted(done))
+    m.fetch()                                              # the run enqueued under the last drain: nothing more comes of it
+    assert m.drain() == [] and sorted(done) == list(range(N))
+    st = m.engine.stats()
+    assert st["games"] + st["dropped"] == N and st["ring_overflow"] == 0 and m.finished == N
+    assert m.lost_games() is not None                      # ... and now the match does say that it is over
+    for uid, g in done.items():
+        assert g["opening"] == m.openings[uid // 2] and g["moves"][:depth] == g["opening"] and len(g["opening"]) == depth
+        assert g["white"] == ("a" if uid % 2 == 0 else "b")
+        assert _legal_from_start(g["moves"]) == g["result"] or (g["result"] == 0 and len(g["moves"]) == 400)
+    for g in range(N, G):                                  # the slots past the cohort: idle, with the opening they were loaded with
+        s = m.engine.game_state(g)
+        assert (s.phase, s.uid, s.ply, s.n_nodes) == (3, g, depth, 1) and (m.engine.tree(g)[0][0] == positions[g]).all()
+    # the oracle, followed for as many iterations as the match ran, ends in the same state
+    m.engine.sync()
+    _oracle_follow(oe, m.net_a, oe.cfg.blockers, round_iters * (r + 2), net_b=m.net_b)
+    compare_all(oe, m.engine, range(G))
+    so = oe.stats()
+    assert all(so[k] == st[k] for k in so)
+    m.close()
+
+
+@pytest.mark.parametrize("argv,games", [(["--game-count", "5"], 5), (["--game-count", "6", "--concurrent", "16"], 6)])
+def test_uai_ringmaster_cli_with_a_cohort_smaller_than_its_slots(tmp_path, argv, games):
+    # an odd cohort (six slots are loaded for five games) and a --concurrent above --game-count: a healthy match ends
+    # with exit code 0 and every game of the cohort scored once
+    nets = [model.random_init(1, 128, seed=s) for s in (2, 3)]
+    pa, pb = str(tmp_path / "a.npy"), str(tmp_path / "b.npy")
+    model.save_model(pa, *nets[0])
+    model.save_model(pb, *nets[1])
+    pgn = str(tmp_path / "out.pgn")
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "uai_ringmaster.py"),
+                          "--engine", "python uai_interface.py --network-path %s --visits 8" % pa,
+                          "--engine", "python uai_interface.py --network-path %s --visits 8" % pb,
+                          "--pgn-out", pgn, "--opening-depth", "3"] + argv, cwd=ROOT, capture_output=True, timeout=400)
+    assert res.returncode == 0, res.stderr.decode()[-3000:]
+    out = res.stdout.decode()
+    wins = re.findall(r"Wins: ([0-9.]+) - ([0-9.]+) \(annulled: (\d+)\)", out)
+    assert len(wins) == games and float(wins[-1][0]) + float(wins[-1][1]) == games
+    assert len(re.findall(r"with opening: \[([a-g1-7, ]+)\]", out)) == games
+    text = open(pgn).read()
+    assert text.count('[Event "?"]') == games and len(re.findall(r'\[Opening "[a-g1-7, ]+"\]', text)) == games

@@ -1,6 +1,7 @@
 """Oracle search engine: invariants the reference's algorithm implies (the oracle is the
 checker for the HIP engine, so it is itself checked against the reference's semantics)."""
 import numpy as np
+import pytest
 
 from oracle import oracle_lib as orc
 from tests.helpers import replay_game_entry, synthetic_evals
@@ -242,3 +243,265 @@ def test_game_limit_plays_exactly_the_games_below_it():
         if st["games"] + st["dropped"] >= 23:
             break
     assert st["games"] + st["dropped"] == 23 and all(e.game_state(g).phase == 3 for g in range(8))
+
+
+# ---------------------------------------------------------------- the game limit with loaded positions
+# orc_engine_set_game_limit together with orc_engine_set_positions (mcts_oracle.h): a loaded slot past the limit
+# that has not begun is idle whichever call came first, keeps what it was loaded with, resumes THAT game when the limit is
+# raised, and adds nothing to any counter meanwhile.  tests/test_gpu_game_limit.py repeats every case in lock step with the
+# HIP engine; here the rules are stated on the oracle alone.
+
+LIMIT_CASES = [(6, 5), (6, 3), (12, 11), (12, 6)]   # (G, N): one slot past the limit, and half of them
+LIMIT_PLIES = 160
+
+
+def limit_engine(G, flags=0, fen=orc.START_FEN_SELFPLAY):
+    return orc.Engine(orc.make_config(G, 4, seed=11, fen_str=fen, max_plies=LIMIT_PLIES, flags=flags))
+
+
+def snapshot(e):
+    """every slot's state words and tree arrays, and the counters"""
+    return [(e.game_state(g).as_tuple(), [a.tobytes() for a in e.tree(g)]) for g in range(e.G)], e.stats()
+
+
+def step(e, evaluator=synthetic_evals):
+    n, _ = e.select()
+    e.backup(*evaluator(e.leaf_boards()))
+    return n
+
+
+def play_out(e, max_iters=6000):
+    """Steps until every slot is idle.  -> (games popped, partial ones included, by uid; uids seen in a slot that was not idle;
+    iteration at which each uid left its slot)"""
+    games, live, ended = {}, set(), {}
+    uid_of = [e.game_state(g).uid for g in range(e.G)]
+    for it in range(max_iters):
+        states = [e.game_state(g) for g in range(e.G)]
+        live |= {s.uid for s in states if s.phase != 3}
+        if all(s.phase == 3 for s in states):
+            break
+        step(e)
+        for g in range(e.G):
+            u = e.game_state(g).uid
+            if u != uid_of[g]:
+                ended[uid_of[g]] = it
+                uid_of[g] = u
+        for rec in e.pop_games(partial=True):
+            assert rec["uid"] not in games
+            games[rec["uid"]] = rec
+    else:
+        raise AssertionError("slots still playing after %d iterations" % max_iters)
+    return games, live, ended
+
+
+def cells_of(board):
+    p = orc.Pos()
+    p.pieces[0], p.pieces[1] = int(board[0]) & ((1 << 63) - 1), int(board[1])
+    return [int(v) for v in orc.board_cells(p)]
+
+
+def assert_loaded_and_idle(e, g, boards, plies):
+    s = e.game_state(g)
+    assert (s.phase, s.uid, s.ply, s.n_nodes, s.root_visits, s.leaf_kind) == (3, g, plies[g], 1, 0, orc.LEAF_NONE), (g, s.as_tuple())
+    assert (e.tree(g)[0][0] == boards[g]).all(), g
+
+
+_free_runs = {}
+
+
+def free_run(G, N):
+    """The loaded engine WITHOUT a limit, played until its first G games are over (computed once per case): what each uid's game
+    is when nothing stops or delays it, and when it ends.  -> (games by uid, iteration each uid < G ended at)"""
+    if (G, N) not in _free_runs:
+        from tests.helpers import cohort_positions
+        boards, plies = cohort_positions(G, N)
+        e = limit_engine(G)
+        e.set_positions(boards, plies)
+        games, ended = {}, {}
+        for it in range(6000):
+            step(e)
+            for g in range(G):
+                if g not in ended and e.game_state(g).uid != g:
+                    ended[g] = it
+            for rec in e.pop_games(partial=True):
+                games[rec["uid"]] = rec
+            if len(ended) == G:
+                break
+        assert len(ended) == G
+        _free_runs[(G, N)] = ({u: r for u, r in games.items() if u < G}, ended)
+    return _free_runs[(G, N)]
+
+
+@pytest.mark.parametrize("G,N", LIMIT_CASES)
+def test_game_limit_idles_loaded_slots_in_either_call_order_and_plays_the_cohort_alone(G, N):
+    from tests.helpers import cohort_positions
+    boards, plies = cohort_positions(G, N)
+    assert plies.max() < LIMIT_PLIES and len(set(plies.tolist())) > 2
+    # precondition, on the engine without a limit: a game past the limit would end before the cohort's last one does — an
+    # engine that plays it hands it out and counts it while the match is still running
+    free_games, free_end = free_run(G, N)
+    assert min(free_end[g] for g in range(N, G)) < max(free_end[g] for g in range(N))
+    a, b = limit_engine(G), limit_engine(G)
+    a.set_positions(boards, plies)
+    a.set_game_limit(N)
+    b.set_game_limit(N)
+    b.set_positions(boards, plies)
+    assert snapshot(a) == snapshot(b)
+    for e in (a, b):
+        for g in range(G):
+            if g >= N:
+                assert_loaded_and_idle(e, g, boards, plies)
+            else:
+                s = e.game_state(g)
+                assert (s.phase, s.uid, s.ply) == (0, g, plies[g]) and (e.tree(g)[0][0] == boards[g]).all()
+    games_a, live_a, _ = play_out(a)
+    games_b, live_b, _ = play_out(b)
+    assert live_a == live_b == set(range(N))
+    st = a.stats()
+    assert st == b.stats() and st["games"] + st["dropped"] == N
+    assert snapshot(a) == snapshot(b) and games_a == games_b
+    assert set(games_a) <= set(range(N)) and len(games_a) == st["games"]
+    # the cohort's games are the games those uids are without a limit, each from its loaded position on
+    for u, rec in games_a.items():
+        assert rec["partial"] and rec["entry"] == free_games[u]["entry"] and rec["entry"]["boards"][0] == cells_of(boards[u])
+    # idle for good: nothing is selected, no counter moves, the slots past the limit still hold what they were loaded with
+    assert step(a) == 0 and a.stats() == st and a.pop_games(partial=True) == []
+    for g in range(N, G):
+        assert_loaded_and_idle(a, g, boards, plies)
+
+
+@pytest.mark.parametrize("G,N", LIMIT_CASES)
+def test_game_limit_raised_before_any_step_equals_the_high_limit_from_the_start(G, N):
+    from tests.helpers import cohort_positions
+    boards, plies = cohort_positions(G, N)
+    a, b, c = limit_engine(G), limit_engine(G), limit_engine(G)
+    a.set_positions(boards, plies)
+    a.set_game_limit(N)
+    a.set_game_limit(G)          # idled with their loaded games, and resumed before anything ran
+    b.set_game_limit(G)
+    b.set_positions(boards, plies)
+    c.set_game_limit(N)
+    c.set_positions(boards, plies)   # (the other order of getting there)
+    c.set_game_limit(G)
+    assert snapshot(a) == snapshot(b) == snapshot(c)
+    for g in range(G):
+        s = a.game_state(g)
+        assert (s.phase, s.uid, s.ply) == (0, g, plies[g]) and (a.tree(g)[0][0] == boards[g]).all()
+    popped = [[], [], []]
+    for it in range(6000):
+        if all(a.game_state(g).phase == 3 for g in range(G)):
+            break
+        for e, out in zip((a, b, c), popped):
+            step(e)
+            out += e.pop_games(partial=True)
+        if it % 9 == 0:
+            assert snapshot(a) == snapshot(b) == snapshot(c), it
+    assert snapshot(a) == snapshot(b) == snapshot(c) and popped[0] == popped[1] == popped[2]
+    st = a.stats()
+    assert st["games"] + st["dropped"] == G and len(popped[0]) == st["games"]
+    free_games, _ = free_run(G, N)
+    assert {r["uid"]: r["entry"] for r in popped[0]} == {u: r["entry"] for u, r in free_games.items()}
+
+
+@pytest.mark.parametrize("G,N", LIMIT_CASES)
+def test_game_limit_raised_after_the_cohort_resumes_loaded_games_and_starts_fresh_ones(G, N):
+    from tests.helpers import cohort_positions
+    boards, plies = cohort_positions(G, N)
+    e = limit_engine(G)
+    e.set_game_limit(N)
+    e.set_positions(boards, plies)
+    play_out(e)
+    first = e.stats()
+    assert first["games"] + first["dropped"] == N
+    # raised past the slot count: the slots idled with a loaded game resume it; slots 0 and 1, whose loaded games are over,
+    # start their next game (uids G, G + 1) at the start position; every other slot stays idle
+    e.set_game_limit(G + 2)
+    start = orc.pos_from_fen(orc.START_FEN_SELFPLAY)
+    for g in range(G):
+        s = e.game_state(g)
+        if g >= N:
+            assert (s.phase, s.uid, s.ply, s.n_nodes, s.root_visits) == (0, g, plies[g], 1, 0), (g, s.as_tuple())
+            assert (e.tree(g)[0][0] == boards[g]).all()
+        elif g < 2:
+            assert (s.phase, s.uid, s.ply, s.n_nodes, s.root_visits) == (0, G + g, 0, 1, 0), (g, s.as_tuple())
+            assert [int(v) for v in e.tree(g)[0][0]] == [int(start.pieces[0]) | (start.turn << 63), int(start.pieces[1])]
+        else:
+            assert (s.phase, s.uid) == (3, G + g)
+    assert e.stats() == first
+    games, live, _ = play_out(e)
+    assert live == set(range(N, G)) | {G, G + 1}
+    st = e.stats()
+    assert st["games"] + st["dropped"] == G + 2 and len(games) == st["games"] - first["games"]
+    free_games, _ = free_run(G, N)
+    for u, rec in games.items():
+        if u < G:
+            # the game it was loaded with: the record starts at the loaded ply, and is the game that uid is without a limit
+            assert rec["partial"] and rec["entry"]["boards"][0] == cells_of(boards[u]) and rec["entry"] == free_games[u]["entry"]
+        else:
+            assert not rec["partial"] and replay_game_entry(rec["entry"], orc.START_FEN_SELFPLAY) == rec["entry"]["result"]
+    assert {u for u in free_games if u >= N} == {u for u in games if u < G}
+
+
+@pytest.mark.parametrize("G,N", LIMIT_CASES)
+def test_game_limit_never_stops_a_loaded_game_whose_root_has_been_evaluated(G, N):
+    from tests.helpers import cohort_positions
+    boards, plies = cohort_positions(G, N)
+    e, twin = limit_engine(G), limit_engine(G)
+    for x in (e, twin):
+        x.set_positions(boards, plies)
+        step(x)
+    before = snapshot(e)
+    e.set_game_limit(N)
+    assert snapshot(e) == before == snapshot(twin)          # begun: the root evaluation is done, nothing is idled
+    assert all(e.game_state(g).phase != 3 for g in range(G))
+    games, live, _ = play_out(e)
+    assert live == set(range(G))
+    st = e.stats()
+    assert st["games"] + st["dropped"] == G and len(games) == st["games"]
+    free_games, _ = free_run(G, N)
+    assert {u: r["entry"] for u, r in games.items()} == {u: r["entry"] for u, r in free_games.items()}
+    # and one whose root evaluation is in flight (selected, not yet backed up) is not idled either
+    f = limit_engine(G)
+    f.set_positions(boards, plies)
+    f.select()
+    f.set_game_limit(N)
+    assert all(f.game_state(g).phase != 3 for g in range(G))
+
+
+@pytest.mark.parametrize("G", [6, 12])
+def test_loaded_positions_without_a_limit_in_force_are_untouched_by_the_limit_rules(G):
+    # no limit, a limit no uid of the run reaches, and a limit of exactly G at load time: three engines, one run, through
+    # the loaded games' ends and the ordinary games that follow them
+    from tests.helpers import cohort_positions
+    boards, plies = cohort_positions(G, G // 2)
+    a, b, c = limit_engine(G), limit_engine(G), limit_engine(G)
+    a.set_positions(boards, plies)
+    b.set_game_limit(1 << 31)
+    b.set_positions(boards, plies)
+    c.set_positions(boards, plies)
+    c.set_game_limit(1 << 31)
+    assert snapshot(a) == snapshot(b) == snapshot(c)
+    popped = [[], [], []]
+    for it in range(1500):
+        for e, out in zip((a, b, c), popped):
+            step(e)
+            out += e.pop_games(partial=True)
+        if it % 11 == 0:
+            assert snapshot(a) == snapshot(b) == snapshot(c), it
+    assert snapshot(a) == snapshot(b) == snapshot(c) and popped[0] == popped[1] == popped[2]
+    st = a.stats()
+    assert st["games"] + st["dropped"] > G and any(not r["partial"] for r in popped[0])
+    # (a limit of exactly G: the first G games are the same, then the slots idle)
+    d = limit_engine(G)
+    d.set_game_limit(G)
+    d.set_positions(boards, plies)
+    assert snapshot(d)[0] == snapshot(limit_engine_loaded(G, boards, plies))[0]
+    games, live, _ = play_out(d)
+    assert live == set(range(G)) and {u: r["entry"] for u, r in games.items()} == \
+        {r["uid"]: r["entry"] for r in popped[0] if r["uid"] < G}
+
+
+def limit_engine_loaded(G, boards, plies):
+    e = limit_engine(G)
+    e.set_positions(boards, plies)
+    return e
