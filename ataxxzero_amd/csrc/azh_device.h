@@ -513,6 +513,147 @@ __host__ __device__ inline int temperature_pick_root(const u32 *n, int M, float 
     return chosen < 0 ? 0 : chosen;
 }
 
+// ---------------------------------------------------------------- Gumbel root search with sequential halving
+// azh_engine_set_gumbel ("Gumbel root search with sequential halving").  Every f32 operation is a single IEEE one in
+// the order written, in whichever translation unit this is compiled (the pragmas keep a multiply and an add apart).  Host and
+// device share every function but the wave's reductions: gumbel_root is the host's whole root (azh_gumbel_root), select_game
+// and advance_game hold the wave's.
+constexpr u32 STREAM_GUMBEL = 7u;
+constexpr int GUMBEL_MAX_ACTIONS = 256;
+constexpr int GUMBEL_MAX_TABLE = 1 << 20;  // entries of the considered-visits table: m * visits
+
+// The sequence of considered visit counts for r considered actions and V simulations (the rule of the header), out [V].
+inline void gumbel_considered_visits(int r, int V, u16 *out)
+{
+    if (r <= 1) {
+        for (int i = 0; i < V; i++)
+            out[i] = (u16)i;
+        return;
+    }
+    int L = 0;
+    while ((1 << L) < r)
+        L++;
+    u16 visits[GUMBEL_MAX_ACTIONS] = {};
+    int k = r, len = 0;
+    while (len < V) {
+        const int d = V / (L * k), extra = d > 1 ? d : 1;
+        for (int x = 0; x < extra && len < V; x++) {
+            for (int i = 0; i < k && len < V; i++)
+                out[len++] = visits[i];
+            for (int i = 0; i < k; i++)
+                visits[i]++;
+        }
+        k = k / 2 > 2 ? k / 2 : 2;
+    }
+}
+// g_j: the Gumbel(0, 1) draw of root edge j of ply `ply` of game `uid`
+__host__ __device__ inline float gumbel_noise(u32 k0, u32 k1, u32 uid, u32 ply, u32 j)
+{
+#pragma clang fp contract(off)
+    const u32 x = philox(k0, k1, uid, ply, STREAM_GUMBEL, j).v[0];
+    const float u = ((float)(x >> 9) + 0.5f) * 0x1p-23f;  // exact, in (0, 1)
+    return -det_logf(-det_logf(u));
+}
+// l_j: the logit of a prior as stored (without its mark)
+__host__ __device__ inline float gumbel_logit(float prior) { return prior > 0.0f ? det_logf(prior) : -INFINITY; }
+// ks = (c_visit + n_max) * c_scale: what a [0, 1] score is multiplied by
+__host__ __device__ inline float gumbel_ks(float c_visit, float c_scale, u32 n_max)
+{
+#pragma clang fp contract(off)
+    return (c_visit + (float)n_max) * c_scale;
+}
+// s_j = a_j + ks * q_j of a visited edge, a_j of an unvisited one
+__host__ __device__ inline float gumbel_score(float a, float W, u32 n, float ks)
+{
+#pragma clang fp contract(off)
+    if (n == 0u)
+        return a;
+    const float t = ks * (W / (float)n);
+    return a + t;
+}
+// Arg-max key of (score, edge): the greatest key is the greatest score, the lowest index among equal ones; 0 for a NaN, which
+// never wins (any other score's key is > 0: the keys of -inf .. +inf ascend from 0x007FFFFF).
+__host__ __device__ inline u64 gumbel_key(float s, u32 j)
+{
+    if (!(s == s))
+        return 0ull;
+    const u32 b = f2u(s + 0.0f);  // (-0 becomes +0: equal scores have equal bits)
+    const u32 o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((u64)o << 32) | (u64)(0xFFFFFFFFu - j);
+}
+// x_j = l_j + ks * cq_j and the written count of an edge whose x is `x` when the greatest is x_max
+__host__ __device__ inline float gumbel_target_logit(float prior, float cq, float ks)
+{
+#pragma clang fp contract(off)
+    const float t = ks * cq;
+    return gumbel_logit(prior) + t;
+}
+__host__ __device__ inline u32 gumbel_count(float x, float x_max)
+{
+#pragma clang fp contract(off)
+    const float w = det_expf(x - x_max) * 65535.0f;
+    const u32 c = (u32)w;
+    return c < 65535u ? c : 65535u;
+}
+// v_mix from the root's own value, its visits N and the two 64-lane sums over the visited edges
+__host__ __device__ inline float gumbel_v_mix(float v0, u32 N, float sp, float sw)
+{
+#pragma clang fp contract(off)
+    if (!(sp > 0.0f))
+        return v0;
+    const float t = ((float)N / sp) * sw;
+    return (v0 + t) / (1.0f + (float)N);
+}
+// The 64-lane sum on the host: lane l adds its terms l, l + 64, ... in that order from 0, then the xor butterfly 1 .. 32.
+inline float gumbel_lane_sum(const float *v, int M)
+{
+    float lane[WAVE] = {};
+    for (int j = 0; j < M; j++)
+        lane[j & 63] = lane[j & 63] + v[j];
+    for (int off = 1; off < WAVE; off <<= 1) {
+        float nx[WAVE];
+        for (int l = 0; l < WAVE; l++)
+            nx[l] = lane[l] + lane[l ^ off];
+        for (int l = 0; l < WAVE; l++)
+            lane[l] = nx[l];
+    }
+    return lane[0];
+}
+// The whole root on the host (azh_gumbel_root): the move played and the written counts (counts [M]; 0: left out).  noise [M]:
+// g_j (gumbel_noise).  Returns the edge of the move.
+inline int gumbel_root(const float *prior, const float *W, const u32 *n, int M, float v0, const float *noise, float c_visit,
+                       float c_scale, u32 *counts)
+{
+#pragma clang fp contract(off)
+    u32 N = 0, n_max = 0;
+    for (int j = 0; j < M; j++) {
+        N += n[j];
+        n_max = n[j] > n_max ? n[j] : n_max;
+    }
+    const float ks = gumbel_ks(c_visit, c_scale, n_max);
+    u64 key = 0;
+    float tp[GUMBEL_MAX_ACTIONS], tw[GUMBEL_MAX_ACTIONS];
+    for (int j = 0; j < M; j++) {
+        const float p = fabsf(prior[j]);
+        if (n[j] == n_max) {
+            const u64 kk = gumbel_key(gumbel_score(noise[j] + gumbel_logit(p), W[j], n[j], ks), (u32)j);
+            key = kk > key ? kk : key;
+        }
+        tp[j] = n[j] >= 1u ? p : 0.0f;
+        tw[j] = n[j] >= 1u ? p * (W[j] / (float)n[j]) : 0.0f;
+    }
+    const float v_mix = gumbel_v_mix(v0, N, gumbel_lane_sum(tp, M), gumbel_lane_sum(tw, M));
+    float x_max = -INFINITY;
+    for (int j = 0; j < M; j++) {
+        tp[j] = gumbel_target_logit(fabsf(prior[j]), n[j] >= 1u ? W[j] / (float)n[j] : v_mix, ks);
+        if (tp[j] > x_max)
+            x_max = tp[j];
+    }
+    for (int j = 0; j < M; j++)
+        counts[j] = gumbel_count(tp[j], x_max);
+    return key ? (int)(0xFFFFFFFFu - (u32)key) : 0;
+}
+
 // ---------------------------------------------------------------- random symmetry per evaluation
 // azh_engine_set_random_symmetry ("Random symmetry per evaluation"): every position goes to the evaluator as its
 // image under one of the 8 dihedral symmetries of the board, and the logits come back through the same symmetry's move map.

@@ -450,6 +450,84 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
             }
         }
         bool expand = false;
+        // Gumbel root search (azh_engine_set_gumbel; DESIGN.md, "Gumbel root search with sequential halving"): at the root of
+        // a fresh descent the edge with exactly cv visits — the entry of the sequential-halving schedule for this simulation —
+        // and the greatest a + ks q is taken, the lowest index among equal scores, in place of the PUCT arg-max.  The shape of
+        // the forced-playout branch above: four records per lane in the loop's record registers, every lane keeps the child
+        // data of its own best edge (the winning lane's best is the winner), the root's level is done here — path entry,
+        // counters, the mark as fast_level moves it — and the loop starts at the child, or is skipped when the edge has no
+        // child yet (a first visit: the expansion below).  No edge with cv visits (or a root past the schedule's end, after
+        // azh_engine_set_visits lowered the threshold): the loop runs as it always has.
+        if (P.gumbel_m != 0 && !resume && kid_count(kid) > 0 && n_node < (u32)P.visits) {
+            const int M0 = kid_count(kid);
+            const u32 f0 = kid_first(kid);
+            const u32 cv = P.gumbel_seq[(size_t)(min(P.gumbel_m, M0) - 1) * (size_t)P.visits + n_node];
+            const float *ga = P.gumbel_a + (size_t)g * MAX_MOVES;
+            uint4 *const rp[4] = {&ea0, &ea1, &eb0, &eb1};
+            u64 mk[4];
+            float av[4];
+            u32 nmx = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int j = lane + 64 * k;
+                bool marked = false;
+                av[k] = 0.0f;
+                if (j < M0) {
+                    const uint4 r = A.ed[f0 + j];
+                    *rp[k] = r;
+                    av[k] = ga[j];
+                    nmx = max(nmx, edge_visits(r));
+                    marked = (int)r.x < 0;
+                }
+                mk[k] = __ballot(marked);
+            }
+            const float ks = gumbel_ks(P.gumbel_c_visit, P.gumbel_c_scale, wave_max_u32(nmx));
+            u64 key = 0;
+            u32 mine = 0, mkid = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int j = lane + 64 * k;
+                if (j < M0 && edge_visits(*rp[k]) == cv) {
+                    const u64 kj = gumbel_key(gumbel_score(av[k], u2f(rp[k]->y), cv, ks), (u32)j);
+                    if (kj > key) {
+                        key = kj;
+                        mine = rp[k]->z;
+                        mkid = rp[k]->w;
+                    }
+                }
+            }
+            key = wave_max_u64(key);
+            if (key) {
+                const int bj = (int)(0xFFFFFFFFu - (u32)key);
+                const u32 zsel = (u32)read_lane((int)mine, bj & 63), wsel = (u32)read_lane((int)mkid, bj & 63);
+                levels_done = 1;
+                st_levels += 1;
+                st_children += (u64)M0;
+                push_path(f0 + (u32)bj);
+                if ((zsel >> 16) == ENONE) {
+                    sel_eidx = f0 + (u32)bj;
+                    expand = true;
+                } else {
+                    int pv = -1;
+#pragma unroll
+                    for (int k = 3; k >= 0; k--)
+                        if (mk[k])
+                            pv = 64 * k + __ffsll((long long)mk[k]) - 1;
+                    if (M0 <= 2 * WAVE && bj != pv) {  // (wider nodes carry no mark: the general level never sets one)
+                        const bool markable = !kid_finished(wsel) && kid_count(wsel) > 0 && kid_count(wsel) <= 2 * WAVE;
+                        if (pv >= 0 && lane == (pv & 63))
+                            reinterpret_cast<u32 *>(&A.ed[f0 + (u32)pv])[0] = (pv >= WAVE ? ea1.x : ea0.x) & PRIOR_MASK;
+                        if (markable && lane == (bj & 63))
+                            reinterpret_cast<u32 *>(&A.ed[f0 + (u32)bj])[0] = (bj >= WAVE ? ea1.x : ea0.x) | ~PRIOR_MASK;
+                    }
+                    node = zsel >> 16;
+                    kid = wsel;
+                    n_node = (zsel & 0xFFFFu) - 1u;
+                    sq_node = sqrt_1p(n_node);
+                }
+            }
+        }
+        if (!expand)
         for (;;) {
             if (level_begin())
                 break;
@@ -790,6 +868,22 @@ __device__ inline void backup_game(const EngineParams &P, int g, azh_game_state 
         apply_priors(P, A, s.leaf_node, P.logits + (size_t)g * AZH_POLICY_SIZE, kind == AZH_LEAF_ROOT && (pk & PLY_FULL) != 0u,
                      s.uid, (u32)s.ply, eval_symmetry_at(P, A, g, s.leaf_node));
 
+    if (P.gumbel_m != 0 && kind == AZH_LEAF_ROOT) {
+        // Gumbel root search: a_j = g_j + l_j of every root edge from the prior just stored (each lane reads back what it
+        // wrote itself), and the root's own value as a score; the ply's select and its move read both
+        const uint4 rinfo = A.ni[0];
+        const int M = (int)(rinfo.y & 0xFFFFu);
+        float *ga = P.gumbel_a + (size_t)g * MAX_MOVES;
+#pragma unroll 1
+        for (int j = lane; j < M; j += WAVE) {
+            u32 jv = (u32)j;
+            asm volatile("" : "+v"(jv));  // (the Philox block in vector registers, as begin_ply)
+            const float l = gumbel_logit(u2f(reinterpret_cast<const u32 *>(&A.ed[rinfo.x + j])[0] & PRIOR_MASK));
+            ga[j] = gumbel_noise(P.k0, P.k1, s.uid, (u32)s.ply, jv) + l;
+        }
+        if (lane == 0)
+            P.gumbel_v0[g] = (P.values[g] + 1.0f) * 0.5f;
+    }
     if ((P.flags & AZH_FLAG_EVAL_CACHE) && kind == AZH_LEAF_EVAL) {
         // the leaf now carries an evaluation: remember its value and enter it in the table
         if (lane == 0) {
@@ -1263,6 +1357,8 @@ struct azh_engine {
     int *d_play_status = nullptr;
     u32 *d_report = nullptr;       // azh_engine_root_report: [G][AZH_ROOT_REPORT_WORDS], allocated by the first call
     u64 *d_stat_out = nullptr;
+    u16 *d_gumbel_seq = nullptr;     // azh_engine_set_gumbel: the considered-visits table, gumbel_seq_cap entries, allocated by the
+    size_t gumbel_seq_cap = 0;       // first call that needs them (a larger m * visits later allocates again)
     float *d_move_temperature = nullptr, *d_root_policy_temperature = nullptr;  // azh_engine_set_temperature: [max_plies] each,
                                                                                 // allocated by the first call that brings one
     // finished games formatted but not yet handed out
@@ -1643,7 +1739,7 @@ struct RunLoop {
     azh_net *net_a, *net_b;
     int dtype, iterations;
     bool pair = false;
-    bool own = false;  // forced playouts, random symmetry, recorded values and resignation, a move temperature: the queued moves in a
+    bool own = false;  // forced playouts, random symmetry, recorded values and resignation, a move temperature, Gumbel: the queued moves in a
                        // k_advance_list launch of their own, on the engine's stream, in front of the tower (the tower kernels'
                        // advance_game records no pruned counts, writes no key word and knows no ply value and no temperature:
                        // engine_device.h)
@@ -1655,7 +1751,8 @@ struct RunLoop {
         const char *pair_s = getenv("AZH_ARENA_PAIR");  // (read per call: a test switches it inside one process)
         const bool pair_env = !(pair_s && atoi(pair_s) == 0);
         pair = pair_env && two_lists(e) && !(e->P.flags & AZH_FLAG_SYMMETRY_AVG);
-        own = e->P.forced_k != 0.0f || e->P.random_symmetry != 0u || e->P.resign_plies != 0u || e->P.move_temperature != nullptr;
+        own = e->P.forced_k != 0.0f || e->P.random_symmetry != 0u || e->P.resign_plies != 0u || e->P.move_temperature != nullptr ||
+              e->P.gumbel_m != 0;
         hook.workers = e->adv_workers;
         hook.at_head = 1;   // (decided per launch by the tower's launch functions: in front only where workgroups queue for slots)
         hook.P = e->P;
@@ -1814,6 +1911,9 @@ static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, b
                             e->P.select_budget > 0 ? "select_budget > 0"
                             : (bad & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS"
                             : (bad & AZH_FLAG_EVAL_CACHE) ? "AZH_FLAG_EVAL_CACHE" : "AZH_FLAG_SYMMETRY_AVG");
+        if (e->P.gumbel_m != 0)  // (nor a Gumbel root level)
+            return azh_fail(-4, "%s: %s is not supported with the Gumbel root search (azh_engine_set_gumbel)", who,
+                            leaves_per_game > 1 ? "more than one leaf per game" : "the solver");
         if (e->P.forced_k != 0.0f)  // (the K-leaf kernel has no forced-playout level)
             return azh_fail(-4, "%s: %s is not supported with forced playouts (azh_engine_set_forced_playouts)", who,
                             leaves_per_game > 1 ? "more than one leaf per game" : "the solver");
@@ -1944,6 +2044,23 @@ extern "C" int azh_engine_set_thin_batches(azh_engine *e, int mode)
     return 0;
 }
 
+// The considered-visits rows r = 1 .. m of the Gumbel root search for a threshold of `visits`, on the device (the stream is idle).
+static int gumbel_upload_table(azh_engine *e, int m, int visits)
+{
+    const size_t n = (size_t)m * (size_t)visits;
+    std::vector<u16> h(n);
+    for (int r = 1; r <= m; r++)
+        gumbel_considered_visits(r, visits, h.data() + (size_t)(r - 1) * visits);
+    if (n > e->gumbel_seq_cap) {
+        if (dev_alloc(e, &e->d_gumbel_seq, n))
+            return -1;
+        e->gumbel_seq_cap = n;
+    }
+    AZH_HIP(hipMemcpy(e->d_gumbel_seq, h.data(), n * sizeof(u16), hipMemcpyHostToDevice));
+    e->P.gumbel_seq = e->d_gumbel_seq;
+    return 0;
+}
+
 // Root-visit threshold for the coming moves (1 .. the value the engine was created with; the
 // arenas are sized for that).  Takes effect at the next k_advance.
 extern "C" int azh_engine_set_visits(azh_engine *e, int visits)
@@ -1952,7 +2069,12 @@ extern "C" int azh_engine_set_visits(azh_engine *e, int visits)
         return azh_fail(-1, "azh_engine_set_visits: need 1 <= visits <= %d", e ? e->cfg.visits : 0);
     if (visits < e->P.fast_visits)
         return azh_fail(-2, "azh_engine_set_visits: %d is below the playout cap's fast_visits %d", visits, e->P.fast_visits);
+    if (e->P.gumbel_m != 0 && (long long)e->P.gumbel_m * visits > GUMBEL_MAX_TABLE)
+        return azh_fail(-2, "azh_engine_set_visits: the Gumbel root search is on with m = %d: m * visits may not exceed %d",
+                        e->P.gumbel_m, GUMBEL_MAX_TABLE);
     AZH_HIP(hipStreamSynchronize(e->stream));
+    if (e->P.gumbel_m != 0 && gumbel_upload_table(e, e->P.gumbel_m, visits))  // (the rows for the new threshold)
+        return -1;
     e->P.visits = visits;
     return 0;
 }
@@ -1971,6 +2093,8 @@ extern "C" int azh_engine_set_playout_cap(azh_engine *e, int fast_visits, int fu
     if (fast_visits != 0 && (e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_ONE_RANDOM_MOVE)))
         return azh_fail(-4, "azh_engine_set_playout_cap: not supported with %s",
                         (e->P.flags & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS" : "AZH_FLAG_ONE_RANDOM_MOVE");
+    if (fast_visits != 0 && e->P.gumbel_m != 0)
+        return azh_fail(-4, "azh_engine_set_playout_cap: not supported with the Gumbel root search (azh_engine_set_gumbel)");
     AZH_HIP(hipStreamSynchronize(e->stream));
     if (fast_visits == 0) {
         e->P.fast_visits = 0;
@@ -2009,6 +2133,8 @@ extern "C" int azh_engine_set_forced_playouts(azh_engine *e, float k)
     if (k != 0.0f && e->vl_active)
         return azh_fail(-4, "azh_engine_set_forced_playouts: not supported with %s",
                         leaf_k(e) > 1 ? "more than one leaf per game (azh_engine_set_leaf_batch)" : "the solver");
+    if (k != 0.0f && e->P.gumbel_m != 0)
+        return azh_fail(-4, "azh_engine_set_forced_playouts: not supported with the Gumbel root search (azh_engine_set_gumbel)");
     AZH_HIP(hipStreamSynchronize(e->stream));
     e->P.forced_k = k;
     return 0;
@@ -2023,6 +2149,99 @@ extern "C" int azh_forced_prune(const float *prior, const float *W, const uint32
     if (!(k >= 0.0f) || k > 3.0e38f)
         return azh_fail(-2, "azh_forced_prune: need a finite k >= 0");
     forced_prune_root(prior, W, n, M, k, c_puct, out);
+    return 0;
+}
+
+// Gumbel root search with sequential halving (Danihelka et al., ICLR 2022).  Definition: the header and DESIGN.md.  Between
+// iterations only.  Every check comes before the first change, so a refused call leaves the engine as it was.
+extern "C" int azh_engine_set_gumbel(azh_engine *e, int m, float c_visit, float c_scale)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_set_gumbel: null engine");
+    if (m < 0 || m > GUMBEL_MAX_ACTIONS)
+        return azh_fail(-2, "azh_engine_set_gumbel: need 0 <= m <= %d (0: off)", GUMBEL_MAX_ACTIONS);
+    if (m != 0 && (!(c_visit >= 0.0f) || c_visit > 3.0e38f || !(c_scale > 0.0f) || c_scale > 3.0e38f))
+        return azh_fail(-2, "azh_engine_set_gumbel: need a finite c_visit >= 0 and a finite c_scale > 0");
+    if ((long long)m * e->P.visits > GUMBEL_MAX_TABLE)
+        return azh_fail(-2, "azh_engine_set_gumbel: m * visits = %lld may not exceed %d", (long long)m * e->P.visits,
+                        GUMBEL_MAX_TABLE);
+    if (e->selected)
+        return azh_fail(-3, "azh_engine_set_gumbel: a selected batch awaits its backup");
+    if (m != 0) {
+        const u32 bad = e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_ONE_RANDOM_MOVE | AZH_FLAG_SAMPLE_POW5 | AZH_FLAG_EVAL_CACHE);
+        if (bad)
+            return azh_fail(-4, "azh_engine_set_gumbel: not supported with %s",
+                            (bad & AZH_FLAG_TWO_NETS)          ? "AZH_FLAG_TWO_NETS"
+                            : (bad & AZH_FLAG_ONE_RANDOM_MOVE) ? "AZH_FLAG_ONE_RANDOM_MOVE"
+                            : (bad & AZH_FLAG_SAMPLE_POW5)     ? "AZH_FLAG_SAMPLE_POW5"
+                                                               : "AZH_FLAG_EVAL_CACHE");
+        if (!(e->P.flags & AZH_FLAG_NO_REUSE) || e->P.noise_w != 0.0f)
+            return azh_fail(-4, "azh_engine_set_gumbel: the engine must have been created with AZH_FLAG_NO_REUSE and "
+                                "dirichlet_weight 0 (the schedule assumes a fresh root, and its noise is the Gumbel)");
+        const char *mode = e->P.fast_visits != 0 ? "the playout cap (azh_engine_set_playout_cap)"
+                           : e->P.forced_k != 0.0f ? "forced playouts (azh_engine_set_forced_playouts)"
+                           : (e->P.move_temperature || e->P.root_policy_temperature) ? "a temperature table (azh_engine_set_temperature)"
+                           : e->vl_active ? (leaf_k(e) > 1 ? "more than one leaf per game (azh_engine_set_leaf_batch)" : "the solver")
+                                          : nullptr;
+        if (mode)
+            return azh_fail(-4, "azh_engine_set_gumbel: not supported with %s", mode);
+    }
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    if (m == 0) {
+        e->P.gumbel_m = 0;
+        e->P.gumbel_c_visit = 0.0f;
+        e->P.gumbel_c_scale = 0.0f;
+        return 0;
+    }
+    const size_t G = (size_t)e->P.G;
+    if (!e->P.gumbel_a && dev_alloc(e, &e->P.gumbel_a, G * MAX_MOVES))
+        return -1;
+    if (!e->P.gumbel_v0 && dev_alloc(e, &e->P.gumbel_v0, G))
+        return -1;
+    if (gumbel_upload_table(e, m, e->P.visits))
+        return -1;
+    if (e->P.gumbel_m == 0) {
+        // a ply whose root was evaluated before the mode came on has no noise of its own: it is searched with a_j = 0 and
+        // a root value of one half (the next root evaluation of the slot writes both)
+        const std::vector<float> half(G, 0.5f);
+        AZH_HIP(hipMemset(e->P.gumbel_a, 0, G * MAX_MOVES * sizeof(float)));
+        AZH_HIP(hipMemcpy(e->P.gumbel_v0, half.data(), G * sizeof(float), hipMemcpyHostToDevice));
+    }
+    e->P.gumbel_c_visit = c_visit;
+    e->P.gumbel_c_scale = c_scale;
+    e->P.gumbel_m = m;
+    return 0;
+}
+
+// One row of the schedule: the considered visit counts for m actions and `visits` simulations, out [visits].  Host arithmetic only.
+extern "C" int azh_gumbel_considered_visits(int m, int visits, uint16_t *out)
+{
+    if (!out || m < 1 || m > GUMBEL_MAX_ACTIONS || visits < 1 || visits > 60000)
+        return azh_fail(-1, "azh_gumbel_considered_visits: bad argument (need out, 1 <= m <= %d and 1 <= visits <= 60000)",
+                        GUMBEL_MAX_ACTIONS);
+    gumbel_considered_visits(m, visits, out);
+    return 0;
+}
+
+// g_j of the root edges j < M of ply `ply` of game `uid` under `seed`, out [M].  Host arithmetic only.
+extern "C" int azh_gumbel_noise(uint64_t seed, uint32_t uid, uint32_t ply, int M, float *out)
+{
+    if (!out || M < 0 || M > MAX_MOVES)
+        return azh_fail(-1, "azh_gumbel_noise: bad argument (need out and 0 <= M <= %d)", MAX_MOVES);
+    for (int j = 0; j < M; j++)
+        out[j] = gumbel_noise((u32)seed, (u32)(seed >> 32), uid, ply, (u32)j);
+    return 0;
+}
+
+// The move and the record's counts of a whole root: the device's ply restated on the host (gumbel_root).  Host arithmetic only.
+extern "C" int azh_gumbel_root(const float *prior, const float *W, const uint32_t *n, int M, float v0, const float *noise,
+                               float c_visit, float c_scale, uint32_t *counts_out, int32_t *move_out)
+{
+    if (!prior || !W || !n || !noise || !counts_out || !move_out || M < 1 || M > MAX_MOVES)
+        return azh_fail(-1, "azh_gumbel_root: bad argument (need every array and 1 <= M <= %d)", MAX_MOVES);
+    if (!(c_visit >= 0.0f) || c_visit > 3.0e38f || !(c_scale > 0.0f) || c_scale > 3.0e38f)
+        return azh_fail(-2, "azh_gumbel_root: need a finite c_visit >= 0 and a finite c_scale > 0");
+    *move_out = gumbel_root(prior, W, n, M, v0, noise, c_visit, c_scale, counts_out);
     return 0;
 }
 
@@ -2090,6 +2309,8 @@ extern "C" int azh_engine_set_temperature(azh_engine *e, const float *move_tempe
                         : (e->P.flags & AZH_FLAG_SAMPLE_POW5)   ? "AZH_FLAG_SAMPLE_POW5"
                         : (e->P.flags & AZH_FLAG_PY_POSTERIOR)  ? "AZH_FLAG_PY_POSTERIOR"
                                                                 : "AZH_FLAG_TWO_NETS");
+    if ((move_temperature || root_policy_temperature) && e->P.gumbel_m != 0)
+        return azh_fail(-4, "azh_engine_set_temperature: not supported with the Gumbel root search (azh_engine_set_gumbel)");
     AZH_HIP(hipStreamSynchronize(e->stream));
     // the engine's two tables are allocated once and kept; a null argument only takes the pointer out of the parameters
     if (move_temperature && !e->d_move_temperature && dev_alloc(e, &e->d_move_temperature, (size_t)n))

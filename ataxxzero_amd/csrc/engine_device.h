@@ -24,6 +24,8 @@ constexpr u32 REC_KIND_FORCED = 8u;       // beside it: the game was played with
 constexpr u32 REC_KIND_VALUES = 16u;      // the game was played with the search value recorded (azh_engine_set_resign): word 5 of
                                           // every ply = the bits of q (sign bit: FULL), and its line carries "values"
 constexpr u32 REC_KIND_RESIGNED = 32u;    // the game ended by resignation: its line carries "resigned"
+constexpr u32 REC_KIND_GUMBEL = 64u;      // the game was played with the Gumbel root search on: the counts of every ply are the
+                                          // improved policy in units of 1/65535 of its greatest entry (json.cpp ignores the bit)
 constexpr int NSTAT = AZH_STAT_COUNT;
 constexpr int BFS_QL = 384;  // re-root frontier entries kept in LDS; later ones spill to bfs_spill in HBM
 
@@ -96,6 +98,12 @@ struct EngineParams {
     const float *move_temperature;         // [max_plies] 1: the proportional draw, 0: the most visited move, else n^(1/T) in
                                            // fixed point (temperature_weight); read by k_advance_list's advance_game alone
     const float *root_policy_temperature;  // [max_plies] apply_priors divides the logits of a noise ply's root by this
+    // Gumbel root search with sequential halving (azh_engine_set_gumbel), off while gumbel_m == 0
+    int gumbel_m;               // considered actions at the root
+    float gumbel_c_visit, gumbel_c_scale;
+    const u16 *gumbel_seq;      // [gumbel_m][visits] row r - 1: the considered visit counts for r actions at the current `visits`
+    float *gumbel_a;            // [G][MAX_MOVES] a_j = g_j + l_j of every root edge, written by the root's backup
+    float *gumbel_v0;           // [G] the root's own value as a [0, 1] score, written beside it
 };
 
 constexpr u32 PLY_FULL = 0x80000000u;
@@ -564,6 +572,71 @@ __device__ inline int tempered_choice(const u32 (&nv)[4], int M, float T, u32 v0
     return chosen < 0 ? 0 : chosen;
 }
 
+// Gumbel root search (azh_engine_set_gumbel; DESIGN.md, "Gumbel root search with sequential halving"): the move of the ply
+// and its record's counts, the wave's form of gumbel_root.  `chosen` receives the edge with n_max visits and the greatest
+// a + ks q (the lowest index among equal ones); rec gets move | c << 16 of every root edge, expanded or not, whose count c of
+// the improved policy softmax(l + ks completedQ) is >= 1, in edge order.  Returns the number of entries written.  Rolled loops
+// over the edges of its own, as record_pruned_counts: only k_advance_list's instantiation of advance_game calls it.
+__device__ inline int gumbel_record(const EngineParams &P, const Arena &A, u32 first, int M, u32 N, int g, u32 *rec, int &chosen)
+{
+#pragma clang fp contract(off)
+    const int lane = lane_id();
+    const float *ga = P.gumbel_a + (size_t)g * MAX_MOVES;
+    u32 nm = 0;
+#pragma unroll 1
+    for (int j = lane; j < M; j += WAVE)
+        nm = max(nm, reinterpret_cast<const u32 *>(&A.ed[first + j])[2] & 0xFFFFu);
+    const u32 n_max = wave_max_u32(nm);
+    const float ks = gumbel_ks(P.gumbel_c_visit, P.gumbel_c_scale, n_max);
+    u64 key = 0;
+    float psp = 0.0f, psw = 0.0f;  // this lane's terms of the two sums, in edge order from 0 (an unvisited edge adds 0)
+#pragma unroll 1
+    for (int j = lane; j < M; j += WAVE) {
+        const uint4 ev = A.ed[first + j];
+        const u32 n = edge_visits(ev);
+        const float pr = u2f(ev.x & PRIOR_MASK);
+        if (n == n_max) {
+            const u64 kk = gumbel_key(gumbel_score(ga[j], u2f(ev.y), n, ks), (u32)j);
+            key = kk > key ? kk : key;
+        }
+        const float tw = n >= 1u ? pr * (u2f(ev.y) / (float)n) : 0.0f;
+        psp = psp + (n >= 1u ? pr : 0.0f);
+        psw = psw + tw;
+    }
+    key = wave_max_u64(key);
+    chosen = key ? (int)(0xFFFFFFFFu - (u32)key) : 0;
+    const float sp = wave_sum_f32(psp), sw = wave_sum_f32(psw);
+    const float v_mix = gumbel_v_mix(P.gumbel_v0[g], N, sp, sw);
+    float xm = -INFINITY;
+#pragma unroll 1
+    for (int j = lane; j < M; j += WAVE) {
+        const uint4 ev = A.ed[first + j];
+        const u32 n = edge_visits(ev);
+        const float x = gumbel_target_logit(u2f(ev.x & PRIOR_MASK), n >= 1u ? u2f(ev.y) / (float)n : v_mix, ks);
+        if (x > xm)
+            xm = x;
+    }
+    const float x_max = wave_max_f32(xm);
+    const u64 lt = (1ULL << lane) - 1ULL;
+    int nd = 0;
+#pragma unroll 1
+    for (int j0 = 0; j0 < M; j0 += WAVE) {
+        const int j = j0 + lane;
+        u32 c = 0, word = 0;
+        if (j < M) {
+            const uint4 ev = A.ed[first + j];
+            const u32 n = edge_visits(ev);
+            c = gumbel_count(gumbel_target_logit(u2f(ev.x & PRIOR_MASK), n >= 1u ? u2f(ev.y) / (float)n : v_mix, ks), x_max);
+            word = (u32)A.em[first + j] | (c << 16);
+        }
+        const u64 mask = __ballot(c != 0u);
+        if (c != 0u)
+            rec[REC_HDR_WORDS + nd + __popcll(mask & lt)] = word;
+        nd += __popcll(mask);
+    }
+    return nd;
+}
+
 // OWN: the instantiation of the move-playing launch of its own, k_advance_list: the one that can record pruned counts (forced
 // playouts), write a game's key word (random symmetry), and record the ply's value and resign (azh_engine_set_resign).  The
 // tower kernels carry the
@@ -573,7 +646,8 @@ __device__ inline int tempered_choice(const u32 (&nv)[4], int M, float T, u32 v0
 // it sent k_tower2<1, false> and <2, false> to scratch memory (12 bytes per lane, 2 VGPR spills;
 // profiles/random_symmetry.txt), so their instantiation starts games without it and that mode, too, plays its moves in
 // k_advance_list.  The ply's value, the resign rule and its once-per-game counts live in the OWN instantiation alone for the
-// same reason, and so does the ply's move temperature (tempered_choice).
+// same reason, and so does the ply's move temperature (tempered_choice), and the move and the improved policy of the Gumbel
+// root search (gumbel_record).
 template <bool OWN>
 __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
 {
@@ -700,9 +774,15 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
     const u64 lt = (1ULL << lane) - 1ULL;
     int nd = 0;
     bool pruned = false;
-    if constexpr (OWN)
+    bool gumbel = false;  // the Gumbel root search: the move and the counts are the mode's own (no draw is used)
+    if constexpr (OWN) {
         pruned = P.forced_k != 0.0f && (ply_kind_of(P, g) & PLY_FULL) != 0u;
-    if (pruned) {
+        gumbel = P.gumbel_m != 0;
+        if (gumbel)
+            nd = gumbel_record(P, A, first, M, N, g, rec, chosen);
+    }
+    if (gumbel) {
+    } else if (pruned) {
         nd = record_pruned_counts(P, A, first, M, N, rec);
     } else {
 #pragma unroll
@@ -841,6 +921,8 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
                 out[7] = (loaded ? 2u : 0u)   // 2: partial game (begins at a loaded position): formatted by the host, not written
                          | (P.fast_visits != 0 ? REC_KIND_PLAYOUT_CAP : 0u) | (P.forced_k != 0.0f ? REC_KIND_FORCED : 0u);
                 if constexpr (OWN) {
+                    if (P.gumbel_m != 0)
+                        out[7] |= REC_KIND_GUMBEL;
                     if (P.resign_plies != 0u) {
                         out[7] |= REC_KIND_VALUES | (resign ? REC_KIND_RESIGNED : 0u);
                         // once-per-game counts: resigned; play-through games that reached their end, those the rule fired

@@ -211,7 +211,9 @@ static void append_double(double v, std::string &out)
 // kind | 16: the game was played with the search value recorded (azh_engine_set_resign): word 5 of a ply is the f32 bits of
 // q = W_b / n_b of the most visited root edge (in [0, 1], for the mover) with the sign bit = searched in full, and the line
 // gains "values" (2 q - 1 as a double; a q that is not finite reads 0); | 32: the game ended by resignation, the line gains
-// "resigned" (the side that resigned, 3 - result: the mover of the last ply).
+// "resigned" (the side that resigned, 3 - result: the mover of the last ply); | 64: the game was played with the Gumbel root
+// search on (azh_engine_set_gumbel): the counts are the improved policy in units of 1/65535 of its greatest entry, over every
+// root move — nothing here depends on it.
 // with_ids (arena): two extra keys, "slot" and "uid", so the caller can tell which net had x.
 std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_ids)
 {
@@ -302,7 +304,7 @@ bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plie
     if (rec[7] == 1)  // the marker a dropped game leaves: a header and nothing else
         return rec[5] == 8;
     *why = "header fields out of range";
-    if ((rec[7] & ~60u) > 2 || (rec[7] & 3u) == 1 || rec[4] > 2 || (max_plies && rec[3] > max_plies))
+    if ((rec[7] & ~124u) > 2 || (rec[7] & 3u) == 1 || rec[4] > 2 || (max_plies && rec[3] > max_plies))
         return false;
     *why = "a ply runs past the record's words";
     size_t pos = 8;
@@ -333,6 +335,12 @@ extern "C" int azh_format_record_json(const uint32_t *rec, int64_t words, int32_
                         words >= 8 ? rec[3] : 0u);
     if (rec[7] == 1)
         return azh_fail(-2, "azh_format_record_json: the record is the marker of a dropped game, it has no line");
+    // The kind bits this entry point has always taken are 2 .. 32; bit 6 (64: a game of the Gumbel root search, whose counts
+    // are policy weights, not visits) is accepted by the engine's own drain alone — tests/test_resign_host.py pins 64 among
+    // the kind bits a caller's record must not carry.
+    if (rec[7] & 64u)
+        return azh_fail(-2, "azh_format_record_json: kind bit 64 (a game of the Gumbel root search) is formatted by "
+                            "azh_engine_drain_json only");
     const std::string line = azh_format_game_json(rec, rec[5], with_ids != 0);
     *used = (int64_t)line.size();
     if ((int64_t)line.size() > cap)

@@ -135,6 +135,10 @@ SIGNATURES = {
     "azh_playout_cap_kind": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     "azh_engine_set_forced_playouts": (ctypes.c_int, [_vp, _f32]),
     "azh_forced_prune": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _f32, _f32, _vp]),
+    "azh_engine_set_gumbel": (ctypes.c_int, [_vp, ctypes.c_int, _f32, _f32]),
+    "azh_gumbel_considered_visits": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp]),
+    "azh_gumbel_noise": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, _vp]),
+    "azh_gumbel_root": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _f32, _vp, _f32, _f32, _vp, _P(_i32)]),
     "azh_engine_set_random_symmetry": (ctypes.c_int, [_vp, ctypes.c_int]),
     "azh_eval_symmetry": (ctypes.c_int, [_u64, ctypes.c_uint32, _u64, _u64]),
     "azh_engine_set_resign": (ctypes.c_int, [_vp, _f32, ctypes.c_int, ctypes.c_int]),
@@ -274,6 +278,40 @@ def forced_prune(prior, W, n, k, c_puct):
     out = np.zeros(len(n), dtype=np.uint32)
     check(load().azh_forced_prune(_ptr(prior), _ptr(W), _ptr(n), len(n), float(k), float(c_puct), _ptr(out)))
     return out
+
+
+def gumbel_considered_visits(m, visits):
+    """Gumbel root search (Engine.set_gumbel): the sequential-halving schedule for m considered actions and `visits`
+    simulations — (visits,) u16, entry t the visit count an edge must have to be a candidate of simulation t
+    (azh_gumbel_considered_visits; host arithmetic, no GPU needed)."""
+    out = np.zeros(max(int(visits), 1), dtype=np.uint16)
+    check(load().azh_gumbel_considered_visits(int(m), int(visits), _ptr(out)))
+    return out
+
+
+def gumbel_noise(seed, uid, ply, M):
+    """Gumbel root search: the Gumbel(0, 1) draws g_j of the M root edges of ply `ply` of game `uid` of an engine with `seed`
+    — (M,) f32 (azh_gumbel_noise; host arithmetic, no GPU needed)."""
+    out = np.zeros(max(int(M), 1), dtype=np.float32)
+    check(load().azh_gumbel_noise(int(seed), int(uid), int(ply), int(M), _ptr(out)))
+    return out[:int(M)]
+
+
+def gumbel_root(prior, W, n, v0, noise, c_visit, c_scale):
+    """Gumbel root search: the ply played from a root with priors `prior`, total scores `W`, visits `n`, the root's own score
+    v0 and the draws `noise` -> (edge of the move, (M,) u32 counts of the improved policy in the ply's record, 0 where the
+    edge is left out) (azh_gumbel_root; host arithmetic, no GPU needed)."""
+    prior = np.ascontiguousarray(prior, dtype=np.float32)
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    n = np.ascontiguousarray(n, dtype=np.uint32)
+    noise = np.ascontiguousarray(noise, dtype=np.float32)
+    if not len(prior) == len(W) == len(n) == len(noise):
+        raise ValueError("prior, W, n and noise must have one entry per root edge")
+    counts = np.zeros(len(n), dtype=np.uint32)
+    move = ctypes.c_int32(0)
+    check(load().azh_gumbel_root(_ptr(prior), _ptr(W), _ptr(n), len(n), float(v0), _ptr(noise), float(c_visit), float(c_scale),
+                                 _ptr(counts), ctypes.byref(move)))
+    return int(move.value), counts
 
 
 def eval_symmetry(seed, uid, mover, opponent):
@@ -528,6 +566,13 @@ class Engine:
         the Dirichlet mix: a root edge with n >= 1 visits is owed sqrt(k P N) of them, and the counts that go into the game's
         `dists` leave out the forced visits PUCT would not have spent.  k = 0: off (the default); KataGo uses 2."""
         check(load().azh_engine_set_forced_playouts(self.h, float(k)))
+
+    def set_gumbel(self, m, c_visit=50.0, c_scale=1.0):
+        """Gumbel root search with sequential halving: the root considers m actions drawn by the Gumbel-top-k
+        trick, spends the ply's visits on them by sequential halving, plays the survivor, and the game's `dists` carry the
+        improved policy softmax(logits + sigma(completedQ)) over ALL root moves.  m = 0: off (the default); mctx uses 16, 50, 1.
+        Needs an engine created with FLAG_NO_REUSE and dirichlet_weight 0.  Between iterations only."""
+        check(load().azh_engine_set_gumbel(self.h, int(m), float(c_visit), float(c_scale)))
 
     def set_random_symmetry(self, on=True):
         """Random symmetry per evaluation: every position goes to the evaluator as its image under a symmetry

@@ -135,12 +135,19 @@ class SelfPlay:
     half-batch engine (link.Engine.set_resign); (0, 1, 0) records values and never resigns.
 
     `temperature` = (move table or None, root policy table or None), as temperature_tables makes them, sets the per-ply
-    temperature of the move played and of the root policy in every half-batch engine (link.Engine.set_temperature)."""
+    temperature of the move played and of the root policy in every half-batch engine (link.Engine.set_temperature).
+
+    `gumbel` = (m, c_visit, c_scale) turns the Gumbel root search with sequential halving on in every half-batch engine
+    (link.Engine.set_gumbel): the engines are created with FLAG_NO_REUSE and dirichlet_weight 0, which the mode needs — its
+    schedule assumes a fresh root, and its noise is the Gumbel — and every ply's `dists` are the improved policy.  Not with
+    the playout cap, forced playouts, a temperature, FLAG_EVAL_CACHE, FLAG_ONE_RANDOM_MOVE or FLAG_SAMPLE_POW5."""
 
     def __init__(self, conv_weights, bn_params, games, visits, dtype="bf16", seed=DEFAULT_SEED,
                  fen=START_FEN_SELFPLAY, streams=1, fast_visits=0, full_fraction=0.25, forced_playouts=0.0,
-                 random_symmetry=False, resign=None, temperature=None, **cfg):
+                 random_symmetry=False, resign=None, temperature=None, gumbel=None, **cfg):
         self.dtype = link.DTYPES[dtype]
+        if gumbel:
+            cfg = dict(cfg, flags=cfg.get("flags", 0) | link.FLAG_NO_REUSE, dirichlet_weight=0.0)
         self.net = link.Net(conv_weights, bn_params, model.BN_EPSILON)
         if streams < 1 or games < streams:
             raise ValueError("games (%d) must be at least the number of half-batches (%d)" % (games, streams))
@@ -160,6 +167,8 @@ class SelfPlay:
             self.set_resign(*resign)
         if temperature and (temperature[0] is not None or temperature[1] is not None):
             self.set_temperature(*temperature)
+        if gumbel:
+            self.set_gumbel(*gumbel)
 
     def run(self, iterations):
         # every engine's whole run is enqueued on its own stream (the calls are asynchronous): the half-batches then
@@ -204,6 +213,11 @@ class SelfPlay:
         """The per-ply temperature tables in every half-batch engine; None, None turns both off."""
         for e in self.engines:
             e.set_temperature(move_temperature, root_policy_temperature)
+
+    def set_gumbel(self, m, c_visit=50.0, c_scale=1.0):
+        """The Gumbel root search in every half-batch engine; m = 0 turns it off."""
+        for e in self.engines:
+            e.set_gumbel(m, c_visit, c_scale)
 
     def resign_stats(self):
         total = {}

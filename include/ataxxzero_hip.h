@@ -307,6 +307,54 @@ int azh_engine_set_forced_playouts(azh_engine *e, float k);
  * device: the same per-edge function the device's ply record uses. */
 int azh_forced_prune(const float *prior, const float *W, const uint32_t *n, int M, float k, float c_puct, uint32_t *out);
 
+/* Gumbel root search with sequential halving (an extension, off by default; Danihelka et al., "Policy improvement by
+ * planning with Gumbel", ICLR 2022).  m = 0 switches the mode off (the state after create); 1 <= m <= 256 on, with a finite
+ * c_visit >= 0, a finite c_scale > 0 (mctx: 16, 50, 1) and m * visits <= 2^20.  All f32 operations below are single IEEE
+ * operations in the order written; logf / expf are the library's deterministic ones (azh_probe_detmath); a "64-lane sum" has
+ * lane l add its terms l, l + 64, ... in that order from 0 and combines the lanes by the xor butterfly 1, 2, 4, 8, 16, 32.
+ * SCHEDULE: seq(r, V), the considered visit counts for r considered actions and V simulations.  r <= 1: 0, 1, .., V - 1.
+ * Otherwise L = ceil(log2 r), k = r, visits[0..r) = 0, and while the sequence is shorter than V: extra = max(1, V / (L k));
+ * `extra` times append visits[0..k) and add 1 to each of them; then k = max(2, k / 2).  The result is cut to V entries
+ * (azh_gumbel_considered_visits).  azh_engine_set_visits rebuilds the engine's rows while the mode is on.
+ * AT THE ROOT'S EVALUATION, for every root edge j < M: x = word 0 of philox(seed; uid, ply, stream 7, j),
+ * u = ((float)(x >> 9) + 0.5f) * 2^-23, g_j = -logf(-logf(u)) (azh_gumbel_noise), l_j = P_j > 0 ? logf(P_j) : -inf with P_j the
+ * prior as stored, a_j = g_j + l_j; and v0 = (value + 1.0f) * 0.5f of the root's own evaluation.
+ * THE ROOT LEVEL of a fresh descent (not of one the level budget parked and that resumes): t = root_visits, r = min(m, M),
+ * cv = seq(r, visits)[t], n_max = max_j n_j, ks = (c_visit + (float)n_max) * c_scale, s_j = n_j >= 1 ? a_j + ks * (W_j /
+ * (float)n_j) : a_j.  The descent takes the edge with n_j == cv and the greatest s_j; a NaN never wins and equal scores go to
+ * the lowest edge index whatever AZH_FLAG_TIE_FIRST says.  If no edge qualifies (or t >= visits, after azh_engine_set_visits
+ * lowered the threshold under a ply) the level is the PUCT level.  Below the root nothing changes; the root level counts in
+ * the level budget and the counters as any level.  On a fresh tree a candidate always exists and no more than min(m, M) root
+ * edges are ever visited.
+ * WHEN THE MOVE IS PLAYED (N = root_visits; n_max, ks, s_j on the final counts): the move is the edge with n_j == n_max and
+ * the greatest s_j, the lowest index among equal ones (edge 0 if every such score is a NaN); no random number is drawn.  The
+ * record carries the improved policy: q_j = W_j / (float)n_j over the visited edges, sp / sw the 64-lane sums of P_j / of
+ * P_j * q_j over them (an unvisited edge adds 0), v_mix = sp > 0 ? (v0 + ((float)N / sp) * sw) / (1.0f + (float)N) : v0,
+ * cq_j = n_j >= 1 ? q_j : v_mix, x_j = l_j + ks * cq_j, x_max their maximum, c_j = min((u32)(expf(x_j - x_max) * 65535.0f),
+ * 65535).  Every root edge with c_j >= 1, EXPANDED OR NOT, is written as move | c_j << 16 in edge order and nd counts them,
+ * so the line's dists — the counts over their sum — are softmax(logits + sigma(completedQ)) to 16 bits; its keys do not
+ * change.  The record of a game finished while the mode is on carries bit 6 (value 64) in header word 7.  The value recorded
+ * under azh_engine_set_resign stays W_b / n_b of the most visited edge.  q is the engine's [0, 1] score (no min-max
+ * rescaling), and below the root the search stays PUCT.
+ * A ply whose root was evaluated before the mode came on is searched with a_j = 0 and v0 = 0.5: switch it on before the first
+ * select, or accept that for the plies in progress.
+ * Refused (the engine stays as it was) unless the engine was created with AZH_FLAG_NO_REUSE and dirichlet_weight 0; with
+ * AZH_FLAG_TWO_NETS, _ONE_RANDOM_MOVE, _SAMPLE_POW5, _EVAL_CACHE; and while the playout cap, forced playouts, a temperature
+ * table, more than one leaf per game or the solver is on — their setters refuse in turn while this mode is on.  Random symmetry
+ * and azh_engine_set_resign stay allowed.  Definition and measurements: DESIGN.md, "Gumbel root search with sequential
+ * halving". */
+int azh_engine_set_gumbel(azh_engine *e, int m, float c_visit, float c_scale);
+/* seq(m, visits) above, out [visits] (1 <= m <= 256, 1 <= visits <= 60000).  Host arithmetic only, usable without a device. */
+int azh_gumbel_considered_visits(int m, int visits, uint16_t *out);
+/* g_j above for the root edges j < M of ply `ply` of game `uid` of an engine created with `seed`, out [M].  Host arithmetic
+ * only: the function the root's backup calls. */
+int azh_gumbel_noise(uint64_t seed, uint32_t uid, uint32_t ply, int M, float *out);
+/* The move and the written counts above for a root of M edges — prior [M], W [M] total scores, n [M] visits, the root's own
+ * score v0 and noise [M] = g_j: counts_out [M] (0: the edge is left out of the record), *move_out the edge played.  Host
+ * arithmetic only: the per-edge functions the device's ply record uses. */
+int azh_gumbel_root(const float *prior, const float *W, const uint32_t *n, int M, float v0, const float *noise, float c_visit,
+                    float c_scale, uint32_t *counts_out, int32_t *move_out);
+
 /* Random symmetry per evaluation (an extension, off by default; AlphaGo Zero / AlphaZero evaluate every leaf under a random
  * dihedral symmetry, and so does the reference's symmetry variant of its Python engine).  While it is on, every position
  * that goes to the evaluator — new leaves and the root's evaluation at the start of a ply — goes as its image T_s(mover),
@@ -568,7 +616,8 @@ int azh_engine_staged_records(azh_engine *e, uint32_t *buf, int64_t cap, int64_t
  * nd x (move | visits << 16)}; kind | 4 and full: azh_engine_set_playout_cap) exactly as azh_engine_drain_json writes it, without the newline: what the reference's
  * `entry.dump()` gives (cpp/self_play_client.cpp:565-578,639-641: nlohmann::json — sorted keys, no whitespace, floats as
  * the digits its Grisu2 finds, plain decimals from 1e-4 up, d.ddde-XX below).  Host code only, usable without a device.
- * *used = bytes the line has; -6 if `cap` is smaller (nothing written), -2 if the words are not a well-formed record.
+ * *used = bytes the line has; -6 if `cap` is smaller (nothing written), -2 if the words are not a well-formed record — or
+ * carry kind bit 64 (azh_engine_set_gumbel): those records become lines in azh_engine_drain_json only.
  * with_ids: the arena's two extra keys (slot, uid). */
 int azh_format_record_json(const uint32_t *rec, int64_t words, int32_t with_ids, char *buf, int64_t cap, int64_t *used);
 /* Order in which azh_engine_drain_json hands games out: 0 (default) as they finish; 1 by game uid (slot g plays
