@@ -620,7 +620,8 @@ inline float gumbel_lane_sum(const float *v, int M)
     return lane[0];
 }
 // The whole root on the host (azh_gumbel_root): the move played and the written counts (counts [M]; 0: left out).  noise [M]:
-// g_j (gumbel_noise).  Returns the edge of the move.
+// g_j (gumbel_noise).  Returns the edge of the move.  A root whose counts would all be 0 (no finite greatest x: every prior 0,
+// every visited W a NaN, ks q out of range) writes 65535 at the move played and nothing else, so no record lacks a target.
 inline int gumbel_root(const float *prior, const float *W, const u32 *n, int M, float v0, const float *noise, float c_visit,
                        float c_scale, u32 *counts)
 {
@@ -649,9 +650,16 @@ inline int gumbel_root(const float *prior, const float *W, const u32 *n, int M, 
         if (tp[j] > x_max)
             x_max = tp[j];
     }
-    for (int j = 0; j < M; j++)
+    u32 any = 0;
+    for (int j = 0; j < M; j++) {
         counts[j] = gumbel_count(tp[j], x_max);
-    return key ? (int)(0xFFFFFFFFu - (u32)key) : 0;
+        any |= counts[j];
+    }
+    const int move = key ? (int)(0xFFFFFFFFu - (u32)key) : 0;
+    // no count at all (x_max is -inf, +inf or every x a NaN, so every x - x_max is a NaN): the record is the move alone
+    if (any == 0u && M > 0)
+        counts[move] = 65535u;
+    return move;
 }
 
 // ---------------------------------------------------------------- random symmetry per evaluation

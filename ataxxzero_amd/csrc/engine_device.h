@@ -634,6 +634,12 @@ __device__ inline int gumbel_record(const EngineParams &P, const Arena &A, u32 f
             rec[REC_HDR_WORDS + nd + __popcll(mask & lt)] = word;
         nd += __popcll(mask);
     }
+    // no count at all (gumbel_root's rule): the record carries the move played with 65535 and nothing else
+    if (nd == 0 && M > 0) {
+        if (lane == 0)
+            rec[REC_HDR_WORDS] = (u32)A.em[first + chosen] | (65535u << 16);
+        nd = 1;
+    }
     return nd;
 }
 

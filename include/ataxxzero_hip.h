@@ -333,7 +333,9 @@ int azh_forced_prune(const float *prior, const float *W, const uint32_t *n, int 
  * cq_j = n_j >= 1 ? q_j : v_mix, x_j = l_j + ks * cq_j, x_max their maximum, c_j = min((u32)(expf(x_j - x_max) * 65535.0f),
  * 65535).  Every root edge with c_j >= 1, EXPANDED OR NOT, is written as move | c_j << 16 in edge order and nd counts them,
  * so the line's dists — the counts over their sum — are softmax(logits + sigma(completedQ)) to 16 bits; its keys do not
- * change.  The record of a game finished while the mode is on carries bit 6 (value 64) in header word 7.  The value recorded
+ * change.  NO RECORD IS WITHOUT A TARGET: when no c_j is >= 1 — there is no finite greatest x_j: every prior is zero (a +inf
+ * logit in the root's row, or a row of NaN), every visited W_j is a NaN, or ks * cq_j overflows, so every x_j - x_max is a
+ * NaN and expf of a NaN is 0 — the record carries the move played with the count 65535 and nothing else (nd = 1).  The record of a game finished while the mode is on carries bit 6 (value 64) in header word 7.  The value recorded
  * under azh_engine_set_resign stays W_b / n_b of the most visited edge.  q is the engine's [0, 1] score (no min-max
  * rescaling), and below the root the search stays PUCT.
  * A ply whose root was evaluated before the mode came on is searched with a_j = 0 and v0 = 0.5: switch it on before the first

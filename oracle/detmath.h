@@ -7,7 +7,8 @@
  * div, sqrt, fma) in a fixed order, so gcc (-ffp-contract=off) and hipcc
  * (-ffp-contract=off) produce identical bits.  The product's own copy lives in
  * ataxxzero_amd/csrc/azh_device.h; the two are kept in step by
- * tests/test_gpu_rules.py::test_detmath_bits_match_oracle.
+ * tests/test_gpu_rules.py::test_detmath_bits_match_oracle and tests/test_gpu_detmath_edges.py; tests/test_detmath_accuracy.py
+ * holds the functions below to float64 log and exp.
  *
  * These functions replace libm's exp/log/gamma sampling that the reference
  * uses in double precision (cpp/self_play_client.cpp:208-218 softmax,

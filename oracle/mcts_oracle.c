@@ -835,6 +835,16 @@ int orc_engine_pending_games(const orc_engine *e) { return e->done_count; }
 
 float orc_probe_expf(float x) { return orc_det_expf(x); }
 float orc_probe_logf(float x) { return orc_det_logf(x); }
+void orc_probe_expf_n(const float *in, int n, float *out)
+{
+    for (int i = 0; i < n; i++)
+        out[i] = orc_det_expf(in[i]);
+}
+void orc_probe_logf_n(const float *in, int n, float *out)
+{
+    for (int i = 0; i < n; i++)
+        out[i] = orc_det_logf(in[i]);
+}
 float orc_probe_gamma(float alpha, uint64_t seed, uint32_t uid, uint32_t ply, uint32_t edge)
 {
     return orc_det_gamma(alpha, (uint32_t)seed, (uint32_t)(seed >> 32), uid, ply, edge);

@@ -126,6 +126,9 @@ int orc_engine_pending_games(const orc_engine *e);
 /* detmath probes for tests */
 float orc_probe_expf(float x);
 float orc_probe_logf(float x);
+/* the same over arrays: out[i] = f(in[i]), i < n (whole-domain sweeps without a call per point) */
+void orc_probe_expf_n(const float *in, int n, float *out);
+void orc_probe_logf_n(const float *in, int n, float *out);
 float orc_probe_gamma(float alpha, uint64_t seed, uint32_t uid, uint32_t ply, uint32_t edge);
 void orc_probe_philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t *out4);
 

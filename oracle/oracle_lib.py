@@ -88,6 +88,7 @@ def lib():
         "orc_engine_pop_game": (ctypes.c_int64, [vp, vp, ctypes.c_int64]),
         "orc_engine_pending_games": (ctypes.c_int, [vp]),
         "orc_probe_expf": (f32, [f32]), "orc_probe_logf": (f32, [f32]),
+        "orc_probe_expf_n": (None, [vp, ctypes.c_int, vp]), "orc_probe_logf_n": (None, [vp, ctypes.c_int, vp]),
         "orc_probe_gamma": (f32, [f32, u64, u32, u32, u32]),
         "orc_probe_philox": (None, [u64, u32, u32, u32, u32, vp]),
     }
@@ -97,6 +98,23 @@ def lib():
         fn.argtypes = args
     _lib = L
     return L
+
+
+def _probe_n(name, x):
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    getattr(lib(), name)(x.ctypes.data, x.size, out.ctypes.data)
+    return out
+
+
+def expf_n(x):
+    """orc_det_expf over a float32 array (its bits are passed as they are, NaN payloads included)"""
+    return _probe_n("orc_probe_expf_n", x)
+
+
+def logf_n(x):
+    """orc_det_logf over a float32 array"""
+    return _probe_n("orc_probe_logf_n", x)
 
 
 # ---------------------------------------------------------------- rules helpers

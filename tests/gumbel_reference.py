@@ -5,7 +5,8 @@ It works on the arrays Engine.tree(g) returns, like tests/vl_reference.py, whose
 it reuses, as tests/forced_reference.py does: select() takes one path — the root level by the schedule's rule, every level
 below it the one-leaf PUCT descent — and root() gives the move a ply plays and the counts its record carries.  Every f32
 operation is a single numpy float32 operation in the order the definition writes it; the logarithm, the exponential and
-Philox are the oracle's probes (held bit for bit against the device by test_detmath_bits_match_oracle), the 64-lane sum is
+Philox are the oracle's probes (held bit for bit against the device by test_detmath_bits_match_oracle and, at the edges and over
+the Gumbel draw's whole grid, by tests/test_gpu_detmath_edges.py), the 64-lane sum is
 tests/priors_reference.wave_sum.
 """
 import ctypes
@@ -189,6 +190,8 @@ def root(prior, W, n, v0, g, c_visit, c_scale):
         x_max = pr._max(x)
         w = (pr.expf((x - x_max).astype(np.float32)) * F32(65535.0)).astype(np.float32)
         counts = np.array([min(int(v), 65535) for v in w], dtype=np.uint32)
+        if not counts.any():
+            counts[move] = 65535     # no count at all: the record carries the move played, alone
         return move, counts
 
 

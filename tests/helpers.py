@@ -146,3 +146,98 @@ def cohort_positions(games, limit, fen=orc.START_FEN_SELFPLAY, seed=1, late_empt
             pick = line[len(line) // 2]
         boards[g], plies[g] = pick[0], pick[1]
     return boards, plies
+
+
+# ---------------------------------------------------------------- evaluations that are not finite
+
+NAN_POS_BITS, NAN_NEG_BITS = 0x7FC00001, 0xFFC00001     # quiet NaNs of both signs with a payload
+_INF_BITS, _NEG_INF_BITS = 0x7F800000, 0xFF800000
+_BIG_BITS = int(np.array([1e30], dtype=np.float32).view(np.uint32)[0])
+
+
+def legal_policy_indices(leaf_board, blockers=0):
+    """the policy indices of the mover's legal moves of a leaf board (mover, opponent), in move order"""
+    p = orc.Pos()
+    p.pieces[0], p.pieces[1], p.blockers, p.turn = int(leaf_board[0]), int(leaf_board[1]), int(blockers), 0
+    return [int(orc.lib().orc_policy_index(int(m))) for m in orc.movegen(p)]
+
+
+class HostileEvaluator:
+    """A base evaluator overridden on a schedule the test controls: __call__(leaf_boards, keys) evaluates the boards with
+    `base` and then, for every row i whose keys[i] is not None, applies the injections schedule(keys[i]) names — an iterable of
+    (name, negative) — to that row's logits and value.  A key is whatever the harness knows of the row's slot before the step
+    ((uid, ply, phase, root visits, ...)), so the engine and a restatement are fed identical bits and every phenomenon occurs by
+    construction.  Bits are written as bits: a NaN is 0x7FC00001, or 0xFFC00001 where `negative`.  seen[(name, negative)]
+    counts the injections into rows with counted[i] set (all rows by default).
+
+        row_nan       every logit a NaN                     row_part_nan  logits 100 .. 299 a NaN
+        row_inf3      +inf at every third logit             row_neginf    every logit -inf
+        row_spike     1e30 at the last legal move's logit (every other prior underflows to zero)
+        row_equal     every logit 0.25                      value_nan / value_pinf / value_ninf / value_plus1 / value_minus1
+    """
+    NAMES = ("row_nan", "row_part_nan", "row_inf3", "row_neginf", "row_spike", "row_equal",
+             "value_nan", "value_pinf", "value_ninf", "value_plus1", "value_minus1")
+
+    def __init__(self, schedule, base=synthetic_evals_distinct, blockers=0):
+        self.schedule, self.base, self.blockers = schedule, base, blockers
+        self.seen = {}
+
+    def __call__(self, leaf_boards, keys, counted=None):
+        lb = np.asarray(leaf_boards, dtype=np.uint64).reshape(-1, 2)
+        logits, values = self.base(lb)
+        lbits, vbits = logits.view(np.uint32), values.view(np.uint32)
+        assert len(keys) == len(lb)
+        for i, key in enumerate(keys):
+            if key is None:
+                continue
+            for name, negative in self.schedule(key):
+                nan = NAN_NEG_BITS if negative else NAN_POS_BITS
+                if name == "row_nan":
+                    lbits[i, :] = nan
+                elif name == "row_part_nan":
+                    lbits[i, 100:300] = nan
+                elif name == "row_inf3":
+                    lbits[i, ::3] = _INF_BITS
+                elif name == "row_neginf":
+                    lbits[i, :] = _NEG_INF_BITS
+                elif name == "row_spike":
+                    legal = legal_policy_indices(lb[i], self.blockers)
+                    if legal:
+                        lbits[i, legal[-1]] = _BIG_BITS
+                elif name == "row_equal":
+                    logits[i, :] = np.float32(0.25)
+                elif name == "value_nan":
+                    vbits[i] = nan
+                elif name == "value_pinf":
+                    vbits[i] = _INF_BITS
+                elif name == "value_ninf":
+                    vbits[i] = _NEG_INF_BITS
+                elif name == "value_plus1":
+                    values[i] = np.float32(1.0)
+                elif name == "value_minus1":
+                    values[i] = np.float32(-1.0)
+                else:
+                    raise ValueError(name)
+                if counted is None or counted[i]:
+                    self.seen[(name, bool(negative))] = self.seen.get((name, bool(negative)), 0) + 1
+        return logits, values
+
+
+def nonfinite_net(seed=3, cell=4, value_channels=(64,), policy_channel=58, policy_layer=16):
+    """(conv, bn) of a one-block, 128-filter random net whose evaluations are not finite for some positions and finite for
+    others.  The value head's 1x1 convolution keeps `value_channels` only, so a cell's activation is exactly 0 where those
+    channels are, and the fc weight of `cell` is +inf: the value is a NaN where that cell's activation is 0 and +-1 elsewhere.
+    The policy head's weight from input channel `policy_channel` to move layer `policy_layer` is +inf: that layer's logit of a
+    cell is +inf where the channel is active there (every prior of a node with such a legal move is then zero) and a NaN where
+    it is not; the other 16 layers stay finite.  The defaults were picked with oracle.net_oracle.forward over the positions of
+    twelve random lines from the late start position of tests/test_gpu_forced_playouts.py: about half of them get a NaN value,
+    about half a +inf logit at a legal move (tests/test_hostile_net.py holds that)."""
+    from ataxxzero_amd import model
+    conv, bn = model.random_init(1, 128, seed=seed, perturb_bn=True)
+    conv = [np.array(a, dtype=np.float32) for a in conv]
+    keep = np.zeros(128, dtype=bool)
+    keep[list(value_channels)] = True
+    conv[4][0, 0, ~keep, 0] = 0.0
+    conv[5][cell, 0] = np.inf
+    conv[3][0, 0, policy_channel, policy_layer] = np.inf
+    return conv, bn

@@ -193,6 +193,70 @@ def test_a_vanishing_scale_gives_the_prior():
         assert (counts[P == 0] == 0).all()
 
 
+NAN, INF = float("nan"), float("inf")
+DENORMAL = float(np.float32(1e-42))
+# (name, prior, W, n, v0, c_visit, c_scale, the record is the move played alone)
+HOSTILE_ROOTS = [
+    ("all priors zero", [0, 0, 0, 0], [1.5, 0.5, 0, 0], [3, 1, 0, 0], 0.5, 50.0, 1.0, True),
+    ("all priors zero, no visits", [0, 0, 0, 0], [0, 0, 0, 0], [0, 0, 0, 0], 0.5, 50.0, 1.0, True),
+    ("W NaN on the most visited edge", [.4, .3, .2, .1], [NAN, 0.5, 0, 0], [3, 1, 0, 0], 0.5, 50.0, 1.0, False),
+    ("W NaN on every visited edge", [.4, .3, .2, .1], [NAN, NAN, 0, 0], [3, 3, 0, 0], 0.5, 50.0, 1.0, True),
+    ("W NaN on every edge", [.4, .3, .2, .1], [NAN, NAN, NAN, NAN], [3, 3, 1, 1], 0.5, 50.0, 1.0, True),
+    ("v0 NaN", [.4, .3, .2, .1], [1.5, 0.5, 0, 0], [3, 1, 0, 0], NAN, 50.0, 1.0, False),
+    ("v0 NaN, no visits", [.4, .3, .2, .1], [0, 0, 0, 0], [0, 0, 0, 0], NAN, 50.0, 1.0, True),
+    ("v0 +inf", [.4, .3, .2, .1], [1.5, 0.5, 0, 0], [3, 1, 0, 0], INF, 50.0, 1.0, True),
+    ("v0 -inf", [.4, .3, .2, .1], [1.5, 0.5, 0, 0], [3, 1, 0, 0], -INF, 50.0, 1.0, False),
+    ("W +inf", [.4, .3, .2, .1], [INF, 0.5, 0, 0], [3, 1, 0, 0], 0.5, 50.0, 1.0, True),
+    ("W -inf", [.4, .3, .2, .1], [-INF, 0.5, 0, 0], [3, 1, 0, 0], 0.5, 50.0, 1.0, False),
+    ("W +inf and -inf", [.4, .3, .2, .1], [INF, -INF, 0, 0], [3, 3, 0, 0], 0.5, 50.0, 1.0, True),
+    ("no visits at all", [.4, .3, .2, .1], [0, 0, 0, 0], [0, 0, 0, 0], 0.5, 50.0, 1.0, False),
+    ("one prior 1 and the rest 0", [0, 1, 0, 0], [0.5, 1.5, 0, 0], [1, 3, 0, 0], 0.5, 50.0, 1.0, False),
+    ("one prior 1, the most visited edge another", [0, 1, 0, 0], [1.5, 0.5, 0, 0], [3, 1, 0, 0], 0.5, 50.0, 1.0, False),
+    ("a denormal prior", [DENORMAL, .5, .5, 0], [1.5, 0.5, 0, 0], [3, 1, 0, 0], 0.5, 50.0, 1.0, False),
+    ("every prior denormal (N / sum P overflows)", [DENORMAL] * 4, [1.5, 0.5, 0, 0], [3, 1, 0, 0], 0.5, 50.0, 1.0, True),
+    ("ks overflows", [.4, .3, .2, .1], [1.5, 0.5, 0, 0], [3, 1, 0, 0], 0.5, 1e30, 1e30, True),
+    ("ks overflows, no visits", [.4, .3, .2, .1], [0, 0, 0, 0], [0, 0, 0, 0], 0.5, 1e30, 1e30, True),
+    ("one move, prior 0", [0], [0], [0], 0.5, 50.0, 1.0, True),
+]
+
+
+@pytest.mark.parametrize("case", HOSTILE_ROOTS, ids=[c[0] for c in HOSTILE_ROOTS])
+def test_a_hostile_root_always_records_a_target(case):
+    """Roots no benign evaluation leaves: the host equals the restatement, the played edge has the most visits, and some count
+    is 65535 — where the improved policy has no finite greatest logit (x_max is -inf, +inf, or every x a NaN) the record is the
+    move played with 65535 and nothing else, never an empty one."""
+    name, P, W, n, v0, c_visit, c_scale, alone = case
+    P, W, n = np.array(P, np.float32), np.array(W, np.float32), np.array(n, np.uint32)
+    for g in (np.zeros(len(n), np.float32), link.gumbel_noise(SEED, 3, 5, len(n))):
+        move, counts = link.gumbel_root(P, W, n, v0, g, c_visit, c_scale)
+        wmove, wcounts = gr.root(P, W, n, v0, g, c_visit, c_scale)
+        assert move == wmove and (counts == wcounts).all(), (name, move, wmove, counts, wcounts)
+        assert n[move] == n.max()
+        assert counts.max() == 65535, (name, counts)
+        assert ((counts != 0).sum() == 1 and counts[move] == 65535) if alone else True, (name, counts)
+        assert alone or (counts[P == 0] == 0).all()
+
+
+def test_a_hostile_root_with_many_edges_and_the_move_beyond_the_first_lane_round():
+    """200 edges, every prior 0, two edges at n_max: 70 with a finite W (its score is -inf, which does win) and 130 with a NaN
+    one (which never does); with both NaN no score wins and the move is edge 0.  Either way the record is that move alone."""
+    M = 200
+    P, W, n = np.zeros(M, np.float32), np.zeros(M, np.float32), np.zeros(M, np.uint32)
+    n[[70, 130]] = 5
+    W[130] = NAN
+    g = link.gumbel_noise(SEED, 1, 1, M)
+    for W70, want in ((2.0, 70), (NAN, 0)):
+        W[70] = W70
+        move, counts = link.gumbel_root(P, W, n, 0.5, g, 50.0, 1.0)
+        wmove, wcounts = gr.root(P, W, n, 0.5, g, 50.0, 1.0)
+        assert move == wmove == want and (counts == wcounts).all()
+        assert (counts != 0).sum() == 1 and counts[move] == 65535
+    P[:] = 1.0 / M
+    W[70] = 2.0
+    move, counts = link.gumbel_root(P, W, n, 0.5, g, 50.0, 1.0)
+    assert move == 70 == gr.root(P, W, n, 0.5, g, 50.0, 1.0)[0] and counts.max() == 65535 and counts[130] == 0
+
+
 @pytest.mark.parametrize("beside", [["--eval-cache"], ["--forced-playouts", "2"], ["--fast-visits", "3"], ["--temperature", "1"],
                                     ["--root-policy-temperature", "1.25"], ["--one-random-move"]])
 def test_the_generator_refuses_what_does_not_go_with_gumbel_actions(tmp_path, beside):
