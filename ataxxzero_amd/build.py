@@ -2,7 +2,7 @@
 
 hipcc cross-compiles without a GPU, so this runs on the CPU-only build box; the
 built .so travels to the GPU box with the repo snapshot.  No cmake, no torch
-extension machinery: five translation units, one link.
+extension machinery: a handful of translation units, one link.
 """
 import os
 import shutil
@@ -22,6 +22,7 @@ UNITS = [
     ("engine.hip", ["-ffp-contract=off"]),
     ("rules_api.hip", ["-ffp-contract=off"]),
     ("net_kernels.hip", []),
+    ("samples.hip", ["-ffp-contract=off"]),
     ("common.cpp", []),
     ("json.cpp", []),
     ("ref_abi.cpp", []),

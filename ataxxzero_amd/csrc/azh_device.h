@@ -519,6 +519,7 @@ __host__ __device__ inline int temperature_pick_root(const u32 *n, int M, float 
 // device share every function but the wave's reductions: gumbel_root is the host's whole root (azh_gumbel_root), select_game
 // and advance_game hold the wave's.
 constexpr u32 STREAM_GUMBEL = 7u;
+constexpr u32 STREAM_SAMPLE_DRAW = 8u;  // azh_samples_draw_gather: counter (step, sample, attempt, 8)
 constexpr int GUMBEL_MAX_ACTIONS = 256;
 constexpr int GUMBEL_MAX_TABLE = 1 << 20;  // entries of the considered-visits table: m * visits
 

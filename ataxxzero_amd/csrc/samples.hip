@@ -1,0 +1,649 @@
+// Device-resident training samples (azh_samples_*; include/ataxxzero_hip.h, DESIGN.md "Device-resident samples"): finished
+// games kept in HBM as bitboards and sparse policy targets, and one kernel that writes a minibatch — features [n][7][7][4],
+// policy [n][7][7][17], value [n][1], f32 — straight into the trainer's tensors, bit for bit what
+// training.make_minibatch_reference builds on the host (train.py:43-77 of the reference).
+//
+// Compiled with -ffp-contract=off: the value target's blend is three IEEE double operations in Python's order.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "azh_device.h"
+#include "azh_host.h"
+
+using namespace azh;
+
+bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plies, const char **why);  // json.cpp
+
+namespace {
+
+constexpr int FEATURES = 196, POLICY = 833, SAMPLE_FLOATS = FEATURES + POLICY + 1;
+constexpr int MAX_ATTEMPTS = 64;  // one per lane of the wave that draws the sample
+constexpr u32 GAME_HAS_FULL = 1u << 8, GAME_HAS_VALUES = 1u << 9;
+
+struct Ply {  // 32 bytes
+    u64 x, o;      // bit = file + 7 * rank, the ring record's layout
+    double value;  // the search's value for the mover in [-1, 1] (games with "values")
+    u32 first_target;
+    u32 targets_flags;  // targets << 8 | AZH_SAMPLES_PLY_*
+};
+
+struct View {  // what the kernels read
+    const uint4 *games;  // {first ply, plies, result | GAME_HAS_*, random_ply + 1}
+    const Ply *plies;
+    const u16 *candidates;  // [first ply + k]: the k-th ply of the game a sample may be drawn from
+    const u32 *candidate_count;
+    const u16 *target_index;
+    const float *target_weight;
+};
+
+// One wave builds sample `i` in LDS and writes it out with coalesced stores; g < 0: the sample is all zeros.
+__device__ void emit_sample(const View &v, float *lds, int i, int g, int p, int s, double blend, float *features,
+                            float *policy, float *value)
+{
+    const int lane = (int)threadIdx.x;
+    for (int k = lane; k < (SAMPLE_FLOATS + 3) / 4; k += WAVE)
+        reinterpret_cast<float4 *>(lds)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    if (g >= 0) {
+        const uint4 game = v.games[g];
+        const Ply ply = v.plies[game.x + (u32)p];
+        const int mover = 1 + (p & 1);  // x (1) moves on even plies
+        const u64 mine = mover == 1 ? ply.x : ply.o, theirs = mover == 1 ? ply.o : ply.x;
+        if (lane < 49) {  // cell [X][Y] of the image shows the cell its source was
+            const int X = lane / 7, Y = lane - 7 * X;
+            const int src = symmetry_source_cell(s, X + 7 * (6 - Y));
+            reinterpret_cast<float4 *>(lds)[lane] =
+                make_float4(1.f, (float)((mine >> src) & 1ULL), (float)((theirs >> src) & 1ULL), 0.f);
+        }
+        const u32 count = ply.targets_flags >> 8;
+        for (u32 t = (u32)lane; t < count; t += WAVE) {
+            const int index = v.target_index[ply.first_target + t];
+            atomicAdd(&lds[FEATURES + symmetry_policy_index(s, index)], v.target_weight[ply.first_target + t]);
+        }
+        if (lane == 0) {
+            const int z = (int)(game.z & 0xFFu) == mover ? 1 : -1;
+            float out = (float)z;
+            if (blend != 0.0 && (game.z & GAME_HAS_VALUES))
+                out = (float)((1.0 - blend) * (double)z + blend * ply.value);
+            lds[FEATURES + POLICY] = out;
+        }
+    }
+    __syncthreads();
+    if (lane < 49)
+        reinterpret_cast<float4 *>(features + (size_t)i * FEATURES)[lane] = reinterpret_cast<const float4 *>(lds)[lane];
+    float *row = policy + (size_t)i * POLICY;  // rows are 3332 bytes apart: four-byte stores, 256 contiguous bytes per wave
+    for (int k = lane; k < POLICY; k += WAVE)
+        row[k] = lds[FEATURES + k];
+    if (lane == 0)
+        value[i] = lds[FEATURES + POLICY];
+}
+
+__global__ __launch_bounds__(WAVE) void k_samples_gather(View v, int n, const int *draws, double blend, float *features,
+                                                         float *policy, float *value)
+{
+    __shared__ __attribute__((aligned(16))) float lds[(SAMPLE_FLOATS + 3) / 4 * 4];
+    const int i = (int)blockIdx.x;
+    if (i >= n)
+        return;
+    emit_sample(v, lds, i, draws[3 * i], draws[3 * i + 1], draws[3 * i + 2], blend, features, policy, value);
+}
+
+// One attempt of sample `i`'s draw from the arrays of `v`, or of the host mirror: the same function on both sides.
+struct Attempt {
+    int game, ply, symmetry;
+    bool ok;
+};
+
+template <class GameAt, class CountAt, class CandidateAt, class FlagsAt>
+__host__ __device__ inline Attempt draw_attempt(u32 k0, u32 k1, u32 step, u32 i, u32 a, u32 first_game, u32 n_games,
+                                                GameAt game_at, CountAt count_at, CandidateAt candidate_at, FlagsAt flags_at)
+{
+    const Philox4 r = philox(k0, k1, step, i, a, STREAM_SAMPLE_DRAW);
+    Attempt out;
+    out.game = (int)(first_game + (u32)(((u64)r.v[0] * n_games) >> 32));
+    out.symmetry = (int)(r.v[2] >> 29);
+    const uint4 game = game_at(out.game);
+    const u32 c = count_at(out.game);
+    out.ply = 0;
+    out.ok = c != 0;  // a game that carries "full" without one full ply gives no sample, whatever else it carries
+    if (out.ok) {
+        out.ply = game.w ? (int)game.w : (int)candidate_at(game.x + (u32)(((u64)r.v[1] * c) >> 32));
+        out.ok = (u32)out.ply < game.y &&
+                 !(flags_at(game.x + (u32)out.ply) & (AZH_SAMPLES_PLY_PASS | AZH_SAMPLES_PLY_BAD));
+    }
+    return out;
+}
+
+__global__ __launch_bounds__(WAVE) void k_samples_draw_gather(View v, int n, u32 k0, u32 k1, u32 step, u32 first_game,
+                                                              u32 n_games, double blend, float *features, float *policy,
+                                                              float *value, int *draws_out, u32 *errors)
+{
+    __shared__ __attribute__((aligned(16))) float lds[(SAMPLE_FLOATS + 3) / 4 * 4];
+    const int i = (int)blockIdx.x;
+    if (i >= n)
+        return;
+    const int lane = (int)threadIdx.x;  // lane a makes attempt a; the first one that succeeds is the draw
+    const Attempt mine = draw_attempt(
+        k0, k1, step, (u32)i, (u32)lane, first_game, n_games, [&](int g) { return v.games[g]; },
+        [&](int g) { return v.candidate_count[g]; }, [&](u32 at) { return (u32)v.candidates[at]; },
+        [&](u32 at) { return v.plies[at].targets_flags & 0xFFu; });
+    const u64 ok = __ballot(mine.ok);
+    const int first = ok ? (int)__builtin_ctzll(ok) : 0;
+    const int g = ok ? __shfl(mine.game, first) : -1;
+    const int p = ok ? __shfl(mine.ply, first) : -1;
+    const int s = ok ? __shfl(mine.symmetry, first) : -1;
+    if (lane == 0) {
+        if (!ok)
+            atomicAdd(errors, 1u);
+        if (draws_out) {
+            draws_out[4 * i] = g;
+            draws_out[4 * i + 1] = p;
+            draws_out[4 * i + 2] = s;
+            draws_out[4 * i + 3] = ok ? first + 1 : MAX_ATTEMPTS;
+        }
+    }
+    emit_sample(v, lds, i, g, p, s, blend, features, policy, value);
+}
+
+template <class T>
+struct DeviceArray {
+    T *d = nullptr;
+    int alloc(size_t n)
+    {
+        AZH_HIP(hipMalloc((void **)&d, std::max<size_t>(n, 1) * sizeof(T)));
+        return 0;
+    }
+    void release()
+    {
+        if (d)
+            (void)hipFree(d);
+        d = nullptr;
+    }
+};
+
+// |1 - sum| >= 1e-3 over the ply's weights added in f32 in ascending index order (equal indices in the order given)
+bool bad_target(const uint16_t *index, const float *weight, size_t n)
+{
+    std::vector<size_t> order(n);
+    for (size_t j = 0; j < n; j++)
+        order[j] = j;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return index[a] < index[b]; });
+    float sum = 0.f;
+    for (size_t j : order)
+        sum += weight[j];
+    return fabsf(1.f - sum) >= 1e-3f;
+}
+
+void move_text(uint32_t mv, std::string &out)  // the key of the move in the game line (json.cpp move_string)
+{
+    const int from = mv & 0xFF, to = (mv >> 8) & 0xFF;
+    out.clear();
+    if (from != to) {
+        out.push_back((char)('a' + from % 7));
+        out.push_back((char)('1' + from / 7));
+    }
+    out.push_back((char)('a' + to % 7));
+    out.push_back((char)('1' + to / 7));
+}
+
+bool board_move(uint32_t mv)  // a clone, or a jump over a distance of exactly two
+{
+    const int from = mv & 0xFF, to = (mv >> 8) & 0xFF;
+    if (from >= 49 || to >= 49)
+        return false;
+    const int dx = abs(to % 7 - from % 7), dy = abs(to / 7 - from / 7);
+    return from == to || std::max(dx, dy) == 2;
+}
+
+}  // namespace
+
+struct azh_samples {
+    int64_t cap_games = 0, cap_plies = 0, cap_targets = 0;
+    int64_t games = 0, plies = 0, targets = 0, bad_plies = 0;
+    DeviceArray<uint4> d_games;
+    DeviceArray<Ply> d_plies;
+    DeviceArray<u16> d_candidates;
+    DeviceArray<u32> d_candidate_count;
+    DeviceArray<u16> d_target_index;
+    DeviceArray<float> d_target_weight;
+    DeviceArray<u32> d_errors;
+    // the host mirror: what a draw is validated against
+    std::vector<uint32_t> h_games;  // [games][4]
+    std::vector<uint8_t> h_flags;   // [plies]
+    // draws on their way to the device: two pinned buffers and two device buffers taken in turn, each guarded by the event
+    // recorded behind the kernel that read it, so the next call never waits for this one
+    hipStream_t stream = nullptr;
+    int *h_stage[2] = {nullptr, nullptr};
+    int *d_stage[2] = {nullptr, nullptr};
+    hipEvent_t used[2] = {nullptr, nullptr};
+    int64_t stage_rows = 0;
+    int turn = 0;
+
+    View view() const
+    {
+        return View{d_games.d, d_plies.d, d_candidates.d, d_candidate_count.d, d_target_index.d, d_target_weight.d};
+    }
+};
+
+static void release_stage(azh_samples *s)
+{
+    for (int k = 0; k < 2; k++) {
+        if (s->used[k]) {
+            (void)hipEventSynchronize(s->used[k]);
+            (void)hipEventDestroy(s->used[k]);
+        }
+        if (s->h_stage[k])
+            (void)hipHostFree(s->h_stage[k]);
+        if (s->d_stage[k])
+            (void)hipFree(s->d_stage[k]);
+        s->used[k] = nullptr;
+        s->h_stage[k] = s->d_stage[k] = nullptr;
+    }
+    s->stage_rows = 0;
+}
+
+static int reserve_stage(azh_samples *s, int64_t rows)
+{
+    if (rows <= s->stage_rows)
+        return 0;
+    release_stage(s);
+    for (int k = 0; k < 2; k++) {
+        AZH_HIP(hipHostMalloc((void **)&s->h_stage[k], (size_t)rows * 3 * sizeof(int), hipHostMallocDefault));
+        AZH_HIP(hipMalloc((void **)&s->d_stage[k], (size_t)rows * 3 * sizeof(int)));
+        AZH_HIP(hipEventCreateWithFlags(&s->used[k], hipEventDisableTiming));
+    }
+    s->stage_rows = rows;
+    return 0;
+}
+
+extern "C" void azh_samples_destroy(azh_samples *s)
+{
+    if (!s)
+        return;
+    if (s->stream)
+        (void)hipStreamSynchronize(s->stream);
+    release_stage(s);
+    s->d_games.release();
+    s->d_plies.release();
+    s->d_candidates.release();
+    s->d_candidate_count.release();
+    s->d_target_index.release();
+    s->d_target_weight.release();
+    s->d_errors.release();
+    if (s->stream)
+        (void)hipStreamDestroy(s->stream);
+    delete s;
+}
+
+extern "C" int azh_samples_create(int64_t cap_games, int64_t cap_plies, int64_t cap_targets, azh_samples **out)
+{
+    if (!out)
+        return azh_fail(-1, "azh_samples_create: null argument");
+    *out = nullptr;
+    if (cap_games < 1 || cap_plies < 1 || cap_targets < 1 || cap_games > 0x7FFFFFFF || cap_plies > 0x7FFFFFFF ||
+        cap_targets > 0x7FFFFFFF)
+        return azh_fail(-1, "azh_samples_create: capacities must lie in [1, 2^31)");
+    if (int rc = azh_require_device())
+        return rc;
+    azh_samples *s = new azh_samples;
+    s->cap_games = cap_games;
+    s->cap_plies = cap_plies;
+    s->cap_targets = cap_targets;
+    int rc = s->d_games.alloc((size_t)cap_games);
+    rc = rc ? rc : s->d_plies.alloc((size_t)cap_plies);
+    rc = rc ? rc : s->d_candidates.alloc((size_t)cap_plies);
+    rc = rc ? rc : s->d_candidate_count.alloc((size_t)cap_games);
+    rc = rc ? rc : s->d_target_index.alloc((size_t)cap_targets);
+    rc = rc ? rc : s->d_target_weight.alloc((size_t)cap_targets);
+    rc = rc ? rc : s->d_errors.alloc(1);
+    if (!rc) {
+        const hipError_t e1 = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+        const hipError_t e2 = e1 == hipSuccess ? hipMemset(s->d_errors.d, 0, sizeof(u32)) : e1;
+        if (e2 != hipSuccess)
+            rc = azh_fail(-100 - (int)e2, "azh_samples_create: %s", hipGetErrorString(e2));
+    }
+    if (rc) {
+        azh_samples_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return 0;
+}
+
+extern "C" int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies,
+                                     const uint64_t *boards, const uint8_t *ply_flags, const double *values,
+                                     const int32_t *target_start, const uint16_t *target_index, const float *target_weight)
+{
+    if (!s || n_games < 0 || n_plies < 0 || (n_games && !games) ||
+        (n_plies && (!boards || !ply_flags || !values)) || !target_start)
+        return azh_fail(-1, "azh_samples_add_games: null argument");
+    const int64_t n_targets = target_start[n_plies];
+    if (target_start[0] != 0 || n_targets < 0 || (n_targets && (!target_index || !target_weight)))
+        return azh_fail(-2, "azh_samples_add_games: target_start must begin at 0 and the targets must be given");
+    // everything is checked and built on the host first: a refused call leaves the store exactly as it was
+    std::vector<uint4> g_words((size_t)n_games);
+    std::vector<u32> g_count((size_t)n_games);
+    std::vector<Ply> p_words((size_t)n_plies);
+    std::vector<u16> p_candidates((size_t)n_plies);
+    std::vector<uint8_t> p_flags((size_t)n_plies);
+    int64_t at = 0, bad = 0;
+    for (int64_t g = 0; g < n_games; g++) {
+        const uint32_t *w = games + 4 * g;
+        const uint32_t result = w[2] & 0xFFu;
+        if ((int64_t)w[0] != at || w[1] < 1 || w[1] > 0xFFFFu || at + w[1] > n_plies || result > 2 ||
+            (w[2] & ~(0xFFu | GAME_HAS_FULL | GAME_HAS_VALUES)) || w[3] > 0xFFFFu)
+            return azh_fail(-2, "azh_samples_add_games: game %lld: plies must follow each other (1 .. 65535 each), result "
+                                "must be 0 .. 2 and the flags known ones", (long long)g);
+        u32 c = 0;
+        for (uint32_t p = 0; p < w[1]; p++) {
+            const int64_t q = at + p;
+            const int64_t lo = target_start[q], hi = target_start[q + 1];
+            if (lo > hi || hi > n_targets || hi - lo > 0xFFFFFF || (ply_flags[q] & ~(AZH_SAMPLES_PLY_PASS | AZH_SAMPLES_PLY_FULL)))
+                return azh_fail(-2, "azh_samples_add_games: ply %lld: targets out of order or unknown flags", (long long)q);
+            for (int64_t t = lo; t < hi; t++)
+                if (target_index[t] >= POLICY)
+                    return azh_fail(-2, "azh_samples_add_games: policy index %u", (unsigned)target_index[t]);
+            uint8_t f = ply_flags[q];
+            if (bad_target(target_index + lo, target_weight + lo, (size_t)(hi - lo))) {
+                f |= AZH_SAMPLES_PLY_BAD;
+                bad += !(f & AZH_SAMPLES_PLY_PASS);  // (a pass has no target and is never a sample: not worth a warning)
+            }
+            p_flags[(size_t)q] = f;
+            p_words[(size_t)q] = Ply{boards[2 * q] & BOARD_MASK, boards[2 * q + 1] & BOARD_MASK, values[q],
+                                     (u32)(s->targets + lo), (u32)(hi - lo) << 8 | f};
+            if (!(w[2] & GAME_HAS_FULL) || (f & AZH_SAMPLES_PLY_FULL))
+                p_candidates[(size_t)(at + c++)] = (u16)p;
+        }
+        g_words[(size_t)g] = make_uint4((u32)(s->plies + at), w[1], w[2], w[3]);
+        g_count[(size_t)g] = c;
+        at += w[1];
+    }
+    if (at != n_plies)
+        return azh_fail(-2, "azh_samples_add_games: the games hold %lld plies, %lld were given", (long long)at, (long long)n_plies);
+    if (s->games + n_games > s->cap_games || s->plies + n_plies > s->cap_plies || s->targets + n_targets > s->cap_targets)
+        return azh_fail(-6, "azh_samples_add_games: %lld games, %lld plies, %lld targets do not fit beside %lld, %lld, %lld "
+                            "in capacities %lld, %lld, %lld", (long long)n_games, (long long)n_plies, (long long)n_targets,
+                        (long long)s->games, (long long)s->plies, (long long)s->targets, (long long)s->cap_games,
+                        (long long)s->cap_plies, (long long)s->cap_targets);
+    // (the copies go behind whatever the store's stream still runs and are waited for: the vectors die with this call.  A
+    // gather in flight on another stream reads only what lies below the counts it was launched with.)
+    if (n_games) {
+        AZH_HIP(hipMemcpyAsync(s->d_games.d + s->games, g_words.data(), (size_t)n_games * sizeof(uint4), hipMemcpyHostToDevice, s->stream));
+        AZH_HIP(hipMemcpyAsync(s->d_candidate_count.d + s->games, g_count.data(), (size_t)n_games * sizeof(u32), hipMemcpyHostToDevice, s->stream));
+    }
+    if (n_plies) {
+        AZH_HIP(hipMemcpyAsync(s->d_plies.d + s->plies, p_words.data(), (size_t)n_plies * sizeof(Ply), hipMemcpyHostToDevice, s->stream));
+        AZH_HIP(hipMemcpyAsync(s->d_candidates.d + s->plies, p_candidates.data(), (size_t)n_plies * sizeof(u16), hipMemcpyHostToDevice, s->stream));
+    }
+    if (n_targets) {
+        AZH_HIP(hipMemcpyAsync(s->d_target_index.d + s->targets, target_index, (size_t)n_targets * sizeof(u16), hipMemcpyHostToDevice, s->stream));
+        AZH_HIP(hipMemcpyAsync(s->d_target_weight.d + s->targets, target_weight, (size_t)n_targets * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    }
+    AZH_HIP(hipStreamSynchronize(s->stream));
+    for (int64_t g = 0; g < n_games; g++) {
+        const uint4 w = g_words[(size_t)g];
+        s->h_games.insert(s->h_games.end(), {w.x, w.y, w.z, w.w});
+    }
+    s->h_flags.insert(s->h_flags.end(), p_flags.begin(), p_flags.end());
+    s->games += n_games;
+    s->plies += n_plies;
+    s->targets += n_targets;
+    s->bad_plies += bad;
+    return 0;
+}
+
+// Ring records -> the arrays azh_samples_add_games takes.  Host code only.
+extern "C" int azh_samples_pack_records(const uint32_t *rec, int64_t words, int64_t *counts, uint32_t *games,
+                                        uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
+                                        uint16_t *target_index, float *target_weight)
+{
+    if (!counts || (words > 0 && !rec) || words < 0)
+        return azh_fail(-1, "azh_samples_pack_records: null argument");
+    const bool write = games != nullptr;
+    if (write && (!boards || !ply_flags || !values || !target_start || !target_index || !target_weight))
+        return azh_fail(-1, "azh_samples_pack_records: null output array");
+    const int64_t cap_games = counts[0], cap_plies = counts[1], cap_targets = counts[2];
+    // the first walk counts and refuses; nothing is written before the whole buffer has been found well formed
+    int64_t n_games = 0, n_plies = 0, n_targets = 0;
+    for (int64_t pos = 0; pos < words;) {
+        const char *why = nullptr;
+        if (!azh_record_well_formed(rec + pos, (size_t)(words - pos), 0u, &why))
+            return azh_fail(-2, "azh_samples_pack_records: word %lld: %s", (long long)pos, why ? why : "not a record");
+        const uint32_t *r = rec + pos;
+        pos += r[5];
+        if ((r[7] & 1u) || (r[7] & 3u) == 2)  // a dropped game's marker; a game begun at a loaded position: neither has a line
+            continue;
+        if (r[3] < 1 || r[3] > 0xFFFFu || r[6] > 0xFFFFu)
+            return azh_fail(-2, "azh_samples_pack_records: a game of %u plies with result %u and random_ply + 1 = %u", r[3], r[4], r[6]);
+        size_t at = 8;
+        for (uint32_t p = 0; p < r[3]; p++) {
+            const uint32_t nd = r[at + 4] >> 16;
+            for (uint32_t j = 0; j < nd; j++)
+                if (!board_move(r[at + 6 + j] & 0xFFFFu))
+                    return azh_fail(-2, "azh_samples_pack_records: target %#x is no clone and no jump", r[at + 6 + j] & 0xFFFFu);
+            n_targets += nd;
+            at += 6 + nd;
+        }
+        n_games++;
+        n_plies += r[3];
+    }
+    counts[0] = n_games;
+    counts[1] = n_plies;
+    counts[2] = n_targets;
+    if (!write)
+        return 0;
+    if (n_games > cap_games || n_plies > cap_plies || n_targets > cap_targets)
+        return azh_fail(-6, "azh_samples_pack_records: %lld games, %lld plies, %lld targets, the arrays hold %lld, %lld, %lld",
+                        (long long)n_games, (long long)n_plies, (long long)n_targets, (long long)cap_games,
+                        (long long)cap_plies, (long long)cap_targets);
+    int64_t g = 0, q = 0, t = 0;
+    std::vector<std::pair<std::string, uint32_t>> ents;
+    std::string key;
+    target_start[0] = 0;
+    for (int64_t pos = 0; pos < words;) {
+        const uint32_t *r = rec + pos;
+        pos += r[5];
+        if ((r[7] & 1u) || (r[7] & 3u) == 2)
+            continue;
+        const bool valued = (r[7] & 16u) != 0, capped = (r[7] & 4u) != 0;
+        games[4 * g] = (uint32_t)q;
+        games[4 * g + 1] = r[3];
+        games[4 * g + 2] = r[4] | (capped ? GAME_HAS_FULL : 0u) | (valued ? GAME_HAS_VALUES : 0u);
+        games[4 * g + 3] = r[6];
+        g++;
+        size_t at = 8;
+        for (uint32_t p = 0; p < r[3]; p++, q++) {
+            boards[2 * q] = (uint64_t)r[at] | ((uint64_t)r[at + 1] << 32);
+            boards[2 * q + 1] = (uint64_t)r[at + 2] | ((uint64_t)r[at + 3] << 32);
+            const uint32_t nd = r[at + 4] >> 16;
+            const bool full = (valued ? r[at + 5] >> 31 : r[at + 5]) != 0;
+            ply_flags[q] = capped && full ? AZH_SAMPLES_PLY_FULL : 0;  // (the device loop records no pass: a ply is a move)
+            double value = 0.0;
+            if (valued) {
+                const uint32_t bits = r[at + 5] & 0x7FFFFFFFu;
+                float qv;
+                memcpy(&qv, &bits, 4);
+                value = std::isfinite(qv) ? 2.0 * (double)qv - 1.0 : 0.0;
+            }
+            values[q] = value;
+            // the line's "dists" object is written with sorted keys, and parsing it keeps that order
+            ents.clear();
+            uint64_t total = 0;
+            for (uint32_t j = 0; j < nd; j++) {
+                const uint32_t e = r[at + 6 + j];
+                move_text(e & 0xFFFFu, key);
+                ents.emplace_back(key, e);
+                total += e >> 16;
+            }
+            std::sort(ents.begin(), ents.end());
+            for (const auto &e : ents) {
+                target_index[t] = (uint16_t)policy_index(e.second & 0xFFFFu);
+                target_weight[t] = total ? (float)((double)(e.second >> 16) / (double)total) : 0.f;
+                t++;
+            }
+            target_start[q + 1] = (int32_t)t;
+            at += 6 + nd;
+        }
+    }
+    return 0;
+}
+
+extern "C" int azh_samples_add_records(azh_samples *s, const uint32_t *rec, int64_t words)
+{
+    if (!s)
+        return azh_fail(-1, "azh_samples_add_records: null store");
+    int64_t counts[3] = {0, 0, 0};
+    if (int rc = azh_samples_pack_records(rec, words, counts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return rc;
+    std::vector<uint32_t> games((size_t)counts[0] * 4 + 1);
+    std::vector<uint64_t> boards((size_t)counts[1] * 2 + 1);
+    std::vector<uint8_t> flags((size_t)counts[1] + 1);
+    std::vector<double> values((size_t)counts[1] + 1);
+    std::vector<int32_t> start((size_t)counts[1] + 1);
+    std::vector<uint16_t> index((size_t)counts[2] + 1);
+    std::vector<float> weight((size_t)counts[2] + 1);
+    if (int rc = azh_samples_pack_records(rec, words, counts, games.data(), boards.data(), flags.data(), values.data(),
+                                          start.data(), index.data(), weight.data()))
+        return rc;
+    return azh_samples_add_games(s, counts[0], games.data(), counts[1], boards.data(), flags.data(), values.data(),
+                                 start.data(), index.data(), weight.data());
+}
+
+extern "C" int azh_samples_counts(const azh_samples *s, int64_t *out)
+{
+    if (!s || !out)
+        return azh_fail(-1, "azh_samples_counts: null argument");
+    out[0] = s->games;
+    out[1] = s->plies;
+    out[2] = s->targets;
+    out[3] = s->bad_plies;
+    return 0;
+}
+
+extern "C" int azh_samples_mirror(const azh_samples *s, uint32_t *games, uint8_t *ply_flags)
+{
+    if (!s || !games || !ply_flags)
+        return azh_fail(-1, "azh_samples_mirror: null argument");
+    if (!s->h_games.empty())
+        memcpy(games, s->h_games.data(), s->h_games.size() * sizeof(uint32_t));
+    if (!s->h_flags.empty())
+        memcpy(ply_flags, s->h_flags.data(), s->h_flags.size());
+    return 0;
+}
+
+extern "C" int azh_samples_gather(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features,
+                                  float *policy, float *value, uintptr_t stream)
+{
+    if (!s || !draws || !features || !policy || !value)
+        return azh_fail(-1, "azh_samples_gather: null argument");
+    if (n < 1)
+        return azh_fail(-1, "azh_samples_gather: n must be at least 1");
+    if (!(value_blend == value_blend))
+        return azh_fail(-1, "azh_samples_gather: value_blend is not a number");
+    for (int i = 0; i < n; i++) {  // no kernel ever sees an index it cannot serve
+        const int64_t g = draws[3 * i], p = draws[3 * i + 1], sym = draws[3 * i + 2];
+        if (g < 0 || g >= s->games || p < 0 || p >= (int64_t)s->h_games[4 * g + 1] || sym < 0 || sym > 7)
+            return azh_fail(-1, "azh_samples_gather: draw %d (game %lld, ply %lld, symmetry %lld) is out of range", i,
+                            (long long)g, (long long)p, (long long)sym);
+        const uint8_t f = s->h_flags[s->h_games[4 * g] + p];
+        if (f & AZH_SAMPLES_PLY_PASS)
+            return azh_fail(-1, "azh_samples_gather: draw %d (game %lld, ply %lld) is a pass", i, (long long)g, (long long)p);
+        if (f & AZH_SAMPLES_PLY_BAD)
+            return azh_fail(-2, "azh_samples_gather: draw %d (game %lld, ply %lld): policy target does not sum to one", i,
+                            (long long)g, (long long)p);
+    }
+    if (int rc = reserve_stage(s, n))
+        return rc;
+    const int k = s->turn;
+    s->turn ^= 1;
+    AZH_HIP(hipEventSynchronize(s->used[k]));  // the call before the last one: long done in a training loop
+    memcpy(s->h_stage[k], draws, (size_t)n * 3 * sizeof(int));
+    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    AZH_HIP(hipMemcpyAsync(s->d_stage[k], s->h_stage[k], (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_samples_gather, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, s->d_stage[k], value_blend,
+                       features, policy, value);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipEventRecord(s->used[k], st));
+    if (!stream)
+        AZH_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int azh_samples_draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game,
+                                       int64_t n_games, double value_blend, float *features, float *policy, float *value,
+                                       int32_t *draws_out, uintptr_t stream)
+{
+    if (!s || !features || !policy || !value)
+        return azh_fail(-1, "azh_samples_draw_gather: null argument");
+    if (n < 1 || first_game < 0 || n_games < 1 || first_game + n_games > s->games)
+        return azh_fail(-1, "azh_samples_draw_gather: n = %d, games [%lld, %lld) of %lld", n, (long long)first_game,
+                        (long long)(first_game + n_games), (long long)s->games);
+    if (!(value_blend == value_blend))
+        return azh_fail(-1, "azh_samples_draw_gather: value_blend is not a number");
+    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    hipLaunchKernelGGL(k_samples_draw_gather, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, (u32)seed,
+                       (u32)(seed >> 32), step, (u32)first_game, (u32)n_games, value_blend, features, policy, value,
+                       draws_out, s->d_errors.d);
+    AZH_HIP(hipGetLastError());
+    if (!stream)
+        AZH_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+// One sample's draw restated on the host from mirror arrays: arithmetic only, no device and no store.
+extern "C" int azh_samples_draw(uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
+                                const uint32_t *games, int64_t total_games, const uint8_t *ply_flags, int32_t *out)
+{
+    if (!games || !ply_flags || !out)
+        return azh_fail(-1, "azh_samples_draw: null argument");
+    if (first_game < 0 || n_games < 1 || first_game + n_games > total_games || total_games > 0x7FFFFFFF)
+        return azh_fail(-1, "azh_samples_draw: games [%lld, %lld) of %lld", (long long)first_game,
+                        (long long)(first_game + n_games), (long long)total_games);
+    auto game_at = [&](int g) { return make_uint4(games[4 * g], games[4 * g + 1], games[4 * g + 2], games[4 * g + 3]); };
+    auto candidate = [&](int g, uint32_t flag) {  // plies a sample may come from: all, or the full ones of a game with "full"
+        return !(games[4 * g + 2] & GAME_HAS_FULL) || (flag & AZH_SAMPLES_PLY_FULL);
+    };
+    out[0] = out[1] = out[2] = -1;
+    out[3] = MAX_ATTEMPTS;
+    for (uint32_t a = 0; a < (uint32_t)MAX_ATTEMPTS; a++) {
+        int drawn = -1;
+        const Attempt t = draw_attempt(
+            (u32)seed, (u32)(seed >> 32), step, sample, a, (u32)first_game, (u32)n_games, game_at,
+            [&](int g) {
+                drawn = g;
+                u32 c = 0;
+                for (uint32_t p = 0; p < games[4 * g + 1]; p++)
+                    c += candidate(g, ply_flags[games[4 * g] + p]);
+                return c;
+            },
+            [&](u32 at) {  // the k-th candidate of the drawn game, k = at - first ply
+                u32 k = at - games[4 * drawn];
+                for (uint32_t p = 0; p < games[4 * drawn + 1]; p++)
+                    if (candidate(drawn, ply_flags[games[4 * drawn] + p]) && k-- == 0)
+                        return p;
+                return 0u;
+            },
+            [&](u32 at) { return (u32)ply_flags[at]; });
+        if (t.ok) {
+            out[0] = t.game;
+            out[1] = t.ply;
+            out[2] = t.symmetry;
+            out[3] = (int32_t)a + 1;
+            break;
+        }
+    }
+    return 0;
+}
+
+extern "C" int azh_samples_status(azh_samples *s, int64_t *failed)
+{
+    if (!s || !failed)
+        return azh_fail(-1, "azh_samples_status: null argument");
+    u32 n = 0;  // (a blocking copy from the null stream: it waits for the kernels enqueued so far on every blocking stream)
+    AZH_HIP(hipDeviceSynchronize());
+    AZH_HIP(hipMemcpy(&n, s->d_errors.d, sizeof(u32), hipMemcpyDeviceToHost));
+    *failed = (int64_t)n;
+    return 0;
+}

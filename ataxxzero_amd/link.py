@@ -39,6 +39,9 @@ PV_MAX = 32
 ROOT_REPORT_PV = 4 + 4 * MAX_MOVES
 ROOT_REPORT_WORDS = ROOT_REPORT_PV + 1 + 2 * PV_MAX
 ROOT_PROOF_WORDS = 1 + MAX_MOVES   # azh_engine_root_proofs
+HIP_STREAM_LEGACY = 1                                                 # hipStreamLegacy: the null stream as a handle
+SAMPLES_PLY_PASS, SAMPLES_PLY_FULL, SAMPLES_PLY_BAD = 1, 2, 4       # azh_samples_*: a ply's flags
+SAMPLES_GAME_HAS_FULL, SAMPLES_GAME_HAS_VALUES = 1 << 8, 1 << 9     # beside the result in a game's third word
 STAT_NAMES = ["steps", "nn_evals", "levels", "children", "new_moves", "plies", "games", "dropped",
               "edge_overflow", "reroot_nodes", "reroot_edges", "ring_overflow", "cache_hits", "parked", "reroot_spills"]
 
@@ -170,6 +173,19 @@ SIGNATURES = {
     "azh_engine_set_emit_order": (ctypes.c_int, [_vp, ctypes.c_int]),
     "azh_engine_set_positions": (ctypes.c_int, [_vp, _vp, _vp]),
     "azh_engine_set_game_limit": (ctypes.c_int, [_vp, ctypes.c_int64]),
+    "azh_samples_create": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P(_vp)]),
+    "azh_samples_destroy": (None, [_vp]),
+    "azh_samples_add_games": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "azh_samples_pack_records": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "azh_samples_add_records": (ctypes.c_int, [_vp, _vp, ctypes.c_int64]),
+    "azh_samples_counts": (ctypes.c_int, [_vp, _vp]),
+    "azh_samples_mirror": (ctypes.c_int, [_vp, _vp, _vp]),
+    "azh_samples_gather": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp, ctypes.c_size_t]),
+    "azh_samples_draw_gather": (ctypes.c_int, [_vp, ctypes.c_int, _u64, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_double, _vp, _vp, _vp, _vp, ctypes.c_size_t]),
+    "azh_samples_draw": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64, _vp,
+                                        ctypes.c_int64, _vp, _vp]),
+    "azh_samples_status": (ctypes.c_int, [_vp, _P(ctypes.c_int64)]),
     # the reference's ABI, link.py:8-32
     "launch_threads": (None, [ctypes.c_char_p, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int]),
     "get_workload": (ctypes.c_int, []),
@@ -778,3 +794,224 @@ class Engine:
                 break
             lines.extend(bytes(self._json[:used.value]).split(b"\n")[:-1])
         return lines
+
+
+# ------------------------------------------------------------------ device-resident training samples
+
+class SampleArrays:
+    """Games as azh_samples_add_games takes them: games (G, 4) u32 {first ply, plies, result | SAMPLES_GAME_*, random_ply + 1},
+    boards (P, 2) u64, ply_flags (P,) u8, values (P,) f64, target_start (P + 1,) i32, target_index (T,) u16, target_weight
+    (T,) f32."""
+    __slots__ = ("games", "boards", "ply_flags", "values", "target_start", "target_index", "target_weight")
+
+    def __init__(self, games, boards, ply_flags, values, target_start, target_index, target_weight):
+        self.games = np.ascontiguousarray(games, dtype=np.uint32).reshape(-1, 4)
+        self.boards = np.ascontiguousarray(boards, dtype=np.uint64).reshape(-1, 2)
+        self.ply_flags = np.ascontiguousarray(ply_flags, dtype=np.uint8)
+        self.values = np.ascontiguousarray(values, dtype=np.float64)
+        self.target_start = np.ascontiguousarray(target_start, dtype=np.int32)
+        self.target_index = np.ascontiguousarray(target_index, dtype=np.uint16)
+        self.target_weight = np.ascontiguousarray(target_weight, dtype=np.float32)
+
+
+# bit x + 7 (6 - y) of a bitboard is the cell the game line's boards[ply][x + 7 y] names
+_CELL_BIT = np.array([1 << (c % 7 + 7 * (6 - c // 7)) for c in range(49)], dtype=np.uint64)
+
+
+def entries_to_arrays(entries):
+    """Parsed game lines -> SampleArrays, with the conversions of training._entry_arrays (weights np.float32 of the parsed
+    double, "pass" keys skipped, an entry without `dists` a one-hot on the move played), in the order given.  Host only."""
+    from . import training
+    games, boards, flags, values, starts, index, weight = [], [], [], [], [np.zeros(1, dtype=np.int32)], [], []
+    plies = targets = 0
+    for entry in entries:
+        cells, idx, wts, start = training._entry_arrays(entry)
+        n = len(entry["boards"])
+        if n < 1 or cells.shape != (n, 49) or cells.min() < 0 or cells.max() > 2:
+            raise ValueError("an entry needs at least one ply and boards of 49 cells in 0..2")
+        word = int(entry["result"])
+        f = np.array([SAMPLES_PLY_PASS if m == "pass" else 0 for m in entry["moves"][:n]], dtype=np.uint8)
+        if "full" in entry:
+            word |= SAMPLES_GAME_HAS_FULL
+            f |= np.where(np.asarray(entry["full"][:n], dtype=bool), SAMPLES_PLY_FULL, 0).astype(np.uint8)
+        if "values" in entry:
+            word |= SAMPLES_GAME_HAS_VALUES
+            values.append(np.asarray(entry["values"][:n], dtype=np.float64))
+        else:
+            values.append(np.zeros(n, dtype=np.float64))
+        games.append((plies, n, word, entry["random_ply"] + 1 if "random_ply" in entry else 0))
+        boards.append(np.stack([((cells == 1) * _CELL_BIT).sum(axis=1, dtype=np.uint64),
+                                ((cells == 2) * _CELL_BIT).sum(axis=1, dtype=np.uint64)], axis=1))
+        flags.append(f)
+        starts.append(start[1:] + targets)
+        index.append(idx.astype(np.uint16))
+        weight.append(wts)
+        plies += n
+        targets += int(start[-1])
+
+    def cat(parts, dtype):
+        return np.concatenate(parts).astype(dtype, copy=False) if parts else np.zeros(0, dtype=dtype)
+    return SampleArrays(np.array(games, dtype=np.uint32).reshape(-1, 4), cat(boards, np.uint64).reshape(-1, 2),
+                        cat(flags, np.uint8), cat(values, np.float64), cat(starts, np.int32), cat(index, np.uint16),
+                        cat(weight, np.float32))
+
+
+def pack_records(records):
+    """Ring records (Engine.staged_records) -> SampleArrays holding what parsing the games' own lines would give
+    (azh_samples_pack_records; host code, no GPU needed)."""
+    rec = np.ascontiguousarray(records, dtype=np.uint32).ravel()
+    counts = np.zeros(3, dtype=np.int64)
+    check(load().azh_samples_pack_records(_ptr(rec), rec.size, _ptr(counts), None, None, None, None, None, None, None))
+    g, p, t = (int(c) for c in counts)
+    a = SampleArrays(np.zeros((g, 4), np.uint32), np.zeros((p, 2), np.uint64), np.zeros(p, np.uint8), np.zeros(p),
+                     np.zeros(p + 1, np.int32), np.zeros(max(t, 1), np.uint16), np.zeros(max(t, 1), np.float32))
+    games = a.games if g else np.zeros((1, 4), np.uint32)      # (non-null: a null `games` asks for the counts only)
+    check(load().azh_samples_pack_records(_ptr(rec), rec.size, _ptr(counts), _ptr(games), _ptr(a.boards), _ptr(a.ply_flags),
+                                          _ptr(a.values), _ptr(a.target_start), _ptr(a.target_index), _ptr(a.target_weight)))
+    a.target_index, a.target_weight = a.target_index[:t], a.target_weight[:t]
+    return a
+
+
+def samples_draw(seed, step, sample, first_game, n_games, games, ply_flags):
+    """One sample's draw of SampleStore.draw_gather restated on the host from mirror arrays -> (game, ply, symmetry, attempts
+    used), (-1, -1, -1, 64) when all 64 attempts fail (azh_samples_draw; host arithmetic, no GPU needed)."""
+    games = np.ascontiguousarray(games, dtype=np.uint32).reshape(-1, 4)
+    ply_flags = np.ascontiguousarray(ply_flags, dtype=np.uint8)
+    out = np.zeros(4, dtype=np.int32)
+    check(load().azh_samples_draw(int(seed), int(step), int(sample), int(first_game), int(n_games), _ptr(games), len(games),
+                                  _ptr(ply_flags), _ptr(out)))
+    return tuple(int(v) for v in out)
+
+
+def hip_runtimes():
+    """The HIP runtime libraries mapped into this process (paths).  torch ships its own: imported BEFORE this package's
+    library is loaded, both resolve to that one copy (same soname) and share streams and memory; loaded after it, the
+    process holds two runtimes that know nothing of each other's handles."""
+    with open("/proc/self/maps") as f:
+        return sorted({line.split()[-1] for line in f if "libamdhip64" in line})
+
+
+_shared_runtime = None
+
+
+def require_torch_runtime():
+    """Raises unless torch and this library run on ONE HIP runtime: a SampleStore enqueues on torch's streams and writes
+    torch's tensors."""
+    global _shared_runtime
+    if _shared_runtime is None:
+        import torch  # noqa: F401  (its runtime is mapped by the import)
+        load()
+        _shared_runtime = hip_runtimes()
+    if len(_shared_runtime) != 1:
+        raise AzhError("torch and libataxxzero_hip.so hold separate HIP runtimes in this process (%s): import torch before "
+                       "anything loads the library (train.py does), or use a fresh process" % ", ".join(_shared_runtime))
+
+
+class SampleStore:
+    """Finished games in device memory and the kernel that writes minibatches from them ("Device-resident
+    samples").  Outputs are torch tensors on the GPU: features (n, 7, 7, 4), policy (n, 7, 7, 17), value (n, 1), f32.
+    The process must hold one HIP runtime (require_torch_runtime)."""
+
+    def __init__(self, cap_games, cap_plies, cap_targets):
+        require_torch_runtime()
+        h = ctypes.c_void_p()
+        check(load().azh_samples_create(int(cap_games), int(cap_plies), int(cap_targets), ctypes.byref(h)))
+        self.h = h
+        self._mirror = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            load().azh_samples_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_arrays(self, a):
+        self._mirror = None
+        check(load().azh_samples_add_games(self.h, len(a.games), _ptr(a.games), len(a.ply_flags), _ptr(a.boards),
+                                           _ptr(a.ply_flags), _ptr(a.values), _ptr(a.target_start), _ptr(a.target_index),
+                                           _ptr(a.target_weight)))
+
+    def add_entries(self, entries):
+        """Parsed game lines, in the order given (entries_to_arrays)."""
+        self.add_arrays(entries_to_arrays(entries))
+
+    def add_records(self, records):
+        """Ring records as Engine.staged_records returns them (azh_samples_add_records)."""
+        rec = np.ascontiguousarray(records, dtype=np.uint32).ravel()
+        self._mirror = None
+        check(load().azh_samples_add_records(self.h, _ptr(rec), rec.size))
+
+    def counts(self):
+        out = np.zeros(4, dtype=np.int64)
+        check(load().azh_samples_counts(self.h, _ptr(out)))
+        return {"games": int(out[0]), "plies": int(out[1]), "targets": int(out[2]), "bad_plies": int(out[3])}
+
+    def mirror(self):
+        """-> (games (G, 4) u32, ply_flags (P,) u8): the host's copy of what a draw is checked against."""
+        if self._mirror is None:
+            c = self.counts()
+            games, flags = np.zeros((max(c["games"], 1), 4), np.uint32), np.zeros(max(c["plies"], 1), np.uint8)
+            check(load().azh_samples_mirror(self.h, _ptr(games), _ptr(flags)))
+            self._mirror = games[:c["games"]], flags[:c["plies"]]
+        return self._mirror
+
+    @staticmethod
+    def outputs(n, device="cuda"):
+        import torch
+        return (torch.empty((n, 7, 7, 4), dtype=torch.float32, device=device),
+                torch.empty((n, 7, 7, 17), dtype=torch.float32, device=device),
+                torch.empty((n, 1), dtype=torch.float32, device=device))
+
+    @staticmethod
+    def _pointers(out, n):
+        import torch
+        shapes = ((n, 7, 7, 4), (n, 7, 7, 17), (n, 1))
+        for t, shape in zip(out, shapes):
+            if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError("out must be contiguous float32 GPU tensors of shapes %r" % (shapes,))
+        # (torch's default stream is the null stream, handle 0 — which the C entry points read as "the store's own stream,
+        # and wait": hipStreamLegacy names the null stream itself, so the call is ordered behind torch's work and returns)
+        return [ctypes.c_void_p(t.data_ptr()) for t in out], torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY
+
+    def gather(self, draws, value_blend=0.0, out=None):
+        """The minibatch of the draws (n, 3) of (game, ply, symmetry), enqueued on torch's current stream; `out`: the three
+        tensors to write (fresh ones by default).  A draw on a bad ply raises the host pipeline's AssertionError."""
+        draws = np.ascontiguousarray(draws, dtype=np.int32).reshape(-1, 3)
+        out = self.outputs(len(draws)) if out is None else out
+        ptrs, stream = self._pointers(out, len(draws))
+        rc = load().azh_samples_gather(self.h, len(draws), _ptr(draws), float(value_blend), *ptrs, stream)
+        if rc == -2:
+            raise AssertionError("policy target does not sum to one")
+        check(rc)
+        return out
+
+    def draw_gather(self, n, seed, step, first_game, n_games, value_blend=0.0, out=None, draws_out=None):
+        """A minibatch of n samples drawn on the device from games [first_game, first_game + n_games) with Philox keyed by
+        `seed` at counter `step`; draws_out: an (n, 4) int32 GPU tensor that receives (game, ply, symmetry, attempts)."""
+        import torch
+        out = self.outputs(n) if out is None else out
+        ptrs, stream = self._pointers(out, n)
+        if draws_out is not None and not (draws_out.is_cuda and draws_out.dtype == torch.int32 and
+                                          tuple(draws_out.shape) == (n, 4) and draws_out.is_contiguous()):
+            raise ValueError("draws_out must be a contiguous int32 GPU tensor of shape (n, 4)")
+        check(load().azh_samples_draw_gather(self.h, int(n), int(seed), int(step), int(first_game), int(n_games),
+                                             float(value_blend), *ptrs,
+                                             ctypes.c_void_p(draws_out.data_ptr()) if draws_out is not None else None, stream))
+        return out
+
+    def draw(self, seed, step, sample, first_game, n_games):
+        """What draw_gather draws for one sample, from the host mirror (samples_draw)."""
+        games, flags = self.mirror()
+        return samples_draw(seed, step, sample, first_game, n_games, games, flags)
+
+    def status(self):
+        """Samples of draw_gather that found no drawable ply in 64 attempts (written as zeros) since the store was made;
+        waits for the device."""
+        n = ctypes.c_int64(0)
+        check(load().azh_samples_status(self.h, ctypes.byref(n)))
+        return int(n.value)

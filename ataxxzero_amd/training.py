@@ -286,6 +286,72 @@ def make_minibatch(entries, size, value_blend=0.0):
     return feats.reshape(size, BOARD, BOARD, 4), pols.reshape(size, BOARD, BOARD, MOVE_TYPES), vals
 
 
+# ---------------------------------------------------------------- device-resident samples (link.SampleStore)
+
+DEVICE_DRAW_SEED = 123456789          # train.py --device-draws: the Philox key of the draws made on the device
+
+
+def _draw_tables(store):
+    """The store's host mirror as plain Python values, built once per state of the store: per game (first ply, plies, has
+    "full", random_ply + 1), the ply flags as bytes, and the full plies of the games that carry "full" (on first use)."""
+    from . import link
+    mirror = store.mirror()
+    tables = getattr(store, "_draw_tables", None)
+    if tables is None or tables[0] is not mirror:
+        games = [(int(a), int(n), bool(w & link.SAMPLES_GAME_HAS_FULL), int(r)) for a, n, w, r in mirror[0]]
+        tables = store._draw_tables = (mirror, games, mirror[1].tobytes(), {})
+    return tables[1:]
+
+
+def make_minibatch_device(store, first_game, n_games, size, value_blend=0.0, out=None, draws="reference", seed=DEVICE_DRAW_SEED,
+                          step=0):
+    """`size` samples of the games [first_game, first_game + n_games) of a link.SampleStore, written by its kernel into the three
+    GPU tensors `out` (fresh ones by default) -> out.  draws="reference": Python's `random` is consumed exactly as make_minibatch
+    consumes it for entries[first_game:first_game + n_games] — game, ply among the candidates, the random_ply replacement, the
+    pass rejection, symmetry — so the same games give the same minibatches, bit for bit; draws="device": the kernel draws with
+    Philox keyed by `seed` at counter `step` (SampleStore.draw_gather)."""
+    if draws == "device":
+        return store.draw_gather(size, seed, step, first_game, n_games, value_blend, out=out)
+    if draws != "reference":
+        raise ValueError("draws must be \"reference\" or \"device\"")
+    from . import link
+    games, flags, full_plies = _draw_tables(store)
+    choices = range(first_game, first_game + n_games)
+    rows = []
+    while len(rows) < size:
+        g = random.choice(choices)                          # the reference's draws, in its order (train.py:45-60)
+        first, plies, has_full, random_ply_1 = games[g]
+        if not has_full:
+            ply = random.randrange(plies)
+        else:
+            full = full_plies.get(g)
+            if full is None:
+                full = full_plies[g] = [p for p in range(plies) if flags[first + p] & link.SAMPLES_PLY_FULL]
+            if not full:
+                continue
+            ply = full[random.randrange(len(full))]
+        if random_ply_1:
+            ply = random_ply_1
+            if ply >= plies:
+                raise IndexError("random_ply + 1 = %d in a game of %d plies" % (ply, plies))
+        if flags[first + ply] & link.SAMPLES_PLY_PASS:
+            continue
+        rows.append((g, ply, random.randrange(8)))
+    return store.gather(np.asarray(rows, dtype=np.int32), value_blend, out=out)
+
+
+def _fill_store(entries, log):
+    from . import link
+    link.require_gpu()
+    arrays = link.entries_to_arrays(entries)
+    store = link.SampleStore(max(len(arrays.games), 1), max(len(arrays.ply_flags), 1), max(len(arrays.target_index), 1))
+    store.add_arrays(arrays)
+    c = store.counts()
+    log("Device samples: %i games, %i plies, %i policy targets in device memory; %i plies whose target does not sum to one."
+        % (c["games"], c["plies"], c["targets"], c["bad_plies"]))
+    return store
+
+
 # ---------------------------------------------------------------- the network (model.py:38-101)
 
 class Network(nn.Module):
@@ -343,6 +409,13 @@ class Network(nn.Module):
         return cw, bn
 
 
+def link_outputs(store, n, device):
+    """The three tensors a store's kernel writes a minibatch of n samples into, on `device`."""
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("device samples need a GPU: the gather has no CPU path")
+    return store.outputs(n, device)
+
+
 def losses(net, features, policies, values):
     """model.py:81-93: (policy cross-entropy, value MSE, 1e-4 * sum(l2_loss(w)) over trainable variables)."""
     x = features.permute(0, 3, 1, 2)
@@ -356,7 +429,10 @@ def losses(net, features, policies, values):
 
 
 def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learning_rate=0.001, blocks=12, filters=128,
-          reference_bn_affine=False, device=None, log=print, value_blend=0.0):
+          reference_bn_affine=False, device=None, log=print, value_blend=0.0, device_samples=False, device_draws=False):
+    """device_samples: the entries are put into a link.SampleStore once and every minibatch is written by its kernel into
+    tensors allocated once (make_minibatch_device) — the same minibatches as without it, no per-step host-to-device copy of
+    the batch; device_draws (implies device_samples): the kernel also draws the samples.  Both need a GPU."""
     random.seed(123456789)                                                # train.py:103
     entries = load_entries(games_paths)
     ply_count = sum(len(e["moves"]) for e in entries)
@@ -380,8 +456,34 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
     def to_dev(batch):
         return tuple(torch.from_numpy(a).to(device) for a in batch)
 
+    store = _fill_store(entries, log) if device_samples or device_draws else None
+    if store is not None:                                                 # validation: games [0, 10); training: [10, n)
+        draws = "device" if device_draws else "reference"
+        n_test = min(10, len(entries))
+        if len(entries) <= n_test:
+            raise ValueError("device samples need more than %d games" % n_test)
+        train_out = link_outputs(store, minibatch_size, device)
+
+        def next_batch(step):
+            return make_minibatch_device(store, n_test, len(entries) - n_test, minibatch_size, value_blend, train_out, draws,
+                                         step=1 + step)
+
+        def check_store():
+            failed = store.status() if device_draws else 0
+            if failed:
+                raise RuntimeError("%d samples found no drawable ply in 64 attempts" % failed)
+    else:
+        def next_batch(step):
+            return to_dev(make_minibatch(train_entries, minibatch_size, value_blend))
+
+        def check_store():
+            pass
+
     random.seed(123456789)                                                # train.py:131
-    val_set = to_dev(make_minibatch(test_entries, 2048, value_blend))
+    if store is not None:
+        val_set = make_minibatch_device(store, 0, n_test, 2048, value_blend, link_outputs(store, 2048, device), draws, step=0)
+    else:
+        val_set = to_dev(make_minibatch(test_entries, 2048, value_blend))
     log("")
     log("Model dimensions: %i filters, %i blocks, %i parameters." % (
         filters, blocks, sum(int(np.prod(a.shape)) for a in cw)))
@@ -393,12 +495,14 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
             with torch.no_grad():
                 pl, vl, _ = losses(net, *val_set)
             log("Step: %4i -- loss: %.6f  (policy: %.6f  value: %.6f)" % (step_number, float(pl + vl), float(pl), float(vl)))
+            check_store()
         net.train()
-        batch = to_dev(make_minibatch(train_entries, minibatch_size, value_blend))
+        batch = next_batch(step_number)
         pl, vl, reg = losses(net, *batch)
         opt.zero_grad(set_to_none=True)
         (pl + vl + reg).backward()
         opt.step()
+    check_store()
     model.save_model(new_path, *net.to_numpy())
     log("\x1b[35mSaved model to:\x1b[0m %s" % new_path)
     return net

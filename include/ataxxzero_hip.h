@@ -649,6 +649,82 @@ int azh_engine_set_emit_order(azh_engine *e, int by_uid);
  *  - With no limit, or a limit >= the slot count when positions are loaded, nothing differs from an engine without one. */
 int azh_engine_set_game_limit(azh_engine *e, int64_t games);
 
+/* ------------------------------------------------------------------ device-resident training samples
+ * (an extension; nothing above changes).  A store keeps finished games in device memory — per game {first ply, plies,
+ * result | AZH_SAMPLES_GAME_*, random_ply + 1 (0: none)}, per ply the two bitboards in the ring record's layout (bit
+ * x + 7 (6 - y) is the cell boards[ply][x + 7 y] of the game line), its flags AZH_SAMPLES_PLY_*, the recorded value as a
+ * double and its policy target as (flat index 119 x + 17 y + layer: u16, weight: f32) pairs — and one kernel writes a
+ * minibatch from it straight into the trainer's tensors: features [n][7][7][4], policy [n][7][7][17], value [n][1], f32,
+ * bit for bit what the host pipeline (training.make_minibatch_reference; the reference's train.py:43-77) builds from the
+ * same games for the same draws: plane 0 ones, plane 1 the mover's stones (the mover is 1 + ply % 2), plane 2 the
+ * opponent's, plane 3 zeros, the board under symmetry s (bit 0 mirrors x, bit 1 mirrors y, bit 2 then transposes); each
+ * weight at azh_symmetry_policy_index(s, index); the value z = +-1 (result == mover), or with value_blend = L != 0 and a
+ * game that has values (1 - L) * z + L * v in double, in that order, rounded once to f32.
+ * The host keeps a mirror of the per-game words and the ply flags (a few bytes per ply) and checks every draw against it:
+ * no kernel ever sees an index it cannot serve.
+ * A ply is BAD when the f32 sum of its weights, added in ascending index order, is off from 1 by at least 1e-3: the host
+ * finds that at ingest.  (The host pipeline sums the 833 cells pairwise: for a sum within an ulp or so of the edge the two
+ * may disagree; agreement exactly at the edge is not claimed.)
+ * Codes: -1 bad argument, -2 malformed input (azh_samples_gather: a draw on a bad ply), -6 capacity. */
+typedef struct azh_samples azh_samples;
+enum { AZH_SAMPLES_PLY_PASS = 1, AZH_SAMPLES_PLY_FULL = 2, AZH_SAMPLES_PLY_BAD = 4 };
+enum { AZH_SAMPLES_GAME_HAS_FULL = 1 << 8, AZH_SAMPLES_GAME_HAS_VALUES = 1 << 9 };
+int azh_samples_create(int64_t cap_games, int64_t cap_plies, int64_t cap_targets, azh_samples **out);
+void azh_samples_destroy(azh_samples *s);
+/* Appends games from host arrays: games [n_games][4] as above with the first ply counted from this call's arrays; boards
+ * [n_plies][2] (x, o); ply_flags [n_plies] (PASS and FULL; BAD is found here); values [n_plies]; target_start
+ * [n_plies + 1] into target_index / target_weight.  A game has 1 .. 65535 plies; result 1 or 2, or 0 for a game cut at the ply
+ * limit and kept (AZH_FLAG_KEEP_UNFINISHED), which is nobody's win: z = -1 for both sides, as the host pipeline has it.  -6 when a capacity would be exceeded,
+ * -2 when the arrays contradict each other: either way the store is exactly what it was. */
+int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies, const uint64_t *boards,
+                          const uint8_t *ply_flags, const double *values, const int32_t *target_start,
+                          const uint16_t *target_index, const float *target_weight);
+/* Ring records, one after the other as azh_engine_staged_records returns them, -> the arrays azh_samples_add_games takes,
+ * holding what parsing each game's own line would give: the targets in the order of the line's sorted keys, weight
+ * (float)((double)count / (double)total) over the written counts (0 when total is 0; the same rule for the Gumbel search's
+ * 65535-unit counts), value isfinite(q) ? 2.0 * (double)q - 1.0 : 0.0 under kind & 16, FULL from word 5 (its sign bit under
+ * kind & 16) under kind & 4, random_ply + 1 from header word 6, indices by the engine's own move -> policy index map.  Each
+ * record must pass the walk azh_format_record_json makes; the markers of dropped games (kind & 1) and games begun at a loaded
+ * position (kind & 3 == 2) have no line and are skipped; anything else — a record cut short, a word count that does not
+ * match, a target that is no clone and no jump — returns -2 with nothing written.  counts [3]: on entry the room of the
+ * arrays in games, plies, targets; on return what the records hold.  With games == NULL only the counts are returned.
+ * -6 when an array is too small.  Host code only, usable without a device. */
+int azh_samples_pack_records(const uint32_t *rec, int64_t words, int64_t *counts, uint32_t *games, uint64_t *boards,
+                             uint8_t *ply_flags, double *values, int32_t *target_start, uint16_t *target_index,
+                             float *target_weight);
+/* azh_samples_pack_records followed by azh_samples_add_games: -2 and -6 add nothing. */
+int azh_samples_add_records(azh_samples *s, const uint32_t *rec, int64_t words);
+/* out [4]: games, plies, targets, bad plies that are no passes. */
+int azh_samples_counts(const azh_samples *s, int64_t *out);
+/* The host mirror: games [games][4] (first ply counted from the store's first), ply_flags [plies]. */
+int azh_samples_mirror(const azh_samples *s, uint32_t *games, uint8_t *ply_flags);
+/* A minibatch for host draws [n][3] of (game, ply, symmetry) into three DEVICE arrays.  Every draw is checked first: out of
+ * range or a pass -> -1, a bad ply -> -2 ("policy target does not sum to one"), nothing launched.  `stream` is a
+ * hipStream_t as a pointer-sized integer: the call enqueues on it and returns; the draws travel through pinned staging the
+ * store owns, two buffers taken in turn, so the next call does not wait for this one.  stream = 0: the store's own stream,
+ * and the call returns after completion — that stream is not ordered against any other, the null stream included: a caller
+ * whose work runs on the null stream passes hipStreamLegacy (1), as link.SampleStore does for torch's default stream. */
+int azh_samples_gather(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features, float *policy,
+                       float *value, uintptr_t stream);
+/* The same with the draws made on the device.  Sample i makes at most 64 attempts; attempt a takes one Philox4x32-10 block
+ * v keyed by `seed` with counter (step, i, a, 8) — stream 8 is drawn from by nothing else:
+ *   game g = first_game + ((u64)v[0] * n_games >> 32);  c = the game's candidate plies: all of them, or the FULL ones of a
+ *   game that has "full"; c == 0 fails the attempt;  ply = random_ply + 1 if the game has one, else candidate
+ *   ((u64)v[1] * c >> 32);  a ply outside the game, a pass or a bad ply fails the attempt;  symmetry = v[2] >> 29.
+ * The first attempt that succeeds is the draw: the host pipeline's distribution — uniform game, uniform ply, everything
+ * redrawn on rejection.  (The multiply-shift picks each of r values with a probability within 2^-32 of 1 / r.)  A sample
+ * whose 64 attempts all fail is written as zeros and counted (azh_samples_status).  draws_out: NULL, or a DEVICE array
+ * [n][4] of (game, ply, symmetry, attempts used); (-1, -1, -1, 64) for a failed sample. */
+int azh_samples_draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game, int64_t n_games,
+                            double value_blend, float *features, float *policy, float *value, int32_t *draws_out,
+                            uintptr_t stream);
+/* One sample's draw restated from mirror arrays (games [total_games][4], ply_flags with BAD set where it applies) -> out [4]
+ * as a row of draws_out.  Host arithmetic only: no device, no store. */
+int azh_samples_draw(uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
+                     const uint32_t *games, int64_t total_games, const uint8_t *ply_flags, int32_t *out);
+/* Waits for the device and returns how many samples of azh_samples_draw_gather have failed since the store was created. */
+int azh_samples_status(azh_samples *s, int64_t *failed);
+
 /* ------------------------------------------------------------------ reference ABI
  * The four symbols link.py:6-32 binds (cpp/self_play_client.cpp:683-749), with
  * the worker threads replaced by GPU game slots: `thread_count` concurrent

@@ -1,0 +1,265 @@
+"""The device-resident sample store (azh_samples_*), the parts that need no device: ring records packed into the store's
+arrays against the parse of the same games' own lines, malformed records, entries converted for the store against
+training._entry_arrays, and the device's draw restated on the oracle's Philox."""
+import ctypes
+import json
+
+import numpy as np
+import pytest
+
+from ataxxzero_amd import link, training
+from oracle import oracle_lib as orc
+
+MAGIC = 0x415A4847
+STREAM_SAMPLE_DRAW = 8
+SEED = 0x1234567_89ABCDEF
+PASS, FULL, BAD = link.SAMPLES_PLY_PASS, link.SAMPLES_PLY_FULL, link.SAMPLES_PLY_BAD
+HAS_FULL, HAS_VALUES = link.SAMPLES_GAME_HAS_FULL, link.SAMPLES_GAME_HAS_VALUES
+
+# every move of the board as (from, to) squares, square = file + 7 * rank: 49 clones and the jumps over a distance of two
+MOVES = [(a, b) for a in range(49) for b in range(49)
+         if a == b or max(abs(a % 7 - b % 7), abs(a // 7 - b // 7)) == 2]
+
+
+def _bits(q):
+    return int(np.array([q], dtype=np.float32).view(np.uint32)[0])
+
+
+def random_record(rng, plies, counts_hi, kind=0, random_ply=None, result=1, zero_total_at=None, empty_at=None, uid=0):
+    """Record words as the device loop leaves them in its ring (the idea of tests/test_json_format.py::random_record, with
+    board moves only — a trainer must be able to read the line — and the kind bits 4, 16 and 32)."""
+    words = [MAGIC, 3, uid, plies, result, 0, 0 if random_ply is None else random_ply + 1, kind]
+    for p in range(plies):
+        cells = rng.integers(0, 3, size=49)
+        x = sum(1 << i for i in range(49) if cells[i] == 1)
+        o = sum(1 << i for i in range(49) if cells[i] == 2)
+        nd = 0 if empty_at == p else int(rng.integers(1, 40))
+        chosen = [MOVES[j] for j in rng.choice(len(MOVES), size=nd, replace=False)]
+        counts = [int(v) for v in rng.integers(0, counts_hi + 1, size=nd)]
+        if zero_total_at == p:
+            counts = [0] * nd
+        frm, to = chosen[0] if chosen else MOVES[int(rng.integers(len(MOVES)))]
+        word5 = int(rng.integers(0, 2)) if kind & 4 else 0
+        if kind & 16:
+            q = [np.nan, np.inf, -np.inf, 0.5, 1.0, 0.0, float(rng.random())][int(rng.integers(0, 7))]
+            word5 = (_bits(q) & 0x7FFFFFFF) | (word5 << 31)
+        words += [x & 0xFFFFFFFF, x >> 32, o & 0xFFFFFFFF, o >> 32, (frm | to << 8) | nd << 16, word5]
+        words += [(f | t << 8) | c << 16 for (f, t), c in zip(chosen, counts)]
+    words[5] = len(words)
+    return np.array(words, dtype=np.uint32)
+
+
+def marker(uid):
+    return np.array([MAGIC, 0, uid, 0, 0, 8, 0, 1], dtype=np.uint32)
+
+
+def record_cases():
+    rng = np.random.default_rng(2024)
+    recs = []
+    for case in range(48):
+        kind = [0, 4, 16, 4 | 16, 16 | 32, 4 | 8, 4 | 8 | 16 | 32, 8][case % 8]
+        plies = 1 if case == 5 else int(rng.integers(2, 30))
+        recs.append(random_record(
+            rng, plies, [1, 7, 400, 2000, 60000, 65535][case % 6], kind=kind,
+            random_ply=int(rng.integers(0, plies - 1)) if case % 4 == 3 and plies > 1 else None, result=1 + case % 2,
+            zero_total_at=0 if case % 10 == 9 else None, empty_at=plies - 1 if case % 7 == 6 else None, uid=case))
+        if case % 5 == 2:
+            recs.append(marker(1000 + case))         # a dropped game's marker in between
+    return recs
+
+
+def _arrays_equal(a, b):
+    for name in link.SampleArrays.__slots__:
+        x, y = getattr(a, name), getattr(b, name)
+        assert x.dtype == y.dtype and x.shape == y.shape, name
+        assert x.tobytes() == y.tobytes(), name      # bit for bit: f32 weights, f64 values
+
+
+def test_packed_records_equal_the_parse_of_their_own_lines():
+    recs = record_cases()
+    packed = link.pack_records(np.concatenate(recs))
+    games = [r for r in recs if r[7] != 1]
+    entries = [json.loads(link.format_record_json(r)) for r in games]
+    assert len(packed.games) == len(games) == 48
+    kinds = {int(r[7]) for r in games}
+    assert {0, 4, 16, 20, 48, 12, 60, 8} <= kinds
+    _arrays_equal(packed, link.entries_to_arrays(entries))
+    # and against training._entry_arrays and the lines themselves, array by array
+    ply = target = 0
+    for g, (rec, entry) in enumerate(zip(games, entries)):
+        cells, idx, wts, start = training._entry_arrays(entry)
+        n = len(entry["boards"])
+        first, plies, word, random_ply_1 = (int(v) for v in packed.games[g])
+        assert (first, plies, word & 0xFF) == (ply, n, entry["result"])
+        assert random_ply_1 == entry.get("random_ply", -1) + 1
+        assert bool(word & HAS_FULL) == ("full" in entry) == bool(rec[7] & 4)
+        assert bool(word & HAS_VALUES) == ("values" in entry) == bool(rec[7] & 16)
+        for p in range(n):
+            x, o = (int(v) for v in packed.boards[ply + p])
+            want = [1 if x >> (c % 7 + 7 * (6 - c // 7)) & 1 else 2 if o >> (c % 7 + 7 * (6 - c // 7)) & 1 else 0
+                    for c in range(49)]
+            assert want == entry["boards"][p] and not x & o
+            assert int(packed.ply_flags[ply + p]) == (FULL if entry.get("full", [0] * n)[p] else 0)
+            assert packed.values[ply + p].tobytes() == np.float64(entry.get("values", [0.0] * n)[p]).tobytes()
+            lo, hi = (int(v) for v in packed.target_start[ply + p:ply + p + 2])
+            assert (lo - target, hi - target) == (int(start[p]), int(start[p + 1]))
+            assert list(packed.target_index[lo:hi]) == list(idx[start[p]:start[p + 1]])
+            assert packed.target_weight[lo:hi].tobytes() == wts[start[p]:start[p + 1]].tobytes()
+        ply += n
+        target += int(start[-1])
+    assert (ply, target) == (len(packed.ply_flags), len(packed.target_index))
+    values = packed.values[packed.values != 0]
+    assert len(values) and np.isfinite(packed.values).all()       # q = nan / inf read 0
+    assert (packed.target_weight == 0).any()                      # the zero-total plies
+
+
+def test_malformed_records_are_refused_and_add_nothing():
+    rng = np.random.default_rng(7)
+    good = [random_record(rng, 6, 50, uid=u) for u in range(3)]
+    whole = np.concatenate(good)
+    n_games = len(link.pack_records(whole).games)
+    assert n_games == 3
+
+    def refused(words):
+        counts = np.array([99, 9999, 99999], dtype=np.int64)
+        before = counts.copy()
+        outs = [np.full(4096, 0xAB, dtype=np.uint8) for _ in range(7)]
+        rc = link.load().azh_samples_pack_records(words.ctypes.data, words.size, counts.ctypes.data,
+                                                  *[o.ctypes.data for o in outs])
+        assert rc == -2, rc
+        assert (counts == before).all() and all((o == 0xAB).all() for o in outs)      # nothing written
+        with pytest.raises(link.AzhError):
+            link.pack_records(words)
+
+    refused(np.ascontiguousarray(whole[:-1]))                     # the last record is cut short
+    wrong = whole.copy()
+    wrong[len(good[0]) + 5] += 1                                  # the second record's word count is off by one
+    refused(wrong)
+    long = whole.copy()
+    long[len(good[0]) + 8 + 4] += 200 << 16                       # nd of its first ply runs past its end
+    refused(long)
+    more = whole.copy()
+    more[3] += 1                                                  # one ply more than the words hold
+    refused(more)
+    no_move = whole.copy()
+    no_move[8 + 6] = (no_move[8 + 6] & 0xFFFF0000) | (0 | 1 << 8)  # a1 -> b1: neither a clone nor a jump
+    refused(no_move)
+    junk = np.concatenate([good[0], np.array([5], dtype=np.uint32), good[1]])
+    refused(junk)                                                 # a stray word between two records
+
+
+def test_entries_for_the_store_follow_entry_arrays():
+    """pass plies and "pass" keys, list-typed moves, an entry without dists, "full", "values", random_ply."""
+    board = [0] * 49
+    entries = [
+        {"boards": [board] * 3, "moves": ["a1", "pass", "a1c3"], "result": 2,
+         "dists": [{"a1": 0.25, "pass": 0.5, "b2": 0.25}, {}, {"a1c3": 1.0}], "full": [1, 0, 1], "values": [0.5, -1.0, 0.125]},
+        {"boards": [[1] * 49, [2] * 49], "moves": [["c", [3, 4]], [[0, 0], [2, 1]]], "result": 1, "random_ply": 0},
+    ]
+    a = link.entries_to_arrays(entries)
+    assert a.games.tolist() == [[0, 3, 2 | HAS_FULL | HAS_VALUES, 0], [3, 2, 1, 1]]
+    assert a.ply_flags.tolist() == [FULL, PASS, FULL, 0, 0]
+    assert a.values.tolist() == [0.5, -1.0, 0.125, 0.0, 0.0]
+    assert a.target_start.tolist() == [0, 2, 2, 3, 4, 5]
+    want = [training._flat_policy_index(m) for m in ("a1", "b2", "a1c3", ["c", [3, 4]], [[0, 0], [2, 1]])]
+    assert a.target_index.tolist() == want
+    assert a.target_weight.tolist() == [0.25, 0.25, 1.0, 1.0, 1.0]
+    assert a.boards.tolist() == [[0, 0]] * 3 + [[(1 << 49) - 1, 0], [0, (1 << 49) - 1]]
+
+
+# ---------------------------------------------------------------- the draw
+
+def philox(seed, c0, c1, c2, c3):
+    out = (ctypes.c_uint32 * 4)()
+    orc.lib().orc_probe_philox(seed, c0, c1, c2, c3, out)
+    return [int(v) for v in out]
+
+
+def restated_draw(seed, step, i, first_game, n_games, games, flags):
+    for a in range(64):
+        v = philox(seed, step, i, a, STREAM_SAMPLE_DRAW)
+        g = first_game + (v[0] * n_games >> 32)
+        first, plies, word, random_ply_1 = (int(w) for w in games[g])
+        candidates = [p for p in range(plies) if not word & HAS_FULL or flags[first + p] & FULL]
+        if not candidates:
+            continue
+        ply = random_ply_1 if random_ply_1 else candidates[v[1] * len(candidates) >> 32]
+        if ply >= plies or flags[first + ply] & (PASS | BAD):
+            continue
+        return g, ply, v[2] >> 29, a + 1
+    return -1, -1, -1, 64
+
+
+def draw_mirror():
+    """40 games, exactly half of which can never give a sample."""
+    rng = np.random.default_rng(40)
+    games, flags = [], []
+
+    def add(ply_flags, word=1, random_ply_1=0):
+        games.append((len(flags), len(ply_flags), word, random_ply_1))
+        flags.extend(ply_flags)
+
+    undrawable = [
+        lambda: add([0, 0, 0, 0], 1 | HAS_FULL),                            # "full" without one full ply
+        lambda: add([0, 0, PASS, 0, 0], 2, 2),                              # the ply after the random move is a pass
+        lambda: add([BAD] * 6),                                             # every ply bad
+        lambda: add([PASS]),                                                # one ply, a pass
+        lambda: add([FULL | BAD, 0, FULL | PASS, 0], 2 | HAS_FULL | HAS_VALUES),   # its full plies are bad or passes
+        lambda: add([0, 0, 0], 1, 3),                                       # the random move was the last one
+        lambda: add([0, 0, FULL], 1 | HAS_FULL, 1),                         # full plies, but random_ply + 1 is bad below
+    ]
+    drawable = [
+        lambda: add([0] * int(rng.integers(2, 60)), 1 + int(rng.integers(2))),
+        lambda: add([0]),                                                   # a one-ply game
+        lambda: add([0, FULL, 0, FULL | BAD, FULL | PASS, FULL, 0], 1 | HAS_FULL),
+        lambda: add([0, 0, 0, PASS, BAD], 2 | HAS_VALUES, 2),
+        lambda: add([BAD, PASS, 0, BAD, PASS, BAD]),                        # one good ply among six
+    ]
+    order = [0] * 20 + [1] * 20
+    rng.shuffle(order)
+    for k, kind in enumerate(order):
+        (drawable if kind else undrawable)[k % (5 if kind else 7)]()
+        if not kind and k % 7 == 6:
+            flags[games[-1][0] + 1] |= BAD
+    games = np.array(games, dtype=np.uint32)
+    flags = np.array(flags, dtype=np.uint8)
+    can = []
+    for first, plies, word, r1 in games.tolist():
+        cand = [p for p in range(plies) if not word & HAS_FULL or flags[first + p] & FULL]
+        plys = ([r1] if r1 else cand) if cand else []
+        can.append(any(p < plies and not flags[first + p] & (PASS | BAD) for p in plys))
+    assert sum(can) == 20 and len(can) == 40
+    return games, flags, can
+
+
+def test_draw_equals_the_restatement_on_the_oracles_philox():
+    games, flags, can = draw_mirror()
+    most = 0
+    seen = set()
+    for step in range(3):
+        for i in range(257):
+            got = link.samples_draw(SEED, step, i, 0, 40, games, flags)
+            assert got == restated_draw(SEED, step, i, 0, 40, games, flags), (step, i)
+            g, ply, sym, attempts = got
+            assert 1 <= attempts <= 64 and g >= 0                  # half the games undrawable: 64 misses have chance 2^-64
+            assert can[g] and 0 <= sym < 8 and ply < games[g][1]
+            assert not flags[games[g][0] + ply] & (PASS | BAD)
+            if games[g][3]:
+                assert ply == games[g][3]
+            elif games[g][2] & HAS_FULL:
+                assert flags[games[g][0] + ply] & FULL
+            most = max(most, attempts)
+            seen.add(g)
+    assert most > 3 and seen == {g for g in range(40) if can[g]}
+    # a sub-range, and another key
+    for i in range(64):
+        got = link.samples_draw(SEED ^ 1 << 40, 7, i, 10, 30, games, flags)
+        assert got == restated_draw(SEED ^ 1 << 40, 7, i, 10, 30, games, flags) and 10 <= got[0] < 40
+
+
+def test_a_range_of_undrawable_games_exhausts_the_attempts():
+    games, flags, can = draw_mirror()
+    g = can.index(False)
+    assert link.samples_draw(SEED, 0, 0, g, 1, games, flags) == (-1, -1, -1, 64)
+    with pytest.raises(link.AzhError):
+        link.samples_draw(SEED, 0, 0, 30, 11, games, flags)       # past the last game
