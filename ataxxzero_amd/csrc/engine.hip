@@ -1346,13 +1346,32 @@ using namespace azh;
 std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_ids);  // json.cpp
 bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plies, const char **why);
 
+// The leaf buffers of EngineParams as one value.  The engine keeps two sets, its own G-slot one and the G K-slot one of the
+// leaf-parallel search, and P points at one of them.
+struct LeafBuffers {
+    ulonglong2 *leaf_board = nullptr;
+    int *need_eval = nullptr, *leaf_list = nullptr, mask_words = 0;
+    u32 *need_mask = nullptr;
+    float *logits = nullptr, *values = nullptr;
+    void read(const EngineParams &P)
+    {
+        leaf_board = P.leaf_board; need_eval = P.need_eval; leaf_list = P.leaf_list;
+        need_mask = P.need_mask; mask_words = P.mask_words; logits = P.logits; values = P.values;
+    }
+    void write(EngineParams &P) const
+    {
+        P.leaf_board = leaf_board; P.need_eval = need_eval; P.leaf_list = leaf_list;
+        P.need_mask = need_mask; P.mask_words = mask_words; P.logits = logits; P.values = values;
+    }
+};
+
 struct azh_engine {
     azh_config cfg;
     EngineParams P;
     hipStream_t stream = nullptr;
     std::vector<void *> allocs;
-    float *d_feat = nullptr;
-    float *d_sym_logits = nullptr, *d_sym_values = nullptr;  // AZH_FLAG_SYMMETRY_AVG scratch
+    float *d_feat = nullptr;       // azh_engine_leaf_features: [G] rows, allocated by the first call
+    float *d_sym_logits = nullptr, *d_sym_values = nullptr;  // AZH_FLAG_SYMMETRY_AVG scratch, allocated by the first evaluation
     u16 *d_play_moves = nullptr;   // azh_engine_play_moves: moves [G] and status [G], allocated by the first call
     int *d_play_status = nullptr;
     u32 *d_report = nullptr;       // azh_engine_root_report: [G][AZH_ROOT_REPORT_WORDS], allocated by the first call
@@ -1406,16 +1425,8 @@ struct azh_engine {
     // engine's own G-slot ones, and every launch is the one-leaf search's.
     VlParams V{};
     int vl_slots_cap = 0;  // slots the G K buffers were allocated for
-    ulonglong2 *g_leaf_board = nullptr;
-    int *g_need_eval = nullptr, *g_leaf_list = nullptr;
-    u32 *g_need_mask = nullptr;
-    int g_mask_words = 0;
-    float *g_logits = nullptr, *g_values = nullptr;
-    ulonglong2 *vl_leaf_board = nullptr;  // the G K-slot buffers while K = 1 is in force
-    int *vl_need_eval = nullptr, *vl_leaf_list = nullptr;
-    u32 *vl_need_mask = nullptr;
-    int vl_mask_words = 0;
-    float *vl_logits = nullptr, *vl_values = nullptr;
+    LeafBuffers g_leaves;   // the engine's own G-slot buffers
+    LeafBuffers vl_leaves;  // the G K-slot buffers (kept while K = 1 is in force)
     // proven wins and losses (azh_engine_set_solver): while it is on, every K — 1 included — runs through k_vl_tree and the
     // G K-slot buffers (vl_active: P's leaf buffers point at them), and its backup is followed by the proof pass
     bool vl_active = false;   // (the solver's own switch is V.solver)
@@ -1439,6 +1450,108 @@ template <typename T> static int dev_alloc(azh_engine *e, T **p, size_t count)
     AZH_HIP(hipMemset(q, 0, count * sizeof(T)));
     e->allocs.push_back(q);
     *p = (T *)q;
+    return 0;
+}
+
+#define AZH_TRY(call) do { if (int _rc = (call)) return _rc; } while (0)  // (as AZH_HIP: the failure is the caller's result)
+
+// allocate on first use: zeroed and owned by e->allocs like every other device buffer
+template <typename T> static int dev_alloc_once(azh_engine *e, T **p, size_t count) { return *p ? 0 : dev_alloc(e, p, count); }
+
+// ------------------------------------------------------------------ the search modes: who refuses whom
+//
+// Eight modes are switched between iterations, by a setter each.  What a mode cannot run beside (create-time flags and settings,
+// other modes) is stated here once, and mode_refusal answers for every setter.  In words: the table "Search modes: who refuses
+// whom" of include/ataxxzero_hip.h and of DESIGN.md.
+
+enum { MODE_NONE = -1, MODE_CAP, MODE_FORCED, MODE_GUMBEL, MODE_TEMPERATURE, MODE_RESIGN, MODE_SYMMETRY, MODE_LEAF_BATCH, MODE_SOLVER };
+
+// Is `bb` its own image under all 8 symmetries?  (the two mirrors and the transposition generate them)
+static bool symmetry_invariant(u64 bb)
+{
+    return symmetry_board(1, bb) == bb && symmetry_board(2, bb) == bb && symmetry_board(4, bb) == bb;
+}
+
+struct ModeInfo {
+    const char *setter, *phrase;  // a refusal calls the mode by its phrase: another setter's (with "(<setter>)" behind it if
+    bool cited, subject;          // `cited`), and its own if `subject`: "<phrase> is not supported with", not "not supported with"
+    bool own_advance;             // while it is on, the device loop plays the queued moves in a launch of their own (RunLoop::own)
+    bool (*on)(const azh_engine *);
+    u32 refused_flags;  // (the create-time requirements that are no flags: mode_refusal)
+};
+
+constexpr u32 ROOT_FLAGS = AZH_FLAG_TWO_NETS | AZH_FLAG_ONE_RANDOM_MOVE, LEAF_FLAGS = AZH_FLAG_TWO_NETS | AZH_FLAG_EVAL_CACHE | AZH_FLAG_SYMMETRY_AVG;
+#define ON(expr) [](const azh_engine *e) -> bool { return expr; }
+static const ModeInfo MODES[] = {  // (in the order of the MODE_ constants)
+    {"azh_engine_set_playout_cap", "the playout cap", true, false, false, ON(e->P.fast_visits != 0), ROOT_FLAGS},
+    {"azh_engine_set_forced_playouts", "forced playouts", true, false, true, ON(e->P.forced_k != 0.0f), ROOT_FLAGS},
+    {"azh_engine_set_gumbel", "the Gumbel root search", true, false, true, ON(e->P.gumbel_m != 0),
+     ROOT_FLAGS | AZH_FLAG_SAMPLE_POW5 | AZH_FLAG_EVAL_CACHE},
+    // (a move temperature needs the launch of its own, a root-policy table does not: RunLoop::begin asks for the former itself)
+    {"azh_engine_set_temperature", "a temperature table", true, false, false, ON(e->P.move_temperature || e->P.root_policy_temperature),
+     ROOT_FLAGS | AZH_FLAG_SAMPLE_POW5 | AZH_FLAG_PY_POSTERIOR},
+    {"azh_engine_set_resign", "recorded values and resignation", true, false, true, ON(e->P.resign_plies != 0u), ROOT_FLAGS},
+    {"azh_engine_set_random_symmetry", "the random symmetry", true, false, true, ON(e->P.random_symmetry != 0u),
+     AZH_FLAG_TWO_NETS | AZH_FLAG_SYMMETRY_AVG},
+    {"azh_engine_set_leaf_batch", "more than one leaf per game", true, true, false, ON(e->V.K > 1), LEAF_FLAGS},
+    {"azh_engine_set_solver", "the solver", false, true, false, ON(e->V.solver != 0), LEAF_FLAGS},
+};
+#undef ON
+
+// The pairs of modes that do not run beside each other, each once: whichever of the two asks second is refused.  (With several
+// modes on, a refusal names the first pair listed here.)
+static const int EXCLUDED[][2] = {
+    {MODE_GUMBEL, MODE_CAP},    {MODE_GUMBEL, MODE_FORCED},     {MODE_GUMBEL, MODE_TEMPERATURE}, {MODE_GUMBEL, MODE_LEAF_BATCH},
+    {MODE_GUMBEL, MODE_SOLVER}, {MODE_FORCED, MODE_LEAF_BATCH}, {MODE_FORCED, MODE_SOLVER},
+};
+
+// The create-time flags a mode can be refused with; of several set at once a refusal names the first one listed here.
+#define NAMED(flag) {flag, #flag}
+static const struct { u32 bit; const char *name; } FLAG_NAMES[] = {
+    NAMED(AZH_FLAG_TWO_NETS),     NAMED(AZH_FLAG_ONE_RANDOM_MOVE), NAMED(AZH_FLAG_SAMPLE_POW5),
+    NAMED(AZH_FLAG_PY_POSTERIOR), NAMED(AZH_FLAG_EVAL_CACHE),      NAMED(AZH_FLAG_SYMMETRY_AVG),
+};
+#undef NAMED
+
+// May `mode` come on in this engine now?  Empty: yes; else why not, as the refusal reads after "<setter>: ".  The flags are looked
+// at first, then what else a mode requires of the engine's configuration, then the modes that are on.
+static std::string mode_refusal(const azh_engine *e, int mode)
+{
+    const ModeInfo &m = MODES[mode];
+    const std::string head = m.subject ? std::string(m.phrase) + " is not supported with " : "not supported with ";
+    for (const auto &f : FLAG_NAMES)
+        if (e->P.flags & m.refused_flags & f.bit)
+            return head + f.name;
+    char mask[32];
+    snprintf(mask, sizeof(mask), "0x%llx", (unsigned long long)e->P.blockers);
+    if ((mode == MODE_LEAF_BATCH || mode == MODE_SOLVER) && e->P.select_budget > 0)
+        return head + "select_budget > 0";
+    if (mode == MODE_GUMBEL && (!(e->P.flags & AZH_FLAG_NO_REUSE) || e->P.noise_w != 0.0f))
+        return "the engine must have been created with AZH_FLAG_NO_REUSE and dirichlet_weight 0 (the schedule assumes a fresh "
+               "root, and its noise is the Gumbel)";
+    if (mode == MODE_SYMMETRY && !symmetry_invariant(e->P.blockers & BOARD_MASK))
+        return head + "a blockers mask (" + mask + ") that is not its own image under all 8 symmetries (the tower takes one "
+                      "blocker plane per launch)";
+    for (const auto &pair : EXCLUDED) {
+        const int other = pair[0] == mode ? pair[1] : pair[1] == mode ? pair[0] : MODE_NONE;
+        if (other != MODE_NONE && MODES[other].on(e))
+            return head + MODES[other].phrase + (MODES[other].cited ? std::string(" (") + MODES[other].setter + ")" : "");
+    }
+    return "";
+}
+
+// What every mode setter does between the checks of its own arguments (-1, -2) and its first change: -3 while a selected batch
+// awaits its backup, -4 where `mode` may not come on (MODE_NONE: the call switches something off, which is no request), then the
+// stream is drained.  Every check comes before the first change, so a refused call leaves the engine as it was.  `who`: the
+// calling entry point, for its errors.
+static int mode_request(azh_engine *e, const char *who, int mode)
+{
+    if (e->selected)
+        return azh_fail(-3, "%s: a selected batch awaits its backup", who);
+    const std::string why = mode != MODE_NONE ? mode_refusal(e, mode) : "";
+    if (!why.empty())
+        return azh_fail(-4, "%s: %s", who, why.c_str());
+    AZH_HIP(hipStreamSynchronize(e->stream));
     return 0;
 }
 
@@ -1531,13 +1644,7 @@ extern "C" int azh_engine_create(const azh_config *cfg, azh_engine **out)
     e->V.K = 1;
     e->V.vl = 1;
     e->V.path_cap = P.path_cap;
-    e->g_leaf_board = P.leaf_board;
-    e->g_need_eval = P.need_eval;
-    e->g_leaf_list = P.leaf_list;
-    e->g_need_mask = P.need_mask;
-    e->g_mask_words = P.mask_words;
-    e->g_logits = P.logits;
-    e->g_values = P.values;
+    e->g_leaves.read(P);
     hipLaunchKernelGGL(k_init, dim3(P.G), dim3(WAVE), 0, e->stream, P);
     if (hipStreamSynchronize(e->stream) != hipSuccess) {
         azh_engine_destroy(e);
@@ -1557,12 +1664,6 @@ extern "C" void azh_engine_destroy(azh_engine *e)
         (void)hipEventDestroy(ev);
     for (void *p : e->allocs)
         (void)hipFree(p);
-    if (e->d_feat)
-        (void)hipFree(e->d_feat);
-    if (e->d_sym_logits)
-        (void)hipFree(e->d_sym_logits);
-    if (e->d_sym_values)
-        (void)hipFree(e->d_sym_values);
     if (e->h_count)
         (void)hipHostFree(e->h_count);
     if (e->h_head)
@@ -1661,8 +1762,7 @@ extern "C" int azh_engine_leaf_features(azh_engine *e, float *out, int32_t *game
     AZH_HIP(hipMemcpy(&n, e->P.leaf_count, 4, hipMemcpyDeviceToHost));
     if (n <= 0)
         return 0;
-    if (!e->d_feat)
-        AZH_HIP(hipMalloc((void **)&e->d_feat, (size_t)e->P.G * AZH_FEATURE_SIZE * 4));
+    AZH_TRY(dev_alloc_once(e, &e->d_feat, (size_t)e->P.G * AZH_FEATURE_SIZE));
     hipLaunchKernelGGL(k_features, dim3((n * 49 + 255) / 256), dim3(256), 0, e->stream,
                        (const ulonglong2 *)e->P.leaf_board, (const int *)e->P.leaf_list, n, e->P.blockers, e->d_feat);
     AZH_HIP(hipGetLastError());
@@ -1679,10 +1779,8 @@ static int launch_eval(azh_engine *e, azh_net *net, int dtype, const int *list, 
     if (!(e->P.flags & AZH_FLAG_SYMMETRY_AVG))
         return azh_net_launch(net, dtype, (const unsigned long long *)e->P.leaf_board, list, count, e->P.G * leaf_k(e),
                               e->P.blockers, e->P.logits, e->P.values, e->stream, nullptr, thin_batches(e), hook);
-    if (!e->d_sym_logits) {
-        AZH_HIP(hipMalloc((void **)&e->d_sym_logits, (size_t)e->P.G * 8 * AZH_POLICY_SIZE * 4));
-        AZH_HIP(hipMalloc((void **)&e->d_sym_values, (size_t)e->P.G * 8 * 4));
-    }
+    AZH_TRY(dev_alloc_once(e, &e->d_sym_logits, (size_t)e->P.G * 8 * AZH_POLICY_SIZE));
+    AZH_TRY(dev_alloc_once(e, &e->d_sym_values, (size_t)e->P.G * 8));
     return azh_net_launch_sym(net, dtype, (const unsigned long long *)e->P.leaf_board, list, count, e->P.G,
                               e->P.blockers, e->d_sym_logits, e->d_sym_values, e->P.logits, e->P.values, e->stream,
                               e->thin_mode >= 0 ? e->thin_mode : (e->P.G * 8 <= AZH_THIN_MAX_GAMES ? 1 : 0),  // (8 virtual boards per leaf)
@@ -1739,10 +1837,9 @@ struct RunLoop {
     azh_net *net_a, *net_b;
     int dtype, iterations;
     bool pair = false;
-    bool own = false;  // forced playouts, random symmetry, recorded values and resignation, a move temperature, Gumbel: the queued moves in a
-                       // k_advance_list launch of their own, on the engine's stream, in front of the tower (the tower kernels'
-                       // advance_game records no pruned counts, writes no key word and knows no ply value and no temperature:
-                       // engine_device.h)
+    bool own = false;  // a mode with own_advance (MODES) or a move temperature: the queued moves in a k_advance_list launch of
+                       // their own, on the engine's stream, in front of the tower (the tower kernels' advance_game records no
+                       // pruned counts, writes no key word and knows no ply value and no temperature: engine_device.h)
     AdvanceHook hook;
 
     int begin()
@@ -1751,8 +1848,9 @@ struct RunLoop {
         const char *pair_s = getenv("AZH_ARENA_PAIR");  // (read per call: a test switches it inside one process)
         const bool pair_env = !(pair_s && atoi(pair_s) == 0);
         pair = pair_env && two_lists(e) && !(e->P.flags & AZH_FLAG_SYMMETRY_AVG);
-        own = e->P.forced_k != 0.0f || e->P.random_symmetry != 0u || e->P.resign_plies != 0u || e->P.move_temperature != nullptr ||
-              e->P.gumbel_m != 0;
+        own = e->P.move_temperature != nullptr;
+        for (const ModeInfo &m : MODES)
+            own = own || (m.own_advance && m.on(e));
         hook.workers = e->adv_workers;
         hook.at_head = 1;   // (decided per launch by the tower's launch functions: in front only where workgroups queue for slots)
         hook.P = e->P;
@@ -1878,12 +1976,7 @@ extern "C" int azh_engine_tree_stamps(azh_engine *e, azh_net *net, int dtype, ui
     if (e->vl_active)
         return azh_fail(-2, "azh_engine_tree_stamps: not available with %d leaves per game%s", leaf_k(e),
                         e->V.solver ? " and the solver" : "");
-    if (!e->P.stamps) {
-        void *q = nullptr;
-        AZH_HIP(hipMalloc(&q, (size_t)e->P.G * TREE_STAMPS * 8));
-        e->allocs.push_back(q);
-        e->P.stamps = (u64 *)q;
-    }
+    AZH_TRY(dev_alloc_once(e, &e->P.stamps, (size_t)e->P.G * TREE_STAMPS));
     AZH_HIP(hipMemsetAsync(e->P.stamps, 0, (size_t)e->P.G * TREE_STAMPS * 8, e->stream));
     e->stamp_next = true;
     const int rc = run_loop(e, net, nullptr, dtype, 2);
@@ -1900,68 +1993,39 @@ extern "C" int azh_engine_tree_stamps(azh_engine *e, azh_net *net, int dtype, ui
 // on; K = 1 without the solver is the one-leaf search and its kernels.  `who`: the calling entry point, for its errors.
 static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, bool solver, const char *who)
 {
-    if (e->selected)
-        return azh_fail(-3, "%s: a selected batch awaits its backup", who);
     const bool want = leaves_per_game > 1 || solver;
-    if (want) {
-        const uint32_t bad = e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_EVAL_CACHE | AZH_FLAG_SYMMETRY_AVG);
-        if (bad || e->P.select_budget > 0)
-            return azh_fail(-4, "%s: %s is not supported with %s", who,
-                            leaves_per_game > 1 ? "more than one leaf per game" : "the solver",
-                            e->P.select_budget > 0 ? "select_budget > 0"
-                            : (bad & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS"
-                            : (bad & AZH_FLAG_EVAL_CACHE) ? "AZH_FLAG_EVAL_CACHE" : "AZH_FLAG_SYMMETRY_AVG");
-        if (e->P.gumbel_m != 0)  // (nor a Gumbel root level)
-            return azh_fail(-4, "%s: %s is not supported with the Gumbel root search (azh_engine_set_gumbel)", who,
-                            leaves_per_game > 1 ? "more than one leaf per game" : "the solver");
-        if (e->P.forced_k != 0.0f)  // (the K-leaf kernel has no forced-playout level)
-            return azh_fail(-4, "%s: %s is not supported with forced playouts (azh_engine_set_forced_playouts)", who,
-                            leaves_per_game > 1 ? "more than one leaf per game" : "the solver");
-    }
-    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_TRY(mode_request(e, who, leaves_per_game > 1 ? MODE_LEAF_BATCH : solver ? MODE_SOLVER : MODE_NONE));
     EngineParams &P = e->P;
-    const size_t G = (size_t)P.G, K = (size_t)leaves_per_game;
-    if (want && !e->vl_active && e->vl_slots_cap > 0) {
-        // back to K-slot buffers allocated by an earlier call
-        P.leaf_board = e->vl_leaf_board; P.need_eval = e->vl_need_eval; P.leaf_list = e->vl_leaf_list;
-        P.need_mask = e->vl_need_mask; P.mask_words = e->vl_mask_words; P.logits = e->vl_logits; P.values = e->vl_values;
-    }
-    if (want && (int)(G * K) > e->vl_slots_cap) {
+    const size_t n = (size_t)P.G * (size_t)leaves_per_game;
+    if (want && (int)n > e->vl_slots_cap) {
         // slot buffers for G K leaves (kept for the engine's life; a larger K later allocates again)
-        const size_t n = G * K;
-        const int mw = (int)((n + 31) / 32);
+        LeafBuffers b;
+        b.mask_words = (int)((n + 31) / 32);
         int rc = 0;
         rc |= dev_alloc(e, &e->V.kind, n);
         rc |= dev_alloc(e, &e->V.leaf_edge, n);
         rc |= dev_alloc(e, &e->V.leaf_node, n);
         rc |= dev_alloc(e, &e->V.path_len, n);
         rc |= dev_alloc(e, &e->V.path, n * (size_t)P.path_cap);
-        rc |= dev_alloc(e, &P.leaf_board, n);
-        rc |= dev_alloc(e, &P.need_eval, n);
-        rc |= dev_alloc(e, &P.leaf_list, n);
-        rc |= dev_alloc(e, &P.need_mask, 2 * (size_t)mw);
-        rc |= dev_alloc(e, &P.logits, n * AZH_POLICY_SIZE);
-        rc |= dev_alloc(e, &P.values, n);
-        P.mask_words = mw;
+        rc |= dev_alloc(e, &b.leaf_board, n);
+        rc |= dev_alloc(e, &b.need_eval, n);
+        rc |= dev_alloc(e, &b.leaf_list, n);
+        rc |= dev_alloc(e, &b.need_mask, 2 * (size_t)b.mask_words);
+        rc |= dev_alloc(e, &b.logits, n * AZH_POLICY_SIZE);
+        rc |= dev_alloc(e, &b.values, n);
         if (rc) {
-            P.leaf_board = e->g_leaf_board; P.need_eval = e->g_need_eval; P.leaf_list = e->g_leaf_list;
-            P.need_mask = e->g_need_mask; P.mask_words = e->g_mask_words; P.logits = e->g_logits; P.values = e->g_values;
+            e->g_leaves.write(P);
             e->V.K = 1;
             e->V.solver = 0;
             e->vl_active = false;
             e->vl_slots_cap = 0;
             return rc;
         }
+        e->vl_leaves = b;
         e->vl_slots_cap = (int)n;
     }
-    if (want) {
-        e->vl_leaf_board = P.leaf_board; e->vl_need_eval = P.need_eval; e->vl_leaf_list = P.leaf_list;
-        e->vl_need_mask = P.need_mask; e->vl_mask_words = P.mask_words; e->vl_logits = P.logits; e->vl_values = P.values;
-    } else {
-        P.leaf_board = e->g_leaf_board; P.need_eval = e->g_need_eval; P.leaf_list = e->g_leaf_list;
-        P.need_mask = e->g_need_mask; P.mask_words = e->g_mask_words; P.logits = e->g_logits; P.values = e->g_values;
-    }
-    e->V.K = (int)K;
+    (want ? e->vl_leaves : e->g_leaves).write(P);
+    e->V.K = leaves_per_game;
     e->V.vl = virtual_loss;
     e->V.solver = solver ? 1 : 0;
     e->vl_active = want;
@@ -2088,20 +2152,13 @@ extern "C" int azh_engine_set_playout_cap(azh_engine *e, int fast_visits, int fu
     if (fast_visits < 0 || fast_visits > e->P.visits || full_per_65536 < 0 || full_per_65536 > 65536)
         return azh_fail(-2, "azh_engine_set_playout_cap: need 0 <= fast_visits <= visits (%d) and 0 <= full_per_65536 <= 65536",
                         e->P.visits);
-    if (e->selected)
-        return azh_fail(-3, "azh_engine_set_playout_cap: a selected batch awaits its backup");
-    if (fast_visits != 0 && (e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_ONE_RANDOM_MOVE)))
-        return azh_fail(-4, "azh_engine_set_playout_cap: not supported with %s",
-                        (e->P.flags & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS" : "AZH_FLAG_ONE_RANDOM_MOVE");
-    if (fast_visits != 0 && e->P.gumbel_m != 0)
-        return azh_fail(-4, "azh_engine_set_playout_cap: not supported with the Gumbel root search (azh_engine_set_gumbel)");
-    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_TRY(mode_request(e, "azh_engine_set_playout_cap", fast_visits != 0 ? MODE_CAP : MODE_NONE));
     if (fast_visits == 0) {
         e->P.fast_visits = 0;
         e->P.full_per_65536 = 0;
         return 0;
     }
-    if (!e->P.ply_kind && dev_alloc(e, &e->P.ply_kind, (size_t)e->P.G))
+    if (dev_alloc_once(e, &e->P.ply_kind, (size_t)e->P.G))
         return -1;
     e->P.fast_visits = fast_visits;
     e->P.full_per_65536 = (u32)full_per_65536;
@@ -2125,17 +2182,7 @@ extern "C" int azh_engine_set_forced_playouts(azh_engine *e, float k)
         return azh_fail(-1, "azh_engine_set_forced_playouts: null engine");
     if (!(k >= 0.0f) || k > 3.0e38f)
         return azh_fail(-2, "azh_engine_set_forced_playouts: need a finite k >= 0 (0: off)");
-    if (e->selected)
-        return azh_fail(-3, "azh_engine_set_forced_playouts: a selected batch awaits its backup");
-    if (k != 0.0f && (e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_ONE_RANDOM_MOVE)))
-        return azh_fail(-4, "azh_engine_set_forced_playouts: not supported with %s",
-                        (e->P.flags & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS" : "AZH_FLAG_ONE_RANDOM_MOVE");
-    if (k != 0.0f && e->vl_active)
-        return azh_fail(-4, "azh_engine_set_forced_playouts: not supported with %s",
-                        leaf_k(e) > 1 ? "more than one leaf per game (azh_engine_set_leaf_batch)" : "the solver");
-    if (k != 0.0f && e->P.gumbel_m != 0)
-        return azh_fail(-4, "azh_engine_set_forced_playouts: not supported with the Gumbel root search (azh_engine_set_gumbel)");
-    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_TRY(mode_request(e, "azh_engine_set_forced_playouts", k != 0.0f ? MODE_FORCED : MODE_NONE));
     e->P.forced_k = k;
     return 0;
 }
@@ -2153,7 +2200,7 @@ extern "C" int azh_forced_prune(const float *prior, const float *W, const uint32
 }
 
 // Gumbel root search with sequential halving (Danihelka et al., ICLR 2022).  Definition: the header and DESIGN.md.  Between
-// iterations only.  Every check comes before the first change, so a refused call leaves the engine as it was.
+// iterations only.
 extern "C" int azh_engine_set_gumbel(azh_engine *e, int m, float c_visit, float c_scale)
 {
     if (!e)
@@ -2165,28 +2212,7 @@ extern "C" int azh_engine_set_gumbel(azh_engine *e, int m, float c_visit, float 
     if ((long long)m * e->P.visits > GUMBEL_MAX_TABLE)
         return azh_fail(-2, "azh_engine_set_gumbel: m * visits = %lld may not exceed %d", (long long)m * e->P.visits,
                         GUMBEL_MAX_TABLE);
-    if (e->selected)
-        return azh_fail(-3, "azh_engine_set_gumbel: a selected batch awaits its backup");
-    if (m != 0) {
-        const u32 bad = e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_ONE_RANDOM_MOVE | AZH_FLAG_SAMPLE_POW5 | AZH_FLAG_EVAL_CACHE);
-        if (bad)
-            return azh_fail(-4, "azh_engine_set_gumbel: not supported with %s",
-                            (bad & AZH_FLAG_TWO_NETS)          ? "AZH_FLAG_TWO_NETS"
-                            : (bad & AZH_FLAG_ONE_RANDOM_MOVE) ? "AZH_FLAG_ONE_RANDOM_MOVE"
-                            : (bad & AZH_FLAG_SAMPLE_POW5)     ? "AZH_FLAG_SAMPLE_POW5"
-                                                               : "AZH_FLAG_EVAL_CACHE");
-        if (!(e->P.flags & AZH_FLAG_NO_REUSE) || e->P.noise_w != 0.0f)
-            return azh_fail(-4, "azh_engine_set_gumbel: the engine must have been created with AZH_FLAG_NO_REUSE and "
-                                "dirichlet_weight 0 (the schedule assumes a fresh root, and its noise is the Gumbel)");
-        const char *mode = e->P.fast_visits != 0 ? "the playout cap (azh_engine_set_playout_cap)"
-                           : e->P.forced_k != 0.0f ? "forced playouts (azh_engine_set_forced_playouts)"
-                           : (e->P.move_temperature || e->P.root_policy_temperature) ? "a temperature table (azh_engine_set_temperature)"
-                           : e->vl_active ? (leaf_k(e) > 1 ? "more than one leaf per game (azh_engine_set_leaf_batch)" : "the solver")
-                                          : nullptr;
-        if (mode)
-            return azh_fail(-4, "azh_engine_set_gumbel: not supported with %s", mode);
-    }
-    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_TRY(mode_request(e, "azh_engine_set_gumbel", m != 0 ? MODE_GUMBEL : MODE_NONE));
     if (m == 0) {
         e->P.gumbel_m = 0;
         e->P.gumbel_c_visit = 0.0f;
@@ -2194,9 +2220,7 @@ extern "C" int azh_engine_set_gumbel(azh_engine *e, int m, float c_visit, float 
         return 0;
     }
     const size_t G = (size_t)e->P.G;
-    if (!e->P.gumbel_a && dev_alloc(e, &e->P.gumbel_a, G * MAX_MOVES))
-        return -1;
-    if (!e->P.gumbel_v0 && dev_alloc(e, &e->P.gumbel_v0, G))
+    if (dev_alloc_once(e, &e->P.gumbel_a, G * MAX_MOVES) || dev_alloc_once(e, &e->P.gumbel_v0, G))
         return -1;
     if (gumbel_upload_table(e, m, e->P.visits))
         return -1;
@@ -2255,21 +2279,14 @@ extern "C" int azh_engine_set_resign(azh_engine *e, float q_below, int consecuti
         return azh_fail(-2, "azh_engine_set_resign: need 0 <= consecutive <= 255 (0: off)");
     if (consecutive != 0 && (!(q_below >= 0.0f) || !(q_below < 1.0f) || playthrough_per_65536 < 0 || playthrough_per_65536 > 65536))
         return azh_fail(-2, "azh_engine_set_resign: need 0 <= q_below < 1 and 0 <= playthrough_per_65536 <= 65536");
-    if (e->selected)
-        return azh_fail(-3, "azh_engine_set_resign: a selected batch awaits its backup");
-    if (consecutive != 0 && (e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_ONE_RANDOM_MOVE)))
-        return azh_fail(-4, "azh_engine_set_resign: not supported with %s",
-                        (e->P.flags & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS" : "AZH_FLAG_ONE_RANDOM_MOVE");
-    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_TRY(mode_request(e, "azh_engine_set_resign", consecutive != 0 ? MODE_RESIGN : MODE_NONE));
     if (consecutive == 0) {
         e->P.resign_plies = 0u;
         e->P.resign_below = 0.0f;
         e->P.resign_through = 0u;
         return 0;
     }
-    if (!e->P.resign_state && dev_alloc(e, &e->P.resign_state, (size_t)e->P.G))
-        return -1;
-    if (!e->P.resign_stats && dev_alloc(e, &e->P.resign_stats, (size_t)AZH_RESIGN_STAT_COUNT))
+    if (dev_alloc_once(e, &e->P.resign_state, (size_t)e->P.G) || dev_alloc_once(e, &e->P.resign_stats, (size_t)AZH_RESIGN_STAT_COUNT))
         return -1;
     AZH_HIP(hipMemset(e->P.resign_state, 0, (size_t)e->P.G * sizeof(u32)));
     e->P.resign_below = q_below;
@@ -2279,7 +2296,7 @@ extern "C" int azh_engine_set_resign(azh_engine *e, float q_below, int consecuti
 }
 
 // Per-ply temperature of the move played and of the root policy.  Definition: the header and DESIGN.md.  Between iterations
-// only.  Every check comes before the first change, so a refused call leaves the engine as it was.
+// only.
 static bool temperature_entry_ok(float t, bool move)
 {
     if (move)
@@ -2300,22 +2317,11 @@ extern "C" int azh_engine_set_temperature(azh_engine *e, const float *move_tempe
         if (!temperature_entry_ok(root_policy_temperature[p], false))
             return azh_fail(-2, "azh_engine_set_temperature: root_policy_temperature[%d] = %g: need 1/4 <= R <= 64", p,
                             (double)root_policy_temperature[p]);
-    if (e->selected)
-        return azh_fail(-3, "azh_engine_set_temperature: a selected batch awaits its backup");
-    const u32 bad = AZH_FLAG_ONE_RANDOM_MOVE | AZH_FLAG_SAMPLE_POW5 | AZH_FLAG_PY_POSTERIOR | AZH_FLAG_TWO_NETS;
-    if ((move_temperature || root_policy_temperature) && (e->P.flags & bad))
-        return azh_fail(-4, "azh_engine_set_temperature: not supported with %s",
-                        (e->P.flags & AZH_FLAG_ONE_RANDOM_MOVE) ? "AZH_FLAG_ONE_RANDOM_MOVE"
-                        : (e->P.flags & AZH_FLAG_SAMPLE_POW5)   ? "AZH_FLAG_SAMPLE_POW5"
-                        : (e->P.flags & AZH_FLAG_PY_POSTERIOR)  ? "AZH_FLAG_PY_POSTERIOR"
-                                                                : "AZH_FLAG_TWO_NETS");
-    if ((move_temperature || root_policy_temperature) && e->P.gumbel_m != 0)
-        return azh_fail(-4, "azh_engine_set_temperature: not supported with the Gumbel root search (azh_engine_set_gumbel)");
-    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_TRY(mode_request(e, "azh_engine_set_temperature", move_temperature || root_policy_temperature ? MODE_TEMPERATURE : MODE_NONE));
     // the engine's two tables are allocated once and kept; a null argument only takes the pointer out of the parameters
-    if (move_temperature && !e->d_move_temperature && dev_alloc(e, &e->d_move_temperature, (size_t)n))
+    if (move_temperature && dev_alloc_once(e, &e->d_move_temperature, (size_t)n))
         return -1;
-    if (root_policy_temperature && !e->d_root_policy_temperature && dev_alloc(e, &e->d_root_policy_temperature, (size_t)n))
+    if (root_policy_temperature && dev_alloc_once(e, &e->d_root_policy_temperature, (size_t)n))
         return -1;
     if (move_temperature)
         AZH_HIP(hipMemcpy(e->d_move_temperature, move_temperature, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
@@ -2359,12 +2365,6 @@ extern "C" int azh_engine_resign_stats(azh_engine *e, uint64_t *out)
     return 0;
 }
 
-// Is `bb` its own image under all 8 symmetries?  (the two mirrors and the transposition generate them)
-static bool symmetry_invariant(u64 bb)
-{
-    return symmetry_board(1, bb) == bb && symmetry_board(2, bb) == bb && symmetry_board(4, bb) == bb;
-}
-
 // Random symmetry per evaluation: every position goes to the evaluator as its image under a symmetry that is a pure function
 // of (seed, uid, position), and its logits are gathered through the same symmetry's move map.  Definition: the header and
 // DESIGN.md.  Between iterations only.
@@ -2372,21 +2372,12 @@ extern "C" int azh_engine_set_random_symmetry(azh_engine *e, int on)
 {
     if (!e)
         return azh_fail(-1, "azh_engine_set_random_symmetry: null engine");
-    if (e->selected)
-        return azh_fail(-3, "azh_engine_set_random_symmetry: a selected batch awaits its backup");
-    if (on && (e->P.flags & (AZH_FLAG_TWO_NETS | AZH_FLAG_SYMMETRY_AVG)))
-        return azh_fail(-4, "azh_engine_set_random_symmetry: not supported with %s",
-                        (e->P.flags & AZH_FLAG_TWO_NETS) ? "AZH_FLAG_TWO_NETS" : "AZH_FLAG_SYMMETRY_AVG");
-    if (on && !symmetry_invariant(e->P.blockers & BOARD_MASK))
-        return azh_fail(-4, "azh_engine_set_random_symmetry: not supported with a blockers mask (0x%llx) that is not its own "
-                            "image under all 8 symmetries (the tower takes one blocker plane per launch)",
-                        (unsigned long long)e->P.blockers);
-    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_TRY(mode_request(e, "azh_engine_set_random_symmetry", on ? MODE_SYMMETRY : MODE_NONE));
     if (!on) {
         e->P.random_symmetry = 0u;
         return 0;
     }
-    if (!e->P.eval_key && dev_alloc(e, &e->P.eval_key, (size_t)e->P.G))
+    if (dev_alloc_once(e, &e->P.eval_key, (size_t)e->P.G))
         return -1;
     e->P.random_symmetry = 1u;
     hipLaunchKernelGGL(k_eval_keys, dim3((e->P.G + 255) / 256), dim3(256), 0, e->stream, e->P);
@@ -2510,7 +2501,7 @@ extern "C" int azh_engine_play_moves(azh_engine *e, const uint16_t *moves, int32
     if (e->P.flags & AZH_FLAG_TWO_NETS)
         return azh_fail(-4, "azh_engine_play_moves: not available on AZH_FLAG_TWO_NETS engines");
     const size_t G = (size_t)e->P.G;
-    if (!e->d_play_moves && (dev_alloc(e, &e->d_play_moves, G) || dev_alloc(e, &e->d_play_status, G)))
+    if (dev_alloc_once(e, &e->d_play_moves, G) || dev_alloc_once(e, &e->d_play_status, G))
         return -1;
     AZH_HIP(hipMemcpyAsync(e->d_play_moves, moves, G * sizeof(u16), hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(k_play_moves, dim3(e->P.G), dim3(WAVE), 0, e->stream, e->P, (const u16 *)e->d_play_moves, e->d_play_status);
@@ -2526,7 +2517,7 @@ extern "C" int azh_engine_root_report(azh_engine *e, int first_game, int n_games
 {
     if (!e || !out || first_game < 0 || n_games < 1 || first_game > e->P.G - n_games)
         return azh_fail(-1, "azh_engine_root_report: bad argument");
-    if (!e->d_report && dev_alloc(e, &e->d_report, (size_t)e->P.G * AZH_ROOT_REPORT_WORDS))
+    if (dev_alloc_once(e, &e->d_report, (size_t)e->P.G * AZH_ROOT_REPORT_WORDS))
         return -1;
     hipLaunchKernelGGL(k_root_report, dim3(n_games), dim3(WAVE), 0, e->stream, e->P, first_game, e->d_report);
     AZH_HIP(hipGetLastError());
@@ -2540,7 +2531,7 @@ extern "C" int azh_engine_root_proofs(azh_engine *e, int first_game, int n_games
 {
     if (!e || !out || first_game < 0 || n_games < 1 || first_game > e->P.G - n_games)
         return azh_fail(-1, "azh_engine_root_proofs: bad argument");
-    if (!e->d_proofs && dev_alloc(e, &e->d_proofs, (size_t)e->P.G * AZH_ROOT_PROOF_WORDS))
+    if (dev_alloc_once(e, &e->d_proofs, (size_t)e->P.G * AZH_ROOT_PROOF_WORDS))
         return -1;
     hipLaunchKernelGGL(k_root_proofs, dim3(n_games), dim3(WAVE), 0, e->stream, e->P, first_game, e->d_proofs);
     AZH_HIP(hipGetLastError());

@@ -241,13 +241,41 @@ int azh_engine_sync(azh_engine *e);
 /* change the root-visit threshold (global_visits) for the coming moves; 1 <= visits <= the
  * value the engine was created with */
 int azh_engine_set_visits(azh_engine *e, int visits);
+/* SEARCH MODES: WHO REFUSES WHOM.  Eight modes are switched by setters below, before the first select or between iterations.
+ * A call that switches a mode on is a request for it; one that switches it off is not, and is never refused for a reason in
+ * this table.  Every one of these setters checks in this order, and changes nothing unless every check passes: -1 a null
+ * engine, -2 a value out of range, -3 a selected batch awaits its backup (requests and switching off alike), -4 the request
+ * is refused by a row of this table.
+ *
+ *   mode            is on while                 refused on an engine created with                         refused beside
+ *   playout cap     fast_visits != 0            TWO_NETS, ONE_RANDOM_MOVE                                 Gumbel
+ *   forced playouts k != 0                      TWO_NETS, ONE_RANDOM_MOVE                                 Gumbel, leaf batch, solver
+ *   Gumbel          m != 0                      TWO_NETS, ONE_RANDOM_MOVE, SAMPLE_POW5, EVAL_CACHE;       playout cap, forced playouts,
+ *                                               without NO_REUSE; dirichlet_weight != 0                   temperature, leaf batch, solver
+ *   temperature     either table is set         TWO_NETS, ONE_RANDOM_MOVE, SAMPLE_POW5, PY_POSTERIOR      Gumbel
+ *   resign          consecutive != 0            TWO_NETS, ONE_RANDOM_MOVE                                 -
+ *   random symmetry on != 0                     TWO_NETS, SYMMETRY_AVG; a blockers mask that is not its   -
+ *                                               own image under all 8 symmetries
+ *   leaf batch      leaves_per_game > 1         TWO_NETS, EVAL_CACHE, SYMMETRY_AVG; select_budget > 0     Gumbel, forced playouts
+ *   solver          on != 0                     TWO_NETS, EVAL_CACHE, SYMMETRY_AVG; select_budget > 0     Gumbel, forced playouts
+ *
+ * The last column is symmetric: of two modes that exclude each other, whichever is asked for second is refused, and comes on
+ * once the other is off.  Everything not listed composes.  The message (azh_last_error) is "<setter>: not supported with
+ * <cause>", from azh_engine_set_leaf_batch and azh_engine_set_solver "<setter>: more than one leaf per game is not supported
+ * with <cause>" / "<setter>: the solver is not supported with <cause>"; the cause is the flag (AZH_FLAG_...), "select_budget
+ * > 0", the blockers mask, or the mode that is on with its setter: "the playout cap (azh_engine_set_playout_cap)", "forced
+ * playouts (azh_engine_set_forced_playouts)", "the Gumbel root search (azh_engine_set_gumbel)", "a temperature table
+ * (azh_engine_set_temperature)", "more than one leaf per game (azh_engine_set_leaf_batch)", "the solver"; Gumbel on an engine
+ * without NO_REUSE or with a dirichlet_weight says that the engine must have been created with both.  Where several causes
+ * apply the message names one: a flag before anything else, in the order TWO_NETS, ONE_RANDOM_MOVE, SAMPLE_POW5, PY_POSTERIOR,
+ * EVAL_CACHE, SYMMETRY_AVG, then the other create-time causes, then the modes, Gumbel first.  The paragraphs below say why. */
 /* Leaf-parallel search (an extension; the reference searches one leaf per tree at a time): every game selects up to
  * `leaves_per_game` = K leaves per iteration (1 <= K <= 64), spread over different lines by a virtual loss of
  * `virtual_loss` visits (1 .. 16) on every edge an earlier path of the batch took; the leaves of all games are evaluated
  * in one tower launch (slots g K + p; the thin tower while G K <= AZH_THIN_MAX_GAMES) and every path is backed up before
  * the next select.  Definition: DESIGN.md, "Leaf-parallel search".  Call before the first select or between iterations;
  * K = 1 restores the one-leaf search exactly.  K > 1 is refused with AZH_FLAG_TWO_NETS, AZH_FLAG_EVAL_CACHE,
- * AZH_FLAG_SYMMETRY_AVG and select_budget > 0.  With K > 1, azh_engine_select / _eval / _backup / _run work on the
+ * AZH_FLAG_SYMMETRY_AVG and select_budget > 0 (the table above).  With K > 1, azh_engine_select / _eval / _backup / _run work on the
  * batch, azh_engine_leaves / _set_evals / _leaf_features / _tree_stamps return an error (their buffers are G-sized): use
  * the two calls below. */
 int azh_engine_set_leaf_batch(azh_engine *e, int leaves_per_game, int virtual_loss);
@@ -272,7 +300,7 @@ int azh_engine_set_batch_evals(azh_engine *e, const float *logits, const float *
  * between "dists" and "moves".  Lines of an engine with the mode off are byte for byte what they were.
  * fast_visits = 0 switches the mode off; else 1 <= fast_visits <= visits and 0 <= full_per_65536 <= 65536 (65536: every
  * ply FULL, 0: none).  Call before the first select or between iterations.  Refused with AZH_FLAG_TWO_NETS (match play
- * searches every move alike) and AZH_FLAG_ONE_RANDOM_MOVE; while it is on azh_engine_set_visits refuses values below
+ * searches every move alike) and AZH_FLAG_ONE_RANDOM_MOVE (the table above); while it is on azh_engine_set_visits refuses values below
  * fast_visits.  Definition and measurements: DESIGN.md, "Playout cap randomization". */
 int azh_engine_set_playout_cap(azh_engine *e, int fast_visits, int full_per_65536);
 /* The kind of ply `ply` of game `uid` of an engine created with `seed`: 1 FULL, 0 FAST.  Host arithmetic only, usable
@@ -299,7 +327,7 @@ int azh_playout_cap_kind(uint64_t seed, uint32_t uid, uint32_t ply, uint32_t ful
  * The record of a game finished while the mode is on carries bit 3 (value 8) in header word 7; its line has the usual keys.
  * Refused (the engine stays as it was) with AZH_FLAG_TWO_NETS and AZH_FLAG_ONE_RANDOM_MOVE, with more than one leaf per
  * game and with the solver; while the mode is on azh_engine_set_leaf_batch (K > 1) and azh_engine_set_solver (on) refuse in
- * turn.  Call before the first select or between iterations.  Definition and measurements: DESIGN.md, "Forced playouts and
+ * turn (the table above).  Call before the first select or between iterations.  Definition and measurements: DESIGN.md, "Forced playouts and
  * policy target pruning". */
 int azh_engine_set_forced_playouts(azh_engine *e, float k);
 /* The visit counts the pruning above writes for a root of M edges — prior [M] (after the noise mix), W [M] total scores,
@@ -343,7 +371,7 @@ int azh_forced_prune(const float *prior, const float *W, const uint32_t *n, int 
  * Refused (the engine stays as it was) unless the engine was created with AZH_FLAG_NO_REUSE and dirichlet_weight 0; with
  * AZH_FLAG_TWO_NETS, _ONE_RANDOM_MOVE, _SAMPLE_POW5, _EVAL_CACHE; and while the playout cap, forced playouts, a temperature
  * table, more than one leaf per game or the solver is on — their setters refuse in turn while this mode is on.  Random symmetry
- * and azh_engine_set_resign stay allowed.  Definition and measurements: DESIGN.md, "Gumbel root search with sequential
+ * and azh_engine_set_resign stay allowed (the table above).  Definition and measurements: DESIGN.md, "Gumbel root search with sequential
  * halving". */
 int azh_engine_set_gumbel(azh_engine *e, int m, float c_visit, float c_scale);
 /* seq(m, visits) above, out [visits] (1 <= m <= 256, 1 <= visits <= 60000).  Host arithmetic only, usable without a device. */
@@ -382,7 +410,7 @@ int azh_gumbel_root(const float *prior, const float *W, const uint32_t *n, int M
  * leaf-parallel search, the solver, thin batches, half-batches, azh_engine_play_moves and azh_engine_set_positions.
  * Refused (the engine stays as it was) with AZH_FLAG_TWO_NETS, with AZH_FLAG_SYMMETRY_AVG, and when the engine's blockers
  * mask is not its own image under all 8 symmetries (the tower takes the blocker plane once per launch; no blockers, the four
- * corners and the self-play start's diamond are).  Call before the first select or between iterations; off (0) is the state
+ * corners and the self-play start's diamond are); the table above.  Call before the first select or between iterations; off (0) is the state
  * after create.  Definition and measurements: DESIGN.md, "Random symmetry per evaluation". */
 int azh_engine_set_random_symmetry(azh_engine *e, int on);
 /* The symmetry, 0..7, under which an engine created with `seed` and the mode on evaluates the position (mover, opponent) of
@@ -427,7 +455,7 @@ int azh_symmetry_policy_index(int s, int index);
  * forced playouts and random symmetry are untouched, and with the mode off every state, tree and record word and every
  * output byte is what it was.
  * Refused (the engine stays as it was) with AZH_FLAG_TWO_NETS and AZH_FLAG_ONE_RANDOM_MOVE, and while a selected batch
- * awaits its backup.  Call before the first select or between iterations; setting it clears every slot's counters.
+ * awaits its backup (the table above).  Call before the first select or between iterations; setting it clears every slot's counters.
  * Definition and measurements: DESIGN.md, "Recorded search value and resignation". */
 int azh_engine_set_resign(azh_engine *e, float q_below, int consecutive, int playthrough_per_65536);
 /* Is game `uid` of an engine created with `seed` a play-through game?  1 / 0.  Host arithmetic only. */
@@ -465,7 +493,7 @@ int azh_engine_resign_stats(azh_engine *e, uint64_t *out /* [AZH_RESIGN_STAT_COU
  * Refused, the engine left as it was: an entry that is NaN or negative, a move temperature that is neither 0 nor in
  * [1/64, 64] (one in (0, 1/64) is refused, not rounded), a root policy temperature outside [1/4, 64]; tables on an engine
  * with AZH_FLAG_ONE_RANDOM_MOVE, AZH_FLAG_SAMPLE_POW5, AZH_FLAG_PY_POSTERIOR or AZH_FLAG_TWO_NETS; a call while a selected
- * batch awaits its backup.  Call before the first select or between iterations.
+ * batch awaits its backup; tables while the Gumbel root search is on (the table above).  Call before the first select or between iterations.
  * Definition and measurements: DESIGN.md, "Temperature of the move and of the root policy". */
 int azh_engine_set_temperature(azh_engine *e, const float *move_temperature /* [max_plies] or NULL */,
                                const float *root_policy_temperature /* [max_plies] or NULL */);
@@ -488,7 +516,7 @@ int azh_temperature_pick(const uint32_t *visits, int M, float temperature, uint6
  * (azh_engine_tree_raw) is set; both are carried through re-roots (the device's own moves and azh_engine_play_moves).
  * While the solver is on, EVERY leaves_per_game — 1 included — runs through the leaf-parallel kernel: the step-wise calls
  * are azh_engine_batch_leaves / _set_batch_evals with K = leaves_per_game slots per game.  Call between iterations only.
- * Refused with AZH_FLAG_TWO_NETS, AZH_FLAG_EVAL_CACHE, AZH_FLAG_SYMMETRY_AVG and select_budget > 0.  Turning it off
+ * Refused with AZH_FLAG_TWO_NETS, AZH_FLAG_EVAL_CACHE, AZH_FLAG_SYMMETRY_AVG and select_budget > 0 (the table above).  Turning it off
  * returns to the dispatch azh_engine_set_leaf_batch describes; marks already in the tree stay where they are (every tree
  * kernel ends a path at them as at a finished position). */
 int azh_engine_set_solver(azh_engine *e, int on);
