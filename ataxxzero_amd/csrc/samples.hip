@@ -21,6 +21,9 @@ namespace {
 constexpr int FEATURES = 196, POLICY = 833, SAMPLE_FLOATS = FEATURES + POLICY + 1;
 constexpr int MAX_ATTEMPTS = 64;  // one per lane of the wave that draws the sample
 constexpr u32 GAME_HAS_FULL = 1u << 8, GAME_HAS_VALUES = 1u << 9;
+constexpr u32 PLY_ODD = 0x80u;  // in the device's targets_flags only: o is the mover (the surprise kernel sees no game)
+constexpr u32 WEIGHT_ONE = 65536u;
+constexpr int SURPRISE_CHUNK = 16384;
 
 struct Ply {  // 32 bytes
     u64 x, o;      // bit = file + 7 * rank, the ring record's layout
@@ -36,6 +39,7 @@ struct View {  // what the kernels read
     const u32 *candidate_count;
     const u16 *target_index;
     const float *target_weight;
+    const u32 *cum;  // null: uniform ply draws; else [first ply + k]: the running sum of the game's candidate weights
 };
 
 // One wave builds sample `i` in LDS and writes it out with coalesced stores; g < 0: the sample is all zeros.
@@ -96,9 +100,11 @@ struct Attempt {
     bool ok;
 };
 
-template <class GameAt, class CountAt, class CandidateAt, class FlagsAt>
+// `weighted`: the ply is picked by cum_at (the running sums of the game's candidate weights) instead of uniformly.
+template <class GameAt, class CountAt, class CandidateAt, class FlagsAt, class CumAt>
 __host__ __device__ inline Attempt draw_attempt(u32 k0, u32 k1, u32 step, u32 i, u32 a, u32 first_game, u32 n_games,
-                                                GameAt game_at, CountAt count_at, CandidateAt candidate_at, FlagsAt flags_at)
+                                                GameAt game_at, CountAt count_at, CandidateAt candidate_at, FlagsAt flags_at,
+                                                bool weighted, CumAt cum_at)
 {
     const Philox4 r = philox(k0, k1, step, i, a, STREAM_SAMPLE_DRAW);
     Attempt out;
@@ -108,8 +114,25 @@ __host__ __device__ inline Attempt draw_attempt(u32 k0, u32 k1, u32 step, u32 i,
     const u32 c = count_at(out.game);
     out.ply = 0;
     out.ok = c != 0;  // a game that carries "full" without one full ply gives no sample, whatever else it carries
+    u32 k = 0;
+    if (out.ok && weighted) {
+        const u32 total = cum_at(game.x + c - 1u);
+        out.ok = total != 0u;
+        const u32 R = (u32)(((u64)r.v[1] * total) >> 32);
+        u32 lo = 0, hi = c - 1u;  // the first k with cum[k] > R: cum[c - 1] = total > R
+        while (lo < hi) {
+            const u32 mid = (lo + hi) >> 1;
+            if (cum_at(game.x + mid) > R)
+                hi = mid;
+            else
+                lo = mid + 1u;
+        }
+        k = lo;
+    } else if (out.ok) {
+        k = (u32)(((u64)r.v[1] * c) >> 32);
+    }
     if (out.ok) {
-        out.ply = game.w ? (int)game.w : (int)candidate_at(game.x + (u32)(((u64)r.v[1] * c) >> 32));
+        out.ply = game.w ? (int)game.w : (int)candidate_at(game.x + k);
         out.ok = (u32)out.ply < game.y &&
                  !(flags_at(game.x + (u32)out.ply) & (AZH_SAMPLES_PLY_PASS | AZH_SAMPLES_PLY_BAD));
     }
@@ -128,7 +151,7 @@ __global__ __launch_bounds__(WAVE) void k_samples_draw_gather(View v, int n, u32
     const Attempt mine = draw_attempt(
         k0, k1, step, (u32)i, (u32)lane, first_game, n_games, [&](int g) { return v.games[g]; },
         [&](int g) { return v.candidate_count[g]; }, [&](u32 at) { return (u32)v.candidates[at]; },
-        [&](u32 at) { return v.plies[at].targets_flags & 0xFFu; });
+        [&](u32 at) { return v.plies[at].targets_flags & 0xFFu; }, v.cum != nullptr, [&](u32 at) { return v.cum[at]; });
     const u64 ok = __ballot(mine.ok);
     const int first = ok ? (int)__builtin_ctzll(ok) : 0;
     const int g = ok ? __shfl(mine.game, first) : -1;
@@ -145,6 +168,86 @@ __global__ __launch_bounds__(WAVE) void k_samples_draw_gather(View v, int n, u32
         }
     }
     emit_sample(v, lds, i, g, p, s, blend, features, policy, value);
+}
+
+// ---------------------------------------------------------------- policy surprise (include/ataxxzero_hip.h)
+
+// The stored value of a ply's KL: a negative, NaN or infinite sum reads 0.
+__host__ __device__ inline float stored_surprise(float kl) { return (kl >= 0.0f && kl <= 3.40282347e38f) ? kl : 0.0f; }
+// One target's term; lp = log p_t.
+__host__ __device__ inline float surprise_term(float w, float lp) { return w * (det_logf(w) - lp); }
+
+// The boards of plies [first, first + n) as the tower takes them: (mover, opponent).
+__global__ __launch_bounds__(256) void k_samples_pack_boards(View v, u32 first, int n, u64 *boards)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n)
+        return;
+    const Ply ply = v.plies[first + (u32)i];
+    const bool odd = (ply.targets_flags & PLY_ODD) != 0;
+    boards[2 * i] = odd ? ply.o : ply.x;
+    boards[2 * i + 1] = odd ? ply.x : ply.o;
+}
+
+// One wave per ply: movegen into LDS, the legal moves marked in an 833-cell map and their logits reduced to (mx, S) in the
+// engine's lane order (apply_priors: move j in lane j % 64, ascending j, then the butterfly), then the targets 64 per step.
+// logits: row i belongs to ply first + i.  A position has at most 49 * 16 jumps and 49 clones: the move list holds them all.
+__global__ __launch_bounds__(WAVE) void k_samples_surprise(View v, u32 first, int n, const float *__restrict__ logits,
+                                                           float *__restrict__ kl_out, u32 *illegal)
+{
+    __shared__ u16 moves[POLICY + 3];
+    __shared__ u32 legal[(POLICY + 31) / 32];
+    const int i = (int)blockIdx.x;
+    if (i >= n)
+        return;
+    const int lane = (int)threadIdx.x;
+    const Ply ply = v.plies[first + (u32)i];
+    const u32 flags = ply.targets_flags & 0xFFu;
+    float out = 0.0f;
+    if (!(flags & (AZH_SAMPLES_PLY_PASS | AZH_SAMPLES_PLY_BAD))) {  // (wave-uniform)
+        if (lane < (POLICY + 31) / 32)
+            legal[lane] = 0u;
+        Board b;
+        b.x = ply.x;
+        b.o = ply.o;
+        b.turn = (flags & PLY_ODD) ? 1 : 0;
+        const int M = wave_movegen(b, 0ULL, moves, nullptr);
+        __syncthreads();
+        const float *row = logits + (size_t)i * POLICY;
+        float mx = -INFINITY;
+        for (int j = lane; j < M; j += WAVE) {
+            const int at = policy_index(moves[j]);
+            atomicOr(&legal[at >> 5], 1u << (at & 31));
+            const float l = row[at];
+            if (l > mx)
+                mx = l;
+        }
+        mx = wave_max_f32(mx);
+        float part = 0.0f;
+        for (int j = lane; j < M; j += WAVE)
+            part = part + det_expf(row[policy_index(moves[j])] - mx);
+        const float log_s = det_logf(wave_sum_f32(part));
+        __syncthreads();
+        const u32 count = ply.targets_flags >> 8;
+        float acc = 0.0f;
+        int missing = 0;
+        for (u32 t = (u32)lane; t < count; t += WAVE) {
+            const int at = v.target_index[ply.first_target + t];
+            const float w = v.target_weight[ply.first_target + t];
+            if (w > 0.0f) {
+                if ((legal[at >> 5] >> (at & 31)) & 1u)
+                    acc = acc + surprise_term(w, (row[at] - mx) - log_s);
+                else
+                    missing++;
+            }
+        }
+        out = stored_surprise(wave_sum_f32(acc));
+        missing = wave_sum_int(missing);
+        if (lane == 0 && missing)
+            atomicAdd(illegal, (u32)missing);
+    }
+    if (lane == 0)
+        kl_out[first + (u32)i] = out;
 }
 
 template <class T>
@@ -209,9 +312,18 @@ struct azh_samples {
     DeviceArray<u16> d_target_index;
     DeviceArray<float> d_target_weight;
     DeviceArray<u32> d_errors;
+    // policy surprise weighting: all null until asked for
+    DeviceArray<u32> d_cum;      // [cap_plies] beside d_candidates (azh_samples_set_ply_weights)
+    DeviceArray<float> d_kl;     // [cap_plies]: the last surprise of every ply
+    DeviceArray<u32> d_illegal;  // [1]
+    std::vector<u32> h_cum;      // [plies] while d_cum is held
+    int surprise_chunk = SURPRISE_CHUNK;
+    float surprise_ms[2] = {0.f, 0.f};
     // the host mirror: what a draw is validated against
     std::vector<uint32_t> h_games;  // [games][4]
     std::vector<uint8_t> h_flags;   // [plies]
+    std::vector<u16> h_candidates;  // [plies]
+    std::vector<u32> h_count;       // [games]
     // draws on their way to the device: two pinned buffers and two device buffers taken in turn, each guarded by the event
     // recorded behind the kernel that read it, so the next call never waits for this one
     hipStream_t stream = nullptr;
@@ -223,7 +335,7 @@ struct azh_samples {
 
     View view() const
     {
-        return View{d_games.d, d_plies.d, d_candidates.d, d_candidate_count.d, d_target_index.d, d_target_weight.d};
+        return View{d_games.d, d_plies.d, d_candidates.d, d_candidate_count.d, d_target_index.d, d_target_weight.d, d_cum.d};
     }
 };
 
@@ -272,6 +384,9 @@ extern "C" void azh_samples_destroy(azh_samples *s)
     s->d_target_index.release();
     s->d_target_weight.release();
     s->d_errors.release();
+    s->d_cum.release();
+    s->d_kl.release();
+    s->d_illegal.release();
     if (s->stream)
         (void)hipStreamDestroy(s->stream);
     delete s;
@@ -352,7 +467,7 @@ extern "C" int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint
             }
             p_flags[(size_t)q] = f;
             p_words[(size_t)q] = Ply{boards[2 * q] & BOARD_MASK, boards[2 * q + 1] & BOARD_MASK, values[q],
-                                     (u32)(s->targets + lo), (u32)(hi - lo) << 8 | f};
+                                     (u32)(s->targets + lo), (u32)(hi - lo) << 8 | f | ((p & 1u) ? PLY_ODD : 0u)};
             if (!(w[2] & GAME_HAS_FULL) || (f & AZH_SAMPLES_PLY_FULL))
                 p_candidates[(size_t)(at + c++)] = (u16)p;
         }
@@ -381,7 +496,18 @@ extern "C" int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint
         AZH_HIP(hipMemcpyAsync(s->d_target_index.d + s->targets, target_index, (size_t)n_targets * sizeof(u16), hipMemcpyHostToDevice, s->stream));
         AZH_HIP(hipMemcpyAsync(s->d_target_weight.d + s->targets, target_weight, (size_t)n_targets * sizeof(float), hipMemcpyHostToDevice, s->stream));
     }
+    std::vector<u32> p_cum;
+    if (s->d_cum.d && n_plies) {  // weights are held: the new games' candidates weigh one each
+        p_cum.resize((size_t)n_plies);
+        for (int64_t g = 0; g < n_games; g++)
+            for (u32 k = 0; k < games[4 * g + 1]; k++)
+                p_cum[(size_t)games[4 * g] + k] = WEIGHT_ONE * (k + 1u);
+        AZH_HIP(hipMemcpyAsync(s->d_cum.d + s->plies, p_cum.data(), (size_t)n_plies * sizeof(u32), hipMemcpyHostToDevice, s->stream));
+    }
     AZH_HIP(hipStreamSynchronize(s->stream));
+    s->h_cum.insert(s->h_cum.end(), p_cum.begin(), p_cum.end());
+    s->h_candidates.insert(s->h_candidates.end(), p_candidates.begin(), p_candidates.end());
+    s->h_count.insert(s->h_count.end(), g_count.begin(), g_count.end());
     for (int64_t g = 0; g < n_games; g++) {
         const uint4 w = g_words[(size_t)g];
         s->h_games.insert(s->h_games.end(), {w.x, w.y, w.z, w.w});
@@ -593,13 +719,16 @@ extern "C" int azh_samples_draw_gather(azh_samples *s, int n, uint64_t seed, uin
 }
 
 // One sample's draw restated on the host from mirror arrays: arithmetic only, no device and no store.
-extern "C" int azh_samples_draw(uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
-                                const uint32_t *games, int64_t total_games, const uint8_t *ply_flags, int32_t *out)
+// cum == null: the uniform ply draw, the candidates found from the flags; else the weighted one from the mirrors of the
+// store's candidates and cum arrays (azh_samples_ply_cum).
+static int draw_host(const char *what, uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
+                     const uint32_t *games, int64_t total_games, const uint8_t *ply_flags, const uint16_t *candidates,
+                     const uint32_t *cum, int32_t *out)
 {
     if (!games || !ply_flags || !out)
-        return azh_fail(-1, "azh_samples_draw: null argument");
+        return azh_fail(-1, "%s: null argument", what);
     if (first_game < 0 || n_games < 1 || first_game + n_games > total_games || total_games > 0x7FFFFFFF)
-        return azh_fail(-1, "azh_samples_draw: games [%lld, %lld) of %lld", (long long)first_game,
+        return azh_fail(-1, "%s: games [%lld, %lld) of %lld", what, (long long)first_game,
                         (long long)(first_game + n_games), (long long)total_games);
     auto game_at = [&](int g) { return make_uint4(games[4 * g], games[4 * g + 1], games[4 * g + 2], games[4 * g + 3]); };
     auto candidate = [&](int g, uint32_t flag) {  // plies a sample may come from: all, or the full ones of a game with "full"
@@ -619,13 +748,15 @@ extern "C" int azh_samples_draw(uint64_t seed, uint32_t step, uint32_t sample, i
                 return c;
             },
             [&](u32 at) {  // the k-th candidate of the drawn game, k = at - first ply
+                if (candidates)
+                    return (u32)candidates[at];
                 u32 k = at - games[4 * drawn];
                 for (uint32_t p = 0; p < games[4 * drawn + 1]; p++)
                     if (candidate(drawn, ply_flags[games[4 * drawn] + p]) && k-- == 0)
                         return p;
                 return 0u;
             },
-            [&](u32 at) { return (u32)ply_flags[at]; });
+            [&](u32 at) { return (u32)ply_flags[at]; }, cum != nullptr, [&](u32 at) { return cum[at]; });
         if (t.ok) {
             out[0] = t.game;
             out[1] = t.ply;
@@ -637,6 +768,23 @@ extern "C" int azh_samples_draw(uint64_t seed, uint32_t step, uint32_t sample, i
     return 0;
 }
 
+extern "C" int azh_samples_draw(uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
+                                const uint32_t *games, int64_t total_games, const uint8_t *ply_flags, int32_t *out)
+{
+    return draw_host("azh_samples_draw", seed, step, sample, first_game, n_games, games, total_games, ply_flags, nullptr, nullptr,
+                     out);
+}
+
+extern "C" int azh_samples_draw_weighted(uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
+                                         const uint32_t *games, int64_t total_games, const uint8_t *ply_flags,
+                                         const uint16_t *candidates, const uint32_t *cum, int32_t *out)
+{
+    if (!candidates || !cum)
+        return azh_fail(-1, "azh_samples_draw_weighted: null argument");
+    return draw_host("azh_samples_draw_weighted", seed, step, sample, first_game, n_games, games, total_games, ply_flags,
+                     candidates, cum, out);
+}
+
 extern "C" int azh_samples_status(azh_samples *s, int64_t *failed)
 {
     if (!s || !failed)
@@ -645,5 +793,270 @@ extern "C" int azh_samples_status(azh_samples *s, int64_t *failed)
     AZH_HIP(hipDeviceSynchronize());
     AZH_HIP(hipMemcpy(&n, s->d_errors.d, sizeof(u32), hipMemcpyDeviceToHost));
     *failed = (int64_t)n;
+    return 0;
+}
+
+// ---------------------------------------------------------------- policy surprise weighting: entry points
+
+static int reserve_surprise(azh_samples *s)
+{
+    if (!s->d_kl.d) {
+        if (int rc = s->d_kl.alloc((size_t)s->cap_plies))
+            return rc;
+        AZH_HIP(hipMemset(s->d_kl.d, 0, (size_t)s->cap_plies * sizeof(float)));
+    }
+    if (!s->d_illegal.d)
+        if (int rc = s->d_illegal.alloc(1))
+            return rc;
+    return 0;
+}
+
+extern "C" int azh_samples_surprise_logits(azh_samples *s, int64_t first_ply, int64_t n_plies, const float *d_logits,
+                                           float *kl_out, int64_t *illegal_out, uintptr_t stream)
+{
+    if (!s || !d_logits || !kl_out || !illegal_out)
+        return azh_fail(-1, "azh_samples_surprise_logits: null argument");
+    if (first_ply < 0 || n_plies < 1 || first_ply + n_plies > s->plies)
+        return azh_fail(-1, "azh_samples_surprise_logits: plies [%lld, %lld) of %lld", (long long)first_ply,
+                        (long long)(first_ply + n_plies), (long long)s->plies);
+    if (int rc = reserve_surprise(s))
+        return rc;
+    hipStream_t st = stream ? (hipStream_t)stream : s->stream;
+    AZH_HIP(hipMemsetAsync(s->d_illegal.d, 0, sizeof(u32), st));
+    hipLaunchKernelGGL(k_samples_surprise, dim3((unsigned)n_plies), dim3(WAVE), 0, st, s->view(), (u32)first_ply, (int)n_plies,
+                       d_logits, s->d_kl.d, s->d_illegal.d);
+    AZH_HIP(hipGetLastError());
+    u32 missing = 0;
+    AZH_HIP(hipMemcpyAsync(kl_out, s->d_kl.d + first_ply, (size_t)n_plies * sizeof(float), hipMemcpyDeviceToHost, st));
+    AZH_HIP(hipMemcpyAsync(&missing, s->d_illegal.d, sizeof(u32), hipMemcpyDeviceToHost, st));
+    AZH_HIP(hipStreamSynchronize(st));
+    *illegal_out = (int64_t)missing;
+    return 0;
+}
+
+extern "C" int azh_samples_set_surprise_chunk(azh_samples *s, int plies)
+{
+    if (!s || plies < 0 || plies > SURPRISE_CHUNK)
+        return azh_fail(-1, "azh_samples_set_surprise_chunk: 0 .. %d plies", SURPRISE_CHUNK);
+    s->surprise_chunk = plies ? plies : SURPRISE_CHUNK;
+    return 0;
+}
+
+extern "C" int azh_samples_surprise_ms(const azh_samples *s, float *ms)
+{
+    if (!s || !ms)
+        return azh_fail(-1, "azh_samples_surprise_ms: null argument");
+    ms[0] = s->surprise_ms[0];
+    ms[1] = s->surprise_ms[1];
+    return 0;
+}
+
+namespace {
+struct SurpriseScratch {  // freed on every path out of azh_samples_surprise
+    u64 *boards = nullptr;
+    float *logits = nullptr, *values = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    ~SurpriseScratch()
+    {
+        (void)hipFree(boards);
+        (void)hipFree(logits);
+        (void)hipFree(values);
+        for (hipEvent_t e : ev)
+            if (e)
+                (void)hipEventDestroy(e);
+    }
+};
+}  // namespace
+
+extern "C" int azh_samples_surprise(azh_samples *s, azh_net *net, int dtype, int64_t first_game, int64_t n_games, float *kl_out,
+                                    int64_t *illegal_out)
+{
+    if (!s || !net || !kl_out || !illegal_out)
+        return azh_fail(-1, "azh_samples_surprise: null argument");
+    if (first_game < 0 || n_games < 1 || first_game + n_games > s->games)
+        return azh_fail(-1, "azh_samples_surprise: games [%lld, %lld) of %lld", (long long)first_game,
+                        (long long)(first_game + n_games), (long long)s->games);
+    if (int rc = reserve_surprise(s))
+        return rc;
+    const int64_t first = s->h_games[4 * first_game];
+    const int64_t end = (int64_t)s->h_games[4 * (first_game + n_games - 1)] + s->h_games[4 * (first_game + n_games - 1) + 1];
+    const int chunk = (int)std::min<int64_t>(s->surprise_chunk, end - first);
+    SurpriseScratch sc;
+    AZH_HIP(hipMalloc((void **)&sc.boards, (size_t)chunk * 2 * sizeof(u64)));
+    AZH_HIP(hipMalloc((void **)&sc.logits, (size_t)chunk * POLICY * sizeof(float)));
+    AZH_HIP(hipMalloc((void **)&sc.values, (size_t)chunk * sizeof(float)));
+    for (hipEvent_t &e : sc.ev)
+        AZH_HIP(hipEventCreate(&e));
+    hipStream_t st = s->stream;
+    AZH_HIP(hipMemsetAsync(s->d_illegal.d, 0, sizeof(u32), st));
+    s->surprise_ms[0] = s->surprise_ms[1] = 0.f;
+    // (each chunk is waited for before the next reuses the scratch and the events: the tower's time dwarfs the wait)
+    for (int64_t at = first; at < end; at += chunk) {
+        const int n = (int)std::min<int64_t>(chunk, end - at);
+        AZH_HIP(hipEventRecord(sc.ev[0], st));
+        hipLaunchKernelGGL(k_samples_pack_boards, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->view(), (u32)at, n,
+                           sc.boards);
+        AZH_HIP(hipGetLastError());
+        if (int rc = azh_net_launch(net, dtype, sc.boards, nullptr, nullptr, n, 0ULL, sc.logits, sc.values, st))
+            return rc;
+        AZH_HIP(hipEventRecord(sc.ev[1], st));
+        hipLaunchKernelGGL(k_samples_surprise, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), (u32)at, n, sc.logits,
+                           s->d_kl.d, s->d_illegal.d);
+        AZH_HIP(hipGetLastError());
+        AZH_HIP(hipEventRecord(sc.ev[2], st));
+        AZH_HIP(hipStreamSynchronize(st));
+        float tower = 0.f, kernel = 0.f;
+        AZH_HIP(hipEventElapsedTime(&tower, sc.ev[0], sc.ev[1]));
+        AZH_HIP(hipEventElapsedTime(&kernel, sc.ev[1], sc.ev[2]));
+        s->surprise_ms[0] += tower;
+        s->surprise_ms[1] += kernel;
+    }
+    u32 missing = 0;
+    AZH_HIP(hipMemcpy(kl_out, s->d_kl.d + first, (size_t)(end - first) * sizeof(float), hipMemcpyDeviceToHost));
+    AZH_HIP(hipMemcpy(&missing, s->d_illegal.d, sizeof(u32), hipMemcpyDeviceToHost));
+    *illegal_out = (int64_t)missing;
+    return 0;
+}
+
+extern "C" int azh_samples_legal(uint64_t mover, uint64_t opponent, uint16_t *index_out, int32_t *n_out)
+{
+    if (!index_out || !n_out)
+        return azh_fail(-1, "azh_samples_legal: null argument");
+    mover &= BOARD_MASK;
+    opponent &= BOARD_MASK;
+    const u64 empty = BOARD_MASK & ~(mover | opponent);
+    int n = 0;
+    for (int from = 0; from < 49; from++)  // wave_movegen's order: jumps by ascending (from, to), then clones ascending
+        if ((mover >> from) & 1ULL)
+            for (u64 to = double_jump_bb(1ULL << from) & empty; to; to &= to - 1ULL)
+                index_out[n++] = (uint16_t)policy_index((u32)from | ((u32)__builtin_ctzll(to) << 8));
+    for (u64 to = single_jump_bb(mover) & empty; to; to &= to - 1ULL) {
+        const u32 sq = (u32)__builtin_ctzll(to);
+        index_out[n++] = (uint16_t)policy_index(sq | (sq << 8));
+    }
+    *n_out = n;
+    return 0;
+}
+
+extern "C" int azh_samples_surprise_host(const float *logits833, const uint16_t *legal_index, int n_legal,
+                                         const uint16_t *target_index, const float *target_weight, int n_targets, float *kl_out,
+                                         int32_t *illegal_out)
+{
+    if (!logits833 || !kl_out || n_legal < 0 || n_targets < 0 || (n_legal && !legal_index) ||
+        (n_targets && (!target_index || !target_weight)))
+        return azh_fail(-1, "azh_samples_surprise_host: bad argument");
+    std::vector<uint8_t> legal(POLICY, 0);
+    std::vector<float> term((size_t)std::max(n_legal, n_targets) + 1);
+    float mx = -INFINITY;
+    for (int j = 0; j < n_legal; j++) {
+        if (legal_index[j] >= POLICY)
+            return azh_fail(-1, "azh_samples_surprise_host: policy index %u", (unsigned)legal_index[j]);
+        legal[legal_index[j]] = 1;
+        const float l = logits833[legal_index[j]];
+        if (l > mx)
+            mx = l;
+    }
+    for (int j = 0; j < n_legal; j++)
+        term[(size_t)j] = det_expf(logits833[legal_index[j]] - mx);
+    const float log_s = det_logf(gumbel_lane_sum(term.data(), n_legal));
+    int32_t missing = 0;
+    for (int t = 0; t < n_targets; t++) {
+        term[(size_t)t] = 0.0f;
+        if (target_index[t] >= POLICY)
+            return azh_fail(-1, "azh_samples_surprise_host: policy index %u", (unsigned)target_index[t]);
+        if (!(target_weight[t] > 0.0f))
+            continue;
+        if (legal[target_index[t]])
+            term[(size_t)t] = surprise_term(target_weight[t], (logits833[target_index[t]] - mx) - log_s);
+        else
+            missing++;
+    }
+    *kl_out = stored_surprise(gumbel_lane_sum(term.data(), n_targets));
+    if (illegal_out)
+        *illegal_out = missing;
+    return 0;
+}
+
+static void default_cum(const azh_samples *s, int64_t game, u32 *cum)  // cum: the store's whole array
+{
+    const u32 first = s->h_games[4 * game];
+    for (u32 k = 0; k < s->h_count[(size_t)game]; k++)
+        cum[first + k] = WEIGHT_ONE * (k + 1u);
+}
+
+extern "C" int azh_samples_set_ply_weights(azh_samples *s, int64_t first_game, int64_t n_games, const float *w)
+{
+    if (!s || !w)
+        return azh_fail(-1, "azh_samples_set_ply_weights: null argument");
+    if (first_game < 0 || n_games < 1 || first_game + n_games > s->games)
+        return azh_fail(-1, "azh_samples_set_ply_weights: games [%lld, %lld) of %lld", (long long)first_game,
+                        (long long)(first_game + n_games), (long long)s->games);
+    // everything is checked and built on the host first: a refused call leaves the store exactly as it was
+    std::vector<u32> cum(s->h_cum);
+    if (cum.empty()) {
+        cum.assign((size_t)s->plies, 0u);
+        for (int64_t g = 0; g < s->games; g++)
+            default_cum(s, g, cum.data());
+    }
+    const int64_t base = s->h_games[4 * first_game];
+    for (int64_t g = first_game; g < first_game + n_games; g++) {
+        const u32 first = s->h_games[4 * g], plies = s->h_games[4 * g + 1];
+        for (u32 p = 0; p < plies; p++) {
+            const float x = w[first - base + p];
+            if (!(x >= 0.0f && x <= 3.40282347e38f))
+                return azh_fail(-1, "azh_samples_set_ply_weights: game %lld, ply %u: a weight must be finite and >= 0",
+                                (long long)g, p);
+        }
+        double total = 0.0;  // (sums of integers below 2^53: exact)
+        for (u32 k = 0; k < s->h_count[(size_t)g]; k++) {
+            const double q = floor((double)w[first - base + s->h_candidates[first + k]] * 65536.0 + 0.5);
+            total = q > 4294967295.0 ? 4294967296.0 : total + q;
+            if (total > 4294967295.0)
+                return azh_fail(-1, "azh_samples_set_ply_weights: game %lld: the weights add up to more than 2^32 - 1 units "
+                                    "of 1 / 65536", (long long)g);
+            cum[first + k] = (u32)total;
+        }
+    }
+    AZH_HIP(hipDeviceSynchronize());
+    if (!s->d_cum.d)
+        if (int rc = s->d_cum.alloc((size_t)s->cap_plies))
+            return rc;
+    const hipError_t e = cum.empty() ? hipSuccess : hipMemcpy(s->d_cum.d, cum.data(), cum.size() * sizeof(u32), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (s->h_cum.empty())
+            s->d_cum.release();
+        return azh_fail(-100 - (int)e, "azh_samples_set_ply_weights: %s", hipGetErrorString(e));
+    }
+    s->h_cum.swap(cum);
+    return 0;
+}
+
+extern "C" int azh_samples_clear_ply_weights(azh_samples *s)
+{
+    if (!s)
+        return azh_fail(-1, "azh_samples_clear_ply_weights: null store");
+    AZH_HIP(hipDeviceSynchronize());
+    s->d_cum.release();
+    s->h_cum.clear();
+    return 0;
+}
+
+extern "C" int azh_samples_ply_cum(const azh_samples *s, uint16_t *candidates, uint32_t *candidate_count, uint32_t *cum,
+                                   int32_t *present)
+{
+    if (!s || !candidates || !candidate_count || !cum || !present)
+        return azh_fail(-1, "azh_samples_ply_cum: null argument");
+    if (s->plies)
+        memcpy(candidates, s->h_candidates.data(), (size_t)s->plies * sizeof(u16));
+    if (s->games)
+        memcpy(candidate_count, s->h_count.data(), (size_t)s->games * sizeof(u32));
+    *present = s->d_cum.d != nullptr;
+    if (*present) {
+        memcpy(cum, s->h_cum.data(), (size_t)s->plies * sizeof(u32));
+    } else {
+        memset(cum, 0, (size_t)s->plies * sizeof(u32));
+        for (int64_t g = 0; g < s->games; g++)
+            default_cum(s, g, cum);
+    }
     return 0;
 }

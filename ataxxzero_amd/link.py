@@ -186,6 +186,18 @@ SIGNATURES = {
     "azh_samples_draw": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64, _vp,
                                         ctypes.c_int64, _vp, _vp]),
     "azh_samples_status": (ctypes.c_int, [_vp, _P(ctypes.c_int64)]),
+    "azh_samples_surprise_logits": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _P(ctypes.c_int64),
+                                                   ctypes.c_size_t]),
+    "azh_samples_surprise": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, _vp, _P(ctypes.c_int64)]),
+    "azh_samples_set_surprise_chunk": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "azh_samples_surprise_ms": (ctypes.c_int, [_vp, _vp]),
+    "azh_samples_legal": (ctypes.c_int, [_u64, _u64, _vp, _P(_i32)]),
+    "azh_samples_surprise_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _P(_f32), _P(_i32)]),
+    "azh_samples_set_ply_weights": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp]),
+    "azh_samples_clear_ply_weights": (ctypes.c_int, [_vp]),
+    "azh_samples_ply_cum": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(_i32)]),
+    "azh_samples_draw_weighted": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64, _vp,
+                                                 ctypes.c_int64, _vp, _vp, _vp, _vp]),
     # the reference's ABI, link.py:8-32
     "launch_threads": (None, [ctypes.c_char_p, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int]),
     "get_workload": (ctypes.c_int, []),
@@ -883,6 +895,48 @@ def samples_draw(seed, step, sample, first_game, n_games, games, ply_flags):
     return tuple(int(v) for v in out)
 
 
+def samples_draw_weighted(seed, step, sample, first_game, n_games, games, ply_flags, candidates, cum):
+    """samples_draw with the weighted ply choice, from the mirrors SampleStore.mirror and SampleStore.ply_cum return
+    (azh_samples_draw_weighted; host arithmetic, no GPU needed)."""
+    games = np.ascontiguousarray(games, dtype=np.uint32).reshape(-1, 4)
+    ply_flags = np.ascontiguousarray(ply_flags, dtype=np.uint8)
+    candidates = np.ascontiguousarray(candidates, dtype=np.uint16)
+    cum = np.ascontiguousarray(cum, dtype=np.uint32)
+    if not len(candidates) == len(cum) == len(ply_flags):
+        raise ValueError("candidates and cum hold one entry per ply")
+    out = np.zeros(4, dtype=np.int32)
+    check(load().azh_samples_draw_weighted(int(seed), int(step), int(sample), int(first_game), int(n_games), _ptr(games),
+                                           len(games), _ptr(ply_flags), _ptr(candidates), _ptr(cum), _ptr(out)))
+    return tuple(int(v) for v in out)
+
+
+def samples_legal(mover, opponent):
+    """The legal moves of a position (the mover's and the opponent's stones as bitboards, no blockers) as flat policy indices
+    in the device movegen's order -> u16 array (azh_samples_legal; host arithmetic)."""
+    index, n = np.zeros(833, dtype=np.uint16), ctypes.c_int32(0)
+    check(load().azh_samples_legal(int(mover), int(opponent), _ptr(index), ctypes.byref(n)))
+    return index[:n.value].copy()
+
+
+def samples_surprise_host(logits, legal_index, target_index, target_weight):
+    """One ply's policy surprise KL(target || softmax of the logits over the legal moves) as the store's kernel computes and
+    stores it -> (f32 KL, targets with a positive weight that are not legal) (azh_samples_surprise_host; host arithmetic)."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32).ravel()
+    if logits.size != 833:
+        raise ValueError("833 logits")
+    legal_index = np.ascontiguousarray(legal_index, dtype=np.uint16)
+    target_index = np.ascontiguousarray(target_index, dtype=np.uint16)
+    target_weight = np.ascontiguousarray(target_weight, dtype=np.float32)
+    if len(target_index) != len(target_weight):
+        raise ValueError("one weight per target")
+    kl, illegal = ctypes.c_float(0.0), ctypes.c_int32(0)
+    check(load().azh_samples_surprise_host(_ptr(logits), _ptr(legal_index) if len(legal_index) else None, len(legal_index),
+                                           _ptr(target_index) if len(target_index) else None,
+                                           _ptr(target_weight) if len(target_weight) else None, len(target_index),
+                                           ctypes.byref(kl), ctypes.byref(illegal)))
+    return np.float32(kl.value), int(illegal.value)
+
+
 def hip_runtimes():
     """The HIP runtime libraries mapped into this process (paths).  torch ships its own: imported BEFORE this package's
     library is loaded, both resolve to that one copy (same soname) and share streams and memory; loaded after it, the
@@ -1008,6 +1062,69 @@ class SampleStore:
         """What draw_gather draws for one sample, from the host mirror (samples_draw)."""
         games, flags = self.mirror()
         return samples_draw(seed, step, sample, first_game, n_games, games, flags)
+
+    # policy surprise weighting (DESIGN.md, "Policy surprise weighting")
+
+    def _game_plies(self, first_game, n_games):
+        games, _ = self.mirror()
+        if not (0 <= first_game and 1 <= n_games and first_game + n_games <= len(games)):
+            raise ValueError("games [%d, %d) of %d" % (first_game, first_game + n_games, len(games)))
+        return int(games[first_game + n_games - 1][0]) + int(games[first_game + n_games - 1][1]) - int(games[first_game][0])
+
+    def surprise(self, net, dtype, first_game, n_games, chunk=0):
+        """KL(policy target || the prior of `net`, a link.Net, in `dtype`) of every ply of games [first_game, first_game +
+        n_games) -> (f32 array, one per ply; targets that are no legal moves: 0 for games the engine wrote).  chunk: plies
+        per tower launch (0: 16384)."""
+        kl, illegal = np.zeros(self._game_plies(first_game, n_games), dtype=np.float32), ctypes.c_int64(0)
+        check(load().azh_samples_set_surprise_chunk(self.h, int(chunk)))
+        check(load().azh_samples_surprise(self.h, net.h, int(dtype), int(first_game), int(n_games), _ptr(kl),
+                                          ctypes.byref(illegal)))
+        return kl, int(illegal.value)
+
+    def surprise_ms(self):
+        """HIP-event milliseconds of the last surprise(): (board packing and tower, surprise kernel)."""
+        ms = np.zeros(2, dtype=np.float32)
+        check(load().azh_samples_surprise_ms(self.h, _ptr(ms)))
+        return float(ms[0]), float(ms[1])
+
+    def surprise_from_logits(self, first_ply, logits):
+        """The same for plies [first_ply, first_ply + n) from an (n, 833) float32 GPU tensor of logits, enqueued on torch's
+        current stream."""
+        import torch
+        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == 833 and
+                logits.is_contiguous() and len(logits) >= 1):
+            raise ValueError("logits must be a contiguous float32 GPU tensor of shape (n, 833)")
+        kl, illegal = np.zeros(len(logits), dtype=np.float32), ctypes.c_int64(0)
+        check(load().azh_samples_surprise_logits(self.h, int(first_ply), len(logits), ctypes.c_void_p(logits.data_ptr()),
+                                                 _ptr(kl), ctypes.byref(illegal),
+                                                 torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY))
+        return kl, int(illegal.value)
+
+    def set_ply_weights(self, first_game, n_games, weights):
+        """One weight >= 0 per ply of games [first_game, first_game + n_games): draw_gather then picks a game's ply in
+        proportion to its candidates' weights (kept in units of 1 / 65536).  A refused call changes nothing."""
+        w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+        if len(w) != self._game_plies(first_game, n_games):
+            raise ValueError("one weight per ply of the games")
+        check(load().azh_samples_set_ply_weights(self.h, int(first_game), int(n_games), _ptr(w)))
+
+    def clear_ply_weights(self):
+        check(load().azh_samples_clear_ply_weights(self.h))
+
+    def ply_cum(self):
+        """-> (candidates (P,) u16, candidate_count (G,) u32, cum (P,) u32, weights held?): the mirror of the weighted draw;
+        cum[first ply + k] is the running sum of the weights of the game's candidates 0 .. k."""
+        c = self.counts()
+        cand, count = np.zeros(max(c["plies"], 1), np.uint16), np.zeros(max(c["games"], 1), np.uint32)
+        cum, present = np.zeros(max(c["plies"], 1), np.uint32), ctypes.c_int32(0)
+        check(load().azh_samples_ply_cum(self.h, _ptr(cand), _ptr(count), _ptr(cum), ctypes.byref(present)))
+        return cand[:c["plies"]], count[:c["games"]], cum[:c["plies"]], bool(present.value)
+
+    def draw_weighted(self, seed, step, sample, first_game, n_games):
+        """What draw_gather draws for one sample while weights are held, from the host mirrors (samples_draw_weighted)."""
+        games, flags = self.mirror()
+        cand, _, cum, _ = self.ply_cum()
+        return samples_draw_weighted(seed, step, sample, first_game, n_games, games, flags, cand, cum)
 
     def status(self):
         """Samples of draw_gather that found no drawable ply in 64 attempts (written as zeros) since the store was made;

@@ -352,6 +352,52 @@ def _fill_store(entries, log):
     return store
 
 
+def surprise_weights(kl, games, candidate_lists, lam):
+    """Policy surprise weighting (Wu 2019, section 3.3) -> one float64 weight per ply.  kl: the surprise of every ply of the
+    games; games: rows (first ply, plies, ...) with the first ply counted from kl[0]; candidate_lists: per game the plies a
+    sample may be drawn from.  A game with n candidates spreads the mass n over them, (1 - lam) of it uniformly and lam in
+    proportion to the surprise: w_i = (1 - lam) + lam * n * KL_i / sum KL; every w_i = 1 where the sum is 0; 0 elsewhere."""
+    kl = np.asarray(kl, dtype=np.float64)
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("the surprise weight must lie in [0, 1]")
+    w = np.zeros(len(kl), dtype=np.float64)
+    for row, cand in zip(games, candidate_lists):
+        at = int(row[0]) + np.asarray(cand, dtype=np.int64)
+        if not len(at):
+            continue
+        total = kl[at].sum()
+        w[at] = (1.0 - lam) + lam * len(at) * kl[at] / total if total > 0.0 else 1.0
+    return w
+
+
+def _apply_surprise(store, old_path, lam, dtype, n_test, log):
+    """One surprise pass over the training games [n_test, games) against the net at old_path, then the ply weights."""
+    import time
+    from . import link
+    cw, bnp = model.load_model(old_path)
+    net = link.Net(cw, bnp)
+    games, _ = store.mirror()
+    count = len(games) - n_test
+    t0 = time.time()
+    kl, illegal = store.surprise(net, link.DTYPES[dtype], n_test, count)
+    seconds = time.time() - t0
+    net.close()
+    cand, counts, _, _ = store.ply_cum()
+    rows = games[n_test:].astype(np.int64)
+    lists = [cand[int(r[0]):int(r[0]) + int(c)] for r, c in zip(rows, counts[n_test:])]
+    rows[:, 0] -= rows[0, 0]
+    w = surprise_weights(kl, rows, lists, lam)
+    picked = np.concatenate([r[0] + np.asarray(c, dtype=np.int64) for r, c in zip(rows, lists)])
+    share = max((float(w[r[0] + np.asarray(c, dtype=np.int64)].max()) / len(c) for r, c in zip(rows, lists) if len(c)),
+                default=0.0)
+    k = kl[picked] if len(picked) else np.zeros(1)
+    log("Policy surprise: %i games, %i plies in %.2f s against %s (%s); KL mean %.4f, median %.4f, max %.4f; the largest share "
+        "one ply holds of its game: %.3f; %i targets that are no legal moves."
+        % (count, len(kl), seconds, old_path, dtype, float(k.mean()), float(np.median(k)), float(k.max()), share, illegal))
+    store.set_ply_weights(n_test, count, w)
+
+
 # ---------------------------------------------------------------- the network (model.py:38-101)
 
 class Network(nn.Module):
@@ -429,10 +475,20 @@ def losses(net, features, policies, values):
 
 
 def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learning_rate=0.001, blocks=12, filters=128,
-          reference_bn_affine=False, device=None, log=print, value_blend=0.0, device_samples=False, device_draws=False):
+          reference_bn_affine=False, device=None, log=print, value_blend=0.0, device_samples=False, device_draws=False,
+          surprise_weight=0.0, surprise_dtype="bf16"):
     """device_samples: the entries are put into a link.SampleStore once and every minibatch is written by its kernel into
     tensors allocated once (make_minibatch_device) — the same minibatches as without it, no per-step host-to-device copy of
-    the batch; device_draws (implies device_samples): the kernel also draws the samples.  Both need a GPU."""
+    the batch; device_draws (implies device_samples): the kernel also draws the samples.  Both need a GPU.
+    surprise_weight L > 0 (implies device_draws, needs old_path): a training game's plies are drawn in proportion to
+    (1 - L) + L n KL_i / sum KL, KL_i the surprise of ply i's policy target to the net at old_path evaluated in surprise_dtype
+    (surprise_weights); the validation games stay uniform."""
+    if surprise_weight != 0.0:
+        if not 0.0 < surprise_weight <= 1.0:
+            raise ValueError("--surprise-weight must lie in [0, 1]")
+        if old_path is None:
+            raise ValueError("--surprise-weight needs --old-path: the surprise is measured against that network")
+        device_samples = device_draws = True
     random.seed(123456789)                                                # train.py:103
     entries = load_entries(games_paths)
     ply_count = sum(len(e["moves"]) for e in entries)
@@ -463,6 +519,8 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
         if len(entries) <= n_test:
             raise ValueError("device samples need more than %d games" % n_test)
         train_out = link_outputs(store, minibatch_size, device)
+        if surprise_weight > 0.0:
+            _apply_surprise(store, old_path, surprise_weight, surprise_dtype, n_test, log)
 
         def next_batch(step):
             return make_minibatch_device(store, n_test, len(entries) - n_test, minibatch_size, value_blend, train_out, draws,

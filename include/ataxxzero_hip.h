@@ -753,6 +753,66 @@ int azh_samples_draw(uint64_t seed, uint32_t step, uint32_t sample, int64_t firs
 /* Waits for the device and returns how many samples of azh_samples_draw_gather have failed since the store was created. */
 int azh_samples_status(azh_samples *s, int64_t *failed);
 
+/* ------------------------------------------------------------------ policy surprise weighting
+ * (an extension of the store; with none of these called, every launch and every draw above is what it was.)
+ *
+ * The SURPRISE of a stored ply is KL(target || prior), the prior being a net's policy for the mover's view of the stored
+ * position (the mover is 1 + ply % 2; the boards go to the tower as (mover, opponent), the orientation the engine feeds it).
+ * With l the net's 833 f32 logits, `legal` the position's moves in the device movegen's order (jumps by ascending
+ * (from, to), then clones ascending; no blockers) mapped by the engine's move -> policy index map:
+ *   mx = max of l over legal;  S = sum over legal of det_expf(l_j - mx);  log p_t = (l_t - mx) - det_logf(S);
+ *   KL = sum over the ply's targets with weight w_t > 0 and t legal of  w_t * (det_logf(w_t) - log p_t).
+ * Everything is f32, every operation a single IEEE one.  BOTH sums run in the engine's 64-lane order: term j (the j-th legal
+ * move; the j-th target of the ply in stored order, a skipped target being a term of +0) is added, from +0, into lane j % 64
+ * in ascending j, then the lanes are folded by the xor butterfly with offsets 1, 2, 4, 8, 16, 32.  The maximum starts at
+ * -inf and a NaN never replaces it.  A result that is negative, NaN or infinite is stored as 0; a pass or a bad ply has KL 0.
+ * A target with w_t > 0 whose index is not legal adds nothing and is counted (0 for games the engine wrote).
+ *
+ * azh_samples_surprise_logits: the surprise of plies [first_ply, first_ply + n_plies) (counted from the store's first ply) from
+ * a DEVICE array of logits [n_plies][833], enqueued on `stream` (0: the store's own) and waited for; kl_out [n_plies] on the
+ * host; *illegal_out the count above.  The values also stay in a device array the store owns, one f32 per ply. */
+int azh_samples_surprise_logits(azh_samples *s, int64_t first_ply, int64_t n_plies, const float *d_logits, float *kl_out,
+                                int64_t *illegal_out, uintptr_t stream);
+/* The same for every ply of games [first_game, first_game + n_games), the logits coming from `net` in `dtype`: in chunks of
+ * at most 16384 plies (azh_samples_set_surprise_chunk: another size, for tests; 0 restores the default) a small kernel packs
+ * the boards, the tower runs, and the surprise kernel runs behind it on the store's stream.  kl_out: one f32 per ply of those
+ * games. */
+int azh_samples_surprise(azh_samples *s, azh_net *net, int dtype, int64_t first_game, int64_t n_games, float *kl_out,
+                         int64_t *illegal_out);
+int azh_samples_set_surprise_chunk(azh_samples *s, int plies);
+/* ms [2]: HIP-event milliseconds of the last azh_samples_surprise, summed over its chunks: {board packing and tower,
+ * surprise kernel}. */
+int azh_samples_surprise_ms(const azh_samples *s, float *ms);
+/* The legal moves of a position as policy indices in the order above -> index_out [up to 833], *n_out.  Host arithmetic. */
+int azh_samples_legal(uint64_t mover, uint64_t opponent, uint16_t *index_out, int32_t *n_out);
+/* One ply's surprise restated on the host: *kl_out is the stored value (the "stored as 0" rule applied), *illegal_out (or
+ * NULL) this ply's count.  Host arithmetic only. */
+int azh_samples_surprise_host(const float *logits833, const uint16_t *legal_index, int n_legal, const uint16_t *target_index,
+                              const float *target_weight, int n_targets, float *kl_out, int32_t *illegal_out);
+
+/* Weighted ply draws.  w [plies of games first_game .. first_game + n_games): one weight per ply, finite and >= 0.  Per
+ * CANDIDATE ply the store keeps q = (u32)floor((double)w * 65536 + 0.5) as a running sum per game, cum[first ply + k] = q_0 +
+ * ... + q_k over the game's candidates 0 .. k (a u32 beside the candidates array); the weights of other plies are checked and
+ * otherwise unused.  -1, with nothing changed, for a weight that is NaN, infinite or negative, or a game whose total
+ * exceeds 2^32 - 1.  Games never given weights, and games added later, have q = 65536 on every candidate.
+ * With weights present an attempt of azh_samples_draw_gather picks its ply as
+ *   total = the game's last cum; total == 0 fails the attempt (also for a game with random_ply);
+ *   R = ((u64)v[1] * total) >> 32;  ply = the candidate at the first k with cum[k] > R (binary search, at most 16 steps);
+ * everything else — game, random_ply + 1, the rejections, symmetry, the 64 attempts, the Philox counters — is unchanged.  With
+ * every q = 65536 this is the uniform draw exactly: floor(floor(v c 2^16 / 2^32) / 2^16) = floor(v c / 2^32).
+ * Neither call may run while a draw is in flight: both wait for the device first.
+ * azh_samples_clear_ply_weights frees the array; the draw is again the one above. */
+int azh_samples_set_ply_weights(azh_samples *s, int64_t first_game, int64_t n_games, const float *w);
+int azh_samples_clear_ply_weights(azh_samples *s);
+/* The draw's mirror: candidates [plies] (the k-th candidate of game g at [first ply + k]), candidate_count [games], cum
+ * [plies] (valid below each game's count; 65536 (k + 1) throughout when the store holds no weights), *present: 1 when it
+ * does. */
+int azh_samples_ply_cum(const azh_samples *s, uint16_t *candidates, uint32_t *candidate_count, uint32_t *cum, int32_t *present);
+/* azh_samples_draw with the weighted ply choice, from mirror arrays.  Host arithmetic only: no device, no store. */
+int azh_samples_draw_weighted(uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
+                              const uint32_t *games, int64_t total_games, const uint8_t *ply_flags,
+                              const uint16_t *candidates, const uint32_t *cum, int32_t *out);
+
 /* ------------------------------------------------------------------ reference ABI
  * The four symbols link.py:6-32 binds (cpp/self_play_client.cpp:683-749), with
  * the worker threads replaced by GPU game slots: `thread_count` concurrent

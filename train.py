@@ -9,6 +9,8 @@ without the key are sampled exactly as the reference does).  Entries written wit
 carry "values", the search's own value at every ply: --value-blend L trains the value head on (1 - L) z + L values[ply]
 instead of the game result z alone.  --device-samples keeps the games in device memory and lets a HIP kernel write every
 minibatch into the trainer's tensors (the same minibatches; needs a GPU); --device-draws also draws the samples there.
+--surprise-weight L draws a training game's plies by policy surprise, KL(policy target || prior of the --old-path network):
+a share L of each game's sampling mass in proportion to it, the rest uniformly (implies --device-draws).
 """
 from ataxxzero_amd import training
 from ataxxzero_amd.cli import flag, parse, switch
@@ -29,11 +31,26 @@ OPTIONS = [
                                "minibatches, no per-step host work on the batch (extension; needs a GPU)"),
     switch("--device-draws", "with --device-samples (implied): the kernel also draws the samples, with Philox keyed by "
                              "123456789, instead of Python's random (extension)"),
+    flag("--surprise-weight", "share L in [0, 1] of a game's sampling mass spread over its plies in proportion to the policy "
+                              "surprise KL(target || prior of the --old-path network), the rest uniformly (extension; implies "
+                              "--device-draws, needs --old-path; 0: off; KataGo uses 0.5)", type=float, default=0.0,
+         metavar="L"),
+    flag("--surprise-dtype", "tower precision of the surprise pass", default="bf16", choices=["f32", "bf16", "f16"],
+         metavar="DTYPE"),
 ]
 
 if __name__ == "__main__":
     args = parse(__doc__.splitlines()[0], OPTIONS)
+    surprise = {}
+    if args.surprise_weight != 0.0:
+        if not 0.0 < args.surprise_weight <= 1.0 or args.old_path is None:
+            raise SystemExit("train.py: --surprise-weight takes L in [0, 1] and needs --old-path, the network the surprise "
+                             "is measured against")
+        surprise = {"surprise_weight": args.surprise_weight, "surprise_dtype": args.surprise_dtype}
+        args.device_draws = True
+    else:                                   # off: the run, and the line below, are those of a train.py without the flags
+        del args.surprise_weight, args.surprise_dtype
     print("Arguments:", args)
     training.train(args.games, args.old_path, args.new_path, steps=args.steps, minibatch_size=args.minibatch_size,
                    learning_rate=args.learning_rate, reference_bn_affine=args.reference_bn_affine, value_blend=args.value_blend,
-                   device_samples=args.device_samples or args.device_draws, device_draws=args.device_draws)
+                   device_samples=args.device_samples or args.device_draws, device_draws=args.device_draws, **surprise)
