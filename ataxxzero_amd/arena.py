@@ -2,7 +2,8 @@
 
 Restates what uai_ringmaster.py does with two `uai_interface.py --network-path X --visits V`
 engine subprocesses (uai_ringmaster.py:75-160,198-265), as one device-resident batch:
-  * no-blocker start (ataxx_rules.py:44-50), engine 1 ("white") moves first
+  * no-blocker start (ataxx_rules.py:44-50) unless another start position is given (`start_fen`, walls included: the
+    engine, its two nets' blocker plane and the random openings then play on that board), engine 1 ("white") moves first
   * each side searches exactly `visits` MCTS steps per move from a fresh tree (the
     per-ply `moves` message makes engine.set_state rebuild it, engine.py:452-472), no
     Dirichlet noise, python posterior and tie-break (engine.py:197-203,291)
@@ -19,13 +20,13 @@ import json
 from . import link, model, selfplay
 
 
-def random_openings(pairs, depth, seed):
+def random_openings(pairs, depth, seed, fen=selfplay.START_FEN_PLAIN):
     """`pairs` openings of `depth` uniformly random plies from the start position — uai_ringmaster.get_opening
     (uai_ringmaster.py:185-196: OPENING_DEPTH random.choice(board.legal_moves()) moves; the constant is 0 in the reference's
     file and is edited there) — played by the HIP playout kernel.  -> (positions (pairs, 2) u64 packed x | turn << 63, o;
     moves: per pairing the list of UAI strings).  Games that end inside the opening are not used."""
     import numpy as np
-    x, o, bl, turn = selfplay.parse_fen(selfplay.START_FEN_PLAIN)
+    x, o, bl, turn = selfplay.parse_fen(fen)
     boards, moves = [], []
     batch = 0
     while len(boards) < pairs:
@@ -54,7 +55,7 @@ def uai_move(mv):
 
 class Match:
     def __init__(self, weights_a, weights_b, visits, games=1024, dtype="f16", seed=selfplay.DEFAULT_SEED,
-                 max_plies=400, opening_depth=0):
+                 max_plies=400, opening_depth=0, start_fen=selfplay.START_FEN_PLAIN):
         if games % 2:
             raise ValueError("the number of concurrent games must be even (each pairing is played both ways)")
         if not 0 <= opening_depth < max_plies:
@@ -62,7 +63,7 @@ class Match:
         self.net_a = link.Net(*weights_a, model.BN_EPSILON)
         self.net_b = link.Net(*weights_b, model.BN_EPSILON)
         self.dtype = link.DTYPES[dtype]
-        cfg = selfplay.make_config(games, visits, seed=seed, fen=selfplay.START_FEN_PLAIN, max_plies=max_plies,
+        cfg = selfplay.make_config(games, visits, seed=seed, fen=start_fen, max_plies=max_plies,
                                    dirichlet_weight=0.0, flags=link.FLAG_ARENA)
         self.engine = link.Engine(cfg)
         self.games = games
@@ -77,7 +78,7 @@ class Match:
             # start from the same position.  Only the FIRST game of a slot starts from it (uid < games): a match from
             # openings is a cohort of at most `games` games.
             import numpy as np
-            boards, self.openings = random_openings(games // 2, opening_depth, seed)
+            boards, self.openings = random_openings(games // 2, opening_depth, seed, start_fen)
             self.opening_boards = boards
             self.engine.set_positions(np.repeat(boards, 2, axis=0), np.full(games, opening_depth, dtype=np.int32))
 

@@ -1344,6 +1344,7 @@ using namespace azh;
 // ------------------------------------------------------------------ host
 
 std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_ids);  // json.cpp
+std::string azh_format_game_json_blockers(const uint32_t *rec, size_t words, bool with_ids, uint64_t blockers);  // json.cpp
 bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plies, const char **why);
 
 // The leaf buffers of EngineParams as one value.  The engine keeps two sets, its own G-slot one and the G K-slot one of the
@@ -1396,6 +1397,7 @@ struct azh_engine {
     // uid-ordered emission: finished games wait here until every game with a smaller uid has been handed out or
     // is known to have been dropped ("" = dropped)
     bool emit_by_uid = false;
+    bool record_blockers = false;  // every line gains "blockers", the engine's mask (azh_engine_set_record_blockers)
     std::map<uint32_t, std::string> held;
     uint32_t next_uid = 0;
     bool order_broken = false;  // records were lost (ring overflow): some uid will never come, see azh_engine_drain_json
@@ -2437,6 +2439,14 @@ extern "C" int azh_engine_set_game_limit(azh_engine *e, int64_t games)
 // consumer that stops reading after N lines (looper.py:51-64 kills the generator at --game-count lines) gets a
 // length-biased sample in finish order; in uid order the first N lines are the first N games started, whatever
 // their length.
+extern "C" int azh_engine_set_record_blockers(azh_engine *e, int on)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_set_record_blockers: null engine");
+    e->record_blockers = on != 0;  // (read when fetched records are formatted: takes effect from the next fetch on)
+    return 0;
+}
+
 extern "C" int azh_engine_set_emit_order(azh_engine *e, int by_uid)
 {
     if (!e)
@@ -2763,7 +2773,9 @@ static void format_staged(azh_engine *e)
     for (auto &o : order) {
         const uint32_t *rec = host.data() + o.second;
         const bool dropped = (rec[7] & 3u) == 1;
-        std::string line = dropped ? std::string() : azh_format_game_json(rec, rec[5], ids);
+        std::string line = dropped                ? std::string()
+                           : e->record_blockers ? azh_format_game_json_blockers(rec, rec[5], ids, e->P.blockers & BOARD_MASK)
+                                                : azh_format_game_json(rec, rec[5], ids);
         if ((rec[7] & 3u) == 2 && !ids)
             line.clear();  // a game that began at a loaded position: record drained and formatted like any other
                            // (the measured path does the same work per finished ply), but it is not a whole game.

@@ -4,6 +4,7 @@
 //   {"boards":[[49 ints]...],"dists":[{"a7c6":0.0025,...}...],"moves":["b7",...],"result":1}
 // boards: index x + 7*y with y = 0 at rank 7, 1 = x, 2 = o, blockers written as 0
 // (serialize_board_for_json :88-107); dists: expanded root edges -> visits / total.
+// On request one more key leads the object, "blockers":[cells]: azh_format_game_json_blockers.
 #include <algorithm>
 #include <charconv>
 #include <cmath>
@@ -289,6 +290,26 @@ std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_id
     return out;
 }
 
+// The same line with one more key in front, "blockers":[...]: the wall cells of `blockers` (bit = file + 7 * rank) in ascending
+// order of the index the line's boards use, x + 7 * y with y = 0 at rank 7.  "blockers" sorts before "boards", so the key
+// leads the object as nlohmann's sorted keys would have it; taking its bytes out gives azh_format_game_json's line.
+std::string azh_format_game_json_blockers(const uint32_t *rec, size_t words, bool with_ids, uint64_t blockers)
+{
+    std::string key = "\"blockers\":[";
+    bool first = true;
+    for (int cell = 0; cell < 49; cell++)
+        if ((blockers >> (cell % 7 + 7 * (6 - cell / 7))) & 1ULL) {
+            if (!first)
+                key += ',';
+            key += std::to_string(cell);
+            first = false;
+        }
+    key += "],";
+    std::string line = azh_format_game_json(rec, words, with_ids);
+    line.insert(1, key);
+    return line;
+}
+
 // Is what starts at `rec` (at most `avail` words of it readable) a whole, well-formed record?  The ply structure must
 // walk to the record's end exactly.  Used by azh_format_record_json and by the engine's drain when it looks for the next
 // header after a damaged record: a payload word may equal the magic (board halves are arbitrary bit patterns), and only a
@@ -322,29 +343,45 @@ bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plie
 
 // One record -> its line, for callers that hold records themselves and for the CPU-side test of the format: host code only,
 // no device is touched.
-extern "C" int azh_format_record_json(const uint32_t *rec, int64_t words, int32_t with_ids, char *buf, int64_t cap,
-                                      int64_t *used)
+static int format_record(const char *who, const uint32_t *rec, int64_t words, int32_t with_ids, bool keyed, uint64_t blockers,
+                         char *buf, int64_t cap, int64_t *used)
 {
     if (!rec || !buf || !used)
-        return azh_fail(-1, "azh_format_record_json: null argument");
+        return azh_fail(-1, "%s: null argument", who);
     *used = 0;
     const char *why = nullptr;
     if (words < 8 || !azh_record_well_formed(rec, (size_t)words, 0u, &why))
-        return azh_fail(-2, "azh_format_record_json: %s (%lld words handed over, header says %u words, %u plies)",
+        return azh_fail(-2, "%s: %s (%lld words handed over, header says %u words, %u plies)", who,
                         why ? why : "not a finished-game record", (long long)words, words >= 8 ? rec[5] : 0u,
                         words >= 8 ? rec[3] : 0u);
     if (rec[7] == 1)
-        return azh_fail(-2, "azh_format_record_json: the record is the marker of a dropped game, it has no line");
+        return azh_fail(-2, "%s: the record is the marker of a dropped game, it has no line", who);
     // The kind bits this entry point has always taken are 2 .. 32; bit 6 (64: a game of the Gumbel root search, whose counts
     // are policy weights, not visits) is accepted by the engine's own drain alone — tests/test_resign_host.py pins 64 among
     // the kind bits a caller's record must not carry.
     if (rec[7] & 64u)
-        return azh_fail(-2, "azh_format_record_json: kind bit 64 (a game of the Gumbel root search) is formatted by "
-                            "azh_engine_drain_json only");
-    const std::string line = azh_format_game_json(rec, rec[5], with_ids != 0);
+        return azh_fail(-2, "%s: kind bit 64 (a game of the Gumbel root search) is formatted by "
+                            "azh_engine_drain_json only", who);
+    const std::string line = keyed ? azh_format_game_json_blockers(rec, rec[5], with_ids != 0, blockers)
+                                   : azh_format_game_json(rec, rec[5], with_ids != 0);
     *used = (int64_t)line.size();
     if ((int64_t)line.size() > cap)
-        return azh_fail(-6, "azh_format_record_json: the line needs %zu bytes, the buffer has %lld", line.size(), (long long)cap);
+        return azh_fail(-6, "%s: the line needs %zu bytes, the buffer has %lld", who, line.size(), (long long)cap);
     memcpy(buf, line.data(), line.size());
     return 0;
+}
+
+extern "C" int azh_format_record_json(const uint32_t *rec, int64_t words, int32_t with_ids, char *buf, int64_t cap,
+                                      int64_t *used)
+{
+    return format_record("azh_format_record_json", rec, words, with_ids, false, 0ULL, buf, cap, used);
+}
+
+extern "C" int azh_format_record_json_blockers(const uint32_t *rec, int64_t words, int32_t with_ids, uint64_t blockers,
+                                               char *buf, int64_t cap, int64_t *used)
+{
+    if (blockers >> 49)
+        return azh_fail(-1, "azh_format_record_json_blockers: the mask %#llx has bits beyond the 49 cells",
+                        (unsigned long long)blockers);
+    return format_record("azh_format_record_json_blockers", rec, words, with_ids, true, blockers, buf, cap, used);
 }

@@ -1,7 +1,8 @@
 // Device-resident training samples (azh_samples_*; include/ataxxzero_hip.h, DESIGN.md "Device-resident samples"): finished
 // games kept in HBM as bitboards and sparse policy targets, and one kernel that writes a minibatch — features [n][7][7][4],
 // policy [n][7][7][17], value [n][1], f32 — straight into the trainer's tensors, bit for bit what
-// training.make_minibatch_reference builds on the host (train.py:43-77 of the reference).
+// training.make_minibatch_reference builds on the host (train.py:43-77 of the reference).  A game may carry a wall mask
+// (DESIGN.md "Walls through the loop"): plane 3 of its samples shows it, and the surprise pass generates moves around it.
 //
 // Compiled with -ffp-contract=off: the value target's blend is three IEEE double operations in Python's order.
 #include <algorithm>
@@ -40,6 +41,7 @@ struct View {  // what the kernels read
     const u16 *target_index;
     const float *target_weight;
     const u32 *cum;  // null: uniform ply draws; else [first ply + k]: the running sum of the game's candidate weights
+    const u64 *blockers;  // null: no stored game has walls; else [game]: its wall mask, bit = file + 7 * rank
 };
 
 // One wave builds sample `i` in LDS and writes it out with coalesced stores; g < 0: the sample is all zeros.
@@ -53,13 +55,14 @@ __device__ void emit_sample(const View &v, float *lds, int i, int g, int p, int 
     if (g >= 0) {
         const uint4 game = v.games[g];
         const Ply ply = v.plies[game.x + (u32)p];
+        const u64 walls = v.blockers ? v.blockers[g] : 0ULL;  // (wave-uniform)
         const int mover = 1 + (p & 1);  // x (1) moves on even plies
         const u64 mine = mover == 1 ? ply.x : ply.o, theirs = mover == 1 ? ply.o : ply.x;
         if (lane < 49) {  // cell [X][Y] of the image shows the cell its source was
             const int X = lane / 7, Y = lane - 7 * X;
             const int src = symmetry_source_cell(s, X + 7 * (6 - Y));
             reinterpret_cast<float4 *>(lds)[lane] =
-                make_float4(1.f, (float)((mine >> src) & 1ULL), (float)((theirs >> src) & 1ULL), 0.f);
+                make_float4(1.f, (float)((mine >> src) & 1ULL), (float)((theirs >> src) & 1ULL), (float)((walls >> src) & 1ULL));
         }
         const u32 count = ply.targets_flags >> 8;
         for (u32 t = (u32)lane; t < count; t += WAVE) {
@@ -192,8 +195,9 @@ __global__ __launch_bounds__(256) void k_samples_pack_boards(View v, u32 first, 
 // One wave per ply: movegen into LDS, the legal moves marked in an 833-cell map and their logits reduced to (mx, S) in the
 // engine's lane order (apply_priors: move j in lane j % 64, ascending j, then the butterfly), then the targets 64 per step.
 // logits: row i belongs to ply first + i.  A position has at most 49 * 16 jumps and 49 clones: the move list holds them all.
+// blockers: the wall mask of the game(s) the plies belong to — one per launch: the host cuts its launches at mask changes.
 __global__ __launch_bounds__(WAVE) void k_samples_surprise(View v, u32 first, int n, const float *__restrict__ logits,
-                                                           float *__restrict__ kl_out, u32 *illegal)
+                                                           float *__restrict__ kl_out, u32 *illegal, u64 blockers)
 {
     __shared__ u16 moves[POLICY + 3];
     __shared__ u32 legal[(POLICY + 31) / 32];
@@ -211,7 +215,7 @@ __global__ __launch_bounds__(WAVE) void k_samples_surprise(View v, u32 first, in
         b.x = ply.x;
         b.o = ply.o;
         b.turn = (flags & PLY_ODD) ? 1 : 0;
-        const int M = wave_movegen(b, 0ULL, moves, nullptr);
+        const int M = wave_movegen(b, blockers, moves, nullptr);
         __syncthreads();
         const float *row = logits + (size_t)i * POLICY;
         float mx = -INFINITY;
@@ -312,6 +316,8 @@ struct azh_samples {
     DeviceArray<u16> d_target_index;
     DeviceArray<float> d_target_weight;
     DeviceArray<u32> d_errors;
+    DeviceArray<u64> d_blockers;      // [cap_games]: null until the first game with walls arrives
+    std::vector<u64> h_blockers;      // [games]
     // policy surprise weighting: all null until asked for
     DeviceArray<u32> d_cum;      // [cap_plies] beside d_candidates (azh_samples_set_ply_weights)
     DeviceArray<float> d_kl;     // [cap_plies]: the last surprise of every ply
@@ -335,7 +341,8 @@ struct azh_samples {
 
     View view() const
     {
-        return View{d_games.d, d_plies.d, d_candidates.d, d_candidate_count.d, d_target_index.d, d_target_weight.d, d_cum.d};
+        return View{d_games.d, d_plies.d, d_candidates.d, d_candidate_count.d, d_target_index.d, d_target_weight.d, d_cum.d,
+                    d_blockers.d};
     }
 };
 
@@ -384,6 +391,7 @@ extern "C" void azh_samples_destroy(azh_samples *s)
     s->d_target_index.release();
     s->d_target_weight.release();
     s->d_errors.release();
+    s->d_blockers.release();
     s->d_cum.release();
     s->d_kl.release();
     s->d_illegal.release();
@@ -431,6 +439,29 @@ extern "C" int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint
                                      const uint64_t *boards, const uint8_t *ply_flags, const double *values,
                                      const int32_t *target_start, const uint16_t *target_index, const float *target_weight)
 {
+    return azh_samples_add_games_blockers(s, n_games, games, n_plies, boards, ply_flags, values, target_start, target_index,
+                                          target_weight, nullptr);
+}
+
+// A wall mask with bits beyond the 49 cells, or a stone of plies [0, n) on a wall cell: why, or null.
+static const char *walls_refusal(uint64_t mask, const uint64_t *boards, int64_t n, int64_t *ply)
+{
+    *ply = -1;
+    if (mask & ~BOARD_MASK)
+        return "the blockers mask has bits beyond the 49 cells";
+    for (int64_t q = 0; q < n; q++)
+        if ((boards[2 * q] | boards[2 * q + 1]) & mask) {
+            *ply = q;
+            return "a stone stands on a wall cell";
+        }
+    return nullptr;
+}
+
+extern "C" int azh_samples_add_games_blockers(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies,
+                                              const uint64_t *boards, const uint8_t *ply_flags, const double *values,
+                                              const int32_t *target_start, const uint16_t *target_index,
+                                              const float *target_weight, const uint64_t *game_blockers)
+{
     if (!s || n_games < 0 || n_plies < 0 || (n_games && !games) ||
         (n_plies && (!boards || !ply_flags || !values)) || !target_start)
         return azh_fail(-1, "azh_samples_add_games: null argument");
@@ -444,6 +475,7 @@ extern "C" int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint
     std::vector<u16> p_candidates((size_t)n_plies);
     std::vector<uint8_t> p_flags((size_t)n_plies);
     int64_t at = 0, bad = 0;
+    bool walled = false;
     for (int64_t g = 0; g < n_games; g++) {
         const uint32_t *w = games + 4 * g;
         const uint32_t result = w[2] & 0xFFu;
@@ -471,6 +503,13 @@ extern "C" int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint
             if (!(w[2] & GAME_HAS_FULL) || (f & AZH_SAMPLES_PLY_FULL))
                 p_candidates[(size_t)(at + c++)] = (u16)p;
         }
+        if (game_blockers) {
+            int64_t ply = -1;
+            if (const char *why = walls_refusal(game_blockers[g], boards + 2 * at, (int64_t)w[1], &ply))
+                return azh_fail(-2, "azh_samples_add_games: game %lld (blockers %#llx, ply %lld): %s", (long long)g,
+                                (unsigned long long)game_blockers[g], (long long)ply, why);
+            walled = walled || game_blockers[g] != 0;
+        }
         g_words[(size_t)g] = make_uint4((u32)(s->plies + at), w[1], w[2], w[3]);
         g_count[(size_t)g] = c;
         at += w[1];
@@ -484,6 +523,16 @@ extern "C" int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint
                         (long long)s->cap_plies, (long long)s->cap_targets);
     // (the copies go behind whatever the store's stream still runs and are waited for: the vectors die with this call.  A
     // gather in flight on another stream reads only what lies below the counts it was launched with.)
+    std::vector<u64> g_blockers((size_t)n_games, 0ULL);
+    if (game_blockers)
+        std::copy(game_blockers, game_blockers + n_games, g_blockers.begin());
+    if (walled && !s->d_blockers.d) {  // the first walls: every game stored so far has none
+        if (int rc = s->d_blockers.alloc((size_t)s->cap_games))
+            return rc;
+        AZH_HIP(hipMemsetAsync(s->d_blockers.d, 0, (size_t)s->cap_games * sizeof(u64), s->stream));
+    }
+    if (n_games && s->d_blockers.d)
+        AZH_HIP(hipMemcpyAsync(s->d_blockers.d + s->games, g_blockers.data(), (size_t)n_games * sizeof(u64), hipMemcpyHostToDevice, s->stream));
     if (n_games) {
         AZH_HIP(hipMemcpyAsync(s->d_games.d + s->games, g_words.data(), (size_t)n_games * sizeof(uint4), hipMemcpyHostToDevice, s->stream));
         AZH_HIP(hipMemcpyAsync(s->d_candidate_count.d + s->games, g_count.data(), (size_t)n_games * sizeof(u32), hipMemcpyHostToDevice, s->stream));
@@ -513,6 +562,7 @@ extern "C" int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint
         s->h_games.insert(s->h_games.end(), {w.x, w.y, w.z, w.w});
     }
     s->h_flags.insert(s->h_flags.end(), p_flags.begin(), p_flags.end());
+    s->h_blockers.insert(s->h_blockers.end(), g_blockers.begin(), g_blockers.end());
     s->games += n_games;
     s->plies += n_plies;
     s->targets += n_targets;
@@ -525,6 +575,18 @@ extern "C" int azh_samples_pack_records(const uint32_t *rec, int64_t words, int6
                                         uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
                                         uint16_t *target_index, float *target_weight)
 {
+    return azh_samples_pack_records_blockers(rec, words, 0ULL, counts, games, boards, ply_flags, values, target_start,
+                                             target_index, target_weight, nullptr);
+}
+
+extern "C" int azh_samples_pack_records_blockers(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts,
+                                                 uint32_t *games, uint64_t *boards, uint8_t *ply_flags, double *values,
+                                                 int32_t *target_start, uint16_t *target_index, float *target_weight,
+                                                 uint64_t *game_blockers)
+{
+    if (blockers & ~BOARD_MASK)
+        return azh_fail(-2, "azh_samples_pack_records: the blockers mask %#llx has bits beyond the 49 cells",
+                        (unsigned long long)blockers);
     if (!counts || (words > 0 && !rec) || words < 0)
         return azh_fail(-1, "azh_samples_pack_records: null argument");
     const bool write = games != nullptr;
@@ -546,6 +608,9 @@ extern "C" int azh_samples_pack_records(const uint32_t *rec, int64_t words, int6
         size_t at = 8;
         for (uint32_t p = 0; p < r[3]; p++) {
             const uint32_t nd = r[at + 4] >> 16;
+            if ((((uint64_t)r[at] | r[at + 2]) | (((uint64_t)r[at + 1] | r[at + 3]) << 32)) & blockers)
+                return azh_fail(-2, "azh_samples_pack_records: word %lld, ply %u: a stone stands on a wall cell of the "
+                                    "blockers mask %#llx", (long long)(r - rec), p, (unsigned long long)blockers);
             for (uint32_t j = 0; j < nd; j++)
                 if (!board_move(r[at + 6 + j] & 0xFFFFu))
                     return azh_fail(-2, "azh_samples_pack_records: target %#x is no clone and no jump", r[at + 6 + j] & 0xFFFFu);
@@ -578,6 +643,8 @@ extern "C" int azh_samples_pack_records(const uint32_t *rec, int64_t words, int6
         games[4 * g + 1] = r[3];
         games[4 * g + 2] = r[4] | (capped ? GAME_HAS_FULL : 0u) | (valued ? GAME_HAS_VALUES : 0u);
         games[4 * g + 3] = r[6];
+        if (game_blockers)
+            game_blockers[g] = blockers;
         g++;
         size_t at = 8;
         for (uint32_t p = 0; p < r[3]; p++, q++) {
@@ -618,11 +685,18 @@ extern "C" int azh_samples_pack_records(const uint32_t *rec, int64_t words, int6
 
 extern "C" int azh_samples_add_records(azh_samples *s, const uint32_t *rec, int64_t words)
 {
+    return azh_samples_add_records_blockers(s, rec, words, 0ULL);
+}
+
+extern "C" int azh_samples_add_records_blockers(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers)
+{
     if (!s)
         return azh_fail(-1, "azh_samples_add_records: null store");
     int64_t counts[3] = {0, 0, 0};
-    if (int rc = azh_samples_pack_records(rec, words, counts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+    if (int rc = azh_samples_pack_records_blockers(rec, words, blockers, counts, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                   nullptr, nullptr, nullptr))
         return rc;
+    std::vector<uint64_t> masks((size_t)counts[0] + 1);
     std::vector<uint32_t> games((size_t)counts[0] * 4 + 1);
     std::vector<uint64_t> boards((size_t)counts[1] * 2 + 1);
     std::vector<uint8_t> flags((size_t)counts[1] + 1);
@@ -630,11 +704,11 @@ extern "C" int azh_samples_add_records(azh_samples *s, const uint32_t *rec, int6
     std::vector<int32_t> start((size_t)counts[1] + 1);
     std::vector<uint16_t> index((size_t)counts[2] + 1);
     std::vector<float> weight((size_t)counts[2] + 1);
-    if (int rc = azh_samples_pack_records(rec, words, counts, games.data(), boards.data(), flags.data(), values.data(),
-                                          start.data(), index.data(), weight.data()))
+    if (int rc = azh_samples_pack_records_blockers(rec, words, blockers, counts, games.data(), boards.data(), flags.data(),
+                                                   values.data(), start.data(), index.data(), weight.data(), masks.data()))
         return rc;
-    return azh_samples_add_games(s, counts[0], games.data(), counts[1], boards.data(), flags.data(), values.data(),
-                                 start.data(), index.data(), weight.data());
+    return azh_samples_add_games_blockers(s, counts[0], games.data(), counts[1], boards.data(), flags.data(), values.data(),
+                                          start.data(), index.data(), weight.data(), blockers ? masks.data() : nullptr);
 }
 
 extern "C" int azh_samples_counts(const azh_samples *s, int64_t *out)
@@ -656,6 +730,15 @@ extern "C" int azh_samples_mirror(const azh_samples *s, uint32_t *games, uint8_t
         memcpy(games, s->h_games.data(), s->h_games.size() * sizeof(uint32_t));
     if (!s->h_flags.empty())
         memcpy(ply_flags, s->h_flags.data(), s->h_flags.size());
+    return 0;
+}
+
+extern "C" int azh_samples_game_blockers(const azh_samples *s, uint64_t *blockers)
+{
+    if (!s || !blockers)
+        return azh_fail(-1, "azh_samples_game_blockers: null argument");
+    if (!s->h_blockers.empty())
+        memcpy(blockers, s->h_blockers.data(), s->h_blockers.size() * sizeof(uint64_t));
     return 0;
 }
 
@@ -811,6 +894,38 @@ static int reserve_surprise(azh_samples *s)
     return 0;
 }
 
+namespace {
+struct MaskRun {  // plies [first, end) of consecutive games that share one wall mask
+    int64_t first, end;
+    u64 blockers;
+};
+}  // namespace
+
+// The stored plies [first, end) cut where the wall mask of their games changes: no launch of the tower or of the surprise kernel
+// spans two masks.  From the host mirror.
+static std::vector<MaskRun> mask_runs(const azh_samples *s, int64_t first, int64_t end)
+{
+    std::vector<MaskRun> runs;
+    int64_t lo = 0, hi = s->games - 1;  // the game that holds ply `first`: the last one whose first ply is <= first
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if ((int64_t)s->h_games[4 * mid] <= first)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    for (int64_t g = lo; g < s->games && (int64_t)s->h_games[4 * g] < end; g++) {
+        const int64_t a = std::max<int64_t>(first, s->h_games[4 * g]);
+        const int64_t b = std::min<int64_t>(end, (int64_t)s->h_games[4 * g] + s->h_games[4 * g + 1]);
+        const u64 mask = s->h_blockers[(size_t)g];
+        if (!runs.empty() && runs.back().blockers == mask)
+            runs.back().end = b;
+        else
+            runs.push_back(MaskRun{a, b, mask});
+    }
+    return runs;
+}
+
 extern "C" int azh_samples_surprise_logits(azh_samples *s, int64_t first_ply, int64_t n_plies, const float *d_logits,
                                            float *kl_out, int64_t *illegal_out, uintptr_t stream)
 {
@@ -823,9 +938,12 @@ extern "C" int azh_samples_surprise_logits(azh_samples *s, int64_t first_ply, in
         return rc;
     hipStream_t st = stream ? (hipStream_t)stream : s->stream;
     AZH_HIP(hipMemsetAsync(s->d_illegal.d, 0, sizeof(u32), st));
-    hipLaunchKernelGGL(k_samples_surprise, dim3((unsigned)n_plies), dim3(WAVE), 0, st, s->view(), (u32)first_ply, (int)n_plies,
-                       d_logits, s->d_kl.d, s->d_illegal.d);
-    AZH_HIP(hipGetLastError());
+    for (const MaskRun &run : mask_runs(s, first_ply, first_ply + n_plies)) {
+        hipLaunchKernelGGL(k_samples_surprise, dim3((unsigned)(run.end - run.first)), dim3(WAVE), 0, st, s->view(),
+                           (u32)run.first, (int)(run.end - run.first), d_logits + (size_t)(run.first - first_ply) * POLICY,
+                           s->d_kl.d, s->d_illegal.d, run.blockers);
+        AZH_HIP(hipGetLastError());
+    }
     u32 missing = 0;
     AZH_HIP(hipMemcpyAsync(kl_out, s->d_kl.d + first_ply, (size_t)n_plies * sizeof(float), hipMemcpyDeviceToHost, st));
     AZH_HIP(hipMemcpyAsync(&missing, s->d_illegal.d, sizeof(u32), hipMemcpyDeviceToHost, st));
@@ -891,17 +1009,23 @@ extern "C" int azh_samples_surprise(azh_samples *s, azh_net *net, int dtype, int
     AZH_HIP(hipMemsetAsync(s->d_illegal.d, 0, sizeof(u32), st));
     s->surprise_ms[0] = s->surprise_ms[1] = 0.f;
     // (each chunk is waited for before the next reuses the scratch and the events: the tower's time dwarfs the wait)
-    for (int64_t at = first; at < end; at += chunk) {
-        const int n = (int)std::min<int64_t>(chunk, end - at);
+    // (a chunk never spans two wall masks: the tower takes one blocker plane per launch, the kernel one mask)
+    std::vector<MaskRun> chunks;  // cut at mask changes as well as at `chunk` plies
+    for (const MaskRun &r : mask_runs(s, first, end))
+        for (int64_t at = r.first; at < r.end; at += chunk)
+            chunks.push_back(MaskRun{at, std::min<int64_t>(at + chunk, r.end), r.blockers});
+    for (const MaskRun &run : chunks) {
+        const int64_t at = run.first;
+        const int n = (int)(run.end - run.first);
         AZH_HIP(hipEventRecord(sc.ev[0], st));
         hipLaunchKernelGGL(k_samples_pack_boards, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->view(), (u32)at, n,
                            sc.boards);
         AZH_HIP(hipGetLastError());
-        if (int rc = azh_net_launch(net, dtype, sc.boards, nullptr, nullptr, n, 0ULL, sc.logits, sc.values, st))
+        if (int rc = azh_net_launch(net, dtype, sc.boards, nullptr, nullptr, n, run.blockers, sc.logits, sc.values, st))
             return rc;
         AZH_HIP(hipEventRecord(sc.ev[1], st));
         hipLaunchKernelGGL(k_samples_surprise, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), (u32)at, n, sc.logits,
-                           s->d_kl.d, s->d_illegal.d);
+                           s->d_kl.d, s->d_illegal.d, run.blockers);
         AZH_HIP(hipGetLastError());
         AZH_HIP(hipEventRecord(sc.ev[2], st));
         AZH_HIP(hipStreamSynchronize(st));
@@ -920,11 +1044,17 @@ extern "C" int azh_samples_surprise(azh_samples *s, azh_net *net, int dtype, int
 
 extern "C" int azh_samples_legal(uint64_t mover, uint64_t opponent, uint16_t *index_out, int32_t *n_out)
 {
+    return azh_samples_legal_blockers(mover, opponent, 0ULL, index_out, n_out);
+}
+
+extern "C" int azh_samples_legal_blockers(uint64_t mover, uint64_t opponent, uint64_t blockers, uint16_t *index_out,
+                                          int32_t *n_out)
+{
     if (!index_out || !n_out)
         return azh_fail(-1, "azh_samples_legal: null argument");
     mover &= BOARD_MASK;
     opponent &= BOARD_MASK;
-    const u64 empty = BOARD_MASK & ~(mover | opponent);
+    const u64 empty = BOARD_MASK & ~(mover | opponent | blockers);
     int n = 0;
     for (int from = 0; from < 49; from++)  // wave_movegen's order: jumps by ascending (from, to), then clones ascending
         if ((mover >> from) & 1ULL)
@@ -975,6 +1105,17 @@ extern "C" int azh_samples_surprise_host(const float *logits833, const uint16_t 
     if (illegal_out)
         *illegal_out = missing;
     return 0;
+}
+
+extern "C" int azh_samples_surprise_host_blockers(const float *logits833, uint64_t mover, uint64_t opponent, uint64_t blockers,
+                                                  const uint16_t *target_index, const float *target_weight, int n_targets,
+                                                  float *kl_out, int32_t *illegal_out)
+{
+    uint16_t legal[POLICY];
+    int32_t n_legal = 0;
+    if (int rc = azh_samples_legal_blockers(mover, opponent, blockers, legal, &n_legal))
+        return rc;
+    return azh_samples_surprise_host(logits833, legal, n_legal, target_index, target_weight, n_targets, kl_out, illegal_out);
 }
 
 static void default_cum(const azh_samples *s, int64_t game, u32 *cum)  // cum: the store's whole array

@@ -171,6 +171,9 @@ SIGNATURES = {
     "azh_engine_drain_json": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _P(ctypes.c_int64), _P(_i32)]),
     "azh_format_record_json": (ctypes.c_int, [_vp, ctypes.c_int64, _i32, _vp, ctypes.c_int64, _P(ctypes.c_int64)]),
     "azh_engine_set_emit_order": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "azh_engine_set_record_blockers": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "azh_format_record_json_blockers": (ctypes.c_int, [_vp, ctypes.c_int64, _i32, _u64, _vp, ctypes.c_int64,
+                                                       _P(ctypes.c_int64)]),
     "azh_engine_set_positions": (ctypes.c_int, [_vp, _vp, _vp]),
     "azh_engine_set_game_limit": (ctypes.c_int, [_vp, ctypes.c_int64]),
     "azh_samples_create": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P(_vp)]),
@@ -178,6 +181,14 @@ SIGNATURES = {
     "azh_samples_add_games": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "azh_samples_pack_records": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "azh_samples_add_records": (ctypes.c_int, [_vp, _vp, ctypes.c_int64]),
+    "azh_samples_add_games_blockers": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                      _vp]),
+    "azh_samples_pack_records_blockers": (ctypes.c_int, [_vp, ctypes.c_int64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                         _vp]),
+    "azh_samples_add_records_blockers": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _u64]),
+    "azh_samples_game_blockers": (ctypes.c_int, [_vp, _vp]),
+    "azh_samples_legal_blockers": (ctypes.c_int, [_u64, _u64, _u64, _vp, _P(_i32)]),
+    "azh_samples_surprise_host_blockers": (ctypes.c_int, [_vp, _u64, _u64, _u64, _vp, _vp, ctypes.c_int, _P(_f32), _P(_i32)]),
     "azh_samples_counts": (ctypes.c_int, [_vp, _vp]),
     "azh_samples_mirror": (ctypes.c_int, [_vp, _vp, _vp]),
     "azh_samples_gather": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp, ctypes.c_size_t]),
@@ -273,19 +284,41 @@ def shutdown():
     load().shutdown()
 
 
-def format_record_json(rec, with_ids=False):
+def format_record_json(rec, with_ids=False, blockers=None):
     """The JSON line (bytes, no newline) of one finished-game record — uint32 words as the device loop leaves them in its
-    ring — in the reference's entry format (cpp/self_play_client.cpp:565-578,639-641).  Host code only: no GPU needed."""
+    ring — in the reference's entry format (cpp/self_play_client.cpp:565-578,639-641).  blockers: None, or a wall mask (bit
+    = file + 7 * rank): the line gains "blockers", its cells in the index of the line's boards, in front
+    (azh_format_record_json_blockers).  Host code only: no GPU needed."""
     rec = np.ascontiguousarray(rec, dtype=np.uint32)
+
+    def call(buf, used):
+        if blockers is None:
+            return load().azh_format_record_json(_ptr(rec), rec.size, int(bool(with_ids)), _ptr(buf), buf.nbytes,
+                                                 ctypes.byref(used))
+        return load().azh_format_record_json_blockers(_ptr(rec), rec.size, int(bool(with_ids)), int(blockers), _ptr(buf),
+                                                      buf.nbytes, ctypes.byref(used))
     buf = np.zeros(1 << 16, dtype=np.uint8)
     used = ctypes.c_int64(0)
-    rc = load().azh_format_record_json(_ptr(rec), rec.size, int(bool(with_ids)), _ptr(buf), buf.nbytes, ctypes.byref(used))
+    rc = call(buf, used)
     if rc == -6:
         buf = np.zeros(used.value, dtype=np.uint8)
-        rc = load().azh_format_record_json(_ptr(rec), rec.size, int(bool(with_ids)), _ptr(buf), buf.nbytes,
-                                           ctypes.byref(used))
+        rc = call(buf, used)
     check(rc)
     return bytes(buf[:used.value])
+
+
+def blockers_to_cells(mask):
+    """A wall mask (bit = file + 7 * rank) -> the ascending list of its cells in the game line's index x + 7 y (y = 0 at rank
+    7): a line's "blockers"."""
+    return [c for c in range(49) if (int(mask) >> (c % 7 + 7 * (6 - c // 7))) & 1]
+
+
+def cells_to_blockers(cells):
+    """A line's "blockers" -> the wall mask."""
+    mask = 0
+    for c in cells:
+        mask |= 1 << (c % 7 + 7 * (6 - c // 7))
+    return mask
 
 
 def playout_cap_kind(seed, uid, ply, full_per_65536):
@@ -700,6 +733,11 @@ class Engine:
         """True: finished games are handed out in uid order (unbiased prefixes); False: as they finish."""
         check(load().azh_engine_set_emit_order(self.h, 1 if by_uid else 0))
 
+    def set_record_blockers(self, on=True):
+        """Every line drain_json writes gains "blockers", the engine's mask as the wall cells in the index of the line's
+        boards (azh_engine_set_record_blockers)."""
+        check(load().azh_engine_set_record_blockers(self.h, 1 if on else 0))
+
     def set_game_limit(self, games):
         """Play uids 0 .. games - 1 only; slots past the limit go idle (call before the first iteration)."""
         check(load().azh_engine_set_game_limit(self.h, int(games)))
@@ -813,10 +851,10 @@ class Engine:
 class SampleArrays:
     """Games as azh_samples_add_games takes them: games (G, 4) u32 {first ply, plies, result | SAMPLES_GAME_*, random_ply + 1},
     boards (P, 2) u64, ply_flags (P,) u8, values (P,) f64, target_start (P + 1,) i32, target_index (T,) u16, target_weight
-    (T,) f32."""
-    __slots__ = ("games", "boards", "ply_flags", "values", "target_start", "target_index", "target_weight")
+    (T,) f32; blockers (G,) u64, every game's wall mask (bit = file + 7 * rank; default: none has walls)."""
+    __slots__ = ("games", "boards", "ply_flags", "values", "target_start", "target_index", "target_weight", "blockers")
 
-    def __init__(self, games, boards, ply_flags, values, target_start, target_index, target_weight):
+    def __init__(self, games, boards, ply_flags, values, target_start, target_index, target_weight, blockers=None):
         self.games = np.ascontiguousarray(games, dtype=np.uint32).reshape(-1, 4)
         self.boards = np.ascontiguousarray(boards, dtype=np.uint64).reshape(-1, 2)
         self.ply_flags = np.ascontiguousarray(ply_flags, dtype=np.uint8)
@@ -824,6 +862,10 @@ class SampleArrays:
         self.target_start = np.ascontiguousarray(target_start, dtype=np.int32)
         self.target_index = np.ascontiguousarray(target_index, dtype=np.uint16)
         self.target_weight = np.ascontiguousarray(target_weight, dtype=np.float32)
+        self.blockers = (np.zeros(len(self.games), dtype=np.uint64) if blockers is None
+                         else np.ascontiguousarray(blockers, dtype=np.uint64))
+        if len(self.blockers) != len(self.games):
+            raise ValueError("one blockers mask per game")
 
 
 # bit x + 7 (6 - y) of a bitboard is the cell the game line's boards[ply][x + 7 y] names
@@ -832,11 +874,15 @@ _CELL_BIT = np.array([1 << (c % 7 + 7 * (6 - c // 7)) for c in range(49)], dtype
 
 def entries_to_arrays(entries):
     """Parsed game lines -> SampleArrays, with the conversions of training._entry_arrays (weights np.float32 of the parsed
-    double, "pass" keys skipped, an entry without `dists` a one-hot on the move played), in the order given.  Host only."""
+    double, "pass" keys skipped, an entry without `dists` a one-hot on the move played), in the order given; an entry's
+    "blockers" becomes its game's mask, after training.check_blockers (ValueError).  Host only."""
     from . import training
     games, boards, flags, values, starts, index, weight = [], [], [], [], [np.zeros(1, dtype=np.int32)], [], []
+    masks = []
     plies = targets = 0
-    for entry in entries:
+    for number, entry in enumerate(entries):
+        training.check_blockers(entry, "entry %d" % number)
+        masks.append(cells_to_blockers(entry.get("blockers", ())))
         cells, idx, wts, start = training._entry_arrays(entry)
         n = len(entry["boards"])
         if n < 1 or cells.shape != (n, 49) or cells.min() < 0 or cells.max() > 2:
@@ -865,21 +911,26 @@ def entries_to_arrays(entries):
         return np.concatenate(parts).astype(dtype, copy=False) if parts else np.zeros(0, dtype=dtype)
     return SampleArrays(np.array(games, dtype=np.uint32).reshape(-1, 4), cat(boards, np.uint64).reshape(-1, 2),
                         cat(flags, np.uint8), cat(values, np.float64), cat(starts, np.int32), cat(index, np.uint16),
-                        cat(weight, np.float32))
+                        cat(weight, np.float32), np.array(masks, dtype=np.uint64))
 
 
-def pack_records(records):
-    """Ring records (Engine.staged_records) -> SampleArrays holding what parsing the games' own lines would give
-    (azh_samples_pack_records; host code, no GPU needed)."""
+def pack_records(records, blockers=0):
+    """Ring records (Engine.staged_records) -> SampleArrays holding what parsing the games' own lines would give; blockers:
+    the wall mask of the engine that wrote them, which a line written with "blockers" carries
+    (azh_samples_pack_records_blockers; host code, no GPU needed)."""
     rec = np.ascontiguousarray(records, dtype=np.uint32).ravel()
     counts = np.zeros(3, dtype=np.int64)
-    check(load().azh_samples_pack_records(_ptr(rec), rec.size, _ptr(counts), None, None, None, None, None, None, None))
+    check(load().azh_samples_pack_records_blockers(_ptr(rec), rec.size, int(blockers), _ptr(counts), None, None, None, None,
+                                                   None, None, None, None))
     g, p, t = (int(c) for c in counts)
     a = SampleArrays(np.zeros((g, 4), np.uint32), np.zeros((p, 2), np.uint64), np.zeros(p, np.uint8), np.zeros(p),
                      np.zeros(p + 1, np.int32), np.zeros(max(t, 1), np.uint16), np.zeros(max(t, 1), np.float32))
     games = a.games if g else np.zeros((1, 4), np.uint32)      # (non-null: a null `games` asks for the counts only)
-    check(load().azh_samples_pack_records(_ptr(rec), rec.size, _ptr(counts), _ptr(games), _ptr(a.boards), _ptr(a.ply_flags),
-                                          _ptr(a.values), _ptr(a.target_start), _ptr(a.target_index), _ptr(a.target_weight)))
+    masks = np.zeros(max(g, 1), np.uint64)
+    check(load().azh_samples_pack_records_blockers(_ptr(rec), rec.size, int(blockers), _ptr(counts), _ptr(games),
+                                                   _ptr(a.boards), _ptr(a.ply_flags), _ptr(a.values), _ptr(a.target_start),
+                                                   _ptr(a.target_index), _ptr(a.target_weight), _ptr(masks)))
+    a.blockers = masks[:g]
     a.target_index, a.target_weight = a.target_index[:t], a.target_weight[:t]
     return a
 
@@ -910,12 +961,30 @@ def samples_draw_weighted(seed, step, sample, first_game, n_games, games, ply_fl
     return tuple(int(v) for v in out)
 
 
-def samples_legal(mover, opponent):
-    """The legal moves of a position (the mover's and the opponent's stones as bitboards, no blockers) as flat policy indices
-    in the device movegen's order -> u16 array (azh_samples_legal; host arithmetic)."""
+def samples_legal(mover, opponent, blockers=0):
+    """The legal moves of a position (the mover's and the opponent's stones and the walls as bitboards) as flat policy indices
+    in the device movegen's order -> u16 array (azh_samples_legal_blockers; host arithmetic)."""
     index, n = np.zeros(833, dtype=np.uint16), ctypes.c_int32(0)
-    check(load().azh_samples_legal(int(mover), int(opponent), _ptr(index), ctypes.byref(n)))
+    check(load().azh_samples_legal_blockers(int(mover), int(opponent), int(blockers), _ptr(index), ctypes.byref(n)))
     return index[:n.value].copy()
+
+
+def samples_surprise_host_blockers(logits, mover, opponent, blockers, target_index, target_weight):
+    """samples_surprise_host with the legal moves found from the position and its walls
+    (azh_samples_surprise_host_blockers; host arithmetic)."""
+    logits = np.ascontiguousarray(logits, dtype=np.float32).ravel()
+    if logits.size != 833:
+        raise ValueError("833 logits")
+    target_index = np.ascontiguousarray(target_index, dtype=np.uint16)
+    target_weight = np.ascontiguousarray(target_weight, dtype=np.float32)
+    if len(target_index) != len(target_weight):
+        raise ValueError("one weight per target")
+    kl, illegal = ctypes.c_float(0.0), ctypes.c_int32(0)
+    check(load().azh_samples_surprise_host_blockers(_ptr(logits), int(mover), int(opponent), int(blockers),
+                                                    _ptr(target_index) if len(target_index) else None,
+                                                    _ptr(target_weight) if len(target_weight) else None, len(target_index),
+                                                    ctypes.byref(kl), ctypes.byref(illegal)))
+    return np.float32(kl.value), int(illegal.value)
 
 
 def samples_surprise_host(logits, legal_index, target_index, target_weight):
@@ -986,19 +1055,28 @@ class SampleStore:
 
     def add_arrays(self, a):
         self._mirror = None
-        check(load().azh_samples_add_games(self.h, len(a.games), _ptr(a.games), len(a.ply_flags), _ptr(a.boards),
-                                           _ptr(a.ply_flags), _ptr(a.values), _ptr(a.target_start), _ptr(a.target_index),
-                                           _ptr(a.target_weight)))
+        masks = a.blockers if len(a.blockers) and a.blockers.any() else None
+        check(load().azh_samples_add_games_blockers(self.h, len(a.games), _ptr(a.games), len(a.ply_flags), _ptr(a.boards),
+                                                    _ptr(a.ply_flags), _ptr(a.values), _ptr(a.target_start),
+                                                    _ptr(a.target_index), _ptr(a.target_weight), _ptr(masks)))
 
     def add_entries(self, entries):
         """Parsed game lines, in the order given (entries_to_arrays)."""
         self.add_arrays(entries_to_arrays(entries))
 
-    def add_records(self, records):
-        """Ring records as Engine.staged_records returns them (azh_samples_add_records)."""
+    def add_records(self, records, blockers=0):
+        """Ring records as Engine.staged_records returns them, and the wall mask of the engine that wrote them
+        (azh_samples_add_records_blockers)."""
         rec = np.ascontiguousarray(records, dtype=np.uint32).ravel()
         self._mirror = None
-        check(load().azh_samples_add_records(self.h, _ptr(rec), rec.size))
+        check(load().azh_samples_add_records_blockers(self.h, _ptr(rec), rec.size, int(blockers)))
+
+    def game_blockers(self):
+        """-> (G,) u64: every stored game's wall mask, 0 for a game without walls (azh_samples_game_blockers)."""
+        n = self.counts()["games"]
+        masks = np.zeros(max(n, 1), np.uint64)
+        check(load().azh_samples_game_blockers(self.h, _ptr(masks)))
+        return masks[:n]
 
     def counts(self):
         out = np.zeros(4, dtype=np.int64)

@@ -44,6 +44,18 @@ def parse_fen(fen):
     return x, o, bl, turn
 
 
+def symmetric_blockers(blockers):
+    """Is the wall mask its own image under all 8 symmetries of the board?  (link.symmetry_board; host arithmetic)"""
+    return all(link.symmetry_board(s, blockers) == blockers for s in (1, 2, 4))
+
+
+def symmetry_refusal(blockers):
+    """Why the random symmetry does not go with an asymmetric wall mask, in the words of the engine's own refusal
+    (azh_engine_set_random_symmetry)."""
+    return ("not supported with a blockers mask (0x%x) that is not its own image under all 8 symmetries (the tower takes one "
+            "blocker plane per launch)" % blockers)
+
+
 def make_config(games, visits, seed=DEFAULT_SEED, fen=START_FEN_SELFPLAY, max_plies=400, edges_per_node=96,
                 c_puct=1.0, dirichlet_alpha=0.15, dirichlet_weight=0.25, flags=0, select_budget=0):
     """Search constants default to cpp/self_play_client.cpp:31-34."""
@@ -250,6 +262,11 @@ class SelfPlay:
     def set_emit_order(self, by_uid):
         for e in self.engines:
             e.set_emit_order(by_uid)
+
+    def set_record_blockers(self, on=True):
+        """Every line gains "blockers", the start position's wall cells (link.Engine.set_record_blockers)."""
+        for e in self.engines:
+            e.set_record_blockers(on)
 
     def set_game_limit(self, games):
         """`games` games in all, then the slots go idle.  uids are per engine: half-batch i of K plays its own uids

@@ -10,7 +10,7 @@ instance this repo's own `uai_interface.py`, which searches on the GPU.
 import random
 import subprocess
 
-from . import selfplay, uai
+from . import link, selfplay, uai
 
 MAXIMUM_GAME_PLIES = 400
 OPENING_RANDOMIZATION_SCHEDULE = [0.2 * (0.5 ** (i / 2)) for i in range(10)]  # generate_games.py:11-14
@@ -65,10 +65,13 @@ class Teacher:
 UAIPlayer = Teacher  # the reference's name for it
 
 
-def generate_game(teacher, ms, rng=random):
-    """One teacher game -> entry {"boards", "moves", "result"} (result None when cut at 400 plies)."""
-    board = uai.Position.initial()
+def generate_game(teacher, ms, rng=random, start_fen=selfplay.START_FEN_PLAIN):
+    """One teacher game -> entry {"boards", "moves", "result"} (result None when cut at 400 plies).  start_fen: the start
+    position; on a board with walls the teacher is sent them (Position.fen writes '-') and the entry gains "blockers"."""
+    board = uai.Position.initial(start_fen)
     entry = {"boards": [], "moves": []}
+    if board.blockers:
+        entry["blockers"] = link.blockers_to_cells(board.blockers)
     result = 0
     for ply in range(MAXIMUM_GAME_PLIES):
         legal, result = board.legal_moves()

@@ -38,15 +38,41 @@ def uai_decode_move(text):
     return text_to_xy_move(text)
 
 
-def board_to_features(cells, to_move):
-    """Four planes [x][y][c] — ones, mover's stones, opponent's stones, blockers (none in training files) — from the 49
-    recorded cells (index x + 7 y), engine.py:53-73."""
+def board_to_features(cells, to_move, blockers=None):
+    """Four planes [x][y][c] — ones, mover's stones, opponent's stones, blockers — from the 49 recorded cells (index
+    x + 7 y), engine.py:53-73.  blockers: the wall cells in that index (an entry's "blockers"; the reference's files carry
+    none and its plane stays zero)."""
     grid = np.asarray(cells, dtype=np.int8).reshape(BOARD, BOARD).T      # grid[x, y]
     planes = np.zeros((BOARD, BOARD, 4), dtype=np.int8)
     planes[..., 0] = 1
     planes[..., 1] = grid == to_move
     planes[..., 2] = (grid != 0) & (grid != to_move)
+    if blockers:
+        planes[..., 3] = _wall_row(blockers).reshape(BOARD, BOARD).T
     return planes
+
+
+def _wall_row(blockers):
+    """The wall cells of an entry's "blockers" as 49 int8 in the index of its boards."""
+    row = np.zeros(BOARD * BOARD, dtype=np.int8)
+    row[np.asarray(blockers, dtype=np.int64)] = 1
+    return row
+
+
+def check_blockers(entry, name):
+    """ValueError naming the game unless the entry's "blockers" (if it has any) is a strictly ascending list of cells in
+    0..48 none of which ever holds a stone."""
+    if "blockers" not in entry:
+        return
+    cells = entry["blockers"]
+    if (not isinstance(cells, list) or any(type(c) is not int or not 0 <= c < BOARD * BOARD for c in cells) or
+            any(a >= b for a, b in zip(cells, cells[1:]))):
+        raise ValueError("%s: \"blockers\" must be an ascending list of distinct cells in 0..48, not %r" % (name, cells))
+    if cells:
+        boards = np.asarray(entry["boards"], dtype=np.int8).reshape(-1, BOARD * BOARD)
+        on = np.flatnonzero((boards[:, cells] != 0).any(axis=1))
+        if len(on):
+            raise ValueError("%s: a stone stands on a wall cell at ply %d" % (name, int(on[0])))
 
 
 def _symmetry_bits(index):
@@ -142,7 +168,7 @@ def get_sample_from_entries(entries, value_blend=0.0):
             continue
         mover = 1 + ply % 2                         # x (1) moves on even plies
         symmetry_index = random.randrange(8)
-        features = apply_symmetry(symmetry_index, board_to_features(entry["boards"][ply], mover))
+        features = apply_symmetry(symmetry_index, board_to_features(entry["boards"][ply], mover, entry.get("blockers")))
         value = [_value_target(entry, ply, mover, value_blend)]
         return features, _policy_target(entry, ply, symmetry_index), value
 
@@ -151,10 +177,11 @@ def load_entries(paths):
     entries = []                                                          # train.py:79-89
     for path in paths:
         with open(path) as f:
-            for line in f:
+            for number, line in enumerate(f, 1):
                 line = line.strip()
                 if line:
                     entries.append(json.loads(line))
+                    check_blockers(entries[-1], "%s, line %d" % (path, number))
     random.shuffle(entries)
     return entries
 
@@ -251,7 +278,7 @@ def make_minibatch(entries, size, value_blend=0.0):
     if _TABLES is None:
         _TABLES = _symmetry_tables()
     cell_src, policy_to = _TABLES
-    cells, movers, syms, targets, rows, pidx, pw = [], [], [], [], [], [], []
+    cells, movers, syms, targets, rows, pidx, pw, walls = [], [], [], [], [], [], [], {}
     while len(cells) < size:
         entry = random.choice(entries)                      # the reference's draws, in its order (train.py:45-60)
         ply = _draw_ply(entry)
@@ -267,6 +294,8 @@ def make_minibatch(entries, size, value_blend=0.0):
         rows.append(np.full(hi - lo, len(cells), dtype=np.int64))
         pidx.append(policy_to[sym, idx[lo:hi]])
         pw.append(wts[lo:hi])
+        if entry.get("blockers"):
+            walls[len(cells)] = _wall_row(entry["blockers"])
         cells.append(c[ply])
         movers.append(1 + ply % 2)
         syms.append(sym)
@@ -278,6 +307,8 @@ def make_minibatch(entries, size, value_blend=0.0):
     feats[..., 0] = 1
     feats[..., 1] = shown == movers
     feats[..., 2] = (shown != 0) & (shown != movers)
+    for i, row in walls.items():                            # plane 3: the walls, under the sample's symmetry like the stones
+        feats[i, :, 3] = row[cell_src[syms[i]]]
     pols = np.zeros((size, BOARD * BOARD * MOVE_TYPES), dtype=np.float32)
     np.add.at(pols, (np.concatenate(rows), np.concatenate(pidx)), np.concatenate(pw))
     if (np.abs(1 - pols.sum(axis=1)) >= 1e-3).any():
@@ -347,8 +378,11 @@ def _fill_store(entries, log):
     store = link.SampleStore(max(len(arrays.games), 1), max(len(arrays.ply_flags), 1), max(len(arrays.target_index), 1))
     store.add_arrays(arrays)
     c = store.counts()
-    log("Device samples: %i games, %i plies, %i policy targets in device memory; %i plies whose target does not sum to one."
-        % (c["games"], c["plies"], c["targets"], c["bad_plies"]))
+    masks = store.game_blockers()
+    walled = masks[masks != 0]
+    log("Device samples: %i games, %i plies, %i policy targets in device memory; %i plies whose target does not sum to one%s."
+        % (c["games"], c["plies"], c["targets"], c["bad_plies"],
+           "; %i games on %i wall maps" % (len(walled), len(set(walled.tolist()))) if len(walled) else ""))
     return store
 
 

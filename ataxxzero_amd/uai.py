@@ -55,27 +55,34 @@ def decode_move(s):
 class Position:
     """Board bookkeeping of the front-end, with the GPU rules behind it."""
 
-    def __init__(self, x, o, turn):
-        self.x, self.o, self.turn = x, o, turn
+    def __init__(self, x, o, turn, blockers=0):
+        self.x, self.o, self.turn, self.blockers = x, o, turn, blockers
 
     @staticmethod
-    def initial():
-        x, o, _, turn = selfplay.parse_fen(selfplay.START_FEN_PLAIN)
-        return Position(x, o, turn)
+    def initial(fen=selfplay.START_FEN_PLAIN):
+        return Position.from_fen(fen)
 
     @staticmethod
     def from_fen(fen):
         x, o, bl, turn = selfplay.parse_fen(fen)
-        return Position(x, o, turn)
+        return Position(x, o, turn, bl)
+
+    def __eq__(self, other):
+        return isinstance(other, Position) and (self.x, self.o, self.turn, self.blockers) == (
+            other.x, other.o, other.turn, other.blockers)
+
+    def copy(self):
+        return Position(self.x, self.o, self.turn, self.blockers)
 
     def fen(self):
-        """FEN in the reference's dialect (ataxx_rules.py fen(): ranks 7..1, x/o/digits, side to move)."""
+        """FEN in the reference's dialect (ataxx_rules.py fen(): ranks 7..1, x/o/digits, side to move), walls as '-', the
+        character selfplay.parse_fen and the reference's parser read (cpp/ataxx.cpp:14-90)."""
         rows = []
         for r in range(6, -1, -1):
             row, run = "", 0
             for f in range(7):
                 bit = 1 << (f + 7 * r)
-                ch = "x" if self.x & bit else ("o" if self.o & bit else None)
+                ch = "x" if self.x & bit else ("o" if self.o & bit else ("-" if self.blockers & bit else None))
                 if ch is None:
                     run += 1
                 else:
@@ -88,7 +95,7 @@ class Position:
         return link.pack_board(self.x, self.o, self.turn)
 
     def legal_moves(self):
-        moves, counts, results = link.rules_batch(self.packed().reshape(1, 2), 0)
+        moves, counts, results = link.rules_batch(self.packed().reshape(1, 2), self.blockers)
         return [int(m) for m in moves[0, :counts[0]]], int(results[0])
 
     def move(self, mv):
@@ -98,7 +105,8 @@ class Position:
     def __str__(self):
         rows = []
         for r in range(6, -1, -1):
-            rows.append(" ".join("X" if (self.x >> (f + 7 * r)) & 1 else ("O" if (self.o >> (f + 7 * r)) & 1 else ".")
+            rows.append(" ".join("X" if (self.x >> (f + 7 * r)) & 1 else ("O" if (self.o >> (f + 7 * r)) & 1 else
+                                                                          ("-" if (self.blockers >> (f + 7 * r)) & 1 else "."))
                                  for f in range(7)))
         return "\n".join(rows)
 
@@ -123,18 +131,18 @@ def find_path(root, target, successors, max_plies=2):
 
 
 class GpuSuccessors:
-    """Move generator for find_path on the GPU rules, positions as (x, o, turn).  prefetch() generates the moves of many
-    positions with one rules call and one make-move call."""
+    """Move generator for find_path on the GPU rules, positions as (x, o, turn) on a board with the walls `blockers`.
+    prefetch() generates the moves of many positions with one rules call and one make-move call."""
 
-    def __init__(self):
-        self.known = {}
+    def __init__(self, blockers=0):
+        self.known, self.blockers = {}, blockers
 
     def prefetch(self, positions):
         todo = [p for p in dict.fromkeys(positions) if p not in self.known]
         if not todo:
             return
         boards = np.array([link.pack_board(*p) for p in todo], dtype=np.uint64)
-        moves, counts, results = link.rules_batch(boards, 0)
+        moves, counts, results = link.rules_batch(boards, self.blockers)
         rows = [(i, int(m)) for i in range(len(todo)) if results[i] == 0 for m in moves[i, :counts[i]]]
         after = link.makemove_batch(boards[[i for i, _ in rows]], np.array([m for _, m in rows], dtype=np.uint16)) if rows else []
         for p in todo:
@@ -189,6 +197,7 @@ class Searcher:
         self.last_note = None     # why the last search was shorter than asked, or None
         self.engine = None        # the session's engine (reuse_tree)
         self.root = None          # (x, o, turn) the session engine's tree is rooted at; None: no tree to keep
+        self.root_blockers = 0    # the walls the session engine was created with: another mask, another engine
 
     def time_cap(self):
         """Visit cap of a time-controlled search: grows with the leaves per iteration, up to the engine's limit."""
@@ -206,15 +215,26 @@ class Searcher:
             self.engine = None
         self.root = None
 
+    def _random_symmetry_on(self, pos):
+        """May the engine of this search evaluate under a random symmetry?  Not on walls that are not their own image under
+        all 8: the search then runs without it and last_note says so, in the engine's words."""
+        if self.random_symmetry and not selfplay.symmetric_blockers(pos.blockers):
+            self.last_note = "the random symmetry is " + selfplay.symmetry_refusal(pos.blockers)
+            return False
+        return self.random_symmetry
+
     def _session_engine(self, pos):
+        if self.engine is not None and self.root_blockers != pos.blockers:
+            self.close()   # an engine keeps one wall mask: a position on another board starts a fresh engine and tree
         if self.engine is None:
             # visits = the engine's limit: no move ever comes due on the device
             cfg = link.Config(games=1, visits=self.MAX_VISITS, max_plies=400, edges_per_node=96, c_puct=1.0,
                               dirichlet_alpha=0.15, dirichlet_weight=0.0, start_turn=pos.turn, seed=random.getrandbits(63),
-                              start_x=pos.x, start_o=pos.o, blockers=0,
+                              start_x=pos.x, start_o=pos.o, blockers=pos.blockers,
                               flags=link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR | self.extra_flags)
             self.engine = link.Engine(cfg)
-            if self.random_symmetry:
+            self.root_blockers = pos.blockers
+            if self._random_symmetry_on(pos):
                 self.engine.set_random_symmetry(True)
             if self.parallel_leaves > 1:
                 self.engine.set_leaf_batch(self.parallel_leaves, self.virtual_loss)
@@ -228,7 +248,7 @@ class Searcher:
         target = (pos.x, pos.o, pos.turn)
         path = None
         if self.root is not None:
-            successors = GpuSuccessors()
+            successors = GpuSuccessors(pos.blockers)
             successors.prefetch([child for _, child in successors(self.root)])
             path = find_path(self.root, target, successors)
         for move in path or []:
@@ -251,6 +271,7 @@ class Searcher:
         limit = self.MAX_VISITS
         target = limit if visits is None else min(inherited + visits, limit)
         self.last_note = None
+        self._random_symmetry_on(pos)   # (the session engine was made without it on asymmetric walls: every search says so)
         if visits is not None and inherited + visits > limit:
             self.last_note = "search shortened to %d of %d visits: %d inherited, the tree holds %d" % (
                 target - inherited, visits, inherited, limit)
@@ -303,12 +324,12 @@ class Searcher:
         cap = visits if visits is not None else self.TIME_CAP_VISITS
         cfg = link.Config(games=1, visits=cap + 1, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
                           dirichlet_weight=0.0, start_turn=pos.turn, seed=random.getrandbits(63), start_x=pos.x,
-                          start_o=pos.o, blockers=0,
+                          start_o=pos.o, blockers=pos.blockers,
                           flags=link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR | self.extra_flags)
         eng = link.Engine(cfg)
         start = time.time()
         try:
-            if self.random_symmetry:
+            if self._random_symmetry_on(pos):
                 eng.set_random_symmetry(True)
             if visits is not None:
                 eng.run(self.net, 1 + visits, self.dtype)  # root evaluation + `visits` steps
@@ -337,14 +358,15 @@ class Searcher:
         target = visits if visits is not None else self.time_cap()
         cfg = link.Config(games=1, visits=target, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
                           dirichlet_weight=0.0, start_turn=pos.turn, seed=random.getrandbits(63), start_x=pos.x,
-                          start_o=pos.o, blockers=0, flags=link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR | self.extra_flags)
+                          start_o=pos.o, blockers=pos.blockers,
+                          flags=link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR | self.extra_flags)
         eng = link.Engine(cfg)
         start = time.time()
         try:
             eng.set_leaf_batch(K, self.virtual_loss)
             if self.solver:
                 eng.set_solver(True)
-            if self.random_symmetry:
+            if self._random_symmetry_on(pos):
                 eng.set_random_symmetry(True)
             eng.run(self.net, 1, self.dtype)  # the root evaluation
             rv = 0
@@ -487,7 +509,8 @@ class Session:
         else:
             budget_ms = max(int(rest) - self.safety_ms, 1)
             move = self.searcher.genmove(self.position, seconds=budget_ms * 1e-3)
-        speed = self.searcher.last_steps / self.searcher.last_seconds
+        # (no search yet: a session whose first `go` meets a position without a move)
+        speed = self.searcher.last_steps / self.searcher.last_seconds if self.searcher.last_seconds else 0.0
         lines = ["info speed %f nps" % (speed,)]
         if getattr(self.searcher, "last_note", None):
             lines.append("info string %s" % (self.searcher.last_note,))

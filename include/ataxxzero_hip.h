@@ -657,6 +657,14 @@ int azh_format_record_json(const uint32_t *rec, int64_t words, int32_t with_ids,
  * ones; with thousands of games in flight that bias is no longer slight, and uid order removes it (the first N
  * lines are the first N games started).  Call before the first drain. */
 int azh_engine_set_emit_order(azh_engine *e, int by_uid);
+/* on != 0: every line azh_engine_drain_json writes gains one key in front, "blockers":[...] — the engine's blockers mask as
+ * the ascending list of wall cells in the index the line's boards use, x + 7 y with y = 0 at rank 7 ([] for no walls; the
+ * start position of the self-play generator gives [17,23,25,31]).  The ring record does not change, and a line with the key's
+ * bytes taken out is the line written without it.  Off by default.  Takes effect for records fetched after the call. */
+int azh_engine_set_record_blockers(azh_engine *e, int on);
+/* azh_format_record_json with that key written from `blockers` (bit = file + 7 * rank; bits beyond the 49 cells: -1). */
+int azh_format_record_json_blockers(const uint32_t *rec, int64_t words, int32_t with_ids, uint64_t blockers, char *buf,
+                                    int64_t cap, int64_t *used);
 /* Play at most `games` games (uids 0 .. games - 1) and then stop searching: a slot whose next game would be past the
  * limit goes idle, the batch thins out as the last games end.  For a generator that was given a target count: in uid
  * order line N appears once the slowest of the first N games has ended, and without a limit every other slot meanwhile
@@ -685,7 +693,8 @@ int azh_engine_set_game_limit(azh_engine *e, int64_t games);
  * minibatch from it straight into the trainer's tensors: features [n][7][7][4], policy [n][7][7][17], value [n][1], f32,
  * bit for bit what the host pipeline (training.make_minibatch_reference; the reference's train.py:43-77) builds from the
  * same games for the same draws: plane 0 ones, plane 1 the mover's stones (the mover is 1 + ply % 2), plane 2 the
- * opponent's, plane 3 zeros, the board under symmetry s (bit 0 mirrors x, bit 1 mirrors y, bit 2 then transposes); each
+ * opponent's, plane 3 zeros (the game's walls where it has a mask: "Walls" below), the board under symmetry s (bit 0 mirrors
+ * x, bit 1 mirrors y, bit 2 then transposes); each
  * weight at azh_symmetry_policy_index(s, index); the value z = +-1 (result == mover), or with value_blend = L != 0 and a
  * game that has values (1 - L) * z + L * v in double, in that order, rounded once to f32.
  * The host keeps a mirror of the per-game words and the ply flags (a few bytes per ply) and checks every draw against it:
@@ -753,13 +762,35 @@ int azh_samples_draw(uint64_t seed, uint32_t step, uint32_t sample, int64_t firs
 /* Waits for the device and returns how many samples of azh_samples_draw_gather have failed since the store was created. */
 int azh_samples_status(azh_samples *s, int64_t *failed);
 
+/* Walls.  The store keeps one u64 blockers mask per game in the ring record's bit layout (bit = file + 7 * rank), 0 for a game
+ * that came without one, in a device array [cap_games] that is allocated when the first game with walls arrives: until then
+ * the kernels are handed a null pointer and every output is what it was.  With a mask, feature plane 3 of a sample holds 1.0
+ * on the wall cells, under the sample's symmetry like planes 1 and 2 (training.make_minibatch_reference with an entry's
+ * "blockers").  The siblings below take the masks; the calls above are the siblings with no walls.
+ *  - azh_samples_add_games_blockers: game_blockers [n_games], or NULL.  -2, nothing added, for a mask with bits beyond the 49
+ *    cells and for a game one of whose plies has a stone on a wall cell (the game is named).
+ *  - azh_samples_pack_records_blockers / azh_samples_add_records_blockers: `blockers` is the mask of the engine that wrote the
+ *    records; game_blockers [games] (or NULL) receives it per game.  The same two refusals, before anything is written.
+ *  - azh_samples_game_blockers: the host mirror of the masks, blockers [games]. */
+int azh_samples_add_games_blockers(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies,
+                                   const uint64_t *boards, const uint8_t *ply_flags, const double *values,
+                                   const int32_t *target_start, const uint16_t *target_index, const float *target_weight,
+                                   const uint64_t *game_blockers);
+int azh_samples_pack_records_blockers(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts, uint32_t *games,
+                                      uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
+                                      uint16_t *target_index, float *target_weight, uint64_t *game_blockers);
+int azh_samples_add_records_blockers(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers);
+int azh_samples_game_blockers(const azh_samples *s, uint64_t *blockers);
+
 /* ------------------------------------------------------------------ policy surprise weighting
  * (an extension of the store; with none of these called, every launch and every draw above is what it was.)
  *
  * The SURPRISE of a stored ply is KL(target || prior), the prior being a net's policy for the mover's view of the stored
  * position (the mover is 1 + ply % 2; the boards go to the tower as (mover, opponent), the orientation the engine feeds it).
  * With l the net's 833 f32 logits, `legal` the position's moves in the device movegen's order (jumps by ascending
- * (from, to), then clones ascending; no blockers) mapped by the engine's move -> policy index map:
+ * (from, to), then clones ascending; no blockers) mapped by the engine's move -> policy index map — for a game stored with a
+ * wall mask, `legal` = the position's moves from wave_movegen with the game's blockers, and the tower is shown that mask as
+ * its blocker plane:
  *   mx = max of l over legal;  S = sum over legal of det_expf(l_j - mx);  log p_t = (l_t - mx) - det_logf(S);
  *   KL = sum over the ply's targets with weight w_t > 0 and t legal of  w_t * (det_logf(w_t) - log p_t).
  * Everything is f32, every operation a single IEEE one.  BOTH sums run in the engine's 64-lane order: term j (the j-th legal
@@ -776,7 +807,8 @@ int azh_samples_surprise_logits(azh_samples *s, int64_t first_ply, int64_t n_pli
 /* The same for every ply of games [first_game, first_game + n_games), the logits coming from `net` in `dtype`: in chunks of
  * at most 16384 plies (azh_samples_set_surprise_chunk: another size, for tests; 0 restores the default) a small kernel packs
  * the boards, the tower runs, and the surprise kernel runs behind it on the store's stream.  kl_out: one f32 per ply of those
- * games. */
+ * games.  A chunk never spans two wall masks: the chunks are cut where the mask changes from one game to the next as well as
+ * at the chunk size (planned on the host from its mirror); azh_samples_surprise_logits cuts its kernel launches the same way. */
 int azh_samples_surprise(azh_samples *s, azh_net *net, int dtype, int64_t first_game, int64_t n_games, float *kl_out,
                          int64_t *illegal_out);
 int azh_samples_set_surprise_chunk(azh_samples *s, int plies);
@@ -785,10 +817,16 @@ int azh_samples_set_surprise_chunk(azh_samples *s, int plies);
 int azh_samples_surprise_ms(const azh_samples *s, float *ms);
 /* The legal moves of a position as policy indices in the order above -> index_out [up to 833], *n_out.  Host arithmetic. */
 int azh_samples_legal(uint64_t mover, uint64_t opponent, uint16_t *index_out, int32_t *n_out);
+/* The same on a board with walls: no move goes onto a cell of `blockers`. */
+int azh_samples_legal_blockers(uint64_t mover, uint64_t opponent, uint64_t blockers, uint16_t *index_out, int32_t *n_out);
 /* One ply's surprise restated on the host: *kl_out is the stored value (the "stored as 0" rule applied), *illegal_out (or
  * NULL) this ply's count.  Host arithmetic only. */
 int azh_samples_surprise_host(const float *logits833, const uint16_t *legal_index, int n_legal, const uint16_t *target_index,
                               const float *target_weight, int n_targets, float *kl_out, int32_t *illegal_out);
+/* The same with `legal` found here: azh_samples_legal_blockers of the position. */
+int azh_samples_surprise_host_blockers(const float *logits833, uint64_t mover, uint64_t opponent, uint64_t blockers,
+                                       const uint16_t *target_index, const float *target_weight, int n_targets, float *kl_out,
+                                       int32_t *illegal_out);
 
 /* Weighted ply draws.  w [plies of games first_game .. first_game + n_games): one weight per ply, finite and >= 0.  Per
  * CANDIDATE ply the store keeps q = (u32)floor((double)w * 65536 + 0.5) as a running sum per game, cum[first ply + k] = q_0 +

@@ -60,6 +60,8 @@ def generate(args, n, out):
         return None
     cmd = [sys.executable, os.path.join(ROOT, "accelerated_generate_games.py"), "--network", model_path(args.prefix, n),
            "--output-games", path, "--visits", str(args.visits)] + args.generator_flags
+    if args.start_fen is not None:       # the games are played on that board and say so: train.py then shows the net its walls
+        cmd += ["--start-fen", args.start_fen, "--record-blockers"]
     gen_log = os.path.join(args.prefix, "generator-%03i.log" % n)
     t0 = time.time()
     with open(gen_log, "w") as lf:
@@ -119,6 +121,8 @@ def arena(args, k, out, other=1):
            "--game-count", str(args.arena_games), "--seed", str(args.seed + 31 * k + other)]
     if args.arena_opening_depth > 0:
         cmd += ["--opening-depth", str(args.arena_opening_depth)]
+    if args.start_fen is not None:
+        cmd += ["--start-fen", args.start_fen]
     t0 = time.time()
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
     if res.returncode != 0:
@@ -183,6 +187,9 @@ def main():
     ap.add_argument("--arena-opening-depth", type=int, default=0,
                     help="matches start from random openings of this many plies (uai_ringmaster.py --opening-depth): two "
                          "near-deterministic nets otherwise shuffle to the 400-ply cut game after game")
+    ap.add_argument("--start-fen", default=None, metavar="FEN",
+                    help="the whole loop on this start position, walls ('-') included: the generator gets it together with "
+                         "--record-blockers, the ringmaster gets it too (default: each tool's own start position)")
     ap.add_argument("--anchor", type=int, default=0, help="> 1: also play every later generation against model-<anchor>")
     ap.add_argument("--blocks", type=int, default=12)
     ap.add_argument("--filters", type=int, default=128)

@@ -11,6 +11,9 @@ instead of the game result z alone.  --device-samples keeps the games in device 
 minibatch into the trainer's tensors (the same minibatches; needs a GPU); --device-draws also draws the samples there.
 --surprise-weight L draws a training game's plies by policy surprise, KL(policy target || prior of the --old-path network):
 a share L of each game's sampling mass in proportion to it, the rest uniformly (implies --device-draws).
+Entries written with the generator's --record-blockers carry "blockers", the wall cells of their board: every path then shows
+them to the net in feature plane 3, and the surprise is measured over the moves the walls leave (no flag; without the key
+nothing changes).
 """
 from ataxxzero_amd import training
 from ataxxzero_amd.cli import flag, parse, switch

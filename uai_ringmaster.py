@@ -57,6 +57,9 @@ if __name__ == "__main__":
                         "search's move in 100 %% of test positions, bf16 in 96 %% (DESIGN.md section 5); bf16 is 3-6 %% faster",
              default="f16", choices=["bf16", "f16", "f32"]),
         flag("--seed", "Philox seed (extension)", type=int, default=selfplay.DEFAULT_SEED),
+        flag("--start-fen", "the position every game starts from, walls ('-') included (extension; default: the reference's "
+                            "board without walls): both engines search on that board, and --opening-depth plays its random "
+                            "plies on it", default=selfplay.START_FEN_PLAIN, metavar="FEN"),
     ])
     print("Options:", args)
     if not args.engine or len(args.engine) != 2:
@@ -80,7 +83,9 @@ if __name__ == "__main__":
                         seed=args.seed,
                         # the reference stops a game once ply_number > --max-plies (uai_ringmaster.py:139-140): N + 1 moves
                         max_plies=args.max_plies + 1 if args.max_plies is not None else 400,
-                        opening_depth=args.opening_depth)
+                        opening_depth=args.opening_depth,
+                        # (another board is an option of its own: without the flag the call is the one it has always been)
+                        **({"start_fen": args.start_fen} if args.start_fen != selfplay.START_FEN_PLAIN else {}))
     names = {"a": " ".join(engines[0]), "b": " ".join(engines[1])}
     wins = {"a": 0, "b": 0}
     annulled = 0
