@@ -12,6 +12,7 @@
 
 #define AZH_NO_REFERENCE_ABI
 #include "../../include/ataxxzero_hip.h"
+#include "record.h"
 
 // Record the message for azh_last_error() and return `code`.
 int azh_fail(int code, const char *fmt, ...);
@@ -26,6 +27,12 @@ int azh_require_device(void);
             return azh_fail(-100 - (int)_e, "%s failed at %s:%d: %s", #expr, __FILE__,     \
                             __LINE__, hipGetErrorString(_e));                               \
     } while (0)
+
+// json.cpp: finished-game records (record.h) -> game lines.  Only azh_record_well_formed takes words nobody has checked.
+bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plies, const char **why);
+std::string azh_format_game_json(const uint32_t *rec, bool with_ids);
+std::string azh_format_game_json_blockers(const uint32_t *rec, bool with_ids, uint64_t blockers);
+uint64_t azh_ply_target(azh::PlyView ply, std::vector<std::pair<std::string, uint32_t>> &ents);
 
 // net_kernels.hip
 int azh_net_launch(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,

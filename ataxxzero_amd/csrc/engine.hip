@@ -1343,10 +1343,6 @@ using namespace azh;
 
 // ------------------------------------------------------------------ host
 
-std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_ids);  // json.cpp
-std::string azh_format_game_json_blockers(const uint32_t *rec, size_t words, bool with_ids, uint64_t blockers);  // json.cpp
-bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plies, const char **why);
-
 // The leaf buffers of EngineParams as one value.  The engine keeps two sets, its own G-slot one and the G K-slot one of the
 // leaf-parallel search, and P points at one of them.
 struct LeafBuffers {
@@ -2753,7 +2749,7 @@ static void format_staged(azh_engine *e)
     size_t pos = 0;
     // (two fetches may sit behind each other in the staging buffer: a fetch that ended in a record cut off by a full
     // ring is followed by the next one's first header, which the scan finds again at the next magic word)
-    while (pos + 8 <= host.size()) {
+    while (pos + REC_HDR_WORDS <= host.size()) {
         if (host[pos] != RING_MAGIC) {
             pos++;
             continue;
@@ -2764,19 +2760,18 @@ static void format_staged(azh_engine *e)
             pos++;
             continue;
         }
-        const size_t words = host[pos + 5];
-        order.emplace_back(host[pos + 2], pos);
-        pos += words;
+        const RecordView rec{host.data() + pos};
+        order.emplace_back(rec.uid(), pos);
+        pos += rec.words();
     }
     std::sort(order.begin(), order.end());
     const bool ids = (e->P.flags & AZH_FLAG_TWO_NETS) != 0;
     for (auto &o : order) {
-        const uint32_t *rec = host.data() + o.second;
-        const bool dropped = (rec[7] & 3u) == 1;
-        std::string line = dropped                ? std::string()
-                           : e->record_blockers ? azh_format_game_json_blockers(rec, rec[5], ids, e->P.blockers & BOARD_MASK)
-                                                : azh_format_game_json(rec, rec[5], ids);
-        if ((rec[7] & 3u) == 2 && !ids)
+        const RecordView rec{host.data() + o.second};
+        std::string line = rec.dropped()        ? std::string()
+                           : e->record_blockers ? azh_format_game_json_blockers(rec.w, ids, e->P.blockers & BOARD_MASK)
+                                                : azh_format_game_json(rec.w, ids);
+        if (rec.loaded() && !ids)
             line.clear();  // a game that began at a loaded position: record drained and formatted like any other
                            // (the measured path does the same work per finished ply), but it is not a whole game.
                            // (The arena hands such games out: a match from given openings — uai_ringmaster.py:185-196 —

@@ -10,22 +10,12 @@
 
 #include "azh_device.h"
 #include "azh_host.h"
+#include "record.h"
 
 namespace azh {
 
-constexpr int REC_HDR_WORDS = 8;
-constexpr int REC_MAXD = 256;
-constexpr int REC_STRIDE_WORDS = REC_HDR_WORDS + REC_MAXD;
-constexpr u32 RING_MAGIC = 0x415A4847u;  // "AZHG"
-constexpr u32 REC_KIND_PLAYOUT_CAP = 4u;  // header word 7, beside its kind in bits 0-1: the game was played with the playout cap on
-                                          // (word 5 of every ply: 1 = FULL), and its line carries "full"
-constexpr u32 REC_KIND_FORCED = 8u;       // beside it: the game was played with forced playouts on — the visit counts of the plies
-                                          // the mode acts on are the pruned ones (json.cpp ignores the bit)
-constexpr u32 REC_KIND_VALUES = 16u;      // the game was played with the search value recorded (azh_engine_set_resign): word 5 of
-                                          // every ply = the bits of q (sign bit: FULL), and its line carries "values"
-constexpr u32 REC_KIND_RESIGNED = 32u;    // the game ended by resignation: its line carries "resigned"
-constexpr u32 REC_KIND_GUMBEL = 64u;      // the game was played with the Gumbel root search on: the counts of every ply are the
-                                          // improved policy in units of 1/65535 of its greatest entry (json.cpp ignores the bit)
+// (the finished-game record's layout, RING_MAGIC and the REC_* constants: record.h)
+constexpr int REC_STRIDE_WORDS = REC_HDR_WORDS + REC_MAXD;  // a ply as it waits on the device for its game to end
 constexpr int NSTAT = AZH_STAT_COUNT;
 constexpr int BFS_QL = 384;  // re-root frontier entries kept in LDS; later ones spill to bfs_spill in HBM
 

@@ -205,28 +205,36 @@ static void append_double(double v, std::string &out)
     }
 }
 
-// rec: ring record (engine.hip k_advance): 8-word header {magic, slot, uid, plies,
-// result, words, random_ply + 1 (0 = none), kind (1 dropped, 2 partial; | 4: playout cap on; | 8: forced playouts on, the
-// counts of the plies it acts on are the pruned ones — nothing here depends on it)} then per ply {x lo, x hi,
-// o lo, o hi, move | nd << 16, full (playout cap: 1 = searched in full), nd x (move | visits << 16)}.
-// kind | 16: the game was played with the search value recorded (azh_engine_set_resign): word 5 of a ply is the f32 bits of
-// q = W_b / n_b of the most visited root edge (in [0, 1], for the mover) with the sign bit = searched in full, and the line
-// gains "values" (2 q - 1 as a double; a q that is not finite reads 0); | 32: the game ended by resignation, the line gains
-// "resigned" (the side that resigned, 3 - result: the mover of the last ply); | 64: the game was played with the Gumbel root
-// search on (azh_engine_set_gumbel): the counts are the improved policy in units of 1/65535 of its greatest entry, over every
-// root move — nothing here depends on it.
-// with_ids (arena): two extra keys, "slot" and "uid", so the caller can tell which net had x.
-std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_ids)
+// The policy target of one ply as the line's "dists" object holds it: (key text, move | count << 16) per recorded target,
+// sorted — nlohmann writes an object's keys sorted, and parsing the line keeps that order — into `ents`; returns the counts'
+// total.  A target's share is count / total as doubles (0 where the total is 0): the line writes it, the sample store
+// (samples.hip, azh_samples_pack_records) narrows it to f32, and so a packed target equals a parsed line bit for bit.
+uint64_t azh_ply_target(azh::PlyView ply, std::vector<std::pair<std::string, uint32_t>> &ents)
 {
-    const uint32_t plies = rec[3], result = rec[4];
+    ents.clear();
+    uint64_t total = 0;
+    for (uint32_t j = 0; j < ply.targets(); j++) {
+        const uint32_t e = ply.target(j);
+        ents.emplace_back(std::string(), e);
+        move_string(e & 0xFFFFu, ents.back().first);
+        total += e >> 16;
+    }
+    std::sort(ents.begin(), ents.end());
+    return total;
+}
+
+// One well-formed record (record.h; azh_record_well_formed has walked it) -> its line.
+// with_ids (arena): two extra keys, "slot" and "uid", so the caller can tell which net had x.
+std::string azh_format_game_json(const uint32_t *words, bool with_ids)
+{
+    const azh::RecordView rec{words};
+    const uint32_t result = rec.result();
     std::string boards = "[", dists = "[", moves = "[", full = "[", values = "[";
-    const bool valued = (rec[7] & 16u) != 0;  // REC_KIND_VALUES: word 5 of a ply = bits of q | full << 31
-    const bool capped = (rec[7] & 4u) != 0;  // playout cap (engine_device.h REC_KIND_PLAYOUT_CAP): word 5 of a ply = searched in full
-    size_t pos = 8;
-    for (uint32_t p = 0; p < plies && pos + 6 <= words; p++) {
-        const uint64_t x = (uint64_t)rec[pos] | ((uint64_t)rec[pos + 1] << 32);
-        const uint64_t o = (uint64_t)rec[pos + 2] | ((uint64_t)rec[pos + 3] << 32);
-        const uint32_t mv = rec[pos + 4] & 0xFFFFu, nd = rec[pos + 4] >> 16;
+    const bool valued = rec.valued(), capped = rec.capped();
+    std::vector<std::pair<std::string, uint32_t>> ents;
+    azh::PlyView ply = rec.first_ply();
+    for (uint32_t p = 0; p < rec.plies(); p++, ply = ply.next()) {
+        const uint64_t x = ply.x(), o = ply.o();
         if (p) {
             boards += ',';
             dists += ',';
@@ -234,13 +242,9 @@ std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_id
             full += ',';
             values += ',';
         }
-        full += (valued ? rec[pos + 5] >> 31 : rec[pos + 5]) ? '1' : '0';
-        if (valued) {
-            const uint32_t qb = rec[pos + 5] & 0x7FFFFFFFu;
-            float q;
-            memcpy(&q, &qb, 4);
-            append_double(std::isfinite(q) ? 2.0 * (double)q - 1.0 : 0.0, values);
-        }
+        full += ply.full(valued) ? '1' : '0';
+        if (valued)
+            append_double(ply.value(true), values);
         boards += '[';
         for (int y = 0; y < 7; y++)
             for (int xx = 0; xx < 7; xx++) {
@@ -251,18 +255,9 @@ std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_id
             }
         boards += ']';
         moves += '"';
-        move_string(mv, moves);
+        move_string(ply.move(), moves);
         moves += '"';
-        uint64_t total = 0;
-        std::vector<std::pair<std::string, uint32_t>> ents;
-        for (uint32_t j = 0; j < nd && pos + 6 + j < words; j++) {
-            const uint32_t e = rec[pos + 6 + j];
-            std::string key;
-            move_string(e & 0xFFFFu, key);
-            ents.emplace_back(key, e >> 16);
-            total += e >> 16;
-        }
-        std::sort(ents.begin(), ents.end());
+        const uint64_t total = azh_ply_target(ply, ents);
         dists += '{';
         for (size_t j = 0; j < ents.size(); j++) {
             if (j)
@@ -270,20 +265,19 @@ std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_id
             dists += '"';
             dists += ents[j].first;
             dists += "\":";
-            append_double(total ? (double)ents[j].second / (double)total : 0.0, dists);
+            append_double(total ? (double)(ents[j].second >> 16) / (double)total : 0.0, dists);
         }
         dists += '}';
-        pos += 6 + nd;
     }
     std::string out = "{\"boards\":" + boards + "],\"dists\":" + dists + (capped ? "],\"full\":" + full : std::string()) +
                       "],\"moves\":" + moves + "],\"result\":";
-    if (rec[6])  // ONE_RANDOM_MOVE games (cpp/self_play_client.cpp:517); keys stay sorted as nlohmann emits them
-        out = out.substr(0, out.size() - 9) + "\"random_ply\":" + std::to_string(rec[6] - 1) + ",\"result\":";
-    if (rec[7] & 32u)  // REC_KIND_RESIGNED
+    if (rec.random_ply_plus_1())  // ONE_RANDOM_MOVE games (cpp/self_play_client.cpp:517); keys stay sorted as nlohmann emits them
+        out = out.substr(0, out.size() - 9) + "\"random_ply\":" + std::to_string(rec.random_ply_plus_1() - 1) + ",\"result\":";
+    if (rec.resigned())
         out = out.substr(0, out.size() - 9) + "\"resigned\":" + std::to_string(3u - result) + ",\"result\":";
     out += std::to_string(result);
     if (with_ids)
-        out += ",\"slot\":" + std::to_string(rec[1]) + ",\"uid\":" + std::to_string(rec[2]);
+        out += ",\"slot\":" + std::to_string(rec.slot()) + ",\"uid\":" + std::to_string(rec.uid());
     if (valued)
         out += ",\"values\":" + values + "]";
     out += '}';
@@ -293,7 +287,7 @@ std::string azh_format_game_json(const uint32_t *rec, size_t words, bool with_id
 // The same line with one more key in front, "blockers":[...]: the wall cells of `blockers` (bit = file + 7 * rank) in ascending
 // order of the index the line's boards use, x + 7 * y with y = 0 at rank 7.  "blockers" sorts before "boards", so the key
 // leads the object as nlohmann's sorted keys would have it; taking its bytes out gives azh_format_game_json's line.
-std::string azh_format_game_json_blockers(const uint32_t *rec, size_t words, bool with_ids, uint64_t blockers)
+std::string azh_format_game_json_blockers(const uint32_t *rec, bool with_ids, uint64_t blockers)
 {
     std::string key = "\"blockers\":[";
     bool first = true;
@@ -305,7 +299,7 @@ std::string azh_format_game_json_blockers(const uint32_t *rec, size_t words, boo
             first = false;
         }
     key += "],";
-    std::string line = azh_format_game_json(rec, words, with_ids);
+    std::string line = azh_format_game_json(rec, with_ids);
     line.insert(1, key);
     return line;
 }
@@ -320,25 +314,28 @@ bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plie
     if (!why)
         why = &dummy;
     *why = "not a finished-game record";
-    if (avail < 8 || rec[0] != 0x415A4847u /* "AZHG", engine.hip RING_MAGIC */ || rec[5] < 8 || (size_t)rec[5] > avail)
+    using namespace azh;
+    if (avail < REC_HDR_WORDS || rec[REC_MAGIC] != RING_MAGIC || rec[REC_WORDS] < REC_HDR_WORDS || (size_t)rec[REC_WORDS] > avail)
         return false;
-    if (rec[7] == 1)  // the marker a dropped game leaves: a header and nothing else
-        return rec[5] == 8;
+    const uint32_t kind = rec[REC_KIND], words = rec[REC_WORDS];
+    if (kind == REC_KIND_DROPPED)  // the marker a dropped game leaves: a header and nothing else
+        return words == REC_HDR_WORDS;
     *why = "header fields out of range";
-    if ((rec[7] & ~124u) > 2 || (rec[7] & 3u) == 1 || rec[4] > 2 || (max_plies && rec[3] > max_plies))
+    if ((kind & ~REC_KIND_MODES) > REC_KIND_LOADED || (kind & REC_KIND_MASK) == REC_KIND_DROPPED || rec[REC_RESULT] > 2 ||
+        (max_plies && rec[REC_PLIES] > max_plies))
         return false;
     *why = "a ply runs past the record's words";
-    size_t pos = 8;
-    for (uint32_t p = 0; p < rec[3]; p++) {
-        if (pos + 6 > rec[5])
+    size_t pos = REC_HDR_WORDS;
+    for (uint32_t p = 0; p < rec[REC_PLIES]; p++) {
+        if (pos + REC_PLY_WORDS > words)
             return false;
-        const uint32_t nd = rec[pos + 4] >> 16;
-        if (nd > 256 || pos + 6 + nd > rec[5])
+        const uint32_t nd = PlyView{rec + pos}.targets();
+        if (nd > (uint32_t)REC_MAXD || pos + REC_PLY_WORDS + nd > words)
             return false;
-        pos += 6 + nd;
+        pos += REC_PLY_WORDS + nd;
     }
     *why = "the plies do not fill the record";
-    return pos == rec[5];
+    return pos == words;
 }
 
 // One record -> its line, for callers that hold records themselves and for the CPU-side test of the format: host code only,
@@ -350,20 +347,22 @@ static int format_record(const char *who, const uint32_t *rec, int64_t words, in
         return azh_fail(-1, "%s: null argument", who);
     *used = 0;
     const char *why = nullptr;
-    if (words < 8 || !azh_record_well_formed(rec, (size_t)words, 0u, &why))
+    const azh::RecordView view{rec};
+    const bool header = words >= azh::REC_HDR_WORDS;
+    if (!header || !azh_record_well_formed(rec, (size_t)words, 0u, &why))
         return azh_fail(-2, "%s: %s (%lld words handed over, header says %u words, %u plies)", who,
-                        why ? why : "not a finished-game record", (long long)words, words >= 8 ? rec[5] : 0u,
-                        words >= 8 ? rec[3] : 0u);
-    if (rec[7] == 1)
+                        why ? why : "not a finished-game record", (long long)words, header ? view.words() : 0u,
+                        header ? view.plies() : 0u);
+    if (view.dropped())
         return azh_fail(-2, "%s: the record is the marker of a dropped game, it has no line", who);
     // The kind bits this entry point has always taken are 2 .. 32; bit 6 (64: a game of the Gumbel root search, whose counts
     // are policy weights, not visits) is accepted by the engine's own drain alone — tests/test_resign_host.py pins 64 among
     // the kind bits a caller's record must not carry.
-    if (rec[7] & 64u)
+    if (view.gumbel())
         return azh_fail(-2, "%s: kind bit 64 (a game of the Gumbel root search) is formatted by "
                             "azh_engine_drain_json only", who);
-    const std::string line = keyed ? azh_format_game_json_blockers(rec, rec[5], with_ids != 0, blockers)
-                                   : azh_format_game_json(rec, rec[5], with_ids != 0);
+    const std::string line = keyed ? azh_format_game_json_blockers(rec, with_ids != 0, blockers)
+                                   : azh_format_game_json(rec, with_ids != 0);
     *used = (int64_t)line.size();
     if ((int64_t)line.size() > cap)
         return azh_fail(-6, "%s: the line needs %zu bytes, the buffer has %lld", who, line.size(), (long long)cap);

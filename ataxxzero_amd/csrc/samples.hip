@@ -15,8 +15,6 @@
 
 using namespace azh;
 
-bool azh_record_well_formed(const uint32_t *rec, size_t avail, uint32_t max_plies, const char **why);  // json.cpp
-
 namespace {
 
 constexpr int FEATURES = 196, POLICY = 833, SAMPLE_FLOATS = FEATURES + POLICY + 1;
@@ -281,18 +279,6 @@ bool bad_target(const uint16_t *index, const float *weight, size_t n)
     for (size_t j : order)
         sum += weight[j];
     return fabsf(1.f - sum) >= 1e-3f;
-}
-
-void move_text(uint32_t mv, std::string &out)  // the key of the move in the game line (json.cpp move_string)
-{
-    const int from = mv & 0xFF, to = (mv >> 8) & 0xFF;
-    out.clear();
-    if (from != to) {
-        out.push_back((char)('a' + from % 7));
-        out.push_back((char)('1' + from / 7));
-    }
-    out.push_back((char)('a' + to % 7));
-    out.push_back((char)('1' + to / 7));
 }
 
 bool board_move(uint32_t mv)  // a clone, or a jump over a distance of exactly two
@@ -599,26 +585,25 @@ extern "C" int azh_samples_pack_records_blockers(const uint32_t *rec, int64_t wo
         const char *why = nullptr;
         if (!azh_record_well_formed(rec + pos, (size_t)(words - pos), 0u, &why))
             return azh_fail(-2, "azh_samples_pack_records: word %lld: %s", (long long)pos, why ? why : "not a record");
-        const uint32_t *r = rec + pos;
-        pos += r[5];
-        if ((r[7] & 1u) || (r[7] & 3u) == 2)  // a dropped game's marker; a game begun at a loaded position: neither has a line
+        const RecordView r{rec + pos};
+        pos += r.words();
+        if (r.dropped() || r.loaded())  // a dropped game's marker; a game begun at a loaded position: neither has a line
             continue;
-        if (r[3] < 1 || r[3] > 0xFFFFu || r[6] > 0xFFFFu)
-            return azh_fail(-2, "azh_samples_pack_records: a game of %u plies with result %u and random_ply + 1 = %u", r[3], r[4], r[6]);
-        size_t at = 8;
-        for (uint32_t p = 0; p < r[3]; p++) {
-            const uint32_t nd = r[at + 4] >> 16;
-            if ((((uint64_t)r[at] | r[at + 2]) | (((uint64_t)r[at + 1] | r[at + 3]) << 32)) & blockers)
+        if (r.plies() < 1 || r.plies() > 0xFFFFu || r.random_ply_plus_1() > 0xFFFFu)
+            return azh_fail(-2, "azh_samples_pack_records: a game of %u plies with result %u and random_ply + 1 = %u", r.plies(),
+                            r.result(), r.random_ply_plus_1());
+        PlyView ply = r.first_ply();
+        for (uint32_t p = 0; p < r.plies(); p++, ply = ply.next()) {
+            if ((ply.x() | ply.o()) & blockers)
                 return azh_fail(-2, "azh_samples_pack_records: word %lld, ply %u: a stone stands on a wall cell of the "
-                                    "blockers mask %#llx", (long long)(r - rec), p, (unsigned long long)blockers);
-            for (uint32_t j = 0; j < nd; j++)
-                if (!board_move(r[at + 6 + j] & 0xFFFFu))
-                    return azh_fail(-2, "azh_samples_pack_records: target %#x is no clone and no jump", r[at + 6 + j] & 0xFFFFu);
-            n_targets += nd;
-            at += 6 + nd;
+                                    "blockers mask %#llx", (long long)(r.w - rec), p, (unsigned long long)blockers);
+            for (uint32_t j = 0; j < ply.targets(); j++)
+                if (!board_move(ply.target(j) & 0xFFFFu))
+                    return azh_fail(-2, "azh_samples_pack_records: target %#x is no clone and no jump", ply.target(j) & 0xFFFFu);
+            n_targets += ply.targets();
         }
         n_games++;
-        n_plies += r[3];
+        n_plies += r.plies();
     }
     counts[0] = n_games;
     counts[1] = n_plies;
@@ -631,53 +616,33 @@ extern "C" int azh_samples_pack_records_blockers(const uint32_t *rec, int64_t wo
                         (long long)cap_plies, (long long)cap_targets);
     int64_t g = 0, q = 0, t = 0;
     std::vector<std::pair<std::string, uint32_t>> ents;
-    std::string key;
     target_start[0] = 0;
     for (int64_t pos = 0; pos < words;) {
-        const uint32_t *r = rec + pos;
-        pos += r[5];
-        if ((r[7] & 1u) || (r[7] & 3u) == 2)
+        const RecordView r{rec + pos};
+        pos += r.words();
+        if (r.dropped() || r.loaded())
             continue;
-        const bool valued = (r[7] & 16u) != 0, capped = (r[7] & 4u) != 0;
+        const bool valued = r.valued(), capped = r.capped();
         games[4 * g] = (uint32_t)q;
-        games[4 * g + 1] = r[3];
-        games[4 * g + 2] = r[4] | (capped ? GAME_HAS_FULL : 0u) | (valued ? GAME_HAS_VALUES : 0u);
-        games[4 * g + 3] = r[6];
+        games[4 * g + 1] = r.plies();
+        games[4 * g + 2] = r.result() | (capped ? GAME_HAS_FULL : 0u) | (valued ? GAME_HAS_VALUES : 0u);
+        games[4 * g + 3] = r.random_ply_plus_1();
         if (game_blockers)
             game_blockers[g] = blockers;
         g++;
-        size_t at = 8;
-        for (uint32_t p = 0; p < r[3]; p++, q++) {
-            boards[2 * q] = (uint64_t)r[at] | ((uint64_t)r[at + 1] << 32);
-            boards[2 * q + 1] = (uint64_t)r[at + 2] | ((uint64_t)r[at + 3] << 32);
-            const uint32_t nd = r[at + 4] >> 16;
-            const bool full = (valued ? r[at + 5] >> 31 : r[at + 5]) != 0;
-            ply_flags[q] = capped && full ? AZH_SAMPLES_PLY_FULL : 0;  // (the device loop records no pass: a ply is a move)
-            double value = 0.0;
-            if (valued) {
-                const uint32_t bits = r[at + 5] & 0x7FFFFFFFu;
-                float qv;
-                memcpy(&qv, &bits, 4);
-                value = std::isfinite(qv) ? 2.0 * (double)qv - 1.0 : 0.0;
-            }
-            values[q] = value;
-            // the line's "dists" object is written with sorted keys, and parsing it keeps that order
-            ents.clear();
-            uint64_t total = 0;
-            for (uint32_t j = 0; j < nd; j++) {
-                const uint32_t e = r[at + 6 + j];
-                move_text(e & 0xFFFFu, key);
-                ents.emplace_back(key, e);
-                total += e >> 16;
-            }
-            std::sort(ents.begin(), ents.end());
+        PlyView ply = r.first_ply();
+        for (uint32_t p = 0; p < r.plies(); p++, q++, ply = ply.next()) {
+            boards[2 * q] = ply.x();
+            boards[2 * q + 1] = ply.o();
+            ply_flags[q] = capped && ply.full(valued) ? AZH_SAMPLES_PLY_FULL : 0;  // (the device loop records no pass: a ply is a move)
+            values[q] = ply.value(valued);
+            const uint64_t total = azh_ply_target(ply, ents);  // in the order of the line's "dists"
             for (const auto &e : ents) {
                 target_index[t] = (uint16_t)policy_index(e.second & 0xFFFFu);
                 target_weight[t] = total ? (float)((double)(e.second >> 16) / (double)total) : 0.f;
                 t++;
             }
             target_start[q + 1] = (int32_t)t;
-            at += 6 + nd;
         }
     }
     return 0;

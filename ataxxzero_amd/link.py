@@ -8,6 +8,7 @@ same argument order, bound to the GPU library instead of
 There is no CPU fallback: if the library is missing it is built with hipcc; if
 no MI355X is visible every compute call raises AzhError.
 """
+import collections
 import ctypes
 import os
 
@@ -305,6 +306,48 @@ def format_record_json(rec, with_ids=False, blockers=None):
         rc = call(buf, used)
     check(rc)
     return bytes(buf[:used.value])
+
+
+# The finished-game record, as csrc/record.h defines it and under its names: the header's words, then per ply 6 fixed words
+# {x lo, x hi, o lo, o hi, move | nd << 16, word 5} and nd x (move | count << 16).
+RECORD_MAGIC = 0x415A4847
+REC_MAGIC, REC_SLOT, REC_UID, REC_PLIES, REC_RESULT, REC_WORDS, REC_RANDOM_PLY_PLUS_1, REC_KIND = range(8)
+REC_HDR_WORDS, REC_PLY_WORDS, REC_MAXD = 8, 6, 256
+REC_KIND_MASK, REC_KIND_WHOLE, REC_KIND_DROPPED, REC_KIND_LOADED = 3, 0, 1, 2      # bits 0-1 of the kind word
+REC_KIND_PLAYOUT_CAP, REC_KIND_FORCED, REC_KIND_VALUES, REC_KIND_RESIGNED, REC_KIND_GUMBEL = 4, 8, 16, 32, 64
+REC_KIND_MODES = 124
+REC_PLY_FULL_BIT, REC_PLY_Q_BITS = 0x80000000, 0x7FFFFFFF                           # word 5 under REC_KIND_VALUES
+
+Record = collections.namedtuple("Record", "slot uid result kind plies words")
+
+
+def records(words, markers=False):
+    """The records of `words` (uint32, one record after the other, as Engine.staged_records returns them), one Record each:
+    slot, uid, result, the kind word, plies = [(move, word 5, {move: count}, (x, o))] and the record's own words (a view).
+    A dropped game's marker is left out unless `markers`.  Asserts the magic, that every record lies within `words` and that
+    its plies walk to its end exactly."""
+    pos = 0
+    while pos < len(words):
+        assert pos + REC_HDR_WORDS <= len(words) and words[pos] == RECORD_MAGIC, pos
+        slot, uid, n_plies, result, n, kind = (int(words[pos + i]) for i in (REC_SLOT, REC_UID, REC_PLIES, REC_RESULT,
+                                                                            REC_WORDS, REC_KIND))
+        assert REC_HDR_WORDS <= n <= len(words) - pos, (pos, n)
+        rec, plies, q = words[pos:pos + n], [], REC_HDR_WORDS
+        pos += n
+        if kind & REC_KIND_MASK == REC_KIND_DROPPED:
+            if not markers:
+                continue
+            n_plies = 0                      # (the marker's ply count is the dropped game's: it carries none of them)
+        for _ in range(n_plies):
+            assert q + REC_PLY_WORDS <= n, (uid, q, n)
+            x_lo, x_hi, o_lo, o_hi, head, word5 = (int(w) for w in rec[q:q + REC_PLY_WORDS])
+            q += REC_PLY_WORDS
+            targets = rec[q:q + (head >> 16)]
+            q += head >> 16
+            plies.append((head & 0xFFFF, word5, {int(w) & 0xFFFF: int(w) >> 16 for w in targets},
+                          (x_lo | x_hi << 32, o_lo | o_hi << 32)))
+        assert q == n, (uid, q, n)
+        yield Record(slot, uid, result, kind, plies, rec)
 
 
 def blockers_to_cells(mask):

@@ -648,7 +648,10 @@ int azh_engine_staged_records(azh_engine *e, uint32_t *buf, int64_t cap, int64_t
  * the digits its Grisu2 finds, plain decimals from 1e-4 up, d.ddde-XX below).  Host code only, usable without a device.
  * *used = bytes the line has; -6 if `cap` is smaller (nothing written), -2 if the words are not a well-formed record — or
  * carry kind bit 64 (azh_engine_set_gumbel): those records become lines in azh_engine_drain_json only.
- * with_ids: the arena's two extra keys (slot, uid). */
+ * with_ids: the arena's two extra keys (slot, uid).
+ * The record's layout, every kind bit included, is defined once, in ataxxzero_amd/csrc/record.h; ataxxzero_amd/link.py
+ * carries the same names (RECORD_MAGIC, REC_KIND_*) and walks it in link.records.  The kind bits are not part of this
+ * header: a caller reads them there. */
 int azh_format_record_json(const uint32_t *rec, int64_t words, int32_t with_ids, char *buf, int64_t cap, int64_t *used);
 /* Order in which azh_engine_drain_json hands games out: 0 (default) as they finish; 1 by game uid (slot g plays
  * uids g, g + games, g + 2 games, ...): a finished game is held back until every game with a smaller uid has been

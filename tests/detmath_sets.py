@@ -80,3 +80,6 @@ def ulp_error(got, ref):
     """|got - ref| in units of the f32 spacing just above |ref| (ref float64, non-zero and normal in f32)"""
     _, e = np.frexp(np.abs(ref))
     return np.abs(got.astype(np.float64) - ref) / np.ldexp(1.0, e - 24)
+
+
+LOGF_ULP, EXPF_ULP = 0.85, 1.05

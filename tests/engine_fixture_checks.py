@@ -3,10 +3,13 @@
 (select / leaf boards / backup / tree).  The engine under test runs with the Python-engine flags
 (AZH_FLAG_NO_REUSE | TIE_FIRST | PY_POSTERIOR | SAMPLE_POW5), no Dirichlet noise (engine.py:325), one game slot whose
 start position is the fixture's position and whose visit threshold is the fixture's step count."""
+import json
+import os
+
 import numpy as np
 
 from oracle import oracle_lib as orc
-from tests.helpers import load_gz, synthetic_evals_distinct
+from tests.helpers import GOLDEN, load_gz, synthetic_evals_distinct
 
 PY_ENGINE_FLAGS = orc.FLAG_NO_REUSE | orc.FLAG_TIE_FIRST | orc.FLAG_PY_POSTERIOR | orc.FLAG_SAMPLE_POW5
 NONE = 0xFFFFFFFF
@@ -167,3 +170,18 @@ def check_reuse_sequence(rec, select, leaves, backup, game_state, tree):
             check_edges(tree(), want["edges"])
             checked += 1
     raise AssertionError("the fixture's plies were not all played")
+
+
+def _reference_random_games():
+    import gzip
+    with gzip.open(os.path.join(GOLDEN, "random_play_games.jsonl.gz")) as f:
+        return [l for l in f.read().decode().split("\n") if l.strip()]
+
+
+def _shape(v):
+    """Structure of a JSON value: types and nesting, lists summarised by the set of their element shapes."""
+    if isinstance(v, dict):
+        return {k: _shape(x) for k, x in v.items()}
+    if isinstance(v, list):
+        return ["list", sorted({json.dumps(_shape(x), sort_keys=True) for x in v})]
+    return type(v).__name__

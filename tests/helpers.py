@@ -6,7 +6,9 @@ import os
 
 import numpy as np
 
+from ataxxzero_amd import link
 from oracle import oracle_lib as orc
+from tests import rules_reference as rr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -230,7 +232,7 @@ def nonfinite_net(seed=3, cell=4, value_channels=(64,), policy_channel=58, polic
     The policy head's weight from input channel `policy_channel` to move layer `policy_layer` is +inf: that layer's logit of a
     cell is +inf where the channel is active there (every prior of a node with such a legal move is then zero) and a NaN where
     it is not; the other 16 layers stay finite.  The defaults were picked with oracle.net_oracle.forward over the positions of
-    twelve random lines from the late start position of tests/test_gpu_forced_playouts.py: about half of them get a NaN value,
+    twelve random lines from the late start position of tests/engine_harness.py: about half of them get a NaN value,
     about half a +inf logit at a legal move (tests/test_hostile_net.py holds that)."""
     from ataxxzero_amd import model
     conv, bn = model.random_init(1, 128, seed=seed, perturb_bn=True)
@@ -241,3 +243,49 @@ def nonfinite_net(seed=3, cell=4, value_channels=(64,), policy_channel=58, polic
     conv[5][cell, 0] = np.inf
     conv[3][0, 0, policy_channel, policy_layer] = np.inf
     return conv, bn
+
+
+BLOCK3_MASK = (1 << 0) | (1 << 9) | (1 << 33)
+
+
+def orc_pos(b):
+    p = orc.Pos()
+    p.pieces[0], p.pieces[1], p.blockers = b.masks()
+    p.turn = b.turn
+    return p
+
+
+def pocket_boards():
+    """[(board, blockers mask)]: the side to move is walled in by blockers and its opponent has no stones, the boards on which
+    the reference's two adjudication orders disagree (left out of rules_edge.json.gz for that reason)"""
+    out = []
+    for pocket in ([0], [48, 47], [6, 13], [42]):
+        wall = {n for sq in pocket for n in rr.NEAR[sq] + rr.FAR[sq]} - set(pocket)
+        for turn in (0, 1):
+            cells = [rr.BLOCK if sq in wall else rr.EMPTY for sq in range(49)]
+            for sq in pocket:
+                cells[sq] = rr.X if turn == 0 else rr.O
+            out.append((rr.Board(cells, turn), sum(1 << sq for sq in wall)))
+    return out
+
+
+def note(text):
+    """numbers a green run should leave behind (pytest -q swallows prints): appended to gpurun_out/nn_gate.txt"""
+    import os
+    print(text)
+    os.makedirs("gpurun_out", exist_ok=True)
+    with open("gpurun_out/nn_gate.txt", "a") as f:
+        f.write(text + "\n")
+
+
+def sample_leaf_boards(n, seed, blockers):
+    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
+    plies, results, boards, moves = link.random_play(64, seed, p.pieces[0], p.pieces[1], blockers, 0, 300)
+    rng = np.random.default_rng(seed)
+    out = []
+    while len(out) < n:
+        g = int(rng.integers(0, 64))
+        ply = int(rng.integers(0, max(plies[g], 1)))
+        x, o = int(boards[g, ply, 0]), int(boards[g, ply, 1])
+        out.append([x, o] if ply % 2 == 0 else [o, x])
+    return np.array(out, dtype=np.uint64)

@@ -12,7 +12,7 @@ import torch
 
 from ataxxzero_amd import link, model, training
 from tests import helpers
-from tests.test_samples_host import MOVES
+from tests.samples_fixtures import MOVES
 
 F32 = np.float32
 BOARD = [(c * 7 + c // 5) % 3 for c in range(49)]            # no symmetry maps it onto itself
@@ -162,16 +162,8 @@ def check_edges_of_the_wave():
     store.close()
 
 
-def _records(words):
-    out, pos = [], 0
-    while pos < len(words):
-        out.append(words[pos:pos + int(words[pos + 5])])
-        pos += int(words[pos + 5])
-    return out
-
-
 def check_the_record_path():
-    from tests.test_gpu_forced_playouts import START
+    from tests.engine_harness import START
     conv, bn = model.random_init(1, 128, seed=3, perturb_bn=True)
     net = link.Net(conv, bn)
     x, o, turn = START
@@ -191,21 +183,22 @@ def check_the_record_path():
         words = e.staged_records().copy()
         lines = e.drain_json()
         e.close()
-        recs = [r for r in _records(words) if not int(r[7]) & 1]
+        recs = list(link.records(words))         # (without the markers of dropped games)
         assert len(recs) == len(lines) >= 4
-        kinds |= {int(r[7]) for r in recs}
-        recs.sort(key=lambda r: int(r[2]))       # the lines come in uid order
+        kinds |= {r.kind for r in recs}
+        recs.sort(key=lambda r: r.uid)           # the lines come in uid order
         entries = [json.loads(line) for line in lines]
-        assert [len(en["boards"]) for en in entries] == [int(r[3]) for r in recs]
-        store = link.SampleStore(len(recs), sum(int(r[3]) for r in recs), len(words))
-        store.add_records(np.concatenate(recs))
+        assert [len(en["boards"]) for en in entries] == [len(r.plies) for r in recs]
+        store = link.SampleStore(len(recs), sum(len(r.plies) for r in recs), len(words))
+        store.add_records(np.concatenate([r.words for r in recs]))
         for blend in (0.0, 0.5):
             random.seed(5)
             want = training.make_minibatch_reference(entries, 128, blend)
             random.seed(5)
             same(host(training.make_minibatch_device(store, 0, len(entries), 128, blend)), want)
         store.close()
-    assert any(k & 64 for k in kinds) and any(k & 16 and k & 4 for k in kinds)
+    assert any(k & link.REC_KIND_GUMBEL for k in kinds) and \
+        any(k & link.REC_KIND_VALUES and k & link.REC_KIND_PLAYOUT_CAP for k in kinds)
     net.close()
 
 

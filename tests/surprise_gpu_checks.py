@@ -13,7 +13,7 @@ from oracle import net_oracle
 from tests import surprise_reference as ref
 from tests.samples_gpu_checks import host, same
 from tests.surprise_reference import BAD, FULL, PASS
-from tests.test_surprise_host import edge_specs
+from tests.surprise_reference import edge_specs
 
 F32 = np.float32
 HOSTILE = (3e38, -3e38, np.inf, -np.inf, np.nan)

@@ -9,7 +9,7 @@ import numpy as np
 from ataxxzero_amd import link
 from oracle import oracle_lib as orc
 from tests import helpers
-from tests.test_detmath_accuracy import EXPF_ULP, LOGF_ULP
+from tests.detmath_sets import EXPF_ULP, LOGF_ULP
 
 F32 = np.float32
 U = 2.0 ** -24                 # the unit roundoff of f32: one rounded operation is off by at most U relative
@@ -143,3 +143,21 @@ def per_game_lists(games, flags, cum):
     lists = [candidates_of(first, plies, word, flags) for first, plies, word, _ in games]
     cums = [[int(c) for c in cum[first:first + len(c_list)]] for (first, _, _, _), c_list in zip(games, lists)]
     return games, flags, lists, cums
+
+
+def edge_specs(rng):
+    """The games of the issue's list; weights None: never given any."""
+    long_w = rng.random(4096).astype(F32)
+    long_w[rng.random(4096) < 0.3] = 0
+    return [
+        ([0], 1, 0, [2.5]),                                               # one candidate
+        ([0, 0, 0, 0], 1 | HAS_FULL, 0, [1, 1, 1, 1]),                    # "full" without one full ply
+        ([0, 0, 0], 2, 0, [0, 0, 0]),                                     # total 0
+        ([0] * 9, 1, 0, [0, 1.5, 0, 0, 0.25, 3, 0, 0, 1e-6]),             # zeros on some plies (1e-6 rounds to 0 units)
+        ([0, 0, 0, 0, 0], 2, 3, [5, 0, 0, 0, 1]),                         # random_ply: ply 3 whatever the weights say
+        ([0] * 4096, 1, 0, long_w),                                       # the search's depth
+        ([0, FULL, 0, FULL | BAD, FULL | PASS, FULL, 0], 1 | HAS_FULL, 0, [9, 0.5, 9, 4, 4, 2, 9]),
+        ([0] * 12, 2, 0, None),                                           # never weighted
+        ([BAD, PASS, 0, BAD, PASS, BAD], 1, 0, [0.125, 0.125, 3, 0.125, 0.125, 0.125]),   # one good ply among six, a heavy one
+        ([0, 0, 0], 1, 0, [65535.0, 0.5, 0.25]),                          # a large total: 65535.75 * 65536 units
+    ]

@@ -7,9 +7,9 @@ import numpy as np
 
 from oracle import oracle_lib as orc
 from tests import detmath_sets as ds
+from tests.detmath_sets import EXPF_ULP, LOGF_ULP
 
 F32 = np.float32
-LOGF_ULP, EXPF_ULP = 0.85, 1.05
 
 
 def test_logf_against_float64():

@@ -13,6 +13,7 @@ from ataxxzero_amd import training
 from oracle import net_oracle
 from oracle import oracle_lib as orc
 from tests import engine_fixture_checks as fx
+from tests.engine_fixture_checks import _reference_random_games, _shape
 from tests.helpers import GOLDEN, linear_evals, load_gz, synthetic_evals_distinct
 
 
@@ -166,21 +167,6 @@ def test_pgn_blocks_equal_the_reference_ringmaster(tmp_path):
         want = [l for l in g["pgn"].split("\n") if not l.startswith(clock)]
         assert got == want
         assert sum(l.startswith(clock) for l in open(path).read().split("\n")) == 3
-
-
-def _reference_random_games():
-    import gzip
-    with gzip.open(os.path.join(GOLDEN, "random_play_games.jsonl.gz")) as f:
-        return [l for l in f.read().decode().split("\n") if l.strip()]
-
-
-def _shape(v):
-    """Structure of a JSON value: types and nesting, lists summarised by the set of their element shapes."""
-    if isinstance(v, dict):
-        return {k: _shape(x) for k, x in v.items()}
-    if isinstance(v, list):
-        return ["list", sorted({json.dumps(_shape(x), sort_keys=True) for x in v})]
-    return type(v).__name__
 
 
 def test_reference_random_play_games_replay_through_the_oracle_rules():

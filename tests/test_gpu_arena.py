@@ -12,7 +12,7 @@ import pytest
 from ataxxzero_amd import arena, link, model
 from oracle import oracle_lib as orc
 from tests.helpers import replay_game_entry, synthetic_evals
-from tests.test_gpu_engine import _oracle_follow, compare_all
+from tests.engine_harness import _oracle_follow, compare_all
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

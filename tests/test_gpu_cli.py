@@ -120,7 +120,7 @@ def test_generate_games_random_play_cli(tmp_path):
         plies.append(len(uai))
     assert 100 < np.mean(plies) < 260  # reference random play averages 182 plies
     # line for line the structure of what the reference's own generate_games.py writes (tests/golden/random_play_games.jsonl.gz)
-    from tests.test_engine_fixtures_oracle import _reference_random_games, _shape
+    from tests.engine_fixture_checks import _reference_random_games, _shape
     ref_line = _reference_random_games()[0]
     ref = json.loads(ref_line)
     for line in lines[:20]:

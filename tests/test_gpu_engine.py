@@ -11,84 +11,11 @@ import pytest
 from ataxxzero_amd import link, model, selfplay
 from oracle import oracle_lib as orc
 from tests.helpers import replay_game_entry, synthetic_evals
+from tests.engine_harness import _oracle_follow, check_marks, compare_all, make_pair, run_lockstep
+from tests.engine_harness import _is_nan_bits
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def make_pair(games, visits, max_plies=400, edges_per_node=96, seed=77, fen=orc.START_FEN_SELFPLAY, weight=0.25,
-              flags=0, select_budget=0):
-    ocfg = orc.make_config(games, visits, seed=seed, fen_str=fen, max_plies=max_plies,
-                           edges_per_node=edges_per_node, weight=weight, flags=flags, select_budget=select_budget)
-    gcfg = link.Config(**{n: getattr(ocfg, n) for n, _ in orc.Config._fields_})
-    return orc.Engine(ocfg), link.Engine(gcfg)
-
-
-def _is_nan_bits(w):
-    return ((w & 0x7F800000) == 0x7F800000) & ((w & 0x007FFFFF) != 0)
-
-
-def compare_all(oe, ge, games, nan_aware=False):
-    """nan_aware: a NaN prior or total score must be a NaN on both sides, whatever its sign and payload — the only words of
-    a tree that are not a function of IEEE arithmetic alone (which NaN an operation hands on is the hardware's choice)."""
-    for g in games:
-        so, sg = oe.game_state(g), ge.game_state(g)
-        assert so.as_tuple() == sg.as_tuple(), (g, so.as_tuple(), sg.as_tuple())
-        to, tg = oe.tree(g), ge.tree(g)
-        for name, a, b in zip(("boards", "info", "edges", "moves"), to, tg):
-            assert a.shape == b.shape, (g, name)
-            if nan_aware and name == "edges":
-                a, b = a.copy(), b.copy()
-                for col in (0, 2):
-                    na, nb = _is_nan_bits(a[:, col]), _is_nan_bits(b[:, col])
-                    assert (na == nb).all(), (g, name, col)
-                    a[na, col] = b[nb, col] = 0x7FC00000
-            assert (a == b).all(), (g, name)
-
-
-def check_marks(ge, games):
-    """The early request's mark (bit 31 of a prior in the device's edge records, azh_engine_tree_raw): at most ONE marked edge
-    per node, and only on an edge whose child exists, is not a finished position and has 1 .. 128 moves — what lets the
-    descent request the marked child's records without a check.  -> (nodes with a mark, marks on an edge index >= 64)."""
-    marked_nodes = high = 0
-    for g in games:
-        _, info, _, _ = ge.tree(g)
-        raw = ge.tree_raw(g)
-        mark = (raw[:, 0] >> 31) != 0
-        for n in range(len(info)):
-            first, m = int(info[n, 0]), int(info[n, 1] & 0xFFFF)
-            idx = np.nonzero(mark[first:first + m])[0]
-            assert len(idx) <= 1, (g, n, idx.tolist())
-            if len(idx):
-                assert m <= 128, (g, n, m)
-                z, w = int(raw[first + idx[0], 2]), int(raw[first + idx[0], 3])
-                assert (z >> 16) != 0xFFFF and (w >> 31) == 0 and 1 <= ((w >> 23) & 0xFF) <= 128, (g, n, int(idx[0]), hex(z), hex(w))
-                marked_nodes += 1
-                high += int(idx[0]) >= 64
-        # no mark outside the nodes' ranges either (every edge belongs to exactly one node)
-        assert int(mark.sum()) <= len(info)
-    return marked_nodes, high
-
-
-def run_lockstep(oe, ge, iterations, check_every=1, evaluator=synthetic_evals):
-    G = oe.G
-    o_games, g_lines = [], []
-    for it in range(iterations):
-        n_o, need_o = oe.select()
-        n_g = ge.select()
-        need_g, lb_g = ge.leaves()
-        lb_o = oe.leaf_boards()
-        assert n_o == n_g and (need_o == need_g).all(), it
-        assert (lb_o[need_o == 1] == lb_g[need_o == 1]).all(), it
-        logits, values = evaluator(lb_o)
-        oe.backup(logits, values)
-        ge.set_evals(logits, values)
-        ge.backup()
-        if it % check_every == 0 or it == iterations - 1:
-            compare_all(oe, ge, range(G))
-        o_games += oe.pop_games()
-        g_lines += ge.drain_json()
-    return o_games, g_lines
 
 
 def test_engine_matches_oracle_bit_for_bit_small_visits():
@@ -576,27 +503,6 @@ def test_full_size_workload_invariants(name, visits, blocks, net_seed, dtype, fl
         assert entry["result"] in (1, 2)
         assert replay_game_entry(entry, orc.START_FEN_SELFPLAY) == entry["result"]
     sp.close()
-
-
-def _oracle_follow(oe, net, blockers, iterations, dtype=link.DTYPE_F32, thin=False, net_b=None):
-    """The oracle plays `iterations` search iterations, its leaves evaluated by the tower the device-resident loop uses for
-    them — the f32 tower, or a 16-bit tower with one board per workgroup (`thin`): both are bit-identical wherever a board
-    sits in a launch (tests/test_gpu_net.py) — i.e. exactly what the loop computes for itself.  `net_b`: the arena's
-    second net, for the leaves whose mover it is (need class 2, uai_ringmaster.py:221-265)."""
-    G = oe.G
-    logits = np.zeros((G, 833), np.float32)
-    values = np.zeros(G, np.float32)
-    for _ in range(iterations):
-        _, need = oe.select()
-        lb = None
-        for cls, n in ((1, net), (2, net_b)):
-            idx = np.nonzero(need == cls)[0] if net_b is not None else (np.nonzero(need)[0] if cls == 1 else [])
-            if len(idx):
-                lb = oe.leaf_boards() if lb is None else lb
-                p, v = n.forward(lb[idx], blockers, dtype, thin=thin)
-                logits[idx] = p.reshape(len(idx), 833)
-                values[idx] = v.reshape(-1)
-        oe.backup(logits, values)
 
 
 @pytest.mark.parametrize("name,games,visits,blocks,max_plies,budget,chunks,chunk,dtype", [

@@ -5,39 +5,18 @@ refusals."""
 import numpy as np
 import pytest
 
-from ataxxzero_amd import link, model
+from ataxxzero_amd import link
 from oracle import oracle_lib as orc
+from tests import engine_harness as eh
 from tests import forced_reference as fr
 from tests import helpers
 from tests import vl_reference as vlr
+from tests.engine_harness import START, WIDE_FEN_BIG, WIDE_FEN_MID
 
 pytestmark = pytest.mark.gpu
 
-MAGIC = 0x415A4847
 SEED = 424242
 C_PUCT = 1.0
-REC_KIND_FORCED = 8
-
-# Positions with many legal moves, found on the CPU with the oracle's uniformly random play from the plain start position
-# (x5o/7/7/7/7/7/o5x x, no blockers): the widest with at most 128 moves (128) and the widest of all (157) in 20,000 games.
-WIDE_FEN_MID = "1xxoo2/x3o2/oooooo1/1ooooo1/1o2o1o/1oo1xx1/1oo1x1x o"
-WIDE_FEN_BIG = "2oo1xx/o2o3/o2oooo/2oo2o/2oo3/o1oooo1/1o2o2 o"
-
-
-def _late_start():
-    """An unfinished fixture position with 10-14 empty squares and both sides well alive: games from it last a few dozen
-    plies, so thresholds, tree reuse, game ends and restarts all occur within a few hundred iterations."""
-    for rec in helpers.load_gz("rules_noblock.json.gz"):
-        p = orc.pos_from_fen(rec["fen"])
-        x, o = int(p.pieces[0]), int(p.pieces[1])
-        if orc.result(p) != 0 or len(orc.movegen(p)) == 0:
-            continue
-        if 10 <= 49 - bin(x | o).count("1") <= 14 and min(bin(x).count("1"), bin(o).count("1")) >= 10:
-            return x, o, int(p.turn)
-    raise AssertionError("no such fixture position")
-
-
-START = _late_start()
 
 
 def _engine(games, visits, weight=0.25, seed=SEED, flags=0, cap=None, k=None, start=START, edges_per_node=96):
@@ -51,51 +30,6 @@ def _engine(games, visits, weight=0.25, seed=SEED, flags=0, cap=None, k=None, st
     if k is not None:
         e.set_forced_playouts(k)
     return e
-
-
-def _net(seed=3):
-    conv, bn = model.random_init(1, 128, seed=seed, perturb_bn=True)
-    return link.Net(conv, bn)
-
-
-def _step(e):
-    e.select()
-    need, lb = e.leaves()
-    logits, values = helpers.synthetic_evals_distinct(lb)
-    e.set_evals(logits, values)
-    e.backup()
-    return values
-
-
-def _dump(e):
-    return [e.game_state(g).as_tuple() for g in range(e.G)], [e.tree(g) for g in range(e.G)]
-
-
-def _same(da, db):
-    (sa, ta), (sb, tb) = da, db
-    assert sa == sb
-    for x, y in zip(ta, tb):
-        for u, v in zip(x, y):
-            assert u.shape == v.shape and (u == v).all()
-
-
-def _records(words):
-    """[(slot, uid, result, kind word, [(move, full, {move: visits})])] of the staged record words (dropped markers skipped)"""
-    out, pos = [], 0
-    while pos < len(words):
-        assert words[pos] == MAGIC
-        slot, uid, plies, result, n, kind = (int(words[pos + i]) for i in (1, 2, 3, 4, 5, 7))
-        if kind & 3 != 1:
-            q, rows = pos + 8, []
-            for _ in range(plies):
-                nd = int(words[q + 4]) >> 16
-                rows.append((int(words[q + 4]) & 0xFFFF, int(words[q + 5]),
-                             {int(w) & 0xFFFF: int(w) >> 16 for w in words[q + 6:q + 6 + nd]}))
-                q += 6 + nd
-            assert q == pos + n
-            out.append((slot, uid, result, kind, rows))
-        pos += n
-    return out
 
 
 def _check_root_marks(e, g=0):
@@ -142,7 +76,7 @@ def _lock_step(e, k, games, cap=None, tie_first=False, max_iterations=9000):
             if not full:
                 prior, W, n, _, _ = fr.root_arrays(pre)
                 seen["fast_owed_ignored"] += int(fr.owed(prior, n, st.root_visits, k).any())
-        values = _step(e)
+        values = eh.step(e)[3]
         s2 = e.game_state(0)
         if b is not None:
             assert (s2.uid, s2.ply) == (st.uid, st.ply)
@@ -161,8 +95,8 @@ def _lock_step(e, k, games, cap=None, tie_first=False, max_iterations=9000):
             expected[(s2.uid, s2.ply)] = (want, full)
         if s2.uid != st.uid:
             e.fetch()
-            for slot, uid, result, kind, rows in _records(e.staged_records()):
-                assert kind & REC_KIND_FORCED and bool(kind & 4) == (cap is not None)
+            for slot, uid, result, kind, rows in eh.records3(e.staged_records()):
+                assert kind & link.REC_KIND_FORCED and bool(kind & link.REC_KIND_PLAYOUT_CAP) == (cap is not None)
                 for ply, (move, fullw, counts) in enumerate(rows):
                     want, f = expected[(uid, ply)]
                     assert counts == want, (uid, ply, f, counts, want)
@@ -216,12 +150,12 @@ def test_wide_roots(fen, lo, hi):
         if st.phase == 2:
             break
         if st.phase != 1:
-            _step(e)
+            eh.step(e)
             continue
         pre = e.tree(0)
         assert int(pre[1][0, 1]) & 0xFFFF == M
         b = fr.select(pre, st.root_visits, k, True, C_PUCT, False, 0)
-        values = _step(e)
+        values = eh.step(e)[3]
         post = e.tree(0)
         (eb, ei, ee, em), added = vlr.expected_tree(b, values, post)
         assert (eb == post[0]).all() and (ei == post[1]).all() and (ee == post[2]).all() and (em == post[3]).all(), it
@@ -235,7 +169,7 @@ def test_wide_roots(fen, lo, hi):
 
 @pytest.mark.parametrize("games", [5, 33, 130])
 def test_device_loop_equals_host_stepping(games):
-    net = _net()
+    net = eh.net()
     visits, k, n = 16, 2.0, 600
     a = _engine(games, visits, k=k)
     b = _engine(games, visits, k=k)
@@ -245,14 +179,14 @@ def test_device_loop_equals_host_stepping(games):
         b.select()
         b.eval(net, link.DTYPE_BF16)
         b.backup()
-    _same(_dump(a), _dump(b))
+    eh.same(eh.dump(a), eh.dump(b))
     assert a.stats() == b.stats() and a.stats()["plies"] > 4 * games
     a.fetch(), b.fetch()
-    ra, rb = _records(a.staged_records()), _records(b.staged_records())
+    ra, rb = eh.records3(a.staged_records()), eh.records3(b.staged_records())
     assert sorted(a.drain_json()) == sorted(b.drain_json()) and len(ra) == len(rb) > 0
     short = 0
     for slot, uid, result, kind, rows in ra:
-        assert kind & REC_KIND_FORCED
+        assert kind & link.REC_KIND_FORCED
         for move, full, counts in rows:
             assert counts and all(c >= 1 for c in counts.values())
             assert sum(counts.values()) <= visits      # (every ply is played at `visits` raw visits: an inherited root has fewer)
@@ -269,14 +203,14 @@ def test_off_is_off():
     lines = {id(x): [] for x in (ref, never, off)}
     for it in range(1500):
         for x in (ref, never, off):
-            _step(x)
+            eh.step(x)
         if it % 10 == 0 or len(lines[id(ref)]) >= 3:
-            _same(_dump(ref), _dump(never))
-            _same(_dump(ref), _dump(off))
+            eh.same(eh.dump(ref), eh.dump(never))
+            eh.same(eh.dump(ref), eh.dump(off))
         for x in (ref, never, off):
             x.fetch()
-            for r in _records(x.staged_records()):
-                assert not r[3] & REC_KIND_FORCED
+            for r in eh.records3(x.staged_records()):
+                assert not r[3] & link.REC_KIND_FORCED
             lines[id(x)] += x.drain_json()
         if len(lines[id(ref)]) >= 3:
             break
@@ -287,7 +221,7 @@ def test_off_is_off():
     ref2 = _engine(3, 24)
     differ = False
     for it in range(200):
-        _step(on), _step(ref2)
+        eh.step(on), eh.step(ref2)
         differ = differ or any((x.shape != y.shape or (x != y).any()) for g in range(3) for x, y in zip(on.tree(g), ref2.tree(g)))
     assert differ
     for x in (ref, never, off, on, ref2):
@@ -299,7 +233,7 @@ def test_refusals_leave_the_engine_usable():
     for bad in (-1.0, float("nan")):
         with pytest.raises(link.AzhError):
             e.set_forced_playouts(bad)
-    _step(e)
+    eh.step(e)
     e.select()
     with pytest.raises(link.AzhError):
         e.set_forced_playouts(2.0)            # a selected batch awaits its backup
@@ -313,7 +247,7 @@ def test_refusals_leave_the_engine_usable():
         e.set_solver(True)
     e.set_leaf_batch(1, 1)                    # K = 1 without the solver is the one-leaf search: no request
     for _ in range(40):
-        _step(e)
+        eh.step(e)
     assert e.stats()["plies"] > 0
     e.set_forced_playouts(0.0)
     e.set_leaf_batch(4, 1)
@@ -326,14 +260,14 @@ def test_refusals_leave_the_engine_usable():
     e.set_solver(False)
     e.set_forced_playouts(2.0)
     for _ in range(30):
-        _step(e)
+        eh.step(e)
     e.close()
     for flags in (link.FLAG_TWO_NETS, link.FLAG_ONE_RANDOM_MOVE):
         r = _engine(4, 24, weight=0.0, flags=flags)
         with pytest.raises(link.AzhError):
             r.set_forced_playouts(2.0)
         r.set_forced_playouts(0.0)            # switching off is no request for the mode
-        net = _net()
+        net = eh.net()
         if flags == link.FLAG_TWO_NETS:
             r.run_arena(net, net, 20, link.DTYPE_F32)
         else:

@@ -11,8 +11,8 @@ import pytest
 from ataxxzero_amd import link, model
 from oracle import oracle_lib as orc
 from tests.helpers import cohort_positions, replay_game_entry, synthetic_evals
-from tests.test_gpu_engine import _oracle_follow, compare_all, make_pair
-from tests.test_oracle_search import LIMIT_CASES, LIMIT_PLIES, cells_of, free_run
+from tests.engine_harness import _oracle_follow, compare_all, make_pair
+from tests.limit_fixtures import LIMIT_CASES, LIMIT_PLIES, cells_of, free_run
 
 pytestmark = pytest.mark.gpu
 

@@ -3,30 +3,24 @@ restatement (tests/gumbel_reference.py) iteration by iteration — whole tree, r
 records' moves and counts against gumbel_root, the game lines, wide roots, a root with one move, the device loop against
 host stepping, off is off, set_visits while the mode is on, and the refusals."""
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from ataxxzero_amd import link, model
+from ataxxzero_amd import link
 from oracle import oracle_lib as orc
+from tests import engine_harness as eh
 from tests import forced_reference as fr
 from tests import gumbel_reference as gr
 from tests import helpers
 from tests import vl_reference as vlr
-from tests.test_gpu_forced_playouts import START, WIDE_FEN_BIG, WIDE_FEN_MID
+from tests.engine_harness import START, WIDE_FEN_BIG, WIDE_FEN_MID
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-MAGIC = 0x415A4847
 SEED = 424242
 C_PUCT = 1.0
 C_VISIT, C_SCALE = 50.0, 1.0
-REC_KIND_GUMBEL = 64
-REC_KIND_VALUES = 16
 ONE_MOVE_FEN = "oooxooo/oooxoxx/ooxxoxx/ooxxxxx/oooxxx1/oooxxxx/ooxxxxx o"
 F32 = np.float32
 
@@ -40,51 +34,6 @@ def _engine(games, visits, gumbel=None, weight=0.0, seed=SEED, flags=link.FLAG_N
     if gumbel is not None:
         e.set_gumbel(gumbel, C_VISIT, C_SCALE)
     return e
-
-
-def _net(seed=3):
-    conv, bn = model.random_init(1, 128, seed=seed, perturb_bn=True)
-    return link.Net(conv, bn)
-
-
-def _step(e):
-    e.select()
-    need, lb = e.leaves()
-    logits, values = helpers.synthetic_evals_distinct(lb)
-    e.set_evals(logits, values)
-    e.backup()
-    return values
-
-
-def _dump(e):
-    return [e.game_state(g).as_tuple() for g in range(e.G)], [e.tree(g) for g in range(e.G)]
-
-
-def _same(da, db):
-    (sa, ta), (sb, tb) = da, db
-    assert sa == sb
-    for x, y in zip(ta, tb):
-        for u, v in zip(x, y):
-            assert u.shape == v.shape and (u == v).all()
-
-
-def _records(words):
-    """[(slot, uid, result, kind word, [(move, word 5, {move: count})])] of the staged record words (dropped markers skipped)"""
-    out, pos = [], 0
-    while pos < len(words):
-        assert words[pos] == MAGIC
-        slot, uid, plies, result, n, kind = (int(words[pos + i]) for i in (1, 2, 3, 4, 5, 7))
-        if kind & 3 != 1:
-            q, rows = pos + 8, []
-            for _ in range(plies):
-                nd = int(words[q + 4]) >> 16
-                rows.append((int(words[q + 4]) & 0xFFFF, int(words[q + 5]),
-                             {int(w) & 0xFFFF: int(w) >> 16 for w in words[q + 6:q + 6 + nd]}))
-                q += 6 + nd
-            assert q == pos + n
-            out.append((slot, uid, result, kind, rows))
-        pos += n
-    return out
 
 
 def _root_mark(e, g=0):
@@ -131,7 +80,7 @@ def _lock_step(e, visits, m, games, plies_checked=12, max_iterations=9000):
             pre = e.tree(0)
             mark = _root_mark(e)
             b = gr.select(pre, st.root_visits, visits, m, root[key][0], C_VISIT, C_SCALE, C_PUCT, False, 0)
-        values = _step(e)
+        values = eh.step(e)[3]
         s2 = e.game_state(0)
         if st.phase == 0:
             # the root was evaluated: its noise and its own value
@@ -164,8 +113,8 @@ def _lock_step(e, visits, m, games, plies_checked=12, max_iterations=9000):
             seen["unexpanded"] += unexpanded
         if s2.uid != st.uid:
             e.fetch()
-            for slot, uid, result, kind, rows in _records(e.staged_records()):
-                assert kind & REC_KIND_GUMBEL and not kind & (4 | 8)
+            for slot, uid, result, kind, rows in eh.records3(e.staged_records()):
+                assert kind & link.REC_KIND_GUMBEL and not kind & (link.REC_KIND_PLAYOUT_CAP | link.REC_KIND_FORCED)
                 for ply, (move, w5, counts) in enumerate(rows):
                     assert (move, counts) == expected[(uid, ply)], (uid, ply)
                     seen["plies"] += 1
@@ -216,7 +165,7 @@ def test_wide_roots(fen, lo, hi, beyond):
     e = _engine(1, visits, gumbel=m, edges_per_node=200)
     e.set_positions(np.array([[int(p.pieces[0]) | (int(p.turn) << 63), int(p.pieces[1])]], dtype=np.uint64),
                     np.zeros(1, dtype=np.int32))
-    values = _step(e)
+    values = eh.step(e)[3]
     st = e.game_state(0)
     assert st.phase == 1
     prior = fr.root_arrays(e.tree(0))[0]
@@ -230,7 +179,7 @@ def test_wide_roots(fen, lo, hi, beyond):
         assert st.phase == 1 and st.root_visits == it
         pre, mark = e.tree(0), _root_mark(e)
         b = gr.select(pre, st.root_visits, visits, m, a, C_VISIT, C_SCALE, C_PUCT, False, 0)
-        values = _step(e)
+        values = eh.step(e)[3]
         post = e.tree(0)
         (eb, ei, ee, em), added = vlr.expected_tree(b, values, post)
         assert (eb == post[0]).all() and (ei == post[1]).all() and (ee == post[2]).all() and (em == post[3]).all(), it
@@ -244,7 +193,7 @@ def test_wide_roots(fen, lo, hi, beyond):
     mv, written, unexpanded = _expected_ply(e.tree(0), v0, g)
     assert unexpanded == 0 and len(written) >= 2     # (every move was considered and expanded: visits >= M)
     # the move is played from this tree (nothing is emitted: a loaded game writes no line)
-    _step(e)
+    eh.step(e)
     s2 = e.game_state(0)
     assert s2.ply == 1 or s2.uid != st.uid
     e.close()
@@ -258,7 +207,7 @@ def test_a_root_with_one_legal_move():
     e = _engine(1, visits, gumbel=4)
     e.set_positions(np.array([[int(p.pieces[0]) | (int(p.turn) << 63), int(p.pieces[1])]], dtype=np.uint64),
                     np.zeros(1, dtype=np.int32))
-    values = _step(e)
+    values = eh.step(e)[3]
     v0 = F32(F32(values[0] + F32(1.0)) * F32(0.5))
     prior = fr.root_arrays(e.tree(0))[0]
     g = link.gumbel_noise(SEED, 0, 0, 1)
@@ -268,7 +217,7 @@ def test_a_root_with_one_legal_move():
         pre = e.tree(0)
         b = gr.select(pre, st.root_visits, visits, 4, a, C_VISIT, C_SCALE, C_PUCT, False, 0)
         assert b.gumbel == 0 and b.cv == it
-        values = _step(e)
+        values = eh.step(e)[3]
         (eb, ei, ee, em), added = vlr.expected_tree(b, values, e.tree(0))
         post = e.tree(0)
         assert (eb == post[0]).all() and (ei == post[1]).all() and (ee == post[2]).all() and (em == post[3]).all()
@@ -277,7 +226,7 @@ def test_a_root_with_one_legal_move():
     mv, written, _ = _expected_ply(e.tree(0), v0, g)
     assert mv == only[0] and written == {only[0]: 65535}
     # the next iteration plays it: the root is the position after the only move, one ply on
-    _step(e)
+    eh.step(e)
     s2 = e.game_state(0)
     assert (s2.uid, s2.ply) == (0, 1)
     board = np.array([[int(p.pieces[0]) | (int(p.turn) << 63), int(p.pieces[1])]], dtype=np.uint64)
@@ -287,7 +236,7 @@ def test_a_root_with_one_legal_move():
 
 @pytest.mark.parametrize("games,extras", [(5, False), (33, True), (130, False)])
 def test_device_loop_equals_host_stepping(games, extras):
-    net = _net()
+    net = eh.net()
     visits, m, n = 8, 4, 500
     a = _engine(games, visits, gumbel=m)
     b = _engine(games, visits, gumbel=m)
@@ -301,14 +250,14 @@ def test_device_loop_equals_host_stepping(games, extras):
         b.select()
         b.eval(net, link.DTYPE_BF16)
         b.backup()
-    _same(_dump(a), _dump(b))
+    eh.same(eh.dump(a), eh.dump(b))
     assert a.stats() == b.stats() and a.stats()["plies"] > 4 * games
     a.fetch(), b.fetch()
-    ra, rb = _records(a.staged_records()), _records(b.staged_records())
+    ra, rb = eh.records3(a.staged_records()), eh.records3(b.staged_records())
     la, lb = a.drain_json(), b.drain_json()
     assert sorted(la) == sorted(lb) and len(ra) == len(rb) > 0
     for slot, uid, result, kind, rows in ra:
-        assert kind & REC_KIND_GUMBEL and bool(kind & REC_KIND_VALUES) == extras
+        assert kind & link.REC_KIND_GUMBEL and bool(kind & link.REC_KIND_VALUES) == extras
         for move, w5, counts in rows:
             assert max(counts.values()) == 65535 and min(counts.values()) >= 1
     for line in la:
@@ -328,14 +277,14 @@ def test_off_is_off():
     lines = {id(x): [] for x in (ref, never, off)}
     for it in range(1500):
         for x in (ref, never, off):
-            _step(x)
+            eh.step(x)
         if it % 10 == 0 or len(lines[id(ref)]) >= 3:
-            _same(_dump(ref), _dump(never))
-            _same(_dump(ref), _dump(off))
+            eh.same(eh.dump(ref), eh.dump(never))
+            eh.same(eh.dump(ref), eh.dump(off))
         for x in (ref, never, off):
             x.fetch()
-            for r in _records(x.staged_records()):
-                assert not r[3] & REC_KIND_GUMBEL
+            for r in eh.records3(x.staged_records()):
+                assert not r[3] & link.REC_KIND_GUMBEL
             lines[id(x)] += x.drain_json()
         if len(lines[id(ref)]) >= 3:
             break
@@ -346,7 +295,7 @@ def test_off_is_off():
     ref2 = _engine(3, 8)
     differ = False
     for it in range(60):
-        _step(on), _step(ref2)
+        eh.step(on), eh.step(ref2)
         differ = differ or any((x.shape != y.shape or (x != y).any()) for g in range(3) for x, y in zip(on.tree(g), ref2.tree(g)))
     assert differ
     for x in (ref, never, off, on, ref2):
@@ -370,7 +319,7 @@ def test_set_visits_while_the_mode_is_on():
         big.set_visits(4097)
     big.set_visits(16)
     for _ in range(45):
-        _step(big)
+        eh.step(big)
     assert big.stats()["plies"] >= 2
     big.set_gumbel(0)
     big.set_visits(60000)
@@ -383,7 +332,7 @@ def test_refusals_leave_the_engine_usable():
                 (4, 50.0, 0.0), (4, 50.0, -1.0), (4, 50.0, float("nan")), (4, 50.0, float("inf"))):
         with pytest.raises(link.AzhError):
             e.set_gumbel(*bad)
-    _step(e)
+    eh.step(e)
     e.select()
     with pytest.raises(link.AzhError):
         e.set_gumbel(4)                        # a selected batch awaits its backup
@@ -412,7 +361,7 @@ def test_refusals_leave_the_engine_usable():
     e.set_random_symmetry(True)                # allowed beside it
     e.set_resign(0.1, 3, 0)
     for _ in range(60):
-        _step(e)
+        eh.step(e)
     assert e.stats()["plies"] > 0
     e.close()
     # the create-time requirements: a fresh root every ply, no Dirichlet mix, and none of the four flags
@@ -425,26 +374,15 @@ def test_refusals_leave_the_engine_usable():
         r.set_gumbel(0)                        # switching off is no request for the mode
         if not flags & link.FLAG_TWO_NETS:
             for _ in range(30):
-                _step(r)
+                eh.step(r)
             assert r.stats()["steps"] > 0
         r.close()
-
-
-def _generator(tmp_path, *flags):
-    conv, bn = model.random_init(1, 128, seed=5)
-    net_path = str(tmp_path / "model-004.npy")
-    model.save_model(net_path, conv, bn)
-    games_path = str(tmp_path / "model-004-0.json")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "accelerated_generate_games.py"), "--network", net_path,
-                          "--output-games", games_path, "--visits", "6", "--buffer-size", "16", "--seed", "9",
-                          "--game-count", "20", "--max-seconds", "60"] + list(flags), cwd=ROOT, capture_output=True, timeout=200)
-    return res, games_path
 
 
 def test_the_generator_with_gumbel_actions(tmp_path):
     """accelerated_generate_games.py --gumbel-actions M: the default cache is switched off with a note, the lines keep their
     keys, replay under the rules, and their dists are distributions over more moves than the ply had visits."""
-    res, games_path = _generator(tmp_path, "--gumbel-actions", "4", "--gumbel-c-visit", "50", "--gumbel-c-scale", "1")
+    res, games_path = eh.generator(tmp_path, "--gumbel-actions", "4", "--gumbel-c-visit", "50", "--gumbel-c-scale", "1")
     text = res.stdout.decode()
     assert res.returncode == 0, text[-2000:] + res.stderr.decode()[-2000:]
     assert "Note: --gumbel-actions searches without the evaluation cache" in text

@@ -7,7 +7,7 @@ of every evaluated node (tests/priors_reference.py), the root visits, and every 
 on a net whose evaluations are not finite for some positions (helpers.nonfinite_net) against host stepping.
 
 A NaN is compared as a NaN whatever its sign and payload (which NaN an operation hands on is the hardware's choice, as in
-tests/test_gpu_engine.compare_all); every other word bit for bit."""
+tests/engine_harness.compare_all); every other word bit for bit."""
 import json
 import random
 
@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from ataxxzero_amd import link, training
+from tests import engine_harness as eh
 from tests import forced_reference as fr
 from tests import gumbel_reference as gr
 from tests import helpers
@@ -22,8 +23,7 @@ from tests import priors_reference as pr
 from tests import symmetry_reference as sym
 from tests import temperature_reference as tr
 from tests import vl_reference as vlr
-from tests.test_gpu_forced_playouts import START
-from tests.test_gpu_gumbel import _records
+from tests.engine_harness import START
 
 pytestmark = pytest.mark.gpu
 
@@ -340,9 +340,10 @@ def _lock_step(mode, games_wanted=2, plies_checked=12, max_iterations=20000):
                                                                      seen, g == 0 and s2[g].ply < plies_checked)
         if any(a.uid != c.uid for a, c in zip(st, s2)):
             e.fetch()
-            for slot, uid, result, kind, rows in _records(e.staged_records()):
-                assert bool(kind & 64) == bool(mode.gumbel) and bool(kind & 8) == bool(mode.forced) and \
-                    bool(kind & 4) == (mode.cap is not None), hex(kind)
+            for slot, uid, result, kind, rows in eh.records3(e.staged_records()):
+                assert bool(kind & link.REC_KIND_GUMBEL) == bool(mode.gumbel) and \
+                    bool(kind & link.REC_KIND_FORCED) == bool(mode.forced) and \
+                    bool(kind & link.REC_KIND_PLAYOUT_CAP) == (mode.cap is not None), hex(kind)
                 for ply, (move, w5, counts) in enumerate(rows):
                     wmove, wcounts, wfull = expected[(uid, ply)]
                     assert (move, counts) == (wmove, wcounts), (uid, ply, move, wmove, counts, wcounts)
@@ -443,10 +444,6 @@ def _net():
     return _NET[0]
 
 
-def _dump(e):
-    return [e.game_state(g).as_tuple() for g in range(e.G)], [e.tree(g) for g in range(e.G)]
-
-
 @pytest.mark.parametrize("games", [5, 33])
 @pytest.mark.parametrize("name", ["gumbel4", "gumbel16", "forced", "temperature", "cap_forced", "symmetry", "leaf_parallel"])
 def test_device_loop_equals_host_stepping(name, games):
@@ -468,7 +465,7 @@ def test_device_loop_equals_host_stepping(name, games):
             b.select()
             b.eval(net, link.DTYPE_BF16)
             b.backup()
-        (sa, ta), (sb, tb) = _dump(a), _dump(b)
+        (sa, ta), (sb, tb) = eh.dump(a), eh.dump(b)
         assert sa == sb
         for g, (x, y) in enumerate(zip(ta, tb)):
             _same_tree(x, y, (name, g, n))
@@ -482,7 +479,7 @@ def test_device_loop_equals_host_stepping(name, games):
                     prior_nodes += int(bool(ed[:, 0].any()))
         assert a.stats() == b.stats()
         a.fetch(), b.fetch()
-        ra, rb = ra + _records(a.staged_records()), rb + _records(b.staged_records())
+        ra, rb = ra + eh.records3(a.staged_records()), rb + eh.records3(b.staged_records())
         la, lb = la + a.drain_json(), lb + b.drain_json()
     assert a.stats()["plies"] > 2 * games
     print("\n%s %d games: W NaN %d, W finite %d, evaluated nodes without a prior %d, with priors %d"

@@ -11,22 +11,9 @@ import pytest
 from ataxxzero_amd import link, model
 from oracle import net_oracle
 from oracle import oracle_lib as orc
-from tests.helpers import BLOCK4_MASK
+from tests.helpers import BLOCK4_MASK, note, sample_leaf_boards
 
 pytestmark = pytest.mark.gpu
-
-
-def sample_leaf_boards(n, seed, blockers):
-    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
-    plies, results, boards, moves = link.random_play(64, seed, p.pieces[0], p.pieces[1], blockers, 0, 300)
-    rng = np.random.default_rng(seed)
-    out = []
-    while len(out) < n:
-        g = int(rng.integers(0, 64))
-        ply = int(rng.integers(0, max(plies[g], 1)))
-        x, o = int(boards[g, ply, 0]), int(boards[g, ply, 1])
-        out.append([x, o] if ply % 2 == 0 else [o, x])
-    return np.array(out, dtype=np.uint64)
 
 
 @pytest.mark.parametrize("blocks,n,perturb", [(2, 37, True), (12, 20, False), (8, 7, True)])
@@ -53,15 +40,6 @@ def game_positions(n, seed, blockers, games=2000):
     odd = (ply % 2 == 1)
     assert 0.3 < odd.mean() < 0.7                           # both sides to move
     return np.where(odd[:, None], xo[:, ::-1], xo).astype(np.uint64)
-
-
-def note(text):
-    """numbers a green run should leave behind (pytest -q swallows prints): appended to gpurun_out/nn_gate.txt"""
-    import os
-    print(text)
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/nn_gate.txt", "a") as f:
-        f.write(text + "\n")
 
 
 def oracle_forward_chunked(conv, bn, lb, blockers, chunk=512):
@@ -185,7 +163,7 @@ def test_other_filter_counts(filters, blocks, n):
     assert st["plies"] > 40 * 5 and st["edge_overflow"] == 0
     # ... and the device-resident loop with this width's f32 tower (whose launch also carries the loop's move-playing
     # workgroups) stays the oracle's search bit for bit
-    from tests.test_gpu_engine import _oracle_follow, compare_all
+    from tests.engine_harness import _oracle_follow, compare_all
     oe, ge = orc.Engine(ocfg), link.Engine(link.Config(**{k: getattr(ocfg, k) for k, _ in orc.Config._fields_}))
     ge.run(net, 150, link.DTYPE_F32)
     _oracle_follow(oe, net, ocfg.blockers, 150)

@@ -16,7 +16,7 @@ import pytest
 from ataxxzero_amd import link, model
 from oracle import net_oracle
 from tests import net_exact as ne
-from tests.test_gpu_net import note, sample_leaf_boards
+from tests.helpers import note, sample_leaf_boards
 
 pytestmark = pytest.mark.gpu
 

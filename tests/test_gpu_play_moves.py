@@ -11,9 +11,9 @@ import pytest
 from ataxxzero_amd import link, model
 from oracle import oracle_lib as orc
 from tests import engine_fixture_checks as fx
+from tests.engine_fixture_checks import _reference_random_games
+from tests.engine_harness import check_marks, step
 from tests.helpers import synthetic_evals_distinct
-from tests.test_engine_fixtures_oracle import _reference_random_games
-from tests.test_gpu_engine import check_marks
 
 pytestmark = pytest.mark.gpu
 
@@ -366,17 +366,10 @@ def _snapshot(e):
     return [(e.game_state(g).as_tuple(), [a.tobytes() for a in e.tree(g)], e.tree_raw(g).tobytes()) for g in range(e.G)]
 
 
-def _step(e):
-    e.select()
-    logits, values = synthetic_evals_distinct(e.leaves()[1])
-    e.set_evals(logits, values)
-    e.backup()
-
-
 def test_refused_while_a_selected_batch_awaits_its_backup():
     e = _small_engine()
     for _ in range(6):
-        _step(e)
+        step(e)
     mv = int(e.root_report()[0].moves[0])
     e.select()
     snap = _snapshot(e)

@@ -7,30 +7,14 @@ import re
 import numpy as np
 import pytest
 
-from ataxxzero_amd import link, model
-from oracle import oracle_lib as orc
+from ataxxzero_amd import link
+from tests import engine_harness as eh
 from tests import helpers
+from tests.engine_harness import START
 
 pytestmark = pytest.mark.gpu
 
-MAGIC = 0x415A4847
 SEED = 424242
-
-
-def _late_start():
-    """An unfinished fixture position with 10-14 empty squares and both sides well alive: games from it last a few dozen
-    plies, so thresholds, tree reuse, game ends and restarts all occur within a few hundred iterations."""
-    for rec in helpers.load_gz("rules_noblock.json.gz"):
-        p = orc.pos_from_fen(rec["fen"])
-        x, o = int(p.pieces[0]), int(p.pieces[1])
-        if orc.result(p) != 0 or len(orc.movegen(p)) == 0:
-            continue
-        if 10 <= 49 - bin(x | o).count("1") <= 14 and min(bin(x).count("1"), bin(o).count("1")) >= 10:
-            return x, o, int(p.turn)
-    raise AssertionError("no such fixture position")
-
-
-START = _late_start()
 
 
 def _engine(games, visits, weight=0.0, seed=SEED, flags=0, cap=None, K=1):
@@ -45,54 +29,8 @@ def _engine(games, visits, weight=0.0, seed=SEED, flags=0, cap=None, K=1):
     return e
 
 
-def _net(seed=3):
-    conv, bn = model.random_init(1, 128, seed=seed, perturb_bn=True)
-    return link.Net(conv, bn)
-
-
-def _step(e):
-    """one iteration of the step-wise API with the synthetic evaluator -> (need, leaf boards)"""
-    e.select()
-    need, lb = e.leaves()
-    logits, values = helpers.synthetic_evals_distinct(lb)
-    e.set_evals(logits, values)
-    e.backup()
-    return need, lb
-
-
-def _dump(e):
-    return [e.game_state(g).as_tuple() for g in range(e.G)], [e.tree(g) for g in range(e.G)]
-
-
-def _same(da, db):
-    (sa, ta), (sb, tb) = da, db
-    assert sa == sb
-    for x, y in zip(ta, tb):
-        for u, v in zip(x, y):
-            assert u.shape == v.shape and (u == v).all()
-
-
 def _strip_full(line):
     return re.sub(rb',"full":\[[01,]*\]', b"", line)
-
-
-def _records(words):
-    """[(slot, uid, result, kind word, [(move, full, {move: visits})])] of the staged record words (dropped markers skipped)"""
-    out, pos = [], 0
-    while pos < len(words):
-        assert words[pos] == MAGIC
-        slot, uid, plies, result, n, kind = (int(words[pos + i]) for i in (1, 2, 3, 4, 5, 7))
-        if kind & 3 != 1:
-            q, rows = pos + 8, []
-            for _ in range(plies):
-                nd = int(words[q + 4]) >> 16
-                rows.append((int(words[q + 4]) & 0xFFFF, int(words[q + 5]),
-                             {int(w) & 0xFFFF: int(w) >> 16 for w in words[q + 6:q + 6 + nd]}))
-                q += 6 + nd
-            assert q == pos + n
-            out.append((slot, uid, result, kind, rows))
-        pos += n
-    return out
 
 
 def test_lock_step_with_a_host_driven_uncapped_engine():
@@ -109,9 +47,9 @@ def test_lock_step_with_a_host_driven_uncapped_engine():
         kinds_seen.add(kind)
         inherited_fast += int(sb.phase == 0 and not kind and sb.root_visits >= fast)
         b.set_visits(visits if kind else fast)
-        _step(a)
-        _step(b)
-        _same(_dump(a), _dump(b))
+        eh.step(a)
+        eh.step(b)
+        eh.same(eh.dump(a), eh.dump(b))
         lines_a += a.drain_json()
         lines_b += b.drain_json()
         if len(lines_b) >= 3:
@@ -129,13 +67,13 @@ def test_lock_step_with_a_host_driven_uncapped_engine():
 @pytest.mark.parametrize("games", [5, 33, 130])
 def test_records_say_what_was_searched(games):
     visits, fast, frac = 16, 4, 16384
-    net = _net()
+    net = eh.net()
     e = _engine(games, visits, weight=0.25, cap=(fast, frac))
     recs, lines = [], []
     for _ in range(40):
         e.run(net, 100, link.DTYPE_BF16)
         e.fetch()
-        recs += _records(e.staged_records())
+        recs += eh.records3(e.staged_records())
         lines += e.drain_json()
         if {r[0] for r in recs} == set(range(games)):
             break
@@ -184,14 +122,14 @@ def test_root_noise_on_full_plies_only():
         if all(s.uid != g for g, s in enumerate(before)):
             break
         roots = np.array([a.tree(g)[0][0] for g in range(G)], dtype=np.uint64)
-        _step(a)
+        eh.step(a)
         due = [g for g, s in enumerate(before) if s.uid == g and s.phase == 0 and a.game_state(g).phase == 1]
         if not due:
             continue
         plies = np.array([s.ply for s in before], dtype=np.int32)
         for ref in (plain, noisy):
             ref.set_positions(roots, plies)
-            _step(ref)
+            eh.step(ref)
         for g in due:
             kind = link.playout_cap_kind(SEED, g, before[g].ply, frac)
             got, p0, p1 = _root_priors(a, g), _root_priors(plain, g), _root_priors(noisy, g)
@@ -234,7 +172,7 @@ def test_leaf_parallel_batches_stop_at_the_plys_own_threshold(K):
 
 
 def test_device_loop_equals_host_stepping_with_the_cap_on():
-    net = _net()
+    net = eh.net()
     n, G = 200, 33
     a = _engine(G, 16, weight=0.25, cap=(4, 16384))
     b = _engine(G, 16, weight=0.25, cap=(4, 16384))
@@ -244,7 +182,7 @@ def test_device_loop_equals_host_stepping_with_the_cap_on():
         b.select()
         b.eval(net, link.DTYPE_BF16)
         b.backup()
-    _same(_dump(a), _dump(b))
+    eh.same(eh.dump(a), eh.dump(b))
     assert a.stats() == b.stats() and a.stats()["plies"] > 10 * G
     la, lb = a.drain_json(), b.drain_json()
     assert sorted(la) == sorted(lb) and all(b'"full":[' in l for l in la)
@@ -252,7 +190,7 @@ def test_device_loop_equals_host_stepping_with_the_cap_on():
 
 
 def test_every_ply_full_and_switched_off_are_the_uncapped_engine():
-    net = _net(seed=5)
+    net = eh.net(seed=5)
     n, G = 400, 5
     ref = _engine(G, 12, weight=0.25)
     every = _engine(G, 12, weight=0.25, cap=(3, 65536))
@@ -261,8 +199,8 @@ def test_every_ply_full_and_switched_off_are_the_uncapped_engine():
     for e in (ref, every, off):
         e.run(net, n, link.DTYPE_F32)
         e.sync()
-    _same(_dump(ref), _dump(every))
-    _same(_dump(ref), _dump(off))
+    eh.same(eh.dump(ref), eh.dump(every))
+    eh.same(eh.dump(ref), eh.dump(off))
     want = ref.drain_json()
     assert len(want) >= G and not any(b"full" in l for l in want)
     assert off.drain_json() == want                      # byte for byte, no "full" key
@@ -279,7 +217,7 @@ def test_refusals_leave_the_engine_usable():
     for bad in [(25, 100), (-1, 100), (6, -1), (6, 65537)]:
         with pytest.raises(link.AzhError):
             e.set_playout_cap(*bad)
-    _step(e)
+    eh.step(e)
     e.set_playout_cap(6, 16384)
     with pytest.raises(link.AzhError):
         e.set_visits(5)                       # below fast_visits while the mode is on
@@ -294,7 +232,7 @@ def test_refusals_leave_the_engine_usable():
     e.set_playout_cap(0, 0)
     e.set_visits(5)                           # the mode is off: any value up to the engine's own
     for _ in range(30):
-        _step(e)
+        eh.step(e)
     assert e.stats()["plies"] > 0
     e.close()
     for flags in (link.FLAG_TWO_NETS, link.FLAG_ONE_RANDOM_MOVE):
@@ -302,7 +240,7 @@ def test_refusals_leave_the_engine_usable():
         with pytest.raises(link.AzhError):
             r.set_playout_cap(6, 16384)
         r.set_playout_cap(0, 0)               # switching off is no request for the mode
-        net = _net()
+        net = eh.net()
         if flags == link.FLAG_TWO_NETS:
             r.run_arena(net, net, 20, link.DTYPE_F32)
         else:

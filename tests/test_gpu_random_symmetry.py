@@ -13,9 +13,10 @@ import pytest
 
 from ataxxzero_amd import link, model
 from oracle import oracle_lib as orc
+from tests import engine_harness as eh
 from tests import helpers
+from tests import solver_reference as solver_ref
 from tests import symmetry_reference as sr
-from tests import test_solver_reference as solver_host
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +46,7 @@ def _midgame(G):
 
 def _late(G, max_empty=8):
     """G distinct unfinished fixture positions without blockers, a few plies before the end"""
-    ps = [(w0, w1) for w0, w1, bl in solver_host.late_positions(max_empty) if bl == 0]
+    ps = [(w0, w1) for w0, w1, bl in solver_ref.late_positions(max_empty) if bl == 0]
     assert len(ps) >= G
     return np.array([ps[(i * len(ps)) // G] for i in range(G)], dtype=np.uint64)
 
@@ -60,30 +61,6 @@ def _engine(G, visits=VISITS, flags=0, budget=0, weight=0.25, blockers=0, max_pl
     if positions is not None:
         e.set_positions(positions, np.zeros(G, np.int32))
     return e
-
-
-_NETS = {}
-
-
-def _net(blocks=2, seed=3):
-    if (blocks, seed) not in _NETS:
-        conv, bn = model.random_init(blocks, 128, seed=seed, perturb_bn=True)
-        _NETS[(blocks, seed)] = link.Net(conv, bn)
-    return _NETS[(blocks, seed)]
-
-
-def _dump(e, raw=False):
-    return ([e.game_state(g).as_tuple() for g in range(e.G)], [e.tree(g) for g in range(e.G)],
-            [e.tree_raw(g) for g in range(e.G)] if raw else [])
-
-
-def _same(da, db):
-    assert da[0] == db[0]
-    for x, y in zip(da[1], db[1]):
-        for u, v in zip(x, y):
-            assert u.shape == v.shape and (u == v).all()
-    for u, v in zip(da[2], db[2]):
-        assert u.shape == v.shape and (u == v).all()
 
 
 class _Coverage:
@@ -134,7 +111,7 @@ def _lock_step_one_leaf(flags=0, budget=0, min_plies=3, until_wide=False):
     the rows brought back through perm_s and the same values, over at least min_plies plies of every game (until_wide: and
     until a node of more than 128 edges has been evaluated) -> the coverage, and A's counters"""
     G = 5
-    net, pos = _net(), _midgame(G)
+    net, pos = eh.net(2), _midgame(G)
     a = _engine(G, flags=flags, budget=budget, positions=pos)
     b = _engine(G, flags=flags, budget=budget, positions=pos)
     a.set_random_symmetry(True)
@@ -151,7 +128,7 @@ def _lock_step_one_leaf(flags=0, budget=0, min_plies=3, until_wide=False):
         b.set_evals(sr.logits_of_the_position(logits, ss), values)
         a.backup()
         b.backup()
-        _same(_dump(a), _dump(b))
+        eh.same(eh.dump(a), eh.dump(b))
         _plies_played(st, [b.game_state(g) for g in range(G)], played)
         if played.min() >= min_plies and (cov.over128 or not until_wide):
             break
@@ -178,7 +155,7 @@ def test_lock_step_with_the_reference_flags_and_with_a_level_budget(flags, budge
 
 def test_cache_on_builds_the_trees_of_cache_off():
     G = 5
-    net, pos = _net(), _midgame(G)
+    net, pos = eh.net(2), _midgame(G)
     c = _engine(G, flags=link.FLAG_EVAL_CACHE, positions=pos)
     d = _engine(G, positions=pos)
     played = np.zeros(G, dtype=np.int64)
@@ -211,7 +188,7 @@ def test_cache_on_builds_the_trees_of_cache_off():
 
 def _lock_step_k_leaves(solver):
     G, K = 3, 4
-    net = _net()
+    net = eh.net(2)
     pos = _late(G) if solver else _midgame(G)
     visits = 48 if solver else VISITS
     a = _engine(G, visits=visits, positions=pos)
@@ -237,7 +214,7 @@ def _lock_step_k_leaves(solver):
         b.set_batch_evals(sr.logits_of_the_position(logits, ss), values)
         a.backup()
         b.backup()
-        _same(_dump(a, raw=True), _dump(b, raw=True))
+        eh.same(eh.dump(a, raw=True), eh.dump(b, raw=True))
         _plies_played(st, [b.game_state(g) for g in range(G)], played)
         if played.min() >= 3 and (not solver or a.proof_stats()["proven_nodes"] > 0):
             break
@@ -258,25 +235,13 @@ def test_lock_step_k_leaf_kernel_with_the_solver():
     assert proofs["proven_nodes"] > 0 and len(cov.symmetries) >= 6
 
 
-def _late_start():
-    """an unfinished fixture position with 10-14 empty squares and both sides well alive: games from it last a few dozen plies"""
-    for rec in helpers.load_gz("rules_noblock.json.gz"):
-        p = orc.pos_from_fen(rec["fen"])
-        x, o = int(p.pieces[0]), int(p.pieces[1])
-        if orc.result(p) != 0 or len(orc.movegen(p)) == 0:
-            continue
-        if 10 <= 49 - bin(x | o).count("1") <= 14 and min(bin(x).count("1"), bin(o).count("1")) >= 10:
-            return x, o, int(p.turn)
-    raise AssertionError("no such fixture position")
-
-
 @pytest.mark.parametrize("games,extras", [(5, False), (33, False), (130, False), (33, True)])
 def test_device_loop_equals_host_stepping(games, extras):
     """extras: the playout cap and forced playouts on as well"""
-    net, n = _net(), 200
+    net, n = eh.net(2), 200
     engines = []
     for _ in range(2):
-        e = _engine(games, visits=16, max_plies=400, start=_late_start())
+        e = _engine(games, visits=16, max_plies=400, start=eh.late_start())
         e.set_random_symmetry(True)
         if extras:
             e.set_playout_cap(4, 16384)
@@ -291,7 +256,7 @@ def test_device_loop_equals_host_stepping(games, extras):
             b.select()
             b.eval(net, link.DTYPE_BF16)
             b.backup()
-        _same(_dump(a), _dump(b))
+        eh.same(eh.dump(a), eh.dump(b))
         assert a.stats() == b.stats()
         la += a.drain_json()
         lb += b.drain_json()
@@ -308,7 +273,7 @@ def test_game_lines_of_a_mode_on_run_are_real_games():
     p = orc.pos_from_fen(orc.START_FEN_SELFPLAY)
     e = _engine(G, visits=8, max_plies=400, blockers=helpers.BLOCK4_MASK, start=(int(p.pieces[0]), int(p.pieces[1]), 0))
     e.set_random_symmetry(True)
-    net, lines = _net(), []
+    net, lines = eh.net(2), []
     for _ in range(60):
         e.run(net, 100, link.DTYPE_BF16)
         lines += e.drain_json()
@@ -324,14 +289,14 @@ def test_game_lines_of_a_mode_on_run_are_real_games():
 
 
 def test_off_is_off():
-    net, n, G = _net(), 400, 5
-    ref = _engine(G, visits=12, max_plies=400, start=_late_start())
-    never = _engine(G, visits=12, max_plies=400, start=_late_start())
+    net, n, G = eh.net(2), 400, 5
+    ref = _engine(G, visits=12, max_plies=400, start=eh.late_start())
+    never = _engine(G, visits=12, max_plies=400, start=eh.late_start())
     never.set_random_symmetry(False)
-    off = _engine(G, visits=12, max_plies=400, start=_late_start())
+    off = _engine(G, visits=12, max_plies=400, start=eh.late_start())
     off.set_random_symmetry(True)
     off.set_random_symmetry(False)
-    on = _engine(G, visits=12, max_plies=400, start=_late_start())
+    on = _engine(G, visits=12, max_plies=400, start=eh.late_start())
     on.set_random_symmetry(True)
     want = []
     for chunk in range(5):        # (until every slot's worth of games has ended)
@@ -340,19 +305,19 @@ def test_off_is_off():
             e.sync()
         lines = ref.drain_json()
         for e in (never, off):
-            _same(_dump(ref), _dump(e))
+            eh.same(eh.dump(ref), eh.dump(e))
             assert e.drain_json() == lines and e.stats() == ref.stats()
         want += lines
         if len(want) >= G:
             break
     assert len(want) >= G
-    assert [t[2].tobytes() for t in _dump(on)[1]] != [t[2].tobytes() for t in _dump(ref)[1]]    # (and on is not off)
+    assert [t[2].tobytes() for t in eh.dump(on)[1]] != [t[2].tobytes() for t in eh.dump(ref)[1]]    # (and on is not off)
     for e in (ref, never, off, on):
         e.close()
 
 
 def test_refusals_leave_the_engine_as_it_was():
-    net = _net()
+    net = eh.net(2)
     inner = ((1 << 8) | (1 << 40), (1 << 12) | (1 << 36), 0)       # a start position that keeps clear of the corners
     corners = (1 << 0) | (1 << 6) | (1 << 42) | (1 << 48)
     for kwargs, word in [(dict(flags=link.FLAG_ARENA), "AZH_FLAG_TWO_NETS"), (dict(flags=link.FLAG_SYMMETRY_AVG), "AZH_FLAG_SYMMETRY_AVG"),

@@ -11,32 +11,16 @@ import re
 import numpy as np
 import pytest
 
-from ataxxzero_amd import link, model
-from oracle import oracle_lib as orc
+from ataxxzero_amd import link
+from tests import engine_harness as eh
 from tests import helpers
 from tests import resign_reference as ref
+from tests.engine_harness import START
 
 pytestmark = pytest.mark.gpu
 
-MAGIC = 0x415A4847
 SEED = 424242
-KIND_CAP, KIND_VALUES, KIND_RESIGNED = 4, 16, 32
-
-
-def _late_start():
-    """An unfinished fixture position with 10-14 empty squares and both sides well alive (as test_gpu_playout_cap.py's):
-    games from it last a few dozen plies."""
-    for rec in helpers.load_gz("rules_noblock.json.gz"):
-        p = orc.pos_from_fen(rec["fen"])
-        x, o = int(p.pieces[0]), int(p.pieces[1])
-        if orc.result(p) != 0 or len(orc.movegen(p)) == 0:
-            continue
-        if 10 <= 49 - bin(x | o).count("1") <= 14 and min(bin(x).count("1"), bin(o).count("1")) >= 10:
-            return x, o, int(p.turn)
-    raise AssertionError("no such fixture position")
-
-
-START = _late_start()
+KIND_CAP, KIND_VALUES, KIND_RESIGNED = link.REC_KIND_PLAYOUT_CAP, link.REC_KIND_VALUES, link.REC_KIND_RESIGNED
 
 
 def _engine(games, visits, weight=0.0, seed=SEED, flags=0, resign=None, cap=None, K=1):
@@ -53,103 +37,14 @@ def _engine(games, visits, weight=0.0, seed=SEED, flags=0, resign=None, cap=None
     return e
 
 
-def _net(seed=3):
-    conv, bn = model.random_init(1, 128, seed=seed, perturb_bn=True)
-    return link.Net(conv, bn)
-
-
-def _step(e, evals=helpers.synthetic_evals_distinct):
-    e.select()
-    need, lb = e.leaves()
-    logits, values = evals(lb)
-    e.set_evals(logits, values)
-    e.backup()
-
-
-def _dump(e, slots=None):
-    slots = range(e.G) if slots is None else slots
-    return [e.game_state(g).as_tuple() for g in slots], [e.tree(g) for g in slots]
-
-
-def _same(da, db):
-    (sa, ta), (sb, tb) = da, db
-    assert sa == sb
-    for x, y in zip(ta, tb):
-        for u, v in zip(x, y):
-            assert u.shape == v.shape and (u == v).all()
-
-
 def _strip_values(line):
     return re.sub(rb',"values":\[[^\]]*\]', b"", line)
 
 
-def _records(words):
-    """[(slot, uid, result, kind word, [(move, word 5, {move: visits}, (x, o))])] of staged record words (markers skipped)"""
-    out, pos = [], 0
-    while pos < len(words):
-        assert words[pos] == MAGIC
-        slot, uid, plies, result, n, kind = (int(words[pos + i]) for i in (1, 2, 3, 4, 5, 7))
-        if kind & 3 != 1:
-            q, rows = pos + 8, []
-            for _ in range(plies):
-                nd = int(words[q + 4]) >> 16
-                board = (int(words[q]) | int(words[q + 1]) << 32, int(words[q + 2]) | int(words[q + 3]) << 32)
-                rows.append((int(words[q + 4]) & 0xFFFF, int(words[q + 5]),
-                             {int(w) & 0xFFFF: int(w) >> 16 for w in words[q + 6:q + 6 + nd]}, board))
-                q += 6 + nd
-            assert q == pos + n
-            out.append((slot, uid, result, kind, rows))
-        pos += n
-    return out
-
-
 def _collect(e, recs, lines):
     e.fetch()
-    recs += _records(e.staged_records())
+    recs += eh.records(e.staged_records())
     lines += e.drain_json()
-
-
-def _mover(ply):
-    """games of these engines begin at START, ply 0, and every move (a pass too) hands the turn over"""
-    return 1 + (START[2] + ply) % 2
-
-
-def _sequence(rows, kind):
-    """a record's plies as the reference rule takes them: [(mover, q bits, counted?)] from its own word-5 values"""
-    return [(_mover(p),) + ref.decode_word5(w5, bool(kind & KIND_CAP)) for p, (_, w5, _, _) in enumerate(rows)]
-
-
-def _ends_finished(rows, n_before):
-    """the last board plus the last move is a position the rules adjudicate as finished"""
-    move, _, _, (x, o) = rows[-1]
-    turn = (START[2] + n_before + len(rows) - 1) % 2
-    board = np.array([[x | (turn << 63), o]], dtype=np.uint64)
-    after = link.makemove_batch(board, np.array([move], dtype=np.uint16))
-    return int(link.rules_batch(after, 0)[2][0]) != 0
-
-
-def _check_records(recs, q_below, consecutive, share, seed=SEED):
-    """Every record against the reference rule on its own word-5 values -> the resign stats recounted from the records."""
-    stats = {"resigned": 0, "playthrough": 0, "playthrough_fired": 0, "playthrough_false": 0}
-    for slot, uid, result, kind, rows in recs:
-        assert kind & KIND_VALUES and result in (1, 2), (uid, kind, result)
-        seq = _sequence(rows, kind)
-        fire = ref.first_fire(seq, q_below, consecutive)
-        through = link.resign_playthrough(seed, uid, share)
-        if kind & KIND_RESIGNED:
-            assert not through, uid                               # a game plays through iff the draw says so
-            assert fire == (len(rows) - 1, seq[-1][0]), (uid, fire, len(rows))    # no longer, no shorter
-            assert result == 3 - seq[-1][0], uid
-            stats["resigned"] += 1
-        else:
-            assert through or fire is None, (uid, fire)
-            assert _ends_finished(rows, 0), uid
-            if through:
-                stats["playthrough"] += 1
-                if fire is not None:
-                    stats["playthrough_fired"] += 1
-                    stats["playthrough_false"] += int(result != 3 - fire[1])
-    return stats
 
 
 # ------------------------------------------------------------------ 1. recording changes no game
@@ -170,11 +65,11 @@ def _recorded_run():
             q, visited = ref.ply_value(rep.visits, rep.scores)
             ties += int((rep.visits == rep.visits.max()).sum() > 1)
             mover = 1 + (int(b.tree(0)[0][0][0]) >> 63)
-            assert mover == _mover(sb.ply)
+            assert mover == eh.mover(sb.ply)
             expect[(sb.uid, sb.ply)] = (q, visited, mover)
-        _step(a)
-        _step(b)
-        _same(_dump(a), _dump(b))
+        eh.step(a)
+        eh.step(b)
+        eh.same(eh.dump(a), eh.dump(b))
         lines_a += a.drain_json()
         lines_b += b.drain_json()
         if len(lines_b) >= 3:
@@ -231,11 +126,11 @@ def test_games_resign_where_the_rule_says_and_the_slot_restarts():
         for g in sorted(live):
             if sb[g].phase == 2 and sb[g].uid == g:
                 q, visited = ref.ply_value(reports[g].visits, reports[g].scores)
-                seq[g].append((_mover(sb[g].ply), ref.q_bits(q), visited))
+                seq[g].append((eh.mover(sb[g].ply), ref.q_bits(q), visited))
                 assert len(seq[g]) == sb[g].ply + 1
                 due[g] = ref.replay(seq[g], t, 2)[-1]
-        _step(a)
-        _step(b)
+        eh.step(a)
+        eh.step(b)
         for g in sorted(live):
             sa, sb2 = a.game_state(g), b.game_state(g)
             if due.get(g):
@@ -247,7 +142,7 @@ def test_games_resign_where_the_rule_says_and_the_slot_restarts():
             elif sb2.uid != g:
                 assert sa.uid == sb2.uid           # a real end, in both
                 live.discard(g)
-        _same(_dump(a, sorted(live)), _dump(b, sorted(live)))
+        eh.same(eh.dump(a, sorted(live)), eh.dump(b, sorted(live)))
         if it % 16 == 0:
             _collect(a, recs_a, lines_a2)
             _collect(b, recs_b, lines_b2)
@@ -277,7 +172,7 @@ def test_games_resign_where_the_rule_says_and_the_slot_restarts():
     assert len(got) == a.resign_stats()["resigned"] >= len(resigned_at)
     for e in got:
         assert list(e.keys()) == ["boards", "dists", "moves", "resigned", "result", "values"]
-        assert e["resigned"] == 3 - e["result"] == _mover(len(e["moves"]) - 1)
+        assert e["resigned"] == 3 - e["result"] == eh.mover(len(e["moves"]) - 1)
     assert a.stats()["games"] == len(recs_a)
     a.close(), b.close()
 
@@ -289,7 +184,7 @@ def _loop_threshold():
     """The threshold of the device-loop tests: the 0.3 quantile of the values a 33-game engine with the tests' random net
     records in 300 iterations with resignation off (q_below = 0) — low enough that games are played for a while, high enough
     that, with two consecutive plies of a side needed, games do resign."""
-    net = _net()
+    net = eh.net()
     e = _engine(33, 16, weight=0.25, resign=(0.0, 1, 0))
     recs, lines = [], []
     e.run(net, 300, link.DTYPE_BF16)
@@ -303,7 +198,7 @@ def _loop_threshold():
 @pytest.mark.parametrize("games", [5, 33, 130])
 def test_play_through_games_are_the_ones_the_draw_names(games):
     t, k, share = _loop_threshold(), 2, 16384
-    net = _net()
+    net = eh.net()
     e = _engine(games, 16, weight=0.25, resign=(t, k, share))
     recs, lines = [], []
     for _ in range(40):
@@ -313,7 +208,7 @@ def test_play_through_games_are_the_ones_the_draw_names(games):
             break
     assert {r[0] for r in recs} == set(range(games))       # every slot has finished a game
     assert len(lines) == len(recs) and all(r[1] % games == r[0] for r in recs)
-    stats = _check_records(recs, t, k, share)
+    stats = eh.check_resign_records(recs, t, k, share)
     assert e.resign_stats() == stats
     assert e.stats()["games"] == len(recs)
     if games >= 33:
@@ -327,7 +222,7 @@ def test_play_through_games_are_the_ones_the_draw_names(games):
 
 def test_fast_plies_neither_advance_nor_reset_a_counter():
     G, visits, fast, frac, t, k = 33, 16, 4, 16384, _loop_threshold(), 2
-    net = _net()
+    net = eh.net()
     e = _engine(G, visits, weight=0.25, cap=(fast, frac), resign=(t, k, 0))
     recs, lines = [], []
     for _ in range(40):
@@ -345,9 +240,9 @@ def test_fast_plies_neither_advance_nor_reset_a_counter():
             assert 0.0 <= float(ref.q_of_bits(w5)) <= 1.0
             fulls += full
             fasts += 1 - full
-        every = [(m, bits, True) for m, bits, _ in _sequence(rows, kind)]
-        differs += int(ref.first_fire(every, t, k) != ref.first_fire(_sequence(rows, kind), t, k))
-    stats = _check_records(recs, t, k, 0)
+        every = [(m, bits, True) for m, bits, _ in eh.resign_sequence(rows, kind)]
+        differs += int(ref.first_fire(every, t, k) != ref.first_fire(eh.resign_sequence(rows, kind), t, k))
+    stats = eh.check_resign_records(recs, t, k, 0)
     assert e.resign_stats() == stats and stats["resigned"] > 0
     assert fasts > fulls > 0 and differs > 0       # the rule over all plies would have ended games elsewhere
     for line in lines:
@@ -361,7 +256,7 @@ def test_fast_plies_neither_advance_nor_reset_a_counter():
 
 @pytest.mark.parametrize("K", [1, 4])
 def test_device_loop_equals_host_stepping_with_the_mode_on(K):
-    net = _net()
+    net = eh.net()
     n, G, t, k, share = 200, 33 if K == 1 else 9, _loop_threshold(), 2, 16384
     a = _engine(G, 16, weight=0.25, resign=(t, k, share), K=K)
     b = _engine(G, 16, weight=0.25, resign=(t, k, share), K=K)
@@ -371,13 +266,13 @@ def test_device_loop_equals_host_stepping_with_the_mode_on(K):
         b.select()
         b.eval(net, link.DTYPE_BF16)
         b.backup()
-    _same(_dump(a), _dump(b))
+    eh.same(eh.dump(a), eh.dump(b))
     assert a.stats() == b.stats() and a.stats()["plies"] > 5 * G
     assert a.resign_stats() == b.resign_stats()
     recs, la, lb = [], [], b.drain_json()
     _collect(a, recs, la)
     assert sorted(la) == sorted(lb) and len(la) > 0 and all(b'"values":[' in l for l in la)
-    assert _check_records(recs, t, k, share) == a.resign_stats()      # records obey the rule (K leaves per game too)
+    assert eh.check_resign_records(recs, t, k, share) == a.resign_stats()      # records obey the rule (K leaves per game too)
     assert a.resign_stats()["resigned"] > 0
     a.close(), b.close()
 
@@ -410,13 +305,13 @@ def test_values_that_are_not_finite(evals):
     e = _engine(G, 12, resign=(t, 1, 0))
     recs, lines = [], []
     for it in range(6000):
-        _step(e, evals)
+        eh.step(e, evals)
         if it % 100 == 99:
             _collect(e, recs, lines)
             if len(recs) >= G:
                 break
     assert len(recs) >= G and e.stats()["plies"] > 5 * G and len(lines) == len(recs)
-    assert _check_records(recs, t, 1, 0) == e.resign_stats()
+    assert eh.check_resign_records(recs, t, 1, 0) == e.resign_stats()
     odd, want = 0, []
     for _, _, _, kind, rows in recs:
         qs = [float(ref.q_of_bits(w5)) for _, w5, _, _ in rows]
@@ -432,7 +327,7 @@ def test_values_that_are_not_finite(evals):
 # ------------------------------------------------------------------ 8. off is the parent, 9. refusals
 
 def test_switched_off_is_the_engine_without_the_mode():
-    net = _net(seed=5)
+    net = eh.net(seed=5)
     n, G = 400, 5
     ref_e = _engine(G, 12, weight=0.25)
     off = _engine(G, 12, weight=0.25, resign=(0.47, 2, 16384))
@@ -440,7 +335,7 @@ def test_switched_off_is_the_engine_without_the_mode():
     for e in (ref_e, off):
         e.run(net, n, link.DTYPE_F32)
         e.sync()
-    _same(_dump(ref_e), _dump(off))
+    eh.same(eh.dump(ref_e), eh.dump(off))
     want = ref_e.drain_json()
     assert len(want) >= G and not any(b"values" in l or b"resigned" in l for l in want)
     recs, got = [], []
@@ -457,7 +352,7 @@ def test_refusals_leave_the_engine_usable():
                 (0.3, 2, -1)]:
         with pytest.raises(link.AzhError):
             e.set_resign(*bad)
-        _step(e)
+        eh.step(e)
     e.set_resign(0.3, 255, 65536)
     e.set_resign(0.0, 1, 0)
     e.select()
@@ -470,7 +365,7 @@ def test_refusals_leave_the_engine_usable():
     e.backup()
     e.set_resign(0.3, 2, 0)
     for _ in range(60):
-        _step(e)
+        eh.step(e)
     assert e.stats()["plies"] > 0
     e.set_resign(0.0, 0, 0)
     e.close()
@@ -479,7 +374,7 @@ def test_refusals_leave_the_engine_usable():
         with pytest.raises(link.AzhError):
             r.set_resign(0.3, 2, 0)
         r.set_resign(0.0, 0, 0)               # switching off is no request for the mode
-        net = _net()
+        net = eh.net()
         if flags == link.FLAG_TWO_NETS:
             r.run_arena(net, net, 20, link.DTYPE_F32)
         else:

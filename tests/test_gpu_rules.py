@@ -147,7 +147,7 @@ def test_reference_random_play_games_replay_on_the_gpu():
     for every ply the GPU must list the played move as legal, adjudicate the position as ongoing, and make-move must
     give the next recorded board; the last move must end the game with the recorded result."""
     import json
-    from tests.test_engine_fixtures_oracle import _reference_random_games
+    from tests.engine_fixture_checks import _reference_random_games
 
     def pack(cells, ply):
         x = o = 0

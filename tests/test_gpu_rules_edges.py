@@ -9,7 +9,7 @@ from ataxxzero_amd import link
 from oracle import oracle_lib as orc
 from tests import rules_reference as rr
 from tests.helpers import load_gz, synthetic_evals_distinct
-from tests.test_rules_reference import BLOCK3_MASK, orc_pos, pocket_boards
+from tests.helpers import BLOCK3_MASK, orc_pos, pocket_boards
 
 pytestmark = pytest.mark.gpu
 
@@ -177,7 +177,7 @@ def edge_roots(name, limit=64):
 
 @pytest.mark.parametrize("name", ["none", "block3", "wall8"])
 def test_engine_on_edge_roots_matches_the_oracle_in_lock_step(name):
-    from tests.test_gpu_engine import compare_all, make_pair, run_lockstep
+    from tests.engine_harness import compare_all, make_pair, run_lockstep
 
     mask, recs, boards, packed = edge_roots(name)
     G = len(boards)

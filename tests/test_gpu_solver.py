@@ -11,9 +11,9 @@ import pytest
 
 from ataxxzero_amd import link, model
 from oracle import oracle_lib as orc
+from tests import engine_harness as eh
 from tests import helpers
 from tests import solver_reference as sr
-from tests import test_solver_reference as host
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +23,7 @@ UAI = link.FLAG_NO_REUSE | link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR
 
 def _late(G, blockers, max_empty=10):
     """G distinct unfinished fixture positions of the blocker set with at most `max_empty` empty cells, spread over them."""
-    ps = [(w0, w1) for w0, w1, bl in host.late_positions(max_empty) if bl == blockers]
+    ps = [(w0, w1) for w0, w1, bl in sr.late_positions(max_empty) if bl == blockers]
     assert len(ps) >= G
     return np.array([ps[(i * len(ps)) // G] for i in range(G)], dtype=np.uint64)
 
@@ -125,15 +125,6 @@ def test_the_matrix_met_win_loss_chained_and_root_proofs():
     assert all(v > 0 for v in total.values()), total
 
 
-def _net(blocks=2, seed=3):
-    conv, bn = model.random_init(blocks, 128, seed=seed, perturb_bn=True)
-    return link.Net(conv, bn)
-
-
-def _dump(e):
-    return [e.game_state(g).as_tuple() for g in range(e.G)], [e.tree(g) for g in range(e.G)], [e.tree_raw(g) for g in range(e.G)]
-
-
 def _same(x, y):
     return x[0] == y[0] and all((u == v).all() for a, b in zip(x[1], y[1]) for u, v in zip(a, b)) and \
         all((u == v).all() for u, v in zip(x[2], y[2]))
@@ -183,7 +174,7 @@ def test_device_loop_equals_host_stepping_and_proofs_survive_re_roots(case):
 
 
 def _device_loop(G, K, dtype, visits, n):
-    net = _net()
+    net = eh.net(2)
     a, _ = _engine(G, K, 2, 0, visits=visits)
     b, _ = _engine(G, K, 2, 0, visits=visits)
     a.run(net, n, dtype)
@@ -207,7 +198,7 @@ def _device_loop(G, K, dtype, visits, n):
                 carried += sum(1 for row in t1[1] if sr.is_proven(row))
         b.eval(net, dtype)
         b.backup()
-    assert _same(_dump(a), _dump(b))
+    assert _same(eh.dump(a, raw=True), eh.dump(b, raw=True))
     assert a.stats() == b.stats() and a.proof_stats() == b.proof_stats()
     assert a.stats()["plies"] > 0 and a.proof_stats()["proven_nodes"] > 0
     a.close(), b.close()
@@ -219,7 +210,7 @@ def test_proven_nodes_were_carried_into_new_trees():
 
 
 def test_play_moves_carries_the_marks():
-    net = _net()
+    net = eh.net(2)
     e, cfg = _engine(2, 16, 2, 0, visits=400)
     e.run(net, 12, link.DTYPE_F32)
     e.sync()
@@ -245,7 +236,7 @@ def test_play_moves_carries_the_marks():
 
 
 def test_switched_on_and_off_again_is_an_untouched_engine():
-    net = _net()
+    net = eh.net(2)
     for K in (1, 16):
         a, _ = _engine(4, K, 2, 0, solver=False)
         b, _ = _engine(4, K, 2, 0, solver=False)
@@ -253,7 +244,7 @@ def test_switched_on_and_off_again_is_an_untouched_engine():
         a.set_solver(False)
         a.run(net, 30, link.DTYPE_BF16)
         b.run(net, 30, link.DTYPE_BF16)
-        assert _same(_dump(a), _dump(b)) and a.stats() == b.stats()
+        assert _same(eh.dump(a, raw=True), eh.dump(b, raw=True)) and a.stats() == b.stats()
         assert a.proof_stats() == {"proven_nodes": 0, "proven_hits": 0}
         if K == 1:   # the one-leaf calls are back
             a.select()
@@ -308,20 +299,20 @@ def _mates():
     """Blocker-free fixture positions whose side to move wins in exactly 1 and in exactly 3 plies (host minimax):
     {plies: (packed words, set of the moves that win that fast)}."""
     out = {}
-    for w0, w1, bl in host.late_positions(4):
+    for w0, w1, bl in sr.late_positions(4):
         if bl != 0:
             continue
         for plies in (1, 3):
             if plies in out:
                 continue
-            p = host._pos(w0, w1, 0)
-            if host._minimax(p, plies, {}, nodes=20000) != 1 or (plies == 3 and host._minimax(p, 1, {}) == 1):
+            p = sr._pos(w0, w1, 0)
+            if sr._minimax(p, plies, {}, nodes=20000) != 1 or (plies == 3 and sr._minimax(p, 1, {}) == 1):
                 continue
             wins = set()
             for mv in orc.movegen(p):
-                q = host._pos(w0, w1, 0)
+                q = sr._pos(w0, w1, 0)
                 orc.lib().orc_makemove(q, int(mv) & 0xFF, int(mv) >> 8)
-                if host._minimax(q, plies - 1, {}, nodes=20000) == -1:
+                if sr._minimax(q, plies - 1, {}, nodes=20000) == -1:
                     wins.add(int(mv))
             out[plies] = ((w0, w1), wins)
         if len(out) == 2:
@@ -342,9 +333,9 @@ def test_genmove_plays_the_mating_move(tmp_path, K):
             # a proven winning move wins; the first one in edge order is played
             proven = [m for m, v in s.last_proofs[1] if v == -1]
             assert mv == proven[0]
-            q = host._pos(w0, w1, 0)
+            q = sr._pos(w0, w1, 0)
             orc.lib().orc_makemove(q, mv & 0xFF, mv >> 8)
-            assert host._minimax(q, 8, {}, nodes=200000) == -1
+            assert sr._minimax(q, 8, {}, nodes=200000) == -1
             if plies == 1:
                 assert mv in wins
 

@@ -12,13 +12,14 @@ import pytest
 
 from ataxxzero_amd import link, model
 from oracle import oracle_lib as orc
+from tests import engine_harness as eh
 from tests import forced_reference as fr
 from tests import helpers
 from tests import priors_reference as pr
 from tests import symmetry_reference as sym
 from tests import temperature_reference as ref
 from tests import vl_reference as vlr
-from tests.test_gpu_resign import START, _check_records, _dump, _net, _records, _same
+from tests.engine_harness import START
 
 pytestmark = pytest.mark.gpu
 
@@ -43,37 +44,10 @@ def _cycle(max_plies=400):
     return np.array([CYCLE[p % len(CYCLE)] for p in range(max_plies)], dtype=np.float32)
 
 
-def _step(e, K=1):
-    """one iteration with the synthetic evaluator -> the logits by slot, (G K, 833)"""
-    e.select()
-    if K == 1:
-        _, lb = e.leaves()
-        logits, values = helpers.synthetic_evals_distinct(lb)
-        e.set_evals(logits, values)
-    else:
-        _, lb, _ = e.batch_leaves()
-        logits, values = helpers.synthetic_evals_distinct(lb.reshape(-1, 2))
-        e.set_batch_evals(logits, values)
-    e.backup()
-    return logits
-
-
-def _staged(e):
-    e.fetch()
-    words = e.staged_records().copy()
-    e.drain_json()
-    return words
-
-
 def _by_uid(words):
     """the staged records, each as its bytes, in uid order (records of games that end in the same iteration reach the ring
     in any order)"""
-    out, pos = [], 0
-    while pos < len(words):
-        assert words[pos] == 0x415A4847
-        out.append((int(words[pos + 2]), words[pos:pos + int(words[pos + 5])].tobytes()))
-        pos += int(words[pos + 5])
-    return sorted(out)
+    return sorted((r.uid, r.words.tobytes()) for r in link.records(words, markers=True))
 
 
 def _check_rule(recs, table, seed, seen):
@@ -106,7 +80,7 @@ def _assert_seen(seen, games):
 # ------------------------------------------------------------------ 1. off is off
 
 def test_off_is_off():
-    net, games, visits, plies = _net(), 5, 16, 12
+    net, games, visits, plies = eh.net(), 5, 16, 12
     ones = np.ones(plies, dtype=np.float32)
     kw = dict(max_plies=plies, flags=link.FLAG_KEEP_UNFINISHED)
     never = _engine(games, visits, **kw)
@@ -118,11 +92,11 @@ def test_off_is_off():
     for e in (never, unit, cleared, on):
         e.run(net, 400, link.DTYPE_F32)
         e.sync()
-        words[id(e)] = _staged(e)
-    assert len(_records(words[id(never)])) >= games       # every slot played its 12 plies at least once
+        words[id(e)] = eh.staged(e)
+    assert len(eh.records(words[id(never)])) >= games       # every slot played its 12 plies at least once
     for e in (unit, cleared):
         assert _by_uid(words[id(e)]) == _by_uid(words[id(never)])
-        _same(_dump(e), _dump(never))
+        eh.same(eh.dump(e), eh.dump(never))
         assert e.stats() == never.stats()
     assert _by_uid(words[id(on)]) != _by_uid(words[id(never)])    # (and on is not off)
     for e in (never, unit, cleared, on):
@@ -137,9 +111,9 @@ def test_every_ply_obeys_the_rule_with_host_stepping(games):
     e = _engine(games, 24, move=table)
     recs = []
     for it in range(3000):
-        _step(e)
+        eh.step(e)
         if it % 100 == 99:
-            recs += _records(_staged(e))
+            recs += eh.records(eh.staged(e))
             if len(recs) >= games:
                 break
     seen = _new_seen()
@@ -151,13 +125,13 @@ def test_every_ply_obeys_the_rule_with_host_stepping(games):
 
 @pytest.mark.parametrize("games", [5, 68])
 def test_every_ply_obeys_the_rule_in_the_device_loop(games):
-    net, table = _net(), _cycle()
+    net, table = eh.net(), _cycle()
     e = _engine(games, 24, move=table)
     recs = []
     for chunk in range(6):
         e.run(net, 300, link.DTYPE_BF16)
         e.sync()
-        recs += _records(_staged(e))
+        recs += eh.records(eh.staged(e))
         if len(recs) >= games:
             break
     seen = _new_seen()
@@ -169,14 +143,14 @@ def test_every_ply_obeys_the_rule_in_the_device_loop(games):
 
 @pytest.mark.parametrize("games", [5, 68])
 def test_every_ply_obeys_the_rule_with_two_engines_enqueued_in_turn(games):
-    net, table = _net(), _cycle()
+    net, table = eh.net(), _cycle()
     engines = [_engine(games, 24, seed=SEED + 1000003 * i, move=table) for i in range(2)]
     recs = [[], []]
     for chunk in range(6):
         link.run_engines(engines, net, 300, link.DTYPE_BF16)
         for i, e in enumerate(engines):
             e.sync()
-            recs[i] += _records(_staged(e))
+            recs[i] += eh.records(eh.staged(e))
         if min(len(r) for r in recs) >= games:
             break
     for i, e in enumerate(engines):
@@ -198,8 +172,7 @@ def test_wide_roots(T):
     """The four wide roots of tests/test_gpu_vl_edges.py (117, 165, 193 and 112-123 moves), one ply each: the counts of
     azh_engine_root_report before the move is played give the reference's pick, and the next root is the position after it.
     (The seed is the one of that file's wide-node test: its root noise sends visits to the last edge of the 193-move board.)"""
-    from tests.test_gpu_vl_edges import _wide_roots
-    positions = _wide_roots()
+    positions = eh._wide_roots()
     G, visits, ply = len(positions), 400, 10
     p = orc.pos_from_fen(orc.START_FEN_PLAIN)
     cfg = link.Config(games=G, visits=visits, max_plies=400, edges_per_node=200, c_puct=1.0, dirichlet_alpha=ALPHA,
@@ -223,7 +196,7 @@ def test_wide_roots(T):
                 WIDE_SEEN["beyond64"] += int((rep.visits[64:] > 0).any())
                 WIDE_SEEN["beyond128"] += int((rep.visits[128:] > 0).any())
                 WIDE_SEEN["picked_beyond64"] += int(j >= 64)
-        _step(e)
+        eh.step(e)
         for g, (st, tree, j, mv) in due.items():
             board, res, _, _ = vlr.expand_position(tree[0][0][0], tree[0][0][1], mv, 0)
             now = e.game_state(g)
@@ -290,7 +263,7 @@ def test_root_priors_are_the_references(weight, R, symmetry, K):
         e.set_leaf_batch(K, 1)
     roots = [e.tree(g) for g in range(G)]
     assert all(e.game_state(g).phase == 0 for g in range(G))
-    logits = _step(e, K)                         # the root evaluations
+    logits = eh.step(e, K=K)[2]                         # the root evaluations
     want = []
     for g in range(G):
         s = _symmetry(symmetry, SEED, g, roots[g][0][0])
@@ -311,7 +284,7 @@ def test_root_priors_are_the_references(weight, R, symmetry, K):
                 checked.add(g)
         if len(checked) == G:
             break
-        _step(e, K)
+        eh.step(e, K=K)
     assert len(checked) == G
     assert others >= G * 4
     e.close()
@@ -344,9 +317,9 @@ def test_plies_with_an_entry_of_one_and_fast_plies_keep_their_priors(K):
         first = [g for g in range(G) if plain.game_state(g).ply == 0 and unit.game_state(g).ply == 0]
         first_fast = [g for g in fast if capped.game_state(g).ply == 0 and tempered.game_state(g).ply == 0]
         for e in (plain, unit, capped, tempered):
-            _step(e, K)
-        _same(_dump(plain, first), _dump(unit, first))
-        _same(_dump(capped, first_fast), _dump(tempered, first_fast))
+            eh.step(e, K=K)
+        eh.same(eh.dump(plain, first), eh.dump(unit, first))
+        eh.same(eh.dump(capped, first_fast), eh.dump(tempered, first_fast))
         moved += sum(int(plain.game_state(g).ply == 1) for g in first) + sum(int(capped.game_state(g).ply == 1) for g in first_fast)
         if it == 0:                                 # the root evaluations of ply 0: the FULL ones did get the temperature
             for g in range(G):
@@ -360,14 +333,14 @@ def test_plies_with_an_entry_of_one_and_fast_plies_keep_their_priors(K):
 # ------------------------------------------------------------------ 5. in company
 
 def test_fast_plies_of_the_playout_cap_sample_by_the_table_too():
-    net, table, games = _net(), _cycle(), 9
+    net, table, games = eh.net(), _cycle(), 9
     e = _engine(games, 24, move=table)
     e.set_playout_cap(6, 32768)
     recs = []
     for chunk in range(6):
         e.run(net, 300, link.DTYPE_BF16)
         e.sync()
-        recs += _records(_staged(e))
+        recs += eh.records(eh.staged(e))
         if len(recs) >= games:
             break
     seen = _new_seen()
@@ -375,7 +348,7 @@ def test_fast_plies_of_the_playout_cap_sample_by_the_table_too():
     _assert_seen(seen, games)
     fast = {float(T): 0 for T in CYCLE}
     for slot, uid, result, kind, rows in recs:
-        assert kind & 4
+        assert kind & link.REC_KIND_PLAYOUT_CAP
         for ply, row in enumerate(rows):
             assert row[1] == link.playout_cap_kind(SEED, uid, ply, 32768)
             fast[float(table[ply])] += int(row[1] == 0)
@@ -399,10 +372,10 @@ def test_with_forced_playouts_the_pick_is_made_on_the_raw_counts():
             want = {int(mv): int(c) for mv, c, ch in zip(moves, m, child) if ch != vlr.NONE and c != 0}
             pruned += int(any(int(a) != int(b) for a, b in zip(m, n)))
             expected[(st.uid, st.ply)] = (int(rep.moves[j]), want)
-        _step(e)
+        eh.step(e)
         if e.game_state(0).uid != st.uid:
-            for slot, uid, result, kind, rows in _records(_staged(e)):
-                assert kind & 8
+            for slot, uid, result, kind, rows in eh.records(eh.staged(e)):
+                assert kind & link.REC_KIND_FORCED
                 for ply, row in enumerate(rows):
                     assert (row[0], row[2]) == expected[(uid, ply)], (uid, ply)
                 done += 1
@@ -413,7 +386,7 @@ def test_with_forced_playouts_the_pick_is_made_on_the_raw_counts():
 
 
 def test_with_recorded_values_and_a_resign_threshold_both_rules_hold():
-    net, table, games = _net(), _cycle(), 12
+    net, table, games = eh.net(), _cycle(), 12
     q_below, consecutive, share = 0.45, 2, 16384
     e = _engine(games, 24, weight=0.0, move=table)
     e.set_resign(q_below, consecutive, share)
@@ -421,14 +394,14 @@ def test_with_recorded_values_and_a_resign_threshold_both_rules_hold():
     for chunk in range(6):
         e.run(net, 300, link.DTYPE_BF16)
         e.sync()
-        recs += _records(_staged(e))
+        recs += eh.records(eh.staged(e))
         if len(recs) >= 2 * games:
             break
     assert len(recs) >= games
     seen = _new_seen()
     _check_rule(recs, table, SEED, seen)          # a resigned game's last ply records the move the rule chose, unplayed
     _assert_seen(seen, games)
-    stats = _check_records(recs, q_below, consecutive, share)
+    stats = eh.check_resign_records(recs, q_below, consecutive, share)
     assert stats == e.resign_stats()
     e.close()
 
@@ -442,13 +415,13 @@ def _continue_beside_a_twin(e, twin, net, arena=False):
         else:
             x.run(net, 200, link.DTYPE_F32)
         x.sync()
-    assert _by_uid(_staged(e)) == _by_uid(_staged(twin))
-    _same(_dump(e), _dump(twin))
+    assert _by_uid(eh.staged(e)) == _by_uid(eh.staged(twin))
+    eh.same(eh.dump(e), eh.dump(twin))
     assert e.stats() == twin.stats() and e.stats()["plies"] > 0
 
 
 def test_refusals_leave_the_engine_as_it_was():
-    net = _net()
+    net = eh.net()
     good = np.ones(400, dtype=np.float32)
     for flags in (link.FLAG_ONE_RANDOM_MOVE, link.FLAG_SAMPLE_POW5, link.FLAG_PY_POSTERIOR, link.FLAG_TWO_NETS):
         e, twin = _engine(5, 16, flags=flags), _engine(5, 16, flags=flags)

@@ -2,20 +2,18 @@
 and of the root (bit for bit tests/priors_reference.py), nodes of 65 to 193 edges, full arenas (the arena-full rule of
 tests/vl_reference.py), and the need mask and leaf compaction over many slots.  Every test runs the HIP engine in lock step
 with the host's restatement, iteration by iteration."""
-import gzip
-import json
-import os
-
 import numpy as np
 import pytest
 
-from ataxxzero_amd import link, model
+from ataxxzero_amd import link
 from oracle import oracle_lib as orc
+from tests import engine_harness as eh
 from tests import helpers
 from tests import priors_reference as pr
 from tests import solver_reference as sor
 from tests import symmetry_reference as sym
 from tests import vl_reference as vlr
+from tests.engine_harness import _edge_positions, _pack, _wide_roots
 
 pytestmark = pytest.mark.gpu
 
@@ -37,11 +35,6 @@ def _engine(positions, K, VL, flags, visits, seed, edges_per_node=96, ply=10):
     return e, cfg
 
 
-def _pack(fen):
-    p = orc.pos_from_fen(fen)
-    return [int(p.pieces[0]) | (p.turn << 63), int(p.pieces[1])]
-
-
 def _fixture_positions(G):
     """G unfinished blocker-free fixture positions, spread over the file (repeated in order when G exceeds them)."""
     ps = []
@@ -51,23 +44,6 @@ def _fixture_positions(G):
             ps.append(_pack(rec["fen"]))
     step = max(1, len(ps) // G)
     return [ps[(i * step) % len(ps)] for i in range(G)]
-
-
-def _edge_positions(family, moves=None, sets="none"):
-    return [r for r in helpers.load_gz("rules_edge.json.gz")["positions"]
-            if r["set"] == sets and r["family"] == family and (moves is None or len(r["moves"]) in moves)]
-
-
-def _midgame(gi, ply):
-    """A board of tests/golden/random_play_games.jsonl.gz, packed (tests/test_gpu_random_symmetry.py reads them the same way)."""
-    with gzip.open(os.path.join(helpers.GOLDEN, "random_play_games.jsonl.gz")) as f:
-        games = [json.loads(l) for l in f.read().splitlines() if l.strip()]
-    x = o = 0
-    for i, v in enumerate(games[gi]["boards"][ply]):
-        sq = i % 7 + 7 * (6 - i // 7)
-        x |= (v == 1) << sq
-        o |= (v == 2) << sq
-    return [x | ((ply % 2) << 63), o]
 
 
 def _same_tree(exp, post):
@@ -202,7 +178,7 @@ PRIOR_CASES = [(2, 7, 2, 0, False), (2, 16, 1, UAI, False), (1, 64, 3, 0, False)
 
 @pytest.mark.parametrize("G,K,VL,flags,symmetry", PRIOR_CASES)
 def test_priors_of_new_nodes_and_of_the_root(G, K, VL, flags, symmetry):
-    from tests.test_gpu_vl_search import _positions
+    from tests.engine_harness import _positions
     e, cfg = _engine(_positions(G, 0), K, VL, flags, visits=64, seed=20261018)
     if symmetry:
         e.set_random_symmetry(True)
@@ -215,14 +191,6 @@ def test_the_prior_cases_used_every_wave_the_noise_and_several_symmetries():
 
 
 # ------------------------------------------------------------------ 2. wide nodes
-
-def _wide_roots():
-    """Four roots: 117 moves (the `wide` family starts at 129 moves: this one is the widest board of the `random` family), 165
-    moves, the 193-move board, and a mid-game board of 112-123 moves whose grandchildren pass 128."""
-    mid = max(_edge_positions("random"), key=lambda r: len(r["moves"]))
-    assert len(mid["moves"]) == 117
-    return [_pack(mid["fen"]), _pack(_edge_positions("wide", (165,))[0]["fen"]), _pack(_edge_positions("wide", (193,))[0]["fen"]),
-            _midgame(4, 70)]
 
 
 @pytest.mark.parametrize("flags", [0, UAI])
@@ -276,25 +244,11 @@ def test_full_arenas_drop_the_path_end_the_batch_and_force_the_move():
 
 # ------------------------------------------------------------------ 4. many slots
 
-_NET = {}
-
-
-def _net():
-    if not _NET:
-        conv, bn = model.random_init(2, 128, seed=3, perturb_bn=True)
-        _NET["net"] = link.Net(conv, bn)
-    return _NET["net"]
-
-
-def _dump(e):
-    return [e.game_state(g).as_tuple() for g in range(e.G)], [e.tree(g) for g in range(e.G)]
-
-
 @pytest.mark.parametrize("G,K", [(130, 7), (33, 64), (5, 33)])
 def test_need_mask_and_leaf_list_over_many_slots(G, K):
     """Engine a evaluates through its own need mask and compacted leaf list; engine b is given the evaluations of exactly the
     ROOT / EVAL slots of the host's copy of the batch.  A game's K need bits start at bit (g K) mod 32 of the mask."""
-    net, VL = _net(), 2
+    net, VL = eh.net(2), 2
     thin = G * K <= link.THIN_MAX_GAMES
     a, cfg = _engine(_fixture_positions(G), K, VL, 0, visits=24, seed=20261018)
     b, _ = _engine(_fixture_positions(G), K, VL, 0, visits=24, seed=20261018)
@@ -316,7 +270,7 @@ def test_need_mask_and_leaf_list_over_many_slots(G, K):
         b.set_batch_evals(logits, values)
         a.backup()
         b.backup()
-        (sa, ta), (sb, tb) = _dump(a), _dump(b)
+        (sa, ta), (sb, tb) = eh.dump(a), eh.dump(b)
         assert sa == sb
         for x, y in zip(ta, tb):
             _same_tree(x, y)

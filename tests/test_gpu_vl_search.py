@@ -10,28 +10,15 @@ import pytest
 
 from ataxxzero_amd import link, model
 from oracle import oracle_lib as orc
+from tests import engine_harness as eh
 from tests import helpers
 from tests import vl_reference as vlr
+from tests.engine_harness import _positions
 
 pytestmark = pytest.mark.gpu
 
 ROOT = helpers.ROOT
 UAI = link.FLAG_NO_REUSE | link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR
-
-
-def _positions(G, blockers):
-    """G distinct unfinished fixture positions of the given blocker set, the last one near the end of its game."""
-    name = "rules_block4.json.gz" if blockers else "rules_noblock.json.gz"
-    out = []
-    for rec in helpers.load_gz(name):
-        p = orc.pos_from_fen(rec["fen"])
-        if orc.result(p) != 0 or len(orc.movegen(p)) == 0:
-            continue
-        empty = 49 - bin(int(p.pieces[0]) | int(p.pieces[1]) | int(p.blockers)).count("1")
-        out.append((empty, [int(p.pieces[0]) | (p.turn << 63), int(p.pieces[1])]))
-    out.sort(key=lambda t: -t[0])
-    picks = [out[i * (len(out) // (2 * G + 1))][1] for i in range(G - 1)] + [min(out, key=lambda t: t[0])[1]]
-    return np.array(picks, dtype=np.uint64)
 
 
 def _engine(G, K, VL, flags, blockers=0, visits=300, seed=11):
@@ -96,18 +83,9 @@ def test_the_matrix_met_collisions_terminal_paths_and_truncation():
     assert SEEN["collision"] > 0 and SEEN["terminal"] > 0 and SEEN["truncated"] > 0, SEEN
 
 
-def _net(blocks=2, seed=3):
-    conv, bn = model.random_init(blocks, 128, seed=seed, perturb_bn=True)
-    return link.Net(conv, bn)
-
-
-def _dump(e):
-    return [e.game_state(g).as_tuple() for g in range(e.G)], [e.tree(g) for g in range(e.G)]
-
-
 @pytest.mark.parametrize("G,K,dtype", [(3, 16, link.DTYPE_F32), (3, 16, link.DTYPE_F16), (9, 64, link.DTYPE_BF16)])
 def test_device_loop_equals_host_stepping(G, K, dtype):
-    net = _net()
+    net = eh.net(2)
     n = 40
     a, _ = _engine(G, K, 2, 0, visits=200)
     b, _ = _engine(G, K, 2, 0, visits=200)
@@ -117,8 +95,8 @@ def test_device_loop_equals_host_stepping(G, K, dtype):
         b.select()
         b.eval(net, dtype)
         b.backup()
-    sa, ta = _dump(a)
-    sb, tb = _dump(b)
+    sa, ta = eh.dump(a)
+    sb, tb = eh.dump(b)
     assert sa == sb
     for x, y in zip(ta, tb):
         for u, v in zip(x, y):
@@ -129,7 +107,7 @@ def test_device_loop_equals_host_stepping(G, K, dtype):
 
 
 def test_k1_through_the_new_call_is_the_one_leaf_search_and_bad_combinations_fail():
-    net = _net()
+    net = eh.net(2)
     a, _ = _engine(4, 1, 1, 0)
     p = orc.pos_from_fen(orc.START_FEN_PLAIN)
     cfg = link.Config(games=4, visits=300, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
@@ -141,8 +119,8 @@ def test_k1_through_the_new_call_is_the_one_leaf_search_and_bad_combinations_fai
     a.set_leaf_batch(1, 1)
     a.run(net, 30, link.DTYPE_BF16)
     b.run(net, 30, link.DTYPE_BF16)
-    sa, ta = _dump(a)
-    sb, tb = _dump(b)
+    sa, ta = eh.dump(a)
+    sb, tb = eh.dump(b)
     assert sa == sb and all((u == v).all() for x, y in zip(ta, tb) for u, v in zip(x, y))
     # errors: the G-sized calls under K > 1, unsupported flags and budgets, bounds
     a.set_leaf_batch(4, 1)

@@ -5,25 +5,14 @@ writes the bits it says."""
 import numpy as np
 
 from oracle import net_oracle
-from oracle import oracle_lib as orc
 from tests import helpers
-
-
-def _late_start_fen():
-    for rec in helpers.load_gz("rules_noblock.json.gz"):      # (the rule of tests/test_gpu_forced_playouts._late_start)
-        p = orc.pos_from_fen(rec["fen"])
-        x, o = int(p.pieces[0]), int(p.pieces[1])
-        if orc.result(p) != 0 or len(orc.movegen(p)) == 0:
-            continue
-        if 10 <= 49 - bin(x | o).count("1") <= 14 and min(bin(x).count("1"), bin(o).count("1")) >= 10:
-            return rec["fen"]
-    raise AssertionError("no such fixture position")
+from tests.engine_harness import late_start_fen
 
 
 def test_the_net_gives_finite_and_non_finite_evaluations():
     boards = []
     for seed in range(12):
-        for packed, _, _ in helpers.random_line(_late_start_fen(), seed):
+        for packed, _, _ in helpers.random_line(late_start_fen(), seed):
             w0, w1 = int(packed[0]), int(packed[1])
             x = w0 & ~(1 << 63)
             boards.append((w1, x) if w0 >> 63 else (x, w1))

@@ -5,6 +5,7 @@ import pytest
 
 from oracle import oracle_lib as orc
 from tests.helpers import replay_game_entry, synthetic_evals
+from tests.limit_fixtures import LIMIT_CASES, LIMIT_PLIES, cells_of, free_run, limit_engine, step
 
 
 def run(e, iters, evaluator):
@@ -251,23 +252,10 @@ def test_game_limit_plays_exactly_the_games_below_it():
 # raised, and adds nothing to any counter meanwhile.  tests/test_gpu_game_limit.py repeats every case in lock step with the
 # HIP engine; here the rules are stated on the oracle alone.
 
-LIMIT_CASES = [(6, 5), (6, 3), (12, 11), (12, 6)]   # (G, N): one slot past the limit, and half of them
-LIMIT_PLIES = 160
-
-
-def limit_engine(G, flags=0, fen=orc.START_FEN_SELFPLAY):
-    return orc.Engine(orc.make_config(G, 4, seed=11, fen_str=fen, max_plies=LIMIT_PLIES, flags=flags))
-
 
 def snapshot(e):
     """every slot's state words and tree arrays, and the counters"""
     return [(e.game_state(g).as_tuple(), [a.tobytes() for a in e.tree(g)]) for g in range(e.G)], e.stats()
-
-
-def step(e, evaluator=synthetic_evals):
-    n, _ = e.select()
-    e.backup(*evaluator(e.leaf_boards()))
-    return n
 
 
 def play_out(e, max_iters=6000):
@@ -294,42 +282,10 @@ def play_out(e, max_iters=6000):
     return games, live, ended
 
 
-def cells_of(board):
-    p = orc.Pos()
-    p.pieces[0], p.pieces[1] = int(board[0]) & ((1 << 63) - 1), int(board[1])
-    return [int(v) for v in orc.board_cells(p)]
-
-
 def assert_loaded_and_idle(e, g, boards, plies):
     s = e.game_state(g)
     assert (s.phase, s.uid, s.ply, s.n_nodes, s.root_visits, s.leaf_kind) == (3, g, plies[g], 1, 0, orc.LEAF_NONE), (g, s.as_tuple())
     assert (e.tree(g)[0][0] == boards[g]).all(), g
-
-
-_free_runs = {}
-
-
-def free_run(G, N):
-    """The loaded engine WITHOUT a limit, played until its first G games are over (computed once per case): what each uid's game
-    is when nothing stops or delays it, and when it ends.  -> (games by uid, iteration each uid < G ended at)"""
-    if (G, N) not in _free_runs:
-        from tests.helpers import cohort_positions
-        boards, plies = cohort_positions(G, N)
-        e = limit_engine(G)
-        e.set_positions(boards, plies)
-        games, ended = {}, {}
-        for it in range(6000):
-            step(e)
-            for g in range(G):
-                if g not in ended and e.game_state(g).uid != g:
-                    ended[g] = it
-            for rec in e.pop_games(partial=True):
-                games[rec["uid"]] = rec
-            if len(ended) == G:
-                break
-        assert len(ended) == G
-        _free_runs[(G, N)] = ({u: r for u, r in games.items() if u < G}, ended)
-    return _free_runs[(G, N)]
 
 
 @pytest.mark.parametrize("G,N", LIMIT_CASES)

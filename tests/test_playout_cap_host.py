@@ -11,7 +11,7 @@ import numpy as np
 from ataxxzero_amd import link, training
 from oracle import oracle_lib as orc
 from tests.helpers import GOLDEN
-from tests.test_json_format import MAGIC, dumped, random_record, shortest
+from tests.record_fixtures import MAGIC, dumped, random_record, shortest
 
 STREAM_PLAYOUT_CAP = 4
 SEED = 0x1234567_89ABCDEF

@@ -14,7 +14,7 @@ from ataxxzero_amd import link, training
 from oracle import oracle_lib as orc
 from tests import resign_reference as ref
 from tests.helpers import GOLDEN
-from tests.test_json_format import MAGIC, dumped, random_record, shortest
+from tests.record_fixtures import MAGIC, dumped, random_record, shortest
 from tools import resign_calibration
 
 STREAM_RESIGN = 6

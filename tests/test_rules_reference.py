@@ -10,9 +10,7 @@ import pytest
 
 from oracle import oracle_lib as orc
 from tests import rules_reference as rr
-from tests.helpers import BLOCK4_MASK, GOLDEN, load_gz
-
-BLOCK3_MASK = (1 << 0) | (1 << 9) | (1 << 33)
+from tests.helpers import BLOCK3_MASK, BLOCK4_MASK, GOLDEN, load_gz, orc_pos, pocket_boards
 
 
 def fixture_records(name):
@@ -21,27 +19,6 @@ def fixture_records(name):
         data = load_gz("rules_edge.json.gz")
         return [(rec, data["sets"][rec["set"]]["mask"]) for rec in data["positions"]]
     return [(rec, mask) for rec in load_gz("rules_%s.json.gz" % name) for mask in [BLOCK4_MASK if name == "block4" else 0]]
-
-
-def orc_pos(b):
-    p = orc.Pos()
-    p.pieces[0], p.pieces[1], p.blockers = b.masks()
-    p.turn = b.turn
-    return p
-
-
-def pocket_boards():
-    """[(board, blockers mask)]: the side to move is walled in by blockers and its opponent has no stones, the boards on which
-    the reference's two adjudication orders disagree (left out of rules_edge.json.gz for that reason)"""
-    out = []
-    for pocket in ([0], [48, 47], [6, 13], [42]):
-        wall = {n for sq in pocket for n in rr.NEAR[sq] + rr.FAR[sq]} - set(pocket)
-        for turn in (0, 1):
-            cells = [rr.BLOCK if sq in wall else rr.EMPTY for sq in range(49)]
-            for sq in pocket:
-                cells[sq] = rr.X if turn == 0 else rr.O
-            out.append((rr.Board(cells, turn), sum(1 << sq for sq in wall)))
-    return out
 
 
 def test_edge_fixture_holds_the_families_it_was_written_for():

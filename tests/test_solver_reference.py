@@ -10,6 +10,7 @@ from oracle import oracle_lib as orc
 from tests import helpers
 from tests import solver_reference as sr
 from tests import vl_reference as vlr
+from tests.solver_reference import _minimax, _pos, late_positions
 
 F32 = np.float32
 
@@ -54,23 +55,6 @@ def host_search(tree, blockers, visits, K, VL, select, backup):
             break
         rv += added
     return tree, log, batches
-
-
-def late_positions(max_empty, count=None):
-    """Unfinished fixture positions with at most `max_empty` empty cells, emptiest boards last: [(packed, blockers)]."""
-    out = []
-    for packed, blockers, rec in helpers.fixture_positions():
-        x, o = int(packed[0]) & ~(1 << 63), int(packed[1])
-        empty = 49 - bin(x | o | blockers).count("1")
-        if empty > max_empty:
-            continue
-        p = orc.pos_from_fen(rec["fen"])
-        p.blockers = blockers
-        if orc.result(p) != 0:
-            continue
-        out.append((empty, int(packed[0]), int(packed[1]), blockers))
-    out = sorted(set(out))
-    return [(a, b, c) for _, a, b, c in out][:count]
 
 
 def test_without_a_proven_node_it_is_vl_reference_step_for_step():
@@ -184,67 +168,6 @@ def test_select_ends_a_path_at_a_proven_node_but_descends_from_a_proven_root():
 
 
 # ------------------------------------------------------------------ soundness against a minimax
-
-class _OutOfBudget(Exception):
-    pass
-
-
-def _search(p, depth, memo, budget):
-    """+1 / -1 for the side to move, or None if `depth` plies do not decide it.  A decided value does not depend on the
-    depth it was found with, so it is remembered under the position alone."""
-    pos = (int(p.pieces[0]), int(p.pieces[1]), int(p.turn))
-    if pos in memo:
-        return memo[pos]
-    if (pos, depth) in memo:
-        return None
-    budget[0] -= 1
-    if budget[0] < 0:
-        raise _OutOfBudget()
-    moves = np.zeros(256, dtype=np.uint16)
-    m = ctypes.c_int(0)
-    res = orc.lib().orc_result(ctypes.byref(p), moves.ctypes.data, ctypes.byref(m))
-    if res != 0:
-        out = 1 if (res == 1) == (p.turn == 0) else -1
-    elif depth == 0:
-        out = None
-    else:
-        out, open_ = -1, False
-        for mv in sorted((int(v) for v in moves[:m.value]), key=lambda v: (v & 0xFF) != (v >> 8)):   # clones first
-            q = orc.Pos()
-            ctypes.memmove(ctypes.byref(q), ctypes.byref(p), ctypes.sizeof(orc.Pos))
-            orc.lib().orc_makemove(ctypes.byref(q), mv & 0xFF, mv >> 8)
-            v = _search(q, depth - 1, memo, budget)
-            if v == -1:
-                out = 1
-                break
-            open_ = open_ or v is None
-        if out == -1 and open_:
-            out = None
-    if out is None:
-        memo[(pos, depth)] = None
-    else:
-        memo[pos] = out
-    return out
-
-
-def _minimax(p, depth, memo, nodes=4000):
-    """Plain minimax on the oracle's rules to the end of the game or `depth` plies, deepened ply by ply; gives up (None:
-    not resolved) after `nodes` positions.  What it does return is exact."""
-    budget = [nodes]
-    try:
-        for d in range(min(1, depth), depth + 1):
-            v = _search(p, d, memo, budget)
-            if v is not None:
-                return v
-    except _OutOfBudget:
-        pass
-    return None
-
-
-def _pos(word0, word1, blockers):
-    p = orc.Pos()
-    p.pieces[0], p.pieces[1], p.blockers, p.turn = int(word0) & ~(1 << 63), int(word1), int(blockers), int(word0) >> 63
-    return p
 
 
 def test_every_proof_agrees_with_a_minimax_on_late_positions():

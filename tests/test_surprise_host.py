@@ -6,7 +6,7 @@ import pytest
 
 from ataxxzero_amd import link, training
 from tests import surprise_reference as ref
-from tests.surprise_reference import BAD, FULL, HAS_FULL, PASS
+from tests.surprise_reference import BAD, PASS, edge_specs
 
 F32 = np.float32
 SEED = 0x1234567_89ABCDEF
@@ -94,23 +94,6 @@ def test_surprise_edge_cases(views):
 
 # ---------------------------------------------------------------- the weighted draw
 
-def edge_specs(rng):
-    """The games of the issue's list; weights None: never given any."""
-    long_w = rng.random(4096).astype(F32)
-    long_w[rng.random(4096) < 0.3] = 0
-    return [
-        ([0], 1, 0, [2.5]),                                               # one candidate
-        ([0, 0, 0, 0], 1 | HAS_FULL, 0, [1, 1, 1, 1]),                    # "full" without one full ply
-        ([0, 0, 0], 2, 0, [0, 0, 0]),                                     # total 0
-        ([0] * 9, 1, 0, [0, 1.5, 0, 0, 0.25, 3, 0, 0, 1e-6]),             # zeros on some plies (1e-6 rounds to 0 units)
-        ([0, 0, 0, 0, 0], 2, 3, [5, 0, 0, 0, 1]),                         # random_ply: ply 3 whatever the weights say
-        ([0] * 4096, 1, 0, long_w),                                       # the search's depth
-        ([0, FULL, 0, FULL | BAD, FULL | PASS, FULL, 0], 1 | HAS_FULL, 0, [9, 0.5, 9, 4, 4, 2, 9]),
-        ([0] * 12, 2, 0, None),                                           # never weighted
-        ([BAD, PASS, 0, BAD, PASS, BAD], 1, 0, [0.125, 0.125, 3, 0.125, 0.125, 0.125]),   # one good ply among six, a heavy one
-        ([0, 0, 0], 1, 0, [65535.0, 0.5, 0.25]),                          # a large total: 65535.75 * 65536 units
-    ]
-
 
 def test_weighted_draw_equals_the_integer_restatement():
     rng = np.random.default_rng(21)
@@ -149,7 +132,7 @@ def test_weighted_draw_equals_the_integer_restatement():
 @pytest.mark.parametrize("units", [65536, 7, 1])
 def test_equal_weights_are_the_uniform_draw(units):
     """floor(floor(v c q / 2^32) / q) = floor(v c / 2^32) for every q >= 1: the rows are azh_samples_draw's."""
-    from tests.test_samples_host import draw_mirror
+    from tests.samples_fixtures import draw_mirror
     games, flags, _ = draw_mirror()
     specs = [([int(f) for f in flags[first:first + plies]], int(word), int(r1), None)
              for first, plies, word, r1 in games.tolist()]

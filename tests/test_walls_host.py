@@ -11,7 +11,7 @@ from ataxxzero_amd import link, selfplay, training, uai
 from tests import rules_reference as rr
 from tests import surprise_reference as ref
 from tests import walls_fixtures as wf
-from tests.test_samples_host import _arrays_equal, random_record
+from tests.samples_fixtures import _arrays_equal, random_record
 
 F32 = np.float32
 FENS = [wf.DEFAULT_FEN, wf.ASYMMETRIC_FEN, "x5o/7/3-3/2-1-2/3-3/7/o5x o", "-------/-------/7/7/7/7/xo5 x"]

@@ -34,44 +34,40 @@ sys.path.insert(0, ROOT)
 from ataxxzero_amd import link, model, selfplay  # noqa: E402
 
 SNAPSHOT = os.path.join(ROOT, "profiles", "round2_steady_state_positions.npz")
-MAGIC = 0x415A4847
+
+
+def staged_plies(words):
+    """(kind word, word 5, the ply's target words) of every ply of the staged record words (layout: link.records), dropped
+    games' markers skipped; a word that is not a header is stepped over until the next magic"""
+    pos = 0
+    while pos + link.REC_HDR_WORDS <= len(words):
+        if words[pos] != link.RECORD_MAGIC:
+            pos += 1
+            continue
+        n, q, kind = int(words[pos + link.REC_WORDS]), pos + link.REC_HDR_WORDS, int(words[pos + link.REC_KIND])
+        if kind & link.REC_KIND_MASK != link.REC_KIND_DROPPED:
+            for _ in range(int(words[pos + link.REC_PLIES])):
+                nd = int(words[q + 4]) >> 16
+                yield kind, int(words[q + 5]), words[q + link.REC_PLY_WORDS:q + link.REC_PLY_WORDS + nd]
+                q += link.REC_PLY_WORDS + nd
+        pos += max(n, link.REC_HDR_WORDS)
 
 
 def pruned_share(words, visits):
     """(sum over the acting plies of 1 - written visits / `visits`, acting plies) over the staged record words of an engine
-    with forced playouts on: the plies of games that carry the mode's bit (8 in header word 7), FULL ones if the cap is on"""
-    share, acting, pos = 0.0, 0, 0
-    while pos + 8 <= len(words):
-        if words[pos] != MAGIC:
-            pos += 1
-            continue
-        n, q, kind = int(words[pos + 5]), pos + 8, int(words[pos + 7])
-        if kind & 3 != 1:
-            for _ in range(int(words[pos + 3])):
-                nd = int(words[q + 4]) >> 16
-                if kind & 8 and (int(words[q + 5]) or not kind & 4):
-                    share += 1.0 - min(1.0, float((words[q + 6:q + 6 + nd] >> 16).sum()) / visits)
-                    acting += 1
-                q += 6 + nd
-        pos += max(n, 8)
+    with forced playouts on: the plies of games that carry the mode's bit, FULL ones if the cap is on"""
+    share, acting = 0.0, 0
+    for kind, word5, targets in staged_plies(words):
+        if kind & link.REC_KIND_FORCED and (word5 or not kind & link.REC_KIND_PLAYOUT_CAP):
+            share += 1.0 - min(1.0, float((targets >> 16).sum()) / visits)
+            acting += 1
     return share, acting
 
 
 def full_share(words):
     """(FULL plies, plies) over the staged record words"""
-    full = plies = pos = 0
-    while pos + 8 <= len(words):
-        if words[pos] != MAGIC:
-            pos += 1
-            continue
-        n, q = int(words[pos + 5]), pos + 8
-        if int(words[pos + 7]) & 3 != 1:
-            for _ in range(int(words[pos + 3])):
-                full += int(words[q + 5])
-                plies += 1
-                q += 6 + (int(words[q + 4]) >> 16)
-        pos += max(n, 8)
-    return full, plies
+    full = [word5 for _, word5, _ in staged_plies(words)]
+    return sum(full), len(full)
 
 
 def leg(conv, bn, args, cap, seed, forced=0.0, symmetry=False):
