@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "azh_device.h"
@@ -23,6 +24,10 @@ constexpr u32 GAME_HAS_FULL = 1u << 8, GAME_HAS_VALUES = 1u << 9;
 constexpr u32 PLY_ODD = 0x80u;  // in the device's targets_flags only: o is the mover (the surprise kernel sees no game)
 constexpr u32 WEIGHT_ONE = 65536u;
 constexpr int SURPRISE_CHUNK = 16384;
+// auxiliary targets (include/ataxxzero_hip.h, "Auxiliary targets"): the aux kernels' LDS behind the sample's padded floats
+constexpr int SAMPLE_LDS = (SAMPLE_FLOATS + 3) / 4 * 4;
+constexpr int AUX_OWNERSHIP = SAMPLE_LDS, AUX_SCORE = AUX_OWNERSHIP + 49, AUX_WEIGHT = AUX_SCORE + 1, AUX_REPLY = AUX_WEIGHT + 2;
+constexpr int AUX_LDS = (AUX_REPLY + POLICY + 3) / 4 * 4;
 
 struct Ply {  // 32 bytes
     u64 x, o;      // bit = file + 7 * rank, the ring record's layout
@@ -42,12 +47,21 @@ struct View {  // what the kernels read
     const u64 *blockers;  // null: no stored game has walls; else [game]: its wall mask, bit = file + 7 * rank
 };
 
+struct NoAux {};  // the kernels without auxiliary targets: emit_sample is what it was
+struct Aux {      // the four further outputs, and where the owners come from
+    const u64 *owners;  // null: no stored game has owners; else [game][2]: the cells x and o own at the game's end
+    float *ownership, *score, *reply, *weight;
+};
+
 // One wave builds sample `i` in LDS and writes it out with coalesced stores; g < 0: the sample is all zeros.
+// A = Aux: also ownership [49], score [1], reply [833] and aux_weight [2], built in the LDS behind the sample.
+template <class A>
 __device__ void emit_sample(const View &v, float *lds, int i, int g, int p, int s, double blend, float *features,
-                            float *policy, float *value)
+                            float *policy, float *value, const A &aux)
 {
+    constexpr bool AUX = std::is_same<A, Aux>::value;
     const int lane = (int)threadIdx.x;
-    for (int k = lane; k < (SAMPLE_FLOATS + 3) / 4; k += WAVE)
+    for (int k = lane; k < (AUX ? AUX_LDS : SAMPLE_LDS) / 4; k += WAVE)
         reinterpret_cast<float4 *>(lds)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
     if (g >= 0) {
@@ -74,6 +88,32 @@ __device__ void emit_sample(const View &v, float *lds, int i, int g, int p, int 
                 out = (float)((1.0 - blend) * (double)z + blend * ply.value);
             lds[FEATURES + POLICY] = out;
         }
+        if constexpr (AUX) {
+            const u64 own_x = aux.owners ? aux.owners[2 * g] : 0ULL, own_o = aux.owners ? aux.owners[2 * g + 1] : 0ULL;
+            const u64 own_mine = mover == 1 ? own_x : own_o, own_theirs = mover == 1 ? own_o : own_x;
+            if (lane < 49) {  // the same source cell as the feature planes
+                const int X = lane / 7, Y = lane - 7 * X;
+                const int src = symmetry_source_cell(s, X + 7 * (6 - Y));
+                lds[AUX_OWNERSHIP + lane] = (float)(int)((own_mine >> src) & 1ULL) - (float)(int)((own_theirs >> src) & 1ULL);
+            }
+            // the reply: ply p + 1's target, where that ply is one a sample could have been drawn from
+            bool reply = (u32)p + 1u < game.y;  // (wave-uniform)
+            if (reply) {
+                const Ply next = v.plies[game.x + (u32)p + 1u];
+                const u32 f = next.targets_flags & 0xFFu;
+                reply = !(f & (AZH_SAMPLES_PLY_PASS | AZH_SAMPLES_PLY_BAD)) && (!(game.z & GAME_HAS_FULL) || (f & AZH_SAMPLES_PLY_FULL));
+                const u32 n_reply = reply ? next.targets_flags >> 8 : 0u;
+                for (u32 t = (u32)lane; t < n_reply; t += WAVE) {
+                    const int index = v.target_index[next.first_target + t];
+                    atomicAdd(&lds[AUX_REPLY + symmetry_policy_index(s, index)], v.target_weight[next.first_target + t]);
+                }
+            }
+            if (lane == 0) {
+                lds[AUX_SCORE] = (float)((int)__popcll(own_mine) - (int)__popcll(own_theirs));
+                lds[AUX_WEIGHT] = (own_x | own_o) ? 1.f : 0.f;
+                lds[AUX_WEIGHT + 1] = reply ? 1.f : 0.f;
+            }
+        }
     }
     __syncthreads();
     if (lane < 49)
@@ -83,16 +123,37 @@ __device__ void emit_sample(const View &v, float *lds, int i, int g, int p, int 
         row[k] = lds[FEATURES + k];
     if (lane == 0)
         value[i] = lds[FEATURES + POLICY];
+    if constexpr (AUX) {
+        if (lane < 49)
+            aux.ownership[(size_t)i * 49 + lane] = lds[AUX_OWNERSHIP + lane];
+        float *reply_row = aux.reply + (size_t)i * POLICY;
+        for (int k = lane; k < POLICY; k += WAVE)
+            reply_row[k] = lds[AUX_REPLY + k];
+        if (lane == 0)
+            aux.score[i] = lds[AUX_SCORE];
+        if (lane < 2)
+            aux.weight[2 * (size_t)i + lane] = lds[AUX_WEIGHT + lane];
+    }
 }
 
 __global__ __launch_bounds__(WAVE) void k_samples_gather(View v, int n, const int *draws, double blend, float *features,
                                                          float *policy, float *value)
 {
-    __shared__ __attribute__((aligned(16))) float lds[(SAMPLE_FLOATS + 3) / 4 * 4];
+    __shared__ __attribute__((aligned(16))) float lds[SAMPLE_LDS];
     const int i = (int)blockIdx.x;
     if (i >= n)
         return;
-    emit_sample(v, lds, i, draws[3 * i], draws[3 * i + 1], draws[3 * i + 2], blend, features, policy, value);
+    emit_sample(v, lds, i, draws[3 * i], draws[3 * i + 1], draws[3 * i + 2], blend, features, policy, value, NoAux{});
+}
+
+__global__ __launch_bounds__(WAVE) void k_samples_gather_aux(View v, int n, const int *draws, double blend, float *features,
+                                                             float *policy, float *value, Aux aux)
+{
+    __shared__ __attribute__((aligned(16))) float lds[AUX_LDS];
+    const int i = (int)blockIdx.x;
+    if (i >= n)
+        return;
+    emit_sample(v, lds, i, draws[3 * i], draws[3 * i + 1], draws[3 * i + 2], blend, features, policy, value, aux);
 }
 
 // One attempt of sample `i`'s draw from the arrays of `v`, or of the host mirror: the same function on both sides.
@@ -140,14 +201,14 @@ __host__ __device__ inline Attempt draw_attempt(u32 k0, u32 k1, u32 step, u32 i,
     return out;
 }
 
-__global__ __launch_bounds__(WAVE) void k_samples_draw_gather(View v, int n, u32 k0, u32 k1, u32 step, u32 first_game,
-                                                              u32 n_games, double blend, float *features, float *policy,
-                                                              float *value, int *draws_out, u32 *errors)
+// Sample i's draw: lane a makes attempt a; the first one that succeeds is the draw.  -> (game, ply, symmetry) in every lane, -1
+// each when all 64 attempts fail (counted in *errors).
+struct Draw {
+    int g, p, s;
+};
+__device__ __forceinline__ Draw draw_sample(const View &v, int i, u32 k0, u32 k1, u32 step, u32 first_game, u32 n_games,
+                                            int *draws_out, u32 *errors)
 {
-    __shared__ __attribute__((aligned(16))) float lds[(SAMPLE_FLOATS + 3) / 4 * 4];
-    const int i = (int)blockIdx.x;
-    if (i >= n)
-        return;
     const int lane = (int)threadIdx.x;  // lane a makes attempt a; the first one that succeeds is the draw
     const Attempt mine = draw_attempt(
         k0, k1, step, (u32)i, (u32)lane, first_game, n_games, [&](int g) { return v.games[g]; },
@@ -168,7 +229,31 @@ __global__ __launch_bounds__(WAVE) void k_samples_draw_gather(View v, int n, u32
             draws_out[4 * i + 3] = ok ? first + 1 : MAX_ATTEMPTS;
         }
     }
-    emit_sample(v, lds, i, g, p, s, blend, features, policy, value);
+    return Draw{g, p, s};
+}
+
+__global__ __launch_bounds__(WAVE) void k_samples_draw_gather(View v, int n, u32 k0, u32 k1, u32 step, u32 first_game,
+                                                              u32 n_games, double blend, float *features, float *policy,
+                                                              float *value, int *draws_out, u32 *errors)
+{
+    __shared__ __attribute__((aligned(16))) float lds[SAMPLE_LDS];
+    const int i = (int)blockIdx.x;
+    if (i >= n)
+        return;
+    const Draw d = draw_sample(v, i, k0, k1, step, first_game, n_games, draws_out, errors);
+    emit_sample(v, lds, i, d.g, d.p, d.s, blend, features, policy, value, NoAux{});
+}
+
+__global__ __launch_bounds__(WAVE) void k_samples_draw_gather_aux(View v, int n, u32 k0, u32 k1, u32 step, u32 first_game,
+                                                                  u32 n_games, double blend, float *features, float *policy,
+                                                                  float *value, int *draws_out, u32 *errors, Aux aux)
+{
+    __shared__ __attribute__((aligned(16))) float lds[AUX_LDS];
+    const int i = (int)blockIdx.x;
+    if (i >= n)
+        return;
+    const Draw d = draw_sample(v, i, k0, k1, step, first_game, n_games, draws_out, errors);
+    emit_sample(v, lds, i, d.g, d.p, d.s, blend, features, policy, value, aux);
 }
 
 // ---------------------------------------------------------------- policy surprise (include/ataxxzero_hip.h)
@@ -304,6 +389,8 @@ struct azh_samples {
     DeviceArray<u32> d_errors;
     DeviceArray<u64> d_blockers;      // [cap_games]: null until the first game with walls arrives
     std::vector<u64> h_blockers;      // [games]
+    DeviceArray<u64> d_owners;        // [cap_games][2]: null until the first game with owners arrives
+    std::vector<u64> h_owners;        // [games][2]
     // policy surprise weighting: all null until asked for
     DeviceArray<u32> d_cum;      // [cap_plies] beside d_candidates (azh_samples_set_ply_weights)
     DeviceArray<float> d_kl;     // [cap_plies]: the last surprise of every ply
@@ -378,6 +465,7 @@ extern "C" void azh_samples_destroy(azh_samples *s)
     s->d_target_weight.release();
     s->d_errors.release();
     s->d_blockers.release();
+    s->d_owners.release();
     s->d_cum.release();
     s->d_kl.release();
     s->d_illegal.release();
@@ -448,6 +536,40 @@ extern "C" int azh_samples_add_games_blockers(azh_samples *s, int64_t n_games, c
                                               const int32_t *target_start, const uint16_t *target_index,
                                               const float *target_weight, const uint64_t *game_blockers)
 {
+    return azh_samples_add_games_aux(s, n_games, games, n_plies, boards, ply_flags, values, target_start, target_index,
+                                     target_weight, game_blockers, nullptr);
+}
+
+// A game's owner masks against its walls and its recorded result: why they are refused, or null.
+static const char *owners_refusal(uint64_t own_x, uint64_t own_o, uint64_t walls, uint32_t result)
+{
+    if (!(own_x | own_o))
+        return nullptr;
+    if (own_x & own_o)
+        return "the owner masks overlap";
+    if ((own_x | own_o) & (walls | ~BOARD_MASK))
+        return "an owner mask has bits on walls or beyond the 49 cells";
+    if ((own_x | own_o | walls) != BOARD_MASK)
+        return "the owner masks leave a cell that is no wall unowned";
+    const int margin = __builtin_popcountll(own_x) - __builtin_popcountll(own_o);
+    if (result != (margin < 0 ? 2u : 1u))
+        return "the owners' margin contradicts the recorded result";
+    return nullptr;
+}
+
+extern "C" int azh_samples_check_owners(uint64_t own_x, uint64_t own_o, uint64_t blockers, uint32_t result)
+{
+    if (const char *why = owners_refusal(own_x, own_o, blockers, result))
+        return azh_fail(-2, "azh_samples_check_owners: owners %#llx, %#llx, walls %#llx, result %u: %s", (unsigned long long)own_x,
+                        (unsigned long long)own_o, (unsigned long long)blockers, (unsigned)result, why);
+    return 0;
+}
+
+extern "C" int azh_samples_add_games_aux(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies,
+                                         const uint64_t *boards, const uint8_t *ply_flags, const double *values,
+                                         const int32_t *target_start, const uint16_t *target_index, const float *target_weight,
+                                         const uint64_t *game_blockers, const uint64_t *game_owners)
+{
     if (!s || n_games < 0 || n_plies < 0 || (n_games && !games) ||
         (n_plies && (!boards || !ply_flags || !values)) || !target_start)
         return azh_fail(-1, "azh_samples_add_games: null argument");
@@ -461,7 +583,7 @@ extern "C" int azh_samples_add_games_blockers(azh_samples *s, int64_t n_games, c
     std::vector<u16> p_candidates((size_t)n_plies);
     std::vector<uint8_t> p_flags((size_t)n_plies);
     int64_t at = 0, bad = 0;
-    bool walled = false;
+    bool walled = false, owned = false;
     for (int64_t g = 0; g < n_games; g++) {
         const uint32_t *w = games + 4 * g;
         const uint32_t result = w[2] & 0xFFu;
@@ -496,6 +618,13 @@ extern "C" int azh_samples_add_games_blockers(azh_samples *s, int64_t n_games, c
                                 (unsigned long long)game_blockers[g], (long long)ply, why);
             walled = walled || game_blockers[g] != 0;
         }
+        if (game_owners) {
+            const uint64_t own_x = game_owners[2 * g], own_o = game_owners[2 * g + 1];
+            if (const char *why = owners_refusal(own_x, own_o, game_blockers ? game_blockers[g] : 0ULL, result))
+                return azh_fail(-2, "azh_samples_add_games: game %lld (owners %#llx, %#llx, result %u): %s", (long long)g,
+                                (unsigned long long)own_x, (unsigned long long)own_o, (unsigned)result, why);
+            owned = owned || (own_x | own_o) != 0;
+        }
         g_words[(size_t)g] = make_uint4((u32)(s->plies + at), w[1], w[2], w[3]);
         g_count[(size_t)g] = c;
         at += w[1];
@@ -519,6 +648,16 @@ extern "C" int azh_samples_add_games_blockers(azh_samples *s, int64_t n_games, c
     }
     if (n_games && s->d_blockers.d)
         AZH_HIP(hipMemcpyAsync(s->d_blockers.d + s->games, g_blockers.data(), (size_t)n_games * sizeof(u64), hipMemcpyHostToDevice, s->stream));
+    std::vector<u64> g_owners((size_t)n_games * 2, 0ULL);
+    if (game_owners)
+        std::copy(game_owners, game_owners + 2 * n_games, g_owners.begin());
+    if (owned && !s->d_owners.d) {  // the first owners: every game stored so far has none
+        if (int rc = s->d_owners.alloc((size_t)s->cap_games * 2))
+            return rc;
+        AZH_HIP(hipMemsetAsync(s->d_owners.d, 0, (size_t)s->cap_games * 2 * sizeof(u64), s->stream));
+    }
+    if (n_games && s->d_owners.d)
+        AZH_HIP(hipMemcpyAsync(s->d_owners.d + 2 * s->games, g_owners.data(), (size_t)n_games * 2 * sizeof(u64), hipMemcpyHostToDevice, s->stream));
     if (n_games) {
         AZH_HIP(hipMemcpyAsync(s->d_games.d + s->games, g_words.data(), (size_t)n_games * sizeof(uint4), hipMemcpyHostToDevice, s->stream));
         AZH_HIP(hipMemcpyAsync(s->d_candidate_count.d + s->games, g_count.data(), (size_t)n_games * sizeof(u32), hipMemcpyHostToDevice, s->stream));
@@ -549,6 +688,7 @@ extern "C" int azh_samples_add_games_blockers(azh_samples *s, int64_t n_games, c
     }
     s->h_flags.insert(s->h_flags.end(), p_flags.begin(), p_flags.end());
     s->h_blockers.insert(s->h_blockers.end(), g_blockers.begin(), g_blockers.end());
+    s->h_owners.insert(s->h_owners.end(), g_owners.begin(), g_owners.end());
     s->games += n_games;
     s->plies += n_plies;
     s->targets += n_targets;
@@ -565,10 +705,43 @@ extern "C" int azh_samples_pack_records(const uint32_t *rec, int64_t words, int6
                                              target_index, target_weight, nullptr);
 }
 
+// A record's owners: azh_samples_final_owners of its last ply's boards and move word.
+static int record_owners(const RecordView &r, uint64_t blockers, uint64_t *owners)
+{
+    PlyView ply = r.first_ply();
+    for (uint32_t p = 0; p + 1 < r.plies(); p++)
+        ply = ply.next();
+    int32_t result = 0;
+    return azh_samples_final_owners(ply.x(), ply.o(), blockers, (int)((r.plies() - 1u) & 1u), ply.move(), owners, &result);
+}
+
+static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts, uint32_t *games,
+                             uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
+                             uint16_t *target_index, float *target_weight, uint64_t *game_blockers, bool aux,
+                             uint64_t *game_owners);
+
 extern "C" int azh_samples_pack_records_blockers(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts,
                                                  uint32_t *games, uint64_t *boards, uint8_t *ply_flags, double *values,
                                                  int32_t *target_start, uint16_t *target_index, float *target_weight,
                                                  uint64_t *game_blockers)
+{
+    return pack_records_impl(rec, words, blockers, counts, games, boards, ply_flags, values, target_start, target_index,
+                             target_weight, game_blockers, false, nullptr);
+}
+
+extern "C" int azh_samples_pack_records_aux(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts,
+                                            uint32_t *games, uint64_t *boards, uint8_t *ply_flags, double *values,
+                                            int32_t *target_start, uint16_t *target_index, float *target_weight,
+                                            uint64_t *game_blockers, uint64_t *game_owners)
+{
+    return pack_records_impl(rec, words, blockers, counts, games, boards, ply_flags, values, target_start, target_index,
+                             target_weight, game_blockers, true, game_owners);
+}
+
+static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts, uint32_t *games,
+                             uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
+                             uint16_t *target_index, float *target_weight, uint64_t *game_blockers, bool aux,
+                             uint64_t *game_owners)
 {
     if (blockers & ~BOARD_MASK)
         return azh_fail(-2, "azh_samples_pack_records: the blockers mask %#llx has bits beyond the 49 cells",
@@ -602,6 +775,12 @@ extern "C" int azh_samples_pack_records_blockers(const uint32_t *rec, int64_t wo
                     return azh_fail(-2, "azh_samples_pack_records: target %#x is no clone and no jump", ply.target(j) & 0xFFFFu);
             n_targets += ply.targets();
         }
+        if (aux) {
+            uint64_t owners[2];
+            if (record_owners(r, blockers, owners))
+                return azh_fail(-2, "azh_samples_pack_records: word %lld: the last move of the game is not legal at its last "
+                                    "board", (long long)(r.w - rec));
+        }
         n_games++;
         n_plies += r.plies();
     }
@@ -629,6 +808,8 @@ extern "C" int azh_samples_pack_records_blockers(const uint32_t *rec, int64_t wo
         games[4 * g + 3] = r.random_ply_plus_1();
         if (game_blockers)
             game_blockers[g] = blockers;
+        if (aux && game_owners)
+            (void)record_owners(r, blockers, game_owners + 2 * g);  // (legal: the first walk has made this call)
         g++;
         PlyView ply = r.first_ply();
         for (uint32_t p = 0; p < r.plies(); p++, q++, ply = ply.next()) {
@@ -653,15 +834,15 @@ extern "C" int azh_samples_add_records(azh_samples *s, const uint32_t *rec, int6
     return azh_samples_add_records_blockers(s, rec, words, 0ULL);
 }
 
-extern "C" int azh_samples_add_records_blockers(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers)
+static int add_records(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers, bool aux)
 {
     if (!s)
         return azh_fail(-1, "azh_samples_add_records: null store");
     int64_t counts[3] = {0, 0, 0};
-    if (int rc = azh_samples_pack_records_blockers(rec, words, blockers, counts, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                   nullptr, nullptr, nullptr))
+    if (int rc = pack_records_impl(rec, words, blockers, counts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   nullptr, aux, nullptr))
         return rc;
-    std::vector<uint64_t> masks((size_t)counts[0] + 1);
+    std::vector<uint64_t> masks((size_t)counts[0] + 1), owners((size_t)counts[0] * 2 + 1);
     std::vector<uint32_t> games((size_t)counts[0] * 4 + 1);
     std::vector<uint64_t> boards((size_t)counts[1] * 2 + 1);
     std::vector<uint8_t> flags((size_t)counts[1] + 1);
@@ -669,11 +850,84 @@ extern "C" int azh_samples_add_records_blockers(azh_samples *s, const uint32_t *
     std::vector<int32_t> start((size_t)counts[1] + 1);
     std::vector<uint16_t> index((size_t)counts[2] + 1);
     std::vector<float> weight((size_t)counts[2] + 1);
-    if (int rc = azh_samples_pack_records_blockers(rec, words, blockers, counts, games.data(), boards.data(), flags.data(),
-                                                   values.data(), start.data(), index.data(), weight.data(), masks.data()))
+    if (int rc = pack_records_impl(rec, words, blockers, counts, games.data(), boards.data(), flags.data(), values.data(),
+                                   start.data(), index.data(), weight.data(), masks.data(), aux, owners.data()))
         return rc;
-    return azh_samples_add_games_blockers(s, counts[0], games.data(), counts[1], boards.data(), flags.data(), values.data(),
-                                          start.data(), index.data(), weight.data(), blockers ? masks.data() : nullptr);
+    return azh_samples_add_games_aux(s, counts[0], games.data(), counts[1], boards.data(), flags.data(), values.data(),
+                                     start.data(), index.data(), weight.data(), blockers ? masks.data() : nullptr,
+                                     aux ? owners.data() : nullptr);
+}
+
+extern "C" int azh_samples_add_records_blockers(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers)
+{
+    return add_records(s, rec, words, blockers, false);
+}
+
+extern "C" int azh_samples_add_records_aux(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers)
+{
+    return add_records(s, rec, words, blockers, true);
+}
+
+extern "C" int azh_samples_final_owners(uint64_t x, uint64_t o, uint64_t blockers, int o_to_move, uint32_t move,
+                                        uint64_t *owners_out, int32_t *result_out)
+{
+    if (!owners_out || !result_out)
+        return azh_fail(-1, "azh_samples_final_owners: null argument");
+    owners_out[0] = owners_out[1] = 0;
+    *result_out = 0;
+    if ((x | o | blockers) & ~BOARD_MASK || (x & o) || ((x | o) & blockers))
+        return azh_fail(-2, "azh_samples_final_owners: boards %#llx, %#llx, walls %#llx overlap or leave the 49 cells",
+                        (unsigned long long)x, (unsigned long long)o, (unsigned long long)blockers);
+    Board b;
+    b.x = x;
+    b.o = o;
+    b.turn = o_to_move ? 1 : 0;
+    uint16_t legal[POLICY];
+    int32_t n_legal = 0;  // the position's moves as the surprise pass lists them: the one statement of the rules on the host
+    if (int rc = azh_samples_legal_blockers(b.turn ? o : x, b.turn ? x : o, blockers, legal, &n_legal))
+        return rc;
+    if ((move & 0xFFFFu) == 0xFFFFu) {
+        if (n_legal)
+            return azh_fail(-2, "azh_samples_final_owners: a pass where the mover has %d moves", (int)n_legal);
+        b.turn ^= 1;  // a pass only hands the turn over
+    } else {
+        if (!board_move(move & 0xFFFFu))
+            return azh_fail(-2, "azh_samples_final_owners: move %#x is no clone and no jump", (unsigned)move);
+        const uint16_t *begin = legal, *end = legal + n_legal;
+        if (std::find(begin, end, (uint16_t)policy_index(move & 0xFFFFu)) == end)
+            return azh_fail(-2, "azh_samples_final_owners: move %#x is not legal for %s on %#llx, %#llx, walls %#llx",
+                            (unsigned)move, b.turn ? "o" : "x", (unsigned long long)x, (unsigned long long)o,
+                            (unsigned long long)blockers);
+        b = make_move(b, (int)(move & 0xFFu), (int)((move >> 8) & 0xFFu));
+    }
+    // the kernels' order of checks (wave_movegen): a side without stones, then a stuck mover, then a full board
+    const u64 empty = BOARD_MASK & ~(b.x | b.o | blockers);
+    u64 own_x = b.x, own_o = b.o;
+    if (azh_samples_legal_blockers(b.turn ? b.o : b.x, b.turn ? b.x : b.o, blockers, legal, &n_legal))
+        return -1;
+    if (!b.x || !b.o) {
+        if ((b.turn ? !b.x : !b.o) && !n_legal && empty)
+            return azh_fail(-2, "azh_samples_final_owners: the mover is stuck and its opponent has no stones: the reference's "
+                                "two orders of adjudication disagree here");
+        (b.x ? own_x : own_o) |= empty;
+    } else if (!n_legal) {
+        (b.turn ? own_x : own_o) |= empty;  // the mover is stuck: the empty cells go to the side not to move
+    } else if (empty) {
+        return 0;  // the game goes on: no owners
+    }
+    owners_out[0] = own_x;
+    owners_out[1] = own_o;
+    *result_out = __builtin_popcountll(own_x) < __builtin_popcountll(own_o) ? 2 : 1;
+    return 0;
+}
+
+extern "C" int azh_samples_game_owners(const azh_samples *s, uint64_t *owners)
+{
+    if (!s || !owners)
+        return azh_fail(-1, "azh_samples_game_owners: null argument");
+    if (!s->h_owners.empty())
+        memcpy(owners, s->h_owners.data(), s->h_owners.size() * sizeof(uint64_t));
+    return 0;
 }
 
 extern "C" int azh_samples_counts(const azh_samples *s, int64_t *out)
@@ -707,8 +961,53 @@ extern "C" int azh_samples_game_blockers(const azh_samples *s, uint64_t *blocker
     return 0;
 }
 
+// The two gather calls, each once for the kernels without auxiliary targets (A = NoAux: the code of the entry points as they
+// were) and once for those with them (A = Aux).
+template <class A>
+static int gather(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features, float *policy,
+                  float *value, const A &aux, uintptr_t stream);
+template <class A>
+static int draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game, int64_t n_games,
+                       double value_blend, float *features, float *policy, float *value, const A &aux, int32_t *draws_out,
+                       uintptr_t stream);
+
 extern "C" int azh_samples_gather(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features,
                                   float *policy, float *value, uintptr_t stream)
+{
+    return gather(s, n, draws, value_blend, features, policy, value, NoAux{}, stream);
+}
+
+extern "C" int azh_samples_gather_aux(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features,
+                                      float *policy, float *value, float *ownership, float *score, float *reply,
+                                      float *aux_weight, uintptr_t stream)
+{
+    if (!s || !ownership || !score || !reply || !aux_weight)
+        return azh_fail(-1, "azh_samples_gather: null argument");
+    const Aux aux{s->d_owners.d, ownership, score, reply, aux_weight};
+    return gather(s, n, draws, value_blend, features, policy, value, aux, stream);
+}
+
+extern "C" int azh_samples_draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game,
+                                       int64_t n_games, double value_blend, float *features, float *policy, float *value,
+                                       int32_t *draws_out, uintptr_t stream)
+{
+    return draw_gather(s, n, seed, step, first_game, n_games, value_blend, features, policy, value, NoAux{}, draws_out, stream);
+}
+
+extern "C" int azh_samples_draw_gather_aux(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game,
+                                           int64_t n_games, double value_blend, float *features, float *policy, float *value,
+                                           float *ownership, float *score, float *reply, float *aux_weight, int32_t *draws_out,
+                                           uintptr_t stream)
+{
+    if (!s || !ownership || !score || !reply || !aux_weight)
+        return azh_fail(-1, "azh_samples_draw_gather: null argument");
+    const Aux aux{s->d_owners.d, ownership, score, reply, aux_weight};
+    return draw_gather(s, n, seed, step, first_game, n_games, value_blend, features, policy, value, aux, draws_out, stream);
+}
+
+template <class A>
+static int gather(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features, float *policy,
+                  float *value, const A &aux, uintptr_t stream)
 {
     if (!s || !draws || !features || !policy || !value)
         return azh_fail(-1, "azh_samples_gather: null argument");
@@ -736,8 +1035,12 @@ extern "C" int azh_samples_gather(azh_samples *s, int n, const int32_t *draws, d
     memcpy(s->h_stage[k], draws, (size_t)n * 3 * sizeof(int));
     hipStream_t st = stream ? (hipStream_t)stream : s->stream;
     AZH_HIP(hipMemcpyAsync(s->d_stage[k], s->h_stage[k], (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_samples_gather, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, s->d_stage[k], value_blend,
-                       features, policy, value);
+    if constexpr (std::is_same<A, Aux>::value)
+        hipLaunchKernelGGL(k_samples_gather_aux, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, s->d_stage[k], value_blend,
+                           features, policy, value, aux);
+    else
+        hipLaunchKernelGGL(k_samples_gather, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, s->d_stage[k], value_blend,
+                           features, policy, value);
     AZH_HIP(hipGetLastError());
     AZH_HIP(hipEventRecord(s->used[k], st));
     if (!stream)
@@ -745,9 +1048,10 @@ extern "C" int azh_samples_gather(azh_samples *s, int n, const int32_t *draws, d
     return 0;
 }
 
-extern "C" int azh_samples_draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game,
-                                       int64_t n_games, double value_blend, float *features, float *policy, float *value,
-                                       int32_t *draws_out, uintptr_t stream)
+template <class A>
+static int draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game, int64_t n_games,
+                       double value_blend, float *features, float *policy, float *value, const A &aux, int32_t *draws_out,
+                       uintptr_t stream)
 {
     if (!s || !features || !policy || !value)
         return azh_fail(-1, "azh_samples_draw_gather: null argument");
@@ -757,9 +1061,14 @@ extern "C" int azh_samples_draw_gather(azh_samples *s, int n, uint64_t seed, uin
     if (!(value_blend == value_blend))
         return azh_fail(-1, "azh_samples_draw_gather: value_blend is not a number");
     hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-    hipLaunchKernelGGL(k_samples_draw_gather, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, (u32)seed,
-                       (u32)(seed >> 32), step, (u32)first_game, (u32)n_games, value_blend, features, policy, value,
-                       draws_out, s->d_errors.d);
+    if constexpr (std::is_same<A, Aux>::value)
+        hipLaunchKernelGGL(k_samples_draw_gather_aux, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, (u32)seed,
+                           (u32)(seed >> 32), step, (u32)first_game, (u32)n_games, value_blend, features, policy, value,
+                           draws_out, s->d_errors.d, aux);
+    else
+        hipLaunchKernelGGL(k_samples_draw_gather, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, (u32)seed,
+                           (u32)(seed >> 32), step, (u32)first_game, (u32)n_games, value_blend, features, policy, value,
+                           draws_out, s->d_errors.d);
     AZH_HIP(hipGetLastError());
     if (!stream)
         AZH_HIP(hipStreamSynchronize(st));

@@ -210,6 +210,19 @@ SIGNATURES = {
     "azh_samples_ply_cum": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(_i32)]),
     "azh_samples_draw_weighted": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64, _vp,
                                                  ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    # auxiliary targets
+    "azh_samples_final_owners": (ctypes.c_int, [_u64, _u64, _u64, ctypes.c_int, ctypes.c_uint32, _vp, _P(_i32)]),
+    "azh_samples_check_owners": (ctypes.c_int, [_u64, _u64, _u64, ctypes.c_uint32]),
+    "azh_samples_add_games_aux": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp]),
+    "azh_samples_pack_records_aux": (ctypes.c_int, [_vp, ctypes.c_int64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                    _vp]),
+    "azh_samples_add_records_aux": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _u64]),
+    "azh_samples_game_owners": (ctypes.c_int, [_vp, _vp]),
+    "azh_samples_gather_aux": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              ctypes.c_size_t]),
+    "azh_samples_draw_gather_aux": (ctypes.c_int, [_vp, ctypes.c_int, _u64, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64,
+                                                   ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t]),
     # the reference's ABI, link.py:8-32
     "launch_threads": (None, [ctypes.c_char_p, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int]),
     "get_workload": (ctypes.c_int, []),
@@ -911,15 +924,70 @@ class SampleArrays:
             raise ValueError("one blockers mask per game")
 
 
+class AuxSampleArrays(SampleArrays):
+    """SampleArrays and owners (G, 2) u64: the cells x and o own at each game's end, both 0 for a game whose final position
+    is not terminal (include/ataxxzero_hip.h, "Auxiliary targets")."""
+    __slots__ = ("owners",)
+
+    def __init__(self, *arrays, owners=None, **named):
+        super().__init__(*arrays, **named)
+        self.owners = (np.zeros((len(self.games), 2), dtype=np.uint64) if owners is None
+                       else np.ascontiguousarray(owners, dtype=np.uint64).reshape(-1, 2))
+        if len(self.owners) != len(self.games):
+            raise ValueError("two owner masks per game")
+
+
 # bit x + 7 (6 - y) of a bitboard is the cell the game line's boards[ply][x + 7 y] names
 _CELL_BIT = np.array([1 << (c % 7 + 7 * (6 - c // 7)) for c in range(49)], dtype=np.uint64)
+MOVE_PASS = 0xFFFF           # the ring record's move word of a pass
 
 
-def entries_to_arrays(entries):
+def samples_final_owners(x, o, blockers, o_to_move, move):
+    """The ring record's 16-bit `move` (from | to << 8, a clone from == to, MOVE_PASS) played by x (o: o_to_move) on the
+    bitboards x, o with walls `blockers` -> (x-owned mask, o-owned mask, result) of the position reached: 0, 0, 0 when it is not
+    terminal.  AzhError (-2) for a move that is not legal there (azh_samples_final_owners; host arithmetic, no GPU needed)."""
+    owners, result = np.zeros(2, dtype=np.uint64), ctypes.c_int32(0)
+    check(load().azh_samples_final_owners(int(x), int(o), int(blockers), int(bool(o_to_move)), int(move), _ptr(owners),
+                                          ctypes.byref(result)))
+    return int(owners[0]), int(owners[1]), int(result.value)
+
+
+def entry_move_word(mv):
+    """A game line's move — UAI text, "pass", or the reference's nested lists ["c", [x, y]] / [[x0, y0], [x1, y1]] — as the
+    ring record's 16-bit move word."""
+    if mv == "pass":
+        return MOVE_PASS
+    if isinstance(mv, str):
+        from .uai import text_to_xy_move
+        mv = text_to_xy_move(mv)
+        if mv == "pass":
+            return MOVE_PASS
+    to = int(mv[1][0]) + 7 * (6 - int(mv[1][1]))
+    frm = to if mv[0] == "c" else int(mv[0][0]) + 7 * (6 - int(mv[0][1]))
+    return frm | to << 8
+
+
+def entry_owners(entry):
+    """(x-owned, o-owned) of a parsed game line: samples_final_owners of its last board, the side to move there (x on even
+    plies), its "blockers" and the last move.  AzhError (-2) where a store would refuse them (azh_samples_check_owners)."""
+    n = len(entry["boards"])
+    cells = np.asarray(entry["boards"][n - 1], dtype=np.int8)
+    x, o = (int(((cells == v) * _CELL_BIT).sum(dtype=np.uint64)) for v in (1, 2))
+    walls = cells_to_blockers(entry.get("blockers", ()))
+    own_x, own_o, _ = samples_final_owners(x, o, walls, (n - 1) % 2, entry_move_word(entry["moves"][n - 1]))
+    # the store's own check (a margin that contradicts the recorded result among it): the host pipeline, which never fills a
+    # store, refuses the games a store refuses
+    check(load().azh_samples_check_owners(own_x, own_o, walls, int(entry["result"]) & 0xFFFFFFFF))
+    return own_x, own_o
+
+
+def entries_to_arrays(entries, aux=False):
     """Parsed game lines -> SampleArrays, with the conversions of training._entry_arrays (weights np.float32 of the parsed
     double, "pass" keys skipped, an entry without `dists` a one-hot on the move played), in the order given; an entry's
-    "blockers" becomes its game's mask, after training.check_blockers (ValueError).  Host only."""
+    "blockers" becomes its game's mask, after training.check_blockers (ValueError).  aux: -> AuxSampleArrays, every game's
+    owners found by entry_owners (AzhError for a game whose last move is not legal at its last board).  Host only."""
     from . import training
+    owners = [entry_owners(e) for e in entries] if aux else None
     games, boards, flags, values, starts, index, weight = [], [], [], [], [np.zeros(1, dtype=np.int32)], [], []
     masks = []
     plies = targets = 0
@@ -952,28 +1020,38 @@ def entries_to_arrays(entries):
 
     def cat(parts, dtype):
         return np.concatenate(parts).astype(dtype, copy=False) if parts else np.zeros(0, dtype=dtype)
-    return SampleArrays(np.array(games, dtype=np.uint32).reshape(-1, 4), cat(boards, np.uint64).reshape(-1, 2),
-                        cat(flags, np.uint8), cat(values, np.float64), cat(starts, np.int32), cat(index, np.uint16),
-                        cat(weight, np.float32), np.array(masks, dtype=np.uint64))
+    arrays = (np.array(games, dtype=np.uint32).reshape(-1, 4), cat(boards, np.uint64).reshape(-1, 2),
+              cat(flags, np.uint8), cat(values, np.float64), cat(starts, np.int32), cat(index, np.uint16),
+              cat(weight, np.float32), np.array(masks, dtype=np.uint64))
+    if aux:
+        return AuxSampleArrays(*arrays, owners=np.array(owners, dtype=np.uint64).reshape(-1, 2))
+    return SampleArrays(*arrays)
 
 
-def pack_records(records, blockers=0):
+def pack_records(records, blockers=0, aux=False):
     """Ring records (Engine.staged_records) -> SampleArrays holding what parsing the games' own lines would give; blockers:
     the wall mask of the engine that wrote them, which a line written with "blockers" carries
-    (azh_samples_pack_records_blockers; host code, no GPU needed)."""
+    (azh_samples_pack_records_blockers; host code, no GPU needed).  aux: -> AuxSampleArrays with every game's owners from its
+    last ply's boards and move word (azh_samples_pack_records_aux; AzhError -2 for a last move that is not legal there)."""
     rec = np.ascontiguousarray(records, dtype=np.uint32).ravel()
     counts = np.zeros(3, dtype=np.int64)
-    check(load().azh_samples_pack_records_blockers(_ptr(rec), rec.size, int(blockers), _ptr(counts), None, None, None, None,
-                                                   None, None, None, None))
+
+    def call(*arrays):
+        if aux:
+            return load().azh_samples_pack_records_aux(_ptr(rec), rec.size, int(blockers), _ptr(counts), *arrays)
+        return load().azh_samples_pack_records_blockers(_ptr(rec), rec.size, int(blockers), _ptr(counts), *arrays[:-1])
+    check(call(*[None] * 9))
     g, p, t = (int(c) for c in counts)
-    a = SampleArrays(np.zeros((g, 4), np.uint32), np.zeros((p, 2), np.uint64), np.zeros(p, np.uint8), np.zeros(p),
-                     np.zeros(p + 1, np.int32), np.zeros(max(t, 1), np.uint16), np.zeros(max(t, 1), np.float32))
+    a = (AuxSampleArrays if aux else SampleArrays)(
+        np.zeros((g, 4), np.uint32), np.zeros((p, 2), np.uint64), np.zeros(p, np.uint8), np.zeros(p),
+        np.zeros(p + 1, np.int32), np.zeros(max(t, 1), np.uint16), np.zeros(max(t, 1), np.float32))
     games = a.games if g else np.zeros((1, 4), np.uint32)      # (non-null: a null `games` asks for the counts only)
-    masks = np.zeros(max(g, 1), np.uint64)
-    check(load().azh_samples_pack_records_blockers(_ptr(rec), rec.size, int(blockers), _ptr(counts), _ptr(games),
-                                                   _ptr(a.boards), _ptr(a.ply_flags), _ptr(a.values), _ptr(a.target_start),
-                                                   _ptr(a.target_index), _ptr(a.target_weight), _ptr(masks)))
+    masks, owners = np.zeros(max(g, 1), np.uint64), np.zeros((max(g, 1), 2), np.uint64)
+    check(call(_ptr(games), _ptr(a.boards), _ptr(a.ply_flags), _ptr(a.values), _ptr(a.target_start), _ptr(a.target_index),
+               _ptr(a.target_weight), _ptr(masks), _ptr(owners)))
     a.blockers = masks[:g]
+    if aux:
+        a.owners = owners[:g]
     a.target_index, a.target_weight = a.target_index[:t], a.target_weight[:t]
     return a
 
@@ -1099,20 +1177,36 @@ class SampleStore:
     def add_arrays(self, a):
         self._mirror = None
         masks = a.blockers if len(a.blockers) and a.blockers.any() else None
+        owners = getattr(a, "owners", None)
+        if owners is not None:                                # AuxSampleArrays: the games' owners go with them
+            check(load().azh_samples_add_games_aux(self.h, len(a.games), _ptr(a.games), len(a.ply_flags), _ptr(a.boards),
+                                                   _ptr(a.ply_flags), _ptr(a.values), _ptr(a.target_start),
+                                                   _ptr(a.target_index), _ptr(a.target_weight), _ptr(masks),
+                                                   _ptr(owners) if len(owners) else None))
+            return
         check(load().azh_samples_add_games_blockers(self.h, len(a.games), _ptr(a.games), len(a.ply_flags), _ptr(a.boards),
                                                     _ptr(a.ply_flags), _ptr(a.values), _ptr(a.target_start),
                                                     _ptr(a.target_index), _ptr(a.target_weight), _ptr(masks)))
 
-    def add_entries(self, entries):
+    def add_entries(self, entries, aux=False):
         """Parsed game lines, in the order given (entries_to_arrays)."""
-        self.add_arrays(entries_to_arrays(entries))
+        self.add_arrays(entries_to_arrays(entries, aux=aux))
 
-    def add_records(self, records, blockers=0):
+    def add_records(self, records, blockers=0, aux=False):
         """Ring records as Engine.staged_records returns them, and the wall mask of the engine that wrote them
-        (azh_samples_add_records_blockers)."""
+        (azh_samples_add_records_blockers; aux: with every game's owners, azh_samples_add_records_aux)."""
         rec = np.ascontiguousarray(records, dtype=np.uint32).ravel()
         self._mirror = None
-        check(load().azh_samples_add_records_blockers(self.h, _ptr(rec), rec.size, int(blockers)))
+        add = load().azh_samples_add_records_aux if aux else load().azh_samples_add_records_blockers
+        check(add(self.h, _ptr(rec), rec.size, int(blockers)))
+
+    def game_owners(self):
+        """-> (G, 2) u64: the cells x and o own at every stored game's end, 0 and 0 for a game without owners
+        (azh_samples_game_owners)."""
+        n = self.counts()["games"]
+        owners = np.zeros((max(n, 1), 2), np.uint64)
+        check(load().azh_samples_game_owners(self.h, _ptr(owners)))
+        return owners[:n]
 
     def game_blockers(self):
         """-> (G,) u64: every stored game's wall mask, 0 for a game without walls (azh_samples_game_blockers)."""
@@ -1143,6 +1237,15 @@ class SampleStore:
                 torch.empty((n, 1), dtype=torch.float32, device=device))
 
     @staticmethod
+    def aux_outputs(n, device="cuda"):
+        """outputs and the four auxiliary tensors: ownership (n, 7, 7), score (n, 1), reply (n, 7, 7, 17), aux_weight (n, 2)."""
+        import torch
+        return SampleStore.outputs(n, device) + (torch.empty((n, 7, 7), dtype=torch.float32, device=device),
+                                                 torch.empty((n, 1), dtype=torch.float32, device=device),
+                                                 torch.empty((n, 7, 7, 17), dtype=torch.float32, device=device),
+                                                 torch.empty((n, 2), dtype=torch.float32, device=device))
+
+    @staticmethod
     def _pointers(out, n):
         import torch
         shapes = ((n, 7, 7, 4), (n, 7, 7, 17), (n, 1))
@@ -1153,9 +1256,23 @@ class SampleStore:
         # and wait": hipStreamLegacy names the null stream itself, so the call is ordered behind torch's work and returns)
         return [ctypes.c_void_p(t.data_ptr()) for t in out], torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY
 
-    def gather(self, draws, value_blend=0.0, out=None):
+    @staticmethod
+    def _aux_pointers(out, n):
+        import torch
+        shapes = ((n, 7, 7, 4), (n, 7, 7, 17), (n, 1), (n, 7, 7), (n, 1), (n, 7, 7, 17), (n, 2))
+        if len(out) != len(shapes):
+            raise ValueError("out must be %d tensors" % len(shapes))
+        for t, shape in zip(out, shapes):
+            if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError("out must be contiguous float32 GPU tensors of shapes %r" % (shapes,))
+        return [ctypes.c_void_p(t.data_ptr()) for t in out], torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY
+
+    def gather(self, draws, value_blend=0.0, out=None, aux=False):
         """The minibatch of the draws (n, 3) of (game, ply, symmetry), enqueued on torch's current stream; `out`: the three
-        tensors to write (fresh ones by default).  A draw on a bad ply raises the host pipeline's AssertionError."""
+        tensors to write (fresh ones by default).  A draw on a bad ply raises the host pipeline's AssertionError.
+        aux: seven tensors, the auxiliary targets behind the three (aux_outputs; azh_samples_gather_aux)."""
+        if aux:
+            return self._gather_aux(draws, value_blend, out)
         draws = np.ascontiguousarray(draws, dtype=np.int32).reshape(-1, 3)
         out = self.outputs(len(draws)) if out is None else out
         ptrs, stream = self._pointers(out, len(draws))
@@ -1165,15 +1282,36 @@ class SampleStore:
         check(rc)
         return out
 
-    def draw_gather(self, n, seed, step, first_game, n_games, value_blend=0.0, out=None, draws_out=None):
+    def _gather_aux(self, draws, value_blend, out):
+        draws = np.ascontiguousarray(draws, dtype=np.int32).reshape(-1, 3)
+        out = self.aux_outputs(len(draws)) if out is None else out
+        ptrs, stream = self._aux_pointers(out, len(draws))
+        rc = load().azh_samples_gather_aux(self.h, len(draws), _ptr(draws), float(value_blend), *ptrs, stream)
+        if rc == -2:
+            raise AssertionError("policy target does not sum to one")
+        check(rc)
+        return out
+
+    def draw_gather(self, n, seed, step, first_game, n_games, value_blend=0.0, out=None, draws_out=None, aux=False):
         """A minibatch of n samples drawn on the device from games [first_game, first_game + n_games) with Philox keyed by
-        `seed` at counter `step`; draws_out: an (n, 4) int32 GPU tensor that receives (game, ply, symmetry, attempts)."""
+        `seed` at counter `step`; draws_out: an (n, 4) int32 GPU tensor that receives (game, ply, symmetry, attempts).
+        aux: seven tensors, as gather (azh_samples_draw_gather_aux)."""
         import torch
-        out = self.outputs(n) if out is None else out
-        ptrs, stream = self._pointers(out, n)
+        if aux:
+            out = self.aux_outputs(n) if out is None else out
+            ptrs, stream = self._aux_pointers(out, n)
+        else:
+            out = self.outputs(n) if out is None else out
+            ptrs, stream = self._pointers(out, n)
         if draws_out is not None and not (draws_out.is_cuda and draws_out.dtype == torch.int32 and
                                           tuple(draws_out.shape) == (n, 4) and draws_out.is_contiguous()):
             raise ValueError("draws_out must be a contiguous int32 GPU tensor of shape (n, 4)")
+        if aux:
+            check(load().azh_samples_draw_gather_aux(self.h, int(n), int(seed), int(step), int(first_game), int(n_games),
+                                                     float(value_blend), *ptrs,
+                                                     ctypes.c_void_p(draws_out.data_ptr()) if draws_out is not None else None,
+                                                     stream))
+            return out
         check(load().azh_samples_draw_gather(self.h, int(n), int(seed), int(step), int(first_game), int(n_games),
                                              float(value_blend), *ptrs,
                                              ctypes.c_void_p(draws_out.data_ptr()) if draws_out is not None else None, stream))

@@ -13,6 +13,7 @@ the net it plays with is not the net it trained.  Here gamma = 1, beta = 0 are f
 restores the reference's train-then-drop behaviour.
 """
 import json
+import os
 import random
 
 import numpy as np
@@ -154,9 +155,61 @@ def _value_target(entry, ply, mover, value_blend):
     return z
 
 
-def get_sample_from_entries(entries, value_blend=0.0):
-    """One training sample (train.py:43-77).  The draws from `random` come in the reference's order — game, ply,
-    symmetry — so a games file yields the same minibatches as there."""
+_OWNERS = {}              # id(entry) -> (entry, owner row): bounded like _ARRAYS
+
+
+def _entry_owner_row(entry):
+    """The owners of an entry's final position (link.entry_owners; include/ataxxzero_hip.h, "Auxiliary targets") as 49 int8 in
+    the index of its boards: +1 where x owns the cell, -1 where o does, 0 on walls — or None when the game has no owners."""
+    row = _OWNERS.get(id(entry))
+    if row is None or row[0] is not entry:
+        from . import link
+        own_x, own_o = link.entry_owners(entry)
+        cells = None
+        if own_x | own_o:
+            bits = [c % BOARD + BOARD * (BOARD - 1 - c // BOARD) for c in range(BOARD * BOARD)]
+            cells = np.array([((own_x >> b) & 1) - ((own_o >> b) & 1) for b in bits], dtype=np.int8)
+        if len(_OWNERS) >= _ARRAYS_MAX:
+            for key in list(_OWNERS)[:_ARRAYS_MAX // 10]:
+                del _OWNERS[key]
+        row = _OWNERS[id(entry)] = (entry, cells)
+    return row[1]
+
+
+def _reply_present(entry, ply):
+    """Is ply + 1 one a sample could have been drawn from (its target is then checked like any sample's)?"""
+    nxt = ply + 1
+    return (nxt < len(entry["boards"]) and entry["moves"][nxt] != "pass" and
+            ("full" not in entry or bool(entry["full"][nxt])))
+
+
+def aux_targets(entry, ply, symmetry):
+    """The auxiliary targets of the sample (entry, ply, symmetry) -> (ownership (7, 7), score (1,), reply (7, 7, 17),
+    aux_weight (2,)), float32, from the entry alone (include/ataxxzero_hip.h, "Auxiliary targets"): the final owners seen by
+    the mover under the symmetry, their margin, the policy target of ply + 1, and which of the two the sample has."""
+    mover = 1 + ply % 2
+    owners = _entry_owner_row(entry)
+    ownership = np.zeros((BOARD, BOARD), dtype=np.float32)
+    score = np.zeros(1, dtype=np.float32)
+    weight = np.zeros(2, dtype=np.float32)
+    if owners is not None:
+        seen = owners if mover == 1 else -owners
+        ownership = apply_symmetry(symmetry, seen.reshape(BOARD, BOARD).T[..., None])[..., 0].astype(np.float32)
+        score[0] = int(seen.sum())
+        weight[0] = 1.0
+    reply = np.zeros((BOARD, BOARD, MOVE_TYPES), dtype=np.float32)
+    if _reply_present(entry, ply):
+        try:
+            reply = _policy_target(entry, ply + 1, symmetry)
+            weight[1] = 1.0
+        except AssertionError:                      # a bad ply: no sample is drawn from it, and it is nobody's reply
+            pass
+    return ownership, score, reply, weight
+
+
+def _draw_sample(entries):
+    """(entry, ply, symmetry) of one sample.  The draws from `random` come in the reference's order — game, ply,
+    symmetry (train.py:45-60)."""
     while True:
         entry = random.choice(entries)
         ply = _draw_ply(entry)
@@ -166,11 +219,18 @@ def get_sample_from_entries(entries, value_blend=0.0):
             ply = entry["random_ply"] + 1
         if entry["moves"][ply] == "pass":
             continue
-        mover = 1 + ply % 2                         # x (1) moves on even plies
-        symmetry_index = random.randrange(8)
-        features = apply_symmetry(symmetry_index, board_to_features(entry["boards"][ply], mover, entry.get("blockers")))
-        value = [_value_target(entry, ply, mover, value_blend)]
-        return features, _policy_target(entry, ply, symmetry_index), value
+        return entry, ply, random.randrange(8)
+
+
+def get_sample_from_entries(entries, value_blend=0.0, aux=False):
+    """One training sample (train.py:43-77).  The draws from `random` come in the reference's order — game, ply,
+    symmetry — so a games file yields the same minibatches as there.  aux: the sample's aux_targets behind the three."""
+    entry, ply, symmetry_index = _draw_sample(entries)
+    mover = 1 + ply % 2                             # x (1) moves on even plies
+    features = apply_symmetry(symmetry_index, board_to_features(entry["boards"][ply], mover, entry.get("blockers")))
+    value = [_value_target(entry, ply, mover, value_blend)]
+    sample = features, _policy_target(entry, ply, symmetry_index), value
+    return sample + aux_targets(entry, ply, symmetry_index) if aux else sample
 
 
 def load_entries(paths):
@@ -186,15 +246,14 @@ def load_entries(paths):
     return entries
 
 
-def make_minibatch_reference(entries, size, value_blend=0.0):
-    """`size` samples drawn one by one with get_sample_from_entries (train.py:123-130)."""
-    feats, pols, vals = [], [], []
+def make_minibatch_reference(entries, size, value_blend=0.0, aux=False):
+    """`size` samples drawn one by one with get_sample_from_entries (train.py:123-130).  aux: seven arrays, the samples'
+    aux_targets (ownership, score, reply, aux_weight) behind the three; `random` is consumed as without it."""
+    columns = [[] for _ in range(7 if aux else 3)]
     for _ in range(size):
-        f, p, v = get_sample_from_entries(entries, value_blend)
-        feats.append(f)
-        pols.append(p)
-        vals.append(v)
-    return (np.asarray(feats, dtype=np.float32), np.asarray(pols, dtype=np.float32), np.asarray(vals, dtype=np.float32))
+        for column, part in zip(columns, get_sample_from_entries(entries, value_blend, aux)):
+            column.append(part)
+    return tuple(np.asarray(column, dtype=np.float32) for column in columns)
 
 
 def _symmetry_tables():
@@ -270,15 +329,16 @@ def _entry_arrays(entry):
     return cache
 
 
-def make_minibatch(entries, size, value_blend=0.0):
+def make_minibatch(entries, size, value_blend=0.0, aux=False):
     """The same `size` samples as make_minibatch_reference — same draws from `random` in the same order, bit-identical
     arrays (tests/test_training.py) — assembled with array operations instead of per-sample Python: the sample pipeline,
-    not the GPU step, bounded train.py's rate.  value_blend: _value_target."""
+    not the GPU step, bounded train.py's rate.  value_blend: _value_target.  aux: seven arrays, as make_minibatch_reference."""
     global _TABLES
     if _TABLES is None:
         _TABLES = _symmetry_tables()
     cell_src, policy_to = _TABLES
     cells, movers, syms, targets, rows, pidx, pw, walls = [], [], [], [], [], [], [], {}
+    owned, r_rows, r_idx, r_w = {}, [], [], []
     while len(cells) < size:
         entry = random.choice(entries)                      # the reference's draws, in its order (train.py:45-60)
         ply = _draw_ply(entry)
@@ -296,6 +356,15 @@ def make_minibatch(entries, size, value_blend=0.0):
         pw.append(wts[lo:hi])
         if entry.get("blockers"):
             walls[len(cells)] = _wall_row(entry["blockers"])
+        if aux:
+            owners = _entry_owner_row(entry)
+            if owners is not None:
+                owned[len(cells)] = owners if ply % 2 == 0 else -owners
+            if _reply_present(entry, ply):
+                lo, hi = start[ply + 1], start[ply + 2]
+                r_rows.append(np.full(hi - lo, len(cells), dtype=np.int64))
+                r_idx.append(policy_to[sym, idx[lo:hi]])
+                r_w.append(wts[lo:hi])
         cells.append(c[ply])
         movers.append(1 + ply % 2)
         syms.append(sym)
@@ -314,11 +383,29 @@ def make_minibatch(entries, size, value_blend=0.0):
     if (np.abs(1 - pols.sum(axis=1)) >= 1e-3).any():
         raise AssertionError("policy target does not sum to one")
     vals = np.asarray(targets, dtype=np.float32)[:, None]
-    return feats.reshape(size, BOARD, BOARD, 4), pols.reshape(size, BOARD, BOARD, MOVE_TYPES), vals
+    batch = feats.reshape(size, BOARD, BOARD, 4), pols.reshape(size, BOARD, BOARD, MOVE_TYPES), vals
+    if not aux:
+        return batch
+    ownership = np.zeros((size, BOARD * BOARD), dtype=np.float32)
+    score = np.zeros((size, 1), dtype=np.float32)
+    weight = np.zeros((size, 2), dtype=np.float32)
+    for i, seen in owned.items():                           # the owners as the mover sees them, under the sample's symmetry
+        ownership[i] = seen[cell_src[syms[i]]]
+        score[i, 0] = int(seen.sum())
+        weight[i, 0] = 1.0
+    replies = np.zeros((size, BOARD * BOARD * MOVE_TYPES), dtype=np.float32)
+    if r_rows:
+        np.add.at(replies, (np.concatenate(r_rows), np.concatenate(r_idx)), np.concatenate(r_w))
+        weight[np.unique(np.concatenate(r_rows)), 1] = 1.0
+    for i in np.flatnonzero(np.abs(1 - replies.sum(axis=1)) >= 1e-3):     # a bad ply (or no ply) is nobody's reply
+        replies[i] = 0
+        weight[i, 1] = 0.0
+    return batch + (ownership.reshape(size, BOARD, BOARD), score, replies.reshape(size, BOARD, BOARD, MOVE_TYPES), weight)
 
 
 # ---------------------------------------------------------------- device-resident samples (link.SampleStore)
 
+AUX_SEED = 987654321                  # numpy's PCG64 seed of freshly initialised auxiliary heads (Network(aux_heads=True))
 DEVICE_DRAW_SEED = 123456789          # train.py --device-draws: the Philox key of the draws made on the device
 
 
@@ -335,14 +422,15 @@ def _draw_tables(store):
 
 
 def make_minibatch_device(store, first_game, n_games, size, value_blend=0.0, out=None, draws="reference", seed=DEVICE_DRAW_SEED,
-                          step=0):
+                          step=0, aux=False):
     """`size` samples of the games [first_game, first_game + n_games) of a link.SampleStore, written by its kernel into the three
     GPU tensors `out` (fresh ones by default) -> out.  draws="reference": Python's `random` is consumed exactly as make_minibatch
     consumes it for entries[first_game:first_game + n_games] — game, ply among the candidates, the random_ply replacement, the
     pass rejection, symmetry — so the same games give the same minibatches, bit for bit; draws="device": the kernel draws with
-    Philox keyed by `seed` at counter `step` (SampleStore.draw_gather)."""
+    Philox keyed by `seed` at counter `step` (SampleStore.draw_gather).  aux: seven tensors, the auxiliary targets behind the
+    three (SampleStore.aux_outputs), for the same draws."""
     if draws == "device":
-        return store.draw_gather(size, seed, step, first_game, n_games, value_blend, out=out)
+        return store.draw_gather(size, seed, step, first_game, n_games, value_blend, out=out, aux=aux)
     if draws != "reference":
         raise ValueError("draws must be \"reference\" or \"device\"")
     from . import link
@@ -368,13 +456,13 @@ def make_minibatch_device(store, first_game, n_games, size, value_blend=0.0, out
         if flags[first + ply] & link.SAMPLES_PLY_PASS:
             continue
         rows.append((g, ply, random.randrange(8)))
-    return store.gather(np.asarray(rows, dtype=np.int32), value_blend, out=out)
+    return store.gather(np.asarray(rows, dtype=np.int32), value_blend, out=out, aux=aux)
 
 
-def _fill_store(entries, log):
+def _fill_store(entries, log, aux=False):
     from . import link
     link.require_gpu()
-    arrays = link.entries_to_arrays(entries)
+    arrays = link.entries_to_arrays(entries, aux=aux)
     store = link.SampleStore(max(len(arrays.games), 1), max(len(arrays.ply_flags), 1), max(len(arrays.target_index), 1))
     store.add_arrays(arrays)
     c = store.counts()
@@ -434,12 +522,34 @@ def _apply_surprise(store, old_path, lam, dtype, n_test, log):
 
 # ---------------------------------------------------------------- the network (model.py:38-101)
 
+def aux_random_init(filters, seed=1):
+    """Fresh weights of the auxiliary heads in torch's layouts, with model.random_init's distributions (truncated normal,
+    stddev 0.2 * sqrt(2 / fan_in); bias 0.01), from numpy's PCG64(seed) alone."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+
+    def weights(shape, fan_in):
+        return model._truncated_normal(rng, shape, 0.2 * (2.0 / fan_in) ** 0.5)
+
+    return {"aux_conv": weights((2, filters, 1, 1), filters), "aux_fc_weight": weights((1, BOARD * BOARD), BOARD * BOARD),
+            "aux_fc_bias": np.full((1,), 0.01, dtype=np.float32), "reply_conv": weights((MOVE_TYPES, filters, 1, 1), filters)}
+
+
+def aux_sidecar(path):
+    """Where the auxiliary heads of the network at `path` are kept: plain arrays, no pickle."""
+    return path + ".aux.npz"
+
+
 class Network(nn.Module):
     """model.Network in NCHW: tensors are [n][c][x][y] (the reference's [n][x][y][c] permuted)."""
 
-    def __init__(self, blocks=12, filters=128, reference_bn_affine=False):
+    def __init__(self, blocks=12, filters=128, reference_bn_affine=False, aux_heads=False, aux_seed=1):
+        """aux_heads: two heads that exist only while training (include/ataxxzero_hip.h, "Auxiliary targets") — a 1x1 conv
+        filters -> 2 (channel 0 through tanh: the ownership; channel 1 flattened into Linear(49, 1): the score in units of 49
+        stones) and a 1x1 conv filters -> 17 (the reply logits) — read by aux_forward and forward_all; forward, the state_dict
+        of the rest and to_numpy are what they are without them.  Their weights come from numpy's PCG64(aux_seed), truncated normal as
+        model.random_init; torch's global generator is left as it was."""
         super().__init__()
-        self.blocks, self.filters = blocks, filters
+        self.blocks, self.filters, self.aux_heads = blocks, filters, bool(aux_heads)
 
         def conv(cin, cout, k):
             return nn.Conv2d(cin, cout, k, padding=k // 2, bias=False)
@@ -453,17 +563,64 @@ class Network(nn.Module):
         self.policy = conv(filters, MOVE_TYPES, 1)
         self.value_conv = conv(filters, 1, 1)
         self.fc = nn.Linear(BOARD * BOARD, 1)
+        if self.aux_heads:
+            with torch.random.fork_rng(devices=[]):                        # (the modules' own initialisation is thrown away)
+                self.aux_conv = conv(filters, 2, 1)
+                self.aux_fc = nn.Linear(BOARD * BOARD, 1)
+                self.reply_conv = conv(filters, MOVE_TYPES, 1)
+            self.load_aux_numpy(aux_random_init(filters, aux_seed))
 
-    def forward(self, x):
+    def _trunk(self, x):
         h = F.relu(self.bns[0](self.convs[0](x)))
         for b in range(self.blocks):
             t = F.relu(self.bns[1 + 2 * b](self.convs[1 + 2 * b](h)))
             t = self.bns[2 + 2 * b](self.convs[2 + 2 * b](t))
             h = F.relu(t + h)
+        return h
+
+    def _heads(self, x, h):
         policy = self.policy(h)                                            # [n][17][x][y]
         v = self.value_conv(h).reshape(x.shape[0], BOARD * BOARD)          # index x*7 + y, as tf.reshape of [n,x,y,1]
         value = torch.tanh(self.fc(v))
         return policy.permute(0, 2, 3, 1), value                           # policy back to [n][x][y][17]
+
+    def _aux_heads(self, x, h):
+        a = self.aux_conv(h)
+        ownership = torch.tanh(a[:, 0])
+        score = self.aux_fc(a[:, 1].reshape(x.shape[0], BOARD * BOARD))
+        return ownership, score, self.reply_conv(h).permute(0, 2, 3, 1)
+
+    def aux_forward(self, x):
+        """-> (ownership [n][x][y] in (-1, 1), score [n][1] in units of 49 stones, reply logits [n][x][y][17]): a pass through
+        the tower of its own."""
+        return self._aux_heads(x, self._trunk(x))
+
+    def forward_all(self, x):
+        """-> forward(x) + aux_forward(x) from ONE pass through the tower: what a training step uses, so that the batch-norm
+        statistics are updated once per step."""
+        h = self._trunk(x)
+        return self._heads(x, h) + self._aux_heads(x, h)
+
+    def aux_to_numpy(self):
+        """The heads' weights as plain arrays (the sidecar of train())."""
+        return {"aux_conv": self.aux_conv.weight.detach().cpu().numpy().copy(),
+                "aux_fc_weight": self.aux_fc.weight.detach().cpu().numpy().copy(),
+                "aux_fc_bias": self.aux_fc.bias.detach().cpu().numpy().copy(),
+                "reply_conv": self.reply_conv.weight.detach().cpu().numpy().copy()}
+
+    def load_aux_numpy(self, arrays):
+        """False, with nothing changed, when an array is missing or a shape does not fit."""
+        mine = {"aux_conv": self.aux_conv.weight, "aux_fc_weight": self.aux_fc.weight, "aux_fc_bias": self.aux_fc.bias,
+                "reply_conv": self.reply_conv.weight}
+        if any(k not in arrays or tuple(np.asarray(arrays[k]).shape) != tuple(p.shape) for k, p in mine.items()):
+            return False
+        with torch.no_grad():
+            for k, p in mine.items():
+                p.copy_(torch.from_numpy(np.ascontiguousarray(arrays[k], dtype=np.float32)))
+        return True
+
+    def forward(self, x):
+        return self._heads(x, self._trunk(x))
 
     # .npy layout <-> torch: conv HWIO (i, j, c, o) <-> OIHW with H = x (i), W = y (j)
     def load_numpy(self, conv_weights, bn_params):
@@ -489,11 +646,11 @@ class Network(nn.Module):
         return cw, bn
 
 
-def link_outputs(store, n, device):
-    """The three tensors a store's kernel writes a minibatch of n samples into, on `device`."""
+def link_outputs(store, n, device, aux=False):
+    """The three tensors a store's kernel writes a minibatch of n samples into, on `device` (aux: the seven)."""
     if torch.device(device).type != "cuda":
         raise RuntimeError("device samples need a GPU: the gather has no CPU path")
-    return store.outputs(n, device)
+    return store.aux_outputs(n, device) if aux else store.outputs(n, device)
 
 
 def losses(net, features, policies, values):
@@ -508,9 +665,40 @@ def losses(net, features, policies, values):
     return policy_loss, value_loss, reg
 
 
+def _aux_loss_terms(predictions, ownership, score, reply, aux_weight):
+    own, sc, logits = predictions
+    n = own.shape[0]
+    w_final, w_reply = aux_weight[:, 0], aux_weight[:, 1]
+    per_own = ((own - ownership) ** 2).reshape(n, -1).mean(dim=1)
+    per_score = ((sc - score / float(BOARD * BOARD)) ** 2).reshape(n)
+    per_reply = -(reply.reshape(n, -1) * F.log_softmax(logits.reshape(n, -1), dim=1)).sum(dim=1)
+    d_final, d_reply = w_final.sum().clamp(min=1.0), w_reply.sum().clamp(min=1.0)
+    return (w_final * per_own).sum() / d_final, (w_final * per_score).sum() / d_final, (w_reply * per_reply).sum() / d_reply
+
+
+def aux_losses(net, features, ownership, score, reply, aux_weight):
+    """The three auxiliary losses of a Network with aux_heads -> (ownership, score, reply) scalars: per sample the mean over
+    the 49 cells of (tanh - target)^2, (prediction - score / 49)^2, and the softmax cross-entropy of the reply over the 833
+    cells; each averaged over the samples that have the target, sum w_i L_i / max(1, sum w_i) with w = aux_weight[:, 0] for the
+    first two and aux_weight[:, 1] for the reply.  A pass through the tower of its own (net.aux_forward): a training step
+    uses all_losses."""
+    return _aux_loss_terms(net.aux_forward(features.permute(0, 3, 1, 2)), ownership, score, reply, aux_weight)
+
+
+def all_losses(net, features, policies, values, ownership, score, reply, aux_weight):
+    """losses(...) + aux_losses(...) -> six scalars from one pass through the tower (net.forward_all)."""
+    logits, v, *aux = net.forward_all(features.permute(0, 3, 1, 2))
+    n = features.shape[0]
+    logp = F.log_softmax(logits.reshape(n, -1), dim=1)
+    policy_loss = -(policies.reshape(n, -1) * logp).sum(dim=1).mean()
+    value_loss = ((values - v) ** 2).mean()
+    reg = 1e-4 * sum((p ** 2).sum() / 2 for p in net.parameters() if p.requires_grad)
+    return (policy_loss, value_loss, reg) + _aux_loss_terms(aux, ownership, score, reply, aux_weight)
+
+
 def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learning_rate=0.001, blocks=12, filters=128,
           reference_bn_affine=False, device=None, log=print, value_blend=0.0, device_samples=False, device_draws=False,
-          surprise_weight=0.0, surprise_dtype="bf16"):
+          surprise_weight=0.0, surprise_dtype="bf16", aux_ownership=0.0, aux_score=0.0, aux_reply=0.0):
     """device_samples: the entries are put into a link.SampleStore once and every minibatch is written by its kernel into
     tensors allocated once (make_minibatch_device) — the same minibatches as without it, no per-step host-to-device copy of
     the batch; device_draws (implies device_samples): the kernel also draws the samples.  Both need a GPU.
@@ -523,6 +711,9 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
         if old_path is None:
             raise ValueError("--surprise-weight needs --old-path: the surprise is measured against that network")
         device_samples = device_draws = True
+    if min(aux_ownership, aux_score, aux_reply) < 0.0:
+        raise ValueError("the auxiliary loss weights must not be negative")
+    aux = bool(aux_ownership or aux_score or aux_reply)                   # all zero: no head, no sidecar, the run as it was
     random.seed(123456789)                                                # train.py:103
     entries = load_entries(games_paths)
     ply_count = sum(len(e["moves"]) for e in entries)
@@ -539,26 +730,44 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
     else:
         log("WARNING: Not loading a previous model!")
         cw, bnp = model.random_init(blocks, filters, seed=random.randrange(1 << 30))
-    net = Network(blocks, filters, reference_bn_affine).to(device)
+    if aux:                                                               # heads that exist only while training
+        net = Network(blocks, filters, reference_bn_affine, aux_heads=True, aux_seed=AUX_SEED).to(device)
+        sidecar = aux_sidecar(old_path) if old_path is not None else None
+        if sidecar is not None and os.path.exists(sidecar):
+            with np.load(sidecar, allow_pickle=False) as kept:
+                loaded = net.load_aux_numpy(kept)
+            log("Auxiliary heads: %s." % ("read from " + sidecar if loaded else
+                                          sidecar + " does not fit this network; freshly initialised"))
+        else:
+            log("Auxiliary heads: freshly initialised.")
+    else:
+        net = Network(blocks, filters, reference_bn_affine).to(device)
     net.load_numpy(cw, bnp)
     opt = torch.optim.SGD(net.parameters(), lr=learning_rate, momentum=0.9)   # tf.train.MomentumOptimizer (model.py:99-100)
 
     def to_dev(batch):
         return tuple(torch.from_numpy(a).to(device) for a in batch)
 
-    store = _fill_store(entries, log) if device_samples or device_draws else None
+    store = _fill_store(entries, log, aux) if device_samples or device_draws else None
+    if aux:
+        if store is not None:
+            with_owners = int(store.game_owners()[min(10, len(entries)):].any(axis=1).sum())
+        else:
+            with_owners = sum(_entry_owner_row(e) is not None for e in train_entries)
+        log("Auxiliary targets: %i of %i training games have owners (a final position the rules adjudicate)."
+            % (with_owners, len(train_entries)))
     if store is not None:                                                 # validation: games [0, 10); training: [10, n)
         draws = "device" if device_draws else "reference"
         n_test = min(10, len(entries))
         if len(entries) <= n_test:
             raise ValueError("device samples need more than %d games" % n_test)
-        train_out = link_outputs(store, minibatch_size, device)
+        train_out = link_outputs(store, minibatch_size, device, aux)
         if surprise_weight > 0.0:
             _apply_surprise(store, old_path, surprise_weight, surprise_dtype, n_test, log)
 
         def next_batch(step):
             return make_minibatch_device(store, n_test, len(entries) - n_test, minibatch_size, value_blend, train_out, draws,
-                                         step=1 + step)
+                                         step=1 + step, aux=aux)
 
         def check_store():
             failed = store.status() if device_draws else 0
@@ -566,16 +775,17 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
                 raise RuntimeError("%d samples found no drawable ply in 64 attempts" % failed)
     else:
         def next_batch(step):
-            return to_dev(make_minibatch(train_entries, minibatch_size, value_blend))
+            return to_dev(make_minibatch(train_entries, minibatch_size, value_blend, aux))
 
         def check_store():
             pass
 
     random.seed(123456789)                                                # train.py:131
     if store is not None:
-        val_set = make_minibatch_device(store, 0, n_test, 2048, value_blend, link_outputs(store, 2048, device), draws, step=0)
+        val_set = make_minibatch_device(store, 0, n_test, 2048, value_blend, link_outputs(store, 2048, device, aux), draws,
+                                        step=0, aux=aux)
     else:
-        val_set = to_dev(make_minibatch(test_entries, 2048, value_blend))
+        val_set = to_dev(make_minibatch(test_entries, 2048, value_blend, aux))
     log("")
     log("Model dimensions: %i filters, %i blocks, %i parameters." % (
         filters, blocks, sum(int(np.prod(a.shape)) for a in cw)))
@@ -585,16 +795,30 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
         if step_number % 100 == 0:
             net.eval()
             with torch.no_grad():
-                pl, vl, _ = losses(net, *val_set)
-            log("Step: %4i -- loss: %.6f  (policy: %.6f  value: %.6f)" % (step_number, float(pl + vl), float(pl), float(vl)))
+                tail = ""
+                if aux:
+                    pl, vl, _, ol, sl, rl = all_losses(net, *val_set)
+                    tail = "  own: %.6f  score: %.6f  reply: %.6f" % (float(ol), float(sl), float(rl))
+                else:
+                    pl, vl, _ = losses(net, *val_set)
+            log("Step: %4i -- loss: %.6f  (policy: %.6f  value: %.6f%s)" % (step_number, float(pl + vl), float(pl), float(vl), tail))
             check_store()
         net.train()
         batch = next_batch(step_number)
-        pl, vl, reg = losses(net, *batch)
+        if aux:                                                           # one pass through the tower for all five heads
+            pl, vl, reg, ol, sl, rl = all_losses(net, *batch)
+            loss = pl + vl + reg + aux_ownership * ol + aux_score * sl + aux_reply * rl
+        else:
+            pl, vl, reg = losses(net, *batch)
+            loss = pl + vl + reg
         opt.zero_grad(set_to_none=True)
-        (pl + vl + reg).backward()
+        loss.backward()
         opt.step()
     check_store()
     model.save_model(new_path, *net.to_numpy())
     log("\x1b[35mSaved model to:\x1b[0m %s" % new_path)
+    if aux:
+        with open(aux_sidecar(new_path), "wb") as f:                      # (np.savez would append ".npz" to a bare path)
+            np.savez(f, **net.aux_to_numpy())
+        log("Saved the auxiliary heads to: %s" % aux_sidecar(new_path))
     return net

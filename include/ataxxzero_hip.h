@@ -854,6 +854,83 @@ int azh_samples_draw_weighted(uint64_t seed, uint32_t step, uint32_t sample, int
                               const uint32_t *games, int64_t total_games, const uint8_t *ply_flags,
                               const uint16_t *candidates, const uint32_t *cum, int32_t *out);
 
+/* ------------------------------------------------------------------ auxiliary targets
+ * (an extension of the store; with none of these called, every byte written above is what it was.)  Three further training
+ * targets per sample — who ends up owning each cell, by how many stones the game is won, what the opponent answers — from what
+ * the store already holds plus the end of each game.
+ *
+ * Final position.  The final position F of a stored game is the position after the move played at its last recorded ply.  The
+ * side to move at ply p is x for even p, as everywhere in the store.  So F has x to move iff `plies` is even.  A last move of
+ * "pass" only hands the turn over.
+ * F is TERMINAL iff the kernels' adjudication gives a result there.  The order of checks is the one of wave_movegen:
+ *   1. a side without stones loses;
+ *   2. else a side to move without a move hands every empty cell to its opponent;
+ *   3. a full board goes to the larger count, and a tie goes to x.
+ *
+ * Owners (two 49-bit masks per game).  Bit = file + 7 * rank, the ring record's layout.  Both masks are 0 when F is not
+ * terminal.  That covers games cut at the ply limit, resigned games and truncated files.  When F is terminal, each cell is
+ * assigned as follows:
+ *   - a stone belongs to its colour;
+ *   - a wall belongs to nobody;
+ *   - an empty cell belongs to the only side that has stones, if one side has none;
+ *   - otherwise an empty cell belongs to the side NOT to move in F (the mover is stuck).
+ * The masks are therefore disjoint, disjoint from the walls, and together cover every non-wall cell.
+ * Let margin_x = popcount(x-owned) - popcount(o-owned).  It must agree with the recorded result: > 0 => 1, < 0 => 2, = 0 => 1.
+ * A game where it does not is refused at ingest (-2, the game named, nothing added).
+ * The reference's Python result() differs from the kernels' order on one freak board: the mover is stuck and the opponent has
+ * no stones (and a cell is empty).  Such a final position is refused: azh_samples_final_owners returns -2 there.
+ *
+ * Per-sample outputs.  Each sample is a (game g, ply p, symmetry s) with mover m = 1 + p % 2.  All outputs are f32.
+ *   - ownership [n][7][7]: cell [X][Y] of the image under s, using the same source-cell map as feature planes 1-3.  It holds
+ *     +1 where the source cell is owned by m, -1 where owned by the opponent, and 0 on walls.  It is all zeros when the game
+ *     has no owners.
+ *   - score [n][1]: popcount(owned by m) - popcount(owned by the opponent) as a float.  This is an exact integer in -49..49.
+ *     It is 0 without owners.
+ *   - reply [n][7][7][17]: the policy target of ply p + 1, each weight placed at azh_symmetry_policy_index(s, index), exactly
+ *     as `policy` is built for ply p.  The row is all zeros unless the reply is present.
+ *   - The reply is PRESENT iff all three hold: p + 1 < plies; ply p + 1 is neither PASS nor BAD; and the game either has no
+ *     "full" or ply p + 1 is FULL.
+ *   - aux_weight [n][2]: {1.0 if the game has owners else 0.0, 1.0 if the reply is present else 0.0}.
+ *   - A failed device draw (g < 0) writes zeros everywhere, the weights included.
+ * All values are exact: small integers, or single f32 weights landing on distinct cells.
+ *
+ * azh_samples_final_owners: host arithmetic only, no device and no store.  Applies the ring record's 16-bit move (from |
+ * to << 8, a clone has from == to, PASS is 0xFFFF) for the side to move (o iff o_to_move) to the position (x, o) on a board with
+ * walls `blockers`, and returns the owners of the position reached in owners_out [2] (x-owned, o-owned) and its result in
+ * *result_out (0, with owners 0, when it is not terminal).  -2 for a move that is not legal there — a pass with a move
+ * available, a source that is not the mover's, a destination that is not empty, a wrong distance, a stone or destination on a
+ * wall — found with the move list of azh_samples_legal_blockers, and for the freak board above. */
+int azh_samples_final_owners(uint64_t x, uint64_t o, uint64_t blockers, int o_to_move, uint32_t move, uint64_t *owners_out,
+                             int32_t *result_out);
+/* azh_samples_add_games_blockers with game_owners [n_games][2] (x-owned, o-owned), or NULL: none has owners.  The store keeps
+ * them in a device array [cap_games][2] that is allocated when the first game with non-zero owners arrives.  -2, store
+ * unchanged, the game named, for: overlapping masks; bits on walls or beyond the 49 cells; non-zero masks that leave a non-wall
+ * cell unowned; a margin that contradicts the result. */
+int azh_samples_add_games_aux(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies, const uint64_t *boards,
+                              const uint8_t *ply_flags, const double *values, const int32_t *target_start,
+                              const uint16_t *target_index, const float *target_weight, const uint64_t *game_blockers,
+                              const uint64_t *game_owners);
+/* The check azh_samples_add_games_aux makes of one game's owners against its walls and its recorded result, by itself: 0, or -2
+ * with the reason in azh_last_error.  Masks that are both 0 pass.  Host arithmetic only: no device, no store. */
+int azh_samples_check_owners(uint64_t own_x, uint64_t own_o, uint64_t blockers, uint32_t result);
+/* azh_samples_pack_records_blockers / azh_samples_add_records_blockers that also compute each game's owners:
+ * azh_samples_final_owners of the last ply's boards and move word with `blockers`, into game_owners [games][2] (or NULL).  A
+ * record whose last move is not legal at its last board is -2, with nothing written (also when only the counts are asked for). */
+int azh_samples_pack_records_aux(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts, uint32_t *games,
+                                 uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
+                                 uint16_t *target_index, float *target_weight, uint64_t *game_blockers, uint64_t *game_owners);
+int azh_samples_add_records_aux(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers);
+/* The host mirror of the owners, owners [games][2]. */
+int azh_samples_game_owners(const azh_samples *s, uint64_t *owners);
+/* azh_samples_gather / azh_samples_draw_gather with four more DEVICE arrays: the same draw checks, pinned staging, stream
+ * contract and error codes, and for the same draws the same bytes in features, policy and value (and draws_out).  A store in
+ * which no game has owners is served: final weight 0 everywhere, reply as defined. */
+int azh_samples_gather_aux(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features, float *policy,
+                           float *value, float *ownership, float *score, float *reply, float *aux_weight, uintptr_t stream);
+int azh_samples_draw_gather_aux(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game, int64_t n_games,
+                                double value_blend, float *features, float *policy, float *value, float *ownership,
+                                float *score, float *reply, float *aux_weight, int32_t *draws_out, uintptr_t stream);
+
 /* ------------------------------------------------------------------ reference ABI
  * The four symbols link.py:6-32 binds (cpp/self_play_client.cpp:683-749), with
  * the worker threads replaced by GPU game slots: `thread_count` concurrent

@@ -7,7 +7,10 @@ Self-play games of a random 2-block net are written to a temporary file; `train.
 without flags (the host pipeline), with --device-samples and with --device-draws — each in a process of its own, wall time
 from start to exit; then one process times SampleStore.add_entries and, by HIP events on torch's stream, the gather at
 minibatch sizes 512 and 2048 (and 32768, where the device and not the host's enqueue rate sets the time) with host draws
-(check of the draws and staging copy included) and with device draws."""
+(check of the draws and staging copy included) and with device draws.  --aux: the games carry "blockers" (the walls of the
+self-play start: a game's owners are found from its line alone), the store also holds the games' owners, and the kernels that
+write the auxiliary targets as well (ownership, score, reply, weights: 4 * 885 more bytes per sample) are timed beside the
+others."""
 import argparse
 import json
 import os
@@ -20,12 +23,15 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 SAMPLE_BYTES = 4 * (196 + 833 + 1)
+AUX_BYTES = 4 * (49 + 1 + 833 + 2)
 
 
-def generate(path, games):
+def generate(path, games, record_blockers=False):
     from ataxxzero_amd import model, selfplay
     conv, bn = model.random_init(2, 128, seed=1)
     sp = selfplay.SelfPlay(conv, bn, games=1024, visits=32, dtype="bf16", seed=7)
+    if record_blockers:                  # the owners are found from a line alone: it has to name the walls of its board
+        sp.set_record_blockers(True)
     lines = []
     while len(lines) < games:
         sp.run(100)
@@ -35,13 +41,13 @@ def generate(path, games):
         f.write(b"\n".join(lines[:games]).decode() + "\n")
 
 
-def kernel_times(path):
+def kernel_times(path, aux=False):
     import torch
     from ataxxzero_amd import link, training
     random.seed(1)
     entries = training.load_entries([path])
     t0 = time.perf_counter()
-    arrays = link.entries_to_arrays(entries)
+    arrays = link.entries_to_arrays(entries, aux=aux)
     t1 = time.perf_counter()
     store = link.SampleStore(len(arrays.games), len(arrays.ply_flags), len(arrays.target_index))
     store.add_arrays(arrays)
@@ -50,14 +56,22 @@ def kernel_times(path):
     print("store: %(games)d games, %(plies)d plies, %(targets)d targets, %(bad_plies)d bad plies" % c)
     print("add_entries: %.2f s converting the parsed lines on the host (training._entry_arrays per entry), %.3f s checking "
           "and copying them to the device" % (t1 - t0, t2 - t1))
+    if aux:
+        print("owners: %d of %d games have them" % (int(store.game_owners().any(axis=1).sum()), c["games"]))
     for n in (512, 2048, 32768):     # (32768: large enough for the device, not the host's enqueue rate, to set the time)
-        out = store.outputs(n)
+        out, aux_out = store.outputs(n), store.aux_outputs(n) if aux else None
         draws = torch.zeros((n, 4), dtype=torch.int32, device="cuda")
         store.draw_gather(n, 1, 0, 0, c["games"], 0.0, out=out, draws_out=draws)
         host_draws = draws.cpu().numpy()[:, :3].copy()
         assert (host_draws >= 0).all()
-        for name, call in (("host draws", lambda k: store.gather(host_draws, 0.0, out=out)),
-                           ("device draws", lambda k: store.draw_gather(n, 1, k, 0, c["games"], 0.0, out=out))):
+        calls = [("host draws", SAMPLE_BYTES, lambda k: store.gather(host_draws, 0.0, out=out)),
+                 ("device draws", SAMPLE_BYTES, lambda k: store.draw_gather(n, 1, k, 0, c["games"], 0.0, out=out))]
+        if aux:
+            calls += [("host draws, aux", SAMPLE_BYTES + AUX_BYTES,
+                       lambda k: store.gather(host_draws, 0.0, out=aux_out, aux=True)),
+                      ("device draws, aux", SAMPLE_BYTES + AUX_BYTES,
+                       lambda k: store.draw_gather(n, 1, k, 0, c["games"], 0.0, out=aux_out, aux=True))]
+        for name, sample_bytes, call in calls:
             for k in range(5):
                 call(k)
             torch.cuda.synchronize()
@@ -71,8 +85,9 @@ def kernel_times(path):
             w1 = time.perf_counter()
             torch.cuda.synchronize()
             us = start.elapsed_time(stop) * 1000.0 / reps
-            print("gather, %4d samples, %-12s: %7.1f us per minibatch by HIP events (%.1f us of host time per call to "
-                  "enqueue), %.1f GB/s written" % (n, name, us, (w1 - w0) * 1e6 / reps, n * SAMPLE_BYTES / us / 1e3))
+            print("gather, %4d samples, %s: %7.1f us per minibatch by HIP events (%.1f us of host time per call to "
+                  "enqueue), %.1f GB/s written" % (n, name.ljust(17 if aux else 12), us, (w1 - w0) * 1e6 / reps,
+                                                   n * sample_bytes / us / 1e3))
     assert store.status() == 0
     store.close()
 
@@ -81,17 +96,19 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--games", type=int, default=2000)
     ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--aux", action="store_true", help="also time the kernels that write the auxiliary targets")
     ap.add_argument("--stage", choices=["generate", "kernel"], help=argparse.SUPPRESS)
     ap.add_argument("--path", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.stage == "generate":
-        return generate(args.path, args.games)
+        return generate(args.path, args.games, args.aux)
     if args.stage == "kernel":
-        return kernel_times(args.path)
+        return kernel_times(args.path, args.aux)
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "games.json")
         me = [sys.executable, os.path.abspath(__file__)]
-        subprocess.run(me + ["--stage", "generate", "--path", path, "--games", str(args.games)], check=True, cwd=ROOT, timeout=600)
+        subprocess.run(me + ["--stage", "generate", "--path", path, "--games", str(args.games)] + (["--aux"] if args.aux else []),
+                       check=True, cwd=ROOT, timeout=600)
         with open(path) as f:
             plies = [len(json.loads(line)["moves"]) for line in f]
         print("%d self-play games (random 2x128 net, 32 visits), %d plies" % (len(plies), sum(plies)))
@@ -108,7 +125,8 @@ def main():
             print("train.py --steps %d %-17s: %6.1f s wall   (last log line: %s)" % (args.steps, " ".join(flags) or "(host pipeline)",
                                                                                    wall, last.strip()))
             sys.stdout.flush()
-        subprocess.run(me + ["--stage", "kernel", "--path", path], check=True, cwd=ROOT, timeout=600)
+        subprocess.run(me + ["--stage", "kernel", "--path", path] + (["--aux"] if args.aux else []), check=True, cwd=ROOT,
+                       timeout=600)
     return 0
 
 

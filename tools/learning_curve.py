@@ -100,16 +100,17 @@ def train(args, n, out):
     low = min(n, max(args.training_window_exclude + 1, n - args.training_window + 1))
     paths = [games_path(args.prefix, i) for i in range(low, n + 1)]
     cmd = [sys.executable, os.path.join(ROOT, "train.py"), "--steps", str(args.training_steps), "--games"] + paths + [
-        "--old-path", model_path(args.prefix, n), "--new-path", model_path(args.prefix, n + 1)]
+        "--old-path", model_path(args.prefix, n), "--new-path", model_path(args.prefix, n + 1)] + args.train_flags
     t0 = time.time()
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
     if res.returncode != 0:
         log(out, "training %d -> %d failed:\n%s\n%s" % (n, n + 1, res.stdout[-3000:], res.stderr[-3000:]))
         raise SystemExit(2)
-    losses = re.findall(r"^Step: +(\d+) -- loss: ([0-9.]+) +\(policy: ([0-9.]+) +value: ([0-9.]+)\)", res.stdout, re.M)
+    losses = re.findall(r"^Step: +(\d+) -- loss: ([0-9.]+) +\(policy: ([0-9.]+) +value: ([0-9.]+)"
+                        r"(?: +own: ([0-9.]+) +score: ([0-9.]+) +reply: ([0-9.]+))?\)", res.stdout, re.M)
     return {"games_files": [os.path.basename(p) for p in paths], "seconds": round(time.time() - t0, 1),
-            "val_loss_first": [float(x) for x in losses[0][1:]] if losses else None,
-            "val_loss_last": [float(x) for x in losses[-1][1:]] if losses else None}
+            "val_loss_first": [float(x) for x in losses[0][1:] if x] if losses else None,      # (with --aux-*: own, score, reply behind)
+            "val_loss_last": [float(x) for x in losses[-1][1:] if x] if losses else None}
 
 
 def arena(args, k, out, other=1):
@@ -203,8 +204,13 @@ def main():
                          "and checks then cover the generations that were completed")
     ap.add_argument("--generator-flags", type=str, default="--buffer-size 1024",
                     help="extension flags appended to the generator command (one string)")
+    ap.add_argument("--train-flags", type=str, default="",
+                    help="extension flags appended to every train.py command (one string), e.g. \"--aux-ownership 1.5 --aux-score "
+                         "0.5 --aux-reply 0.15\"; the auxiliary targets find a game's owners from its line alone, so games on a "
+                         "board with walls must say so: give --start-fen, which records them")
     args = ap.parse_args()
     args.generator_flags = args.generator_flags.split()
+    args.train_flags = args.train_flags.split()
     from ataxxzero_amd import model
 
     os.makedirs(os.path.join(args.prefix, "models"), exist_ok=True)

@@ -14,6 +14,10 @@ a share L of each game's sampling mass in proportion to it, the rest uniformly (
 Entries written with the generator's --record-blockers carry "blockers", the wall cells of their board: every path then shows
 them to the net in feature plane 3, and the surprise is measured over the moves the walls leave (no flag; without the key
 nothing changes).
+--aux-ownership, --aux-score and --aux-reply add auxiliary training targets (an extension): heads that exist only while training
+predict who owns each cell at the game's end, the final margin in stones and the opponent's answer, from what the game lines
+already hold; their weights go to NEW-PATH.aux.npz and the .npy file is what it always was.  All three 0 (the default):
+nothing changes.
 """
 from ataxxzero_amd import training
 from ataxxzero_amd.cli import flag, parse, switch
@@ -40,6 +44,15 @@ OPTIONS = [
          metavar="L"),
     flag("--surprise-dtype", "tower precision of the surprise pass", default="bf16", choices=["f32", "bf16", "f16"],
          metavar="DTYPE"),
+    flag("--aux-ownership", "weight A of the ownership loss: a head that exists only while training predicts, per cell, who owns "
+                            "it at the game's end (games the rules adjudicate; extension, on every sample path; 0: off).  "
+                            "KataGo weighs ownership 1.5 and the opponent's policy 0.15: a starting point, no value has been "
+                            "tuned for Ataxx", type=float, default=0.0, metavar="A"),
+    flag("--aux-score", "weight A of the score loss: the same head's prediction of the final margin in units of 49 stones "
+                        "(extension; 0: off; not tuned for Ataxx)", type=float, default=0.0, metavar="A"),
+    flag("--aux-reply", "weight A of the reply loss: a second training-only head predicts the policy target of the next ply, "
+                        "the opponent's answer (extension; 0: off; KataGo: 0.15; not tuned for Ataxx)", type=float, default=0.0,
+         metavar="A"),
 ]
 
 if __name__ == "__main__":
@@ -53,7 +66,13 @@ if __name__ == "__main__":
         args.device_draws = True
     else:                                   # off: the run, and the line below, are those of a train.py without the flags
         del args.surprise_weight, args.surprise_dtype
+    aux = {"aux_ownership": args.aux_ownership, "aux_score": args.aux_score, "aux_reply": args.aux_reply}
+    if min(aux.values()) < 0.0:
+        raise SystemExit("train.py: --aux-ownership, --aux-score and --aux-reply take weights >= 0")
+    if not any(aux.values()):               # off: as above
+        del args.aux_ownership, args.aux_score, args.aux_reply
+        aux = {}
     print("Arguments:", args)
     training.train(args.games, args.old_path, args.new_path, steps=args.steps, minibatch_size=args.minibatch_size,
                    learning_rate=args.learning_rate, reference_bn_affine=args.reference_bn_affine, value_blend=args.value_blend,
-                   device_samples=args.device_samples or args.device_draws, device_draws=args.device_draws, **surprise)
+                   device_samples=args.device_samples or args.device_draws, device_draws=args.device_draws, **surprise, **aux)
