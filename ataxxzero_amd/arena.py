@@ -55,7 +55,9 @@ def uai_move(mv):
 
 class Match:
     def __init__(self, weights_a, weights_b, visits, games=1024, dtype="f16", seed=selfplay.DEFAULT_SEED,
-                 max_plies=400, opening_depth=0, start_fen=selfplay.START_FEN_PLAIN):
+                 max_plies=400, opening_depth=0, start_fen=selfplay.START_FEN_PLAIN, start_fens=None):
+        """start_fens: a pool of start positions (link.Engine.set_start_pool with stride 2) in place of start_fen: pairing k
+        — the games with uids 2k and 2k + 1 — plays map k % n both ways, and its random opening is played on that map."""
         if games % 2:
             raise ValueError("the number of concurrent games must be even (each pairing is played both ways)")
         if not 0 <= opening_depth < max_plies:
@@ -63,6 +65,8 @@ class Match:
         self.net_a = link.Net(*weights_a, model.BN_EPSILON)
         self.net_b = link.Net(*weights_b, model.BN_EPSILON)
         self.dtype = link.DTYPES[dtype]
+        if start_fens:
+            start_fen = start_fens[0]     # (the engine's own start: the start of no game while the pool is set)
         cfg = selfplay.make_config(games, visits, seed=seed, fen=start_fen, max_plies=max_plies,
                                    dirichlet_weight=0.0, flags=link.FLAG_ARENA)
         self.engine = link.Engine(cfg)
@@ -73,12 +77,23 @@ class Match:
         self.limit = None        # set_game_limit: the size of the match
         self.finished = 0        # games of the match handed out so far (under a limit: those with uid < limit)
         self.thin = False        # the tower runs one board per workgroup (the match's last games)
+        self.start_fens = list(start_fens) if start_fens else None
+        if self.start_fens:
+            self.engine.set_start_pool(self.start_fens, stride=2)
         if opening_depth > 0:
             # every pairing gets its own random opening, played both ways (uai_ringmaster.py:242-246): slots 2k and 2k + 1
             # start from the same position.  Only the FIRST game of a slot starts from it (uid < games): a match from
             # openings is a cohort of at most `games` games.
             import numpy as np
-            boards, self.openings = random_openings(games // 2, opening_depth, seed, start_fen)
+            if self.start_fens:
+                # pairing k's opening on its own map k % n: one batch of openings per map, dealt out in pairing order
+                n = len(self.start_fens)
+                per_map = [random_openings(len(range(m, games // 2, n)), opening_depth, seed + 7919 * m, fen)
+                           if m < games // 2 else (None, []) for m, fen in enumerate(self.start_fens)]
+                boards = np.array([per_map[k % n][0][k // n] for k in range(games // 2)], dtype=np.uint64)
+                self.openings = [per_map[k % n][1][k // n] for k in range(games // 2)]
+            else:
+                boards, self.openings = random_openings(games // 2, opening_depth, seed, start_fen)
             self.opening_boards = boards
             self.engine.set_positions(np.repeat(boards, 2, axis=0), np.full(games, opening_depth, dtype=np.int32))
 

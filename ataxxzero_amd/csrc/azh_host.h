@@ -38,16 +38,17 @@ uint64_t azh_ply_target(azh::PlyView ply, std::vector<std::pair<std::string, uin
 int azh_net_launch(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
                    const int *d_count, int max_n, unsigned long long blockers, float *d_logits,
                    float *d_values, hipStream_t stream, unsigned long long *d_stamps = nullptr, int thin = 0,
-                   const void *advance_hook = nullptr);
+                   const void *advance_hook = nullptr, const unsigned long long *d_masks = nullptr);
+// d_masks (all three launches): null — every board stands on `blockers` — or the wall mask of every board, indexed as d_boards
 // advance_hook (all three launches): an azh::AdvanceHook (engine_device.h) or null — the device-resident search loop's queued
 // moves are played by the first `workers` workgroups of the launch
 // symmetry-averaged evaluation (nn_evals.py:48-62); scratch: [8 max_n][833] and [8 max_n] floats
 int azh_net_launch_sym(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
                        const int *d_count, int max_n, unsigned long long blockers, float *d_tmp_logits,
                        float *d_tmp_values, float *d_logits, float *d_values, hipStream_t stream, int thin = 0,
-                       const void *advance_hook = nullptr);
+                       const void *advance_hook = nullptr, const unsigned long long *d_masks = nullptr);
 // two nets, two dense leaf lists, one launch (arena); 1 = not applicable here, nothing launched (launch them one by one)
 int azh_net_launch_pair(azh_net *net_a, azh_net *net_b, int dtype, const unsigned long long *d_boards, const int *d_list_a,
                         const int *d_count_a, const int *d_list_b, const int *d_count_b, int max_n,
                         unsigned long long blockers, float *d_logits, float *d_values, hipStream_t stream, int thin = 0,
-                        const void *advance_hook = nullptr);
+                        const void *advance_hook = nullptr, const unsigned long long *d_masks = nullptr);

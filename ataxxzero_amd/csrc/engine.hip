@@ -80,7 +80,9 @@ __global__ __launch_bounds__(WAVE) void k_init_positions(EngineParams P, const u
     const int g = blockIdx.x;
     azh_game_state s;
     const ulonglong2 w = boards[g];
-    init_game_at(P, g, (u32)g, s, s_moves, unpack_board(w.x, w.y), plies[g], 1);
+    // (under a start pool the slot plays on the walls of the uid it gets, its slot number)
+    const u64 walls = P.pool ? P.pool[start_pool_entry((u32)g, P.pool_n, P.pool_stride)].blockers : P.blockers;
+    init_game_at(P, g, (u32)g, s, s_moves, unpack_board(w.x, w.y), plies[g], 1, walls);
     if (P.uid_limit != 0u && (u32)g >= P.uid_limit)
         s.phase = 3;
     if (threadIdx.x == 0)
@@ -111,6 +113,17 @@ __global__ __launch_bounds__(WAVE) void k_limit_slots(EngineParams P)
         if (threadIdx.x == 0)
             P.gs[g].phase = 3;
     }
+}
+
+// azh_engine_set_start_pool (before the first select): every slot starts its game again, from the entry of its uid
+__global__ __launch_bounds__(WAVE) void k_restart(EngineParams P)
+{
+    __shared__ u16 s_moves[MAX_MOVES];
+    const int g = blockIdx.x;
+    azh_game_state s = P.gs[g];
+    init_game(P, g, s.uid, s, s_moves);
+    if (threadIdx.x == 0)
+        P.gs[g] = s;
 }
 
 __global__ __launch_bounds__(WAVE) void k_init(EngineParams P)
@@ -170,7 +183,9 @@ __device__ inline float puct_score(float prior, float W, u32 n, float sq, float 
 // `s` is the game's state, held in registers by the caller (the same values in all 64 lanes); written back here.
 // Returns what the leaf needs: 0 nothing, 1 an evaluation (by net A), 2 an evaluation by net B (arena).  `pk`: the ply's kind
 // word (forced playouts act on the plies whose root got the noise).
-template <bool STAMP = false>
+// POOL: the instantiation for an engine with a start pool (azh_engine_set_start_pool) — the expansion generates moves on the
+// slot's own walls and the leaf's mask is written beside its board.  Without it no instruction of the kernel knows of the pool.
+template <bool STAMP = false, bool POOL = false>
 __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &s, u16 *s_moves, u32 pk, u64 *st = nullptr)
 {
     const int lane = lane_id();
@@ -613,7 +628,7 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
             const ulonglong2 pw = A.nb[node];
             const Board cb = make_move(unpack_board(pw.x, pw.y), (int)(mv & 0xFF), (int)(mv >> 8));
             int res2;
-            const int M2 = wave_movegen(cb, P.blockers, s_moves, &res2);
+            const int M2 = wave_movegen(cb, POOL ? P.slot_mask[g] : P.blockers, s_moves, &res2);
             wave_sync();
             if (s.n_nodes >= P.node_cap || (res2 == 0 && (s.n_edges + M2 > P.edge_cap || M2 > 255))) {
                 over = 1;
@@ -695,6 +710,8 @@ __device__ inline int select_game(const EngineParams &P, int g, azh_game_state &
         P.gs[g] = s;
         P.need_eval[g] = need;
         P.leaf_board[g] = make_ulonglong2(leaf_mover, leaf_opp);
+        if constexpr (POOL)
+            P.leaf_mask[g] = P.slot_mask[g];
         if (over)
             P.force[g] = 1;
     }
@@ -1230,7 +1247,7 @@ __device__ inline int last_tree_workgroup(const EngineParams &P, u32 seen)
 // the next select, with the game's state in registers throughout; TREE_WAVES games share a workgroup (each wave on
 // its own: wave_sync, never a workgroup barrier, inside a game), and the last workgroup to finish compacts the leaf
 // list.  mode bit 0: backup + mark, bit 1: select (+ compaction).
-template <bool STAMP, int TREE_WAVES>
+template <bool STAMP, int TREE_WAVES, bool POOL = false>
 __global__ __launch_bounds__(TREE_WAVES * WAVE) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_tree(EngineParams P, int mode, int two)
 {
     __shared__ u16 s_moves[TREE_WAVES][MAX_MOVES];  // per game: the move list of the node being expanded
@@ -1258,7 +1275,7 @@ __global__ __launch_bounds__(TREE_WAVES * WAVE) __attribute__((amdgpu_waves_per_
             if (!(mode & 1)) st[2] = st[3];
         }
         if (mode & 2)
-            need = select_game<STAMP>(P, g, s, s_moves[w], pk, st);  // stores the state
+            need = select_game<STAMP, POOL>(P, g, s, s_moves[w], pk, st);  // stores the state
         else if (lane_id() == 0)
             P.gs[g] = s;
     }
@@ -1301,14 +1318,18 @@ __global__ __launch_bounds__(TREE_WAVES * WAVE) __attribute__((amdgpu_waves_per_
 }
 
 // Reference feature rows for the dense leaf list (cpp/self_play_client.cpp:174-202).
-__global__ void k_features(const ulonglong2 *boards, const int *list, int n, u64 blockers, float *out)
+// masks: null, or the wall mask of every board (indexed as boards) in place of `blockers`
+__global__ void k_features(const ulonglong2 *boards, const int *list, int n, u64 blockers, const u64 *masks, float *out)
 {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n * 49)
         return;
     const int row = idx / 49, c = idx % 49;
     const int x = c / 7, y = c % 7, sq = x + 7 * (6 - y);
-    const ulonglong2 b = boards[list ? list[row] : row];
+    const int game = list ? list[row] : row;
+    const ulonglong2 b = boards[game];
+    if (masks)
+        blockers = masks[game];
     float4 f;
     f.x = 1.0f;
     f.y = (float)((b.x >> sq) & 1ULL);
@@ -1347,17 +1368,18 @@ using namespace azh;
 // leaf-parallel search, and P points at one of them.
 struct LeafBuffers {
     ulonglong2 *leaf_board = nullptr;
+    u64 *leaf_mask = nullptr;
     int *need_eval = nullptr, *leaf_list = nullptr, mask_words = 0;
     u32 *need_mask = nullptr;
     float *logits = nullptr, *values = nullptr;
     void read(const EngineParams &P)
     {
-        leaf_board = P.leaf_board; need_eval = P.need_eval; leaf_list = P.leaf_list;
+        leaf_board = P.leaf_board; leaf_mask = P.leaf_mask; need_eval = P.need_eval; leaf_list = P.leaf_list;
         need_mask = P.need_mask; mask_words = P.mask_words; logits = P.logits; values = P.values;
     }
     void write(EngineParams &P) const
     {
-        P.leaf_board = leaf_board; P.need_eval = need_eval; P.leaf_list = leaf_list;
+        P.leaf_board = leaf_board; P.leaf_mask = leaf_mask; P.need_eval = need_eval; P.leaf_list = leaf_list;
         P.need_mask = need_mask; P.mask_words = mask_words; P.logits = logits; P.values = values;
     }
 };
@@ -1414,6 +1436,10 @@ struct azh_engine {
     size_t h_stage_words = 0;
     std::vector<u32 *> h_stage_retired;
     bool selected = false;
+    bool begun = false;  // a tree launch has been enqueued (the first select): the start position, pool included, is settled
+    StartEntry *d_pool = nullptr;        // azh_engine_set_start_pool: the entries on the device (pool_cap of them) and on the host
+    size_t pool_cap = 0;
+    std::vector<StartEntry> pool;
     bool arena_lists = false;  // run_arena: one leaf list per net
     bool stamp_next = false;   // azh_engine_tree_stamps: the next fused tree launch of the loop is the stamped instantiation
     int thin_mode = -1;        // azh_engine_set_thin_batches: 0 the 3-board tower, 1 one board per workgroup, -1 by the engine's size
@@ -1434,6 +1460,15 @@ struct azh_engine {
 static int leaf_k(const azh_engine *e) { return e->V.K > 1 ? e->V.K : 1; }
 
 // the tower for this engine's leaf batches: one board per workgroup for engines (or batches the host says are) small
+// the wall mask of every leaf slot, for the tower and k_features: null (the engine's one mask) while no pool is set
+static const unsigned long long *leaf_masks(const azh_engine *e) { return e->P.pool ? (const unsigned long long *)e->P.leaf_mask : nullptr; }
+
+// the walls game `uid` is played on
+static u64 uid_blockers(const azh_engine *e, u32 uid)
+{
+    return e->pool.empty() ? e->P.blockers : e->pool[start_pool_entry(uid, (u32)e->pool.size(), e->P.pool_stride)].blockers;
+}
+
 static int thin_batches(const azh_engine *e)
 {
     return e->thin_mode >= 0 ? e->thin_mode : (e->P.G * leaf_k(e) <= AZH_THIN_MAX_GAMES ? 1 : 0);  // (by slots: G K)
@@ -1511,6 +1546,22 @@ static const struct { u32 bit; const char *name; } FLAG_NAMES[] = {
 };
 #undef NAMED
 
+// The random symmetry's cause against the masks games are played on — the pool's entries, or `blockers` where there is none:
+// empty if every one is its own image under the 8 symmetries, else the refusal's words with the first mask that is not.
+static std::string asymmetric_mask(const StartEntry *pool, size_t n, u64 blockers)
+{
+    for (size_t i = 0; i < (pool ? n : 1); i++) {
+        const u64 bb = pool ? pool[i].blockers : blockers;
+        if (symmetry_invariant(bb & BOARD_MASK))
+            continue;
+        char mask[32];
+        snprintf(mask, sizeof(mask), "0x%llx", (unsigned long long)bb);
+        return std::string("a blockers mask (") + mask + ") that is not its own image under all 8 symmetries (the tower takes one "
+               "blocker plane per launch)";
+    }
+    return "";
+}
+
 // May `mode` come on in this engine now?  Empty: yes; else why not, as the refusal reads after "<setter>: ".  The flags are looked
 // at first, then what else a mode requires of the engine's configuration, then the modes that are on.
 static std::string mode_refusal(const azh_engine *e, int mode)
@@ -1520,16 +1571,16 @@ static std::string mode_refusal(const azh_engine *e, int mode)
     for (const auto &f : FLAG_NAMES)
         if (e->P.flags & m.refused_flags & f.bit)
             return head + f.name;
-    char mask[32];
-    snprintf(mask, sizeof(mask), "0x%llx", (unsigned long long)e->P.blockers);
     if ((mode == MODE_LEAF_BATCH || mode == MODE_SOLVER) && e->P.select_budget > 0)
         return head + "select_budget > 0";
     if (mode == MODE_GUMBEL && (!(e->P.flags & AZH_FLAG_NO_REUSE) || e->P.noise_w != 0.0f))
         return "the engine must have been created with AZH_FLAG_NO_REUSE and dirichlet_weight 0 (the schedule assumes a fresh "
                "root, and its noise is the Gumbel)";
-    if (mode == MODE_SYMMETRY && !symmetry_invariant(e->P.blockers & BOARD_MASK))
-        return head + "a blockers mask (" + mask + ") that is not its own image under all 8 symmetries (the tower takes one "
-                      "blocker plane per launch)";
+    if (mode == MODE_SYMMETRY) {
+        const std::string why = asymmetric_mask(e->pool.empty() ? nullptr : e->pool.data(), e->pool.size(), e->P.blockers);
+        if (!why.empty())
+            return head + why;
+    }
     for (const auto &pair : EXCLUDED) {
         const int other = pair[0] == mode ? pair[1] : pair[1] == mode ? pair[0] : MODE_NONE;
         if (other != MODE_NONE && MODES[other].on(e))
@@ -1609,6 +1660,8 @@ extern "C" int azh_engine_create(const azh_config *cfg, azh_engine **out)
     rc |= dev_alloc(e, &P.edge, 2 * G * P.edge_cap);
     rc |= dev_alloc(e, &P.edge_move, 2 * G * P.edge_cap);
     rc |= dev_alloc(e, &P.leaf_board, G);
+    rc |= dev_alloc(e, &P.leaf_mask, G);
+    rc |= dev_alloc(e, &P.slot_mask, G);
     rc |= dev_alloc(e, &P.need_eval, G);
     rc |= dev_alloc(e, &P.leaf_list, G);
     rc |= dev_alloc(e, &P.leaf_count, 1);
@@ -1697,19 +1750,29 @@ static int two_lists(const azh_engine *e) { return (e->P.flags & AZH_FLAG_TWO_NE
 static int enqueue_tree(azh_engine *e, int mode, bool stamped = false)
 {
     const int two = two_lists(e);
+    e->begun = true;
     const bool small = e->P.G <= TREE_ONE_ROUND_GAMES;
     const int waves = small ? TREE_WAVES_SMALL : TREE_WAVES_LARGE;
     const dim3 grid((e->P.G + waves - 1) / waves), block(waves * WAVE);
+    const bool pool = e->P.pool != nullptr;  // (the instantiations that know of the start pool)
+#define TREE_LAUNCH(STAMP, WAVES)                                                                                              \
+    do {                                                                                                                       \
+        if (pool)                                                                                                              \
+            hipExtLaunchKernelGGL((k_tree<STAMP, WAVES, true>), grid, block, 0, e->stream, nullptr, nullptr, 0, e->P, mode, two); \
+        else                                                                                                                   \
+            hipExtLaunchKernelGGL((k_tree<STAMP, WAVES>), grid, block, 0, e->stream, nullptr, nullptr, 0, e->P, mode, two);    \
+    } while (0)
     if (e->vl_active)  // leaf-parallel search: one workgroup per game (not stamped: azh_engine_tree_stamps refuses)
         hipExtLaunchKernelGGL(k_vl_tree, dim3(e->P.G), dim3(VL_WAVES * WAVE), 0, e->stream, nullptr, nullptr, 0, e->P, e->V, mode);
     else if (stamped && small)
-        hipExtLaunchKernelGGL((k_tree<true, TREE_WAVES_SMALL>), grid, block, 0, e->stream, nullptr, nullptr, 0, e->P, mode, two);
+        TREE_LAUNCH(true, TREE_WAVES_SMALL);
     else if (stamped)
-        hipExtLaunchKernelGGL((k_tree<true, TREE_WAVES_LARGE>), grid, block, 0, e->stream, nullptr, nullptr, 0, e->P, mode, two);
+        TREE_LAUNCH(true, TREE_WAVES_LARGE);
     else if (small)
-        hipExtLaunchKernelGGL((k_tree<false, TREE_WAVES_SMALL>), grid, block, 0, e->stream, nullptr, nullptr, 0, e->P, mode, two);
+        TREE_LAUNCH(false, TREE_WAVES_SMALL);
     else
-        hipExtLaunchKernelGGL((k_tree<false, TREE_WAVES_LARGE>), grid, block, 0, e->stream, nullptr, nullptr, 0, e->P, mode, two);
+        TREE_LAUNCH(false, TREE_WAVES_LARGE);
+#undef TREE_LAUNCH
     AZH_HIP(hipGetLastError());
     return 0;
 }
@@ -1762,7 +1825,8 @@ extern "C" int azh_engine_leaf_features(azh_engine *e, float *out, int32_t *game
         return 0;
     AZH_TRY(dev_alloc_once(e, &e->d_feat, (size_t)e->P.G * AZH_FEATURE_SIZE));
     hipLaunchKernelGGL(k_features, dim3((n * 49 + 255) / 256), dim3(256), 0, e->stream,
-                       (const ulonglong2 *)e->P.leaf_board, (const int *)e->P.leaf_list, n, e->P.blockers, e->d_feat);
+                       (const ulonglong2 *)e->P.leaf_board, (const int *)e->P.leaf_list, n, e->P.blockers,
+                       (const u64 *)leaf_masks(e), e->d_feat);
     AZH_HIP(hipGetLastError());
     AZH_HIP(hipStreamSynchronize(e->stream));
     AZH_HIP(hipMemcpy(out, e->d_feat, (size_t)n * AZH_FEATURE_SIZE * 4, hipMemcpyDeviceToHost));
@@ -1776,13 +1840,13 @@ static int launch_eval(azh_engine *e, azh_net *net, int dtype, const int *list, 
 {
     if (!(e->P.flags & AZH_FLAG_SYMMETRY_AVG))
         return azh_net_launch(net, dtype, (const unsigned long long *)e->P.leaf_board, list, count, e->P.G * leaf_k(e),
-                              e->P.blockers, e->P.logits, e->P.values, e->stream, nullptr, thin_batches(e), hook);
+                              e->P.blockers, e->P.logits, e->P.values, e->stream, nullptr, thin_batches(e), hook, leaf_masks(e));
     AZH_TRY(dev_alloc_once(e, &e->d_sym_logits, (size_t)e->P.G * 8 * AZH_POLICY_SIZE));
     AZH_TRY(dev_alloc_once(e, &e->d_sym_values, (size_t)e->P.G * 8));
     return azh_net_launch_sym(net, dtype, (const unsigned long long *)e->P.leaf_board, list, count, e->P.G,
                               e->P.blockers, e->d_sym_logits, e->d_sym_values, e->P.logits, e->P.values, e->stream,
                               e->thin_mode >= 0 ? e->thin_mode : (e->P.G * 8 <= AZH_THIN_MAX_GAMES ? 1 : 0),  // (8 virtual boards per leaf)
-                              hook);
+                              hook, leaf_masks(e));
 }
 
 extern "C" int azh_engine_eval(azh_engine *e, azh_net *net, int dtype)
@@ -1880,7 +1944,7 @@ struct RunLoop {
         if (net_b && pair)  // both nets' leaf lists in ONE tower launch (1: not applicable -> one after the other)
             rc = azh_net_launch_pair(net_a, net_b, dtype, (const unsigned long long *)e->P.leaf_board, e->P.leaf_list,
                                      e->P.leaf_count, e->P.leaf_list2, e->P.leaf_count2, e->P.G, e->P.blockers, e->P.logits,
-                                     e->P.values, e->stream, thin_batches(e), moves);
+                                     e->P.values, e->stream, thin_batches(e), moves, leaf_masks(e));
         if (rc == 1) {
             rc = launch_eval(e, net_a, dtype, e->P.leaf_list, e->P.leaf_count, moves);   // (the first launch plays the moves)
             if (rc == 0 && net_b)
@@ -2006,6 +2070,7 @@ static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, b
         rc |= dev_alloc(e, &e->V.path_len, n);
         rc |= dev_alloc(e, &e->V.path, n * (size_t)P.path_cap);
         rc |= dev_alloc(e, &b.leaf_board, n);
+        rc |= dev_alloc(e, &b.leaf_mask, n);
         rc |= dev_alloc(e, &b.need_eval, n);
         rc |= dev_alloc(e, &b.leaf_list, n);
         rc |= dev_alloc(e, &b.need_mask, 2 * (size_t)b.mask_words);
@@ -2453,6 +2518,85 @@ extern "C" int azh_engine_set_emit_order(azh_engine *e, int by_uid)
     return 0;
 }
 
+// A start position and wall map per game: the header.  Validation first, then the change: a refused call leaves the engine as it was.
+extern "C" int azh_start_pool_entry(uint32_t uid, int n, int stride)
+{
+    if (n < 1 || stride < 1)
+        return azh_fail(-1, "azh_start_pool_entry: need n >= 1 and stride >= 1");
+    return (int)start_pool_entry(uid, (u32)n, (u32)stride);
+}
+
+extern "C" int azh_engine_uid_blockers(const azh_engine *e, uint32_t uid, uint64_t *out)
+{
+    if (!e || !out)
+        return azh_fail(-1, "azh_engine_uid_blockers: null argument");
+    *out = uid_blockers(e, uid) & BOARD_MASK;
+    return 0;
+}
+
+extern "C" int azh_engine_set_start_pool(azh_engine *e, int n, const uint64_t *x, const uint64_t *o, const uint64_t *blockers,
+                                         const int32_t *turn, int stride)
+{
+    const char *who = "azh_engine_set_start_pool";
+    if (!e || (n > 0 && (!x || !o || !blockers || !turn)))
+        return azh_fail(-1, "%s: null argument", who);
+    if (n < 0 || n > AZH_START_POOL_MAX || (n > 0 && stride < 1))
+        return azh_fail(-2, "%s: need 0 <= n <= %d and stride >= 1 (n %d, stride %d)", who, AZH_START_POOL_MAX, n, stride);
+    std::vector<StartEntry> pool((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const u64 bx = x[i], bo = o[i], bl = blockers[i];
+        const char *why = nullptr;
+        if ((bx | bo | bl) & ~BOARD_MASK)
+            why = "bits beyond the 49 cells";
+        else if (bx & bo)
+            why = "a cell holds stones of both sides";
+        else if ((bx | bo) & bl)
+            why = "a stone stands on a wall";
+        else if (!bx || !bo)
+            why = "a side has no stone";
+        else if (turn[i] != 0 && turn[i] != 1)
+            why = "the side to move is neither 0 (x) nor 1 (o)";
+        else {
+            // (get_board_result: the board is full, or the side to move cannot move and the empty cells go to the other)
+            const u64 empty = BOARD_MASK & ~(bx | bo | bl), own = turn[i] ? bo : bx;
+            if (!((single_jump_bb(own) | double_jump_bb(own)) & empty))
+                why = "the position is finished (the side to move has no move)";
+        }
+        if (why)
+            return azh_fail(-2, "%s: entry %d (x %#llx, o %#llx, blockers %#llx, turn %d): %s", who, i, (unsigned long long)bx,
+                            (unsigned long long)bo, (unsigned long long)bl, (int)turn[i], why);
+        pool[(size_t)i] = StartEntry{bx, bo, bl, (int)turn[i], 0};
+    }
+    if (e->selected)
+        return azh_fail(-3, "%s: a selected batch awaits its backup", who);
+    if (e->begun)
+        return azh_fail(-4, "%s: the engine has begun to search (the pool, like the start position it replaces, is set before "
+                            "the first select)", who);
+    if (n > 0 && e->P.random_symmetry != 0u) {
+        const std::string why = asymmetric_mask(pool.data(), pool.size(), 0ULL);
+        if (!why.empty())
+            return azh_fail(-4, "%s: the random symmetry is not supported with %s", who, why.c_str());
+    }
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    if ((size_t)n > e->pool_cap) {
+        StartEntry *d = nullptr;
+        AZH_TRY(dev_alloc(e, &d, (size_t)n));
+        e->d_pool = d;
+        e->pool_cap = (size_t)n;
+    }
+    if (n > 0)
+        AZH_HIP(hipMemcpy(e->d_pool, pool.data(), (size_t)n * sizeof(StartEntry), hipMemcpyHostToDevice));
+    e->pool.swap(pool);
+    e->P.pool = n > 0 ? e->d_pool : nullptr;
+    e->P.pool_n = (u32)n;
+    e->P.pool_stride = n > 0 ? (u32)stride : 0u;
+    // every slot starts again: the game of its uid from its entry (n = 0: from the configured start position)
+    hipLaunchKernelGGL(k_restart, dim3(e->P.G), dim3(WAVE), 0, e->stream, e->P);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
 // Every slot restarts at a given position: boards [G][2] packed (x | turn << 63, o), plies [G] (the ply the position is at;
 // < max_plies).  Fresh trees, uids = slot numbers.  Games started this way are played and counted like any other, but
 // their records would lack the plies before the start, so they are not written (the slot's NEXT game is a normal one).
@@ -2477,7 +2621,7 @@ extern "C" int azh_engine_set_positions(azh_engine *e, const uint64_t *boards, c
     AZH_HIP(hipMemsetAsync(e->P.ring_head, 0, 8, e->stream));
     for (size_t g = 0; g < G; g++) {
         const uint64_t x = boards[2 * g] & ~TURN_BIT, o = boards[2 * g + 1];
-        if (plies[g] < 0 || plies[g] >= e->P.max_plies || (x & o) || ((x | o) & (e->P.blockers | ~BOARD_MASK)) || !x || !o)
+        if (plies[g] < 0 || plies[g] >= e->P.max_plies || (x & o) || ((x | o) & (uid_blockers(e, (u32)g) | ~BOARD_MASK)) || !x || !o)
             return azh_fail(-2, "azh_engine_set_positions: slot %zu: bad position or ply %d", g, plies[g]);
     }
     ulonglong2 *d_b = nullptr;
@@ -2769,7 +2913,7 @@ static void format_staged(azh_engine *e)
     for (auto &o : order) {
         const RecordView rec{host.data() + o.second};
         std::string line = rec.dropped()        ? std::string()
-                           : e->record_blockers ? azh_format_game_json_blockers(rec.w, ids, e->P.blockers & BOARD_MASK)
+                           : e->record_blockers ? azh_format_game_json_blockers(rec.w, ids, uid_blockers(e, rec.uid()) & BOARD_MASK)
                                                 : azh_format_game_json(rec.w, ids);
         if (rec.loaded() && !ids)
             line.clear();  // a game that began at a loaded position: record drained and formatted like any other

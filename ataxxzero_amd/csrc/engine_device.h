@@ -19,6 +19,12 @@ constexpr int REC_STRIDE_WORDS = REC_HDR_WORDS + REC_MAXD;  // a ply as it waits
 constexpr int NSTAT = AZH_STAT_COUNT;
 constexpr int BFS_QL = 384;  // re-root frontier entries kept in LDS; later ones spill to bfs_spill in HBM
 
+// One start position of the pool: stones, walls, side to move (0: x).
+struct StartEntry {
+    u64 x, o, blockers;
+    int turn, pad;
+};
+
 struct EngineParams {
     int G, visits, node_cap, edge_cap, path_cap, max_plies;
     float c_puct, alpha, noise_w;
@@ -94,7 +100,16 @@ struct EngineParams {
     const u16 *gumbel_seq;      // [gumbel_m][visits] row r - 1: the considered visit counts for r actions at the current `visits`
     float *gumbel_a;            // [G][MAX_MOVES] a_j = g_j + l_j of every root edge, written by the root's backup
     float *gumbel_v0;           // [G] the root's own value as a [0, 1] score, written beside it
+    // a start position and wall map per game (azh_engine_set_start_pool; DESIGN.md "A start position per game"), off while null
+    const StartEntry *pool;     // [pool_n] game uid starts from entry (uid / pool_stride) % pool_n
+    u32 pool_n, pool_stride;
+    u64 *slot_mask;             // [G] the wall mask of each slot's current game, written where a game begins (init_game_at)
+    u64 *leaf_mask;             // [slots] beside leaf_board: the mask of the game that selected the slot's leaf, written by that
+                                // select — the tower reads it, never slot_mask (the launch's first workgroups restart games)
 };
+
+// The walls slot g's game is played on (g wave-uniform: one scalar 8-byte load); the engine's one mask while no pool is set.
+__device__ inline u64 game_blockers(const EngineParams &P, int g) { return P.pool ? P.slot_mask[g] : P.blockers; }
 
 constexpr u32 PLY_FULL = 0x80000000u;
 constexpr int NO_EMIT_LOADED = 1 << 30;        // no_emit: the game stands where azh_engine_set_positions put it (max_plies < 2^30)
@@ -256,12 +271,12 @@ __device__ inline void tt_clear(u32 *tt, int size)
 // key word of the random symmetry (begin_game_key) — every caller's but the tower kernels' advance_game, see there.
 template <bool KEY = true>
 __device__ inline void init_game_at(const EngineParams &P, int g, u32 uid, azh_game_state &s, u16 *s_moves, Board b, int ply,
-                                    int loaded)
+                                    int loaded, u64 walls)
 {
     const int lane = lane_id();
     Arena A = arena_of(P, 0, g);
     int res;
-    const int M = wave_movegen(b, P.blockers, s_moves, &res);
+    const int M = wave_movegen(b, walls, s_moves, &res);
     wave_sync();
     for (int j = lane; j < M; j += WAVE) {
         A.ed[j] = fresh_edge(0u);
@@ -272,6 +287,8 @@ __device__ inline void init_game_at(const EngineParams &P, int g, u32 uid, azh_g
         A.ni[0] = make_uint4(0u, (u32)M | ((u32)res << 16), 0u, 0u);
         P.force[g] = 0;
         P.no_emit[g] = loaded ? (ply + 1) | NO_EMIT_LOADED : 0;
+        if (P.pool)
+            P.slot_mask[g] = walls;
     }
     if (P.flags & AZH_FLAG_EVAL_CACHE)
         tt_clear(tt_of(P, 0, g), P.tt_size);
@@ -291,7 +308,10 @@ __device__ inline void init_game_at(const EngineParams &P, int g, u32 uid, azh_g
     s.uid = uid;
 }
 
-// Fresh game at the configured start position — or, past the game limit, no game: the slot goes idle.
+// The pool entry game `uid` starts from: round robin over the entries, `stride` consecutive uids sharing one (azh_start_pool_entry).
+__host__ __device__ inline u32 start_pool_entry(u32 uid, u32 n, u32 stride) { return (uid / stride) % n; }
+
+// Fresh game at the configured start position (the pool's entry of its uid where a pool is set) — or, past the game limit, no game: the slot goes idle.
 template <bool KEY = true>
 __device__ inline void init_game(const EngineParams &P, int g, u32 uid, azh_game_state &s, u16 *s_moves)
 {
@@ -311,7 +331,15 @@ __device__ inline void init_game(const EngineParams &P, int g, u32 uid, azh_game
     b.x = P.start_x;
     b.o = P.start_o;
     b.turn = P.start_turn;
-    init_game_at<KEY>(P, g, uid, s, s_moves, b, 0, 0);
+    u64 walls = P.blockers;
+    if (P.pool) {
+        const StartEntry &en = P.pool[start_pool_entry(uid, P.pool_n, P.pool_stride)];
+        b.x = en.x;
+        b.o = en.o;
+        b.turn = en.turn;
+        walls = en.blockers;
+    }
+    init_game_at<KEY>(P, g, uid, s, s_moves, b, 0, 0, walls);
 }
 
 constexpr u32 PRIOR_MASK = 0x7FFFFFFFu;  // the prior proper (bit 31 marks the remembered child)
@@ -351,7 +379,7 @@ __device__ inline int reroot_game(const EngineParams &P, int g, TreeLds &L, azh_
     if (c == ENONE) {
         // miss: fresh tree from the position after the move (:479-483)
         const Board nbrd = make_move(unpack_board(rootw.x, rootw.y), (int)(mv & 0xFF), (int)(mv >> 8));
-        const int Mn = wave_movegen(nbrd, P.blockers, s_moves, &result);
+        const int Mn = wave_movegen(nbrd, game_blockers(P, g), s_moves, &result);
         wave_sync();
         const int Mw = result != 0 ? 0 : Mn;
         for (int j = lane; j < Mw; j += WAVE) {

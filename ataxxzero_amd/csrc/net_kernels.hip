@@ -143,6 +143,7 @@ struct TowerArgs {
     const int *count;        // device count (or nullptr -> n)
     int n;
     unsigned long long blockers;
+    const unsigned long long *masks;  // null: every board stands on `blockers`; else the wall mask of every board, indexed as boards
     float *logits;           // [..][833], indexed by game
     float *values;           // [..], indexed by game
     unsigned long long *stamps;  // diagnostic build only: [workgroup][wave][128] s_memtime stamps
@@ -488,7 +489,8 @@ __global__ __launch_bounds__(64 * (FT / 32), WPS) void k_tower(TowerArgs A, Adva
         const unsigned long long mover = A.boards[2 * (size_t)game + 0];
         const unsigned long long opp = A.boards[2 * (size_t)game + 1];
         const float f1 = (float)((mover >> sq) & 1ULL), f2 = (float)((opp >> sq) & 1ULL);
-        const float f3 = (float)((A.blockers >> sq) & 1ULL);
+        const unsigned long long walls = A.masks ? A.masks[game] : A.blockers;
+        const float f3 = (float)((walls >> sq) & 1ULL);
         if constexpr (DT == AZH_DTYPE_F32) {
             *reinterpret_cast<float *>(smem + G::ch_off(G::real_slot(0, cell), 0)) = 1.0f;
             *reinterpret_cast<float *>(smem + G::ch_off(G::real_slot(0, cell), 1)) = f1;
@@ -1237,6 +1239,7 @@ __device__ __forceinline__ void tower2_run(const TowerArgs &A, unsigned char *sm
             const int game = tower_src(A, tile0 + bl, x, y, sq0);
             const unsigned long long mover = A.boards[2 * (size_t)game + 0];
             const unsigned long long opp = A.boards[2 * (size_t)game + 1];
+            const unsigned long long walls = A.masks ? A.masks[game] : A.blockers;
             typename Tr::afrag o;
 #pragma unroll
             for (int h = 0; h < 2; h++) {
@@ -1249,7 +1252,7 @@ __device__ __forceinline__ void tower2_run(const TowerArgs &A, unsigned char *sm
                 o[4 * h + 0] = (typename Tr::elem)(on ? 1.0f : 0.0f);
                 o[4 * h + 1] = (typename Tr::elem)(float)(on ? (mover >> sq) & 1ULL : 0ULL);
                 o[4 * h + 2] = (typename Tr::elem)(float)(on ? (opp >> sq) & 1ULL : 0ULL);
-                o[4 * h + 3] = (typename Tr::elem)(float)(on ? (A.blockers >> sq) & 1ULL : 0ULL);
+                o[4 * h + 3] = (typename Tr::elem)(float)(on ? (walls >> sq) & 1ULL : 0ULL);
             }
             *reinterpret_cast<typename Tr::afrag *>(smem + u * G::CS + G::real_slot(0, cell) * G::UB) = o;
         }
@@ -1263,11 +1266,12 @@ __device__ __forceinline__ void tower2_run(const TowerArgs &A, unsigned char *sm
             const int game = tower_src(A, tile0 + bl, x, y, sq);
             const unsigned long long mover = A.boards[2 * (size_t)game + 0];
             const unsigned long long opp = A.boards[2 * (size_t)game + 1];
+            const unsigned long long walls = A.masks ? A.masks[game] : A.blockers;
             typename Tr::quad o;
             o[0] = (typename Tr::elem)1.0f;
             o[1] = (typename Tr::elem)(float)((mover >> sq) & 1ULL);
             o[2] = (typename Tr::elem)(float)((opp >> sq) & 1ULL);
-            o[3] = (typename Tr::elem)(float)((A.blockers >> sq) & 1ULL);
+            o[3] = (typename Tr::elem)(float)((walls >> sq) & 1ULL);
             *reinterpret_cast<typename Tr::quad *>(smem + G::ch_off(G::real_slot(0, cell), 0)) = o;
         }
     }
@@ -1824,27 +1828,29 @@ __global__ __launch_bounds__(256) void k_sym_reduce(const float *__restrict__ sy
 static int net_launch(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
                       const int *d_count, int max_n, unsigned long long blockers, float *d_logits,
                       float *d_values, hipStream_t stream, unsigned long long *d_stamps, int sym, int thin = 0,
-                      const void *hook = nullptr);
+                      const void *hook = nullptr, const unsigned long long *d_masks = nullptr);
 
 // thin: the caller expects a handful of boards (<= 512): one board per workgroup (Geo2Thin) where that kernel applies
 int azh_net_launch(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
                    const int *d_count, int max_n, unsigned long long blockers, float *d_logits,
-                   float *d_values, hipStream_t stream, unsigned long long *d_stamps, int thin, const void *advance_hook)
+                   float *d_values, hipStream_t stream, unsigned long long *d_stamps, int thin, const void *advance_hook,
+                   const unsigned long long *d_masks)
 {
     return net_launch(net, dtype, d_boards, d_list, d_count, max_n, blockers, d_logits, d_values, stream, d_stamps, 0, thin,
-                      advance_hook);
+                      advance_hook, d_masks);
 }
 
 // Symmetry-averaged evaluation: the tower runs 8 * n virtual boards into the scratch arrays
 // (d_tmp_logits [8 max_n][833], d_tmp_values [8 max_n]), k_sym_reduce writes the averages by game.
 int azh_net_launch_sym(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
                        const int *d_count, int max_n, unsigned long long blockers, float *d_tmp_logits,
-                       float *d_tmp_values, float *d_logits, float *d_values, hipStream_t stream, int thin, const void *advance_hook)
+                       float *d_tmp_values, float *d_logits, float *d_values, hipStream_t stream, int thin, const void *advance_hook,
+                       const unsigned long long *d_masks)
 {
     if (max_n <= 0)
         return 0;
     int rc = net_launch(net, dtype, d_boards, d_list, d_count, max_n, blockers, d_tmp_logits, d_tmp_values, stream,
-                        nullptr, 1, thin, advance_hook);
+                        nullptr, 1, thin, advance_hook, d_masks);
     if (rc)
         return rc;
     hipLaunchKernelGGL(k_sym_reduce, dim3(max_n), dim3(256), 0, stream, (const float *)d_tmp_logits,
@@ -1855,7 +1861,7 @@ int azh_net_launch_sym(azh_net *net, int dtype, const unsigned long long *d_boar
 
 static TowerArgs tower_args(const azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
                             const int *d_count, int max_n, unsigned long long blockers, float *d_logits, float *d_values,
-                            unsigned long long *d_stamps, int sym)
+                            unsigned long long *d_stamps, int sym, const unsigned long long *d_masks)
 {
     TowerArgs a;
     a.conv_w = net->bufs[dtype].conv_w;
@@ -1871,6 +1877,7 @@ static TowerArgs tower_args(const azh_net *net, int dtype, const unsigned long l
     a.count = d_count;
     a.n = max_n;
     a.blockers = blockers;
+    a.masks = d_masks;
     a.logits = d_logits;
     a.values = d_values;
     a.stamps = d_stamps;
@@ -1884,7 +1891,7 @@ static TowerArgs tower_args(const azh_net *net, int dtype, const unsigned long l
 int azh_net_launch_pair(azh_net *net_a, azh_net *net_b, int dtype, const unsigned long long *d_boards, const int *d_list_a,
                         const int *d_count_a, const int *d_list_b, const int *d_count_b, int max_n,
                         unsigned long long blockers, float *d_logits, float *d_values, hipStream_t stream, int thin,
-                        const void *advance_hook)
+                        const void *advance_hook, const unsigned long long *d_masks)
 {
     if (dtype != AZH_DTYPE_BF16 && dtype != AZH_DTYPE_F16)
         return 1;
@@ -1896,8 +1903,8 @@ int azh_net_launch_pair(azh_net *net_a, azh_net *net_b, int dtype, const unsigne
 #endif
     if (net_pack(net_a, dtype) || net_pack(net_b, dtype))
         return -1;
-    const TowerArgs a = tower_args(net_a, dtype, d_boards, d_list_a, d_count_a, max_n, blockers, d_logits, d_values, nullptr, 0);
-    const TowerArgs b = tower_args(net_b, dtype, d_boards, d_list_b, d_count_b, max_n, blockers, d_logits, d_values, nullptr, 0);
+    const TowerArgs a = tower_args(net_a, dtype, d_boards, d_list_a, d_count_a, max_n, blockers, d_logits, d_values, nullptr, 0, d_masks);
+    const TowerArgs b = tower_args(net_b, dtype, d_boards, d_list_b, d_count_b, max_n, blockers, d_logits, d_values, nullptr, 0, d_masks);
     static bool attr_set[MAX_DEVICES][4] = {};
     const int dev = current_device();
     if (dev < 0)
@@ -1925,14 +1932,15 @@ int azh_net_launch_pair(azh_net *net_a, azh_net *net_b, int dtype, const unsigne
 
 static int net_launch(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
                       const int *d_count, int max_n, unsigned long long blockers, float *d_logits,
-                      float *d_values, hipStream_t stream, unsigned long long *d_stamps, int sym, int thin, const void *hook)
+                      float *d_values, hipStream_t stream, unsigned long long *d_stamps, int sym, int thin, const void *hook,
+                      const unsigned long long *d_masks)
 {
     if (dtype < 0 || dtype > 2)
         return azh_fail(-2, "bad dtype %d", dtype);
     const AdvanceHook &H = hook ? *static_cast<const AdvanceHook *>(hook) : no_hook();
     if (net_pack(net, dtype))
         return -1;
-    TowerArgs a = tower_args(net, dtype, d_boards, d_list, d_count, max_n, blockers, d_logits, d_values, d_stamps, sym);
+    TowerArgs a = tower_args(net, dtype, d_boards, d_list, d_count, max_n, blockers, d_logits, d_values, d_stamps, sym, d_masks);
     if (sym)
         max_n *= 8;  // grid size: virtual boards
     if (net->filters != 128) {
@@ -1995,59 +2003,82 @@ struct DevBuf {
     DevBuf &operator=(const DevBuf &) = delete;
 };
 
-static int net_forward(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, uint64_t blockers, float *logits_out,
-                       float *values_out, int thin);
+// mode: 0 the ordinary tower, 1 one board per workgroup (thin), 2 test-time symmetry averaging; masks: null, or one per board
+static int net_forward(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, uint64_t blockers, const uint64_t *masks,
+                       float *logits_out, float *values_out, int mode, const char *who);
 
 extern "C" int azh_net_forward(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
                                uint64_t blockers, float *logits_out, float *values_out)
 {
-    return net_forward(net, dtype, n, leaf_boards, blockers, logits_out, values_out, 0);
+    return net_forward(net, dtype, n, leaf_boards, blockers, nullptr, logits_out, values_out, 0, "azh_net_forward");
 }
 
 extern "C" int azh_net_forward_thin(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
                                     uint64_t blockers, float *logits_out, float *values_out)
 {
-    return net_forward(net, dtype, n, leaf_boards, blockers, logits_out, values_out, 1);
-}
-
-static int net_forward(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, uint64_t blockers, float *logits_out,
-                       float *values_out, int thin)
-{
-    if (!net || !leaf_boards || !logits_out || !values_out || n < 0)
-        return azh_fail(-1, "azh_net_forward: bad argument");
-    if (n == 0)
-        return 0;
-    DevBuf d_b, d_l, d_v;  // freed on every path out of this function
-    AZH_HIP(d_b.alloc((size_t)n * 16));
-    AZH_HIP(d_l.alloc((size_t)n * 833 * 4));
-    AZH_HIP(d_v.alloc((size_t)n * 4));
-    AZH_HIP(hipMemcpy(d_b.p, leaf_boards, (size_t)n * 16, hipMemcpyHostToDevice));
-    const int rc = azh_net_launch(net, dtype, d_b.as<unsigned long long>(), nullptr, nullptr, n, blockers, d_l.as<float>(),
-                                  d_v.as<float>(), 0, nullptr, thin);
-    if (rc)
-        return rc;
-    AZH_HIP(hipDeviceSynchronize());
-    AZH_HIP(hipMemcpy(logits_out, d_l.p, (size_t)n * 833 * 4, hipMemcpyDeviceToHost));
-    AZH_HIP(hipMemcpy(values_out, d_v.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return 0;
+    return net_forward(net, dtype, n, leaf_boards, blockers, nullptr, logits_out, values_out, 1, "azh_net_forward");
 }
 
 extern "C" int azh_net_forward_sym(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
                                    uint64_t blockers, float *logits_out, float *values_out)
 {
+    return net_forward(net, dtype, n, leaf_boards, blockers, nullptr, logits_out, values_out, 2, "azh_net_forward_sym");
+}
+
+// A wall mask per board (null: no walls anywhere, as blockers = 0): the header.
+static int net_forward_masks(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, const uint64_t *masks, float *logits_out,
+                             float *values_out, int mode, const char *who)
+{
+    for (int i = 0; masks && i < n; i++)
+        if (masks[i] >> 49)
+            return azh_fail(-2, "%s: the mask of board %d (%#llx) has bits beyond the 49 cells", who, i, (unsigned long long)masks[i]);
+    return net_forward(net, dtype, n, leaf_boards, 0ULL, masks, logits_out, values_out, mode, who);
+}
+
+extern "C" int azh_net_forward_masks(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
+                                     const uint64_t *blockers_per_board, float *logits_out, float *values_out)
+{
+    return net_forward_masks(net, dtype, n, leaf_boards, blockers_per_board, logits_out, values_out, 0, "azh_net_forward_masks");
+}
+
+extern "C" int azh_net_forward_masks_thin(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
+                                          const uint64_t *blockers_per_board, float *logits_out, float *values_out)
+{
+    return net_forward_masks(net, dtype, n, leaf_boards, blockers_per_board, logits_out, values_out, 1, "azh_net_forward_masks_thin");
+}
+
+extern "C" int azh_net_forward_masks_sym(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
+                                         const uint64_t *blockers_per_board, float *logits_out, float *values_out)
+{
+    return net_forward_masks(net, dtype, n, leaf_boards, blockers_per_board, logits_out, values_out, 2, "azh_net_forward_masks_sym");
+}
+
+static int net_forward(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, uint64_t blockers, const uint64_t *masks,
+                       float *logits_out, float *values_out, int mode, const char *who)
+{
     if (!net || !leaf_boards || !logits_out || !values_out || n < 0)
-        return azh_fail(-1, "azh_net_forward_sym: bad argument");
+        return azh_fail(-1, "%s: bad argument", who);
     if (n == 0)
         return 0;
-    DevBuf d_b, d_l, d_v, d_tl, d_tv;
+    DevBuf d_b, d_m, d_l, d_v, d_tl, d_tv;  // freed on every path out of this function
     AZH_HIP(d_b.alloc((size_t)n * 16));
     AZH_HIP(d_l.alloc((size_t)n * 833 * 4));
     AZH_HIP(d_v.alloc((size_t)n * 4));
-    AZH_HIP(d_tl.alloc((size_t)n * 8 * 833 * 4));
-    AZH_HIP(d_tv.alloc((size_t)n * 8 * 4));
     AZH_HIP(hipMemcpy(d_b.p, leaf_boards, (size_t)n * 16, hipMemcpyHostToDevice));
-    const int rc = azh_net_launch_sym(net, dtype, d_b.as<unsigned long long>(), nullptr, nullptr, n, blockers,
-                                      d_tl.as<float>(), d_tv.as<float>(), d_l.as<float>(), d_v.as<float>(), 0);
+    if (masks) {
+        AZH_HIP(d_m.alloc((size_t)n * 8));
+        AZH_HIP(hipMemcpy(d_m.p, masks, (size_t)n * 8, hipMemcpyHostToDevice));
+    }
+    int rc;
+    if (mode == 2) {
+        AZH_HIP(d_tl.alloc((size_t)n * 8 * 833 * 4));
+        AZH_HIP(d_tv.alloc((size_t)n * 8 * 4));
+        rc = azh_net_launch_sym(net, dtype, d_b.as<unsigned long long>(), nullptr, nullptr, n, blockers, d_tl.as<float>(),
+                                d_tv.as<float>(), d_l.as<float>(), d_v.as<float>(), 0, 0, nullptr, d_m.as<unsigned long long>());
+    } else {
+        rc = azh_net_launch(net, dtype, d_b.as<unsigned long long>(), nullptr, nullptr, n, blockers, d_l.as<float>(),
+                            d_v.as<float>(), 0, nullptr, mode, nullptr, d_m.as<unsigned long long>());
+    }
     if (rc)
         return rc;
     AZH_HIP(hipDeviceSynchronize());

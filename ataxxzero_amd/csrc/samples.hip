@@ -718,7 +718,7 @@ static int record_owners(const RecordView &r, uint64_t blockers, uint64_t *owner
 static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts, uint32_t *games,
                              uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
                              uint16_t *target_index, float *target_weight, uint64_t *game_blockers, bool aux,
-                             uint64_t *game_owners);
+                             uint64_t *game_owners, const uint64_t *record_masks = nullptr, int64_t n_masks = 0);
 
 extern "C" int azh_samples_pack_records_blockers(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts,
                                                  uint32_t *games, uint64_t *boards, uint8_t *ply_flags, double *values,
@@ -741,8 +741,15 @@ extern "C" int azh_samples_pack_records_aux(const uint32_t *rec, int64_t words, 
 static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts, uint32_t *games,
                              uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
                              uint16_t *target_index, float *target_weight, uint64_t *game_blockers, bool aux,
-                             uint64_t *game_owners)
+                             uint64_t *game_owners, const uint64_t *record_masks, int64_t n_masks)
 {
+    // record_masks: null, or one mask per record of the buffer in its order (markers of dropped and loaded games included),
+    // in place of `blockers`: records of an engine with a start pool (azh_engine_uid_blockers of each record's uid)
+    int64_t ri = 0;
+    for (int64_t i = 0; record_masks && i < n_masks; i++)
+        if (record_masks[i] & ~BOARD_MASK)
+            return azh_fail(-2, "azh_samples_pack_records: the blockers mask %#llx of record %lld has bits beyond the 49 cells",
+                            (unsigned long long)record_masks[i], (long long)i);
     if (blockers & ~BOARD_MASK)
         return azh_fail(-2, "azh_samples_pack_records: the blockers mask %#llx has bits beyond the 49 cells",
                         (unsigned long long)blockers);
@@ -760,6 +767,11 @@ static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blocke
             return azh_fail(-2, "azh_samples_pack_records: word %lld: %s", (long long)pos, why ? why : "not a record");
         const RecordView r{rec + pos};
         pos += r.words();
+        if (record_masks) {
+            if (ri >= n_masks)
+                return azh_fail(-2, "azh_samples_pack_records: %lld masks for a buffer of more records", (long long)n_masks);
+            blockers = record_masks[ri++];
+        }
         if (r.dropped() || r.loaded())  // a dropped game's marker; a game begun at a loaded position: neither has a line
             continue;
         if (r.plies() < 1 || r.plies() > 0xFFFFu || r.random_ply_plus_1() > 0xFFFFu)
@@ -784,6 +796,8 @@ static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blocke
         n_games++;
         n_plies += r.plies();
     }
+    if (record_masks && ri != n_masks)
+        return azh_fail(-2, "azh_samples_pack_records: %lld masks for a buffer of %lld records", (long long)n_masks, (long long)ri);
     counts[0] = n_games;
     counts[1] = n_plies;
     counts[2] = n_targets;
@@ -794,11 +808,14 @@ static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blocke
                         (long long)n_games, (long long)n_plies, (long long)n_targets, (long long)cap_games,
                         (long long)cap_plies, (long long)cap_targets);
     int64_t g = 0, q = 0, t = 0;
+    ri = 0;
     std::vector<std::pair<std::string, uint32_t>> ents;
     target_start[0] = 0;
     for (int64_t pos = 0; pos < words;) {
         const RecordView r{rec + pos};
         pos += r.words();
+        if (record_masks)
+            blockers = record_masks[ri++];
         if (r.dropped() || r.loaded())
             continue;
         const bool valued = r.valued(), capped = r.capped();
@@ -834,13 +851,14 @@ extern "C" int azh_samples_add_records(azh_samples *s, const uint32_t *rec, int6
     return azh_samples_add_records_blockers(s, rec, words, 0ULL);
 }
 
-static int add_records(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers, bool aux)
+static int add_records(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers, bool aux,
+                       const uint64_t *record_masks = nullptr, int64_t n_masks = 0)
 {
     if (!s)
         return azh_fail(-1, "azh_samples_add_records: null store");
     int64_t counts[3] = {0, 0, 0};
     if (int rc = pack_records_impl(rec, words, blockers, counts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                   nullptr, aux, nullptr))
+                                   nullptr, aux, nullptr, record_masks, n_masks))
         return rc;
     std::vector<uint64_t> masks((size_t)counts[0] + 1), owners((size_t)counts[0] * 2 + 1);
     std::vector<uint32_t> games((size_t)counts[0] * 4 + 1);
@@ -851,10 +869,11 @@ static int add_records(azh_samples *s, const uint32_t *rec, int64_t words, uint6
     std::vector<uint16_t> index((size_t)counts[2] + 1);
     std::vector<float> weight((size_t)counts[2] + 1);
     if (int rc = pack_records_impl(rec, words, blockers, counts, games.data(), boards.data(), flags.data(), values.data(),
-                                   start.data(), index.data(), weight.data(), masks.data(), aux, owners.data()))
+                                   start.data(), index.data(), weight.data(), masks.data(), aux, owners.data(), record_masks,
+                                   n_masks))
         return rc;
     return azh_samples_add_games_aux(s, counts[0], games.data(), counts[1], boards.data(), flags.data(), values.data(),
-                                     start.data(), index.data(), weight.data(), blockers ? masks.data() : nullptr,
+                                     start.data(), index.data(), weight.data(), blockers || record_masks ? masks.data() : nullptr,
                                      aux ? owners.data() : nullptr);
 }
 
@@ -866,6 +885,14 @@ extern "C" int azh_samples_add_records_blockers(azh_samples *s, const uint32_t *
 extern "C" int azh_samples_add_records_aux(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers)
 {
     return add_records(s, rec, words, blockers, true);
+}
+
+extern "C" int azh_samples_add_records_masks(azh_samples *s, const uint32_t *rec, int64_t words, const uint64_t *masks,
+                                             int64_t n_masks, int aux)
+{
+    if (!masks || n_masks < 0)
+        return azh_fail(-1, "azh_samples_add_records_masks: null argument");
+    return add_records(s, rec, words, 0ULL, aux != 0, masks, n_masks);
 }
 
 extern "C" int azh_samples_final_owners(uint64_t x, uint64_t o, uint64_t blockers, int o_to_move, uint32_t move,

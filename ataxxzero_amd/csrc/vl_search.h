@@ -141,7 +141,7 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
                 const ulonglong2 pw = A.nb[node];
                 const Board cb = make_move(unpack_board(pw.x, pw.y), (int)(mv & 0xFF), (int)(mv >> 8));
                 int res2;
-                const int M2 = wave_movegen(cb, P.blockers, s_moves, &res2);
+                const int M2 = wave_movegen(cb, game_blockers(P, g), s_moves, &res2);
                 wave_sync();
                 if (s.n_nodes >= P.node_cap || (res2 == 0 && (s.n_edges + M2 > P.edge_cap || M2 > 255))) {
                     // arena full: this path is dropped (it keeps its virtual loss until the backup) and the batch ends
@@ -221,6 +221,8 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
         V.path_len[base + lane] = r_len;
         P.need_eval[base + lane] = need ? 1 : 0;
         P.leaf_board[base + lane] = make_ulonglong2(r_mover, r_opp);
+        if (P.pool)
+            P.leaf_mask[base + lane] = P.slot_mask[g];
     }
     if (lane == 0) {
         P.gs[g] = s;

@@ -114,6 +114,9 @@ SIGNATURES = {
     "azh_net_forward_sym": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _u64, _vp, _vp]),
     "azh_net_bench": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(_f32)]),
     "azh_net_forward_thin": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _u64, _vp, _vp]),
+    "azh_net_forward_masks": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "azh_net_forward_masks_thin": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "azh_net_forward_masks_sym": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "azh_net_bench_thin": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(_f32)]),
     "azh_net_stamps": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
     "azh_engine_create": (ctypes.c_int, [_P(Config), _P(_vp)]),
@@ -176,6 +179,9 @@ SIGNATURES = {
     "azh_format_record_json_blockers": (ctypes.c_int, [_vp, ctypes.c_int64, _i32, _u64, _vp, ctypes.c_int64,
                                                        _P(ctypes.c_int64)]),
     "azh_engine_set_positions": (ctypes.c_int, [_vp, _vp, _vp]),
+    "azh_engine_set_start_pool": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int]),
+    "azh_start_pool_entry": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_int, ctypes.c_int]),
+    "azh_engine_uid_blockers": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp]),
     "azh_engine_set_game_limit": (ctypes.c_int, [_vp, ctypes.c_int64]),
     "azh_samples_create": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P(_vp)]),
     "azh_samples_destroy": (None, [_vp]),
@@ -218,6 +224,7 @@ SIGNATURES = {
     "azh_samples_pack_records_aux": (ctypes.c_int, [_vp, ctypes.c_int64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                     _vp]),
     "azh_samples_add_records_aux": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _u64]),
+    "azh_samples_add_records_masks": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int]),
     "azh_samples_game_owners": (ctypes.c_int, [_vp, _vp]),
     "azh_samples_gather_aux": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                               ctypes.c_size_t]),
@@ -375,6 +382,15 @@ def cells_to_blockers(cells):
     for c in cells:
         mask |= 1 << (c % 7 + 7 * (6 - c // 7))
     return mask
+
+
+def start_pool_entry(uid, n, stride=1):
+    """The entry of a start pool of n entries that game `uid` starts from, (uid // stride) % n (azh_start_pool_entry; host
+    arithmetic, no device)."""
+    r = load().azh_start_pool_entry(int(uid), int(n), int(stride))
+    if r < 0:
+        check(r)
+    return r
 
 
 def playout_cap_kind(seed, uid, ply, full_per_65536):
@@ -542,6 +558,13 @@ def probe_detmath(kind, values=None, aux=None, seed=0):
 
 # ------------------------------------------------------------------ network
 
+def _board_masks(blockers, n):
+    masks = np.ascontiguousarray(blockers, dtype=np.uint64).ravel()
+    if masks.size != n:
+        raise ValueError("%d wall masks for %d boards" % (masks.size, n))
+    return masks
+
+
 class Net:
     """Device-resident policy/value net (model.Network forward, model.py:38-79)."""
 
@@ -558,13 +581,19 @@ class Net:
         self.h = h
 
     def forward(self, leaf_boards, blockers, dtype=DTYPE_BF16, thin=False):
-        """thin: one board per workgroup (the kernel for a handful of boards, azh_net_forward_thin)."""
+        """thin: one board per workgroup (the kernel for a handful of boards, azh_net_forward_thin).  blockers: one wall
+        mask for every board, or an array of one mask per board (azh_net_forward_masks: all of them in one launch)."""
         leaf_boards = np.ascontiguousarray(leaf_boards, dtype=np.uint64).reshape(-1, 2)
         n = len(leaf_boards)
         logits = np.zeros((n, 7, 7, 17), dtype=np.float32)
         values = np.zeros((n, 1), dtype=np.float32)
-        fn = load().azh_net_forward_thin if thin else load().azh_net_forward
-        check(fn(self.h, dtype, n, _ptr(leaf_boards), int(blockers), _ptr(logits), _ptr(values)))
+        if np.ndim(blockers) == 0:
+            fn = load().azh_net_forward_thin if thin else load().azh_net_forward
+            check(fn(self.h, dtype, n, _ptr(leaf_boards), int(blockers), _ptr(logits), _ptr(values)))
+        else:
+            masks = _board_masks(blockers, n)
+            fn = load().azh_net_forward_masks_thin if thin else load().azh_net_forward_masks
+            check(fn(self.h, dtype, n, _ptr(leaf_boards), _ptr(masks), _ptr(logits), _ptr(values)))
         return logits, values
 
     def forward_sym(self, leaf_boards, blockers, dtype=DTYPE_BF16):
@@ -573,7 +602,11 @@ class Net:
         n = len(leaf_boards)
         logits = np.zeros((n, 7, 7, 17), dtype=np.float32)
         values = np.zeros((n, 1), dtype=np.float32)
-        check(load().azh_net_forward_sym(self.h, dtype, n, _ptr(leaf_boards), int(blockers), _ptr(logits), _ptr(values)))
+        if np.ndim(blockers) == 0:
+            check(load().azh_net_forward_sym(self.h, dtype, n, _ptr(leaf_boards), int(blockers), _ptr(logits), _ptr(values)))
+        else:                                    # (one mask per board, as forward)
+            check(load().azh_net_forward_masks_sym(self.h, dtype, n, _ptr(leaf_boards), _ptr(_board_masks(blockers, n)),
+                                                   _ptr(logits), _ptr(values)))
         return logits, values
 
     def bench(self, n, iters=20, dtype=DTYPE_BF16, thin=False):
@@ -784,6 +817,27 @@ class Engine:
         boards = np.ascontiguousarray(boards, dtype=np.uint64).reshape(self.G, 2)
         plies = np.ascontiguousarray(plies, dtype=np.int32).reshape(self.G)
         check(load().azh_engine_set_positions(self.h, _ptr(boards), _ptr(plies)))
+
+    def set_start_pool(self, starts, stride=1):
+        """A start position and wall map per game: game uid starts from entry (uid // stride) % n of `starts` — FEN strings,
+        or (x, o, blockers, turn) tuples of bitboards — and is played on its walls (azh_engine_set_start_pool; before the
+        first select).  stride 2: a two-net match, whose slots 2k and 2k + 1 share a map.  An empty list takes the pool away."""
+        from . import selfplay
+        rows = [selfplay.parse_fen(e) if isinstance(e, str) else tuple(int(v) for v in e) for e in starts]
+        x, o, bl = (np.array([r[i] for r in rows], dtype=np.uint64) for i in range(3))
+        turn = np.array([r[3] for r in rows], dtype=np.int32)
+        check(load().azh_engine_set_start_pool(self.h, len(rows), _ptr(x), _ptr(o), _ptr(bl), _ptr(turn), int(stride)))
+
+    def uid_blockers(self, uid):
+        """The walls game `uid` is played on: its pool entry's, or the engine's mask (azh_engine_uid_blockers)."""
+        out = ctypes.c_uint64(0)
+        check(load().azh_engine_uid_blockers(self.h, int(uid), ctypes.byref(out)))
+        return int(out.value)
+
+    def record_blockers(self, words):
+        """One wall mask per record of `words` (staged_records; markers included): what SampleStore.add_records takes as
+        `blockers` for the records of an engine with a start pool."""
+        return np.array([self.uid_blockers(r.uid) for r in records(words, markers=True)], dtype=np.uint64)
 
     def set_emit_order(self, by_uid):
         """True: finished games are handed out in uid order (unbiased prefixes); False: as they finish."""
@@ -1194,9 +1248,14 @@ class SampleStore:
 
     def add_records(self, records, blockers=0, aux=False):
         """Ring records as Engine.staged_records returns them, and the wall mask of the engine that wrote them
-        (azh_samples_add_records_blockers; aux: with every game's owners, azh_samples_add_records_aux)."""
+        (azh_samples_add_records_blockers; aux: with every game's owners, azh_samples_add_records_aux) — or, for an engine
+        with a start pool, an array of one mask per record (Engine.record_blockers; azh_samples_add_records_masks)."""
         rec = np.ascontiguousarray(records, dtype=np.uint32).ravel()
         self._mirror = None
+        if np.ndim(blockers) != 0:
+            masks = np.ascontiguousarray(blockers, dtype=np.uint64).ravel()
+            check(load().azh_samples_add_records_masks(self.h, _ptr(rec), rec.size, _ptr(masks), masks.size, 1 if aux else 0))
+            return
         add = load().azh_samples_add_records_aux if aux else load().azh_samples_add_records_blockers
         check(add(self.h, _ptr(rec), rec.size, int(blockers)))
 

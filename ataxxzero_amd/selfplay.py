@@ -44,6 +44,49 @@ def parse_fen(fen):
     return x, o, bl, turn
 
 
+def parse_fen_file(path):
+    """A file of start positions, one FEN per line (blank lines and lines that begin with '#' skipped) -> the FENs.
+    ValueError, with the file and line named, for a line parse_fen does not take, a position the engine would refuse
+    (start_refusal) and a file without a position."""
+    fens = []
+    with open(path) as f:
+        for number, line in enumerate(f, 1):
+            line = line.strip()
+            if not line or line.startswith("#"):
+                continue
+            try:
+                why = start_refusal(*parse_fen(line))
+            except ValueError as err:
+                why = str(err)
+            if why:
+                raise ValueError("%s, line %d: %s" % (path, number, why))
+            fens.append(line)
+    if not fens:
+        raise ValueError("%s holds no position" % path)
+    return fens
+
+
+def start_refusal(x, o, blockers, turn):
+    """Why the engine refuses a start position (azh_engine_set_start_pool's checks, host arithmetic), or None."""
+    board = (1 << 49) - 1
+    if (x | o | blockers) & ~board:
+        return "a row is longer than 7 cells"
+    if x & o or (x | o) & blockers:
+        return "a stone stands on a wall or on another stone"
+    if not x or not o:
+        return "a side has no stone"
+    empty, own, reach = board & ~(x | o | blockers), (o if turn else x), 0
+    for sq in range(49):
+        if (own >> sq) & 1:
+            for dy in range(-2, 3):
+                for dx in range(-2, 3):
+                    if 0 <= sq % 7 + dx < 7 and 0 <= sq // 7 + dy < 7:
+                        reach |= 1 << (sq + dx + 7 * dy)
+    if not reach & empty:
+        return "the position is finished (the side to move has no move)"
+    return None
+
+
 def symmetric_blockers(blockers):
     """Is the wall mask its own image under all 8 symmetries of the board?  (link.symmetry_board; host arithmetic)"""
     return all(link.symmetry_board(s, blockers) == blockers for s in (1, 2, 4))
@@ -143,6 +186,9 @@ class SelfPlay:
     (link.Engine.set_random_symmetry): every leaf goes to the net as its image under a symmetry drawn per (seed, uid,
     position); the start position's blockers must be their own image under all 8 symmetries.
 
+    `start_fens` sets a pool of start positions in every half-batch engine (link.Engine.set_start_pool): game uid of an
+    engine starts from entry uid % n and is played on its walls; `fen` is then the start of no game.
+
     `resign` = (q_below, consecutive, playthrough_fraction) turns the recorded search value and resignation on in every
     half-batch engine (link.Engine.set_resign); (0, 1, 0) records values and never resigns.
 
@@ -156,7 +202,7 @@ class SelfPlay:
 
     def __init__(self, conv_weights, bn_params, games, visits, dtype="bf16", seed=DEFAULT_SEED,
                  fen=START_FEN_SELFPLAY, streams=1, fast_visits=0, full_fraction=0.25, forced_playouts=0.0,
-                 random_symmetry=False, resign=None, temperature=None, gumbel=None, **cfg):
+                 random_symmetry=False, resign=None, temperature=None, gumbel=None, start_fens=None, **cfg):
         self.dtype = link.DTYPES[dtype]
         if gumbel:
             cfg = dict(cfg, flags=cfg.get("flags", 0) | link.FLAG_NO_REUSE, dirichlet_weight=0.0)
@@ -169,6 +215,9 @@ class SelfPlay:
                         for i in range(streams)]
         self.engine = self.engines[0]
         self.games = games
+        if start_fens:      # every half-batch engine maps its own uids onto the pool
+            for e in self.engines:
+                e.set_start_pool(start_fens)
         if fast_visits:
             self.set_playout_cap(fast_visits, full_fraction)
         if forced_playouts:

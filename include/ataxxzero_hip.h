@@ -122,6 +122,16 @@ int azh_net_bench(azh_net *net, int dtype, int n, int iters, float *ms_out);
 int azh_net_forward_thin(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, uint64_t blockers,
                          float *logits_out, float *values_out);
 int azh_net_bench_thin(azh_net *net, int dtype, int n, int iters, float *ms_out);
+/* azh_net_forward, _thin and _sym with a wall mask PER BOARD, blockers_per_board [n] (bits beyond the 49 cells: -2): board i is
+ * evaluated with the wall plane of its own mask, in the same launch as the others — what the engine's loop does under a start
+ * pool (azh_engine_set_start_pool).  A board's rows are bit for bit those of the same launch with that board's mask for every
+ * board.  blockers_per_board = NULL: no walls anywhere, the bytes of azh_net_forward with blockers = 0. */
+int azh_net_forward_masks(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, const uint64_t *blockers_per_board,
+                          float *logits_out, float *values_out);
+int azh_net_forward_masks_thin(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, const uint64_t *blockers_per_board,
+                               float *logits_out, float *values_out);
+int azh_net_forward_masks_sym(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, const uint64_t *blockers_per_board,
+                              float *logits_out, float *values_out);
 /* Diagnostic build of the bf16 tower with s_memtime stamps per layer phase: copies the
  * stamps of the first `wgs` workgroups, [wg][wave][128] u64, to out (layout: net_kernels.hip). */
 int azh_net_stamps(azh_net *net, int n, int wgs, uint64_t *out);
@@ -548,6 +558,36 @@ int azh_engine_set_thin_batches(azh_engine *e, int mode);
  * is raised): see there. */
 int azh_engine_set_positions(azh_engine *e, const uint64_t *boards, const int32_t *plies);
 
+/* A start position and wall map per game, drawn from a pool (an extension, off by default; DESIGN.md, "A start position per
+ * game").  With a pool of n entries — x [n], o [n], blockers [n] bitboards, turn [n] (0: x to move, 1: o), copied — the game
+ * with uid u starts from entry (u / stride) % n and is played on that entry's walls, instead of azh_config's start_x, start_o,
+ * start_turn and blockers; azh_start_pool_entry restates the rule on the host.  Slot g plays uids g, g + games, ..., so a slot
+ * changes map from one game to the next unless n divides games / stride.  stride 1: self-play; stride 2: a two-net match, whose
+ * slots 2k and 2k + 1 play one map with the colours swapped as they share an opening.  Round robin keeps every prefix of a
+ * uid-ordered games file balanced over the maps.  All games are evaluated in the same tower launches — each leaf goes to the
+ * net with the wall plane of its own game, which the select that produced the leaf wrote beside it — and are written into the
+ * same lines: with azh_engine_set_record_blockers every line's "blockers" is the mask of the line's game, and
+ * azh_engine_uid_blockers gives a host the mask of any uid (the engine's one mask while no pool is set).
+ * n = 0 takes the pool away: every game starts from the configured position again.  1 <= n <= AZH_START_POOL_MAX, stride >= 1.
+ * Call before the engine's first select (the pool replaces the start position the engine was created with; every slot starts
+ * its game again, so positions loaded by azh_engine_set_positions before the call are gone: load them after it).  Under a pool
+ * azh_engine_set_positions checks slot g's position against the walls of uid g and plays it on them.
+ * Checked in the setters' order, and a refused call changes nothing: -1 a null argument; -2 n or stride out of range, or an
+ * entry (named in azh_last_error, the first one) with bits beyond the 49 cells, a cell with stones of both sides, a stone on
+ * a wall, a side without a stone, a turn that is neither 0 nor 1, or a position the rules adjudicate as finished; -3 a
+ * selected batch awaits its backup; -4 the engine has begun to search, or random symmetry is on and an entry's mask is not its
+ * own image under all 8 symmetries ("azh_engine_set_start_pool: the random symmetry is not supported with a blockers mask (0x...)
+ * that is not its own image under all 8 symmetries (...)").  With a pool set, azh_engine_set_random_symmetry refuses in the same
+ * words when any entry's mask is not invariant (the table above reads "the engine's blockers mask" as "every mask games are
+ * played on"). */
+#define AZH_START_POOL_MAX 65536
+int azh_engine_set_start_pool(azh_engine *e, int n, const uint64_t *x, const uint64_t *o, const uint64_t *blockers,
+                              const int32_t *turn, int stride);
+/* (uid / stride) % n, or a negative code for n < 1 or stride < 1.  Host arithmetic only, usable without a device. */
+int azh_start_pool_entry(uint32_t uid, int n, int stride);
+/* The walls game `uid` of this engine is played on: its pool entry's, or the engine's blockers while no pool is set. */
+int azh_engine_uid_blockers(const azh_engine *e, uint32_t uid, uint64_t *out);
+
 /* ------------------------------------------------------------------ moves named by the host (an extension)
  * A front-end that keeps its search tree across moves (uai_interface.py --reuse-tree; the reference's
  * MCTSEngine.set_state, engine.py:452-472, walks to the new root with MCTS.play, engine.py:411-424) tells the engine
@@ -660,7 +700,8 @@ int azh_format_record_json(const uint32_t *rec, int64_t words, int32_t with_ids,
  * ones; with thousands of games in flight that bias is no longer slight, and uid order removes it (the first N
  * lines are the first N games started).  Call before the first drain. */
 int azh_engine_set_emit_order(azh_engine *e, int by_uid);
-/* on != 0: every line azh_engine_drain_json writes gains one key in front, "blockers":[...] — the engine's blockers mask as
+/* on != 0: every line azh_engine_drain_json writes gains one key in front, "blockers":[...] — the engine's blockers mask (under a
+ * start pool: the mask of the line's game, azh_engine_uid_blockers of its uid) as
  * the ascending list of wall cells in the index the line's boards use, x + 7 y with y = 0 at rank 7 ([] for no walls; the
  * start position of the self-play generator gives [17,23,25,31]).  The ring record does not change, and a line with the key's
  * bytes taken out is the line written without it.  Off by default.  Takes effect for records fetched after the call. */
@@ -784,6 +825,12 @@ int azh_samples_pack_records_blockers(const uint32_t *rec, int64_t words, uint64
                                       uint16_t *target_index, float *target_weight, uint64_t *game_blockers);
 int azh_samples_add_records_blockers(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers);
 int azh_samples_game_blockers(const azh_samples *s, uint64_t *blockers);
+/* azh_samples_add_records_blockers (aux = 0) / azh_samples_add_records_aux (aux != 0) for the records of an engine with a start
+ * pool (azh_engine_set_start_pool): masks [n_masks], one per record of the buffer in its order — the markers of dropped and
+ * loaded games included — each azh_engine_uid_blockers of the record's uid.  The same refusals, before anything is written; -2
+ * too when n_masks is not the number of records. */
+int azh_samples_add_records_masks(azh_samples *s, const uint32_t *rec, int64_t words, const uint64_t *masks, int64_t n_masks,
+                                  int aux);
 
 /* ------------------------------------------------------------------ policy surprise weighting
  * (an extension of the store; with none of these called, every launch and every draw above is what it was.)

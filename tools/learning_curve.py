@@ -62,6 +62,8 @@ def generate(args, n, out):
            "--output-games", path, "--visits", str(args.visits)] + args.generator_flags
     if args.start_fen is not None:       # the games are played on that board and say so: train.py then shows the net its walls
         cmd += ["--start-fen", args.start_fen, "--record-blockers"]
+    if args.start_fens is not None:      # (the generator records every game's own walls by itself)
+        cmd += ["--start-fens", args.start_fens]
     gen_log = os.path.join(args.prefix, "generator-%03i.log" % n)
     t0 = time.time()
     with open(gen_log, "w") as lf:
@@ -124,6 +126,8 @@ def arena(args, k, out, other=1):
         cmd += ["--opening-depth", str(args.arena_opening_depth)]
     if args.start_fen is not None:
         cmd += ["--start-fen", args.start_fen]
+    if args.start_fens is not None:
+        cmd += ["--start-fens", args.start_fens]
     t0 = time.time()
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
     if res.returncode != 0:
@@ -191,6 +195,9 @@ def main():
     ap.add_argument("--start-fen", default=None, metavar="FEN",
                     help="the whole loop on this start position, walls ('-') included: the generator gets it together with "
                          "--record-blockers, the ringmaster gets it too (default: each tool's own start position)")
+    ap.add_argument("--start-fens", default=None, metavar="FILE",
+                    help="the whole loop on a pool of start positions, one FEN per line: the generator and the ringmaster both "
+                         "get the file (not with --start-fen)")
     ap.add_argument("--anchor", type=int, default=0, help="> 1: also play every later generation against model-<anchor>")
     ap.add_argument("--blocks", type=int, default=12)
     ap.add_argument("--filters", type=int, default=128)
@@ -209,6 +216,10 @@ def main():
                          "0.5 --aux-reply 0.15\"; the auxiliary targets find a game's owners from its line alone, so games on a "
                          "board with walls must say so: give --start-fen, which records them")
     args = ap.parse_args()
+    if args.start_fen is not None and args.start_fens is not None:
+        ap.error("--start-fen and --start-fens exclude each other")
+    if args.start_fens is not None:
+        args.start_fens = os.path.abspath(args.start_fens)
     args.generator_flags = args.generator_flags.split()
     args.train_flags = args.train_flags.split()
     from ataxxzero_amd import model

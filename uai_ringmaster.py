@@ -60,6 +60,9 @@ if __name__ == "__main__":
         flag("--start-fen", "the position every game starts from, walls ('-') included (extension; default: the reference's "
                             "board without walls): both engines search on that board, and --opening-depth plays its random "
                             "plies on it", default=selfplay.START_FEN_PLAIN, metavar="FEN"),
+        flag("--start-fens", "a file of start positions, one FEN per line (blank lines and '#' comments skipped; extension): "
+                             "pairing k plays entry k mod n both ways, and --opening-depth plays each pairing's random plies on "
+                             "its own map.  Not with --start-fen", metavar="FILE"),
     ])
     print("Options:", args)
     if not args.engine or len(args.engine) != 2:
@@ -73,6 +76,14 @@ if __name__ == "__main__":
     (path_a, visits_a), (path_b, visits_b) = parse_engine(engines[0]), parse_engine(engines[1])
     if visits_a != visits_b:
         raise SystemExit("uai_ringmaster.py: both engines must use the same --visits in the batched arena")
+    start_fens = None
+    if args.start_fens is not None:
+        if args.start_fen != selfplay.START_FEN_PLAIN:
+            raise SystemExit("uai_ringmaster.py: --start-fens and --start-fen exclude each other")
+        try:
+            start_fens = selfplay.parse_fen_file(args.start_fens)
+        except (OSError, ValueError) as err:
+            raise SystemExit("uai_ringmaster.py: --start-fens: %s" % err)
     selfplay.select_device(0)
     concurrent = args.concurrent or min(2048, args.game_count + args.game_count % 2)
     concurrent += concurrent % 2
@@ -85,7 +96,8 @@ if __name__ == "__main__":
                         max_plies=args.max_plies + 1 if args.max_plies is not None else 400,
                         opening_depth=args.opening_depth,
                         # (another board is an option of its own: without the flag the call is the one it has always been)
-                        **({"start_fen": args.start_fen} if args.start_fen != selfplay.START_FEN_PLAIN else {}))
+                        **({"start_fen": args.start_fen} if args.start_fen != selfplay.START_FEN_PLAIN else {}),
+                        **({"start_fens": start_fens} if start_fens else {}))
     names = {"a": " ".join(engines[0]), "b": " ".join(engines[1])}
     wins = {"a": 0, "b": 0}
     annulled = 0
