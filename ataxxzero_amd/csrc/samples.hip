@@ -509,14 +509,6 @@ extern "C" int azh_samples_create(int64_t cap_games, int64_t cap_plies, int64_t 
     return 0;
 }
 
-extern "C" int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies,
-                                     const uint64_t *boards, const uint8_t *ply_flags, const double *values,
-                                     const int32_t *target_start, const uint16_t *target_index, const float *target_weight)
-{
-    return azh_samples_add_games_blockers(s, n_games, games, n_plies, boards, ply_flags, values, target_start, target_index,
-                                          target_weight, nullptr);
-}
-
 // A wall mask with bits beyond the 49 cells, or a stone of plies [0, n) on a wall cell: why, or null.
 static const char *walls_refusal(uint64_t mask, const uint64_t *boards, int64_t n, int64_t *ply)
 {
@@ -529,15 +521,6 @@ static const char *walls_refusal(uint64_t mask, const uint64_t *boards, int64_t 
             return "a stone stands on a wall cell";
         }
     return nullptr;
-}
-
-extern "C" int azh_samples_add_games_blockers(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies,
-                                              const uint64_t *boards, const uint8_t *ply_flags, const double *values,
-                                              const int32_t *target_start, const uint16_t *target_index,
-                                              const float *target_weight, const uint64_t *game_blockers)
-{
-    return azh_samples_add_games_aux(s, n_games, games, n_plies, boards, ply_flags, values, target_start, target_index,
-                                     target_weight, game_blockers, nullptr);
 }
 
 // A game's owner masks against its walls and its recorded result: why they are refused, or null.
@@ -565,17 +548,25 @@ extern "C" int azh_samples_check_owners(uint64_t own_x, uint64_t own_o, uint64_t
     return 0;
 }
 
-extern "C" int azh_samples_add_games_aux(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies,
-                                         const uint64_t *boards, const uint8_t *ply_flags, const double *values,
-                                         const int32_t *target_start, const uint16_t *target_index, const float *target_weight,
-                                         const uint64_t *game_blockers, const uint64_t *game_owners)
+extern "C" int azh_samples_add_games(azh_samples *s, const azh_sample_arrays *a)
 {
-    if (!s || n_games < 0 || n_plies < 0 || (n_games && !games) ||
-        (n_plies && (!boards || !ply_flags || !values)) || !target_start)
+    if (!s || !a)
         return azh_fail(-1, "azh_samples_add_games: null argument");
-    const int64_t n_targets = target_start[n_plies];
+    const int64_t n_games = a->n_games, n_plies = a->n_plies, n_targets = a->n_targets;
+    const uint32_t *games = a->games;
+    const uint64_t *boards = a->boards, *game_blockers = a->game_blockers, *game_owners = a->game_owners;
+    const uint8_t *ply_flags = a->ply_flags;
+    const double *values = a->values;
+    const int32_t *target_start = a->target_start;
+    const uint16_t *target_index = a->target_index;
+    const float *target_weight = a->target_weight;
+    if (n_games < 0 || n_plies < 0 || (n_games && !games) || (n_plies && (!boards || !ply_flags || !values)) || !target_start)
+        return azh_fail(-1, "azh_samples_add_games: null argument");
     if (target_start[0] != 0 || n_targets < 0 || (n_targets && (!target_index || !target_weight)))
         return azh_fail(-2, "azh_samples_add_games: target_start must begin at 0 and the targets must be given");
+    if (n_targets != target_start[n_plies])
+        return azh_fail(-2, "azh_samples_add_games: n_targets is %lld, target_start ends at %lld", (long long)n_targets,
+                        (long long)target_start[n_plies]);
     // everything is checked and built on the host first: a refused call leaves the store exactly as it was
     std::vector<uint4> g_words((size_t)n_games);
     std::vector<u32> g_count((size_t)n_games);
@@ -696,15 +687,6 @@ extern "C" int azh_samples_add_games_aux(azh_samples *s, int64_t n_games, const 
     return 0;
 }
 
-// Ring records -> the arrays azh_samples_add_games takes.  Host code only.
-extern "C" int azh_samples_pack_records(const uint32_t *rec, int64_t words, int64_t *counts, uint32_t *games,
-                                        uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
-                                        uint16_t *target_index, float *target_weight)
-{
-    return azh_samples_pack_records_blockers(rec, words, 0ULL, counts, games, boards, ply_flags, values, target_start,
-                                             target_index, target_weight, nullptr);
-}
-
 // A record's owners: azh_samples_final_owners of its last ply's boards and move word.
 static int record_owners(const RecordView &r, uint64_t blockers, uint64_t *owners)
 {
@@ -715,36 +697,16 @@ static int record_owners(const RecordView &r, uint64_t blockers, uint64_t *owner
     return azh_samples_final_owners(ply.x(), ply.o(), blockers, (int)((r.plies() - 1u) & 1u), ply.move(), owners, &result);
 }
 
-static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts, uint32_t *games,
-                             uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
-                             uint16_t *target_index, float *target_weight, uint64_t *game_blockers, bool aux,
-                             uint64_t *game_owners, const uint64_t *record_masks = nullptr, int64_t n_masks = 0);
-
-extern "C" int azh_samples_pack_records_blockers(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts,
-                                                 uint32_t *games, uint64_t *boards, uint8_t *ply_flags, double *values,
-                                                 int32_t *target_start, uint16_t *target_index, float *target_weight,
-                                                 uint64_t *game_blockers)
-{
-    return pack_records_impl(rec, words, blockers, counts, games, boards, ply_flags, values, target_start, target_index,
-                             target_weight, game_blockers, false, nullptr);
-}
-
-extern "C" int azh_samples_pack_records_aux(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts,
-                                            uint32_t *games, uint64_t *boards, uint8_t *ply_flags, double *values,
-                                            int32_t *target_start, uint16_t *target_index, float *target_weight,
-                                            uint64_t *game_blockers, uint64_t *game_owners)
-{
-    return pack_records_impl(rec, words, blockers, counts, games, boards, ply_flags, values, target_start, target_index,
-                             target_weight, game_blockers, true, game_owners);
-}
-
-static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts, uint32_t *games,
-                             uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
-                             uint16_t *target_index, float *target_weight, uint64_t *game_blockers, bool aux,
-                             uint64_t *game_owners, const uint64_t *record_masks, int64_t n_masks)
+// Ring records -> the arrays azh_samples_add_games takes.  Host code only.
+extern "C" int azh_samples_pack_records(const uint32_t *rec, int64_t words, uint64_t blockers, const uint64_t *record_masks,
+                                        int64_t n_masks, int aux, azh_sample_arrays *out)
 {
     // record_masks: null, or one mask per record of the buffer in its order (markers of dropped and loaded games included),
     // in place of `blockers`: records of an engine with a start pool (azh_engine_uid_blockers of each record's uid)
+    if (record_masks && blockers)
+        return azh_fail(-1, "azh_samples_pack_records: walls are given by `blockers` or by record_masks, not both");
+    if (record_masks && n_masks < 0)
+        return azh_fail(-1, "azh_samples_pack_records: %lld masks", (long long)n_masks);
     int64_t ri = 0;
     for (int64_t i = 0; record_masks && i < n_masks; i++)
         if (record_masks[i] & ~BOARD_MASK)
@@ -753,12 +715,13 @@ static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blocke
     if (blockers & ~BOARD_MASK)
         return azh_fail(-2, "azh_samples_pack_records: the blockers mask %#llx has bits beyond the 49 cells",
                         (unsigned long long)blockers);
-    if (!counts || (words > 0 && !rec) || words < 0)
+    if (!out || (words > 0 && !rec) || words < 0)
         return azh_fail(-1, "azh_samples_pack_records: null argument");
-    const bool write = games != nullptr;
-    if (write && (!boards || !ply_flags || !values || !target_start || !target_index || !target_weight))
+    const bool write = out->games != nullptr;
+    if (write && (!out->boards || !out->ply_flags || !out->values || !out->target_start || !out->target_index ||
+                  !out->target_weight))
         return azh_fail(-1, "azh_samples_pack_records: null output array");
-    const int64_t cap_games = counts[0], cap_plies = counts[1], cap_targets = counts[2];
+    const int64_t cap_games = out->n_games, cap_plies = out->n_plies, cap_targets = out->n_targets;
     // the first walk counts and refuses; nothing is written before the whole buffer has been found well formed
     int64_t n_games = 0, n_plies = 0, n_targets = 0;
     for (int64_t pos = 0; pos < words;) {
@@ -798,9 +761,9 @@ static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blocke
     }
     if (record_masks && ri != n_masks)
         return azh_fail(-2, "azh_samples_pack_records: %lld masks for a buffer of %lld records", (long long)n_masks, (long long)ri);
-    counts[0] = n_games;
-    counts[1] = n_plies;
-    counts[2] = n_targets;
+    out->n_games = n_games;
+    out->n_plies = n_plies;
+    out->n_targets = n_targets;
     if (!write)
         return 0;
     if (n_games > cap_games || n_plies > cap_plies || n_targets > cap_targets)
@@ -810,7 +773,7 @@ static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blocke
     int64_t g = 0, q = 0, t = 0;
     ri = 0;
     std::vector<std::pair<std::string, uint32_t>> ents;
-    target_start[0] = 0;
+    out->target_start[0] = 0;
     for (int64_t pos = 0; pos < words;) {
         const RecordView r{rec + pos};
         pos += r.words();
@@ -819,80 +782,57 @@ static int pack_records_impl(const uint32_t *rec, int64_t words, uint64_t blocke
         if (r.dropped() || r.loaded())
             continue;
         const bool valued = r.valued(), capped = r.capped();
-        games[4 * g] = (uint32_t)q;
-        games[4 * g + 1] = r.plies();
-        games[4 * g + 2] = r.result() | (capped ? GAME_HAS_FULL : 0u) | (valued ? GAME_HAS_VALUES : 0u);
-        games[4 * g + 3] = r.random_ply_plus_1();
-        if (game_blockers)
-            game_blockers[g] = blockers;
-        if (aux && game_owners)
-            (void)record_owners(r, blockers, game_owners + 2 * g);  // (legal: the first walk has made this call)
+        uint32_t *game = out->games + 4 * g;
+        game[0] = (uint32_t)q;
+        game[1] = r.plies();
+        game[2] = r.result() | (capped ? GAME_HAS_FULL : 0u) | (valued ? GAME_HAS_VALUES : 0u);
+        game[3] = r.random_ply_plus_1();
+        if (out->game_blockers)
+            out->game_blockers[g] = blockers;
+        if (aux && out->game_owners)
+            (void)record_owners(r, blockers, out->game_owners + 2 * g);  // (legal: the first walk has made this call)
         g++;
         PlyView ply = r.first_ply();
         for (uint32_t p = 0; p < r.plies(); p++, q++, ply = ply.next()) {
-            boards[2 * q] = ply.x();
-            boards[2 * q + 1] = ply.o();
-            ply_flags[q] = capped && ply.full(valued) ? AZH_SAMPLES_PLY_FULL : 0;  // (the device loop records no pass: a ply is a move)
-            values[q] = ply.value(valued);
+            out->boards[2 * q] = ply.x();
+            out->boards[2 * q + 1] = ply.o();
+            out->ply_flags[q] = capped && ply.full(valued) ? AZH_SAMPLES_PLY_FULL : 0;  // (the device loop records no pass: a ply is a move)
+            out->values[q] = ply.value(valued);
             const uint64_t total = azh_ply_target(ply, ents);  // in the order of the line's "dists"
             for (const auto &e : ents) {
-                target_index[t] = (uint16_t)policy_index(e.second & 0xFFFFu);
-                target_weight[t] = total ? (float)((double)(e.second >> 16) / (double)total) : 0.f;
+                out->target_index[t] = (uint16_t)policy_index(e.second & 0xFFFFu);
+                out->target_weight[t] = total ? (float)((double)(e.second >> 16) / (double)total) : 0.f;
                 t++;
             }
-            target_start[q + 1] = (int32_t)t;
+            out->target_start[q + 1] = (int32_t)t;
         }
     }
     return 0;
 }
 
-extern "C" int azh_samples_add_records(azh_samples *s, const uint32_t *rec, int64_t words)
-{
-    return azh_samples_add_records_blockers(s, rec, words, 0ULL);
-}
-
-static int add_records(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers, bool aux,
-                       const uint64_t *record_masks = nullptr, int64_t n_masks = 0)
+extern "C" int azh_samples_add_records(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers,
+                                       const uint64_t *record_masks, int64_t n_masks, int aux)
 {
     if (!s)
         return azh_fail(-1, "azh_samples_add_records: null store");
-    int64_t counts[3] = {0, 0, 0};
-    if (int rc = pack_records_impl(rec, words, blockers, counts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                   nullptr, aux, nullptr, record_masks, n_masks))
+    azh_sample_arrays a = {};  // no arrays: the counts only
+    if (int rc = azh_samples_pack_records(rec, words, blockers, record_masks, n_masks, aux, &a))
         return rc;
-    std::vector<uint64_t> masks((size_t)counts[0] + 1), owners((size_t)counts[0] * 2 + 1);
-    std::vector<uint32_t> games((size_t)counts[0] * 4 + 1);
-    std::vector<uint64_t> boards((size_t)counts[1] * 2 + 1);
-    std::vector<uint8_t> flags((size_t)counts[1] + 1);
-    std::vector<double> values((size_t)counts[1] + 1);
-    std::vector<int32_t> start((size_t)counts[1] + 1);
-    std::vector<uint16_t> index((size_t)counts[2] + 1);
-    std::vector<float> weight((size_t)counts[2] + 1);
-    if (int rc = pack_records_impl(rec, words, blockers, counts, games.data(), boards.data(), flags.data(), values.data(),
-                                   start.data(), index.data(), weight.data(), masks.data(), aux, owners.data(), record_masks,
-                                   n_masks))
+    std::vector<uint64_t> masks((size_t)a.n_games + 1), owners((size_t)a.n_games * 2 + 1);
+    std::vector<uint32_t> games((size_t)a.n_games * 4 + 1);
+    std::vector<uint64_t> boards((size_t)a.n_plies * 2 + 1);
+    std::vector<uint8_t> flags((size_t)a.n_plies + 1);
+    std::vector<double> values((size_t)a.n_plies + 1);
+    std::vector<int32_t> start((size_t)a.n_plies + 1);
+    std::vector<uint16_t> index((size_t)a.n_targets + 1);
+    std::vector<float> weight((size_t)a.n_targets + 1);
+    a = azh_sample_arrays{a.n_games, a.n_plies, a.n_targets, games.data(), boards.data(), flags.data(), values.data(),
+                          start.data(), index.data(), weight.data(), masks.data(), owners.data()};
+    if (int rc = azh_samples_pack_records(rec, words, blockers, record_masks, n_masks, aux, &a))
         return rc;
-    return azh_samples_add_games_aux(s, counts[0], games.data(), counts[1], boards.data(), flags.data(), values.data(),
-                                     start.data(), index.data(), weight.data(), blockers || record_masks ? masks.data() : nullptr,
-                                     aux ? owners.data() : nullptr);
-}
-
-extern "C" int azh_samples_add_records_blockers(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers)
-{
-    return add_records(s, rec, words, blockers, false);
-}
-
-extern "C" int azh_samples_add_records_aux(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers)
-{
-    return add_records(s, rec, words, blockers, true);
-}
-
-extern "C" int azh_samples_add_records_masks(azh_samples *s, const uint32_t *rec, int64_t words, const uint64_t *masks,
-                                             int64_t n_masks, int aux)
-{
-    if (!masks || n_masks < 0)
-        return azh_fail(-1, "azh_samples_add_records_masks: null argument");
-    return add_records(s, rec, words, 0ULL, aux != 0, masks, n_masks);
+    a.game_blockers = blockers || record_masks ? masks.data() : nullptr;
+    a.game_owners = aux ? owners.data() : nullptr;
+    return azh_samples_add_games(s, &a);
 }
 
 extern "C" int azh_samples_final_owners(uint64_t x, uint64_t o, uint64_t blockers, int o_to_move, uint32_t move,
@@ -911,7 +851,7 @@ extern "C" int azh_samples_final_owners(uint64_t x, uint64_t o, uint64_t blocker
     b.turn = o_to_move ? 1 : 0;
     uint16_t legal[POLICY];
     int32_t n_legal = 0;  // the position's moves as the surprise pass lists them: the one statement of the rules on the host
-    if (int rc = azh_samples_legal_blockers(b.turn ? o : x, b.turn ? x : o, blockers, legal, &n_legal))
+    if (int rc = azh_samples_legal(b.turn ? o : x, b.turn ? x : o, blockers, legal, &n_legal))
         return rc;
     if ((move & 0xFFFFu) == 0xFFFFu) {
         if (n_legal)
@@ -930,7 +870,7 @@ extern "C" int azh_samples_final_owners(uint64_t x, uint64_t o, uint64_t blocker
     // the kernels' order of checks (wave_movegen): a side without stones, then a stuck mover, then a full board
     const u64 empty = BOARD_MASK & ~(b.x | b.o | blockers);
     u64 own_x = b.x, own_o = b.o;
-    if (azh_samples_legal_blockers(b.turn ? b.o : b.x, b.turn ? b.x : b.o, blockers, legal, &n_legal))
+    if (azh_samples_legal(b.turn ? b.o : b.x, b.turn ? b.x : b.o, blockers, legal, &n_legal))
         return -1;
     if (!b.x || !b.o) {
         if ((b.turn ? !b.x : !b.o) && !n_legal && empty)
@@ -988,56 +928,26 @@ extern "C" int azh_samples_game_blockers(const azh_samples *s, uint64_t *blocker
     return 0;
 }
 
-// The two gather calls, each once for the kernels without auxiliary targets (A = NoAux: the code of the entry points as they
-// were) and once for those with them (A = Aux).
-template <class A>
-static int gather(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features, float *policy,
-                  float *value, const A &aux, uintptr_t stream);
-template <class A>
-static int draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game, int64_t n_games,
-                       double value_blend, float *features, float *policy, float *value, const A &aux, int32_t *draws_out,
-                       uintptr_t stream);
-
-extern "C" int azh_samples_gather(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features,
-                                  float *policy, float *value, uintptr_t stream)
+// The outputs of a minibatch call: 0 with *aux set when the four auxiliary arrays are given, 0 with it clear when none is.
+static int check_outputs(const char *what, const azh_sample_outputs *out, bool *aux)
 {
-    return gather(s, n, draws, value_blend, features, policy, value, NoAux{}, stream);
+    if (!out || !out->features || !out->policy || !out->value)
+        return azh_fail(-1, "%s: null argument", what);
+    const int given = !!out->ownership + !!out->score + !!out->reply + !!out->aux_weight;
+    if (given != 0 && given != 4)
+        return azh_fail(-1, "%s: %d of the four auxiliary outputs are given: all or none", what, given);
+    *aux = given == 4;
+    return 0;
 }
 
-extern "C" int azh_samples_gather_aux(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features,
-                                      float *policy, float *value, float *ownership, float *score, float *reply,
-                                      float *aux_weight, uintptr_t stream)
+extern "C" int azh_samples_gather(azh_samples *s, int n, const int32_t *draws, double value_blend,
+                                  const azh_sample_outputs *out, uintptr_t stream)
 {
-    if (!s || !ownership || !score || !reply || !aux_weight)
+    bool aux = false;
+    if (!s || !draws)
         return azh_fail(-1, "azh_samples_gather: null argument");
-    const Aux aux{s->d_owners.d, ownership, score, reply, aux_weight};
-    return gather(s, n, draws, value_blend, features, policy, value, aux, stream);
-}
-
-extern "C" int azh_samples_draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game,
-                                       int64_t n_games, double value_blend, float *features, float *policy, float *value,
-                                       int32_t *draws_out, uintptr_t stream)
-{
-    return draw_gather(s, n, seed, step, first_game, n_games, value_blend, features, policy, value, NoAux{}, draws_out, stream);
-}
-
-extern "C" int azh_samples_draw_gather_aux(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game,
-                                           int64_t n_games, double value_blend, float *features, float *policy, float *value,
-                                           float *ownership, float *score, float *reply, float *aux_weight, int32_t *draws_out,
-                                           uintptr_t stream)
-{
-    if (!s || !ownership || !score || !reply || !aux_weight)
-        return azh_fail(-1, "azh_samples_draw_gather: null argument");
-    const Aux aux{s->d_owners.d, ownership, score, reply, aux_weight};
-    return draw_gather(s, n, seed, step, first_game, n_games, value_blend, features, policy, value, aux, draws_out, stream);
-}
-
-template <class A>
-static int gather(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features, float *policy,
-                  float *value, const A &aux, uintptr_t stream)
-{
-    if (!s || !draws || !features || !policy || !value)
-        return azh_fail(-1, "azh_samples_gather: null argument");
+    if (int rc = check_outputs("azh_samples_gather", out, &aux))
+        return rc;
     if (n < 1)
         return azh_fail(-1, "azh_samples_gather: n must be at least 1");
     if (!(value_blend == value_blend))
@@ -1062,12 +972,13 @@ static int gather(azh_samples *s, int n, const int32_t *draws, double value_blen
     memcpy(s->h_stage[k], draws, (size_t)n * 3 * sizeof(int));
     hipStream_t st = stream ? (hipStream_t)stream : s->stream;
     AZH_HIP(hipMemcpyAsync(s->d_stage[k], s->h_stage[k], (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, st));
-    if constexpr (std::is_same<A, Aux>::value)
+    if (aux)
         hipLaunchKernelGGL(k_samples_gather_aux, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, s->d_stage[k], value_blend,
-                           features, policy, value, aux);
+                           out->features, out->policy, out->value,
+                           Aux{s->d_owners.d, out->ownership, out->score, out->reply, out->aux_weight});
     else
         hipLaunchKernelGGL(k_samples_gather, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, s->d_stage[k], value_blend,
-                           features, policy, value);
+                           out->features, out->policy, out->value);
     AZH_HIP(hipGetLastError());
     AZH_HIP(hipEventRecord(s->used[k], st));
     if (!stream)
@@ -1075,27 +986,30 @@ static int gather(azh_samples *s, int n, const int32_t *draws, double value_blen
     return 0;
 }
 
-template <class A>
-static int draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game, int64_t n_games,
-                       double value_blend, float *features, float *policy, float *value, const A &aux, int32_t *draws_out,
-                       uintptr_t stream)
+extern "C" int azh_samples_draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game,
+                                       int64_t n_games, double value_blend, const azh_sample_outputs *out, int32_t *draws_out,
+                                       uintptr_t stream)
 {
-    if (!s || !features || !policy || !value)
+    bool aux = false;
+    if (!s)
         return azh_fail(-1, "azh_samples_draw_gather: null argument");
+    if (int rc = check_outputs("azh_samples_draw_gather", out, &aux))
+        return rc;
     if (n < 1 || first_game < 0 || n_games < 1 || first_game + n_games > s->games)
         return azh_fail(-1, "azh_samples_draw_gather: n = %d, games [%lld, %lld) of %lld", n, (long long)first_game,
                         (long long)(first_game + n_games), (long long)s->games);
     if (!(value_blend == value_blend))
         return azh_fail(-1, "azh_samples_draw_gather: value_blend is not a number");
     hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-    if constexpr (std::is_same<A, Aux>::value)
+    if (aux)
         hipLaunchKernelGGL(k_samples_draw_gather_aux, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, (u32)seed,
-                           (u32)(seed >> 32), step, (u32)first_game, (u32)n_games, value_blend, features, policy, value,
-                           draws_out, s->d_errors.d, aux);
+                           (u32)(seed >> 32), step, (u32)first_game, (u32)n_games, value_blend, out->features, out->policy,
+                           out->value, draws_out, s->d_errors.d,
+                           Aux{s->d_owners.d, out->ownership, out->score, out->reply, out->aux_weight});
     else
         hipLaunchKernelGGL(k_samples_draw_gather, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), n, (u32)seed,
-                           (u32)(seed >> 32), step, (u32)first_game, (u32)n_games, value_blend, features, policy, value,
-                           draws_out, s->d_errors.d);
+                           (u32)(seed >> 32), step, (u32)first_game, (u32)n_games, value_blend, out->features, out->policy,
+                           out->value, draws_out, s->d_errors.d);
     AZH_HIP(hipGetLastError());
     if (!stream)
         AZH_HIP(hipStreamSynchronize(st));
@@ -1105,14 +1019,14 @@ static int draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int6
 // One sample's draw restated on the host from mirror arrays: arithmetic only, no device and no store.
 // cum == null: the uniform ply draw, the candidates found from the flags; else the weighted one from the mirrors of the
 // store's candidates and cum arrays (azh_samples_ply_cum).
-static int draw_host(const char *what, uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
-                     const uint32_t *games, int64_t total_games, const uint8_t *ply_flags, const uint16_t *candidates,
-                     const uint32_t *cum, int32_t *out)
+extern "C" int azh_samples_draw(uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
+                                const uint32_t *games, int64_t total_games, const uint8_t *ply_flags, const uint16_t *candidates,
+                                const uint32_t *cum, int32_t *out)
 {
-    if (!games || !ply_flags || !out)
-        return azh_fail(-1, "%s: null argument", what);
+    if (!games || !ply_flags || !out || (candidates != nullptr) != (cum != nullptr))
+        return azh_fail(-1, "azh_samples_draw: null argument (candidates and cum go together)");
     if (first_game < 0 || n_games < 1 || first_game + n_games > total_games || total_games > 0x7FFFFFFF)
-        return azh_fail(-1, "%s: games [%lld, %lld) of %lld", what, (long long)first_game,
+        return azh_fail(-1, "azh_samples_draw: games [%lld, %lld) of %lld", (long long)first_game,
                         (long long)(first_game + n_games), (long long)total_games);
     auto game_at = [&](int g) { return make_uint4(games[4 * g], games[4 * g + 1], games[4 * g + 2], games[4 * g + 3]); };
     auto candidate = [&](int g, uint32_t flag) {  // plies a sample may come from: all, or the full ones of a game with "full"
@@ -1150,23 +1064,6 @@ static int draw_host(const char *what, uint64_t seed, uint32_t step, uint32_t sa
         }
     }
     return 0;
-}
-
-extern "C" int azh_samples_draw(uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
-                                const uint32_t *games, int64_t total_games, const uint8_t *ply_flags, int32_t *out)
-{
-    return draw_host("azh_samples_draw", seed, step, sample, first_game, n_games, games, total_games, ply_flags, nullptr, nullptr,
-                     out);
-}
-
-extern "C" int azh_samples_draw_weighted(uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
-                                         const uint32_t *games, int64_t total_games, const uint8_t *ply_flags,
-                                         const uint16_t *candidates, const uint32_t *cum, int32_t *out)
-{
-    if (!candidates || !cum)
-        return azh_fail(-1, "azh_samples_draw_weighted: null argument");
-    return draw_host("azh_samples_draw_weighted", seed, step, sample, first_game, n_games, games, total_games, ply_flags,
-                     candidates, cum, out);
 }
 
 extern "C" int azh_samples_status(azh_samples *s, int64_t *failed)
@@ -1343,13 +1240,7 @@ extern "C" int azh_samples_surprise(azh_samples *s, azh_net *net, int dtype, int
     return 0;
 }
 
-extern "C" int azh_samples_legal(uint64_t mover, uint64_t opponent, uint16_t *index_out, int32_t *n_out)
-{
-    return azh_samples_legal_blockers(mover, opponent, 0ULL, index_out, n_out);
-}
-
-extern "C" int azh_samples_legal_blockers(uint64_t mover, uint64_t opponent, uint64_t blockers, uint16_t *index_out,
-                                          int32_t *n_out)
+extern "C" int azh_samples_legal(uint64_t mover, uint64_t opponent, uint64_t blockers, uint16_t *index_out, int32_t *n_out)
 {
     if (!index_out || !n_out)
         return azh_fail(-1, "azh_samples_legal: null argument");
@@ -1414,7 +1305,7 @@ extern "C" int azh_samples_surprise_host_blockers(const float *logits833, uint64
 {
     uint16_t legal[POLICY];
     int32_t n_legal = 0;
-    if (int rc = azh_samples_legal_blockers(mover, opponent, blockers, legal, &n_legal))
+    if (int rc = azh_samples_legal(mover, opponent, blockers, legal, &n_legal))
         return rc;
     return azh_samples_surprise_host(logits833, legal, n_legal, target_index, target_weight, n_targets, kl_out, illegal_out);
 }

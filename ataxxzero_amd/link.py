@@ -185,51 +185,32 @@ SIGNATURES = {
     "azh_engine_set_game_limit": (ctypes.c_int, [_vp, ctypes.c_int64]),
     "azh_samples_create": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P(_vp)]),
     "azh_samples_destroy": (None, [_vp]),
-    "azh_samples_add_games": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "azh_samples_pack_records": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "azh_samples_add_records": (ctypes.c_int, [_vp, _vp, ctypes.c_int64]),
-    "azh_samples_add_games_blockers": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                      _vp]),
-    "azh_samples_pack_records_blockers": (ctypes.c_int, [_vp, ctypes.c_int64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                         _vp]),
-    "azh_samples_add_records_blockers": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _u64]),
+    "azh_samples_add_games": (ctypes.c_int, [_vp, _vp]),
+    "azh_samples_pack_records": (ctypes.c_int, [_vp, ctypes.c_int64, _u64, _vp, ctypes.c_int64, ctypes.c_int, _vp]),
+    "azh_samples_add_records": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _u64, _vp, ctypes.c_int64, ctypes.c_int]),
     "azh_samples_game_blockers": (ctypes.c_int, [_vp, _vp]),
-    "azh_samples_legal_blockers": (ctypes.c_int, [_u64, _u64, _u64, _vp, _P(_i32)]),
     "azh_samples_surprise_host_blockers": (ctypes.c_int, [_vp, _u64, _u64, _u64, _vp, _vp, ctypes.c_int, _P(_f32), _P(_i32)]),
     "azh_samples_counts": (ctypes.c_int, [_vp, _vp]),
     "azh_samples_mirror": (ctypes.c_int, [_vp, _vp, _vp]),
-    "azh_samples_gather": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp, ctypes.c_size_t]),
+    "azh_samples_gather": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_double, _vp, ctypes.c_size_t]),
     "azh_samples_draw_gather": (ctypes.c_int, [_vp, ctypes.c_int, _u64, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64,
-                                               ctypes.c_double, _vp, _vp, _vp, _vp, ctypes.c_size_t]),
+                                               ctypes.c_double, _vp, _vp, ctypes.c_size_t]),
     "azh_samples_draw": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64, _vp,
-                                        ctypes.c_int64, _vp, _vp]),
+                                        ctypes.c_int64, _vp, _vp, _vp, _vp]),
     "azh_samples_status": (ctypes.c_int, [_vp, _P(ctypes.c_int64)]),
     "azh_samples_surprise_logits": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _P(ctypes.c_int64),
                                                    ctypes.c_size_t]),
     "azh_samples_surprise": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, _vp, _P(ctypes.c_int64)]),
     "azh_samples_set_surprise_chunk": (ctypes.c_int, [_vp, ctypes.c_int]),
     "azh_samples_surprise_ms": (ctypes.c_int, [_vp, _vp]),
-    "azh_samples_legal": (ctypes.c_int, [_u64, _u64, _vp, _P(_i32)]),
+    "azh_samples_legal": (ctypes.c_int, [_u64, _u64, _u64, _vp, _P(_i32)]),
     "azh_samples_surprise_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _P(_f32), _P(_i32)]),
     "azh_samples_set_ply_weights": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp]),
     "azh_samples_clear_ply_weights": (ctypes.c_int, [_vp]),
     "azh_samples_ply_cum": (ctypes.c_int, [_vp, _vp, _vp, _vp, _P(_i32)]),
-    "azh_samples_draw_weighted": (ctypes.c_int, [_u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64, _vp,
-                                                 ctypes.c_int64, _vp, _vp, _vp, _vp]),
-    # auxiliary targets
     "azh_samples_final_owners": (ctypes.c_int, [_u64, _u64, _u64, ctypes.c_int, ctypes.c_uint32, _vp, _P(_i32)]),
     "azh_samples_check_owners": (ctypes.c_int, [_u64, _u64, _u64, ctypes.c_uint32]),
-    "azh_samples_add_games_aux": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                 _vp]),
-    "azh_samples_pack_records_aux": (ctypes.c_int, [_vp, ctypes.c_int64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                    _vp]),
-    "azh_samples_add_records_aux": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _u64]),
-    "azh_samples_add_records_masks": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int]),
     "azh_samples_game_owners": (ctypes.c_int, [_vp, _vp]),
-    "azh_samples_gather_aux": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                              ctypes.c_size_t]),
-    "azh_samples_draw_gather_aux": (ctypes.c_int, [_vp, ctypes.c_int, _u64, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64,
-                                                   ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t]),
     # the reference's ABI, link.py:8-32
     "launch_threads": (None, [ctypes.c_char_p, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int]),
     "get_workload": (ctypes.c_int, []),
@@ -958,13 +939,30 @@ class Engine:
 
 # ------------------------------------------------------------------ device-resident training samples
 
-class SampleArrays:
+class CSampleArrays(ctypes.Structure):                        # azh_sample_arrays
+    _fields_ = [(n, ctypes.c_int64) for n in ("n_games", "n_plies", "n_targets")] + \
+               [(n, _vp) for n in ("games", "boards", "ply_flags", "values", "target_start", "target_index", "target_weight",
+                                   "game_blockers", "game_owners")]
+
+
+class CSampleOutputs(ctypes.Structure):                       # azh_sample_outputs
+    _fields_ = [(n, _vp) for n in ("features", "policy", "value", "ownership", "score", "reply", "aux_weight")]
+
+
+class _OptionalOwners:
+    __slots__ = ("owners",)                                   # kept apart: SampleArrays.__slots__ names the arrays every game has
+
+
+class SampleArrays(_OptionalOwners):
     """Games as azh_samples_add_games takes them: games (G, 4) u32 {first ply, plies, result | SAMPLES_GAME_*, random_ply + 1},
     boards (P, 2) u64, ply_flags (P,) u8, values (P,) f64, target_start (P + 1,) i32, target_index (T,) u16, target_weight
-    (T,) f32; blockers (G,) u64, every game's wall mask (bit = file + 7 * rank; default: none has walls)."""
+    (T,) f32; blockers (G,) u64, every game's wall mask (bit = file + 7 * rank; default: none has walls); owners: None, or
+    (G, 2) u64, the cells x and o own at each game's end, both 0 for a game whose final position is not terminal
+    (include/ataxxzero_hip.h, "Auxiliary targets")."""
     __slots__ = ("games", "boards", "ply_flags", "values", "target_start", "target_index", "target_weight", "blockers")
 
-    def __init__(self, games, boards, ply_flags, values, target_start, target_index, target_weight, blockers=None):
+    def __init__(self, games, boards, ply_flags, values, target_start, target_index, target_weight, blockers=None,
+                 owners=None):
         self.games = np.ascontiguousarray(games, dtype=np.uint32).reshape(-1, 4)
         self.boards = np.ascontiguousarray(boards, dtype=np.uint64).reshape(-1, 2)
         self.ply_flags = np.ascontiguousarray(ply_flags, dtype=np.uint8)
@@ -976,19 +974,16 @@ class SampleArrays:
                          else np.ascontiguousarray(blockers, dtype=np.uint64))
         if len(self.blockers) != len(self.games):
             raise ValueError("one blockers mask per game")
-
-
-class AuxSampleArrays(SampleArrays):
-    """SampleArrays and owners (G, 2) u64: the cells x and o own at each game's end, both 0 for a game whose final position
-    is not terminal (include/ataxxzero_hip.h, "Auxiliary targets")."""
-    __slots__ = ("owners",)
-
-    def __init__(self, *arrays, owners=None, **named):
-        super().__init__(*arrays, **named)
-        self.owners = (np.zeros((len(self.games), 2), dtype=np.uint64) if owners is None
-                       else np.ascontiguousarray(owners, dtype=np.uint64).reshape(-1, 2))
-        if len(self.owners) != len(self.games):
+        self.owners = None if owners is None else np.ascontiguousarray(owners, dtype=np.uint64).reshape(-1, 2)
+        if self.owners is not None and len(self.owners) != len(self.games):
             raise ValueError("two owner masks per game")
+
+    def c_arrays(self):
+        """-> the azh_sample_arrays of these arrays, the counts their lengths.  It points into them: keep them alive."""
+        return CSampleArrays(len(self.games), len(self.ply_flags), len(self.target_index),
+                             *[None if a is None else a.ctypes.data for a in (
+                                 self.games, self.boards, self.ply_flags, self.values, self.target_start, self.target_index,
+                                 self.target_weight, self.blockers, self.owners)])
 
 
 # bit x + 7 (6 - y) of a bitboard is the cell the game line's boards[ply][x + 7 y] names
@@ -1038,8 +1033,8 @@ def entry_owners(entry):
 def entries_to_arrays(entries, aux=False):
     """Parsed game lines -> SampleArrays, with the conversions of training._entry_arrays (weights np.float32 of the parsed
     double, "pass" keys skipped, an entry without `dists` a one-hot on the move played), in the order given; an entry's
-    "blockers" becomes its game's mask, after training.check_blockers (ValueError).  aux: -> AuxSampleArrays, every game's
-    owners found by entry_owners (AzhError for a game whose last move is not legal at its last board).  Host only."""
+    "blockers" becomes its game's mask, after training.check_blockers (ValueError).  aux: with `owners`, every game's
+    found by entry_owners (AzhError for a game whose last move is not legal at its last board).  Host only."""
     from . import training
     owners = [entry_owners(e) for e in entries] if aux else None
     games, boards, flags, values, starts, index, weight = [], [], [], [], [np.zeros(1, dtype=np.int32)], [], []
@@ -1074,73 +1069,68 @@ def entries_to_arrays(entries, aux=False):
 
     def cat(parts, dtype):
         return np.concatenate(parts).astype(dtype, copy=False) if parts else np.zeros(0, dtype=dtype)
-    arrays = (np.array(games, dtype=np.uint32).reshape(-1, 4), cat(boards, np.uint64).reshape(-1, 2),
-              cat(flags, np.uint8), cat(values, np.float64), cat(starts, np.int32), cat(index, np.uint16),
-              cat(weight, np.float32), np.array(masks, dtype=np.uint64))
-    if aux:
-        return AuxSampleArrays(*arrays, owners=np.array(owners, dtype=np.uint64).reshape(-1, 2))
-    return SampleArrays(*arrays)
+    return SampleArrays(np.array(games, dtype=np.uint32).reshape(-1, 4), cat(boards, np.uint64).reshape(-1, 2),
+                        cat(flags, np.uint8), cat(values, np.float64), cat(starts, np.int32), cat(index, np.uint16),
+                        cat(weight, np.float32), np.array(masks, dtype=np.uint64),
+                        owners=np.array(owners, dtype=np.uint64).reshape(-1, 2) if aux else None)
+
+
+def _record_walls(blockers):
+    """blockers as the records calls take the walls: -> (the scalar mask, the array of one mask per record or None)."""
+    if np.ndim(blockers) == 0:
+        return int(blockers), None
+    return 0, np.ascontiguousarray(blockers, dtype=np.uint64).ravel()
 
 
 def pack_records(records, blockers=0, aux=False):
     """Ring records (Engine.staged_records) -> SampleArrays holding what parsing the games' own lines would give; blockers:
-    the wall mask of the engine that wrote them, which a line written with "blockers" carries
-    (azh_samples_pack_records_blockers; host code, no GPU needed).  aux: -> AuxSampleArrays with every game's owners from its
-    last ply's boards and move word (azh_samples_pack_records_aux; AzhError -2 for a last move that is not legal there)."""
+    the wall mask of the engine that wrote them, which a line written with "blockers" carries — or, for an engine with a
+    start pool, an array of one mask per record (Engine.record_blockers).  aux: with `owners`, every game's from its last
+    ply's boards and move word (AzhError -2 for a last move that is not legal there).  (azh_samples_pack_records; host code,
+    no GPU needed.)"""
     rec = np.ascontiguousarray(records, dtype=np.uint32).ravel()
-    counts = np.zeros(3, dtype=np.int64)
+    mask, masks = _record_walls(blockers)
 
-    def call(*arrays):
-        if aux:
-            return load().azh_samples_pack_records_aux(_ptr(rec), rec.size, int(blockers), _ptr(counts), *arrays)
-        return load().azh_samples_pack_records_blockers(_ptr(rec), rec.size, int(blockers), _ptr(counts), *arrays[:-1])
-    check(call(*[None] * 9))
-    g, p, t = (int(c) for c in counts)
-    a = (AuxSampleArrays if aux else SampleArrays)(
-        np.zeros((g, 4), np.uint32), np.zeros((p, 2), np.uint64), np.zeros(p, np.uint8), np.zeros(p),
-        np.zeros(p + 1, np.int32), np.zeros(max(t, 1), np.uint16), np.zeros(max(t, 1), np.float32))
-    games = a.games if g else np.zeros((1, 4), np.uint32)      # (non-null: a null `games` asks for the counts only)
-    masks, owners = np.zeros(max(g, 1), np.uint64), np.zeros((max(g, 1), 2), np.uint64)
-    check(call(_ptr(games), _ptr(a.boards), _ptr(a.ply_flags), _ptr(a.values), _ptr(a.target_start), _ptr(a.target_index),
-               _ptr(a.target_weight), _ptr(masks), _ptr(owners)))
-    a.blockers = masks[:g]
-    if aux:
-        a.owners = owners[:g]
+    def call(c):
+        check(load().azh_samples_pack_records(_ptr(rec), rec.size, mask, _ptr(masks), 0 if masks is None else masks.size,
+                                              int(bool(aux)), ctypes.byref(c)))
+        return c.n_games, c.n_plies, c.n_targets
+    g, p, t = call(CSampleArrays())                            # no arrays: the counts only
+    a = SampleArrays(np.zeros((max(g, 1), 4), np.uint32), np.zeros((p, 2), np.uint64), np.zeros(p, np.uint8), np.zeros(p),
+                     np.zeros(p + 1, np.int32), np.zeros(max(t, 1), np.uint16), np.zeros(max(t, 1), np.float32),
+                     owners=np.zeros((max(g, 1), 2), np.uint64) if aux else None)   # (a null `games` asks for the counts)
+    call(a.c_arrays())
+    a.games, a.blockers, a.owners = a.games[:g], a.blockers[:g], a.owners[:g] if aux else None
     a.target_index, a.target_weight = a.target_index[:t], a.target_weight[:t]
     return a
 
 
-def samples_draw(seed, step, sample, first_game, n_games, games, ply_flags):
+def samples_draw(seed, step, sample, first_game, n_games, games, ply_flags, candidates=None, cum=None):
     """One sample's draw of SampleStore.draw_gather restated on the host from mirror arrays -> (game, ply, symmetry, attempts
-    used), (-1, -1, -1, 64) when all 64 attempts fail (azh_samples_draw; host arithmetic, no GPU needed)."""
+    used), (-1, -1, -1, 64) when all 64 attempts fail; with candidates and cum (SampleStore.ply_cum) the weighted ply choice
+    (azh_samples_draw; host arithmetic, no GPU needed)."""
     games = np.ascontiguousarray(games, dtype=np.uint32).reshape(-1, 4)
     ply_flags = np.ascontiguousarray(ply_flags, dtype=np.uint8)
+    candidates = None if candidates is None else np.ascontiguousarray(candidates, dtype=np.uint16)
+    cum = None if cum is None else np.ascontiguousarray(cum, dtype=np.uint32)
+    if any(a is not None and len(a) != len(ply_flags) for a in (candidates, cum)):
+        raise ValueError("candidates and cum hold one entry per ply")
     out = np.zeros(4, dtype=np.int32)
     check(load().azh_samples_draw(int(seed), int(step), int(sample), int(first_game), int(n_games), _ptr(games), len(games),
-                                  _ptr(ply_flags), _ptr(out)))
+                                  _ptr(ply_flags), _ptr(candidates), _ptr(cum), _ptr(out)))
     return tuple(int(v) for v in out)
 
 
 def samples_draw_weighted(seed, step, sample, first_game, n_games, games, ply_flags, candidates, cum):
-    """samples_draw with the weighted ply choice, from the mirrors SampleStore.mirror and SampleStore.ply_cum return
-    (azh_samples_draw_weighted; host arithmetic, no GPU needed)."""
-    games = np.ascontiguousarray(games, dtype=np.uint32).reshape(-1, 4)
-    ply_flags = np.ascontiguousarray(ply_flags, dtype=np.uint8)
-    candidates = np.ascontiguousarray(candidates, dtype=np.uint16)
-    cum = np.ascontiguousarray(cum, dtype=np.uint32)
-    if not len(candidates) == len(cum) == len(ply_flags):
-        raise ValueError("candidates and cum hold one entry per ply")
-    out = np.zeros(4, dtype=np.int32)
-    check(load().azh_samples_draw_weighted(int(seed), int(step), int(sample), int(first_game), int(n_games), _ptr(games),
-                                           len(games), _ptr(ply_flags), _ptr(candidates), _ptr(cum), _ptr(out)))
-    return tuple(int(v) for v in out)
+    """samples_draw with the weighted ply choice, from the mirrors SampleStore.mirror and SampleStore.ply_cum return."""
+    return samples_draw(seed, step, sample, first_game, n_games, games, ply_flags, candidates, cum)
 
 
 def samples_legal(mover, opponent, blockers=0):
     """The legal moves of a position (the mover's and the opponent's stones and the walls as bitboards) as flat policy indices
-    in the device movegen's order -> u16 array (azh_samples_legal_blockers; host arithmetic)."""
+    in the device movegen's order -> u16 array (azh_samples_legal; host arithmetic)."""
     index, n = np.zeros(833, dtype=np.uint16), ctypes.c_int32(0)
-    check(load().azh_samples_legal_blockers(int(mover), int(opponent), int(blockers), _ptr(index), ctypes.byref(n)))
+    check(load().azh_samples_legal(int(mover), int(opponent), int(blockers), _ptr(index), ctypes.byref(n)))
     return index[:n.value].copy()
 
 
@@ -1229,35 +1219,23 @@ class SampleStore:
             pass
 
     def add_arrays(self, a):
+        """The games of a SampleArrays, with their owners when it has them (azh_samples_add_games)."""
         self._mirror = None
-        masks = a.blockers if len(a.blockers) and a.blockers.any() else None
-        owners = getattr(a, "owners", None)
-        if owners is not None:                                # AuxSampleArrays: the games' owners go with them
-            check(load().azh_samples_add_games_aux(self.h, len(a.games), _ptr(a.games), len(a.ply_flags), _ptr(a.boards),
-                                                   _ptr(a.ply_flags), _ptr(a.values), _ptr(a.target_start),
-                                                   _ptr(a.target_index), _ptr(a.target_weight), _ptr(masks),
-                                                   _ptr(owners) if len(owners) else None))
-            return
-        check(load().azh_samples_add_games_blockers(self.h, len(a.games), _ptr(a.games), len(a.ply_flags), _ptr(a.boards),
-                                                    _ptr(a.ply_flags), _ptr(a.values), _ptr(a.target_start),
-                                                    _ptr(a.target_index), _ptr(a.target_weight), _ptr(masks)))
+        check(load().azh_samples_add_games(self.h, ctypes.byref(a.c_arrays())))
 
     def add_entries(self, entries, aux=False):
         """Parsed game lines, in the order given (entries_to_arrays)."""
         self.add_arrays(entries_to_arrays(entries, aux=aux))
 
     def add_records(self, records, blockers=0, aux=False):
-        """Ring records as Engine.staged_records returns them, and the wall mask of the engine that wrote them
-        (azh_samples_add_records_blockers; aux: with every game's owners, azh_samples_add_records_aux) — or, for an engine
-        with a start pool, an array of one mask per record (Engine.record_blockers; azh_samples_add_records_masks)."""
+        """Ring records as Engine.staged_records returns them, and the wall mask of the engine that wrote them — or, for an
+        engine with a start pool, an array of one mask per record (Engine.record_blockers); aux: with every game's owners
+        (azh_samples_add_records)."""
         rec = np.ascontiguousarray(records, dtype=np.uint32).ravel()
+        mask, masks = _record_walls(blockers)
         self._mirror = None
-        if np.ndim(blockers) != 0:
-            masks = np.ascontiguousarray(blockers, dtype=np.uint64).ravel()
-            check(load().azh_samples_add_records_masks(self.h, _ptr(rec), rec.size, _ptr(masks), masks.size, 1 if aux else 0))
-            return
-        add = load().azh_samples_add_records_aux if aux else load().azh_samples_add_records_blockers
-        check(add(self.h, _ptr(rec), rec.size, int(blockers)))
+        check(load().azh_samples_add_records(self.h, _ptr(rec), rec.size, mask, _ptr(masks),
+                                             0 if masks is None else masks.size, int(bool(aux))))
 
     def game_owners(self):
         """-> (G, 2) u64: the cells x and o own at every stored game's end, 0 and 0 for a game without owners
@@ -1288,64 +1266,41 @@ class SampleStore:
             self._mirror = games[:c["games"]], flags[:c["plies"]]
         return self._mirror
 
+    # features, policy, value; ownership, score, reply, aux_weight: a sample's shape in each output tensor
+    _SHAPES = ((7, 7, 4), (7, 7, 17), (1,), (7, 7), (1,), (7, 7, 17), (2,))
+
     @staticmethod
-    def outputs(n, device="cuda"):
+    def outputs(n, device="cuda", count=3):
         import torch
-        return (torch.empty((n, 7, 7, 4), dtype=torch.float32, device=device),
-                torch.empty((n, 7, 7, 17), dtype=torch.float32, device=device),
-                torch.empty((n, 1), dtype=torch.float32, device=device))
+        return tuple(torch.empty((n,) + shape, dtype=torch.float32, device=device) for shape in SampleStore._SHAPES[:count])
 
     @staticmethod
     def aux_outputs(n, device="cuda"):
         """outputs and the four auxiliary tensors: ownership (n, 7, 7), score (n, 1), reply (n, 7, 7, 17), aux_weight (n, 2)."""
-        import torch
-        return SampleStore.outputs(n, device) + (torch.empty((n, 7, 7), dtype=torch.float32, device=device),
-                                                 torch.empty((n, 1), dtype=torch.float32, device=device),
-                                                 torch.empty((n, 7, 7, 17), dtype=torch.float32, device=device),
-                                                 torch.empty((n, 2), dtype=torch.float32, device=device))
+        return SampleStore.outputs(n, device, count=7)
 
     @staticmethod
     def _pointers(out, n):
+        """-> (the azh_sample_outputs of three tensors, or of seven with the auxiliary targets; the stream to enqueue on)."""
         import torch
-        shapes = ((n, 7, 7, 4), (n, 7, 7, 17), (n, 1))
+        if len(out) not in (3, 7):
+            raise ValueError("out must be 3 tensors, or 7 with the auxiliary targets")
+        shapes = tuple((n,) + shape for shape in SampleStore._SHAPES[:len(out)])
         for t, shape in zip(out, shapes):
             if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()):
                 raise ValueError("out must be contiguous float32 GPU tensors of shapes %r" % (shapes,))
         # (torch's default stream is the null stream, handle 0 — which the C entry points read as "the store's own stream,
         # and wait": hipStreamLegacy names the null stream itself, so the call is ordered behind torch's work and returns)
-        return [ctypes.c_void_p(t.data_ptr()) for t in out], torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY
-
-    @staticmethod
-    def _aux_pointers(out, n):
-        import torch
-        shapes = ((n, 7, 7, 4), (n, 7, 7, 17), (n, 1), (n, 7, 7), (n, 1), (n, 7, 7, 17), (n, 2))
-        if len(out) != len(shapes):
-            raise ValueError("out must be %d tensors" % len(shapes))
-        for t, shape in zip(out, shapes):
-            if not (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()):
-                raise ValueError("out must be contiguous float32 GPU tensors of shapes %r" % (shapes,))
-        return [ctypes.c_void_p(t.data_ptr()) for t in out], torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY
+        return CSampleOutputs(*[t.data_ptr() for t in out]), torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY
 
     def gather(self, draws, value_blend=0.0, out=None, aux=False):
         """The minibatch of the draws (n, 3) of (game, ply, symmetry), enqueued on torch's current stream; `out`: the three
-        tensors to write (fresh ones by default).  A draw on a bad ply raises the host pipeline's AssertionError.
-        aux: seven tensors, the auxiliary targets behind the three (aux_outputs; azh_samples_gather_aux)."""
-        if aux:
-            return self._gather_aux(draws, value_blend, out)
+        tensors to write, or seven: the auxiliary targets behind the three (fresh ones by default: outputs, or aux_outputs
+        under aux).  A draw on a bad ply raises the host pipeline's AssertionError."""
         draws = np.ascontiguousarray(draws, dtype=np.int32).reshape(-1, 3)
-        out = self.outputs(len(draws)) if out is None else out
+        out = self.outputs(len(draws), count=7 if aux else 3) if out is None else out
         ptrs, stream = self._pointers(out, len(draws))
-        rc = load().azh_samples_gather(self.h, len(draws), _ptr(draws), float(value_blend), *ptrs, stream)
-        if rc == -2:
-            raise AssertionError("policy target does not sum to one")
-        check(rc)
-        return out
-
-    def _gather_aux(self, draws, value_blend, out):
-        draws = np.ascontiguousarray(draws, dtype=np.int32).reshape(-1, 3)
-        out = self.aux_outputs(len(draws)) if out is None else out
-        ptrs, stream = self._aux_pointers(out, len(draws))
-        rc = load().azh_samples_gather_aux(self.h, len(draws), _ptr(draws), float(value_blend), *ptrs, stream)
+        rc = load().azh_samples_gather(self.h, len(draws), _ptr(draws), float(value_blend), ctypes.byref(ptrs), stream)
         if rc == -2:
             raise AssertionError("policy target does not sum to one")
         check(rc)
@@ -1353,26 +1308,16 @@ class SampleStore:
 
     def draw_gather(self, n, seed, step, first_game, n_games, value_blend=0.0, out=None, draws_out=None, aux=False):
         """A minibatch of n samples drawn on the device from games [first_game, first_game + n_games) with Philox keyed by
-        `seed` at counter `step`; draws_out: an (n, 4) int32 GPU tensor that receives (game, ply, symmetry, attempts).
-        aux: seven tensors, as gather (azh_samples_draw_gather_aux)."""
+        `seed` at counter `step`; out, aux: as gather; draws_out: an (n, 4) int32 GPU tensor that receives (game, ply,
+        symmetry, attempts)."""
         import torch
-        if aux:
-            out = self.aux_outputs(n) if out is None else out
-            ptrs, stream = self._aux_pointers(out, n)
-        else:
-            out = self.outputs(n) if out is None else out
-            ptrs, stream = self._pointers(out, n)
+        out = self.outputs(n, count=7 if aux else 3) if out is None else out
+        ptrs, stream = self._pointers(out, n)
         if draws_out is not None and not (draws_out.is_cuda and draws_out.dtype == torch.int32 and
                                           tuple(draws_out.shape) == (n, 4) and draws_out.is_contiguous()):
             raise ValueError("draws_out must be a contiguous int32 GPU tensor of shape (n, 4)")
-        if aux:
-            check(load().azh_samples_draw_gather_aux(self.h, int(n), int(seed), int(step), int(first_game), int(n_games),
-                                                     float(value_blend), *ptrs,
-                                                     ctypes.c_void_p(draws_out.data_ptr()) if draws_out is not None else None,
-                                                     stream))
-            return out
         check(load().azh_samples_draw_gather(self.h, int(n), int(seed), int(step), int(first_game), int(n_games),
-                                             float(value_blend), *ptrs,
+                                             float(value_blend), ctypes.byref(ptrs),
                                              ctypes.c_void_p(draws_out.data_ptr()) if draws_out is not None else None, stream))
         return out
 

@@ -752,14 +752,28 @@ enum { AZH_SAMPLES_PLY_PASS = 1, AZH_SAMPLES_PLY_FULL = 2, AZH_SAMPLES_PLY_BAD =
 enum { AZH_SAMPLES_GAME_HAS_FULL = 1 << 8, AZH_SAMPLES_GAME_HAS_VALUES = 1 << 9 };
 int azh_samples_create(int64_t cap_games, int64_t cap_plies, int64_t cap_targets, azh_samples **out);
 void azh_samples_destroy(azh_samples *s);
-/* Appends games from host arrays: games [n_games][4] as above with the first ply counted from this call's arrays; boards
- * [n_plies][2] (x, o); ply_flags [n_plies] (PASS and FULL; BAD is found here); values [n_plies]; target_start
- * [n_plies + 1] into target_index / target_weight.  A game has 1 .. 65535 plies; result 1 or 2, or 0 for a game cut at the ply
- * limit and kept (AZH_FLAG_KEEP_UNFINISHED), which is nobody's win: z = -1 for both sides, as the host pipeline has it.  -6 when a capacity would be exceeded,
- * -2 when the arrays contradict each other: either way the store is exactly what it was. */
-int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies, const uint64_t *boards,
-                          const uint8_t *ply_flags, const double *values, const int32_t *target_start,
-                          const uint16_t *target_index, const float *target_weight);
+/* Games as host arrays, what azh_samples_add_games takes and azh_samples_pack_records fills: games [n_games][4] as above with
+ * the first ply counted from these arrays; boards [n_plies][2] (x, o); ply_flags [n_plies] (PASS and FULL; BAD is found at
+ * ingest); values [n_plies]; target_start [n_plies + 1] into target_index / target_weight [n_targets].  A game has 1 .. 65535
+ * plies; result 1 or 2, or 0 for a game cut at the ply limit and kept (AZH_FLAG_KEEP_UNFINISHED), which is nobody's win: z = -1
+ * for both sides, as the host pipeline has it.  The two optional arrays: "Walls" and "Auxiliary targets" below. */
+typedef struct azh_sample_arrays {
+    int64_t n_games, n_plies, n_targets;
+    uint32_t *games;  uint64_t *boards;  uint8_t *ply_flags;  double *values;
+    int32_t *target_start;  uint16_t *target_index;  float *target_weight;
+    uint64_t *game_blockers;            /* [n_games], or NULL: no game has walls */
+    uint64_t *game_owners;              /* [n_games][2] (x-owned, o-owned), or NULL: no game has owners */
+} azh_sample_arrays;
+/* The DEVICE arrays a minibatch is written into: features [n][7][7][4], policy [n][7][7][17], value [n][1], and either all
+ * four or none of ownership [n][7][7], score [n][1], reply [n][7][7][17], aux_weight [n][2] ("Auxiliary targets" below). */
+typedef struct azh_sample_outputs {
+    float *features, *policy, *value;
+    float *ownership, *score, *reply, *aux_weight; /* all four NULL: no auxiliary targets */
+} azh_sample_outputs;
+/* Appends the games of `a`.  -1 for a missing array, -2 when the arrays contradict each other (n_targets is not
+ * target_start[n_plies] among it) or walls or owners are refused (below), -6 when a capacity would be exceeded: every time
+ * the store is exactly what it was. */
+int azh_samples_add_games(azh_samples *s, const azh_sample_arrays *a);
 /* Ring records, one after the other as azh_engine_staged_records returns them, -> the arrays azh_samples_add_games takes,
  * holding what parsing each game's own line would give: the targets in the order of the line's sorted keys, weight
  * (float)((double)count / (double)total) over the written counts (0 when total is 0; the same rule for the Gumbel search's
@@ -767,26 +781,35 @@ int azh_samples_add_games(azh_samples *s, int64_t n_games, const uint32_t *games
  * kind & 16) under kind & 4, random_ply + 1 from header word 6, indices by the engine's own move -> policy index map.  Each
  * record must pass the walk azh_format_record_json makes; the markers of dropped games (kind & 1) and games begun at a loaded
  * position (kind & 3 == 2) have no line and are skipped; anything else — a record cut short, a word count that does not
- * match, a target that is no clone and no jump — returns -2 with nothing written.  counts [3]: on entry the room of the
- * arrays in games, plies, targets; on return what the records hold.  With games == NULL only the counts are returned.
- * -6 when an array is too small.  Host code only, usable without a device. */
-int azh_samples_pack_records(const uint32_t *rec, int64_t words, int64_t *counts, uint32_t *games, uint64_t *boards,
-                             uint8_t *ply_flags, double *values, int32_t *target_start, uint16_t *target_index,
-                             float *target_weight);
-/* azh_samples_pack_records followed by azh_samples_add_games: -2 and -6 add nothing. */
-int azh_samples_add_records(azh_samples *s, const uint32_t *rec, int64_t words);
+ * match, a target that is no clone and no jump — returns -2 with nothing written.
+ * Walls come one of two ways: `blockers`, the mask of the engine that wrote the records, with record_masks NULL; or, for an
+ * engine with a start pool (azh_engine_set_start_pool), record_masks [n_masks], one mask per record of the buffer in its
+ * order — the markers of dropped and loaded games included — each azh_engine_uid_blockers of the record's uid, with `blockers`
+ * 0.  A non-zero `blockers` beside record_masks is -1; n_masks other than the number of records is -2.
+ * aux != 0: each game's owners are computed too ("Auxiliary targets").
+ * out: n_games, n_plies, n_targets hold the room of the arrays on entry and what the records hold on return; with
+ * out->games == NULL only these counts are returned; game_blockers and game_owners are filled where they are not NULL (the
+ * owners only under aux).  -6 when an array is too small.  Host code only, usable without a device. */
+int azh_samples_pack_records(const uint32_t *rec, int64_t words, uint64_t blockers, const uint64_t *record_masks,
+                             int64_t n_masks, int aux, azh_sample_arrays *out);
+/* azh_samples_pack_records followed by azh_samples_add_games, the walls going along when `blockers` or record_masks is
+ * given and the owners under aux: -1, -2 and -6 add nothing. */
+int azh_samples_add_records(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers,
+                            const uint64_t *record_masks, int64_t n_masks, int aux);
 /* out [4]: games, plies, targets, bad plies that are no passes. */
 int azh_samples_counts(const azh_samples *s, int64_t *out);
 /* The host mirror: games [games][4] (first ply counted from the store's first), ply_flags [plies]. */
 int azh_samples_mirror(const azh_samples *s, uint32_t *games, uint8_t *ply_flags);
-/* A minibatch for host draws [n][3] of (game, ply, symmetry) into three DEVICE arrays.  Every draw is checked first: out of
- * range or a pass -> -1, a bad ply -> -2 ("policy target does not sum to one"), nothing launched.  `stream` is a
+/* A minibatch for host draws [n][3] of (game, ply, symmetry) into the arrays of `out`: with the four auxiliary arrays the
+ * kernel that also writes them runs, for the same draws the same bytes in features, policy and value (a store in which no
+ * game has owners is served: final weight 0 everywhere, reply as defined); with one to three of them -1.  Every draw is
+ * checked first: out of range or a pass -> -1, a bad ply -> -2 ("policy target does not sum to one"), nothing launched.  `stream` is a
  * hipStream_t as a pointer-sized integer: the call enqueues on it and returns; the draws travel through pinned staging the
  * store owns, two buffers taken in turn, so the next call does not wait for this one.  stream = 0: the store's own stream,
  * and the call returns after completion — that stream is not ordered against any other, the null stream included: a caller
  * whose work runs on the null stream passes hipStreamLegacy (1), as link.SampleStore does for torch's default stream. */
-int azh_samples_gather(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features, float *policy,
-                       float *value, uintptr_t stream);
+int azh_samples_gather(azh_samples *s, int n, const int32_t *draws, double value_blend, const azh_sample_outputs *out,
+                       uintptr_t stream);
 /* The same with the draws made on the device.  Sample i makes at most 64 attempts; attempt a takes one Philox4x32-10 block
  * v keyed by `seed` with counter (step, i, a, 8) — stream 8 is drawn from by nothing else:
  *   game g = first_game + ((u64)v[0] * n_games >> 32);  c = the game's candidate plies: all of them, or the FULL ones of a
@@ -797,12 +820,13 @@ int azh_samples_gather(azh_samples *s, int n, const int32_t *draws, double value
  * whose 64 attempts all fail is written as zeros and counted (azh_samples_status).  draws_out: NULL, or a DEVICE array
  * [n][4] of (game, ply, symmetry, attempts used); (-1, -1, -1, 64) for a failed sample. */
 int azh_samples_draw_gather(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game, int64_t n_games,
-                            double value_blend, float *features, float *policy, float *value, int32_t *draws_out,
-                            uintptr_t stream);
+                            double value_blend, const azh_sample_outputs *out, int32_t *draws_out, uintptr_t stream);
 /* One sample's draw restated from mirror arrays (games [total_games][4], ply_flags with BAD set where it applies) -> out [4]
- * as a row of draws_out.  Host arithmetic only: no device, no store. */
+ * as a row of draws_out.  candidates and cum both NULL: the uniform ply draw above; both given (azh_samples_ply_cum's
+ * mirrors): the weighted one ("Weighted ply draws" below); one of them: -1.  Host arithmetic only: no device, no store. */
 int azh_samples_draw(uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
-                     const uint32_t *games, int64_t total_games, const uint8_t *ply_flags, int32_t *out);
+                     const uint32_t *games, int64_t total_games, const uint8_t *ply_flags, const uint16_t *candidates,
+                     const uint32_t *cum, int32_t *out);
 /* Waits for the device and returns how many samples of azh_samples_draw_gather have failed since the store was created. */
 int azh_samples_status(azh_samples *s, int64_t *failed);
 
@@ -810,27 +834,13 @@ int azh_samples_status(azh_samples *s, int64_t *failed);
  * that came without one, in a device array [cap_games] that is allocated when the first game with walls arrives: until then
  * the kernels are handed a null pointer and every output is what it was.  With a mask, feature plane 3 of a sample holds 1.0
  * on the wall cells, under the sample's symmetry like planes 1 and 2 (training.make_minibatch_reference with an entry's
- * "blockers").  The siblings below take the masks; the calls above are the siblings with no walls.
- *  - azh_samples_add_games_blockers: game_blockers [n_games], or NULL.  -2, nothing added, for a mask with bits beyond the 49
- *    cells and for a game one of whose plies has a stone on a wall cell (the game is named).
- *  - azh_samples_pack_records_blockers / azh_samples_add_records_blockers: `blockers` is the mask of the engine that wrote the
- *    records; game_blockers [games] (or NULL) receives it per game.  The same two refusals, before anything is written.
+ * "blockers").
+ *  - azh_samples_add_games: -2, nothing added, for a mask of game_blockers with bits beyond the 49 cells and for a game one of
+ *    whose plies has a stone on a wall cell (the game is named).
+ *  - azh_samples_pack_records / azh_samples_add_records: the same two refusals for `blockers` and for every mask of
+ *    record_masks, before anything is written; game_blockers receives each game's mask.
  *  - azh_samples_game_blockers: the host mirror of the masks, blockers [games]. */
-int azh_samples_add_games_blockers(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies,
-                                   const uint64_t *boards, const uint8_t *ply_flags, const double *values,
-                                   const int32_t *target_start, const uint16_t *target_index, const float *target_weight,
-                                   const uint64_t *game_blockers);
-int azh_samples_pack_records_blockers(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts, uint32_t *games,
-                                      uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
-                                      uint16_t *target_index, float *target_weight, uint64_t *game_blockers);
-int azh_samples_add_records_blockers(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers);
 int azh_samples_game_blockers(const azh_samples *s, uint64_t *blockers);
-/* azh_samples_add_records_blockers (aux = 0) / azh_samples_add_records_aux (aux != 0) for the records of an engine with a start
- * pool (azh_engine_set_start_pool): masks [n_masks], one per record of the buffer in its order — the markers of dropped and
- * loaded games included — each azh_engine_uid_blockers of the record's uid.  The same refusals, before anything is written; -2
- * too when n_masks is not the number of records. */
-int azh_samples_add_records_masks(azh_samples *s, const uint32_t *rec, int64_t words, const uint64_t *masks, int64_t n_masks,
-                                  int aux);
 
 /* ------------------------------------------------------------------ policy surprise weighting
  * (an extension of the store; with none of these called, every launch and every draw above is what it was.)
@@ -865,15 +875,14 @@ int azh_samples_set_surprise_chunk(azh_samples *s, int plies);
 /* ms [2]: HIP-event milliseconds of the last azh_samples_surprise, summed over its chunks: {board packing and tower,
  * surprise kernel}. */
 int azh_samples_surprise_ms(const azh_samples *s, float *ms);
-/* The legal moves of a position as policy indices in the order above -> index_out [up to 833], *n_out.  Host arithmetic. */
-int azh_samples_legal(uint64_t mover, uint64_t opponent, uint16_t *index_out, int32_t *n_out);
-/* The same on a board with walls: no move goes onto a cell of `blockers`. */
-int azh_samples_legal_blockers(uint64_t mover, uint64_t opponent, uint64_t blockers, uint16_t *index_out, int32_t *n_out);
+/* The legal moves of a position as policy indices in the order above -> index_out [up to 833], *n_out; no move goes onto a
+ * cell of `blockers` (0: no walls).  Host arithmetic. */
+int azh_samples_legal(uint64_t mover, uint64_t opponent, uint64_t blockers, uint16_t *index_out, int32_t *n_out);
 /* One ply's surprise restated on the host: *kl_out is the stored value (the "stored as 0" rule applied), *illegal_out (or
  * NULL) this ply's count.  Host arithmetic only. */
 int azh_samples_surprise_host(const float *logits833, const uint16_t *legal_index, int n_legal, const uint16_t *target_index,
                               const float *target_weight, int n_targets, float *kl_out, int32_t *illegal_out);
-/* The same with `legal` found here: azh_samples_legal_blockers of the position. */
+/* The same with `legal` found here: azh_samples_legal of the position. */
 int azh_samples_surprise_host_blockers(const float *logits833, uint64_t mover, uint64_t opponent, uint64_t blockers,
                                        const uint16_t *target_index, const float *target_weight, int n_targets, float *kl_out,
                                        int32_t *illegal_out);
@@ -894,12 +903,8 @@ int azh_samples_set_ply_weights(azh_samples *s, int64_t first_game, int64_t n_ga
 int azh_samples_clear_ply_weights(azh_samples *s);
 /* The draw's mirror: candidates [plies] (the k-th candidate of game g at [first ply + k]), candidate_count [games], cum
  * [plies] (valid below each game's count; 65536 (k + 1) throughout when the store holds no weights), *present: 1 when it
- * does. */
+ * does.  azh_samples_draw restates the weighted draw from candidates and cum. */
 int azh_samples_ply_cum(const azh_samples *s, uint16_t *candidates, uint32_t *candidate_count, uint32_t *cum, int32_t *present);
-/* azh_samples_draw with the weighted ply choice, from mirror arrays.  Host arithmetic only: no device, no store. */
-int azh_samples_draw_weighted(uint64_t seed, uint32_t step, uint32_t sample, int64_t first_game, int64_t n_games,
-                              const uint32_t *games, int64_t total_games, const uint8_t *ply_flags,
-                              const uint16_t *candidates, const uint32_t *cum, int32_t *out);
 
 /* ------------------------------------------------------------------ auxiliary targets
  * (an extension of the store; with none of these called, every byte written above is what it was.)  Three further training
@@ -946,37 +951,20 @@ int azh_samples_draw_weighted(uint64_t seed, uint32_t step, uint32_t sample, int
  * walls `blockers`, and returns the owners of the position reached in owners_out [2] (x-owned, o-owned) and its result in
  * *result_out (0, with owners 0, when it is not terminal).  -2 for a move that is not legal there — a pass with a move
  * available, a source that is not the mover's, a destination that is not empty, a wrong distance, a stone or destination on a
- * wall — found with the move list of azh_samples_legal_blockers, and for the freak board above. */
+ * wall — found with the move list of azh_samples_legal, and for the freak board above. */
 int azh_samples_final_owners(uint64_t x, uint64_t o, uint64_t blockers, int o_to_move, uint32_t move, uint64_t *owners_out,
                              int32_t *result_out);
-/* azh_samples_add_games_blockers with game_owners [n_games][2] (x-owned, o-owned), or NULL: none has owners.  The store keeps
- * them in a device array [cap_games][2] that is allocated when the first game with non-zero owners arrives.  -2, store
- * unchanged, the game named, for: overlapping masks; bits on walls or beyond the 49 cells; non-zero masks that leave a non-wall
- * cell unowned; a margin that contradicts the result. */
-int azh_samples_add_games_aux(azh_samples *s, int64_t n_games, const uint32_t *games, int64_t n_plies, const uint64_t *boards,
-                              const uint8_t *ply_flags, const double *values, const int32_t *target_start,
-                              const uint16_t *target_index, const float *target_weight, const uint64_t *game_blockers,
-                              const uint64_t *game_owners);
-/* The check azh_samples_add_games_aux makes of one game's owners against its walls and its recorded result, by itself: 0, or -2
+/* azh_samples_add_games with game_owners: the store keeps them in a device array [cap_games][2] that is allocated when the
+ * first game with non-zero owners arrives.  -2, store unchanged, the game named, for: overlapping masks; bits on walls or
+ * beyond the 49 cells; non-zero masks that leave a non-wall cell unowned; a margin that contradicts the result.
+ * azh_samples_check_owners: that check of one game's owners against its walls and its recorded result, by itself: 0, or -2
  * with the reason in azh_last_error.  Masks that are both 0 pass.  Host arithmetic only: no device, no store. */
 int azh_samples_check_owners(uint64_t own_x, uint64_t own_o, uint64_t blockers, uint32_t result);
-/* azh_samples_pack_records_blockers / azh_samples_add_records_blockers that also compute each game's owners:
- * azh_samples_final_owners of the last ply's boards and move word with `blockers`, into game_owners [games][2] (or NULL).  A
- * record whose last move is not legal at its last board is -2, with nothing written (also when only the counts are asked for). */
-int azh_samples_pack_records_aux(const uint32_t *rec, int64_t words, uint64_t blockers, int64_t *counts, uint32_t *games,
-                                 uint64_t *boards, uint8_t *ply_flags, double *values, int32_t *target_start,
-                                 uint16_t *target_index, float *target_weight, uint64_t *game_blockers, uint64_t *game_owners);
-int azh_samples_add_records_aux(azh_samples *s, const uint32_t *rec, int64_t words, uint64_t blockers);
-/* The host mirror of the owners, owners [games][2]. */
+/* azh_samples_pack_records / azh_samples_add_records under aux: each game's owners are azh_samples_final_owners of its last
+ * ply's boards and move word with the record's walls.  A record whose last move is not legal at its last board is -2, with
+ * nothing written (also when only the counts are asked for).
+ * azh_samples_game_owners: the host mirror of the owners, owners [games][2]. */
 int azh_samples_game_owners(const azh_samples *s, uint64_t *owners);
-/* azh_samples_gather / azh_samples_draw_gather with four more DEVICE arrays: the same draw checks, pinned staging, stream
- * contract and error codes, and for the same draws the same bytes in features, policy and value (and draws_out).  A store in
- * which no game has owners is served: final weight 0 everywhere, reply as defined. */
-int azh_samples_gather_aux(azh_samples *s, int n, const int32_t *draws, double value_blend, float *features, float *policy,
-                           float *value, float *ownership, float *score, float *reply, float *aux_weight, uintptr_t stream);
-int azh_samples_draw_gather_aux(azh_samples *s, int n, uint64_t seed, uint32_t step, int64_t first_game, int64_t n_games,
-                                double value_blend, float *features, float *policy, float *value, float *ownership,
-                                float *score, float *reply, float *aux_weight, int32_t *draws_out, uintptr_t stream);
 
 /* ------------------------------------------------------------------ reference ABI
  * The four symbols link.py:6-32 binds (cpp/self_play_client.cpp:683-749), with

@@ -180,7 +180,7 @@ def scattered(arrays, ply, s):
 
 def check_edges_of_the_wave_for_the_reply_scatter():
     counts = [2, 1, 63, 64, 65, 833]
-    arrays = link.AuxSampleArrays(*hand_built(counts, [0] * 6))
+    arrays = link.SampleArrays(*hand_built(counts, [0] * 6), owners=np.zeros((1, 2), np.uint64))
     store = store_of(arrays)
     assert store.counts()["bad_plies"] == 0
     _, policy_to = training._symmetry_tables()
@@ -204,9 +204,11 @@ def check_edges_of_the_wave_for_the_reply_scatter():
 
 def check_reply_absent():
     # no "full": ply 1 is a pass, ply 3 is bad (its weights sum to a half), ply 4 is the last
-    plain = link.AuxSampleArrays(*hand_built([3, 0, 5, 4, 6], [0, PASS, 0, 0, 0], weights=[1, 1, 1, 0.5, 1]))
+    plain = link.SampleArrays(*hand_built([3, 0, 5, 4, 6], [0, PASS, 0, 0, 0], weights=[1, 1, 1, 0.5, 1]),
+                              owners=np.zeros((1, 2), np.uint64))
     # "full": plies 0, 2 and 3 were searched in full
-    capped = link.AuxSampleArrays(*hand_built([3, 4, 5, 6], [FULL, 0, FULL, FULL], game_word=2 | link.SAMPLES_GAME_HAS_FULL))
+    capped = link.SampleArrays(*hand_built([3, 4, 5, 6], [FULL, 0, FULL, FULL], game_word=2 | link.SAMPLES_GAME_HAS_FULL),
+                               owners=np.zeros((1, 2), np.uint64))
     for arrays, draws, present in ((plain, [0, 2, 4], [0, 0, 0]), (capped, [0, 1, 2, 3], [0, 1, 1, 0])):
         store = store_of(arrays)
         got = host(store.gather([(0, p, 5) for p in draws], aux=True))

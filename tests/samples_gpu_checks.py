@@ -2,6 +2,7 @@
 torch's streams, so torch must be imported before the library is loaded (link.require_torch_runtime) — in a pytest process
 that has run other device tests it is the other way round.  `python -m tests.samples_gpu_checks OUT.json` runs every check
 and writes {name: "ok" | traceback}; after a check that ends in a device error nothing more is run."""
+import ctypes
 import json
 import random
 import sys
@@ -11,7 +12,7 @@ import numpy as np
 import torch
 
 from ataxxzero_amd import link, model, training
-from tests import helpers
+from tests import aux_fixtures, helpers
 from tests.samples_fixtures import MOVES
 
 F32 = np.float32
@@ -345,8 +346,48 @@ def check_bad_ply():
     store.close()
 
 
+def check_argument_refusals():
+    """One to three of the four auxiliary outputs: -1, nothing launched, and the calls that follow are a fresh store's; a target
+    count that is not where target_start ends: -2, nothing added."""
+    arrays = link.entries_to_arrays([aux_fixtures.cut(aux_fixtures.walled_games()[0][0], 2)], aux=True)
+    assert len(arrays.games) == 1 and len(arrays.ply_flags) == 2 and 2 <= len(arrays.target_index) <= 24
+    fresh, store = link.SampleStore(2, 4, 48), link.SampleStore(2, 4, 48)
+    fresh.add_arrays(arrays)
+    store.add_arrays(arrays)
+    draws = np.array([[0, 0, 5]], dtype=np.int32)
+    want = [host(fresh.gather(draws)), host(fresh.gather(draws, aux=True)), host(fresh.draw_gather(1, 9, 0, 0, 1)),
+            host(fresh.draw_gather(1, 9, 0, 0, 1, aux=True))]
+    assert want[1][6].tolist() == [[0.0, 1.0]] and want[1][5].any() and want[0][1].any()     # (cut short: no owners; a reply)
+    out = store.aux_outputs(1)
+    for t in out:
+        t.fill_(7.0)
+    whole, stream = store._pointers(out, 1)
+    lib = link.load()
+    for given in ((3,), (4,), (5,), (6,), (3, 4), (4, 6), (3, 4, 5), (4, 5, 6)):
+        part = link.CSampleOutputs(*[getattr(whole, name) if k < 3 or k in given else None
+                                     for k, (name, _) in enumerate(link.CSampleOutputs._fields_)])
+        assert lib.azh_samples_gather(store.h, 1, draws.ctypes.data, 0.0, ctypes.byref(part), stream) == -1, given
+        assert lib.azh_samples_draw_gather(store.h, 1, 9, 0, 0, 1, 0.0, ctypes.byref(part), None, stream) == -1, given
+    torch.cuda.synchronize()
+    assert all(bool((t == 7.0).all()) for t in out) and store.status() == 0      # nothing was launched
+    got = [host(store.gather(draws)), host(store.gather(draws, aux=True)), host(store.draw_gather(1, 9, 0, 0, 1)),
+           host(store.draw_gather(1, 9, 0, 0, 1, aux=True))]
+    for g, w in zip(got, want):
+        assert len(g) == len(w) and all(x.tobytes() == y.tobytes() for x, y in zip(g, w))
+    counts = store.counts()
+    for off in (-1, 1):
+        c = arrays.c_arrays()
+        c.n_targets += off
+        assert lib.azh_samples_add_games(store.h, ctypes.byref(c)) == -2, off
+        assert store.counts() == counts
+    store.add_arrays(arrays)                                 # and the arrays as they are go in
+    assert store.counts()["games"] == 2
+    fresh.close()
+    store.close()
+
+
 CHECKS = [check_reference_parity, check_every_index_under_every_symmetry, check_edges_of_the_wave, check_the_record_path,
-          check_device_draws, check_stream_and_reuse, check_capacity, check_bad_ply]
+          check_device_draws, check_stream_and_reuse, check_capacity, check_bad_ply, check_argument_refusals]
 
 
 def main(path):

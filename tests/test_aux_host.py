@@ -180,7 +180,7 @@ def test_record_path_equals_line_path():
         packed = link.pack_records(np.concatenate(recs), mask, aux=True)
         lines = [json.loads(link.format_record_json(r, blockers=mask if mask else None)) for r in recs]
         from_lines = link.entries_to_arrays(lines, aux=True)
-        assert isinstance(packed, link.AuxSampleArrays) and packed.owners.dtype == np.uint64 and packed.owners.shape == (3, 2)
+        assert packed.owners is not None and packed.owners.dtype == np.uint64 and packed.owners.shape == (3, 2)
         assert packed.owners.tobytes() == from_lines.owners.tobytes()
         assert packed.owners[:2].all() and not packed.owners[2].any()
         for name in link.SampleArrays.__slots__:                      # and the rest is what it is without aux
@@ -188,7 +188,7 @@ def test_record_path_equals_line_path():
             assert getattr(packed, name).tobytes() == plain.tobytes() == getattr(from_lines, name).tobytes(), name
         for (e, _), row in zip(games, packed.owners):
             assert tuple(int(v) for v in row) == ar.entry_owners(e)[:2]
-    assert not hasattr(link.pack_records(np.concatenate(recs), mask), "owners")
+    assert link.pack_records(np.concatenate(recs), mask).owners is None
 
 
 def test_a_record_with_an_illegal_last_move():

@@ -1,4 +1,4 @@
-"""The auxiliary training targets on the MI355X (include/ataxxzero_hip.h, "Auxiliary targets"; azh_samples_*_aux,
+"""The auxiliary training targets on the MI355X (include/ataxxzero_hip.h, "Auxiliary targets"; azh_samples_gather,
 link.SampleStore.gather(aux=True), train.py --aux-*): ownership, score, reply and weights bit for bit those of the host
 restatement (tests/aux_reference.py), from game lines and from ring records, with host draws and with draws made on the device,
 and the three existing outputs byte for byte what the kernels without them write.

@@ -67,6 +67,10 @@ def test_bad_ply(verdicts):
     _passed(verdicts, "check_bad_ply")
 
 
+def test_argument_refusals(verdicts):
+    _passed(verdicts, "check_argument_refusals")
+
+
 @pytest.mark.parametrize("flags", [["--device-samples"], ["--device-draws"]])
 def test_train_cli_with_device_samples(tmp_path, flags):
     with open(os.path.join(GOLDEN, "train_entries.json")) as f:

@@ -1,12 +1,15 @@
 """The device-resident sample store (azh_samples_*), the parts that need no device: ring records packed into the store's
 arrays against the parse of the same games' own lines, malformed records, entries converted for the store against
 training._entry_arrays, and the device's draw restated on the oracle's Philox."""
+import ctypes
 import json
 
 import numpy as np
 import pytest
 
 from ataxxzero_amd import link, training
+from tests import aux_fixtures as afx
+from tests import walls_fixtures as wf
 from tests.samples_fixtures import (BAD, FULL, HAS_FULL, HAS_VALUES, PASS, _arrays_equal, draw_mirror, marker,
                                     random_record, restated_draw)
 
@@ -74,13 +77,12 @@ def test_malformed_records_are_refused_and_add_nothing():
     assert n_games == 3
 
     def refused(words):
-        counts = np.array([99, 9999, 99999], dtype=np.int64)
-        before = counts.copy()
         outs = [np.full(4096, 0xAB, dtype=np.uint8) for _ in range(7)]
-        rc = link.load().azh_samples_pack_records(words.ctypes.data, words.size, counts.ctypes.data,
-                                                  *[o.ctypes.data for o in outs])
+        arrays = link.CSampleArrays(99, 9999, 99999, *[o.ctypes.data for o in outs])
+        rc = link.load().azh_samples_pack_records(words.ctypes.data, words.size, 0, None, 0, 0, ctypes.byref(arrays))
         assert rc == -2, rc
-        assert (counts == before).all() and all((o == 0xAB).all() for o in outs)      # nothing written
+        assert (arrays.n_games, arrays.n_plies, arrays.n_targets) == (99, 9999, 99999)
+        assert all((o == 0xAB).all() for o in outs)                                    # nothing written
         with pytest.raises(link.AzhError):
             link.pack_records(words)
 
@@ -99,6 +101,59 @@ def test_malformed_records_are_refused_and_add_nothing():
     refused(no_move)
     junk = np.concatenate([good[0], np.array([5], dtype=np.uint32), good[1]])
     refused(junk)                                                 # a stray word between two records
+
+
+def walled_records():
+    """A game on the default walls, a dropped game's marker, a game on the asymmetric walls -> (records, a mask for each)."""
+    recs, masks = [], []
+    for uid, fen in ((0, wf.DEFAULT_FEN), (2, wf.ASYMMETRIC_FEN)):
+        entry, positions = afx.passless_games(fen, 1)[0]
+        recs.append(afx.record_of(entry, positions, uid))
+        masks.append(positions[0].masks()[2])
+    assert masks[0] and masks[1] and masks[0] != masks[1]
+    return [recs[0], marker(1), recs[1]], [masks[0], masks[0], masks[1]]
+
+
+def test_two_ways_to_give_walls_are_refused_together_and_a_wrong_mask_count_writes_nothing():
+    recs, masks = walled_records()
+    words = np.concatenate(recs)
+    pack = link.load().azh_samples_pack_records
+    for aux in (0, 1):
+        for n_masks, blockers, want in ((3, masks[0], -1), (2, 0, -2), (4, 0, -2)):
+            given = np.array(masks + [0], dtype=np.uint64)
+            outs = [np.full(1 << 16, 0xAB, dtype=np.uint8) for _ in range(9)]
+            arrays = link.CSampleArrays(99, 9999, 99999, *[o.ctypes.data for o in outs])
+            rc = pack(words.ctypes.data, words.size, blockers, given.ctypes.data, n_masks, aux, ctypes.byref(arrays))
+            assert rc == want, (aux, n_masks, rc)
+            assert (arrays.n_games, arrays.n_plies, arrays.n_targets) == (99, 9999, 99999)
+            assert all((o == 0xAB).all() for o in outs)
+    with pytest.raises(link.AzhError, match="error -2"):
+        link.pack_records(words, np.array(masks[:2], dtype=np.uint64))
+    assert len(link.pack_records(words, np.array(masks, dtype=np.uint64)).games) == 2
+
+
+@pytest.mark.parametrize("aux", [False, True])
+def test_packing_with_a_mask_per_record_is_packing_each_record_with_its_own(aux):
+    recs, masks = walled_records()
+    whole = link.pack_records(np.concatenate(recs), np.array(masks, dtype=np.uint64), aux=aux)
+    first, second = (link.pack_records(recs[k], masks[k], aux=aux) for k in (0, 2))
+    assert len(link.pack_records(recs[1], masks[1], aux=aux).games) == 0          # the marker alone: no game
+    plies, targets = len(first.ply_flags), len(first.target_index)
+    moved = second.games.copy()
+    moved[:, 0] += plies
+    want = {"games": np.concatenate([first.games, moved]),
+            "target_start": np.concatenate([first.target_start, second.target_start[1:] + targets]).astype(np.int32)}
+    if not aux:
+        assert whole.owners is None and first.owners is None and second.owners is None
+    for name in link.SampleArrays.__slots__ + (("owners",) if aux else ()):
+        got = getattr(whole, name)
+        expect = want.get(name)
+        if expect is None:
+            expect = np.concatenate([getattr(first, name), getattr(second, name)])
+        assert got.dtype == expect.dtype and got.shape == expect.shape, name
+        assert got.tobytes() == expect.tobytes(), name
+    assert whole.blockers.tolist() == [masks[0], masks[2]]
+    assert len(whole.games) == 2 and (plies, targets) != (0, 0) and (not aux or whole.owners.any())
 
 
 def test_entries_for_the_store_follow_entry_arrays():

@@ -1,5 +1,5 @@
 """Policy surprise weighting, the parts that need no device: one ply's surprise (azh_samples_surprise_host) against a float64
-restatement, the weighted draw (azh_samples_draw_weighted) against a restatement in Python integers on the oracle's Philox, and
+restatement, the weighted draw (azh_samples_draw with candidates and cum) against a restatement in Python integers on the oracle's Philox, and
 training.surprise_weights."""
 import numpy as np
 import pytest
@@ -127,6 +127,28 @@ def test_weighted_draw_equals_the_integer_restatement():
     assert link.samples_draw_weighted(SEED, 0, 0, 1, 2, games, flags, cand, cum) == (-1, -1, -1, 64)
     with pytest.raises(link.AzhError):
         link.samples_draw_weighted(SEED, 0, 0, 5, 6, games, flags, cand, cum)
+
+
+def test_the_draw_takes_candidates_and_cum_together_or_not_at_all():
+    """azh_samples_draw called as the library exports it: with one of the two mirrors it returns -1; with both its rows are the
+    weighted restatement's, with neither the uniform one's."""
+    from tests.samples_fixtures import restated_draw
+    games, flags, cand, cum = ref.build_mirror(edge_specs(np.random.default_rng(21)))
+    g_list, f_list, lists, cums = ref.per_game_lists(games, flags, cum)
+    out = np.full(4, 77, dtype=np.int32)
+
+    def draw(step, i, first, count, candidates, sums):
+        return link.load().azh_samples_draw(SEED, step, i, first, count, games.ctypes.data, len(games), flags.ctypes.data,
+                                            link._ptr(candidates), link._ptr(sums), out.ctypes.data)
+    assert draw(0, 0, 0, len(g_list), cand, None) == -1 and draw(0, 0, 0, len(g_list), None, cum) == -1
+    assert out.tolist() == [77] * 4
+    for step in range(2):
+        for i in range(100):
+            first, count = (0, len(g_list)) if step == 0 else (3, 6)
+            assert draw(step, i, first, count, cand, cum) == 0
+            assert tuple(out.tolist()) == ref.restated_weighted_draw(SEED, step, i, first, count, g_list, f_list, lists, cums)
+            assert draw(step, i, first, count, None, None) == 0
+            assert tuple(out.tolist()) == restated_draw(SEED, step, i, first, count, games, flags)
 
 
 @pytest.mark.parametrize("units", [65536, 7, 1])

@@ -1,6 +1,7 @@
 """Walls through the loop, the parts that need no device: the FEN round trip of uai.Position, the game line's "blockers" key,
 feature plane 3 in the host sample pipeline, the refusals of malformed wall lists, the record path with a mask, and the masked
 legal-move list and surprise of the store's host restatements."""
+import ctypes
 import json
 import random
 
@@ -164,11 +165,11 @@ def test_malformed_walls_are_refused_by_name(tmp_path):
     rec = _record(5, 0)
     stone = int(rec[8]) & -int(rec[8]) or 1 << 32
     for mask in (1 << 49, stone):
-        counts = np.array([9, 99, 9999], dtype=np.int64)
-        outs = [np.full(4096, 0xAB, dtype=np.uint8) for _ in range(8)]
-        rc = link.load().azh_samples_pack_records_blockers(rec.ctypes.data, rec.size, mask, counts.ctypes.data,
-                                                           *[o.ctypes.data for o in outs])
-        assert rc == -2 and counts.tolist() == [9, 99, 9999] and all((o == 0xAB).all() for o in outs)
+        outs = [np.full(4096, 0xAB, dtype=np.uint8) for _ in range(8)]       # the seven arrays and game_blockers
+        arrays = link.CSampleArrays(9, 99, 9999, *[o.ctypes.data for o in outs])
+        rc = link.load().azh_samples_pack_records(rec.ctypes.data, rec.size, mask, None, 0, 0, ctypes.byref(arrays))
+        assert rc == -2 and (arrays.n_games, arrays.n_plies, arrays.n_targets) == (9, 99, 9999)
+        assert all((o == 0xAB).all() for o in outs)
         with pytest.raises(link.AzhError):
             link.pack_records(rec, mask)
 
