@@ -471,6 +471,39 @@ __host__ __device__ inline void forced_prune_root(const float *prior, const floa
         out[j] = (j == b || n[j] == 0u) ? n[j] : forced_prune_edge(fabsf(prior[j]), W[j], n[j], N, k, c_puct, sq, S);
 }
 
+// First-play urgency and the exploration rate of the leaf-parallel search (azh_engine_set_exploration; DESIGN.md, "First-play
+// urgency and the exploration rate").  Host (azh_exploration_scores) and device (vl_select_game) share every function but the
+// wave's two sums; every f32 operation is a single IEEE one in the order written.
+// The mode is on while either knob is: fpu_reduction < 0 is FPU off, c_base == 0 the constant c_puct.
+__host__ __device__ inline bool exploration_on(float fpu_reduction, float c_base) { return fpu_reduction >= 0.0f || c_base > 0.0f; }
+// c of a node whose children hold N effective visits: AlphaZero's log((1 + N + c_base) / c_base) + c_init, or c_puct.
+__host__ __device__ inline float exploration_c(u32 N, float c_puct, float c_base, float c_init)
+{
+#pragma clang fp contract(off)
+    if (!(c_base > 0.0f))
+        return c_puct;
+    return det_logf(((float)(1u + N) + c_base) / c_base) + c_init;
+}
+// f, the Q of the node's unvisited children, from the 64-lane sums of W over all children and of P over the visited ones: the
+// node's mean score less fpu_reduction * sqrt(visited policy mass), not below 0 (a NaN becomes 0); 0 with FPU off or N == 0.
+__host__ __device__ inline float exploration_fpu(float Wsum, float Psum, u32 N, float fpu_reduction)
+{
+#pragma clang fp contract(off)
+    if (!(fpu_reduction >= 0.0f) || N == 0u)
+        return 0.0f;
+    const float qX = Wsum / (float)N;
+    const float f = qX - fpu_reduction * sqrtf(Psum);
+    return f > 0.0f ? f : 0.0f;
+}
+// Q + U of an edge of that node (puct_score's operation order; prior without its mark): with c = c_puct and f = 0 puct_score itself.
+__host__ __device__ inline float exploration_score(float prior, float W, u32 n, float sq, float c, float f)
+{
+#pragma clang fp contract(off)
+    const float q = n ? W / (float)n : f;
+    const float u = (sq / (1.0f + (float)n)) * (c * prior);
+    return u + q;
+}
+
 // Temperature of the move played (azh_engine_set_temperature; DESIGN.md, "Temperature of the move and of the root policy").
 // The fixed-point weight of a root edge with n visits when the most visited edge has exp(log_nmax) of them: (n / n_max)^(1/T)
 // in units of 2^-20, from det_logf / det_expf and one IEEE f32 division, so host and device agree to the bit and the sum of

@@ -1459,6 +1459,17 @@ struct azh_engine {
 
 static int leaf_k(const azh_engine *e) { return e->V.K > 1 ? e->V.K : 1; }
 
+static bool explores(const azh_engine *e) { return exploration_on(e->P.fpu_reduction, e->P.c_base); }
+
+// what beside K keeps the leaf-parallel kernel in force, for the errors of the one-leaf calls ("" if nothing; `joint`: " with" / " and")
+static std::string vl_beside(const azh_engine *e, const char *joint)
+{
+    if (!e->V.solver && !explores(e))
+        return "";
+    return std::string(joint) + (e->V.solver ? " the solver" : "") + (e->V.solver && explores(e) ? " and" : "") +
+           (explores(e) ? " azh_engine_set_exploration" : "");
+}
+
 // the tower for this engine's leaf batches: one board per workgroup for engines (or batches the host says are) small
 // the wall mask of every leaf slot, for the tower and k_features: null (the engine's one mask) while no pool is set
 static const unsigned long long *leaf_masks(const azh_engine *e) { return e->P.pool ? (const unsigned long long *)e->P.leaf_mask : nullptr; }
@@ -1493,11 +1504,12 @@ template <typename T> static int dev_alloc_once(azh_engine *e, T **p, size_t cou
 
 // ------------------------------------------------------------------ the search modes: who refuses whom
 //
-// Eight modes are switched between iterations, by a setter each.  What a mode cannot run beside (create-time flags and settings,
+// Nine modes are switched between iterations, by a setter each.  What a mode cannot run beside (create-time flags and settings,
 // other modes) is stated here once, and mode_refusal answers for every setter.  In words: the table "Search modes: who refuses
 // whom" of include/ataxxzero_hip.h and of DESIGN.md.
 
-enum { MODE_NONE = -1, MODE_CAP, MODE_FORCED, MODE_GUMBEL, MODE_TEMPERATURE, MODE_RESIGN, MODE_SYMMETRY, MODE_LEAF_BATCH, MODE_SOLVER };
+enum { MODE_NONE = -1, MODE_CAP, MODE_FORCED, MODE_GUMBEL, MODE_TEMPERATURE, MODE_RESIGN, MODE_SYMMETRY, MODE_LEAF_BATCH, MODE_SOLVER,
+       MODE_EXPLORATION };
 
 // Is `bb` its own image under all 8 symmetries?  (the two mirrors and the transposition generate them)
 static bool symmetry_invariant(u64 bb)
@@ -1528,6 +1540,8 @@ static const ModeInfo MODES[] = {  // (in the order of the MODE_ constants)
      AZH_FLAG_TWO_NETS | AZH_FLAG_SYMMETRY_AVG},
     {"azh_engine_set_leaf_batch", "more than one leaf per game", true, true, false, ON(e->V.K > 1), LEAF_FLAGS},
     {"azh_engine_set_solver", "the solver", false, true, false, ON(e->V.solver != 0), LEAF_FLAGS},
+    {"azh_engine_set_exploration", "first-play urgency or a growing exploration rate", true, false, false,
+     ON(exploration_on(e->P.fpu_reduction, e->P.c_base)), LEAF_FLAGS},
 };
 #undef ON
 
@@ -1536,6 +1550,8 @@ static const ModeInfo MODES[] = {  // (in the order of the MODE_ constants)
 static const int EXCLUDED[][2] = {
     {MODE_GUMBEL, MODE_CAP},    {MODE_GUMBEL, MODE_FORCED},     {MODE_GUMBEL, MODE_TEMPERATURE}, {MODE_GUMBEL, MODE_LEAF_BATCH},
     {MODE_GUMBEL, MODE_SOLVER}, {MODE_FORCED, MODE_LEAF_BATCH}, {MODE_FORCED, MODE_SOLVER},
+    // (both restate the root's PUCT with q = 0 for an unvisited edge and the constant c_puct)
+    {MODE_GUMBEL, MODE_EXPLORATION}, {MODE_FORCED, MODE_EXPLORATION},
 };
 
 // The create-time flags a mode can be refused with; of several set at once a refusal names the first one listed here.
@@ -1571,7 +1587,7 @@ static std::string mode_refusal(const azh_engine *e, int mode)
     for (const auto &f : FLAG_NAMES)
         if (e->P.flags & m.refused_flags & f.bit)
             return head + f.name;
-    if ((mode == MODE_LEAF_BATCH || mode == MODE_SOLVER) && e->P.select_budget > 0)
+    if ((mode == MODE_LEAF_BATCH || mode == MODE_SOLVER || mode == MODE_EXPLORATION) && e->P.select_budget > 0)
         return head + "select_budget > 0";
     if (mode == MODE_GUMBEL && (!(e->P.flags & AZH_FLAG_NO_REUSE) || e->P.noise_w != 0.0f))
         return "the engine must have been created with AZH_FLAG_NO_REUSE and dirichlet_weight 0 (the schedule assumes a fresh "
@@ -1628,6 +1644,7 @@ extern "C" int azh_engine_create(const azh_config *cfg, azh_engine **out)
     P.path_cap = P.node_cap;
     P.max_plies = cfg->max_plies;
     P.c_puct = cfg->c_puct;
+    P.fpu_reduction = -1.0f;  // (azh_engine_set_exploration: off)
     P.alpha = cfg->dirichlet_alpha;
     P.noise_w = cfg->dirichlet_weight;
     P.k0 = (u32)cfg->seed;
@@ -1801,7 +1818,7 @@ extern "C" int azh_engine_leaves(azh_engine *e, int32_t *need_eval, uint64_t *le
         return azh_fail(-1, "azh_engine_leaves: null engine");
     if (e->vl_active)
         return azh_fail(-2, "azh_engine_leaves: %d leaves per game%s: use azh_engine_batch_leaves", leaf_k(e),
-                        e->V.solver ? " with the solver" : "");
+                        vl_beside(e, " with").c_str());
     AZH_HIP(hipStreamSynchronize(e->stream));
     if (need_eval)
         AZH_HIP(hipMemcpy(need_eval, e->P.need_eval, (size_t)e->P.G * 4, hipMemcpyDeviceToHost));
@@ -1817,7 +1834,7 @@ extern "C" int azh_engine_leaf_features(azh_engine *e, float *out, int32_t *game
         return azh_fail(-1, "azh_engine_leaf_features: null argument");
     if (e->vl_active)
         return azh_fail(-2, "azh_engine_leaf_features: not available with %d leaves per game%s", leaf_k(e),
-                        e->V.solver ? " and the solver" : "");
+                        vl_beside(e, " and").c_str());
     AZH_HIP(hipStreamSynchronize(e->stream));
     int n = 0;
     AZH_HIP(hipMemcpy(&n, e->P.leaf_count, 4, hipMemcpyDeviceToHost));
@@ -1862,7 +1879,7 @@ extern "C" int azh_engine_set_evals(azh_engine *e, const float *logits, const fl
         return azh_fail(-1, "azh_engine_set_evals: null argument");
     if (e->vl_active)
         return azh_fail(-2, "azh_engine_set_evals: %d leaves per game%s: use azh_engine_set_batch_evals", leaf_k(e),
-                        e->V.solver ? " with the solver" : "");
+                        vl_beside(e, " with").c_str());
     AZH_HIP(hipMemcpyAsync(e->P.logits, logits, (size_t)e->P.G * AZH_POLICY_SIZE * 4, hipMemcpyHostToDevice, e->stream));
     AZH_HIP(hipMemcpyAsync(e->P.values, values, (size_t)e->P.G * 4, hipMemcpyHostToDevice, e->stream));
     AZH_HIP(hipStreamSynchronize(e->stream));
@@ -2037,7 +2054,7 @@ extern "C" int azh_engine_tree_stamps(azh_engine *e, azh_net *net, int dtype, ui
         return azh_fail(-1, "azh_engine_tree_stamps: null argument");
     if (e->vl_active)
         return azh_fail(-2, "azh_engine_tree_stamps: not available with %d leaves per game%s", leaf_k(e),
-                        e->V.solver ? " and the solver" : "");
+                        vl_beside(e, " and").c_str());
     AZH_TRY(dev_alloc_once(e, &e->P.stamps, (size_t)e->P.G * TREE_STAMPS));
     AZH_HIP(hipMemsetAsync(e->P.stamps, 0, (size_t)e->P.G * TREE_STAMPS * 8, e->stream));
     e->stamp_next = true;
@@ -2051,12 +2068,17 @@ extern "C" int azh_engine_tree_stamps(azh_engine *e, azh_net *net, int dtype, ui
 }
 
 // Leaf-parallel search: K leaves per game and iteration, spread by a virtual loss of `virtual_loss` visits
-// (vl_search.h), and the solver on top of it.  k_vl_tree and the G K-slot buffers are in force while K > 1 or the solver is
-// on; K = 1 without the solver is the one-leaf search and its kernels.  `who`: the calling entry point, for its errors.
-static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, bool solver, const char *who)
+// (vl_search.h), and the solver and the exploration mode on top of it.  k_vl_tree and the G K-slot buffers are in force while
+// K > 1 or the solver or the exploration mode is on; K = 1 without either is the one-leaf search and its kernels.  `who`: the
+// calling entry point, for its errors.  `explore`: null (the exploration mode stays as it is), or the three values of
+// azh_engine_set_exploration, which are the call's request then.
+static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, bool solver, const char *who,
+                         const float *explore = nullptr)
 {
-    const bool want = leaves_per_game > 1 || solver;
-    AZH_TRY(mode_request(e, who, leaves_per_game > 1 ? MODE_LEAF_BATCH : solver ? MODE_SOLVER : MODE_NONE));
+    const bool explore_on = explore ? exploration_on(explore[0], explore[1]) : explores(e);
+    const bool want = leaves_per_game > 1 || solver || explore_on;
+    AZH_TRY(mode_request(e, who, explore ? (explore_on ? MODE_EXPLORATION : MODE_NONE)
+                                 : leaves_per_game > 1 ? MODE_LEAF_BATCH : solver ? MODE_SOLVER : MODE_NONE));
     EngineParams &P = e->P;
     const size_t n = (size_t)P.G * (size_t)leaves_per_game;
     if (want && (int)n > e->vl_slots_cap) {
@@ -2080,6 +2102,8 @@ static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, b
             e->g_leaves.write(P);
             e->V.K = 1;
             e->V.solver = 0;
+            P.fpu_reduction = -1.0f;
+            P.c_base = P.c_init = 0.0f;
             e->vl_active = false;
             e->vl_slots_cap = 0;
             return rc;
@@ -2091,6 +2115,11 @@ static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, b
     e->V.K = leaves_per_game;
     e->V.vl = virtual_loss;
     e->V.solver = solver ? 1 : 0;
+    if (explore) {
+        P.fpu_reduction = explore[0] >= 0.0f ? explore[0] : -1.0f;
+        P.c_base = explore[1];
+        P.c_init = explore[1] > 0.0f ? explore[2] : 0.0f;  // (ignored with the constant c)
+    }
     e->vl_active = want;
     return 0;
 }
@@ -2113,6 +2142,56 @@ extern "C" int azh_engine_set_solver(azh_engine *e, int on)
     if (!e)
         return azh_fail(-1, "azh_engine_set_solver: null engine");
     return set_leaf_mode(e, leaf_k(e), e->V.vl, on != 0, "azh_engine_set_solver");
+}
+
+// First-play urgency (fpu_reduction >= 0) and the exploration rate that grows with log N (c_base > 0) in the leaf-parallel
+// kernel; while either is on every K — 1 included — runs through k_vl_tree, as under the solver.  Definition: the header and
+// DESIGN.md.  Between iterations only.
+extern "C" int azh_engine_set_exploration(azh_engine *e, float fpu_reduction, float c_base, float c_init)
+{
+    if (!e)
+        return azh_fail(-1, "azh_engine_set_exploration: null engine");
+    if (!std::isfinite(fpu_reduction) || !std::isfinite(c_base) || !std::isfinite(c_init) || c_base < 0.0f || c_init < 0.0f)
+        return azh_fail(-2, "azh_engine_set_exploration: need finite arguments, c_base >= 0 and c_init >= 0");
+    const float explore[3] = {fpu_reduction, c_base, c_init};
+    return set_leaf_mode(e, leaf_k(e), e->V.vl, e->V.solver != 0, "azh_engine_set_exploration", explore);
+}
+
+// The three values in force: out [3] = fpu_reduction (-1: off), c_base (0: the constant c_puct), c_init.
+extern "C" int azh_engine_exploration(const azh_engine *e, float *out)
+{
+    if (!e || !out)
+        return azh_fail(-1, "azh_engine_exploration: bad argument");
+    out[0] = e->P.fpu_reduction;
+    out[1] = e->P.c_base;
+    out[2] = e->P.c_init;
+    return 0;
+}
+
+// One node's M scores under the rule of azh_engine_set_exploration, from the functions vl_select_game uses and the 64-lane
+// sums restated on the host (gumbel_lane_sum).  Host arithmetic only.
+extern "C" int azh_exploration_scores(const float *prior, const float *W, const uint32_t *n, int M, float c_puct, float fpu_reduction,
+                                      float c_base, float c_init, float *scores_out)
+{
+    if (!prior || !W || !n || !scores_out || M < 1 || M > MAX_MOVES)
+        return azh_fail(-1, "azh_exploration_scores: bad argument (need every array and 1 <= M <= %d)", MAX_MOVES);
+    if (!std::isfinite(fpu_reduction) || !std::isfinite(c_base) || !std::isfinite(c_init) || c_base < 0.0f || c_init < 0.0f)
+        return azh_fail(-2, "azh_exploration_scores: need finite arguments, c_base >= 0 and c_init >= 0");
+    u32 N = 0;
+    float tp[MAX_MOVES];
+    for (int j = 0; j < M; j++) {
+        N += n[j];
+        tp[j] = n[j] ? fabsf(prior[j]) : 0.0f;
+    }
+    const float sq = sqrtf((float)(1u + N));
+    float c = c_puct, f = 0.0f;
+    if (exploration_on(fpu_reduction, c_base)) {
+        c = exploration_c(N, c_puct, c_base, c_init);
+        f = exploration_fpu(gumbel_lane_sum(W, M), gumbel_lane_sum(tp, M), N, fpu_reduction);
+    }
+    for (int j = 0; j < M; j++)
+        scores_out[j] = exploration_score(fabsf(prior[j]), W[j], n[j], sq, c, f);
+    return 0;
 }
 
 // Sums over the games of the proof pass's counters: out [AZH_PROOF_STAT_COUNT].

@@ -106,6 +106,10 @@ struct EngineParams {
     u64 *slot_mask;             // [G] the wall mask of each slot's current game, written where a game begins (init_game_at)
     u64 *leaf_mask;             // [slots] beside leaf_board: the mask of the game that selected the slot's leaf, written by that
                                 // select — the tower reads it, never slot_mask (the launch's first workgroups restart games)
+    // first-play urgency and the exploration rate (azh_engine_set_exploration), read by vl_select_game alone; off
+    // while fpu_reduction < 0 and c_base == 0 (exploration_on)
+    float fpu_reduction;        // an unvisited child's Q is the node's mean score less this * sqrt(visited policy mass); < 0: 0
+    float c_base, c_init;       // c = log((1 + N + c_base) / c_base) + c_init; c_base == 0: the constant c_puct
 };
 
 // The walls slot g's game is played on (g wave-uniform: one scalar 8-byte load); the engine's one mask while no pool is set.

@@ -1,7 +1,9 @@
 // Leaf-parallel search with virtual loss (azh_engine_set_leaf_batch): one tree selects up to K leaves per iteration, the
 // leaves go to the net in the same tower launch, and the K paths are backed up before the next select.  Included by
 // engine.hip (compiled -ffp-contract=off) after the one-leaf tree kernels, whose device functions it shares
-// (puct_score, apply_priors, mark_game, compact_leaves); none of those changes with it.
+// (apply_priors, mark_game, compact_leaves); none of those changes with it.  A level's score is exploration_score
+// (azh_device.h): puct_score's operations with the node's c and the unvisited children's Q as arguments — c_puct and 0, i.e.
+// puct_score itself, unless azh_engine_set_exploration switched first-play urgency or the growing exploration rate on.
 //
 // The definition (DESIGN.md "Leaf-parallel search"; tests/vl_reference.py restates it in numpy):
 //   k = min(K, T - root_visits) paths per iteration (at least 1; T = visits, or the ply's own threshold under the playout cap), selected as if one after the other, each on the
@@ -45,6 +47,8 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
     const size_t base = (size_t)g * K;
     Arena A = arena_of(P, s.arena, g);
     const u32 tie_flip = (P.flags & AZH_FLAG_TIE_FIRST) ? 0xFFFFFFFFu : 0u;
+    // first-play urgency and the exploration rate (azh_engine_set_exploration): wave-uniform, a kernel argument
+    const bool explore = exploration_on(P.fpu_reduction, P.c_base);
     // lane p collects slot p's result
     int r_kind = AZH_LEAF_NONE, r_node = 0, r_len = 0;
     u32 r_edge = NONE;
@@ -102,7 +106,22 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
                     }
                 }
                 // N = the sum of the children's effective counts, as the oracle sums them
-                const float sq = sqrtf((float)(1u + wave_sum_u32(nsum)));
+                const u32 N = wave_sum_u32(nsum);
+                const float sq = sqrtf((float)(1u + N));
+                // c and the unvisited children's Q: c_puct and 0 unless the mode is on (exploration_score is then puct_score)
+                float c = P.c_puct, fpu = 0.0f;
+                if (explore) {
+                    float wpart = 0.0f, ppart = 0.0f;  // the lane's terms j = lane, lane + 64, ... from +0 in that order
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        if (r < rounds && lane + 64 * r < M) {
+                            wpart = wpart + u2f(ev[r].y);
+                            ppart = ppart + (edge_visits(ev[r]) ? __builtin_fabsf(u2f(ev[r].x)) : 0.0f);
+                        }
+                    const float Wsum = wave_sum_f32(wpart), Psum = wave_sum_f32(ppart);
+                    c = exploration_c(N, P.c_puct, P.c_base, P.c_init);
+                    fpu = exploration_fpu(Wsum, Psum, N, P.fpu_reduction);
+                }
                 // arg-max with the engine's tie rule: (score bits << 32 | index or ~index), NaN and empty lanes key 0
                 u64 key = 0;
                 u32 mine = ev[0].z, mkid = ev[0].w;
@@ -110,7 +129,7 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
                 for (int r = 0; r < 4; r++) {
                     const int j = lane + 64 * r;
                     if (r < rounds && j < M) {
-                        const float score = puct_score(u2f(ev[r].x), u2f(ev[r].y), edge_visits(ev[r]), sq, P.c_puct);
+                        const float score = exploration_score(__builtin_fabsf(u2f(ev[r].x)), u2f(ev[r].y), edge_visits(ev[r]), sq, c, fpu);
                         const u64 kj = score >= 0.0f ? (((u64)f2u(score + 0.0f)) << 32) | (u64)((u32)j ^ tie_flip) : 0ull;
                         if (kj > key) {
                             key = kj;

@@ -158,6 +158,9 @@ SIGNATURES = {
     "azh_symmetry_policy_index": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "azh_engine_set_solver": (ctypes.c_int, [_vp, ctypes.c_int]),
     "azh_engine_proof_stats": (ctypes.c_int, [_vp, _vp]),
+    "azh_engine_set_exploration": (ctypes.c_int, [_vp, _f32, _f32, _f32]),
+    "azh_engine_exploration": (ctypes.c_int, [_vp, _vp]),
+    "azh_exploration_scores": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _f32, _f32, _f32, _f32, _vp]),
     "azh_engine_root_proofs": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
     "azh_engine_play_moves": (ctypes.c_int, [_vp, _vp, _vp]),
     "azh_engine_root_report": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
@@ -426,6 +429,21 @@ def gumbel_root(prior, W, n, v0, noise, c_visit, c_scale):
     check(load().azh_gumbel_root(_ptr(prior), _ptr(W), _ptr(n), len(n), float(v0), _ptr(noise), float(c_visit), float(c_scale),
                                  _ptr(counts), ctypes.byref(move)))
     return int(move.value), counts
+
+
+def exploration_scores(prior, W, n, c_puct, fpu_reduction=-1.0, c_base=0.0, c_init=0.0):
+    """First-play urgency and the exploration rate (Engine.set_exploration): the scores of one node's edges with priors
+    `prior`, total scores `W` and effective visit counts `n` — (M,) f32; with (-1, 0, 0) the reference's PUCT scores
+    (azh_exploration_scores; host arithmetic, no GPU needed)."""
+    prior = np.ascontiguousarray(prior, dtype=np.float32)
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    n = np.ascontiguousarray(n, dtype=np.uint32)
+    if not len(prior) == len(W) == len(n):
+        raise ValueError("prior, W and n must have one entry per edge")
+    out = np.zeros(max(len(n), 1), dtype=np.float32)
+    check(load().azh_exploration_scores(_ptr(prior), _ptr(W), _ptr(n), len(n), float(c_puct), float(fpu_reduction), float(c_base),
+                                        float(c_init), _ptr(out)))
+    return out[:len(n)]
 
 
 def eval_symmetry(seed, uid, mover, opponent):
@@ -758,6 +776,20 @@ class Engine:
         """Proven wins and losses in the tree ("Proven wins and losses").  While it is on every K, 1 included,
         runs through the leaf-parallel kernel (batch_leaves / set_batch_evals).  Between iterations only."""
         check(load().azh_engine_set_solver(self.h, 1 if on else 0))
+
+    def set_exploration(self, fpu_reduction=-1.0, c_base=0.0, c_init=0.0):
+        """First-play urgency (fpu_reduction >= 0: an unvisited child's Q is its parent's mean score less fpu_reduction *
+        sqrt(visited policy mass), not 0) and the exploration rate that grows with log N (c_base > 0: c = log((1 + N + c_base)
+        / c_base) + c_init, not c_puct) — DESIGN.md, "First-play urgency and the exploration rate".  While either is on every
+        K, 1 included, runs through the leaf-parallel kernel (batch_leaves / set_batch_evals).  The defaults switch both off.
+        Between iterations only."""
+        check(load().azh_engine_set_exploration(self.h, float(fpu_reduction), float(c_base), float(c_init)))
+
+    def exploration(self):
+        """-> (fpu_reduction, c_base, c_init) in force: (-1, 0, 0) while the mode is off."""
+        out = np.zeros(3, dtype=np.float32)
+        check(load().azh_engine_exploration(self.h, _ptr(out)))
+        return float(out[0]), float(out[1]), float(out[2])
 
     def proof_stats(self):
         """-> {"proven_nodes", "proven_hits"}: nodes the proof pass proved; paths that ended at a proven node."""

@@ -17,6 +17,10 @@ the new position is not there.  The root's edges and the principal variation com
 With `solver` (an option, off by default) the search proves wins and losses in its tree ("Proven wins and
 losses"; every K then runs through the leaf-parallel kernel): a move that is proven to win is played without sampling, a
 root that is proven lost plays its most visited move, and a timed search stops as soon as the root is proven.
+
+With `fpu_reduction` and / or `cpuct_base` (options, off by default) an unvisited move scores its parent's mean score less a
+reduction, not 0, and the exploration factor grows with the logarithm of the visits ("First-play urgency and the
+exploration rate"; every K then runs through the leaf-parallel kernel, as under the solver).
 """
 import random
 import time
@@ -161,7 +165,8 @@ class Searcher:
                              # tree per visit (96 edge slots of 18 bytes per node, two arenas): at most about 210 MB
 
     def __init__(self, network_path, dtype="f16", symmetry_average=False, parallel_leaves=1, virtual_loss=1,
-                 reuse_tree=False, show_pv=False, solver=False, random_symmetry=False):
+                 reuse_tree=False, show_pv=False, solver=False, random_symmetry=False, fpu_reduction=None, cpuct_base=None,
+                 cpuct_init=0.0):
         # parallel_leaves = K > 1: leaf-parallel search with virtual loss ("Leaf-parallel search"): up to K
         # leaves per iteration in one tower launch.  An extension; 1 is the reference's one-leaf search.
         if not 1 <= parallel_leaves <= link.MAX_LEAVES_PER_GAME or not 1 <= virtual_loss <= link.MAX_VIRTUAL_LOSS:
@@ -173,6 +178,17 @@ class Searcher:
             raise ValueError("symmetry averaging is not available with the solver")
         if random_symmetry and symmetry_average:
             raise ValueError("a random symmetry per evaluation is not available with symmetry averaging")
+        # fpu_reduction, cpuct_base, cpuct_init: first-play urgency and the growing exploration rate
+        # (azh_engine_set_exploration); None leaves a knob off.  self.exploration: the setter's arguments, or None
+        self.exploration = None
+        if fpu_reduction is not None or cpuct_base is not None:
+            if symmetry_average:
+                raise ValueError("symmetry averaging is not available with fpu_reduction or cpuct_base")
+            if (fpu_reduction is not None and not 0.0 <= fpu_reduction < float("inf")) or \
+                    (cpuct_base is not None and not 0.0 < cpuct_base < float("inf")) or not 0.0 <= cpuct_init < float("inf"):
+                raise ValueError("need fpu_reduction >= 0, cpuct_base > 0 and cpuct_init >= 0, all finite")
+            self.exploration = (-1.0 if fpu_reduction is None else float(fpu_reduction),
+                                0.0 if cpuct_base is None else float(cpuct_base), float(cpuct_init))
         self.parallel_leaves, self.virtual_loss = parallel_leaves, virtual_loss
         # random_symmetry: every position is evaluated under one of the 8 symmetries of the board, drawn per (engine seed,
         # position) — link.Engine.set_random_symmetry; the net's orientation bias averages out over a search at no tower work
@@ -240,6 +256,8 @@ class Searcher:
                 self.engine.set_leaf_batch(self.parallel_leaves, self.virtual_loss)
             if self.solver:
                 self.engine.set_solver(True)
+            if self.exploration:
+                self.engine.set_exploration(*self.exploration)
         return self.engine
 
     def _bring_tree_to(self, pos):
@@ -319,7 +337,7 @@ class Searcher:
         self.last_inherited, self.last_report, self.last_note, self.last_proofs = 0, None, None, None
         if self.reuse_tree:
             return self._root_visits_reusing(pos, visits, seconds)
-        if self.parallel_leaves > 1 or self.solver:   # (the solver runs every K through the leaf-parallel kernel)
+        if self.parallel_leaves > 1 or self.solver or self.exploration:   # (both run every K through the leaf-parallel kernel)
             return self._root_visits_parallel(pos, visits, seconds)
         cap = visits if visits is not None else self.TIME_CAP_VISITS
         cfg = link.Config(games=1, visits=cap + 1, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
@@ -366,6 +384,8 @@ class Searcher:
             eng.set_leaf_batch(K, self.virtual_loss)
             if self.solver:
                 eng.set_solver(True)
+            if self.exploration:
+                eng.set_exploration(*self.exploration)
             if self._random_symmetry_on(pos):
                 eng.set_random_symmetry(True)
             eng.run(self.net, 1, self.dtype)  # the root evaluation

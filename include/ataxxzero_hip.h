@@ -251,7 +251,7 @@ int azh_engine_sync(azh_engine *e);
 /* change the root-visit threshold (global_visits) for the coming moves; 1 <= visits <= the
  * value the engine was created with */
 int azh_engine_set_visits(azh_engine *e, int visits);
-/* SEARCH MODES: WHO REFUSES WHOM.  Eight modes are switched by setters below, before the first select or between iterations.
+/* SEARCH MODES: WHO REFUSES WHOM.  Nine modes are switched by setters below, before the first select or between iterations.
  * A call that switches a mode on is a request for it; one that switches it off is not, and is never refused for a reason in
  * this table.  Every one of these setters checks in this order, and changes nothing unless every check passes: -1 a null
  * engine, -2 a value out of range, -3 a selected batch awaits its backup (requests and switching off alike), -4 the request
@@ -259,15 +259,19 @@ int azh_engine_set_visits(azh_engine *e, int visits);
  *
  *   mode            is on while                 refused on an engine created with                         refused beside
  *   playout cap     fast_visits != 0            TWO_NETS, ONE_RANDOM_MOVE                                 Gumbel
- *   forced playouts k != 0                      TWO_NETS, ONE_RANDOM_MOVE                                 Gumbel, leaf batch, solver
+ *   forced playouts k != 0                      TWO_NETS, ONE_RANDOM_MOVE                                 Gumbel, leaf batch, solver,
+ *                                                                                                         exploration
  *   Gumbel          m != 0                      TWO_NETS, ONE_RANDOM_MOVE, SAMPLE_POW5, EVAL_CACHE;       playout cap, forced playouts,
- *                                               without NO_REUSE; dirichlet_weight != 0                   temperature, leaf batch, solver
+ *                                               without NO_REUSE; dirichlet_weight != 0                   temperature, leaf batch, solver,
+ *                                                                                                         exploration
  *   temperature     either table is set         TWO_NETS, ONE_RANDOM_MOVE, SAMPLE_POW5, PY_POSTERIOR      Gumbel
  *   resign          consecutive != 0            TWO_NETS, ONE_RANDOM_MOVE                                 -
  *   random symmetry on != 0                     TWO_NETS, SYMMETRY_AVG; a blockers mask that is not its   -
  *                                               own image under all 8 symmetries
  *   leaf batch      leaves_per_game > 1         TWO_NETS, EVAL_CACHE, SYMMETRY_AVG; select_budget > 0     Gumbel, forced playouts
  *   solver          on != 0                     TWO_NETS, EVAL_CACHE, SYMMETRY_AVG; select_budget > 0     Gumbel, forced playouts
+ *   exploration     fpu_reduction >= 0 ||       TWO_NETS, EVAL_CACHE, SYMMETRY_AVG; select_budget > 0     Gumbel, forced playouts
+ *                   c_base > 0
  *
  * The last column is symmetric: of two modes that exclude each other, whichever is asked for second is refused, and comes on
  * once the other is off.  Everything not listed composes.  The message (azh_last_error) is "<setter>: not supported with
@@ -275,7 +279,8 @@ int azh_engine_set_visits(azh_engine *e, int visits);
  * with <cause>" / "<setter>: the solver is not supported with <cause>"; the cause is the flag (AZH_FLAG_...), "select_budget
  * > 0", the blockers mask, or the mode that is on with its setter: "the playout cap (azh_engine_set_playout_cap)", "forced
  * playouts (azh_engine_set_forced_playouts)", "the Gumbel root search (azh_engine_set_gumbel)", "a temperature table
- * (azh_engine_set_temperature)", "more than one leaf per game (azh_engine_set_leaf_batch)", "the solver"; Gumbel on an engine
+ * (azh_engine_set_temperature)", "more than one leaf per game (azh_engine_set_leaf_batch)", "the solver", "first-play
+ * urgency or a growing exploration rate (azh_engine_set_exploration)"; Gumbel on an engine
  * without NO_REUSE or with a dirichlet_weight says that the engine must have been created with both.  Where several causes
  * apply the message names one: a flag before anything else, in the order TWO_NETS, ONE_RANDOM_MOVE, SAMPLE_POW5, PY_POSTERIOR,
  * EVAL_CACHE, SYMMETRY_AVG, then the other create-time causes, then the modes, Gumbel first.  The paragraphs below say why. */
@@ -540,6 +545,48 @@ int azh_engine_proof_stats(azh_engine *e, uint64_t *out /* [AZH_PROOF_STAT_COUNT
  * move wins for the root's mover); 0 for an edge without a child, an undecided child and j >= root edges. */
 enum { AZH_ROOT_PROOF_WORDS = 1 + AZH_MAX_MOVES };
 int azh_engine_root_proofs(azh_engine *e, int first_game, int n_games, int32_t *out /* [n_games][AZH_ROOT_PROOF_WORDS] */);
+
+/* First-play urgency and the exploration rate of the leaf-parallel search (an extension, off by default; the reference scores
+ * an unvisited child with Q = 0 and explores with the constant c_puct; DESIGN.md, "First-play urgency and the exploration
+ * rate").  The setter is azh_engine_set_exploration(e, fpu_reduction, c_base, c_init).
+ *   - fpu_reduction < 0 means FPU off: an unvisited child's Q is 0, as today.
+ *   - c_base == 0 means the constant cfg.c_puct, as today.  c_init is then ignored.
+ *   - The mode is on while fpu_reduction >= 0 || c_base > 0.
+ *   - Return -2 for a NaN or infinite argument, c_base < 0 or c_init < 0.
+ * For one level of one path, at a node with children j = 0..M-1 in edge order:
+ *   - n_j is the effective count: stored visits plus VL times the number of earlier paths of the batch.
+ *   - W_j is unchanged.
+ *   - P_j is |prior|.
+ *   - N = sum of the n_j as u32.
+ *   - sq = sqrtf((float)(1u + N)), as today.
+ * All arithmetic is f32, every operation a single IEEE one, compiled -ffp-contract=off as the rest of engine.hip is.
+ *   - c.  If c_base > 0, c = det_logf(((float)(1u + N) + c_base) / c_base) + c_init.  Otherwise c = c_puct.
+ *   - f, with FPU on and N > 0.
+ *       Wsum is the 64-lane sum of W_j over all j.  Unvisited edges add their stored +0.
+ *       Psum is the 64-lane sum of (n_j > 0 ? P_j : +0.0f).
+ *       Both sums are in the engine's canonical order: term j is added from +0 into lane j % 64 in ascending j, and the lanes
+ *       are then folded by the xor butterfly 1, 2, 4, 8, 16, 32.  This is wave_sum_f32, restated in numpy by
+ *       tests/priors_reference.wave_sum.
+ *       qX = Wsum / (float)N, then f = qX - fpu_reduction * sqrtf(Psum), then f = f > 0.0f ? f : 0.0f.  A NaN becomes 0.
+ *   - f, with FPU off or N == 0.  f = 0.
+ *   - Score.  score_j = (sq / (1.0f + (float)n_j)) * (c * P_j) + (n_j ? W_j / (float)n_j : f), in puct_score's operation order.
+ * Nothing else changes: a score is selectable only if score >= 0; ties follow the flags; path ends are unchanged (EVAL,
+ * TERMINAL, COLLISION, dropped); the virtual loss, the backup, the solver's proofs and marks, re-roots, the root report and the
+ * PV are all what they are today.  With the mode off, every byte of every arena is what it was before the mode existed.
+ * While the mode is on, EVERY leaves_per_game — 1 included — runs through the leaf-parallel kernel, as under the solver: the
+ * step-wise calls are azh_engine_batch_leaves / _set_batch_evals; off with K = 1 and no solver returns to the one-leaf kernels.
+ * Call between iterations only.  Refused with AZH_FLAG_TWO_NETS, AZH_FLAG_EVAL_CACHE, AZH_FLAG_SYMMETRY_AVG and select_budget
+ * > 0, and beside the Gumbel root search and forced playouts, which restate the root's PUCT with q = 0 and the constant c (the
+ * table above); a refused call changes nothing.  AlphaZero's published c_base = 19652, c_init = 1.25 are a starting point;
+ * nothing is tuned for Ataxx. */
+int azh_engine_set_exploration(azh_engine *e, float fpu_reduction, float c_base, float c_init);
+/* the three values in force: out [3] = fpu_reduction (-1: off), c_base (0: the constant c_puct), c_init */
+int azh_engine_exploration(const azh_engine *e, float *out);
+/* One node's M scores (1 <= M <= 256) under the rule above: prior [M], W [M] total scores, n [M] effective counts, into
+ * scores_out [M].  With (-1, 0, 0) these are the reference's PUCT scores.  -2 for the arguments the setter refuses.  Host
+ * arithmetic only, usable without a device: the functions the device's level uses, the two sums restated lane by lane. */
+int azh_exploration_scores(const float *prior, const float *W, const uint32_t *n, int M, float c_puct, float fpu_reduction,
+                           float c_base, float c_init, float *scores_out);
 
 /* Which tower the device-resident loop evaluates its leaves with: 0 the 3-board workgroups (throughput), 1 one board per
  * workgroup (latency: azh_net_forward_thin's kernel), -1 (default) by the engine's size — thin for engines of at most

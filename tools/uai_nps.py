@@ -20,6 +20,13 @@ with the solver off and on, one after the other in the same process; the lines c
 on K = 1 runs through the leaf-parallel kernel, so its off/on pair is also the one-leaf kernels against k_vl_tree.
 
     python tools/uai_nps.py --solver --ks 1,32 [--out profiles/uai_solver.txt]
+
+--exploration R,B,C measures what first-play urgency and the growing exploration rate cost ("First-play urgency
+and the exploration rate"): every (position, K) of --ks is searched with the mode off and with
+azh_engine_set_exploration(R, B, C), --repeats times each, off and on in turn in the same process.  With the mode on K = 1
+runs through the leaf-parallel kernel, as under the solver.  (Random weights: the rate is measured, not the strength.)
+
+    python tools/uai_nps.py --exploration 0.25,19652,1.25 --ks 1,32 [--repeats 3] [--out profiles/FILE.txt]
 """
 import argparse
 import os
@@ -40,7 +47,7 @@ POSITIONS = [
 ]
 
 
-def search(net, pos, K, VL, seconds, dtype, solver=False):
+def search(net, pos, K, VL, seconds, dtype, solver=False, exploration=None):
     """One timed search as uai.Searcher runs it, with every iteration's tree and tower launches timed."""
     target = min(uai.Searcher.TIME_CAP_VISITS * K, uai.Searcher.MAX_VISITS)
     cfg = link.Config(games=1, visits=target + (1 if K == 1 else 0), max_plies=400, edges_per_node=96, c_puct=1.0,
@@ -51,6 +58,8 @@ def search(net, pos, K, VL, seconds, dtype, solver=False):
         eng.set_leaf_batch(K, VL)
     if solver:
         eng.set_solver(True)
+    if exploration:
+        eng.set_exploration(*exploration)
     eng.timing_reset(1)
     start = time.time()
     eng.run(net, 1, dtype)
@@ -204,6 +213,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reuse-tree", action="store_true", help="measure tree reuse across the moves of a fixed line instead")
     ap.add_argument("--solver", action="store_true", help="every (position, K) with the proof layer off and on")
+    ap.add_argument("--exploration", default=None, metavar="R,B,C",
+                    help="every (position, K) with azh_engine_set_exploration(R, B, C) off and on")
+    ap.add_argument("--repeats", type=int, default=3, help="searches per (position, K, off / on) with --exploration")
     ap.add_argument("--movetime-ms", type=int, default=1000)
     ap.add_argument("--ks", default="1,8,16,32,48,64")
     ap.add_argument("--virtual-loss", type=int, default=1)
@@ -237,6 +249,35 @@ def main():
                         r["proofs"]["proven_hits"], nps / off)
                     print(line, flush=True)
                     lines.append(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+    if a.exploration:
+        params = tuple(float(v) for v in a.exploration.split(","))
+        assert len(params) == 3, "--exploration takes fpu_reduction,c_base,c_init"
+        lines[0] += "; exploration %g,%g,%g, %d searches each" % (params + (a.repeats,))
+        lines[1] = "# columns: position K exploration visits/s  iterations  tree ms/it  tower ms/it  collisions/path  (last line of a pair: mean on / mean off)"
+        search(net, uai.Position.from_fen(POSITIONS[0][1]), 1, 1, 0.2, dtype, exploration=params)
+        for name, fen in POSITIONS:
+            pos = uai.Position.from_fen(fen)
+            for K in ks:
+                rates = {False: [], True: []}
+                for _ in range(a.repeats):
+                    for on in (False, True):
+                        r = search(net, pos, K, a.virtual_loss, a.movetime_ms * 1e-3, dtype, exploration=params if on else None)
+                        nps = r["visits"] / r["seconds"]
+                        rates[on].append(nps)
+                        line = "%-6s K=%-3d exploration=%d %9.0f visits/s  %6d it  tree %.4f  tower %.4f  coll %.3f" % (
+                            name, K, int(on), nps, r["iterations"], r["tree_ms"], r["tower_ms"], r["collisions"] / max(r["paths"], 1))
+                        print(line, flush=True)
+                        lines.append(line)
+                mean = {on: sum(v) / len(v) for on, v in rates.items()}
+                line = "%-6s K=%-3d off %9.0f (%.0f .. %.0f)  on %9.0f (%.0f .. %.0f) visits/s  x%.3f" % (
+                    name, K, mean[False], min(rates[False]), max(rates[False]), mean[True], min(rates[True]), max(rates[True]),
+                    mean[True] / mean[False])
+                print(line, flush=True)
+                lines.append(line)
         if a.out:
             with open(a.out, "w") as f:
                 f.write("\n".join(lines) + "\n")

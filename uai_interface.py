@@ -23,7 +23,8 @@ def main(options):
     searcher = uai.Searcher(options.network_path, dtype=options.dtype, symmetry_average=options.symmetry_average,
                             parallel_leaves=options.parallel_leaves, virtual_loss=options.virtual_loss,
                             reuse_tree=options.reuse_tree, show_pv=options.show_pv, solver=options.solver,
-                            random_symmetry=options.random_symmetry)
+                            random_symmetry=options.random_symmetry, fpu_reduction=options.fpu_reduction,
+                            cpuct_base=options.cpuct_base, cpuct_init=options.cpuct_init)
     session = uai.Session(searcher, visits=options.visits, safety_ms=options.safety_ms, show_game=options.show_game,
                           log=sys.stderr)
     session.serve(sys.stdin, sys.stdout)
@@ -52,11 +53,22 @@ if __name__ == "__main__":
     cli.add_argument("--solver", action="store_true",
                      help="prove wins and losses in the search tree (MCTS-solver; extension): a proven winning move is played "
                           "without sampling (`info string proven win`), a timed search stops once the root is proven")
+    cli.add_argument("--fpu-reduction", type=float, default=None, metavar="R",
+                     help="first-play urgency (extension, off by default): an unvisited move scores its parent's mean score "
+                          "less R * sqrt(policy mass of the visited moves), not 0, R >= 0 (Leela's reduction; 0.25 is a "
+                          "starting point, nothing is tuned for Ataxx)")
+    cli.add_argument("--cpuct-base", type=float, default=None, metavar="B",
+                     help="an exploration rate that grows with the visits (extension, off by default): c = log((1 + N + B) / B) "
+                          "+ C in the place of the constant 1.0, B > 0.  AlphaZero's published 19652 with --cpuct-init 1.25 is "
+                          "a starting point; nothing is tuned for Ataxx")
+    cli.add_argument("--cpuct-init", type=float, default=0.0, metavar="C", help="the C of --cpuct-base (ignored without it)")
     cli.add_argument("--dtype", default="f16", choices=["bf16", "f16", "f32"],
                      help="tower arithmetic (extension).  Match play defaults to f16: with a trained net the f16 search picks "
                           "the f32 search's move in 100 %% of test positions, bf16 in 96 %% (DESIGN.md section 5); bf16 is 3-6 %% faster")
     options = cli.parse_args()
     if options.random_symmetry and options.symmetry_average:
         cli.error("--random-symmetry and --symmetry-average exclude each other")
+    if (options.fpu_reduction is not None or options.cpuct_base is not None) and options.symmetry_average:
+        cli.error("--fpu-reduction and --cpuct-base are not available with --symmetry-average")
     print(options, file=sys.stderr)
     main(options)
