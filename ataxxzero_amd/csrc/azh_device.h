@@ -504,6 +504,24 @@ __host__ __device__ inline float exploration_score(float prior, float W, u32 n, 
     return u + q;
 }
 
+// Search settings per side (azh_engine_set_search_sets; DESIGN.md, "Search settings per side"): the sets of x and of o in game
+// `uid` among n sets, as x | o << 8.  With q = uid / 2 and t = q % (n (n - 1) / 2), (a, b), a < b, is the t-th unordered pair
+// in lexicographic order; x plays a in an even uid and b in an odd one.  n < 2: both sides play set 0.  The host's
+// azh_search_set_pairing and the kernels that write a slot's word (begin_game_key, k_slot_sets) run this one function.
+__host__ __device__ inline u32 search_set_pairing(u32 uid, u32 n)
+{
+    if (n < 2u)
+        return 0u;
+    u32 t = (uid >> 1) % (n * (n - 1u) / 2u);
+    u32 a = 0;
+    while (t >= n - 1u - a) {  // row a holds the n - 1 - a pairs (a, a + 1) .. (a, n - 1)
+        t -= n - 1u - a;
+        a++;
+    }
+    const u32 b = a + 1u + t;
+    return (uid & 1u) ? (b | (a << 8)) : (a | (b << 8));
+}
+
 // Temperature of the move played (azh_engine_set_temperature; DESIGN.md, "Temperature of the move and of the root policy").
 // The fixed-point weight of a root edge with n visits when the most visited edge has exp(log_nmax) of them: (n / n_max)^(1/T)
 // in units of 2^-20, from det_logf / det_expf and one IEEE f32 division, so host and device agree to the bit and the sum of

@@ -155,6 +155,14 @@ __global__ void k_eval_keys(EngineParams P)
         P.eval_key[g] = eval_symmetry_key(P.k0, P.k1, P.gs[g].uid);
 }
 
+// azh_engine_set_search_sets: the pairing of the game every slot is at (one thread per slot)
+__global__ void k_slot_sets(EngineParams P)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < P.G)
+        P.slot_sets[g] = search_set_pairing(P.gs[g].uid, (u32)P.n_search_sets);
+}
+
 // The symmetry under which `node` of slot g's tree goes to the evaluator (0, the identity, while the mode is off): a function
 // of the game's key word and the node's own board, so the select that sends the position, the backup that gathers its logits,
 // the root's re-evaluation at a later ply and a transposition's source node all agree on it.  g, node: wave-uniform.
@@ -940,13 +948,19 @@ __device__ inline void backup_game(const EngineParams &P, int g, azh_game_state 
 // subtree copy (one dependent round trip per tree level) no longer sits on every iteration's critical path.
 // `forced`: force[g], loaded by the caller beside the state; `pk`: the ply's kind word (playout cap: a FAST ply's move is
 // due at fast_visits).
-__device__ inline void mark_game(const EngineParams &P, int g, azh_game_state &s, int forced, u32 pk)
+// mark_game_at: the same with the threshold given (k_vl_tree: the visits of the ply's search set).
+__device__ inline void mark_game_at(const EngineParams &P, int g, azh_game_state &s, int forced, int threshold)
 {
-    if (s.phase == 1 && s.leaf_kind != AZH_LEAF_DESCENT && (s.root_visits >= ply_threshold(P, pk) || forced != 0)) {
+    if (s.phase == 1 && s.leaf_kind != AZH_LEAF_DESCENT && (s.root_visits >= threshold || forced != 0)) {
         s.phase = 2;
         if (lane_id() == 0)
             P.adv_list[atomicAdd(P.adv_count, 1)] = g;
     }
+}
+
+__device__ inline void mark_game(const EngineParams &P, int g, azh_game_state &s, int forced, u32 pk)
+{
+    mark_game_at(P, g, s, forced, ply_threshold(P, pk));
 }
 
 __global__ __launch_bounds__(WAVE) void k_advance_list(EngineParams P)
@@ -1455,19 +1469,26 @@ struct azh_engine {
     // G K-slot buffers (vl_active: P's leaf buffers point at them), and its backup is followed by the proof pass
     bool vl_active = false;   // (the solver's own switch is V.solver)
     int32_t *d_proofs = nullptr;  // azh_engine_root_proofs: [G][AZH_ROOT_PROOF_WORDS], allocated by the first call
+    // search settings per side (azh_engine_set_search_sets): the sets in force on the host (P.n_search_sets of them) and the
+    // device's table, AZH_SEARCH_SETS_MAX entries allocated by the first call that brings sets; P.search_sets points at it
+    // while the mode is on
+    azh_search_set sets[AZH_SEARCH_SETS_MAX] = {};
+    azh_search_set *d_sets = nullptr;
 };
 
 static int leaf_k(const azh_engine *e) { return e->V.K > 1 ? e->V.K : 1; }
 
 static bool explores(const azh_engine *e) { return exploration_on(e->P.fpu_reduction, e->P.c_base); }
 
+static bool search_sets_on(const azh_engine *e) { return e->P.n_search_sets != 0; }
+
 // what beside K keeps the leaf-parallel kernel in force, for the errors of the one-leaf calls ("" if nothing; `joint`: " with" / " and")
 static std::string vl_beside(const azh_engine *e, const char *joint)
 {
-    if (!e->V.solver && !explores(e))
+    const char *mode = explores(e) ? " azh_engine_set_exploration" : search_sets_on(e) ? " azh_engine_set_search_sets" : "";  // (never both)
+    if (!e->V.solver && !mode[0])
         return "";
-    return std::string(joint) + (e->V.solver ? " the solver" : "") + (e->V.solver && explores(e) ? " and" : "") +
-           (explores(e) ? " azh_engine_set_exploration" : "");
+    return std::string(joint) + (e->V.solver ? " the solver" : "") + (e->V.solver && mode[0] ? " and" : "") + mode;
 }
 
 // the tower for this engine's leaf batches: one board per workgroup for engines (or batches the host says are) small
@@ -1504,12 +1525,12 @@ template <typename T> static int dev_alloc_once(azh_engine *e, T **p, size_t cou
 
 // ------------------------------------------------------------------ the search modes: who refuses whom
 //
-// Nine modes are switched between iterations, by a setter each.  What a mode cannot run beside (create-time flags and settings,
+// Ten modes are switched between iterations, by a setter each.  What a mode cannot run beside (create-time flags and settings,
 // other modes) is stated here once, and mode_refusal answers for every setter.  In words: the table "Search modes: who refuses
 // whom" of include/ataxxzero_hip.h and of DESIGN.md.
 
 enum { MODE_NONE = -1, MODE_CAP, MODE_FORCED, MODE_GUMBEL, MODE_TEMPERATURE, MODE_RESIGN, MODE_SYMMETRY, MODE_LEAF_BATCH, MODE_SOLVER,
-       MODE_EXPLORATION };
+       MODE_EXPLORATION, MODE_SEARCH_SETS };
 
 // Is `bb` its own image under all 8 symmetries?  (the two mirrors and the transposition generate them)
 static bool symmetry_invariant(u64 bb)
@@ -1542,6 +1563,9 @@ static const ModeInfo MODES[] = {  // (in the order of the MODE_ constants)
     {"azh_engine_set_solver", "the solver", false, true, false, ON(e->V.solver != 0), LEAF_FLAGS},
     {"azh_engine_set_exploration", "first-play urgency or a growing exploration rate", true, false, false,
      ON(exploration_on(e->P.fpu_reduction, e->P.c_base)), LEAF_FLAGS},
+    // (own_advance: the tally of the games' results lives in k_advance_list's advance_game, and so does the slot word's write)
+    {"azh_engine_set_search_sets", "search settings per side", true, false, true, ON(e->P.n_search_sets != 0),
+     LEAF_FLAGS | AZH_FLAG_ONE_RANDOM_MOVE},
 };
 #undef ON
 
@@ -1552,6 +1576,8 @@ static const int EXCLUDED[][2] = {
     {MODE_GUMBEL, MODE_SOLVER}, {MODE_FORCED, MODE_LEAF_BATCH}, {MODE_FORCED, MODE_SOLVER},
     // (both restate the root's PUCT with q = 0 for an unvisited edge and the constant c_puct)
     {MODE_GUMBEL, MODE_EXPLORATION}, {MODE_FORCED, MODE_EXPLORATION},
+    // (a set carries its side's threshold and exploration knobs: a second source for either is an ambiguity)
+    {MODE_GUMBEL, MODE_SEARCH_SETS}, {MODE_FORCED, MODE_SEARCH_SETS}, {MODE_CAP, MODE_SEARCH_SETS}, {MODE_EXPLORATION, MODE_SEARCH_SETS},
 };
 
 // The create-time flags a mode can be refused with; of several set at once a refusal names the first one listed here.
@@ -1587,7 +1613,7 @@ static std::string mode_refusal(const azh_engine *e, int mode)
     for (const auto &f : FLAG_NAMES)
         if (e->P.flags & m.refused_flags & f.bit)
             return head + f.name;
-    if ((mode == MODE_LEAF_BATCH || mode == MODE_SOLVER || mode == MODE_EXPLORATION) && e->P.select_budget > 0)
+    if ((mode == MODE_LEAF_BATCH || mode == MODE_SOLVER || mode == MODE_EXPLORATION || mode == MODE_SEARCH_SETS) && e->P.select_budget > 0)
         return head + "select_budget > 0";
     if (mode == MODE_GUMBEL && (!(e->P.flags & AZH_FLAG_NO_REUSE) || e->P.noise_w != 0.0f))
         return "the engine must have been created with AZH_FLAG_NO_REUSE and dirichlet_weight 0 (the schedule assumes a fresh "
@@ -2069,15 +2095,19 @@ extern "C" int azh_engine_tree_stamps(azh_engine *e, azh_net *net, int dtype, ui
 
 // Leaf-parallel search: K leaves per game and iteration, spread by a virtual loss of `virtual_loss` visits
 // (vl_search.h), and the solver and the exploration mode on top of it.  k_vl_tree and the G K-slot buffers are in force while
-// K > 1 or the solver or the exploration mode is on; K = 1 without either is the one-leaf search and its kernels.  `who`: the
+// K > 1 or the solver, the exploration mode or search sets are on; K = 1 without any of them is the one-leaf search and its kernels.  `who`: the
 // calling entry point, for its errors.  `explore`: null (the exploration mode stays as it is), or the three values of
-// azh_engine_set_exploration, which are the call's request then.
+// azh_engine_set_exploration, which are the call's request then.  `sets`: -1 (the search sets stay as they are), or the number
+// of sets azh_engine_set_search_sets is about to put in force, which is the call's request then; that caller fills in the
+// sets themselves once this has succeeded.
 static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, bool solver, const char *who,
-                         const float *explore = nullptr)
+                         const float *explore = nullptr, int sets = -1)
 {
     const bool explore_on = explore ? exploration_on(explore[0], explore[1]) : explores(e);
-    const bool want = leaves_per_game > 1 || solver || explore_on;
-    AZH_TRY(mode_request(e, who, explore ? (explore_on ? MODE_EXPLORATION : MODE_NONE)
+    const bool sets_on = sets >= 0 ? sets > 0 : search_sets_on(e);
+    const bool want = leaves_per_game > 1 || solver || explore_on || sets_on;
+    AZH_TRY(mode_request(e, who, sets >= 0 ? (sets_on ? MODE_SEARCH_SETS : MODE_NONE)
+                                 : explore ? (explore_on ? MODE_EXPLORATION : MODE_NONE)
                                  : leaves_per_game > 1 ? MODE_LEAF_BATCH : solver ? MODE_SOLVER : MODE_NONE));
     EngineParams &P = e->P;
     const size_t n = (size_t)P.G * (size_t)leaves_per_game;
@@ -2104,6 +2134,8 @@ static int set_leaf_mode(azh_engine *e, int leaves_per_game, int virtual_loss, b
             e->V.solver = 0;
             P.fpu_reduction = -1.0f;
             P.c_base = P.c_init = 0.0f;
+            P.search_sets = nullptr;
+            P.n_search_sets = 0;
             e->vl_active = false;
             e->vl_slots_cap = 0;
             return rc;
@@ -2132,6 +2164,10 @@ extern "C" int azh_engine_set_leaf_batch(azh_engine *e, int leaves_per_game, int
     if (leaves_per_game < 1 || leaves_per_game > VL_MAX_LEAVES || virtual_loss < 1 || virtual_loss > VL_MAX_LOSS)
         return azh_fail(-2, "azh_engine_set_leaf_batch: need 1 <= leaves_per_game <= %d and 1 <= virtual_loss <= %d",
                         VL_MAX_LEAVES, VL_MAX_LOSS);
+    for (int i = 0; i < e->P.n_search_sets; i++)
+        if (leaves_per_game < e->sets[i].leaves)
+            return azh_fail(-2, "azh_engine_set_leaf_batch: %d is below the leaves %d of search set %d", leaves_per_game,
+                            e->sets[i].leaves, i);
     return set_leaf_mode(e, leaves_per_game, virtual_loss, e->V.solver != 0, "azh_engine_set_leaf_batch");
 }
 
@@ -2191,6 +2227,91 @@ extern "C" int azh_exploration_scores(const float *prior, const float *W, const 
     }
     for (int j = 0; j < M; j++)
         scores_out[j] = exploration_score(fabsf(prior[j]), W[j], n[j], sq, c, f);
+    return 0;
+}
+
+// Search settings per side: the two sides of a game search with a set each (its pairing: search_set_pairing), every K through
+// k_vl_tree, and the device tallies the results by (set of x, set of o).  Definition: the header and DESIGN.md.  Between
+// iterations only; n = 0 switches the mode off.
+extern "C" int azh_engine_set_search_sets(azh_engine *e, int n, const azh_search_set *sets)
+{
+    const char *who = "azh_engine_set_search_sets";
+    if (!e || (n > 0 && !sets))
+        return azh_fail(-1, "%s: null argument", who);
+    if (n < 0 || n > AZH_SEARCH_SETS_MAX)
+        return azh_fail(-2, "%s: need 0 <= n <= %d", who, AZH_SEARCH_SETS_MAX);
+    for (int i = 0; i < n; i++) {
+        const azh_search_set &t = sets[i];
+        if (t.visits < 1 || t.visits > e->P.visits)
+            return azh_fail(-2, "%s: set %d: need 1 <= visits <= %d (the engine's)", who, i, e->P.visits);
+        if (t.leaves < 1 || t.leaves > leaf_k(e))
+            return azh_fail(-2, "%s: set %d: need 1 <= leaves <= %d (azh_engine_set_leaf_batch)", who, i, leaf_k(e));
+        if (t.virtual_loss < 1 || t.virtual_loss > VL_MAX_LOSS || t.leaves * t.virtual_loss > VL_MAX_LEAVES * VL_MAX_LOSS)
+            return azh_fail(-2, "%s: set %d: need 1 <= virtual_loss <= %d", who, i, VL_MAX_LOSS);
+        if (!std::isfinite(t.c_puct) || t.c_puct < 0.0f)
+            return azh_fail(-2, "%s: set %d: need a finite c_puct >= 0", who, i);
+        if (!std::isfinite(t.fpu_reduction) || !std::isfinite(t.c_base) || !std::isfinite(t.c_init) || t.c_base < 0.0f || t.c_init < 0.0f)
+            return azh_fail(-2, "%s: set %d: need finite arguments, c_base >= 0 and c_init >= 0", who, i);
+    }
+    if (n > 0) {  // (allocations change nothing a refused call could show; a failed one is the call's failure before any change)
+        AZH_TRY(dev_alloc_once(e, &e->d_sets, (size_t)AZH_SEARCH_SETS_MAX));
+        AZH_TRY(dev_alloc_once(e, &e->P.slot_sets, (size_t)e->P.G));
+        AZH_TRY(dev_alloc_once(e, &e->P.set_stats, (size_t)AZH_SEARCH_SETS_MAX * AZH_SEARCH_SETS_MAX * AZH_SET_STAT_COUNT));
+    }
+    AZH_TRY(set_leaf_mode(e, leaf_k(e), e->V.vl, e->V.solver != 0, who, nullptr, n));  // (-3, -4; the stream is idle after it)
+    for (int i = 0; i < n; i++) {
+        e->sets[i] = sets[i];
+        if (!(e->sets[i].fpu_reduction >= 0.0f))
+            e->sets[i].fpu_reduction = -1.0f;
+        if (!(e->sets[i].c_base > 0.0f))
+            e->sets[i].c_init = 0.0f;  // (ignored with the constant c, as azh_engine_set_exploration)
+    }
+    e->P.n_search_sets = n;
+    e->P.search_sets = n > 0 ? e->d_sets : nullptr;
+    if (n == 0)
+        return 0;
+    AZH_HIP(hipMemcpy(e->d_sets, e->sets, (size_t)n * sizeof(azh_search_set), hipMemcpyHostToDevice));
+    AZH_HIP(hipMemset(e->P.set_stats, 0, (size_t)AZH_SEARCH_SETS_MAX * AZH_SEARCH_SETS_MAX * AZH_SET_STAT_COUNT * 8));
+    hipLaunchKernelGGL(k_slot_sets, dim3((e->P.G + 255) / 256), dim3(256), 0, e->stream, e->P);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// The sets in force: *n_out their number, sets_out (or null) the sets themselves.
+extern "C" int azh_engine_search_sets(const azh_engine *e, int32_t *n_out, azh_search_set *sets_out)
+{
+    if (!e || !n_out)
+        return azh_fail(-1, "azh_engine_search_sets: bad argument");
+    *n_out = e->P.n_search_sets;
+    for (int i = 0; sets_out && i < e->P.n_search_sets; i++)
+        sets_out[i] = e->sets[i];
+    return 0;
+}
+
+// out [2] = the set of x, the set of o in game `uid` among n sets.  Host arithmetic only: the function the kernels call.
+extern "C" int azh_search_set_pairing(uint32_t uid, int n, int32_t *out)
+{
+    if (!out)
+        return azh_fail(-1, "azh_search_set_pairing: null out");
+    if (n < 1 || n > AZH_SEARCH_SETS_MAX)
+        return azh_fail(-2, "azh_search_set_pairing: need 1 <= n <= %d", AZH_SEARCH_SETS_MAX);
+    const u32 w = search_set_pairing(uid, (u32)n);
+    out[0] = (int32_t)(w & 0xFFu);
+    out[1] = (int32_t)(w >> 8);
+    return 0;
+}
+
+// The tally of the games' results by (set of x, set of o) since the sets were set: out [n][n][AZH_SET_STAT_COUNT].
+extern "C" int azh_engine_search_set_stats(azh_engine *e, uint64_t *out)
+{
+    if (!e || !out)
+        return azh_fail(-1, "azh_engine_search_set_stats: bad argument");
+    const size_t n = (size_t)e->P.n_search_sets;
+    if (n == 0)
+        return 0;
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    AZH_HIP(hipMemcpy(out, e->P.set_stats, n * n * AZH_SET_STAT_COUNT * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2275,6 +2396,9 @@ extern "C" int azh_engine_set_visits(azh_engine *e, int visits)
         return azh_fail(-1, "azh_engine_set_visits: need 1 <= visits <= %d", e ? e->cfg.visits : 0);
     if (visits < e->P.fast_visits)
         return azh_fail(-2, "azh_engine_set_visits: %d is below the playout cap's fast_visits %d", visits, e->P.fast_visits);
+    for (int i = 0; i < e->P.n_search_sets; i++)
+        if (visits < e->sets[i].visits)
+            return azh_fail(-2, "azh_engine_set_visits: %d is below the visits %d of search set %d", visits, e->sets[i].visits, i);
     if (e->P.gumbel_m != 0 && (long long)e->P.gumbel_m * visits > GUMBEL_MAX_TABLE)
         return azh_fail(-2, "azh_engine_set_visits: the Gumbel root search is on with m = %d: m * visits may not exceed %d",
                         e->P.gumbel_m, GUMBEL_MAX_TABLE);

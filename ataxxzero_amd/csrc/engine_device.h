@@ -110,6 +110,13 @@ struct EngineParams {
     // while fpu_reduction < 0 and c_base == 0 (exploration_on)
     float fpu_reduction;        // an unvisited child's Q is the node's mean score less this * sqrt(visited policy mass); < 0: 0
     float c_base, c_init;       // c = log((1 + N + c_base) / c_base) + c_init; c_base == 0: the constant c_puct
+    // search settings per side (azh_engine_set_search_sets; DESIGN.md "Search settings per side"), off while search_sets is null
+    const azh_search_set *search_sets;  // [n_search_sets] on the device: k_vl_tree loads the set of the root's mover (a table
+    int n_search_sets;                  // in this block would ride in every launch's kernel arguments)
+    u32 *slot_sets;             // [G] the set of x | the set of o << 8 in each slot's current game (search_set_pairing), written
+                                // where a game begins (begin_game_key)
+    u64 *set_stats;             // [n][n][AZH_SET_STAT_COUNT] once-per-game counts by (set of x, set of o): global atomics at a
+                                // game's end, in k_advance_list's advance_game alone
 };
 
 // The walls slot g's game is played on (g wave-uniform: one scalar 8-byte load); the engine's one mask while no pool is set.
@@ -146,6 +153,8 @@ __device__ inline void begin_game_key(const EngineParams &P, int g, u32 uid)
     }
     if (P.resign_plies != 0u && lane_id() == 0)  // the game's resign counters (the same instantiations: every game start but
         P.resign_state[g] = 0u;                  // the tower kernels', which play no move while the mode is on)
+    if (P.search_sets != nullptr && lane_id() == 0)  // the game's pairing (search settings per side; the same instantiations)
+        P.slot_sets[g] = search_set_pairing(uid, (u32)P.n_search_sets);
 }
 
 // The kind word of slot g's ply as the tree kernels use it (g wave-uniform: a scalar load); PLY_FULL while the mode is off.
@@ -921,6 +930,11 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
     };
     const int loaded = P.no_emit[g] & NO_EMIT_PLY;  // start ply + 1 of a game that began at a loaded position, else 0
     const int p0 = loaded ? loaded - 1 : 0;     // first ply this game recorded
+    u32 sets_word = 0;  // search settings per side: the pairing of the game that may end here (its successor's start overwrites it)
+    if constexpr (OWN) {
+        if (P.search_sets != nullptr)
+            sets_word = P.slot_sets[g];
+    }
     if (no_sample) {
         st_dropped = 1;
         drop_marker();
@@ -994,6 +1008,18 @@ __device__ inline void advance_game(const EngineParams &P, int g, TreeLds &L)
         if constexpr (OWN) {
             if (P.resign_plies != 0u && lane == 0)
                 P.resign_state[g] = rs_word;
+        }
+    }
+    if constexpr (OWN) {
+        // search settings per side: the once-per-game tally by (set of x, set of o), wherever the game was counted above
+        if (P.search_sets != nullptr && (st_games | st_dropped) != 0 && lane == 0) {
+            u64 *t = P.set_stats + ((size_t)(sets_word & 0xFFu) * (size_t)P.n_search_sets + (size_t)((sets_word >> 8) & 0xFFu)) *
+                                       AZH_SET_STAT_COUNT;
+            atomicAdd((unsigned long long *)&t[AZH_SET_STAT_GAMES], 1ull);
+            if (cut)
+                atomicAdd((unsigned long long *)&t[AZH_SET_STAT_UNDECIDED], 1ull);
+            else if (result == 1 || result == 2)
+                atomicAdd((unsigned long long *)&t[result == 1 ? AZH_SET_STAT_X_WINS : AZH_SET_STAT_O_WINS], 1ull);
         }
     }
     if (lane == 0) {

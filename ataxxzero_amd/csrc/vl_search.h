@@ -37,18 +37,59 @@ struct VlParams {
     u64 *proofs;      // [G][2] counters of the proof pass: AZH_PROOF_STAT_NODES, _HITS (azh_engine_proof_stats)
 };
 
+// What the ply of a game searches with: the engine's own settings, or (azh_engine_set_search_sets) the set of the side to move
+// at the root.  Wave-uniform, resolved once per game and launch by k_vl_tree.
+struct PlySearch {
+    int visits, leaves, vl;  // root visits at which the move is due; paths per iteration; the virtual loss
+    float c_puct, fpu_reduction, c_base, c_init;
+};
+
+__device__ inline PlySearch engine_search(const EngineParams &P, const VlParams &V, u32 pk)
+{
+    PlySearch S;
+    S.visits = ply_threshold(P, pk);
+    S.leaves = V.K;
+    S.vl = V.vl;
+    S.c_puct = P.c_puct;
+    S.fpu_reduction = P.fpu_reduction;
+    S.c_base = P.c_base;
+    S.c_init = P.c_init;
+    return S;
+}
+
+// Search settings per side: the set of the root's mover — the root board's turn bit picks the byte of the slot's word, and the
+// set's seven values come from the table on the device.  g, s: wave-uniform, and so is every load here (readfirstlane: the
+// values live in scalar registers beside the engine's own, which they replace).  The root is the same for the backup, the
+// mark and the select of one launch: a batch's backup removes the virtual loss its select put on.
+__device__ inline void set_search(const EngineParams &P, int g, const azh_game_state &s, PlySearch &S)
+{
+    if (P.search_sets == nullptr)
+        return;
+    const u64 w0 = arena_of(P, s.arena, g).nb[0].x;
+    const u32 word = P.slot_sets[g];
+    const int i = __builtin_amdgcn_readfirstlane((int)((w0 & TURN_BIT) ? (word >> 8) & 0xFFu : word & 0xFFu));
+    const azh_search_set &t = P.search_sets[i];
+    S.visits = __builtin_amdgcn_readfirstlane(t.visits);
+    S.leaves = __builtin_amdgcn_readfirstlane(t.leaves);
+    S.vl = __builtin_amdgcn_readfirstlane(t.virtual_loss);
+    S.c_puct = u2f((u32)__builtin_amdgcn_readfirstlane((int)f2u(t.c_puct)));
+    S.fpu_reduction = u2f((u32)__builtin_amdgcn_readfirstlane((int)f2u(t.fpu_reduction)));
+    S.c_base = u2f((u32)__builtin_amdgcn_readfirstlane((int)f2u(t.c_base)));
+    S.c_init = u2f((u32)__builtin_amdgcn_readfirstlane((int)f2u(t.c_init)));
+}
+
 // Selects the game's batch: k paths in path order (phase 1), the root evaluation (phase 0, slot 0), or nothing.  `s` is
 // the game's state in registers (uniform over the lanes); stored here.  Returns the slots that need the net (bit p: slot p).
-// `pk`: the ply's kind word (its threshold is the T of k below).
-__device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, int g, azh_game_state &s, u16 *s_moves, u32 pk)
+// `S`: what the ply searches with (its visits are the T of k below, its leaves the K).
+__device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, int g, azh_game_state &s, u16 *s_moves, const PlySearch &S)
 {
     const int lane = lane_id();
     const int K = V.K;
     const size_t base = (size_t)g * K;
     Arena A = arena_of(P, s.arena, g);
     const u32 tie_flip = (P.flags & AZH_FLAG_TIE_FIRST) ? 0xFFFFFFFFu : 0u;
-    // first-play urgency and the exploration rate (azh_engine_set_exploration): wave-uniform, a kernel argument
-    const bool explore = exploration_on(P.fpu_reduction, P.c_base);
+    // first-play urgency and the exploration rate (azh_engine_set_exploration, or the ply's search set): wave-uniform
+    const bool explore = exploration_on(S.fpu_reduction, S.c_base);
     // lane p collects slot p's result
     int r_kind = AZH_LEAF_NONE, r_node = 0, r_len = 0;
     u32 r_edge = NONE;
@@ -71,7 +112,7 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
         s.leaf_kind = AZH_LEAF_ROOT;
     } else {
         const int nodes0 = s.n_nodes;  // nodes from this id on were created by this batch (unevaluated until its backup)
-        const int k = max(1, min(K, ply_threshold(P, pk) - s.root_visits));
+        const int k = max(1, min(S.leaves, S.visits - s.root_visits));
         const uint4 rinfo = A.ni[0];
         const u32 root_kid = pack_kid(rinfo.x, rinfo.y & 0xFFFFu, (rinfo.y >> 16) != 0u);
         for (int p = 0; p < k; p++) {
@@ -109,7 +150,7 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
                 const u32 N = wave_sum_u32(nsum);
                 const float sq = sqrtf((float)(1u + N));
                 // c and the unvisited children's Q: c_puct and 0 unless the mode is on (exploration_score is then puct_score)
-                float c = P.c_puct, fpu = 0.0f;
+                float c = S.c_puct, fpu = 0.0f;
                 if (explore) {
                     float wpart = 0.0f, ppart = 0.0f;  // the lane's terms j = lane, lane + 64, ... from +0 in that order
 #pragma unroll
@@ -119,8 +160,8 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
                             ppart = ppart + (edge_visits(ev[r]) ? __builtin_fabsf(u2f(ev[r].x)) : 0.0f);
                         }
                     const float Wsum = wave_sum_f32(wpart), Psum = wave_sum_f32(ppart);
-                    c = exploration_c(N, P.c_puct, P.c_base, P.c_init);
-                    fpu = exploration_fpu(Wsum, Psum, N, P.fpu_reduction);
+                    c = exploration_c(N, S.c_puct, S.c_base, S.c_init);
+                    fpu = exploration_fpu(Wsum, Psum, N, S.fpu_reduction);
                 }
                 // arg-max with the engine's tie rule: (score bits << 32 | index or ~index), NaN and empty lanes key 0
                 u64 key = 0;
@@ -150,7 +191,7 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
                 const u32 child = zsel >> 16;
                 if (child != ENONE) {
                     if (lane == 0)  // the path's virtual loss on this edge
-                        reinterpret_cast<u32 *>(&A.ed[eidx])[2] = zsel + (u32)V.vl;
+                        reinterpret_cast<u32 *>(&A.ed[eidx])[2] = zsel + (u32)S.vl;
                     node = child;
                     kid = wsel;
                     continue;
@@ -167,7 +208,7 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
                     over = 1;
                     kind = AZH_LEAF_NONE;
                     if (lane == 0)
-                        reinterpret_cast<u32 *>(&A.ed[eidx])[2] = zsel + (u32)V.vl;
+                        reinterpret_cast<u32 *>(&A.ed[eidx])[2] = zsel + (u32)S.vl;
                     break;
                 }
                 const u32 cid = (u32)s.n_nodes;
@@ -199,7 +240,7 @@ __device__ inline u64 vl_select_game(const EngineParams &P, const VlParams &V, i
                     A.nb[cid] = make_ulonglong2(pack_word0(cb), cb.o);
                     // the edge gets its child, the child's range, and this path's virtual loss
                     reinterpret_cast<uint2 *>(&A.ed[eidx])[1] =
-                        make_uint2((cid << 16) | (u32)V.vl, res2 != 0 ? pack_kid(0u, 0u, 1u) : pack_kid(nf, (u32)M2, 0u));
+                        make_uint2((cid << 16) | (u32)S.vl, res2 != 0 ? pack_kid(0u, 0u, 1u) : pack_kid(nf, (u32)M2, 0u));
                 }
                 node = cid;
                 break;
@@ -371,7 +412,8 @@ __device__ inline void vl_prove(const EngineParams &P, const VlParams &V, int g,
 // The batch's edge backup (one wave; lane p = path p).  Level by level — the paths that share an edge share it at the
 // same depth — every edge gets ONE read-modify-write: W plus the scores of the EVAL and TERMINAL paths through it in path
 // order (f32, the oracle's per-level inversion), visits plus those paths minus every path's virtual loss.
-__device__ inline void vl_backup_edges(const EngineParams &P, const VlParams &V, int g, azh_game_state &s)
+// `vl`: the virtual loss of the ply's search (the select that made the batch put it on).
+__device__ inline void vl_backup_edges(const EngineParams &P, const VlParams &V, int g, azh_game_state &s, int vl)
 {
     const int lane = lane_id();
     if (s.leaf_kind == AZH_LEAF_ROOT) {
@@ -430,10 +472,10 @@ __device__ inline void vl_backup_edges(const EngineParams &P, const VlParams &V,
             }
         }
         if (on && d == len - 1)
-            fresh = (z & 0xFFFFu) == (u32)V.vl * paths;
+            fresh = (z & 0xFFFFu) == (u32)vl * paths;
         if (leader) {
             rec[1] = f2u(W);
-            rec[2] = z + adds - (u32)V.vl * paths;  // (visits: the low half; never borrows from the child id)
+            rec[2] = z + adds - (u32)vl * paths;  // (visits: the low half; never borrows from the child id)
         }
     }
     s.root_visits += (int)wave_sum_u32((counted && len > 0) ? 1u : 0u);
@@ -456,19 +498,22 @@ __global__ __launch_bounds__(VL_WAVES * WAVE) void k_vl_tree(EngineParams P, VlP
     azh_game_state s = P.gs[g];
     const int forced = P.force[g];
     const u32 pk = ply_kind_of(P, g);
+    PlySearch S = engine_search(P, V, pk);
+    if (w == 0)
+        set_search(P, g, s, S);  // (the other waves compute priors: none of these values)
     if (mode & 1) {
         vl_backup_priors(P, V, g, s, w, pk);
         if (w == 0)
-            vl_backup_edges(P, V, g, s);
+            vl_backup_edges(P, V, g, s, S.vl);
         __threadfence_block();
         __syncthreads();
     }
     u64 need = 0;
     if (w == 0) {
         if (mode & 1)
-            mark_game(P, g, s, forced, pk);
+            mark_game_at(P, g, s, forced, S.visits);
         if (mode & 2)
-            need = vl_select_game(P, V, g, s, s_moves, pk);  // stores the state
+            need = vl_select_game(P, V, g, s, s_moves, S);  // stores the state
         else if (lane_id() == 0)
             P.gs[g] = s;
     }

@@ -92,6 +92,18 @@ class Timing(ctypes.Structure):
                 ("iterations", ctypes.c_int64), ("net_evals", ctypes.c_int64)]
 
 
+class SearchSet(ctypes.Structure):                            # azh_search_set
+    _fields_ = [("visits", ctypes.c_int32), ("leaves", ctypes.c_int32), ("virtual_loss", ctypes.c_int32),
+                ("c_puct", ctypes.c_float), ("fpu_reduction", ctypes.c_float), ("c_base", ctypes.c_float),
+                ("c_init", ctypes.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+SEARCH_SETS_MAX = 16
+SET_STAT_GAMES, SET_STAT_X_WINS, SET_STAT_O_WINS, SET_STAT_UNDECIDED, SET_STAT_COUNT = 0, 1, 2, 3, 4
+
 _vp, _i32, _u64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_float
 _P = ctypes.POINTER
 
@@ -161,6 +173,10 @@ SIGNATURES = {
     "azh_engine_set_exploration": (ctypes.c_int, [_vp, _f32, _f32, _f32]),
     "azh_engine_exploration": (ctypes.c_int, [_vp, _vp]),
     "azh_exploration_scores": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _f32, _f32, _f32, _f32, _vp]),
+    "azh_engine_set_search_sets": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
+    "azh_engine_search_sets": (ctypes.c_int, [_vp, _P(_i32), _vp]),
+    "azh_search_set_pairing": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_int, _vp]),
+    "azh_engine_search_set_stats": (ctypes.c_int, [_vp, _vp]),
     "azh_engine_root_proofs": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
     "azh_engine_play_moves": (ctypes.c_int, [_vp, _vp, _vp]),
     "azh_engine_root_report": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
@@ -375,6 +391,15 @@ def start_pool_entry(uid, n, stride=1):
     if r < 0:
         check(r)
     return r
+
+
+def search_set_pairing(uid, n):
+    """-> (set of x, set of o) in game `uid` among n search sets (Engine.set_search_sets): uids 2q and 2q + 1 are the q-th
+    unordered pair, in lexicographic order and round robin, with the colours swapped (azh_search_set_pairing; host arithmetic,
+    no device)."""
+    out = np.zeros(2, dtype=np.int32)
+    check(load().azh_search_set_pairing(int(uid), int(n), _ptr(out)))
+    return int(out[0]), int(out[1])
 
 
 def playout_cap_kind(seed, uid, ply, full_per_65536):
@@ -790,6 +815,32 @@ class Engine:
         out = np.zeros(3, dtype=np.float32)
         check(load().azh_engine_exploration(self.h, _ptr(out)))
         return float(out[0]), float(out[1]), float(out[2])
+
+    def set_search_sets(self, sets):
+        """Search settings per side ("Search settings per side"): `sets` is a list of up to 16 dicts with the keys
+        of SearchSet (visits, leaves, virtual_loss, c_puct, fpu_reduction, c_base, c_init) or tuples in that order.  In game
+        uid x and o search with the sets link.search_set_pairing(uid, n) names, every ply with the set of the side to move at
+        its root, and the device tallies the results (search_set_stats).  While it is on every K, 1 included, runs through
+        the leaf-parallel kernel (batch_leaves / set_batch_evals).  An empty list: off.  Between iterations only."""
+        rows = (SearchSet * max(len(sets), 1))()
+        for i, t in enumerate(sets):
+            rows[i] = SearchSet(**t) if isinstance(t, dict) else SearchSet(*t)
+        check(load().azh_engine_set_search_sets(self.h, len(sets), ctypes.cast(rows, ctypes.c_void_p)))
+
+    def search_sets(self):
+        """-> the sets in force, a list of dicts (empty while the mode is off)."""
+        n = ctypes.c_int32(0)
+        rows = (SearchSet * SEARCH_SETS_MAX)()
+        check(load().azh_engine_search_sets(self.h, ctypes.byref(n), ctypes.cast(rows, ctypes.c_void_p)))
+        return [rows[i].as_dict() for i in range(n.value)]
+
+    def search_set_stats(self):
+        """-> (n, n, 4) uint64, indexed [set of x][set of o][SET_STAT_GAMES / _X_WINS / _O_WINS / _UNDECIDED]: the games that
+        ended since set_search_sets, counted on the device."""
+        n = len(self.search_sets())
+        out = np.zeros((n, n, SET_STAT_COUNT), dtype=np.uint64)
+        check(load().azh_engine_search_set_stats(self.h, _ptr(out)))
+        return out
 
     def proof_stats(self):
         """-> {"proven_nodes", "proven_hits"}: nodes the proof pass proved; paths that ended at a proven node."""

@@ -251,19 +251,20 @@ int azh_engine_sync(azh_engine *e);
 /* change the root-visit threshold (global_visits) for the coming moves; 1 <= visits <= the
  * value the engine was created with */
 int azh_engine_set_visits(azh_engine *e, int visits);
-/* SEARCH MODES: WHO REFUSES WHOM.  Nine modes are switched by setters below, before the first select or between iterations.
+/* SEARCH MODES: WHO REFUSES WHOM.  Ten modes.  Nine modes are switched by setters below, each by values of its own, and the
+ * tenth by a table of search sets (azh_engine_set_search_sets); all of them before the first select or between iterations.
  * A call that switches a mode on is a request for it; one that switches it off is not, and is never refused for a reason in
  * this table.  Every one of these setters checks in this order, and changes nothing unless every check passes: -1 a null
  * engine, -2 a value out of range, -3 a selected batch awaits its backup (requests and switching off alike), -4 the request
  * is refused by a row of this table.
  *
  *   mode            is on while                 refused on an engine created with                         refused beside
- *   playout cap     fast_visits != 0            TWO_NETS, ONE_RANDOM_MOVE                                 Gumbel
+ *   playout cap     fast_visits != 0            TWO_NETS, ONE_RANDOM_MOVE                                 Gumbel, search sets
  *   forced playouts k != 0                      TWO_NETS, ONE_RANDOM_MOVE                                 Gumbel, leaf batch, solver,
- *                                                                                                         exploration
+ *                                                                                                         exploration, search sets
  *   Gumbel          m != 0                      TWO_NETS, ONE_RANDOM_MOVE, SAMPLE_POW5, EVAL_CACHE;       playout cap, forced playouts,
  *                                               without NO_REUSE; dirichlet_weight != 0                   temperature, leaf batch, solver,
- *                                                                                                         exploration
+ *                                                                                                         exploration, search sets
  *   temperature     either table is set         TWO_NETS, ONE_RANDOM_MOVE, SAMPLE_POW5, PY_POSTERIOR      Gumbel
  *   resign          consecutive != 0            TWO_NETS, ONE_RANDOM_MOVE                                 -
  *   random symmetry on != 0                     TWO_NETS, SYMMETRY_AVG; a blockers mask that is not its   -
@@ -271,7 +272,9 @@ int azh_engine_set_visits(azh_engine *e, int visits);
  *   leaf batch      leaves_per_game > 1         TWO_NETS, EVAL_CACHE, SYMMETRY_AVG; select_budget > 0     Gumbel, forced playouts
  *   solver          on != 0                     TWO_NETS, EVAL_CACHE, SYMMETRY_AVG; select_budget > 0     Gumbel, forced playouts
  *   exploration     fpu_reduction >= 0 ||       TWO_NETS, EVAL_CACHE, SYMMETRY_AVG; select_budget > 0     Gumbel, forced playouts
- *                   c_base > 0
+ *                   c_base > 0                                                                            (and search sets)
+ *   search sets     n != 0                      TWO_NETS, ONE_RANDOM_MOVE, EVAL_CACHE, SYMMETRY_AVG;      Gumbel, forced playouts,
+ *                                               select_budget > 0                                         playout cap, exploration
  *
  * The last column is symmetric: of two modes that exclude each other, whichever is asked for second is refused, and comes on
  * once the other is off.  Everything not listed composes.  The message (azh_last_error) is "<setter>: not supported with
@@ -280,10 +283,12 @@ int azh_engine_set_visits(azh_engine *e, int visits);
  * > 0", the blockers mask, or the mode that is on with its setter: "the playout cap (azh_engine_set_playout_cap)", "forced
  * playouts (azh_engine_set_forced_playouts)", "the Gumbel root search (azh_engine_set_gumbel)", "a temperature table
  * (azh_engine_set_temperature)", "more than one leaf per game (azh_engine_set_leaf_batch)", "the solver", "first-play
- * urgency or a growing exploration rate (azh_engine_set_exploration)"; Gumbel on an engine
+ * urgency or a growing exploration rate (azh_engine_set_exploration)", "search settings per side
+ * (azh_engine_set_search_sets)"; Gumbel on an engine
  * without NO_REUSE or with a dirichlet_weight says that the engine must have been created with both.  Where several causes
  * apply the message names one: a flag before anything else, in the order TWO_NETS, ONE_RANDOM_MOVE, SAMPLE_POW5, PY_POSTERIOR,
- * EVAL_CACHE, SYMMETRY_AVG, then the other create-time causes, then the modes, Gumbel first.  The paragraphs below say why. */
+ * EVAL_CACHE, SYMMETRY_AVG, then the other create-time causes, then the modes, Gumbel first, the pairs of the search sets
+ * last.  The paragraphs below say why. */
 /* Leaf-parallel search (an extension; the reference searches one leaf per tree at a time): every game selects up to
  * `leaves_per_game` = K leaves per iteration (1 <= K <= 64), spread over different lines by a virtual loss of
  * `virtual_loss` visits (1 .. 16) on every edge an earlier path of the batch took; the leaves of all games are evaluated
@@ -587,6 +592,54 @@ int azh_engine_exploration(const azh_engine *e, float *out);
  * arithmetic only, usable without a device: the functions the device's level uses, the two sums restated lane by lane. */
 int azh_exploration_scores(const float *prior, const float *W, const uint32_t *n, int M, float c_puct, float fpu_reduction,
                            float c_base, float c_init, float *scores_out);
+
+/* Search settings per side (an extension, off by default; DESIGN.md, "Search settings per side"): the two sides of a game
+ * search with different settings inside the device-resident loop, every setting meets every other with the colours swapped,
+ * and the device keeps the result table.  A SEARCH SET is what one side searches with: */
+typedef struct azh_search_set {
+    int32_t visits;          /* root visits at which this side's move is due */
+    int32_t leaves;          /* paths per iteration: k = max(1, min(leaves, visits - root_visits)) */
+    int32_t virtual_loss;
+    float   c_puct;
+    float   fpu_reduction;   /* < 0: off, as azh_engine_set_exploration */
+    float   c_base, c_init;  /* c_base == 0: the constant c_puct */
+} azh_search_set;
+#define AZH_SEARCH_SETS_MAX 16
+/* azh_engine_set_search_sets(e, n, sets), 0 <= n <= AZH_SEARCH_SETS_MAX: the sets are copied to the device, every slot learns
+ * the pairing of the game it holds, and the tally (below) is zeroed.  n = 0 switches the mode off.
+ * PAIRING.  For n >= 2 let q = uid / 2 and t = q % (n (n - 1) / 2); (a, b), a < b, is the t-th unordered pair in
+ * lexicographic order.  In game uid x plays a and o plays b if uid is even, and the other way round if it is odd: uids 2q and
+ * 2q + 1 are one pairing with the colours swapped (and share their opening under azh_engine_set_start_pool with stride 2), and
+ * any n (n - 1) consecutive uids that start at a multiple of that number hold every ordered pair exactly once.  n = 1: (0, 0).
+ * azh_search_set_pairing restates the rule on the host (out [2] = the set of x, the set of o); host and kernels run one function.
+ * A PLY'S SET is the set of the side to move at the root (the root board's turn bit, not the ply's parity), whether the root
+ * was reached by the engine's own move, by azh_engine_play_moves or loaded by azh_engine_set_positions.
+ * While the mode is on every ply searches with its set: its move is due at the set's `visits`; a select takes up to the
+ * set's `leaves` paths with the set's `virtual_loss`; a level scores with the set's c_puct, fpu_reduction, c_base and c_init
+ * under the rule of azh_engine_set_exploration; a batch's backup removes the virtual loss of the set that selected it.  The
+ * engine's own visits, c_puct and virtual loss are not used for the search of a ply; its leaves_per_game K stays the stride
+ * of the leaf slots (g K + p), and no set may ask for more leaves.  Everything else is what it is without the mode: root
+ * noise, the tie rule, expansion, backup, the move's draw, records, game lines, the re-root.  Every K, 1 included, runs
+ * through the leaf-parallel kernel (the step-wise calls are azh_engine_batch_leaves / _set_batch_evals), and the device loop
+ * plays the queued moves in a launch of their own.  With tree reuse a new root inherits the subtree the other side's settings
+ * built; that is allowed, and a match tool wants AZH_FLAG_NO_REUSE.
+ * -2, the first offending set named: visits outside 1 .. the engine's current visits; leaves outside 1 .. K in force;
+ * virtual_loss outside 1 .. 16 (so leaves * virtual_loss <= 1024, the leaf batch's bound); c_puct not finite or < 0;
+ * fpu_reduction, c_base, c_init as azh_engine_set_exploration checks them.  While sets are on azh_engine_set_visits below a
+ * set's visits and azh_engine_set_leaf_batch below a set's leaves are refused with -2.  -3, -4: the table above.  A refused
+ * call changes nothing.  Composes with the leaf batch, the solver, temperature, resign, random symmetry, the start pool, the
+ * game limit, azh_engine_set_positions and azh_engine_play_moves.
+ * TALLY.  azh_engine_search_set_stats: out [n][n][AZH_SET_STAT_COUNT], indexed [set of x][set of o], counted once per game
+ * where AZH_STAT_GAMES or AZH_STAT_DROPPED is: GAMES every such game, X_WINS / O_WINS by the result (a resigned game by its
+ * result), UNDECIDED a game cut at the ply limit (the rules know no draw), so GAMES = X_WINS + O_WINS + UNDECIDED. */
+int azh_engine_set_search_sets(azh_engine *e, int n, const azh_search_set *sets);
+/* the sets in force: *n_out their number (0: the mode is off), sets_out [AZH_SEARCH_SETS_MAX] or NULL */
+int azh_engine_search_sets(const azh_engine *e, int32_t *n_out, azh_search_set *sets_out);
+/* out [2] = the set of x, the set of o in game `uid` among n sets; -1 for a null out, -2 for n outside 1 ..
+ * AZH_SEARCH_SETS_MAX.  Host arithmetic only, usable without a device. */
+int azh_search_set_pairing(uint32_t uid, int n, int32_t *out);
+enum { AZH_SET_STAT_GAMES = 0, AZH_SET_STAT_X_WINS = 1, AZH_SET_STAT_O_WINS = 2, AZH_SET_STAT_UNDECIDED = 3, AZH_SET_STAT_COUNT = 4 };
+int azh_engine_search_set_stats(azh_engine *e, uint64_t *out /* [n][n][AZH_SET_STAT_COUNT] */);
 
 /* Which tower the device-resident loop evaluates its leaves with: 0 the 3-board workgroups (throughput), 1 one board per
  * workgroup (latency: azh_net_forward_thin's kernel), -1 (default) by the engine's size — thin for engines of at most

@@ -11,6 +11,11 @@ still on there — is played twice, the mode's side once x and once o.  Both sid
 K = --parallel-leaves, a fresh tree per move.  Reported: games, the mode's side's wins, losses and unfinished games, its score
 of the decided games and the 95 % interval of that score (Wilson).
 
+HOW TO MEASURE: this tool plays one game at a time on one position at a time, so 200 games at 400 visits take a quarter of
+an hour and leave an interval of about +-7 points.  tools/settings_match.py plays the same comparison — and any other between
+search settings — inside the device-resident loop, thousands of games in flight:
+    python tools/settings_match.py --network model.npy --set visits=400 --set visits=400,fpu=0.25,cpuct-base=19652,cpuct-init=1.25
+
     python tools/exploration_match.py --network model.npy [--fpu-reduction 0.25] [--cpuct-base 19652 --cpuct-init 1.25]
                                       [--games 200] [--visits 400] [--opening-plies 8] [--out profiles/FILE.txt]
 """

@@ -6,6 +6,10 @@ still on there — is played twice, the solver's side once x and once o.  Both s
 visits, K = --parallel-leaves, a fresh tree per move; the net has random weights (--blocks x 128).  Reported: the solver
 side's wins, losses and score, the moves it played, and the share of them it played as proven (win or loss).
 
+HOW TO MEASURE: one game at a time on one position at a time is slow (200 games at 400 visits: a quarter of an hour).  Search
+settings are compared inside the device-resident loop by tools/settings_match.py, thousands of games in flight, with --solver
+for both sides; the solver itself is one switch for both sides there, so solver on against off stays this tool's.
+
     python tools/solver_match.py [--games 200] [--visits 400] [--opening-plies 60] [--out profiles/FILE.txt]
 """
 import argparse
