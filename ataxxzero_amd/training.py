@@ -696,6 +696,28 @@ def all_losses(net, features, policies, values, ownership, score, reply, aux_wei
     return (policy_loss, value_loss, reg) + _aux_loss_terms(aux, ownership, score, reply, aux_weight)
 
 
+def make_optimizer(net, learning_rate):
+    """tf.train.MomentumOptimizer(learning_rate, 0.9) (model.py:99-100): v <- 0.9 v + g, w <- w - lr v."""
+    return torch.optim.SGD(net.parameters(), lr=learning_rate, momentum=0.9)
+
+
+def train_step(net, opt, batch, aux_loss_weights=None):
+    """One optimisation step of a net that is in train() mode on one minibatch -> the loss terms, as tensors.  batch: the three
+    tensors of losses; with aux_loss_weights = (ownership, score, reply) the seven of all_losses, the three auxiliary terms
+    added with those weights — one pass through the tower for all five heads."""
+    if aux_loss_weights is not None:
+        w_own, w_score, w_reply = aux_loss_weights
+        terms = pl, vl, reg, ol, sl, rl = all_losses(net, *batch)
+        loss = pl + vl + reg + w_own * ol + w_score * sl + w_reply * rl
+    else:
+        terms = pl, vl, reg = losses(net, *batch)
+        loss = pl + vl + reg
+    opt.zero_grad(set_to_none=True)
+    loss.backward()
+    opt.step()
+    return terms
+
+
 def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learning_rate=0.001, blocks=12, filters=128,
           reference_bn_affine=False, device=None, log=print, value_blend=0.0, device_samples=False, device_draws=False,
           surprise_weight=0.0, surprise_dtype="bf16", aux_ownership=0.0, aux_score=0.0, aux_reply=0.0):
@@ -743,7 +765,7 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
     else:
         net = Network(blocks, filters, reference_bn_affine).to(device)
     net.load_numpy(cw, bnp)
-    opt = torch.optim.SGD(net.parameters(), lr=learning_rate, momentum=0.9)   # tf.train.MomentumOptimizer (model.py:99-100)
+    opt = make_optimizer(net, learning_rate)
 
     def to_dev(batch):
         return tuple(torch.from_numpy(a).to(device) for a in batch)
@@ -804,16 +826,7 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
             log("Step: %4i -- loss: %.6f  (policy: %.6f  value: %.6f%s)" % (step_number, float(pl + vl), float(pl), float(vl), tail))
             check_store()
         net.train()
-        batch = next_batch(step_number)
-        if aux:                                                           # one pass through the tower for all five heads
-            pl, vl, reg, ol, sl, rl = all_losses(net, *batch)
-            loss = pl + vl + reg + aux_ownership * ol + aux_score * sl + aux_reply * rl
-        else:
-            pl, vl, reg = losses(net, *batch)
-            loss = pl + vl + reg
-        opt.zero_grad(set_to_none=True)
-        loss.backward()
-        opt.step()
+        train_step(net, opt, next_batch(step_number), (aux_ownership, aux_score, aux_reply) if aux else None)
     check_store()
     model.save_model(new_path, *net.to_numpy())
     log("\x1b[35mSaved model to:\x1b[0m %s" % new_path)
