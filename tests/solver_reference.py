@@ -25,8 +25,7 @@ from tests import vl_reference as vlr
 NONE = vlr.NONE
 LEAF_NONE, LEAF_EVAL, LEAF_TERMINAL, LEAF_ROOT, LEAF_COLLISION = (vlr.LEAF_NONE, vlr.LEAF_EVAL, vlr.LEAF_TERMINAL,
                                                                   vlr.LEAF_ROOT, vlr.LEAF_COLLISION)
-WIN_BITS, LOSS_BITS = 0x3F800000, 0xBF800000   # +1.0f, -1.0f
-_PROVEN_FLAG = 0x80000000                      # select()'s private mark in a copy of info word 1: never handed out
+WIN_BITS, LOSS_BITS, is_proven = vlr.WIN_BITS, vlr.LOSS_BITS, vlr.is_proven
 
 
 def decided_value(info_row):
@@ -37,24 +36,10 @@ def decided_value(info_row):
     return 1 if w == WIN_BITS else -1
 
 
-def is_proven(info_row):
-    """Decided without being a finished position."""
-    return (int(info_row[1]) >> 16) == 0 and int(info_row[3]) in (WIN_BITS, LOSS_BITS)
-
-
-def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers):
-    """vl_reference.select on a tree in which every proven node but the root ends a path like a finished position."""
-    boards, info, edges, moves = tree
-    info = np.array(info, dtype=np.uint32).reshape(-1, 4).copy()
-    marked = [n for n in range(1, len(info)) if is_proven(info[n])]
-    for n in marked:
-        info[n, 1] |= _PROVEN_FLAG   # vl_reference: "result != 0" ends the path, its value is info word 3
-    b = vlr.select((boards, info, edges, moves), root_visits, visits, K, VL, c_puct, tie_first, blockers)
-    b.nodes0 = len(info)   # nodes from this id on were created by this batch
-    for n in marked:
-        b.info[n][1] &= ~_PROVEN_FLAG
-    b.proven_hits = sum(1 for p, k in enumerate(b.kind) if k == LEAF_TERMINAL and b.leaf_node[p] in set(marked))
-    return b
+def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers, node_cap=None, edge_cap=None):
+    """vl_reference.select in which every proven node but the root ends a path like a finished position."""
+    return vlr.select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers, node_cap, edge_cap,
+                      proven_end_paths=True)
 
 
 def prove(b):

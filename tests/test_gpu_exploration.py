@@ -12,17 +12,15 @@ import numpy as np
 import pytest
 
 from ataxxzero_amd import link, model
-from oracle import oracle_lib as orc
 from tests import engine_harness as eh
 from tests import exploration_reference as xr
 from tests import helpers
-from tests import solver_reference as sr
-from tests import vl_reference as vlr
+from tests import leaf_lockstep as lls
 
 pytestmark = pytest.mark.gpu
 
 ROOT = helpers.ROOT
-UAI = link.FLAG_NO_REUSE | link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR
+UAI = lls.UAI
 FPU, RATE, BOTH = (0.25, 0.0, 0.0), (-1.0, 19652.0, 1.25), (0.25, 19652.0, 1.25)
 PARAMS = [FPU, RATE, BOTH]
 SHAPES = [(1, 1, 1, UAI, 0), (1, 64, 3, UAI, 0), (5, 7, 3, 0, helpers.BLOCK4_MASK), (5, 64, 1, 0, 0)]   # (G, K, VL, flags, blockers)
@@ -32,94 +30,30 @@ CASES = [(shape, params, family, False) for family in ("late", "start") for shap
 CASES.append(((5, 7, 3, 0, helpers.BLOCK4_MASK), BOTH, "late", True))
 
 
-def _config(G, flags, blockers=0, visits=160, seed=11, **more):
-    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
-    return link.Config(games=G, visits=visits, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
-                       dirichlet_weight=0.0 if flags else 0.25, start_turn=0, seed=seed, start_x=int(p.pieces[0]),
-                       start_o=int(p.pieces[1]), blockers=blockers, flags=flags, **more)
+def _engine(G, K, VL, flags, blockers=0, visits=160, seed=11, params=None, solver=False, family="late"):
+    return lls.engine(G, flags, blockers, visits, seed, start=family, leaf_batch=(K, VL), solver=solver, exploration=params)
 
 
-def _late(G, blockers, max_empty=10):
-    ps = [(w0, w1) for w0, w1, bl in sr.late_positions(max_empty) if bl == blockers]
-    assert len(ps) >= G
-    return np.array([ps[(i * len(ps)) // G] for i in range(G)], dtype=np.uint64)
-
-
-def _engine(G, K, VL, flags, blockers=0, visits=160, seed=11, params=None, solver=False, family="late", positions=None):
-    cfg = _config(G, flags, blockers, visits, seed)
-    e = link.Engine(cfg)
-    if positions is not None:
-        e.set_positions(np.array(positions, dtype=np.uint64), np.full(G, 10, np.int32))
-    elif family == "late":
-        e.set_positions(_late(G, blockers), np.full(G, 10, np.int32))
-    e.set_leaf_batch(K, VL)
-    if solver:
-        e.set_solver(True)
-    if params is not None:
-        e.set_exploration(*params)
-    return e, cfg
-
-
-_RESULTS = {}   # case -> what it met, or the exception it ended with: every case runs once per session, whoever asks first
+_RESULTS = {}   # case -> what it met: every case runs once per session, whoever asks first
 
 
 def _case(case):
-    if case not in _RESULTS:
-        try:
-            _RESULTS[case] = _lock_step(*case)
-        except BaseException as err:
-            _RESULTS[case] = err
-    if isinstance(_RESULTS[case], BaseException):
-        raise _RESULTS[case]
-    return _RESULTS[case]
+    return lls.memo(_RESULTS, case, lambda: _lock_step(*case))
 
 
-def _lock_step(shape, params, family, solver, e=None, cfg=None, limit=400):
+def _lock_step(shape, params, family, solver, limit=400, **more):
     """The engine against the restatement, iteration by iteration, until every game's move is due.  -> what the run met."""
     G, K, VL, flags, blockers = shape
     seen = {"differs": 0, "zero_levels": 0, "sparse_levels": 0, "fpu_picks": 0, "idx64": 0, "idx128": 0, "idx192": 0, "proven": 0}
-    if e is None:
-        e, cfg = _engine(G, K, VL, flags, blockers, params=params, solver=solver, family=family)
+    e, cfg = _engine(G, K, VL, flags, blockers, params=params, solver=solver, family=family, **more)
     assert e.exploration() == tuple(float(np.float32(v)) for v in params)
-    done = np.zeros(G, bool)
-    for _ in range(limit):
-        pre = [e.tree(g) for g in range(G)]
-        st = [e.game_state(g) for g in range(G)]
-        e.select()
-        kind, lb, le = e.batch_leaves()
-        batches = {}
-        for g in range(G):
-            if st[g].phase == 1:
-                args = (pre[g], st[g].root_visits, cfg.visits, K, VL, cfg.c_puct, bool(flags & 2), blockers)
-                b = xr.select(*args, *params)
-                k = len(b.kind)
-                assert list(kind[g, :k]) == b.kind and (kind[g, k:] == 0).all(), (g, list(kind[g]), b.kind)
-                assert list(le[g, :k]) == b.leaf_edge
-                assert [tuple(int(v) for v in x) for x in lb[g, :k]] == b.leaf_board
-                batches[g] = b
-                seen["differs"] += int(sr.select(*args).leaf_edge != b.leaf_edge)   # what the search selects with the mode off
-                _levels(b, pre[g], seen)
-            elif st[g].phase == 0:
-                assert kind[g, 0] == vlr.LEAF_ROOT and (kind[g, 1:] == 0).all()
-        logits, values = helpers.synthetic_evals_distinct(lb.reshape(-1, 2))
-        e.set_batch_evals(logits, values)
-        e.backup()
-        for g, b in batches.items():
-            post = e.tree(g)
-            if solver:
-                exp, added, proven = sr.expected_tree(b, values[g * K:(g + 1) * K], post)
-                seen["proven"] += len(proven)
-                assert ((e.tree_raw(g)[:, 3] >> 31) == sr.finished_bits(post)).all()
-            else:
-                exp, added = vlr.expected_tree(b, values[g * K:(g + 1) * K], post)
-            for a, x in zip(exp, post):
-                assert a.shape == x.shape and (a == x).all()
-            assert e.game_state(g).root_visits == st[g].root_visits + added
-            if st[g].root_visits + added >= cfg.visits:
-                done[g] = True   # the move is due: the next select plays it
-        if done.all():
-            break
-    assert done.all()
+    ls = lls.LockStep(e, cfg, VL, solver=solver)
+    for rec in ls.until_due(limit):
+        for r in rec.games.values():
+            off = ls.select(r.pre, r.state.root_visits, dict(r.settings, fpu_reduction=-1.0, c_base=0.0))
+            seen["differs"] += int(off.leaf_edge != r.batch.leaf_edge)   # what the search selects with the mode off
+            seen["proven"] += len(r.proven)
+            _levels(r.batch, r.pre, seen)
     e.close()
     return seen
 
@@ -127,23 +61,19 @@ def _lock_step(shape, params, family, solver, e=None, cfg=None, limit=400):
 def _levels(b, pre, seen):
     """What the batch's first path met, level by level, on the tree before the batch (no virtual loss yet): levels without
     a visit (N == 0), levels with at most two visited children under more unvisited ones, picks of an unvisited child beside
-    a visited one, and the lane round of every edge taken."""
-    edges = pre[2]
-    for p, path in enumerate(b.paths):
-        node = 0
-        for ed in path:
-            first, M = b.info[node][0], b.info[node][1] & 0xFFFF
-            j = ed - first
-            seen["idx64"] += j >= 64
-            seen["idx128"] += j >= 128
-            seen["idx192"] += j >= 192
-            if p == 0 and first + M <= len(edges):
-                n = edges[first:first + M, 1]
-                visited = int((n > 0).sum())
-                seen["zero_levels"] += visited == 0
-                seen["sparse_levels"] += 0 < visited <= 2 < M
-                seen["fpu_picks"] += visited > 0 and int(n[j]) == 0
-            node = b.child[ed]
+    a visited one; and the lane round of every edge the batch took."""
+    edges, node = pre[2], 0
+    for ed in b.paths[0]:
+        first, M = b.info[node][0], b.info[node][1] & 0xFFFF
+        if first + M <= len(edges):
+            n = edges[first:first + M, 1]
+            visited = int((n > 0).sum())
+            seen["zero_levels"] += visited == 0
+            seen["sparse_levels"] += 0 < visited <= 2 < M
+            seen["fpu_picks"] += visited > 0 and int(n[ed - first]) == 0
+        node = b.child[ed]
+    for key, count in zip(("idx64", "idx128", "idx192"), lls.lane_rounds(b)):
+        seen[key] += count
 
 
 @pytest.mark.parametrize("case", CASES, ids=["%s-G%dK%dVL%d-%d%s" % (c[2], c[0][0], c[0][1], c[0][2], PARAMS.index(c[1]),
@@ -174,8 +104,7 @@ _WIDE = {}
 def _wide():
     if "seen" not in _WIDE:
         roots = eh._wide_roots()
-        e, cfg = _engine(len(roots), 8, 3, 0, visits=48, seed=20261109, params=BOTH, positions=roots)
-        _WIDE["seen"] = _lock_step((len(roots), 8, 3, 0, 0), BOTH, "wide", False, e=e, cfg=cfg, limit=200)
+        _WIDE["seen"] = _lock_step((len(roots), 8, 3, 0, 0), BOTH, roots, False, limit=200, visits=48, seed=20261109)
     return _WIDE["seen"]
 
 
@@ -258,21 +187,15 @@ SETTER = "azh_engine_set_exploration"
 PHRASE = "first-play urgency or a growing exploration rate (azh_engine_set_exploration)"
 
 
-def _refused(call, code, message):
-    with pytest.raises(link.AzhError) as ei:
-        call()
-    assert str(ei.value) == "ataxxzero_hip error %d: %s" % (code, message)
-
-
 @pytest.mark.parametrize("kwargs,cause", [(dict(flags=link.FLAG_NO_REUSE | link.FLAG_TWO_NETS), "AZH_FLAG_TWO_NETS"),
                                           (dict(flags=link.FLAG_NO_REUSE | link.FLAG_EVAL_CACHE), "AZH_FLAG_EVAL_CACHE"),
                                           (dict(flags=link.FLAG_NO_REUSE | link.FLAG_SYMMETRY_AVG), "AZH_FLAG_SYMMETRY_AVG"),
                                           (dict(flags=link.FLAG_NO_REUSE, select_budget=4), "select_budget > 0")])
 def test_every_create_time_cause(kwargs, cause):
-    cfg = _config(4, kwargs.pop("flags"), visits=24, seed=7, **kwargs)
+    cfg = lls.config(4, kwargs.pop("flags"), visits=24, seed=7, **kwargs)
     e = link.Engine(cfg)
     for params in PARAMS:
-        _refused(lambda: e.set_exploration(*params), -4, "%s: not supported with %s" % (SETTER, cause))
+        lls.refused(lambda: e.set_exploration(*params), -4, "%s: not supported with %s" % (SETTER, cause))
         assert e.exploration() == xr.OFF
     e.set_exploration(*xr.OFF)     # switching off is no request for the mode
     e.close()
@@ -284,13 +207,13 @@ def test_gumbel_and_forced_playouts_in_both_orders():
               "forced": ("azh_engine_set_forced_playouts", lambda e: e.set_forced_playouts(2.0),
                          lambda e: e.set_forced_playouts(0.0), "forced playouts (azh_engine_set_forced_playouts)")}
     for setter, on, off, phrase in others.values():
-        e = link.Engine(_config(4, link.FLAG_NO_REUSE, visits=24, seed=7))
+        e = link.Engine(lls.config(4, link.FLAG_NO_REUSE, visits=24, seed=7))
         on(e)
-        _refused(lambda: e.set_exploration(*FPU), -4, "%s: not supported with %s" % (SETTER, phrase))
+        lls.refused(lambda: e.set_exploration(*FPU), -4, "%s: not supported with %s" % (SETTER, phrase))
         assert e.exploration() == xr.OFF
         off(e)
         e.set_exploration(*RATE)
-        _refused(lambda: on(e), -4, "%s: not supported with %s" % (setter, PHRASE))
+        lls.refused(lambda: on(e), -4, "%s: not supported with %s" % (setter, PHRASE))
         e.set_exploration(*xr.OFF)
         on(e)
         off(e)
@@ -298,7 +221,7 @@ def test_gumbel_and_forced_playouts_in_both_orders():
 
 
 def test_it_composes_with_the_other_modes():
-    e = link.Engine(_config(4, link.FLAG_NO_REUSE, visits=24, seed=7))
+    e = link.Engine(lls.config(4, link.FLAG_NO_REUSE, visits=24, seed=7))
     e.set_exploration(*BOTH)
     e.set_leaf_batch(4, 2)
     e.set_solver(True)
@@ -317,21 +240,21 @@ def test_it_composes_with_the_other_modes():
 
 
 def test_a_selected_batch_bad_arguments_and_an_unchanged_engine():
-    e = link.Engine(_config(4, link.FLAG_NO_REUSE, visits=24, seed=7))
-    twin = link.Engine(_config(4, link.FLAG_NO_REUSE, visits=24, seed=7))
+    e = link.Engine(lls.config(4, link.FLAG_NO_REUSE, visits=24, seed=7))
+    twin = link.Engine(lls.config(4, link.FLAG_NO_REUSE, visits=24, seed=7))
     for x in (e, twin):
         x.set_exploration(*FPU)
     bad = [(np.nan, 0.0, 0.0), (0.25, np.nan, 0.0), (0.25, 1.0, np.nan), (np.inf, 0.0, 0.0), (-np.inf, 0.0, 0.0),
            (0.25, np.inf, 0.0), (0.25, 1.0, np.inf), (0.25, -1.0, 0.0), (0.25, 1.0, -0.5)]
     for args in bad:
-        _refused(lambda: e.set_exploration(*args), -2, SETTER + ": need finite arguments, c_base >= 0 and c_init >= 0")
+        lls.refused(lambda: e.set_exploration(*args), -2, SETTER + ": need finite arguments, c_base >= 0 and c_init >= 0")
         assert e.exploration() == FPU
     e.select()
     kind, lb, _ = e.batch_leaves()
     for args in (BOTH, xr.OFF):      # requests and switching off alike
-        _refused(lambda: e.set_exploration(*args), -3, SETTER + ": a selected batch awaits its backup")
+        lls.refused(lambda: e.set_exploration(*args), -3, SETTER + ": a selected batch awaits its backup")
         assert e.exploration() == FPU
-    _refused(lambda: e.set_exploration(np.nan, 0.0, 0.0), -2, SETTER + ": need finite arguments, c_base >= 0 and c_init >= 0")
+    lls.refused(lambda: e.set_exploration(np.nan, 0.0, 0.0), -2, SETTER + ": need finite arguments, c_base >= 0 and c_init >= 0")
     e.set_batch_evals(*helpers.synthetic_evals_distinct(lb.reshape(-1, 2)))
     e.backup()
     eh.step(twin, K=2)               # (K = 2: any K but 1 takes the batch calls; here K is 1 under the mode)
@@ -358,18 +281,11 @@ def test_the_header_holds_the_row():
 # ------------------------------------------------------------------ the front-end
 
 
-def _npy(tmp_path):
-    conv, bn = model.random_init(2, 128, seed=5, perturb_bn=True)
-    path = str(tmp_path / "net.npy")
-    model.save_model(path, conv, bn)
-    return path
-
-
 @pytest.mark.parametrize("more", [[], ["--parallel-leaves", "16", "--solver", "--reuse-tree"]], ids=["k1", "k16-solver-reuse"])
 def test_cli_plays_legal_moves(tmp_path, more):
     from ataxxzero_amd import uai
     script = "uai\nisready\nposition fen x5o/7/7/7/7/7/o5x x\ngo movetime 200\nmoves g2\ngo movetime 200\nquit\n"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "uai_interface.py"), "--network-path", _npy(tmp_path),
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "uai_interface.py"), "--network-path", lls.npy(tmp_path),
                           "--fpu-reduction", "0.25", "--cpuct-base", "19652", "--cpuct-init", "1.25", "--visits", "64"] + more,
                          input=script, capture_output=True, text=True, timeout=120, cwd=ROOT, env=dict(os.environ))
     assert out.returncode == 0, out.stderr[-2000:]
@@ -397,6 +313,6 @@ def test_searcher_refuses_symmetry_averaging_before_any_device_call(tmp_path, mo
 
 def test_searcher_visits_sum_exactly_at_k1(tmp_path):
     from ataxxzero_amd import uai
-    s = uai.Searcher(_npy(tmp_path), dtype="f16", fpu_reduction=0.25, cpuct_base=19652.0, cpuct_init=1.25)
+    s = uai.Searcher(lls.npy(tmp_path), dtype="f16", fpu_reduction=0.25, cpuct_base=19652.0, cpuct_init=1.25)
     edges = s.root_visits(uai.Position.initial(), visits=100)
     assert sum(n for _, n in edges) == 100 and s.last_steps == 100

@@ -13,12 +13,10 @@ import numpy as np
 import pytest
 
 from ataxxzero_amd import link, model
-from oracle import oracle_lib as orc
 from tests import engine_harness as eh
-from tests import exploration_reference as xr
 from tests import helpers
+from tests import leaf_lockstep as lls
 from tests import solver_reference as sr
-from tests import vl_reference as vlr
 
 pytestmark = pytest.mark.gpu
 
@@ -32,30 +30,12 @@ VISITS = 48      # the engines' own threshold: above every set's, so a move that
 
 
 def _config(G, flags, blockers=0, visits=VISITS, seed=11, max_plies=400, **more):
-    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
-    return link.Config(games=G, visits=visits, max_plies=max_plies, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
-                       dirichlet_weight=0.0 if flags else 0.25, start_turn=0, seed=seed, start_x=int(p.pieces[0]),
-                       start_o=int(p.pieces[1]), blockers=blockers, flags=flags, **more)
-
-
-def _late(G, blockers, max_empty=10):
-    ps = [(w0, w1) for w0, w1, bl in sr.late_positions(max_empty) if bl == blockers]
-    assert len(ps) >= G
-    return np.array([ps[(i * len(ps)) // G] for i in range(G)], dtype=np.uint64)
+    return lls.config(G, flags, blockers, visits, seed, max_plies, **more)
 
 
 def _engine(G, K, flags, blockers, sets, family="late", solver=False, max_plies=400, visits=VISITS, seed=11, vl=1):
-    cfg = _config(G, flags, blockers, visits, seed, max_plies)
-    e = link.Engine(cfg)
-    if family == "late":
-        e.set_positions(_late(G, blockers), np.full(G, 10, np.int32))
-    if K > 1:
-        e.set_leaf_batch(K, vl)
-    if solver:
-        e.set_solver(True)
-    if sets is not None:
-        e.set_search_sets(sets)
-    return e, cfg
+    return lls.engine(G, flags, blockers, visits, seed, max_plies, start=family, leaf_batch=(K, vl) if K > 1 else None,
+                      solver=solver, sets=sets)
 
 
 def _f32(t):
@@ -66,82 +46,38 @@ def _turn(tree):
     return int(tree[0][0][0]) >> 63
 
 
-def _select(tree, root_visits, t, tie_first, blockers, leaves=None, vl=None):
-    """The restatement's batch on `tree` with the values of set t."""
-    return xr.select(tree, root_visits, t["visits"], t["leaves"] if leaves is None else leaves,
-                     t["virtual_loss"] if vl is None else vl, t["c_puct"], tie_first, blockers, t["fpu_reduction"], t["c_base"],
-                     t["c_init"])
+class Met:
+    """The lock step of tests/leaf_lockstep.py with the set of the root's mover as the settings in force, and what its
+    iterations met: what every test below that steps an engine uses."""
 
-
-class LockStep:
-    """One engine against the restatement, iteration by iteration: what every test below that steps an engine uses."""
-
-    def __init__(self, e, cfg, sets, K, blockers, solver=False):
-        self.e, self.cfg, self.sets, self.K, self.blockers, self.solver = e, cfg, sets, K, blockers, solver
-        self.tie_first = bool(cfg.flags & link.FLAG_TIE_FIRST)
-        self.G = cfg.games
+    def __init__(self, e, cfg, sets, solver=False):
+        self.sets = sets
+        self.ls = lls.LockStep(e, cfg, solver=solver, settings=lambda g, tree, state: sets[self.set_of(tree, state.uid)])
         self.seen = {"differs": 0, "batches": 0, "proven": 0, "roots": 0, "due": 0}
         self.used = set()                            # set indices used at a root
-        self.plies = [set() for _ in range(self.G)]  # (uid, ply) whose root was searched, per slot
-        self.last_set = [None] * self.G              # the set index of the slot's last batch
+        self.plies = [set() for _ in range(e.G)]     # (uid, ply) whose root was searched, per slot
+        self.last_set = [None] * e.G                 # the set index of the slot's last batch
 
-    def set_of(self, tree, uid):
-        return link.search_set_pairing(uid, len(self.sets))[_turn(tree)]
+    def set_of(self, tree, uid, other=False):
+        return link.search_set_pairing(uid, len(self.sets))[_turn(tree) ^ int(other)]
 
     def iteration(self):
-        e, G, K = self.e, self.G, self.K
-        pre = [e.tree(g) for g in range(G)]
-        st = [e.game_state(g) for g in range(G)]
-        e.select()
-        kind, lb, le = e.batch_leaves()
-        assert kind.shape == (G, K)
-        batches = {}
-        for g in range(G):
-            if st[g].phase == 1:
-                i = self.set_of(pre[g], st[g].uid)
-                t = self.sets[i]
-                b = _select(pre[g], st[g].root_visits, t, self.tie_first, self.blockers)
-                k = len(b.kind)
-                assert k == max(1, min(t["leaves"], t["visits"] - st[g].root_visits))
-                assert list(kind[g, :k]) == b.kind and (kind[g, k:] == 0).all(), (g, i, list(kind[g]), b.kind)
-                assert list(le[g, :k]) == b.leaf_edge, (g, i)
-                assert [tuple(int(v) for v in x) for x in lb[g, :k]] == b.leaf_board, (g, i)
-                batches[g] = (b, t)
-                self.used.add(i)
-                self.plies[g].add((st[g].uid, st[g].ply))
-                self.last_set[g] = i
-                self.seen["batches"] += 1
-                # a level where the game's two sets pick different edges: the first path under each set's scoring alone
-                j = link.search_set_pairing(st[g].uid, len(self.sets))[1 - _turn(pre[g])]
-                if j != i:
-                    mine = _select(pre[g], st[g].root_visits, t, self.tie_first, self.blockers, leaves=1, vl=1)
-                    other = _select(pre[g], st[g].root_visits, dict(self.sets[j], visits=t["visits"]), self.tie_first, self.blockers,
-                                    leaves=1, vl=1)
-                    self.seen["differs"] += int(mine.paths != other.paths)
-            elif st[g].phase == 0:
-                assert kind[g, 0] == vlr.LEAF_ROOT and (kind[g, 1:] == 0).all()
-                self.seen["roots"] += 1
-            else:
-                assert (kind[g] == 0).all()          # the move is due (this select plays it), or the slot is idle
-        logits, values = helpers.synthetic_evals_distinct(lb.reshape(-1, 2))
-        e.set_batch_evals(logits, values)
-        e.backup()
-        for g, (b, t) in batches.items():
-            post = e.tree(g)
-            if self.solver:
-                exp, added, proven = sr.expected_tree(b, values[g * K:(g + 1) * K], post)
-                self.seen["proven"] += len(proven)
-                assert ((e.tree_raw(g)[:, 3] >> 31) == sr.finished_bits(post)).all()
-            else:
-                exp, added = vlr.expected_tree(b, values[g * K:(g + 1) * K], post)
-            for a, x in zip(exp, post):
-                assert a.shape == x.shape and (a == x).all(), g
-            now = e.game_state(g)
-            assert now.root_visits == st[g].root_visits + added
-            due = vlr.move_is_due(b, now.root_visits, t["visits"])     # exactly at the set's visits, not the engine's
-            assert (now.phase == 2) == due, (g, now.root_visits, t["visits"], now.phase)
-            self.seen["due"] += int(due)
-        return st
+        rec = self.ls.step()
+        for g, r in rec.games.items():
+            i, j = self.set_of(r.pre, r.state.uid), self.set_of(r.pre, r.state.uid, other=True)
+            self.used.add(i)
+            self.plies[g].add((r.state.uid, r.state.ply))
+            self.last_set[g] = i
+            self.seen["batches"] += 1
+            self.seen["proven"] += len(r.proven)
+            self.seen["due"] += int(r.due)
+            # a level where the game's two sets pick different edges: the first path under each set's scoring alone
+            if j != i:
+                one = dict(visits=r.settings["visits"], leaves=1, virtual_loss=1)
+                mine = self.ls.select(r.pre, r.state.root_visits, dict(r.settings, **one))
+                other = self.ls.select(r.pre, r.state.root_visits, dict(self.sets[j], **one))
+                self.seen["differs"] += int(mine.paths != other.paths)
+        self.seen["roots"] += sum(1 for st in rec.states if st.phase == 0)
 
 
 # (G, engine K, blockers, flags, sets, family, solver, max_plies): max_plies cuts the games short, so that every slot begins
@@ -158,20 +94,13 @@ _RESULTS = {}
 
 
 def _case(name):
-    if name not in _RESULTS:
-        try:
-            _RESULTS[name] = _run_case(*CASES[name])
-        except BaseException as err:
-            _RESULTS[name] = err
-    if isinstance(_RESULTS[name], BaseException):
-        raise _RESULTS[name]
-    return _RESULTS[name]
+    return lls.memo(_RESULTS, name, lambda: _run_case(*CASES[name]))
 
 
 def _run_case(G, K, blockers, flags, sets, family, solver, max_plies, limit=400):
     e, cfg = _engine(G, K, flags, blockers, sets, family, solver, max_plies)
     assert e.search_sets() == [_f32(t) for t in sets]
-    ls = LockStep(e, cfg, sets, K, blockers, solver)
+    ls = Met(e, cfg, sets, solver)
     for _ in range(limit):
         ls.iteration()
         second = [any(uid >= G for uid, _ in p) for p in ls.plies]
@@ -238,7 +167,7 @@ def test_one_set_equal_to_the_engines_settings_changes_nothing():
 def test_after_a_host_move_the_new_movers_set_searches(flags, status):
     G, K = 2, 7
     e, cfg = _engine(G, K, flags, 0, [A, B], family="start")      # (from the start position: no move ends the game)
-    ls = LockStep(e, cfg, [A, B], K, 0)
+    ls = Met(e, cfg, [A, B])
     for _ in range(6):
         ls.iteration()
     before = list(ls.last_set)
@@ -264,7 +193,7 @@ def test_a_loaded_position_with_o_to_move_is_searched_with_os_set():
     boards = [(w0, w1) for w0, w1, bl in sr.late_positions(10) if bl == 0 and w0 >> 63][:G]
     assert len(boards) == G
     e.set_positions(np.array(boards, dtype=np.uint64), np.full(G, 11, np.int32))
-    ls = LockStep(e, cfg, [A, B], K, 0)
+    ls = Met(e, cfg, [A, B])
     for _ in range(4):
         ls.iteration()
     assert ls.last_set == [link.search_set_pairing(g, 2)[1] for g in range(G)]
@@ -357,12 +286,6 @@ PHRASE = "search settings per side (azh_engine_set_search_sets)"
 UAI = link.FLAG_NO_REUSE | link.FLAG_TIE_FIRST
 
 
-def _refused(call, code, message):
-    with pytest.raises(link.AzhError) as ei:
-        call()
-    assert str(ei.value) == "ataxxzero_hip error %d: %s" % (code, message)
-
-
 @pytest.mark.parametrize("kwargs,cause", [(dict(flags=UAI | link.FLAG_TWO_NETS), "AZH_FLAG_TWO_NETS"),
                                           (dict(flags=UAI | link.FLAG_ONE_RANDOM_MOVE), "AZH_FLAG_ONE_RANDOM_MOVE"),
                                           (dict(flags=UAI | link.FLAG_EVAL_CACHE), "AZH_FLAG_EVAL_CACHE"),
@@ -370,7 +293,7 @@ def _refused(call, code, message):
                                           (dict(flags=UAI, select_budget=4), "select_budget > 0")])
 def test_every_create_time_cause(kwargs, cause):
     e = link.Engine(_config(4, kwargs.pop("flags"), seed=7, **kwargs))
-    _refused(lambda: e.set_search_sets([A, dict(B, leaves=1)]), -4, "%s: not supported with %s" % (SETTER, cause))
+    lls.refused(lambda: e.set_search_sets([A, dict(B, leaves=1)]), -4, "%s: not supported with %s" % (SETTER, cause))
     assert e.search_sets() == []
     e.set_search_sets([])          # switching off is no request for the mode
     e.close()
@@ -395,11 +318,11 @@ def test_the_excluded_modes_in_both_orders(other):
     sets = [A, dict(B, leaves=1)]
     e = link.Engine(_config(4, UAI, seed=7))
     on(e)
-    _refused(lambda: e.set_search_sets(sets), -4, "%s: not supported with %s" % (SETTER, phrase))
+    lls.refused(lambda: e.set_search_sets(sets), -4, "%s: not supported with %s" % (SETTER, phrase))
     assert e.search_sets() == []
     off(e)
     e.set_search_sets(sets)
-    _refused(lambda: on(e), -4, "%s: not supported with %s" % (setter, PHRASE))
+    lls.refused(lambda: on(e), -4, "%s: not supported with %s" % (setter, PHRASE))
     e.set_search_sets([])
     on(e)
     off(e)
@@ -443,20 +366,20 @@ def test_bad_arguments_a_selected_batch_and_an_unchanged_engine():
             rows = [dict(t) for t in sets]
             rows[1][field] = value
             rows[at][field] = value
-            _refused(lambda: e.set_search_sets(rows), -2, "%s: set %d: %s" % (SETTER, at, why))
+            lls.refused(lambda: e.set_search_sets(rows), -2, "%s: set %d: %s" % (SETTER, at, why))
             assert e.search_sets() == [_f32(t) for t in sets]
-    _refused(lambda: e.set_search_sets([A] * 17), -2, SETTER + ": need 0 <= n <= 16")
+    lls.refused(lambda: e.set_search_sets([A] * 17), -2, SETTER + ": need 0 <= n <= 16")
     # the engine's visits and K may not go below a set's
-    _refused(lambda: e.set_visits(39), -2, "azh_engine_set_visits: 39 is below the visits 40 of search set 1")
-    _refused(lambda: e.set_leaf_batch(3, 2), -2, "azh_engine_set_leaf_batch: 3 is below the leaves 4 of search set 1")
+    lls.refused(lambda: e.set_visits(39), -2, "azh_engine_set_visits: 39 is below the visits 40 of search set 1")
+    lls.refused(lambda: e.set_leaf_batch(3, 2), -2, "azh_engine_set_leaf_batch: 3 is below the leaves 4 of search set 1")
     e.set_visits(40), twin.set_visits(40)
     # a selected batch awaits its backup: requests and switching off alike, and a bad argument is still -2
     e.select()
     kind, lb, _ = e.batch_leaves()
     for rows in ([dict(B, leaves=4), A], []):
-        _refused(lambda: e.set_search_sets(rows), -3, SETTER + ": a selected batch awaits its backup")
+        lls.refused(lambda: e.set_search_sets(rows), -3, SETTER + ": a selected batch awaits its backup")
         assert e.search_sets() == [_f32(t) for t in sets]
-    _refused(lambda: e.set_search_sets([dict(A, visits=0)]), -2, SETTER + ": set 0: need 1 <= visits <= 40 (the engine's)")
+    lls.refused(lambda: e.set_search_sets([dict(A, visits=0)]), -2, SETTER + ": set 0: need 1 <= visits <= 40 (the engine's)")
     e.set_batch_evals(*helpers.synthetic_evals_distinct(lb.reshape(-1, 2)))
     e.backup()
     eh.step(twin, K=4)

@@ -9,54 +9,32 @@ import sys
 import numpy as np
 import pytest
 
-from ataxxzero_amd import link, model
+from ataxxzero_amd import link
 from oracle import oracle_lib as orc
 from tests import engine_harness as eh
 from tests import helpers
+from tests import leaf_lockstep as lls
 from tests import solver_reference as sr
 
 pytestmark = pytest.mark.gpu
 
 ROOT = helpers.ROOT
-UAI = link.FLAG_NO_REUSE | link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR
+UAI = lls.UAI
 
 
-def _late(G, blockers, max_empty=10):
-    """G distinct unfinished fixture positions of the blocker set with at most `max_empty` empty cells, spread over them."""
-    ps = [(w0, w1) for w0, w1, bl in sr.late_positions(max_empty) if bl == blockers]
-    assert len(ps) >= G
-    return np.array([ps[(i * len(ps)) // G] for i in range(G)], dtype=np.uint64)
-
-
-def _engine(G, K, VL, flags, blockers=0, visits=300, seed=11, solver=True, positions=None):
-    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
-    cfg = link.Config(games=G, visits=visits, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
-                      dirichlet_weight=0.0 if flags else 0.25, start_turn=0, seed=seed, start_x=int(p.pieces[0]),
-                      start_o=int(p.pieces[1]), blockers=blockers, flags=flags)
-    e = link.Engine(cfg)
-    e.set_positions(_late(G, blockers) if positions is None else positions, np.full(G, 10, np.int32))
-    e.set_leaf_batch(K, VL)
-    if solver:
-        e.set_solver(True)
-    return e, cfg
+def _engine(G, K, VL, flags, blockers=0, visits=300, seed=11, solver=True):
+    return lls.engine(G, flags, blockers, visits, seed, leaf_batch=(K, VL), solver=solver)
 
 
 CASES = [  # (G, K, VL, flags, blockers)
     (1, 1, 1, UAI, 0), (1, 7, 3, 0, 0), (1, 64, 3, UAI, 0), (5, 1, 1, 0, 0), (5, 7, 1, UAI, 0), (5, 64, 1, 0, 0),
     (5, 7, 3, UAI, helpers.BLOCK4_MASK), (5, 64, 3, 0, helpers.BLOCK4_MASK),
 ]
-_RESULTS = {}   # case -> what it met, or the exception it ended with: every case runs once per session, whoever asks first
+_RESULTS = {}   # case -> what it met: every case runs once per session, whoever asks first
 
 
 def _case(case):
-    if case not in _RESULTS:
-        try:
-            _RESULTS[case] = _lock_step(*case)
-        except BaseException as err:
-            _RESULTS[case] = err
-    if isinstance(_RESULTS[case], BaseException):
-        raise _RESULTS[case]
-    return _RESULTS[case]
+    return lls.memo(_RESULTS, case, lambda: _lock_step(*case))
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -67,54 +45,16 @@ def test_every_iteration_equals_the_restatement(case):
 def _lock_step(G, K, VL, flags, blockers):
     SEEN = {"win": 0, "loss": 0, "chained": 0, "root": 0, "hits": 0}
     e, cfg = _engine(G, K, VL, flags, blockers, visits=160)
-    done = np.zeros(G, bool)
-    nodes = hits = 0
-    for _ in range(400):
-        pre = [e.tree(g) for g in range(G)]
-        st = [e.game_state(g) for g in range(G)]
-        e.select()
-        kind, lb, le = e.batch_leaves()
-        batches = {}
-        for g in range(G):
-            if st[g].phase == 1:
-                b = sr.select(pre[g], st[g].root_visits, cfg.visits, K, VL, cfg.c_puct, bool(flags & 2), blockers)
-                k = len(b.kind)
-                assert list(kind[g, :k]) == b.kind and (kind[g, k:] == 0).all()
-                assert list(le[g, :k]) == b.leaf_edge
-                assert [tuple(int(v) for v in x) for x in lb[g, :k]] == b.leaf_board
-                batches[g] = b
-                hits += b.proven_hits
-            elif st[g].phase == 0:
-                assert kind[g, 0] == sr.LEAF_ROOT and (kind[g, 1:] == 0).all()
-        logits, values = helpers.synthetic_evals_distinct(lb.reshape(-1, 2))
-        e.set_batch_evals(logits, values)
-        e.backup()
-        proofs = e.root_proofs()
-        for g, b in batches.items():
-            post = e.tree(g)
-            exp, added, proven = sr.expected_tree(b, values[g * K:(g + 1) * K], post)
-            for a, x in zip(exp, post):
-                assert a.shape == x.shape and (a == x).all()
-            # the edge records carry the "finished" bit exactly where the child is decided
-            assert ((e.tree_raw(g)[:, 3] >> 31) == sr.finished_bits(post)).all()
-            # and the root's record says what the tree says
-            first, M = int(post[1][0, 0]), int(post[1][0, 1] & 0xFFFF)
-            assert proofs[g][0] == sr.decided_value(post[1][0])
-            assert list(proofs[g][1][:M]) == [sr.decided_value(post[1][c]) if c != sr.NONE else 0
-                                              for c in (int(v) for v in post[2][first:first + M, 3])]
-            assert e.game_state(g).root_visits == st[g].root_visits + added
-            nodes += len(proven)
-            for node, value, _, levels in proven:
+    nodes = 0
+    for rec in lls.LockStep(e, cfg, VL, solver=True, root_proofs=True).until_due():
+        for r in rec.games.values():
+            SEEN["hits"] += r.batch.proven_hits
+            nodes += len(r.proven)
+            for node, value, _, levels in r.proven:
                 SEEN["win" if value == 1 else "loss"] += 1
                 SEEN["chained"] += int(levels > 1)
                 SEEN["root"] += int(node == 0)
-            if st[g].root_visits + added >= cfg.visits:
-                done[g] = True  # the move is due: the next select plays it
-        if done.all():
-            break
-    assert done.all()
-    assert e.proof_stats() == {"proven_nodes": nodes, "proven_hits": hits}
-    SEEN["hits"] += hits
+    assert e.proof_stats() == {"proven_nodes": nodes, "proven_hits": SEEN["hits"]}
     e.close()
     return SEEN
 
@@ -158,14 +98,7 @@ _LOOP_RESULTS = {}
 
 
 def _loop(case):
-    if case not in _LOOP_RESULTS:
-        try:
-            _LOOP_RESULTS[case] = _device_loop(*case)
-        except BaseException as err:
-            _LOOP_RESULTS[case] = err
-    if isinstance(_LOOP_RESULTS[case], BaseException):
-        raise _LOOP_RESULTS[case]
-    return _LOOP_RESULTS[case]
+    return lls.memo(_LOOP_RESULTS, case, lambda: _device_loop(*case))
 
 
 @pytest.mark.parametrize("case", LOOPS)
@@ -255,10 +188,7 @@ def test_switched_on_and_off_again_is_an_untouched_engine():
 
 
 def test_refusals():
-    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
-    cfg = link.Config(games=4, visits=300, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
-                      dirichlet_weight=0.25, start_turn=0, seed=11, start_x=int(p.pieces[0]), start_o=int(p.pieces[1]),
-                      blockers=0, flags=0)
+    cfg = lls.config(4)
     for flags, budget, word in [(link.FLAG_TWO_NETS, 0, "AZH_FLAG_TWO_NETS"), (link.FLAG_EVAL_CACHE, 0, "AZH_FLAG_EVAL_CACHE"),
                                 (link.FLAG_SYMMETRY_AVG, 0, "AZH_FLAG_SYMMETRY_AVG"), (0, 4, "select_budget > 0")]:
         cfg.flags, cfg.select_budget = flags, budget
@@ -286,13 +216,6 @@ def test_refusals():
     c.set_solver(False)
     c.leaves()
     c.close()
-
-
-def _npy(tmp_path):
-    conv, bn = model.random_init(2, 128, seed=5, perturb_bn=True)
-    path = str(tmp_path / "net.npy")
-    model.save_model(path, conv, bn)
-    return path
 
 
 def _mates():
@@ -324,7 +247,7 @@ def _mates():
 @pytest.mark.parametrize("K", [1, 16])
 def test_genmove_plays_the_mating_move(tmp_path, K):
     from ataxxzero_amd import uai
-    s = uai.Searcher(_npy(tmp_path), dtype="f16", parallel_leaves=K, virtual_loss=2, solver=True)
+    s = uai.Searcher(lls.npy(tmp_path), dtype="f16", parallel_leaves=K, virtual_loss=2, solver=True)
     for plies, ((w0, w1), wins) in _mates().items():
         pos = uai.Position(w0 & ~(1 << 63), w1, w0 >> 63)
         for _ in range(3):
@@ -345,7 +268,7 @@ def test_cli_solver_reports_a_proven_win(tmp_path):
     (w0, w1), _ = _mates()[3]
     pos = uai.Position(w0 & ~(1 << 63), w1, w0 >> 63)
     script = "uai\nisready\nposition fen %s\ngo movetime 200\nquit\n" % pos.fen()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "uai_interface.py"), "--network-path", _npy(tmp_path),
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "uai_interface.py"), "--network-path", lls.npy(tmp_path),
                           "--solver", "--visits", "400", "--show-pv"],
                          input=script, capture_output=True, text=True, timeout=120, cwd=ROOT, env=dict(os.environ))
     assert out.returncode == 0, out.stderr[-2000:]

@@ -9,30 +9,21 @@ from ataxxzero_amd import link
 from oracle import oracle_lib as orc
 from tests import engine_harness as eh
 from tests import helpers
+from tests import leaf_lockstep as lls
 from tests import priors_reference as pr
-from tests import solver_reference as sor
-from tests import symmetry_reference as sym
 from tests import vl_reference as vlr
 from tests.engine_harness import _edge_positions, _pack, _wide_roots
 
 pytestmark = pytest.mark.gpu
 
-UAI = link.FLAG_NO_REUSE | link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR
-ALPHA, WEIGHT = 0.15, 0.25
+UAI = lls.UAI
 SEEN = {"eval_slots": 0, "symmetries": set(), "root_noise": 0, "idx64": 0, "idx128": 0, "idx192": 0, "wide_proofs": 0,
         "over_first": 0, "over_inside": 0, "forced_moves": 0, "mask_offsets": set()}
 
 
 def _engine(positions, K, VL, flags, visits, seed, edges_per_node=96, ply=10):
-    G = len(positions)
-    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
-    cfg = link.Config(games=G, visits=visits, max_plies=400, edges_per_node=edges_per_node, c_puct=1.0, dirichlet_alpha=ALPHA,
-                      dirichlet_weight=0.0 if flags else WEIGHT, start_turn=0, seed=seed, start_x=int(p.pieces[0]),
-                      start_o=int(p.pieces[1]), blockers=0, flags=flags)
-    e = link.Engine(cfg)
-    e.set_positions(np.array(positions, dtype=np.uint64), np.full(G, ply, np.int32))
-    e.set_leaf_batch(K, VL)
-    return e, cfg
+    return lls.engine(len(positions), flags, 0, visits, seed, edges_per_node=edges_per_node, start=positions, ply=ply,
+                      leaf_batch=(K, VL))
 
 
 def _fixture_positions(G):
@@ -51,124 +42,32 @@ def _same_tree(exp, post):
         assert a.shape == x.shape and (a == x).all()
 
 
-class LockStep:
-    """One engine against the restatement.  step() runs one iteration (select, the synthetic evaluations, backup) and checks
-    it: the batch (kinds, leaf edges, leaf boards, the number of paths), the whole tree after the backup, the priors of every
-    evaluated node against tests/priors_reference.py, the state, the move a due game plays and the overflow counter."""
-
-    def __init__(self, e, cfg, K, VL, solver=False, symmetry=False, caps=False):
-        self.e, self.cfg, self.K, self.VL, self.solver, self.symmetry = e, cfg, K, VL, solver, symmetry
-        self.caps = (e.node_cap, e.edge_cap) if caps else (None, None)
-        self.G = e.G
-        self.due = np.zeros(self.G, bool)      # the move became due at some backup
-        self.overflows = 0
-        self.proven = []                       # (edge count of the node, value)
-
-    def _symmetry(self, uid, board):
-        return sym.eval_symmetry(self.cfg.seed, uid, board[0], board[1]) if self.symmetry else 0
-
-    def _image(self, s, board):
-        return (sym.board(s, board[0]), sym.board(s, board[1])) if s else tuple(board)
-
-    def step(self):
-        e, cfg, K, G, flags = self.e, self.cfg, self.K, self.G, self.cfg.flags
-        pre = [e.tree(g) for g in range(G)]
-        st = [e.game_state(g) for g in range(G)]
-        e.select()
-        kind, lb, le = e.batch_leaves()
-        batches, roots, syms = {}, {}, {}
-        for g in range(G):
-            if st[g].phase == 1:
-                if self.solver:
-                    b = sor.select(pre[g], st[g].root_visits, cfg.visits, K, self.VL, cfg.c_puct, bool(flags & 2), 0)
-                    b.over = False
-                else:
-                    b = vlr.select(pre[g], st[g].root_visits, cfg.visits, K, self.VL, cfg.c_puct, bool(flags & 2), 0, *self.caps)
-                k = len(b.kind)
-                assert list(kind[g, :k]) == b.kind and (kind[g, k:] == 0).all(), (g, list(kind[g]), b.kind)
-                assert list(le[g, :k]) == b.leaf_edge
-                assert e.game_state(g).path_len == k          # the batch ended with its last path (a dropped one included)
-                ss = [self._symmetry(st[g].uid, x) if kd == vlr.LEAF_EVAL else 0 for kd, x in zip(b.kind, b.leaf_board)]
-                assert [tuple(int(v) for v in x) for x in lb[g, :k]] == [self._image(s, x) for s, x in zip(ss, b.leaf_board)]
-                batches[g], syms[g] = b, ss
-                SEEN["symmetries"] |= {s for s, kd in zip(ss, b.kind) if kd == vlr.LEAF_EVAL} if self.symmetry else set()
-                SEEN["eval_slots"] = max(SEEN["eval_slots"], b.kind.count(vlr.LEAF_EVAL))
-                if b.over:
-                    SEEN["over_first" if k == 1 else "over_inside"] += 1
-                    self.overflows += 1
-                for path in b.paths:          # the index of every edge the descent selected, at its level
-                    node = 0
-                    for ed in path:
-                        j = ed - b.info[node][0]
-                        SEEN["idx64"] += j >= 64
-                        SEEN["idx128"] += j >= 128
-                        SEEN["idx192"] += j >= 192
-                        node = b.child[ed]
-            elif st[g].phase == 0:
-                assert kind[g, 0] == vlr.LEAF_ROOT and (kind[g, 1:] == 0).all()
-                board = vlr.leaf_board(*pre[g][0][0])
-                s = self._symmetry(st[g].uid, board)
-                assert tuple(int(v) for v in lb[g, 0]) == self._image(s, board)
-                roots[g] = s
-            else:
-                assert (kind[g] == 0).all()
-                if st[g].phase == 2:
-                    self._check_played_move(g, pre[g], st[g])
-        logits, values = helpers.synthetic_evals_distinct(lb.reshape(-1, 2))
-        e.set_batch_evals(logits, values)
-        e.backup()
-        for g, b in batches.items():
-            post = e.tree(g)
-            if self.solver:
-                exp, added, proven = sor.expected_tree(b, values[g * K:(g + 1) * K], post)
-                self.proven += [(b.info[x][1] & 0xFFFF, v) for x, v, _, _ in proven]
-            else:
-                exp, added = vlr.expected_tree(b, values[g * K:(g + 1) * K], post)
-            _same_tree(exp, post)             # (every prior but the new nodes' is the one of the dump before)
-            for p, kd in enumerate(b.kind):
-                if kd == vlr.LEAF_EVAL:
-                    first, M = b.info[b.leaf_node[p]][0], b.info[b.leaf_node[p]][1] & 0xFFFF
-                    assert first >= b.edges0
-                    want = pr.priors(logits[g * K + p], post[3][first:first + M], flags, syms[g][p])
-                    assert (post[2][first:first + M, 0] == want).all(), (g, p, M)
-            after = e.game_state(g)
-            assert after.root_visits == st[g].root_visits + added
-            due = vlr.move_is_due(b, after.root_visits, cfg.visits)
-            assert after.phase == (2 if due else 1)
-            self.due[g] |= due
-        for g, s in roots.items():
-            post = e.tree(g)
-            first, M = int(post[1][0, 0]), int(post[1][0, 1]) & 0xFFFF
-            noise = (ALPHA, cfg.dirichlet_weight, cfg.seed, st[g].uid, st[g].ply)
-            want = pr.priors(logits[g * K], post[3][first:first + M], flags, s, noise)
-            assert (post[2][first:first + M, 0] == want).all(), (g, M)
-            SEEN["root_noise"] += int(cfg.dirichlet_weight > 0)
-            rest = np.ones(len(post[2]), bool)
-            rest[first:first + M] = False
-            assert all((a == x).all() for a, x in zip((pre[g][0], pre[g][1], pre[g][3]), (post[0], post[1], post[3])))
-            assert (pre[g][2][:, 1:] == post[2][:, 1:]).all() and (pre[g][2][rest, 0] == post[2][rest, 0]).all()
-            assert e.game_state(g).phase == 1
-        assert e.stats()["edge_overflow"] == self.overflows
-
-    def _check_played_move(self, g, pre, st):
-        """A due game: this select gave it no leaf and played vl_reference.forced_move on the tree the backup left."""
-        now = self.e.game_state(g)
-        j, mv = vlr.forced_move(pre, st.root_visits, self.cfg.seed, st.uid, st.ply)
-        board, res, _, _ = vlr.expand_position(pre[0][0][0], pre[0][0][1], mv, 0)
-        if res == 0 and now.uid == st.uid:
-            assert now.ply == st.ply + 1 and now.phase == 0
-            assert tuple(int(v) for v in self.e.tree(g)[0][0]) == board
-            SEEN["forced_moves"] += 1
-        else:
-            assert res != 0 or now.ply == 0   # the game ended with the move (or at the ply limit): the slot began its next game
+def _run_until_due(e, cfg, VL, limit=200, **more):
+    """Lock step (tests/leaf_lockstep.py) with the priors, the played moves and the overflow counter checked, until every
+    game's move is due.  -> (the LockStep, [(edge count of a proven node, its value)])"""
+    ls = lls.LockStep(e, cfg, VL, priors=True, played_move=True, overflow=True, **more)
+    proven = []
+    for rec in ls.until_due(limit):
+        proven += _count(rec, ls)
+    return ls, proven
 
 
-def _run_until_due(ls, limit=200):
-    for _ in range(limit):
-        ls.step()
-        if ls.due.all():
-            break
-    assert ls.due.all()
+def _count(rec, ls):
+    """What an iteration met, into SEEN.  -> [(edge count of a node it proved, the value)]"""
+    proven = []
+    for r in rec.games.values():
+        b = r.batch
+        evals = [s for s, kd in zip(r.syms, b.kind) if kd == vlr.LEAF_EVAL]
+        SEEN["symmetries"] |= set(evals) if ls.symmetry else set()
+        SEEN["eval_slots"] = max(SEEN["eval_slots"], len(evals))
+        if b.over:
+            SEEN["over_first" if len(b.kind) == 1 else "over_inside"] += 1
+        for key, count in zip(("idx64", "idx128", "idx192"), lls.lane_rounds(b)):   # every edge the descent took
+            SEEN[key] += count
+        proven += [(b.info[x][1] & 0xFFFF, v) for x, v, _, _ in r.proven]
+    SEEN["root_noise"] += sum(1 for st in rec.states if st.phase == 0 and ls.cfg.dirichlet_weight > 0)
+    SEEN["forced_moves"] += len(rec.played)
+    return proven
 
 
 # ------------------------------------------------------------------ 1. pinned priors
@@ -182,7 +81,7 @@ def test_priors_of_new_nodes_and_of_the_root(G, K, VL, flags, symmetry):
     e, cfg = _engine(_positions(G, 0), K, VL, flags, visits=64, seed=20261018)
     if symmetry:
         e.set_random_symmetry(True)
-    _run_until_due(LockStep(e, cfg, K, VL, symmetry=symmetry))
+    _run_until_due(e, cfg, VL, symmetry=symmetry)
     e.close()
 
 
@@ -198,7 +97,7 @@ def test_nodes_of_65_to_193_edges(flags):
     """(seed: one under which the root noise of the 193-move board in slot 2 makes the descent take its last edge, found
     with the restatement on the host)"""
     e, cfg = _engine(_wide_roots(), 8, 3, flags, visits=48, seed=20261109)
-    _run_until_due(LockStep(e, cfg, 8, 3))
+    _run_until_due(e, cfg, 3)
     e.close()
 
 
@@ -210,11 +109,10 @@ def test_a_proof_at_a_node_of_more_than_64_edges():
     wide = _edge_positions("wide")
     e, cfg = _engine([_pack(wide[i]["fen"]) for i in (15, 13, 16, 5)], 8, 3, 0, visits=48, seed=20261018)
     e.set_solver(True)
-    ls = LockStep(e, cfg, 8, 3, solver=True)
-    _run_until_due(ls)
-    SEEN["wide_proofs"] += sum(1 for M, v in ls.proven if M > 64)
-    assert e.proof_stats()["proven_nodes"] == len(ls.proven)
-    assert any(M > 128 and v == 1 for M, v in ls.proven), ls.proven
+    _, proven = _run_until_due(e, cfg, 3, solver=True)
+    SEEN["wide_proofs"] += sum(1 for M, v in proven if M > 64)
+    assert e.proof_stats()["proven_nodes"] == len(proven)
+    assert any(M > 128 and v == 1 for M, v in proven), proven
     e.close()
 
 
@@ -233,11 +131,10 @@ def test_full_arenas_drop_the_path_end_the_batch_and_force_the_move():
     wide = _edge_positions("wide")
     e, cfg = _engine([_pack(wide[1]["fen"]), _pack(wide[5]["fen"])], 8, 2, 0, visits=40, seed=20261018, edges_per_node=8)
     assert (e.node_cap, e.edge_cap) == (48, 384)
-    ls = LockStep(e, cfg, 8, 2, caps=True)
-    _run_until_due(ls)
+    ls, _ = _run_until_due(e, cfg, 2, caps=True)
     assert SEEN["over_first"] >= 1 and SEEN["over_inside"] >= 1 and ls.overflows >= 2, SEEN
     for _ in range(20):
-        ls.step()
+        _count(ls.step(), ls)
     assert SEEN["forced_moves"] >= 2, SEEN
     e.close()
 

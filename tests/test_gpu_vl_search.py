@@ -8,28 +8,21 @@ import sys
 import numpy as np
 import pytest
 
-from ataxxzero_amd import link, model
-from oracle import oracle_lib as orc
+from ataxxzero_amd import link
 from tests import engine_harness as eh
 from tests import helpers
+from tests import leaf_lockstep as lls
 from tests import vl_reference as vlr
 from tests.engine_harness import _positions
 
 pytestmark = pytest.mark.gpu
 
 ROOT = helpers.ROOT
-UAI = link.FLAG_NO_REUSE | link.FLAG_TIE_FIRST | link.FLAG_PY_POSTERIOR
+UAI = lls.UAI
 
 
 def _engine(G, K, VL, flags, blockers=0, visits=300, seed=11):
-    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
-    cfg = link.Config(games=G, visits=visits, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
-                      dirichlet_weight=0.0 if flags else 0.25, start_turn=0, seed=seed, start_x=int(p.pieces[0]),
-                      start_o=int(p.pieces[1]), blockers=blockers, flags=flags)
-    e = link.Engine(cfg)
-    e.set_positions(_positions(G, blockers), np.full(G, 10, np.int32))
-    e.set_leaf_batch(K, VL)
-    return e, cfg
+    return lls.engine(G, flags, blockers, visits, seed, start=_positions(G, blockers), leaf_batch=(K, VL))
 
 
 CASES = [  # (G, K, VL, flags, blockers)
@@ -42,40 +35,12 @@ SEEN = {"collision": 0, "terminal": 0, "truncated": 0}
 @pytest.mark.parametrize("G,K,VL,flags,blockers", CASES)
 def test_every_iteration_equals_the_restatement(G, K, VL, flags, blockers):
     e, cfg = _engine(G, K, VL, flags, blockers)
-    done = np.zeros(G, bool)
-    for _ in range(400):
-        pre = [e.tree(g) for g in range(G)]
-        st = [e.game_state(g) for g in range(G)]
-        e.select()
-        kind, lb, le = e.batch_leaves()
-        batches = {}
-        for g in range(G):
-            if st[g].phase == 1 and not done[g]:
-                b = vlr.select(pre[g], st[g].root_visits, cfg.visits, K, VL, cfg.c_puct, bool(flags & 2), blockers)
-                k = len(b.kind)
-                assert list(kind[g, :k]) == b.kind and (kind[g, k:] == 0).all()
-                assert list(le[g, :k]) == b.leaf_edge
-                assert [tuple(int(v) for v in x) for x in lb[g, :k]] == b.leaf_board
-                batches[g] = b
-                SEEN["collision"] += b.kind.count(vlr.LEAF_COLLISION)
-                SEEN["terminal"] += b.kind.count(vlr.LEAF_TERMINAL)
-                SEEN["truncated"] += int(k < K and st[g].root_visits + k == cfg.visits)
-            elif st[g].phase == 0:
-                assert kind[g, 0] == vlr.LEAF_ROOT and (kind[g, 1:] == 0).all()
-        logits, values = helpers.synthetic_evals_distinct(lb.reshape(-1, 2))
-        e.set_batch_evals(logits, values)
-        e.backup()
-        for g, b in batches.items():
-            post = e.tree(g)
-            exp, added = vlr.expected_tree(b, values[g * K:(g + 1) * K], post)
-            for a, x in zip(exp, post):
-                assert a.shape == x.shape and (a == x).all()
-            assert e.game_state(g).root_visits == st[g].root_visits + added
-            if st[g].root_visits + added >= cfg.visits:
-                done[g] = True  # the move is due: the next select plays it
-        if done.all():
-            break
-    assert done.all()
+    for rec in lls.LockStep(e, cfg, VL).until_due(past_due=False):
+        for r in rec.games.values():
+            k = len(r.batch.kind)
+            SEEN["collision"] += r.batch.kind.count(vlr.LEAF_COLLISION)
+            SEEN["terminal"] += r.batch.kind.count(vlr.LEAF_TERMINAL)
+            SEEN["truncated"] += int(k < K and r.state.root_visits + k == cfg.visits)
     e.close()
 
 
@@ -109,12 +74,7 @@ def test_device_loop_equals_host_stepping(G, K, dtype):
 def test_k1_through_the_new_call_is_the_one_leaf_search_and_bad_combinations_fail():
     net = eh.net(2)
     a, _ = _engine(4, 1, 1, 0)
-    p = orc.pos_from_fen(orc.START_FEN_PLAIN)
-    cfg = link.Config(games=4, visits=300, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
-                      dirichlet_weight=0.25, start_turn=0, seed=11, start_x=int(p.pieces[0]), start_o=int(p.pieces[1]),
-                      blockers=0, flags=0)
-    b = link.Engine(cfg)
-    b.set_positions(_positions(4, 0), np.full(4, 10, np.int32))
+    b, cfg = lls.engine(4, start=_positions(4, 0))
     a.set_leaf_batch(8, 2)   # there and back again, between iterations
     a.set_leaf_batch(1, 1)
     a.run(net, 30, link.DTYPE_BF16)
@@ -141,16 +101,9 @@ def test_k1_through_the_new_call_is_the_one_leaf_search_and_bad_combinations_fai
     a.close(), b.close()
 
 
-def _npy(tmp_path):
-    conv, bn = model.random_init(2, 128, seed=5, perturb_bn=True)
-    path = str(tmp_path / "net.npy")
-    model.save_model(path, conv, bn)
-    return path
-
-
 def test_searcher_visits_sum_exactly(tmp_path):
     from ataxxzero_amd import uai
-    s = uai.Searcher(_npy(tmp_path), dtype="f16", parallel_leaves=16)
+    s = uai.Searcher(lls.npy(tmp_path), dtype="f16", parallel_leaves=16)
     edges = s.root_visits(uai.Position.initial(), visits=200)
     assert sum(n for _, n in edges) == 200 and s.last_steps == 200
     edges = s.root_visits(uai.Position.initial(), seconds=0.05)
@@ -158,7 +111,7 @@ def test_searcher_visits_sum_exactly(tmp_path):
 
 
 def test_cli_parallel_leaves_plays_legal_moves(tmp_path):
-    net = _npy(tmp_path)
+    net = lls.npy(tmp_path)
     script = "uai\nisready\nposition fen x5o/7/7/7/7/7/o5x x\ngo movetime 200\nmoves g2\ngo movetime 200\nquit\n"
     env = dict(os.environ)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "uai_interface.py"), "--network-path", net,

@@ -21,6 +21,7 @@ from oracle import oracle_lib as orc
 
 NONE = 0xFFFFFFFF
 LEAF_NONE, LEAF_EVAL, LEAF_TERMINAL, LEAF_ROOT, LEAF_COLLISION = 0, 1, 2, 3, 5
+WIN_BITS, LOSS_BITS = 0x3F800000, 0xBF800000   # +1.0f, -1.0f: info word 3 of a proven node
 F32 = np.float32
 
 
@@ -83,14 +84,29 @@ class Batch:
     """One iteration's selected batch and the working tree it left (virtual losses kept apart)."""
 
 
-def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers, node_cap=None, edge_cap=None):
+def is_proven(info_row):
+    """Decided without being a finished position: result bits 0 and the bits of +1.0f or -1.0f in info word 3
+    (tests/solver_reference.py)."""
+    return (int(info_row[1]) >> 16) == 0 and int(info_row[3]) in (WIN_BITS, LOSS_BITS)
+
+
+def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers, node_cap=None, edge_cap=None, *,
+           proven_end_paths=False, scores=None):
     """The batch of one game in search phase 1: k = max(1, min(K, visits - root_visits)) paths as if one after the other.
     node_cap, edge_cap: the arenas' sizes (both None: unbounded) — the arena-full rule of the module's docstring.
+    proven_end_paths: a path ends at a proven node as at a finished position (TERMINAL), the root excepted — the descent of
+    tests/solver_reference.py.  scores(priors, W, n, N) -> the M f32 scores of a level, n the effective visits
+    n + VL * vl and N their sum; the default is puct_scores with c_puct (tests/exploration_reference.py has another).
     -> Batch with .kind, .leaf_edge (NONE: none), .leaf_board (mover, opponent; (0, 0) unless EVAL), .paths, .leaf_node,
-    .over (a path was dropped: the batch ended there and the move is forced)."""
+    .over (a path was dropped: the batch ended there and the move is forced), .nodes0 (nodes from this id on were created
+    by this batch) and .proven_hits (the paths that ended at a proven node)."""
     boards, info, edges, moves = tree
     boards = [tuple(int(v) for v in b) for b in boards]
     info = [list(int(v) for v in r) for r in info]
+    marked = {x for x in range(1, len(info)) if is_proven(info[x])} if proven_end_paths else set()
+    if scores is None:
+        def scores(P, W, n, N):
+            return puct_scores(P, W, n, N, c_puct)
     prior = [int(e[0]) for e in edges]
     n = [int(e[1]) for e in edges]
     W = [int(e[2]) for e in edges]
@@ -107,7 +123,7 @@ def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers, node_c
         node, path = 0, []
         while True:
             first, M, res = info[node][0], info[node][1] & 0xFFFF, info[node][1] >> 16
-            if res != 0 or M == 0:
+            if res != 0 or M == 0 or node in marked:
                 kind = LEAF_TERMINAL
                 break
             if node >= nodes0:
@@ -115,7 +131,7 @@ def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers, node_c
                 break
             rng = range(first, first + M)
             ne = [n[e] + VL * vl[e] for e in rng]
-            sc = puct_scores([_f(prior[e]) for e in rng], [_f(W[e]) for e in rng], ne, sum(ne), c_puct)
+            sc = scores([_f(prior[e]) for e in rng], [_f(W[e]) for e in rng], ne, sum(ne))
             e = first + pick(sc, tie_first)
             path.append(e)
             if child[e] != NONE:
@@ -149,7 +165,8 @@ def select(tree, root_visits, visits, K, VL, c_puct, tie_first, blockers, node_c
         b.paths.append(path)
         if b.over:
             break
-    b.edges0 = edges0
+    b.nodes0, b.edges0 = nodes0, edges0
+    b.proven_hits = sum(1 for p, kd in enumerate(b.kind) if kd == LEAF_TERMINAL and b.leaf_node[p] in marked)
     b.boards, b.info, b.prior, b.n, b.W, b.child, b.moves = boards, info, prior, n, W, child, mv
     return b
 
