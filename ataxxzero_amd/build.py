@@ -21,6 +21,7 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-Wall", "-Wno
 UNITS = [
     ("engine.hip", ["-ffp-contract=off"]),
     ("rules_api.hip", ["-ffp-contract=off"]),
+    ("alphabeta.hip", ["-ffp-contract=off"]),
     ("net_kernels.hip", []),
     ("samples.hip", ["-ffp-contract=off"]),
     ("common.cpp", []),

@@ -120,6 +120,10 @@ SIGNATURES = {
     "azh_random_play": (ctypes.c_int, [ctypes.c_int, _u64, _u64, _u64, _u64, ctypes.c_int, ctypes.c_int,
                                        _vp, _vp, _vp, _vp]),
     "azh_probe_detmath": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _u64, _vp]),
+    "azh_alphabeta_search": (ctypes.c_int, [ctypes.c_int, _vp, _u64, _vp, ctypes.c_int, _u64, _vp, _vp, _vp, _vp]),
+    "azh_alphabeta_host": (ctypes.c_int, [_u64, _u64, _u64, ctypes.c_int, ctypes.c_int, _u64, _vp, _vp, _vp, _vp]),
+    "azh_alphabeta_play": (ctypes.c_int, [ctypes.c_int, _u64, _u64, _u64, _u64, ctypes.c_int, _vp, _vp, ctypes.c_int, _u64,
+                                          _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "azh_net_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _f32, _P(_vp)]),
     "azh_net_destroy": (None, [_vp]),
     "azh_net_forward": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _u64, _vp, _vp]),
@@ -569,6 +573,71 @@ def random_play(n_games, seed, x, o, blockers, turn, max_plies=400, trace=True):
     check(load().azh_random_play(n_games, int(seed), int(x), int(o), int(blockers), int(turn), max_plies,
                                  _ptr(plies), _ptr(results), _ptr(boards), _ptr(moves)))
     return plies, results, boards, moves
+
+
+ALPHABETA_MAX_DEPTH, ALPHABETA_UNBOUNDED_DEPTH, ALPHABETA_WIN = 8, 3, 1000   # AZH_ALPHABETA_*; rule 1's 1000
+AlphaBeta = collections.namedtuple("AlphaBeta", "moves values depth_done nodes")
+
+
+def _wall_arguments(blockers, n):
+    """blockers: one mask for every board, or one mask per board -> (the word, the per-board array or None)"""
+    if np.ndim(blockers) == 0:
+        return int(blockers), None
+    return 0, _board_masks(blockers, n)
+
+
+def alphabeta_search(boards, blockers, depth, node_budget=0, outputs=("moves", "values", "depth_done", "nodes")):
+    """The depth-limited material alpha-beta search of n packed boards on the device, one wave per root
+    (azh_alphabeta_search) -> AlphaBeta(moves (n,) u16 — best(p, depth), 0xFFFF for a finished root —, values (n,) i32,
+    depth_done (n,) i32, nodes (n,) u64); a field left out of `outputs` is None.  blockers: one wall mask, or one per
+    board.  node_budget 0: no limit (depth <= 3 only)."""
+    boards = np.ascontiguousarray(boards, dtype=np.uint64).reshape(-1, 2)
+    n = len(boards)
+    word, masks = _wall_arguments(blockers, n)
+    out = {"moves": np.zeros(n, dtype=np.uint16), "values": np.zeros(n, dtype=np.int32),
+           "depth_done": np.zeros(n, dtype=np.int32), "nodes": np.zeros(n, dtype=np.uint64)}
+    out = {k: (v if k in outputs else None) for k, v in out.items()}
+    check(load().azh_alphabeta_search(n, _ptr(boards), word, _ptr(masks), int(depth), int(node_budget), _ptr(out["moves"]),
+                                      _ptr(out["values"]), _ptr(out["depth_done"]), _ptr(out["nodes"])))
+    return AlphaBeta(**out)
+
+
+def alphabeta_host(x, o, blockers, turn, depth, node_budget=0):
+    """The same search of one position as a plain negamax on the host, without pruning -> (move, value, depth_done, nodes)
+    (azh_alphabeta_host; host arithmetic, no GPU needed)."""
+    move, value, done, nodes = ctypes.c_uint16(0), ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_uint64(0)
+    check(load().azh_alphabeta_host(int(x), int(o), int(blockers), int(turn), int(depth), int(node_budget), ctypes.addressof(move),
+                                    ctypes.addressof(value), ctypes.addressof(done), ctypes.addressof(nodes)))
+    return int(move.value), int(value.value), int(done.value), int(nodes.value)
+
+
+def teacher_thresholds(probabilities):
+    """Per-ply probabilities of a random move -> azh_alphabeta_play's u32 thresholds, floor(p * 2**32)."""
+    return np.array([min(int(p * 2 ** 32), 2 ** 32 - 1) for p in probabilities], dtype=np.uint32)
+
+
+def alphabeta_play(n_games, seed, x, o, blockers, turn, depth, node_budget=0, thresholds=(), max_plies=400, starts=None):
+    """Teacher games on the device (azh_alphabeta_play): every ply's training move is the alpha-beta search's, the move
+    played a uniformly random one where the Philox draw of (seed; game, ply) falls below thresholds[ply]
+    -> (plies, results, boards (n, max_plies, 2) (x, o), training moves, played moves (n, max_plies)).
+    starts: None, or (packed boards (n, 2), wall masks (n,)), a start position and a wall map per game."""
+    thresholds = np.ascontiguousarray(thresholds, dtype=np.uint32)
+    first = masks = None
+    if starts is not None:
+        first = np.ascontiguousarray(starts[0], dtype=np.uint64).reshape(-1, 2)
+        masks = _board_masks(starts[1], n_games)
+        if len(first) != n_games:
+            raise ValueError("%d start positions for %d games" % (len(first), n_games))
+    plies = np.zeros(n_games, dtype=np.int32)
+    results = np.zeros(n_games, dtype=np.int32)
+    boards = np.zeros((n_games, max_plies, 2), dtype=np.uint64)
+    training = np.zeros((n_games, max_plies), dtype=np.uint16)
+    played = np.zeros((n_games, max_plies), dtype=np.uint16)
+    check(load().azh_alphabeta_play(n_games, int(seed), int(x), int(o), int(blockers), int(turn), _ptr(first), _ptr(masks),
+                                    int(depth), int(node_budget), _ptr(thresholds) if len(thresholds) else None,
+                                    len(thresholds), max_plies, _ptr(plies), _ptr(results), _ptr(boards), _ptr(training),
+                                    _ptr(played)))
+    return plies, results, boards, training, played
 
 
 def probe_detmath(kind, values=None, aux=None, seed=0):

@@ -65,6 +65,26 @@ class Teacher:
 UAIPlayer = Teacher  # the reference's name for it
 
 
+def alphabeta_entries(n_games, seed, depth, node_budget=0, start_fen=selfplay.START_FEN_PLAIN, max_plies=MAXIMUM_GAME_PLIES):
+    """n_games teacher games whose teacher is the device's alpha-beta search (link.alphabeta_play), all in flight at once
+    -> entries shaped as generate_game shapes them: "moves" holds the training moves, the moves played were replaced by
+    random ones with the opening-randomisation schedule's probability; result None when cut at max_plies."""
+    x, o, blockers, turn = selfplay.parse_fen(start_fen)
+    plies, results, boards, training, _ = link.alphabeta_play(
+        n_games, seed, x, o, blockers, turn, depth, node_budget, link.teacher_thresholds(OPENING_RANDOMIZATION_SCHEDULE),
+        max_plies)
+    entries = []
+    for g in range(n_games):
+        n = int(plies[g])
+        entry = {"boards": [selfplay.board_cells(int(boards[g, p, 0]), int(boards[g, p, 1])) for p in range(n)],
+                 "moves": [selfplay.python_move(int(training[g, p])) for p in range(n)]}
+        if blockers:
+            entry["blockers"] = link.blockers_to_cells(blockers)
+        entry["result"] = int(results[g]) if results[g] else None
+        entries.append(entry)
+    return entries
+
+
 def generate_game(teacher, ms, rng=random, start_fen=selfplay.START_FEN_PLAIN):
     """One teacher game -> entry {"boards", "moves", "result"} (result None when cut at 400 plies).  start_fen: the start
     position; on a board with walls the teacher is sent them (Position.fen writes '-') and the entry gains "blockers"."""

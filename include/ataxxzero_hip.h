@@ -78,6 +78,46 @@ int azh_random_play(int n_games, uint64_t seed, uint64_t x, uint64_t o, uint64_t
                     int max_plies, int32_t *plies, int32_t *results, uint64_t *boards_out,
                     uint16_t *moves_out);
 
+/* ------------------------------------------------------------------ alpha-beta search
+ * A depth-limited material search without a net: the teacher of generate_games.py --supervised-depth and the fixed
+ * opponent of tools/anchor_match.py ("Alpha-beta search").  With result(p) the adjudication and moves(p) the
+ * move order of azh_rules_batch, value(p, d), an integer seen from the side to move, is
+ *   1. result(p) != 0: +(1000 + d) when the side to move has won, -(1000 + d) otherwise;
+ *   2. d == 0: the stones of the side to move minus the opponent's;
+ *   3. else the maximum over m in moves(p) of -value(makemove(p, m), d - 1),
+ * and best(p, d) is the FIRST move of moves(p) that reaches value(p, d); a finished root has the move 0xFFFF and the value
+ * of rule 1.  The search deepens d = 1 .. depth and counts nodes: the positions value was entered on, roots excluded,
+ * summed over the iterations.  node_budget > 0: an iteration during which the count passes the budget is abandoned and the
+ * last completed one is reported (depth 1 always completes: node_budget >= AZH_MAX_MOVES); node_budget == 0, no limit, is
+ * accepted up to depth AZH_ALPHABETA_UNBOUNDED_DEPTH.  depth outside 1 .. AZH_ALPHABETA_MAX_DEPTH, a refused budget and a
+ * board whose stones or walls overlap: -2. */
+#define AZH_ALPHABETA_MAX_DEPTH 8
+#define AZH_ALPHABETA_UNBOUNDED_DEPTH 3
+
+/* n packed boards (as azh_rules_batch), one wave each, pruned; every root on `blockers`, or root i on
+ * blockers_per_board[i] when that is not NULL.  Outputs, all optional: moves_out[n] = best, values_out[n] = value,
+ * depth_done_out[n] = the iteration reported, nodes_out[n]. */
+int azh_alphabeta_search(int n, const uint64_t *boards, uint64_t blockers, const uint64_t *blockers_per_board, int depth,
+                         uint64_t node_budget, uint16_t *moves_out, int32_t *values_out, int32_t *depth_done_out,
+                         uint64_t *nodes_out);
+
+/* The same for one position as a plain negamax on the host: no pruning, no device.  Its node count is the definition's
+ * own, so under a budget it may complete fewer iterations than the device does.  Outputs optional. */
+int azh_alphabeta_host(uint64_t x, uint64_t o, uint64_t blockers, int turn, int depth, uint64_t node_budget,
+                       uint16_t *move_out, int32_t *value_out, int32_t *depth_done_out, uint64_t *nodes_out);
+
+/* Teacher games (generate_games.py:26-57 with --supervised, the engine being this search): n_games games from (x, o, turn)
+ * on `blockers`, or game g from the packed board starts[2g .. 2g+1] and on blockers_per_game[g] where those are not NULL.
+ * At every ply the training move is best(p, depth) under the budget; the move played is replaced by legal move number
+ * (v[1] * M) >> 32 of the M legal moves when v[0] < random_per_2_32[ply], v = philox(seed; game, ply, 9, 0); plies from
+ * n_schedule on are never replaced.  One launch per ply.  Outputs, all optional, as azh_random_play: plies[n], results[n]
+ * (0 = unfinished at max_plies), boards_out [n][max_plies][2] (x, o), training_moves_out and played_moves_out
+ * [n][max_plies]. */
+int azh_alphabeta_play(int n_games, uint64_t seed, uint64_t x, uint64_t o, uint64_t blockers, int turn,
+                       const uint64_t *starts, const uint64_t *blockers_per_game, int depth, uint64_t node_budget,
+                       const uint32_t *random_per_2_32, int n_schedule, int max_plies, int32_t *plies, int32_t *results,
+                       uint64_t *boards_out, uint16_t *training_moves_out, uint16_t *played_moves_out);
+
 /* Test hook for the engine's deterministic f32 math / Philox4x32-10 (the arithmetic
  * the search's bit-exact contract with the CPU oracle rests on).  kind 0: exp(in[i]);
  * 1: log(in[i]); 2: gamma(alpha = in[0]) keyed (seed, aux[3i..3i+2] = uid, ply, edge);

@@ -1,0 +1,77 @@
+"""The alpha-beta search's definition on the host (azh_alphabeta_host, a plain negamax in C++ over the kernels' own make_move
+and ring masks) against the cell-list restatement (tests/alphabeta_reference.py): move, value and node count, exact.  No
+device."""
+import pytest
+
+from ataxxzero_amd import link
+from tests import alphabeta_cases as ac
+from tests import alphabeta_reference as ab
+from tests import rules_reference as rr
+
+BUDGET = 1 << 22  # beyond every case: depths past 3 need a budget
+
+
+def host(board, depth, budget=None):
+    x, o, blockers = board.masks()
+    return link.alphabeta_host(x, o, blockers, board.turn, depth, (0 if depth <= 3 else BUDGET) if budget is None else budget)
+
+
+@pytest.mark.parametrize("name", [n for n, _, _ in ac.cases()])
+def test_host_negamax_equals_the_restatement_at_every_depth(name):
+    board, depth = next((b, d) for n, b, d in ac.cases() if n == name)
+    want = ac.restated(name)
+    nodes = 0
+    for d in range(1, depth + 1):
+        move, value, it = want[d - 1]
+        nodes += it
+        assert host(board, d) == (move, value, d, nodes), (name, board.fen(), d)
+
+
+def test_the_cases_the_issue_names_behave_as_stated():
+    f1 = rr.move_from_string("f1")
+    assert [(m, v) for m, v, _ in ac.restated("start")] == [(f1, 1), (f1, 0), (f1, 1)]
+    # depth 1 at the start: eight jumps that win nothing stand before the clones, and several clones tie at +1
+    start = rr.Board.from_fen(ac.START)
+    scores = [-ab.value(rr.make_move(start, m), 0) for m in rr.legal_moves(start)]
+    assert scores[:8] == [0] * 8 and scores.count(1) > 1 and rr.legal_moves(start)[scores.index(1)] == f1
+    assert len(rr.legal_moves(rr.Board.from_fen(ac.WIDE))) == 157
+    assert [v for _, v, _ in ac.restated("wide")] == [1000, 1001, 1002]
+    assert len(rr.legal_moves(rr.Board.from_fen(ac.LOST))) == 2
+    assert [v for _, v, _ in ac.restated("lost")] == [-14, -1000, -1001]
+    assert rr.Board.from_fen(ac.WALLED_START).masks()[2] != 0
+    assert any(d == 5 for n, _, d in ac.cases() if n.startswith("endgame"))
+    assert all(len(rr.legal_moves(b)) > 128 for n, b, _ in ac.cases() if n.startswith("hill climb"))
+
+
+def test_a_finished_root_has_no_move_and_the_value_of_rule_1():
+    for board in ac.finished_boards():
+        res = rr.result(board)
+        assert res != 0
+        for d in (1, 3, 8):
+            want = ab.WIN + d if res == board.turn + 1 else -(ab.WIN + d)
+            assert ab.search(board, d) == (ab.NO_MOVE, want, 0)
+            assert host(board, d, BUDGET) == (0xFFFF, want, d, 0)
+
+
+def test_a_budget_reports_the_last_completed_iteration():
+    board = rr.Board.from_fen(ac.WIDE)
+    want = ac.restated("wide")
+    # depth 1 costs 157 nodes; the plain depth 2 another 1055: 256 and 1211 stop it, 1212 does not
+    for budget, done in ((256, 1), (157 + 1055 - 1, 1), (157 + 1055, 2)):
+        move, value, depth_done, nodes = host(board, 3, budget)
+        assert (move, value, depth_done) == (want[done - 1][0], want[done - 1][1], done), budget
+        assert nodes == budget + 1  # the node that passed the budget is the last one counted
+
+
+def test_refusals():
+    x, o, blockers = rr.Board.from_fen(ac.START).masks()
+    for depth, budget in ((0, 0), (9, 1 << 20), (-1, 0), (4, 0), (8, 0), (2, 255), (2, 1)):
+        with pytest.raises(link.AzhError) as err:
+            link.alphabeta_host(x, o, blockers, 0, depth, budget)
+        assert "error -2" in str(err.value), (depth, budget)
+    assert link.alphabeta_host(x, o, blockers, 0, 3, 0)[2] == 3
+    assert link.alphabeta_host(x, o, blockers, 0, 4, 1 << 20)[2] == 4
+    for bad in ((x, o | x, blockers), (x, o, 1 << 49), (x, o, x)):
+        with pytest.raises(link.AzhError) as err:
+            link.alphabeta_host(bad[0], bad[1], bad[2], 0, 1, 0)
+        assert "error -2" in str(err.value)
