@@ -34,21 +34,29 @@ std::string azh_format_game_json(const uint32_t *rec, bool with_ids);
 std::string azh_format_game_json_blockers(const uint32_t *rec, bool with_ids, uint64_t blockers);
 uint64_t azh_ply_target(azh::PlyView ply, std::vector<std::pair<std::string, uint32_t>> &ents);
 
-// net_kernels.hip
-int azh_net_launch(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
-                   const int *d_count, int max_n, unsigned long long blockers, float *d_logits,
-                   float *d_values, hipStream_t stream, unsigned long long *d_stamps = nullptr, int thin = 0,
-                   const void *advance_hook = nullptr, const unsigned long long *d_masks = nullptr);
-// d_masks (all three launches): null — every board stands on `blockers` — or the wall mask of every board, indexed as d_boards
-// advance_hook (all three launches): an azh::AdvanceHook (engine_device.h) or null — the device-resident search loop's queued
-// moves are played by the first `workers` workgroups of the launch
-// symmetry-averaged evaluation (nn_evals.py:48-62); scratch: [8 max_n][833] and [8 max_n] floats
-int azh_net_launch_sym(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
-                       const int *d_count, int max_n, unsigned long long blockers, float *d_tmp_logits,
-                       float *d_tmp_values, float *d_logits, float *d_values, hipStream_t stream, int thin = 0,
-                       const void *advance_hook = nullptr, const unsigned long long *d_masks = nullptr);
-// two nets, two dense leaf lists, one launch (arena); 1 = not applicable here, nothing launched (launch them one by one)
-int azh_net_launch_pair(azh_net *net_a, azh_net *net_b, int dtype, const unsigned long long *d_boards, const int *d_list_a,
-                        const int *d_count_a, const int *d_list_b, const int *d_count_b, int max_n,
-                        unsigned long long blockers, float *d_logits, float *d_values, hipStream_t stream, int thin = 0,
-                        const void *advance_hook = nullptr, const unsigned long long *d_masks = nullptr);
+// net_kernels.hip: one tower launch over a batch of boards.  Every pointer is a device pointer.
+namespace azh {
+struct AdvanceHook;  // engine_device.h
+struct NetBatch {
+    const unsigned long long *boards = nullptr;  // (mover, opponent) per game
+    const int *list = nullptr, *count = nullptr;  // dense list of the games to evaluate; both null: the first max_n boards
+    int max_n = 0;                                // bound of *count (of count_a + count_b for a pair: a game has one leaf)
+    unsigned long long blockers = 0;              // the wall mask of every board ...
+    const unsigned long long *masks = nullptr;    // ... or, non-null, one mask per board, indexed as `boards`
+    float *logits = nullptr, *values = nullptr;   // [.][833] and [.], indexed by game
+};
+struct NetOptions {
+    int thin = 0;  // the caller expects a handful of boards (<= 512): one board per workgroup (Geo2Thin) where that kernel applies
+    unsigned long long *stamps = nullptr;  // diagnostic: the stamped bf16 tower writes [wg][wave][128] clock values here
+    const AdvanceHook *hook = nullptr;     // the device-resident search loop's queued moves are played by the first
+                                           // `workers` workgroups of the launch
+    // both non-null: the symmetry-averaged evaluation (nn_evals.py:48-62) — the tower runs 8 * max_n virtual boards into
+    // this scratch ([8 max_n][833] and [8 max_n] floats), k_sym_reduce behind it writes the averages by game
+    float *sym_logits = nullptr, *sym_values = nullptr;
+};
+}  // namespace azh
+int azh_net_launch(azh_net *net, int dtype, const azh::NetBatch &batch, hipStream_t stream, const azh::NetOptions &options = {});
+// two nets, two dense leaf lists (batch.list / batch.count are net_a's), one launch (arena); 1 = not applicable here, nothing
+// launched (launch them one by one)
+int azh_net_launch_pair(azh_net *net_a, azh_net *net_b, int dtype, const azh::NetBatch &batch, const int *list_b,
+                        const int *count_b, hipStream_t stream, const azh::NetOptions &options);

@@ -1878,18 +1878,38 @@ extern "C" int azh_engine_leaf_features(azh_engine *e, float *out, int32_t *game
     return 0;
 }
 
+// the engine's leaf boards and evaluation arrays as a tower batch of at most G listed games
+static NetBatch leaf_batch(const azh_engine *e, const int *list, const int *count)
+{
+    NetBatch b;
+    b.boards = (const unsigned long long *)e->P.leaf_board;
+    b.list = list;
+    b.count = count;
+    b.max_n = e->P.G;
+    b.blockers = e->P.blockers;
+    b.masks = leaf_masks(e);
+    b.logits = e->P.logits;
+    b.values = e->P.values;
+    return b;
+}
+
 // one evaluation of the listed leaves by `net`; with AZH_FLAG_SYMMETRY_AVG the 8-way averaged one
 static int launch_eval(azh_engine *e, azh_net *net, int dtype, const int *list, const int *count, const AdvanceHook *hook = nullptr)
 {
-    if (!(e->P.flags & AZH_FLAG_SYMMETRY_AVG))
-        return azh_net_launch(net, dtype, (const unsigned long long *)e->P.leaf_board, list, count, e->P.G * leaf_k(e),
-                              e->P.blockers, e->P.logits, e->P.values, e->stream, nullptr, thin_batches(e), hook, leaf_masks(e));
+    NetBatch b = leaf_batch(e, list, count);
+    NetOptions o;
+    o.hook = hook;
+    if (!(e->P.flags & AZH_FLAG_SYMMETRY_AVG)) {
+        b.max_n = e->P.G * leaf_k(e);
+        o.thin = thin_batches(e);
+        return azh_net_launch(net, dtype, b, e->stream, o);
+    }
     AZH_TRY(dev_alloc_once(e, &e->d_sym_logits, (size_t)e->P.G * 8 * AZH_POLICY_SIZE));
     AZH_TRY(dev_alloc_once(e, &e->d_sym_values, (size_t)e->P.G * 8));
-    return azh_net_launch_sym(net, dtype, (const unsigned long long *)e->P.leaf_board, list, count, e->P.G,
-                              e->P.blockers, e->d_sym_logits, e->d_sym_values, e->P.logits, e->P.values, e->stream,
-                              e->thin_mode >= 0 ? e->thin_mode : (e->P.G * 8 <= AZH_THIN_MAX_GAMES ? 1 : 0),  // (8 virtual boards per leaf)
-                              hook, leaf_masks(e));
+    o.sym_logits = e->d_sym_logits;
+    o.sym_values = e->d_sym_values;
+    o.thin = e->thin_mode >= 0 ? e->thin_mode : (e->P.G * 8 <= AZH_THIN_MAX_GAMES ? 1 : 0);  // (8 virtual boards per leaf)
+    return azh_net_launch(net, dtype, b, e->stream, o);
 }
 
 extern "C" int azh_engine_eval(azh_engine *e, azh_net *net, int dtype)
@@ -1984,10 +2004,13 @@ struct RunLoop {
         }
         if (rec) AZH_HIP(hipEventRecord(ev[0], e->stream));
         int rc = 1;
-        if (net_b && pair)  // both nets' leaf lists in ONE tower launch (1: not applicable -> one after the other)
-            rc = azh_net_launch_pair(net_a, net_b, dtype, (const unsigned long long *)e->P.leaf_board, e->P.leaf_list,
-                                     e->P.leaf_count, e->P.leaf_list2, e->P.leaf_count2, e->P.G, e->P.blockers, e->P.logits,
-                                     e->P.values, e->stream, thin_batches(e), moves, leaf_masks(e));
+        if (net_b && pair) {  // both nets' leaf lists in ONE tower launch (1: not applicable -> one after the other)
+            NetOptions o;
+            o.thin = thin_batches(e);
+            o.hook = moves;
+            rc = azh_net_launch_pair(net_a, net_b, dtype, leaf_batch(e, e->P.leaf_list, e->P.leaf_count), e->P.leaf_list2,
+                                     e->P.leaf_count2, e->stream, o);
+        }
         if (rc == 1) {
             rc = launch_eval(e, net_a, dtype, e->P.leaf_list, e->P.leaf_count, moves);   // (the first launch plays the moves)
             if (rc == 0 && net_b)

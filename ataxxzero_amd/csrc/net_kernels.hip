@@ -1632,7 +1632,7 @@ extern "C" int azh_net_create(int blocks, int filters, const float *conv_flat, c
     if (azh_require_device())
         return -3;
 #if AZH_OOBZERO
-    if (lds_range_check() < 0)  // probes the device once; the answer picks the tower variant in net_launch
+    if (lds_range_check() < 0)  // probes the device once; the answer picks the tower variant in choose_tower
         return -5;
 #endif
     azh_net *net = new azh_net();
@@ -1680,12 +1680,6 @@ extern "C" void azh_net_destroy(azh_net *net)
 }
 
 
-static const AdvanceHook &no_hook()
-{
-    static const AdvanceHook h = {};   // workers = 0
-    return h;
-}
-
 // Where a launch of `tiles` tile workgroups puts its move-playing workgroups: in front when the launch has more workgroups than
 // the chip has slots for them (`per_cu` workgroups of this kernel per CU), behind the tiles when everything starts at once.
 static AdvanceHook place_workers(const AdvanceHook &H, int tiles, int per_cu)
@@ -1703,68 +1697,127 @@ static AdvanceHook place_workers(const AdvanceHook &H, int tiles, int per_cu)
     return out;
 }
 
-template <int DT, int NB, int WPS, bool STAMP = false, int FT = F>
-static int launch_tower(const TowerArgs &args, int max_n, hipStream_t stream, const AdvanceHook &H = no_hook())
+// What a tower kernel is to the host.  Every instantiation the library launches has one row, in towers(), and is named there
+// and nowhere else; choose_tower picks the row, launch_tower launches it.
+struct TowerKernel {
+    const void *fn;    // the kernel's host address
+    const char *name;  // as azh_net_tower_choice reports it
+    int boards;        // per workgroup
+    int threads, lds_bytes;
+    int per_cu;        // workgroups of this kernel that a CU holds, as place_workers wants them
+    mutable bool attr_set[MAX_DEVICES];  // the dynamic-LDS attribute is set once per device: a process may drive several GPUs
+};
+
+// G: the kernel's geometry; wps: the second argument of its __launch_bounds__
+template <typename G> static TowerKernel tower_row(const void *fn, const char *name, int threads, int wps)
 {
-    typedef Geo<DT, NB, FT> G;
     static_assert(G::LDS_BYTES <= 160 * 1024, "tower image does not fit one CU's LDS");
     static_assert(G::LDS_BYTES >= (int)sizeof(TreeLds), "the launch's move-playing workgroups use the tower's LDS as their scratch");
-    static bool attr_set[MAX_DEVICES] = {};  // the attribute is per device: a process may drive several GPUs
-    const int dev = current_device();
-    if (dev < 0)
-        return azh_fail(-4, "launch_tower: hipGetDevice failed");
-    if (!attr_set[dev]) {
-        AZH_HIP(hipFuncSetAttribute((const void *)k_tower<DT, NB, WPS, STAMP, FT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    G::LDS_BYTES));
-        attr_set[dev] = true;
-    }
-    const int tiles = (max_n + G::BOARDS - 1) / G::BOARDS, grid = tiles + H.workers;
-    if (grid <= 0)
+    const int per_cu = wps * 256 / threads;
+    return {fn, name, G::BOARDS, threads, G::LDS_BYTES, per_cu > 0 ? per_cu : 1, {}};
+}
+
+// Variant 1 (k_tower: 32x32x16 MFMA, one wave per 32 output channels; also the f32 tower and the other widths) and variant 2
+// (k_tower2*: 16x16x32 MFMA, 64 channels per wave, the 16-bit towers at 128 filters).  Pairs of 16-bit rows are [bf16, f16].
+// (The members stand in the order in which the compiler has always emitted the kernels: moving one moves the device code.)
+struct TowerTable {
+    TowerKernel pair[2][2];   // [thin]: two nets, two leaf lists, one launch
+    TowerKernel w64[3];       // [dtype]: other widths (the reference's FILTERS is a class attribute, uai_interface.py:92-93
+    TowerKernel w256[3];      //          patches it); 3 boards per workgroup, 1 for f32 at 256 filters (LDS)
+    TowerKernel v2_stamped;   // diagnostic instantiations: bf16 only
+    TowerKernel v2_thin[2];   // one board per workgroup (Geo2Thin): the launch for a handful of boards
+    TowerKernel v2[2];
+    TowerKernel v1_stamped[2];  // [6 boards, 3 boards]
+    TowerKernel v1_f32;
+    TowerKernel v1[2][2];       // [16-bit dtype][6 boards, 3 boards]: one 6-board workgroup per CU, or 3 boards (two per CU)
+};
+
+template <int DT, int NB, int WPS, bool STAMP = false, int FT = F> static TowerKernel row1(const char *name)
+{
+    typedef Geo<DT, NB, FT> G;
+    return tower_row<G>((const void *)k_tower<DT, NB, WPS, STAMP, FT>, name, G::NTHR, WPS);
+}
+
+static const TowerTable &towers()
+{
+    constexpr int f32 = AZH_DTYPE_F32, bf16 = AZH_DTYPE_BF16, f16 = AZH_DTYPE_F16;
+    static const TowerTable t = {
+        {{tower_row<Geo2>((const void *)k_tower2_pair<bf16>, "k_tower2_pair<bf16>", NTHREADS, 2),
+          tower_row<Geo2>((const void *)k_tower2_pair<f16>, "k_tower2_pair<f16>", NTHREADS, 2)},
+         {tower_row<Geo2Thin>((const void *)k_tower2_pair<bf16, Geo2Thin>, "k_tower2_pair<bf16,Geo2Thin>", NTHREADS, 2),
+          tower_row<Geo2Thin>((const void *)k_tower2_pair<f16, Geo2Thin>, "k_tower2_pair<f16,Geo2Thin>", NTHREADS, 2)}},
+        {row1<f32, 3, 1, false, 64>("k_tower<f32,3,1,false,64>"), row1<bf16, 3, 1, false, 64>("k_tower<bf16,3,1,false,64>"),
+         row1<f16, 3, 1, false, 64>("k_tower<f16,3,1,false,64>")},
+        {row1<f32, 1, 2, false, 256>("k_tower<f32,1,2,false,256>"), row1<bf16, 3, 2, false, 256>("k_tower<bf16,3,2,false,256>"),
+         row1<f16, 3, 2, false, 256>("k_tower<f16,3,2,false,256>")},
+        tower_row<Geo2>((const void *)k_tower2<bf16, true>, "k_tower2<bf16,true>", NTHREADS, 2),
+        {tower_row<Geo2Thin>((const void *)k_tower2_thin<bf16>, "k_tower2_thin<bf16>", NTHREADS, 2),
+         tower_row<Geo2Thin>((const void *)k_tower2_thin<f16>, "k_tower2_thin<f16>", NTHREADS, 2)},
+        {tower_row<Geo2>((const void *)k_tower2<bf16>, "k_tower2<bf16>", NTHREADS, 2),
+         tower_row<Geo2>((const void *)k_tower2<f16>, "k_tower2<f16>", NTHREADS, 2)},
+        {row1<bf16, 6, 1, true>("k_tower<bf16,6,1,true>"), row1<bf16, 3, 2, true>("k_tower<bf16,3,2,true>")},
+        row1<f32, 3, 1>("k_tower<f32,3,1>"),
+        {{row1<bf16, 6, 1>("k_tower<bf16,6,1>"), row1<bf16, 3, 2>("k_tower<bf16,3,2>")},
+         {row1<f16, 6, 1>("k_tower<f16,6,1>"), row1<f16, 3, 2>("k_tower<f16,3,2>")}},
+    };
+    return t;
+}
+
+// The dispatch, and nothing else: which row a launch runs.  Reads no environment and touches no device — tower_variant(),
+// tower_boards() and lds_range_ok() feed it, azh_net_tower_choice asks it the same question without a launch.
+// 0: *row is the kernel; -2: refused (message recorded); 1: `pair` only — the fused pair kernel does not apply (f32, another
+// width, AZH_TOWER=1, a device without the LDS range check) and the caller launches the two nets one after the other.
+static int choose_tower(int filters, int dtype, bool thin, bool stamped, bool pair, bool variant1, bool six, bool lds_range_ok,
+                        const TowerKernel **row)
+{
+    const TowerTable &t = towers();
+    const bool bits16 = dtype == AZH_DTYPE_BF16 || dtype == AZH_DTYPE_F16;
+    const bool v2 = filters == 128 && bits16 && !variant1 && lds_range_ok;
+    const int h = dtype == AZH_DTYPE_F16;  // index of a 16-bit pair of rows
+    if (pair) {
+        if (stamped)
+            return azh_fail(-2, "stamps are built for single launches only");
+        if (!v2)
+            return 1;
+        *row = &t.pair[thin][h];
         return 0;
-    hipLaunchKernelGGL((k_tower<DT, NB, WPS, STAMP, FT>), dim3(grid), dim3(G::NTHR), G::LDS_BYTES, stream, args,
-                       place_workers(H, tiles, WPS * 256 / G::NTHR > 0 ? WPS * 256 / G::NTHR : 1));
-    AZH_HIP(hipGetLastError());
+    }
+    if (dtype < 0 || dtype > 2)
+        return azh_fail(-2, "bad dtype %d", dtype);
+    if (filters != 64 && filters != 128 && filters != 256)
+        return azh_fail(-2, "towers are built for 64, 128 and 256 filters, got %d", filters);
+    if (stamped && filters != 128)
+        return azh_fail(-2, "stamps are built for the 128-filter bf16 tower only");
+    if (stamped && dtype != AZH_DTYPE_BF16)
+        return azh_fail(-2, "stamps are built for bf16 only");
+    if (filters != 128)
+        *row = filters == 64 ? &t.w64[dtype] : &t.w256[dtype];
+    else if (v2)
+        *row = stamped ? &t.v2_stamped : thin ? &t.v2_thin[h] : &t.v2[h];
+    else if (stamped)
+        *row = &t.v1_stamped[six ? 0 : 1];
+    else
+        *row = dtype == AZH_DTYPE_F32 ? &t.v1_f32 : &t.v1[h][six ? 0 : 1];
     return 0;
 }
 
-// Boards per workgroup for the 16-bit towers: 3 (two workgroups per CU) unless
-// AZH_TOWER_BOARDS=6 asks for one 6-board workgroup per CU.
-template <int DT, bool STAMP = false> static int launch_tower2(const TowerArgs &args, int max_n, hipStream_t stream,
-                                                               const AdvanceHook &H = no_hook())
+// One launch of `tiles` tile workgroups of kernel k (and the hook's move-playing workgroups); b: the second net of a pair kernel.
+static int launch_tower(const TowerKernel &k, int tiles, const TowerArgs &a, const TowerArgs *b, hipStream_t stream, const AdvanceHook *hook)
 {
-    static_assert(Geo2::LDS_BYTES >= (int)sizeof(TreeLds), "the launch's move-playing workgroups use the tower's LDS as their scratch");
-    static bool attr_set[MAX_DEVICES] = {};
     const int dev = current_device();
     if (dev < 0)
-        return azh_fail(-4, "launch_tower2: hipGetDevice failed");
-    if (!attr_set[dev]) {
-        AZH_HIP(hipFuncSetAttribute((const void *)k_tower2<DT, STAMP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    Geo2::LDS_BYTES));
-        attr_set[dev] = true;
+        return azh_fail(-4, "%s: hipGetDevice failed", k.name);
+    if (!k.attr_set[dev]) {
+        AZH_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes));
+        k.attr_set[dev] = true;
     }
-    const int tiles = (max_n + Geo2::BOARDS - 1) / Geo2::BOARDS, grid = tiles + H.workers;
+    static const AdvanceHook none = {};  // workers = 0
+    AdvanceHook H = place_workers(hook ? *hook : none, tiles, k.per_cu);
+    const int grid = tiles + H.workers;
     if (grid <= 0)
         return 0;
-    hipLaunchKernelGGL((k_tower2<DT, STAMP>), dim3(grid), dim3(NTHREADS), Geo2::LDS_BYTES, stream, args, place_workers(H, tiles, 2));
-    AZH_HIP(hipGetLastError());
-    return 0;
-}
-
-// one board per workgroup (Geo2Thin): the launch for a handful of boards
-template <int DT> static int launch_tower2_thin(const TowerArgs &args, int max_n, hipStream_t stream, const AdvanceHook &H = no_hook())
-{
-    static bool attr_set[MAX_DEVICES] = {};
-    const int dev = current_device();
-    if (dev < 0)
-        return azh_fail(-4, "launch_tower2_thin: hipGetDevice failed");
-    if (!attr_set[dev]) {
-        AZH_HIP(hipFuncSetAttribute((const void *)k_tower2_thin<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo2::LDS_BYTES));
-        attr_set[dev] = true;
-    }
-    if (max_n + H.workers <= 0)
-        return 0;
-    hipLaunchKernelGGL((k_tower2_thin<DT>), dim3(max_n + H.workers), dim3(NTHREADS), Geo2::LDS_BYTES, stream, args,
-                       place_workers(H, max_n, 2));
+    void *args[3] = {(void *)&a, b ? (void *)b : (void *)&H, &H};  // (A, H) or (A, B, H): a kernel reads as many as it takes
+    (void)hipLaunchKernel(k.fn, dim3(grid), dim3(k.threads), args, k.lds_bytes, stream);
     AZH_HIP(hipGetLastError());
     return 0;
 }
@@ -1823,46 +1876,18 @@ __global__ __launch_bounds__(256) void k_sym_reduce(const float *__restrict__ sy
     }
 }
 
-// Evaluate up to max_n boards (dense list `list`/`count` on the device, or the
-// first n boards when both are null).  Everything is indexed by game.
-static int net_launch(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
-                      const int *d_count, int max_n, unsigned long long blockers, float *d_logits,
-                      float *d_values, hipStream_t stream, unsigned long long *d_stamps, int sym, int thin = 0,
-                      const void *hook = nullptr, const unsigned long long *d_masks = nullptr);
-
-// thin: the caller expects a handful of boards (<= 512): one board per workgroup (Geo2Thin) where that kernel applies
-int azh_net_launch(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
-                   const int *d_count, int max_n, unsigned long long blockers, float *d_logits,
-                   float *d_values, hipStream_t stream, unsigned long long *d_stamps, int thin, const void *advance_hook,
-                   const unsigned long long *d_masks)
+static bool lds_range_ok()
 {
-    return net_launch(net, dtype, d_boards, d_list, d_count, max_n, blockers, d_logits, d_values, stream, d_stamps, 0, thin,
-                      advance_hook, d_masks);
+#if AZH_OOBZERO
+    return lds_range_check() == 1;
+#else
+    return true;  // (this build steers the off-board taps to zero slots inside the allocation)
+#endif
 }
 
-// Symmetry-averaged evaluation: the tower runs 8 * n virtual boards into the scratch arrays
-// (d_tmp_logits [8 max_n][833], d_tmp_values [8 max_n]), k_sym_reduce writes the averages by game.
-int azh_net_launch_sym(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
-                       const int *d_count, int max_n, unsigned long long blockers, float *d_tmp_logits,
-                       float *d_tmp_values, float *d_logits, float *d_values, hipStream_t stream, int thin, const void *advance_hook,
-                       const unsigned long long *d_masks)
+static TowerArgs tower_args(const azh_net *net, int dtype, const NetBatch &b, const NetOptions &o)
 {
-    if (max_n <= 0)
-        return 0;
-    int rc = net_launch(net, dtype, d_boards, d_list, d_count, max_n, blockers, d_tmp_logits, d_tmp_values, stream,
-                        nullptr, 1, thin, advance_hook, d_masks);
-    if (rc)
-        return rc;
-    hipLaunchKernelGGL(k_sym_reduce, dim3(max_n), dim3(256), 0, stream, (const float *)d_tmp_logits,
-                       (const float *)d_tmp_values, d_list, d_count, max_n, d_logits, d_values);
-    AZH_HIP(hipGetLastError());
-    return 0;
-}
-
-static TowerArgs tower_args(const azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
-                            const int *d_count, int max_n, unsigned long long blockers, float *d_logits, float *d_values,
-                            unsigned long long *d_stamps, int sym, const unsigned long long *d_masks)
-{
+    const bool sym = o.sym_logits && o.sym_values;
     TowerArgs a;
     a.conv_w = net->bufs[dtype].conv_w;
     a.head_w = net->bufs[dtype].head_w;
@@ -1872,124 +1897,77 @@ static TowerArgs tower_args(const azh_net *net, int dtype, const unsigned long l
     a.fc_w = net->d_fcw;
     a.fc_b = net->fc_b;
     a.blocks = net->blocks;
-    a.boards = d_boards;
-    a.list = d_list;
-    a.count = d_count;
-    a.n = max_n;
-    a.blockers = blockers;
-    a.masks = d_masks;
-    a.logits = d_logits;
-    a.values = d_values;
-    a.stamps = d_stamps;
+    a.boards = b.boards;
+    a.list = b.list;
+    a.count = b.count;
+    a.n = b.max_n;
+    a.blockers = b.blockers;
+    a.masks = b.masks;
+    a.logits = sym ? o.sym_logits : b.logits;
+    a.values = sym ? o.sym_values : b.values;
+    a.stamps = o.stamps;
     a.sym = sym;
     return a;
 }
 
-// Two nets, two dense leaf lists, ONE launch (k_tower2_pair): the arena's evaluator.  Returns 1 — nothing launched — where
-// the fused pair kernel does not apply (f32, another width, AZH_TOWER=1, a device without the LDS range check): the caller
-// then launches the two nets one after the other.  max_n bounds count_a + count_b (a game has one leaf).
-int azh_net_launch_pair(azh_net *net_a, azh_net *net_b, int dtype, const unsigned long long *d_boards, const int *d_list_a,
-                        const int *d_count_a, const int *d_list_b, const int *d_count_b, int max_n,
-                        unsigned long long blockers, float *d_logits, float *d_values, hipStream_t stream, int thin,
-                        const void *advance_hook, const unsigned long long *d_masks)
+// Evaluate up to batch.max_n boards; everything is indexed by game.
+int azh_net_launch(azh_net *net, int dtype, const NetBatch &b, hipStream_t stream, const NetOptions &o)
 {
-    if (dtype != AZH_DTYPE_BF16 && dtype != AZH_DTYPE_F16)
-        return 1;
-    if (net_a->filters != 128 || net_b->filters != 128 || tower_variant() != 2 || !d_count_a || !d_count_b)
-        return 1;
-#if AZH_OOBZERO
-    if (lds_range_check() != 1)
-        return 1;
-#endif
-    if (net_pack(net_a, dtype) || net_pack(net_b, dtype))
+    const bool sym = o.sym_logits && o.sym_values;
+    if (sym && b.max_n <= 0)
+        return 0;
+    const TowerKernel *k = nullptr;
+    if (int rc = choose_tower(net->filters, dtype, o.thin != 0, o.stamps != nullptr, false, tower_variant() == 1,
+                              tower_boards() == 6, lds_range_ok(), &k))
+        return rc;
+    if (net_pack(net, dtype))
         return -1;
-    const TowerArgs a = tower_args(net_a, dtype, d_boards, d_list_a, d_count_a, max_n, blockers, d_logits, d_values, nullptr, 0, d_masks);
-    const TowerArgs b = tower_args(net_b, dtype, d_boards, d_list_b, d_count_b, max_n, blockers, d_logits, d_values, nullptr, 0, d_masks);
-    static bool attr_set[MAX_DEVICES][4] = {};
-    const int dev = current_device();
-    if (dev < 0)
-        return azh_fail(-4, "azh_net_launch_pair: hipGetDevice failed");
-    const int k = (dtype == AZH_DTYPE_BF16 ? 0 : 1) + (thin ? 2 : 0);
-    const void *fn = k == 0 ? (const void *)k_tower2_pair<AZH_DTYPE_BF16> : k == 1 ? (const void *)k_tower2_pair<AZH_DTYPE_F16>
-                   : k == 2 ? (const void *)k_tower2_pair<AZH_DTYPE_BF16, Geo2Thin> : (const void *)k_tower2_pair<AZH_DTYPE_F16, Geo2Thin>;
-    if (!attr_set[dev][k]) {
-        AZH_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, Geo2::LDS_BYTES));
-        attr_set[dev][k] = true;
-    }
-    // ceil(nA / B) + ceil(nB / B) <= (nA + nB) / B + 2 workgroups of B boards (B = 3, or 1 for thin batches)
-    const int tiles = max_n / (thin ? Geo2Thin::BOARDS : Geo2::BOARDS) + 2;
-    const AdvanceHook H = place_workers(advance_hook ? *static_cast<const AdvanceHook *>(advance_hook) : no_hook(), tiles, 2);
-    const int grid = tiles + H.workers;
-    switch (k) {
-    case 0: hipLaunchKernelGGL((k_tower2_pair<AZH_DTYPE_BF16>), dim3(grid), dim3(NTHREADS), Geo2::LDS_BYTES, stream, a, b, H); break;
-    case 1: hipLaunchKernelGGL((k_tower2_pair<AZH_DTYPE_F16>), dim3(grid), dim3(NTHREADS), Geo2::LDS_BYTES, stream, a, b, H); break;
-    case 2: hipLaunchKernelGGL((k_tower2_pair<AZH_DTYPE_BF16, Geo2Thin>), dim3(grid), dim3(NTHREADS), Geo2::LDS_BYTES, stream, a, b, H); break;
-    default: hipLaunchKernelGGL((k_tower2_pair<AZH_DTYPE_F16, Geo2Thin>), dim3(grid), dim3(NTHREADS), Geo2::LDS_BYTES, stream, a, b, H); break;
-    }
+    const int n = sym ? 8 * b.max_n : b.max_n;  // grid size: virtual boards
+    if (int rc = launch_tower(*k, (n + k->boards - 1) / k->boards, tower_args(net, dtype, b, o), nullptr, stream, o.hook))
+        return rc;
+    if (!sym)
+        return 0;
+    hipLaunchKernelGGL(k_sym_reduce, dim3(b.max_n), dim3(256), 0, stream, (const float *)o.sym_logits,
+                       (const float *)o.sym_values, b.list, b.count, b.max_n, b.logits, b.values);
     AZH_HIP(hipGetLastError());
     return 0;
 }
 
-static int net_launch(azh_net *net, int dtype, const unsigned long long *d_boards, const int *d_list,
-                      const int *d_count, int max_n, unsigned long long blockers, float *d_logits,
-                      float *d_values, hipStream_t stream, unsigned long long *d_stamps, int sym, int thin, const void *hook,
-                      const unsigned long long *d_masks)
+int azh_net_launch_pair(azh_net *net_a, azh_net *net_b, int dtype, const NetBatch &b, const int *list_b, const int *count_b,
+                        hipStream_t stream, const NetOptions &o)
 {
-    if (dtype < 0 || dtype > 2)
-        return azh_fail(-2, "bad dtype %d", dtype);
-    const AdvanceHook &H = hook ? *static_cast<const AdvanceHook *>(hook) : no_hook();
-    if (net_pack(net, dtype))
+    if (net_b->filters != net_a->filters || !b.count || !count_b || o.sym_logits || o.sym_values)
+        return 1;
+    const TowerKernel *k = nullptr;
+    if (int rc = choose_tower(net_a->filters, dtype, o.thin != 0, o.stamps != nullptr, true, tower_variant() == 1,
+                              tower_boards() == 6, lds_range_ok(), &k))
+        return rc;
+    if (net_pack(net_a, dtype) || net_pack(net_b, dtype))
         return -1;
-    TowerArgs a = tower_args(net, dtype, d_boards, d_list, d_count, max_n, blockers, d_logits, d_values, d_stamps, sym, d_masks);
-    if (sym)
-        max_n *= 8;  // grid size: virtual boards
-    if (net->filters != 128) {
-        // Other widths (the reference's FILTERS is a class attribute, uai_interface.py:92-93 patches it): the 32x32 tower
-        // templated on the width — one wave per 32 output channels, 3 boards per workgroup (1 for f32 at 256 filters: LDS).
-        if (d_stamps)
-            return azh_fail(-2, "stamps are built for the 128-filter bf16 tower only");
-        if (net->filters == 64) {
-            switch (dtype) {
-            case AZH_DTYPE_F32: return launch_tower<AZH_DTYPE_F32, 3, 1, false, 64>(a, max_n, stream, H);
-            case AZH_DTYPE_BF16: return launch_tower<AZH_DTYPE_BF16, 3, 1, false, 64>(a, max_n, stream, H);
-            default: return launch_tower<AZH_DTYPE_F16, 3, 1, false, 64>(a, max_n, stream, H);
-            }
-        }
-        switch (dtype) {
-        case AZH_DTYPE_F32: return launch_tower<AZH_DTYPE_F32, 1, 2, false, 256>(a, max_n, stream, H);
-        case AZH_DTYPE_BF16: return launch_tower<AZH_DTYPE_BF16, 3, 2, false, 256>(a, max_n, stream, H);
-        default: return launch_tower<AZH_DTYPE_F16, 3, 2, false, 256>(a, max_n, stream, H);
-        }
-    }
-    const bool six = tower_boards() == 6;
-    bool v2 = tower_variant() == 2 && dtype != AZH_DTYPE_F32;
-#if AZH_OOBZERO
-    if (v2 && lds_range_check() != 1)
-        v2 = false;
-#endif
-    if (v2) {
-        if (d_stamps)
-            return dtype == AZH_DTYPE_BF16 ? launch_tower2<AZH_DTYPE_BF16, true>(a, max_n, stream, H)
-                                           : azh_fail(-2, "stamps are built for bf16 only");
-        if (thin)
-            return dtype == AZH_DTYPE_BF16 ? launch_tower2_thin<AZH_DTYPE_BF16>(a, max_n, stream, H)
-                                           : launch_tower2_thin<AZH_DTYPE_F16>(a, max_n, stream, H);
-        return dtype == AZH_DTYPE_BF16 ? launch_tower2<AZH_DTYPE_BF16>(a, max_n, stream, H)
-                                       : launch_tower2<AZH_DTYPE_F16>(a, max_n, stream, H);
-    }
-    if (d_stamps) {  // diagnostic instantiations (bf16 only)
-        if (dtype != AZH_DTYPE_BF16)
-            return azh_fail(-2, "stamps are built for bf16 only");
-        return six ? launch_tower<AZH_DTYPE_BF16, 6, 1, true>(a, max_n, stream, H)
-                   : launch_tower<AZH_DTYPE_BF16, 3, 2, true>(a, max_n, stream, H);
-    }
-    switch (dtype) {
-    case AZH_DTYPE_F32: return launch_tower<AZH_DTYPE_F32, 3, 1>(a, max_n, stream, H);
-    case AZH_DTYPE_BF16:
-        return six ? launch_tower<AZH_DTYPE_BF16, 6, 1>(a, max_n, stream, H) : launch_tower<AZH_DTYPE_BF16, 3, 2>(a, max_n, stream, H);
-    default:
-        return six ? launch_tower<AZH_DTYPE_F16, 6, 1>(a, max_n, stream, H) : launch_tower<AZH_DTYPE_F16, 3, 2>(a, max_n, stream, H);
-    }
+    NetBatch second = b;
+    second.list = list_b;
+    second.count = count_b;
+    const TowerArgs args_a = tower_args(net_a, dtype, b, o), args_b = tower_args(net_b, dtype, second, o);
+    // ceil(nA / B) + ceil(nB / B) <= (nA + nB) / B + 2 workgroups of B boards (B = 3, or 1 for thin batches)
+    return launch_tower(*k, b.max_n / k->boards + 2, args_a, &args_b, stream, o.hook);
+}
+
+extern "C" int azh_net_tower_choice(int filters, int dtype, int thin, int stamped, int pair, int variant1, int six_boards,
+                                    int lds_range_ok, azh_tower_choice *out)
+{
+    if (!out)
+        return azh_fail(-1, "azh_net_tower_choice: null argument");
+    memset(out, 0, sizeof *out);
+    const TowerKernel *k = nullptr;
+    if (int rc = choose_tower(filters, dtype, thin != 0, stamped != 0, pair != 0, variant1 != 0, six_boards != 0,
+                              lds_range_ok != 0, &k))
+        return rc;
+    snprintf(out->kernel, sizeof out->kernel, "%s", k->name);
+    out->boards = k->boards;
+    out->threads = k->threads;
+    out->lds_bytes = k->lds_bytes;
+    out->per_cu = k->per_cu;
+    return 0;
 }
 
 // device temporary owned by a host function: released when the function returns, error paths included
@@ -2003,61 +1981,21 @@ struct DevBuf {
     DevBuf &operator=(const DevBuf &) = delete;
 };
 
-// mode: 0 the ordinary tower, 1 one board per workgroup (thin), 2 test-time symmetry averaging; masks: null, or one per board
-static int net_forward(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, uint64_t blockers, const uint64_t *masks,
-                       float *logits_out, float *values_out, int mode, const char *who);
-
-extern "C" int azh_net_forward(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
-                               uint64_t blockers, float *logits_out, float *values_out)
+extern "C" int azh_net_forward(azh_net *net, int dtype, int mode, int n, const uint64_t *leaf_boards, uint64_t blockers,
+                               const uint64_t *blockers_per_board, float *logits_out, float *values_out)
 {
-    return net_forward(net, dtype, n, leaf_boards, blockers, nullptr, logits_out, values_out, 0, "azh_net_forward");
-}
-
-extern "C" int azh_net_forward_thin(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
-                                    uint64_t blockers, float *logits_out, float *values_out)
-{
-    return net_forward(net, dtype, n, leaf_boards, blockers, nullptr, logits_out, values_out, 1, "azh_net_forward");
-}
-
-extern "C" int azh_net_forward_sym(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
-                                   uint64_t blockers, float *logits_out, float *values_out)
-{
-    return net_forward(net, dtype, n, leaf_boards, blockers, nullptr, logits_out, values_out, 2, "azh_net_forward_sym");
-}
-
-// A wall mask per board (null: no walls anywhere, as blockers = 0): the header.
-static int net_forward_masks(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, const uint64_t *masks, float *logits_out,
-                             float *values_out, int mode, const char *who)
-{
+    const uint64_t *masks = blockers_per_board;
+    if (!net || !leaf_boards || !logits_out || !values_out || n < 0)
+        return azh_fail(-1, "azh_net_forward: bad argument");
+    if (mode != AZH_FORWARD_PLAIN && mode != AZH_FORWARD_THIN && mode != AZH_FORWARD_SYM)
+        return azh_fail(-2, "azh_net_forward: bad mode %d", mode);
+    if (masks && blockers)
+        return azh_fail(-2, "azh_net_forward: a mask per board AND blockers = %#llx: the wall plane has one source",
+                        (unsigned long long)blockers);
     for (int i = 0; masks && i < n; i++)
         if (masks[i] >> 49)
-            return azh_fail(-2, "%s: the mask of board %d (%#llx) has bits beyond the 49 cells", who, i, (unsigned long long)masks[i]);
-    return net_forward(net, dtype, n, leaf_boards, 0ULL, masks, logits_out, values_out, mode, who);
-}
-
-extern "C" int azh_net_forward_masks(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
-                                     const uint64_t *blockers_per_board, float *logits_out, float *values_out)
-{
-    return net_forward_masks(net, dtype, n, leaf_boards, blockers_per_board, logits_out, values_out, 0, "azh_net_forward_masks");
-}
-
-extern "C" int azh_net_forward_masks_thin(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
-                                          const uint64_t *blockers_per_board, float *logits_out, float *values_out)
-{
-    return net_forward_masks(net, dtype, n, leaf_boards, blockers_per_board, logits_out, values_out, 1, "azh_net_forward_masks_thin");
-}
-
-extern "C" int azh_net_forward_masks_sym(azh_net *net, int dtype, int n, const uint64_t *leaf_boards,
-                                         const uint64_t *blockers_per_board, float *logits_out, float *values_out)
-{
-    return net_forward_masks(net, dtype, n, leaf_boards, blockers_per_board, logits_out, values_out, 2, "azh_net_forward_masks_sym");
-}
-
-static int net_forward(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, uint64_t blockers, const uint64_t *masks,
-                       float *logits_out, float *values_out, int mode, const char *who)
-{
-    if (!net || !leaf_boards || !logits_out || !values_out || n < 0)
-        return azh_fail(-1, "%s: bad argument", who);
+            return azh_fail(-2, "azh_net_forward: the mask of board %d (%#llx) has bits beyond the 49 cells", i,
+                            (unsigned long long)masks[i]);
     if (n == 0)
         return 0;
     DevBuf d_b, d_m, d_l, d_v, d_tl, d_tv;  // freed on every path out of this function
@@ -2069,17 +2007,22 @@ static int net_forward(azh_net *net, int dtype, int n, const uint64_t *leaf_boar
         AZH_HIP(d_m.alloc((size_t)n * 8));
         AZH_HIP(hipMemcpy(d_m.p, masks, (size_t)n * 8, hipMemcpyHostToDevice));
     }
-    int rc;
-    if (mode == 2) {
+    NetBatch b;
+    b.boards = d_b.as<unsigned long long>();
+    b.max_n = n;
+    b.blockers = blockers;
+    b.masks = d_m.as<unsigned long long>();
+    b.logits = d_l.as<float>();
+    b.values = d_v.as<float>();
+    NetOptions o;
+    o.thin = mode == AZH_FORWARD_THIN;
+    if (mode == AZH_FORWARD_SYM) {
         AZH_HIP(d_tl.alloc((size_t)n * 8 * 833 * 4));
         AZH_HIP(d_tv.alloc((size_t)n * 8 * 4));
-        rc = azh_net_launch_sym(net, dtype, d_b.as<unsigned long long>(), nullptr, nullptr, n, blockers, d_tl.as<float>(),
-                                d_tv.as<float>(), d_l.as<float>(), d_v.as<float>(), 0, 0, nullptr, d_m.as<unsigned long long>());
-    } else {
-        rc = azh_net_launch(net, dtype, d_b.as<unsigned long long>(), nullptr, nullptr, n, blockers, d_l.as<float>(),
-                            d_v.as<float>(), 0, nullptr, mode, nullptr, d_m.as<unsigned long long>());
+        o.sym_logits = d_tl.as<float>();
+        o.sym_values = d_tv.as<float>();
     }
-    if (rc)
+    if (int rc = azh_net_launch(net, dtype, b, 0, o))
         return rc;
     AZH_HIP(hipDeviceSynchronize());
     AZH_HIP(hipMemcpy(logits_out, d_l.p, (size_t)n * 833 * 4, hipMemcpyDeviceToHost));
@@ -2087,53 +2030,70 @@ static int net_forward(azh_net *net, int dtype, int n, const uint64_t *leaf_boar
     return 0;
 }
 
+// n synthetic boards on the device with arrays for their evaluations: what azh_net_bench and azh_net_stamps launch over
+struct SyntheticBatch {
+    DevBuf boards, logits, values;
+    NetBatch batch;
+    int upload(int n)
+    {
+        std::vector<unsigned long long> h((size_t)n * 2);
+        unsigned long long x = 0x9E3779B97F4A7C15ULL;
+        for (int i = 0; i < n; i++) {
+            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+            const unsigned long long m = x & 0x1FFFFFFFFFFFFULL;
+            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+            h[2 * (size_t)i] = m;
+            h[2 * (size_t)i + 1] = x & 0x1FFFFFFFFFFFFULL & ~m;
+        }
+        AZH_HIP(boards.alloc((size_t)n * 16));
+        AZH_HIP(logits.alloc((size_t)n * 833 * 4));
+        AZH_HIP(values.alloc((size_t)n * 4));
+        AZH_HIP(hipMemcpy(boards.p, h.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+        batch.boards = boards.as<unsigned long long>();
+        batch.max_n = n;
+        batch.logits = logits.as<float>();
+        batch.values = values.as<float>();
+        return 0;
+    }
+};
+
 // Net-only timing hook: `iters` launches of the tower over n synthetic boards, HIP-event
 // timed on one stream; *ms_out = average milliseconds per launch.
-static int net_bench(azh_net *net, int dtype, int n, int iters, float *ms_out, int thin);
-extern "C" int azh_net_bench(azh_net *net, int dtype, int n, int iters, float *ms_out) { return net_bench(net, dtype, n, iters, ms_out, 0); }
-extern "C" int azh_net_bench_thin(azh_net *net, int dtype, int n, int iters, float *ms_out) { return net_bench(net, dtype, n, iters, ms_out, 1); }
-
-static int net_bench(azh_net *net, int dtype, int n, int iters, float *ms_out, int thin)
+extern "C" int azh_net_bench(azh_net *net, int dtype, int mode, int n, int iters, float *ms_out)
 {
     if (!net || n <= 0 || iters <= 0 || !ms_out)
         return azh_fail(-1, "azh_net_bench: bad argument");
-    std::vector<unsigned long long> boards((size_t)n * 2);
-    unsigned long long x = 0x9E3779B97F4A7C15ULL;
-    for (int i = 0; i < n; i++) {
-        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-        const unsigned long long m = x & 0x1FFFFFFFFFFFFULL;
-        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-        boards[2 * (size_t)i] = m;
-        boards[2 * (size_t)i + 1] = x & 0x1FFFFFFFFFFFFULL & ~m;
-    }
-    unsigned long long *d_b = nullptr;
-    float *d_l = nullptr, *d_v = nullptr;
-    AZH_HIP(hipMalloc((void **)&d_b, (size_t)n * 16));
-    AZH_HIP(hipMalloc((void **)&d_l, (size_t)n * 833 * 4));
-    AZH_HIP(hipMalloc((void **)&d_v, (size_t)n * 4));
-    AZH_HIP(hipMemcpy(d_b, boards.data(), (size_t)n * 16, hipMemcpyHostToDevice));
-    hipStream_t st;
-    hipEvent_t e0, e1;
-    AZH_HIP(hipStreamCreate(&st));
-    AZH_HIP(hipEventCreate(&e0));
-    AZH_HIP(hipEventCreate(&e1));
+    if (mode != AZH_FORWARD_PLAIN && mode != AZH_FORWARD_THIN)
+        return azh_fail(-2, "azh_net_bench: bad mode %d", mode);
+    struct Clock {  // released on every path out of this function
+        hipStream_t st = nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Clock()
+        {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+            if (st) (void)hipStreamDestroy(st);
+        }
+    } c;
+    SyntheticBatch s;
+    if (int rc = s.upload(n))
+        return rc;
+    AZH_HIP(hipStreamCreate(&c.st));
+    AZH_HIP(hipEventCreate(&c.e0));
+    AZH_HIP(hipEventCreate(&c.e1));
+    NetOptions o;
+    o.thin = mode == AZH_FORWARD_THIN;
     int rc = 0;
     for (int i = 0; i < 3 && rc == 0; i++)
-        rc = azh_net_launch(net, dtype, d_b, nullptr, nullptr, n, 0, d_l, d_v, st, nullptr, thin);
-    AZH_HIP(hipEventRecord(e0, st));
+        rc = azh_net_launch(net, dtype, s.batch, c.st, o);
+    AZH_HIP(hipEventRecord(c.e0, c.st));
     for (int i = 0; i < iters && rc == 0; i++)
-        rc = azh_net_launch(net, dtype, d_b, nullptr, nullptr, n, 0, d_l, d_v, st, nullptr, thin);
-    AZH_HIP(hipEventRecord(e1, st));
-    AZH_HIP(hipStreamSynchronize(st));
+        rc = azh_net_launch(net, dtype, s.batch, c.st, o);
+    AZH_HIP(hipEventRecord(c.e1, c.st));
+    AZH_HIP(hipStreamSynchronize(c.st));
     float ms = 0.0f;
-    AZH_HIP(hipEventElapsedTime(&ms, e0, e1));
+    AZH_HIP(hipEventElapsedTime(&ms, c.e0, c.e1));
     *ms_out = ms / (float)iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipStreamDestroy(st);
-    (void)hipFree(d_b);
-    (void)hipFree(d_l);
-    (void)hipFree(d_v);
     return rc;
 }
 
@@ -2143,33 +2103,21 @@ extern "C" int azh_net_stamps(azh_net *net, int n, int wgs, uint64_t *out)
 {
     if (!net || n <= 0 || wgs <= 0 || !out)
         return azh_fail(-1, "azh_net_stamps: bad argument");
-    if (net->filters != 128)
-        return azh_fail(-2, "azh_net_stamps: built for the 128-filter bf16 tower only");
     const int grid_max = (n + 2) / 3;
-    std::vector<unsigned long long> boards((size_t)n * 2);
-    unsigned long long x = 0x9E3779B97F4A7C15ULL;
-    for (int i = 0; i < n; i++) {
-        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-        const unsigned long long m = x & 0x1FFFFFFFFFFFFULL;
-        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-        boards[2 * (size_t)i] = m;
-        boards[2 * (size_t)i + 1] = x & 0x1FFFFFFFFFFFFULL & ~m;
-    }
-    unsigned long long *d_b = nullptr, *d_s = nullptr;
-    float *d_l = nullptr, *d_v = nullptr;
     const size_t sbytes = (size_t)grid_max * OCT * 128 * 8;
-    AZH_HIP(hipMalloc((void **)&d_b, (size_t)n * 16));
-    AZH_HIP(hipMalloc((void **)&d_l, (size_t)n * 833 * 4));
-    AZH_HIP(hipMalloc((void **)&d_v, (size_t)n * 4));
-    AZH_HIP(hipMalloc((void **)&d_s, sbytes));
-    AZH_HIP(hipMemset(d_s, 0, sbytes));
-    AZH_HIP(hipMemcpy(d_b, boards.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+    SyntheticBatch s;
+    DevBuf d_s;
+    if (int rc = s.upload(n))
+        return rc;
+    AZH_HIP(d_s.alloc(sbytes));
+    AZH_HIP(hipMemset(d_s.p, 0, sbytes));
+    NetOptions o;
+    o.stamps = d_s.as<unsigned long long>();
     int rc = 0;
     for (int i = 0; i < 3 && rc == 0; i++)
-        rc = azh_net_launch(net, AZH_DTYPE_BF16, d_b, nullptr, nullptr, n, 0, d_l, d_v, 0, d_s);
+        rc = azh_net_launch(net, AZH_DTYPE_BF16, s.batch, 0, o);  // (refused for another width: choose_tower)
     AZH_HIP(hipDeviceSynchronize());
     const int have = wgs < grid_max ? wgs : grid_max;
-    AZH_HIP(hipMemcpy(out, d_s, (size_t)have * OCT * 128 * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(d_b); (void)hipFree(d_l); (void)hipFree(d_v); (void)hipFree(d_s);
+    AZH_HIP(hipMemcpy(out, d_s.p, (size_t)have * OCT * 128 * 8, hipMemcpyDeviceToHost));
     return rc;
 }

@@ -1219,7 +1219,13 @@ extern "C" int azh_samples_surprise(azh_samples *s, azh_net *net, int dtype, int
         hipLaunchKernelGGL(k_samples_pack_boards, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s->view(), (u32)at, n,
                            sc.boards);
         AZH_HIP(hipGetLastError());
-        if (int rc = azh_net_launch(net, dtype, sc.boards, nullptr, nullptr, n, run.blockers, sc.logits, sc.values, st))
+        azh::NetBatch batch;
+        batch.boards = sc.boards;
+        batch.max_n = n;
+        batch.blockers = run.blockers;
+        batch.logits = sc.logits;
+        batch.values = sc.values;
+        if (int rc = azh_net_launch(net, dtype, batch, st))
             return rc;
         AZH_HIP(hipEventRecord(sc.ev[1], st));
         hipLaunchKernelGGL(k_samples_surprise, dim3((unsigned)n), dim3(WAVE), 0, st, s->view(), (u32)at, n, sc.logits,

@@ -24,6 +24,7 @@ THIN_MAX_GAMES = 512        # AZH_THIN_MAX_GAMES: engines of at most this many g
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "float32": DTYPE_F32, "bf16": DTYPE_BF16,
           "f16": DTYPE_F16, "fp16": DTYPE_F16}
+FORWARD_PLAIN, FORWARD_THIN, FORWARD_SYM = 0, 1, 2          # azh_net_forward's modes
 LEAF_NONE, LEAF_EVAL, LEAF_TERMINAL, LEAF_ROOT = 0, 1, 2, 3
 LEAF_COLLISION = 5          # leaf-parallel search: the path met a node an earlier path of its batch created
 MAX_LEAVES_PER_GAME, MAX_VIRTUAL_LOSS = 64, 16
@@ -126,14 +127,9 @@ SIGNATURES = {
                                           _vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "azh_net_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _f32, _P(_vp)]),
     "azh_net_destroy": (None, [_vp]),
-    "azh_net_forward": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _u64, _vp, _vp]),
-    "azh_net_forward_sym": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _u64, _vp, _vp]),
-    "azh_net_bench": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(_f32)]),
-    "azh_net_forward_thin": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _u64, _vp, _vp]),
-    "azh_net_forward_masks": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
-    "azh_net_forward_masks_thin": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
-    "azh_net_forward_masks_sym": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
-    "azh_net_bench_thin": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(_f32)]),
+    "azh_net_forward": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _u64, _vp, _vp, _vp]),
+    "azh_net_bench": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P(_f32)]),
+    "azh_net_tower_choice": (ctypes.c_int, [ctypes.c_int] * 8 + [_vp]),
     "azh_net_stamps": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
     "azh_engine_create": (ctypes.c_int, [_P(Config), _P(_vp)]),
     "azh_engine_destroy": (None, [_vp]),
@@ -412,6 +408,19 @@ def playout_cap_kind(seed, uid, ply, full_per_65536):
     return int(load().azh_playout_cap_kind(int(seed), int(uid), int(ply), int(full_per_65536)))
 
 
+class TowerChoice(ctypes.Structure):                           # azh_tower_choice
+    _fields_ = [("kernel", ctypes.c_char * 64)] + [(f, ctypes.c_int32) for f in ("boards", "threads", "lds_bytes", "per_cu")]
+
+
+def tower_choice(filters, dtype, thin=False, stamped=False, pair=False, variant1=False, six_boards=False, lds_range_ok=True):
+    """Which tower kernel such a launch runs (azh_net_tower_choice: the library's own dispatch; host arithmetic, no GPU
+    needed): (0, {kernel, boards, threads, lds_bytes, per_cu}), (-2, None) refused, (1, None) no pair kernel here."""
+    c = TowerChoice()
+    rc = int(load().azh_net_tower_choice(filters, dtype, thin, stamped, pair, variant1, six_boards, lds_range_ok, ctypes.byref(c)))
+    return rc, ({"kernel": c.kernel.decode(), **{f: getattr(c, f) for f in ("boards", "threads", "lds_bytes", "per_cu")}}
+                if rc == 0 else None)
+
+
 def forced_prune(prior, W, n, k, c_puct):
     """Policy target pruning (Engine.set_forced_playouts): the visit counts written into a ply's record for a root with
     priors `prior` (after the noise mix), total scores `W` and visits `n` — (M,) u32, 0 where the edge is left out
@@ -673,39 +682,29 @@ class Net:
         check(load().azh_net_create(blocks, filters, _ptr(conv_flat), _ptr(bn_flat), bn_eps, ctypes.byref(h)))
         self.h = h
 
-    def forward(self, leaf_boards, blockers, dtype=DTYPE_BF16, thin=False):
-        """thin: one board per workgroup (the kernel for a handful of boards, azh_net_forward_thin).  blockers: one wall
-        mask for every board, or an array of one mask per board (azh_net_forward_masks: all of them in one launch)."""
+    def _forward(self, mode, leaf_boards, blockers, dtype):
         leaf_boards = np.ascontiguousarray(leaf_boards, dtype=np.uint64).reshape(-1, 2)
         n = len(leaf_boards)
         logits = np.zeros((n, 7, 7, 17), dtype=np.float32)
         values = np.zeros((n, 1), dtype=np.float32)
-        if np.ndim(blockers) == 0:
-            fn = load().azh_net_forward_thin if thin else load().azh_net_forward
-            check(fn(self.h, dtype, n, _ptr(leaf_boards), int(blockers), _ptr(logits), _ptr(values)))
-        else:
-            masks = _board_masks(blockers, n)
-            fn = load().azh_net_forward_masks_thin if thin else load().azh_net_forward_masks
-            check(fn(self.h, dtype, n, _ptr(leaf_boards), _ptr(masks), _ptr(logits), _ptr(values)))
+        masks = None if np.ndim(blockers) == 0 else _board_masks(blockers, n)
+        check(load().azh_net_forward(self.h, dtype, mode, n, _ptr(leaf_boards), 0 if masks is not None else int(blockers),
+                                     _ptr(masks), _ptr(logits), _ptr(values)))
         return logits, values
+
+    def forward(self, leaf_boards, blockers, dtype=DTYPE_BF16, thin=False):
+        """thin: one board per workgroup (the kernel for a handful of boards, AZH_FORWARD_THIN).  blockers: one wall
+        mask for every board, or an array of one mask per board (all of them in one launch)."""
+        return self._forward(FORWARD_THIN if thin else FORWARD_PLAIN, leaf_boards, blockers, dtype)
 
     def forward_sym(self, leaf_boards, blockers, dtype=DTYPE_BF16):
         """nn_evals.evaluate (nn_evals.py:48-62): mean over the 8 dihedral images, one tower launch."""
-        leaf_boards = np.ascontiguousarray(leaf_boards, dtype=np.uint64).reshape(-1, 2)
-        n = len(leaf_boards)
-        logits = np.zeros((n, 7, 7, 17), dtype=np.float32)
-        values = np.zeros((n, 1), dtype=np.float32)
-        if np.ndim(blockers) == 0:
-            check(load().azh_net_forward_sym(self.h, dtype, n, _ptr(leaf_boards), int(blockers), _ptr(logits), _ptr(values)))
-        else:                                    # (one mask per board, as forward)
-            check(load().azh_net_forward_masks_sym(self.h, dtype, n, _ptr(leaf_boards), _ptr(_board_masks(blockers, n)),
-                                                   _ptr(logits), _ptr(values)))
-        return logits, values
+        return self._forward(FORWARD_SYM, leaf_boards, blockers, dtype)
 
     def bench(self, n, iters=20, dtype=DTYPE_BF16, thin=False):
         """Average milliseconds per tower launch over n synthetic boards."""
         ms = ctypes.c_float(0)
-        check((load().azh_net_bench_thin if thin else load().azh_net_bench)(self.h, dtype, n, iters, ctypes.byref(ms)))
+        check(load().azh_net_bench(self.h, dtype, FORWARD_THIN if thin else FORWARD_PLAIN, n, iters, ctypes.byref(ms)))
         return float(ms.value)
 
     def stamps(self, n, wgs=64):

@@ -140,38 +140,36 @@ int azh_net_create(int blocks, int filters, const float *conv_flat, const float 
                    float bn_eps, azh_net **out);
 void azh_net_destroy(azh_net *net);
 
-/* logits_out [n][833] f32 (raw policy logits, model.py:66-69), values_out [n]
- * (tanh value, model.py:71-79), for n leaf boards (mover, opponent). */
-int azh_net_forward(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, uint64_t blockers,
-                    float *logits_out, float *values_out);
-/* The same with test-time symmetry averaging, nn_evals.evaluate (nn_evals.py:48-62): the tower runs the 8
- * dihedral images of every board in one launch; logits come back through the inverse symmetry
- * (spatially) and are averaged, values are averaged. */
-int azh_net_forward_sym(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, uint64_t blockers,
-                        float *logits_out, float *values_out);
-
-/* Measurement hook: average HIP-event milliseconds per launch of the tower kernel over
- * n synthetic boards (iters launches on one stream, 3 untimed warm-up launches). */
-int azh_net_bench(azh_net *net, int dtype, int n, int iters, float *ms_out);
-/* THIN batches (a match's last games, a UAI engine's single position): the 16-bit towers with ONE board per workgroup — the
- * latency of a launch of a handful of boards is one workgroup's time for the 25 layers, and a board alone in its workgroup
- * needs 288 MFMAs per wave and layer instead of the 3-board workgroup's 720.  Same net, same boards -> the same logits and
- * values up to the summation order (the last bits of the 16-bit towers differ from the 3-board kernel's); f32 and other
- * widths run the ordinary tower.  azh_net_forward_thin / azh_net_bench_thin: azh_net_forward / azh_net_bench through that
- * kernel. */
-int azh_net_forward_thin(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, uint64_t blockers,
-                         float *logits_out, float *values_out);
-int azh_net_bench_thin(azh_net *net, int dtype, int n, int iters, float *ms_out);
-/* azh_net_forward, _thin and _sym with a wall mask PER BOARD, blockers_per_board [n] (bits beyond the 49 cells: -2): board i is
- * evaluated with the wall plane of its own mask, in the same launch as the others — what the engine's loop does under a start
- * pool (azh_engine_set_start_pool).  A board's rows are bit for bit those of the same launch with that board's mask for every
- * board.  blockers_per_board = NULL: no walls anywhere, the bytes of azh_net_forward with blockers = 0. */
-int azh_net_forward_masks(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, const uint64_t *blockers_per_board,
-                          float *logits_out, float *values_out);
-int azh_net_forward_masks_thin(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, const uint64_t *blockers_per_board,
-                               float *logits_out, float *values_out);
-int azh_net_forward_masks_sym(azh_net *net, int dtype, int n, const uint64_t *leaf_boards, const uint64_t *blockers_per_board,
-                              float *logits_out, float *values_out);
+/* The forward pass of n leaf boards (mover, opponent): logits_out [n][833] f32 (raw policy logits, model.py:66-69), values_out
+ * [n] (tanh value, model.py:71-79).  Null arguments and n < 0: -1; a mode outside the enum: -2.
+ * mode: AZH_FORWARD_PLAIN, the ordinary tower, or
+ *   AZH_FORWARD_THIN   THIN batches (a match's last games, a UAI engine's single position): the 16-bit towers with ONE board
+ *     per workgroup — the latency of a launch of a handful of boards is one workgroup's time for the 25 layers, and a board
+ *     alone in its workgroup needs 288 MFMAs per wave and layer instead of the 3-board workgroup's 720.  Same net, same boards
+ *     -> the same logits and values up to the summation order (the last bits of the 16-bit towers differ from the 3-board
+ *     kernel's); f32 and other widths run the ordinary tower.
+ *   AZH_FORWARD_SYM    test-time symmetry averaging, nn_evals.evaluate (nn_evals.py:48-62): the tower runs the 8 dihedral
+ *     images of every board in one launch; logits come back through the inverse symmetry (spatially) and are averaged,
+ *     values are averaged.
+ * Walls: `blockers` is the wall mask of every board, unless blockers_per_board [n] is given (bits beyond the 49 cells: -2, the
+ * message names the board): then board i is evaluated with the wall plane of its own mask, in the same launch as the others —
+ * what the engine's loop does under a start pool (azh_engine_set_start_pool).  A board's rows are bit for bit those of the
+ * same launch with that board's mask for every board.  blockers_per_board = NULL and blockers = 0: no walls anywhere.  Both
+ * given (a mask array and blockers != 0) is two sources for one plane: -2. */
+enum { AZH_FORWARD_PLAIN = 0, AZH_FORWARD_THIN = 1, AZH_FORWARD_SYM = 2 };
+int azh_net_forward(azh_net *net, int dtype, int mode, int n, const uint64_t *leaf_boards, uint64_t blockers,
+                    const uint64_t *blockers_per_board, float *logits_out, float *values_out);
+/* Measurement hook: average HIP-event milliseconds per launch of the tower kernel (mode: AZH_FORWARD_PLAIN or _THIN, else
+ * -2) over n synthetic boards (iters launches on one stream, 3 untimed warm-up launches). */
+int azh_net_bench(azh_net *net, int dtype, int mode, int n, int iters, float *ms_out);
+/* Which tower kernel a launch runs (host arithmetic, no GPU needed): the library's one dispatch function, asked without a
+ * launch.  stamped: azh_net_stamps; pair: the arena's two-net launch; variant1: AZH_TOWER=1; six_boards: AZH_TOWER_BOARDS=6;
+ * lds_range_ok: what azh_net_create's probe of the device found (1 where the towers were built for, and with -DAZH_OOBZERO=0).
+ * 0: *out is filled (the instantiation's name; boards, threads and dynamic LDS bytes per workgroup, workgroups per CU);
+ * -2: the launch would be refused; 1 (pair only): no pair kernel here, the two nets are launched one after the other. */
+typedef struct { char kernel[64]; int32_t boards, threads, lds_bytes, per_cu; } azh_tower_choice;
+int azh_net_tower_choice(int filters, int dtype, int thin, int stamped, int pair, int variant1, int six_boards,
+                         int lds_range_ok, azh_tower_choice *out);
 /* Diagnostic build of the bf16 tower with s_memtime stamps per layer phase: copies the
  * stamps of the first `wgs` workgroups, [wg][wave][128] u64, to out (layout: net_kernels.hip). */
 int azh_net_stamps(azh_net *net, int n, int wgs, uint64_t *out);
@@ -682,7 +680,7 @@ enum { AZH_SET_STAT_GAMES = 0, AZH_SET_STAT_X_WINS = 1, AZH_SET_STAT_O_WINS = 2,
 int azh_engine_search_set_stats(azh_engine *e, uint64_t *out /* [n][n][AZH_SET_STAT_COUNT] */);
 
 /* Which tower the device-resident loop evaluates its leaves with: 0 the 3-board workgroups (throughput), 1 one board per
- * workgroup (latency: azh_net_forward_thin's kernel), -1 (default) by the engine's size — thin for engines of at most
+ * workgroup (latency: AZH_FORWARD_THIN's kernel), -1 (default) by the engine's size — thin for engines of at most
  * AZH_THIN_MAX_GAMES game slots.  A host that knows its batch has thinned out (a match under a game limit whose last games
  * are running, uai_ringmaster.py:221-262) switches at a drain; results of the 16-bit towers differ in the last bits between
  * the two kernels, so switch at points that do not depend on timing. */

@@ -257,7 +257,7 @@ def forward_lowp(conv_weights, bn_params, features, fmt, eps=BN_EPS):
 
 
 def forward_lowp_sym(conv_weights, bn_params, features, fmt, eps=BN_EPS):
-    """sym_average around forward_lowp: the symmetry-averaged towers (azh_net_launch_sym + k_sym_reduce, whose f32 sum
+    """sym_average around forward_lowp: the symmetry-averaged towers (azh_net_launch with symmetry scratch + k_sym_reduce, whose f32 sum
     of eight logits times 0.125 is exact wherever the eight logits are exact integers of magnitude < 2^21)."""
     features = np.asarray(features, dtype=np.float64)
     return sym_average(lambda images: forward_lowp(conv_weights, bn_params, images, fmt, eps), features)

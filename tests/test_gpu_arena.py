@@ -198,7 +198,7 @@ def test_arena_device_loop_matches_oracle_at_config5_size(dtype):
     net B by the side to move: every game of every round, every state and arena word at four sync points, one of them after
     the switch.  f32: one launch per net, bit-identical wherever a board sits.  f16 — the leg's own dtype: both nets' lists in
     ONE launch of k_tower2_pair, three boards per workgroup until the switch, one board per workgroup after it; the oracle's
-    leaves go through azh_net_forward (before the switch) / azh_net_forward_thin (after it) list by list in game order, which
+    leaves go through azh_net_forward, plain (before the switch) / thin (after it), list by list in game order, which
     puts every board in the slot it has in the pair launch (each list starts at a workgroup of its own).  The match starts from
     random openings of 170 plies (uai_ringmaster.get_opening) so that games end, slots idle and the batch thins within a
     few thousand iterations instead of forty thousand."""
@@ -226,7 +226,7 @@ def test_arena_device_loop_matches_oracle_at_config5_size(dtype):
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_arena_thin_pair_kernel_matches_oracle_bit_for_bit(dtype):
     """The arena's last games as they really run: both nets' leaf lists in one launch of the one-board-per-workgroup tower
-    (k_tower2_pair<Geo2Thin>), 16-bit — pinned to the oracle with azh_net_forward_thin as its evaluator for either net (the
+    (k_tower2_pair<Geo2Thin>), 16-bit — pinned to the oracle with the thin azh_net_forward as its evaluator for either net (the
     thin kernel's result for a board does not depend on where it sits or which launch carries it).  A match that starts
     above 512 games is followed through its switch: 3-board kernel results cannot be reproduced board by board from the
     host (a 16-bit board's last bits depend on its slot in the workgroup), so the followed part begins at the switch."""

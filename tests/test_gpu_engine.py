@@ -379,7 +379,7 @@ def test_symmetry_averaging_flag_in_the_device_loop_equals_host_evaluated_search
     mk = lambda: link.Engine(link.Config(**{n: getattr(base, n) for n, _ in orc.Config._fields_}))
     dev, host = mk(), mk()
     if dtype != "f32":
-        dev.set_thin_batches(0)          # (azh_net_forward_sym runs the three-board kernel)
+        dev.set_thin_batches(0)          # (AZH_FORWARD_SYM runs the three-board kernel)
     iters = 90
     dev.run(net, iters, dt)
     dev.sync()
@@ -648,7 +648,7 @@ def test_thin_batch_switch_in_the_device_loop():
 def test_thin_batch_device_loop_in_16_bits_matches_oracle_bit_for_bit(dtype):
     """The one-board-per-workgroup tower inside the device-resident loop (engines of at most 512 slots pick it by themselves;
     arena.Match and the generator switch to it for their last games) pinned to the oracle: the thin kernel is bit-identical
-    wherever a board sits in a launch (tests/test_gpu_net.py), so an oracle whose leaves go through azh_net_forward_thin sees
+    wherever a board sits in a launch (tests/test_gpu_net.py), so an oracle whose leaves go through AZH_FORWARD_THIN sees
     exactly the loop's evaluations — states, arena words, lines, counters.  Both ways of getting there: by size (384 slots)
     and by azh_engine_set_thin_batches(1) on a larger engine."""
     dt = link.DTYPES[dtype]

@@ -229,6 +229,41 @@ def test_first_boards_of_partial_tiles_and_empty_batch():
     assert p.shape == (0, 7, 7, 17)
 
 
+def test_stamped_tower_stamps_every_workgroup_and_is_refused_for_another_width():
+    """The diagnostic instantiation (azh_net_stamps): 7 boards in tiles of 3 are three workgroups, and each leaves clock
+    values behind; a 64-filter net has no stamped kernel."""
+    net = link.Net(*model.random_init(1, 128, seed=4, perturb_bn=True))
+    stamps = net.stamps(7, wgs=3)
+    assert stamps.shape == (3, 4, 128)
+    for wg in range(3):
+        assert stamps[wg].any(), wg
+    with pytest.raises(link.AzhError):
+        link.Net(*model.random_init(1, 64, seed=4)).stamps(7, wgs=3)
+
+
+def test_refusals_of_the_forward_call_and_its_empty_batch():
+    net = link.Net(*model.random_init(1, 128, seed=4, perturb_bn=True))
+    lb = np.ascontiguousarray(sample_leaf_boards(4, 8, 0), dtype=np.uint64)
+    logits, values = np.zeros((4, 7, 7, 17), np.float32), np.zeros((4, 1), np.float32)
+    masks = np.zeros(4, np.uint64)
+
+    def call(mode, n, blockers, per_board):
+        return link.load().azh_net_forward(net.h, link.DTYPE_BF16, mode, n, lb.ctypes.data, blockers,
+                                           None if per_board is None else per_board.ctypes.data, logits.ctypes.data, values.ctypes.data)
+
+    assert call(link.FORWARD_PLAIN, 4, BLOCK4_MASK, None) == 0 and logits.any()
+    for mode in (-1, 3):
+        assert call(mode, 4, 0, None) == -2 and "mode" in link.load().azh_last_error().decode()
+    assert call(link.FORWARD_PLAIN, 4, 0, masks) == 0
+    for mode in (link.FORWARD_PLAIN, link.FORWARD_THIN, link.FORWARD_SYM):
+        assert call(mode, 4, BLOCK4_MASK, masks) == -2     # two sources for one plane
+        assert call(mode, -1, 0, None) == -1
+        assert call(mode, 0, 0, None) == 0
+    for p, v in (net.forward(lb[:0], 0, link.DTYPE_BF16), net.forward(lb[:0], 0, link.DTYPE_BF16, thin=True),
+                 net.forward_sym(lb[:0], 0, link.DTYPE_BF16)):
+        assert p.shape == (0, 7, 7, 17) and v.shape == (0, 1)
+
+
 # tolerances = 3x the error measured on this net (tools/precision_in_the_loop.py, profiles/round2_precision_in_the_loop.json:
 # max |dlogit| 6.9e-4 bf16 / 9.6e-5 f16 on logits of scale 0.1; what that does to the search is reported there)
 @pytest.mark.parametrize("dtype,tol", [(link.DTYPE_BF16, 2e-3), (link.DTYPE_F16, 3e-4)])
@@ -247,7 +282,7 @@ def test_reduced_precision_tower_tracks_f32(dtype, tol):
 
 
 def test_symmetry_averaged_forward_matches_nn_evals_restatement():
-    """azh_net_forward_sym == nn_evals.evaluate (nn_evals.py:48-62) as restated in float64; an asymmetric
+    """azh_net_forward in AZH_FORWARD_SYM mode == nn_evals.evaluate (nn_evals.py:48-62) as restated in float64; an asymmetric
     blocker mask checks that the blocker plane is transformed with the board."""
     conv, bn = model.random_init(2, 128, seed=21, perturb_bn=True)
     net = link.Net(conv, bn)
@@ -268,7 +303,7 @@ def test_symmetry_averaged_forward_matches_nn_evals_restatement():
 
 @pytest.mark.parametrize("dtype,tol", [(link.DTYPE_BF16, 2e-3), (link.DTYPE_F16, 3e-4)])
 def test_thin_tower_equals_the_three_board_tower_to_rounding_and_is_position_independent(dtype, tol):
-    """One board per workgroup (azh_net_forward_thin: the kernel for a match's last games and a UAI engine's single
+    """One board per workgroup (azh_net_forward in AZH_FORWARD_THIN mode: the kernel for a match's last games and a UAI engine's single
     position) computes model.Network's forward (model.py:38-79) for the same boards: equal to the 3-board tower within the
     16-bit towers' own rounding (another summation order), bounded against the f32 tower like it, and bit-identical
     wherever a board sits in the launch and whatever is beside it — empty batch, one board, a ragged count."""

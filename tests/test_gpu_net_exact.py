@@ -74,7 +74,7 @@ def test_batch_sizes_and_a_partial_last_workgroup(fmt):
 
 @pytest.mark.parametrize("case", ne.SYM_CASES, ids=lambda c: c[2])
 def test_symmetry_average_equals_the_emulator_bit_for_bit(case):
-    """azh_net_forward_sym: the tower on the 8 dihedral images (the asymmetric mask transformed with the board), then
+    """azh_net_forward, AZH_FORWARD_SYM: the tower on the 8 dihedral images (the asymmetric mask transformed with the board), then
     k_sym_reduce's f32 mean — exact on these logits; the value a mean of eight tanhf"""
     fmt = case[2]
     conv, bn, lb = ne.sym_net(*case)

@@ -59,19 +59,21 @@ def test_symmetry_averaged_tower_with_a_mask_per_board():
         assert (values[rows].view(np.uint32) == want_v[rows].view(np.uint32)).all(), hex(m)
 
 
-@pytest.mark.parametrize("name,thin", [("azh_net_forward_masks", False), ("azh_net_forward_masks_thin", True),
-                                       ("azh_net_forward_masks_sym", None)])
-def test_tower_without_a_mask_array_gives_the_bytes_of_the_plain_forward(name, thin):
+@pytest.mark.parametrize("mode,thin", [(link.FORWARD_PLAIN, False), (link.FORWARD_THIN, True), (link.FORWARD_SYM, None)],
+                         ids=["plain", "thin", "sym"])
+def test_tower_without_a_mask_array_gives_the_bytes_of_the_plain_forward(mode, thin):
+    """azh_net_forward in its three modes with a null mask array"""
     net = eh.net()
     boards, _ = _seven_boards()
     logits = np.zeros((7, 7, 7, 17), np.float32)
     values = np.zeros((7, 1), np.float32)
-    link.check(getattr(link.load(), name)(net.h, BF16, 7, boards.ctypes.data, None, logits.ctypes.data, values.ctypes.data))
+    link.check(link.load().azh_net_forward(net.h, BF16, mode, 7, boards.ctypes.data, 0, None, logits.ctypes.data, values.ctypes.data))
     want_l, want_v = net.forward_sym(boards, 0, BF16) if thin is None else net.forward(boards, 0, BF16, thin=thin)
     assert logits.tobytes() == want_l.tobytes() and values.tobytes() == want_v.tobytes()
     bad = np.array([0, 0, 1 << 49, 0, 0, 0, 0], dtype=np.uint64)
     with pytest.raises(link.AzhError) as err:
-        link.check(getattr(link.load(), name)(net.h, BF16, 7, boards.ctypes.data, bad.ctypes.data, logits.ctypes.data, values.ctypes.data))
+        link.check(link.load().azh_net_forward(net.h, BF16, mode, 7, boards.ctypes.data, 0, bad.ctypes.data, logits.ctypes.data,
+                                               values.ctypes.data))
     assert "board 2" in str(err.value)
 
 

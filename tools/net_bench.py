@@ -14,7 +14,7 @@ flops = model.flops_per_eval(blocks, 128)
 for dt_name in os.environ.get("DTYPES", "bf16").split(","):
     dt = link.DTYPES[dt_name]
     for n in [int(a) for a in sys.argv[1:]] or [4096, 16384]:
-        thin = bool(os.environ.get("THIN"))     # THIN=1: one board per workgroup (azh_net_bench_thin)
+        thin = bool(os.environ.get("THIN"))     # THIN=1: one board per workgroup (azh_net_bench, AZH_FORWARD_THIN)
         ms = net.bench(n, iters=10, dtype=dt, thin=thin)
         print("boards/wg=%s dtype=%s n=%d: %.3f ms/launch  %.2f M evals/s  %.1f TFLOP/s (%.1f%% of %s peak)" % (
             "1" if thin else os.environ.get("AZH_TOWER_BOARDS", "3"), dt_name, n, ms, n / ms / 1e3, n * flops / ms / 1e9,
