@@ -1,10 +1,12 @@
 """The positions the alpha-beta tests share (tests/test_alphabeta_host.py, tests/test_gpu_alphabeta.py) with the restatement's
 answers (tests/alphabeta_reference.py), computed once per process and left unchanged.  The whole set stays under some
-300 k restated nodes."""
+300 k restated nodes.  deep(): the roots of small walled regions with their answers to depth 8, read from the fixture."""
+import collections
 import random
 
 from tests import alphabeta_reference as ab
 from tests import rules_reference as rr
+from tests.helpers import load_gz
 
 START = "x5o/7/7/7/7/7/o5x x"
 WALLED_START = "x5o/7/2-1-2/7/2-1-2/7/o5x x"
@@ -57,3 +59,18 @@ def restated(name):
 
 def finished_boards():
     return [rr.Board.from_fen(f) for f in FINISHED]
+
+
+Deep = collections.namedtuple("Deep", "board family region answers pruned")
+
+
+def deep():
+    """The roots of tests/golden/alphabeta_deep.json.gz (tests/golden/gen_alphabeta_deep.py: small walled regions, on which
+    tests/alphabeta_memo.py restates depth 8) -> [Deep(board, "game" | "finished" | "forced", region name,
+    [(move, value, plain negamax nodes of the iteration)] for d = 1 .. 8, [a textbook alpha-beta's nodes] for d = 1 .. 8)]"""
+    if "deep" not in _cache:
+        data = load_gz("alphabeta_deep.json.gz")
+        _cache["deep"] = [Deep(rr.Board.from_fen(r["fen"]), r["family"], r["region"], [tuple(a) for a in r["answers"]],
+                               r["pruned"]) for r in data["roots"]]
+        assert all(d.board.masks()[2] == r["walls"] for d, r in zip(_cache["deep"], data["roots"]))
+    return _cache["deep"]

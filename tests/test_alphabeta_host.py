@@ -63,6 +63,35 @@ def test_a_budget_reports_the_last_completed_iteration():
         assert nodes == budget + 1  # the node that passed the budget is the last one counted
 
 
+HOST_NODES = 1 << 22  # the deep roots the host walks: those whose plain counts of d = 1 .. 8 sum to no more
+
+
+def host_deep_roots():
+    return [(r, [sum(a[2] for a in r.answers[:d]) for d in range(1, 9)]) for r in ac.deep()
+            if sum(a[2] for a in r.answers) <= HOST_NODES]
+
+
+def test_host_negamax_at_depth_8_on_the_deep_roots():
+    roots = host_deep_roots()
+    assert len(roots) >= 64
+    # wins and losses with five plies or more of depth left, finished roots among them (rem = 8)
+    assert {ab.WIN + rem for rem in (5, 6, 7, 8)} <= {abs(r.answers[7][1]) for r, _ in roots}
+    for r, plain in roots:
+        move, value, _ = r.answers[7]
+        # a budget of exactly the count is not passed
+        assert host(r.board, 8, max(plain[7], 256)) == (move, value, 8, plain[7]), r.board.fen()
+
+
+def test_host_budget_abandons_iterations_5_to_8():
+    roots = sorted(host_deep_roots(), key=lambda rp: rp[1][7])[-8:]
+    for r, plain in roots:
+        for d in (5, 6, 7, 8):
+            budget = (plain[d - 2] + plain[d - 1]) // 2  # iteration d - 1 completes, iteration d does not
+            assert 256 <= plain[d - 2] <= budget < plain[d - 1]
+            move, value, _ = r.answers[d - 2]
+            assert host(r.board, 8, budget) == (move, value, d - 1, budget + 1), (r.board.fen(), d)
+
+
 def test_refusals():
     x, o, blockers = rr.Board.from_fen(ac.START).masks()
     for depth, budget in ((0, 0), (9, 1 << 20), (-1, 0), (4, 0), (8, 0), (2, 255), (2, 1)):

@@ -1,7 +1,11 @@
 """The device alpha-beta search (azh_alphabeta_search) against the plain negamax of tests/alphabeta_reference.py: the move is
 the FIRST best one, the value and the reported depth are exact, the node count lies between the root's move count and the
 plain negamax count.  Shapes: one root, a wave short of / exactly / one past a workgroup row of 64, several workgroups;
-move lists past 64 and 128 entries; walls per root."""
+move lists past 64 and 128 entries; walls per root.  Depths 6 to 8 run on the deep set (small walled regions, restated by
+tests/alphabeta_memo.py and kept in tests/golden/alphabeta_deep.json.gz): every stack row, every win value 1000 .. 1008,
+budgets that abandon iterations 5 to 8, and a node count held to a textbook alpha-beta's."""
+import collections
+
 import numpy as np
 import pytest
 
@@ -165,3 +169,94 @@ def test_refusals():
         assert "error -2" in str(err.value)
     with pytest.raises(link.AzhError):
         link.alphabeta_search(packed, packed[0, 0], 1)  # walls on the x stones
+
+
+# ---------------------------------------------------------------- depths 6 to 8: the deep set
+# tests/golden/alphabeta_deep.json.gz: roots in walled regions of at most 12 cells, restated to depth 8 by
+# tests/alphabeta_memo.py (tests/test_alphabeta_memo.py holds the file to it, without a device).
+
+def deep_set():
+    if "deep" not in _cache:
+        roots = ac.deep()
+        _cache["deep"] = (roots,) + pack([r.board for r in roots])
+    return _cache["deep"]
+
+
+def deep_run(depth):
+    """the whole set in one batch, walls per root, under a budget that lets every iteration complete: the largest plain
+    negamax count of that depth, which no sound pruned search reaches"""
+    if ("deep run", depth) not in _cache:
+        roots, packed, walls = deep_set()
+        budget = max(r.answers[depth - 1][2] for r in roots)
+        assert budget > max(sum(r.pruned[:depth]) for r in roots)  # (and a textbook alpha-beta stays far below it)
+        _cache["deep run", depth] = link.alphabeta_search(packed, walls, depth, budget), budget
+    return _cache["deep run", depth]
+
+
+@pytest.mark.parametrize("depth", [6, 7, 8])
+def test_the_deep_set_at_depths_6_to_8(depth):
+    roots, packed, walls = deep_set()
+    assert len(roots) >= 64 and len(set(walls.tolist())) >= 7
+    out, _ = deep_run(depth)
+    assert (out.depth_done == depth).all()
+    # move, value and root move count <= nodes <= the plain negamax counts of d = 1 .. depth
+    check_against_restatement([r.board for r in roots], out, depth, [r.answers[:depth] for r in roots])
+    # the window goes down whole: no more nodes than a textbook alpha-beta in the same move order enters
+    textbook = np.array([sum(r.pruned[:depth]) for r in roots], dtype=np.uint64)
+    worst = int(np.argmax(out.nodes.astype(np.int64) - textbook.astype(np.int64)))
+    assert (out.nodes <= textbook).all(), (roots[worst].board.fen(), int(out.nodes[worst]), int(textbook[worst]))
+    print("depth %d: device nodes %d, textbook alpha-beta %d, plain negamax %d; win values met %s" % (
+        depth, int(out.nodes.sum()), int(textbook.sum()), sum(sum(a[2] for a in r.answers[:depth]) for r in roots),
+        sorted({int(v) for v in out.values if abs(int(v)) >= ab.WIN})))
+
+
+def test_a_budget_abandons_iterations_past_the_fourth_deep_in_the_stack():
+    """Budgets from the fixture's plain counts C_j (iterations 1 .. j summed): C_4, halfway to C_5, and C_5.  A sound pruned
+    search enters no more than C_4 nodes in its first four iterations, so each budget lets them complete and whatever is
+    abandoned is iteration 5, 6, 7 or 8, the loop standing two plies or more below the root nearly always.  (An interval
+    [C_(d-1), moves * d) that would also force iteration d to be abandoned is empty on every root: C_(d-1) is far above it.
+    That the budgets do abandon is asserted below, not assumed: a minimal alpha-beta tree of depth 8 alone has about twice
+    the leaves a plain tree of depth 4 has.)"""
+    roots, _, _ = deep_set()
+    big = [r for r in roots if r.answers[7][2] >= 1 << 20][::3]
+    assert len(big) >= 12
+    abandoned_at, roots_abandoned = collections.Counter(), 0
+    for r in big:
+        packed, walls = pack([r.board])
+        plain = np.cumsum([a[2] for a in r.answers]).tolist()
+        textbook = np.cumsum(r.pruned).tolist()
+        moves = rr.kernel_count(r.board)
+        hit = False
+        for budget in (plain[3], (plain[3] + plain[4]) // 2, plain[4]):
+            assert budget >= link.MAX_MOVES
+            out = link.alphabeta_search(packed, walls, 8, budget)
+            done, nodes = int(out.depth_done[0]), int(out.nodes[0])
+            assert 4 <= done <= 8, (r.board.fen(), budget)
+            assert (int(out.moves[0]), int(out.values[0])) == r.answers[done - 1][:2], (r.board.fen(), budget, done)
+            assert moves * done <= nodes <= budget + link.MAX_MOVES, (r.board.fen(), budget, done)
+            assert (nodes > budget) == (done < 8), (r.board.fen(), budget, done)  # abandoned: the count passed the budget
+            # the iterations a textbook alpha-beta completes inside the budget are completed
+            assert done >= max(d for d in range(1, 9) if textbook[d - 1] <= budget), (r.board.fen(), budget, done)
+            if done < 8:
+                abandoned_at[done + 1] += 1
+                hit = True
+        roots_abandoned += hit
+    print("iterations abandoned: %s; %d of %d roots" % (sorted(abandoned_at.items()), roots_abandoned, len(big)))
+    assert 2 * roots_abandoned >= len(big)
+    assert sum(abandoned_at.values()) >= len(big) and len(abandoned_at) >= 2  # at d >= 5 each, and not all at one depth
+
+
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 0])
+def test_deep_answers_do_not_depend_on_the_batch_or_the_waves_beside(n):
+    """4 roots share a workgroup, each wave on its own stack in LDS: the longest searches first, beside shorter ones"""
+    roots, packed, walls = deep_set()
+    whole, budget = deep_run(8)
+    rng = np.random.default_rng(8)
+    size = np.array([r.answers[7][2] for r in roots])
+    perm = np.concatenate([rng.permutation(np.nonzero(size >= 1 << 20)[0]), rng.permutation(np.nonzero(size < 1 << 20)[0])])
+    perm = perm[:n] if n else rng.permutation(len(roots))
+    out = link.alphabeta_search(packed[perm], walls[perm], 8, budget)
+    for i, j in enumerate(perm):
+        assert (int(out.moves[i]), int(out.values[i]), int(out.depth_done[i])) == roots[j].answers[7][:2] + (8,), roots[j].board.fen()
+    for got, ref in zip(out, whole):
+        assert (got == ref[perm]).all()

@@ -1,6 +1,7 @@
 """Teacher games from the device's alpha-beta search (azh_alphabeta_play, generate_games.py --supervised-depth): the training
 move of every traced ply is the restatement's best move, the move played is replaced exactly where the host Philox says so,
-the boards follow under the restated rules, and the generator writes lines the trainer reads."""
+the boards follow under the restated rules, and the generator writes lines the trainer reads.  Depth 2 on the whole board
+against the cell-list negamax; depths 3 and 4 on walled 12-cell regions against the memoised one (tests/alphabeta_memo.py)."""
 import json
 import os
 import subprocess
@@ -11,6 +12,7 @@ import pytest
 
 from ataxxzero_amd import link, supervised, training
 from tests import alphabeta_cases as ac
+from tests import alphabeta_memo as am
 from tests import alphabeta_reference as ab
 from tests import rules_reference as rr
 from tests.samples_fixtures import philox
@@ -43,12 +45,12 @@ def best(b):
     return _cache[key]
 
 
-def check_games(trace, thresholds, walls, first=None, sample_every=7):
+def check_games(trace, thresholds, walls, first=None, sample_every=7, best=best):
     """everything but the search: boards follow the moves played, moves are replaced where Philox says, results; the
-    training move of every `sample_every`-th (game, ply) is restated"""
+    training move of every `sample_every`-th (game, ply) is restated by `best`"""
     plies, results, boards, training_moves, played = trace
     replaced = 0
-    for g in range(GAMES):
+    for g in range(len(plies)):
         b = first[g] if first is not None else rr.Board.from_fen(ac.START)
         wall = walls[g] if np.ndim(walls) else walls
         for p in range(int(plies[g])):
@@ -108,6 +110,39 @@ def test_a_start_and_a_wall_map_per_game():
     check_games(trace, SCHEDULE, walls, first, sample_every=61)
     assert (trace[0][3::4] < 10).all() and (trace[1][3::4] != 0).all()  # the lost position (two empty squares) is soon over
     assert (trace[2][2::4, 0, 0] == packed[2, 0] & np.uint64((1 << 49) - 1)).all()  # o moves first where the start says so
+
+
+def region_start(f0, r0, w, h, turn):
+    """the four-corner start of a w x h region whose lowest cell is (file f0, rank r0), every other cell a wall"""
+    cells = [f + 7 * r for r in range(r0, r0 + h) for f in range(f0, f0 + w)]
+    corner = lambda f, r: 1 << (f0 + f + 7 * (r0 + r))  # noqa: E731
+    return rr.Board.from_masks(corner(0, 0) | corner(w - 1, h - 1), corner(w - 1, 0) | corner(0, h - 1),
+                               (1 << 49) - 1 - sum(1 << c for c in cells), turn)
+
+
+@pytest.mark.parametrize("depth", [3, 4])
+def test_teacher_games_at_depths_3_and_4_in_walled_regions(depth):
+    """16 games on 12-cell regions, four placements and so four wall words, either side first: every training move of
+    every ply against the memoised restatement at the depth played (generate_games.py recommends depth 3).  The budget is
+    beyond every position's plain count of depths 1 .. 4 (at most some 10 k there), so no iteration is abandoned."""
+    places = ((0, 0, 3, 4), (4, 3, 3, 4), (2, 2, 4, 3), (3, 0, 4, 3))
+    first = [region_start(*places[g % 4], (g // 4) % 2) for g in range(16)]
+    packed = np.array([b.packed() for b in first], dtype=np.uint64)
+    walls = [b.masks()[2] for b in first]
+    assert len(set(walls)) == 4
+    trace = link.alphabeta_play(16, SEED, 0, 0, 0, 0, depth, 1 << 20, SCHEDULE, PLIES, (packed, np.array(walls, dtype=np.uint64)))
+    seen = {}
+
+    def memo_best(b):
+        seen[b.fen()] = am.search(b, depth)
+        return seen[b.fen()][0]
+
+    check_games(trace, SCHEDULE, walls, first, sample_every=1, best=memo_best)
+    print("depth %d: %d plies, %d distinct positions, %d games ended" % (depth, trace[0].sum(), len(seen), (trace[1] != 0).sum()))
+    assert trace[0].sum() >= 64 and len(seen) >= 32 and (trace[1] != 0).any()
+    assert max(n for _, _, n in seen.values()) < 1 << 18  # the budget was never near
+    for walls_of_region in set(walls):
+        am.forget(walls_of_region)
 
 
 def run_generator(*argv):
