@@ -2902,6 +2902,17 @@ extern "C" int azh_engine_root_report(azh_engine *e, int first_game, int n_games
     return 0;
 }
 
+// The same records left in a device array of the caller's: no copy to the host (azh_samples_retarget reads them there).
+extern "C" int azh_engine_root_report_device(azh_engine *e, int first_game, int n_games, uint32_t *d_out)
+{
+    if (!e || !d_out || first_game < 0 || n_games < 1 || first_game > e->P.G - n_games)
+        return azh_fail(-1, "azh_engine_root_report_device: bad argument");
+    hipLaunchKernelGGL(k_root_report, dim3(n_games), dim3(WAVE), 0, e->stream, e->P, first_game, d_out);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
 // Decided values of the root and of its edges' children: n_games records of AZH_ROOT_PROOF_WORDS i32 (layout: the header).
 extern "C" int azh_engine_root_proofs(azh_engine *e, int first_game, int n_games, int32_t *out)
 {

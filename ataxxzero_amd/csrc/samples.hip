@@ -398,6 +398,9 @@ struct azh_samples {
     std::vector<u32> h_cum;      // [plies] while d_cum is held
     int surprise_chunk = SURPRISE_CHUNK;
     float surprise_ms[2] = {0.f, 0.f};
+    // reanalysis: scratch of azh_samples_read_plies and azh_samples_retarget, null until one of them is called
+    DeviceArray<unsigned char> d_scratch;
+    size_t scratch_bytes = 0;
     // the host mirror: what a draw is validated against
     std::vector<uint32_t> h_games;  // [games][4]
     std::vector<uint8_t> h_flags;   // [plies]
@@ -469,6 +472,7 @@ extern "C" void azh_samples_destroy(azh_samples *s)
     s->d_cum.release();
     s->d_kl.release();
     s->d_illegal.release();
+    s->d_scratch.release();
     if (s->stream)
         (void)hipStreamDestroy(s->stream);
     delete s;
@@ -1397,5 +1401,453 @@ extern "C" int azh_samples_ply_cum(const azh_samples *s, uint16_t *candidates, u
         for (int64_t g = 0; g < s->games; g++)
             default_cum(s, g, cum);
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------- reanalysis of stored plies (include/ataxxzero_hip.h)
+
+namespace {
+
+constexpr int REPORT_WORDS = AZH_ROOT_REPORT_WORDS;
+constexpr int SCAN_BLOCK = 256;
+
+// One edge of a root report.  Records are AZH_ROOT_REPORT_WORDS words apart, so an edge is aligned to its words only: the
+// 16-byte load is one that needs no more (global memory takes a dwordx4 load at any word address).
+struct ReportEdge {
+    u32 move, visits, w, prior;
+};
+
+// The definition's move test: a clone, or a jump over a distance of exactly two, between two of the 49 cells.
+__host__ __device__ inline bool report_move(u32 mv)
+{
+    if (mv > 0xFFFFu)
+        return false;
+    const int from = (int)(mv & 0xFFu), to = (int)(mv >> 8);
+    if (from >= 49 || to >= 49)
+        return false;
+    int dx = to % 7 - from % 7, dy = to / 7 - from / 7;
+    dx = dx < 0 ? -dx : dx;
+    dy = dy < 0 ? -dy : dy;
+    return from == to || (dx > dy ? dx : dy) == 2;
+}
+
+__host__ __device__ inline double report_value(float w, u32 visits)
+{
+    const float q = w / (float)visits;  // (one IEEE division on both sides: no fast-math, no contraction)
+    return (f2u(q) & 0x7F800000u) != 0x7F800000u ? 2.0 * (double)q - 1.0 : 0.0;
+}
+
+// The edges j = lane + 64 k, k < 4, of a record in this lane's registers; zero beyond M.
+struct LaneEdges {
+    ReportEdge e[4];
+};
+__device__ __forceinline__ LaneEdges load_edges(const u32 *rec, int M, int lane)
+{
+    LaneEdges L;
+    const ReportEdge *edges = reinterpret_cast<const ReportEdge *>(rec + 4);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int j = lane + 64 * k;
+        L.e[k] = j < M ? edges[j] : ReportEdge{0u, 0u, 0u, 0u};
+    }
+    return L;
+}
+
+// Phase 1: record i -> counts[i] = its new targets (0: unchanged), bad[i] = 1 for a malformed record.
+__global__ __launch_bounds__(WAVE) void k_retarget_count(const u32 *__restrict__ reports, int n, u32 *__restrict__ counts,
+                                                         u32 *__restrict__ bad)
+{
+    const int i = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (i >= n)
+        return;
+    const u32 *rec = reports + (size_t)i * REPORT_WORDS;
+    const u32 M = rec[1], finished = rec[3];
+    bool malformed = M > (u32)AZH_MAX_MOVES;
+    u32 count = 0;
+    if (!malformed) {  // (wave-uniform)
+        const LaneEdges L = load_edges(rec, (int)M, lane);
+        bool wrong = false;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool visited = L.e[k].visits > 0u;
+            wrong = wrong || (visited && !report_move(L.e[k].move));
+            count += (u32)__popcll(__ballot(visited));
+        }
+        malformed = __ballot(wrong) != 0ULL;
+    }
+    if (lane == 0) {
+        counts[i] = malformed || finished ? 0u : count;
+        bad[i] = malformed ? 1u : 0u;
+    }
+}
+
+__device__ __forceinline__ u64 block_sum_u64(u64 v, u64 *lds)  // SCAN_BLOCK threads; the sum in every thread
+{
+    const int t = (int)threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (int step = SCAN_BLOCK / 2; step > 0; step >>= 1) {
+        if (t < step)
+            lds[t] += lds[t + step];
+        __syncthreads();
+    }
+    const u64 out = lds[0];
+    __syncthreads();
+    return out;
+}
+
+// The scan's first pass: sums[2 b] = the counts of block b's SCAN_BLOCK records, sums[2 b + 1] = its malformed records.
+__global__ __launch_bounds__(SCAN_BLOCK) void k_retarget_block_sums(const u32 *__restrict__ counts, const u32 *__restrict__ bad,
+                                                                    int n, u64 *__restrict__ sums)
+{
+    __shared__ u64 lds[SCAN_BLOCK];
+    const int i = (int)(blockIdx.x * SCAN_BLOCK + threadIdx.x);
+    const u64 c = block_sum_u64(i < n ? counts[i] : 0u, lds);
+    const u64 b = block_sum_u64(i < n ? bad[i] : 0u, lds);
+    if (threadIdx.x == 0) {
+        sums[2 * blockIdx.x] = c;
+        sums[2 * blockIdx.x + 1] = b;
+    }
+}
+
+// The second: offsets[i] = the counts of the records before i (exclusive, call order); the last block leaves the total and
+// the number of malformed records in totals[0 .. 1].
+__global__ __launch_bounds__(SCAN_BLOCK) void k_retarget_scan(const u32 *__restrict__ counts, int n, const u64 *__restrict__ sums,
+                                                              u32 *__restrict__ offsets, u64 *__restrict__ totals)
+{
+    __shared__ u64 lds[SCAN_BLOCK];
+    __shared__ u32 wave_total[SCAN_BLOCK / WAVE];
+    const int t = (int)threadIdx.x, b = (int)blockIdx.x, i = b * SCAN_BLOCK + t;
+    u64 before = 0, malformed = 0;
+    for (int k = t; k < b; k += SCAN_BLOCK)
+        before += sums[2 * k];
+    before = block_sum_u64(before, lds);
+    const u32 mine = i < n ? counts[i] : 0u;
+    const u32 incl = (u32)wave_incl_scan((int)mine);
+    if ((t & 63) == 63)
+        wave_total[t >> 6] = incl;
+    __syncthreads();
+    u32 waves_before = 0;
+    for (int w = 0; w < (t >> 6); w++)
+        waves_before += wave_total[w];
+    if (i < n)
+        offsets[i] = (u32)before + waves_before + incl - mine;
+    if (b == (int)gridDim.x - 1) {  // (block-uniform)
+        for (int k = t; k < (int)gridDim.x; k += SCAN_BLOCK)
+            malformed += sums[2 * k + 1];
+        malformed = block_sum_u64(malformed, lds);
+        if (t == 0) {
+            totals[0] = before + sums[2 * b];
+            totals[1] = malformed;
+        }
+    }
+}
+
+// The sum of one u64 per lane whose value is below 2^48, exactly: three 16-bit columns, each below 2^22 over the wave.
+__device__ __forceinline__ u64 wave_sum_u48(u64 v)
+{
+    const u64 a = wave_sum_u32((u32)(v & 0xFFFFu)), b = wave_sum_u32((u32)((v >> 16) & 0xFFFFu)),
+              c = wave_sum_u32((u32)((v >> 32) & 0xFFFFu));
+    return a + (b << 16) + (c << 32);
+}
+
+// Phase 2: record i -> ply ply_at[i]: the visited edges compacted in edge order behind base + offsets[i], the value, and the
+// ply's two target words.  Phase 1 has found every record well formed and the host has found the room.
+__global__ __launch_bounds__(WAVE) void k_retarget_write(const u32 *__restrict__ reports, int n, const u32 *__restrict__ ply_at,
+                                                         const u32 *__restrict__ offsets, u32 base, Ply *__restrict__ plies,
+                                                         u16 *__restrict__ target_index, float *__restrict__ target_weight,
+                                                         int *__restrict__ status)
+{
+    const int i = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (i >= n)
+        return;
+    const u32 *rec = reports + (size_t)i * REPORT_WORDS;
+    const int M = (int)min(rec[1], (u32)AZH_MAX_MOVES);
+    const LaneEdges L = load_edges(rec, M, lane);
+    u64 part = 0, key = 0;
+    u32 best_w = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        part += L.e[k].visits;
+        const u64 kj = ((u64)L.e[k].visits << 32) | (u64)(0xFFFFFFFFu - (u32)(lane + 64 * k));  // most visits, first on a tie
+        if (kj > key) {
+            key = kj;
+            best_w = L.e[k].w;
+        }
+    }
+    const u64 total = wave_sum_u48(part);
+    const bool changed = total != 0ULL && rec[3] == 0u;  // (wave-uniform)
+    if (changed) {
+        key = wave_max_u64(key);
+        const int bj = (int)(0xFFFFFFFFu - (u32)key);
+        const u32 w_bits = (u32)read_lane((int)best_w, bj & 63);
+        const u32 first = base + offsets[i];
+        u32 at = first;
+        const u64 below = (1ULL << lane) - 1ULL;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool visited = L.e[k].visits > 0u;
+            const u64 mask = __ballot(visited);
+            if (visited) {
+                const u32 to = at + (u32)__popcll(mask & below);
+                target_index[to] = (u16)policy_index(L.e[k].move);
+                target_weight[to] = (float)((double)L.e[k].visits / (double)total);
+            }
+            at += (u32)__popcll(mask);
+        }
+        if (lane == 0) {
+            Ply *ply = plies + ply_at[i];
+            ply->value = report_value(u2f(w_bits), (u32)(key >> 32));
+            ply->first_target = first;
+            ply->targets_flags = (at - first) << 8 | (ply->targets_flags & 0xFFu);
+        }
+    }
+    if (lane == 0)
+        status[i] = changed ? 1 : 0;
+}
+
+// azh_samples_read_plies: ply ply_at[i] as it is stored.  (k_samples_pack_boards serves a run of consecutive plies in the
+// tower's (mover, opponent) order; a scattered list in (x, o) order with the value and the target words is another kernel, not
+// a branch in that one.)
+__global__ __launch_bounds__(256) void k_samples_read_plies(View v, int n, const u32 *__restrict__ ply_at, Ply *__restrict__ out)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n)
+        out[i] = v.plies[ply_at[i]];
+}
+
+// One wave per ply: its targets, in stored order, to start[i] of the packed arrays.
+__global__ __launch_bounds__(WAVE) void k_samples_read_targets(View v, int n, const u32 *__restrict__ ply_at,
+                                                               const u32 *__restrict__ start, u16 *__restrict__ index,
+                                                               float *__restrict__ weight)
+{
+    const int i = (int)blockIdx.x;
+    if (i >= n)
+        return;
+    const Ply ply = v.plies[ply_at[i]];
+    const u32 count = ply.targets_flags >> 8;
+    for (u32 t = threadIdx.x; t < count; t += WAVE) {
+        index[start[i] + t] = v.target_index[ply.first_target + t];
+        weight[start[i] + t] = v.target_weight[ply.first_target + t];
+    }
+}
+
+size_t round_up(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+}  // namespace
+
+// Device scratch of the two calls below, kept from call to call and grown on demand.
+static int reserve_scratch(azh_samples *s, size_t bytes)
+{
+    if (bytes <= s->scratch_bytes)
+        return 0;
+    s->d_scratch.release();
+    s->scratch_bytes = 0;
+    if (int rc = s->d_scratch.alloc(bytes))
+        return rc;
+    s->scratch_bytes = bytes;
+    return 0;
+}
+
+// (game, ply) pairs -> the plies' places in the store, from the mirror: -1 for a pair outside it.
+static int ply_places(const azh_samples *s, const char *what, int n, const int32_t *plies, std::vector<u32> &at)
+{
+    at.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int64_t g = plies[2 * i], p = plies[2 * i + 1];
+        if (g < 0 || g >= s->games || p < 0 || p >= (int64_t)s->h_games[4 * g + 1])
+            return azh_fail(-1, "%s: pair %d (game %lld, ply %lld) is outside the store", what, i, (long long)g, (long long)p);
+        at[(size_t)i] = s->h_games[4 * g] + (u32)p;
+    }
+    return 0;
+}
+
+// The plies at `at` as the device holds them -> got; waits for the store's stream.
+static int fetch_plies(azh_samples *s, const std::vector<u32> &at, std::vector<Ply> &got)
+{
+    const size_t N = at.size(), at_bytes = round_up(N * sizeof(u32)), ply_bytes = round_up(N * sizeof(Ply));
+    if (int rc = reserve_scratch(s, at_bytes + ply_bytes))
+        return rc;
+    u32 *d_at = reinterpret_cast<u32 *>(s->d_scratch.d);
+    Ply *d_out = reinterpret_cast<Ply *>(s->d_scratch.d + at_bytes);
+    got.resize(N);
+    AZH_HIP(hipMemcpyAsync(d_at, at.data(), N * sizeof(u32), hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(k_samples_read_plies, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, s->view(), (int)N, d_at,
+                       d_out);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipMemcpyAsync(got.data(), d_out, N * sizeof(Ply), hipMemcpyDeviceToHost, s->stream));
+    AZH_HIP(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+extern "C" int azh_samples_ply_targets(azh_samples *s, int n, const int32_t *plies, uint32_t *out)
+{
+    if (!s || !plies || !out || n < 1)
+        return azh_fail(-1, "azh_samples_ply_targets: bad argument");
+    std::vector<u32> at;
+    if (int rc = ply_places(s, "azh_samples_ply_targets", n, plies, at))
+        return rc;
+    std::vector<Ply> got;
+    if (int rc = fetch_plies(s, at, got))
+        return rc;
+    for (size_t i = 0; i < got.size(); i++) {
+        out[2 * i] = got[i].first_target;
+        out[2 * i + 1] = got[i].targets_flags >> 8;
+    }
+    return 0;
+}
+
+extern "C" int azh_samples_read_plies(azh_samples *s, int n, const int32_t *plies, uint64_t *boards_out, double *values_out,
+                                      uint8_t *flags_out, int32_t *target_start_out, uint16_t *index_out, float *weight_out,
+                                      int64_t cap_targets)
+{
+    if (!s || !plies || !boards_out || !values_out || !flags_out || !target_start_out || n < 1 ||
+        (index_out != nullptr) != (weight_out != nullptr))
+        return azh_fail(-1, "azh_samples_read_plies: bad argument (n >= 1; index_out and weight_out go together)");
+    std::vector<u32> at;
+    if (int rc = ply_places(s, "azh_samples_read_plies", n, plies, at))
+        return rc;
+    std::vector<Ply> got;
+    if (int rc = fetch_plies(s, at, got))
+        return rc;
+    const size_t N = (size_t)n, at_bytes = round_up(N * sizeof(u32));
+    std::vector<u32> start(N + 1, 0u);
+    int64_t total = 0;
+    target_start_out[0] = 0;
+    for (size_t i = 0; i < N; i++) {
+        boards_out[2 * i] = got[i].x;
+        boards_out[2 * i + 1] = got[i].o;
+        values_out[i] = got[i].value;
+        flags_out[i] = (uint8_t)(got[i].targets_flags & (AZH_SAMPLES_PLY_PASS | AZH_SAMPLES_PLY_FULL | AZH_SAMPLES_PLY_BAD));
+        total += got[i].targets_flags >> 8;
+        if (total > 0x7FFFFFFF)
+            return azh_fail(-6, "azh_samples_read_plies: the plies hold more than 2^31 - 1 targets");
+        start[i + 1] = (u32)total;
+        target_start_out[i + 1] = (int32_t)total;
+    }
+    if (!index_out || total == 0)
+        return 0;
+    if (total > cap_targets)
+        return azh_fail(-6, "azh_samples_read_plies: the plies hold %lld targets, the arrays %lld", (long long)total,
+                        (long long)cap_targets);
+    const size_t T = (size_t)total, start_bytes = round_up((N + 1) * sizeof(u32)), weight_bytes = round_up(T * sizeof(float));
+    if (int rc = reserve_scratch(s, at_bytes + start_bytes + weight_bytes + round_up(T * sizeof(u16))))
+        return rc;
+    u32 *d_at = reinterpret_cast<u32 *>(s->d_scratch.d);
+    u32 *d_start = reinterpret_cast<u32 *>(s->d_scratch.d + at_bytes);
+    float *d_weight = reinterpret_cast<float *>(s->d_scratch.d + at_bytes + start_bytes);
+    u16 *d_index = reinterpret_cast<u16 *>(s->d_scratch.d + at_bytes + start_bytes + weight_bytes);
+    AZH_HIP(hipMemcpyAsync(d_at, at.data(), N * sizeof(u32), hipMemcpyHostToDevice, s->stream));
+    AZH_HIP(hipMemcpyAsync(d_start, start.data(), (N + 1) * sizeof(u32), hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(k_samples_read_targets, dim3((unsigned)n), dim3(WAVE), 0, s->stream, s->view(), n, d_at, d_start, d_index,
+                       d_weight);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipMemcpyAsync(index_out, d_index, T * sizeof(u16), hipMemcpyDeviceToHost, s->stream));
+    AZH_HIP(hipMemcpyAsync(weight_out, d_weight, T * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    AZH_HIP(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+extern "C" int azh_samples_retarget_host(const uint32_t *report, uint16_t *index_out, float *weight_out, int32_t *n_out,
+                                         double *value_out)
+{
+    if (!report || !index_out || !weight_out || !n_out || !value_out)
+        return azh_fail(-1, "azh_samples_retarget_host: null argument");
+    *n_out = 0;
+    *value_out = 0.0;
+    const uint32_t M = report[1];
+    if (M > (uint32_t)AZH_MAX_MOVES)
+        return azh_fail(-2, "azh_samples_retarget_host: a root of %u edges", (unsigned)M);
+    uint64_t total = 0;
+    uint32_t best = 0, best_visits = 0;
+    for (uint32_t j = 0; j < M; j++) {
+        const uint32_t *e = report + 4 + 4 * j;
+        if (e[1] > 0u && !report_move(e[0]))
+            return azh_fail(-2, "azh_samples_retarget_host: edge %u: move %#x is no clone and no jump", (unsigned)j, (unsigned)e[0]);
+        total += e[1];
+        if (e[1] > best_visits) {  // (the first in edge order on a tie)
+            best_visits = e[1];
+            best = j;
+        }
+    }
+    if (total == 0 || report[3] != 0u)
+        return 0;
+    int32_t n = 0;
+    for (uint32_t j = 0; j < M; j++) {
+        const uint32_t *e = report + 4 + 4 * j;
+        if (e[1] > 0u) {
+            index_out[n] = (uint16_t)policy_index(e[0]);
+            weight_out[n] = (float)((double)e[1] / (double)total);
+            n++;
+        }
+    }
+    *n_out = n;
+    *value_out = report_value(u2f(report[6 + 4 * best]), best_visits);
+    return 0;
+}
+
+extern "C" int azh_samples_retarget(azh_samples *s, int n, const int32_t *plies, const uint32_t *d_reports,
+                                    uint64_t report_blockers, int32_t *status_out, uintptr_t stream)
+{
+    if (!s || !plies || !d_reports || !status_out || n < 1)
+        return azh_fail(-1, "azh_samples_retarget: bad argument");
+    // everything the mirror can tell is checked first: a refused call launches nothing
+    std::vector<u32> at;
+    if (int rc = ply_places(s, "azh_samples_retarget", n, plies, at))
+        return rc;
+    for (int i = 0; i < n; i++) {
+        const int64_t g = plies[2 * i];
+        const uint8_t f = s->h_flags[at[(size_t)i]];
+        if (f & AZH_SAMPLES_PLY_PASS)
+            return azh_fail(-1, "azh_samples_retarget: pair %d (game %lld, ply %d) is a pass", i, (long long)g, plies[2 * i + 1]);
+        if ((s->h_games[4 * g + 2] & GAME_HAS_FULL) && !(f & AZH_SAMPLES_PLY_FULL))
+            return azh_fail(-1, "azh_samples_retarget: pair %d (game %lld, ply %d) is not among its game's candidates", i,
+                            (long long)g, plies[2 * i + 1]);
+        if (f & AZH_SAMPLES_PLY_BAD)
+            return azh_fail(-2, "azh_samples_retarget: pair %d (game %lld, ply %d): policy target does not sum to one", i,
+                            (long long)g, plies[2 * i + 1]);
+        if (s->h_blockers[(size_t)g] != report_blockers)
+            return azh_fail(-2, "azh_samples_retarget: pair %d: game %lld is stored with walls %#llx, the reports were searched "
+                                "on %#llx", i, (long long)g, (unsigned long long)s->h_blockers[(size_t)g],
+                            (unsigned long long)report_blockers);
+    }
+    {
+        std::vector<u32> sorted(at);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return azh_fail(-1, "azh_samples_retarget: a pair is given twice");
+    }
+    const size_t N = (size_t)n, blocks = (N + SCAN_BLOCK - 1) / SCAN_BLOCK;
+    const size_t sums_bytes = round_up((2 * blocks + 2) * sizeof(u64)), row_bytes = round_up(N * sizeof(u32));
+    if (int rc = reserve_scratch(s, sums_bytes + 5 * row_bytes))
+        return rc;
+    u64 *d_sums = reinterpret_cast<u64 *>(s->d_scratch.d), *d_totals = d_sums + 2 * blocks;
+    u32 *d_at = reinterpret_cast<u32 *>(s->d_scratch.d + sums_bytes);
+    u32 *d_counts = d_at + row_bytes / 4, *d_bad = d_counts + row_bytes / 4, *d_offsets = d_bad + row_bytes / 4;
+    int *d_status = reinterpret_cast<int *>(d_offsets + row_bytes / 4);
+    AZH_HIP(hipStreamSynchronize(s->stream));
+    if (stream)
+        AZH_HIP(hipStreamSynchronize((hipStream_t)stream));
+    hipStream_t st = s->stream;
+    AZH_HIP(hipMemcpyAsync(d_at, at.data(), N * sizeof(u32), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_retarget_count, dim3((unsigned)n), dim3(WAVE), 0, st, d_reports, n, d_counts, d_bad);
+    hipLaunchKernelGGL(k_retarget_block_sums, dim3((unsigned)blocks), dim3(SCAN_BLOCK), 0, st, d_counts, d_bad, n, d_sums);
+    hipLaunchKernelGGL(k_retarget_scan, dim3((unsigned)blocks), dim3(SCAN_BLOCK), 0, st, d_counts, n, d_sums, d_offsets, d_totals);
+    AZH_HIP(hipGetLastError());
+    u64 totals[2] = {0, 0};
+    AZH_HIP(hipMemcpyAsync(totals, d_totals, sizeof(totals), hipMemcpyDeviceToHost, st));
+    AZH_HIP(hipStreamSynchronize(st));
+    if (totals[1])
+        return azh_fail(-2, "azh_samples_retarget: %llu of the %d records are malformed (more than %d edges, or a visited "
+                            "move that is no clone and no jump)", (unsigned long long)totals[1], n, AZH_MAX_MOVES);
+    if ((u64)s->targets + totals[0] > (u64)s->cap_targets)
+        return azh_fail(-6, "azh_samples_retarget: %llu new targets do not fit beside %lld in a capacity of %lld",
+                        (unsigned long long)totals[0], (long long)s->targets, (long long)s->cap_targets);
+    hipLaunchKernelGGL(k_retarget_write, dim3((unsigned)n), dim3(WAVE), 0, st, d_reports, n, d_at, d_offsets, (u32)s->targets,
+                       s->d_plies.d, s->d_target_index.d, s->d_target_weight.d, d_status);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipMemcpyAsync(status_out, d_status, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AZH_HIP(hipStreamSynchronize(st));
+    s->targets += (int64_t)totals[0];
     return 0;
 }

@@ -180,6 +180,7 @@ SIGNATURES = {
     "azh_engine_root_proofs": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
     "azh_engine_play_moves": (ctypes.c_int, [_vp, _vp, _vp]),
     "azh_engine_root_report": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
+    "azh_engine_root_report_device": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp]),
     "azh_engine_game_state": (ctypes.c_int, [_vp, ctypes.c_int, _P(GameState)]),
     "azh_engine_tree": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "azh_engine_tree_raw": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
@@ -230,6 +231,10 @@ SIGNATURES = {
     "azh_samples_final_owners": (ctypes.c_int, [_u64, _u64, _u64, ctypes.c_int, ctypes.c_uint32, _vp, _P(_i32)]),
     "azh_samples_check_owners": (ctypes.c_int, [_u64, _u64, _u64, ctypes.c_uint32]),
     "azh_samples_game_owners": (ctypes.c_int, [_vp, _vp]),
+    "azh_samples_read_plies": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64]),
+    "azh_samples_ply_targets": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
+    "azh_samples_retarget": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _u64, _vp, ctypes.c_size_t]),
+    "azh_samples_retarget_host": (ctypes.c_int, [_vp, _vp, _vp, _P(_i32), _P(ctypes.c_double)]),
     # the reference's ABI, link.py:8-32
     "launch_threads": (None, [ctypes.c_char_p, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int]),
     "get_workload": (ctypes.c_int, []),
@@ -1001,6 +1006,17 @@ class Engine:
         check(load().azh_engine_root_report(self.h, int(first), int(n), _ptr(out)))
         return [RootReport(out[i]) for i in range(n)]
 
+    def root_report_device(self, out, first=0, n=None):
+        """The same records written into `out`, a contiguous int32 GPU tensor with room for n rows of ROOT_REPORT_WORDS (uint32
+        words; torch has no such dtype), by the same kernel: nothing is copied to the host, and the call returns when the
+        kernel has completed (azh_engine_root_report_device).  What SampleStore.retarget reads."""
+        import torch
+        n = self.G - first if n is None else n
+        if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n * ROOT_REPORT_WORDS):
+            raise ValueError("out must be a contiguous int32 GPU tensor of at least n * ROOT_REPORT_WORDS words")
+        check(load().azh_engine_root_report_device(self.h, int(first), int(n), ctypes.c_void_p(out.data_ptr())))
+        return out
+
     def game_state(self, g):
         s = GameState()
         check(load().azh_engine_game_state(self.h, g, ctypes.byref(s)))
@@ -1322,6 +1338,19 @@ def samples_surprise_host(logits, legal_index, target_index, target_weight):
     return np.float32(kl.value), int(illegal.value)
 
 
+def retarget_host(report):
+    """One root report record (ROOT_REPORT_WORDS uint32) -> (index (n,) u16, weight (n,) f32, value): the policy target and
+    the value a reanalysed ply takes from it, n == 0 (value 0.0) for a record that leaves its ply as it was; AzhError (-2) for
+    a malformed record (azh_samples_retarget_host; host arithmetic, no GPU needed)."""
+    report = np.ascontiguousarray(report, dtype=np.uint32).ravel()
+    if report.size != ROOT_REPORT_WORDS:
+        raise ValueError("a record has %d words" % ROOT_REPORT_WORDS)
+    index, weight = np.zeros(MAX_MOVES, dtype=np.uint16), np.zeros(MAX_MOVES, dtype=np.float32)
+    n, value = ctypes.c_int32(0), ctypes.c_double(0.0)
+    check(load().azh_samples_retarget_host(_ptr(report), _ptr(index), _ptr(weight), ctypes.byref(n), ctypes.byref(value)))
+    return index[:n.value].copy(), weight[:n.value].copy(), float(value.value)
+
+
 def hip_runtimes():
     """The HIP runtime libraries mapped into this process (paths).  torch ships its own: imported BEFORE this package's
     library is loaded, both resolve to that one copy (same soname) and share streams and memory; loaded after it, the
@@ -1546,3 +1575,47 @@ class SampleStore:
         n = ctypes.c_int64(0)
         check(load().azh_samples_status(self.h, ctypes.byref(n)))
         return int(n.value)
+
+    # reanalysis of stored plies ("Reanalysis of stored plies")
+
+    def read_plies(self, plies, targets=True):
+        """The stored plies (n, 2) of (game, ply) read back from the device -> (boards (n, 2) u64 of (x, o), values (n,) f64,
+        flags (n,) u8, target_start (n + 1,) i32, index u16, weight f32): what the store holds now, the targets in stored
+        order; targets=False: index and weight are None (azh_samples_read_plies)."""
+        plies = np.ascontiguousarray(plies, dtype=np.int32).reshape(-1, 2)
+        n = len(plies)
+        boards, values = np.zeros((n, 2), dtype=np.uint64), np.zeros(n, dtype=np.float64)
+        flags, start = np.zeros(n, dtype=np.uint8), np.zeros(n + 1, dtype=np.int32)
+        lib = load()
+        check(lib.azh_samples_read_plies(self.h, n, _ptr(plies), _ptr(boards), _ptr(values), _ptr(flags), _ptr(start), None,
+                                         None, 0))
+        if not targets:
+            return boards, values, flags, start, None, None
+        total = int(start[n])
+        index, weight = np.zeros(max(total, 1), dtype=np.uint16), np.zeros(max(total, 1), dtype=np.float32)
+        check(lib.azh_samples_read_plies(self.h, n, _ptr(plies), _ptr(boards), _ptr(values), _ptr(flags), _ptr(start),
+                                         _ptr(index), _ptr(weight), total))
+        return boards, values, flags, start, index[:total], weight[:total]
+
+    def ply_targets(self, plies):
+        """Diagnostic -> (n, 2) u32 of (first target, targets): where the targets of the plies (n, 2) of (game, ply) lie in the
+        store (azh_samples_ply_targets)."""
+        plies = np.ascontiguousarray(plies, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros((len(plies), 2), dtype=np.uint32)
+        check(load().azh_samples_ply_targets(self.h, len(plies), _ptr(plies), _ptr(out)))
+        return out
+
+    def retarget(self, plies, reports, blockers=0):
+        """The plies (n, 2) of (game, ply) take the first n records of `reports`, an int32 GPU tensor of root reports
+        (Engine.root_report_device) searched on the walls `blockers`, as their policy target and value -> status (n,) int32:
+        1 changed, 0 left as it was.  A refused call changes nothing (azh_samples_retarget)."""
+        import torch
+        plies = np.ascontiguousarray(plies, dtype=np.int32).reshape(-1, 2)
+        n = len(plies)
+        if not (reports.is_cuda and reports.dtype == torch.int32 and reports.is_contiguous() and
+                reports.numel() >= n * ROOT_REPORT_WORDS):
+            raise ValueError("reports must be a contiguous int32 GPU tensor of at least n * ROOT_REPORT_WORDS words")
+        status = np.zeros(n, dtype=np.int32)
+        check(load().azh_samples_retarget(self.h, n, _ptr(plies), ctypes.c_void_p(reports.data_ptr()), int(blockers),
+                                          _ptr(status), torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY))
+        return status

@@ -459,11 +459,24 @@ def make_minibatch_device(store, first_game, n_games, size, value_blend=0.0, out
     return store.gather(np.asarray(rows, dtype=np.int32), value_blend, out=out, aux=aux)
 
 
-def _fill_store(entries, log, aux=False):
+def _fill_store(entries, log, aux=False, reanalyse_fraction=0.0, n_test=10):
+    """reanalyse_fraction F > 0: the store gets round(F * C) * MAX_MOVES targets of head-room, C the candidate plies of the
+    training games [n_test, n) that are no passes (reanalysed targets are appended: SampleStore.retarget)."""
     from . import link
     link.require_gpu()
     arrays = link.entries_to_arrays(entries, aux=aux)
-    store = link.SampleStore(max(len(arrays.games), 1), max(len(arrays.ply_flags), 1), max(len(arrays.target_index), 1))
+    spare = 0
+    if reanalyse_fraction > 0.0:
+        c = 0
+        for first, plies, word, _ in arrays.games[n_test:].tolist():
+            f = arrays.ply_flags[first:first + plies]
+            cand = (f & link.SAMPLES_PLY_FULL) != 0 if word & link.SAMPLES_GAME_HAS_FULL else np.ones(plies, dtype=bool)
+            c += int((cand & ((f & link.SAMPLES_PLY_PASS) == 0)).sum())
+        spare = round(reanalyse_fraction * c) * link.MAX_MOVES
+        if len(arrays.target_index) + spare >= 1 << 31:
+            raise ValueError("--reanalyse-fraction %g of %d plies asks for %d targets of head-room: a store holds fewer than 2^31"
+                             % (reanalyse_fraction, c, spare))
+    store = link.SampleStore(max(len(arrays.games), 1), max(len(arrays.ply_flags), 1), max(len(arrays.target_index) + spare, 1))
     store.add_arrays(arrays)
     c = store.counts()
     masks = store.game_blockers()
@@ -518,6 +531,155 @@ def _apply_surprise(store, old_path, lam, dtype, n_test, log):
         "one ply holds of its game: %.3f; %i targets that are no legal moves."
         % (count, len(kl), seconds, old_path, dtype, float(k.mean()), float(np.median(k)), float(k.max()), share, illegal))
     store.set_ply_weights(n_test, count, w)
+
+
+# ---------------------------------------------------------------- reanalysis of stored plies
+
+REANALYSE_SEED = 246813579            # train.py --reanalyse-fraction: the seed of the plan's own random.Random
+
+
+def reanalyse_plan(games, ply_flags, candidates, candidate_count, blockers, first_game, n_games, fraction, slots, seed):
+    """Which stored plies are searched again, and in which rounds -> [(wall mask, plies (n, 2) int32 of (game, ply))], n <= slots.
+    From the store's mirrors (SampleStore.mirror, ply_cum, game_blockers), pure Python.  C = the candidate plies of the games
+    [first_game, first_game + n_games) that are neither passes nor BAD; round(fraction * C) of them are picked without
+    replacement with a random.Random(seed) of the plan's own — the global `random` is not touched, so the minibatch draws of a run
+    do not move — sorted by (wall mask, game, ply) and cut into rounds of at most `slots` plies that never span two masks."""
+    from . import link
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError("the reanalysed fraction must lie in [0, 1]")
+    if slots < 1:
+        raise ValueError("a round needs at least one slot")
+    if not (0 <= first_game and 0 <= n_games and first_game + n_games <= len(games)):
+        raise ValueError("games [%d, %d) of %d" % (first_game, first_game + n_games, len(games)))
+    skip = link.SAMPLES_PLY_PASS | link.SAMPLES_PLY_BAD
+    eligible = []
+    for g in range(first_game, first_game + n_games):
+        first = int(games[g][0])
+        for k in range(int(candidate_count[g])):
+            p = int(candidates[first + k])
+            if not int(ply_flags[first + p]) & skip:
+                eligible.append((int(blockers[g]), g, p))
+    picked = sorted(random.Random(seed).sample(eligible, round(fraction * len(eligible))))
+    rounds = []
+    for mask, g, p in picked:
+        if not rounds or rounds[-1][0] != mask or len(rounds[-1][1]) >= slots:
+            rounds.append((mask, []))
+        rounds[-1][1].append((g, p))
+    return [(mask, np.asarray(rows, dtype=np.int32).reshape(-1, 2)) for mask, rows in rounds]
+
+
+def reanalysis_config(slots, visits, mask, max_plies, seed=REANALYSE_SEED):
+    """The engine a reanalysis round runs on: `slots` positions on the walls `mask`, a fresh tree per position, no root noise, and
+    visits + 1 so that no move ever comes due — every root stops at `visits` visits below it and nothing is played."""
+    from . import link, selfplay
+    cfg = selfplay.make_config(slots, visits + 1, seed=seed, fen=selfplay.START_FEN_PLAIN, max_plies=max_plies,
+                               dirichlet_weight=0.0, flags=link.FLAG_NO_REUSE)
+    cfg.blockers = int(mask)                         # (the start position is never searched: every round loads its own)
+    return cfg
+
+
+def _flat_targets(start, index, weight):
+    """The targets of n plies (a read_plies result) as one float64 array [n * 833], equal cells of a ply added up."""
+    n, cells = len(start) - 1, BOARD * BOARD * MOVE_TYPES
+    keys = np.repeat(np.arange(n, dtype=np.int64), np.diff(start)) * cells + index.astype(np.int64)
+    return np.bincount(keys, weights=weight.astype(np.float64), minlength=n * cells)
+
+
+def target_kl(old, new):
+    """KL(old target || new target) per ply in float64, from two read_plies results (start, index, weight) of the same plies; a
+    cell the new target lacks counts with a weight of 1e-12."""
+    p, q = _flat_targets(*old), _flat_targets(*new)
+    at = np.flatnonzero(p > 0.0)
+    terms = p[at] * (np.log(p[at]) - np.log(np.maximum(q[at], 1e-12)))
+    return np.bincount(at // (BOARD * BOARD * MOVE_TYPES), weights=terms, minlength=len(old[0]) - 1)
+
+
+def reanalyse(store, net, dtype, plan, visits, slots, log=print, seed=REANALYSE_SEED):
+    """Searches the plies of `plan` (reanalyse_plan) afresh with `net`, a link.Net, in `dtype` and makes the roots their policy
+    targets and values, one wall mask after the other.  Per mask one engine of `slots` slots with a fresh tree per position, no
+    root noise and visits + 1 so that no move ever comes due; per round: read_plies, set_positions (x | (ply & 1) << 63, o, the
+    stored ply number; a short round padded with its first position), run(net, 1 + visits), root_report_device into a tensor
+    allocated once, retarget on the round's records.  -> {"changed", "unchanged", "rounds", "seconds", "positions_per_second",
+    "mean_kl" (KL(old target || new target) over the changed plies), "stage_seconds" (per stage, summed over the rounds)}."""
+    import time
+    from . import link
+    if visits < 1:
+        raise ValueError("a reanalysis search needs at least one visit")
+    games, _ = store.mirror()
+    max_plies = int(games[:, 1].max()) + 1 if len(games) else 1
+    reports = torch.zeros(slots * link.ROOT_REPORT_WORDS, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    stages = {k: 0.0 for k in ("read_plies", "set_positions", "run", "report", "retarget", "kl")}
+    changed = unchanged = 0
+    kls = []
+    engine, engine_mask = None, None
+    t_start = time.time()
+
+    def lap(name, t0):
+        t1 = time.time()
+        stages[name] += t1 - t0
+        return t1
+
+    try:
+        for mask, plies in plan:
+            n = len(plies)
+            t = time.time()
+            boards, _, _, start, index, weight = store.read_plies(plies)
+            t = lap("read_plies", t)
+            loaded = np.empty((slots, 2), dtype=np.uint64)
+            loaded[:n, 0] = boards[:, 0] | ((plies[:, 1].astype(np.uint64) & np.uint64(1)) << np.uint64(63))
+            loaded[:n, 1] = boards[:, 1]
+            loaded[n:] = loaded[0]
+            at = np.empty(slots, dtype=np.int32)
+            at[:n] = plies[:, 1]
+            at[n:] = at[0]
+            if engine is None or engine_mask != mask:
+                if engine is not None:
+                    engine.close()
+                engine, engine_mask = link.Engine(reanalysis_config(slots, visits, mask, max_plies, seed)), mask
+                t = time.time()
+            engine.set_positions(loaded, at)
+            t = lap("set_positions", t)
+            engine.run(net, 1 + visits, dtype)               # the roots' evaluation and `visits` steps
+            engine.sync()
+            t = lap("run", t)
+            engine.root_report_device(reports, 0, n)
+            t = lap("report", t)
+            status = store.retarget(plies, reports, mask)
+            t = lap("retarget", t)
+            _, _, _, start2, index2, weight2 = store.read_plies(plies)
+            kl = target_kl((start, index, weight), (start2, index2, weight2))
+            kls.append(kl[status == 1])
+            changed += int((status == 1).sum())
+            unchanged += int((status != 1).sum())
+            lap("kl", t)
+    finally:
+        if engine is not None:
+            engine.close()
+    seconds = time.time() - t_start
+    kls = np.concatenate(kls) if kls else np.zeros(0)
+    out = {"changed": changed, "unchanged": unchanged, "rounds": len(plan), "seconds": seconds,
+           "positions_per_second": (changed + unchanged) / seconds if seconds > 0 else 0.0,
+           "mean_kl": float(kls.mean()) if len(kls) else 0.0, "stage_seconds": stages}
+    log("Reanalysis: %i plies changed, %i unchanged in %i rounds of at most %i slots at %i visits: %.2f s, %.0f positions/s; "
+        "mean KL(old target || new target) %.4f over the changed plies."
+        % (changed, unchanged, len(plan), slots, visits, seconds, out["positions_per_second"], out["mean_kl"]))
+    return out
+
+
+def _apply_reanalysis(store, old_path, fraction, visits, slots, dtype, n_test, log):
+    """One reanalysis of the training games [n_test, games) with the net at old_path, before the first step."""
+    from . import link
+    games, flags = store.mirror()
+    cand, counts, _, _ = store.ply_cum()
+    plan = reanalyse_plan(games, flags, cand, counts, store.game_blockers(), n_test, len(games) - n_test, fraction, slots,
+                          REANALYSE_SEED)
+    cw, bnp = model.load_model(old_path)
+    net = link.Net(cw, bnp)
+    try:
+        return reanalyse(store, net, link.DTYPES[dtype], plan, visits, slots, log)
+    finally:
+        net.close()
 
 
 # ---------------------------------------------------------------- the network (model.py:38-101)
@@ -720,13 +882,26 @@ def train_step(net, opt, batch, aux_loss_weights=None):
 
 def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learning_rate=0.001, blocks=12, filters=128,
           reference_bn_affine=False, device=None, log=print, value_blend=0.0, device_samples=False, device_draws=False,
-          surprise_weight=0.0, surprise_dtype="bf16", aux_ownership=0.0, aux_score=0.0, aux_reply=0.0):
+          surprise_weight=0.0, surprise_dtype="bf16", aux_ownership=0.0, aux_score=0.0, aux_reply=0.0,
+          reanalyse_fraction=0.0, reanalyse_visits=0, reanalyse_slots=4096, reanalyse_dtype="bf16"):
     """device_samples: the entries are put into a link.SampleStore once and every minibatch is written by its kernel into
     tensors allocated once (make_minibatch_device) — the same minibatches as without it, no per-step host-to-device copy of
     the batch; device_draws (implies device_samples): the kernel also draws the samples.  Both need a GPU.
     surprise_weight L > 0 (implies device_draws, needs old_path): a training game's plies are drawn in proportion to
     (1 - L) + L n KL_i / sum KL, KL_i the surprise of ply i's policy target to the net at old_path evaluated in surprise_dtype
-    (surprise_weights); the validation games stay uniform."""
+    (surprise_weights); the validation games stay uniform.
+    reanalyse_fraction F > 0 (implies device_samples, needs old_path): before the first step, and before the surprise pass, that
+    share of the training games' candidate plies is searched again with the net at old_path — reanalyse_visits visits each,
+    reanalyse_slots positions per round, the tower in reanalyse_dtype — and trained on with the new visit distribution and search
+    value (reanalyse); the validation games stay as recorded.  F = 0: nothing is called, every byte of the run is what it was."""
+    if reanalyse_fraction != 0.0:
+        if not 0.0 < reanalyse_fraction <= 1.0:
+            raise ValueError("--reanalyse-fraction must lie in [0, 1]")
+        if reanalyse_visits < 1 or reanalyse_slots < 1:
+            raise ValueError("--reanalyse-visits and --reanalyse-slots must be at least 1")
+        if old_path is None:
+            raise ValueError("--reanalyse-fraction needs --old-path: the stored plies are searched with that network")
+        device_samples = True
     if surprise_weight != 0.0:
         if not 0.0 < surprise_weight <= 1.0:
             raise ValueError("--surprise-weight must lie in [0, 1]")
@@ -770,7 +945,7 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
     def to_dev(batch):
         return tuple(torch.from_numpy(a).to(device) for a in batch)
 
-    store = _fill_store(entries, log, aux) if device_samples or device_draws else None
+    store = _fill_store(entries, log, aux, reanalyse_fraction) if device_samples or device_draws else None
     if aux:
         if store is not None:
             with_owners = int(store.game_owners()[min(10, len(entries)):].any(axis=1).sum())
@@ -784,6 +959,8 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
         if len(entries) <= n_test:
             raise ValueError("device samples need more than %d games" % n_test)
         train_out = link_outputs(store, minibatch_size, device, aux)
+        if reanalyse_fraction > 0.0:
+            _apply_reanalysis(store, old_path, reanalyse_fraction, reanalyse_visits, reanalyse_slots, reanalyse_dtype, n_test, log)
         if surprise_weight > 0.0:
             _apply_surprise(store, old_path, surprise_weight, surprise_dtype, n_test, log)
 

@@ -769,6 +769,9 @@ int azh_engine_play_moves(azh_engine *e, const uint16_t *moves /* [games] */, in
 #define AZH_PV_MAX 32
 enum { AZH_ROOT_REPORT_PV = 4 + 4 * AZH_MAX_MOVES, AZH_ROOT_REPORT_WORDS = AZH_ROOT_REPORT_PV + 1 + 2 * AZH_PV_MAX };
 int azh_engine_root_report(azh_engine *e, int first_game, int n_games, uint32_t *out /* [n_games][AZH_ROOT_REPORT_WORDS] */);
+/* The same kernel and the same records written into a DEVICE array of the caller's, d_out [n_games][AZH_ROOT_REPORT_WORDS] (a
+ * torch tensor's pointer): no device-to-host copy; returns when the kernel has completed.  What azh_samples_retarget reads. */
+int azh_engine_root_report_device(azh_engine *e, int first_game, int n_games, uint32_t *d_out);
 
 int azh_engine_game_state(azh_engine *e, int game, azh_game_state *out);
 /* arena dump: boards [n_nodes][2] u64, info [n_nodes][4] u32
@@ -1103,6 +1106,66 @@ int azh_samples_check_owners(uint64_t own_x, uint64_t own_o, uint64_t blockers, 
  * nothing written (also when only the counts are asked for).
  * azh_samples_game_owners: the host mirror of the owners, owners [games][2]. */
 int azh_samples_game_owners(const azh_samples *s, uint64_t *owners);
+
+/* ------------------------------------------------------------------ reanalysis of stored plies
+ * (an extension of the store; with none of these called, every call, launch and byte above is what it was.)  A stored ply's
+ * policy target and value are replaced by what a fresh search of its position gives (MuZero's Reanalyse): the positions are read
+ * back (azh_samples_read_plies), an engine searches them without playing a move (azh_engine_set_positions, AZH_FLAG_NO_REUSE,
+ * visits + 1), its root reports stay on the device (azh_engine_root_report_device) and a kernel of the store turns them into
+ * targets (azh_samples_retarget).  training.reanalyse drives the rounds; DESIGN.md section 4, "Reanalysis of stored plies".
+ *
+ * azh_samples_read_plies: a host read-back of n stored plies, plies [n][2] = (game, ply): boards_out [n][2] (x, o),
+ * values_out [n], flags_out [n] (AZH_SAMPLES_PLY_*), target_start_out [n + 1] (the running sum of the plies' target counts
+ * from 0) and, unless index_out and weight_out are both NULL, the targets in stored order behind one another, cap_targets
+ * being the room of those two arrays.  A small gather kernel, then a copy; waits for the store's stream.  -1 for a pair
+ * outside the store (checked against the mirror before any launch) or one of the two arrays without the other, -6 when
+ * cap_targets is too small (the counts have been written by then: target_start_out [n] says how much room is needed). */
+int azh_samples_read_plies(azh_samples *s, int n, const int32_t *plies /* [n][2] (game, ply) */,
+                           uint64_t *boards_out /* [n][2] x, o */, double *values_out /* [n] */,
+                           uint8_t *flags_out /* [n] */, int32_t *target_start_out /* [n + 1] */,
+                           uint16_t *index_out, float *weight_out, int64_t cap_targets);
+/* Diagnostic: where the targets of those plies lie, out [n][2] = (first target, counted from the store's first; targets), read
+ * from the device like azh_samples_read_plies.  tests/reanalyse_gpu_checks.py checks azh_samples_retarget's placement on it. */
+int azh_samples_ply_targets(azh_samples *s, int n, const int32_t *plies /* [n][2] */, uint32_t *out /* [n][2] */);
+/* The definition, stated once; azh_samples_retarget (device) and azh_samples_retarget_host (host arithmetic) both follow it.
+ * A RECORD r is one slot's AZH_ROOT_REPORT_WORDS words of azh_engine_root_report.  M = r[1]; edge j < M has move r[4 + 4 j],
+ * visits r[5 + 4 j] and total score W = the f32 in r[6 + 4 j].
+ *   MALFORMED: M > AZH_MAX_MOVES, or an edge j < M with visits > 0 whose move word is no clone and no jump over a distance of
+ *     two between two of the 49 cells (from | to << 8, nothing above bit 15).
+ *   total = the sum of the visits of the edges j < M, as a u64.
+ *   UNCHANGED: total == 0 (M == 0 among it) or r[3] != 0 (a finished root): the ply stays exactly as it was, status 0.
+ *   Otherwise the NEW TARGET is, for the edges j < M with visits_j > 0 in edge order, the pair
+ *     index = the engine's move -> policy index map of move_j,  weight = (float)((double)visits_j / (double)total)
+ *   — the rule azh_samples_pack_records applies to a game line's counts — and the NEW VALUE comes from the edge b with the most
+ *   visits, the first in edge order on a tie: q = W_b / (float)visits_b, one IEEE f32 division, and
+ *     value = isfinite(q) ? 2.0 * (double)q - 1.0 : 0.0,
+ *   the record rule under kind & 16.  The value is always written; it is read, as before, only for games that have values.
+ *
+ * azh_samples_retarget_host: one record -> its new pairs in index_out / weight_out [up to AZH_MAX_MOVES], their number in
+ * *n_out (0: unchanged, *value_out is then 0.0) and the value in *value_out.  -2 for a malformed record.  Host arithmetic only,
+ * usable without a device.
+ *
+ * azh_samples_retarget: ply i of plies [n][2] = (game, ply) takes record i of d_reports, a DEVICE array
+ * [n][AZH_ROOT_REPORT_WORDS].  status_out [n] on the host: 1 changed, 0 unchanged.
+ * Placement.  New targets are appended: with T the store's target count before the call, changed ply i gets first_target =
+ * T + (the sum of the new counts of the changed plies < i) and its new count; its flag byte is untouched, the old pairs stay
+ * where they are, unreferenced; azh_samples_counts reports the new total and later azh_samples_add_games calls append behind it.
+ * A reanalysed ply stays the candidate it was.
+ * Checked on the host first, against the mirror, nothing launched: -1 for a pair out of range, a pass ply, a ply that is
+ * not among its game's candidates (not FULL in a game that has "full") or a pair given twice; -2 for a BAD ply, and for
+ * report_blockers (the walls the reports were searched on) differing from the game's stored mask (0 for a game without one).
+ * Then two phases, so that a refused call changes nothing.  Phase 1, one wave per record, counts the new targets and marks
+ * malformed records; an exclusive scan of the counts in call order follows and the host reads the total and the number of
+ * malformed records: any malformed record -> -2, a total that does not fit beside T in the store's target capacity -> -6,
+ * nothing written either time.  Phase 2, one wave per record, writes the pairs, the value and the ply's two target words.
+ * The call waits for the store's own stream and for `stream` (0: none) before it writes, runs on the store's stream and
+ * returns after completion.  It must not run while a minibatch call is in flight on another stream.  The per-ply surprise
+ * kept by azh_samples_surprise is stale for changed plies: run the surprise pass afterwards. */
+int azh_samples_retarget(azh_samples *s, int n, const int32_t *plies /* [n][2] */,
+                         const uint32_t *d_reports /* DEVICE [n][AZH_ROOT_REPORT_WORDS] */, uint64_t report_blockers,
+                         int32_t *status_out /* [n] */, uintptr_t stream);
+int azh_samples_retarget_host(const uint32_t *report /* one record */, uint16_t *index_out, float *weight_out, int32_t *n_out,
+                              double *value_out);
 
 /* ------------------------------------------------------------------ reference ABI
  * The four symbols link.py:6-32 binds (cpp/self_play_client.cpp:683-749), with

@@ -18,6 +18,10 @@ nothing changes).
 predict who owns each cell at the game's end, the final margin in stones and the opponent's answer, from what the game lines
 already hold; their weights go to NEW-PATH.aux.npz and the .npy file is what it always was.  All three 0 (the default):
 nothing changes.
+--reanalyse-fraction F searches that share of the training games' candidate plies again with the --old-path network before the
+first step (--reanalyse-visits V each, --reanalyse-slots positions per round) and trains on the new visit distributions and
+search values (MuZero's Reanalyse; an extension; implies --device-samples, needs --old-path).  F = 0 (the default): nothing
+changes.
 """
 from ataxxzero_amd import training
 from ataxxzero_amd.cli import flag, parse, switch
@@ -53,6 +57,14 @@ OPTIONS = [
     flag("--aux-reply", "weight A of the reply loss: a second training-only head predicts the policy target of the next ply, "
                         "the opponent's answer (extension; 0: off; KataGo: 0.15; not tuned for Ataxx)", type=float, default=0.0,
          metavar="A"),
+    flag("--reanalyse-fraction", "share F in [0, 1] of the training games' candidate plies that are searched again with the "
+                                 "--old-path network before the first step; their policy targets and values become the new "
+                                 "roots' (extension; implies --device-samples, needs --old-path and --reanalyse-visits; 0: off)",
+         type=float, default=0.0, metavar="F"),
+    flag("--reanalyse-visits", "visits of each reanalysis search", type=int, default=0, metavar="V"),
+    flag("--reanalyse-slots", "positions searched per round", type=int, default=4096, metavar="G"),
+    flag("--reanalyse-dtype", "tower precision of the reanalysis searches", default="bf16", choices=["f32", "bf16", "f16"],
+         metavar="DTYPE"),
 ]
 
 if __name__ == "__main__":
@@ -66,6 +78,17 @@ if __name__ == "__main__":
         args.device_draws = True
     else:                                   # off: the run, and the line below, are those of a train.py without the flags
         del args.surprise_weight, args.surprise_dtype
+    reanalysis = {}
+    if args.reanalyse_fraction != 0.0:
+        if not 0.0 < args.reanalyse_fraction <= 1.0 or args.reanalyse_visits < 1 or args.reanalyse_slots < 1 or \
+                args.old_path is None:
+            raise SystemExit("train.py: --reanalyse-fraction takes F in [0, 1], --reanalyse-visits V >= 1 (and --reanalyse-slots "
+                             "G >= 1) and needs --old-path, the network the stored plies are searched with")
+        reanalysis = {"reanalyse_fraction": args.reanalyse_fraction, "reanalyse_visits": args.reanalyse_visits,
+                      "reanalyse_slots": args.reanalyse_slots, "reanalyse_dtype": args.reanalyse_dtype}
+        args.device_samples = True
+    else:                                   # off: as above
+        del args.reanalyse_fraction, args.reanalyse_visits, args.reanalyse_slots, args.reanalyse_dtype
     aux = {"aux_ownership": args.aux_ownership, "aux_score": args.aux_score, "aux_reply": args.aux_reply}
     if min(aux.values()) < 0.0:
         raise SystemExit("train.py: --aux-ownership, --aux-score and --aux-reply take weights >= 0")
@@ -75,4 +98,5 @@ if __name__ == "__main__":
     print("Arguments:", args)
     training.train(args.games, args.old_path, args.new_path, steps=args.steps, minibatch_size=args.minibatch_size,
                    learning_rate=args.learning_rate, reference_bn_affine=args.reference_bn_affine, value_blend=args.value_blend,
-                   device_samples=args.device_samples or args.device_draws, device_draws=args.device_draws, **surprise, **aux)
+                   device_samples=args.device_samples or args.device_draws, device_draws=args.device_draws, **surprise, **aux,
+                   **reanalysis)
