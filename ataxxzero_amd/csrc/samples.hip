@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "alphabeta_search.h"
 #include "azh_device.h"
 #include "azh_host.h"
 
@@ -45,6 +46,7 @@ struct View {  // what the kernels read
     const float *target_weight;
     const u32 *cum;  // null: uniform ply draws; else [first ply + k]: the running sum of the game's candidate weights
     const u64 *blockers;  // null: no stored game has walls; else [game]: its wall mask, bit = file + 7 * rank
+    const int16_t *proofs;  // null: azh_samples_prove was never called; else [ply]: the proven value of its mover, 0: none
 };
 
 struct NoAux {};  // the kernels without auxiliary targets: emit_sample is what it was
@@ -86,6 +88,11 @@ __device__ void emit_sample(const View &v, float *lds, int i, int g, int p, int 
             float out = (float)z;
             if (blend != 0.0 && (game.z & GAME_HAS_VALUES))
                 out = (float)((1.0 - blend) * (double)z + blend * ply.value);
+            if (v.proofs) {  // a proven outcome stands above the game's result and the search's value
+                const int proof = v.proofs[game.x + (u32)p];
+                if (proof != 0)
+                    out = proof > 0 ? 1.0f : -1.0f;
+            }
             lds[FEATURES + POLICY] = out;
         }
         if constexpr (AUX) {
@@ -401,6 +408,11 @@ struct azh_samples {
     // reanalysis: scratch of azh_samples_read_plies and azh_samples_retarget, null until one of them is called
     DeviceArray<unsigned char> d_scratch;
     size_t scratch_bytes = 0;
+    // proven outcomes (azh_samples_prove): all null until its first call that commits
+    DeviceArray<int16_t> d_proofs;       // [cap_plies]: 0, or the search's value, |value| >= 1000
+    DeviceArray<u16> d_proof_moves;      // [cap_plies]: the move of the ply's last search, 0xFFFF before one
+    DeviceArray<uint8_t> d_proof_depths; // [cap_plies]: the iteration that search completed
+    std::vector<int16_t> h_proofs;       // [plies at the last call]: the mirror of d_proofs
     // the host mirror: what a draw is validated against
     std::vector<uint32_t> h_games;  // [games][4]
     std::vector<uint8_t> h_flags;   // [plies]
@@ -418,7 +430,7 @@ struct azh_samples {
     View view() const
     {
         return View{d_games.d, d_plies.d, d_candidates.d, d_candidate_count.d, d_target_index.d, d_target_weight.d, d_cum.d,
-                    d_blockers.d};
+                    d_blockers.d, d_proofs.d};
     }
 };
 
@@ -473,6 +485,9 @@ extern "C" void azh_samples_destroy(azh_samples *s)
     s->d_kl.release();
     s->d_illegal.release();
     s->d_scratch.release();
+    s->d_proofs.release();
+    s->d_proof_moves.release();
+    s->d_proof_depths.release();
     if (s->stream)
         (void)hipStreamDestroy(s->stream);
     delete s;
@@ -1849,5 +1864,228 @@ extern "C" int azh_samples_retarget(azh_samples *s, int n, const int32_t *plies,
     AZH_HIP(hipMemcpyAsync(status_out, d_status, N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     AZH_HIP(hipStreamSynchronize(st));
     s->targets += (int64_t)totals[0];
+    return 0;
+}
+
+// ---------------------------------------------------------------- proven outcomes for stored plies (include/ataxxzero_hip.h)
+
+namespace {
+
+constexpr int PROVE_CHUNK = SURPRISE_CHUNK;  // plies per launch: a launch runs no longer than this many searches under the budget
+
+struct ProveItem {  // one eligible ply of a call
+    u32 ply, game;  // its place in the store; its game, whose wall mask the search runs on
+};
+struct ProveResult {  // what azh_alphabeta_search reports for the ply's position
+    int value;
+    u32 move_depth;  // move | depth_done << 16
+    u64 nodes;
+};
+struct ProofRow {  // azh_samples_proofs: one ply's three words
+    int proof, move, depth_done;
+};
+
+// k_alphabeta's shape: one wave per ply, AB_WAVES of them per workgroup, each on its own stack in LDS; no wave waits for
+// another.  The position is read where the store keeps it: the ply's record and its game's wall mask.
+__global__ __launch_bounds__(AB_WAVES *WAVE) void k_samples_prove(View v, const ProveItem *__restrict__ items, int n, int depth,
+                                                                  u64 budget, ProveResult *__restrict__ out)
+{
+    __shared__ AbStack stacks[AB_WAVES];
+    const int wave = (int)(threadIdx.x >> 6);
+    const int r = uni((int)blockIdx.x * AB_WAVES + wave);
+    if (r >= n)
+        return;  // the whole wave
+    const ProveItem it = items[r];
+    const Ply ply = v.plies[it.ply];
+    Board root;
+    root.x = ply.x;
+    root.o = ply.o;
+    root.turn = (ply.targets_flags & PLY_ODD) ? 1 : 0;
+    const u64 bl = v.blockers ? v.blockers[it.game] : 0ULL;
+    const AbAnswer a = ab_search_position(root, bl, &stacks[wave], depth, budget);
+    if (lane_id() == 0)
+        out[r] = ProveResult{a.value, a.move | ((u32)a.depth_done << 16), a.nodes};
+}
+
+// Phase 2: item i's result goes to its ply's three proof words (the proof only where the value is a proven one); slot[i] !=
+// NONE: the ply also takes the single pair (its move, 1.0f) at target slot[i].  The host has found the room.
+__global__ __launch_bounds__(256) void k_samples_prove_commit(const ProveItem *__restrict__ items, const ProveResult *__restrict__ res,
+                                                              const u32 *__restrict__ slot, int n, Ply *__restrict__ plies,
+                                                              int16_t *__restrict__ proofs, u16 *__restrict__ moves,
+                                                              uint8_t *__restrict__ depths, u16 *__restrict__ target_index,
+                                                              float *__restrict__ target_weight)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n)
+        return;
+    const u32 at = items[i].ply;
+    const ProveResult r = res[i];
+    if (r.value >= AB_WIN || r.value <= -AB_WIN)
+        proofs[at] = (int16_t)r.value;
+    moves[at] = (u16)(r.move_depth & 0xFFFFu);
+    depths[at] = (uint8_t)(r.move_depth >> 16);
+    if (slot && slot[i] != NONE) {
+        target_index[slot[i]] = (u16)policy_index(r.move_depth & 0xFFFFu);
+        target_weight[slot[i]] = 1.0f;
+        plies[at].first_target = slot[i];
+        plies[at].targets_flags = (1u << 8) | (plies[at].targets_flags & 0xFFu);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_samples_read_proofs(int n, const u32 *__restrict__ ply_at, const int16_t *__restrict__ proofs,
+                                                             const u16 *__restrict__ moves, const uint8_t *__restrict__ depths,
+                                                             ProofRow *__restrict__ out)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n)
+        out[i] = ProofRow{(int)proofs[ply_at[i]], (int)moves[ply_at[i]], (int)depths[ply_at[i]]};
+}
+
+}  // namespace
+
+// The three proof arrays, all or none: no proof, no move (0xFFFF), no iteration for every ply the store can hold.
+static int reserve_proofs(azh_samples *s)
+{
+    if (s->d_proofs.d)
+        return 0;
+    DeviceArray<int16_t> proofs;
+    DeviceArray<u16> moves;
+    DeviceArray<uint8_t> depths;
+    const size_t cap = (size_t)s->cap_plies;
+    int rc = proofs.alloc(cap);
+    rc = rc ? rc : moves.alloc(cap);
+    rc = rc ? rc : depths.alloc(cap);
+    if (!rc) {
+        hipError_t e = hipMemsetAsync(proofs.d, 0, cap * sizeof(int16_t), s->stream);
+        e = e == hipSuccess ? hipMemsetAsync(moves.d, 0xFF, cap * sizeof(u16), s->stream) : e;
+        e = e == hipSuccess ? hipMemsetAsync(depths.d, 0, cap, s->stream) : e;
+        e = e == hipSuccess ? hipStreamSynchronize(s->stream) : e;
+        if (e != hipSuccess)
+            rc = azh_fail(-100 - (int)e, "azh_samples_prove: %s", hipGetErrorString(e));
+    }
+    if (rc) {
+        proofs.release();
+        moves.release();
+        depths.release();
+        return rc;
+    }
+    s->d_proofs = proofs;
+    s->d_proof_moves = moves;
+    s->d_proof_depths = depths;
+    return 0;
+}
+
+extern "C" int azh_samples_prove(azh_samples *s, int64_t first_game, int64_t n_games, int depth, uint64_t node_budget,
+                                 int retarget_wins, uint64_t *stats_out)
+{
+    if (!s || !stats_out)
+        return azh_fail(-1, "azh_samples_prove: null argument");
+    if (first_game < 0 || n_games < 1 || first_game + n_games > s->games)
+        return azh_fail(-1, "azh_samples_prove: games [%lld, %lld) of %lld", (long long)first_game,
+                        (long long)(first_game + n_games), (long long)s->games);
+    if (const char *why = limits_refusal(depth, node_budget))
+        return azh_fail(-2, "azh_samples_prove: %s", why);
+    // the eligible plies in ascending (game, ply) order, from the mirrors: a game's candidates are kept in ply order
+    std::vector<ProveItem> items;
+    for (int64_t g = first_game; g < first_game + n_games; g++) {
+        const u32 first = s->h_games[4 * g];
+        for (u32 k = 0; k < s->h_count[(size_t)g]; k++) {
+            const u32 at = first + s->h_candidates[first + k];
+            if (s->h_flags[at] & (AZH_SAMPLES_PLY_PASS | AZH_SAMPLES_PLY_BAD))
+                continue;
+            if (at < s->h_proofs.size() && s->h_proofs[at] != 0)
+                continue;
+            items.push_back(ProveItem{at, (u32)g});
+        }
+    }
+    uint64_t stats[AZH_SAMPLES_PROOF_STAT_COUNT] = {};
+    const size_t N = items.size();
+    if (N == 0) {
+        memcpy(stats_out, stats, sizeof(stats));
+        return 0;
+    }
+    // phase 1: every search into scratch, nothing of the store written
+    const size_t item_bytes = round_up(N * sizeof(ProveItem)), result_bytes = round_up(N * sizeof(ProveResult));
+    if (int rc = reserve_scratch(s, item_bytes + result_bytes + round_up(N * sizeof(u32))))
+        return rc;
+    ProveItem *d_items = reinterpret_cast<ProveItem *>(s->d_scratch.d);
+    ProveResult *d_results = reinterpret_cast<ProveResult *>(s->d_scratch.d + item_bytes);
+    u32 *d_slot = reinterpret_cast<u32 *>(s->d_scratch.d + item_bytes + result_bytes);
+    hipStream_t st = s->stream;
+    AZH_HIP(hipStreamSynchronize(st));
+    AZH_HIP(hipMemcpyAsync(d_items, items.data(), N * sizeof(ProveItem), hipMemcpyHostToDevice, st));
+    for (size_t at = 0; at < N; at += PROVE_CHUNK) {
+        const int n = (int)std::min<size_t>(PROVE_CHUNK, N - at);
+        hipLaunchKernelGGL(k_samples_prove, dim3((unsigned)((n + AB_WAVES - 1) / AB_WAVES)), dim3(AB_WAVES * WAVE), 0, st, s->view(),
+                           d_items + at, n, depth, (u64)node_budget, d_results + at);
+        AZH_HIP(hipGetLastError());
+    }
+    std::vector<ProveResult> results(N);
+    AZH_HIP(hipMemcpyAsync(results.data(), d_results, N * sizeof(ProveResult), hipMemcpyDeviceToHost, st));
+    AZH_HIP(hipStreamSynchronize(st));
+    std::vector<u32> slot(N, NONE);
+    stats[AZH_PROOF_VISITED] = N;
+    for (size_t i = 0; i < N; i++) {
+        const ProveResult &r = results[i];
+        stats[AZH_PROOF_NODES] += r.nodes;
+        if (r.value > -AB_WIN && r.value < AB_WIN)
+            continue;
+        const u32 p = items[i].ply - s->h_games[4 * (size_t)items[i].game];
+        const bool mover_won = (s->h_games[4 * (size_t)items[i].game + 2] & 0xFFu) == 1u + (p & 1u);
+        stats[r.value > 0 ? AZH_PROOF_WINS : AZH_PROOF_LOSSES]++;
+        stats[AZH_PROOF_CONTRADICTED] += (r.value > 0) != mover_won;
+        if (retarget_wins && r.value > 0 && (r.move_depth & 0xFFFFu) != 0xFFFFu)
+            slot[i] = (u32)(s->targets + (int64_t)stats[AZH_PROOF_RETARGETED]++);
+    }
+    if ((u64)s->targets + stats[AZH_PROOF_RETARGETED] > (u64)s->cap_targets)
+        return azh_fail(-6, "azh_samples_prove: %llu new targets do not fit beside %lld in a capacity of %lld",
+                        (unsigned long long)stats[AZH_PROOF_RETARGETED], (long long)s->targets, (long long)s->cap_targets);
+    // phase 2
+    if (int rc = reserve_proofs(s))
+        return rc;
+    const bool pairs = stats[AZH_PROOF_RETARGETED] != 0;
+    if (pairs)
+        AZH_HIP(hipMemcpyAsync(d_slot, slot.data(), N * sizeof(u32), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_samples_prove_commit, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d_items, d_results,
+                       pairs ? d_slot : (const u32 *)nullptr, (int)N, s->d_plies.d, s->d_proofs.d, s->d_proof_moves.d,
+                       s->d_proof_depths.d, s->d_target_index.d, s->d_target_weight.d);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipStreamSynchronize(st));
+    s->h_proofs.resize((size_t)s->plies, 0);
+    for (size_t i = 0; i < N; i++)
+        if (results[i].value >= AB_WIN || results[i].value <= -AB_WIN)
+            s->h_proofs[items[i].ply] = (int16_t)results[i].value;
+    s->targets += (int64_t)stats[AZH_PROOF_RETARGETED];
+    memcpy(stats_out, stats, sizeof(stats));
+    return 0;
+}
+
+extern "C" int azh_samples_proofs(azh_samples *s, int n, const int32_t *plies, int32_t *proof_out, uint16_t *move_out,
+                                  int32_t *depth_done_out)
+{
+    if (!s || !plies || !proof_out || !move_out || !depth_done_out || n < 1)
+        return azh_fail(-1, "azh_samples_proofs: bad argument");
+    std::vector<u32> at;
+    if (int rc = ply_places(s, "azh_samples_proofs", n, plies, at))
+        return rc;
+    const size_t N = (size_t)n, at_bytes = round_up(N * sizeof(u32));
+    std::vector<ProofRow> got(N, ProofRow{0, 0xFFFF, 0});
+    if (s->d_proofs.d) {
+        if (int rc = reserve_scratch(s, at_bytes + round_up(N * sizeof(ProofRow))))
+            return rc;
+        u32 *d_at = reinterpret_cast<u32 *>(s->d_scratch.d);
+        ProofRow *d_out = reinterpret_cast<ProofRow *>(s->d_scratch.d + at_bytes);
+        AZH_HIP(hipMemcpyAsync(d_at, at.data(), N * sizeof(u32), hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(k_samples_read_proofs, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, n, d_at, s->d_proofs.d,
+                           s->d_proof_moves.d, s->d_proof_depths.d, d_out);
+        AZH_HIP(hipGetLastError());
+        AZH_HIP(hipMemcpyAsync(got.data(), d_out, N * sizeof(ProofRow), hipMemcpyDeviceToHost, s->stream));
+        AZH_HIP(hipStreamSynchronize(s->stream));
+    }
+    for (size_t i = 0; i < N; i++) {
+        proof_out[i] = got[i].proof;
+        move_out[i] = (uint16_t)got[i].move;
+        depth_done_out[i] = got[i].depth_done;
+    }
     return 0;
 }

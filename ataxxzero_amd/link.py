@@ -235,6 +235,8 @@ SIGNATURES = {
     "azh_samples_ply_targets": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     "azh_samples_retarget": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _u64, _vp, ctypes.c_size_t]),
     "azh_samples_retarget_host": (ctypes.c_int, [_vp, _vp, _vp, _P(_i32), _P(ctypes.c_double)]),
+    "azh_samples_prove": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _u64, ctypes.c_int, _vp]),
+    "azh_samples_proofs": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
     # the reference's ABI, link.py:8-32
     "launch_threads": (None, [ctypes.c_char_p, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int]),
     "get_workload": (ctypes.c_int, []),
@@ -1619,3 +1621,29 @@ class SampleStore:
         check(load().azh_samples_retarget(self.h, n, _ptr(plies), ctypes.c_void_p(reports.data_ptr()), int(blockers),
                                           _ptr(status), torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY))
         return status
+
+    # proven outcomes for stored plies ("Proven outcomes for stored plies")
+
+    PROOF_STATS = ("visited", "wins", "losses", "contradicted", "retargeted", "nodes")   # AZH_PROOF_*
+
+    def prove(self, first_game, n_games, depth, node_budget=0, retarget_wins=False):
+        """The alpha-beta search of every eligible ply of games [first_game, first_game + n_games) that has no proof yet, at
+        (depth, node_budget) as alphabeta_search takes them; a value of 1000 or more in magnitude becomes the ply's proof, and
+        minibatches then train its value on the proven outcome; retarget_wins: a ply newly proven won also takes its move as
+        its policy target -> this call's counts, a dict over PROOF_STATS.  A refused call changes nothing (azh_samples_prove).
+        Minibatch calls enqueued on torch's current stream are waited for first."""
+        import torch
+        torch.cuda.current_stream().synchronize()
+        stats = np.zeros(len(self.PROOF_STATS), dtype=np.uint64)
+        check(load().azh_samples_prove(self.h, int(first_game), int(n_games), int(depth), int(node_budget),
+                                       int(bool(retarget_wins)), _ptr(stats)))
+        return dict(zip(self.PROOF_STATS, (int(v) for v in stats)))
+
+    def proofs(self, plies):
+        """The plies (n, 2) of (game, ply) -> (proof (n,) i32: 0 or the proving search's value; move (n,) u16 and depth_done
+        (n,) i32 of the ply's last search, 0xFFFF and 0 before one), read back from the device (azh_samples_proofs)."""
+        plies = np.ascontiguousarray(plies, dtype=np.int32).reshape(-1, 2)
+        n = len(plies)
+        proof, move, done = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.int32)
+        check(load().azh_samples_proofs(self.h, n, _ptr(plies), _ptr(proof), _ptr(move), _ptr(done)))
+        return proof, move, done

@@ -459,23 +459,24 @@ def make_minibatch_device(store, first_game, n_games, size, value_blend=0.0, out
     return store.gather(np.asarray(rows, dtype=np.int32), value_blend, out=out, aux=aux)
 
 
-def _fill_store(entries, log, aux=False, reanalyse_fraction=0.0, n_test=10):
+def _fill_store(entries, log, aux=False, reanalyse_fraction=0.0, n_test=10, prove_policy=False):
     """reanalyse_fraction F > 0: the store gets round(F * C) * MAX_MOVES targets of head-room, C the candidate plies of the
-    training games [n_test, n) that are no passes (reanalysed targets are appended: SampleStore.retarget)."""
+    training games [n_test, n) that are no passes (reanalysed targets are appended: SampleStore.retarget).  prove_policy: C
+    more, one per ply a proof pass can retarget (SampleStore.prove)."""
     from . import link
     link.require_gpu()
     arrays = link.entries_to_arrays(entries, aux=aux)
     spare = 0
-    if reanalyse_fraction > 0.0:
+    if reanalyse_fraction > 0.0 or prove_policy:
         c = 0
         for first, plies, word, _ in arrays.games[n_test:].tolist():
             f = arrays.ply_flags[first:first + plies]
             cand = (f & link.SAMPLES_PLY_FULL) != 0 if word & link.SAMPLES_GAME_HAS_FULL else np.ones(plies, dtype=bool)
             c += int((cand & ((f & link.SAMPLES_PLY_PASS) == 0)).sum())
-        spare = round(reanalyse_fraction * c) * link.MAX_MOVES
+        spare = round(reanalyse_fraction * c) * link.MAX_MOVES + (c if prove_policy else 0)
         if len(arrays.target_index) + spare >= 1 << 31:
-            raise ValueError("--reanalyse-fraction %g of %d plies asks for %d targets of head-room: a store holds fewer than 2^31"
-                             % (reanalyse_fraction, c, spare))
+            raise ValueError("--reanalyse-fraction %g%s of %d plies asks for %d targets of head-room: a store holds fewer than "
+                             "2^31" % (reanalyse_fraction, " and --prove-policy" if prove_policy else "", c, spare))
     store = link.SampleStore(max(len(arrays.games), 1), max(len(arrays.ply_flags), 1), max(len(arrays.target_index) + spare, 1))
     store.add_arrays(arrays)
     c = store.counts()
@@ -684,6 +685,32 @@ def _apply_reanalysis(store, old_path, fraction, visits, slots, dtype, n_test, l
 
 # ---------------------------------------------------------------- the network (model.py:38-101)
 
+# ---------------------------------------------------------------- proven outcomes for stored plies
+
+def prove_refusal(depth, nodes):
+    """Why train.py --prove-depth D --prove-nodes N is refused, or None: the limits of the alpha-beta search, checked before
+    anything touches the device."""
+    from . import link
+    if not 1 <= depth <= link.ALPHABETA_MAX_DEPTH:
+        return "--prove-depth must be 1 .. %d" % link.ALPHABETA_MAX_DEPTH
+    if nodes == 0 and depth > link.ALPHABETA_UNBOUNDED_DEPTH:
+        return "--prove-nodes 0 (no limit) is accepted up to --prove-depth %d only" % link.ALPHABETA_UNBOUNDED_DEPTH
+    if nodes != 0 and nodes < link.MAX_MOVES:
+        return "--prove-nodes must be 0 (no limit) or at least %d" % link.MAX_MOVES
+    return None
+
+
+def _apply_proofs(store, depth, nodes, policy, n_test, log):
+    """One proof pass over the training games [n_test, games), before the first step (SampleStore.prove)."""
+    games, _ = store.mirror()
+    s = store.prove(n_test, len(games) - n_test, depth, nodes, retarget_wins=policy)
+    log("Proofs: %i proven wins, %i proven losses among %i plies searched to depth %i (%s); %i contradict their game's result; "
+        "%i policy targets replaced" % (s["wins"], s["losses"], s["visited"], depth,
+                                        "at most %i nodes each" % nodes if nodes else "no node limit", s["contradicted"],
+                                        s["retargeted"]))
+    return s
+
+
 def aux_random_init(filters, seed=1):
     """Fresh weights of the auxiliary heads in torch's layouts, with model.random_init's distributions (truncated normal,
     stddev 0.2 * sqrt(2 / fan_in); bias 0.01), from numpy's PCG64(seed) alone."""
@@ -883,7 +910,8 @@ def train_step(net, opt, batch, aux_loss_weights=None):
 def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learning_rate=0.001, blocks=12, filters=128,
           reference_bn_affine=False, device=None, log=print, value_blend=0.0, device_samples=False, device_draws=False,
           surprise_weight=0.0, surprise_dtype="bf16", aux_ownership=0.0, aux_score=0.0, aux_reply=0.0,
-          reanalyse_fraction=0.0, reanalyse_visits=0, reanalyse_slots=4096, reanalyse_dtype="bf16"):
+          reanalyse_fraction=0.0, reanalyse_visits=0, reanalyse_slots=4096, reanalyse_dtype="bf16", prove_depth=0,
+          prove_nodes=0, prove_policy=False):
     """device_samples: the entries are put into a link.SampleStore once and every minibatch is written by its kernel into
     tensors allocated once (make_minibatch_device) — the same minibatches as without it, no per-step host-to-device copy of
     the batch; device_draws (implies device_samples): the kernel also draws the samples.  Both need a GPU.
@@ -893,7 +921,17 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
     reanalyse_fraction F > 0 (implies device_samples, needs old_path): before the first step, and before the surprise pass, that
     share of the training games' candidate plies is searched again with the net at old_path — reanalyse_visits visits each,
     reanalyse_slots positions per round, the tower in reanalyse_dtype — and trained on with the new visit distribution and search
-    value (reanalyse); the validation games stay as recorded.  F = 0: nothing is called, every byte of the run is what it was."""
+    value (reanalyse); the validation games stay as recorded.  F = 0: nothing is called, every byte of the run is what it was.
+    prove_depth D > 0 (implies device_samples, needs no net): after reanalysis and before the surprise pass, the device's
+    alpha-beta search of depth D (prove_nodes nodes at most per ply, 0: no limit, D <= 3) runs on the training games' eligible
+    plies; a ply it proves won or lost trains the value head on that outcome instead of the game's result, and under
+    prove_policy a ply proven won takes the winning move as its policy target (SampleStore.prove); the validation games stay
+    as recorded.  D = 0: nothing is called, every byte of the run is what it was."""
+    if prove_depth != 0 or prove_nodes != 0 or prove_policy:
+        why = prove_refusal(prove_depth, prove_nodes) if prove_depth != 0 else "--prove-nodes and --prove-policy need --prove-depth"
+        if why:
+            raise ValueError(why)
+        device_samples = True
     if reanalyse_fraction != 0.0:
         if not 0.0 < reanalyse_fraction <= 1.0:
             raise ValueError("--reanalyse-fraction must lie in [0, 1]")
@@ -945,7 +983,8 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
     def to_dev(batch):
         return tuple(torch.from_numpy(a).to(device) for a in batch)
 
-    store = _fill_store(entries, log, aux, reanalyse_fraction) if device_samples or device_draws else None
+    store = _fill_store(entries, log, aux, reanalyse_fraction, prove_policy=prove_policy) if device_samples or device_draws \
+        else None
     if aux:
         if store is not None:
             with_owners = int(store.game_owners()[min(10, len(entries)):].any(axis=1).sum())
@@ -961,6 +1000,8 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
         train_out = link_outputs(store, minibatch_size, device, aux)
         if reanalyse_fraction > 0.0:
             _apply_reanalysis(store, old_path, reanalyse_fraction, reanalyse_visits, reanalyse_slots, reanalyse_dtype, n_test, log)
+        if prove_depth > 0:
+            _apply_proofs(store, prove_depth, prove_nodes, prove_policy, n_test, log)
         if surprise_weight > 0.0:
             _apply_surprise(store, old_path, surprise_weight, surprise_dtype, n_test, log)
 

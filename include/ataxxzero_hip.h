@@ -1167,6 +1167,52 @@ int azh_samples_retarget(azh_samples *s, int n, const int32_t *plies /* [n][2] *
 int azh_samples_retarget_host(const uint32_t *report /* one record */, uint16_t *index_out, float *weight_out, int32_t *n_out,
                               double *value_out);
 
+/* ------------------------------------------------------------------ proven outcomes for stored plies
+ * (an extension of the store; with azh_samples_prove never called, every call, launch and byte above is what it was.)  The
+ * alpha-beta search proves stored plies won or lost, and the minibatch kernels train a proven ply's value on the proven outcome
+ * instead of the game's result (what tablebase rescoring does for lc0's training data).  training.train drives it under
+ * train.py --prove-depth; DESIGN.md section 4, "Proven outcomes for stored plies".
+ *
+ * The definition, stated once.  The position of stored ply q of game g is (x, o, turn = q & 1, the game's stored wall mask, 0
+ * for a game without one).  (move, value, depth_done, nodes) are exactly what azh_alphabeta_search reports for that position at
+ * (depth, node_budget): the same iterative deepening, the same rule that abandons an iteration under a budget, the same node
+ * count.
+ *   proof(q) = value if |value| >= 1000, else 0.  Sound at any completed iteration: material scores are at most 49 in
+ *   magnitude, so a value of 1000 or more is a forced adjudicated end.  A stored position that is already finished is proven by
+ *   rule 1, and its move is 0xFFFF.
+ *   ELIGIBLE are the plies training.reanalyse_plan calls eligible — the candidate plies (every ply, or the FULL ones of a game
+ *   that has "full") of games [first_game, first_game + n_games) that are neither PASS nor BAD — which also have proof == 0.
+ *   They are visited in ascending (game, ply) order.  A proof, once set, is never removed or changed: a later call skips the ply.
+ *
+ * azh_samples_prove searches every eligible ply, one wave per ply on the store's own records, and writes this call's counts to
+ * stats_out: VISITED the eligible plies searched, WINS and LOSSES the new proofs by sign, CONTRADICTED the new proofs whose sign
+ * differs from the mover's z ((game word 2 & 0xFF) == 1 + (ply & 1) -> +1, else -1), RETARGETED the policy targets replaced,
+ * NODES the sum of the searches' node counts.
+ * Storage.  Proofs live in an array of their own, one 16-bit word per ply the store can hold, allocated by the first call that
+ * commits; beside it lie the move and the completed iteration of every ply's LAST search (0xFFFF and 0 before one), which
+ * azh_samples_proofs reads back from the device like azh_samples_read_plies: proof_out, move_out, depth_done_out [n].
+ * Minibatches.  Once the array exists, the four gather / draw-gather kernels write proof > 0 ? 1.0f : -1.0f as the value target
+ * of a sample whose ply has proof != 0, whatever z, value_blend and the stored value say.  Features, policy, the auxiliary
+ * outputs and the draws do not change; without the array the kernels write what they wrote.
+ * retarget_wins != 0: each ply newly proven in this call with proof > 0 and move != 0xFFFF gets the single policy pair (the
+ * engine's policy index of move, 1.0f), appended by azh_samples_retarget's placement rule in visiting order: first_target = T +
+ * (the number of such plies before it), count 1, the old pairs stay unreferenced, flag byte and stored value untouched,
+ * azh_samples_counts reports the new total.  Rule 1 scores 1000 + the remaining depth, so the quickest win is the move.  Proven
+ * losses keep their recorded policy.
+ * Refusals, in this order, each changing nothing: -1 a null argument or a game range outside the store; -2 the limits of
+ * azh_alphabeta_search (depth 1 .. AZH_ALPHABETA_MAX_DEPTH, node_budget 0 up to AZH_ALPHABETA_UNBOUNDED_DEPTH only, else at
+ * least AZH_MAX_MOVES); -6 with retarget_wins, the new pairs do not fit in the target capacity.  Hence two phases: every search
+ * goes to scratch memory, in launches of 16384 plies, the host counts, and only then one kernel commits proofs and pairs.
+ * Streams as azh_samples_retarget: the call waits for the store's stream, runs on it and returns after completion; it must not
+ * run while a minibatch call is in flight on another stream; the surprise kept by azh_samples_surprise is stale for retargeted
+ * plies. */
+enum { AZH_PROOF_VISITED, AZH_PROOF_WINS, AZH_PROOF_LOSSES, AZH_PROOF_CONTRADICTED, AZH_PROOF_RETARGETED, AZH_PROOF_NODES,
+       AZH_SAMPLES_PROOF_STAT_COUNT };
+int azh_samples_prove(azh_samples *s, int64_t first_game, int64_t n_games, int depth, uint64_t node_budget, int retarget_wins,
+                      uint64_t *stats_out /* [AZH_SAMPLES_PROOF_STAT_COUNT], this call's */);
+int azh_samples_proofs(azh_samples *s, int n, const int32_t *plies /* [n][2] (game, ply) */, int32_t *proof_out,
+                       uint16_t *move_out, int32_t *depth_done_out);
+
 /* ------------------------------------------------------------------ reference ABI
  * The four symbols link.py:6-32 binds (cpp/self_play_client.cpp:683-749), with
  * the worker threads replaced by GPU game slots: `thread_count` concurrent

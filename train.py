@@ -22,6 +22,11 @@ nothing changes.
 first step (--reanalyse-visits V each, --reanalyse-slots positions per round) and trains on the new visit distributions and
 search values (MuZero's Reanalyse; an extension; implies --device-samples, needs --old-path).  F = 0 (the default): nothing
 changes.
+--prove-depth D runs the device's depth-D material alpha-beta search on the training games' stored plies before the first step
+(--prove-nodes N nodes at most per ply; 0, the default, means no limit and is accepted up to depth 3): a ply the search proves
+won or lost trains the value head on that outcome instead of the game's result, and with --prove-policy a ply proven won takes the
+winning move as its policy target (what tablebase rescoring does for lc0; an extension; implies --device-samples, needs no
+network).  D = 0 (the default): nothing changes.
 """
 from ataxxzero_amd import training
 from ataxxzero_amd.cli import flag, parse, switch
@@ -65,6 +70,12 @@ OPTIONS = [
     flag("--reanalyse-slots", "positions searched per round", type=int, default=4096, metavar="G"),
     flag("--reanalyse-dtype", "tower precision of the reanalysis searches", default="bf16", choices=["f32", "bf16", "f16"],
          metavar="DTYPE"),
+    flag("--prove-depth", "depth D in 1 .. 8 of an alpha-beta search of the training games' stored plies before the first step; "
+                          "a ply it proves won or lost trains the value head on the proven outcome (extension; implies "
+                          "--device-samples; 0: off)", type=int, default=0, metavar="D"),
+    flag("--prove-nodes", "node budget of that search per ply; 0: no limit, depth 1 .. 3 only, otherwise at least 256",
+         type=int, default=0, metavar="N"),
+    switch("--prove-policy", "with --prove-depth: a ply proven won takes the winning move as its policy target"),
 ]
 
 if __name__ == "__main__":
@@ -89,6 +100,17 @@ if __name__ == "__main__":
         args.device_samples = True
     else:                                   # off: as above
         del args.reanalyse_fraction, args.reanalyse_visits, args.reanalyse_slots, args.reanalyse_dtype
+    proofs = {}
+    if args.prove_depth != 0:
+        why = training.prove_refusal(args.prove_depth, args.prove_nodes)
+        if why:
+            raise SystemExit("train.py: " + why)
+        proofs = {"prove_depth": args.prove_depth, "prove_nodes": args.prove_nodes, "prove_policy": args.prove_policy}
+        args.device_samples = True
+    elif args.prove_nodes != 0 or args.prove_policy:
+        raise SystemExit("train.py: --prove-nodes and --prove-policy need --prove-depth")
+    else:                                   # off: as above
+        del args.prove_depth, args.prove_nodes, args.prove_policy
     aux = {"aux_ownership": args.aux_ownership, "aux_score": args.aux_score, "aux_reply": args.aux_reply}
     if min(aux.values()) < 0.0:
         raise SystemExit("train.py: --aux-ownership, --aux-score and --aux-reply take weights >= 0")
@@ -99,4 +121,4 @@ if __name__ == "__main__":
     training.train(args.games, args.old_path, args.new_path, steps=args.steps, minibatch_size=args.minibatch_size,
                    learning_rate=args.learning_rate, reference_bn_affine=args.reference_bn_affine, value_blend=args.value_blend,
                    device_samples=args.device_samples or args.device_draws, device_draws=args.device_draws, **surprise, **aux,
-                   **reanalysis)
+                   **reanalysis, **proofs)
