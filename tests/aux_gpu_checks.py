@@ -3,51 +3,18 @@ gives: `python -m tests.aux_gpu_checks OUT.json` runs every check and writes {na
 in a device error nothing more is run.  Stores of at most a dozen games, launches of at most 130 samples."""
 import json
 import random
-import sys
-import traceback
 
 import numpy as np
 import torch
 
 from ataxxzero_amd import link, training
 from tests import aux_fixtures as fx
-from tests import aux_reference as ar
+from tests import fresh_process
 from tests import walls_fixtures as wf
+from tests.store_checks import host, move_text, restated, same, store_of
 
 F32 = np.float32
-NAMES = ("features", "policy", "value", "ownership", "score", "reply", "aux_weight")
 PASS, FULL = link.SAMPLES_PLY_PASS, link.SAMPLES_PLY_FULL
-
-
-def host(out):
-    return tuple(t.cpu().numpy() for t in out)
-
-
-def same(got, want, what=""):
-    assert len(got) == len(want), what
-    for g, w, name in zip(got, want, NAMES):
-        assert g.dtype == w.dtype == F32 and g.shape == w.shape, (what, name, g.shape, w.shape)
-        assert g.tobytes() == w.tobytes(), (what, name)
-
-
-def restated(entries, draws, blend=0.0):
-    """The seven arrays for draws (game, ply, symmetry): the first three sample by sample with the host pipeline's own functions
-    (tests/samples_gpu_checks.py::reference_for, with the walls), the four auxiliary ones from tests/aux_reference.py."""
-    feats, pols, vals = [], [], []
-    for g, ply, s in draws:
-        e = entries[g]
-        mover = 1 + ply % 2
-        feats.append(training.apply_symmetry(s, training.board_to_features(e["boards"][ply], mover, e.get("blockers"))))
-        pols.append(training._policy_target(e, ply, s))
-        vals.append([training._value_target(e, ply, mover, blend)])
-    first = np.asarray(feats, dtype=F32), np.asarray(pols, dtype=F32), np.asarray(vals, dtype=F32)
-    return first + ar.batch(entries, draws)
-
-
-def store_of(arrays, spare=0):
-    store = link.SampleStore(len(arrays.games) + spare, len(arrays.ply_flags) + spare, len(arrays.target_index) + spare)
-    store.add_arrays(arrays)
-    return store
 
 
 def parity_entries():
@@ -184,8 +151,7 @@ def check_edges_of_the_wave_for_the_reply_scatter():
     store = store_of(arrays)
     assert store.counts()["bad_plies"] == 0
     _, policy_to = training._symmetry_tables()
-    name = lambda sq: "abcdefg"[sq % 7] + "1234567"[sq // 7]
-    real = [training._flat_policy_index(name(b) if a == b else name(a) + name(b)) for a in range(49) for b in range(49)
+    real = [training._flat_policy_index(move_text(a | b << 8)) for a in range(49) for b in range(49)
             if a == b or max(abs(a % 7 - b % 7), abs(a // 7 - b // 7)) == 2]
     assert len(set(real)) == 529
     for s in range(8):
@@ -316,24 +282,5 @@ CHECKS = [check_parity_from_game_lines, check_parity_from_records, check_parity_
           check_no_owners_anywhere, check_ingest_refusals]
 
 
-def main(path):
-    link.require_gpu()
-    link.require_torch_runtime()
-    results = {}
-    for check in CHECKS:
-        try:
-            check()
-            results[check.__name__] = "ok"
-        except Exception:
-            results[check.__name__] = traceback.format_exc()
-            text = results[check.__name__].lower()
-            if ("hip" in text and "failed at" in text) or "illegal memory access" in text or "hip error" in text:
-                break                                  # a device error: nothing more runs on this GPU
-        with open(path, "w") as f:
-            json.dump(results, f, indent=1)
-    with open(path, "w") as f:
-        json.dump(results, f, indent=1)
-
-
 if __name__ == "__main__":
-    main(sys.argv[1])
+    fresh_process.main(CHECKS)

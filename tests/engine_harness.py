@@ -1,7 +1,9 @@
-"""What the GPU search tests share: the late start position, a cached random net, one iteration of the step-wise API, dumps
-of the engines' states and trees and their comparison, the staged records, the generator's command line, the wide roots, the
-resign rule recounted from records, and the lock step of a device engine with the CPU oracle.  The engines themselves differ
-from module to module and stay there.  Importing this touches no device."""
+"""What the GPU search tests share: the late start position, a cached random net, the engine of the root-mode tests, one
+iteration of the step-wise API, dumps of the engines' states and trees and their comparison, the staged records, the
+generator's command line, the wide roots, the raw mark's invariant, the resign rule recounted from records, and the lock step
+of a device engine with the CPU oracle.  The root-mode tests (playout cap, forced playouts, Gumbel, temperature, resign, hostile
+evaluations) build their engines with root_engine; the tests that start from other positions (the random symmetry, the
+leaf-parallel search: tests/leaf_lockstep.py) keep builders of their own.  Importing this touches no device."""
 import functools
 import gzip
 import json
@@ -19,6 +21,7 @@ from tests.helpers import synthetic_evals
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 424242
+C_PUCT, ALPHA = 1.0, 0.15          # root_engine's exploration constant and Dirichlet alpha
 
 # Positions with many legal moves, found on the CPU with the oracle's uniformly random play from the plain start position
 # (x5o/7/7/7/7/7/o5x x, no blockers): the widest with at most 128 moves (128) and the widest of all (157) in 20,000 games.
@@ -53,6 +56,35 @@ START = late_start()
 def net(blocks=1, seed=3):
     conv, bn = model.random_init(blocks, 128, seed=seed, perturb_bn=True)
     return link.Net(conv, bn)
+
+
+def root_engine(games, visits, *, weight, seed=SEED, flags=0, max_plies=400, edges_per_node=96, cap=None, forced=None,
+                gumbel=None, temperature=None, resign=None, symmetry=False, K=1):
+    """An engine at START (no blockers, C_PUCT, ALPHA) with the root modes asked for, each given as its setter
+    takes it: cap (fast visits, full per 65536), forced k, gumbel (m, c_visit, c_scale), temperature (move table, root table),
+    resign (q below, consecutive, play-through per 65536).  The setters are called in one order, resign last, so where a mode
+    refuses another it is always the same call that raises.  `weight` has no default: the root noise decides what a test of a
+    root mode sees, so every caller says it."""
+    x, o, turn = START
+    cfg = link.Config(games=games, visits=visits, max_plies=max_plies, edges_per_node=edges_per_node, c_puct=C_PUCT,
+                      dirichlet_alpha=ALPHA, dirichlet_weight=weight, start_turn=turn, seed=seed, start_x=x, start_o=o, blockers=0,
+                      flags=flags)
+    e = link.Engine(cfg)
+    if cap is not None:
+        e.set_playout_cap(*cap)
+    if forced is not None:
+        e.set_forced_playouts(forced)
+    if temperature is not None:
+        e.set_temperature(*temperature)
+    if symmetry:
+        e.set_random_symmetry(True)
+    if K > 1:
+        e.set_leaf_batch(K, 1)
+    if gumbel is not None:
+        e.set_gumbel(*gumbel)
+    if resign is not None:
+        e.set_resign(*resign)
+    return e
 
 
 def step(e, evals=helpers.synthetic_evals_distinct, K=1):
@@ -252,6 +284,20 @@ def check_marks(ge, games):
         # no mark outside the nodes' ranges either (every edge belongs to exactly one node)
         assert int(mark.sum()) <= len(info)
     return marked_nodes, high
+
+
+def root_mark(e, g=0):
+    """check_marks' invariant at the root of game g alone -> the root edge that carries the mark, or None"""
+    _, info, _, _ = e.tree(g)
+    raw = e.tree_raw(g)
+    first, m = int(info[0, 0]), int(info[0, 1] & 0xFFFF)
+    idx = np.nonzero((raw[first:first + m, 0] >> 31) != 0)[0]
+    assert len(idx) <= 1, idx.tolist()
+    if len(idx):
+        z, w = int(raw[first + idx[0], 2]), int(raw[first + idx[0], 3])
+        assert m <= 128 and (z >> 16) != 0xFFFF and (w >> 31) == 0 and 1 <= ((w >> 23) & 0xFF) <= 128, (m, hex(z), hex(w))
+        return int(idx[0])
+    return None
 
 
 def _wide_roots():

@@ -1,21 +1,16 @@
 """The device checks of tests/test_gpu_prove.py, run in a process of their own (as tests/reanalyse_gpu_checks.py, and for its
 reason: a SampleStore needs torch imported before the library is loaded).  `python -m tests.prove_gpu_checks OUT.json` runs
 every check and writes {name: "ok" | traceback}; after a check that ends in a device error nothing more is run."""
-import json
-import os
-import sys
-import traceback
-
 import numpy as np
 import torch
 
 from ataxxzero_amd import link
 from tests import alphabeta_cases as ac
 from tests import alphabeta_reference as ab
+from tests import fresh_process, store_checks
 from tests import rules_reference as rr
-from tests.helpers import GOLDEN
-from tests.reanalyse_gpu_checks import all_pairs, eligible_pairs, host
 from tests.reanalyse_reference import policy_index
+from tests.store_checks import all_pairs, eligible_pairs, host, store_of
 
 WIN, NO_MOVE = link.ALPHABETA_WIN, 0xFFFF
 LAST = 13               # the plies of each golden game the restatement is run on
@@ -26,8 +21,7 @@ _cache = {}
 
 
 def golden_entries():
-    with open(os.path.join(GOLDEN, "train_entries.json")) as f:
-        entries = json.load(f)
+    entries = store_checks.golden_entries()
     rng = np.random.default_rng(11)
     for e in entries[::2]:                          # every other game carries the search's values: value_blend has a say
         e["values"] = rng.uniform(-1.0, 1.0, len(e["boards"])).tolist()
@@ -35,9 +29,7 @@ def golden_entries():
 
 
 def golden_store(spare_targets=0, room=0):
-    a = link.entries_to_arrays(golden_entries())
-    store = link.SampleStore(len(a.games) + room, len(a.ply_flags) + 300 * room, len(a.target_index) + spare_targets)
-    store.add_arrays(a)
+    store = store_of(link.entries_to_arrays(golden_entries()), (room, 300 * room, spare_targets))
     assert store.counts()["bad_plies"] == 0 and store.counts()["games"] == 6
     return store
 
@@ -336,26 +328,5 @@ def check_refusals():
 CHECKS = [check_proofs_are_the_searchs, check_deep_rows_walls_budgets, check_minibatches, check_monotone, check_refusals]
 
 
-def main(path, only=None):
-    link.require_gpu()
-    link.require_torch_runtime()
-    results = {}
-    for check in CHECKS:
-        if only and check.__name__ not in only:
-            continue
-        try:
-            check()
-            results[check.__name__] = "ok"
-        except Exception:
-            results[check.__name__] = traceback.format_exc()
-            text = results[check.__name__].lower()
-            if ("hip" in text and "failed at" in text) or "illegal memory access" in text or "hip error" in text:
-                break                                  # a device error: nothing more runs on this GPU
-        with open(path, "w") as f:
-            json.dump(results, f, indent=1)
-    with open(path, "w") as f:
-        json.dump(results, f, indent=1)
-
-
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2:])
+    fresh_process.main(CHECKS)

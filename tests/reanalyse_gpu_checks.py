@@ -2,32 +2,20 @@
 reason: a SampleStore needs torch imported before the library is loaded).  `python -m tests.reanalyse_gpu_checks OUT.json` runs
 every check and writes {name: "ok" | traceback}; after a check that ends in a device error nothing more is run."""
 import json
-import sys
-import traceback
 
 import numpy as np
 import torch
 
 from ataxxzero_amd import link, model, selfplay, training
 from tests import aux_reference as ar
+from tests import fresh_process
 from tests import reanalyse_reference as ref
-from tests.aux_gpu_checks import restated
 from tests.samples_fixtures import random_record
+from tests.store_checks import all_pairs, eligible_pairs, first_three, host, move_text, restated, same
 
 F32 = np.float32
 PASS, FULL, BAD = link.SAMPLES_PLY_PASS, link.SAMPLES_PLY_FULL, link.SAMPLES_PLY_BAD
 PICKED = 600            # more than two workgroups of the 256-wide scan, and no multiple of it
-
-
-def host(out):
-    return tuple(t.cpu().numpy() for t in out)
-
-
-def move_text(mv):
-    def name(sq):
-        return "abcdefg"[sq % 7] + "1234567"[sq // 7]
-    frm, to = mv & 0xFF, mv >> 8
-    return name(to) if frm == to else name(frm) + name(to)
 
 
 def fixture_games(seed=7):
@@ -40,24 +28,12 @@ def fixture_games(seed=7):
     return recs, entries, link.pack_records(np.concatenate(recs))
 
 
-def all_pairs(store):
-    games, _ = store.mirror()
-    return np.array([(g, p) for g in range(len(games)) for p in range(int(games[g][1]))], dtype=np.int32)
-
-
 def snapshot(store, pairs=None):
     """What the store holds for the plies (all of them by default), ply by ply, as bytes."""
     pairs = all_pairs(store) if pairs is None else np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
     boards, values, flags, start, index, weight = store.read_plies(pairs)
     return [(boards[i].tobytes(), values[i].tobytes(), int(flags[i]), index[start[i]:start[i + 1]].tobytes(),
              weight[start[i]:start[i + 1]].tobytes()) for i in range(len(pairs))]
-
-
-def eligible_pairs(store):
-    games, flags = store.mirror()
-    cand, count, _, _ = store.ply_cum()
-    return [(g, int(cand[int(games[g][0]) + k])) for g in range(len(games)) for k in range(int(count[g]))
-            if not flags[int(games[g][0]) + int(cand[int(games[g][0]) + k])] & (PASS | BAD)]
 
 
 def upload(records):
@@ -84,24 +60,6 @@ def apply_to_entries(entries, pairs, records, status):
         entries[g]["dists"][p] = {move_text(mv): float(w) for mv, w in zip(moves, weight)}
         if "values" in entries[g]:
             entries[g]["values"][p] = value
-
-
-def first_three(entries, draws, blend):
-    feats, pols, vals = [], [], []
-    for g, ply, s in draws:
-        e = entries[g]
-        mover = 1 + ply % 2
-        feats.append(training.apply_symmetry(s, training.board_to_features(e["boards"][ply], mover, e.get("blockers"))))
-        pols.append(training._policy_target(e, ply, s))
-        vals.append([training._value_target(e, ply, mover, blend)])
-    return np.asarray(feats, dtype=F32), np.asarray(pols, dtype=F32), np.asarray(vals, dtype=F32)
-
-
-def same_arrays(got, want, what=""):
-    assert len(got) == len(want), what
-    for k, (g, w) in enumerate(zip(got, want)):
-        assert g.dtype == w.dtype and g.shape == w.shape, (what, k, g.shape, w.shape)
-        assert g.tobytes() == w.tobytes(), (what, k)
 
 
 # ---------------------------------------------------------------- the checks
@@ -279,7 +237,7 @@ def check_refusals():
                 [(2, p, 5) for p in range(64) if (2, p) not in {tuple(q) for q in pairs_all.tolist()} and
                  not flags[2 * 64 + p] & (PASS | BAD)]
         for blend in (0.0, 0.5):
-            same_arrays(host(store.gather(draws, blend)), first_three(lines, draws, blend), blend)
+            same(host(store.gather(draws, blend)), first_three(lines, draws, blend), blend)
         store.close()
 
 
@@ -306,9 +264,9 @@ def check_minibatch_parity():
         draws = [(g, p, s) for g, p in picks]
         for blend in (0.0, 0.5):
             want = first_three(entries, draws, blend)
-            same_arrays(host(store.gather(draws, blend)), want, (s, blend))
+            same(host(store.gather(draws, blend)), want, (s, blend))
             got = host(store.gather(draws, blend, aux=True))
-            same_arrays(got[:3], want, (s, blend, "aux"))
+            same(got[:3], want, (s, blend, "aux"))
             for k, (g, p, _) in enumerate(draws):                       # the reply: ply p + 1's target as it is now
                 e = entries[g]
                 present = p + 1 < len(e["boards"]) and ("full" not in e or bool(e["full"][p + 1]))
@@ -431,8 +389,8 @@ def whole_path(starts, picks, seed):
         draws = [(g, p, s) for g, p in picks_]
         for blend in (0.0, 0.5):
             want = restated(entries, draws, blend)
-            same_arrays(host(store.gather(draws, blend, aux=True)), want, (s, blend))
-            same_arrays(host(store.gather(draws, blend)), want[:3], (s, blend))
+            same(host(store.gather(draws, blend, aux=True)), want, (s, blend))
+            same(host(store.gather(draws, blend)), want[:3], (s, blend))
     # the surprise of the new targets: azh_samples_surprise_host on the new pairs in stored (edge) order
     n_plies = store.counts()["plies"]
     logits = (3.0 * np.random.default_rng(4).standard_normal((n_plies, 833))).astype(F32)
@@ -464,26 +422,5 @@ def check_walls():
 CHECKS = [check_read_plies, check_synthetic_reports, check_refusals, check_minibatch_parity, check_whole_path, check_walls]
 
 
-def main(path, only=None):
-    link.require_gpu()
-    link.require_torch_runtime()
-    results = {}
-    for check in CHECKS:
-        if only and check.__name__ not in only:
-            continue
-        try:
-            check()
-            results[check.__name__] = "ok"
-        except Exception:
-            results[check.__name__] = traceback.format_exc()
-            text = results[check.__name__].lower()
-            if ("hip" in text and "failed at" in text) or "illegal memory access" in text or "hip error" in text:
-                break                                  # a device error: nothing more runs on this GPU
-        with open(path, "w") as f:
-            json.dump(results, f, indent=1)
-    with open(path, "w") as f:
-        json.dump(results, f, indent=1)
-
-
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2:])
+    fresh_process.main(CHECKS)

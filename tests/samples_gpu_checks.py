@@ -1,34 +1,23 @@
 """The device checks of tests/test_gpu_samples.py, run in a process of their own: a SampleStore writes torch's tensors on
 torch's streams, so torch must be imported before the library is loaded (link.require_torch_runtime) — in a pytest process
 that has run other device tests it is the other way round.  `python -m tests.samples_gpu_checks OUT.json` runs every check
-and writes {name: "ok" | traceback}; after a check that ends in a device error nothing more is run."""
+and writes {name: "ok" | traceback}; after a check that ends in a device error nothing more is run (tests/fresh_process.py).
+What the store's checks modules share is in tests/store_checks.py."""
 import ctypes
 import json
 import random
-import sys
-import traceback
 
 import numpy as np
 import torch
 
 from ataxxzero_amd import link, model, training
-from tests import aux_fixtures, helpers
+from tests import aux_fixtures, fresh_process
 from tests.samples_fixtures import MOVES
+from tests.store_checks import first_three, golden_entries, host, move_text, same, store_of_entries
 
 F32 = np.float32
 BOARD = [(c * 7 + c // 5) % 3 for c in range(49)]            # no symmetry maps it onto itself
-
-
-def name_of(sq):
-    return "abcdefg"[sq % 7] + "1234567"[sq // 7]
-
-
-MOVE_TEXT = [name_of(b) if a == b else name_of(a) + name_of(b) for a, b in MOVES]
-
-
-def golden_entries():
-    with open(helpers.GOLDEN + "/train_entries.json") as f:
-        return json.load(f)
+MOVE_TEXT = [move_text(a | b << 8) for a, b in MOVES]
 
 
 def synthetic_entries(seed=1, games=12):
@@ -71,41 +60,12 @@ def synthetic_entries(seed=1, games=12):
     return out
 
 
-def store_of(entries, spare=0):
-    a = link.entries_to_arrays(entries)
-    store = link.SampleStore(len(a.games) + spare, len(a.ply_flags) + spare, len(a.target_index) + spare)
-    store.add_arrays(a)
-    return store
-
-
-def host(out):
-    return tuple(t.cpu().numpy() for t in out)
-
-
-def same(got, want):
-    for g, w, what in zip(got, want, ("features", "policy", "value")):
-        assert g.dtype == w.dtype == F32 and g.shape == w.shape, what
-        assert g.tobytes() == w.tobytes(), what
-
-
-def reference_for(entries, draws, blend=0.0):
-    """make_minibatch_reference's arrays for given draws (game, ply, symmetry), sample by sample with its own functions."""
-    feats, pols, vals = [], [], []
-    for g, ply, s in draws:
-        e = entries[g]
-        mover = 1 + ply % 2
-        feats.append(training.apply_symmetry(s, training.board_to_features(e["boards"][ply], mover)))
-        pols.append(training._policy_target(e, ply, s))
-        vals.append([training._value_target(e, ply, mover, blend)])
-    return np.asarray(feats, dtype=F32), np.asarray(pols, dtype=F32), np.asarray(vals, dtype=F32)
-
-
 # ---------------------------------------------------------------- the checks
 
 def check_reference_parity():
     entries = golden_entries() + synthetic_entries()
     assert any("random_ply" in e for e in entries) and any("dists" not in e for e in entries)
-    store = store_of(entries)
+    store = store_of_entries(entries)
     c = store.counts()
     assert c["games"] == len(entries) and c["plies"] == sum(len(e["boards"]) for e in entries)
     for blend in (0.0, 0.5):
@@ -129,7 +89,7 @@ def check_reference_parity():
 def check_every_index_under_every_symmetry():
     assert len(MOVE_TEXT) == len(set(MOVE_TEXT)) == 529
     entry = {"boards": [BOARD] * 529, "moves": MOVE_TEXT, "result": 2}
-    store = store_of([entry])
+    store = store_of_entries([entry])
     seen = set()
     for s in range(8):
         feats, pols, vals = host(store.gather([(0, p, s) for p in range(529)]))
@@ -153,7 +113,7 @@ def check_edges_of_the_wave():
         w = rng.dirichlet(np.ones(k))
         entries.append({"boards": [[int(v) for v in rng.integers(0, 3, size=49)]], "moves": [chosen[0]], "result": 1,
                         "dists": [{m: float(x) for m, x in zip(chosen, w)}]})
-    store = store_of(entries)
+    store = store_of_entries(entries)
     assert store.counts()["bad_plies"] == 0 and store.counts()["targets"] == 1 + 63 + 64 + 65 + 128 + 529
     for size in (1, 63, 64, 65, 257):
         random.seed(size)
@@ -219,7 +179,7 @@ def drawable_mix():
 
 def check_device_draws():
     entries = drawable_mix()
-    store = store_of(entries)
+    store = store_of_entries(entries)
     games, flags = store.mirror()
     assert store.counts()["bad_plies"] > 0
     n, first, count = 257, 10, len(entries) - 10
@@ -235,7 +195,7 @@ def check_device_draws():
             assert not f & (link.SAMPLES_PLY_PASS | link.SAMPLES_PLY_BAD)
             assert games[g][3] == ply if games[g][3] else (f & link.SAMPLES_PLY_FULL or not games[g][2] & link.SAMPLES_GAME_HAS_FULL)
         same(out, host(store.gather(draws[:, :3], 0.5)))
-        same(out, reference_for(entries, draws[:, :3].tolist(), 0.5))
+        same(out, first_three(entries, draws[:, :3].tolist(), 0.5))
     assert store.status() == 0
     # a range of undrawable games only: zeros, counted, and the call ends
     out = store.outputs(n)
@@ -250,7 +210,7 @@ def check_device_draws():
 
 def check_stream_and_reuse():
     entries = golden_entries() + synthetic_entries()
-    store = store_of(entries)
+    store = store_of_entries(entries)
     rng = np.random.default_rng(8)
 
     def some_draws(n):
@@ -271,7 +231,7 @@ def check_stream_and_reuse():
         sums = [t.sum(dim=tuple(range(1, t.dim()))) for t in out_a + out_b]      # consumed with no host wait in between
         doubled = out_b[1] * 2
     side.synchronize()
-    want_a, want_b = reference_for(entries, a, 0.5), reference_for(entries, b, 0.5)
+    want_a, want_b = first_three(entries, a, 0.5), first_three(entries, b, 0.5)
     same(host(out_a), want_a)
     same(host(out_b), want_b)
     assert doubled.cpu().numpy().tobytes() == (want_b[1] * 2).tobytes()
@@ -314,7 +274,7 @@ def check_capacity():
 def check_bad_ply():
     entries = synthetic_entries(seed=4, games=3)
     bad = {"boards": [BOARD], "moves": ["a1"], "result": 1, "dists": [{"a1": 0.25, "b2": 0.25}]}
-    store = store_of(entries + [bad])
+    store = store_of_entries(entries + [bad])
     assert store.counts()["bad_plies"] == 1
     for fn in (lambda: training.make_minibatch_reference([bad], 4), lambda: training.make_minibatch([bad], 4),
                lambda: training.make_minibatch_device(store, 3, 1, 4)):
@@ -390,24 +350,5 @@ CHECKS = [check_reference_parity, check_every_index_under_every_symmetry, check_
           check_device_draws, check_stream_and_reuse, check_capacity, check_bad_ply, check_argument_refusals]
 
 
-def main(path):
-    link.require_gpu()
-    link.require_torch_runtime()
-    results = {}
-    for check in CHECKS:
-        try:
-            check()
-            results[check.__name__] = "ok"
-        except Exception:
-            results[check.__name__] = traceback.format_exc()
-            text = results[check.__name__].lower()
-            if ("hip" in text and "failed at" in text) or "illegal memory access" in text or "hip error" in text:
-                break                                  # a device error: nothing more runs on this GPU
-        with open(path, "w") as f:
-            json.dump(results, f, indent=1)
-    with open(path, "w") as f:
-        json.dump(results, f, indent=1)
-
-
 if __name__ == "__main__":
-    main(sys.argv[1])
+    fresh_process.main(CHECKS)

@@ -1,14 +1,16 @@
 """The in-process hand-off from a pooled engine to the sample store, in a process of its own (the store wants torch's HIP runtime
-loaded before the library): run by tests/test_gpu_start_pool.py as `python -m tests.start_pool_store_check`, prints "ok"."""
+loaded before the library): run by tests/test_gpu_start_pool.py as `python -m tests.start_pool_store_check OUT.json`
+(tests/fresh_process.py)."""
 import numpy as np
 import torch  # noqa: F401  (its HIP runtime first: link.require_torch_runtime)
 
 from ataxxzero_amd import link
 from tests import engine_harness as eh
+from tests import fresh_process
 from tests import start_pool_fixtures as spf
 
 
-def main():
+def check_records_enter_the_store_with_their_own_masks():
     pool, net = spf.entries(), eh.net()
     e = spf.pooled_engine(pool, 6, 8)
     words = np.zeros(0, np.uint32)
@@ -41,8 +43,9 @@ def main():
     assert aux.counts()["games"] == len(recs)
     store.close()
     aux.close()
-    print("ok")
 
+
+CHECKS = [check_records_enter_the_store_with_their_own_masks]
 
 if __name__ == "__main__":
-    main()
+    fresh_process.main(CHECKS)

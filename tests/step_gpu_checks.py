@@ -8,16 +8,14 @@ conventions (moving variance, eps, momentum) are held to the float64 restatement
 seam between the HIP minibatch kernel's seven outputs and the loss.  The allowance is 8 x d32 per quantity (d32:
 tests/test_train_step_host.py) — twice the CPU's factor, for atomics and algorithm choice in the backend's reductions — under the
 same condition: below a quarter of what separates the two moving-variance rules."""
-import json
 import os
-import sys
 import tempfile
-import traceback
 
 import numpy as np
 import torch
 
-from ataxxzero_amd import link, training
+from ataxxzero_amd import training
+from tests import fresh_process
 from tests import step_reference as ref
 from tests import test_train_step_host as host
 
@@ -74,24 +72,5 @@ def check_device_equals_cpu_to_rounding():
 CHECKS = [check_step_on_device, check_train_through_the_store, check_device_equals_cpu_to_rounding]
 
 
-def main(path):
-    link.require_gpu()
-    link.require_torch_runtime()
-    results = {"measured": MEASURED}
-    for check in CHECKS:
-        try:
-            check()
-            results[check.__name__] = "ok"
-        except Exception:
-            results[check.__name__] = traceback.format_exc()
-            text = results[check.__name__].lower()
-            if ("hip" in text and "failed at" in text) or "illegal memory access" in text or "hip error" in text:
-                break                                  # a device error: nothing more runs on this GPU
-        with open(path, "w") as f:
-            json.dump(results, f, indent=1)
-    with open(path, "w") as f:
-        json.dump(results, f, indent=1)
-
-
 if __name__ == "__main__":
-    main(sys.argv[1])
+    fresh_process.main(CHECKS, extra={"measured": MEASURED})

@@ -1,17 +1,14 @@
 """The device checks of tests/test_gpu_surprise.py, run in a process of their own for the reason tests/samples_gpu_checks.py
 gives: torch's runtime must be loaded first.  `python -m tests.surprise_gpu_checks OUT.json` runs every check and writes
 {name: "ok" | traceback}; after a check that ends in a device error nothing more is run."""
-import json
-import sys
-import traceback
-
 import numpy as np
 import torch
 
 from ataxxzero_amd import link, model
 from oracle import net_oracle
+from tests import fresh_process
 from tests import surprise_reference as ref
-from tests.samples_gpu_checks import host, same
+from tests.store_checks import arrays_of, host, same, store_of
 from tests.surprise_reference import BAD, FULL, PASS
 from tests.surprise_reference import edge_specs
 
@@ -19,26 +16,9 @@ F32 = np.float32
 HOSTILE = (3e38, -3e38, np.inf, -np.inf, np.nan)
 
 
-def arrays_of(games):
-    """games: [[(mover stones, opponent stones, flags, target indices, target weights)] per ply] -> link.SampleArrays; the mover
-    of ply p is x on even plies."""
-    rows, boards, flags, start, index, weight = [], [], [], [0], [], []
-    for plies in games:
-        rows.append((len(flags), len(plies), 1, 0))
-        for p, (mover, opponent, f, t_index, t_weight) in enumerate(plies):
-            boards.append((mover, opponent) if p % 2 == 0 else (opponent, mover))
-            flags.append(f)
-            index.extend(int(i) for i in t_index)
-            weight.extend(float(w) for w in t_weight)
-            start.append(len(index))
-    return link.SampleArrays(rows, np.array(boards, dtype=np.uint64), flags, np.zeros(len(flags)), start,
-                             np.array(index, dtype=np.uint16), np.array(weight, dtype=F32))
-
-
-def store_of_arrays(a, spare=0):
-    store = link.SampleStore(len(a.games) + spare, len(a.ply_flags) + spare, len(a.target_index) + spare)
-    store.add_arrays(a)
-    return store
+def unwalled(games):
+    """games: [[ply] per game] as tests/store_checks.py::arrays_of takes them: every game without a wall mask"""
+    return [(None, plies) for plies in games]
 
 
 def seam_plies():
@@ -75,8 +55,8 @@ def seam_plies():
 def check_from_logits_bit_exact():
     plies = seam_plies()
     games = [plies[:7], plies[7:8], plies[8:]]               # three games: the mover follows the ply's parity in its game
-    a = arrays_of(games)
-    store = store_of_arrays(a)
+    a = arrays_of(unwalled(games))
+    store = store_of(a)
     flags = store.mirror()[1]
     assert store.counts()["bad_plies"] == 1 and int(flags[9]) & PASS and int(flags[10]) & BAD
     rng = np.random.default_rng(23)
@@ -125,7 +105,7 @@ def check_net_surprise():
         k = int(rng.integers(1, min(len(legal), 30) + 1))
         plies.append((mover, opponent, 0, rng.choice(legal, size=k, replace=False), rng.dirichlet(np.ones(k)).astype(F32)))
     games = [plies[:5], plies[5:37], plies[37:38], plies[38:]]
-    store = store_of_arrays(arrays_of(games))
+    store = store_of(arrays_of(unwalled(games)))
     conv, bn = model.random_init(2, 64, seed=7, perturb_bn=True)
     net = link.Net(conv, bn)
     got, illegal = store.surprise(net, link.DTYPE_F32, 0, 4)
@@ -170,7 +150,7 @@ def weighted_store():
             weight = [] if f & PASS else [0.5 if f & BAD else 1.0]
             plies.append((x, o, f & (PASS | FULL), [int(rng.integers(833))] * len(weight), weight))
         games.append(plies)
-    a = arrays_of(games)
+    a = arrays_of(unwalled(games))
     a.games[:, 2] = [s[1] for s in specs]
     a.games[:, 3] = [s[2] for s in specs]
     return specs, a
@@ -182,7 +162,7 @@ def per_ply_weights(specs, lo, hi):
 
 def check_weighted_draws():
     specs, a = weighted_store()
-    store = store_of_arrays(a, spare=64)
+    store = store_of(a, spare=64)
     games, flags, cand, cum = ref.build_mirror(specs)
     assert (store.mirror()[0] == games).all()
     assert (store.mirror()[1] == np.where(flags & PASS, flags | BAD, flags)).all()      # (a pass has no target: bad as well)
@@ -254,7 +234,7 @@ def check_weighted_draws():
     assert any((d != u).any() for d, u in ((drawn(0)[1], uniform[0]), (drawn(2)[1], uniform[2])))
     assert store.status() == 0
     # a game added while weights are held weighs one per candidate
-    extra = arrays_of([[(1, 2, 0, [5], [1.0])] * 4])
+    extra = arrays_of(unwalled([[(1, 2, 0, [5], [1.0])] * 4]))
     store.add_arrays(extra)
     c2, k2, cum2, _ = store.ply_cum()
     assert k2[-1] == 4 and list(cum2[-4:]) == [65536, 131072, 196608, 262144] and (cum2[:-4] == held).all()
@@ -272,24 +252,5 @@ def check_weighted_draws():
 CHECKS = [check_from_logits_bit_exact, check_net_surprise, check_weighted_draws]
 
 
-def main(path):
-    link.require_gpu()
-    link.require_torch_runtime()
-    results = {}
-    for check in CHECKS:
-        try:
-            check()
-            results[check.__name__] = "ok"
-        except Exception:
-            results[check.__name__] = traceback.format_exc()
-            text = results[check.__name__].lower()
-            if ("hip" in text and "failed at" in text) or "illegal memory access" in text or "hip error" in text:
-                break                                  # a device error: nothing more runs on this GPU
-        with open(path, "w") as f:
-            json.dump(results, f, indent=1)
-    with open(path, "w") as f:
-        json.dump(results, f, indent=1)
-
-
 if __name__ == "__main__":
-    main(sys.argv[1])
+    fresh_process.main(CHECKS)

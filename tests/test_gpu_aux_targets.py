@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from ataxxzero_amd import model, training
+from tests.fresh_process import passed, verdicts_of
 from tests.helpers import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -22,52 +23,43 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def verdicts(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("aux") / "verdicts.json")
-    res = subprocess.run([sys.executable, "-m", "tests.aux_gpu_checks", path], cwd=ROOT, capture_output=True, timeout=600)
-    assert res.returncode == 0 and os.path.exists(path), (res.stdout.decode()[-2000:], res.stderr.decode()[-4000:])
-    with open(path) as f:
-        return json.load(f)
-
-
-def _passed(verdicts, name):
-    assert name in verdicts, "not run: an earlier check ended in a device error (%s)" % ", ".join(verdicts)
-    assert verdicts[name] == "ok", "\n" + verdicts[name]
+    return verdicts_of("tests.aux_gpu_checks", str(tmp_path_factory.mktemp("aux") / "verdicts.json"))
 
 
 def test_parity_from_game_lines(verdicts):
-    _passed(verdicts, "check_parity_from_game_lines")
+    passed(verdicts, "check_parity_from_game_lines")
 
 
 def test_parity_from_records(verdicts):
-    _passed(verdicts, "check_parity_from_records")
+    passed(verdicts, "check_parity_from_records")
 
 
 def test_parity_of_the_existing_outputs(verdicts):
-    _passed(verdicts, "check_parity_of_the_existing_outputs")
+    passed(verdicts, "check_parity_of_the_existing_outputs")
 
 
 def test_edges_of_the_wave_for_the_reply_scatter(verdicts):
-    _passed(verdicts, "check_edges_of_the_wave_for_the_reply_scatter")
+    passed(verdicts, "check_edges_of_the_wave_for_the_reply_scatter")
 
 
 def test_reply_absent(verdicts):
-    _passed(verdicts, "check_reply_absent")
+    passed(verdicts, "check_reply_absent")
 
 
 def test_device_draws_with_aux(verdicts):
-    _passed(verdicts, "check_device_draws_with_aux")
+    passed(verdicts, "check_device_draws_with_aux")
 
 
 def test_stale_rows(verdicts):
-    _passed(verdicts, "check_stale_rows")
+    passed(verdicts, "check_stale_rows")
 
 
 def test_no_owners_anywhere(verdicts):
-    _passed(verdicts, "check_no_owners_anywhere")
+    passed(verdicts, "check_no_owners_anywhere")
 
 
 def test_ingest_refusals(verdicts):
-    _passed(verdicts, "check_ingest_refusals")
+    passed(verdicts, "check_ingest_refusals")
 
 
 @pytest.mark.parametrize("flags", [["--device-samples"], ["--device-draws"]])

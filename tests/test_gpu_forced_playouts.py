@@ -11,39 +11,9 @@ from tests import engine_harness as eh
 from tests import forced_reference as fr
 from tests import helpers
 from tests import vl_reference as vlr
-from tests.engine_harness import START, WIDE_FEN_BIG, WIDE_FEN_MID
+from tests.engine_harness import C_PUCT, SEED, WIDE_FEN_BIG, WIDE_FEN_MID
 
 pytestmark = pytest.mark.gpu
-
-SEED = 424242
-C_PUCT = 1.0
-
-
-def _engine(games, visits, weight=0.25, seed=SEED, flags=0, cap=None, k=None, start=START, edges_per_node=96):
-    x, o, turn = start
-    cfg = link.Config(games=games, visits=visits, max_plies=400, edges_per_node=edges_per_node, c_puct=C_PUCT,
-                      dirichlet_alpha=0.15, dirichlet_weight=weight, start_turn=turn, seed=seed, start_x=x, start_o=o,
-                      blockers=0, flags=flags)
-    e = link.Engine(cfg)
-    if cap is not None:
-        e.set_playout_cap(*cap)
-    if k is not None:
-        e.set_forced_playouts(k)
-    return e
-
-
-def _check_root_marks(e, g=0):
-    """the raw-mark invariant of tests/test_gpu_engine.py at the root: at most one mark, and only on an edge whose child
-    exists, is unfinished and has 1 .. 128 moves"""
-    _, info, _, _ = e.tree(g)
-    raw = e.tree_raw(g)
-    first, m = int(info[0, 0]), int(info[0, 1] & 0xFFFF)
-    idx = np.nonzero((raw[first:first + m, 0] >> 31) != 0)[0]
-    assert len(idx) <= 1, idx.tolist()
-    if len(idx):
-        z, w = int(raw[first + idx[0], 2]), int(raw[first + idx[0], 3])
-        assert m <= 128 and (z >> 16) != 0xFFFF and (w >> 31) == 0 and 1 <= ((w >> 23) & 0xFF) <= 128, (m, hex(z), hex(w))
-    return len(idx)
 
 
 def _expected_counts(tree, k):
@@ -86,7 +56,7 @@ def _lock_step(e, k, games, cap=None, tie_first=False, max_iterations=9000):
             assert s2.root_visits == st.root_visits + added
             seen["owed"] += int(b.forced is not None)
             seen["differs"] += int(b.forced is not None and b.forced != b.puct)
-            seen["marks"] += _check_root_marks(e)
+            seen["marks"] += int(eh.root_mark(e) is not None)
         if s2.phase == 2 and st.phase != 2:
             # the move of this ply is due: the next iteration plays it from this tree
             post = e.tree(0)
@@ -111,7 +81,7 @@ def _lock_step(e, k, games, cap=None, tie_first=False, max_iterations=9000):
 
 
 def test_lock_step_with_the_restatement():
-    e = _engine(1, 48, k=2.0)
+    e = eh.root_engine(1, 48, weight=0.25, forced=2.0)
     seen = _lock_step(e, 2.0, 3)
     assert seen["owed"] > 0 and seen["differs"] > 0 and seen["pruned_plies"] > 0 and seen["marks"] > 0, seen
     e.close()
@@ -119,7 +89,7 @@ def test_lock_step_with_the_restatement():
 
 def test_lock_step_with_the_playout_cap_on():
     cap = (6, 32768)
-    e = _engine(1, 48, k=2.0, cap=cap)
+    e = eh.root_engine(1, 48, weight=0.25, forced=2.0, cap=cap)
     seen = _lock_step(e, 2.0, 3, cap=cap)
     assert seen["owed"] > 0 and seen["differs"] > 0 and seen["pruned_plies"] > 0, seen
     assert seen["fast"] > 0 and seen["full"] > 0 and seen["fast_owed_ignored"] > 0, seen
@@ -127,7 +97,7 @@ def test_lock_step_with_the_playout_cap_on():
 
 
 def test_lock_step_with_ties_to_the_first_edge():
-    e = _engine(1, 48, k=2.0, flags=link.FLAG_TIE_FIRST)
+    e = eh.root_engine(1, 48, weight=0.25, forced=2.0, flags=link.FLAG_TIE_FIRST)
     seen = _lock_step(e, 2.0, 1, tie_first=True)
     assert seen["owed"] > 0 and seen["differs"] > 0, seen
     e.close()
@@ -141,7 +111,7 @@ def test_wide_roots(fen, lo, hi):
     M = len(orc.movegen(p))
     assert lo <= M <= hi
     visits, k = 3 * M, 8.0
-    e = _engine(1, visits, k=k, edges_per_node=200)
+    e = eh.root_engine(1, visits, weight=0.25, forced=k, edges_per_node=200)
     e.set_positions(np.array([[int(p.pieces[0]) | (int(p.turn) << 63), int(p.pieces[1])]], dtype=np.uint64),
                     np.zeros(1, dtype=np.int32))
     owed_high = differs = 0
@@ -161,7 +131,7 @@ def test_wide_roots(fen, lo, hi):
         assert (eb == post[0]).all() and (ei == post[1]).all() and (ee == post[2]).all() and (em == post[3]).all(), it
         owed_high += int(b.forced is not None and b.forced >= 64)
         differs += int(b.forced is not None and b.forced != b.puct)
-        _check_root_marks(e)
+        eh.root_mark(e)
     st = e.game_state(0)
     assert st.phase == 2 and st.root_visits >= visits and owed_high > 0 and differs > 0, (st.as_tuple(), owed_high, differs)
     e.close()
@@ -171,8 +141,8 @@ def test_wide_roots(fen, lo, hi):
 def test_device_loop_equals_host_stepping(games):
     net = eh.net()
     visits, k, n = 16, 2.0, 600
-    a = _engine(games, visits, k=k)
-    b = _engine(games, visits, k=k)
+    a = eh.root_engine(games, visits, weight=0.25, forced=k)
+    b = eh.root_engine(games, visits, weight=0.25, forced=k)
     a.run(net, n, link.DTYPE_BF16)
     a.sync()
     for _ in range(n):
@@ -196,9 +166,9 @@ def test_device_loop_equals_host_stepping(games):
 
 
 def test_off_is_off():
-    ref = _engine(3, 24)
-    never = _engine(3, 24)
-    off = _engine(3, 24, k=2.0)
+    ref = eh.root_engine(3, 24, weight=0.25)
+    never = eh.root_engine(3, 24, weight=0.25)
+    off = eh.root_engine(3, 24, weight=0.25, forced=2.0)
     off.set_forced_playouts(0.0)
     lines = {id(x): [] for x in (ref, never, off)}
     for it in range(1500):
@@ -217,8 +187,8 @@ def test_off_is_off():
     assert len(lines[id(ref)]) >= 3 and lines[id(ref)] == lines[id(never)] == lines[id(off)]
     assert ref.stats() == never.stats() == off.stats()
     # ... and the mode, switched on, does change the search (the comparison above is not vacuous)
-    on = _engine(3, 24, k=2.0)
-    ref2 = _engine(3, 24)
+    on = eh.root_engine(3, 24, weight=0.25, forced=2.0)
+    ref2 = eh.root_engine(3, 24, weight=0.25)
     differ = False
     for it in range(200):
         eh.step(on), eh.step(ref2)
@@ -229,7 +199,7 @@ def test_off_is_off():
 
 
 def test_refusals_leave_the_engine_usable():
-    e = _engine(4, 24)
+    e = eh.root_engine(4, 24, weight=0.25)
     for bad in (-1.0, float("nan")):
         with pytest.raises(link.AzhError):
             e.set_forced_playouts(bad)
@@ -263,7 +233,7 @@ def test_refusals_leave_the_engine_usable():
         eh.step(e)
     e.close()
     for flags in (link.FLAG_TWO_NETS, link.FLAG_ONE_RANDOM_MOVE):
-        r = _engine(4, 24, weight=0.0, flags=flags)
+        r = eh.root_engine(4, 24, weight=0.0, flags=flags)
         with pytest.raises(link.AzhError):
             r.set_forced_playouts(2.0)
         r.set_forced_playouts(0.0)            # switching off is no request for the mode

@@ -14,41 +14,13 @@ from tests import forced_reference as fr
 from tests import gumbel_reference as gr
 from tests import helpers
 from tests import vl_reference as vlr
-from tests.engine_harness import START, WIDE_FEN_BIG, WIDE_FEN_MID
+from tests.engine_harness import C_PUCT, SEED, WIDE_FEN_BIG, WIDE_FEN_MID
 
 pytestmark = pytest.mark.gpu
 
-SEED = 424242
-C_PUCT = 1.0
 C_VISIT, C_SCALE = 50.0, 1.0
 ONE_MOVE_FEN = "oooxooo/oooxoxx/ooxxoxx/ooxxxxx/oooxxx1/oooxxxx/ooxxxxx o"
 F32 = np.float32
-
-
-def _engine(games, visits, gumbel=None, weight=0.0, seed=SEED, flags=link.FLAG_NO_REUSE, start=START, edges_per_node=96):
-    x, o, turn = start
-    cfg = link.Config(games=games, visits=visits, max_plies=400, edges_per_node=edges_per_node, c_puct=C_PUCT,
-                      dirichlet_alpha=0.15, dirichlet_weight=weight, start_turn=turn, seed=seed, start_x=x, start_o=o,
-                      blockers=0, flags=flags)
-    e = link.Engine(cfg)
-    if gumbel is not None:
-        e.set_gumbel(gumbel, C_VISIT, C_SCALE)
-    return e
-
-
-def _root_mark(e, g=0):
-    """the root edge that carries the raw prefetch mark, or None; at most one does, and only an edge whose child exists, is
-    unfinished and has 1 .. 128 moves (the raw-mark invariant of tests/test_gpu_engine.py at the root)"""
-    _, info, _, _ = e.tree(g)
-    raw = e.tree_raw(g)
-    first, m = int(info[0, 0]), int(info[0, 1] & 0xFFFF)
-    idx = np.nonzero((raw[first:first + m, 0] >> 31) != 0)[0]
-    assert len(idx) <= 1, idx.tolist()
-    if len(idx):
-        z, w = int(raw[first + idx[0], 2]), int(raw[first + idx[0], 3])
-        assert m <= 128 and (z >> 16) != 0xFFFF and (w >> 31) == 0 and 1 <= ((w >> 23) & 0xFF) <= 128, (m, hex(z), hex(w))
-        return int(idx[0])
-    return None
 
 
 def _expected_ply(tree, v0, g):
@@ -78,7 +50,7 @@ def _lock_step(e, visits, m, games, plies_checked=12, max_iterations=9000):
         b = None
         if st.phase == 1 and st.ply < plies_checked:
             pre = e.tree(0)
-            mark = _root_mark(e)
+            mark = eh.root_mark(e)
             b = gr.select(pre, st.root_visits, visits, m, root[key][0], C_VISIT, C_SCALE, C_PUCT, False, 0)
         values = eh.step(e)[3]
         s2 = e.game_state(0)
@@ -97,7 +69,7 @@ def _lock_step(e, visits, m, games, plies_checked=12, max_iterations=9000):
             (eb, ei, ee, em), added = vlr.expected_tree(b, values, post)
             assert (eb == post[0]).all() and (ei == post[1]).all() and (ee == post[2]).all() and (em == post[3]).all(), it
             assert s2.root_visits == st.root_visits + added
-            after = _root_mark(e)
+            after = eh.root_mark(e)
             assert after == gr.next_mark(pre, mark, b.root_edge), (it, mark, b.root_edge, after)
             seen["cv"].add(b.cv)
             seen["fallback"] += int(b.gumbel is None)
@@ -142,7 +114,7 @@ def _check_lines(lines, expected_by_game):
 
 @pytest.mark.parametrize("visits,m", [(16, 4), (33, 16)])
 def test_lock_step_with_the_restatement(visits, m):
-    e = _engine(1, visits, gumbel=m)
+    e = eh.root_engine(1, visits, weight=0.0, flags=link.FLAG_NO_REUSE, gumbel=(m, C_VISIT, C_SCALE))
     seen, lines, expected = _lock_step(e, visits, m, 2)
     # every count the schedules of the checked plies hold was asked for (so every halving phase ran), the rule always found
     # its edge, and it did take edges PUCT would not have
@@ -162,7 +134,7 @@ def test_wide_roots(fen, lo, hi, beyond):
     M = len(orc.movegen(p))
     assert lo <= M <= hi
     visits, m = 160, 256
-    e = _engine(1, visits, gumbel=m, edges_per_node=200)
+    e = eh.root_engine(1, visits, weight=0.0, flags=link.FLAG_NO_REUSE, gumbel=(m, C_VISIT, C_SCALE), edges_per_node=200)
     e.set_positions(np.array([[int(p.pieces[0]) | (int(p.turn) << 63), int(p.pieces[1])]], dtype=np.uint64),
                     np.zeros(1, dtype=np.int32))
     values = eh.step(e)[3]
@@ -177,13 +149,13 @@ def test_wide_roots(fen, lo, hi, beyond):
     for it in range(visits):
         st = e.game_state(0)
         assert st.phase == 1 and st.root_visits == it
-        pre, mark = e.tree(0), _root_mark(e)
+        pre, mark = e.tree(0), eh.root_mark(e)
         b = gr.select(pre, st.root_visits, visits, m, a, C_VISIT, C_SCALE, C_PUCT, False, 0)
         values = eh.step(e)[3]
         post = e.tree(0)
         (eb, ei, ee, em), added = vlr.expected_tree(b, values, post)
         assert (eb == post[0]).all() and (ei == post[1]).all() and (ee == post[2]).all() and (em == post[3]).all(), it
-        assert _root_mark(e) == gr.next_mark(pre, mark, b.root_edge)
+        assert eh.root_mark(e) == gr.next_mark(pre, mark, b.root_edge)
         assert b.gumbel is not None
         high += int(b.gumbel >= beyond)
         differs += int(b.gumbel != b.puct)
@@ -204,7 +176,7 @@ def test_a_root_with_one_legal_move():
     only = [int(x) for x in orc.movegen(p)]
     assert len(only) == 1 and orc.result(p) == 0
     visits = 6
-    e = _engine(1, visits, gumbel=4)
+    e = eh.root_engine(1, visits, weight=0.0, flags=link.FLAG_NO_REUSE, gumbel=(4, C_VISIT, C_SCALE))
     e.set_positions(np.array([[int(p.pieces[0]) | (int(p.turn) << 63), int(p.pieces[1])]], dtype=np.uint64),
                     np.zeros(1, dtype=np.int32))
     values = eh.step(e)[3]
@@ -238,8 +210,8 @@ def test_a_root_with_one_legal_move():
 def test_device_loop_equals_host_stepping(games, extras):
     net = eh.net()
     visits, m, n = 8, 4, 500
-    a = _engine(games, visits, gumbel=m)
-    b = _engine(games, visits, gumbel=m)
+    a = eh.root_engine(games, visits, weight=0.0, flags=link.FLAG_NO_REUSE, gumbel=(m, C_VISIT, C_SCALE))
+    b = eh.root_engine(games, visits, weight=0.0, flags=link.FLAG_NO_REUSE, gumbel=(m, C_VISIT, C_SCALE))
     if extras:
         for x in (a, b):
             x.set_random_symmetry(True)
@@ -270,9 +242,9 @@ def test_device_loop_equals_host_stepping(games, extras):
 
 
 def test_off_is_off():
-    ref = _engine(3, 8)
-    never = _engine(3, 8)
-    off = _engine(3, 8, gumbel=4)
+    ref = eh.root_engine(3, 8, weight=0.0, flags=link.FLAG_NO_REUSE)
+    never = eh.root_engine(3, 8, weight=0.0, flags=link.FLAG_NO_REUSE)
+    off = eh.root_engine(3, 8, weight=0.0, flags=link.FLAG_NO_REUSE, gumbel=(4, C_VISIT, C_SCALE))
     off.set_gumbel(0)
     lines = {id(x): [] for x in (ref, never, off)}
     for it in range(1500):
@@ -291,8 +263,8 @@ def test_off_is_off():
     assert len(lines[id(ref)]) >= 3 and lines[id(ref)] == lines[id(never)] == lines[id(off)]
     assert ref.stats() == never.stats() == off.stats()
     # ... and the mode, switched on, does change the search (the comparison above is not vacuous)
-    on = _engine(3, 8, gumbel=4)
-    ref2 = _engine(3, 8)
+    on = eh.root_engine(3, 8, weight=0.0, flags=link.FLAG_NO_REUSE, gumbel=(4, C_VISIT, C_SCALE))
+    ref2 = eh.root_engine(3, 8, weight=0.0, flags=link.FLAG_NO_REUSE)
     differ = False
     for it in range(60):
         eh.step(on), eh.step(ref2)
@@ -305,12 +277,12 @@ def test_off_is_off():
 def test_set_visits_while_the_mode_is_on():
     """The engine's rows follow azh_engine_set_visits: a ply searched at the new threshold in lock step with the restatement
     on seq(r, new visits); a threshold whose table would be too large is refused and changes nothing."""
-    e = _engine(1, 33, gumbel=4)
+    e = eh.root_engine(1, 33, weight=0.0, flags=link.FLAG_NO_REUSE, gumbel=(4, C_VISIT, C_SCALE))
     e.set_visits(12)
     seen, lines, expected = _lock_step(e, 12, 4, 1, plies_checked=3)
     assert seen["cv"] == seen["schedule"] and len(seen["cv"]) >= 3 and seen["fallback"] == 0 and seen["differs"] > 0, seen
     e.close()
-    big = _engine(1, 60000, edges_per_node=8)
+    big = eh.root_engine(1, 60000, weight=0.0, flags=link.FLAG_NO_REUSE, edges_per_node=8)
     with pytest.raises(link.AzhError):
         big.set_gumbel(256, C_VISIT, C_SCALE)          # 256 * 60000 entries
     big.set_visits(4096)
@@ -327,7 +299,7 @@ def test_set_visits_while_the_mode_is_on():
 
 
 def test_refusals_leave_the_engine_usable():
-    e = _engine(4, 24)
+    e = eh.root_engine(4, 24, weight=0.0, flags=link.FLAG_NO_REUSE)
     for bad in ((-1, 50.0, 1.0), (257, 50.0, 1.0), (4, -1.0, 1.0), (4, float("nan"), 1.0), (4, float("inf"), 1.0),
                 (4, 50.0, 0.0), (4, 50.0, -1.0), (4, 50.0, float("nan")), (4, 50.0, float("inf"))):
         with pytest.raises(link.AzhError):
@@ -368,7 +340,7 @@ def test_refusals_leave_the_engine_usable():
     for flags, weight in ((0, 0.0), (link.FLAG_NO_REUSE, 0.25),
                           (link.FLAG_NO_REUSE | link.FLAG_TWO_NETS, 0.0), (link.FLAG_NO_REUSE | link.FLAG_ONE_RANDOM_MOVE, 0.0),
                           (link.FLAG_NO_REUSE | link.FLAG_SAMPLE_POW5, 0.0), (link.FLAG_NO_REUSE | link.FLAG_EVAL_CACHE, 0.0)):
-        r = _engine(4, 24, weight=weight, flags=flags)
+        r = eh.root_engine(4, 24, weight=weight, flags=flags)
         with pytest.raises(link.AzhError):
             r.set_gumbel(4)
         r.set_gumbel(0)                        # switching off is no request for the mode

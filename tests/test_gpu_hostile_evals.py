@@ -23,13 +23,10 @@ from tests import priors_reference as pr
 from tests import symmetry_reference as sym
 from tests import temperature_reference as tr
 from tests import vl_reference as vlr
-from tests.engine_harness import START
+from tests.engine_harness import ALPHA, C_PUCT, SEED
 
 pytestmark = pytest.mark.gpu
 
-SEED = 424242
-C_PUCT = 1.0
-ALPHA = 0.15
 C_VISIT, C_SCALE = 50.0, 1.0
 MAX_PLIES = 400
 F32 = np.float32
@@ -47,25 +44,13 @@ class Mode:
         self.cap, self.symmetry, self.K, self.move_table, self.root_table = cap, symmetry, K, move_table, root_table
 
     def engine(self, games=None, visits=None, max_plies=MAX_PLIES, flags=0):
-        x, o, turn = START
-        cfg = link.Config(games=games or self.games, visits=visits or self.visits, max_plies=max_plies, edges_per_node=96,
-                          c_puct=C_PUCT, dirichlet_alpha=ALPHA, dirichlet_weight=self.weight, start_turn=turn, seed=SEED,
-                          start_x=x, start_o=o, blockers=0, flags=link.FLAG_NO_REUSE | flags)
-        e = link.Engine(cfg)
-        if self.cap:
-            e.set_playout_cap(*self.cap)
-        if self.forced:
-            e.set_forced_playouts(self.forced)
+        tables = None
         if self.move_table is not None or self.root_table is not None:
-            e.set_temperature(None if self.move_table is None else self.move_table[:max_plies],
-                              None if self.root_table is None else self.root_table[:max_plies])
-        if self.symmetry:
-            e.set_random_symmetry(True)
-        if self.K > 1:
-            e.set_leaf_batch(self.K, 1)
-        if self.gumbel:
-            e.set_gumbel(self.gumbel, C_VISIT, C_SCALE)
-        return e
+            tables = (None if self.move_table is None else self.move_table[:max_plies],
+                      None if self.root_table is None else self.root_table[:max_plies])
+        return eh.root_engine(games or self.games, visits or self.visits, weight=self.weight, flags=link.FLAG_NO_REUSE | flags,
+                              max_plies=max_plies, cap=self.cap or None, forced=self.forced or None, temperature=tables,
+                              symmetry=self.symmetry, K=self.K, gumbel=(self.gumbel, C_VISIT, C_SCALE) if self.gumbel else None)
 
     def full(self, uid, ply):
         return True if self.cap is None else bool(link.playout_cap_kind(SEED, uid, ply, self.cap[1]))

@@ -10,23 +10,9 @@ import pytest
 from ataxxzero_amd import link
 from tests import engine_harness as eh
 from tests import helpers
-from tests.engine_harness import START
+from tests.engine_harness import SEED
 
 pytestmark = pytest.mark.gpu
-
-SEED = 424242
-
-
-def _engine(games, visits, weight=0.0, seed=SEED, flags=0, cap=None, K=1):
-    x, o, turn = START
-    cfg = link.Config(games=games, visits=visits, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
-                      dirichlet_weight=weight, start_turn=turn, seed=seed, start_x=x, start_o=o, blockers=0, flags=flags)
-    e = link.Engine(cfg)
-    if K > 1:
-        e.set_leaf_batch(K, 1)
-    if cap is not None:
-        e.set_playout_cap(*cap)
-    return e
 
 
 def _strip_full(line):
@@ -38,8 +24,8 @@ def test_lock_step_with_a_host_driven_uncapped_engine():
     at: every state word and tree row equal after every iteration over three complete games, the lines equal but for
     A's "full" key."""
     visits, fast, frac = 24, 6, 32768
-    a = _engine(1, visits, cap=(fast, frac))
-    b = _engine(1, visits)
+    a = eh.root_engine(1, visits, weight=0.0, cap=(fast, frac))
+    b = eh.root_engine(1, visits, weight=0.0)
     lines_a, lines_b, kinds_seen, inherited_fast = [], [], set(), 0
     for it in range(6000):
         sb = b.game_state(0)
@@ -68,7 +54,7 @@ def test_lock_step_with_a_host_driven_uncapped_engine():
 def test_records_say_what_was_searched(games):
     visits, fast, frac = 16, 4, 16384
     net = eh.net()
-    e = _engine(games, visits, weight=0.25, cap=(fast, frac))
+    e = eh.root_engine(games, visits, weight=0.25, cap=(fast, frac))
     recs, lines = [], []
     for _ in range(40):
         e.run(net, 100, link.DTYPE_BF16)
@@ -112,9 +98,9 @@ def test_root_noise_on_full_plies_only():
     those of an engine without noise, on FULL plies those of the uncapped engine with noise, at the same uid, ply and
     position (loaded with set_positions: uids restart at the slot numbers), bit for bit."""
     G, visits, fast, frac = 8, 12, 3, 32768
-    a = _engine(G, visits, weight=0.25, cap=(fast, frac))
-    plain = _engine(G, visits, weight=0.0)
-    noisy = _engine(G, visits, weight=0.25)
+    a = eh.root_engine(G, visits, weight=0.25, cap=(fast, frac))
+    plain = eh.root_engine(G, visits, weight=0.0)
+    noisy = eh.root_engine(G, visits, weight=0.25)
     checked = {0: 0, 1: 0}
     differ = 0
     for it in range(1500):
@@ -144,7 +130,7 @@ def test_root_noise_on_full_plies_only():
 @pytest.mark.parametrize("K", [4, 8])
 def test_leaf_parallel_batches_stop_at_the_plys_own_threshold(K):
     G, visits, fast, frac = 3, 24, 6, 32768
-    e = _engine(G, visits, cap=(fast, frac), K=K)
+    e = eh.root_engine(G, visits, weight=0.0, cap=(fast, frac), K=K)
     seen = {0: 0, 1: 0}
     truncated = 0
     for it in range(400):
@@ -174,8 +160,8 @@ def test_leaf_parallel_batches_stop_at_the_plys_own_threshold(K):
 def test_device_loop_equals_host_stepping_with_the_cap_on():
     net = eh.net()
     n, G = 200, 33
-    a = _engine(G, 16, weight=0.25, cap=(4, 16384))
-    b = _engine(G, 16, weight=0.25, cap=(4, 16384))
+    a = eh.root_engine(G, 16, weight=0.25, cap=(4, 16384))
+    b = eh.root_engine(G, 16, weight=0.25, cap=(4, 16384))
     a.run(net, n, link.DTYPE_BF16)
     a.sync()
     for _ in range(n):
@@ -192,9 +178,9 @@ def test_device_loop_equals_host_stepping_with_the_cap_on():
 def test_every_ply_full_and_switched_off_are_the_uncapped_engine():
     net = eh.net(seed=5)
     n, G = 400, 5
-    ref = _engine(G, 12, weight=0.25)
-    every = _engine(G, 12, weight=0.25, cap=(3, 65536))
-    off = _engine(G, 12, weight=0.25, cap=(3, 16384))
+    ref = eh.root_engine(G, 12, weight=0.25)
+    every = eh.root_engine(G, 12, weight=0.25, cap=(3, 65536))
+    off = eh.root_engine(G, 12, weight=0.25, cap=(3, 16384))
     off.set_playout_cap(0, 0)
     for e in (ref, every, off):
         e.run(net, n, link.DTYPE_F32)
@@ -213,7 +199,7 @@ def test_every_ply_full_and_switched_off_are_the_uncapped_engine():
 
 
 def test_refusals_leave_the_engine_usable():
-    e = _engine(4, 24)
+    e = eh.root_engine(4, 24, weight=0.0)
     for bad in [(25, 100), (-1, 100), (6, -1), (6, 65537)]:
         with pytest.raises(link.AzhError):
             e.set_playout_cap(*bad)
@@ -236,7 +222,7 @@ def test_refusals_leave_the_engine_usable():
     assert e.stats()["plies"] > 0
     e.close()
     for flags in (link.FLAG_TWO_NETS, link.FLAG_ONE_RANDOM_MOVE):
-        r = _engine(4, 24, flags=flags)
+        r = eh.root_engine(4, 24, weight=0.0, flags=flags)
         with pytest.raises(link.AzhError):
             r.set_playout_cap(6, 16384)
         r.set_playout_cap(0, 0)               # switching off is no request for the mode

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from ataxxzero_amd import link, training
+from tests.fresh_process import passed, verdicts_of
 from tests.helpers import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -23,36 +24,27 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def verdicts(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("prove") / "verdicts.json")
-    res = subprocess.run([sys.executable, "-m", "tests.prove_gpu_checks", path], cwd=ROOT, capture_output=True, timeout=600)
-    assert res.returncode == 0 and os.path.exists(path), (res.stdout.decode()[-2000:], res.stderr.decode()[-4000:])
-    with open(path) as f:
-        return json.load(f)
-
-
-def _passed(verdicts, name):
-    assert name in verdicts, "not run: an earlier check ended in a device error (%s)" % ", ".join(verdicts)
-    assert verdicts[name] == "ok", "\n" + verdicts[name]
+    return verdicts_of("tests.prove_gpu_checks", str(tmp_path_factory.mktemp("prove") / "verdicts.json"))
 
 
 def test_proofs_are_the_searchs(verdicts):
-    _passed(verdicts, "check_proofs_are_the_searchs")
+    passed(verdicts, "check_proofs_are_the_searchs")
 
 
 def test_deep_rows_walls_and_budgets(verdicts):
-    _passed(verdicts, "check_deep_rows_walls_budgets")
+    passed(verdicts, "check_deep_rows_walls_budgets")
 
 
 def test_minibatches_change_in_proven_value_entries_only(verdicts):
-    _passed(verdicts, "check_minibatches")
+    passed(verdicts, "check_minibatches")
 
 
 def test_proofs_only_accumulate(verdicts):
-    _passed(verdicts, "check_monotone")
+    passed(verdicts, "check_monotone")
 
 
 def test_refusals_change_nothing(verdicts):
-    _passed(verdicts, "check_refusals")
+    passed(verdicts, "check_refusals")
 
 
 def test_train_cli_proves_before_the_first_step(tmp_path):

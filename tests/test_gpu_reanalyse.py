@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from ataxxzero_amd import link, model, training
+from tests.fresh_process import passed, verdicts_of
 from tests.helpers import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -24,40 +25,31 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def verdicts(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("reanalyse") / "verdicts.json")
-    res = subprocess.run([sys.executable, "-m", "tests.reanalyse_gpu_checks", path], cwd=ROOT, capture_output=True, timeout=600)
-    assert res.returncode == 0 and os.path.exists(path), (res.stdout.decode()[-2000:], res.stderr.decode()[-4000:])
-    with open(path) as f:
-        return json.load(f)
-
-
-def _passed(verdicts, name):
-    assert name in verdicts, "not run: an earlier check ended in a device error (%s)" % ", ".join(verdicts)
-    assert verdicts[name] == "ok", "\n" + verdicts[name]
+    return verdicts_of("tests.reanalyse_gpu_checks", str(tmp_path_factory.mktemp("reanalyse") / "verdicts.json"))
 
 
 def test_read_plies_returns_what_was_stored(verdicts):
-    _passed(verdicts, "check_read_plies")
+    passed(verdicts, "check_read_plies")
 
 
 def test_synthetic_reports_become_the_restated_targets(verdicts):
-    _passed(verdicts, "check_synthetic_reports")
+    passed(verdicts, "check_synthetic_reports")
 
 
 def test_refusals_change_nothing_and_later_games_append_behind(verdicts):
-    _passed(verdicts, "check_refusals")
+    passed(verdicts, "check_refusals")
 
 
 def test_minibatch_parity_after_retarget(verdicts):
-    _passed(verdicts, "check_minibatch_parity")
+    passed(verdicts, "check_minibatch_parity")
 
 
 def test_whole_path_against_an_engine_driven_by_existing_calls(verdicts):
-    _passed(verdicts, "check_whole_path")
+    passed(verdicts, "check_whole_path")
 
 
 def test_walls_one_engine_per_mask(verdicts):
-    _passed(verdicts, "check_walls")
+    passed(verdicts, "check_walls")
 
 
 def test_train_cli_reanalyses_before_the_first_step(tmp_path):

@@ -15,26 +15,11 @@ from ataxxzero_amd import link
 from tests import engine_harness as eh
 from tests import helpers
 from tests import resign_reference as ref
-from tests.engine_harness import START
+from tests.engine_harness import SEED
 
 pytestmark = pytest.mark.gpu
 
-SEED = 424242
 KIND_CAP, KIND_VALUES, KIND_RESIGNED = link.REC_KIND_PLAYOUT_CAP, link.REC_KIND_VALUES, link.REC_KIND_RESIGNED
-
-
-def _engine(games, visits, weight=0.0, seed=SEED, flags=0, resign=None, cap=None, K=1):
-    x, o, turn = START
-    cfg = link.Config(games=games, visits=visits, max_plies=400, edges_per_node=96, c_puct=1.0, dirichlet_alpha=0.15,
-                      dirichlet_weight=weight, start_turn=turn, seed=seed, start_x=x, start_o=o, blockers=0, flags=flags)
-    e = link.Engine(cfg)
-    if K > 1:
-        e.set_leaf_batch(K, 1)
-    if cap is not None:
-        e.set_playout_cap(*cap)
-    if resign is not None:
-        e.set_resign(*resign)
-    return e
 
 
 def _strip_values(line):
@@ -55,8 +40,8 @@ def _recorded_run():
     synthetic evaluator, three complete games.  -> (A's lines, B's lines, {(uid, ply): (q, visited?, mover)} from B's root
     report in the iteration before each move, ties between most-visited edges seen, A's resign stats)."""
     visits = 16
-    a = _engine(1, visits, resign=(0.3, 2, 65536))
-    b = _engine(1, visits)
+    a = eh.root_engine(1, visits, weight=0.0, resign=(0.3, 2, 65536))
+    b = eh.root_engine(1, visits, weight=0.0)
     lines_a, lines_b, expect, ties = [], [], {}, 0
     for it in range(8000):
         sb = b.game_state(0)
@@ -111,8 +96,8 @@ def test_games_resign_where_the_rule_says_and_the_slot_restarts():
     qs = np.array([(v + 1) / 2 for l in lines_a for v in json.loads(l)["values"]], dtype=np.float32)
     t = float(np.quantile(qs, 0.05))
     G, visits = 33, 16
-    a = _engine(G, visits, resign=(t, 2, 0))
-    b = _engine(G, visits)
+    a = eh.root_engine(G, visits, weight=0.0, resign=(t, 2, 0))
+    b = eh.root_engine(G, visits, weight=0.0)
     seq = [[] for _ in range(G)]               # B's plies as the rule takes them
     live = set(range(G))                       # slots whose first game A and B still play together
     resigned_at = {}
@@ -185,7 +170,7 @@ def _loop_threshold():
     records in 300 iterations with resignation off (q_below = 0) — low enough that games are played for a while, high enough
     that, with two consecutive plies of a side needed, games do resign."""
     net = eh.net()
-    e = _engine(33, 16, weight=0.25, resign=(0.0, 1, 0))
+    e = eh.root_engine(33, 16, weight=0.25, resign=(0.0, 1, 0))
     recs, lines = [], []
     e.run(net, 300, link.DTYPE_BF16)
     _collect(e, recs, lines)
@@ -199,7 +184,7 @@ def _loop_threshold():
 def test_play_through_games_are_the_ones_the_draw_names(games):
     t, k, share = _loop_threshold(), 2, 16384
     net = eh.net()
-    e = _engine(games, 16, weight=0.25, resign=(t, k, share))
+    e = eh.root_engine(games, 16, weight=0.25, resign=(t, k, share))
     recs, lines = [], []
     for _ in range(40):
         e.run(net, 100, link.DTYPE_BF16)
@@ -223,7 +208,7 @@ def test_play_through_games_are_the_ones_the_draw_names(games):
 def test_fast_plies_neither_advance_nor_reset_a_counter():
     G, visits, fast, frac, t, k = 33, 16, 4, 16384, _loop_threshold(), 2
     net = eh.net()
-    e = _engine(G, visits, weight=0.25, cap=(fast, frac), resign=(t, k, 0))
+    e = eh.root_engine(G, visits, weight=0.25, cap=(fast, frac), resign=(t, k, 0))
     recs, lines = [], []
     for _ in range(40):
         e.run(net, 100, link.DTYPE_BF16)
@@ -258,8 +243,8 @@ def test_fast_plies_neither_advance_nor_reset_a_counter():
 def test_device_loop_equals_host_stepping_with_the_mode_on(K):
     net = eh.net()
     n, G, t, k, share = 200, 33 if K == 1 else 9, _loop_threshold(), 2, 16384
-    a = _engine(G, 16, weight=0.25, resign=(t, k, share), K=K)
-    b = _engine(G, 16, weight=0.25, resign=(t, k, share), K=K)
+    a = eh.root_engine(G, 16, weight=0.25, resign=(t, k, share), K=K)
+    b = eh.root_engine(G, 16, weight=0.25, resign=(t, k, share), K=K)
     a.run(net, n, link.DTYPE_BF16)
     a.sync()
     for _ in range(n):
@@ -302,7 +287,7 @@ def test_values_that_are_not_finite(evals):
     are never below, and -inf is recorded and judged without its sign, so no game resigns at such a ply — a q that is not
     finite is written as 0, and the loop goes on."""
     G, t = 8, 0.4
-    e = _engine(G, 12, resign=(t, 1, 0))
+    e = eh.root_engine(G, 12, weight=0.0, resign=(t, 1, 0))
     recs, lines = [], []
     for it in range(6000):
         eh.step(e, evals)
@@ -329,8 +314,8 @@ def test_values_that_are_not_finite(evals):
 def test_switched_off_is_the_engine_without_the_mode():
     net = eh.net(seed=5)
     n, G = 400, 5
-    ref_e = _engine(G, 12, weight=0.25)
-    off = _engine(G, 12, weight=0.25, resign=(0.47, 2, 16384))
+    ref_e = eh.root_engine(G, 12, weight=0.25)
+    off = eh.root_engine(G, 12, weight=0.25, resign=(0.47, 2, 16384))
     off.set_resign(0.9, 0, 123)
     for e in (ref_e, off):
         e.run(net, n, link.DTYPE_F32)
@@ -347,7 +332,7 @@ def test_switched_off_is_the_engine_without_the_mode():
 
 
 def test_refusals_leave_the_engine_usable():
-    e = _engine(4, 24)
+    e = eh.root_engine(4, 24, weight=0.0)
     for bad in [(1.0, 2, 0), (-0.1, 2, 0), (float("nan"), 2, 0), (1.5, 2, 0), (0.3, 256, 0), (0.3, -1, 0), (0.3, 2, 65537),
                 (0.3, 2, -1)]:
         with pytest.raises(link.AzhError):
@@ -370,7 +355,7 @@ def test_refusals_leave_the_engine_usable():
     e.set_resign(0.0, 0, 0)
     e.close()
     for flags in (link.FLAG_TWO_NETS, link.FLAG_ONE_RANDOM_MOVE):
-        r = _engine(4, 24, flags=flags)
+        r = eh.root_engine(4, 24, weight=0.0, flags=flags)
         with pytest.raises(link.AzhError):
             r.set_resign(0.3, 2, 0)
         r.set_resign(0.0, 0, 0)               # switching off is no request for the mode

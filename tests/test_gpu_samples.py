@@ -5,7 +5,7 @@ host draws and with draws made on the device.
 A SampleStore enqueues on torch's streams and writes torch's tensors, so the process must hold ONE HIP runtime: torch
 imported before the library is loaded (link.require_torch_runtime).  A pytest process that has run other device tests loaded
 the library first, so the checks (tests/samples_gpu_checks.py) run in one fresh process, once for the module, and each test
-below reads its check's verdict."""
+below reads its check's verdict (tests/fresh_process.py)."""
 import json
 import os
 import subprocess
@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from ataxxzero_amd import model
+from tests.fresh_process import passed, verdicts_of
 from tests.helpers import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -23,52 +24,43 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def verdicts(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("samples") / "verdicts.json")
-    res = subprocess.run([sys.executable, "-m", "tests.samples_gpu_checks", path], cwd=ROOT, capture_output=True, timeout=600)
-    assert res.returncode == 0 and os.path.exists(path), (res.stdout.decode()[-2000:], res.stderr.decode()[-4000:])
-    with open(path) as f:
-        return json.load(f)
-
-
-def _passed(verdicts, name):
-    assert name in verdicts, "not run: an earlier check ended in a device error (%s)" % ", ".join(verdicts)
-    assert verdicts[name] == "ok", "\n" + verdicts[name]
+    return verdicts_of("tests.samples_gpu_checks", str(tmp_path_factory.mktemp("samples") / "verdicts.json"))
 
 
 def test_reference_parity(verdicts):
-    _passed(verdicts, "check_reference_parity")
+    passed(verdicts, "check_reference_parity")
 
 
 def test_every_index_under_every_symmetry(verdicts):
-    _passed(verdicts, "check_every_index_under_every_symmetry")
+    passed(verdicts, "check_every_index_under_every_symmetry")
 
 
 def test_edges_of_the_wave(verdicts):
-    _passed(verdicts, "check_edges_of_the_wave")
+    passed(verdicts, "check_edges_of_the_wave")
 
 
 def test_the_record_path(verdicts):
-    _passed(verdicts, "check_the_record_path")
+    passed(verdicts, "check_the_record_path")
 
 
 def test_device_draws(verdicts):
-    _passed(verdicts, "check_device_draws")
+    passed(verdicts, "check_device_draws")
 
 
 def test_stream_and_reuse(verdicts):
-    _passed(verdicts, "check_stream_and_reuse")
+    passed(verdicts, "check_stream_and_reuse")
 
 
 def test_capacity(verdicts):
-    _passed(verdicts, "check_capacity")
+    passed(verdicts, "check_capacity")
 
 
 def test_bad_ply(verdicts):
-    _passed(verdicts, "check_bad_ply")
+    passed(verdicts, "check_bad_ply")
 
 
 def test_argument_refusals(verdicts):
-    _passed(verdicts, "check_argument_refusals")
+    passed(verdicts, "check_argument_refusals")
 
 
 @pytest.mark.parametrize("flags", [["--device-samples"], ["--device-draws"]])

@@ -13,7 +13,7 @@ import pytest
 from ataxxzero_amd import arena, link, model
 from oracle import oracle_lib as orc
 from tests import engine_harness as eh
-from tests import helpers
+from tests import fresh_process, helpers
 from tests import start_pool_fixtures as spf
 
 pytestmark = pytest.mark.gpu
@@ -379,7 +379,7 @@ def _start_cells(x, o):
     return [1 if (x >> (c % 7 + 7 * (6 - c // 7))) & 1 else 2 if (o >> (c % 7 + 7 * (6 - c // 7))) & 1 else 0 for c in range(49)]
 
 
-def test_records_of_a_pooled_engine_enter_the_store_with_their_own_masks():
+def test_records_of_a_pooled_engine_enter_the_store_with_their_own_masks(tmp_path):
     """(in a process of its own: the sample store wants torch's HIP runtime loaded before the library, tests/samples_gpu_checks.py)"""
-    res = subprocess.run([sys.executable, "-m", "tests.start_pool_store_check"], cwd=ROOT, capture_output=True, timeout=300)
-    assert res.returncode == 0 and res.stdout.decode().strip().endswith("ok"), (res.stdout.decode()[-2000:], res.stderr.decode()[-4000:])
+    verdicts = fresh_process.verdicts_of("tests.start_pool_store_check", str(tmp_path / "verdicts.json"), timeout=300)
+    fresh_process.passed(verdicts, "check_records_enter_the_store_with_their_own_masks")

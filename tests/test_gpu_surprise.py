@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from ataxxzero_amd import model
+from tests.fresh_process import passed, verdicts_of
 from tests.helpers import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -21,29 +22,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def verdicts(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("surprise") / "verdicts.json")
-    res = subprocess.run([sys.executable, "-m", "tests.surprise_gpu_checks", path], cwd=ROOT, capture_output=True, timeout=600)
-    assert res.returncode == 0 and os.path.exists(path), (res.stdout.decode()[-2000:], res.stderr.decode()[-4000:])
-    print(res.stdout.decode()[-2000:])
-    with open(path) as f:
-        return json.load(f)
-
-
-def _passed(verdicts, name):
-    assert name in verdicts, "not run: an earlier check ended in a device error (%s)" % ", ".join(verdicts)
-    assert verdicts[name] == "ok", "\n" + verdicts[name]
+    return verdicts_of("tests.surprise_gpu_checks", str(tmp_path_factory.mktemp("surprise") / "verdicts.json"), echo=True)
 
 
 def test_surprise_from_logits_equals_the_host_bit_for_bit(verdicts):
-    _passed(verdicts, "check_from_logits_bit_exact")
+    passed(verdicts, "check_from_logits_bit_exact")
 
 
 def test_surprise_of_a_net_against_the_float64_oracle(verdicts):
-    _passed(verdicts, "check_net_surprise")
+    passed(verdicts, "check_net_surprise")
 
 
 def test_weighted_draws_and_ply_weights(verdicts):
-    _passed(verdicts, "check_weighted_draws")
+    passed(verdicts, "check_weighted_draws")
 
 
 def _train(tmp_path, extra, with_old=True):

@@ -19,25 +19,12 @@ from tests import priors_reference as pr
 from tests import symmetry_reference as sym
 from tests import temperature_reference as ref
 from tests import vl_reference as vlr
-from tests.engine_harness import START
+from tests.engine_harness import ALPHA, SEED
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED = 424242
-ALPHA = 0.15
 CYCLE = (0.0, 0.25, 1.0, 2.0)
-
-
-def _engine(games, visits, weight=0.25, seed=SEED, flags=0, max_plies=400, edges_per_node=96, move=None, root=None):
-    x, o, turn = START
-    cfg = link.Config(games=games, visits=visits, max_plies=max_plies, edges_per_node=edges_per_node, c_puct=1.0,
-                      dirichlet_alpha=ALPHA, dirichlet_weight=weight, start_turn=turn, seed=seed, start_x=x, start_o=o,
-                      blockers=0, flags=flags)
-    e = link.Engine(cfg)
-    if move is not None or root is not None:
-        e.set_temperature(move, root)
-    return e
 
 
 def _cycle(max_plies=400):
@@ -83,11 +70,11 @@ def test_off_is_off():
     net, games, visits, plies = eh.net(), 5, 16, 12
     ones = np.ones(plies, dtype=np.float32)
     kw = dict(max_plies=plies, flags=link.FLAG_KEEP_UNFINISHED)
-    never = _engine(games, visits, **kw)
-    unit = _engine(games, visits, move=ones, root=ones, **kw)
-    cleared = _engine(games, visits, move=_cycle(plies), root=np.full(plies, 1.25, np.float32), **kw)
+    never = eh.root_engine(games, visits, weight=0.25, **kw)
+    unit = eh.root_engine(games, visits, weight=0.25, temperature=(ones, ones), **kw)
+    cleared = eh.root_engine(games, visits, weight=0.25, temperature=(_cycle(plies), np.full(plies, 1.25, np.float32)), **kw)
     cleared.set_temperature(None, None)
-    on = _engine(games, visits, move=np.zeros(plies, np.float32), **kw)
+    on = eh.root_engine(games, visits, weight=0.25, temperature=(np.zeros(plies, np.float32), None), **kw)
     words = {}
     for e in (never, unit, cleared, on):
         e.run(net, 400, link.DTYPE_F32)
@@ -108,7 +95,7 @@ def test_off_is_off():
 @pytest.mark.parametrize("games", [5, 68])
 def test_every_ply_obeys_the_rule_with_host_stepping(games):
     table = _cycle()
-    e = _engine(games, 24, move=table)
+    e = eh.root_engine(games, 24, weight=0.25, temperature=(table, None))
     recs = []
     for it in range(3000):
         eh.step(e)
@@ -126,7 +113,7 @@ def test_every_ply_obeys_the_rule_with_host_stepping(games):
 @pytest.mark.parametrize("games", [5, 68])
 def test_every_ply_obeys_the_rule_in_the_device_loop(games):
     net, table = eh.net(), _cycle()
-    e = _engine(games, 24, move=table)
+    e = eh.root_engine(games, 24, weight=0.25, temperature=(table, None))
     recs = []
     for chunk in range(6):
         e.run(net, 300, link.DTYPE_BF16)
@@ -144,7 +131,7 @@ def test_every_ply_obeys_the_rule_in_the_device_loop(games):
 @pytest.mark.parametrize("games", [5, 68])
 def test_every_ply_obeys_the_rule_with_two_engines_enqueued_in_turn(games):
     net, table = eh.net(), _cycle()
-    engines = [_engine(games, 24, seed=SEED + 1000003 * i, move=table) for i in range(2)]
+    engines = [eh.root_engine(games, 24, weight=0.25, seed=SEED + 1000003 * i, temperature=(table, None)) for i in range(2)]
     recs = [[], []]
     for chunk in range(6):
         link.run_engines(engines, net, 300, link.DTYPE_BF16)
@@ -256,7 +243,7 @@ def test_root_priors_are_the_references(weight, R, symmetry, K):
     G, visits = 4, 16
     table = np.full(400, 2.0, dtype=np.float32)   # (the later plies' entry differs, so an index slip would show)
     table[0] = R
-    e = _engine(G, visits, weight=weight, root=table)
+    e = eh.root_engine(G, visits, weight=weight, temperature=(None, table))
     if symmetry:
         e.set_random_symmetry(True)
     if K > 1:
@@ -300,7 +287,7 @@ def test_plies_with_an_entry_of_one_and_fast_plies_keep_their_priors(K):
     one_first[0] = 1.0
 
     def make(root, capped):
-        e = _engine(G, visits, root=root)
+        e = eh.root_engine(G, visits, weight=0.25, temperature=(None, root))
         if K > 1:
             e.set_leaf_batch(K, 1)
         if capped:
@@ -334,7 +321,7 @@ def test_plies_with_an_entry_of_one_and_fast_plies_keep_their_priors(K):
 
 def test_fast_plies_of_the_playout_cap_sample_by_the_table_too():
     net, table, games = eh.net(), _cycle(), 9
-    e = _engine(games, 24, move=table)
+    e = eh.root_engine(games, 24, weight=0.25, temperature=(table, None))
     e.set_playout_cap(6, 32768)
     recs = []
     for chunk in range(6):
@@ -358,7 +345,7 @@ def test_fast_plies_of_the_playout_cap_sample_by_the_table_too():
 
 def test_with_forced_playouts_the_pick_is_made_on_the_raw_counts():
     k, table = 2.0, _cycle()
-    e = _engine(1, 48, move=table)
+    e = eh.root_engine(1, 48, weight=0.25, temperature=(table, None))
     e.set_forced_playouts(k)
     expected, done, pruned = {}, 0, 0
     for it in range(9000):
@@ -388,7 +375,7 @@ def test_with_forced_playouts_the_pick_is_made_on_the_raw_counts():
 def test_with_recorded_values_and_a_resign_threshold_both_rules_hold():
     net, table, games = eh.net(), _cycle(), 12
     q_below, consecutive, share = 0.45, 2, 16384
-    e = _engine(games, 24, weight=0.0, move=table)
+    e = eh.root_engine(games, 24, weight=0.0, temperature=(table, None))
     e.set_resign(q_below, consecutive, share)
     recs = []
     for chunk in range(6):
@@ -424,14 +411,14 @@ def test_refusals_leave_the_engine_as_it_was():
     net = eh.net()
     good = np.ones(400, dtype=np.float32)
     for flags in (link.FLAG_ONE_RANDOM_MOVE, link.FLAG_SAMPLE_POW5, link.FLAG_PY_POSTERIOR, link.FLAG_TWO_NETS):
-        e, twin = _engine(5, 16, flags=flags), _engine(5, 16, flags=flags)
+        e, twin = eh.root_engine(5, 16, weight=0.25, flags=flags), eh.root_engine(5, 16, weight=0.25, flags=flags)
         for move, root in ((_cycle(), None), (None, good * 1.25), (good, good)):
             with pytest.raises(link.AzhError, match="not supported"):
                 e.set_temperature(move, root)
         _continue_beside_a_twin(e, twin, net, arena=flags == link.FLAG_TWO_NETS)
         e.close(), twin.close()
     kept = _cycle()
-    e, twin = _engine(5, 16, move=kept, root=good * 1.25), _engine(5, 16, move=kept, root=good * 1.25)
+    e, twin = (eh.root_engine(5, 16, weight=0.25, temperature=(kept, good * 1.25)) for _ in range(2))
     for x in (e, twin):
         x.run(net, 100, link.DTYPE_F32)
         x.sync()

@@ -13,6 +13,7 @@ import pytest
 from ataxxzero_amd import link, model, selfplay, uai
 from tests import rules_reference as rr
 from tests import walls_fixtures as wf
+from tests.fresh_process import passed, verdicts_of
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,24 +22,15 @@ REFUSAL = "not its own image under all 8 symmetries"
 
 @pytest.fixture(scope="module")
 def verdicts(tmp_path_factory):
-    path = str(tmp_path_factory.mktemp("walls") / "verdicts.json")
-    res = subprocess.run([sys.executable, "-m", "tests.walls_gpu_checks", path], cwd=ROOT, capture_output=True, timeout=600)
-    assert res.returncode == 0 and os.path.exists(path), (res.stdout.decode()[-2000:], res.stderr.decode()[-4000:])
-    with open(path) as f:
-        return json.load(f)
-
-
-def _passed(verdicts, name):
-    assert name in verdicts, "not run: an earlier check ended in a device error (%s)" % ", ".join(verdicts)
-    assert verdicts[name] == "ok", "\n" + verdicts[name]
+    return verdicts_of("tests.walls_gpu_checks", str(tmp_path_factory.mktemp("walls") / "verdicts.json"))
 
 
 def test_gather_writes_the_walls_of_every_game(verdicts):
-    _passed(verdicts, "check_gather_with_walls")
+    passed(verdicts, "check_gather_with_walls")
 
 
 def test_surprise_kernel_with_walls_equals_the_host(verdicts):
-    _passed(verdicts, "check_surprise_with_walls")
+    passed(verdicts, "check_surprise_with_walls")
 
 
 @pytest.fixture(scope="module")

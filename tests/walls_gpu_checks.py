@@ -1,17 +1,14 @@
 """The device checks of tests/test_gpu_walls.py on the sample store, run in a process of their own for the reason
 tests/samples_gpu_checks.py gives: torch's runtime must be loaded first.  `python -m tests.walls_gpu_checks OUT.json` runs every
 check and writes {name: "ok" | traceback}; after a check that ends in a device error nothing more is run."""
-import json
-import sys
-import traceback
-
 import numpy as np
 import torch
 
 from ataxxzero_amd import link, model, selfplay, training
+from tests import fresh_process
 from tests import rules_reference as rr
 from tests import walls_fixtures as wf
-from tests.samples_gpu_checks import host, same, store_of
+from tests.store_checks import arrays_of, first_three, host, same, store_of_entries
 
 F32 = np.float32
 PASS = link.SAMPLES_PLY_PASS
@@ -19,23 +16,11 @@ ASYMMETRIC = selfplay.parse_fen(wf.ASYMMETRIC_FEN)[2]
 DEFAULT = selfplay.parse_fen(wf.DEFAULT_FEN)[2]
 
 
-def reference_for(entries, draws):
-    """The host pipeline's arrays for given draws (game, ply, symmetry), sample by sample with its own functions."""
-    feats, pols, vals = [], [], []
-    for g, ply, s in draws:
-        e = entries[g]
-        mover = 1 + ply % 2
-        feats.append(training.apply_symmetry(s, training.board_to_features(e["boards"][ply], mover, e.get("blockers"))))
-        pols.append(training._policy_target(e, ply, s))
-        vals.append([training._value_target(e, ply, mover, 0.0)])
-    return np.asarray(feats, dtype=F32), np.asarray(pols, dtype=F32), np.asarray(vals, dtype=F32)
-
-
 # ---------------------------------------------------------------- 8. the gather
 
 def check_gather_with_walls():
     entries, _ = wf.mixed_entries()
-    store = store_of(entries, spare=8)
+    store = store_of_entries(entries, spare=8)
     masks = store.game_blockers()
     assert masks.tolist() == [DEFAULT, 0, ASYMMETRIC, ASYMMETRIC, DEFAULT, 0]
     # every (game, ply, symmetry) of a grid: all 8 symmetries, both movers, the three kinds of game
@@ -43,7 +28,7 @@ def check_gather_with_walls():
             for s in range(8)]
     assert len(grid) >= 6 * 3 * 8
     got = host(store.gather(np.array(grid, dtype=np.int32)))
-    want = reference_for(entries, grid)
+    want = first_three(entries, grid)
     same(got, want)
     walls = got[0][..., 3].reshape(len(grid), -1).sum(axis=1)
     assert [int(walls[i]) for i, (g, _, _) in enumerate(grid)] == [(0 if not masks[g] else 4) for g, _, _ in grid]
@@ -66,7 +51,7 @@ def check_gather_with_walls():
     for i in range(n):
         assert tuple(int(v) for v in draws[i]) == store.draw(77, 3, i, 0, len(entries)), i
     same(out, host(store.gather(draws[:, :3])))
-    same(out, reference_for(entries, [tuple(int(v) for v in row[:3]) for row in draws]))
+    same(out, first_three(entries, [tuple(int(v) for v in row[:3]) for row in draws]))
     assert {int(g) for g in draws[:, 0]} == set(range(6)) and {int(s) for s in draws[:, 2]} == set(range(8))
     assert store.status() == 0
     # refusals leave the store as it was
@@ -89,10 +74,10 @@ def check_gather_with_walls():
         raise AssertionError("a descending wall list was accepted")
     assert store.counts() == before
     # an unwalled store never allocates the masks and gathers what it did
-    plain = store_of([entries[1], entries[5]])
+    plain = store_of_entries([entries[1], entries[5]])
     assert plain.game_blockers().tolist() == [0, 0]
     rows = [(g, ply, s) for g in (0, 1) for ply in (0, 1) for s in range(8)]
-    same(host(plain.gather(np.array(rows, dtype=np.int32))), reference_for([entries[1], entries[5]], rows))
+    same(host(plain.gather(np.array(rows, dtype=np.int32))), first_three([entries[1], entries[5]], rows))
     plain.close()
     store.close()
 
@@ -120,22 +105,6 @@ def seam_positions():
     found[1] = (1, everything & ~(1 | corner_walls | (1 << 7)), corner_walls)
     stuck = (1, everything & ~(1 | corner_walls), corner_walls)
     return found, stuck
-
-
-def arrays_of(games):
-    """games: [(walls, [(mover, opponent, flags, target indices, target weights)] per ply)] -> link.SampleArrays."""
-    rows, boards, flags, start, index, weight, masks = [], [], [], [0], [], [], []
-    for walls, plies in games:
-        rows.append((len(flags), len(plies), 1, 0))
-        masks.append(walls)
-        for p, (mover, opponent, f, t_index, t_weight) in enumerate(plies):
-            boards.append((mover, opponent) if p % 2 == 0 else (opponent, mover))
-            flags.append(f)
-            index.extend(int(i) for i in t_index)
-            weight.extend(float(w) for w in t_weight)
-            start.append(len(index))
-    return link.SampleArrays(rows, np.array(boards, dtype=np.uint64), flags, np.zeros(len(flags)), start,
-                             np.array(index, dtype=np.uint16), np.array(weight, dtype=F32), np.array(masks, dtype=np.uint64))
 
 
 def surprise_games():
@@ -236,24 +205,5 @@ def check_surprise_with_walls():
 CHECKS = [check_gather_with_walls, check_surprise_with_walls]
 
 
-def main(path):
-    link.require_gpu()
-    link.require_torch_runtime()
-    results = {}
-    for check in CHECKS:
-        try:
-            check()
-            results[check.__name__] = "ok"
-        except Exception:
-            results[check.__name__] = traceback.format_exc()
-            text = results[check.__name__].lower()
-            if ("hip" in text and "failed at" in text) or "illegal memory access" in text or "hip error" in text:
-                break                                  # a device error: nothing more runs on this GPU
-        with open(path, "w") as f:
-            json.dump(results, f, indent=1)
-    with open(path, "w") as f:
-        json.dump(results, f, indent=1)
-
-
 if __name__ == "__main__":
-    main(sys.argv[1])
+    fresh_process.main(CHECKS)
