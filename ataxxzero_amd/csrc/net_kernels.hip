@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <cmath>
 #include <stdlib.h>
 #include <stdio.h>
 #include <mutex>
@@ -413,7 +414,8 @@ __device__ inline void conv_layer(unsigned char *lds, int in_img, int out_img, b
             a[i] = t[i];
     }
 
-    // epilogue: relu, convert, write [cell][channel]
+    // epilogue: relu, convert, write [cell][channel].  relu as IEEE has it and as the emulator (oracle/net_oracle.py) states it:
+    // a NaN stays a NaN, +inf stays +inf, -inf and -0 give a zero — "v < 0 ? 0 : v", never "v > 0 ? v : 0", which erases a NaN
 #pragma unroll
     for (int ct = 0; ct < NT; ct++) {
         const int cell = ct * 32 + r;
@@ -428,13 +430,13 @@ __device__ inline void conv_layer(unsigned char *lds, int in_img, int out_img, b
                 if constexpr (DT == AZH_DTYPE_F32) {
 #pragma unroll
                     for (int i = 0; i < 4; i++)
-                        *reinterpret_cast<float *>(lds + G::ch_off(G::real_slot(out_img, cell), ch + i)) = v[i] > 0.0f ? v[i] : 0.0f;
+                        *reinterpret_cast<float *>(lds + G::ch_off(G::real_slot(out_img, cell), ch + i)) = v[i] < 0.0f ? 0.0f : v[i];
                 } else {
                     typedef typename Tr::pair pair;
                     const int off = G::ch_off(G::real_slot(out_img, cell), ch);
 #pragma unroll
                     for (int i = 0; i < 4; i++)
-                        v[i] = v[i] > 0.0f ? v[i] : 0.0f;
+                        v[i] = v[i] < 0.0f ? 0.0f : v[i];
                     f32x2 lo, hi;
                     lo[0] = v[0]; lo[1] = v[1]; hi[0] = v[2]; hi[1] = v[3];
                     const pair plo = __builtin_convertvector(lo, pair), phi = __builtin_convertvector(hi, pair);
@@ -745,11 +747,34 @@ __device__ constexpr bool skip_pair(int chf, int ct, int inner)
     return (ct == 0 && inner == 0) || (ct == 1 && inner == 2) || (chf == 0 && ct == 4 && inner == 2);
 }
 
+// relu and conversion of two accumulators to a packed 16-bit pair.  Conversion and relu commute for NUMBERS (both are monotone
+// and keep the sign); they differ in what becomes of a NaN, and the NaN that the MI355X generates (inf - inf, 0 * inf, in the
+// matrix unit and in the adders, every format) is 0xFFC00000: its sign bit is SET (measured, tests/test_gpu_net_edges.py).
+//   f16   v_pk_maximum3_f16 on the converted pair — IEEE maximum, as the emulator (oracle/net_oracle.py) states relu: a NaN
+//         stays a NaN, +inf stays +inf, -inf and -0 give +0.  One instruction per pair, as many as the integer max it replaced.
+//   bf16  a packed integer max with 0 on the 16-bit patterns (a negative bf16 is a negative int16).  It clears every pattern
+//         with the sign bit set, the generated NaN among them: where an activation is a NaN this tower goes on with 0, and the
+//         f32 tower, the 32x32 towers, the f16 tower and the emulator say NaN.  bf16 has no packed maximum; v_maximum3_f32
+//         before the conversion (two instructions more per four channels) is right and was measured against the headline:
+//         DESIGN.md, "Towers at the edges of their formats".  Known, pinned by strict expected failures in the tests.
+template <int DT> __device__ inline unsigned relu_pack(f32x2 v)
+{
+    typedef typename Traits<DT>::pair pair;
+    const pair p = __builtin_convertvector(v, pair);
+    if constexpr (DT == AZH_DTYPE_F16) {
+        const pair zero = {0, 0};
+        return __builtin_bit_cast(unsigned, __builtin_elementwise_maximum(p, zero));
+    } else {
+        typedef short short2v __attribute__((ext_vector_type(2)));
+        const short2v zero2 = {0, 0};
+        return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(short2v, p), zero2));
+    }
+}
+
 // Epilogue of a variant-2 layer — relu, convert, write 4 channels (8 bytes) per (A tile, cell tile) into image out_img —
 // as TEXT shared by conv_layer2 and first_layer2 (as a function taking the 80 accumulator registers by reference it
-// made the kernel spill 240 of them).  relu after the conversion, on the packed pair: a negative bf16 / f16 is a negative
-// int16, so one packed integer max with 0 clears it (conversion and relu commute: both are monotone and keep the sign).
-// Uses lds, out_img, acc, vmask, cellv, cbase, kg, NA, Tr, G, TPW of the enclosing function.
+// made the kernel spill 240 of them).  relu and conversion: relu_pack below.
+// Uses lds, out_img, acc, vmask, cellv, cbase, kg, NA, DT, G, TPW of the enclosing function.
 #if AZH_OOBZERO
 #define AZH_LAYER_EPILOGUE2 \
     _Pragma("unroll") \
@@ -764,13 +789,9 @@ __device__ constexpr bool skip_pair(int chf, int ct, int inner)
                     v[i] = acc[t][ct][i]; \
                 f32x2 lo, hi; \
                 lo[0] = v[0]; lo[1] = v[1]; hi[0] = v[2]; hi[1] = v[3]; \
-                typedef typename Tr::pair pair; \
-                const pair plo = __builtin_convertvector(lo, pair), phi = __builtin_convertvector(hi, pair); \
                 uint2 packed; \
-                typedef short short2v __attribute__((ext_vector_type(2))); \
-                const short2v zero2 = {0, 0}; \
-                packed.x = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(short2v, plo), zero2)); \
-                packed.y = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(short2v, phi), zero2)); \
+                packed.x = relu_pack<DT>(lo); \
+                packed.y = relu_pack<DT>(hi); \
                 *reinterpret_cast<uint2 *>(lds + cellq + G::ch_off(0, cbase + 16 * t + 4 * kg)) = packed; \
             } \
         } \
@@ -789,13 +810,9 @@ __device__ constexpr bool skip_pair(int chf, int ct, int inner)
                     v[i] = acc[t][ct][i]; \
                 f32x2 lo, hi; \
                 lo[0] = v[0]; lo[1] = v[1]; hi[0] = v[2]; hi[1] = v[3]; \
-                typedef typename Tr::pair pair; \
-                const pair plo = __builtin_convertvector(lo, pair), phi = __builtin_convertvector(hi, pair); \
                 uint2 packed; \
-                typedef short short2v __attribute__((ext_vector_type(2))); \
-                const short2v zero2 = {0, 0}; \
-                packed.x = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(short2v, plo), zero2)); \
-                packed.y = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(short2v, phi), zero2)); \
+                packed.x = relu_pack<DT>(lo); \
+                packed.y = relu_pack<DT>(hi); \
                 *reinterpret_cast<uint2 *>(lds + G::ch_off(G::real_slot(out_img, cell), cbase + 16 * t + 4 * kg)) = packed; \
             } \
         } \
@@ -1491,6 +1508,23 @@ static int net_pack(azh_net *net, int dt)
     const int ks_in = dt == AZH_DTYPE_F32 ? 2 : 1;
     const int ks_full = F / kstep;
     const size_t head_off = (size_t)9 * 4 * F + (size_t)2 * B * 9 * F * F;
+    // A finite folded tower weight that this dtype rounds to an infinity (70000 in f16; a product beyond the f32 range in any
+    // dtype) is refused before anything is allocated: the net stays usable in the dtypes that hold it.  (azh_net_create has
+    // checked that weights and scales are finite; the heads are not restricted.)
+    for (int l = 0; l < 2 * B + 1; l++) {
+        const float *w = p + (l == 0 ? 0 : (size_t)9 * 4 * F + (size_t)(l - 1) * 9 * F * F);
+        const float *sc = net->scale.data() + (size_t)l * F;
+        const size_t nw = (size_t)9 * (l == 0 ? 4 : F) * F;
+        for (size_t i = 0; i < nw; i++) {
+            const float v = w[i] * sc[i % F];
+            bool inf = !std::isfinite(v);
+            if (dt != AZH_DTYPE_F32)
+                inf = inf || (cvt_elem<uint16_t>(v, dt) & 0x7FFF) >= (dt == AZH_DTYPE_BF16 ? 0x7F80 : 0x7C00);
+            if (inf)
+                return azh_fail(-2, "tower layer %d: weight %zu (output channel %zu), %g times the batch-norm scale %g, is not "
+                                    "finite in dtype %d", l, i, i % F, (double)w[i], (double)sc[i % F], dt);
+        }
+    }
     // fused head matrix [128][32]: columns 0..16 policy, 17 value conv
     std::vector<float> head((size_t)F * 32, 0.0f);
     for (int c = 0; c < F; c++) {
@@ -1629,6 +1663,35 @@ extern "C" int azh_net_create(int blocks, int filters, const float *conv_flat, c
     const int F = filters;
     if (blocks < 0 || blocks > 64)
         return azh_fail(-2, "azh_net_create: bad block count %d", blocks);
+    const size_t n_conv = (size_t)9 * 4 * F + (size_t)2 * blocks * 9 * F * F + (size_t)F * 17 + F + 49 + 1;
+    const int nbn = 2 * blocks + 1;
+    std::vector<float> scale((size_t)nbn * F), shift((size_t)(nbn + 1) * F, 0.0f);  // + one look-ahead row
+    // A tower whose numbers are not finite is refused, not run (a diverged trainer writes NaNs): with a NaN or an infinity in
+    // a tower weight the result would depend on which 0 * NaN a kernel happens to form (skipped taps, zero slots), per cell,
+    // per tile and per variant.  Checked before the device is touched: every tower convolution weight, every batch-norm
+    // mean, every derived scale and shift (var + eps <= 0 gives an infinite or NaN scale).  The two 1x1 heads, fc_w and fc_b
+    // stay unrestricted: what they do with an infinity is defined and tested (tests/helpers.py, nonfinite_net).
+    for (int l = 0; l < nbn; l++) {
+        const float *w = conv_flat + (l == 0 ? 0 : (size_t)9 * 4 * F + (size_t)(l - 1) * 9 * F * F);
+        const size_t nw = (size_t)9 * (l == 0 ? 4 : F) * F;
+        for (size_t i = 0; i < nw; i++)
+            if (!std::isfinite(w[i]))
+                return azh_fail(-2, "azh_net_create: tower layer %d: convolution weight %zu (output channel %zu) is %g, not a "
+                                    "finite number", l, i, i % F, (double)w[i]);
+        for (int c = 0; c < F; c++) {
+            const float mean = bn_flat[((size_t)2 * l) * F + c], var = bn_flat[((size_t)2 * l + 1) * F + c];
+            const double inv = 1.0 / sqrt((double)var + (double)bn_eps);
+            scale[(size_t)l * F + c] = (float)inv;
+            shift[(size_t)l * F + c] = (float)(-(double)mean * inv);
+            if (!std::isfinite(mean))
+                return azh_fail(-2, "azh_net_create: tower layer %d: batch-norm mean of channel %d is %g, not a finite number",
+                                l, c, (double)mean);
+            if (!std::isfinite(scale[(size_t)l * F + c]) || !std::isfinite(shift[(size_t)l * F + c]))
+                return azh_fail(-2, "azh_net_create: tower layer %d: batch-norm channel %d (mean %g, variance %g, eps %g) gives "
+                                    "scale %g and shift %g, not finite numbers", l, c, (double)mean, (double)var, (double)bn_eps,
+                                (double)scale[(size_t)l * F + c], (double)shift[(size_t)l * F + c]);
+        }
+    }
     if (azh_require_device())
         return -3;
 #if AZH_OOBZERO
@@ -1638,17 +1701,7 @@ extern "C" int azh_net_create(int blocks, int filters, const float *conv_flat, c
     azh_net *net = new azh_net();
     net->blocks = blocks;
     net->filters = filters;
-    const size_t n_conv = (size_t)9 * 4 * F + (size_t)2 * blocks * 9 * F * F + (size_t)F * 17 + F + 49 + 1;
     net->conv_flat.assign(conv_flat, conv_flat + n_conv);
-    const int nbn = 2 * blocks + 1;
-    std::vector<float> scale((size_t)nbn * F), shift((size_t)(nbn + 1) * F, 0.0f);  // + one look-ahead row
-    for (int l = 0; l < nbn; l++)
-        for (int c = 0; c < F; c++) {
-            const float mean = bn_flat[((size_t)2 * l) * F + c], var = bn_flat[((size_t)2 * l + 1) * F + c];
-            const double inv = 1.0 / sqrt((double)var + (double)bn_eps);
-            scale[(size_t)l * F + c] = (float)inv;
-            shift[(size_t)l * F + c] = (float)(-(double)mean * inv);
-        }
     const float *fc = conv_flat + n_conv - 50;
     net->fc_b = fc[49];
     net->scale = scale;
@@ -1920,8 +1973,8 @@ int azh_net_launch(azh_net *net, int dtype, const NetBatch &b, hipStream_t strea
     if (int rc = choose_tower(net->filters, dtype, o.thin != 0, o.stamps != nullptr, false, tower_variant() == 1,
                               tower_boards() == 6, lds_range_ok(), &k))
         return rc;
-    if (net_pack(net, dtype))
-        return -1;
+    if (int rc = net_pack(net, dtype))
+        return rc;  // (-2: a tower weight is not finite in this dtype; nothing is launched)
     const int n = sym ? 8 * b.max_n : b.max_n;  // grid size: virtual boards
     if (int rc = launch_tower(*k, (n + k->boards - 1) / k->boards, tower_args(net, dtype, b, o), nullptr, stream, o.hook))
         return rc;
@@ -1942,8 +1995,10 @@ int azh_net_launch_pair(azh_net *net_a, azh_net *net_b, int dtype, const NetBatc
     if (int rc = choose_tower(net_a->filters, dtype, o.thin != 0, o.stamps != nullptr, true, tower_variant() == 1,
                               tower_boards() == 6, lds_range_ok(), &k))
         return rc;
-    if (net_pack(net_a, dtype) || net_pack(net_b, dtype))
-        return -1;
+    if (int rc = net_pack(net_a, dtype))
+        return rc;
+    if (int rc = net_pack(net_b, dtype))
+        return rc;
     NetBatch second = b;
     second.list = list_b;
     second.count = count_b;

@@ -675,7 +675,14 @@ def _board_masks(blockers, n):
 
 
 class Net:
-    """Device-resident policy/value net (model.Network forward, model.py:38-79)."""
+    """Device-resident policy/value net (model.Network forward, model.py:38-79).
+    AzhError (error -2, the message names the tower layer): a tower convolution weight, a batch-norm mean or a derived
+    scale or shift is not finite — raised here, before a device is needed; or, from forward() and the engine's launches,
+    a finite tower weight is infinite in the dtype asked for (the net still serves the other dtypes).  The two 1x1 heads,
+    fc_w and fc_b may hold anything.
+    Activations may still overflow from finite weights; infinities and NaNs then travel as IEEE arithmetic has them (ReLU
+    keeps a NaN) in every tower but the default bf16 one at 128 filters (k_tower2, k_tower2_thin and k_tower2_pair in
+    bf16), whose ReLU turns a NaN activation into 0: include/ataxxzero_hip.h at azh_net_forward."""
 
     def __init__(self, conv_weights, bn_params, bn_eps=1e-3):
         blocks = (len(conv_weights) - 5) // 2

@@ -135,13 +135,26 @@ typedef struct azh_net azh_net;
  * second list, (moving_mean, moving_variance) per batch-norm in creation order.
  * gamma = 1, beta = 0 as after model.load_model;
  * bn_eps is TensorFlow's default 1e-3.  filters: 128 (model.py:16; the tuned towers), 64 or 256 (model.Network.FILTERS
- * is a class attribute that uai_interface.py:92-93 patches: these run on the width-templated 32x32 tower). */
+ * is a class attribute that uai_interface.py:92-93 patches: these run on the width-templated 32x32 tower).
+ * A tower whose numbers are not finite is refused, not run: -2, with a message that names the tower layer, when a tower
+ * convolution weight, a batch-norm mean, or a derived batch-norm scale 1 / sqrt(var + eps) or shift -mean * scale is a NaN or
+ * an infinity (var + eps <= 0 is the usual cause).  The check needs no device and comes before the device is asked for.  The
+ * policy and value 1x1 heads, fc_w and fc_b are not restricted: an infinity there gives infinite logits, values of +-1 and
+ * NaNs exactly where IEEE arithmetic puts them, in every tower. */
 int azh_net_create(int blocks, int filters, const float *conv_flat, const float *bn_flat,
                    float bn_eps, azh_net **out);
 void azh_net_destroy(azh_net *net);
 
 /* The forward pass of n leaf boards (mover, opponent): logits_out [n][833] f32 (raw policy logits, model.py:66-69), values_out
  * [n] (tanh value, model.py:71-79).  Null arguments and n < 0: -1; a mode outside the enum: -2.
+ * A net with a finite tower weight that `dtype` rounds to an infinity after the batch-norm scale is folded in (70000 in f16):
+ * -2, the message names the layer; nothing is launched and nothing allocated, and the net goes on serving the dtypes that
+ * hold it.  (The engine's launches pass the same refusal on.)  Activations may still overflow from finite weights: an f16
+ * activation of 65520 or more is +inf, and the layers after it carry infinities and NaNs as IEEE arithmetic has them — ReLU
+ * keeps a NaN and +inf and turns -inf into 0 — identically in every tower kernel (tests/test_gpu_net_edges.py) but one family:
+ * the bf16 16x16x32 towers (k_tower2<bf16>, k_tower2_thin<bf16>, k_tower2_pair<bf16>: the default bf16 path at 128 filters)
+ * take ReLU as an integer max on the bit pattern and turn a NaN activation into 0, so a bf16 net whose f32 accumulators
+ * overflow goes on with finite numbers there where f32, f16 and the 32x32 towers (AZH_TOWER=1) report NaN.
  * mode: AZH_FORWARD_PLAIN, the ordinary tower, or
  *   AZH_FORWARD_THIN   THIN batches (a match's last games, a UAI engine's single position): the 16-bit towers with ONE board
  *     per workgroup — the latency of a launch of a handful of boards is one workgroup's time for the 25 layers, and a board

@@ -105,23 +105,36 @@ def forward_sym(conv_weights, bn_params, features, dtype=np.float64):
 #
 # forward_lowp restates what the HIP towers (ataxxzero_amd/csrc/net_kernels.hip) compute, in float64 with a rounding at
 # exactly the places where the kernels round (line numbers of net_kernels.hip):
-#   batch norm   azh_net_create :1643-1646: inv = 1/sqrt(double(var) + double(eps)), eps arriving as a float (link.Net
+#   batch norm   azh_net_create :1683-1685: inv = 1/sqrt(double(var) + double(eps)), eps arriving as a float (link.Net
 #                passes a c_float); scale = float(inv), shift = float(-double(mean) * inv)
-#   conv weights pack_conv :1423-1440, pack_conv16 :1443-1458, the im2col first layer :1528-1537: the float product
-#                w * scale, rounded once to bf16 / f16 (f32_to_bf16 :1398, f32_to_f16 :1408: round to nearest even)
-#   head weights net_pack :1490-1495: the policy and value 1x1 convolutions rounded to 16 bits without a scale
+#   conv weights pack_conv :1444, pack_conv16 :1464, the im2col first layer :1567 (net_pack): the float product
+#                w * scale, rounded once to bf16 / f16 (f32_to_bf16 :1419, f32_to_f16 :1429: round to nearest even)
+#   head weights net_pack :1528: the policy and value 1x1 convolutions rounded to 16 bits without a scale
 #   input planes exact 0 / 1
-#   each layer   the f32 accumulator starts at the shift (:246, :832-842) plus, for a block's second convolution, the
-#                stored 16-bit residual input (:272, :868), and sums the products; the epilogue converts the sum to 16
-#                bits with round to nearest even (__builtin_convertvector, :439, :766) and applies ReLU, which commutes
-#                with the conversion (:746-750)
-#   outputs      logits = the f32 head accumulators (:591, :1313-1315); the value conv channel stays f32 (:593, :1316);
-#                value = tanhf(s + fc_b), s the fmaf chain over c = 7 x + y of vcell[c] * fc_w[c] (:603-604, :1326-1327)
+#   each layer   the f32 accumulator starts at the shift (:248, :860) plus, for a block's second convolution, the
+#                stored 16-bit residual input (:274, :887), and sums the products; the epilogue converts the sum to 16
+#                bits with round to nearest even (__builtin_convertvector, :442, relu_pack :763) and applies ReLU.
+#                ReLU is IEEE's maximum with 0, here and in the kernels: a NaN stays a NaN, +inf stays +inf, -inf and -0
+#                give a zero.  For numbers it commutes with the conversion; for a NaN it does not commute with every
+#                way of taking it: the bf16 16x16x32 towers (k_tower2, k_tower2_thin, k_tower2_pair) take a packed
+#                integer max on the converted pair and clear the NaN the device generates, whose sign bit is set
+#                (relu_pack :760).  That behaviour is the defect "relu_erases_negative_nan_only" below, and
+#                tests/test_gpu_net_edges.py pins the bf16 towers to it bit for bit.
+#   edges        measured on the MI355X (tests/test_gpu_net_edges.py on the nets of tests/net_edges.py): the MFMAs keep
+#                subnormal 16-bit and f32 operands and accumulators, the conversions round ties to even down to half the
+#                smallest subnormal and overflow to infinity at the tie (65520 in f16), tanhf returns a subnormal argument
+#                and +-1 for an infinite one — all as numpy computes them below, so no hardware switch exists here.  The
+#                NaN the device generates is 0xFFC00000; a NaN is compared as a NaN, whatever its sign.
+#   outputs      logits = the f32 head accumulators (:595; tower2_run); the value conv channel stays f32 (:597);
+#                value = tanhf(s + fc_b), s the fmaf chain over c = 7 x + y of vcell[c] * fc_w[c] (:607-608, :1347-1348)
 # The sums themselves are taken in float64 and rounded to float once: on nets whose products and partial sums are all
 # exact in f32 (tests/net_exact.py) that IS the kernels' accumulator in every summation order; elsewhere the two differ
 # by accumulation-order noise.  fmt "f32" is the f32 tower (the same folding, no 16-bit rounding anywhere).
 
 LOWP_FORMATS = ("f32", "bf16", "f16")
+# The sign bit of the NaN that the MI355X generates (inf - inf, 0 * inf; matrix unit and adders, every format): the pattern
+# is 0xFFC00000, measured by tests/test_gpu_net_edges.py on the overflow nets.  Only a ReLU taken on bit patterns can tell.
+GENERATED_NAN_SIGN_BIT = 1
 
 
 def round_bf16(x):
@@ -163,7 +176,7 @@ def _rounder(fmt):
 
 
 def bn_constants(mean, var, eps=BN_EPS):
-    """(scale, shift) as float32, as azh_net_create derives them (net_kernels.hip:1634-1650)."""
+    """(scale, shift) as float32, as azh_net_create derives them (net_kernels.hip:1683-1685)."""
     inv = 1.0 / np.sqrt(np.asarray(var, np.float32).astype(np.float64) + np.float64(np.float32(eps)))
     return inv.astype(np.float32), (-np.asarray(mean, np.float32).astype(np.float64) * inv).astype(np.float32)
 
@@ -193,15 +206,33 @@ def _truncate_f16(x):
     return np.where(np.abs(t.astype(np.float32)) > np.abs(x), np.nextafter(t, np.float16(0)), t).astype(np.float32)
 
 
+# smallest normal, smallest subnormal and largest finite value of each tower format (activations and folded weights)
+FORMAT_LIMITS = {"f32": (2.0 ** -126, 2.0 ** -149, float(np.finfo(np.float32).max)),
+                 "bf16": (2.0 ** -126, 2.0 ** -133, (2.0 - 2.0 ** -7) * 2.0 ** 127),
+                 "f16": (2.0 ** -14, 2.0 ** -24, 65504.0)}
+
+
+def _flush_subnormals(x, fmt):
+    """values below the format's smallest normal become zeros of their sign"""
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(np.abs(x) < FORMAT_LIMITS[fmt][0], np.copysign(0.0, x), x)
+
+
 def _only_tap(w, i, j):
     out = np.zeros_like(w)
     out[i, j] = w[i, j]
     return out
 
 
-def _forward_lowp(conv_weights, bn_params, features, fmt, eps=BN_EPS, defect=None):
-    """forward_lowp with an optional deliberate `defect` (tests/test_net_emulation.py's mutants: what a subtly wrong
-    kernel would compute).  -> (policy (n,7,7,17), value (n,1), activations per tower layer)."""
+def _forward_lowp(conv_weights, bn_params, features, fmt, eps=BN_EPS, defect=None, with_argument=False):
+    """forward_lowp with an optional deliberate `defect` (the mutants of tests/test_net_emulation.py and
+    tests/test_net_edges_host.py: what a subtly wrong kernel would compute).
+    -> (policy (n,7,7,17), value (n,1), activations per tower layer[, the f32 argument of tanh (n,1) with_argument])."""
+    with np.errstate(invalid="ignore", over="ignore"):       # infinities and NaNs are ordinary values here
+        return _forward_lowp_body(conv_weights, bn_params, features, fmt, eps, defect, with_argument)
+
+
+def _forward_lowp_body(conv_weights, bn_params, features, fmt, eps, defect, with_argument):
     rnd = _rounder(fmt)
     f32 = np.float32
     layers, head_p, head_v, fc_w, fc_b = lowp_parameters(conv_weights, bn_params, fmt, eps)
@@ -211,10 +242,41 @@ def _forward_lowp(conv_weights, bn_params, features, fmt, eps=BN_EPS, defect=Non
                   for i, (_, sh) in enumerate(layers)]
     if defect == "truncate" and fmt != "f32":
         rnd = _truncate_bf16 if fmt == "bf16" else _truncate_f16
+    if defect == "flush_subnormal_inputs":
+        # a matrix unit that reads subnormal A / B operands as zeros: weights here, activations where a layer reads them
+        layers = [(_flush_subnormals(w, fmt), sh) for w, sh in layers]
+        head_p, head_v = _flush_subnormals(head_p, fmt), _flush_subnormals(head_v, fmt)
     h = np.asarray(features, dtype=np.float64)
     acts = []
 
+    def relu(out):
+        """IEEE, what the kernels' epilogues are held to: a NaN stays a NaN, +inf stays +inf, -inf and -0 give a zero"""
+        if defect == "relu_erases_nan":
+            return np.where(out > 0, out, 0.0)               # "v > 0 ? v : 0": every NaN becomes 0
+        if defect == "relu_erases_negative_nan_only":
+            # a packed integer max with 0 on the 16-bit pattern: clears what has the sign bit set, a NaN included, and
+            # keeps a NaN whose sign bit is clear.  No NaN enters these towers from outside (non-finite tower weights are
+            # refused), so every NaN is one the arithmetic generated, and its sign is GENERATED_NAN_SIGN_BIT — the
+            # device's, not this host's.  With the bit set this mutant is what the bf16 16x16x32 towers compute today,
+            # and it coincides with relu_erases_nan; with the bit clear it would be the faithful ReLU.
+            erased = np.isnan(out) if GENERATED_NAN_SIGN_BIT else np.zeros(out.shape, dtype=bool)
+            return np.where(erased, 0.0, np.maximum(out, 0))
+        return np.maximum(out, 0)
+
+    def to_format(z):
+        """the f32 accumulator, converted to the format"""
+        z32 = np.asarray(z, dtype=np.float64).astype(np.float32)
+        out = rnd(z32).astype(np.float64)
+        if defect == "saturate_overflow":
+            over = np.isinf(out) & np.isfinite(z)
+            out = np.where(over, np.copysign(FORMAT_LIMITS[fmt][2], z), out)
+        if defect == "flush_subnormal_outputs":
+            out = _flush_subnormals(out, fmt)
+        return out
+
     def layer(x, w, shift, residual=None, index=0):
+        if defect == "flush_subnormal_inputs":
+            x = _flush_subnormals(x, fmt)
         z = conv2d_same(x, w.astype(np.float64))
         if defect == "edge_tap" and index > 0:
             # one on-board tap (dx = +1, dy = 0) missing for the cells of the y = 0 edge
@@ -223,10 +285,10 @@ def _forward_lowp(conv_weights, bn_params, features, fmt, eps=BN_EPS, defect=Non
         z = z + shift.astype(np.float64)
         if residual is not None and defect != "residual_after_rounding":
             z = z + residual
-        out = rnd(z.astype(np.float32)).astype(np.float64)
+        out = to_format(z)
         if residual is not None and defect == "residual_after_rounding":
-            out = rnd((out + residual).astype(np.float32)).astype(np.float64)
-        return np.maximum(out, 0)
+            out = to_format(out + residual)
+        return relu(out)
 
     blocks = (len(layers) - 1) // 2
     h = layer(h, *layers[0])
@@ -236,16 +298,19 @@ def _forward_lowp(conv_weights, bn_params, features, fmt, eps=BN_EPS, defect=Non
         acts.append(t)
         h = layer(t, *layers[2 + 2 * b], residual=h, index=2 + 2 * b)
         acts.append(h)
-    policy = (h @ head_p.astype(np.float64)).astype(np.float32)
-    vcell = (h @ head_v.astype(np.float64)).astype(np.float32)             # (n,7,7), f32
+    hh = _flush_subnormals(h, fmt) if defect == "flush_subnormal_inputs" else h
+    policy = (hh @ head_p.astype(np.float64)).astype(np.float32)
+    vcell = (hh @ head_v.astype(np.float64)).astype(np.float32)            # (n,7,7), f32
     if defect == "policy16_from_value_row":
         policy[..., 16] = vcell
     v = (np.swapaxes(vcell, 1, 2) if defect == "value_xy_swapped" else vcell).reshape(len(h), 49)
     s = np.zeros(len(h), dtype=np.float32)
     for c in range(49):                                                   # fmaf chain, c = 7 x + y (model.py:75)
         s = (v[:, c].astype(np.float64) * np.float64(fc_w[c]) + s.astype(np.float64)).astype(f32)
-    value = np.tanh((s + fc_b).astype(f32).astype(np.float64)).reshape(-1, 1)
-    return policy.astype(np.float64) + 0.0, value, acts      # (+ 0.0: a zero logit is +0, as the kernels write it)
+    arg = (s + fc_b).astype(f32).astype(np.float64).reshape(-1, 1)
+    value = np.tanh(arg)                                     # tanh(+-inf) = +-1, tanh(NaN) a NaN, tanh(-0) = -0
+    out = (policy.astype(np.float64) + 0.0, value, acts)     # (+ 0.0: a zero logit is +0, as the kernels write it)
+    return out + (arg,) if with_argument else out
 
 
 def forward_lowp(conv_weights, bn_params, features, fmt, eps=BN_EPS):

@@ -178,7 +178,9 @@ def test_zero_slot_build_of_the_tower_equals_the_default_bit_for_bit(tmp_path):
     """The default 16-bit tower reads off-board taps as out-of-range LDS addresses (AZH_OOBZERO=1: the hardware's range
     check supplies the zeros; probed per device).  Its escape hatch — the -DAZH_OOBZERO=0 build, off-board taps steered to
     zero slots inside the allocation — is compiled here and must give the same bits on the same boards, bf16 and f16:
-    the two differ only in WHERE a zero is read."""
+    the two differ only in WHERE a zero is read.  Two edge nets of tests/net_edges.py ride along — f16 activations that
+    overflow (infinities and NaNs beside the zeros that are read) and bf16 subnormals: the zero-slot build equals the
+    emulator on them by the class-aware rule of tests/net_compare.py, as the default build does in test_gpu_net_edges.py."""
     import os
     import shutil
     import subprocess
@@ -193,6 +195,17 @@ def test_zero_slot_build_of_the_tower_equals_the_default_bit_for_bit(tmp_path):
     weights, boards, out = str(tmp_path / "w.npy"), str(tmp_path / "boards.npy"), str(tmp_path / "out.npz")
     model.save_model(weights, conv, bn)
     np.save(boards, lb)
+    from tests import net_edges, net_exact
+    from tests.net_compare import assert_equals_emulator
+    edge_cases = [("overflow", 1, 128, "f16"), ("small", 1, 128, "bf16")]
+    edge_jobs = []
+    for case in edge_cases:
+        e_conv, e_bn, e_lb, _ = net_edges.edge_net(*case)
+        e_weights, e_boards = str(tmp_path / (net_edges.case_id(case) + ".npy")), str(tmp_path / (net_edges.case_id(case) + "-boards.npy"))
+        model.save_model(e_weights, e_conv, e_bn)
+        np.save(e_boards, e_lb)
+        edge_jobs.append((net_edges.case_id(case), e_weights, e_boards, net_exact.ASYM_BLOCKERS,
+                          link.DTYPE_F16 if case[3] == "f16" else link.DTYPE_BF16))
     script = ("import sys, numpy as np\n"
               "sys.path.insert(0, %r)\n"
               "from ataxxzero_amd import link, model\n"
@@ -203,8 +216,11 @@ def test_zero_slot_build_of_the_tower_equals_the_default_bit_for_bit(tmp_path):
               "for name, dt in (('bf16', link.DTYPE_BF16), ('f16', link.DTYPE_F16)):\n"
               "    p, v = net.forward(lb, %d, dt)\n"
               "    res[name + '_p'], res[name + '_v'] = p, v\n"
+              "for name, w, b, mask, dt in %r:\n"
+              "    p, v = link.Net(*model.load_model(w)).forward(np.load(b), mask, dt)\n"
+              "    res[name + '_p'], res[name + '_v'] = p, v\n"
               "np.savez(%r, **res)\n") % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), lib, lib, weights,
-                                          boards, BLOCK4_MASK, out)
+                                          boards, BLOCK4_MASK, edge_jobs, out)
     env = dict(os.environ, AZH_LIB=lib)
     res = subprocess.run([sys.executable, "-c", script], env=env, capture_output=True, timeout=600)
     assert res.returncode == 0, res.stdout.decode()[-2000:] + res.stderr.decode()[-2000:]
@@ -215,6 +231,10 @@ def test_zero_slot_build_of_the_tower_equals_the_default_bit_for_bit(tmp_path):
         assert np.abs(p).max() > 1e-3
         assert (p.view(np.uint32) == other[name + "_p"].view(np.uint32)).all(), name
         assert (v.view(np.uint32) == other[name + "_v"].view(np.uint32)).all(), name
+    for case in edge_cases:
+        ref_p, ref_v, ref_arg = net_edges.reference(*case, net_exact.ASYM_BLOCKERS)
+        name = net_edges.case_id(case)
+        assert_equals_emulator(other[name + "_p"], other[name + "_v"], ref_p, ref_v, "zero-slot build, " + name, ref_arg=ref_arg)
 
 
 def test_first_boards_of_partial_tiles_and_empty_batch():

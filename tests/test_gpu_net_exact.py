@@ -6,10 +6,6 @@ bit for bit; values are tanhf of an exact argument and may differ from the float
 the f32 tower, the 16-bit 16x16x32 tower (k_tower2) and its one-board kernel (k_tower2_thin), the symmetry average
 (k_sym_reduce), the 32x32 towers of 64 and 256 filters in every dtype, and — in child processes, the variables being read
 once per process — the 32x32 16-bit tower at 128 filters (AZH_TOWER=1, three boards and AZH_TOWER_BOARDS=6)."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -17,28 +13,19 @@ from ataxxzero_amd import link, model
 from oracle import net_oracle
 from tests import net_exact as ne
 from tests.helpers import note, sample_leaf_boards
+from tests.net_compare import assert_equals_emulator as assert_exact, run_forward_jobs
 
 pytestmark = pytest.mark.gpu
 
 DT = {"f32": link.DTYPE_F32, "bf16": link.DTYPE_BF16, "f16": link.DTYPE_F16}
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def reference(conv, bn, lb, mask, fmt):
     return net_oracle.forward_lowp(conv, bn, net_oracle.features_from_leaf_boards(lb, mask), fmt)
 
 
-def assert_exact(p, v, ref_p, ref_v, what, value_tol=None):
-    """logits bit for bit (zeros of either sign equal), values within 4 f32 ulp of the float64 tanh (or value_tol)"""
-    ref32 = ref_p.astype(np.float32)
-    bad = p != ref32
-    if bad.any():
-        i = tuple(np.argwhere(bad)[0])
-        raise AssertionError("%s: %d of %d logits differ; first at %s: kernel %r, emulator %r"
-                             % (what, bad.sum(), bad.size, i, float(p[i]), float(ref32[i])))
-    tol = value_tol if value_tol is not None else 4 * np.spacing(np.abs(ref_v).astype(np.float32)).astype(np.float64)
-    dv = np.abs(v.astype(np.float64) - ref_v)
-    assert (dv <= tol).all(), (what, "value", float(dv.max()))
+# assert_exact: logits bit for bit (zeros of either sign equal), values within 4 f32 ulp of the float64 tanh (or value_tol) —
+# tests/net_compare.py, where the rule also says what holds for infinities and NaNs (none occur on these nets)
 
 
 @pytest.mark.parametrize("case", ne.TOWER_CASES, ids=lambda c: "%dx%d-%s" % c[:3])
@@ -87,20 +74,6 @@ def test_symmetry_average_equals_the_emulator_bit_for_bit(case):
         assert (plain_p != ref_p).any()                           # the average is not the plain forward
 
 
-CHILD = """import sys, numpy as np
-sys.path.insert(0, %r)
-from ataxxzero_amd import link, model
-jobs = np.load(sys.argv[1], allow_pickle=True).item()
-out = {}
-for name, (weights, lb, mask, dtype, sym) in sorted(jobs.items()):
-    net = link.Net(*model.load_model(weights))
-    p, v = (net.forward_sym if sym else net.forward)(lb, int(mask), int(dtype))
-    out[name + '_p'], out[name + '_v'] = p, v
-    net.close()
-np.savez(sys.argv[2], **out)
-"""
-
-
 @pytest.mark.parametrize("env", [{"AZH_TOWER": "1"}, {"AZH_TOWER": "1", "AZH_TOWER_BOARDS": "6"}],
                          ids=["variant1-3boards", "variant1-6boards"])
 def test_variant1_towers_equal_the_emulator_bit_for_bit(env, tmp_path):
@@ -124,14 +97,7 @@ def test_variant1_towers_equal_the_emulator_bit_for_bit(env, tmp_path):
         ref_p, ref_v = net_oracle.forward_lowp_sym(conv, bn, net_oracle.features_from_leaf_boards(lb, ne.ASYM_BLOCKERS), case[2])
         jobs["sym-" + case[2]] = (weights, lb, ne.ASYM_BLOCKERS, DT[case[2]], 1)
         refs["sym-" + case[2]] = (ref_p, ref_v, 1e-6)
-    job_file, out = str(tmp_path / "jobs.npy"), str(tmp_path / "out.npz")
-    np.save(job_file, jobs, allow_pickle=True)
-    script = str(tmp_path / "child.py")
-    with open(script, "w") as f:
-        f.write(CHILD % ROOT)
-    res = subprocess.run([sys.executable, script, job_file, out], env=dict(os.environ, **env), capture_output=True, timeout=600)
-    assert res.returncode == 0, res.stdout.decode()[-2000:] + res.stderr.decode()[-2000:]
-    got = np.load(out)
+    got = run_forward_jobs(jobs, env, tmp_path)
     for name, (ref_p, ref_v, tol) in refs.items():
         assert_exact(got[name + "_p"], got[name + "_v"], ref_p, ref_v, "%s %s" % (env, name), value_tol=tol)
 
