@@ -4,7 +4,8 @@
 // training.make_minibatch_reference builds on the host (train.py:43-77 of the reference).  A game may carry a wall mask
 // (DESIGN.md "Walls through the loop"): plane 3 of its samples shows it, and the surprise pass generates moves around it.
 //
-// Compiled with -ffp-contract=off: the value target's blend is three IEEE double operations in Python's order.
+// Compiled with -ffp-contract=off: the value target's blend is three IEEE double operations in Python's order, and a
+// lambda-return's step four (include/ataxxzero_hip.h, "lambda-returns as value targets").
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -24,6 +25,7 @@ constexpr int MAX_ATTEMPTS = 64;  // one per lane of the wave that draws the sam
 constexpr u32 GAME_HAS_FULL = 1u << 8, GAME_HAS_VALUES = 1u << 9;
 constexpr u32 PLY_ODD = 0x80u;  // in the device's targets_flags only: o is the mover (the surprise kernel sees no game)
 constexpr u32 WEIGHT_ONE = 65536u;
+constexpr u64 RETURN_ABSENT = ~0ULL;  // the bits of a ply's lambda-return that no pass has covered (a NaN no arithmetic yields)
 constexpr int SURPRISE_CHUNK = 16384;
 // auxiliary targets (include/ataxxzero_hip.h, "Auxiliary targets"): the aux kernels' LDS behind the sample's padded floats
 constexpr int SAMPLE_LDS = (SAMPLE_FLOATS + 3) / 4 * 4;
@@ -47,7 +49,15 @@ struct View {  // what the kernels read
     const u32 *cum;  // null: uniform ply draws; else [first ply + k]: the running sum of the game's candidate weights
     const u64 *blockers;  // null: no stored game has walls; else [game]: its wall mask, bit = file + 7 * rank
     const int16_t *proofs;  // null: azh_samples_prove was never called; else [ply]: the proven value of its mover, 0: none
+    const double *returns;  // null: no lambda-returns (azh_samples_value_returns); else [ply]: G_p, RETURN_ABSENT: not covered
 };
+
+__host__ __device__ inline u64 f64_bits(double v)
+{
+    u64 bits;
+    memcpy(&bits, &v, sizeof(bits));
+    return bits;
+}
 
 struct NoAux {};  // the kernels without auxiliary targets: emit_sample is what it was
 struct Aux {      // the four further outputs, and where the owners come from
@@ -86,7 +96,10 @@ __device__ void emit_sample(const View &v, float *lds, int i, int g, int p, int 
         if (lane == 0) {
             const int z = (int)(game.z & 0xFFu) == mover ? 1 : -1;
             float out = (float)z;
-            if (blend != 0.0 && (game.z & GAME_HAS_VALUES))
+            const double ret = v.returns ? v.returns[game.x + (u32)p] : 0.0;
+            if (v.returns && f64_bits(ret) != RETURN_ABSENT)  // a covered ply: the lambda-return in place of z or the blend
+                out = (float)ret;
+            else if (blend != 0.0 && (game.z & GAME_HAS_VALUES))
                 out = (float)((1.0 - blend) * (double)z + blend * ply.value);
             if (v.proofs) {  // a proven outcome stands above the game's result and the search's value
                 const int proof = v.proofs[game.x + (u32)p];
@@ -413,6 +426,8 @@ struct azh_samples {
     DeviceArray<u16> d_proof_moves;      // [cap_plies]: the move of the ply's last search, 0xFFFF before one
     DeviceArray<uint8_t> d_proof_depths; // [cap_plies]: the iteration that search completed
     std::vector<int16_t> h_proofs;       // [plies at the last call]: the mirror of d_proofs
+    // lambda-returns (azh_samples_value_returns): null until its first call, and again after azh_samples_clear_value_returns
+    DeviceArray<double> d_returns;       // [cap_plies]: G_p, RETURN_ABSENT where no pass has covered the ply
     // the host mirror: what a draw is validated against
     std::vector<uint32_t> h_games;  // [games][4]
     std::vector<uint8_t> h_flags;   // [plies]
@@ -430,7 +445,7 @@ struct azh_samples {
     View view() const
     {
         return View{d_games.d, d_plies.d, d_candidates.d, d_candidate_count.d, d_target_index.d, d_target_weight.d, d_cum.d,
-                    d_blockers.d, d_proofs.d};
+                    d_blockers.d, d_proofs.d, d_returns.d};
     }
 };
 
@@ -488,6 +503,7 @@ extern "C" void azh_samples_destroy(azh_samples *s)
     s->d_proofs.release();
     s->d_proof_moves.release();
     s->d_proof_depths.release();
+    s->d_returns.release();
     if (s->stream)
         (void)hipStreamDestroy(s->stream);
     delete s;
@@ -2086,6 +2102,181 @@ extern "C" int azh_samples_proofs(azh_samples *s, int n, const int32_t *plies, i
         proof_out[i] = got[i].proof;
         move_out[i] = (uint16_t)got[i].move;
         depth_done_out[i] = got[i].depth_done;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- lambda-returns as value targets (include/ataxxzero_hip.h)
+
+namespace {
+
+constexpr int RETURNS_WAVES = 4;  // games per workgroup, one wave each; no wave waits for another
+
+// The definition's step: a = 1.0 - lambda comes in, four IEEE double operations in all, none fused (-ffp-contract=off).
+__host__ __device__ inline double return_step(double b /* a * v_p */, double lambda, double next) { return b + lambda * next; }
+
+__host__ __device__ inline double result_for_mover(u32 result, u32 ply) { return result == 1u + (ply & 1u) ? 1.0 : -1.0; }
+
+__device__ __forceinline__ double read_lane_f64(double v, int src)
+{
+    const u64 bits = f64_bits(v);
+    const u64 got = (u64)(u32)read_lane((int)(u32)bits, src) | ((u64)(u32)read_lane((int)(u32)(bits >> 32), src) << 32);
+    double out;
+    memcpy(&out, &got, sizeof(out));
+    return out;
+}
+
+// One wave per game, from the game's end in chunks of 64 plies: lane l loads the value and the proof of ply lo + l (the
+// independent part, a * v_p, is done there), the proofs become two wave-uniform masks, and the chunk's steps run in ply order on
+// b read from lane j's register; lane j keeps G_j and stores it.  `next` is carried from chunk to chunk.
+__global__ __launch_bounds__(RETURNS_WAVES *WAVE) void k_samples_value_returns(View v, u32 first_game, int n_games, double lambda,
+                                                                              double *__restrict__ returns)
+{
+    const int lane = lane_id();
+    const int r = uni((int)blockIdx.x * RETURNS_WAVES + (int)(threadIdx.x >> 6));
+    if (r >= n_games)
+        return;  // the whole wave
+    const uint4 game = v.games[first_game + (u32)r];
+    if (!(game.z & GAME_HAS_VALUES))
+        return;  // (wave-uniform) its plies stay absent
+    const int T = (int)game.y;
+    const double a = 1.0 - lambda;
+    double next = result_for_mover(game.z & 0xFFu, (u32)(T - 1));  // z of the last ply's mover
+    for (int hi = T; hi > 0; hi -= WAVE) {
+        const int lo = hi > WAVE ? hi - WAVE : 0, n = hi - lo;
+        const u32 at = game.x + (u32)(lo + lane);
+        double value = 0.0;
+        int proof = 0;
+        if (lane < n) {
+            value = v.plies[at].value;
+            proof = v.proofs ? (int)v.proofs[at] : 0;
+        }
+        const double b = a * value;
+        const u64 won = __ballot(proof > 0), lost = __ballot(proof < 0);
+        double mine = 0.0;
+        for (int j = n - 1; j >= 0; j--) {  // (wave-uniform: every lane computes every step)
+            double G = return_step(read_lane_f64(b, j), lambda, next);
+            if ((won >> j) & 1ULL)
+                G = 1.0;
+            else if ((lost >> j) & 1ULL)
+                G = -1.0;
+            if (lane == j)
+                mine = G;
+            next = -G;
+        }
+        if (lane < n)
+            returns[at] = mine;
+    }
+}
+
+struct ReturnRow {
+    double value;
+    int present;
+};
+
+__global__ __launch_bounds__(256) void k_samples_read_returns(int n, const u32 *__restrict__ ply_at, const double *__restrict__ returns,
+                                                              ReturnRow *__restrict__ out)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n)
+        return;
+    const double g = returns[ply_at[i]];
+    const bool present = f64_bits(g) != RETURN_ABSENT;
+    out[i] = ReturnRow{present ? g : 0.0, present ? 1 : 0};
+}
+
+const char *lambda_refusal(double lambda)
+{
+    return lambda >= 0.0 && lambda <= 1.0 ? nullptr : "lambda must be a number in [0, 1]";
+}
+
+}  // namespace
+
+extern "C" int azh_samples_value_returns_host(const double *values, const int32_t *proofs, int64_t T, uint32_t result,
+                                              double lambda, double *out)
+{
+    if (T < 0 || (T > 0 && (!values || !out)))
+        return azh_fail(-1, "azh_samples_value_returns_host: null argument or a game of %lld plies", (long long)T);
+    if (const char *why = lambda_refusal(lambda))
+        return azh_fail(-2, "azh_samples_value_returns_host: %s", why);
+    const double a = 1.0 - lambda;
+    double next = 0.0;
+    for (int64_t p = T - 1; p >= 0; p--) {
+        if (p == T - 1)
+            next = result_for_mover(result, (u32)p);
+        const double b = a * values[p];
+        double G = return_step(b, lambda, next);
+        if (proofs && proofs[p] != 0)
+            G = proofs[p] > 0 ? 1.0 : -1.0;
+        out[p] = G;
+        next = -G;
+    }
+    return 0;
+}
+
+extern "C" int azh_samples_value_returns(azh_samples *s, int64_t first_game, int64_t n_games, double lambda)
+{
+    if (!s)
+        return azh_fail(-1, "azh_samples_value_returns: null store");
+    if (first_game < 0 || n_games < 1 || first_game + n_games > s->games)
+        return azh_fail(-1, "azh_samples_value_returns: games [%lld, %lld) of %lld", (long long)first_game,
+                        (long long)(first_game + n_games), (long long)s->games);
+    if (const char *why = lambda_refusal(lambda))
+        return azh_fail(-2, "azh_samples_value_returns: %s", why);
+    hipStream_t st = s->stream;
+    AZH_HIP(hipStreamSynchronize(st));
+    if (!s->d_returns.d) {  // every ply the store can hold: absent
+        DeviceArray<double> fresh;
+        if (int rc = fresh.alloc((size_t)s->cap_plies))
+            return rc;
+        hipError_t e = hipMemsetAsync(fresh.d, 0xFF, (size_t)s->cap_plies * sizeof(double), st);
+        e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+        if (e != hipSuccess) {
+            fresh.release();
+            return azh_fail(-100 - (int)e, "azh_samples_value_returns: %s", hipGetErrorString(e));
+        }
+        s->d_returns = fresh;
+    }
+    hipLaunchKernelGGL(k_samples_value_returns, dim3((unsigned)((n_games + RETURNS_WAVES - 1) / RETURNS_WAVES)),
+                       dim3(RETURNS_WAVES * WAVE), 0, st, s->view(), (u32)first_game, (int)n_games, lambda, s->d_returns.d);
+    AZH_HIP(hipGetLastError());
+    AZH_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int azh_samples_clear_value_returns(azh_samples *s)
+{
+    if (!s)
+        return azh_fail(-1, "azh_samples_clear_value_returns: null store");
+    AZH_HIP(hipDeviceSynchronize());
+    s->d_returns.release();
+    return 0;
+}
+
+extern "C" int azh_samples_read_value_returns(azh_samples *s, int n, const int32_t *plies, double *out, int32_t *present)
+{
+    if (!s || !plies || !out || !present || n < 1)
+        return azh_fail(-1, "azh_samples_read_value_returns: bad argument");
+    std::vector<u32> at;
+    if (int rc = ply_places(s, "azh_samples_read_value_returns", n, plies, at))
+        return rc;
+    const size_t N = (size_t)n, at_bytes = round_up(N * sizeof(u32));
+    std::vector<ReturnRow> got(N, ReturnRow{0.0, 0});
+    if (s->d_returns.d) {
+        if (int rc = reserve_scratch(s, at_bytes + round_up(N * sizeof(ReturnRow))))
+            return rc;
+        u32 *d_at = reinterpret_cast<u32 *>(s->d_scratch.d);
+        ReturnRow *d_out = reinterpret_cast<ReturnRow *>(s->d_scratch.d + at_bytes);
+        AZH_HIP(hipMemcpyAsync(d_at, at.data(), N * sizeof(u32), hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(k_samples_read_returns, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, n, d_at,
+                           s->d_returns.d, d_out);
+        AZH_HIP(hipGetLastError());
+        AZH_HIP(hipMemcpyAsync(got.data(), d_out, N * sizeof(ReturnRow), hipMemcpyDeviceToHost, s->stream));
+        AZH_HIP(hipStreamSynchronize(s->stream));
+    }
+    for (size_t i = 0; i < N; i++) {
+        out[i] = got[i].value;
+        present[i] = got[i].present;
     }
     return 0;
 }

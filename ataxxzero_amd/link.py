@@ -237,6 +237,10 @@ SIGNATURES = {
     "azh_samples_retarget_host": (ctypes.c_int, [_vp, _vp, _vp, _P(_i32), _P(ctypes.c_double)]),
     "azh_samples_prove": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _u64, ctypes.c_int, _vp]),
     "azh_samples_proofs": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "azh_samples_value_returns": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_double]),
+    "azh_samples_clear_value_returns": (ctypes.c_int, [_vp]),
+    "azh_samples_read_value_returns": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, _vp]),
+    "azh_samples_value_returns_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_uint32, ctypes.c_double, _vp]),
     # the reference's ABI, link.py:8-32
     "launch_threads": (None, [ctypes.c_char_p, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int]),
     "get_workload": (ctypes.c_int, []),
@@ -1360,6 +1364,20 @@ def retarget_host(report):
     return index[:n.value].copy(), weight[:n.value].copy(), float(value.value)
 
 
+def value_returns_host(values, proofs, result, lam):
+    """The lambda-returns G_p of one game (include/ataxxzero_hip.h, "lambda-returns as value targets") -> (T,) f64: values
+    (T,) the search's value of every ply, proofs (T,) its proof words or None, result the game's (0 .. 2), lam in [0, 1]
+    (azh_samples_value_returns_host; host arithmetic, no GPU needed)."""
+    values = np.ascontiguousarray(values, dtype=np.float64).ravel()
+    proofs = None if proofs is None else np.ascontiguousarray(proofs, dtype=np.int32).ravel()
+    if proofs is not None and len(proofs) != len(values):
+        raise ValueError("one proof word per ply")
+    out = np.zeros(max(len(values), 1), dtype=np.float64)
+    check(load().azh_samples_value_returns_host(_ptr(values) if len(values) else None, _ptr(proofs), len(values), int(result),
+                                                float(lam), _ptr(out)))
+    return out[:len(values)]
+
+
 def hip_runtimes():
     """The HIP runtime libraries mapped into this process (paths).  torch ships its own: imported BEFORE this package's
     library is loaded, both resolve to that one copy (same soname) and share streams and memory; loaded after it, the
@@ -1654,3 +1672,28 @@ class SampleStore:
         proof, move, done = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint16), np.zeros(n, dtype=np.int32)
         check(load().azh_samples_proofs(self.h, n, _ptr(plies), _ptr(proof), _ptr(move), _ptr(done)))
         return proof, move, done
+
+    # lambda-returns as value targets ("Lambda-returns as value targets")
+
+    def value_returns(self, first_game, n_games, lam):
+        """The TD(lambda) return G_p of every ply of the games [first_game, first_game + n_games) that carry values, from the
+        stored values and proofs as they are now, one wave per game; minibatches then write (float)G_p as the value target of
+        a covered ply.  Run it after retarget and prove: either leaves the returns stale; calling it again recomputes.  A
+        refused call changes nothing (azh_samples_value_returns).  Minibatch calls enqueued on torch's current stream are
+        waited for first."""
+        import torch
+        torch.cuda.current_stream().synchronize()
+        check(load().azh_samples_value_returns(self.h, int(first_game), int(n_games), float(lam)))
+
+    def clear_value_returns(self):
+        """Minibatches are again what they were before the first value_returns (azh_samples_clear_value_returns)."""
+        check(load().azh_samples_clear_value_returns(self.h))
+
+    def read_value_returns(self, plies):
+        """The plies (n, 2) of (game, ply) -> (G (n,) f64, 0.0 where absent; present (n,) bool), read back from the device
+        (azh_samples_read_value_returns)."""
+        plies = np.ascontiguousarray(plies, dtype=np.int32).reshape(-1, 2)
+        n = len(plies)
+        out, present = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int32)
+        check(load().azh_samples_read_value_returns(self.h, n, _ptr(plies), _ptr(out), _ptr(present)))
+        return out, present != 0

@@ -145,11 +145,59 @@ def _draw_ply(entry):
     return full[random.randrange(len(full))] if full else None
 
 
-def _value_target(entry, ply, mover, value_blend):
+def lambda_returns(values, result, lam, proofs=None):
+    """The TD(lambda) returns G_p of one game in Python floats (include/ataxxzero_hip.h, "lambda-returns as value targets"):
+    values the search's value of every ply for its mover, result the game's (1: x, 2: o, 0: none), lam in [0, 1], proofs one
+    word per ply (0: none) or None.  From the last ply down: next = z_p at the last ply and -G_{p+1} before it, then
+    a = 1.0 - lam, b = a * v_p, c = lam * next, G_p = b + c — four operations in this order — and +-1.0 where the ply is proven."""
+    out = [0.0] * len(values)
+    a = 1.0 - lam
+    nxt = 0.0
+    for p in range(len(values) - 1, -1, -1):
+        if p == len(values) - 1:
+            nxt = 1.0 if result == 1 + p % 2 else -1.0
+        b = a * float(values[p])
+        c = lam * nxt
+        g = b + c
+        if proofs is not None and proofs[p] != 0:
+            g = 1.0 if proofs[p] > 0 else -1.0
+        out[p] = g
+        nxt = -g
+    return out
+
+
+_RETURNS = {}             # id(entry) -> (entry, lambda, returns): bounded like _ARRAYS
+
+
+def _entry_returns(entry, lam):
+    """lambda_returns of an entry that carries "values", computed once per (entry, lambda)."""
+    row = _RETURNS.get(id(entry))
+    if row is None or row[0] is not entry or row[1] != lam:
+        if len(_RETURNS) >= _ARRAYS_MAX:
+            for key in list(_RETURNS)[:_ARRAYS_MAX // 10]:
+                del _RETURNS[key]
+        values = entry["values"][:len(entry["boards"])]                   # the plies the store keeps (link.entries_to_arrays)
+        row = _RETURNS[id(entry)] = (entry, lam, lambda_returns(values, entry["result"], lam))
+    return row[2]
+
+
+def value_lambda_refusal(value_lambda, value_blend):
+    """Why train.py --value-lambda L is refused, or None."""
+    if value_blend != 0.0:
+        return "--value-lambda and --value-blend are two value targets: give one of them"
+    if not 0.0 <= value_lambda <= 1.0:
+        return "--value-lambda must lie in [0, 1]"
+    return None
+
+
+def _value_target(entry, ply, mover, value_blend, value_lambda=None):
     """The value target of a sample: the game result z seen by the mover, +-1 — or, with value_blend = L != 0 and an entry that
     carries "values" (the search's own value at every ply, the mover's expectation in [-1, 1]), the blend
-    (1 - L) * z + L * values[ply] in Python floats."""
+    (1 - L) * z + L * values[ply] in Python floats — or, with value_lambda = L (not None) and such an entry, the ply's
+    lambda-return (lambda_returns); an entry without "values" keeps z."""
     z = 1 if entry["result"] == mover else -1
+    if value_lambda is not None and "values" in entry:
+        return _entry_returns(entry, value_lambda)[ply]
     if value_blend and "values" in entry:
         return (1 - value_blend) * z + value_blend * entry["values"][ply]
     return z
@@ -222,13 +270,14 @@ def _draw_sample(entries):
         return entry, ply, random.randrange(8)
 
 
-def get_sample_from_entries(entries, value_blend=0.0, aux=False):
+def get_sample_from_entries(entries, value_blend=0.0, aux=False, value_lambda=None):
     """One training sample (train.py:43-77).  The draws from `random` come in the reference's order — game, ply,
-    symmetry — so a games file yields the same minibatches as there.  aux: the sample's aux_targets behind the three."""
+    symmetry — so a games file yields the same minibatches as there.  aux: the sample's aux_targets behind the three.
+    value_lambda: _value_target."""
     entry, ply, symmetry_index = _draw_sample(entries)
     mover = 1 + ply % 2                             # x (1) moves on even plies
     features = apply_symmetry(symmetry_index, board_to_features(entry["boards"][ply], mover, entry.get("blockers")))
-    value = [_value_target(entry, ply, mover, value_blend)]
+    value = [_value_target(entry, ply, mover, value_blend, value_lambda)]
     sample = features, _policy_target(entry, ply, symmetry_index), value
     return sample + aux_targets(entry, ply, symmetry_index) if aux else sample
 
@@ -246,12 +295,12 @@ def load_entries(paths):
     return entries
 
 
-def make_minibatch_reference(entries, size, value_blend=0.0, aux=False):
+def make_minibatch_reference(entries, size, value_blend=0.0, aux=False, value_lambda=None):
     """`size` samples drawn one by one with get_sample_from_entries (train.py:123-130).  aux: seven arrays, the samples'
     aux_targets (ownership, score, reply, aux_weight) behind the three; `random` is consumed as without it."""
     columns = [[] for _ in range(7 if aux else 3)]
     for _ in range(size):
-        for column, part in zip(columns, get_sample_from_entries(entries, value_blend, aux)):
+        for column, part in zip(columns, get_sample_from_entries(entries, value_blend, aux, value_lambda)):
             column.append(part)
     return tuple(np.asarray(column, dtype=np.float32) for column in columns)
 
@@ -329,10 +378,11 @@ def _entry_arrays(entry):
     return cache
 
 
-def make_minibatch(entries, size, value_blend=0.0, aux=False):
+def make_minibatch(entries, size, value_blend=0.0, aux=False, value_lambda=None):
     """The same `size` samples as make_minibatch_reference — same draws from `random` in the same order, bit-identical
     arrays (tests/test_training.py) — assembled with array operations instead of per-sample Python: the sample pipeline,
-    not the GPU step, bounded train.py's rate.  value_blend: _value_target.  aux: seven arrays, as make_minibatch_reference."""
+    not the GPU step, bounded train.py's rate.  value_blend, value_lambda: _value_target.  aux: seven arrays, as
+    make_minibatch_reference."""
     global _TABLES
     if _TABLES is None:
         _TABLES = _symmetry_tables()
@@ -368,7 +418,7 @@ def make_minibatch(entries, size, value_blend=0.0, aux=False):
         cells.append(c[ply])
         movers.append(1 + ply % 2)
         syms.append(sym)
-        targets.append(_value_target(entry, ply, 1 + ply % 2, value_blend))
+        targets.append(_value_target(entry, ply, 1 + ply % 2, value_blend, value_lambda))
     cells = np.stack(cells)
     movers = np.asarray(movers, dtype=np.int8)[:, None]
     shown = np.take_along_axis(cells, cell_src[np.asarray(syms)], axis=1)        # [b][x * 7 + y]
@@ -711,6 +761,24 @@ def _apply_proofs(store, depth, nodes, policy, n_test, log):
     return s
 
 
+# ---------------------------------------------------------------- lambda-returns as value targets
+
+def _log_value_lambda(lam, games, log):
+    """games: (plies, carries values?) per training game."""
+    valued = [n for n, has in games if has]
+    log("Value targets: lambda-returns (L = %g) over %i plies of %i games; %i games without values keep z."
+        % (lam, sum(valued), len(valued), len(games) - len(valued)))
+
+
+def _apply_value_lambda(store, lam, n_test, log):
+    """One returns pass over the training games [n_test, games), after reanalysis and the proof pass: it reads the values and the
+    proofs they left (SampleStore.value_returns)."""
+    from . import link
+    games, _ = store.mirror()
+    store.value_returns(n_test, len(games) - n_test, lam)
+    _log_value_lambda(lam, [(int(n), bool(w & link.SAMPLES_GAME_HAS_VALUES)) for _, n, w, _ in games[n_test:].tolist()], log)
+
+
 def aux_random_init(filters, seed=1):
     """Fresh weights of the auxiliary heads in torch's layouts, with model.random_init's distributions (truncated normal,
     stddev 0.2 * sqrt(2 / fan_in); bias 0.01), from numpy's PCG64(seed) alone."""
@@ -911,7 +979,7 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
           reference_bn_affine=False, device=None, log=print, value_blend=0.0, device_samples=False, device_draws=False,
           surprise_weight=0.0, surprise_dtype="bf16", aux_ownership=0.0, aux_score=0.0, aux_reply=0.0,
           reanalyse_fraction=0.0, reanalyse_visits=0, reanalyse_slots=4096, reanalyse_dtype="bf16", prove_depth=0,
-          prove_nodes=0, prove_policy=False):
+          prove_nodes=0, prove_policy=False, value_lambda=None):
     """device_samples: the entries are put into a link.SampleStore once and every minibatch is written by its kernel into
     tensors allocated once (make_minibatch_device) — the same minibatches as without it, no per-step host-to-device copy of
     the batch; device_draws (implies device_samples): the kernel also draws the samples.  Both need a GPU.
@@ -926,7 +994,18 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
     alpha-beta search of depth D (prove_nodes nodes at most per ply, 0: no limit, D <= 3) runs on the training games' eligible
     plies; a ply it proves won or lost trains the value head on that outcome instead of the game's result, and under
     prove_policy a ply proven won takes the winning move as its policy target (SampleStore.prove); the validation games stay
-    as recorded.  D = 0: nothing is called, every byte of the run is what it was."""
+    as recorded.  D = 0: nothing is called, every byte of the run is what it was.
+    value_lambda L in [0, 1] (not None; refused together with a non-zero value_blend): a training game that carries "values"
+    trains the value head on its plies' TD(lambda) returns over the search values that follow, closed with the result
+    (lambda_returns).  With a store the returns are computed on the device after reanalysis and the proof pass — they see the
+    refreshed values and the proofs — and before the surprise pass (SampleStore.value_returns); without one each entry's are
+    computed once on the host, the same bits.  The validation games stay as recorded.  None: nothing is called, every byte of
+    the run is what it was."""
+    if value_lambda is not None:
+        why = value_lambda_refusal(value_lambda, value_blend)
+        if why:
+            raise ValueError(why)
+        value_lambda = float(value_lambda)
     if prove_depth != 0 or prove_nodes != 0 or prove_policy:
         why = prove_refusal(prove_depth, prove_nodes) if prove_depth != 0 else "--prove-nodes and --prove-policy need --prove-depth"
         if why:
@@ -1002,6 +1081,8 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
             _apply_reanalysis(store, old_path, reanalyse_fraction, reanalyse_visits, reanalyse_slots, reanalyse_dtype, n_test, log)
         if prove_depth > 0:
             _apply_proofs(store, prove_depth, prove_nodes, prove_policy, n_test, log)
+        if value_lambda is not None:
+            _apply_value_lambda(store, value_lambda, n_test, log)
         if surprise_weight > 0.0:
             _apply_surprise(store, old_path, surprise_weight, surprise_dtype, n_test, log)
 
@@ -1014,8 +1095,11 @@ def train(games_paths, old_path, new_path, steps=1000, minibatch_size=512, learn
             if failed:
                 raise RuntimeError("%d samples found no drawable ply in 64 attempts" % failed)
     else:
+        if value_lambda is not None:
+            _log_value_lambda(value_lambda, [(len(e["boards"]), "values" in e) for e in train_entries], log)
+
         def next_batch(step):
-            return to_dev(make_minibatch(train_entries, minibatch_size, value_blend, aux))
+            return to_dev(make_minibatch(train_entries, minibatch_size, value_blend, aux, value_lambda))
 
         def check_store():
             pass

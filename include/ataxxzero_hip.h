@@ -1226,6 +1226,57 @@ int azh_samples_prove(azh_samples *s, int64_t first_game, int64_t n_games, int d
 int azh_samples_proofs(azh_samples *s, int n, const int32_t *plies /* [n][2] (game, ply) */, int32_t *proof_out,
                        uint16_t *move_out, int32_t *depth_done_out);
 
+/* ------------------------------------------------------------------ lambda-returns as value targets
+ * (an extension of the store; with azh_samples_value_returns never called, or after azh_samples_clear_value_returns, every call,
+ * launch and byte above is what it was.)  The value target of a stored ply becomes the TD(lambda) return over the search values
+ * of the plies that follow it, closed with the game's result (KataGo's short-term value targets; MuZero trains on n-step
+ * returns).  training.train drives it under train.py --value-lambda; DESIGN.md section 4, "Lambda-returns as value targets".
+ *
+ * The definition, stated once; azh_samples_value_returns (device), azh_samples_value_returns_host (host arithmetic) and
+ * tests/lambda_reference.py (Python floats) all follow it.  Take a stored game of T plies that carries values (game word 2 has
+ * bit 9, "values") and lambda in [0, 1].  The mover of ply p is x for even p.  z_p = +1 when (game word 2 & 0xFF) == 1 + (p & 1),
+ * else -1 — the integer the minibatch kernels compute, also for a game without a result.  v_p is the ply's stored value.  For
+ * p = T - 1 down to 0:
+ *     next = z_p          if p == T - 1
+ *          = -G_{p+1}     otherwise
+ *     G_p  = (1.0 - lambda) * v_p + lambda * next
+ * in four IEEE double operations in exactly this order: a = 1.0 - lambda, b = a * v_p, c = lambda * next, G_p = b + c, none of them
+ * fused.  Where the store has proofs and proof(p) != 0, G_p is exactly +1.0 or -1.0 by the proof's sign instead, and the
+ * recursion goes on from that value: a proven ply corrects the targets of the plies before it.
+ * Two identities follow from the arithmetic: lambda = 1 gives G_p = z_p bit for bit (for a game with a result: z alternates
+ * with the mover; without one every z_p is -1 and G alternates from the last ply's), and lambda = 0 gives G_p = v_p bit for
+ * bit (for v_p other than -0.0), the target of value_blend = 1.0.
+ *
+ * azh_samples_value_returns fills G_p for every ply of the games [first_game, first_game + n_games) that carry values, one wave
+ * per game: the wave walks its game from the end in chunks of 64 plies, each lane loads one ply's value and proof, the chunk's
+ * steps run in order on values read from the lanes' registers, and each lane stores its own ply's return.  Storage: one
+ * double per ply the store can hold, allocated by the first call, every entry ABSENT until a call covers it (a game without
+ * values is never covered).  A second call replaces the entries of its games and leaves every other entry as it was.
+ * Minibatches.  While the array exists, the four gather / draw-gather kernels write (float)G_p as the value target of a sample
+ * whose ply is covered, in place of z or the value_blend mix; a ply that is absent keeps its target.  Proofs stand above both,
+ * as before; they already went into G_p, so a ply proven before the pass trains on +-1 either way.  Features, policy, the
+ * auxiliary outputs and the draws do not change.
+ * Order.  The pass reads the stored values and the proofs as they are when it runs.  azh_samples_retarget or azh_samples_prove
+ * after it leave the returns stale: run the pass after them (training.train does: reanalysis, proofs, returns, surprise).
+ * Calling it again recomputes.
+ * azh_samples_clear_value_returns frees the array: minibatches are again what they were without it.
+ * azh_samples_read_value_returns reads entries back from the device like azh_samples_proofs: out [n] (0.0 where absent) and
+ * present [n] (1 covered, 0 absent; all 0 while there is no array).
+ * Refusals, each changing nothing: -1 a null argument or a game range outside the store (n_games < 1 among them), -2 a lambda
+ * that is not a number or lies outside [0, 1].
+ * Streams as azh_samples_prove: the calls wait for the store's stream, run on it and return after completion; they must not
+ * run while a minibatch call is in flight on another stream.
+ *
+ * azh_samples_value_returns_host: the definition itself for one game, host arithmetic only, usable without a device.  values
+ * [T]; proofs [T] (azh_samples_proofs' proof words) or NULL; result the game's (0 .. 2); out [T].  -1 for a null argument or
+ * T < 0, -2 for lambda as above. */
+int azh_samples_value_returns(azh_samples *s, int64_t first_game, int64_t n_games, double lambda);
+int azh_samples_clear_value_returns(azh_samples *s);
+int azh_samples_read_value_returns(azh_samples *s, int n, const int32_t *plies /* [n][2] (game, ply) */, double *out /* [n] */,
+                                   int32_t *present /* [n] */);
+int azh_samples_value_returns_host(const double *values /* [T] */, const int32_t *proofs /* [T] or NULL */, int64_t T,
+                                   uint32_t result, double lambda, double *out /* [T] */);
+
 /* ------------------------------------------------------------------ reference ABI
  * The four symbols link.py:6-32 binds (cpp/self_play_client.cpp:683-749), with
  * the worker threads replaced by GPU game slots: `thread_count` concurrent

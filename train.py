@@ -27,6 +27,11 @@ changes.
 won or lost trains the value head on that outcome instead of the game's result, and with --prove-policy a ply proven won takes the
 winning move as its policy target (what tablebase rescoring does for lc0; an extension; implies --device-samples, needs no
 network).  D = 0 (the default): nothing changes.
+--value-lambda L trains the value head of entries that carry "values" on TD(lambda) returns: an exponentially discounted average
+of the search values of the plies that follow, closed with the game's result (KataGo's short-term value targets; an extension).
+It works on every sample path; with a device store the pass runs after reanalysis and the proof pass, so refreshed values and
+proven plies correct the targets of the plies before them.  Not together with --value-blend.  Absent (the default): nothing
+changes.
 """
 from ataxxzero_amd import training
 from ataxxzero_amd.cli import flag, parse, switch
@@ -41,6 +46,10 @@ OPTIONS = [
     flag("--value-blend", "weight L of the search's recorded value in the value target, (1 - L) * z + L * values[ply], for "
                           "entries that carry \"values\" (extension; 0: the game result alone, as the reference)", type=float,
          default=0.0, metavar="L"),
+    flag("--value-lambda", "L in [0, 1]: entries that carry \"values\" train the value head on their plies' TD(lambda) returns, "
+                           "G_p = (1 - L) * values[p] + L * -G_{p+1}, closed with the game result at the last ply; with a device "
+                           "store, plies proven by --prove-depth enter as +-1 (extension; not together with --value-blend; "
+                           "absent: off)", type=float, default=None, metavar="L"),
     switch("--reference-bn-affine", "train batch-norm gamma/beta as the reference does and drop them on save "
                                     "(extension; see training.py)"),
     switch("--device-samples", "keep the games in device memory and build every minibatch with a HIP kernel: the same "
@@ -111,6 +120,14 @@ if __name__ == "__main__":
         raise SystemExit("train.py: --prove-nodes and --prove-policy need --prove-depth")
     else:                                   # off: as above
         del args.prove_depth, args.prove_nodes, args.prove_policy
+    returns = {}
+    if args.value_lambda is not None:
+        why = training.value_lambda_refusal(args.value_lambda, args.value_blend)
+        if why:
+            raise SystemExit("train.py: " + why)
+        returns = {"value_lambda": args.value_lambda}
+    else:                                   # off: as above
+        del args.value_lambda
     aux = {"aux_ownership": args.aux_ownership, "aux_score": args.aux_score, "aux_reply": args.aux_reply}
     if min(aux.values()) < 0.0:
         raise SystemExit("train.py: --aux-ownership, --aux-score and --aux-reply take weights >= 0")
@@ -121,4 +138,4 @@ if __name__ == "__main__":
     training.train(args.games, args.old_path, args.new_path, steps=args.steps, minibatch_size=args.minibatch_size,
                    learning_rate=args.learning_rate, reference_bn_affine=args.reference_bn_affine, value_blend=args.value_blend,
                    device_samples=args.device_samples or args.device_draws, device_draws=args.device_draws, **surprise, **aux,
-                   **reanalysis, **proofs)
+                   **reanalysis, **proofs, **returns)
